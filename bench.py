@@ -6,7 +6,11 @@ steps: the reads are synthesised and a few builds prime the library's device-mem
 k-mer extraction -> k-mer table -> sorted distinct edges -> node numbering, endpoints, labels
 (everything `Build::create` + the PtGraph::create post-pass do in the reference), result left in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c5] [--reads R]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c5] [--reads R] [--dump-outputs DIR]
+
+--dump-outputs DIR (one GPU): after the timed steps, the graph the last of them built -- the arrays a caller of the device
+path receives -- is written as DIR/<name>.npy (float64 / float32, at most 64 MB: a fixed, seeded sample of the rows; see
+dump_outputs).  The reads are synthesised from fixed seeds, so the same arguments give the same inputs on every run.
 
 N>1: one rank per GPU.  Started by a launcher (torch.distributed.run: WORLD_SIZE set) or, without one, by this very
 script (katome_amd/launch.py: the parent starts the N ranks before anything touches the GPU and relays rank 0's line).
@@ -24,7 +28,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s
+HBM_PEAK_GBS = 8000.0          # MI355X: HBM3E peak 8.0 TB/s
 # what the card reaches for the partition pass's MEMORY PATTERN with the ranking work taken out (4096-record tiles written as 128-byte
 # stretches into 256 streams; tools/microbench_scatter.hip, profiles/r04_scatter_ceiling.txt) and for a plain copy of the same bytes
 SCATTER_PATTERN_CEILING_GBS = 4870.0
@@ -100,6 +104,66 @@ def lc_phases(reset):
     return res
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+DUMP_SEED = 0x6B61746F6D65
+
+
+def sample_rows(n, cap, seed=DUMP_SEED):
+    """the rows of an array of n rows that a dump keeps: all of them when they fit under `cap`, else at most `cap` distinct
+    rows drawn from a fixed seed, ascending -- the same rows for the same n on every run"""
+    import numpy as np
+    if n <= cap:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.default_rng(seed).integers(0, n, size=cap, dtype=np.int64))
+
+
+def key_words_as_float(words):
+    """[n, nw] int64 (u64 key words) -> [n, 2 nw] float64: every word as its high then its low 32 bits, each exact in a double"""
+    import numpy as np
+    u = np.ascontiguousarray(words).view(np.uint64).reshape(len(words), -1)
+    return np.stack([u >> np.uint64(32), u & np.uint64(0xFFFFFFFF)], axis=-1).reshape(len(u), -1).astype(np.float64)
+
+
+def dump_outputs(g, out_dir, limit=DUMP_LIMIT_BYTES):
+    """write the graph `g` (device.DeviceGraph: what the timed path returns) as out_dir/<name>.npy, float64 for integers that a
+    float32 would round, float32 for label bytes; at most `limit` bytes in all.  Rows are sampled with sample_rows (edges and
+    nodes separately; edge_index / node_index name them); graph_totals = [n_edges, n_nodes, sum and max of all edge weights]
+    covers every edge.  Returns {name: shape}."""
+    import numpy as np
+    import torch
+    edge_cols = {"edge_key": 16 * g.key_words, "edge_weight": 8, "edge_src": 8, "edge_dst": 8, "edge_label": 4 * g.label_stride}
+    if g.edge_age is not None:
+        edge_cols["edge_age"] = 8
+    header = 128 * (len(edge_cols) + 4)                          # (an .npy header per file)
+    edge_rows = sample_rows(g.n_edges, (limit * 3 // 4) // (8 + sum(edge_cols.values())))
+    node_rows = sample_rows(g.n_nodes, (limit // 4 - header - 64) // (8 + 16 * g.key_words))
+
+    def rows(t, idx):
+        return t.index_select(0, torch.from_numpy(idx).to(t.device)).cpu().numpy()
+
+    w_sum = w_max = 0
+    for i in range(0, g.n_edges, 1 << 26):                  # (u32 weights widened a slice at a time: no copy of the whole array)
+        w = g.edge_weight[i:i + (1 << 26)].to(torch.int64) & 0xFFFFFFFF
+        w_sum, w_max = w_sum + int(w.sum()), max(w_max, int(w.max()))
+    out = {"graph_totals": np.array([g.n_edges, g.n_nodes, w_sum, w_max], dtype=np.float64),
+           "edge_index": edge_rows.astype(np.float64),
+           "edge_key": key_words_as_float(rows(g.edge_key, edge_rows)),
+           "edge_weight": rows(g.edge_weight, edge_rows).view(np.uint32).astype(np.float64),
+           "edge_src": rows(g.edge_src, edge_rows).view(np.uint64).astype(np.float64),
+           "edge_dst": rows(g.edge_dst, edge_rows).view(np.uint64).astype(np.float64),
+           "edge_label": rows(g.edge_label, edge_rows).astype(np.float32),
+           "node_index": node_rows.astype(np.float64),
+           "node_key": key_words_as_float(rows(g.node_key, node_rows))}
+    if g.edge_age is not None:
+        out["edge_age"] = rows(g.edge_age, edge_rows).astype(np.float64)
+    total = sum(a.nbytes + 128 for a in out.values())
+    assert total <= limit, "dump of %d bytes over the %d-byte limit" % (total, limit)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: a.shape for name, a in out.items()}
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -128,6 +192,8 @@ def parse_args():
                     help="SURVEY 8(d) region (ii): host packed reads -> host arrays through katome_build_packed, on this many reads")
     ap.add_argument("--next-stages-reads", type=int, default=20_000_000,
                     help="also time first-seen-order build + remove_dead_paths + shrink on this many reads (0 = skip; N = 1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the graph the last timed step built to DIR/<name>.npy (one GPU; see dump_outputs)")
     return ap.parse_args()
 
 
@@ -152,9 +218,11 @@ class PhaseTimer:
         return out
 
 
-def one_build_single(wl, packed, skip, recbuf, batch_reads, timer, first_seen=False, min_weight=0, table_factor=2.2, prune=False):
+def one_build_single(wl, packed, skip, recbuf, batch_reads, timer, first_seen=False, min_weight=0, table_factor=2.2, prune=False,
+                     keep=None):
     """one step on one GPU; returns (n_edges, n_nodes).  table_factor 0 = no hint: the tables start small and grow by
-    re-hashing, as for a caller that knows nothing about its input (settings.table_slots_hint = 0)"""
+    re-hashing, as for a caller that knows nothing about its input (settings.table_slots_hint = 0).  keep: a list the
+    finished graph is appended to; the builder's memory then lives until the caller lets go of the graph"""
     from katome_amd import device as kd
     hint = int(wl.expected_distinct_canonical() * table_factor)
     b = kd.Builder(wl.k, wl.reverse_complement, device=packed.device.index, table_slots_hint=hint,
@@ -183,6 +251,8 @@ def one_build_single(wl, packed, skip, recbuf, batch_reads, timer, first_seen=Fa
         if prune:                                   # BASELINE config 5's pruner pass (pruner.rs:36-82)
             dg, _ = b.remove_dead_paths()
             n_edges, n_nodes = dg.n_edges, dg.n_nodes
+        if keep is not None:
+            keep.append(dg)
         timer.add(b.profile_read())
         timer.counts = b.counts()
         return n_edges, n_nodes
@@ -394,6 +464,10 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.gpus > 1 or args.force_dist):
+        raise SystemExit("--dump-outputs needs --gpus 1 without --force-dist: a sharded build leaves each rank only its share")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return run_as_parent(args)
     # libraries (RCCL) print banners on fd 1; the contract is ONE JSON line on stdout, so the real stdout is
@@ -451,9 +525,9 @@ def main():
         recbuf = torch.empty(max(min(batch_reads, wl.reads) * per_read_buf * kd.record_words(wl.k), 1), dtype=torch.int64,
                              device=packed.device)
 
-        def step():
+        def step(keep=None):
             return one_build_single(wl, packed, skip_arg, recbuf, batch_reads, timer, args.first_seen_order, args.min_weight,
-                                    args.table_factor, args.prune)
+                                    args.table_factor, args.prune, keep)
     else:
         from katome_amd import shard as ks
         comm = ks.Comm.rccl(rank, world, local_rank)
@@ -462,7 +536,7 @@ def main():
                            table_factor=args.table_factor, prune=args.prune)
         accepted = job.accepted_total
 
-        def step():
+        def step(keep=None):                # (--dump-outputs is refused on this route: `keep` is always None)
             return job.build()
 
     # Set-up, like synthesising the reads: builds until the library's device-memory cache holds the working set.  The first
@@ -490,15 +564,19 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     lc_phases(True)
+    last = [] if args.dump_outputs else None          # (the last step's graph, kept for the dump)
     t0 = time.perf_counter()
     n_edges = n_nodes = 0
-    for _ in range(args.steps):
-        n_edges, n_nodes = step()
+    for i in range(args.steps):
+        n_edges, n_nodes = step(last if i == args.steps - 1 else None)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
     phases = timer.collect()
+    if last:
+        shapes = dump_outputs(last.pop(), args.dump_outputs)   # (the graph, and with it its builder, is freed once written)
+        print("[bench] outputs of the last timed step: %s -> %s" % (shapes, args.dump_outputs), file=sys.stderr, flush=True)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

@@ -97,3 +97,35 @@ def test_bench_gpus_2_on_a_one_gpu_box_fails_loudly():
     r = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--reads", "100000", "--no-cpu-baseline"])
     assert r.returncode != 0 and r.stdout.strip() == b""
     assert b"only 1 GPU(s) visible" in r.stderr
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_steps_graph_on_every_run(tmp_path):
+    """--dump-outputs: two runs with the same arguments write the same files; in the reference's numbering the dumped rows are
+    the oracle's edges index for index and the totals are the oracle's over every edge"""
+    import numpy as np
+    from katome_amd.workloads import WORKLOADS
+    from oracle import oracle as o
+    reads = 20000
+    for d in ("a", "b"):
+        r = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--reads", str(reads), "--no-cpu-baseline", "--no-extras",
+                        "--first-seen-order", "--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
+        line = json.loads(r.stdout.decode().strip().splitlines()[-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0
+    names = sorted(os.listdir(str(tmp_path / "a")))
+    assert names == sorted(os.listdir(str(tmp_path / "b"))) and "edge_key.npy" in names
+    for n in names:
+        assert open(str(tmp_path / "a" / n), "rb").read() == open(str(tmp_path / "b" / n), "rb").read(), n
+    d = {n[:-4]: np.load(str(tmp_path / "a" / n)) for n in names}
+    wl = WORKLOADS["c3"].scaled(reads)
+    ref = o.build_ascii(o.synth_reads(0, wl.reads, wl.read_len, wl.genome_len, wl.err_rate, wl.n_inject_percent), wl.k,
+                        wl.reverse_complement)
+    w = ref.edge_weight.astype(np.uint64)
+    assert d["graph_totals"].tolist() == [ref.n_edges, ref.n_nodes, float(w.sum()), float(w.max())]
+    rows = d["edge_index"].astype(np.int64)
+    assert len(rows) == ref.n_edges                                          # (a graph this small is written whole)
+    assert np.array_equal(d["edge_src"], ref.edge_src[rows].astype(np.float64))
+    assert np.array_equal(d["edge_dst"], ref.edge_dst[rows].astype(np.float64))
+    assert np.array_equal(d["edge_weight"], w[rows].astype(np.float64))
+    assert np.array_equal(d["edge_label"], ref.edge_label[rows].astype(np.float32))
