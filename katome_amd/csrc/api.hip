@@ -650,7 +650,7 @@ static int kmer_records_in_parts(katome_builder* b, const uint64_t* lk, const ui
 // the tile records are gone.  KATOME_E_UNSUPPORTED: a level could not be counted this way (or there is nothing to count) -- the
 // tile records, or the distinct big tiles with their counts, are in the tile table instead and the caller goes on in tables.
 int tile_recs_to_kmer_records(katome_builder* b, DevBuf& keys, DevBuf& weights, uint64_t* n_records, uint64_t extra_room, hipStream_t stream,
-                              DevBuf* first_counts) {
+                              DevBuf* first_counts, bool rep) {
     *n_records = 0;
     const uint32_t k = b->s.k, span = b->span, tile_bases = k + span - 1, nwt = (uint32_t)key_words_for_k(tile_bases);
     b->span2 = mid_span(span);
@@ -711,6 +711,7 @@ int tile_recs_to_kmer_records(katome_builder* b, DevBuf& keys, DevBuf& weights, 
         // in parts first (kmer_records_in_parts): their lists stand in for the level's records
         if (first_counts) first_counts->release();
         const int prc = kmer_records_in_parts(b, lk, lw, n_last, last_bases, last_span, keys, weights, n_records, extra_room, stream);
+        if (prc == KATOME_OK && rep && b->rc) return table_orient_records(keys.as<u64>(), *n_records, k, true, stream);
         if (prc != KATOME_E_UNSUPPORTED) return prc;
         keys.release(); weights.release(); *n_records = 0;
         // the k-mer level would not fit by sorting: the distinct tiles of the last level go into their table with their counts (the mid
@@ -727,7 +728,16 @@ int tile_recs_to_kmer_records(katome_builder* b, DevBuf& keys, DevBuf& weights, 
     }
     PhaseScope ps(b->prof, PH_EXPAND_TILES, stream);
     // (first_counts: for a caller that orders exactly these records by the whole k-mer's hash next -- table_list_to_records)
-    return table_list_to_records(lk, lw, n_last, last_bases, k, last_span, 1, b->rc, keys, weights, n_records, stream, extra_room, first_counts);
+    return table_list_to_records(lk, lw, n_last, last_bases, k, last_span, 1, b->rc, keys, weights, n_records, stream, extra_room, first_counts, rep);
+}
+
+// The k-mer level counted in order (table.hip, lds_count_ordered_kernel): half of the edges leave the count sorted, the edge sort takes
+// only the reverse complements and one merge (half_sort_finish).  Where lds_count_packed_kernel would run: one-word k-mers of odd k
+// (k >= 9: 16 key bits name the group) or one strand, default numbering, no owner split.  KATOME_EDGE_HALF_SORT=0: the full edge sort
+static bool half_sort_route(const katome_builder* b) {
+    static const bool on = !getenv("KATOME_EDGE_HALF_SORT") || atoi(getenv("KATOME_EDGE_HALF_SORT")) != 0;
+    const uint32_t k = b->s.k;
+    return on && b->nw == 1 && !b->first_seen && k >= 9 && ((k & 1) || !b->rc);
 }
 
 // keeps a batch's left-over windows aside (see builder.h); *kept = false: they have to go into the table
@@ -1003,7 +1013,9 @@ int katome_dev_edges(katome_builder* b, uint64_t** d_edge_key, uint32_t** d_edge
             uint64_t n_rec = 0, n_rest = 0, distinct = 0;
             KCHECK(rest_valid(b, &n_rest, stream));
             DevBuf first_counts(stream);
-            int rc = tile_recs_to_kmer_records(b, rk, rw, &n_rec, n_rest, stream, &first_counts);
+            const bool half = half_sort_route(b);
+            HalfSort hs;
+            int rc = tile_recs_to_kmer_records(b, rk, rw, &n_rec, n_rest, stream, &first_counts, half);
             if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
             if (rc == KATOME_OK) {         // (otherwise the tiles are in their table now, and the blocks below take it from there)
                 {
@@ -1011,19 +1023,23 @@ int katome_dev_edges(katome_builder* b, uint64_t** d_edge_key, uint32_t** d_edge
                     if (n_rest) {
                         KCHECK_HIP(hipMemcpyAsync(rk.as<u64>() + n_rec * b->nw, b->rest_k.p, n_rest * 8 * b->nw, hipMemcpyDeviceToDevice, stream));
                         KCHECK(dev_fill_u32(rw.as<u32>() + n_rec, n_rest, 1u, stream));
+                        if (half && b->rc) KCHECK(table_orient_records(rk.as<u64>() + n_rec, n_rest, k, true, stream));
                         n_rec += n_rest;
                     }
                     rest_reset(b);
-                    rc = sorted_fail("last") ? KATOME_E_UNSUPPORTED
+                    const bool fail = sorted_fail("last");
+                    if (fail && half && b->rc) KCHECK(table_orient_records(rk.as<u64>(), n_rec, k, false, stream));     // (the table takes canonical k-mers)
+                    rc = fail ? KATOME_E_UNSUPPORTED
                         : records_to_edges_sorted(rk, rw, n_rec, k, b->rc, b->prune_weight, b->edge_key, b->edge_weight, &b->n_edges, &distinct, stream, nullptr,
-                                                  n_rest ? nullptr : first_counts.as<u32>());
+                                                  n_rest ? nullptr : first_counts.as<u32>(), half ? &hs : nullptr);
                     if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
                 }
                 if (rc == KATOME_OK) {
                     b->stat_kmers = distinct; b->stat_kmer_slots = 0;
                     rk.release(); rw.release();
                     PhaseScope ps(b->prof, PH_SORT_EDGES, stream);
-                    KCHECK(dev_sort_bufs(b->edge_key, &b->edge_weight, b->n_edges, b->nw, 2 * k, stream, true));
+                    if (hs.taken) KCHECK(half_sort_finish(hs, b->edge_key, b->edge_weight, stream));
+                    else KCHECK(dev_sort_bufs(b->edge_key, &b->edge_weight, b->n_edges, b->nw, 2 * k, stream, true));
                     counted = true;
                 } else {
                     // the k-mers cannot be counted this way (a hash group beyond the LDS route): their records, counts and all, go

@@ -85,7 +85,7 @@ int keep_tile_recs(katome_builder* b, const uint64_t* d_records, uint64_t n, uin
 int tile_recs_valid(katome_builder* b, uint64_t* n, hipStream_t stream);      // how many of them there are
 // ... counted level by level by sorting, down to the (k-mer, count) records of the last tile level (api.hip)
 int tile_recs_to_kmer_records(katome_builder* b, DevBuf& keys, DevBuf& weights, uint64_t* n_records, uint64_t extra_room, hipStream_t stream,
-                              DevBuf* first_counts = nullptr);
+                              DevBuf* first_counts = nullptr, bool rep = false);      // (rep: the k-mer records in their representative orientation)
 int sorted_count_mode();            // KATOME_SORTED_COUNT
 int sorted_tiles_mode();            // KATOME_SORTED_TILES
 bool tile_recs_shape(uint32_t nwt, uint32_t nw, bool first_seen);   // tile / k-mer word counts whose levels are all counted by sorting

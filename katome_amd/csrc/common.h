@@ -84,7 +84,7 @@ enum Phase { PH_EXTRACT, PH_REGION_ORDER, PH_INSERT, PH_EMIT_EDGES, PH_SORT_EDGE
              PH_INSERT_TILES, PH_EXPAND_TILES, PH_EXPAND_MID, PH_FIRST_SEEN, PH_DEAD_PATHS, PH_SHRINK,
              K_SORT_SCATTER, K_SORT_HIST, K_RUN_SORT, K_HASH_SCATTER, K_HASH_HIST, K_OWNER_SCATTER, K_OWNER_HIST, K_PASS_OFFSETS,
              K_RECORDS, K_GROUP_INDEX, K_LDS_COUNT, K_SRC_IDS, K_DST_MERGE, K_EXPAND, K_SORT_SCATTER_KEYS, K_RUN_SORT_KEYS,
-             K_TILE_HASH_SCATTER, K_TILE_HASH_HIST, K_TILE_RECORDS, K_TILE_GROUP_INDEX, K_TILE_LDS_COUNT, PH_COUNT };
+             K_TILE_HASH_SCATTER, K_TILE_HASH_HIST, K_TILE_RECORDS, K_TILE_GROUP_INDEX, K_TILE_LDS_COUNT, K_HALF_MERGE, PH_COUNT };
 static const char* const PHASE_NAMES[PH_COUNT] = {
     "extract", "region_order", "insert", "emit_edges", "sort_edges", "node_set", "rank", "labels", "insert_tiles", "expand_tiles",
     "expand_mid_tiles", "first_seen_order", "remove_dead_paths", "shrink",
@@ -96,7 +96,7 @@ static const char* const PHASE_NAMES[PH_COUNT] = {
     "k:radix_scatter_kernel<RadixDigit> (keys only)", "k:run_sort (keys only)",
     // (the same kernels counting a TILE level by sorting -- other record sizes, so timed apart: TileLevelScope)
     "k:radix_scatter_kernel<HashDigit> (tile records)", "k:radix_hist_kernel<HashDigit> (tile records)", "k:tiles_to_records_kernel (tile records)",
-    "k:hash_group_index_kernel (tile records)", "k:lds_count_kernel (tile records)"};
+    "k:hash_group_index_kernel (tile records)", "k:lds_count_kernel (tile records)", "k:half_merge_kernel"};
 struct Profiler {
     bool on = false;
     struct Ev { int phase; hipEvent_t a, b; uint64_t work; };      // work: elements the launch processed (K_* entries)
@@ -206,6 +206,16 @@ int dev_region_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uin
 int dev_hash_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t nw, uint64_t* ka, uint64_t* kb, uint32_t* wa, uint32_t* wb,
                    const uint64_t** k_out, const uint32_t** w_out, uint32_t* group_bits, hipStream_t stream, const uint32_t* first_counts = nullptr);
 uint32_t dev_sort_tile_keys(uint32_t nw);
+// one-word records by their leading 16 key bits (k = 8..32): two stable passes; the result where *k_out / *w_out point (kb / wb)
+int dev_key_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t k, uint64_t* ka, uint64_t* kb, uint32_t* wa, uint32_t* wb,
+                  const uint64_t** k_out, const uint32_t** w_out, hipStream_t stream, const uint32_t* first_counts = nullptr);
+// index[g] (65537 of them) = first of n ascending one-word keys whose bits [shift, shift + 16) are >= g
+int dev_key_group_index(const uint64_t* d_keys, uint64_t n, uint32_t shift, uint64_t* d_index, hipStream_t stream);
+// merges, per 16-bit key prefix g, a_count[g] ascending keys at a_key + a_first[g] with the sorted b_key[b_first[g] .. b_first[g + 1])
+// into out + a_off[g] + b_first[g] (a_off: exclusive sums of a_count)
+int dev_half_merge(const uint64_t* a_key, const uint32_t* a_w, const uint64_t* a_first, const uint32_t* a_count, const uint64_t* a_off,
+                   const uint64_t* b_key, const uint32_t* b_w, const uint64_t* b_first, uint64_t* out_key, uint32_t* out_w, uint64_t n_out,
+                   hipStream_t stream);
 int dev_unique(uint64_t* d_keys, uint64_t n, uint32_t nw, uint64_t* n_out, hipStream_t stream);
 int dev_rank(const uint64_t* d_sorted, uint64_t n_sorted, uint32_t nw, uint32_t key_bits, const uint64_t* d_q, uint64_t nq,
              uint64_t* d_out, hipStream_t stream);
@@ -332,7 +342,12 @@ int table_expand_tiles(Table& tiles, uint64_t slot0, uint64_t slot1, Table& kmer
 int table_expand_tiles_to_records(Table& tiles, uint32_t k, uint32_t span, bool rc, DevBuf& keys, DevBuf& weights,
                                   uint64_t* n_records, hipStream_t stream, DevBuf* seen = nullptr);
 int table_list_to_records(const uint64_t* d_tiles, const uint32_t* d_counts, uint64_t n_tiles, uint32_t tile_bases, uint32_t k, uint32_t span, uint32_t stride, bool rc,
-                          DevBuf& keys, DevBuf& weights, uint64_t* n_records, hipStream_t stream, uint64_t extra_room = 0, DevBuf* first_counts = nullptr);
+                          DevBuf& keys, DevBuf& weights, uint64_t* n_records, hipStream_t stream, uint64_t extra_room = 0, DevBuf* first_counts = nullptr,
+                          bool rep = false);
+// (rep: the k-mers in their representative orientation -- kmer_bits.h rep_orientation -- for the ordered count, records_to_edges_sorted
+// with a HalfSort; first_counts are then that count's first key digit)
+// in place: n one-word k-mer records into their representative orientation (rep) or back into the canonical one
+int table_orient_records(uint64_t* d_keys, uint64_t n, uint32_t k, bool rep, hipStream_t stream);
 // (first_counts: filled with the digit counts per tile of the first partition pass over these records -- dev_hash_order's first_counts --
 // when the kernel can make them as it writes; released otherwise)
 // (extra_room: records the caller will append behind them -- the windows left over after the tiles)
@@ -360,9 +375,25 @@ struct OwnerSplit {
     uint32_t n_parts = 0, core_shift = 0, core_bases = 0;
     uint64_t base[KATOME_MAX_RANKS] = {0}, count[KATOME_MAX_RANKS] = {0};
 };
+// The k-mer level's ordered count (lds_count_ordered_kernel): S1, the representatives in key order with holes (s1_key / s1_w at
+// group_first[g], group_count[g] of them), and S2, their reverse complements in no order (n_s2).  half_sort_finish sorts S2 and merges
+// the two into the sorted edge list -- the arrays a sort of all edges gives -- and releases them.
+struct HalfSort {
+    DevBuf s1_key, s1_w, group_first, group_count, s2_key, s2_w;
+    uint64_t n_s1 = 0, n_s2 = 0;
+    uint32_t k = 0;
+    bool taken = false;
+    void release() {
+        s1_key.release(); s1_w.release(); group_first.release(); group_count.release(); s2_key.release(); s2_w.release();
+        n_s1 = n_s2 = 0; taken = false;
+    }
+};
+int half_sort_finish(HalfSort& hs, DevBuf& edge_key, DevBuf& edge_weight, hipStream_t stream);
+// (half: the records are in their representative orientation -- table_list_to_records with rep -- and the level is counted in order
+// into *half when it can be (half->taken); otherwise they are turned back and counted the usual way, with unsorted edges out)
 int records_to_edges_sorted(DevBuf& keys, DevBuf& weights, uint64_t n, uint32_t k, bool rc, uint32_t min_weight, DevBuf& edge_key,
                             DevBuf& edge_weight, uint64_t* n_edges, uint64_t* n_distinct, hipStream_t stream, OwnerSplit* split = nullptr,
-                            const uint32_t* first_counts = nullptr);
+                            const uint32_t* first_counts = nullptr, HalfSort* half = nullptr);
 int table_to_records(Table& t, DevBuf& keys, DevBuf& weights, uint64_t* n_records, hipStream_t stream, DevBuf* seen_pairs = nullptr);
 int table_expand_tiles_to_subtiles(Table& tiles, uint32_t k, uint32_t span, uint32_t stride, bool rc, DevBuf& keys, DevBuf& weights,
                                    uint64_t* n_records, hipStream_t stream, DevBuf* seen = nullptr);

@@ -186,6 +186,11 @@ template <int NW> KD Key<NW> canonical(const Key<NW>& a, u32 k) {
     Key<NW> rc = revcomp(a, k);
     return key_lt(rc, a) ? rc : a;
 }
+// Odd k only: the orientation of a one-word k-mer whose middle base has a 0 in the high bit of its 2-bit code.  The middle base
+// is its own mirror under reverse complement and complement is bitwise NOT, so exactly one of x and rc(x) qualifies and
+// rep(rc x) = rep(x).  Unlike canonical(), which piles its leading bases at the low end, rep's leading bases are as uniform as the
+// input's: key ranges cut on them are as even as hash ranges (the k-mer level's ordered count, table.hip).
+KD Key<1> rep_orientation(const Key<1>& a, u32 k) { return ((a.w[0] >> k) & 1ull) ? revcomp(a, k) : a; }
 // same, telling whether the reverse complement was taken
 template <int NW> KD Key<NW> canonical_flip(const Key<NW>& a, u32 k, bool& flipped) {
     Key<NW> rc = revcomp(a, k);

@@ -101,6 +101,13 @@ template <int NW> struct CoreHashDigit {
     __device__ __forceinline__ u32 operator()(const Key<NW>& k) const { return (u32)(core_hash(k, core_shift, core_bases) >> shift) & (RADIX - 1); }
 };
 
+// ... and the k-mer level's KEY digit for the ordered count (table.hip, lds_count_ordered_kernel): the records are in their
+// representative orientation and ordered by their leading 16 key bits, so that group g is a contiguous key range
+struct LevelKeyDigit {
+    u32 shift;
+    __device__ __forceinline__ u32 operator()(const Key<1>& k) const { return (u32)(k.w[0] >> shift) & (RADIX - 1); }
+};
+
 template <int NW> __device__ __forceinline__ Key<NW> load_key(const u64* p, u64 i) {
     Key<NW> k;
     if (NW == 1) { k.w[0] = p[i]; }
@@ -369,6 +376,7 @@ struct PassBuffers {
 template <class Digit> struct DigitTimers { static constexpr int HIST = K_SORT_HIST, SCATTER = K_SORT_SCATTER; };
 template <int NW> struct DigitTimers<HashDigit<NW>> { static constexpr int HIST = K_HASH_HIST, SCATTER = K_HASH_SCATTER; };
 template <int NW> struct DigitTimers<HashTaggedDigit<NW>> { static constexpr int HIST = K_HASH_HIST, SCATTER = K_HASH_SCATTER; };
+template <> struct DigitTimers<LevelKeyDigit> { static constexpr int HIST = K_HASH_HIST, SCATTER = K_HASH_SCATTER; };
 template <int NW> struct DigitTimers<CoreHashDigit<NW>> { static constexpr int HIST = K_HASH_HIST, SCATTER = K_HASH_SCATTER; };
 template <int NW> struct DigitTimers<OwnerDigit<NW>> { static constexpr int HIST = K_OWNER_HIST, SCATTER = K_OWNER_SCATTER; };
 template <> struct DigitTimers<SupermerOwnerDigit> { static constexpr int HIST = K_OWNER_HIST, SCATTER = K_OWNER_SCATTER; };
@@ -848,6 +856,105 @@ int dev_hash_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint3
     if (nw == 3) return region_order_t<3>(d_in, w_in, n, 2, ka, kb, wa, wb, k_out, w_out, stream, first_counts);      // (tiles of 64..95 bases)
     return region_order_t<2>(d_in, w_in, n, 2, ka, kb, wa, wb, k_out, w_out, stream, first_counts);
 }
+// one-word (k-mer, count) records ordered by their leading 16 key bits (bits 2k - 16 .. 2k - 1): two stable 8-bit passes, the
+// result where *k_out / *w_out point (first_counts: the first pass's digit counts per tile, made while the records were written)
+int dev_key_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t k, uint64_t* ka, uint64_t* kb, uint32_t* wa, uint32_t* wb,
+                  const uint64_t** k_out, const uint32_t** w_out, hipStream_t stream, const uint32_t* first_counts) {
+    if (k < 8 || 2 * k > 64) { set_error("key order: k = %u", k); return KATOME_E_ARG; }
+    PassBuffers pb;
+    KCHECK(pb.init(n, 1, stream));
+    if (first_counts) KCHECK_HIP(hipMemcpyAsync(pb.counts.p, first_counts, pb.nblocks * RADIX * sizeof(u32), hipMemcpyDeviceToDevice, stream));
+    KCHECK((radix_pass<1, true>(d_in, w_in, n, LevelKeyDigit{2 * k - 16}, ka, wa, pb, stream, first_counts != nullptr)));
+    KCHECK((radix_pass<1, true>(ka, wa, n, LevelKeyDigit{2 * k - 8}, kb, wb, pb, stream)));
+    *k_out = kb; *w_out = wb;
+    return KATOME_OK;
+}
+
+// index[g] = first of n ascending-by-leading-bits one-word keys whose bits [shift, shift + 16) are >= g, g = 0 .. 65536
+__global__ __launch_bounds__(BLOCK) void key_group_index_kernel(const u64* __restrict__ keys, u64 n, u32 shift, u64* __restrict__ index) {
+    for (u64 g = (u64)blockIdx.x * BLOCK + threadIdx.x; g <= (1ull << 16); g += (u64)gridDim.x * BLOCK) {
+        u64 lo = 0, hi = n;
+        while (lo < hi) {
+            const u64 mid = lo + ((hi - lo) >> 1);
+            if ((keys[mid] >> shift) < g) lo = mid + 1; else hi = mid;
+        }
+        index[g] = lo;
+    }
+}
+int dev_key_group_index(const uint64_t* d_keys, uint64_t n, uint32_t shift, uint64_t* d_index, hipStream_t stream) {
+    KernelScope ks(K_GROUP_INDEX, stream, n);
+    hipLaunchKernelGGL(key_group_index_kernel, dim3(grid_for((1ull << 16) + 1, BLOCK)), dim3(BLOCK), 0, stream, d_keys, n, shift, d_index);
+    KCHECK_HIP(hipGetLastError());
+    return KATOME_OK;
+}
+
+// The edge list of the ordered k-mer count in one streaming pass: for every 16-bit key prefix g, A = the representatives of group g
+// (a_key + a_first[g], a_count[g] of them, ascending: lds_count_ordered_kernel) and B = the sorted reverse complements with that
+// prefix (b_key + b_first[g] .. b_first[g + 1]) are merged into out + a_off[g] + b_first[g].  A and B are disjoint and every key
+// is distinct, so the order is the one a sort of both lists together gives.  A workgroup walks its prefix's two runs through two
+// LDS rings of MW keys: each step tops both rings up to MW (or to the run's end), and the first min(MW, loaded) of their merge are
+// final -- a key among them from one ring is below every key still unloaded in the other, whose ring is full or done.  Every
+// thread places MI outputs by a merge-path search in the rings (MT = 512 threads: 24 waves per CU beside the rings' 48 KiB; with
+// 256 threads and 8 outputs each the steps' loads and barriers were not hidden -- 14.6 ms at C3, 2.6 TB/s)
+constexpr u32 MW = 2048, MT = 512, MI = MW / MT;
+__global__ __launch_bounds__(MT) void half_merge_kernel(const u64* __restrict__ a_key, const u32* __restrict__ a_w, const u64* __restrict__ a_first,
+                                                          const u32* __restrict__ a_count, const u64* __restrict__ a_off, const u64* __restrict__ b_key,
+                                                          const u32* __restrict__ b_w, const u64* __restrict__ b_first, u64* __restrict__ out_key,
+                                                          u32* __restrict__ out_w, u64 out_cap) {
+    __shared__ u64 ak[MW], bk[MW];
+    __shared__ u32 aw[MW], bw[MW];
+    __shared__ u32 used_a;
+    const u32 tid = threadIdx.x;
+    for (u32 g = blockIdx.x; g < (1u << 16); g += gridDim.x) {
+        const u64* ap = a_key + a_first[g]; const u32* awp = a_w + a_first[g];
+        const u64 b0 = b_first[g];
+        const u64* bp = b_key + b0; const u32* bwp = b_w + b0;
+        const u32 na = a_count[g], nb = (u32)(b_first[g + 1] - b0);
+        u64 o = a_off[g] + b0;
+        u32 ca = 0, cb = 0, la = 0, lb = 0;                   // consumed / loaded of each run
+        while (ca < na || cb < nb) {
+            const u32 ea = na - ca < MW ? na : ca + MW, eb = nb - cb < MW ? nb : cb + MW;
+#pragma unroll 4
+            for (u32 i = la + tid; i < ea; i += MT) { ak[i & (MW - 1)] = ap[i]; aw[i & (MW - 1)] = awp[i]; }
+#pragma unroll 4
+            for (u32 i = lb + tid; i < eb; i += MT) { bk[i & (MW - 1)] = bp[i]; bw[i & (MW - 1)] = bwp[i]; }
+            la = ea; lb = eb;
+            __syncthreads();
+            const u32 va = la - ca, vb = lb - cb, c = va + vb < MW ? va + vb : MW;
+            const u32 d0 = tid * MI;
+            if (d0 < c) {
+                // merge path: the number of A keys among the first d0 outputs
+                u32 lo = d0 > vb ? d0 - vb : 0, hi = d0 < va ? d0 : va;
+                while (lo < hi) {
+                    const u32 m = (lo + hi) >> 1;
+                    if (ak[(ca + m) & (MW - 1)] < bk[(cb + d0 - m - 1) & (MW - 1)]) lo = m + 1; else hi = m;
+                }
+                u32 i = lo, j = d0 - lo;
+                const u32 d1 = d0 + MI < c ? d0 + MI : c;
+                for (u32 d = d0; d < d1; ++d) {
+                    const bool take_a = i < va && (j >= vb || ak[(ca + i) & (MW - 1)] < bk[(cb + j) & (MW - 1)]);
+                    u64 key; u32 w;
+                    if (take_a) { key = ak[(ca + i) & (MW - 1)]; w = aw[(ca + i) & (MW - 1)]; ++i; }
+                    else        { key = bk[(cb + j) & (MW - 1)]; w = bw[(cb + j) & (MW - 1)]; ++j; }
+                    if (o + d < out_cap) { out_key[o + d] = key; out_w[o + d] = w; }
+                }
+                if (d1 == c) used_a = i;                      // (the thread that places the step's last output)
+            }
+            __syncthreads();
+            ca += used_a; cb += c - used_a; o += c;
+            __syncthreads();                                  // (used_a is read before the next step's last thread writes it)
+        }
+    }
+}
+int dev_half_merge(const uint64_t* a_key, const uint32_t* a_w, const uint64_t* a_first, const uint32_t* a_count, const uint64_t* a_off,
+                   const uint64_t* b_key, const uint32_t* b_w, const uint64_t* b_first, uint64_t* out_key, uint32_t* out_w, uint64_t n_out,
+                   hipStream_t stream) {
+    KernelScope ks(K_HALF_MERGE, stream, n_out);
+    hipLaunchKernelGGL(half_merge_kernel, dim3(2048u), dim3(MT), 0, stream, a_key, a_w, a_first, a_count, a_off, b_key, b_w, b_first, out_key, out_w, n_out);
+    KCHECK_HIP(hipGetLastError());
+    return KATOME_OK;
+}
+
 // records per tile of a partition pass over records of nw words, and the digit of dev_hash_order's first pass (for a kernel that
 // writes such records and counts that pass's digits per tile as it goes: table.hip, list_to_records_kernel)
 uint32_t dev_sort_tile_keys(uint32_t nw) { return nw == 1 ? SortTile<1>::KEYS : nw == 2 ? SortTile<2>::KEYS : SortTile<3>::KEYS; }

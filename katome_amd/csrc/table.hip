@@ -616,7 +616,12 @@ __global__ __launch_bounds__(BLOCK) void tiles_to_records_kernel(const typename 
 
 // a compact list of distinct tiles with their counts (what the sorted counting of a level leaves) -> the (sub-window, count) records
 // of the next level: record p is sub-window p % span of tile p / span; consecutive lanes write consecutive records
-template <int NWT, int NWK, bool RC>
+// (REP: one-word k-mers of the ordered count, lds_count_ordered_kernel -- the representative orientation instead of the canonical one)
+template <int NWK, bool RC, bool REP> __device__ __forceinline__ Key<NWK> level_orientation(const Key<NWK>& x, u32 k) {
+    if constexpr (REP) { static_assert(NWK == 1, "one-word k-mers"); return RC ? rep_orientation(x, k) : x; }
+    else return RC ? canonical(x, k) : x;
+}
+template <int NWT, int NWK, bool RC, bool REP = false>
 __global__ __launch_bounds__(BLOCK) void list_to_records_kernel(const u64* __restrict__ tiles, const u32* __restrict__ counts, u64 n_tiles, u32 k, u32 span,
                                                                  u32 stride, u64* __restrict__ out_keys, u32* __restrict__ out_w) {
     const u64 n = n_tiles * span;
@@ -626,8 +631,7 @@ __global__ __launch_bounds__(BLOCK) void list_to_records_kernel(const u64* __res
         Key<NWT> tile;
 #pragma unroll
         for (int q = 0; q < NWT; ++q) tile.w[q] = tiles[t * NWT + q];
-        Key<NWK> x = sub_window<NWT, NWK>(tile, k, span, stride, o);
-        if (RC) x = canonical(x, k);
+        const Key<NWK> x = level_orientation<NWK, RC, REP>(sub_window<NWT, NWK>(tile, k, span, stride, o), k);
 #pragma unroll
         for (int q = 0; q < NWK; ++q) out_keys[p * NWK + q] = x.w[q];
         out_w[p] = counts[t];
@@ -637,7 +641,8 @@ __global__ __launch_bounds__(BLOCK) void list_to_records_kernel(const u64* __res
 // The same records written tile by tile of the partition pass that follows -- `tile_keys` consecutive records per trip of a workgroup
 // -- with that pass's digit (bits 48..55 of the record's hash: dev_hash_order's first pass) counted per tile in LDS as they are made:
 // counts[tile][digit] is what radix_hist_kernel would count, without reading the records back (C3: 17 + 15 GB not read per build).
-template <int NWT, int NWK, bool RC>
+// (REP: the ordered count's records and the first digit of dev_key_order, bits 2k - 16 .. 2k - 9 of the key)
+template <int NWT, int NWK, bool RC, bool REP = false>
 __global__ __launch_bounds__(BLOCK) void list_to_records_hist_kernel(const u64* __restrict__ tiles, const u32* __restrict__ counts, u64 n_tiles, u32 k, u32 span,
                                                                       u32 stride, u64* __restrict__ out_keys, u32* __restrict__ out_w, u32 tile_keys,
                                                                       u32* __restrict__ digit_counts) {
@@ -654,12 +659,11 @@ __global__ __launch_bounds__(BLOCK) void list_to_records_hist_kernel(const u64* 
             Key<NWT> tile;
 #pragma unroll
             for (int q = 0; q < NWT; ++q) tile.w[q] = tiles[t * NWT + q];
-            Key<NWK> x = sub_window<NWT, NWK>(tile, k, span, stride, o);
-            if (RC) x = canonical(x, k);
+            const Key<NWK> x = level_orientation<NWK, RC, REP>(sub_window<NWT, NWK>(tile, k, span, stride, o), k);
 #pragma unroll
             for (int q = 0; q < NWK; ++q) out_keys[p * NWK + q] = x.w[q];
             out_w[p] = counts[t];
-            atomicAdd(&h[(u32)(hash_key(x) >> 48) & 255u], 1u);
+            atomicAdd(&h[(REP ? (u32)(x.w[0] >> (2 * k - 16)) : (u32)(hash_key(x) >> 48)) & 255u], 1u);
         }
         __syncthreads();
         digit_counts[ot * 256 + threadIdx.x] = h[threadIdx.x];
@@ -1001,6 +1005,160 @@ __global__ __launch_bounds__(LC_THREADS) void lds_count_packed_kernel(const u64*
     }
     my_distinct = wave_sum(my_distinct);
     if (lane == 0 && my_distinct) atomicAdd(distinct, (unsigned long long)my_distinct);
+}
+
+// The k-mer level counted so that half of its edges leave it in order (KATOME_EDGE_HALF_SORT; one-word k-mers of odd k or one strand,
+// one visit per record).  The records are in their representative orientation (kmer_bits.h rep_orientation; as they are with one
+// strand) and ordered by their leading 16 key bits (dev_key_order), so group g is the key range of prefix g.  The insert loop is
+// lds_count_packed_kernel's, with the key's low 2k - 16 bits in the slot instead of the hash's (the probe sequence still comes from the
+// hash).  At read-out the group's kept keys are put in key order in the table's own LDS -- a counting sort on the remainder's top 11
+// bits into 2048 buckets, then every key is placed by counting the keys of its bucket (about 6 at C3) below it -- and leave as two lists:
+//   S1, the representatives, ascending, from the group's first record on (s1_key + index[g]: fixed before the count, so the groups
+//       stay in key order; a group has no more distinct keys than records), their number in group_count[g];
+//   S2 (both strands), their reverse complements, behind a cursor in no order.
+// half_merge_kernel (radix.hip) merges S1 with S2 once S2 is sorted.  err 5 / err 3 as in lds_count_packed_kernel: the caller then
+// counts the usual way.
+constexpr u32 LO_BUCKETS = 2 * LC_THREADS;                           // (two 16-bit counters to a word, one word per thread in the scan)
+template <bool RC>
+__global__ __launch_bounds__(LC_THREADS) void lds_count_ordered_kernel(const u64* keys, const u32* wts, const u64* __restrict__ index, u32 k,
+                                                                        u32 min_weight, u64* s1_key, u32* s1_w, u32* group_count, u64* s2_key,
+                                                                        u32* s2_w, u64 s2_cap, unsigned long long* cursor,
+                                                                        unsigned long long* distinct, u32* err, u32 probe_limit) {
+    extern __shared__ unsigned long long lc_mem[];
+    unsigned long long* slot = lc_mem;                                   // [LP_SLOTS]: remainder << 16 | count; then the kept ones in key order
+    u32* bucket = reinterpret_cast<u32*>(lc_mem + LP_SLOTS);             // [LO_BUCKETS / 2]: counters of buckets 2i (low half), 2i + 1
+    __shared__ u32 wtot[LC_THREADS / 64];
+    __shared__ unsigned long long base_sh;
+    const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const u32 rem_bits = 2 * k - 16, bshift = rem_bits > 11 ? rem_bits - 11 : 0;            // (bucket: the remainder's top 11 bits)
+    const u64 REM = (1ull << rem_bits) - 1;
+    u32 my_distinct = 0;
+    LC_PHASE_BEGIN();
+    for (u32 g = blockIdx.x; g < (1u << 16); g += gridDim.x) {
+        const u64 lo = index[g], hi = index[g + 1];
+        if (lo == hi) continue;
+        for (u32 i = tid; i < LP_SLOTS; i += LC_THREADS) slot[i] = 0ull;
+        bucket[tid] = 0u;
+        __syncthreads();
+        LC_PHASE(12);
+        constexpr u32 LU = KATOME_LC_LU;
+        constexpr u32 NB = LP_SLOTS / 2;
+        for (u64 i0 = lo + tid; i0 < hi; i0 += (u64)LC_THREADS * LU) {
+            u64 kv[LU]; u32 wv[LU];
+#pragma unroll
+            for (u32 u = 0; u < LU; ++u) { const u64 i = i0 + (u64)u * LC_THREADS; kv[u] = 0; wv[u] = 0; if (i < hi) { kv[u] = keys[i]; wv[u] = wts[i]; } }
+#pragma unroll
+            for (u32 u = 0; u < LU; ++u) {
+                const u64 i = i0 + (u64)u * LC_THREADS;
+                if (i >= hi) continue;
+                const u64 h = mix64(kv[u]);
+                const u32 w = wv[u];
+                if (w == 0u || w > 0xFFFFu) { *err = 5; continue; }
+                const unsigned long long rem = kv[u] & REM, mine = (rem << 16) | w;
+                u32 b0 = (u32)(((h & 0x3FFFFFFFull) * NB) >> 30);
+                const u32 step = lc_step<LP_PER>(h);
+                u32 probes = 0;
+                for (; probes < probe_limit; ++probes) {
+                    u32 b1 = b0 + step; if (b1 >= NB) b1 -= NB;
+                    const ulonglong2 x = *reinterpret_cast<const ulonglong2*>(slot + 2 * b0), y = *reinterpret_cast<const ulonglong2*>(slot + 2 * b1);
+                    const unsigned long long c[4] = {x.x, x.y, y.x, y.y};
+                    u32 at = ~0u; bool have = false;
+#pragma unroll
+                    for (int j = 3; j >= 0; --j) if ((c[j] >> 16) == rem && c[j] != 0ull) { at = (j < 2 ? 2 * b0 : 2 * b1 - 2) + j; have = true; }
+                    if (!have) {
+#pragma unroll
+                        for (int j = 3; j >= 0; --j) if (c[j] == 0ull) at = (j < 2 ? 2 * b0 : 2 * b1 - 2) + j;
+                        if (at == ~0u) { b0 = b1 + step; if (b0 >= NB) b0 -= NB; continue; }
+                        const unsigned long long cur = atomicCAS(&slot[at], 0ull, mine);
+                        if (cur == 0ull) break;
+                        if ((cur >> 16) != rem) continue;
+                    }
+                    const unsigned long long old = atomicAdd(&slot[at], (unsigned long long)w);
+                    if ((old & 0xFFFFull) + w > 0xFFFFull) *err = 5;
+                    break;
+                }
+                if (probes == probe_limit) *err = 3;
+            }
+        }
+        __syncthreads();
+        LC_PHASE(13);
+        // read-out into registers; the table's LDS then takes the kept entries in bucket order
+        unsigned long long v[LP_PER]; u32 keep = 0;
+#pragma unroll
+        for (u32 j = 0; j < LP_PER; ++j) {
+            v[j] = slot[tid * LP_PER + j];
+            if (v[j]) { ++my_distinct; if (((u32)v[j] & 0xFFFFu) >= min_weight) keep |= 1u << j; }      // Clean::remove_weak_edges
+        }
+        // (2048 buckets of 16-bit counters, two to a word: a group holds at most LP_SLOTS < 2^16 keys, so no half carries into the other)
+#pragma unroll
+        for (u32 j = 0; j < LP_PER; ++j) {
+            if (!((keep >> j) & 1u)) continue;
+            const u32 b = (u32)((v[j] >> 16) >> bshift);
+            atomicAdd(&bucket[b >> 1], 1u << ((b & 1u) * 16u));
+        }
+        __syncthreads();
+        const u32 pair = bucket[tid], lo_cnt = pair & 0xFFFFu, cnt = lo_cnt + (pair >> 16);
+        u32 incl = cnt;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { u32 t = __shfl_up(incl, o, 64); if (lane >= (u32)o) incl += t; }
+        if (lane == 63) wtot[wave] = incl;
+        __syncthreads();
+        u32 woff = 0, total = 0;
+#pragma unroll
+        for (u32 w = 0; w < LC_THREADS / 64; ++w) { if (w < wave) woff += wtot[w]; total += wtot[w]; }
+        const u32 start = woff + incl - cnt;
+        bucket[tid] = start | ((start + lo_cnt) << 16);
+        if (tid == 0) { group_count[g] = total; base_sh = total ? atomicAdd(cursor, (unsigned long long)total) : 0ull; }
+        __syncthreads();
+#pragma unroll
+        for (u32 j = 0; j < LP_PER; ++j) {
+            if (!((keep >> j) & 1u)) continue;
+            const u32 b = (u32)((v[j] >> 16) >> bshift), sh = (b & 1u) * 16u;
+            slot[(atomicAdd(&bucket[b >> 1], 1u << sh) >> sh) & 0xFFFFu] = v[j];
+        }
+        __syncthreads();
+        // bucket b now spans [end(b - 1), end(b)).  A key's place in key order is its bucket's start plus the keys of its bucket
+        // below it (distinct remainders, so the whole entries compare as keys): independent reads of half a dozen entries -- an insertion
+        // sort per bucket instead was a chain of dependent LDS round trips that every wave waited out for its longest bucket, 62 % of
+        // the kernel (profiles/r05_half_sort.md)
+        u32 pos[LP_PER];
+#pragma unroll
+        for (u32 j = 0; j < LP_PER; ++j) {
+            pos[j] = 0;
+            if (!((keep >> j) & 1u)) continue;
+            const u32 b = (u32)((v[j] >> 16) >> bshift), e = (bucket[b >> 1] >> ((b & 1u) * 16u)) & 0xFFFFu;
+            u32 r = b ? (bucket[(b - 1) >> 1] >> (((b - 1) & 1u) * 16u)) & 0xFFFFu : 0u;
+            const u32 s0 = r;
+#pragma unroll 4
+            for (u32 i = s0; i < e; ++i) r += slot[i] < v[j] ? 1u : 0u;
+            pos[j] = r;
+        }
+        __syncthreads();
+#pragma unroll
+        for (u32 j = 0; j < LP_PER; ++j) if ((keep >> j) & 1u) slot[pos[j]] = v[j];
+        __syncthreads();
+        LC_PHASE(14);
+        for (u32 i = tid; i < total; i += LC_THREADS) {
+            const unsigned long long e = slot[i];
+            Key<1> x; x.w[0] = ((u64)g << rem_bits) | (e >> 16);
+            const u32 c = (u32)e & 0xFFFFu;
+            if (lo + i < hi) { s1_key[lo + i] = x.w[0]; s1_w[lo + i] = c; }
+            if (RC && base_sh + i < s2_cap) { s2_key[base_sh + i] = revcomp(x, k).w[0]; s2_w[base_sh + i] = c; }
+        }
+        __syncthreads();
+        LC_PHASE(15);
+    }
+    my_distinct = wave_sum(my_distinct);
+    if (lane == 0 && my_distinct) atomicAdd(distinct, (unsigned long long)my_distinct);
+}
+
+// in place: the level's one-word k-mer records in their representative orientation (rep) or back in the canonical one
+template <bool REP>
+__global__ __launch_bounds__(BLOCK) void orient_records_kernel(u64* keys, u64 n, u32 k) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
+        Key<1> x; x.w[0] = keys[i];
+        keys[i] = (REP ? rep_orientation(x, k) : canonical(x, k)).w[0];
+    }
 }
 
 // group boundaries when the records are ordered by the hash of their core (dev_hash_order_core), and the owners' first positions:
@@ -1985,8 +2143,9 @@ int table_to_records(Table& t, DevBuf& keys, DevBuf& weights, uint64_t* n_record
 
 // the (sub-window, count) records of a compact list of distinct tiles (list_to_records_kernel); extra_room: see below
 int table_list_to_records(const uint64_t* d_tiles, const uint32_t* d_counts, uint64_t n_tiles, uint32_t tile_bases, uint32_t k, uint32_t span, uint32_t stride, bool rc,
-                          DevBuf& keys, DevBuf& weights, uint64_t* n_records, hipStream_t stream, uint64_t extra_room, DevBuf* first_counts) {
+                          DevBuf& keys, DevBuf& weights, uint64_t* n_records, hipStream_t stream, uint64_t extra_room, DevBuf* first_counts, bool rep) {
     const uint32_t nwt = (uint32_t)key_words_for_k(tile_bases), nwk = (uint32_t)key_words_for_k(k);
+    if (rep && (nwk != 1 || nwt > 2 || k < 9 || (rc && !(k & 1)))) { set_error("records in their representative orientation: one-word k-mers, k >= 9, odd k or one strand"); return KATOME_E_ARG; }
     *n_records = n_tiles * span;
     KCHECK(keys.alloc((*n_records + extra_room + 1) * 8 * nwk, stream));
     KCHECK(weights.alloc((*n_records + extra_room + 1) * 4, stream));
@@ -2000,28 +2159,39 @@ int table_list_to_records(const uint64_t* d_tiles, const uint32_t* d_counts, uin
         KCHECK(first_counts->alloc(n_out_tiles * 256 * 4 + 16, stream));
         const dim3 hgrid(grid_for(n_out_tiles, 1, 256u * 32u)), block(BLOCK);
         KernelScope ks(K_RECORDS, stream, n_tiles);
+#define KATOME_LRH_REP(NWT, RCV) hipLaunchKernelGGL((list_to_records_hist_kernel<NWT, 1, RCV, true>), hgrid, block, 0, stream, d_tiles, d_counts, n_tiles, k, span, stride, keys.as<u64>(), weights.as<u32>(), tile_keys, first_counts->as<u32>())
 #define KATOME_LRH(NWT, NWK)                                                                                                            \
         do {                                                                                                                          \
             if (rc) hipLaunchKernelGGL((list_to_records_hist_kernel<NWT, NWK, true>), hgrid, block, 0, stream, d_tiles, d_counts, n_tiles, k, span, stride, keys.as<u64>(), weights.as<u32>(), tile_keys, first_counts->as<u32>()); \
             else    hipLaunchKernelGGL((list_to_records_hist_kernel<NWT, NWK, false>), hgrid, block, 0, stream, d_tiles, d_counts, n_tiles, k, span, stride, keys.as<u64>(), weights.as<u32>(), tile_keys, first_counts->as<u32>()); \
         } while (0)
+        if (rep) {               // (the ordered count's records: dev_key_order's first digit)
+            if (nwt == 2) { if (rc) KATOME_LRH_REP(2, true); else KATOME_LRH_REP(2, false); }
+            else          { if (rc) KATOME_LRH_REP(1, true); else KATOME_LRH_REP(1, false); }
+        } else
         if (nwt == 3 && nwk == 3) KATOME_LRH(3, 3);
         else if (nwt == 3 && nwk == 2) KATOME_LRH(3, 2);
         else if (nwt == 2 && nwk == 2) KATOME_LRH(2, 2);
         else if (nwt == 2 && nwk == 1) KATOME_LRH(2, 1);
         else KATOME_LRH(1, 1);
 #undef KATOME_LRH
+#undef KATOME_LRH_REP
         KCHECK_HIP(hipGetLastError());
         return KATOME_OK;
     }
     if (first_counts) first_counts->release();
     const dim3 grid(grid_for(*n_records, BLOCK, 256u * 32u)), block(BLOCK);
     KernelScope ks(K_RECORDS, stream, n_tiles);
+#define KATOME_LR_REP(NWT, RCV) hipLaunchKernelGGL((list_to_records_kernel<NWT, 1, RCV, true>), grid, block, 0, stream, d_tiles, d_counts, n_tiles, k, span, stride, keys.as<u64>(), weights.as<u32>())
 #define KATOME_LR(NWT, NWK)                                                                                                             \
     do {                                                                                                                              \
         if (rc) hipLaunchKernelGGL((list_to_records_kernel<NWT, NWK, true>), grid, block, 0, stream, d_tiles, d_counts, n_tiles, k, span, stride, keys.as<u64>(), weights.as<u32>()); \
         else    hipLaunchKernelGGL((list_to_records_kernel<NWT, NWK, false>), grid, block, 0, stream, d_tiles, d_counts, n_tiles, k, span, stride, keys.as<u64>(), weights.as<u32>()); \
     } while (0)
+    if (rep) {
+        if (nwt == 2) { if (rc) KATOME_LR_REP(2, true); else KATOME_LR_REP(2, false); }
+        else          { if (rc) KATOME_LR_REP(1, true); else KATOME_LR_REP(1, false); }
+    } else
     if (nwt == 3 && nwk == 3) KATOME_LR(3, 3);
     else if (nwt == 3 && nwk == 2) KATOME_LR(3, 2);
     else if (nwt == 2 && nwk == 2) KATOME_LR(2, 2);
@@ -2029,6 +2199,7 @@ int table_list_to_records(const uint64_t* d_tiles, const uint32_t* d_counts, uin
     else if (nwt == 1 && nwk == 1) KATOME_LR(1, 1);
     else { set_error("records of a tile list: tiles of %u words into windows of %u", nwt, nwk); return KATOME_E_UNSUPPORTED; }
 #undef KATOME_LR
+#undef KATOME_LR_REP
     KCHECK_HIP(hipGetLastError());
     return KATOME_OK;
 }
@@ -2242,10 +2413,97 @@ int tagged_records_sorted(DevBuf& recs, DevBuf& wts, uint64_t n, uint32_t k, boo
 // (k-mer, count) records in any order -> oriented edges (both strands with rc, weights summed per k-mer, threshold applied): counted
 // by sorting instead of in a table (see lds_count_kernel).  keys/weights: the records (consumed).  KATOME_E_UNSUPPORTED when
 // the input is out of the kernel's range (the caller counts in the table instead).
+int table_orient_records(uint64_t* d_keys, uint64_t n, uint32_t k, bool rep, hipStream_t stream) {
+    if (!n) return KATOME_OK;
+    KernelScope ks(K_RECORDS, stream, n);
+    if (rep) hipLaunchKernelGGL(orient_records_kernel<true>, dim3(grid_for(n, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, d_keys, n, k);
+    else     hipLaunchKernelGGL(orient_records_kernel<false>, dim3(grid_for(n, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, d_keys, n, k);
+    KCHECK_HIP(hipGetLastError());
+    return KATOME_OK;
+}
+
+// The ordered count of records_to_edges_sorted (lds_count_ordered_kernel).  KATOME_E_UNSUPPORTED: not this way -- the level's shape, a
+// group of more distinct keys than the table holds (err 3: key ranges are far less even than hash ranges on skewed or low-complexity
+// input) or a count beyond 16 bits (err 5); the records are then still all there, ordered by key, in their representative orientation.
+static int ordered_count(DevBuf& keys, DevBuf& weights, uint64_t n, uint32_t k, bool rc, uint32_t min_weight, HalfSort& hs, uint64_t* n_edges,
+                         uint64_t* n_distinct, hipStream_t stream, const uint32_t* first_counts) {
+    // (one visit per record: a group must fit the 8-byte-slot table at lds_count_packed_kernel's planning load)
+    const u64 avg = n >> 16;
+    if (!n || !weights.p || k < 9 || 2 * k > 62 || (rc && !(k & 1)) || (double)avg * 0.56 > LP_SLOTS * 0.66) return KATOME_E_UNSUPPORTED;
+    const u64* ko = nullptr; const u32* wo = nullptr;
+    {
+        DevBuf kb(stream), wb(stream);
+        KCHECK(kb.alloc((n + 1) * 8)); KCHECK(wb.alloc((n + 1) * 4));
+        KCHECK(dev_key_order(keys.as<u64>(), weights.as<u32>(), n, k, kb.as<u64>(), keys.as<u64>(), wb.as<u32>(), weights.as<u32>(), &ko, &wo, stream,
+                             first_counts));
+    }
+    KCHECK(hs.group_first.alloc(((1ull << 16) + 1) * 8, stream));
+    KCHECK(dev_key_group_index(ko, n, 2 * k - 16, hs.group_first.as<u64>(), stream));
+    KCHECK(hs.group_count.alloc((1ull << 16) * 4, stream));
+    KCHECK_HIP(hipMemsetAsync(hs.group_count.p, 0, (1ull << 16) * 4, stream));
+    KCHECK(hs.s1_key.alloc((n + 1) * 8, stream)); KCHECK(hs.s1_w.alloc((n + 1) * 4, stream));
+    const u64 s2_cap = rc ? n + 1 : 0;          // (a reverse complement per distinct key: no more than the records)
+    if (rc) { KCHECK(hs.s2_key.alloc(s2_cap * 8, stream)); KCHECK(hs.s2_w.alloc(s2_cap * 4, stream)); }
+    DevBuf aux(stream);
+    KCHECK(aux.alloc(64));
+    KCHECK_HIP(hipMemsetAsync(aux.p, 0, 64, stream));
+    unsigned long long* cursor = aux.as<unsigned long long>();
+    const size_t lds = (size_t)LP_SLOTS * 8 + LO_BUCKETS * 2;
+    {
+#define KATOME_LO_LAUNCH(RCV)                                                                                                               \
+        do {                                                                                                                              \
+            KCHECK_HIP(hipFuncSetAttribute((const void*)lds_count_ordered_kernel<RCV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            KernelScope ks(K_LDS_COUNT, stream, n);                                                                                       \
+            hipLaunchKernelGGL((lds_count_ordered_kernel<RCV>), dim3(256u), dim3(LC_THREADS), lds, stream, ko, wo, hs.group_first.as<u64>(), k, min_weight, \
+                               hs.s1_key.as<u64>(), hs.s1_w.as<u32>(), hs.group_count.as<u32>(), hs.s2_key.as<u64>(), hs.s2_w.as<u32>(), s2_cap,   \
+                               cursor, cursor + 1, reinterpret_cast<u32*>(cursor + 2), std::min<u32>(lc_probe_limit(), LP_SLOTS));              \
+        } while (0)
+        if (rc) KATOME_LO_LAUNCH(true); else KATOME_LO_LAUNCH(false);
+#undef KATOME_LO_LAUNCH
+    }
+    KCHECK_HIP(hipGetLastError());
+    uint64_t h[3] = {0, 0, 0};
+    KCHECK_HIP(hipMemcpyAsync(h, aux.p, 24, hipMemcpyDeviceToHost, stream));
+    KCHECK_HIP(hipStreamSynchronize(stream));
+    if (getenv("KATOME_LC_TRACE")) fprintf(stderr, "[lds count] in key order, 8-byte slots, 1 visit(s) per record: code %u\n", (unsigned)h[2]);
+    if ((uint32_t)h[2]) {
+        if (getenv("KATOME_LC_TRACE")) fprintf(stderr, "[lds count] in key order: %s; counting by hash groups\n", (uint32_t)h[2] == 5 ? "a count over 16 bits" : "a group filled its table");
+        hs.release();
+        return KATOME_E_UNSUPPORTED;
+    }
+    hs.n_s1 = h[0]; hs.n_s2 = rc ? h[0] : 0; hs.k = k; hs.taken = true;
+    *n_edges = hs.n_s1 + hs.n_s2; *n_distinct = h[1];
+    return KATOME_OK;
+}
+
+int half_sort_finish(HalfSort& hs, DevBuf& edge_key, DevBuf& edge_weight, hipStream_t stream) {
+    if (!hs.taken) { set_error("half sort: no ordered count to finish"); return KATOME_E_ARG; }
+    const uint32_t k = hs.k;
+    if (hs.n_s2) KCHECK(dev_sort_bufs(hs.s2_key, &hs.s2_w, hs.n_s2, 1, 2 * k, stream, true));
+    DevBuf b_first(stream), a_off(stream);
+    KCHECK(b_first.alloc(((1ull << 16) + 1) * 8)); KCHECK(a_off.alloc(((1ull << 16) + 1) * 8));
+    if (hs.n_s2) KCHECK(dev_key_group_index(hs.s2_key.as<u64>(), hs.n_s2, 2 * k - 16, b_first.as<u64>(), stream));
+    else KCHECK_HIP(hipMemsetAsync(b_first.p, 0, b_first.bytes, stream));
+    KCHECK(dev_scan_counts(hs.group_count.as<u32>(), 1ull << 16, a_off.as<u64>(), stream));
+    const uint64_t n_out = hs.n_s1 + hs.n_s2;
+    KCHECK(edge_key.alloc((n_out + 1) * 8, stream)); KCHECK(edge_weight.alloc((n_out + 1) * 4, stream));
+    KCHECK(dev_half_merge(hs.s1_key.as<u64>(), hs.s1_w.as<u32>(), hs.group_first.as<u64>(), hs.group_count.as<u32>(), a_off.as<u64>(),
+                          hs.s2_key.as<u64>(), hs.s2_w.as<u32>(), b_first.as<u64>(), edge_key.as<u64>(), edge_weight.as<u32>(), n_out, stream));
+    hs.release();
+    return KATOME_OK;
+}
+
 int records_to_edges_sorted(DevBuf& keys, DevBuf& weights, uint64_t n, uint32_t k, bool rc, uint32_t min_weight, DevBuf& edge_key,
                             DevBuf& edge_weight, uint64_t* n_edges, uint64_t* n_distinct, hipStream_t stream, OwnerSplit* split,
-                            const uint32_t* first_counts) {
+                            const uint32_t* first_counts, HalfSort* half) {
     *n_edges = 0; *n_distinct = 0;
+    if (half) {
+        half->taken = false;
+        const int orc = split ? KATOME_E_UNSUPPORTED : ordered_count(keys, weights, n, k, rc, min_weight, *half, n_edges, n_distinct, stream, first_counts);
+        if (orc != KATOME_E_UNSUPPORTED) return orc;
+        if (rc) KCHECK(table_orient_records(keys.as<u64>(), n, k, false, stream));      // (the usual route and the table take canonical k-mers)
+        first_counts = nullptr;
+    }
     const uint32_t nw = (uint32_t)key_words_for_k(k);
     if (nw > 3 || (nw == 3 && (rc || min_weight))) return KATOME_E_UNSUPPORTED;      // (three words: tiles of 64..95 bases -- never k-mers, so never oriented)
     if (split && (nw != 1 || rc || min_weight || split->n_parts == 0 || split->n_parts > (uint32_t)KATOME_MAX_RANKS)) {
