@@ -136,6 +136,15 @@ int katome_build_files_staged(const katome_settings *s, const char *const *paths
  * read_len < k is KATOME_E_SHORT_READ (pt_graph.rs:278). */
 int katome_build_packed(const katome_settings *s, const uint8_t *packed, uint64_t n_reads,
                         uint32_t read_len, const uint8_t *skip, katome_graph **out);
+/* katome_build_packed followed by the stages of katome_build_files_staged.  With settings.n_devices > 1 they run on the
+ * sharded graph when KATOME_DIST_STAGES=sharded is set or when the graph cannot be gathered (2^32 edges or nodes and more),
+ * else on the graph gathered to the first GPU (KATOME_DIST_STAGES=gather forces that); the same holds for
+ * katome_build_files_staged.  On the sharded route the KATOME_FLAG_REMOVE_DEAD_PATHS pruning runs sharded as well, whatever
+ * KATOME_DIST_PRUNE says (a gathered graph cannot go back to the shares).  katome_graph.edge_age is 32 bits wide: after a
+ * stage that may remove edges, a surviving edge aged 2^32 or more makes the copy-out fail with KATOME_E_UNSUPPORTED; such a
+ * graph is read through katome_dist_* (katome_dist_graph.d_edge_age is 64-bit). */
+int katome_build_packed_staged(const katome_settings *s, const uint8_t *packed, uint64_t n_reads, uint32_t read_len,
+                               const uint8_t *skip, const char *stages, uint64_t original_genome_length, katome_graph **out);
 
 void katome_graph_free(katome_graph *g);
 
@@ -461,7 +470,8 @@ typedef struct {
     uint64_t *d_node_key;                 /* [n_nodes][key_words]                                                    */
     uint64_t *d_edge_id, *d_node_id;      /* FIRST_SEEN_ORDER: the reference's (petgraph) index of every edge / node of
                                              this rank; NULL by packed key                                           */
-    uint64_t *d_edge_age;                 /* after katome_dist_remove_dead_paths: the index each edge had when it was built
+    uint64_t *d_edge_age;                 /* after katome_dist_remove_dead_paths or a stage that may remove edges
+                                             (katome_dist_prune_weak_edges, _standardize_edges): the index each edge had when it was built
                                              (= its place in petgraph's adjacency lists, see katome_graph.edge_age); else NULL */
 } katome_dist_graph;
 /* settings as for katome_builder_create (settings.device = this rank's GPU; table_slots_hint for the WHOLE build);
@@ -489,7 +499,29 @@ int  katome_dist_gather(katome_dist_builder *d, int root, katome_builder **root_
  * describes this rank's share of the pruned graph: d_edge_id / d_node_id are the indices the reference's PtGraph would hold,
  * d_edge_age the edges' ages.  Collective.                                                                              */
 int  katome_dist_remove_dead_paths(katome_dist_builder *d, katome_dist_graph *out, katome_prune_stats *stats, void *stream);
-/* this rank's share of the graph as it stands (after katome_dist_finalize / katome_dist_remove_dead_paths) */
+/* The stages of assemble_with_graph after the first pruning (asm/basic_assembler.rs:63-72) on the SHARDED graph of a
+ * finalized FIRST_SEEN_ORDER build whose shares were not gathered, no gather (katome_amd/csrc/dist_stages.hip); each may
+ * run straight after katome_dist_finalize or after katome_dist_remove_dead_paths, in any order, any number of times.  A
+ * packed-key or gathered builder gets KATOME_E_ARG.  Afterwards `out` describes this rank's share as after
+ * katome_dist_remove_dead_paths: d_edge_id / d_node_id hold petgraph's indices, d_edge_age the ages (which move with their
+ * edges) once a stage that may remove edges has run; edges stay on the rank that owns their source.  Collective.
+ * KATOME_DIST_STAGES_FAIL=edges|nodes (tests): rank 0's index replay of that kind fails, and every rank returns the error.
+ *   standardize_contigs (standardizer.rs:72-122): every contig gets the rounded mean of its weights, bit for bit as on one
+ *     GPU.  Every rank holds a table of 12 bytes per node of the WHOLE graph while it runs: KATOME_E_OOM on every rank
+ *     when a rank has no room for it (BASELINE config 5 in full on 8 ranks does not fit: DESIGN.md section 6).
+ * A rank's share stays below 2^32 edges and 2^32 nodes (KATOME_E_UNSUPPORTED on every rank otherwise), and one retain may
+ * remove fewer than 2^32 edges / nodes.
+ *   prune_weak_edges: Clean::remove_weak_edges(threshold) (pruner.rs:84-93), at once: retain_edges, then retain_nodes,
+ *     petgraph's swap_remove numbering on 64-bit positions.  (katome_dist_remove_weak_edges is another thing: by packed
+ *     key, the threshold applied when the edges are read out.)
+ *   standardize_edges (standardizer.rs:42-70): the weight sums of all ranks, the scaling of the one-GPU form, then
+ *     prune_weak_edges(1); original_genome_length < k: KATOME_E_ARG on every rank.
+ * After a stage that removed edges or nodes, katome_dist_remove_dead_paths runs for real again.                        */
+int  katome_dist_standardize_contigs(katome_dist_builder *d, katome_dist_graph *out, void *stream);
+int  katome_dist_prune_weak_edges(katome_dist_builder *d, uint32_t threshold, katome_dist_graph *out, void *stream);
+int  katome_dist_standardize_edges(katome_dist_builder *d, uint64_t original_genome_length, uint32_t threshold,
+                                   katome_dist_graph *out, void *stream);
+/* this rank's share of the graph as it stands (after katome_dist_finalize / katome_dist_remove_dead_paths / the stages) */
 int  katome_dist_current_graph(katome_dist_builder *d, katome_dist_graph *out);
 /* the rank's single-GPU builder underneath (per-phase kernel timing: katome_builder_profile*) */
 katome_builder *katome_dist_inner(katome_dist_builder *d);

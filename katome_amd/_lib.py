@@ -89,6 +89,7 @@ SYMBOLS = {
     "katome_build_files": (_i, [C.POINTER(Settings), _pp, _sz, C.POINTER(C.POINTER(Graph))]),
     "katome_build_files_staged": (_i, [C.POINTER(Settings), _pp, _sz, C.c_char_p, _u64, C.POINTER(C.POINTER(Graph))]),
     "katome_build_packed": (_i, [C.POINTER(Settings), _vp, _u64, _u32, _vp, C.POINTER(C.POINTER(Graph))]),
+    "katome_build_packed_staged": (_i, [C.POINTER(Settings), _vp, _u64, _u32, _vp, C.c_char_p, _u64, C.POINTER(C.POINTER(Graph))]),
     "katome_graph_free": (None, [C.POINTER(Graph)]),
     "katome_graph_stats": (_i, [C.POINTER(Graph), C.POINTER(Stats)]),
     "katome_last_error": (C.c_char_p, []),
@@ -171,6 +172,9 @@ SYMBOLS = {
     "katome_dist_route": (C.c_char_p, [_vp]),
     "katome_dist_remove_dead_paths": (_i, [_vp, C.POINTER(DistGraph), C.POINTER(PruneStats), _vp]),
     "katome_dist_current_graph": (_i, [_vp, C.POINTER(DistGraph)]),
+    "katome_dist_standardize_contigs": (_i, [_vp, C.POINTER(DistGraph), _vp]),
+    "katome_dist_prune_weak_edges": (_i, [_vp, C.c_uint32, C.POINTER(DistGraph), _vp]),
+    "katome_dist_standardize_edges": (_i, [_vp, C.c_uint64, C.c_uint32, C.POINTER(DistGraph), _vp]),
     "katome_dist_exchange_count": (_u32, []),
     "katome_dist_exchange_name": (C.c_char_p, [_u32]),
     "katome_dist_exchange_read": (_i, [_vp, u64p]),

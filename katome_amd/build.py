@@ -208,9 +208,11 @@ class GpuGraph:
     @classmethod
     def create_from_packed(cls, packed, n_reads, read_len, skip=None, reverse_complement=False, device=0, k=None,
                            first_seen_order=False, remove_dead_paths=False, n_devices=1, ranks_share_device=False,
-                           table_slots_hint=0):
-        """Same build from 2-bit packed reads (numpy uint8), the synthetic-workload entry."""
-        s = make_settings(K_SIZE if k is None else k, InputFileType.Fastq, reverse_complement, 0, device,
+                           table_slots_hint=0, stages=None, original_genome_length=0, minimal_weight_threshold=0):
+        """Same build from 2-bit packed reads (numpy uint8), the synthetic-workload entry.  stages / original_genome_length /
+        minimal_weight_threshold: as for create(); with n_devices > 1 the stages run on the sharded graph when
+        KATOME_DIST_STAGES=sharded is set or the graph is too big to gather, else on the gathered one."""
+        s = make_settings(K_SIZE if k is None else k, InputFileType.Fastq, reverse_complement, minimal_weight_threshold, device,
                           table_slots_hint=table_slots_hint, first_seen_order=first_seen_order,
                           remove_dead_paths=remove_dead_paths, n_devices=n_devices, ranks_share_device=ranks_share_device)
         packed = np.ascontiguousarray(packed, dtype=np.uint8)
@@ -219,7 +221,11 @@ class GpuGraph:
             skip = np.ascontiguousarray(skip, dtype=np.uint8)
             skip_p = skip.ctypes.data
         gp = C.POINTER(_lib.Graph)()
-        _check(_lib.lib().katome_build_packed(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, C.byref(gp)))
+        if stages:
+            _check(_lib.lib().katome_build_packed_staged(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, stages.encode(),
+                                                         original_genome_length, C.byref(gp)))
+        else:
+            _check(_lib.lib().katome_build_packed(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, C.byref(gp)))
         g = cls(gp)
         return g, g.read_bytes
 

@@ -1913,8 +1913,10 @@ extern "C" {
 
 // settings.n_devices > 1: the sharded build (dist.hip) with the ranks as host threads of this call, one per GPU.  Reads are
 // split contiguously by index; every rank copies its own share to its GPU.  By packed key the host arrays are the ranks'
-// shares one after the other (every rank copies its slice out itself); in the reference's numbering the graph is
-// gathered to the first GPU in index order, where the stages the flags ask for run and the result is copied out.
+// shares one after the other (every rank copies its slice out itself); in the reference's numbering every rank puts its
+// share at its indices.  The stages after the build (d, c, w, e) run on the sharded graph (dist_prune.hip, dist_stages.hip)
+// with KATOME_DIST_STAGES=sharded or when the graph cannot be gathered (2^32 edges or nodes and more); otherwise, and with
+// KATOME_DIST_STAGES=gather, the graph is gathered to the first GPU, where they run.  shrink always gathers.
 static int build_packed_multi(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len,
                               const uint8_t* skip, const Finish& finish, uint64_t read_bytes) {
     const int n = s->n_devices;
@@ -1928,8 +1930,9 @@ static int build_packed_multi(const katome_settings* s, const uint8_t* packed, u
         set_error("n_devices > 1: shrink and the stages after the build need KATOME_FLAG_FIRST_SEEN_ORDER (they run on the graph gathered in the reference's numbering)");
         return KATOME_E_ARG;
     }
-    // first-seen order: shrink and the staged pipeline still run on the graph gathered to the first GPU; the build itself and
-    // remove_dead_paths do not (KATOME_DIST_PRUNE=gather: the gathered route for those too)
+    // first-seen order: shrink runs on the graph gathered to the first GPU, and so do the stages unless KATOME_DIST_STAGES or the
+    // graph's size sends them to the sharded graph (decided after finalize); the build itself and remove_dead_paths do not
+    // (KATOME_DIST_PRUNE=gather: the gathered route for those too)
     const char* prune_route = getenv("KATOME_DIST_PRUNE");
     const bool direct = first_seen && !finish.contigs && !(finish.stages && *finish.stages) && !(prune_route && !strcmp(prune_route, "gather"));
     std::vector<int> devices(n);
@@ -1978,7 +1981,14 @@ static int build_packed_multi(const katome_settings* s, const uint8_t* packed, u
             if (!sync->barrier()) { set_error("another rank of this build failed"); rc = KATOME_E_DEVICE; break; }
             katome_dist_graph g;
             if ((rc = katome_dist_finalize(d, &g, stream))) break;
-            if (first_seen && !direct) {
+            bool gather = first_seen && !direct;
+            if (gather && !finish.contigs && finish.stages && *finish.stages) {
+                // (every rank sees the same totals and the same environment: they all take the same route)
+                const char* route = getenv("KATOME_DIST_STAGES");
+                const bool too_big = g.total_edges >= 0xFFFFFFFFull || g.total_nodes >= 0xFFFFFFFFull;
+                if ((route && !strcmp(route, "sharded")) || (too_big && !(route && !strcmp(route, "gather")))) gather = false;
+            }
+            if (gather) {
                 katome_builder* root = nullptr;
                 if ((rc = katome_dist_gather(d, 0, &root, stream))) break;
                 if (r == 0) {
@@ -1987,13 +1997,22 @@ static int build_packed_multi(const katome_settings* s, const uint8_t* packed, u
                 }
                 break;
             }
-            // the reference's numbering without a gather: remove_dead_paths (if asked for) on the sharded graph, then every rank
-            // puts its edges and nodes at their indices in the host arrays
-            bool pruned = false;
+            // the reference's numbering without a gather: remove_dead_paths (if asked for) and the stages on the sharded graph, then
+            // every rank puts its edges and nodes at their indices in the host arrays
             if (first_seen && (s->flags & KATOME_FLAG_REMOVE_DEAD_PATHS)) {
                 if ((rc = katome_dist_remove_dead_paths(d, &g, nullptr, stream))) break;
-                pruned = true;
             }
+            for (const char* st = first_seen && finish.stages ? finish.stages : ""; *st && rc == KATOME_OK; ++st) {
+                switch (*st) {
+                    case 'd': rc = katome_dist_remove_dead_paths(d, &g, nullptr, stream); break;
+                    case 'c': rc = katome_dist_standardize_contigs(d, &g, stream); break;
+                    case 'w': rc = katome_dist_prune_weak_edges(d, s->min_weight, &g, stream); break;
+                    case 'e': rc = katome_dist_standardize_edges(d, finish.genome_len, s->min_weight, &g, stream); break;
+                    default: set_error("unknown stage '%c' (d, c, w, e)", *st); rc = KATOME_E_ARG; break;      // (the same on every rank)
+                }
+            }
+            if (rc) break;
+            const bool pruned = g.d_edge_age != nullptr;      // (the ages come along once a stage that may remove edges has run)
             // by packed key: rank by rank
             sh.n_edges[r] = g.n_edges; sh.node_base[r] = g.node_base; sh.n_nodes[r] = g.n_nodes;
             if (!sync->barrier()) { set_error("another rank of this build failed"); rc = KATOME_E_DEVICE; break; }
@@ -2091,9 +2110,9 @@ static int build_packed_multi(const katome_settings* s, const uint8_t* packed, u
     for (int r = 0; r < n && !rc; ++r)
         if (sh.rc[r] && sh.err[r] != "another rank of this build failed") { rc = sh.rc[r]; set_error("rank %d of %d: %s", r, n, sh.err[r].c_str()); }
     for (int r = 0; r < n && !rc; ++r) if (sh.rc[r]) { rc = sh.rc[r]; set_error("rank %d of %d: %s", r, n, sh.err[r].c_str()); }
-    if (!first_seen || direct) {
-        if (rc == KATOME_OK && sh.owner && finish.graph) *finish.graph = &sh.owner->g;
-        else if (sh.owner) katome_graph_free(&sh.owner->g);
+    if (sh.owner) {                                              // (the ranks' shares were copied out: no gathered route ran)
+        if (rc == KATOME_OK && finish.graph) *finish.graph = &sh.owner->g;
+        else katome_graph_free(&sh.owner->g);
     }
     return rc;
 }
@@ -2170,6 +2189,14 @@ int katome_build_packed(const katome_settings* s, const uint8_t* packed, uint64_
     if (!out) { set_error("null argument"); return KATOME_E_ARG; }
     *out = nullptr;
     return build_packed_impl(s, packed, n_reads, read_len, skip, Finish{out, nullptr});
+}
+int katome_build_packed_staged(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len,
+                               const uint8_t* skip, const char* stages, uint64_t original_genome_length, katome_graph** out) {
+    if (!out) { set_error("null argument"); return KATOME_E_ARG; }
+    *out = nullptr;
+    Finish f{out, nullptr};
+    f.stages = stages; f.genome_len = original_genome_length;
+    return build_packed_impl(s, packed, n_reads, read_len, skip, f);
 }
 int katome_shrink_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len,
                          const uint8_t* skip, katome_contigs** out) {

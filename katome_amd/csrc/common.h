@@ -285,6 +285,10 @@ int dev_remove_weak_edges_ordered(PruneGraph& g, uint32_t threshold, hipStream_t
 // standardize.hip: Standardizable (standardizer.rs:41-128)
 int dev_standardize_contigs(const uint64_t* src, const uint64_t* dst, uint32_t* weight, uint64_t E, uint64_t N, hipStream_t stream);
 int dev_standardize_scale(uint32_t* weight, uint64_t E, uint64_t original_genome_length, uint32_t k, uint32_t threshold, hipStream_t stream);
+// its parts, for the sharded form (dist_stages.hip), which sums over all ranks in between
+int dev_weight_sums(const uint32_t* weight, uint64_t E, uint32_t threshold, uint64_t sums[2], hipStream_t stream);
+double standardization_ratio(uint64_t original_genome_length, uint32_t k, const uint64_t sums[2]);
+int dev_scale_weights(uint32_t* weight, uint64_t E, double p, uint32_t threshold, hipStream_t stream);
 
 // shrink.hip: Shrinkable::shrink (shrinker.rs:165-209) on a finalized graph; the result lives in its own buffers
 struct ShrinkInput {

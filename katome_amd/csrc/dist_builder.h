@@ -38,11 +38,13 @@ struct katome_dist_builder {
     uint64_t n_edges = 0, n_nodes = 0, total_edges = 0, total_nodes = 0, node_base = 0;
     katome::ExchangeStats xstats[X_COUNT];
     // kept for the stages that run on the sharded graph (dist_prune.hip; first-seen order only): every edge's source as the
-    // LOCAL index of the node (all out-edges of a node live on the node's owner) and its target as (owner rank, local index there)
+    // LOCAL index of the node (all out-edges of a node live on the node's owner) and its target as (owner rank, local index there);
+    // released by whatever removes edges or nodes, rebuilt by dist_rebuild_links
     DevBuf edge_lsrc, edge_drank, edge_dlocal;
-    DevBuf edge_age;                         // after katome_dist_remove_dead_paths: first-seen index each surviving edge had (u64)
+    DevBuf edge_age;                         // after katome_dist_remove_dead_paths or a stage that may remove edges (dist_stages.hip):
+                                             // the first-seen index each surviving edge had (u64)
     uint64_t n_src = 0;                      // this rank's nodes [0, n_src) have out-edges (ascending by key), the rest do not
-    bool dead_paths_removed = false;         // katome_dist_remove_dead_paths has run to its fixpoint on this sharded graph
+    bool dead_paths_removed = false;         // katome_dist_remove_dead_paths has run to its fixpoint and no edge or node went since
     bool gathered = false;                   // katome_dist_gather has consumed the ranks' shares
 
     int world() const { return comm->world(); }
@@ -88,3 +90,5 @@ struct katome_dist_builder {
     }
 };
 
+// dist_stages.hip: edge_lsrc / edge_drank / edge_dlocal / n_src of the share as it stands (collective)
+int dist_rebuild_links(katome_dist_builder* d, hipStream_t stream);

@@ -102,22 +102,38 @@ int dev_standardize_contigs(const uint64_t* src, const uint64_t* dst, uint32_t* 
     return KATOME_OK;
 }
 
+// the two sums of calculate_standardization_ratio: all weights, and those under the threshold (sums[0], sums[1]; host)
+int dev_weight_sums(const uint32_t* weight, uint64_t E, uint32_t threshold, uint64_t sums[2], hipStream_t stream) {
+    sums[0] = sums[1] = 0;
+    if (E == 0) return KATOME_OK;
+    DevBuf d_sums(stream);
+    KCHECK(d_sums.alloc(16));
+    KCHECK_HIP(hipMemsetAsync(d_sums.p, 0, 16, stream));
+    hipLaunchKernelGGL(weight_sums_kernel, dim3(grid_for(E, BLOCK, 256u * 16u)), dim3(BLOCK), 0, stream, weight, E, threshold, d_sums.as<u64>());
+    KCHECK_HIP(hipGetLastError());
+    KCHECK_HIP(hipMemcpyAsync(sums, d_sums.p, 16, hipMemcpyDeviceToHost, stream));
+    KCHECK_HIP(hipStreamSynchronize(stream));
+    return KATOME_OK;
+}
+// calculate_standardization_ratio (124-128)
+double standardization_ratio(uint64_t original_genome_length, uint32_t k, const uint64_t sums[2]) {
+    return (double)(original_genome_length - k) / (double)(sums[0] - sums[1]);
+}
+// every weight scaled by p as `as EdgeWeight` does it, lifted to 1 where a weight at or above the threshold would vanish
+int dev_scale_weights(uint32_t* weight, uint64_t E, double p, uint32_t threshold, hipStream_t stream) {
+    if (E == 0) return KATOME_OK;
+    hipLaunchKernelGGL(scale_weights_kernel, dim3(grid_for(E, BLOCK, 256u * 16u)), dim3(BLOCK), 0, stream, weight, E, p, threshold);
+    KCHECK_HIP(hipGetLastError());
+    return KATOME_OK;
+}
+
 // the scaling half of standardize_edges; the caller follows with remove_weak_edges(1)
 int dev_standardize_scale(uint32_t* weight, uint64_t E, uint64_t original_genome_length, uint32_t k, uint32_t threshold, hipStream_t stream) {
     if (original_genome_length < k) { set_error("standardize_edges: original_genome_length < k"); return KATOME_E_ARG; }
     if (E == 0) return KATOME_OK;
-    DevBuf sums(stream);
-    KCHECK(sums.alloc(16));
-    KCHECK_HIP(hipMemsetAsync(sums.p, 0, 16, stream));
-    const dim3 grid(grid_for(E, BLOCK, 256u * 16u)), blk(BLOCK);
-    hipLaunchKernelGGL(weight_sums_kernel, grid, blk, 0, stream, weight, E, threshold, sums.as<u64>());
-    u64 h[2] = {0, 0};
-    KCHECK_HIP(hipMemcpyAsync(h, sums.p, 16, hipMemcpyDeviceToHost, stream));
-    KCHECK_HIP(hipStreamSynchronize(stream));
-    const double p = (double)(original_genome_length - k) / (double)(h[0] - h[1]);      // calculate_standardization_ratio (124-128)
-    hipLaunchKernelGGL(scale_weights_kernel, grid, blk, 0, stream, weight, E, p, threshold);
-    KCHECK_HIP(hipGetLastError());
-    return KATOME_OK;
+    uint64_t h[2] = {0, 0};
+    KCHECK(dev_weight_sums(weight, E, threshold, h, stream));
+    return dev_scale_weights(weight, E, standardization_ratio(original_genome_length, k, h), threshold, stream);
 }
 
 }  // namespace katome

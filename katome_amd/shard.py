@@ -167,7 +167,8 @@ class RankGraph:
         self.node_key = _view(g.d_node_key, (nn, nw), "<i8", owner, device)
         self.edge_id = _view(g.d_edge_id, (ne,), "<i8", owner, device) if g.d_edge_id else None
         self.node_id = _view(g.d_node_id, (nn,), "<i8", owner, device) if g.d_node_id else None
-        # after remove_dead_paths on the sharded graph: the index each edge had when it was built (petgraph's adjacency order)
+        # after remove_dead_paths or a stage that may remove edges on the sharded graph: the index each edge had when it was
+        # built (petgraph's adjacency order)
         self.edge_age = _view(g.d_edge_age, (ne,), "<i8", owner, device) if g.d_edge_age else None
 
 
@@ -236,6 +237,32 @@ class ShardedBuilder(_ViewOwner):
         g, st = _lib.DistGraph(), _lib.PruneStats()
         _check(_lib.lib().katome_dist_remove_dead_paths(self._h, C.byref(g), C.byref(st), _stream()))
         return RankGraph(g, self, self.tdev), {f: getattr(st, f) for f, _ in _lib.PruneStats._fields_}
+
+    # ---- the stages after the first pruning on the sharded graph (katome_dist_*; first-seen order, shares not gathered) ----
+    def standardize_contigs(self):
+        """Standardizable::standardize_contigs (standardizer.rs:72-122) -> this rank's share"""
+        g = _lib.DistGraph()
+        _check(_lib.lib().katome_dist_standardize_contigs(self._h, C.byref(g), _stream()))
+        return RankGraph(g, self, self.tdev)
+
+    def prune_weak_edges(self, threshold):
+        """Clean::remove_weak_edges(threshold) (pruner.rs:84-93) at once, in petgraph's numbering -> this rank's share
+        (remove_weak_edges is the packed-key threshold applied when the edges are read out)"""
+        g = _lib.DistGraph()
+        _check(_lib.lib().katome_dist_prune_weak_edges(self._h, threshold, C.byref(g), _stream()))
+        return RankGraph(g, self, self.tdev)
+
+    def standardize_edges(self, original_genome_length, threshold):
+        """Standardizable::standardize_edges (standardizer.rs:42-70), then prune_weak_edges(1) -> this rank's share"""
+        g = _lib.DistGraph()
+        _check(_lib.lib().katome_dist_standardize_edges(self._h, original_genome_length, threshold, C.byref(g), _stream()))
+        return RankGraph(g, self, self.tdev)
+
+    def graph(self):
+        """this rank's share as it stands (katome_dist_current_graph)"""
+        g = _lib.DistGraph()
+        _check(_lib.lib().katome_dist_current_graph(self._h, C.byref(g)))
+        return RankGraph(g, self, self.tdev)
 
     def gather(self, root=0):
         """FIRST_SEEN_ORDER: the whole graph to `root` in the reference's index order -> on the root a builder on which
