@@ -84,7 +84,8 @@ enum Phase { PH_EXTRACT, PH_REGION_ORDER, PH_INSERT, PH_EMIT_EDGES, PH_SORT_EDGE
              PH_INSERT_TILES, PH_EXPAND_TILES, PH_EXPAND_MID, PH_FIRST_SEEN, PH_DEAD_PATHS, PH_SHRINK,
              K_SORT_SCATTER, K_SORT_HIST, K_RUN_SORT, K_HASH_SCATTER, K_HASH_HIST, K_OWNER_SCATTER, K_OWNER_HIST, K_PASS_OFFSETS,
              K_RECORDS, K_GROUP_INDEX, K_LDS_COUNT, K_SRC_IDS, K_DST_MERGE, K_EXPAND, K_SORT_SCATTER_KEYS, K_RUN_SORT_KEYS,
-             K_TILE_HASH_SCATTER, K_TILE_HASH_HIST, K_TILE_RECORDS, K_TILE_GROUP_INDEX, K_TILE_LDS_COUNT, K_HALF_MERGE, PH_COUNT };
+             K_TILE_HASH_SCATTER, K_TILE_HASH_HIST, K_TILE_RECORDS, K_TILE_GROUP_INDEX, K_TILE_LDS_COUNT, K_HALF_MERGE, K_GROUP_MERGE,
+             PH_COUNT };
 static const char* const PHASE_NAMES[PH_COUNT] = {
     "extract", "region_order", "insert", "emit_edges", "sort_edges", "node_set", "rank", "labels", "insert_tiles", "expand_tiles",
     "expand_mid_tiles", "first_seen_order", "remove_dead_paths", "shrink",
@@ -96,7 +97,8 @@ static const char* const PHASE_NAMES[PH_COUNT] = {
     "k:radix_scatter_kernel<RadixDigit> (keys only)", "k:run_sort (keys only)",
     // (the same kernels counting a TILE level by sorting -- other record sizes, so timed apart: TileLevelScope)
     "k:radix_scatter_kernel<HashDigit> (tile records)", "k:radix_hist_kernel<HashDigit> (tile records)", "k:tiles_to_records_kernel (tile records)",
-    "k:hash_group_index_kernel (tile records)", "k:lds_count_kernel (tile records)", "k:half_merge_kernel"};
+    "k:hash_group_index_kernel (tile records)", "k:lds_count_kernel (tile records)", "k:half_merge_kernel",
+    "k:group_merge_kernel"};
 struct Profiler {
     bool on = false;
     struct Ev { int phase; hipEvent_t a, b; uint64_t work; };      // work: elements the launch processed (K_* entries)
@@ -216,6 +218,14 @@ int dev_key_group_index(const uint64_t* d_keys, uint64_t n, uint32_t shift, uint
 int dev_half_merge(const uint64_t* a_key, const uint32_t* a_w, const uint64_t* a_first, const uint32_t* a_count, const uint64_t* a_off,
                    const uint64_t* b_key, const uint32_t* b_w, const uint64_t* b_first, uint64_t* out_key, uint32_t* out_w, uint64_t n_out,
                    hipStream_t stream);
+// the same without a sort of B: b_key / b_w only partitioned by the 16-bit prefix (dev_key_order), at most dev_group_merge_cap() keys
+// to a prefix (dev_key_group_max), weights below 2^16; B's groups are put in key order in LDS (radix.hip group_merge_kernel)
+uint32_t dev_group_merge_cap();
+int dev_group_merge(const uint64_t* a_key, const uint32_t* a_w, const uint64_t* a_first, const uint32_t* a_count, const uint64_t* a_off,
+                    const uint64_t* b_key, const uint32_t* b_w, const uint64_t* b_first, uint32_t k, uint64_t* out_key, uint32_t* out_w,
+                    uint64_t n_out, hipStream_t stream);
+// *d_out = the largest index[g + 1] - index[g], g < 65536 (the largest group of a dev_key_group_index)
+int dev_key_group_max(const uint64_t* d_index, uint64_t* d_out, hipStream_t stream);
 int dev_unique(uint64_t* d_keys, uint64_t n, uint32_t nw, uint64_t* n_out, hipStream_t stream);
 int dev_rank(const uint64_t* d_sorted, uint64_t n_sorted, uint32_t nw, uint32_t key_bits, const uint64_t* d_q, uint64_t nq,
              uint64_t* d_out, hipStream_t stream);
@@ -380,8 +390,9 @@ struct OwnerSplit {
     uint64_t base[KATOME_MAX_RANKS] = {0}, count[KATOME_MAX_RANKS] = {0};
 };
 // The k-mer level's ordered count (lds_count_ordered_kernel): S1, the representatives in key order with holes (s1_key / s1_w at
-// group_first[g], group_count[g] of them), and S2, their reverse complements in no order (n_s2).  half_sort_finish sorts S2 and merges
-// the two into the sorted edge list -- the arrays a sort of all edges gives -- and releases them.
+// group_first[g], group_count[g] of them), and S2, their reverse complements in no order (n_s2).  half_sort_finish orders S2 (per
+// 16-bit group inside the merge, or by a full sort) and merges the two into the sorted edge list -- the arrays a sort of all edges
+// gives -- and releases them.
 struct HalfSort {
     DevBuf s1_key, s1_w, group_first, group_count, s2_key, s2_w;
     uint64_t n_s1 = 0, n_s2 = 0;

@@ -9,6 +9,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "lds_order.h"
 
 namespace katome {
 
@@ -951,6 +952,121 @@ int dev_half_merge(const uint64_t* a_key, const uint32_t* a_w, const uint64_t* a
                    hipStream_t stream) {
     KernelScope ks(K_HALF_MERGE, stream, n_out);
     hipLaunchKernelGGL(half_merge_kernel, dim3(2048u), dim3(MT), 0, stream, a_key, a_w, a_first, a_count, a_off, b_key, b_w, b_first, out_key, out_w, n_out);
+    KCHECK_HIP(hipGetLastError());
+    return KATOME_OK;
+}
+
+// The same merge without a sort of B (KATOME_S2_GROUP_SORT): the reverse complements are only partitioned by their 16-bit prefix
+// (dev_key_order), b_first[g] .. b_first[g + 1] of group g in no order.  A workgroup takes group g and
+//   loads   its B keys into registers, GM_PER to a thread, as remainder << 16 | weight: 2k - 16 <= 46 bits of remainder, and a B
+//           weight is its representative's count, below 2^16 in the ordered count.  At most GM_CAP of them (the caller checks);
+//   orders  them in LDS with the count's read-out (lds_order.h -- the remainders of a group are distinct);
+//   merges  them with A[g], in the same form, through an LDS ring of GM_RING = 2 GM_STEP entries.  Every step places GM_STEP outputs
+//           (or what is left), GM_MI to a thread after a merge-path search; they are final when the ring holds GM_STEP unconsumed
+//           entries or A's end, since B is all in LDS (as in half_merge_kernel).  A is read GM_STEP entries ahead into registers:
+//           a block goes into the ring once there is room, and the next block's loads are in flight during the step's merge.
+// LDS: 160 KiB -- B (the last 16 words hold the scan's wave totals and the step's A count, so GM_CAP is 16 short of 16 Ki) and the
+// ring, whose first 4 KiB hold the buckets while B is ordered.  One workgroup of 1024 per CU.
+constexpr u32 GM_THREADS = LDS_ORDER_THREADS, GM_PER = 16, GM_WORDS = GM_THREADS * GM_PER, GM_CAP = GM_WORDS - 16;
+constexpr u32 GM_STEP = 2048, GM_RING = 2 * GM_STEP, GM_MI = GM_STEP / GM_THREADS, GM_PF = GM_STEP / GM_THREADS;
+constexpr size_t GM_LDS = ((size_t)GM_WORDS + GM_RING) * 8;
+static_assert(LDS_ORDER_BUCKETS * 2 <= GM_RING * 8 && GM_THREADS / 64 + 1 <= 2 * 16, "aliases in the merge's LDS");
+__global__ __launch_bounds__(GM_THREADS) void group_merge_kernel(const u64* __restrict__ a_key, const u32* __restrict__ a_w, const u64* __restrict__ a_first,
+                                                                   const u32* __restrict__ a_count, const u64* __restrict__ a_off, const u64* __restrict__ b_key,
+                                                                   const u32* __restrict__ b_w, const u64* __restrict__ b_first, u32 k,
+                                                                   u64* __restrict__ out_key, u32* __restrict__ out_w, u64 out_cap) {
+    extern __shared__ unsigned long long gm_mem[];
+    unsigned long long* bs = gm_mem;                                     // [GM_CAP]: the group's B in key order
+    u32* wtot = reinterpret_cast<u32*>(gm_mem + GM_CAP);                 // [GM_THREADS / 64]
+    u32* used_a = wtot + GM_THREADS / 64;
+    unsigned long long* ring = gm_mem + GM_WORDS;                        // [GM_RING]: A
+    u32* bucket = reinterpret_cast<u32*>(ring);                          // [LDS_ORDER_BUCKETS / 2], while B is ordered
+    const u32 tid = threadIdx.x;
+    const u32 rem_bits = 2 * k - 16, bshift = rem_bits > 11 ? rem_bits - 11 : 0;            // (bucket: the remainder's top 11 bits)
+    const u64 REM = (1ull << rem_bits) - 1;
+    for (u32 g = blockIdx.x; g < (1u << 16); g += gridDim.x) {
+        const u64 b0 = b_first[g], a0 = a_first[g];
+        const u32 na = a_count[g], nb = (u32)(b_first[g + 1] - b0);
+        const u64* ap = a_key + a0; const u32* awp = a_w + a0;
+        u64 o = a_off[g] + b0;
+        unsigned long long v[GM_PER]; u32 keep = 0;
+#pragma unroll
+        for (u32 j = 0; j < GM_PER; ++j) {
+            const u32 i = tid + j * GM_THREADS;
+            v[j] = 0;
+            if (i < nb) { v[j] = ((b_key[b0 + i] & REM) << 16) | b_w[b0 + i]; keep |= 1u << j; }
+        }
+        bucket[tid] = 0u;
+        __syncthreads();                                  // (the last group's merge is done with the ring and bs)
+        lds_order_entries<GM_PER>(v, keep, bs, bucket, wtot, bshift, [](u32) {});
+        // A's next block [la, la + pn) in registers
+        u64 pk[GM_PF]; u32 pw[GM_PF];
+        u32 ca = 0, cb = 0, la = 0, pn = na < GM_STEP ? na : GM_STEP;          // A consumed and in the ring, B consumed
+#pragma unroll
+        for (u32 r = 0; r < GM_PF; ++r) { const u32 i = tid + r * GM_THREADS; if (i < pn) { pk[r] = ap[i]; pw[r] = awp[i]; } }
+        while (ca < na || cb < nb) {
+            if (pn && la - ca + pn <= GM_RING) {          // (otherwise more than GM_STEP are in the ring already)
+#pragma unroll
+                for (u32 r = 0; r < GM_PF; ++r) {
+                    const u32 i = tid + r * GM_THREADS;
+                    if (i < pn) ring[(la + i) & (GM_RING - 1)] = ((pk[r] & REM) << 16) | pw[r];
+                }
+                la += pn;
+                pn = na - la < GM_STEP ? na - la : GM_STEP;
+#pragma unroll
+                for (u32 r = 0; r < GM_PF; ++r) { const u32 i = tid + r * GM_THREADS; if (i < pn) { pk[r] = ap[la + i]; pw[r] = awp[la + i]; } }
+            }
+            __syncthreads();
+            const u32 va = la - ca, vb = nb - cb, c = va + vb < GM_STEP ? va + vb : GM_STEP;
+            const u32 d0 = tid * GM_MI;
+            if (d0 < c) {
+                // merge path: the number of A entries among the first d0 outputs
+                u32 lo = d0 > vb ? d0 - vb : 0, hi = d0 < va ? d0 : va;
+                while (lo < hi) {
+                    const u32 m = (lo + hi) >> 1;
+                    if (ring[(ca + m) & (GM_RING - 1)] < bs[cb + d0 - m - 1]) lo = m + 1; else hi = m;
+                }
+                u32 i = lo, j = d0 - lo;
+                const u32 d1 = d0 + GM_MI < c ? d0 + GM_MI : c;
+                for (u32 d = d0; d < d1; ++d) {
+                    unsigned long long e;
+                    if (i < va && (j >= vb || ring[(ca + i) & (GM_RING - 1)] < bs[cb + j])) e = ring[(ca + i++) & (GM_RING - 1)];
+                    else e = bs[cb + j++];
+                    if (o + d < out_cap) { out_key[o + d] = ((u64)g << rem_bits) | (e >> 16); out_w[o + d] = (u32)e & 0xFFFFu; }
+                }
+                if (d1 == c) *used_a = i;                     // (the thread that places the step's last output)
+            }
+            __syncthreads();
+            const u32 ua = *used_a;
+            ca += ua; cb += c - ua; o += c;
+            __syncthreads();                                  // (used_a is read before the next step's last thread writes it)
+        }
+    }
+}
+uint32_t dev_group_merge_cap() { return GM_CAP; }
+int dev_group_merge(const uint64_t* a_key, const uint32_t* a_w, const uint64_t* a_first, const uint32_t* a_count, const uint64_t* a_off,
+                    const uint64_t* b_key, const uint32_t* b_w, const uint64_t* b_first, uint32_t k, uint64_t* out_key, uint32_t* out_w,
+                    uint64_t n_out, hipStream_t stream) {
+    if (k < 9 || 2 * k > 62) { set_error("group merge: k = %u", k); return KATOME_E_ARG; }
+    KCHECK_HIP(hipFuncSetAttribute((const void*)group_merge_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GM_LDS));
+    KernelScope ks(K_GROUP_MERGE, stream, n_out);
+    hipLaunchKernelGGL(group_merge_kernel, dim3(256u), dim3(GM_THREADS), GM_LDS, stream, a_key, a_w, a_first, a_count, a_off, b_key, b_w, b_first, k,
+                       out_key, out_w, n_out);
+    KCHECK_HIP(hipGetLastError());
+    return KATOME_OK;
+}
+
+__global__ __launch_bounds__(BLOCK) void key_group_max_kernel(const u64* __restrict__ index, unsigned long long* __restrict__ out) {
+    unsigned long long m = 0;
+    for (u32 g = blockIdx.x * BLOCK + threadIdx.x; g < (1u << 16); g += gridDim.x * BLOCK) m = max(m, (unsigned long long)(index[g + 1] - index[g]));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned long long)__shfl_xor(m, o, 64));
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
+}
+int dev_key_group_max(const uint64_t* d_index, uint64_t* d_out, hipStream_t stream) {
+    KCHECK_HIP(hipMemsetAsync(d_out, 0, 8, stream));
+    KernelScope ks(K_GROUP_INDEX, stream, 1ull << 16);
+    hipLaunchKernelGGL(key_group_max_kernel, dim3(64u), dim3(BLOCK), 0, stream, d_index, reinterpret_cast<unsigned long long*>(d_out));
     KCHECK_HIP(hipGetLastError());
     return KATOME_OK;
 }

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "common.h"
+#include "lds_order.h"
 
 namespace katome {
 
@@ -1016,9 +1017,10 @@ __global__ __launch_bounds__(LC_THREADS) void lds_count_packed_kernel(const u64*
 //   S1, the representatives, ascending, from the group's first record on (s1_key + index[g]: fixed before the count, so the groups
 //       stay in key order; a group has no more distinct keys than records), their number in group_count[g];
 //   S2 (both strands), their reverse complements, behind a cursor in no order.
-// half_merge_kernel (radix.hip) merges S1 with S2 once S2 is sorted.  err 5 / err 3 as in lds_count_packed_kernel: the caller then
-// counts the usual way.
-constexpr u32 LO_BUCKETS = 2 * LC_THREADS;                           // (two 16-bit counters to a word, one word per thread in the scan)
+// group_merge_kernel (radix.hip) orders S2 group by group and merges it with S1 (half_merge_kernel when S2 is sorted in full).
+// err 5 / err 3 as in lds_count_packed_kernel: the caller then counts the usual way.
+constexpr u32 LO_BUCKETS = LDS_ORDER_BUCKETS;
+static_assert(LC_THREADS == LDS_ORDER_THREADS, "the read-out orders with lds_order.h");
 template <bool RC>
 __global__ __launch_bounds__(LC_THREADS) void lds_count_ordered_kernel(const u64* keys, const u32* wts, const u64* __restrict__ index, u32 k,
                                                                         u32 min_weight, u64* s1_key, u32* s1_w, u32* group_count, u64* s2_key,
@@ -1029,7 +1031,7 @@ __global__ __launch_bounds__(LC_THREADS) void lds_count_ordered_kernel(const u64
     u32* bucket = reinterpret_cast<u32*>(lc_mem + LP_SLOTS);             // [LO_BUCKETS / 2]: counters of buckets 2i (low half), 2i + 1
     __shared__ u32 wtot[LC_THREADS / 64];
     __shared__ unsigned long long base_sh;
-    const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const u32 tid = threadIdx.x, lane = tid & 63;
     const u32 rem_bits = 2 * k - 16, bshift = rem_bits > 11 ? rem_bits - 11 : 0;            // (bucket: the remainder's top 11 bits)
     const u64 REM = (1ull << rem_bits) - 1;
     u32 my_distinct = 0;
@@ -1089,54 +1091,10 @@ __global__ __launch_bounds__(LC_THREADS) void lds_count_ordered_kernel(const u64
             v[j] = slot[tid * LP_PER + j];
             if (v[j]) { ++my_distinct; if (((u32)v[j] & 0xFFFFu) >= min_weight) keep |= 1u << j; }      // Clean::remove_weak_edges
         }
-        // (2048 buckets of 16-bit counters, two to a word: a group holds at most LP_SLOTS < 2^16 keys, so no half carries into the other)
-#pragma unroll
-        for (u32 j = 0; j < LP_PER; ++j) {
-            if (!((keep >> j) & 1u)) continue;
-            const u32 b = (u32)((v[j] >> 16) >> bshift);
-            atomicAdd(&bucket[b >> 1], 1u << ((b & 1u) * 16u));
-        }
-        __syncthreads();
-        const u32 pair = bucket[tid], lo_cnt = pair & 0xFFFFu, cnt = lo_cnt + (pair >> 16);
-        u32 incl = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { u32 t = __shfl_up(incl, o, 64); if (lane >= (u32)o) incl += t; }
-        if (lane == 63) wtot[wave] = incl;
-        __syncthreads();
-        u32 woff = 0, total = 0;
-#pragma unroll
-        for (u32 w = 0; w < LC_THREADS / 64; ++w) { if (w < wave) woff += wtot[w]; total += wtot[w]; }
-        const u32 start = woff + incl - cnt;
-        bucket[tid] = start | ((start + lo_cnt) << 16);
-        if (tid == 0) { group_count[g] = total; base_sh = total ? atomicAdd(cursor, (unsigned long long)total) : 0ull; }
-        __syncthreads();
-#pragma unroll
-        for (u32 j = 0; j < LP_PER; ++j) {
-            if (!((keep >> j) & 1u)) continue;
-            const u32 b = (u32)((v[j] >> 16) >> bshift), sh = (b & 1u) * 16u;
-            slot[(atomicAdd(&bucket[b >> 1], 1u << sh) >> sh) & 0xFFFFu] = v[j];
-        }
-        __syncthreads();
-        // bucket b now spans [end(b - 1), end(b)).  A key's place in key order is its bucket's start plus the keys of its bucket
-        // below it (distinct remainders, so the whole entries compare as keys): independent reads of half a dozen entries -- an insertion
-        // sort per bucket instead was a chain of dependent LDS round trips that every wave waited out for its longest bucket, 62 % of
-        // the kernel (profiles/r05_half_sort.md)
-        u32 pos[LP_PER];
-#pragma unroll
-        for (u32 j = 0; j < LP_PER; ++j) {
-            pos[j] = 0;
-            if (!((keep >> j) & 1u)) continue;
-            const u32 b = (u32)((v[j] >> 16) >> bshift), e = (bucket[b >> 1] >> ((b & 1u) * 16u)) & 0xFFFFu;
-            u32 r = b ? (bucket[(b - 1) >> 1] >> (((b - 1) & 1u) * 16u)) & 0xFFFFu : 0u;
-            const u32 s0 = r;
-#pragma unroll 4
-            for (u32 i = s0; i < e; ++i) r += slot[i] < v[j] ? 1u : 0u;
-            pos[j] = r;
-        }
-        __syncthreads();
-#pragma unroll
-        for (u32 j = 0; j < LP_PER; ++j) if ((keep >> j) & 1u) slot[pos[j]] = v[j];
-        __syncthreads();
+        // the kept ones into key order in the table's LDS (lds_order.h); the group's S2 room is reserved once their number is known
+        const u32 total = lds_order_entries<LP_PER>(v, keep, slot, bucket, wtot, bshift, [&](u32 t) {
+            if (tid == 0) { group_count[g] = t; base_sh = t ? atomicAdd(cursor, (unsigned long long)t) : 0ull; }
+        });
         LC_PHASE(14);
         for (u32 i = tid; i < total; i += LC_THREADS) {
             const unsigned long long e = slot[i];
@@ -2476,19 +2434,61 @@ static int ordered_count(DevBuf& keys, DevBuf& weights, uint64_t n, uint32_t k, 
     return KATOME_OK;
 }
 
+// KATOME_S2_GROUP_SORT=0: S2 sorted in full and half_merge_kernel, as before group_merge_kernel.  KATOME_S2_GROUP_CAP=n: groups of more
+// than n keys (and always more than the kernel's LDS holds) take that route too -- tests of the way back
+static bool s2_group_sort_on() {
+    static const bool on = !getenv("KATOME_S2_GROUP_SORT") || atoi(getenv("KATOME_S2_GROUP_SORT")) != 0;
+    return on;
+}
+static uint64_t s2_group_cap() {
+    static const uint64_t cap = [] {
+        const char* e = getenv("KATOME_S2_GROUP_CAP");
+        const uint64_t c = e ? strtoull(e, nullptr, 10) : UINT64_MAX;
+        return std::min<uint64_t>(c, dev_group_merge_cap());
+    }();
+    return cap;
+}
+
+// S2 ordered per 16-bit group only, in LDS inside the merge (group_merge_kernel), when its largest group fits: two partition passes
+// instead of four and no run sort.  Otherwise, or with KATOME_S2_GROUP_SORT=0, S2 is sorted in full and half_merge_kernel merges it
+// (a full sort of the partitioned S2 leaves the same groups, so b_first stands).
 int half_sort_finish(HalfSort& hs, DevBuf& edge_key, DevBuf& edge_weight, hipStream_t stream) {
     if (!hs.taken) { set_error("half sort: no ordered count to finish"); return KATOME_E_ARG; }
     const uint32_t k = hs.k;
-    if (hs.n_s2) KCHECK(dev_sort_bufs(hs.s2_key, &hs.s2_w, hs.n_s2, 1, 2 * k, stream, true));
     DevBuf b_first(stream), a_off(stream);
     KCHECK(b_first.alloc(((1ull << 16) + 1) * 8)); KCHECK(a_off.alloc(((1ull << 16) + 1) * 8));
-    if (hs.n_s2) KCHECK(dev_key_group_index(hs.s2_key.as<u64>(), hs.n_s2, 2 * k - 16, b_first.as<u64>(), stream));
-    else KCHECK_HIP(hipMemsetAsync(b_first.p, 0, b_first.bytes, stream));
+    bool grouped = false;
+    if (hs.n_s2 && s2_group_sort_on()) {
+        {
+            DevBuf tk(stream), tw(stream);
+            KCHECK(tk.alloc((hs.n_s2 + 1) * 8)); KCHECK(tw.alloc((hs.n_s2 + 1) * 4));
+            const u64* ko = nullptr; const u32* wo = nullptr;
+            KCHECK(dev_key_order(hs.s2_key.as<u64>(), hs.s2_w.as<u32>(), hs.n_s2, k, tk.as<u64>(), hs.s2_key.as<u64>(), tw.as<u32>(),
+                                 hs.s2_w.as<u32>(), &ko, &wo, stream));
+        }
+        KCHECK(dev_key_group_index(hs.s2_key.as<u64>(), hs.n_s2, 2 * k - 16, b_first.as<u64>(), stream));
+        KCHECK(dev_key_group_max(b_first.as<u64>(), a_off.as<u64>(), stream));      // (a_off: scratch until the scan below)
+        uint64_t largest = 0;
+        KCHECK_HIP(hipMemcpyAsync(&largest, a_off.p, 8, hipMemcpyDeviceToHost, stream));
+        KCHECK_HIP(hipStreamSynchronize(stream));
+        grouped = largest <= s2_group_cap();
+        if (getenv("KATOME_LC_TRACE"))
+            fprintf(stderr, "[half sort] S2: %llu keys, largest group %llu: %s\n", (unsigned long long)hs.n_s2, (unsigned long long)largest,
+                    grouped ? "ordered per group in the merge" : "too large for the merge's LDS; sorted in full");
+        if (!grouped) KCHECK(dev_sort_bufs(hs.s2_key, &hs.s2_w, hs.n_s2, 1, 2 * k, stream, true));
+    } else if (hs.n_s2) {
+        KCHECK(dev_sort_bufs(hs.s2_key, &hs.s2_w, hs.n_s2, 1, 2 * k, stream, true));
+        KCHECK(dev_key_group_index(hs.s2_key.as<u64>(), hs.n_s2, 2 * k - 16, b_first.as<u64>(), stream));
+    } else KCHECK_HIP(hipMemsetAsync(b_first.p, 0, b_first.bytes, stream));
     KCHECK(dev_scan_counts(hs.group_count.as<u32>(), 1ull << 16, a_off.as<u64>(), stream));
     const uint64_t n_out = hs.n_s1 + hs.n_s2;
     KCHECK(edge_key.alloc((n_out + 1) * 8, stream)); KCHECK(edge_weight.alloc((n_out + 1) * 4, stream));
-    KCHECK(dev_half_merge(hs.s1_key.as<u64>(), hs.s1_w.as<u32>(), hs.group_first.as<u64>(), hs.group_count.as<u32>(), a_off.as<u64>(),
-                          hs.s2_key.as<u64>(), hs.s2_w.as<u32>(), b_first.as<u64>(), edge_key.as<u64>(), edge_weight.as<u32>(), n_out, stream));
+    if (grouped)
+        KCHECK(dev_group_merge(hs.s1_key.as<u64>(), hs.s1_w.as<u32>(), hs.group_first.as<u64>(), hs.group_count.as<u32>(), a_off.as<u64>(),
+                               hs.s2_key.as<u64>(), hs.s2_w.as<u32>(), b_first.as<u64>(), k, edge_key.as<u64>(), edge_weight.as<u32>(), n_out, stream));
+    else
+        KCHECK(dev_half_merge(hs.s1_key.as<u64>(), hs.s1_w.as<u32>(), hs.group_first.as<u64>(), hs.group_count.as<u32>(), a_off.as<u64>(),
+                              hs.s2_key.as<u64>(), hs.s2_w.as<u32>(), b_first.as<u64>(), edge_key.as<u64>(), edge_weight.as<u32>(), n_out, stream));
     hs.release();
     return KATOME_OK;
 }
