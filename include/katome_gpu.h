@@ -483,6 +483,19 @@ void katome_dist_destroy(katome_dist_builder *d);
  * again with the reads that follow.                                                                           */
 int  katome_dist_add_reads(katome_dist_builder *d, const uint8_t *d_packed, uint64_t first_read, uint64_t n_reads,
                            uint32_t read_len, const uint8_t *d_skip, uint64_t batch_reads, void *stream);
+/* this rank's reads of VARYING length, device pointers in katome_dev_extract_var's layout: read r is len[r] bases at byte
+ * byte_off[r] of d_packed (2 bits per base, packed_bytes in all).  first_window: the global window index of this rank's
+ * first read -- the sum of len - k + 1 over every read before it in input order (the reference's numbering needs it, as the
+ * fixed-length entry needs first_read); it is the same on every call of a rank: a later call continues with the reads that
+ * follow, after the windows of this rank's earlier calls.  Batches of about batch_windows windows (0 = default).
+ * Collective, every call (a rank without reads calls with n_reads = 0): the first call agrees one tile span from all ranks'
+ * reads; a read shorter than k gives KATOME_E_SHORT_READ, and any failure the same error, on every rank.  In first-seen
+ * order a build takes either this entry or katome_dist_add_reads (KATOME_E_UNSUPPORTED for the mix); by packed key both,
+ * except after a batch of one length that planned the supermer route (KATOME_E_UNSUPPORTED).  Routes "local" and "tiles";
+ * with KATOME_DIST_ROUTE=supermers these reads plan the tiles route, which later batches of one length then take.
+ * batch_windows is capped at 2^31 (a batch's records are indexed by 32 bits).                                        */
+int  katome_dist_add_reads_var(katome_dist_builder *d, const uint8_t *d_packed, uint64_t packed_bytes, const uint64_t *d_byte_off,
+                               const uint32_t *d_len, uint64_t n_reads, uint64_t first_window, uint64_t batch_windows, void *stream);
 /* Clean::remove_weak_edges(threshold) when the edges are read out (by packed key only; see katome_dev_remove_weak_edges) */
 int  katome_dist_remove_weak_edges(katome_dist_builder *d, uint32_t threshold);
 int  katome_dist_finalize(katome_dist_builder *d, katome_dist_graph *out, void *stream);

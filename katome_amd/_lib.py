@@ -165,6 +165,7 @@ SYMBOLS = {
     "katome_dist_create": (_i, [C.POINTER(Settings), _vp, C.POINTER(_vp)]),
     "katome_dist_destroy": (None, [_vp]),
     "katome_dist_add_reads": (_i, [_vp, _vp, _u64, _u64, _u32, _vp, _u64, _vp]),
+    "katome_dist_add_reads_var": (_i, [_vp, _vp, _u64, _vp, _vp, _u64, _u64, _u64, _vp]),
     "katome_dist_remove_weak_edges": (_i, [_vp, _u32]),
     "katome_dist_finalize": (_i, [_vp, C.POINTER(DistGraph), _vp]),
     "katome_dist_gather": (_i, [_vp, _i, C.POINTER(_vp), _vp]),

@@ -1912,13 +1912,14 @@ extern "C" {
 }  // extern "C"
 
 // settings.n_devices > 1: the sharded build (dist.hip) with the ranks as host threads of this call, one per GPU.  Reads are
-// split contiguously by index; every rank copies its own share to its GPU.  By packed key the host arrays are the ranks'
-// shares one after the other (every rank copies its slice out itself); in the reference's numbering every rank puts its
-// share at its indices.  The stages after the build (d, c, w, e) run on the sharded graph (dist_prune.hip, dist_stages.hip)
-// with KATOME_DIST_STAGES=sharded or when the graph cannot be gathered (2^32 edges or nodes and more); otherwise, and with
-// KATOME_DIST_STAGES=gather, the graph is gathered to the first GPU, where they run.  shrink always gathers.
-static int build_packed_multi(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len,
-                              const uint8_t* skip, const Finish& finish, uint64_t read_bytes) {
+// split contiguously by index; every rank copies its own share to its GPU (`add_reads(rank, world, builder, stream)`: fixed- or
+// variable-length reads).  By packed key the host arrays are the ranks' shares one after the other (every rank copies its slice
+// out itself); in the reference's numbering every rank puts its share at its indices.  The stages after the build (d, c, w, e)
+// run on the sharded graph (dist_prune.hip, dist_stages.hip) with KATOME_DIST_STAGES=sharded or when the graph cannot be
+// gathered (2^32 edges or nodes and more); otherwise, and with KATOME_DIST_STAGES=gather, the graph is gathered to the first
+// GPU, where they run.  shrink always gathers.
+template <class AddReads>
+static int build_multi(const katome_settings* s, const Finish& finish, uint64_t read_bytes, const AddReads& add_reads) {
     const int n = s->n_devices;
     const bool share = (s->flags & KATOME_FLAG_RANKS_SHARE_DEVICE) != 0, first_seen = (s->flags & KATOME_FLAG_FIRST_SEEN_ORDER) != 0;
     if (n > KATOME_MAX_RANKS) { set_error("n_devices = %d: at most %d", n, KATOME_MAX_RANKS); return KATOME_E_UNSUPPORTED; }
@@ -1954,7 +1955,6 @@ static int build_packed_multi(const katome_settings* s, const uint8_t* packed, u
         uint64_t total_edges = 0, total_nodes = 0;
     } sh;
     sh.rc.assign(n, KATOME_OK); sh.err.resize(n); sh.n_edges.assign(n, 0); sh.node_base.assign(n, 0); sh.n_nodes.assign(n, 0);
-    const uint32_t stride = (read_len + 3) / 4;
     auto body = [&](int r) -> int {
         KCHECK(use_device(devices[r]));
         hipStream_t stream = nullptr;
@@ -1965,17 +1965,7 @@ static int build_packed_multi(const katome_settings* s, const uint8_t* packed, u
         int rc = katome_dist_create(&mine, comms[r], &d);
         do {
             if (rc) break;
-            uint64_t first = 0, cnt = 0;
-            katome_shard_range(n_reads, (uint32_t)n, (uint32_t)r, &first, &cnt);
-            DevBuf d_packed(stream), d_skip(stream);
-            if ((rc = d_packed.alloc(cnt * stride + 32))) break;
-            if (cnt && hipMemcpyAsync(d_packed.p, packed + first * stride, cnt * stride, hipMemcpyHostToDevice, stream) != hipSuccess) { set_error("H2D copy failed"); rc = KATOME_E_DEVICE; break; }
-            if (skip) {
-                if ((rc = d_skip.alloc(cnt + 16))) break;
-                if (cnt && hipMemcpyAsync(d_skip.p, skip + first, cnt, hipMemcpyHostToDevice, stream) != hipSuccess) { set_error("H2D copy failed"); rc = KATOME_E_DEVICE; break; }
-            }
-            if ((rc = katome_dist_add_reads(d, d_packed.as<uint8_t>(), first, cnt, read_len, skip ? d_skip.as<uint8_t>() : nullptr, 0, stream))) break;
-            d_packed.release(); d_skip.release();
+            if ((rc = add_reads(r, n, d, stream))) break;
             // a rank whose reads could not be taken (memory, reads the route does not take) must not leave the others waiting inside
             // finalize's exchange: everybody meets here first, and a failed rank has poisoned the meeting
             if (!sync->barrier()) { set_error("another rank of this build failed"); rc = KATOME_E_DEVICE; break; }
@@ -2115,6 +2105,54 @@ static int build_packed_multi(const katome_settings* s, const uint8_t* packed, u
         else katome_graph_free(&sh.owner->g);
     }
     return rc;
+}
+
+static int build_packed_multi(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len,
+                              const uint8_t* skip, const Finish& finish, uint64_t read_bytes) {
+    const uint32_t stride = (read_len + 3) / 4;
+    return build_multi(s, finish, read_bytes, [&](int r, int n, katome_dist_builder* d, hipStream_t stream) -> int {
+        uint64_t first = 0, cnt = 0;
+        katome_shard_range(n_reads, (uint32_t)n, (uint32_t)r, &first, &cnt);
+        DevBuf d_packed(stream), d_skip(stream);
+        KCHECK(d_packed.alloc(cnt * stride + 32));
+        if (cnt && hipMemcpyAsync(d_packed.p, packed + first * stride, cnt * stride, hipMemcpyHostToDevice, stream) != hipSuccess) { set_error("H2D copy failed"); return KATOME_E_DEVICE; }
+        if (skip) {
+            KCHECK(d_skip.alloc(cnt + 16));
+            if (cnt && hipMemcpyAsync(d_skip.p, skip + first, cnt, hipMemcpyHostToDevice, stream) != hipSuccess) { set_error("H2D copy failed"); return KATOME_E_DEVICE; }
+        }
+        return katome_dist_add_reads(d, d_packed.as<uint8_t>(), first, cnt, read_len, skip ? d_skip.as<uint8_t>() : nullptr, 0, stream);
+    });
+}
+
+// Reads of varying length on the sharded route: split contiguously by index, every rank copies its slice (its bytes, its byte
+// offsets rebased to the slice, its lengths) and starts at the global window of its first read.  Every rank takes part in the
+// collective katome_dist_add_reads_var, a rank without reads too.
+static int build_var_multi(const katome_settings* s, const HostReads& hr, const Finish& finish) {
+    const int n = s->n_devices;
+    std::vector<uint64_t> first_window(std::max(n, 1) + 1, 0);
+    for (int r = 0; r < n; ++r) {                        // (each rank's window offset: the windows of the ranks before it)
+        uint64_t first = 0, cnt = 0, w = 0;
+        katome_shard_range(hr.n_reads, (uint32_t)n, (uint32_t)r, &first, &cnt);
+        for (uint64_t i = first; i < first + cnt; ++i) w += hr.len[i] >= s->k ? hr.len[i] - s->k + 1 : 0;
+        first_window[r + 1] = first_window[r] + w;
+    }
+    // (KATOME_DIST_VAR_BATCH_WINDOWS: tests -- many small batches)
+    const uint64_t batch = getenv("KATOME_DIST_VAR_BATCH_WINDOWS") ? strtoull(getenv("KATOME_DIST_VAR_BATCH_WINDOWS"), nullptr, 10) : 0;
+    return build_multi(s, finish, hr.read_bytes, [&](int r, int n, katome_dist_builder* d, hipStream_t stream) -> int {
+        uint64_t first = 0, cnt = 0;
+        katome_shard_range(hr.n_reads, (uint32_t)n, (uint32_t)r, &first, &cnt);
+        const uint64_t b0 = hr.byte_off[first], bytes = hr.byte_off[first + cnt] - b0;
+        std::vector<uint64_t> off(cnt + 1, 0);
+        for (uint64_t i = 0; i < cnt; ++i) off[i] = hr.byte_off[first + i] - b0;
+        off[cnt] = bytes;
+        DevBuf d_packed(stream), d_off(stream), d_len(stream);
+        KCHECK(d_packed.alloc(bytes + 32)); KCHECK(d_off.alloc((cnt + 1) * 8)); KCHECK(d_len.alloc(cnt * 4 + 16));
+        if (cnt && (hipMemcpyAsync(d_packed.p, hr.packed + b0, bytes, hipMemcpyHostToDevice, stream) != hipSuccess ||
+                    hipMemcpyAsync(d_off.p, off.data(), (cnt + 1) * 8, hipMemcpyHostToDevice, stream) != hipSuccess ||
+                    hipMemcpyAsync(d_len.p, hr.len + first, cnt * 4, hipMemcpyHostToDevice, stream) != hipSuccess)) { set_error("H2D copy failed"); return KATOME_E_DEVICE; }
+        // (the copies come from pageable host memory the call owns until it returns; the reads are taken before that)
+        return katome_dist_add_reads_var(d, d_packed.as<uint8_t>(), bytes, d_off.as<u64>(), d_len.as<u32>(), cnt, first_window[r], batch, stream);
+    });
 }
 
 static int build_packed_impl(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len,
@@ -2262,6 +2300,11 @@ static int build_files_impl(const katome_settings* s, const char* const* paths, 
         return rc;
     }
     if (hr.fixed_len) return build_packed_impl(s, hr.packed, hr.n_reads, hr.fixed_len, nullptr, finish, &hr.read_bytes);
+    // reads of unequal length over several GPUs (or, KATOME_FORCE_SHARDED=1, one GPU as a world of one rank): the sharded route
+    if (hr.n_reads && (s->n_devices > 1 || (s->n_devices == 1 && getenv("KATOME_FORCE_SHARDED")))) {
+        KCHECK(check_k(s->k));
+        return build_var_multi(s, hr, finish);
+    }
     katome_builder* b = nullptr;
     KCHECK(katome_builder_create(s, &b));
     int rc = KATOME_OK;

@@ -16,6 +16,8 @@
 //      input, owners keep the earliest sequence number per k-mer and strand, and edges and nodes get their GLOBAL rank
 //      among all ranks' sequence numbers (global_rank: range partition by splitters from a merged histogram, local sort,
 //      ranks back over the mirrored exchange) -- the same indices whatever the number of ranks.
+// Reads of varying length (katome_dist_add_reads_var) take the same routes: the span is agreed from all ranks' reads, and on the
+// tiles route in first-seen order the sender resolves every record's two sequence numbers before it leaves.
 // The stages of assemble_with_graph that walk petgraph's adjacency and swap_remove by index (pruner.rs:36-82) need the whole
 // graph in index order: katome_dist_gather brings it to one rank, where prune.hip runs unchanged.
 #include <algorithm>
@@ -25,6 +27,7 @@
 
 #include <cstring>
 #include "dist_builder.h"
+#include "seq_pair.h"
 
 const char* const XPHASE_NAMES[X_COUNT] = {"exchange_records", "exchange_kmers", "exchange_targets", "exchange_ids",
                                            "rank_nodes", "rank_edges", "gather", "exchange_mid_tiles", "prune"};
@@ -131,6 +134,74 @@ __global__ __launch_bounds__(BLOCK) void scatter_const_kernel(const u32* __restr
     KLOOP(j, b - a) out[pos[a + j]] = v;
 }
 
+// ---- reads of varying length (katome_dist_add_reads_var) ----------------------------------------------------------------
+constexpr int VAR_SPANS = 32;                // the candidate tile spans 2..33 (build_files_impl's plan)
+// per read its windows (0 for a read shorter than k); over all reads: [0] how many are shorter than k, [s - 1] the insertions
+// span s costs -- whole tiles + the windows left over, + 4 per read for a span whose tiles cannot be broken into mid tiles
+__global__ __launch_bounds__(BLOCK) void var_stats_kernel(const u32* __restrict__ len, u64 n, u32 k, u32* __restrict__ wcount,
+                                                          unsigned long long* __restrict__ stats) {
+    u64 acc[VAR_SPANS + 1];
+#pragma unroll
+    for (int j = 0; j <= VAR_SPANS; ++j) acc[j] = 0;
+    KLOOP(r, n) {
+        const u32 L = len[r], W = L >= k ? L - k + 1 : 0;
+        wcount[r] = W;
+        acc[0] += L < k;
+#pragma unroll
+        for (u32 sp = 2; sp < 2 + VAR_SPANS; ++sp) {
+            const bool breakable = sp <= 16 || sp % 3 == 0 || sp % 4 == 0 || sp % 5 == 0 || sp % 6 == 0 || sp % 7 == 0 || sp % 8 == 0;
+            acc[sp - 1] += W / sp + W % sp + (breakable ? 0 : 4);
+        }
+    }
+    // (the wave's sums, then the block's in LDS: one atomic per value and block, and the grid is capped at 1024 blocks)
+    __shared__ u64 part[BLOCK / 64][VAR_SPANS + 1];
+#pragma unroll
+    for (int j = 0; j <= VAR_SPANS; ++j) {
+        u64 v = acc[j];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][j] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x <= VAR_SPANS) {
+        u64 v = 0;
+#pragma unroll
+        for (int w = 0; w < BLOCK / 64; ++w) v += part[w][threadIdx.x];
+        if (v) atomicAdd(&stats[threadIdx.x], (unsigned long long)v);
+    }
+}
+// batch b of a call holds reads [out[2b], out[2b + 2]): batch b starts at the first read whose window prefix reaches b * per_batch
+// (so a batch holds at most per_batch windows + one read's); out[2b + 1]: the windows before it
+__global__ __launch_bounds__(BLOCK) void var_bounds_kernel(const u64* __restrict__ pref, u64 n, u64 per_batch, u64 nb, u64* __restrict__ out) {
+    KLOOP(bt, nb + 1) {
+        u64 r = n;
+        if (bt < nb) {
+            const u64 want = bt * per_batch;
+            u64 lo = 0, hi = n;                    // first r in [0, n] with pref[r] >= want (pref[n] = all windows > want)
+            while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (pref[mid] >= want) hi = mid; else lo = mid + 1; }
+            r = lo;
+        }
+        out[2 * bt] = r; out[2 * bt + 1] = pref[r];
+    }
+}
+// a batch's whole tiles and left-over windows per read
+__global__ __launch_bounds__(BLOCK) void var_split_kernel(const u32* __restrict__ wcount, u64 n, u32 span, u32* __restrict__ tiles,
+                                                          u32* __restrict__ rest) {
+    KLOOP(r, n) { const u32 W = wcount[r]; tiles[r] = W / span; rest[r] = W % span; }
+}
+// The sender's side of the tiles route in first-seen order: the owner of a record cannot tell where in the input it sits (the
+// reads' lengths stay with the sender), so every record, already grouped by owner, turns its index in this rank's batch into
+// its two sequence numbers (as cut, its reverse complement); they travel beside it and the owner takes them as they are.
+__global__ __launch_bounds__(BLOCK) void var_pairs_kernel(const u32* __restrict__ pidx, u64 n, const u64* __restrict__ win_prefix,
+                                                          const u64* __restrict__ rec_prefix, u64 n_reads, u32 mode, u32 span, u64 seq_base,
+                                                          u64* __restrict__ pairs) {
+    KLOOP(j, n) {
+        u64 P, Q;
+        var_seq_pair(win_prefix, rec_prefix, n_reads, mode, span, seq_base, pidx[j], P, Q);
+        *reinterpret_cast<ulonglong2*>(pairs + 2 * j) = make_ulonglong2(P, Q);
+    }
+}
+
 uint64_t sum(const std::vector<uint64_t>& v) { uint64_t t = 0; for (uint64_t x : v) t += x; return t; }
 
 // KATOME_DIST_TRACE=1: order-free checksum of a device array of u64 words at the checkpoints of a sharded build (stderr)
@@ -190,6 +261,51 @@ int route_and_insert(katome_dist_builder* d, const u64* part, const u32* idx, co
     }
     return builder_insert(b, b->table, b->table_ready, d->nw, b->s.table_slots_hint, recv.as<u64>(), nullptr, nR,
                           d->first_seen ? &origin : nullptr, PH_INSERT, stream);
+}
+
+// The same for a batch of reads of varying length: in first-seen order every record travels with its two sequence numbers
+// (`pairs`, [n][2], resolved by the sender: 16 B per record instead of the index's 4).  Nothing here leaves a peer waiting:
+// whether every rank could make room for what it receives is agreed -- with any failure a rank has met on its side of the batch
+// (`status`, a KATOME_E_* code or 0) -- before the records move, and all ranks return that agreed error together; a failure
+// while counting what arrived is kept in `status` and agreed by the caller's closing allreduce.
+int route_and_insert_var(katome_dist_builder* d, const u64* part, const u64* pairs, const std::vector<uint64_t>& counts, uint32_t nwr,
+                         bool tiles, uint32_t span, hipStream_t stream, int& status, std::string& why) {
+    katome_builder* b = d->b;
+    const int world = d->world();
+    std::vector<uint64_t> rcnt(world, 0);
+    uint64_t pair_max = 0;
+    KCHECK(d->comm->exchange_counts(counts.data(), rcnt.data(), &pair_max));
+    const uint64_t nR = sum(rcnt);
+    DevBuf recv(stream), rpairs(stream);
+    if (!status) {
+        int rc = recv.alloc(std::max<uint64_t>(nR, 1) * 8 * nwr);
+        if (!rc && d->first_seen) rc = rpairs.alloc(std::max<uint64_t>(nR, 1) * 16);
+        if (rc) { status = rc; why = get_error(); }
+    }
+    uint64_t agreed = status ? (uint64_t)(-status) : 0;
+    KCHECK(d->comm->allreduce(&agreed, 1, OP_MAX));
+    if (agreed) {
+        set_error("%s", status ? why.c_str() : "another rank of this build failed");
+        return -(int)agreed;
+    }
+    KCHECK(d->xchg(X_RECORDS, part, counts.data(), recv.p, rcnt.data(), 8 * nwr, stream, false, pair_max));
+    SeenOrigin origin;
+    if (d->first_seen) {
+        KCHECK(d->xchg(X_RECORDS, pairs, counts.data(), rpairs.p, rcnt.data(), 16, stream, false, pair_max));
+        origin.pairs = rpairs.as<u64>(); origin.rc = d->rc;
+    }
+    if (nR == 0) return KATOME_OK;
+    int rc;
+    if (tiles) {
+        b->span = span;
+        rc = builder_insert(b, b->tiles, b->tiles_ready, d->nwt, b->s.table_slots_hint / 4, recv.as<u64>(), nullptr, nR,
+                            d->first_seen ? &origin : nullptr, PH_INSERT_TILES, stream);
+    } else {
+        rc = builder_insert(b, b->table, b->table_ready, d->nw, b->s.table_slots_hint, recv.as<u64>(), nullptr, nR,
+                            d->first_seen ? &origin : nullptr, PH_INSERT, stream);
+    }
+    if (rc && !status) { status = rc; why = get_error(); }
+    return KATOME_OK;
 }
 
 // Weighted records [with their two sequence numbers] to their owners, which add them to `table`: in slices of at most a quarter
@@ -637,7 +753,12 @@ int katome_dist_add_reads(katome_dist_builder* d, const uint8_t* d_packed, uint6
     if (d->finalized) { set_error("builder already finalized"); return KATOME_E_ARG; }
     const uint32_t k = d->s.k, nw = d->nw;
     if (read_len < k) { set_error("Read is too short!"); return KATOME_E_SHORT_READ; }       // pt_graph.rs:278
-    if (!d->planned) {
+    if (d->var && d->first_seen) { set_error("first-seen order: fixed- and variable-length batches cannot be mixed in one build"); return KATOME_E_UNSUPPORTED; }
+    if (d->var && d->read_len == 0) {
+        // (by packed key after reads of varying length: this length under the span the ranks agreed on)
+        d->read_len = read_len; d->W = read_len - k + 1;
+        d->tiles_per_read = d->span > 1 ? d->W / d->span : 0; d->rest = d->span > 1 ? d->W % d->span : d->W;
+    } else if (!d->planned) {
         d->read_len = read_len; d->W = read_len - k + 1;
         if (!katome_tile_plan_limited(k, read_len, 3, &d->span, &d->tiles_per_read, &d->rest)) { d->span = 1; d->tiles_per_read = 0; d->rest = d->W; }
         d->nwt = d->span > 1 ? katome_tile_words(k, d->span) : nw;
@@ -649,6 +770,7 @@ int katome_dist_add_reads(katome_dist_builder* d, const uint8_t* d_packed, uint6
         set_error("the sharded build takes reads of one length (%u, then %u)", d->read_len, read_len);
         return KATOME_E_UNSUPPORTED;
     }
+    d->fixed_added = true;
     const int world = d->world();
     if (const char* f = getenv("KATOME_DIST_ADD_FAIL"))          // (tests: this rank's reads are refused, as a failed allocation would refuse them)
         if (atoi(f) == d->comm->rank()) { set_error("reads refused (KATOME_DIST_ADD_FAIL)"); return KATOME_E_OOM; }
@@ -800,6 +922,191 @@ int katome_dist_add_reads(katome_dist_builder* d, const uint8_t* d_packed, uint6
     return KATOME_OK;
 }
 
+int katome_dist_add_reads_var(katome_dist_builder* d, const uint8_t* d_packed, uint64_t packed_bytes, const uint64_t* d_byte_off,
+                              const uint32_t* d_len, uint64_t n_reads, uint64_t first_window, uint64_t batch_windows, void* stream_) {
+    if (!d) { set_error("null argument"); return KATOME_E_ARG; }
+    hipStream_t stream = (hipStream_t)stream_;
+    katome_builder* b = d->b;
+    KCHECK_HIP(hipSetDevice(d->s.device));
+    d->comm->use_stream(stream);
+    const int world = d->world();
+    const uint32_t k = d->s.k, nw = d->nw;
+    // Every failure is agreed before anything is exchanged: this rank's own verdict travels with the first allreduce, so a
+    // rank that cannot take its reads never leaves the others waiting, and every rank returns the same error.
+    int mine = KATOME_OK;
+    std::string why;
+    auto fail = [&](int rc) { if (rc && !mine) { mine = rc; why = get_error(); } return rc; };
+    auto agreed = [&](uint64_t code) -> int {               // (code: the largest -status over all ranks; every rank returns it)
+        set_error("%s", mine ? why.c_str() : "another rank of this build failed");
+        return -(int)code;
+    };
+    if (d->finalized) { set_error("builder already finalized"); fail(KATOME_E_ARG); }
+    else if (n_reads && (!d_packed || !d_byte_off || !d_len)) { set_error("null argument"); fail(KATOME_E_ARG); }
+    else if (d->first_seen && d->fixed_added) { set_error("first-seen order: fixed- and variable-length batches cannot be mixed in one build"); fail(KATOME_E_UNSUPPORTED); }
+    else if (d->supermers) { set_error("the supermer route (planned by an earlier batch of one length) takes reads of one length only"); fail(KATOME_E_UNSUPPORTED); }
+    // (by packed key after reads of one length on the local route: the tile records that batch kept aside go into the tile table,
+    // where this call's tiles go -- finalize then expands one table)
+    if (!mine && d->local_first && b->tile_recs_n) { b->tile_recs_closed = true; fail(flush_tile_recs(b, stream)); }
+    if (const char* f = getenv("KATOME_DIST_ADD_FAIL"))      // (tests: this rank's reads are refused, as a failed allocation would refuse them)
+        if (!mine && atoi(f) == d->comm->rank()) { set_error("reads refused (KATOME_DIST_ADD_FAIL)"); fail(KATOME_E_OOM); }
+    // every read's windows, and what each candidate span would cost on this rank's reads
+    DevBuf wcount(stream), pref(stream), stats_d(stream);
+    std::vector<uint64_t> stats(VAR_SPANS + 1, 0);
+    uint64_t windows = 0;
+    if (!mine && n_reads) {
+        if (!fail(wcount.alloc(n_reads * 4 + 16)) && !fail(pref.alloc((n_reads + 1) * 8)) && !fail(stats_d.alloc((VAR_SPANS + 1) * 8))) {
+            if (hipMemsetAsync(stats_d.p, 0, (VAR_SPANS + 1) * 8, stream) != hipSuccess) { set_error("memset failed"); fail(KATOME_E_DEVICE); }
+            else {
+                hipLaunchKernelGGL(var_stats_kernel, dim3(grid_for(n_reads, BLOCK, 1024u)), dim3(BLOCK), 0, stream, d_len, n_reads, k, wcount.as<u32>(),
+                                   stats_d.as<unsigned long long>());
+                if (!fail(dev_scan_counts(wcount.as<u32>(), n_reads, pref.as<u64>(), stream))) {
+                    if (hipMemcpyAsync(stats.data(), stats_d.p, (VAR_SPANS + 1) * 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                        hipMemcpyAsync(&windows, pref.as<u64>() + n_reads, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                        hipStreamSynchronize(stream) != hipSuccess) { set_error("device failure while sizing the reads"); fail(KATOME_E_DEVICE); }
+                }
+            }
+        }
+    }
+    uint64_t verdict[2] = {mine ? (uint64_t)(-mine) : 0, stats[0]};
+    KCHECK(d->comm->allreduce(verdict, 2, OP_MAX));
+    if (verdict[0]) return agreed(verdict[0]);
+    if (verdict[1]) { set_error("Read is too short!"); return KATOME_E_SHORT_READ; }     // pt_graph.rs:278, on every rank
+    // the plan: one span for the whole build, the cheapest over all ranks' reads of the first call (tiles of the same content must
+    // meet on one owner: the same span everywhere)
+    stats[0] = windows;                                        // ([0]: all ranks' windows, the cost without tiles)
+    KCHECK(d->comm->allreduce(stats.data(), VAR_SPANS + 1, OP_SUM));
+    if (!d->planned) {
+        uint32_t span = 1;
+        if (!getenv("KATOME_NO_TILES")) {
+            uint64_t best = stats[0];
+            for (uint32_t sp = 2; sp < 2 + VAR_SPANS && k + sp - 1 <= 95; ++sp)
+                if (stats[sp - 1] < best || (stats[sp - 1] == best && span > 1)) { best = stats[sp - 1]; span = sp; }
+            if (const char* e = getenv("KATOME_TILE_SPAN")) { const uint32_t sp = (uint32_t)atoi(e); if (sp >= 1 && k + sp - 1 <= 95) span = sp; }
+        }
+        d->span = span; d->nwt = span > 1 ? katome_tile_words(k, span) : nw;
+        d->read_len = 0; d->W = 0; d->tiles_per_read = 0; d->rest = 0;
+        d->supermers = false; d->want_supermers = false;          // (the supermer route takes reads of one length)
+        d->planned = true;
+    }
+    if (!d->var) d->var_first_window = first_window;
+    d->var = true;
+    const bool tiled = d->span > 1;
+    const uint32_t span = d->span, nwt = d->nwt, nwr = std::max(nwt, nw);
+    const bool tiles_route = !d->local_first;
+    // batches of at most batch_windows windows (+ one read's), at most 2^31: a batch's records are indexed by 32 bits
+    const uint64_t per_batch = std::min<uint64_t>(std::max<uint64_t>(1, batch_windows ? batch_windows : (tiles_route ? (4ull << 20) : (64ull << 20))),
+                                                  1ull << 31);
+    uint64_t nb = (windows + per_batch - 1) / per_batch;
+    std::vector<uint64_t> bounds(2 * (nb + 1), 0);
+    uint64_t cap_rec = 0, cap_reads = 0;
+    DevBuf recbuf(stream), part(stream), idx(stream), pidx(stream), pairs(stream), cnt_t(stream), cnt_r(stream), wp(stream), tp(stream), rp(stream);
+    if (nb) {
+        DevBuf bd(stream);
+        if (!fail(bd.alloc((nb + 1) * 16))) {
+            KLAUNCH(var_bounds_kernel, nb + 1, stream, pref.as<u64>(), n_reads, per_batch, nb, bd.as<u64>());
+            if (hipMemcpyAsync(bounds.data(), bd.p, (nb + 1) * 16, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                hipStreamSynchronize(stream) != hipSuccess) { set_error("device failure while cutting the reads into batches"); fail(KATOME_E_DEVICE); }
+        }
+        for (uint64_t i = 0; i < nb && !mine; ++i) {
+            cap_rec = std::max(cap_rec, bounds[2 * i + 3] - bounds[2 * i + 1]);
+            cap_reads = std::max(cap_reads, bounds[2 * i + 2] - bounds[2 * i]);
+        }
+        if (!mine && cap_rec >= (1ull << 32)) { set_error("a batch of more than 2^32 windows (a read of more than 2^31 bases)"); fail(KATOME_E_UNSUPPORTED); }
+    }
+    {   // (the batch's records, the per-read counts and their prefixes; the tiles route also partitions [and resolves sequence
+        // numbers].  A rank without reads gets them too, small: it passes them to the exchanges of the others' batches)
+        if (!mine && !fail(recbuf.alloc(cap_rec * 8 * nwr + 64)) && !fail(cnt_t.alloc(cap_reads * 4 + 16)) && !fail(cnt_r.alloc(cap_reads * 4 + 16)) &&
+            !fail(wp.alloc((cap_reads + 1) * 8)) && !fail(tp.alloc((cap_reads + 1) * 8)) && !fail(rp.alloc((cap_reads + 1) * 8)) && tiles_route &&
+            !fail(part.alloc(cap_rec * 8 * nwr + 64)) && d->first_seen) {
+            if (!fail(idx.alloc(cap_rec * 4 + 64)) && !fail(pidx.alloc(cap_rec * 4 + 64))) fail(pairs.alloc(cap_rec * 16 + 64));
+        }
+    }
+    uint64_t agree[2] = {nb, mine ? (uint64_t)(-mine) : 0};
+    KCHECK(d->comm->allreduce(agree, 2, OP_MAX));
+    if (agree[1]) return agreed(agree[1]);
+    nb = agree[0];
+    const uint64_t seq0 = 2 * (d->var_first_window + d->var_windows);      // this call's first sequence number
+    const bool mark = d->first_seen && d->rc;
+    for (uint64_t i = 0; i < nb; ++i) {
+        // (a rank with fewer batches, or one that failed, takes part in the exchanges of the others with nothing to send)
+        const bool have = i + 1 < bounds.size() / 2 && !mine;
+        const uint64_t r0 = have ? bounds[2 * i] : 0, nr = have ? bounds[2 * i + 2] - r0 : 0;
+        const uint64_t w_before = have ? bounds[2 * i + 1] : 0, nwin = have ? bounds[2 * i + 3] - w_before : 0;
+        const uint64_t seq_base = seq0 + 2 * w_before;
+        uint64_t n_tiles = 0, n_rest = 0;
+        // (no `continue` past a failure: the exchanges below must still be met)
+        if (nr && nwin) {
+            const u32* wc = wcount.as<u32>() + r0;
+            if (!fail(dev_scan_counts(wc, nr, wp.as<u64>(), stream))) {
+                if (!tiled) n_rest = nwin;
+                else {
+                    KLAUNCH(var_split_kernel, nr, stream, wc, nr, span, cnt_t.as<u32>(), cnt_r.as<u32>());
+                    uint64_t nn[2] = {0, 0};
+                    if (!fail(dev_scan_counts(cnt_t.as<u32>(), nr, tp.as<u64>(), stream)) && !fail(dev_scan_counts(cnt_r.as<u32>(), nr, rp.as<u64>(), stream))) {
+                        if (hipMemcpyAsync(&nn[0], tp.as<u64>() + nr, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                            hipMemcpyAsync(&nn[1], rp.as<u64>() + nr, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                            hipStreamSynchronize(stream) != hipSuccess) { set_error("device failure while counting a batch's tiles"); fail(KATOME_E_DEVICE); }
+                        else { n_tiles = nn[0]; n_rest = nn[1]; }
+                    }
+                }
+            }
+        }
+        const uint8_t* p = d_packed;
+        const uint64_t* off = d_byte_off ? d_byte_off + r0 : nullptr;
+        const uint32_t* ln = d_len ? d_len + r0 : nullptr;
+        // the batch's kinds of record: whole tiles (mode 1) and the windows after them (mode 2), or every window (mode 0)
+        for (int kind = tiled ? 0 : 1; kind < 2; ++kind) {
+            const bool tile_kind = kind == 0;
+            const uint32_t mode = tile_kind ? 1 : tiled ? 2 : 0, rw = tile_kind ? nwt : nw;
+            const uint64_t n_rec = mine ? 0 : tile_kind ? n_tiles : n_rest;
+            const u64* rec_prefix = tile_kind ? tp.as<u64>() : tiled ? rp.as<u64>() : wp.as<u64>();
+            if (n_rec) {
+                PhaseScope ps(b->prof, PH_EXTRACT, stream);
+                fail(launch_extract_var(k, d->rc, p, packed_bytes, off, ln, rec_prefix, nr, n_rec, recbuf.as<u64>(), stream, mark, tiled ? span : 1, mode));
+            }
+            SeenOrigin origin;
+            origin.win_prefix = wp.as<u64>(); origin.rec_prefix = rec_prefix; origin.n_reads = nr; origin.seq_base = seq_base;
+            origin.mode = mode; origin.span = tiled ? span : 1; origin.rc = d->rc;
+            if (!tiles_route) {                                // counted here, as one GPU counts them; nothing is exchanged yet
+                if (!n_rec || mine) continue;
+                if (tile_kind) {
+                    b->span = span;
+                    fail(builder_insert(b, b->tiles, b->tiles_ready, nwt, b->s.table_slots_hint / 4, recbuf.as<u64>(), nullptr, n_rec,
+                                        d->first_seen ? &origin : nullptr, PH_INSERT_TILES, stream));
+                } else {
+                    fail(builder_insert(b, b->table, b->table_ready, nw, b->s.table_slots_hint, recbuf.as<u64>(), nullptr, n_rec,
+                                        d->first_seen ? &origin : nullptr, PH_INSERT, stream));
+                }
+                continue;
+            }
+            // the tiles route: grouped by owner (a tile's owner: a hash of the whole tile; a k-mer's: its canonical middle), with the
+            // sequence numbers resolved here in first-seen order
+            std::vector<uint64_t> counts(world, 0);
+            if (n_rec && !mine) {
+                PhaseScope ps(b->prof, PH_REGION_ORDER, stream);
+                if (d->first_seen && fail(dev_iota(idx.as<u32>(), n_rec, stream))) { counts.assign(world, 0); }
+                else if (fail(dev_partition(recbuf.as<u64>(), d->first_seen ? idx.as<u32>() : nullptr, n_rec, rw, world, part.as<u64>(),
+                                            d->first_seen ? pidx.as<u32>() : nullptr, counts.data(), stream, tile_kind ? 0 : 2, tile_kind ? 0 : k - 2))) {
+                    counts.assign(world, 0);
+                } else if (d->first_seen) {
+                    KLAUNCH(var_pairs_kernel, n_rec, stream, pidx.as<u32>(), n_rec, wp.as<u64>(), rec_prefix, nr, mode, tiled ? span : 1, seq_base,
+                            pairs.as<u64>());
+                    if (hipGetLastError() != hipSuccess) { set_error("var_pairs_kernel launch failed"); fail(KATOME_E_DEVICE); counts.assign(world, 0); }
+                }
+            }
+            KCHECK(route_and_insert_var(d, part.as<u64>(), pairs.as<u64>(), counts, rw, tile_kind, tiled && tile_kind ? span : 1, stream, mine, why));
+        }
+        if (!mine && hipStreamSynchronize(stream) != hipSuccess) { set_error("device failure during a batch of reads"); fail(KATOME_E_DEVICE); }
+    }
+    if (hipGetLastError() != hipSuccess && !mine) { set_error("kernel launch failed"); fail(KATOME_E_DEVICE); }
+    // the closing agreement: a failure while counting (or on the sender's side of an exchange) reaches every rank
+    uint64_t closing = mine ? (uint64_t)(-mine) : 0;
+    KCHECK(d->comm->allreduce(&closing, 1, OP_MAX));
+    if (closing) return agreed(closing);
+    d->var_windows += windows; d->var_calls += 1;
+    return KATOME_OK;
+}
+
 int katome_dist_finalize(katome_dist_builder* d, katome_dist_graph* out, void* stream_) {
     if (!d) { set_error("null argument"); return KATOME_E_ARG; }
     hipStream_t stream = (hipStream_t)stream_;
@@ -810,10 +1117,11 @@ int katome_dist_finalize(katome_dist_builder* d, katome_dist_graph* out, void* s
     const int world = d->world(), rank = d->rank();
     const uint32_t nw = d->nw, k = d->s.k, node_bits = 2 * (k - 1);
     // agree on the plan (a rank that was given no reads has none) and on the extent of the input
-    uint64_t plan[2] = {d->planned ? d->span : 0, d->reads_end};
-    KCHECK(d->comm->allreduce(plan, 2, OP_MAX));
+    // (reads of varying length: the sequence numbers end at twice the windows of all ranks)
+    uint64_t plan[3] = {d->planned ? d->span : 0, d->reads_end, d->var ? 2 * (d->var_first_window + d->var_windows) : 0};
+    KCHECK(d->comm->allreduce(plan, 3, OP_MAX));
     const bool tiled = plan[0] > 1;
-    const uint64_t total_reads = plan[1];
+    const uint64_t total_reads = plan[1], var_seq_end = plan[2];
     {   // (a rank that was given no reads made no plan: it takes the route of those that did)
         uint64_t route = d->planned ? (d->supermers ? 2 : 1) : 0;
         KCHECK(d->comm->allreduce(&route, 1, OP_MAX));
@@ -1012,7 +1320,7 @@ int katome_dist_finalize(katome_dist_builder* d, katome_dist_graph* out, void* s
     if (d->first_seen) {
         // the reference numbers a node when its first edge is added (add_fasta_node, pt_graph.rs:142-154): source of the
         // edge's first insertion at 2 * seq, target at 2 * seq + 1; the node's index is the rank of the earliest such number
-        const uint64_t max_seq = 2 * (total_reads + 1) * 2 * (uint64_t)std::max<uint32_t>(d->W, 1) + 2;
+        const uint64_t max_seq = var_seq_end ? var_seq_end + 2 : 2 * (total_reads + 1) * 2 * (uint64_t)std::max<uint32_t>(d->W, 1) + 2;
         DevBuf node_first(stream);
         KCHECK(node_first.alloc((n_owned + 1) * 8));
         KCHECK_HIP(hipMemsetAsync(node_first.p, 0xFF, n_owned * 8, stream));
@@ -1053,7 +1361,7 @@ int katome_dist_finalize(katome_dist_builder* d, katome_dist_graph* out, void* s
         d->n_src = n_src;
     }
     if (d->first_seen) {                                     // petgraph edge index = rank of the edge's first insertion (pt_graph.rs:194)
-        const uint64_t max_seq = 2 * (total_reads + 1) * 2 * (uint64_t)std::max<uint32_t>(d->W, 1) + 2;
+        const uint64_t max_seq = var_seq_end ? var_seq_end + 2 : 2 * (total_reads + 1) * 2 * (uint64_t)std::max<uint32_t>(d->W, 1) + 2;
         KCHECK(d->edge_gid.alloc((E + 1) * 8, stream));
         KCHECK(global_rank(d, X_RANK_EDGES, seq, E, max_seq, d->edge_gid.as<u64>(), stream));
     }

@@ -19,6 +19,11 @@ struct katome_dist_builder {
     bool planned = false;
     uint32_t read_len = 0, W = 0, span = 1, tiles_per_read = 0, rest = 0, nwt = 1;
     uint64_t reads_end = 0;                  // one past the last read this rank has added (first-seen: bounds the sequence numbers)
+    // reads of varying length (katome_dist_add_reads_var): the span was agreed from all ranks' reads at the first call; this
+    // rank's reads start at global window var_first_window, its calls so far added var_windows windows (first-seen: the
+    // sequence numbers of its next read start at 2 * (var_first_window + var_windows))
+    bool var = false, fixed_added = false;
+    uint64_t var_first_window = 0, var_windows = 0, var_calls = 0;
     bool finalized = false;
     // Which records travel.  Few ranks share few links: every rank counts its own reads down to k-mers and
     // sends each DISTINCT k-mer once ("local first": one exchange, 12 B per k-mer and rank).  Many ranks: tiles, mid tiles and

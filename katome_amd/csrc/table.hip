@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "lds_order.h"
+#include "seq_pair.h"
 
 namespace katome {
 
@@ -263,12 +264,7 @@ __global__ __launch_bounds__(BLOCK) void insert_kernel(typename SlotOf<NW>::type
                 const u64 r = sp.seg_read0[seg] + j / sp.per_read, i0 = sp.win0 + (j % sp.per_read) * sp.span;
                 P = r * 2 * sp.windows + i0; Q = r * 2 * sp.windows + 2 * sp.windows - i0 - sp.span;
             } else if (sp.win_prefix) {        // a read's forward windows take 2*prefix + [0, W), its reverse complement's the next W
-                u64 lo = 0, hi = sp.n_reads;
-                while (hi - lo > 1) { const u64 mid = (lo + hi) >> 1; if (sp.rec_prefix[mid] <= g) lo = mid; else hi = mid; }
-                const u64 w0 = sp.win_prefix[lo], W = sp.win_prefix[lo + 1] - w0, j = g - sp.rec_prefix[lo];
-                const u64 i0 = sp.mode == 1 ? j * sp.span : sp.mode == 2 ? (W / sp.span) * sp.span + j : j;
-                const u64 width = sp.mode == 1 ? sp.span : 1;
-                P = sp.seq_base + 2 * w0 + i0; Q = sp.seq_base + 2 * w0 + 2 * W - i0 - width;
+                var_seq_pair(sp.win_prefix, sp.rec_prefix, sp.n_reads, sp.mode, sp.span, sp.seq_base, g, P, Q);
             } else {
                 const u64 r = sp.read0 + g / sp.per_read, i0 = sp.win0 + (g % sp.per_read) * sp.span;
                 P = r * 2 * sp.windows + i0; Q = r * 2 * sp.windows + 2 * sp.windows - i0 - sp.span;

@@ -223,6 +223,25 @@ class ShardedBuilder(_ViewOwner):
     def add_reads(self, packed, first_read, n_reads, read_len, skip=None, batch_reads=0):
         _check(_lib.lib().katome_dist_add_reads(self._h, _ptr(packed), first_read, n_reads, read_len, _ptr(skip), batch_reads, _stream()))
 
+    def add_reads_var(self, packed, byte_off, lens, first_window=None, batch_windows=0):
+        """this rank's reads of varying length (katome_dist_add_reads_var): `packed` 2-bit bases, read r is lens[r] bases at byte
+        byte_off[r] (int64, len(lens) + 1 entries, the last one the bytes in all), device tensors.  first_window: the global
+        window of this rank's first read; None (one call per rank, ranks in input order): from every rank's windows with one
+        allreduce.  Later calls continue after this rank's earlier ones.  Collective: a rank without reads passes empty tensors."""
+        n = int(lens.numel())
+        if first_window is None:
+            first_window = getattr(self, "_first_window", None)
+        if first_window is None:
+            mine = int((lens.to(torch.int64) - (self.k - 1)).clamp(min=0).sum().item()) if n else 0
+            per_rank = [0] * self.comm.world
+            per_rank[self.comm.rank] = mine
+            per_rank = self.comm.allreduce(per_rank, "sum")
+            first_window = sum(per_rank[:self.comm.rank])
+        self._first_window = first_window
+        packed_bytes = int(byte_off[n].item()) if n else 0
+        _check(_lib.lib().katome_dist_add_reads_var(self._h, _ptr(packed), packed_bytes, _ptr(byte_off), _ptr(lens), n, first_window,
+                                                    batch_windows, _stream()))
+
     def remove_weak_edges(self, threshold):
         _check(_lib.lib().katome_dist_remove_weak_edges(self._h, threshold))
 
