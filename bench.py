@@ -6,7 +6,13 @@ steps: the reads are synthesised and a few builds prime the library's device-mem
 k-mer extraction -> k-mer table -> sorted distinct edges -> node numbering, endpoints, labels
 (everything `Build::create` + the PtGraph::create post-pass do in the reference), result left in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c5] [--reads R] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c5] [--reads R] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the dump if asked for, the JSON line (with
+the per-phase and per-kernel figures of the timed steps themselves).  --full adds what takes runs of its own, after the
+timed steps: the CPU baselines (`cpu_baseline`, `cpu_baseline_c2`), the build in the reference's numbering and the unhinted
+build, the host-ABI region (`end_to_end`) and the stages after the build (`next_stages`); --no-cpu-baseline, --no-cpu-c2,
+--no-extras and --next-stages-reads 0 leave parts of it out.
 
 --dump-outputs DIR (one GPU): after the timed steps, the graph the last of them built -- the arrays a caller of the device
 path receives -- is written as DIR/<name>.npy (float64 / float32, at most 64 MB: a fixed, seeded sample of the rows; see
@@ -174,8 +180,11 @@ def parse_args():
     ap.add_argument("--genome-len", type=int, default=0,
                     help="with --reads: keep this genome length instead of scaling it with the reads (a rank's share of a bigger job)")
     ap.add_argument("--batch-reads", type=int, default=DEFAULT_BATCH_READS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cpu-c2", action="store_true", help="skip the second CPU line: BASELINE configs[1] (1 M reads) in full on one core and on the GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the measurements that take runs of their own: CPU baselines, reference-order and "
+                         "unhinted builds, the end-to-end region, the stages after the build (one GPU)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-cpu-c2", action="store_true", help="with --full: skip the second CPU line: BASELINE configs[1] (1 M reads) in full on one core and on the GPU")
     ap.add_argument("--first-seen-order", action="store_true",
                     help="number edges and nodes in the reference's first-seen (petgraph) order (single GPU)")
     ap.add_argument("--force-dist", action="store_true", help="run the multi-GPU driver even with one rank (testing)")
@@ -187,11 +196,11 @@ def parse_args():
     ap.add_argument("--prune", action="store_true",
                     help="BASELINE config 5: Prunable::remove_dead_paths after the build (reference order; N > 1: on the gathered graph)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the headline: skip the reference-order build, the unhinted build and the end-to-end region")
+                    help="with --full: skip the reference-order build, the unhinted build, the end-to-end region and the next stages")
     ap.add_argument("--end-to-end-reads", type=int, default=20_000_000,
-                    help="SURVEY 8(d) region (ii): host packed reads -> host arrays through katome_build_packed, on this many reads")
+                    help="with --full: SURVEY 8(d) region (ii): host packed reads -> host arrays through katome_build_packed, on this many reads")
     ap.add_argument("--next-stages-reads", type=int, default=20_000_000,
-                    help="also time first-seen-order build + remove_dead_paths + shrink on this many reads (0 = skip; N = 1 only)")
+                    help="with --full: also time first-seen-order build + remove_dead_paths + shrink on this many reads (0 = skip; N = 1 only)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the graph the last timed step built to DIR/<name>.npy (one GPU; see dump_outputs)")
     return ap.parse_args()
@@ -918,14 +927,14 @@ def main():
             line["config"]["transport"] = comm.kind
             line["config"]["route"] = getattr(job, "route", None)
             line["config"]["comm_ranks"] = comm.world          # (the communicator's own rank count: RCCL saw this many ranks)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(wl, args.cpu_sample_reads)
             if not args.no_cpu_c2:
                 try:
                     line["cpu_baseline_c2"] = c2_in_full(torch)
                 except Exception as e:   # noqa: BLE001  (a side line: never the reason the bench line is missing)
                     line["cpu_baseline_c2"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:200])}
-        if world == 1 and not use_dist and not args.no_extras:
+        if args.full and world == 1 and not use_dist and not args.no_extras:
             # Beside the headline (not `value`): the build in the reference's own numbering -- what INTEGRATION.md's GpuGIR binds
             # (flags: 1) --, the build of a caller that passes no table hint, and the end-to-end region incl. H2D/D2H
             try:
@@ -947,7 +956,7 @@ def main():
                     line["end_to_end"] = end_to_end(wl, args.end_to_end_reads)
             except Exception as e:     # noqa: BLE001
                 line["end_to_end"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not use_dist and args.next_stages_reads > 0 and not args.no_extras:
+        if args.full and world == 1 and not use_dist and args.next_stages_reads > 0 and not args.no_extras:
             try:                       # not part of the metric: whatever goes wrong here must not cost the line above
                 kd.release_cache()
                 line["next_stages"] = next_stages(wl, args.next_stages_reads)

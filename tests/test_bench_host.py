@@ -99,3 +99,13 @@ def test_bench_refuses_steps_it_cannot_time_and_dumps_of_a_share():
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                            timeout=120)
         assert r.returncode != 0 and r.stdout.strip() == b"" and msg in r.stderr
+
+
+def test_side_measurements_are_off_unless_full(monkeypatch):
+    """a plain run is the headline alone: the CPU baselines and the other side measurements need --full"""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "2"])
+    assert bench.parse_args().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-c2"])
+    a = bench.parse_args()
+    assert a.full and a.no_cpu_c2 and not a.no_cpu_baseline and not a.no_extras

@@ -129,3 +129,25 @@ def test_bench_dump_outputs_are_the_last_steps_graph_on_every_run(tmp_path):
     assert np.array_equal(d["edge_dst"], ref.edge_dst[rows].astype(np.float64))
     assert np.array_equal(d["edge_weight"], w[rows].astype(np.float64))
     assert np.array_equal(d["edge_label"], ref.edge_label[rows].astype(np.float32))
+
+
+@pytest.mark.gpu
+def test_plain_bench_is_the_headline_and_full_adds_the_side_measurements():
+    """a plain run prints the headline of its timed steps and nothing that takes runs of its own; --full adds the CPU baseline,
+    the reference-order and unhinted builds, the end-to-end region and the next stages, none of them failed"""
+    base = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--reads", "20000"]
+    side = ("cpu_baseline", "cpu_baseline_c2", "reference_order", "unhinted_table", "end_to_end", "next_stages", "extras_error")
+    r = _run_bench(base)
+    assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
+    plain = json.loads(r.stdout.decode().strip().splitlines()[-1])
+    assert plain["metric"] == "k-mers/s" and plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["steps"] == 2
+    assert plain["higher_is_better"] is True and plain["dtype"] == "u64" and plain["kernels"]
+    assert not [k for k in side if k in plain]
+    r = _run_bench(base + ["--full", "--no-cpu-c2"])
+    assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
+    full = json.loads(r.stdout.decode().strip().splitlines()[-1])
+    assert (full["distinct_edges"], full["nodes"]) == (plain["distinct_edges"], plain["nodes"])
+    assert full["cpu_baseline"]["value"] > 0 and "cpu_baseline_c2" not in full and "extras_error" not in full
+    assert full["reference_order"]["ms_per_step"] > 0 and full["unhinted_table"]["ms_per_step"] > 0
+    assert full["end_to_end"]["distinct_edges"] == plain["distinct_edges"]
+    assert "error" not in full["next_stages"] and full["next_stages"]["edges"] == plain["distinct_edges"]
