@@ -318,6 +318,8 @@ int expand_to_last_level(katome_builder* b, Table** last, uint32_t* last_span, h
     return KATOME_OK;
 }
 
+void release_tile_tables(katome_builder* b) { b->tiles.release(); b->tiles2.release(); b->tiles_ready = false; b->tiles2_ready = false; }
+
 // every distinct tile adds its count to its k-mers; afterwards the tile tables are released
 int expand_tiles(katome_builder* b, hipStream_t stream) {
     if (b->tile_recs_n) KCHECK(flush_tile_recs(b, stream));
@@ -342,9 +344,7 @@ int expand_tiles(katome_builder* b, hipStream_t stream) {
         }
         KCHECK(expand_level(b, *last, b->table, b->table_ready, b->nw, hint, b->s.k, last_span, 1, PH_EXPAND_TILES, stream));
     }
-    b->tiles.release();
-    b->tiles2.release();
-    b->tiles_ready = false; b->tiles2_ready = false;
+    release_tile_tables(b);
     return KATOME_OK;
 }
 
@@ -388,6 +388,10 @@ int sorted_count_mode() {
     static const int mode = getenv("KATOME_SORTED_COUNT") ? atoi(getenv("KATOME_SORTED_COUNT")) : 1;
     return mode;
 }
+// is counting n records by sorting worth its extra launches?  (KATOME_SORTED_COUNT=2: however few -- tests)
+bool sorting_pays(uint64_t n) { return n && (n >= (1ull << 22) || sorted_count_mode() == 2); }
+// the most records a caller hands to the LDS counting route (2^16 hash groups of 32 sub-rounds of 2900 records)
+bool lds_route_takes(uint64_t n) { return (n >> 21) <= 2900; }
 
 // plain (weight-1 or weighted) records into the k-mer table, by packed key (no origin)
 static int insert_plain(katome_builder* b, const uint64_t* d_records, const uint32_t* d_weights, uint64_t n_records, hipStream_t stream) {
@@ -463,6 +467,11 @@ int tile_recs_valid(katome_builder* b, uint64_t* n, hipStream_t stream) {
     KCHECK_HIP(hipStreamSynchronize(stream));
     return KATOME_OK;
 }
+// no tile records are kept from here on (they were counted, or went into the tile table)
+static void close_tile_recs(katome_builder* b) {
+    b->tile_recs.release(); b->tile_recs_count.release(); b->tile_recs_n = b->tile_recs_cap = 0;
+    b->tile_recs_exact = false; b->tile_recs_closed = true;
+}
 int flush_tile_recs(katome_builder* b, hipStream_t stream) {
     if (b->tile_recs_n) {
         const uint32_t nwt = (uint32_t)key_words_for_k(b->s.k + b->span - 1);
@@ -487,10 +496,7 @@ int flush_tile_recs(katome_builder* b, hipStream_t stream) {
             done += m;
         }
     }
-    b->tile_recs.release(); b->tile_recs_count.release();
-    b->tile_recs_n = b->tile_recs_cap = 0;
-    b->tile_recs_exact = false;
-    b->tile_recs_closed = true;
+    close_tile_recs(b);
     return KATOME_OK;
 }
 
@@ -671,9 +677,7 @@ int tile_recs_to_kmer_records(katome_builder* b, DevBuf& keys, DevBuf& weights, 
         KCHECK(flush_tile_recs(b, stream));          // (the records are all still there, in another order: into the table with them)
         return KATOME_E_UNSUPPORTED;
     }
-    b->tile_recs.release(); b->tile_recs_count.release(); b->tile_recs_n = b->tile_recs_cap = 0;
-    b->tile_recs_exact = false;
-    b->tile_recs_closed = true;
+    close_tile_recs(b);
     b->stat_tiles = n1; b->stat_tile_slots = 0; b->stat_tiles2 = 0; b->stat_tile2_slots = 0;
     KCHECK(shrink_to_fit(t1k, n1 * 8 * nwt, stream)); KCHECK(shrink_to_fit(t1w, n1 * 4, stream));
     const uint64_t* lk = t1k.as<u64>(); const uint32_t* lw = t1w.as<u32>();
@@ -954,9 +958,7 @@ int katome_dev_expand_tiles(katome_builder* b, uint64_t** d_keys, uint32_t** d_w
         PhaseScope ps(b->prof, PH_EXPAND_TILES, stream);
         KCHECK(table_expand_tiles_to_records(*last, b->s.k, last_span, b->rc, b->scratch_k[0], b->scratch_w[0], n_records, stream));
     }
-    b->tiles.release();
-    b->tiles2.release();
-    b->tiles_ready = false; b->tiles2_ready = false;
+    release_tile_tables(b);
     *d_keys = b->scratch_k[0].as<u64>(); *d_weights = b->scratch_w[0].as<u32>();
     return KATOME_OK;
 }
@@ -992,283 +994,286 @@ int katome_dev_table_count(katome_builder* b, uint64_t* out, void* stream) {
     return table_occupied(b->table, out, (hipStream_t)stream);
 }
 
+// The left-over windows kept aside (b->rest_k, `words` words each: nw, or nw + 1 for tagged records) behind the n_rec records in
+// keys / weights, weight 1 each.  orient: the records are in their representative orientation (the half sort's k-mer records)
+static int append_rest(katome_builder* b, DevBuf& keys, DevBuf& weights, uint64_t* n_rec, uint64_t n_rest, uint32_t words, bool orient, hipStream_t stream) {
+    if (!n_rest) return KATOME_OK;
+    KCHECK_HIP(hipMemcpyAsync(keys.as<u64>() + *n_rec * words, b->rest_k.p, n_rest * 8 * words, hipMemcpyDeviceToDevice, stream));
+    KCHECK(dev_fill_u32(weights.as<u32>() + *n_rec, n_rest, 1u, stream));
+    if (orient) KCHECK(table_orient_records(keys.as<u64>() + *n_rec * words, n_rest, b->s.k, true, stream));
+    *n_rec += n_rest;
+    return KATOME_OK;
+}
+
+// The last level counted by sorting instead of in a table (table.hip, lds_count_kernel / lds_count_wide_kernel): k <= 63, by packed
+// key, nothing in the k-mer table yet (left-over windows were kept aside).  With the tiles kept as records (katome_dev_insert_tiles)
+// the tile levels above it are counted the same way: every level is "records -> two hash passes -> counted in LDS -> a compact list
+// of distinct keys with their counts", the next level's records are cut out of that list (table.hip, list_to_records_kernel).
+// on fallback: the tiles are in their table, or the k-mer records with their counts in b->table; n_edges == 0
+static int edges_from_tile_recs(katome_builder* b, bool* counted, hipStream_t stream) {
+    const uint32_t k = b->s.k;
+    DevBuf rk(stream), rw(stream);
+    uint64_t n_rec = 0, n_rest = 0, distinct = 0;
+    KCHECK(rest_valid(b, &n_rest, stream));
+    DevBuf first_counts(stream);
+    const bool half = half_sort_route(b);
+    HalfSort hs;
+    int rc = tile_recs_to_kmer_records(b, rk, rw, &n_rec, n_rest, stream, &first_counts, half);
+    if (rc == KATOME_E_UNSUPPORTED) return KATOME_OK;          // (the tiles are in their table now, the table routes take it from there)
+    if (rc != KATOME_OK) return rc;
+    {
+        PhaseScope ps(b->prof, PH_EXPAND_TILES, stream);
+        KCHECK(append_rest(b, rk, rw, &n_rec, n_rest, b->nw, half && b->rc, stream));
+        rest_reset(b);
+        const bool fail = sorted_fail("last");
+        if (fail && half && b->rc) KCHECK(table_orient_records(rk.as<u64>(), n_rec, k, false, stream));     // (the table takes canonical k-mers)
+        rc = fail ? KATOME_E_UNSUPPORTED
+            : records_to_edges_sorted(rk, rw, n_rec, k, b->rc, b->prune_weight, b->edge_key, b->edge_weight, &b->n_edges, &distinct, stream, nullptr,
+                                      n_rest ? nullptr : first_counts.as<u32>(), half ? &hs : nullptr);
+        if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
+    }
+    if (rc != KATOME_OK) {
+        // the k-mers cannot be counted this way (a hash group beyond the LDS route): their records, counts and all, go into the k-mer
+        // table and the edges are read out of it
+        b->n_edges = 0;
+        return builder_insert(b, b->table, b->table_ready, b->nw, b->s.table_slots_hint, rk.as<u64>(), rw.as<u32>(), n_rec, nullptr, PH_INSERT, stream);
+    }
+    b->stat_kmers = distinct; b->stat_kmer_slots = 0;
+    rk.release(); rw.release();
+    PhaseScope ps(b->prof, PH_SORT_EDGES, stream);
+    if (hs.taken) KCHECK(half_sort_finish(hs, b->edge_key, b->edge_weight, stream));
+    else KCHECK(dev_sort_bufs(b->edge_key, &b->edge_weight, b->n_edges, b->nw, 2 * k, stream, true));
+    *counted = true;
+    return KATOME_OK;
+}
+
+// The k-mers counted by sorting when the big tiles are in their table (KATOME_SORTED_TILES=1, a build that could not keep them aside
+// as records, or one that had to give them up half-way), the mid tiles too where they can be.
+// on fallback: the tiles are in their table (the big ones still there if the mid tiles were counted by sorting), b->table is empty; n_edges == 0
+static int edges_from_tile_table(katome_builder* b, bool* counted, hipStream_t stream) {
+    if (!sorted_count_mode() || !b->tiles_ready || !b->tiles.cap || b->table_ready || b->nw > 2) return KATOME_OK;
+    uint64_t n_tiles = 0;
+    KCHECK(table_occupied(b->tiles, &n_tiles, stream));
+    const uint64_t bound = n_tiles * b->span + b->rest_n;        // the k-mer records can be no more than this
+    const uint32_t nwt = b->tiles.nw;
+    const bool shapes = (b->nw == 1 && nwt <= 2) || (b->nw == 2 && (nwt == 2 || nwt == 3));      // (what tiles_to_records streams)
+    if (!shapes || !sorting_pays(bound) || !lds_route_takes(bound)) return KATOME_OK;
+    Table* last = nullptr; uint32_t last_span = 1;
+    // The mid tiles are counted by sorting all the same: the big tiles' sub-tiles leave the tile table as records, two hash passes,
+    // counted in LDS into a compact list of (mid tile, count), and the k-mer records are cut out of that list -- no mid-tile table,
+    // no 7e8 128-bit upserts (C3: 45 -> 32 ms for the level).
+    DevBuf t2k(stream), t2w(stream);
+    uint64_t n_mid_list = 0;
+    bool mid_sorted = false;
+    const uint32_t sp2 = mid_span(b->span);
+    if (sorted_tiles_mode() && nwt == 2 && b->nw == 1 && sp2 && !b->tiles2_ready && b->tiles.cap && n_tiles &&
+        level_fits(n_tiles * (b->span / sp2), (uint32_t)key_words_for_k(b->s.k + sp2 - 1), false, "mid tiles (big tiles in their table)")) {
+        const uint32_t kk2 = b->s.k + sp2 - 1, n_sub = b->span / sp2;
+        PhaseScope ps(b->prof, PH_EXPAND_MID, stream);
+        TileLevelScope tl;
+        DevBuf mk(stream), mw(stream);
+        uint64_t n_mid = 0, d2 = 0;
+        KCHECK(table_expand_tiles_to_subtiles(b->tiles, kk2, n_sub, sp2, b->rc, mk, mw, &n_mid, stream, nullptr));
+        int rc2 = (n_mid && !sorted_fail("mid")) ? records_to_edges_sorted(mk, mw, n_mid, kk2, false, 0, t2k, t2w, &n_mid_list, &d2, stream) : KATOME_E_UNSUPPORTED;
+        if (rc2 != KATOME_OK && rc2 != KATOME_E_UNSUPPORTED) return rc2;
+        if (rc2 == KATOME_OK) {
+            mid_sorted = true;           // (the big-tile table stays until the k-mers are counted: the table route's way back)
+            b->stat_tiles = n_tiles; b->stat_tile_slots = b->tiles.cap;
+            b->span2 = sp2; b->stat_tiles2 = n_mid_list; b->stat_tile2_slots = 0;
+            last_span = sp2;
+        } else { t2k.release(); t2w.release(); }
+    }
+    if (!mid_sorted) KCHECK(expand_to_last_level(b, &last, &last_span, stream));
+    if (!mid_sorted && !((b->nw == 1 && last->nw <= 2) || (b->nw == 2 && (last->nw == 2 || last->nw == 3)))) return KATOME_OK;
+    uint64_t last_tiles = n_mid_list;          // (... and the records of the level fit the card with their scratch and their output)
+    if (!mid_sorted) KCHECK(table_occupied(*last, &last_tiles, stream));
+    if (!level_fits(last_tiles * last_span + b->rest_n, b->nw, b->rc, "k-mers (tiles in their table)")) return KATOME_OK;
+    DevBuf rk(stream), rw(stream);
+    uint64_t n_rec = 0, distinct = 0;
+    int rc = KATOME_OK;
+    {
+        PhaseScope ps(b->prof, PH_EXPAND_TILES, stream);
+        uint64_t n_rest = 0;
+        KCHECK(rest_valid(b, &n_rest, stream));
+        if (mid_sorted) {
+            KCHECK(table_list_to_records(t2k.as<u64>(), t2w.as<u32>(), n_mid_list, b->s.k + sp2 - 1, b->s.k, sp2, 1, b->rc, rk, rw, &n_rec, stream, n_rest));
+            t2k.release(); t2w.release();
+        } else
+        KCHECK(table_tiles_to_records_fast(*last, b->s.k, last_span, b->rc, rk, rw, &n_rec, stream, n_rest));
+        KCHECK(append_rest(b, rk, rw, &n_rec, n_rest, b->nw, false, stream));
+        rc = sorted_fail("last") ? KATOME_E_UNSUPPORTED
+            : records_to_edges_sorted(rk, rw, n_rec, b->s.k, b->rc, b->prune_weight, b->edge_key, b->edge_weight, &b->n_edges, &distinct, stream);
+        if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
+    }
+    // (a group too large for the LDS route: the table counts, from the tiles that are still there)
+    if (rc != KATOME_OK) { b->n_edges = 0; return KATOME_OK; }
+    release_tile_tables(b);
+    rest_reset(b);
+    b->stat_kmers = distinct; b->stat_kmer_slots = 0;
+    for (int i = 0; i < 2; ++i) { b->scratch_k[i].release(); b->scratch_w[i].release(); }
+    rk.release(); rw.release();
+    PhaseScope ps(b->prof, PH_SORT_EDGES, stream);
+    KCHECK(dev_sort_bufs(b->edge_key, &b->edge_weight, b->n_edges, b->nw, 2 * b->s.k, stream, true));
+    *counted = true;
+    return KATOME_OK;
+}
+
+// edges_from_tile_recs for a first-seen-order build, with the tiles kept as TAGGED records (keep_tile_recs in such a build): every level's
+// distinct keys leave with their counts and their two lowered numbers packed into a tag again (lds_count_seen_kernel, LIST), the
+// next level's tagged records are cut out of that list (list_to_tagged_records_kernel: a sub-window's numbers are its tile's plus its
+// place in it).
+// on fallback: the tile records, or the distinct big tiles with their counts and numbers, are in the tile table; n_edges == 0
+static int seen_edges_from_tile_recs(katome_builder* b, DevBuf& raw_seq, bool* counted, hipStream_t stream) {
+    const uint32_t k = b->s.k, span = b->span, tile_bases = k + span - 1;
+    const uint64_t spr = 2ull * (b->seen_read_len - k + 1);
+    b->span2 = mid_span(span);
+    uint64_t n = 0, n1 = 0, d1 = 0, distinct = 0;
+    KCHECK(tile_recs_valid(b, &n, stream));
+    DevBuf l1(stream), c1(stream);
+    int rc = KATOME_E_UNSUPPORTED;
+    if (n) {
+        PhaseScope ps(b->prof, PH_INSERT_TILES, stream);
+        TileLevelScope tl;
+        DevBuf ones(stream);               // (stays empty: the records count once each)
+        rc = tagged_records_sorted(b->tile_recs, ones, n, tile_bases, b->rc, spr, true, l1, c1, &n1, &d1, stream);
+        if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
+    }
+    if (rc == KATOME_E_UNSUPPORTED) return flush_tile_recs(b, stream);      // (the records are all still there, in another order: into the table with them)
+    close_tile_recs(b);
+    b->stat_tiles = n1; b->stat_tile_slots = 0; b->stat_tiles2 = 0; b->stat_tile2_slots = 0;
+    const uint64_t* lk = l1.as<u64>(); const uint32_t* lw = c1.as<u32>();
+    uint64_t n_last = n1; uint32_t last_bases = tile_bases, last_span = span;
+    DevBuf l2(stream), c2(stream);
+    if (b->span2 && n1) {
+        const uint32_t kk2 = k + b->span2 - 1, n_sub = span / b->span2;
+        PhaseScope ps(b->prof, PH_EXPAND_MID, stream);
+        TileLevelScope tl;
+        DevBuf mk(stream), mw(stream);
+        uint64_t n_mid = 0, n2 = 0, d2 = 0;
+        DevBuf mid_counts(stream);         // (the first partition pass's digit counts per tile, made while the records are written)
+        KCHECK(table_list_to_tagged_records(lk, lw, n1, tile_bases, kk2, n_sub, b->span2, b->rc, mk, mw, &n_mid, stream, 0, &mid_counts));
+        rc = sorted_fail("mid") ? KATOME_E_UNSUPPORTED
+            : tagged_records_sorted(mk, mw, n_mid, kk2, b->rc, spr, true, l2, c2, &n2, &d2, stream, mid_counts.as<u32>());
+        if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
+        if (rc == KATOME_OK) { b->stat_tiles2 = n2; lk = l2.as<u64>(); lw = c2.as<u32>(); n_last = n2; last_bases = kk2; last_span = b->span2; }
+    }
+    if (rc == KATOME_OK) {
+        PhaseScope ps(b->prof, PH_EXPAND_TILES, stream);
+        DevBuf kr(stream), kw(stream);
+        uint64_t n_rec = 0, n_rest = 0;
+        KCHECK(rest_valid(b, &n_rest, stream));
+        DevBuf last_counts(stream);
+        KCHECK(table_list_to_tagged_records(lk, lw, n_last, last_bases, k, last_span, 1, b->rc, kr, kw, &n_rec, stream, n_rest, &last_counts));
+        l2.release(); c2.release();
+        KCHECK(append_rest(b, kr, kw, &n_rec, n_rest, b->nw + 1, false, stream));
+        rc = sorted_fail("last") ? KATOME_E_UNSUPPORTED
+            : tagged_records_sorted(kr, kw, n_rec, k, b->rc, spr, false, b->edge_key, raw_seq, &b->n_edges, &distinct, stream, last_counts.as<u32>());
+        if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
+    }
+    if (rc == KATOME_OK) {
+        l1.release(); c1.release();
+        rest_reset(b);
+        b->stat_kmers = distinct; b->stat_kmer_slots = 0;
+        *counted = true;
+        return KATOME_OK;
+    }
+    // a level below gave up: the distinct big tiles go into the tile table with their counts and their numbers, and the build goes on
+    // from there as if they had been counted in it
+    b->n_edges = 0;
+    l2.release(); c2.release();
+    const uint32_t nwt = (uint32_t)key_words_for_k(tile_bases);
+    DevBuf keys(stream), pairs(stream);
+    KCHECK(keys.alloc(n1 * 8 * nwt + 16)); KCHECK(pairs.alloc(n1 * 16 + 16));
+    KCHECK(table_tagged_to_pairs(l1.as<u64>(), n1, nwt, spr, keys.as<u64>(), pairs.as<u64>(), stream));
+    l1.release();
+    SeenOrigin origin;
+    origin.pairs = pairs.as<u64>(); origin.rc = b->rc;
+    return builder_insert(b, b->tiles, b->tiles_ready, nwt, b->s.table_slots_hint / 4, keys.as<u64>(), c1.as<u32>(), n1, &origin, PH_INSERT_TILES, stream);
+}
+
+// The k-mers of a first-seen-order build counted by sorting out of the tile table (table.hip, lds_count_seen_kernel): reads of one
+// length whose windows are whole tiles, so that a record's two sequence numbers pack into one word.
+// on fallback: the tiles are in their table (mid tiles in b->tiles2 if it made them); n_edges == 0
+static int seen_edges_from_tile_table(katome_builder* b, DevBuf& raw_seq, bool* counted, hipStream_t stream) {
+    if (!sorted_count_mode() || !b->tiles_ready || b->table_ready || b->nw > 2 || b->var_seq_base || b->var_prefix || b->direct_edges ||
+        b->seen_read_len < b->s.k)
+        return KATOME_OK;
+    uint64_t n_tiles = 0;
+    KCHECK(table_occupied(b->tiles, &n_tiles, stream));
+    if (!sorting_pays(n_tiles * b->span)) return KATOME_OK;     // (the last level's own size is checked where its records are made)
+    Table* last = nullptr; uint32_t last_span = 1;
+    KCHECK(expand_to_last_level(b, &last, &last_span, stream));
+    uint64_t distinct = 0;
+    int rc = KATOME_OK;
+    {
+        PhaseScope ps(b->prof, PH_EXPAND_TILES, stream);
+        uint64_t n_rest = 0;
+        KCHECK(rest_valid(b, &n_rest, stream));
+        rc = tiles_to_edges_sorted_seen(*last, b->s.k, last_span, b->rc, 2ull * (b->seen_read_len - b->s.k + 1), b->edge_key, raw_seq, &b->n_edges,
+                                        &distinct, stream, n_rest ? b->rest_k.as<u64>() : nullptr, n_rest);
+        if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
+    }
+    // (numbers that do not pack, or a group too large: the table counts, from the tiles that are still there)
+    if (rc != KATOME_OK) { b->n_edges = 0; return KATOME_OK; }
+    release_tile_tables(b);
+    rest_reset(b);
+    b->stat_kmers = distinct; b->stat_kmer_slots = 0;
+    *counted = true;
+    return KATOME_OK;
+}
+
+// The table route: what is left in the tile tables adds its counts to the k-mer table, whose edges are emitted and sorted.  It is
+// also the first-seen routes' sort tail: seen_counted -- their edges are in edge_key / raw_seq already, only the sort is left.
+static int edges_from_table(katome_builder* b, bool seen_counted, DevBuf& raw_seq, hipStream_t stream) {
+    DevBuf raw_w(stream);
+    if (!seen_counted) {
+        KCHECK(expand_tiles(b, stream));
+        if (!b->table_ready) {                    // (nothing was counted: an empty edge list)
+            KCHECK(b->edge_key.alloc(16, stream)); KCHECK(b->edge_weight.alloc(16, stream));
+            return KATOME_OK;
+        }
+        KCHECK(table_occupied(b->table, &b->stat_kmers, stream));
+        b->stat_kmer_slots = b->table.cap;
+        PhaseScope ps(b->prof, PH_EMIT_EDGES, stream);
+        // (first-seen order: the threshold is applied after the numbering, as the reference's retain passes do)
+        if (b->first_seen) KCHECK(table_emit_edges(b->table, b->s.k, b->rc, 0, b->edge_key, raw_w, &b->n_edges, stream, &raw_seq));
+        else KCHECK(table_emit_edges(b->table, b->s.k, b->rc, b->prune_weight, b->edge_key, b->edge_weight, &b->n_edges, stream));
+    }
+    for (int i = 0; i < 2; ++i) { b->scratch_k[i].release(); b->scratch_w[i].release(); }
+    b->table.release();                       // the table is spent; its memory serves the sort
+    b->table_ready = false;
+    PhaseScope ps(b->prof, PH_SORT_EDGES, stream);
+    if (!b->first_seen) return dev_sort_bufs(b->edge_key, &b->edge_weight, b->n_edges, b->nw, 2 * b->s.k, stream, true);
+    // sort (key, position) and bring weight and sequence number along through the positions
+    if (b->n_edges >= (1ull << 32)) { set_error("first-seen order: more than 2^32 edges on one GPU"); return KATOME_E_UNSUPPORTED; }
+    DevBuf idx(stream);
+    KCHECK(idx.alloc((b->n_edges + 1) * 4));
+    KCHECK(dev_iota(idx.as<u32>(), b->n_edges, stream));
+    KCHECK(dev_sort_bufs(b->edge_key, &idx, b->n_edges, b->nw, 2 * b->s.k, stream));
+    KCHECK(b->edge_weight.alloc((b->n_edges + 1) * 4, stream));
+    KCHECK(b->edge_seq.alloc((b->n_edges + 1) * 8, stream));
+    return dev_gather_seq_weight(raw_seq.as<u64>(), idx.as<u32>(), b->n_edges, b->edge_seq.as<u64>(), b->edge_weight.as<u32>(), stream);
+}
+
+// The builder's sorted distinct edges: the counting routes are tried in turn, each leaving to the next what it could not count
 int katome_dev_edges(katome_builder* b, uint64_t** d_edge_key, uint32_t** d_edge_weight, uint64_t* n_edges, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     KCHECK_HIP(hipSetDevice(b->s.device));
     if (!b->edges_ready) {
         b->n_edges = 0;
         b->tile_scratch.release();
-        // Counting the last level by sorting instead of in a table (table.hip, lds_count_kernel / lds_count_wide_kernel): k <= 63, by
-        // packed key, nothing in the k-mer table yet (left-over windows were kept aside), enough tiles to be worth the extra launches
-        const int sorted_count = sorted_count_mode();
+        // (tile records with k-mers in the table already, or too few of them to be worth sorting: into the tile table)
+        if (b->tile_recs_n && (b->table_ready || !sorting_pays(b->tile_recs_n * b->span))) KCHECK(flush_tile_recs(b, stream));
         bool counted = false;
-        // ... and the tile levels above it the same way when the tiles were kept as records (katome_dev_insert_tiles): every level is
-        // "records -> two hash passes -> counted in LDS -> a compact list of distinct keys with their counts", the next level's
-        // records are cut out of that list (table.hip, list_to_records_kernel)
-        if (!b->first_seen && b->tile_recs_n && (b->table_ready || (b->tile_recs_n * b->span < (1ull << 22) && sorted_count != 2)))
-            KCHECK(flush_tile_recs(b, stream));      // (k-mers in the table already, or too few tiles to be worth it)
-        if (!b->first_seen && b->tile_recs_n) {
-            const uint32_t k = b->s.k;
-            DevBuf rk(stream), rw(stream);
-            uint64_t n_rec = 0, n_rest = 0, distinct = 0;
-            KCHECK(rest_valid(b, &n_rest, stream));
-            DevBuf first_counts(stream);
-            const bool half = half_sort_route(b);
-            HalfSort hs;
-            int rc = tile_recs_to_kmer_records(b, rk, rw, &n_rec, n_rest, stream, &first_counts, half);
-            if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
-            if (rc == KATOME_OK) {         // (otherwise the tiles are in their table now, and the blocks below take it from there)
-                {
-                    PhaseScope ps(b->prof, PH_EXPAND_TILES, stream);
-                    if (n_rest) {
-                        KCHECK_HIP(hipMemcpyAsync(rk.as<u64>() + n_rec * b->nw, b->rest_k.p, n_rest * 8 * b->nw, hipMemcpyDeviceToDevice, stream));
-                        KCHECK(dev_fill_u32(rw.as<u32>() + n_rec, n_rest, 1u, stream));
-                        if (half && b->rc) KCHECK(table_orient_records(rk.as<u64>() + n_rec, n_rest, k, true, stream));
-                        n_rec += n_rest;
-                    }
-                    rest_reset(b);
-                    const bool fail = sorted_fail("last");
-                    if (fail && half && b->rc) KCHECK(table_orient_records(rk.as<u64>(), n_rec, k, false, stream));     // (the table takes canonical k-mers)
-                    rc = fail ? KATOME_E_UNSUPPORTED
-                        : records_to_edges_sorted(rk, rw, n_rec, k, b->rc, b->prune_weight, b->edge_key, b->edge_weight, &b->n_edges, &distinct, stream, nullptr,
-                                                  n_rest ? nullptr : first_counts.as<u32>(), half ? &hs : nullptr);
-                    if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
-                }
-                if (rc == KATOME_OK) {
-                    b->stat_kmers = distinct; b->stat_kmer_slots = 0;
-                    rk.release(); rw.release();
-                    PhaseScope ps(b->prof, PH_SORT_EDGES, stream);
-                    if (hs.taken) KCHECK(half_sort_finish(hs, b->edge_key, b->edge_weight, stream));
-                    else KCHECK(dev_sort_bufs(b->edge_key, &b->edge_weight, b->n_edges, b->nw, 2 * k, stream, true));
-                    counted = true;
-                } else {
-                    // the k-mers cannot be counted this way (a hash group beyond the LDS route): their records, counts and all, go
-                    // into the k-mer table and the edges are read out of it
-                    b->n_edges = 0;
-                    KCHECK(builder_insert(b, b->table, b->table_ready, b->nw, b->s.table_slots_hint, rk.as<u64>(), rw.as<u32>(), n_rec, nullptr, PH_INSERT, stream));
-                }
-            }
-        }
-        if (!counted && sorted_count && b->tiles_ready && b->tiles.cap && !b->table_ready && !b->first_seen && b->nw <= 2) {
-            uint64_t n_tiles = 0;
-            KCHECK(table_occupied(b->tiles, &n_tiles, stream));
-            const uint64_t bound = n_tiles * b->span + b->rest_n;        // the k-mer records can be no more than this
-            const uint32_t nwt = b->tiles.nw;
-            const bool shapes = (b->nw == 1 && nwt <= 2) || (b->nw == 2 && (nwt == 2 || nwt == 3));      // (what tiles_to_records streams)
-            if (shapes && (bound >= (1ull << 22) || (sorted_count == 2 && bound)) && (bound >> 21) <= 2900) {      // (2: however few -- tests)
-                Table* last = nullptr; uint32_t last_span = 1;
-                // Big tiles that are in their table (KATOME_SORTED_TILES=1, a build that could not keep them aside as records, or one
-                // that had to give them up half-way): the mid tiles are counted by sorting all the same -- the big tiles' sub-tiles
-                // leave the tile table as records, two hash passes, counted in LDS into a compact list of (mid tile, count), and the
-                // k-mer records are cut out of that list -- no mid-tile table, no 7e8 128-bit upserts (C3: 45 -> 32 ms for the level).
-                DevBuf t2k(stream), t2w(stream);
-                uint64_t n_mid_list = 0;
-                bool mid_sorted = false;
-                const uint32_t sp2 = mid_span(b->span);
-                if (sorted_tiles_mode() && nwt == 2 && b->nw == 1 && sp2 && !b->tiles2_ready && b->tiles.cap && n_tiles &&
-                    level_fits(n_tiles * (b->span / sp2), (uint32_t)key_words_for_k(b->s.k + sp2 - 1), false, "mid tiles (big tiles in their table)")) {
-                    const uint32_t kk2 = b->s.k + sp2 - 1, n_sub = b->span / sp2;
-                    PhaseScope ps(b->prof, PH_EXPAND_MID, stream);
-                    TileLevelScope tl;
-                    DevBuf mk(stream), mw(stream);
-                    uint64_t n_mid = 0, d2 = 0;
-                    KCHECK(table_expand_tiles_to_subtiles(b->tiles, kk2, n_sub, sp2, b->rc, mk, mw, &n_mid, stream, nullptr));
-                    int rc2 = (n_mid && !sorted_fail("mid")) ? records_to_edges_sorted(mk, mw, n_mid, kk2, false, 0, t2k, t2w, &n_mid_list, &d2, stream) : KATOME_E_UNSUPPORTED;
-                    if (rc2 != KATOME_OK && rc2 != KATOME_E_UNSUPPORTED) return rc2;
-                    if (rc2 == KATOME_OK) {
-                        mid_sorted = true;           // (the big-tile table stays until the k-mers are counted: the table route's way back)
-                        b->stat_tiles = n_tiles; b->stat_tile_slots = b->tiles.cap;
-                        b->span2 = sp2; b->stat_tiles2 = n_mid_list; b->stat_tile2_slots = 0;
-                        last_span = sp2;
-                    } else { t2k.release(); t2w.release(); }
-                }
-                if (!mid_sorted) KCHECK(expand_to_last_level(b, &last, &last_span, stream));
-                bool last_ok = mid_sorted || (b->nw == 1 && last->nw <= 2) || (b->nw == 2 && (last->nw == 2 || last->nw == 3));
-                if (last_ok) {        // (... and the records of the level fit the card with their scratch and their output)
-                    uint64_t last_tiles = n_mid_list;
-                    if (!mid_sorted) KCHECK(table_occupied(*last, &last_tiles, stream));
-                    last_ok = level_fits(last_tiles * last_span + b->rest_n, b->nw, b->rc, "k-mers (tiles in their table)");
-                }
-                if (last_ok) {
-                    DevBuf rk(stream), rw(stream);
-                    uint64_t n_rec = 0, distinct = 0;
-                    int rc = KATOME_OK;
-                    {
-                        PhaseScope ps(b->prof, PH_EXPAND_TILES, stream);
-                        uint64_t n_rest = 0;
-                        KCHECK(rest_valid(b, &n_rest, stream));
-                        if (mid_sorted) {
-                            KCHECK(table_list_to_records(t2k.as<u64>(), t2w.as<u32>(), n_mid_list, b->s.k + sp2 - 1, b->s.k, sp2, 1, b->rc, rk, rw, &n_rec, stream, n_rest));
-                            t2k.release(); t2w.release();
-                        } else
-                        KCHECK(table_tiles_to_records_fast(*last, b->s.k, last_span, b->rc, rk, rw, &n_rec, stream, n_rest));
-                        if (n_rest) {             // the left-over windows behind them, one each
-                            KCHECK_HIP(hipMemcpyAsync(rk.as<u64>() + n_rec * b->nw, b->rest_k.p, n_rest * 8 * b->nw, hipMemcpyDeviceToDevice, stream));
-                            KCHECK(dev_fill_u32(rw.as<u32>() + n_rec, n_rest, 1u, stream));
-                            n_rec += n_rest;
-                        }
-                        rc = sorted_fail("last") ? KATOME_E_UNSUPPORTED
-                            : records_to_edges_sorted(rk, rw, n_rec, b->s.k, b->rc, b->prune_weight, b->edge_key, b->edge_weight, &b->n_edges, &distinct, stream);
-                        if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
-                    }
-                    if (rc == KATOME_OK) {
-                        b->tiles.release(); b->tiles2.release();
-                        b->tiles_ready = false; b->tiles2_ready = false;
-                        rest_reset(b);
-                        b->stat_kmers = distinct; b->stat_kmer_slots = 0;
-                        for (int i = 0; i < 2; ++i) { b->scratch_k[i].release(); b->scratch_w[i].release(); }
-                        rk.release(); rw.release();
-                        PhaseScope ps(b->prof, PH_SORT_EDGES, stream);
-                        KCHECK(dev_sort_bufs(b->edge_key, &b->edge_weight, b->n_edges, b->nw, 2 * b->s.k, stream, true));
-                        counted = true;
-                    } else {
-                        b->n_edges = 0;           // (a group too large for the LDS route: the table counts, from the tiles that are still there)
-                    }
-                }
-            }
-        }
-        // The same for a first-seen-order build (table.hip, lds_count_seen_kernel): reads of one length whose windows are whole tiles
-        // (nothing in the k-mer table), so that a record's two sequence numbers pack into one word
-        DevBuf raw_w(stream), raw_seq(stream);
-        bool counted_seen = false;
-        // ... and with the tiles kept as TAGGED records (keep_tile_recs in such a build) every level of it: a level's distinct keys leave
-        // with their counts and their two lowered numbers packed into a tag again (lds_count_seen_kernel, LIST), the next level's tagged
-        // records are cut out of that list (list_to_tagged_records_kernel: a sub-window's numbers are its tile's plus its place in it)
-        if (b->first_seen && b->tile_recs_n && (b->table_ready || (b->tile_recs_n * b->span < (1ull << 22) && sorted_count != 2)))
-            KCHECK(flush_tile_recs(b, stream));
-        if (b->first_seen && b->tile_recs_n) {
-            const uint32_t k = b->s.k, span = b->span, tile_bases = k + span - 1;
-            const uint64_t spr = 2ull * (b->seen_read_len - k + 1);
-            b->span2 = mid_span(span);
-            uint64_t n = 0, n1 = 0, d1 = 0, distinct = 0;
-            KCHECK(tile_recs_valid(b, &n, stream));
-            DevBuf l1(stream), c1(stream);
-            int rc = KATOME_E_UNSUPPORTED;
-            if (n) {
-                PhaseScope ps(b->prof, PH_INSERT_TILES, stream);
-                TileLevelScope tl;
-                DevBuf ones(stream);               // (stays empty: the records count once each)
-                rc = tagged_records_sorted(b->tile_recs, ones, n, tile_bases, b->rc, spr, true, l1, c1, &n1, &d1, stream);
-                if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
-            }
-            if (rc == KATOME_E_UNSUPPORTED) {
-                KCHECK(flush_tile_recs(b, stream));          // (the records are all still there, in another order: into the table with them)
-            } else {
-                b->tile_recs.release(); b->tile_recs_count.release(); b->tile_recs_n = b->tile_recs_cap = 0;
-                b->tile_recs_exact = false; b->tile_recs_closed = true;
-                b->stat_tiles = n1; b->stat_tile_slots = 0; b->stat_tiles2 = 0; b->stat_tile2_slots = 0;
-                const uint64_t* lk = l1.as<u64>(); const uint32_t* lw = c1.as<u32>();
-                uint64_t n_last = n1; uint32_t last_bases = tile_bases, last_span = span;
-                DevBuf l2(stream), c2(stream);
-                if (b->span2 && n1) {
-                    const uint32_t kk2 = k + b->span2 - 1, n_sub = span / b->span2;
-                    PhaseScope ps(b->prof, PH_EXPAND_MID, stream);
-                    TileLevelScope tl;
-                    DevBuf mk(stream), mw(stream);
-                    uint64_t n_mid = 0, n2 = 0, d2 = 0;
-                    DevBuf mid_counts(stream);         // (the first partition pass's digit counts per tile, made while the records are written)
-                    KCHECK(table_list_to_tagged_records(lk, lw, n1, tile_bases, kk2, n_sub, b->span2, b->rc, mk, mw, &n_mid, stream, 0, &mid_counts));
-                    rc = sorted_fail("mid") ? KATOME_E_UNSUPPORTED
-                        : tagged_records_sorted(mk, mw, n_mid, kk2, b->rc, spr, true, l2, c2, &n2, &d2, stream, mid_counts.as<u32>());
-                    if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
-                    if (rc == KATOME_OK) { b->stat_tiles2 = n2; lk = l2.as<u64>(); lw = c2.as<u32>(); n_last = n2; last_bases = kk2; last_span = b->span2; }
-                }
-                if (rc == KATOME_OK) {
-                    PhaseScope ps(b->prof, PH_EXPAND_TILES, stream);
-                    DevBuf kr(stream), kw(stream);
-                    uint64_t n_rec = 0, n_rest = 0;
-                    KCHECK(rest_valid(b, &n_rest, stream));
-                    DevBuf last_counts(stream);
-                    KCHECK(table_list_to_tagged_records(lk, lw, n_last, last_bases, k, last_span, 1, b->rc, kr, kw, &n_rec, stream, n_rest, &last_counts));
-                    l2.release(); c2.release();
-                    if (n_rest) {             // the left-over windows behind them (tagged records already), one each
-                        KCHECK_HIP(hipMemcpyAsync(kr.as<u64>() + n_rec * (b->nw + 1), b->rest_k.p, n_rest * 8 * (b->nw + 1), hipMemcpyDeviceToDevice, stream));
-                        KCHECK(dev_fill_u32(kw.as<u32>() + n_rec, n_rest, 1u, stream));
-                        n_rec += n_rest;
-                    }
-                    rc = sorted_fail("last") ? KATOME_E_UNSUPPORTED
-                        : tagged_records_sorted(kr, kw, n_rec, k, b->rc, spr, false, b->edge_key, raw_seq, &b->n_edges, &distinct, stream, last_counts.as<u32>());
-                    if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
-                }
-                if (rc == KATOME_OK) {
-                    l1.release(); c1.release();
-                    rest_reset(b);
-                    b->stat_kmers = distinct; b->stat_kmer_slots = 0;
-                    counted_seen = true;
-                } else {
-                    // a level below gave up: the distinct big tiles go into the tile table with their counts and their numbers, and the
-                    // build goes on from there as if they had been counted in it
-                    b->n_edges = 0;
-                    l2.release(); c2.release();
-                    const uint32_t nwt = (uint32_t)key_words_for_k(tile_bases);
-                    DevBuf keys(stream), pairs(stream);
-                    KCHECK(keys.alloc(n1 * 8 * nwt + 16)); KCHECK(pairs.alloc(n1 * 16 + 16));
-                    KCHECK(table_tagged_to_pairs(l1.as<u64>(), n1, nwt, spr, keys.as<u64>(), pairs.as<u64>(), stream));
-                    l1.release();
-                    SeenOrigin origin;
-                    origin.pairs = pairs.as<u64>(); origin.rc = b->rc;
-                    KCHECK(builder_insert(b, b->tiles, b->tiles_ready, nwt, b->s.table_slots_hint / 4, keys.as<u64>(), c1.as<u32>(), n1, &origin, PH_INSERT_TILES, stream));
-                }
-            }
-        }
-        if (!counted_seen && sorted_count && b->first_seen && b->tiles_ready && !b->table_ready && b->nw <= 2 && !b->var_seq_base && !b->var_prefix && !b->direct_edges &&
-            b->seen_read_len >= b->s.k) {
-            uint64_t n_tiles = 0;
-            KCHECK(table_occupied(b->tiles, &n_tiles, stream));
-            const uint64_t bound = n_tiles * b->span;
-            if (bound >= (1ull << 22) || (sorted_count == 2 && bound)) {       // (the last level's own size is checked where its records are made)
-                Table* last = nullptr; uint32_t last_span = 1;
-                KCHECK(expand_to_last_level(b, &last, &last_span, stream));
-                uint64_t distinct = 0;
-                int rc = KATOME_OK;
-                {
-                    PhaseScope ps(b->prof, PH_EXPAND_TILES, stream);
-                    uint64_t n_rest = 0;
-                    KCHECK(rest_valid(b, &n_rest, stream));
-                    rc = tiles_to_edges_sorted_seen(*last, b->s.k, last_span, b->rc, 2ull * (b->seen_read_len - b->s.k + 1), b->edge_key, raw_seq, &b->n_edges,
-                                                    &distinct, stream, n_rest ? b->rest_k.as<u64>() : nullptr, n_rest);
-                    if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
-                }
-                if (rc == KATOME_OK) {
-                    b->tiles.release(); b->tiles2.release();
-                    b->tiles_ready = false; b->tiles2_ready = false;
-                    rest_reset(b);
-                    b->stat_kmers = distinct; b->stat_kmer_slots = 0;
-                    counted_seen = true;
-                } else {
-                    b->n_edges = 0;               // (numbers that do not pack, or a group too large: the table counts, from the tiles that are still there)
-                }
-            }
-        }
-        if (!counted && !counted_seen) KCHECK(expand_tiles(b, stream));
-        if (!counted && (b->table_ready || counted_seen)) {
-            if (!counted_seen) {
-                KCHECK(table_occupied(b->table, &b->stat_kmers, stream));
-                b->stat_kmer_slots = b->table.cap;
-                PhaseScope ps(b->prof, PH_EMIT_EDGES, stream);
-                // (first-seen order: the threshold is applied after the numbering, as the reference's retain passes do)
-                if (b->first_seen) KCHECK(table_emit_edges(b->table, b->s.k, b->rc, 0, b->edge_key, raw_w, &b->n_edges, stream, &raw_seq));
-                else KCHECK(table_emit_edges(b->table, b->s.k, b->rc, b->prune_weight, b->edge_key, b->edge_weight, &b->n_edges, stream));
-            }
-            for (int i = 0; i < 2; ++i) { b->scratch_k[i].release(); b->scratch_w[i].release(); }
-            b->table.release();                       // the table is spent; its memory serves the sort
-            b->table_ready = false;
-            PhaseScope ps(b->prof, PH_SORT_EDGES, stream);
-            if (b->first_seen) {
-                // sort (key, position) and bring weight and sequence number along through the positions
-                if (b->n_edges >= (1ull << 32)) { set_error("first-seen order: more than 2^32 edges on one GPU"); return KATOME_E_UNSUPPORTED; }
-                DevBuf idx(stream);
-                KCHECK(idx.alloc((b->n_edges + 1) * 4));
-                KCHECK(dev_iota(idx.as<u32>(), b->n_edges, stream));
-                KCHECK(dev_sort_bufs(b->edge_key, &idx, b->n_edges, b->nw, 2 * b->s.k, stream));
-                KCHECK(b->edge_weight.alloc((b->n_edges + 1) * 4, stream));
-                KCHECK(b->edge_seq.alloc((b->n_edges + 1) * 8, stream));
-                KCHECK(dev_gather_seq_weight(raw_seq.as<u64>(), idx.as<u32>(), b->n_edges, b->edge_seq.as<u64>(), b->edge_weight.as<u32>(), stream));
-            } else {
-                KCHECK(dev_sort_bufs(b->edge_key, &b->edge_weight, b->n_edges, b->nw, 2 * b->s.k, stream, true));
-            }
-        } else if (!counted) {
-            KCHECK(b->edge_key.alloc(16, stream)); KCHECK(b->edge_weight.alloc(16, stream));
+        DevBuf raw_seq(stream);                  // (first-seen order: the edges' sequence numbers and weights until the sort tail)
+        if (!b->first_seen) {
+            if (b->tile_recs_n) KCHECK(edges_from_tile_recs(b, &counted, stream));
+            if (!counted) KCHECK(edges_from_tile_table(b, &counted, stream));
+            if (!counted) KCHECK(edges_from_table(b, false, raw_seq, stream));
+        } else {
+            if (b->tile_recs_n) KCHECK(seen_edges_from_tile_recs(b, raw_seq, &counted, stream));
+            if (!counted) KCHECK(seen_edges_from_tile_table(b, raw_seq, &counted, stream));
+            KCHECK(edges_from_table(b, counted, raw_seq, stream));
         }
         b->edges_ready = true;
     }

@@ -79,6 +79,7 @@ int builder_insert(katome_builder* b, Table& table, bool& ready, uint32_t nw, ui
                    const uint32_t* d_weights, uint64_t n, SeenOrigin* origin, int phase, hipStream_t stream);
 // big tiles -> mid tiles (when the span is large); leaves the tiles that hold k-mers directly in `*last`
 int expand_to_last_level(katome_builder* b, Table** last, uint32_t* last_span, hipStream_t stream);
+void release_tile_tables(katome_builder* b);     // b->tiles and b->tiles2 are spent
 int expand_tiles(katome_builder* b, hipStream_t stream);       // every distinct tile adds its count to its k-mers (b->table); the tile tables go
 int flush_rest(katome_builder* b, hipStream_t stream);
 int keep_tile_recs(katome_builder* b, const uint64_t* d_records, uint64_t n, uint32_t nwt, bool* kept, hipStream_t stream);   // a batch's valid tile records behind those kept so far
@@ -87,6 +88,8 @@ int tile_recs_valid(katome_builder* b, uint64_t* n, hipStream_t stream);      //
 int tile_recs_to_kmer_records(katome_builder* b, DevBuf& keys, DevBuf& weights, uint64_t* n_records, uint64_t extra_room, hipStream_t stream,
                               DevBuf* first_counts = nullptr, bool rep = false);      // (rep: the k-mer records in their representative orientation)
 int sorted_count_mode();            // KATOME_SORTED_COUNT
+bool sorting_pays(uint64_t n);       // n records are worth counting by sorting
+bool lds_route_takes(uint64_t n);    // ... and not too many for the LDS counting route
 int sorted_tiles_mode();            // KATOME_SORTED_TILES
 bool tile_recs_shape(uint32_t nwt, uint32_t nw, bool first_seen);   // tile / k-mer word counts whose levels are all counted by sorting
 bool sorted_fail(const char* level);     // KATOME_SORTED_FAIL (tests)

@@ -376,8 +376,7 @@ int route_weighted(katome_dist_builder* d, int xphase, const DevBuf& keys, const
         if (d->first_seen) { origin.pairs = sl.rp.as<u64>(); origin.rc = d->rc; }
         // (room for what this rank sends and an eighth more to begin with; KATOME_SORTED_COUNT=2 -- tests -- starts from nothing,
         // so that every slice makes the array grow)
-        static const bool tight = getenv("KATOME_SORTED_COUNT") && atoi(getenv("KATOME_SORTED_COUNT")) == 2;
-        if (sl.nR && collect) KCHECK(collect->append(sl.rk.p, sl.rw.p, sl.nR, nwr, tight ? 0 : n_rec + n_rec / 8 + (1u << 20), stream));
+        if (sl.nR && collect) KCHECK(collect->append(sl.rk.p, sl.rw.p, sl.nR, nwr, sorted_count_mode() == 2 ? 0 : n_rec + n_rec / 8 + (1u << 20), stream));
         else if (sl.nR) KCHECK(builder_insert(b, table, ready, nwr, hint, sl.rk.as<u64>(), sl.rw.as<u32>(), sl.nR, d->first_seen ? &origin : nullptr, phase, stream));
         return KATOME_OK;
     };
@@ -448,12 +447,11 @@ int route_owned(katome_dist_builder* d, int xphase, const DevBuf& keys, const De
     KCHECK_HIP(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
     for (auto& sl : slot) KCHECK_HIP(hipEventCreateWithFlags(&sl.arrived, hipEventDisableTiming));
     d->comm->use_stream(X);
-    static const bool tight = getenv("KATOME_SORTED_COUNT") && atoi(getenv("KATOME_SORTED_COUNT")) == 2;
     auto take_slice = [&](Slot& sl) -> int {
         KCHECK_HIP(hipStreamWaitEvent(stream, sl.arrived, 0));
         trace_words("kmers received: keys", d->rank(), sl.rk.p, sl.nR * nwr, stream);
         trace_words("kmers received: weights", d->rank(), sl.rw.p, sl.nR / 2, stream);
-        if (sl.nR) KCHECK(collect.append(sl.rk.p, sl.rw.p, sl.nR, nwr, tight ? 0 : n_rec + n_rec / 8 + (1u << 20), stream));
+        if (sl.nR) KCHECK(collect.append(sl.rk.p, sl.rw.p, sl.nR, nwr, sorted_count_mode() == 2 ? 0 : n_rec + n_rec / 8 + (1u << 20), stream));
         return KATOME_OK;
     };
     int rc = KATOME_OK;
@@ -484,16 +482,14 @@ int route_owned(katome_dist_builder* d, int xphase, const DevBuf& keys, const De
 // may the k-mer records that arrive be kept and counted by sorting (katome_dev_edges' rule: one-word k-mers by packed key,
 // nothing in the k-mer table yet)?
 bool may_collect(const katome_dist_builder* d) {
-    static const int sorted_count = getenv("KATOME_SORTED_COUNT") ? atoi(getenv("KATOME_SORTED_COUNT")) : 1;
-    return sorted_count && !d->first_seen && d->nw == 1 && !d->b->table_ready;
+    return sorted_count_mode() && !d->first_seen && d->nw == 1 && !d->b->table_ready;
 }
 // the collected records of this rank's k-mers -> its sorted edges (lds_count_kernel), or, out of that kernel's range, into the
 // k-mer table after all.  No collective in here: every rank decides for itself.
 int count_collected(katome_dist_builder* d, Collected& c, hipStream_t stream) {
-    static const int sorted_count = getenv("KATOME_SORTED_COUNT") ? atoi(getenv("KATOME_SORTED_COUNT")) : 1;
     katome_builder* b = d->b;
     if (c.n == 0) return KATOME_OK;
-    if ((c.n >= (1ull << 22) || sorted_count == 2) && (c.n >> 21) <= 2900) {
+    if (sorting_pays(c.n) && lds_route_takes(c.n)) {
         uint64_t distinct = 0;
         int rc;
         {
@@ -563,8 +559,7 @@ int expand_and_route_kmers(katome_dist_builder* d, uint32_t span, hipStream_t st
             else KCHECK(table_tiles_to_records_fast(*last, k, last_span, d->rc, keys, weights, &n_rec, stream));      // (same records, any order)
         }
         trace_words("last level after: slots", d->rank(), last->slots.p, last->cap * last->slot_bytes() / 8, stream);
-        b->tiles.release(); b->tiles2.release();
-        b->tiles_ready = false; b->tiles2_ready = false;
+        release_tile_tables(b);
     }
     if (getenv("KATOME_DIST_STATS"))
         fprintf(stderr, "[dist] rank %d of %d: %llu distinct tiles, %llu on the last level -> %llu k-mer records to route\n", d->rank(), world,
@@ -1183,11 +1178,10 @@ int katome_dist_finalize(katome_dist_builder* d, katome_dist_graph* out, void* s
         uint64_t n_rec = 0;
         OwnerSplit split;
         bool split_used = false;
-        static const int sorted_count = getenv("KATOME_SORTED_COUNT") ? atoi(getenv("KATOME_SORTED_COUNT")) : 1;
         // (owner split: grouped by the hash that names the owner, every group's keys written into its owner's stretch: no partition pass
         // before the exchange; KATOME_DIST_OWNER_SPLIT=0: by the whole k-mer's hash, then route_weighted's partition)
         static const bool owner_split_on = !getenv("KATOME_DIST_OWNER_SPLIT") || atoi(getenv("KATOME_DIST_OWNER_SPLIT")) != 0;
-        if (b->tile_recs_n && (!may_collect(d) || (b->tile_recs_n * b->span < (1ull << 22) && sorted_count != 2))) KCHECK(flush_tile_recs(b, stream));
+        if (b->tile_recs_n && (!may_collect(d) || !sorting_pays(b->tile_recs_n * b->span))) KCHECK(flush_tile_recs(b, stream));
         if (b->tile_recs_n) {
             // the tiles kept as records: every level by sorting, down to this rank's distinct k-mers
             DevBuf rk(stream), rw(stream);
@@ -1211,15 +1205,14 @@ int katome_dist_finalize(katome_dist_builder* d, katome_dist_graph* out, void* s
             uint64_t n_tiles = 0;
             KCHECK(table_occupied(b->tiles, &n_tiles, stream));
             const uint64_t bound = n_tiles * b->span;
-            if ((bound >= (1ull << 22) || (sorted_count == 2 && bound)) && (bound >> 21) <= 2900) {
+            if (sorting_pays(bound) && lds_route_takes(bound)) {
                 Table* last = nullptr; uint32_t last_span = 1;
                 KCHECK(expand_to_last_level(b, &last, &last_span, stream));
                 DevBuf rk(stream), rw(stream);
                 uint64_t n_win = 0, distinct = 0;
                 PhaseScope ps(b->prof, PH_EXPAND_TILES, stream);
                 KCHECK(table_tiles_to_records_fast(*last, k, last_span, d->rc, rk, rw, &n_win, stream));
-                b->tiles.release(); b->tiles2.release();
-                b->tiles_ready = false; b->tiles2_ready = false;
+                release_tile_tables(b);
                 if (owner_split_on) { split.n_parts = (uint32_t)world; split.core_shift = 2; split.core_bases = k - 2; split_used = true; }
                 KCHECK(records_to_edges_sorted(rk, rw, n_win, k, false, 0, keys, weights, &n_rec, &distinct, stream, split_used ? &split : nullptr));
             }
