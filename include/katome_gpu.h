@@ -364,7 +364,10 @@ int katome_dev_standardize_contigs(katome_builder *b, void *stream);
 int katome_dev_standardize_edges(katome_builder *b, uint64_t original_genome_length, uint32_t threshold, void *stream);
 
 /* host result of katome_shrink_files / katome_shrink_packed: the build (with the pruning the flags ask for) followed by
- * Shrinkable::shrink, see katome_dev_shrink below for what the arrays mean.  Owned by the library until katome_contigs_free */
+ * Shrinkable::shrink, see katome_dev_shrink below for what the arrays mean.  Owned by the library until katome_contigs_free.
+ * With settings.n_devices > 1 a FIRST_SEEN_ORDER build is gathered to one GPU and shrunk there (KATOME_SHRINK_AUTO); with
+ * KATOME_DIST_SHRINK=sharded a build in either numbering is shrunk on the sharded graph (katome_dist_shrink, the fast form;
+ * edges in the order of their head edges, nodes by new id), KATOME_DIST_SHRINK=gather gathers and runs the fast form. */
 typedef struct {
     uint64_t n_nodes, n_edges, label_bytes, read_bytes;
     uint32_t k, key_words;
@@ -534,6 +537,44 @@ int  katome_dist_standardize_contigs(katome_dist_builder *d, katome_dist_graph *
 int  katome_dist_prune_weak_edges(katome_dist_builder *d, uint32_t threshold, katome_dist_graph *out, void *stream);
 int  katome_dist_standardize_edges(katome_dist_builder *d, uint64_t original_genome_length, uint32_t threshold,
                                    katome_dist_graph *out, void *stream);
+/* this rank's merged edges after katome_dist_shrink, device arrays owned by the builder (valid until its next
+ * katome_dist_shrink or destroy).  Node ids are the NEW ones: a surviving vertex's id is the number of surviving vertices
+ * with a smaller global id, so they run over [0, total_nodes).                                                      */
+typedef struct {
+    uint64_t n_edges, n_nodes;            /* on this rank: the merged edges whose head edge it holds, the surviving nodes it owns */
+    uint64_t total_edges, total_nodes;    /* ... of the whole shrunk graph                                          */
+    uint64_t label_bytes;
+    uint32_t key_words, _pad;
+    uint64_t *d_edge_src, *d_edge_dst;    /* new global node ids                                                     */
+    uint32_t *d_edge_weight;              /* the head edge's weight                                                  */
+    uint32_t *d_edge_kmers;               /* k-mers on the path                                                      */
+    uint64_t *d_edge_label_off;           /* [n_edges + 1]: edge i's compress_edge label at d_edge_label[off[i], off[i+1]) */
+    uint8_t  *d_edge_label;
+    uint64_t *d_edge_head_id;             /* the head edge's global index in the input graph: its petgraph index in
+                                             FIRST_SEEN_ORDER, by packed key the rank's edge base + its local index  */
+    uint64_t *d_node_id;                  /* [n_nodes] new id of every surviving node of this rank ...               */
+    uint64_t *d_node_key;                 /* ... and its (k-1)-mer, [n_nodes][key_words]                            */
+} katome_dist_contigs;
+typedef struct {
+    uint32_t rank_rounds;                 /* exchange rounds of the list ranking (grows with log2 of the longest path) */
+    uint32_t cycle_rounds;                /* rounds of the second ranking over the cycles of inner vertices (0: none)  */
+    uint64_t cycles;                      /* cycles of inner vertices in the whole graph                               */
+    uint64_t longest_path;                /* k-mers on the longest merged edge                                         */
+    uint64_t bytes_sent;                  /* bytes this rank sent to its peers during the call                         */
+} katome_dist_shrink_stats;
+/* Shrinkable::shrink in the traversal-free form of katome_dev_shrink_mode(KATOME_SHRINK_FAST) on the SHARDED graph, no
+ * gather (katome_amd/csrc/dist_shrink.hip): a finalized build in either numbering, straight after katome_dist_finalize or
+ * after katome_dist_remove_dead_paths and the katome_dist_standardize_* / katome_dist_prune_weak_edges stages, in any order.
+ * Every maximal straight path becomes one edge on the rank that holds its head edge (the edge whose source is not inner),
+ * spelling the whole path, with the head's weight; a cycle of inner vertices becomes a self-loop at its smallest global
+ * node id.  The paths are ranked by pointer jumping: the exchange rounds grow with log2 of the longest path.  The rank's
+ * graph is left as it is, so the other stages still run afterwards.  Ordered by d_edge_head_id (edges) and by new id
+ * (nodes), FIRST_SEEN_ORDER shares give array for array what katome_dev_shrink_mode(FAST) gives on one GPU.  A builder
+ * that was not finalized or whose shares were gathered gets KATOME_E_ARG; a share of 2^32 edges or nodes or more, node
+ * ids of 2^40 or more and a path of 2^32 k-mers or more give KATOME_E_UNSUPPORTED, on every rank.  Memory per rank is
+ * O(share).  KATOME_DIST_SHRINK_FAIL=<rank> (tests): that rank fails after the first ranking round, and every rank returns
+ * the error.  `out` and `stats` may be NULL.  Collective.                                                              */
+int  katome_dist_shrink(katome_dist_builder *d, katome_dist_contigs *out, katome_dist_shrink_stats *stats, void *stream);
 /* this rank's share of the graph as it stands (after katome_dist_finalize / katome_dist_remove_dead_paths / the stages) */
 int  katome_dist_current_graph(katome_dist_builder *d, katome_dist_graph *out);
 /* the rank's single-GPU builder underneath (per-phase kernel timing: katome_builder_profile*) */

@@ -73,6 +73,19 @@ class DistGraph(C.Structure):
                 ("d_edge_id", C.c_void_p), ("d_node_id", C.c_void_p), ("d_edge_age", C.c_void_p)]
 
 
+class DistContigs(C.Structure):
+    _fields_ = [("n_edges", C.c_uint64), ("n_nodes", C.c_uint64), ("total_edges", C.c_uint64), ("total_nodes", C.c_uint64),
+                ("label_bytes", C.c_uint64), ("key_words", C.c_uint32), ("_pad", C.c_uint32),
+                ("d_edge_src", C.c_void_p), ("d_edge_dst", C.c_void_p), ("d_edge_weight", C.c_void_p), ("d_edge_kmers", C.c_void_p),
+                ("d_edge_label_off", C.c_void_p), ("d_edge_label", C.c_void_p), ("d_edge_head_id", C.c_void_p),
+                ("d_node_id", C.c_void_p), ("d_node_key", C.c_void_p)]
+
+
+class DistShrinkStats(C.Structure):
+    _fields_ = [("rank_rounds", C.c_uint32), ("cycle_rounds", C.c_uint32), ("cycles", C.c_uint64), ("longest_path", C.c_uint64),
+                ("bytes_sent", C.c_uint64)]
+
+
 # the caller's transport (katome_comm_callbacks)
 A2A_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, u64p, u64p, C.c_void_p, u64p, u64p, C.c_uint64, C.c_int)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, u64p, C.c_uint64, C.c_int)
@@ -176,6 +189,7 @@ SYMBOLS = {
     "katome_dist_standardize_contigs": (_i, [_vp, C.POINTER(DistGraph), _vp]),
     "katome_dist_prune_weak_edges": (_i, [_vp, C.c_uint32, C.POINTER(DistGraph), _vp]),
     "katome_dist_standardize_edges": (_i, [_vp, C.c_uint64, C.c_uint32, C.POINTER(DistGraph), _vp]),
+    "katome_dist_shrink": (_i, [_vp, C.POINTER(DistContigs), C.POINTER(DistShrinkStats), _vp]),
     "katome_dist_exchange_count": (_u32, []),
     "katome_dist_exchange_name": (C.c_char_p, [_u32]),
     "katome_dist_exchange_read": (_i, [_vp, u64p]),

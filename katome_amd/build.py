@@ -300,6 +300,27 @@ class GpuContigs:
             _lib.lib().katome_contigs_free(cp)
         return c, c.read_bytes
 
+    @classmethod
+    def create_from_packed(cls, packed, n_reads, read_len, skip=None, reverse_complement=False, device=0, k=None,
+                           first_seen_order=False, remove_dead_paths=False, n_devices=1, ranks_share_device=False):
+        """The same from 2-bit packed reads (numpy uint8; katome_shrink_packed).  With n_devices > 1 the shrink runs on the
+        graph gathered to one GPU, or with KATOME_DIST_SHRINK=sharded in the traversal-free form on the sharded graph."""
+        s = make_settings(K_SIZE if k is None else k, InputFileType.Fastq, reverse_complement, 0, device,
+                          first_seen_order=first_seen_order, remove_dead_paths=remove_dead_paths, n_devices=n_devices,
+                          ranks_share_device=ranks_share_device)
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        skip_p = None
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.uint8)
+            skip_p = skip.ctypes.data
+        cp = C.POINTER(_lib.Contigs)()
+        _check(_lib.lib().katome_shrink_packed(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, C.byref(cp)))
+        try:
+            c = cls(cp)
+        finally:
+            _lib.lib().katome_contigs_free(cp)
+        return c, c.read_bytes
+
     def contigs(self):
         """sorted (sequence, weight): the parity observable"""
         return sorted(zip(self.edge_seq, (int(w) for w in self.edge_weight)))

@@ -1868,12 +1868,12 @@ static int graph_to_host(katome_builder* b, uint64_t read_bytes, katome_graph** 
 }
 
 // finalize (+ the pruning the flags ask for) + shrink, copied to host arrays
-static int contigs_to_host(katome_builder* b, uint64_t read_bytes, katome_contigs** out) {
+static int contigs_to_host(katome_builder* b, uint64_t read_bytes, katome_contigs** out, uint32_t shrink_mode = KATOME_SHRINK_AUTO) {
     katome_dev_graph dg;
     KCHECK(katome_dev_finalize(b, &dg, nullptr));
     if (b->s.flags & KATOME_FLAG_REMOVE_DEAD_PATHS) KCHECK(katome_dev_remove_dead_paths(b, &dg, nullptr, nullptr));
     katome_dev_contigs dc;
-    KCHECK(katome_dev_shrink(b, &dc, nullptr));
+    KCHECK(katome_dev_shrink_mode(b, shrink_mode, &dc, nullptr, nullptr));
     ContigsOwner* o = new (std::nothrow) ContigsOwner();
     if (!o) { set_error("out of host memory"); return KATOME_E_OOM; }
     memset(&o->c, 0, sizeof o->c);
@@ -1898,8 +1898,9 @@ static int contigs_to_host(katome_builder* b, uint64_t read_bytes, katome_contig
 struct Finish {
     katome_graph** graph; katome_contigs** contigs;
     const char* stages = nullptr; uint64_t genome_len = 0;
+    uint32_t shrink_mode = KATOME_SHRINK_AUTO;
     int operator()(katome_builder* b, uint64_t read_bytes) const {
-        return contigs ? contigs_to_host(b, read_bytes, contigs) : graph_to_host(b, read_bytes, graph, stages, genome_len);
+        return contigs ? contigs_to_host(b, read_bytes, contigs, shrink_mode) : graph_to_host(b, read_bytes, graph, stages, genome_len);
     }
 };
 
@@ -1922,7 +1923,88 @@ extern "C" {
 // out itself); in the reference's numbering every rank puts its share at its indices.  The stages after the build (d, c, w, e)
 // run on the sharded graph (dist_prune.hip, dist_stages.hip) with KATOME_DIST_STAGES=sharded or when the graph cannot be
 // gathered (2^32 edges or nodes and more); otherwise, and with KATOME_DIST_STAGES=gather, the graph is gathered to the first
-// GPU, where they run.  shrink always gathers.
+// GPU, where they run.  shrink gathers and runs the one-GPU form (AUTO: the exact one in first-seen order), unless
+// KATOME_DIST_SHRINK=sharded asks for the traversal-free form on the sharded graph (dist_shrink.hip; either numbering, no
+// gather): every rank's merged edges come over and are put in the order of their head edges, the nodes in the order of their
+// new ids -- in first-seen order array for array what the one-GPU fast form gives.  The two forms number their results
+// differently: nothing switches from one to the other without being asked.  KATOME_DIST_SHRINK=gather (first-seen order, for
+// comparisons): the gather, then the fast form on the first GPU.  KATOME_DIST_SHRINK_TRACE: the shrink's time per rank on stderr.
+struct RankShrunk {                                              // one rank's part of a result of katome_dist_shrink, on the host
+    std::vector<uint64_t> src, dst, off, head, nid, nkey;
+    std::vector<uint32_t> weight, kmers;
+    std::vector<uint8_t> label;
+    uint64_t total_edges = 0, total_nodes = 0;
+    uint32_t key_words = 1;
+};
+static int shrunk_to_host(katome_dist_builder* d, RankShrunk& P, hipStream_t stream) {
+    katome_dist_contigs c;
+    KCHECK(katome_dist_shrink(d, &c, nullptr, stream));
+    const uint64_t H = c.n_edges, NK = c.n_nodes, nw = c.key_words;
+    try {
+        P.src.resize(H); P.dst.resize(H); P.off.resize(H + 1); P.head.resize(H); P.nid.resize(NK); P.nkey.resize(NK * nw);
+        P.weight.resize(H); P.kmers.resize(H); P.label.resize(c.label_bytes);
+    } catch (const std::bad_alloc&) { set_error("out of host memory"); return KATOME_E_OOM; }
+    hipError_t e = hipSuccess;
+    auto down = [&](void* h, const void* dv, size_t bytes) { if (bytes && e == hipSuccess) e = hipMemcpyAsync(h, dv, bytes, hipMemcpyDeviceToHost, stream); };
+    down(P.src.data(), c.d_edge_src, H * 8); down(P.dst.data(), c.d_edge_dst, H * 8); down(P.off.data(), c.d_edge_label_off, (H + 1) * 8);
+    down(P.head.data(), c.d_edge_head_id, H * 8); down(P.nid.data(), c.d_node_id, NK * 8); down(P.nkey.data(), c.d_node_key, NK * 8 * nw);
+    down(P.weight.data(), c.d_edge_weight, H * 4); down(P.kmers.data(), c.d_edge_kmers, H * 4); down(P.label.data(), c.d_edge_label, c.label_bytes);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); return KATOME_E_DEVICE; }
+    P.total_edges = c.total_edges; P.total_nodes = c.total_nodes; P.key_words = c.key_words;
+    return KATOME_OK;
+}
+// the ranks' parts as one katome_contigs: edges in the order of their head edges' global indices, nodes at their new ids
+static int assemble_shrunk(std::vector<RankShrunk>& parts, uint32_t k, uint64_t read_bytes, katome_contigs** out) {
+    const uint32_t nw = parts.empty() ? 1 : parts[0].key_words;
+    const uint64_t TE = parts.empty() ? 0 : parts[0].total_edges, TN = parts.empty() ? 0 : parts[0].total_nodes;
+    std::vector<std::pair<uint64_t, std::pair<uint32_t, uint32_t>>> order;          // (head id, (rank, index there))
+    uint64_t lb = 0;
+    try {
+        order.reserve(TE);
+        for (size_t r = 0; r < parts.size(); ++r)
+            for (uint64_t i = 0; i < parts[r].head.size(); ++i) order.push_back({parts[r].head[i], {(uint32_t)r, (uint32_t)i}});
+    } catch (const std::bad_alloc&) { set_error("out of host memory"); return KATOME_E_OOM; }
+    std::sort(order.begin(), order.end());
+    for (auto& p : parts) lb += p.label.size();
+    ContigsOwner* o = new (std::nothrow) ContigsOwner();
+    if (!o) { set_error("out of host memory"); return KATOME_E_OOM; }
+    memset(&o->c, 0, sizeof o->c);
+    katome_contigs* c = &o->c;
+    bool oom = false;
+    auto take = [&](size_t bytes) -> void* { void* q = host_result_alloc(std::max<size_t>(bytes, 8)); if (q) o->mem.push_back(q); else oom = true; return q; };
+    uint64_t* src = (uint64_t*)take(TE * 8); uint64_t* dst = (uint64_t*)take(TE * 8); uint32_t* w = (uint32_t*)take(TE * 4);
+    uint32_t* km = (uint32_t*)take(TE * 4); uint64_t* off = (uint64_t*)take((TE + 1) * 8); uint8_t* lab = (uint8_t*)take(lb);
+    uint64_t* nkey = (uint64_t*)take(TN * 8 * nw); uint8_t* seen = (uint8_t*)take(TN);
+    if (oom) { katome_contigs_free(c); set_error("out of host memory"); return KATOME_E_OOM; }
+    bool bad = order.size() != TE;
+    uint64_t at = 0;
+    off[0] = 0;
+    for (uint64_t i = 0; i < order.size() && !bad; ++i) {
+        const RankShrunk& P = parts[order[i].second.first];
+        const uint32_t j = order[i].second.second;
+        const uint64_t n = P.off[j + 1] - P.off[j];
+        src[i] = P.src[j]; dst[i] = P.dst[j]; w[i] = P.weight[j]; km[i] = P.kmers[j];
+        if (at + n > lb || src[i] >= TN || dst[i] >= TN) { bad = true; break; }
+        memcpy(lab + at, P.label.data() + P.off[j], n);
+        at += n; off[i + 1] = at;
+    }
+    memset(seen, 0, TN);
+    uint64_t placed = 0;
+    for (auto& P : parts)
+        for (uint64_t j = 0; j < P.nid.size() && !bad; ++j) {
+            const uint64_t id = P.nid[j];
+            if (id >= TN || seen[id]) { bad = true; break; }
+            seen[id] = 1; ++placed;
+            for (uint32_t q = 0; q < nw; ++q) nkey[id * nw + q] = P.nkey[j * nw + q];
+        }
+    if (bad || placed != TN) { katome_contigs_free(c); set_error("sharded shrink: the ranks' merged edges or nodes do not fit together"); return KATOME_E_DEVICE; }
+    c->n_nodes = TN; c->n_edges = TE; c->label_bytes = lb; c->read_bytes = read_bytes; c->k = k; c->key_words = nw;
+    c->edge_src = src; c->edge_dst = dst; c->edge_weight = w; c->edge_kmers = km; c->edge_label_off = off; c->edge_label = lab; c->node_key = nkey;
+    *out = c;
+    return KATOME_OK;
+}
+
 template <class AddReads>
 static int build_multi(const katome_settings* s, const Finish& finish, uint64_t read_bytes, const AddReads& add_reads) {
     const int n = s->n_devices;
@@ -1932,15 +2014,18 @@ static int build_multi(const katome_settings* s, const Finish& finish, uint64_t 
     int n_visible = 0;
     KCHECK_HIP(hipGetDeviceCount(&n_visible));
     if (!share && s->device + n > n_visible) { set_error("n_devices = %d from device %d, but %d GPU(s) are visible", n, s->device, n_visible); return KATOME_E_DEVICE; }
-    if ((finish.contigs || (finish.stages && *finish.stages) || (s->flags & KATOME_FLAG_REMOVE_DEAD_PATHS)) && !first_seen) {
-        set_error("n_devices > 1: shrink and the stages after the build need KATOME_FLAG_FIRST_SEEN_ORDER (they run on the graph gathered in the reference's numbering)");
+    const char* shrink_route = getenv("KATOME_DIST_SHRINK");
+    const bool sharded_shrink = finish.contigs && shrink_route && !strcmp(shrink_route, "sharded");
+    const bool gather_fast = finish.contigs && shrink_route && !strcmp(shrink_route, "gather");
+    if (((finish.contigs && !sharded_shrink) || (finish.stages && *finish.stages) || (s->flags & KATOME_FLAG_REMOVE_DEAD_PATHS)) && !first_seen) {
+        set_error("n_devices > 1: shrink and the stages after the build need KATOME_FLAG_FIRST_SEEN_ORDER (they run on the graph gathered in the reference's numbering; KATOME_DIST_SHRINK=sharded shrinks a packed-key build)");
         return KATOME_E_ARG;
     }
     // first-seen order: shrink runs on the graph gathered to the first GPU, and so do the stages unless KATOME_DIST_STAGES or the
     // graph's size sends them to the sharded graph (decided after finalize); the build itself and remove_dead_paths do not
     // (KATOME_DIST_PRUNE=gather: the gathered route for those too)
     const char* prune_route = getenv("KATOME_DIST_PRUNE");
-    const bool direct = first_seen && !finish.contigs && !(finish.stages && *finish.stages) && !(prune_route && !strcmp(prune_route, "gather"));
+    const bool direct = first_seen && (!finish.contigs || sharded_shrink) && !(finish.stages && *finish.stages) && !(prune_route && !strcmp(prune_route, "gather"));
     std::vector<int> devices(n);
     for (int r = 0; r < n; ++r) devices[r] = share ? s->device : s->device + r;
     std::vector<katome_comm*> comms(n, nullptr);
@@ -1958,7 +2043,9 @@ static int build_multi(const katome_settings* s, const Finish& finish, uint64_t 
         std::vector<uint64_t> n_edges, node_base, n_nodes;
         GraphOwner* owner = nullptr; int alloc_rc = KATOME_OK;
         uint64_t total_edges = 0, total_nodes = 0;
+        std::vector<RankShrunk> shrunk;
     } sh;
+    if (sharded_shrink) sh.shrunk.resize(n);
     sh.rc.assign(n, KATOME_OK); sh.err.resize(n); sh.n_edges.assign(n, 0); sh.node_base.assign(n, 0); sh.n_nodes.assign(n, 0);
     auto body = [&](int r) -> int {
         KCHECK(use_device(devices[r]));
@@ -1985,10 +2072,16 @@ static int build_multi(const katome_settings* s, const Finish& finish, uint64_t 
             }
             if (gather) {
                 katome_builder* root = nullptr;
+                const auto t_gather = std::chrono::steady_clock::now();
                 if ((rc = katome_dist_gather(d, 0, &root, stream))) break;
                 if (r == 0) {
                     root->s.flags = s->flags; root->s.min_weight = s->min_weight;       // the stages the caller asked for run here
-                    rc = finish(root, read_bytes);
+                    Finish f = finish;
+                    if (gather_fast) f.shrink_mode = KATOME_SHRINK_FAST;
+                    rc = f(root, read_bytes);
+                    if (gather_fast && getenv("KATOME_DIST_SHRINK_TRACE"))
+                        fprintf(stderr, "[katome_dist_shrink] gather + fast form on rank 0: %.2f ms (result in host arrays)\n",
+                                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_gather).count());
                 }
                 break;
             }
@@ -1997,6 +2090,7 @@ static int build_multi(const katome_settings* s, const Finish& finish, uint64_t 
             if (first_seen && (s->flags & KATOME_FLAG_REMOVE_DEAD_PATHS)) {
                 if ((rc = katome_dist_remove_dead_paths(d, &g, nullptr, stream))) break;
             }
+            if (sharded_shrink) { rc = shrunk_to_host(d, sh.shrunk[r], stream); break; }
             for (const char* st = first_seen && finish.stages ? finish.stages : ""; *st && rc == KATOME_OK; ++st) {
                 switch (*st) {
                     case 'd': rc = katome_dist_remove_dead_paths(d, &g, nullptr, stream); break;
@@ -2105,6 +2199,7 @@ static int build_multi(const katome_settings* s, const Finish& finish, uint64_t 
     for (int r = 0; r < n && !rc; ++r)
         if (sh.rc[r] && sh.err[r] != "another rank of this build failed") { rc = sh.rc[r]; set_error("rank %d of %d: %s", r, n, sh.err[r].c_str()); }
     for (int r = 0; r < n && !rc; ++r) if (sh.rc[r]) { rc = sh.rc[r]; set_error("rank %d of %d: %s", r, n, sh.err[r].c_str()); }
+    if (rc == KATOME_OK && sharded_shrink) rc = assemble_shrunk(sh.shrunk, s->k, read_bytes, finish.contigs);
     if (sh.owner) {                                              // (the ranks' shares were copied out: no gathered route ran)
         if (rc == KATOME_OK && finish.graph) *finish.graph = &sh.owner->g;
         else katome_graph_free(&sh.owner->g);

@@ -51,6 +51,9 @@ struct katome_dist_builder {
     uint64_t n_src = 0;                      // this rank's nodes [0, n_src) have out-edges (ascending by key), the rest do not
     bool dead_paths_removed = false;         // katome_dist_remove_dead_paths has run to its fixpoint and no edge or node went since
     bool gathered = false;                   // katome_dist_gather has consumed the ranks' shares
+    // the last katome_dist_shrink's merged edges on this rank (dist_shrink.hip), kept until the next call or destroy
+    DevBuf sh_src, sh_dst, sh_weight, sh_kmers, sh_label_off, sh_label, sh_head, sh_node_id, sh_node_key;
+    uint64_t sh_edges = 0, sh_nodes = 0, sh_total_edges = 0, sh_total_nodes = 0, sh_label_bytes = 0;
 
     int world() const { return comm->world(); }
     int rank() const { return comm->rank(); }

@@ -12,7 +12,7 @@ import torch.distributed as dist
 
 from . import _lib
 from .build import KatomePanic, make_settings
-from .device import Builder, _ViewOwner, _ptr, _stream, _view
+from .device import Builder, DeviceContigs, _ViewOwner, _ptr, _stream, _view
 
 
 def _check(status):
@@ -172,6 +172,30 @@ class RankGraph:
         self.edge_age = _view(g.d_edge_age, (ne,), "<i8", owner, device) if g.d_edge_age else None
 
 
+class RankContigs:
+    """this rank's merged edges after ShardedBuilder.shrink() (zero-copy views of the builder's device arrays, valid until
+    the next shrink or close): the paths whose head edge this rank holds, with NEW global node ids, and the surviving nodes
+    it owns.  head_id: the head edge's global index in the input graph (petgraph index in the reference's numbering, the
+    rank's edge base + its local index by packed key).  stats: rank_rounds, cycle_rounds, cycles, longest_path, bytes_sent."""
+
+    def __init__(self, c, stats, owner, device):
+        ne, nn, nw = c.n_edges, c.n_nodes, c.key_words
+        self.n_edges, self.n_nodes, self.total_edges, self.total_nodes = ne, nn, c.total_edges, c.total_nodes
+        self.label_bytes, self.key_words = c.label_bytes, nw
+        self.edge_src = _view(c.d_edge_src, (ne,), "<i8", owner, device)
+        self.edge_dst = _view(c.d_edge_dst, (ne,), "<i8", owner, device)
+        self.edge_weight = _view(c.d_edge_weight, (ne,), "<i4", owner, device)
+        self.edge_kmers = _view(c.d_edge_kmers, (ne,), "<i4", owner, device)
+        self.edge_label_off = _view(c.d_edge_label_off, (ne + 1,), "<i8", owner, device)
+        self.edge_label = _view(c.d_edge_label, (c.label_bytes,), "|u1", owner, device)
+        self.edge_head_id = _view(c.d_edge_head_id, (ne,), "<i8", owner, device)
+        self.node_id = _view(c.d_node_id, (nn,), "<i8", owner, device)
+        self.node_key = _view(c.d_node_key, (nn, nw), "<i8", owner, device)
+        self.stats = {f: getattr(stats, f) for f, _ in _lib.DistShrinkStats._fields_}
+
+    sequences = DeviceContigs.sequences
+
+
 class _InnerBuilder(Builder):
     """the single-GPU builder underneath a ShardedBuilder (owned by it): profile counters, and -- on the root after
     gather() -- the stages of device.Builder"""
@@ -276,6 +300,13 @@ class ShardedBuilder(_ViewOwner):
         g = _lib.DistGraph()
         _check(_lib.lib().katome_dist_standardize_edges(self._h, original_genome_length, threshold, C.byref(g), _stream()))
         return RankGraph(g, self, self.tdev)
+
+    def shrink(self):
+        """Shrinkable::shrink in the traversal-free form (Builder.shrink(mode="fast")) on the sharded graph, no gather
+        (katome_dist_shrink) -> RankContigs; the rank's graph stays as it is"""
+        c, st = _lib.DistContigs(), _lib.DistShrinkStats()
+        _check(_lib.lib().katome_dist_shrink(self._h, C.byref(c), C.byref(st), _stream()))
+        return RankContigs(c, st, self, self.tdev)
 
     def graph(self):
         """this rank's share as it stands (katome_dist_current_graph)"""
