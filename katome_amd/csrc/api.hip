@@ -1,24 +1,17 @@
-// api.hip -- the C ABI of include/katome_gpu.h: the build driver behind `Build::create`
-// (reference src/katome/algorithms/builder.rs:42-54) and the PtGraph::create post-pass
-// (collections/graphs/pt_graph.rs:333-345), composed from the kernels in extract.hip, table.hip
-// and radix.hip.  No CPU fallback: every entry that needs the device fails with KATOME_E_DEVICE
-// when there is none.
+// api.hip -- the device half of the C ABI of include/katome_gpu.h (katome_dev_*, the counting levels, finalize): the
+// build driver behind `Build::create` (reference src/katome/algorithms/builder.rs:42-54) and the PtGraph::create
+// post-pass (collections/graphs/pt_graph.rs:333-345), composed from the kernels in extract.hip, table.hip and radix.hip.
+// The entries that take and return host memory are in host_build.cpp.  No CPU fallback: every entry that needs the
+// device fails with KATOME_E_DEVICE when there is none.
 #include <stdlib.h>
 
 #include <algorithm>
 #include <chrono>
-#include <new>
-#include <string>
-#include <condition_variable>
 #include <memory>
-#include <mutex>
-#include <thread>
+#include <new>
 #include <vector>
 
-#include <sys/mman.h>
-
 #include "builder.h"
-#include "comm.h"
 
 extern "C" {
 
@@ -98,10 +91,8 @@ uint32_t katome_tile_plan_limited(uint32_t k, uint32_t read_len, uint32_t max_ti
             const uint32_t s = (uint32_t)atoi(e);
             if (s >= 2 && s <= W && k + s - 1 <= max_bases) { best_s = s; best_cost = 0; }
         }
-        for (uint32_t s = 2; best_cost != 0 && s <= 33 && s <= W && k + s - 1 <= max_bases; ++s) {
-            bool breakable = s <= 16;
-            for (uint32_t d = 3; d <= 8 && !breakable; ++d) breakable = s % d == 0;
-            const uint32_t cost = W / s + W % s + (breakable ? 0 : 4);
+        for (uint32_t s = 2; best_cost != 0 && s <= TILE_SPAN_MAX && s <= W && k + s - 1 <= max_bases; ++s) {
+            const uint32_t cost = tile_cost(W, s);
             if (cost < best_cost || (cost == best_cost && s > best_s)) { best_cost = cost; best_s = s; }
         }
         if (best_cost != 0 && best_cost >= W) best_s = 1;
@@ -115,6 +106,31 @@ uint32_t katome_tile_plan(uint32_t k, uint32_t read_len, uint32_t* span, uint32_
     return katome_tile_plan_limited(k, read_len, 3, span, tiles, remainder);
 }
 uint32_t katome_tile_words(uint32_t k, uint32_t span) { return (uint32_t)key_words_for_k(k + span - 1); }
+
+}  // extern "C"
+
+// The same plan for reads of several lengths (`len`, none shorter than k): one span for the whole input, the one with the fewest
+// table insertions over all reads -- tiles from the front of every read + the windows left over.  1: tiling does not pay.
+uint32_t tile_span_for_lengths(uint32_t k, const uint32_t* len, uint64_t n_reads, uint64_t total_windows) {
+    if (getenv("KATOME_NO_TILES")) return 1;
+    std::vector<uint64_t> hist;                             // hist[W]: reads of W windows
+    uint64_t best = total_windows;                          // every window on its own: one insertion each
+    for (uint64_t r = 0; r < n_reads; ++r) {
+        const uint32_t W = len[r] - k + 1;
+        if (W >= hist.size()) hist.resize(W + 1, 0);
+        hist[W] += 1;
+    }
+    uint32_t span = 1;
+    for (uint32_t sp = 2; sp <= TILE_SPAN_MAX && k + sp - 1 <= 95; ++sp) {
+        uint64_t cost = 0;
+        for (size_t W = 1; W < hist.size(); ++W) cost += hist[W] * tile_cost((uint32_t)W, sp);
+        if (cost < best || (cost == best && span > 1)) { best = cost; span = sp; }
+    }
+    if (const char* e = getenv("KATOME_TILE_SPAN")) { const uint32_t sp = (uint32_t)atoi(e); if (sp >= 1 && k + sp - 1 <= 95) span = sp; }
+    return span;
+}
+
+extern "C" {
 
 int katome_dev_extract_tiles(katome_builder* b, const uint8_t* d_packed, uint64_t n_reads, uint32_t read_len, uint32_t span,
                              const uint8_t* d_skip, uint64_t* d_records, void* stream) {
@@ -358,7 +374,7 @@ static int region_passes(uint64_t table_bytes) {
 // BFCounter input: one edge per kept line and strand, never merged (add_single_edge_bfc, pt_graph.rs:201-213, calls
 // add_edge unconditionally).  d_fwd: the lines' k-mers as packed keys in line order, d_w their weights.  Leaves the
 // builder with its sorted edge list, as katome_dev_edges would.
-static int bfc_set_edges(katome_builder* b, const uint64_t* d_fwd, const uint32_t* d_w, uint64_t n_lines, hipStream_t stream) {
+int bfc_set_edges(katome_builder* b, const uint64_t* d_fwd, const uint32_t* d_w, uint64_t n_lines, hipStream_t stream) {
     const uint64_t E = n_lines * (b->rc ? 2 : 1);
     const uint32_t nw = b->nw;
     if (b->edges_ready || b->table_ready || b->tiles_ready) { set_error("BFCounter input cannot be mixed with counted reads"); return KATOME_E_ARG; }
@@ -1713,817 +1729,6 @@ int katome_dev_synth_reads(int device, uint64_t first_read, uint64_t n_reads, ui
                            double err_rate, uint32_t n_inject_percent, uint8_t* d_packed, uint8_t* d_skip, void* stream) {
     KCHECK(use_device(device));
     return launch_synth(first_read, n_reads, read_len, genome_len, err_rate, n_inject_percent, d_packed, d_skip, (hipStream_t)stream);
-}
-
-// ---- host-memory entry points ---------------------------------------------------------------------
-struct GraphOwner {            // katome_graph followed by what it owns
-    katome_graph g;
-    std::vector<void*> mem;
-};
-
-void katome_graph_free(katome_graph* g) {
-    if (!g) return;
-    GraphOwner* o = reinterpret_cast<GraphOwner*>(g);
-    for (void* p : o->mem) free(p);
-    delete o;
-}
-
-struct ContigsOwner {          // katome_contigs followed by what it owns
-    katome_contigs c;
-    std::vector<void*> mem;
-};
-void katome_contigs_free(katome_contigs* c) {
-    if (!c) return;
-    ContigsOwner* o = reinterpret_cast<ContigsOwner*>(c);
-    for (void* p : o->mem) free(p);
-    delete o;
-}
-
-}  // extern "C"
-
-// KATOME_TRACE_BUILD=1: wall time of the host entries' stages on stderr
-static void build_lap(const char* what, bool reset = false) {
-    static const bool on = getenv("KATOME_TRACE_BUILD") != nullptr;
-    static std::chrono::steady_clock::time_point last;
-    if (!on) return;
-    const auto now = std::chrono::steady_clock::now();
-    if (!reset) fprintf(stderr, "[build] %-28s %9.2f ms\n", what, std::chrono::duration<double, std::milli>(now - last).count());
-    last = now;
-}
-
-// Host memory for a result array.  A device -> host copy into pages the process has never touched runs at the rate one
-// thread takes page faults (~9 GB/s measured on the MI355X box; into touched pages, pinned or not, the same copy runs at
-// ~55 GB/s), so large arrays are taken 2 MiB-aligned, offered to the kernel as huge pages and first touched by several
-// threads at once.  Released with free().
-static void* host_result_reserve(size_t bytes) {          // (pages not touched yet)
-    const size_t big = (size_t)64 << 20, huge = (size_t)2 << 20;
-    if (bytes < big) return malloc(std::max<size_t>(bytes, 1));
-    void* p = nullptr;
-    if (posix_memalign(&p, huge, (bytes + huge - 1) / huge * huge) != 0) return nullptr;
-    (void)madvise(p, bytes, MADV_HUGEPAGE);
-    return p;
-}
-static void host_result_touch(void* p, size_t bytes) {
-    if (bytes < ((size_t)64 << 20)) return;
-    unsigned T = std::thread::hardware_concurrency();
-    T = std::max(1u, std::min(T ? T : 4u, 16u));
-    const size_t pages = (bytes + 4095) / 4096, per = (pages + T - 1) / T;
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < T; ++t)
-        th.emplace_back([=]() {
-            volatile char* c = static_cast<volatile char*>(p);
-            for (size_t pg = t * per; pg < std::min(pages, (t + 1) * per); ++pg) c[pg * 4096] = 0;
-        });
-    for (auto& x : th) x.join();
-}
-static void* host_result_alloc(size_t bytes) {
-    void* p = host_result_reserve(bytes);
-    if (p) host_result_touch(p, bytes);
-    return p;
-}
-
-// Several result arrays: while array i comes over PCIe, the pages of array i + 1 are being touched (a third of the time of
-// a 7 GB graph was the touching, done array by array in front of each copy).
-struct HostCopy { void** dst; const void* src; size_t bytes; void* h = nullptr; };
-template <class Owner> static int d2h_all(Owner* o, std::vector<HostCopy>& jobs) {
-    for (auto& j : jobs) {
-        j.h = host_result_reserve(j.bytes);
-        if (!j.h) { set_error("out of host memory"); return KATOME_E_OOM; }
-        o->mem.push_back(j.h);
-        *j.dst = j.h;
-    }
-    std::mutex m; std::condition_variable cv; size_t touched = 0;
-    std::thread toucher([&]() {
-        for (auto& j : jobs) {
-            host_result_touch(j.h, j.bytes);
-            { std::lock_guard<std::mutex> lk(m); ++touched; }
-            cv.notify_all();
-        }
-    });
-    int rc = KATOME_OK;
-    for (size_t i = 0; i < jobs.size(); ++i) {
-        { std::unique_lock<std::mutex> lk(m); cv.wait(lk, [&]() { return touched > i; }); }
-        if (rc == KATOME_OK && jobs[i].bytes && hipMemcpy(jobs[i].h, jobs[i].src, jobs[i].bytes, hipMemcpyDeviceToHost) != hipSuccess) {
-            set_error("device -> host copy failed: %s", hipGetErrorString(hipGetLastError()));
-            rc = KATOME_E_DEVICE;
-        }
-    }
-    toucher.join();
-    return rc;
-}
-
-template <class T, class Owner> static int d2h(Owner* o, const T** dst, const void* d_src, size_t count) {
-    T* h = (T*)host_result_alloc(std::max<size_t>(count, 1) * sizeof(T));
-    if (!h) { set_error("out of host memory"); return KATOME_E_OOM; }
-    o->mem.push_back(h);
-    if (count) KCHECK_HIP(hipMemcpy(h, d_src, count * sizeof(T), hipMemcpyDeviceToHost));
-    *dst = h;
-    return KATOME_OK;
-}
-
-// the stages of assemble_with_graph (asm/basic_assembler.rs:58-72) a host entry may ask for after the build, in the
-// order given: d = remove_dead_paths, c = standardize_contigs, w = remove_weak_edges(min_weight),
-// e = standardize_edges(original_genome_length, k, min_weight)
-static int run_stages(katome_builder* b, const char* stages, uint64_t genome_len) {
-    for (const char* st = stages ? stages : ""; *st; ++st) {
-        switch (*st) {
-            case 'd': KCHECK(katome_dev_remove_dead_paths(b, nullptr, nullptr, nullptr)); break;
-            case 'c': KCHECK(katome_dev_standardize_contigs(b, nullptr)); break;
-            case 'w': KCHECK(katome_dev_remove_weak_edges(b, b->s.min_weight, nullptr)); break;
-            case 'e': KCHECK(katome_dev_standardize_edges(b, genome_len, b->s.min_weight, nullptr)); break;
-            default: set_error("unknown stage '%c' (d, c, w, e)", *st); return KATOME_E_ARG;
-        }
-    }
-    return KATOME_OK;
-}
-
-static int graph_to_host(katome_builder* b, uint64_t read_bytes, katome_graph** out, const char* stages = nullptr, uint64_t genome_len = 0) {
-    katome_dev_graph dg;
-    if (stages && *stages && !b->first_seen) { set_error("stages after the build need KATOME_FLAG_FIRST_SEEN_ORDER"); return KATOME_E_ARG; }
-    build_lap("counting (H2D, kernels)");
-    KCHECK(katome_dev_finalize(b, &dg, nullptr));
-    build_lap("finalize");
-    if (b->s.flags & KATOME_FLAG_REMOVE_DEAD_PATHS) KCHECK(katome_dev_remove_dead_paths(b, &dg, nullptr, nullptr));
-    KCHECK(run_stages(b, stages, genome_len));
-    KCHECK(katome_dev_current_graph(b, &dg));
-    build_lap("stages after the build");
-    GraphOwner* o = new (std::nothrow) GraphOwner();
-    if (!o) { set_error("out of host memory"); return KATOME_E_OOM; }
-    memset(&o->g, 0, sizeof o->g);
-    katome_graph* g = &o->g;
-    g->n_nodes = dg.n_nodes; g->n_edges = dg.n_edges; g->read_bytes = read_bytes;
-    g->k = b->s.k; g->key_words = dg.key_words; g->label_stride = dg.label_stride;
-    std::vector<HostCopy> jobs = {
-        {(void**)&g->edge_src, dg.d_edge_src, dg.n_edges * 8}, {(void**)&g->edge_dst, dg.d_edge_dst, dg.n_edges * 8},
-        {(void**)&g->edge_weight, dg.d_edge_weight, dg.n_edges * 4},
-        {(void**)&g->edge_label, dg.d_edge_label, dg.n_edges * (size_t)dg.label_stride},
-        {(void**)&g->edge_key, dg.d_edge_key, dg.n_edges * 8 * (size_t)dg.key_words},
-        {(void**)&g->node_key, dg.d_node_key, dg.n_nodes * 8 * (size_t)dg.key_words}};
-    if (dg.d_edge_age) jobs.push_back({(void**)&g->edge_age, dg.d_edge_age, dg.n_edges * 4});
-    const int rc = d2h_all(o, jobs);
-    if (rc) { katome_graph_free(g); return rc; }
-    build_lap("graph to host arrays");
-    *out = g;
-    return KATOME_OK;
-}
-
-// finalize (+ the pruning the flags ask for) + shrink, copied to host arrays
-static int contigs_to_host(katome_builder* b, uint64_t read_bytes, katome_contigs** out, uint32_t shrink_mode = KATOME_SHRINK_AUTO) {
-    katome_dev_graph dg;
-    KCHECK(katome_dev_finalize(b, &dg, nullptr));
-    if (b->s.flags & KATOME_FLAG_REMOVE_DEAD_PATHS) KCHECK(katome_dev_remove_dead_paths(b, &dg, nullptr, nullptr));
-    katome_dev_contigs dc;
-    KCHECK(katome_dev_shrink_mode(b, shrink_mode, &dc, nullptr, nullptr));
-    ContigsOwner* o = new (std::nothrow) ContigsOwner();
-    if (!o) { set_error("out of host memory"); return KATOME_E_OOM; }
-    memset(&o->c, 0, sizeof o->c);
-    katome_contigs* c = &o->c;
-    c->n_nodes = dc.n_nodes; c->n_edges = dc.n_edges; c->label_bytes = dc.label_bytes; c->read_bytes = read_bytes;
-    c->k = b->s.k; c->key_words = dc.key_words;
-    int rc = KATOME_OK;
-    if ((rc = d2h(o, &c->edge_src, dc.d_edge_src, dc.n_edges)) || (rc = d2h(o, &c->edge_dst, dc.d_edge_dst, dc.n_edges)) ||
-        (rc = d2h(o, &c->edge_weight, dc.d_edge_weight, dc.n_edges)) || (rc = d2h(o, &c->edge_kmers, dc.d_edge_kmers, dc.n_edges)) ||
-        (rc = d2h(o, &c->edge_label_off, dc.d_edge_label_off, dc.n_edges ? dc.n_edges + 1 : 0)) ||
-        (rc = d2h(o, &c->edge_label, dc.d_edge_label, dc.label_bytes)) ||
-        (rc = d2h(o, &c->node_key, dc.d_node_key, dc.n_nodes * dc.key_words))) {
-        katome_contigs_free(c);
-        return rc;
-    }
-    if (dc.n_edges == 0) const_cast<uint64_t*>(c->edge_label_off)[0] = 0;       // (d2h hands out room for one entry even when asked for none)
-    *out = c;
-    return KATOME_OK;
-}
-
-// what a host entry hands back: the graph, or the graph after shrink
-struct Finish {
-    katome_graph** graph; katome_contigs** contigs;
-    const char* stages = nullptr; uint64_t genome_len = 0;
-    uint32_t shrink_mode = KATOME_SHRINK_AUTO;
-    int operator()(katome_builder* b, uint64_t read_bytes) const {
-        return contigs ? contigs_to_host(b, read_bytes, contigs, shrink_mode) : graph_to_host(b, read_bytes, graph, stages, genome_len);
-    }
-};
-
-// records per extraction batch: bounded by a slice of free device memory
-static uint64_t batch_records(uint32_t nw) {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return 1ull << 24;
-    free_b += dev_cached_bytes();
-    uint64_t r = (uint64_t)(free_b / 8) / (8ull * nw);
-    return std::min<uint64_t>(std::max<uint64_t>(r, 1ull << 20), 1ull << 30);
-}
-
-extern "C" {
-
-}  // extern "C"
-
-// settings.n_devices > 1: the sharded build (dist.hip) with the ranks as host threads of this call, one per GPU.  Reads are
-// split contiguously by index; every rank copies its own share to its GPU (`add_reads(rank, world, builder, stream)`: fixed- or
-// variable-length reads).  By packed key the host arrays are the ranks' shares one after the other (every rank copies its slice
-// out itself); in the reference's numbering every rank puts its share at its indices.  The stages after the build (d, c, w, e)
-// run on the sharded graph (dist_prune.hip, dist_stages.hip) with KATOME_DIST_STAGES=sharded or when the graph cannot be
-// gathered (2^32 edges or nodes and more); otherwise, and with KATOME_DIST_STAGES=gather, the graph is gathered to the first
-// GPU, where they run.  shrink gathers and runs the one-GPU form (AUTO: the exact one in first-seen order), unless
-// KATOME_DIST_SHRINK=sharded asks for the traversal-free form on the sharded graph (dist_shrink.hip; either numbering, no
-// gather): every rank's merged edges come over and are put in the order of their head edges, the nodes in the order of their
-// new ids -- in first-seen order array for array what the one-GPU fast form gives.  The two forms number their results
-// differently: nothing switches from one to the other without being asked.  KATOME_DIST_SHRINK=gather (first-seen order, for
-// comparisons): the gather, then the fast form on the first GPU.  KATOME_DIST_SHRINK_TRACE: the shrink's time per rank on stderr.
-struct RankShrunk {                                              // one rank's part of a result of katome_dist_shrink, on the host
-    std::vector<uint64_t> src, dst, off, head, nid, nkey;
-    std::vector<uint32_t> weight, kmers;
-    std::vector<uint8_t> label;
-    uint64_t total_edges = 0, total_nodes = 0;
-    uint32_t key_words = 1;
-};
-static int shrunk_to_host(katome_dist_builder* d, RankShrunk& P, hipStream_t stream) {
-    katome_dist_contigs c;
-    KCHECK(katome_dist_shrink(d, &c, nullptr, stream));
-    const uint64_t H = c.n_edges, NK = c.n_nodes, nw = c.key_words;
-    try {
-        P.src.resize(H); P.dst.resize(H); P.off.resize(H + 1); P.head.resize(H); P.nid.resize(NK); P.nkey.resize(NK * nw);
-        P.weight.resize(H); P.kmers.resize(H); P.label.resize(c.label_bytes);
-    } catch (const std::bad_alloc&) { set_error("out of host memory"); return KATOME_E_OOM; }
-    hipError_t e = hipSuccess;
-    auto down = [&](void* h, const void* dv, size_t bytes) { if (bytes && e == hipSuccess) e = hipMemcpyAsync(h, dv, bytes, hipMemcpyDeviceToHost, stream); };
-    down(P.src.data(), c.d_edge_src, H * 8); down(P.dst.data(), c.d_edge_dst, H * 8); down(P.off.data(), c.d_edge_label_off, (H + 1) * 8);
-    down(P.head.data(), c.d_edge_head_id, H * 8); down(P.nid.data(), c.d_node_id, NK * 8); down(P.nkey.data(), c.d_node_key, NK * 8 * nw);
-    down(P.weight.data(), c.d_edge_weight, H * 4); down(P.kmers.data(), c.d_edge_kmers, H * 4); down(P.label.data(), c.d_edge_label, c.label_bytes);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); return KATOME_E_DEVICE; }
-    P.total_edges = c.total_edges; P.total_nodes = c.total_nodes; P.key_words = c.key_words;
-    return KATOME_OK;
-}
-// the ranks' parts as one katome_contigs: edges in the order of their head edges' global indices, nodes at their new ids
-static int assemble_shrunk(std::vector<RankShrunk>& parts, uint32_t k, uint64_t read_bytes, katome_contigs** out) {
-    const uint32_t nw = parts.empty() ? 1 : parts[0].key_words;
-    const uint64_t TE = parts.empty() ? 0 : parts[0].total_edges, TN = parts.empty() ? 0 : parts[0].total_nodes;
-    std::vector<std::pair<uint64_t, std::pair<uint32_t, uint32_t>>> order;          // (head id, (rank, index there))
-    uint64_t lb = 0;
-    try {
-        order.reserve(TE);
-        for (size_t r = 0; r < parts.size(); ++r)
-            for (uint64_t i = 0; i < parts[r].head.size(); ++i) order.push_back({parts[r].head[i], {(uint32_t)r, (uint32_t)i}});
-    } catch (const std::bad_alloc&) { set_error("out of host memory"); return KATOME_E_OOM; }
-    std::sort(order.begin(), order.end());
-    for (auto& p : parts) lb += p.label.size();
-    ContigsOwner* o = new (std::nothrow) ContigsOwner();
-    if (!o) { set_error("out of host memory"); return KATOME_E_OOM; }
-    memset(&o->c, 0, sizeof o->c);
-    katome_contigs* c = &o->c;
-    bool oom = false;
-    auto take = [&](size_t bytes) -> void* { void* q = host_result_alloc(std::max<size_t>(bytes, 8)); if (q) o->mem.push_back(q); else oom = true; return q; };
-    uint64_t* src = (uint64_t*)take(TE * 8); uint64_t* dst = (uint64_t*)take(TE * 8); uint32_t* w = (uint32_t*)take(TE * 4);
-    uint32_t* km = (uint32_t*)take(TE * 4); uint64_t* off = (uint64_t*)take((TE + 1) * 8); uint8_t* lab = (uint8_t*)take(lb);
-    uint64_t* nkey = (uint64_t*)take(TN * 8 * nw); uint8_t* seen = (uint8_t*)take(TN);
-    if (oom) { katome_contigs_free(c); set_error("out of host memory"); return KATOME_E_OOM; }
-    bool bad = order.size() != TE;
-    uint64_t at = 0;
-    off[0] = 0;
-    for (uint64_t i = 0; i < order.size() && !bad; ++i) {
-        const RankShrunk& P = parts[order[i].second.first];
-        const uint32_t j = order[i].second.second;
-        const uint64_t n = P.off[j + 1] - P.off[j];
-        src[i] = P.src[j]; dst[i] = P.dst[j]; w[i] = P.weight[j]; km[i] = P.kmers[j];
-        if (at + n > lb || src[i] >= TN || dst[i] >= TN) { bad = true; break; }
-        memcpy(lab + at, P.label.data() + P.off[j], n);
-        at += n; off[i + 1] = at;
-    }
-    memset(seen, 0, TN);
-    uint64_t placed = 0;
-    for (auto& P : parts)
-        for (uint64_t j = 0; j < P.nid.size() && !bad; ++j) {
-            const uint64_t id = P.nid[j];
-            if (id >= TN || seen[id]) { bad = true; break; }
-            seen[id] = 1; ++placed;
-            for (uint32_t q = 0; q < nw; ++q) nkey[id * nw + q] = P.nkey[j * nw + q];
-        }
-    if (bad || placed != TN) { katome_contigs_free(c); set_error("sharded shrink: the ranks' merged edges or nodes do not fit together"); return KATOME_E_DEVICE; }
-    c->n_nodes = TN; c->n_edges = TE; c->label_bytes = lb; c->read_bytes = read_bytes; c->k = k; c->key_words = nw;
-    c->edge_src = src; c->edge_dst = dst; c->edge_weight = w; c->edge_kmers = km; c->edge_label_off = off; c->edge_label = lab; c->node_key = nkey;
-    *out = c;
-    return KATOME_OK;
-}
-
-template <class AddReads>
-static int build_multi(const katome_settings* s, const Finish& finish, uint64_t read_bytes, const AddReads& add_reads) {
-    const int n = s->n_devices;
-    const bool share = (s->flags & KATOME_FLAG_RANKS_SHARE_DEVICE) != 0, first_seen = (s->flags & KATOME_FLAG_FIRST_SEEN_ORDER) != 0;
-    if (n > KATOME_MAX_RANKS) { set_error("n_devices = %d: at most %d", n, KATOME_MAX_RANKS); return KATOME_E_UNSUPPORTED; }
-    KCHECK(use_device(s->device));
-    int n_visible = 0;
-    KCHECK_HIP(hipGetDeviceCount(&n_visible));
-    if (!share && s->device + n > n_visible) { set_error("n_devices = %d from device %d, but %d GPU(s) are visible", n, s->device, n_visible); return KATOME_E_DEVICE; }
-    const char* shrink_route = getenv("KATOME_DIST_SHRINK");
-    const bool sharded_shrink = finish.contigs && shrink_route && !strcmp(shrink_route, "sharded");
-    const bool gather_fast = finish.contigs && shrink_route && !strcmp(shrink_route, "gather");
-    if (((finish.contigs && !sharded_shrink) || (finish.stages && *finish.stages) || (s->flags & KATOME_FLAG_REMOVE_DEAD_PATHS)) && !first_seen) {
-        set_error("n_devices > 1: shrink and the stages after the build need KATOME_FLAG_FIRST_SEEN_ORDER (they run on the graph gathered in the reference's numbering; KATOME_DIST_SHRINK=sharded shrinks a packed-key build)");
-        return KATOME_E_ARG;
-    }
-    // first-seen order: shrink runs on the graph gathered to the first GPU, and so do the stages unless KATOME_DIST_STAGES or the
-    // graph's size sends them to the sharded graph (decided after finalize); the build itself and remove_dead_paths do not
-    // (KATOME_DIST_PRUNE=gather: the gathered route for those too)
-    const char* prune_route = getenv("KATOME_DIST_PRUNE");
-    const bool direct = first_seen && (!finish.contigs || sharded_shrink) && !(finish.stages && *finish.stages) && !(prune_route && !strcmp(prune_route, "gather"));
-    std::vector<int> devices(n);
-    for (int r = 0; r < n; ++r) devices[r] = share ? s->device : s->device + r;
-    std::vector<katome_comm*> comms(n, nullptr);
-    const char* transport = getenv("KATOME_COMM");
-    auto sync = std::make_shared<LocalGroup>(n);                 // host rendezvous of the rank threads, whatever moves the data
-    std::shared_ptr<LocalGroup> group;                           // (the local transport's own rendezvous, poisoned with `sync`)
-    if (share || (transport && !strcmp(transport, "local"))) {
-        group = std::make_shared<LocalGroup>(n);
-        for (int r = 0; r < n; ++r) KCHECK(make_local_comm(group, r, devices[r], &comms[r]));
-    } else {
-        KCHECK(make_rccl_comms_all(devices.data(), n, comms.data()));
-    }
-    struct Shared {
-        std::vector<int> rc; std::vector<std::string> err;
-        std::vector<uint64_t> n_edges, node_base, n_nodes;
-        GraphOwner* owner = nullptr; int alloc_rc = KATOME_OK;
-        uint64_t total_edges = 0, total_nodes = 0;
-        std::vector<RankShrunk> shrunk;
-    } sh;
-    if (sharded_shrink) sh.shrunk.resize(n);
-    sh.rc.assign(n, KATOME_OK); sh.err.resize(n); sh.n_edges.assign(n, 0); sh.node_base.assign(n, 0); sh.n_nodes.assign(n, 0);
-    auto body = [&](int r) -> int {
-        KCHECK(use_device(devices[r]));
-        hipStream_t stream = nullptr;
-        KCHECK_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        katome_settings mine = *s;
-        mine.device = devices[r];
-        katome_dist_builder* d = nullptr;
-        int rc = katome_dist_create(&mine, comms[r], &d);
-        do {
-            if (rc) break;
-            if ((rc = add_reads(r, n, d, stream))) break;
-            // a rank whose reads could not be taken (memory, reads the route does not take) must not leave the others waiting inside
-            // finalize's exchange: everybody meets here first, and a failed rank has poisoned the meeting
-            if (!sync->barrier()) { set_error("another rank of this build failed"); rc = KATOME_E_DEVICE; break; }
-            katome_dist_graph g;
-            if ((rc = katome_dist_finalize(d, &g, stream))) break;
-            bool gather = first_seen && !direct;
-            if (gather && !finish.contigs && finish.stages && *finish.stages) {
-                // (every rank sees the same totals and the same environment: they all take the same route)
-                const char* route = getenv("KATOME_DIST_STAGES");
-                const bool too_big = g.total_edges >= 0xFFFFFFFFull || g.total_nodes >= 0xFFFFFFFFull;
-                if ((route && !strcmp(route, "sharded")) || (too_big && !(route && !strcmp(route, "gather")))) gather = false;
-            }
-            if (gather) {
-                katome_builder* root = nullptr;
-                const auto t_gather = std::chrono::steady_clock::now();
-                if ((rc = katome_dist_gather(d, 0, &root, stream))) break;
-                if (r == 0) {
-                    root->s.flags = s->flags; root->s.min_weight = s->min_weight;       // the stages the caller asked for run here
-                    Finish f = finish;
-                    if (gather_fast) f.shrink_mode = KATOME_SHRINK_FAST;
-                    rc = f(root, read_bytes);
-                    if (gather_fast && getenv("KATOME_DIST_SHRINK_TRACE"))
-                        fprintf(stderr, "[katome_dist_shrink] gather + fast form on rank 0: %.2f ms (result in host arrays)\n",
-                                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_gather).count());
-                }
-                break;
-            }
-            // the reference's numbering without a gather: remove_dead_paths (if asked for) and the stages on the sharded graph, then
-            // every rank puts its edges and nodes at their indices in the host arrays
-            if (first_seen && (s->flags & KATOME_FLAG_REMOVE_DEAD_PATHS)) {
-                if ((rc = katome_dist_remove_dead_paths(d, &g, nullptr, stream))) break;
-            }
-            if (sharded_shrink) { rc = shrunk_to_host(d, sh.shrunk[r], stream); break; }
-            for (const char* st = first_seen && finish.stages ? finish.stages : ""; *st && rc == KATOME_OK; ++st) {
-                switch (*st) {
-                    case 'd': rc = katome_dist_remove_dead_paths(d, &g, nullptr, stream); break;
-                    case 'c': rc = katome_dist_standardize_contigs(d, &g, stream); break;
-                    case 'w': rc = katome_dist_prune_weak_edges(d, s->min_weight, &g, stream); break;
-                    case 'e': rc = katome_dist_standardize_edges(d, finish.genome_len, s->min_weight, &g, stream); break;
-                    default: set_error("unknown stage '%c' (d, c, w, e)", *st); rc = KATOME_E_ARG; break;      // (the same on every rank)
-                }
-            }
-            if (rc) break;
-            const bool pruned = g.d_edge_age != nullptr;      // (the ages come along once a stage that may remove edges has run)
-            // by packed key: rank by rank
-            sh.n_edges[r] = g.n_edges; sh.node_base[r] = g.node_base; sh.n_nodes[r] = g.n_nodes;
-            if (!sync->barrier()) { set_error("another rank of this build failed"); rc = KATOME_E_DEVICE; break; }
-            if (r == 0) {
-                GraphOwner* o = new (std::nothrow) GraphOwner();
-                if (!o) { set_error("out of host memory"); sh.alloc_rc = KATOME_E_OOM; }
-                else {
-                    memset(&o->g, 0, sizeof o->g);
-                    katome_graph* hg = &o->g;
-                    hg->n_nodes = g.total_nodes; hg->n_edges = g.total_edges; hg->read_bytes = read_bytes;
-                    hg->k = s->k; hg->key_words = g.key_words; hg->label_stride = g.label_stride;
-                    auto take = [&](size_t bytes) -> void* { void* q = host_result_alloc(bytes); if (q) o->mem.push_back(q); else sh.alloc_rc = KATOME_E_OOM; return q; };
-                    hg->edge_src = (uint64_t*)take(std::max<uint64_t>(g.total_edges, 1) * 8);
-                    hg->edge_dst = (uint64_t*)take(std::max<uint64_t>(g.total_edges, 1) * 8);
-                    hg->edge_weight = (uint32_t*)take(std::max<uint64_t>(g.total_edges, 1) * 4);
-                    hg->edge_label = (uint8_t*)take(std::max<uint64_t>(g.total_edges, 1) * (size_t)g.label_stride);
-                    hg->edge_key = (uint64_t*)take(std::max<uint64_t>(g.total_edges, 1) * 8 * g.key_words);
-                    hg->node_key = (uint64_t*)take(std::max<uint64_t>(g.total_nodes, 1) * 8 * g.key_words);
-                    if (pruned) hg->edge_age = (uint32_t*)take(std::max<uint64_t>(g.total_edges, 1) * 4);
-                    if (sh.alloc_rc) { set_error("out of host memory"); katome_graph_free(hg); o = nullptr; }
-                }
-                sh.owner = o;
-            }
-            if (!sync->barrier()) { set_error("another rank of this build failed"); rc = KATOME_E_DEVICE; break; }
-            if (!sh.owner) { rc = sh.alloc_rc ? sh.alloc_rc : KATOME_E_OOM; break; }
-            if (first_seen) {
-                // every edge / node at its petgraph index: the rank's share comes over in its own order and is placed on the host
-                katome_graph* hg = &sh.owner->g;
-                const uint64_t E = g.n_edges, N = g.n_nodes;
-                const uint32_t nwk = g.key_words, ls = g.label_stride;
-                std::vector<uint64_t> id(E), src(E), dst(E), key(E * nwk), nid(N), nkey(N * nwk), age(pruned ? E : 0);
-                std::vector<uint32_t> w(E);
-                std::vector<uint8_t> lab(E * (size_t)ls);
-                hipError_t e = hipSuccess;
-                auto down = [&](void* h, const void* dv, size_t bytes) { if (bytes && e == hipSuccess) e = hipMemcpyAsync(h, dv, bytes, hipMemcpyDeviceToHost, stream); };
-                down(id.data(), g.d_edge_id, E * 8); down(src.data(), g.d_edge_src, E * 8); down(dst.data(), g.d_edge_dst, E * 8);
-                down(w.data(), g.d_edge_weight, E * 4); down(lab.data(), g.d_edge_label, E * (size_t)ls); down(key.data(), g.d_edge_key, E * 8 * nwk);
-                down(nid.data(), g.d_node_id, N * 8); down(nkey.data(), g.d_node_key, N * 8 * nwk);
-                if (pruned) down(age.data(), g.d_edge_age, E * 8);
-                if (e == hipSuccess) e = hipStreamSynchronize(stream);
-                if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = KATOME_E_DEVICE; break; }
-                uint64_t* h_src = const_cast<uint64_t*>(hg->edge_src); uint64_t* h_dst = const_cast<uint64_t*>(hg->edge_dst);
-                uint32_t* h_w = const_cast<uint32_t*>(hg->edge_weight); uint8_t* h_lab = const_cast<uint8_t*>(hg->edge_label);
-                uint64_t* h_key = const_cast<uint64_t*>(hg->edge_key); uint64_t* h_nkey = const_cast<uint64_t*>(hg->node_key);
-                uint32_t* h_age = const_cast<uint32_t*>(hg->edge_age);
-                bool bad = false;
-                for (uint64_t i = 0; i < E; ++i) {
-                    const uint64_t at = id[i];
-                    if (at >= hg->n_edges) { bad = true; break; }
-                    h_src[at] = src[i]; h_dst[at] = dst[i]; h_w[at] = w[i];
-                    memcpy(h_lab + at * ls, lab.data() + i * (size_t)ls, ls);
-                    for (uint32_t q = 0; q < nwk; ++q) h_key[at * nwk + q] = key[i * nwk + q];
-                    if (pruned) { if (age[i] > 0xFFFFFFFFull) bad = true; h_age[at] = (uint32_t)age[i]; }
-                }
-                for (uint64_t j = 0; j < N && !bad; ++j) {
-                    const uint64_t at = nid[j];
-                    if (at >= hg->n_nodes) { bad = true; break; }
-                    for (uint32_t q = 0; q < nwk; ++q) h_nkey[at * nwk + q] = nkey[j * nwk + q];
-                }
-                if (bad) { set_error("sharded build: an index does not fit the host result (katome_graph.edge_age is 32 bits wide)"); rc = KATOME_E_UNSUPPORTED; }
-            } else {
-                uint64_t e0 = 0;
-                for (int p = 0; p < r; ++p) e0 += sh.n_edges[p];
-                katome_graph* hg = &sh.owner->g;
-                const uint64_t E = g.n_edges, N = g.n_nodes;
-                const uint32_t nwk = g.key_words, ls = g.label_stride;
-                hipError_t e = hipSuccess;
-                if (E) {
-                    if (e == hipSuccess) e = hipMemcpyAsync(const_cast<uint64_t*>(hg->edge_src) + e0, g.d_edge_src, E * 8, hipMemcpyDeviceToHost, stream);
-                    if (e == hipSuccess) e = hipMemcpyAsync(const_cast<uint64_t*>(hg->edge_dst) + e0, g.d_edge_dst, E * 8, hipMemcpyDeviceToHost, stream);
-                    if (e == hipSuccess) e = hipMemcpyAsync(const_cast<uint32_t*>(hg->edge_weight) + e0, g.d_edge_weight, E * 4, hipMemcpyDeviceToHost, stream);
-                    if (e == hipSuccess) e = hipMemcpyAsync(const_cast<uint8_t*>(hg->edge_label) + e0 * ls, g.d_edge_label, E * (size_t)ls, hipMemcpyDeviceToHost, stream);
-                    if (e == hipSuccess) e = hipMemcpyAsync(const_cast<uint64_t*>(hg->edge_key) + e0 * nwk, g.d_edge_key, E * 8 * nwk, hipMemcpyDeviceToHost, stream);
-                }
-                if (N && e == hipSuccess) e = hipMemcpyAsync(const_cast<uint64_t*>(hg->node_key) + g.node_base * nwk, g.d_node_key, N * 8 * nwk, hipMemcpyDeviceToHost, stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(stream);
-                if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = KATOME_E_DEVICE; }
-            }
-        } while (0);
-        if (d) katome_dist_destroy(d);
-        dev_retire_stream(stream);
-        (void)hipStreamDestroy(stream);
-        return rc;
-    };
-    std::vector<std::thread> threads;
-    for (int r = 0; r < n; ++r)
-        threads.emplace_back([&, r]() {
-            const int rc = body(r);
-            sh.rc[r] = rc;
-            if (rc) { sh.err[r] = get_error(); sync->poison(); if (group) group->poison(); }     // (ranks waiting at a host rendezvous give up)
-        });
-    for (auto& t : threads) t.join();
-    for (int r = 0; r < n; ++r) katome_comm_destroy(comms[r]);
-    int rc = KATOME_OK;
-    for (int r = 0; r < n && !rc; ++r)
-        if (sh.rc[r] && sh.err[r] != "another rank of this build failed") { rc = sh.rc[r]; set_error("rank %d of %d: %s", r, n, sh.err[r].c_str()); }
-    for (int r = 0; r < n && !rc; ++r) if (sh.rc[r]) { rc = sh.rc[r]; set_error("rank %d of %d: %s", r, n, sh.err[r].c_str()); }
-    if (rc == KATOME_OK && sharded_shrink) rc = assemble_shrunk(sh.shrunk, s->k, read_bytes, finish.contigs);
-    if (sh.owner) {                                              // (the ranks' shares were copied out: no gathered route ran)
-        if (rc == KATOME_OK && finish.graph) *finish.graph = &sh.owner->g;
-        else katome_graph_free(&sh.owner->g);
-    }
-    return rc;
-}
-
-static int build_packed_multi(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len,
-                              const uint8_t* skip, const Finish& finish, uint64_t read_bytes) {
-    const uint32_t stride = (read_len + 3) / 4;
-    return build_multi(s, finish, read_bytes, [&](int r, int n, katome_dist_builder* d, hipStream_t stream) -> int {
-        uint64_t first = 0, cnt = 0;
-        katome_shard_range(n_reads, (uint32_t)n, (uint32_t)r, &first, &cnt);
-        DevBuf d_packed(stream), d_skip(stream);
-        KCHECK(d_packed.alloc(cnt * stride + 32));
-        if (cnt && hipMemcpyAsync(d_packed.p, packed + first * stride, cnt * stride, hipMemcpyHostToDevice, stream) != hipSuccess) { set_error("H2D copy failed"); return KATOME_E_DEVICE; }
-        if (skip) {
-            KCHECK(d_skip.alloc(cnt + 16));
-            if (cnt && hipMemcpyAsync(d_skip.p, skip + first, cnt, hipMemcpyHostToDevice, stream) != hipSuccess) { set_error("H2D copy failed"); return KATOME_E_DEVICE; }
-        }
-        return katome_dist_add_reads(d, d_packed.as<uint8_t>(), first, cnt, read_len, skip ? d_skip.as<uint8_t>() : nullptr, 0, stream);
-    });
-}
-
-// Reads of varying length on the sharded route: split contiguously by index, every rank copies its slice (its bytes, its byte
-// offsets rebased to the slice, its lengths) and starts at the global window of its first read.  Every rank takes part in the
-// collective katome_dist_add_reads_var, a rank without reads too.
-static int build_var_multi(const katome_settings* s, const HostReads& hr, const Finish& finish) {
-    const int n = s->n_devices;
-    std::vector<uint64_t> first_window(std::max(n, 1) + 1, 0);
-    for (int r = 0; r < n; ++r) {                        // (each rank's window offset: the windows of the ranks before it)
-        uint64_t first = 0, cnt = 0, w = 0;
-        katome_shard_range(hr.n_reads, (uint32_t)n, (uint32_t)r, &first, &cnt);
-        for (uint64_t i = first; i < first + cnt; ++i) w += hr.len[i] >= s->k ? hr.len[i] - s->k + 1 : 0;
-        first_window[r + 1] = first_window[r] + w;
-    }
-    // (KATOME_DIST_VAR_BATCH_WINDOWS: tests -- many small batches)
-    const uint64_t batch = getenv("KATOME_DIST_VAR_BATCH_WINDOWS") ? strtoull(getenv("KATOME_DIST_VAR_BATCH_WINDOWS"), nullptr, 10) : 0;
-    return build_multi(s, finish, hr.read_bytes, [&](int r, int n, katome_dist_builder* d, hipStream_t stream) -> int {
-        uint64_t first = 0, cnt = 0;
-        katome_shard_range(hr.n_reads, (uint32_t)n, (uint32_t)r, &first, &cnt);
-        const uint64_t b0 = hr.byte_off[first], bytes = hr.byte_off[first + cnt] - b0;
-        std::vector<uint64_t> off(cnt + 1, 0);
-        for (uint64_t i = 0; i < cnt; ++i) off[i] = hr.byte_off[first + i] - b0;
-        off[cnt] = bytes;
-        DevBuf d_packed(stream), d_off(stream), d_len(stream);
-        KCHECK(d_packed.alloc(bytes + 32)); KCHECK(d_off.alloc((cnt + 1) * 8)); KCHECK(d_len.alloc(cnt * 4 + 16));
-        if (cnt && (hipMemcpyAsync(d_packed.p, hr.packed + b0, bytes, hipMemcpyHostToDevice, stream) != hipSuccess ||
-                    hipMemcpyAsync(d_off.p, off.data(), (cnt + 1) * 8, hipMemcpyHostToDevice, stream) != hipSuccess ||
-                    hipMemcpyAsync(d_len.p, hr.len + first, cnt * 4, hipMemcpyHostToDevice, stream) != hipSuccess)) { set_error("H2D copy failed"); return KATOME_E_DEVICE; }
-        // (the copies come from pageable host memory the call owns until it returns; the reads are taken before that)
-        return katome_dist_add_reads_var(d, d_packed.as<uint8_t>(), bytes, d_off.as<u64>(), d_len.as<u32>(), cnt, first_window[r], batch, stream);
-    });
-}
-
-static int build_packed_impl(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len,
-                             const uint8_t* skip, const Finish& finish, const uint64_t* read_bytes_override = nullptr) {
-    if (!s || (!packed && n_reads)) { set_error("null argument"); return KATOME_E_ARG; }
-    KCHECK(check_k(s->k));
-    // (KATOME_FORCE_SHARDED=1: one GPU through the sharded route as well -- a world of one rank with the transport a larger
-    // world would use; testing)
-    if ((s->n_devices > 1 || (s->n_devices == 1 && getenv("KATOME_FORCE_SHARDED"))) && n_reads && read_len >= s->k) {
-        uint64_t read_bytes = 0;
-        if (read_bytes_override) read_bytes = *read_bytes_override;
-        else for (uint64_t r = 0; r < n_reads; ++r) if (!skip || !skip[r]) read_bytes += read_len;
-        return build_packed_multi(s, packed, n_reads, read_len, skip, finish, read_bytes);
-    }
-    if (n_reads && read_len < s->k) {
-        // only an ACCEPTED read can be too short (builder.rs:155-158 filters first)
-        bool any = !skip;
-        for (uint64_t r = 0; skip && r < n_reads && !any; ++r) any = skip[r] == 0;
-        if (any) { set_error("Read is too short!"); return KATOME_E_SHORT_READ; }
-        n_reads = 0;
-    }
-    katome_builder* b = nullptr;
-    KCHECK(katome_builder_create(s, &b));
-    build_lap("", true);
-    int rc = KATOME_OK;
-    do {
-        const uint32_t stride = (read_len + 3) / 4, W = read_len >= s->k ? read_len - s->k + 1 : 0;
-        uint64_t read_bytes = 0;
-        for (uint64_t r = 0; r < n_reads; ++r) if (!skip || !skip[r]) read_bytes += read_len;
-        DevBuf d_packed, d_skip, d_rec;
-        if ((rc = d_packed.alloc(n_reads * stride + 32))) break;
-        if (n_reads && hipMemcpy(d_packed.p, packed, n_reads * stride, hipMemcpyHostToDevice) != hipSuccess) { set_error("H2D copy failed"); rc = KATOME_E_DEVICE; break; }
-        if (skip) {
-            if ((rc = d_skip.alloc(n_reads + 16))) break;
-            if (n_reads && hipMemcpy(d_skip.p, skip, n_reads, hipMemcpyHostToDevice) != hipSuccess) { set_error("H2D copy failed"); rc = KATOME_E_DEVICE; break; }
-        }
-        if (n_reads && W) {
-            uint64_t reads_per_batch = std::max<uint64_t>(batch_records(b->nw) / W, 64);
-            reads_per_batch = (reads_per_batch / 64) * 64;       // keeps batch starts 16-byte aligned
-            if ((rc = d_rec.alloc(std::min(reads_per_batch, n_reads) * W * 8 * b->nw + 16))) break;
-            uint32_t span = 1, tiles = 0, rest = 0;
-            katome_tile_plan(s->k, read_len, &span, &tiles, &rest);
-            for (uint64_t r0 = 0; r0 < n_reads && !rc; r0 += reads_per_batch) {
-                const uint64_t nr = std::min(reads_per_batch, n_reads - r0);
-                if (span > 1) {       // tiled counting: W/span tile records per read, then the windows that are left over
-                    rc = katome_dev_count_tiles(b, d_packed.as<uint8_t>() + r0 * stride, nr, read_len, span,
-                                                skip ? d_skip.as<uint8_t>() + r0 : nullptr, nullptr);
-                    if (!rc && rest) {
-                        rc = katome_dev_extract_remainder(b, d_packed.as<uint8_t>() + r0 * stride, nr, read_len, span,
-                                                          skip ? d_skip.as<uint8_t>() + r0 : nullptr, d_rec.as<u64>(), nullptr);
-                        if (!rc) rc = katome_dev_insert(b, d_rec.as<u64>(), nr * rest, nullptr);
-                    }
-                } else {
-                    rc = katome_dev_extract_fixed(b, d_packed.as<uint8_t>() + r0 * stride, nr, read_len,
-                                                  skip ? d_skip.as<uint8_t>() + r0 : nullptr, d_rec.as<u64>(), nullptr);
-                    if (!rc) rc = katome_dev_insert(b, d_rec.as<u64>(), nr * W, nullptr);
-                }
-            }
-            if (rc) break;
-        }
-        d_rec.release(); d_packed.release(); d_skip.release();
-        rc = finish(b, read_bytes_override ? *read_bytes_override : read_bytes);
-    } while (0);
-    katome_builder_destroy(b);
-    return rc;
-}
-
-extern "C" {
-
-int katome_build_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len,
-                        const uint8_t* skip, katome_graph** out) {
-    if (!out) { set_error("null argument"); return KATOME_E_ARG; }
-    *out = nullptr;
-    return build_packed_impl(s, packed, n_reads, read_len, skip, Finish{out, nullptr});
-}
-int katome_build_packed_staged(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len,
-                               const uint8_t* skip, const char* stages, uint64_t original_genome_length, katome_graph** out) {
-    if (!out) { set_error("null argument"); return KATOME_E_ARG; }
-    *out = nullptr;
-    Finish f{out, nullptr};
-    f.stages = stages; f.genome_len = original_genome_length;
-    return build_packed_impl(s, packed, n_reads, read_len, skip, f);
-}
-int katome_shrink_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len,
-                         const uint8_t* skip, katome_contigs** out) {
-    if (!out) { set_error("null argument"); return KATOME_E_ARG; }
-    *out = nullptr;
-    return build_packed_impl(s, packed, n_reads, read_len, skip, Finish{nullptr, out});
-}
-
-int katome_ingest_files(const katome_settings* s, const char* const* paths, size_t n_paths, katome_reads** out) {
-    if (!s || !out || (!paths && n_paths)) { set_error("null argument"); return KATOME_E_ARG; }
-    *out = nullptr;
-    HostReads* hr = new (std::nothrow) HostReads();
-    if (!hr) { set_error("out of host memory"); return KATOME_E_OOM; }
-    int rc = ingest_files(s, paths, n_paths, *hr);
-    if (rc) { delete hr; return rc; }
-    struct Owner { katome_reads r; HostReads* hr; };
-    Owner* o = new (std::nothrow) Owner();
-    if (!o) { delete hr; set_error("out of host memory"); return KATOME_E_OOM; }
-    o->hr = hr;
-    o->r.n_records = hr->n_records; o->r.n_reads = hr->n_reads; o->r.read_bytes = hr->read_bytes;
-    o->r.packed_bytes = hr->packed_bytes; o->r.total_windows = hr->total_windows; o->r.fixed_len = hr->fixed_len; o->r._pad = 0;
-    o->r.packed = hr->packed; o->r.byte_off = hr->byte_off; o->r.len = hr->len;
-    *out = &o->r;
-    return KATOME_OK;
-}
-void katome_reads_free(katome_reads* r) {
-    if (!r) return;
-    struct Owner { katome_reads r; HostReads* hr; };
-    Owner* o = reinterpret_cast<Owner*>(r);
-    delete o->hr;
-    delete o;
-}
-
-}  // extern "C"
-
-static int build_files_impl(const katome_settings* s, const char* const* paths, size_t n_paths, const Finish& finish) {
-    if (!s || (!paths && n_paths)) { set_error("null argument"); return KATOME_E_ARG; }
-    HostReads hr;
-    build_lap("", true);
-    KCHECK(ingest_files(s, paths, n_paths, hr));           // path / parse / short-read errors surface before any GPU work
-    build_lap("ingest (host)");
-    if (s->file_type == 2) {
-        // BFCounter (create_bfc, builder.rs:79-115; add_read_bfc, pt_graph.rs:317-330): every kept line is a k-mer
-        // with a weight -> one edge per line and strand, exactly as add_single_edge_bfc (pt_graph.rs:201-213) adds them:
-        // lines naming the same k-mer, and a k-mer that is its own reverse complement, stay parallel edges.
-        katome_builder* b = nullptr;
-        KCHECK(katome_builder_create(s, &b));
-        int rc = KATOME_OK;
-        do {
-            if (hr.n_reads) {
-                DevBuf d_packed, d_w, d_rec;
-                if ((rc = d_packed.alloc(hr.packed_bytes + 32)) || (rc = d_w.alloc(hr.n_reads * 4)) || (rc = d_rec.alloc(hr.n_reads * 8 * b->nw + 16))) break;
-                if (hipMemcpy(d_packed.p, hr.packed, hr.packed_bytes, hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(d_w.p, hr.weight, hr.n_reads * 4, hipMemcpyHostToDevice) != hipSuccess) { set_error("H2D copy failed"); rc = KATOME_E_DEVICE; break; }
-                // the lines' k-mers as they are written (no canonical form: both strands become edges of their own)
-                if ((rc = launch_extract_fixed(s->k, false, d_packed.as<uint8_t>(), hr.n_reads, s->k, nullptr, d_rec.as<u64>(), nullptr))) break;
-                if ((rc = bfc_set_edges(b, d_rec.as<u64>(), d_w.as<u32>(), hr.n_reads, nullptr))) break;
-                if (hipStreamSynchronize(nullptr) != hipSuccess) { set_error("device failure during build"); rc = KATOME_E_DEVICE; break; }
-            }
-            rc = finish(b, hr.read_bytes);
-        } while (0);
-        katome_builder_destroy(b);
-        return rc;
-    }
-    if (hr.fixed_len) return build_packed_impl(s, hr.packed, hr.n_reads, hr.fixed_len, nullptr, finish, &hr.read_bytes);
-    // reads of unequal length over several GPUs (or, KATOME_FORCE_SHARDED=1, one GPU as a world of one rank): the sharded route
-    if (hr.n_reads && (s->n_devices > 1 || (s->n_devices == 1 && getenv("KATOME_FORCE_SHARDED")))) {
-        KCHECK(check_k(s->k));
-        return build_var_multi(s, hr, finish);
-    }
-    katome_builder* b = nullptr;
-    KCHECK(katome_builder_create(s, &b));
-    int rc = KATOME_OK;
-    do {
-        if (hr.n_reads == 0) { rc = finish(b, hr.read_bytes); break; }
-        DevBuf d_packed, d_off, d_len, d_pref, d_rec;
-        if ((rc = d_packed.alloc(hr.packed_bytes + 32)) || (rc = d_off.alloc((hr.n_reads + 1) * 8)) || (rc = d_len.alloc(hr.n_reads * 4))) break;
-        if (hipMemcpy(d_packed.p, hr.packed, hr.packed_bytes, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_off.p, hr.byte_off, (hr.n_reads + 1) * 8, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_len.p, hr.len, hr.n_reads * 4, hipMemcpyHostToDevice) != hipSuccess) { set_error("H2D copy failed"); rc = KATOME_E_DEVICE; break; }
-        uint64_t cap = batch_records(b->nw);
-        if (const char* e = getenv("KATOME_VAR_BATCH_RECORDS")) cap = std::max<uint64_t>(1, strtoull(e, nullptr, 10));   // tests: many small batches
-        // one span for the whole input: the one with the fewest table insertions over all reads (tiles from the front of
-        // every read + the windows left over, as for fixed-length reads)
-        uint32_t span = 1;
-        if (!getenv("KATOME_NO_TILES")) {
-            std::vector<uint64_t> hist;
-            for (uint64_t r = 0; r < hr.n_reads; ++r) {
-                const uint32_t W = hr.len[r] - s->k + 1;
-                if (W >= hist.size()) hist.resize(W + 1, 0);
-                hist[W] += 1;
-            }
-            uint64_t best = hr.total_windows;
-            for (uint32_t sp = 2; sp <= 33 && s->k + sp - 1 <= 95; ++sp) {      // (the same charges as katome_tile_plan)
-                bool breakable = sp <= 16;
-                for (uint32_t d = 3; d <= 8 && !breakable; ++d) breakable = sp % d == 0;
-                uint64_t cost = 0;
-                for (size_t W = 1; W < hist.size(); ++W) cost += hist[W] * (W / sp + W % sp + (breakable ? 0 : 4));
-                if (cost < best || (cost == best && span > 1)) { best = cost; span = sp; }
-            }
-            if (const char* e = getenv("KATOME_TILE_SPAN")) { const uint32_t sp = (uint32_t)atoi(e); if (sp >= 1 && s->k + sp - 1 <= 95) span = sp; }
-        }
-        DevBuf d_tpref, d_rpref;
-        std::vector<uint64_t> pref, tpref, rpref;
-        for (uint64_t r0 = 0; r0 < hr.n_reads && !rc;) {
-            pref.assign(1, 0); tpref.assign(1, 0); rpref.assign(1, 0);
-            uint64_t r1 = r0;
-            while (r1 < hr.n_reads && (r1 == r0 || pref.back() + (hr.len[r1] - s->k + 1) <= cap)) {
-                const uint64_t W = hr.len[r1] - s->k + 1;
-                pref.push_back(pref.back() + W);
-                tpref.push_back(tpref.back() + W / span);
-                rpref.push_back(rpref.back() + W % span);
-                ++r1;
-            }
-            const uint64_t windows = pref.back(), tiles = tpref.back(), rest = rpref.back(), nr = r1 - r0;
-            if ((rc = d_pref.alloc(pref.size() * 8)) || (rc = d_rec.alloc(windows * 8 * b->nw + 16))) break;
-            if (hipMemcpy(d_pref.p, pref.data(), pref.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { set_error("H2D copy failed"); rc = KATOME_E_DEVICE; break; }
-            if (span > 1) {
-                if ((rc = d_tpref.alloc(tpref.size() * 8)) || (rc = d_rpref.alloc(rpref.size() * 8))) break;
-                if (hipMemcpy(d_tpref.p, tpref.data(), tpref.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(d_rpref.p, rpref.data(), rpref.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { set_error("H2D copy failed"); rc = KATOME_E_DEVICE; break; }
-                if (tiles) {
-                    rc = katome_dev_extract_var_tiles(b, d_packed.as<uint8_t>(), hr.packed_bytes, d_off.as<u64>() + r0, d_len.as<u32>() + r0,
-                                                      d_tpref.as<u64>(), d_pref.as<u64>(), nr, tiles, windows, span, d_rec.as<u64>(), nullptr);
-                    if (!rc) rc = katome_dev_insert_tiles(b, d_rec.as<u64>(), tiles, span, nullptr);
-                }
-                if (!rc) rc = katome_dev_extract_var_remainder(b, d_packed.as<uint8_t>(), hr.packed_bytes, d_off.as<u64>() + r0, d_len.as<u32>() + r0,
-                                                               d_rpref.as<u64>(), d_pref.as<u64>(), nr, rest, windows, span, d_rec.as<u64>(), nullptr);
-                if (!rc) rc = katome_dev_insert(b, d_rec.as<u64>(), rest, nullptr);       // (also closes the batch when nothing is left over)
-            } else {
-                rc = katome_dev_extract_var(b, d_packed.as<uint8_t>(), hr.packed_bytes, d_off.as<u64>() + r0, d_len.as<u32>() + r0,
-                                            d_pref.as<u64>(), nr, windows, d_rec.as<u64>(), nullptr);
-                if (!rc) rc = katome_dev_insert(b, d_rec.as<u64>(), windows, nullptr);
-            }
-            if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) { set_error("device failure during build"); rc = KATOME_E_DEVICE; }
-            r0 = r1;
-        }
-        if (rc) break;
-        d_rec.release(); d_packed.release(); d_off.release(); d_len.release(); d_pref.release();
-        rc = finish(b, hr.read_bytes);
-    } while (0);
-    katome_builder_destroy(b);
-    return rc;
-}
-
-extern "C" {
-
-int katome_build_files(const katome_settings* s, const char* const* paths, size_t n_paths, katome_graph** out) {
-    if (!out) { set_error("null argument"); return KATOME_E_ARG; }
-    *out = nullptr;
-    return build_files_impl(s, paths, n_paths, Finish{out, nullptr});
-}
-int katome_build_files_staged(const katome_settings* s, const char* const* paths, size_t n_paths, const char* stages,
-                              uint64_t original_genome_length, katome_graph** out) {
-    if (!out) { set_error("null argument"); return KATOME_E_ARG; }
-    *out = nullptr;
-    Finish f{out, nullptr};
-    f.stages = stages; f.genome_len = original_genome_length;
-    return build_files_impl(s, paths, n_paths, f);
-}
-int katome_shrink_files(const katome_settings* s, const char* const* paths, size_t n_paths, katome_contigs** out) {
-    if (!out) { set_error("null argument"); return KATOME_E_ARG; }
-    *out = nullptr;
-    return build_files_impl(s, paths, n_paths, Finish{nullptr, out});
-}
-
-// Stats<CollectionStats> for PtGraph (stats/collections.rs:137-168), from the host arrays
-int katome_graph_stats(const katome_graph* g, katome_stats* st) {
-    if (!g || !st) { set_error("null argument"); return KATOME_E_ARG; }
-    memset(st, 0, sizeof *st);
-    st->node_count = g->n_nodes; st->edge_count = g->n_edges;
-    std::vector<uint32_t> outd(g->n_nodes, 0), ind(g->n_nodes, 0);
-    uint64_t sum_w = 0;
-    for (uint64_t e = 0; e < g->n_edges; ++e) {
-        st->max_edge_weight = std::max(st->max_edge_weight, g->edge_weight[e]);
-        sum_w += g->edge_weight[e];
-        ++outd[g->edge_src[e]]; ++ind[g->edge_dst[e]];
-    }
-    st->avg_edge_weight = (double)sum_w / (double)g->n_edges;
-    uint64_t sum_out = 0;
-    for (uint64_t n = 0; n < g->n_nodes; ++n) {
-        st->max_out_degree = std::max<uint64_t>(st->max_out_degree, outd[n]);
-        st->max_in_degree = std::max<uint64_t>(st->max_in_degree, ind[n]);
-        sum_out += outd[n];
-        if (ind[n] == 0) ++st->incoming_vert_count;      // externals(Incoming)
-        if (outd[n] == 0) ++st->outgoing_vert_count;     // externals(Outgoing)
-    }
-    st->avg_out_degree = (double)sum_out / (double)g->n_nodes;
-    return KATOME_OK;
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // builder.h -- one GPU's share of a build: the state behind `katome_builder` and the internal steps that the C ABI
-// (api.hip) and the sharded driver (dist.hip) compose.  Reference path: Build::create (builder.rs:42-54) ->
+// (api.hip, host_build.cpp) and the sharded driver (dist.hip) compose.  Reference path: Build::create (builder.rs:42-54) ->
 // add_read_fastaq (pt_graph.rs:277-315) -> add_single_edge_fastaq (172-198) -> post-pass (333-345).
 #pragma once
 #include <vector>
@@ -95,3 +95,10 @@ bool tile_recs_shape(uint32_t nwt, uint32_t nw, bool first_seen);   // tile / k-
 bool sorted_fail(const char* level);     // KATOME_SORTED_FAIL (tests)
 int flush_tile_recs(katome_builder* b, hipStream_t stream);    // the tile records kept aside -> b->tiles         // the left-over windows kept aside -> b->table
 uint32_t mid_span(uint32_t span);      // span of the mid tiles a big tile is broken into (0: expanded directly)
+
+// ---- what the host entry points (host_build.cpp) take from api.hip; not part of the library's dynamic symbols ---------------
+#define KATOME_INTERNAL __attribute__((visibility("hidden")))
+// BFCounter input: one edge per kept line and strand; leaves the builder with its sorted edge list
+KATOME_INTERNAL int bfc_set_edges(katome_builder* b, const uint64_t* d_fwd, const uint32_t* d_w, uint64_t n_lines, hipStream_t stream);
+// one tile span for reads of several lengths (none shorter than k), by katome_tile_plan's charges; 1: no tiles
+KATOME_INTERNAL uint32_t tile_span_for_lengths(uint32_t k, const uint32_t* len, uint64_t n_reads, uint64_t total_windows);

@@ -26,7 +26,7 @@ void LocalGroup::poison() {
 }
 #define KBARRIER(g)                                                                                       \
     do {                                                                                                  \
-        if (!(g)->barrier()) { set_error("another rank of this build failed"); return KATOME_E_DEVICE; } \
+        if (!(g)->barrier()) { set_error("%s", RANK_GAVE_UP); return KATOME_E_DEVICE; }                    \
     } while (0)
 
 namespace {

@@ -74,6 +74,9 @@ struct katome_comm {
 
 namespace katome {
 
+// the error of a rank that gave up at a poisoned rendezvous: the rank that failed by itself is the one to report
+constexpr const char* RANK_GAVE_UP = "another rank of this build failed";
+
 // ranks that are threads of one process: shared rendezvous state (LocalTransport, and the thread group of an n_devices build)
 struct LocalGroup {
     explicit LocalGroup(int n) : world(n), send(n), send_off(n), send_cnt(n), dev(n), red(n) {}

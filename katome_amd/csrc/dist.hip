@@ -149,8 +149,7 @@ __global__ __launch_bounds__(BLOCK) void var_stats_kernel(const u32* __restrict_
         acc[0] += L < k;
 #pragma unroll
         for (u32 sp = 2; sp < 2 + VAR_SPANS; ++sp) {
-            const bool breakable = sp <= 16 || sp % 3 == 0 || sp % 4 == 0 || sp % 5 == 0 || sp % 6 == 0 || sp % 7 == 0 || sp % 8 == 0;
-            acc[sp - 1] += W / sp + W % sp + (breakable ? 0 : 4);
+            acc[sp - 1] += tile_cost(W, sp);
         }
     }
     // (the wave's sums, then the block's in LDS: one atomic per value and block, and the grid is capped at 1024 blocks)

@@ -37,6 +37,15 @@ template <int NW> struct Key { u64 w[NW]; };
 // top bits free for the table's flags, as it does for one and two words)
 KD int key_words_for_k(u32 k) { return 2 * k <= 62 ? 1 : 2 * k <= 126 ? 2 : 3; }
 
+// ---- tiled counting ------------------------------------------------------------------------
+constexpr u32 TILE_SPAN_MAX = 33;     // the tile plans try spans 2..33
+// table insertions that counting the W windows of a read with tiles of `span` windows costs: the whole tiles, the windows left
+// over, and 4 for a span above 16 that no divisor in 3..8 breaks into mid tiles (its tiles expand in two levels)
+KD u32 tile_cost(u32 W, u32 span) {
+    const bool breakable = span <= 16 || span % 3 == 0 || span % 4 == 0 || span % 5 == 0 || span % 6 == 0 || span % 7 == 0 || span % 8 == 0;
+    return W / span + W % span + (breakable ? 0 : 4);
+}
+
 // ---- hashing ------------------------------------------------------------------------------
 KD u64 mix64(u64 x) {
     x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
