@@ -378,6 +378,7 @@ int bfc_set_edges(katome_builder* b, const uint64_t* d_fwd, const uint32_t* d_w,
     const uint64_t E = n_lines * (b->rc ? 2 : 1);
     const uint32_t nw = b->nw;
     if (b->edges_ready || b->table_ready || b->tiles_ready) { set_error("BFCounter input cannot be mixed with counted reads"); return KATOME_E_ARG; }
+    b->drop_edge_heads();
     b->n_edges = E; b->direct_edges = E;
     KCHECK(b->edge_key.alloc((E + 1) * 8 * nw, stream));
     KCHECK(b->edge_weight.alloc((E + 1) * 4, stream));
@@ -599,9 +600,18 @@ static bool level_fits(uint64_t n_records, uint32_t key_words, bool oriented, co
                 what, (unsigned long long)n_records, need / 1073741824.0, have / 1073741824.0);
     return false;
 }
-// a list that was sized for its records and holds far fewer keys moves into a buffer of its own size (thin coverage: the room is needed)
+// a list that was sized for its records and holds far fewer keys gives the room behind them back (thin coverage: the room is needed).
+// The list already sits at the front of its block, so the block is trimmed where it lies (DevBuf::trim); KATOME_TRIM_IN_PLACE=0: the
+// list moves into a buffer of its own size instead, as it did before the allocator could trim
 static int shrink_to_fit(DevBuf& buf, size_t used, hipStream_t stream) {
     if (!buf.p || buf.bytes < (1ull << 30) || used * 2 > buf.bytes) return KATOME_OK;
+    static const bool in_place = !getenv("KATOME_TRIM_IN_PLACE") || atoi(getenv("KATOME_TRIM_IN_PLACE")) != 0;
+    if (in_place) {
+        const size_t before = buf.bytes;
+        if (buf.trim(used + 64) && getenv("KATOME_LC_TRACE"))
+            fprintf(stderr, "[levels] list trimmed in place: %zu -> %zu bytes\n", before, buf.bytes);
+        return KATOME_OK;
+    }
     DevBuf small(stream);
     if (small.alloc(used + 64) != KATOME_OK) return KATOME_OK;          // (no room for the copy: the list stays where it is)
     if (used) KCHECK_HIP(hipMemcpyAsync(small.p, buf.p, used, hipMemcpyDeviceToDevice, stream));
@@ -1056,9 +1066,12 @@ static int edges_from_tile_recs(katome_builder* b, bool* counted, hipStream_t st
     }
     b->stat_kmers = distinct; b->stat_kmer_slots = 0;
     rk.release(); rw.release();
+    first_counts.release();                  // (the order call worked in them: prefixes now, of no use to anyone)
     PhaseScope ps(b->prof, PH_SORT_EDGES, stream);
-    if (hs.taken) KCHECK(half_sort_finish(hs, b->edge_key, b->edge_weight, stream));
-    else KCHECK(dev_sort_bufs(b->edge_key, &b->edge_weight, b->n_edges, b->nw, 2 * k, stream, true));
+    if (hs.taken) {
+        KCHECK(half_sort_finish(hs, b->edge_key, b->edge_weight, stream, &b->edge_heads));
+        if (b->edge_heads.p) { b->edge_heads_key = b->edge_key.p; b->edge_heads_n = b->n_edges; }
+    } else KCHECK(dev_sort_bufs(b->edge_key, &b->edge_weight, b->n_edges, b->nw, 2 * k, stream, true));
     *counted = true;
     return KATOME_OK;
 }
@@ -1277,6 +1290,7 @@ int katome_dev_edges(katome_builder* b, uint64_t** d_edge_key, uint32_t** d_edge
     KCHECK_HIP(hipSetDevice(b->s.device));
     if (!b->edges_ready) {
         b->n_edges = 0;
+        b->drop_edge_heads();
         b->tile_scratch.release();
         // (tile records with k-mers in the table already, or too few of them to be worth sorting: into the tile table)
         if (b->tile_recs_n && (b->table_ready || !sorting_pays(b->tile_recs_n * b->span))) KCHECK(flush_tile_recs(b, stream));
@@ -1311,11 +1325,23 @@ int katome_dev_finalize(katome_builder* b, katome_dev_graph* out, void* stream_)
     KCHECK(b->edge_dst.alloc((E + 1) * 8, stream));
     DevBuf node_first(stream);                 // first-seen order: the nodes' first touches come out of the same merge
     uint64_t n_marked = 0;                     // ... and, for targets below this index, "this edge touches it first" as a mark in edge_dst
+    const uint32_t stride = label_stride_for_k(k);
+    // default numbering: the edges stay where they are, so the pass that writes their source ids writes their labels too (radix.hip
+    // src_write_kernel) and no kernel reads the keys again for them.  KATOME_LABELS_IN_IDS=0: dev_labels afterwards, as in first-seen
+    // order, whose edges are renumbered first
+    static const bool labels_in_ids = !getenv("KATOME_LABELS_IN_IDS") || atoi(getenv("KATOME_LABELS_IN_IDS")) != 0;
+    const bool labels_early = labels_in_ids && !b->first_seen && E;
+    if (labels_early) KCHECK(b->edge_label.alloc((E + 1) * (size_t)stride + 16, stream));
     {
         PhaseScope ps(b->prof, PH_NODE_SET, stream);
         const bool fs = b->first_seen && E && b->edge_seq.p;
-        KCHECK(dev_node_ids(b->edge_key.as<u64>(), E, k, b->node_key, b->edge_src.as<u64>(), b->edge_dst.as<u64>(), &b->n_nodes, stream,
-                            fs ? b->edge_seq.as<u64>() : nullptr, fs ? &node_first : nullptr, &n_marked));
+        // (the merge's head counts, if they were made for exactly this edge list)
+        const bool heads = b->edge_heads.p && b->edge_heads_key == b->edge_key.p && b->edge_heads_n == E;
+        const int rc = dev_node_ids(b->edge_key.as<u64>(), E, k, b->node_key, b->edge_src.as<u64>(), b->edge_dst.as<u64>(), &b->n_nodes, stream,
+                                    fs ? b->edge_seq.as<u64>() : nullptr, fs ? &node_first : nullptr, &n_marked, heads ? b->edge_heads.as<u32>() : nullptr,
+                                    labels_early ? b->edge_label.as<uint8_t>() : nullptr);
+        b->drop_edge_heads();
+        if (rc != KATOME_OK) { b->edge_label.release(); return rc; }      // (a builder that is not finalized holds no labels)
     }
     u64* cand = b->node_key.as<u64>();
     if (b->first_seen && E) {
@@ -1442,9 +1468,8 @@ int katome_dev_finalize(katome_builder* b, katome_dev_graph* out, void* stream_)
         if (b->prune_weight) KCHECK(weak_edges_ordered(b, b->prune_weight, stream));
         cand = b->node_key.as<u64>();
     }
-    const uint32_t stride = label_stride_for_k(k);
-    KCHECK(b->edge_label.alloc((E + 1) * (size_t)stride + 16, stream));
-    {
+    if (!labels_early) {
+        KCHECK(b->edge_label.alloc((E + 1) * (size_t)stride + 16, stream));
         PhaseScope ps(b->prof, PH_LABELS, stream);
         KCHECK(dev_labels(b->edge_key.as<u64>(), b->n_edges, k, b->edge_label.as<uint8_t>(), stream));
     }

@@ -61,6 +61,13 @@ struct katome_builder {
     bool edges_ready = false;
     DevBuf edge_key, edge_weight;
     uint64_t n_edges = 0;
+    // the source run heads per block of edges, where the edges' merge counted them (half_sort_finish), and the edge list they were
+    // counted for: katome_dev_finalize hands them to dev_node_ids only if edge_key and n_edges are still those.  Whoever installs
+    // other edges drops them
+    DevBuf edge_heads;
+    const void* edge_heads_key = nullptr;
+    uint64_t edge_heads_n = 0;
+    void drop_edge_heads() { edge_heads.release(); edge_heads_key = nullptr; edge_heads_n = 0; }
     // scratch for ordering a batch by table region before it is inserted
     DevBuf scratch_k[2], scratch_w[2];
     // finalized graph

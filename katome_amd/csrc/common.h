@@ -35,6 +35,9 @@ const char* get_error();
 // caching allocator (mem.cpp): blocks are reused across phases and across builds
 int dev_malloc(void** out, size_t bytes, hipStream_t stream);
 void dev_free(void* p, hipStream_t stream);
+// a live block keeps its first `keep` bytes and gives its tail back to the cache without a copy (mem_pool.h trim); returns the
+// block's size afterwards (unchanged where the tail would be too small to keep), 0 for a pointer the cache does not know
+size_t dev_trim(void* p, size_t keep);
 size_t dev_cached_bytes();
 // call before hipStreamDestroy: cached blocks remember the stream they were last used on
 void dev_retire_stream(hipStream_t stream);
@@ -70,6 +73,14 @@ struct DevBuf {
     void release() {
         if (p) dev_free(p, stream);
         p = nullptr; bytes = 0;
+    }
+    // keeps the first `keep` bytes where they are; true: the rest went back to the cache (`bytes` is what the block still holds)
+    bool trim(size_t keep) {
+        if (!p || keep >= bytes) return false;
+        const size_t left = dev_trim(p, keep);
+        if (!left || left >= bytes) return false;
+        bytes = left;
+        return true;
     }
     void* take() { void* q = p; p = nullptr; bytes = 0; return q; }
     void adopt(void* q, size_t n) { release(); p = q; bytes = n; }
@@ -201,16 +212,18 @@ int dev_source_ids(const uint64_t* d_edge_key, uint64_t n_edges, uint32_t k, Dev
                    hipStream_t stream);
 int dev_hash_order_core(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t core_shift, uint32_t core_bases, uint64_t* ka, uint64_t* kb,
                         uint32_t* wa, uint32_t* wb, const uint64_t** k_out, const uint32_t** w_out, uint32_t* group_bits, hipStream_t stream);
+// (first_counts of the three order calls below: the first pass's digit counts per tile, made by whoever wrote the records.  The pass
+// works IN that buffer and leaves prefixes there: its contents are gone after the call, and no caller reads them again)
 int dev_hash_order_tagged(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t nwk, uint64_t* ka, uint64_t* kb, uint32_t* wa, uint32_t* wb,
-                          const uint64_t** k_out, const uint32_t** w_out, uint32_t* group_bits, hipStream_t stream, const uint32_t* first_counts = nullptr);
+                          const uint64_t** k_out, const uint32_t** w_out, uint32_t* group_bits, hipStream_t stream, uint32_t* first_counts = nullptr);
 int dev_region_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t nw, int passes, uint64_t* ka, uint64_t* kb,
                      uint32_t* wa, uint32_t* wb, const uint64_t** k_out, const uint32_t** w_out, hipStream_t stream);
 int dev_hash_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t nw, uint64_t* ka, uint64_t* kb, uint32_t* wa, uint32_t* wb,
-                   const uint64_t** k_out, const uint32_t** w_out, uint32_t* group_bits, hipStream_t stream, const uint32_t* first_counts = nullptr);
+                   const uint64_t** k_out, const uint32_t** w_out, uint32_t* group_bits, hipStream_t stream, uint32_t* first_counts = nullptr);
 uint32_t dev_sort_tile_keys(uint32_t nw);
 // one-word records by their leading 16 key bits (k = 8..32): two stable passes; the result where *k_out / *w_out point (kb / wb)
 int dev_key_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t k, uint64_t* ka, uint64_t* kb, uint32_t* wa, uint32_t* wb,
-                  const uint64_t** k_out, const uint32_t** w_out, hipStream_t stream, const uint32_t* first_counts = nullptr);
+                  const uint64_t** k_out, const uint32_t** w_out, hipStream_t stream, uint32_t* first_counts = nullptr);
 // index[g] (65537 of them) = first of n ascending one-word keys whose bits [shift, shift + 16) are >= g
 int dev_key_group_index(const uint64_t* d_keys, uint64_t n, uint32_t shift, uint64_t* d_index, hipStream_t stream);
 // merges, per 16-bit key prefix g, a_count[g] ascending keys at a_key + a_first[g] with the sorted b_key[b_first[g] .. b_first[g + 1])
@@ -220,10 +233,13 @@ int dev_half_merge(const uint64_t* a_key, const uint32_t* a_w, const uint64_t* a
                    hipStream_t stream);
 // the same without a sort of B: b_key / b_w only partitioned by the 16-bit prefix (dev_key_order), at most dev_group_merge_cap() keys
 // to a prefix (dev_key_group_max), weights below 2^16; B's groups are put in key order in LDS (radix.hip group_merge_kernel)
+// (head_counts, dev_source_head_blocks(n_out) of them: also counts the source run heads of every block of output edges, which
+// dev_node_ids then need not count again)
 uint32_t dev_group_merge_cap();
+uint64_t dev_source_head_blocks(uint64_t n_edges);
 int dev_group_merge(const uint64_t* a_key, const uint32_t* a_w, const uint64_t* a_first, const uint32_t* a_count, const uint64_t* a_off,
                     const uint64_t* b_key, const uint32_t* b_w, const uint64_t* b_first, uint32_t k, uint64_t* out_key, uint32_t* out_w,
-                    uint64_t n_out, hipStream_t stream);
+                    uint64_t n_out, hipStream_t stream, uint32_t* head_counts = nullptr);
 // *d_out = the largest index[g + 1] - index[g], g < 65536 (the largest group of a dev_key_group_index)
 int dev_key_group_max(const uint64_t* d_index, uint64_t* d_out, hipStream_t stream);
 int dev_unique(uint64_t* d_keys, uint64_t n, uint32_t nw, uint64_t* n_out, hipStream_t stream);
@@ -231,9 +247,11 @@ int dev_rank(const uint64_t* d_sorted, uint64_t n_sorted, uint32_t nw, uint32_t 
              uint64_t* d_out, hipStream_t stream);
 // d_seq + node_first (first-seen order): also the nodes' first touches (dev_node_first's result), filled on the way; node_first
 // comes back EMPTY when that was not done and dev_node_first has to run
+// head_counts: dev_group_merge's, made for exactly these edges (the heads are then not counted again); d_label: the edges' labels
+// (dev_labels' bytes) are written in the same pass as the source ids
 int dev_node_ids(const uint64_t* d_edge_key, uint64_t n_edges, uint32_t k, DevBuf& node_key, uint64_t* d_edge_src,
                  uint64_t* d_edge_dst, uint64_t* n_nodes, hipStream_t stream, const uint64_t* d_seq = nullptr, DevBuf* node_first = nullptr,
-                 uint64_t* n_marked = nullptr);
+                 uint64_t* n_marked = nullptr, const uint32_t* head_counts = nullptr, uint8_t* d_label = nullptr);
 int dev_iota(uint32_t* d, uint64_t n, hipStream_t stream);
 int dev_fill_u32(uint32_t* d, uint64_t n, uint32_t v, hipStream_t stream);
 int dev_gather_seq_weight(const uint64_t* pairs, const uint32_t* idx, uint64_t n, uint64_t* seq, uint32_t* weight, hipStream_t stream);
@@ -377,7 +395,7 @@ int tiles_to_edges_sorted_seen(Table& tiles, uint32_t k, uint32_t span, bool rc,
 int table_keep_rest(const uint64_t* d_rec, uint64_t n, uint32_t nw, bool tagged, uint64_t read0, uint32_t per_read, uint32_t win0, uint32_t seq_per_read,
                     uint64_t* d_out, uint64_t* d_cursor, hipStream_t stream, uint32_t win_stride = 1, uint32_t span = 1);
 int tagged_records_sorted(DevBuf& recs, DevBuf& wts, uint64_t n, uint32_t k, bool rc, uint64_t seq_per_read, bool list, DevBuf& out_keys,
-                          DevBuf& out_second, uint64_t* n_out, uint64_t* n_distinct, hipStream_t stream, const uint32_t* first_counts = nullptr);
+                          DevBuf& out_second, uint64_t* n_out, uint64_t* n_distinct, hipStream_t stream, uint32_t* first_counts = nullptr);
 int table_list_to_tagged_records(const uint64_t* d_list, const uint32_t* d_counts, uint64_t n_tiles, uint32_t tile_bases, uint32_t sub_len, uint32_t n_sub,
                                  uint32_t stride, bool rc, DevBuf& recs, DevBuf& weights, uint64_t* n_records, hipStream_t stream, uint64_t extra_room = 0,
                                  DevBuf* first_counts = nullptr);
@@ -403,12 +421,14 @@ struct HalfSort {
         n_s1 = n_s2 = 0; taken = false;
     }
 };
-int half_sort_finish(HalfSort& hs, DevBuf& edge_key, DevBuf& edge_weight, hipStream_t stream);
+// (head_counts: filled with the merge's source run heads per block of edges -- dev_group_merge -- where the merge makes them, else released)
+int half_sort_finish(HalfSort& hs, DevBuf& edge_key, DevBuf& edge_weight, hipStream_t stream, DevBuf* head_counts = nullptr);
 // (half: the records are in their representative orientation -- table_list_to_records with rep -- and the level is counted in order
 // into *half when it can be (half->taken); otherwise they are turned back and counted the usual way, with unsorted edges out)
+// (first_counts, here and in tagged_records_sorted: handed to the order call, which overwrites them -- see dev_hash_order)
 int records_to_edges_sorted(DevBuf& keys, DevBuf& weights, uint64_t n, uint32_t k, bool rc, uint32_t min_weight, DevBuf& edge_key,
                             DevBuf& edge_weight, uint64_t* n_edges, uint64_t* n_distinct, hipStream_t stream, OwnerSplit* split = nullptr,
-                            const uint32_t* first_counts = nullptr, HalfSort* half = nullptr);
+                            uint32_t* first_counts = nullptr, HalfSort* half = nullptr);
 int table_to_records(Table& t, DevBuf& keys, DevBuf& weights, uint64_t* n_records, hipStream_t stream, DevBuf* seen_pairs = nullptr);
 int table_expand_tiles_to_subtiles(Table& tiles, uint32_t k, uint32_t span, uint32_t stride, bool rc, DevBuf& keys, DevBuf& weights,
                                    uint64_t* n_records, hipStream_t stream, DevBuf* seen = nullptr);

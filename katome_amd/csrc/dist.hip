@@ -500,6 +500,7 @@ int count_collected(katome_dist_builder* d, Collected& c, hipStream_t stream) {
             c.keys.release(); c.weights.release();
             PhaseScope ps(b->prof, PH_SORT_EDGES, stream);
             KCHECK(dev_sort_bufs(b->edge_key, &b->edge_weight, b->n_edges, b->nw, 2 * d->s.k, stream, true));
+            b->drop_edge_heads();                        // (other edges than any a merge counted heads for)
             b->edges_ready = true;
             return KATOME_OK;
         }
@@ -1454,6 +1455,7 @@ int katome_dist_gather(katome_dist_builder* d, int root, katome_builder** root_b
         KCHECK(b->edge_label.alloc((TE + 1) * (size_t)lstride + 16, stream));
         KCHECK(dev_labels(b->edge_key.as<u64>(), TE, d->s.k, b->edge_label.as<uint8_t>(), stream));
         b->edge_age.release();
+        b->drop_edge_heads();
         b->edges_ready = true; b->finalized = true;
         if (root_builder) *root_builder = b;
     }

@@ -63,6 +63,18 @@ void dev_free(void* p, hipStream_t stream) {
     if (!c.pool.deallocate(p, stream, stream != nullptr)) (void)hipFree(p);
 }
 
+// a live block keeps its first `keep` bytes; the rest goes back to the cache where it lies (SegmentPool::trim).  Returns the
+// block's size afterwards, 0 for a pointer the cache does not know
+size_t dev_trim(void* p, size_t keep) {
+    if (!p) return 0;
+    Cache& c = cache();
+    std::lock_guard<std::mutex> lk(c.mu);
+    const size_t left = c.pool.trim(p, keep);
+    static const bool log_all = getenv("KATOME_TRACE_BLOCKS") != nullptr;
+    if (log_all) fprintf(stderr, "[katome block] < %p %zu (keeps %zu)\n", p, left, keep);
+    return left;
+}
+
 void dev_retire_stream(hipStream_t stream) {
     if (!stream) return;
     (void)hipStreamSynchronize(stream);

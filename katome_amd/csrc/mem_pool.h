@@ -71,6 +71,26 @@ public:
         return true;
     }
 
+    // A live block keeps its first `keep` bytes and gives the rest back: the tail becomes a free block of the same segment (the
+    // split take_free makes), which inherits the block's stream -- a taker on another stream waits for it -- and merges with a
+    // free right neighbour.  Returns the block's size afterwards; nothing changes for a block of the small cache or a tail below
+    // KEEP.  0: not one of ours.  (Blocks of the large cache stay whole multiples of round_size's 2 MiB.)
+    size_t trim(void* p, size_t keep) {
+        auto it = live_.find(p);
+        if (it == live_.end()) return 0;
+        Block* b = it->second;
+        const size_t want = round_size(keep < SMALL ? SMALL : keep);
+        if (b->seg_bytes < SMALL || want >= b->bytes || b->bytes - want < KEEP) return b->bytes;
+        Block* rest = new Block(*b);
+        rest->p = b->p + want; rest->bytes = b->bytes - want; rest->is_free = true;
+        rest->prev = b; rest->next = b->next;
+        if (b->next) b->next->prev = rest;
+        b->next = rest; b->bytes = want;
+        if (rest->next && rest->next->is_free) { remove_free(rest->next); absorb_next(rest); }
+        insert_free(rest);
+        return b->bytes;
+    }
+
     void release_free_segments(int device) {                            // device < 0: all
         for (auto it = free_.begin(); it != free_.end();) {
             Block* b = it->second;

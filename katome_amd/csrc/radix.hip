@@ -358,6 +358,9 @@ __global__ __launch_bounds__(BLOCK, KATOME_SORT_WAVES) void radix_scatter_kernel
 
 struct PassBuffers {
     DevBuf counts, chunk, totals;
+    // (first: the first pass's digit counts per tile, [nblocks][RADIX], made by whoever wrote the records.  That pass works IN this
+    // buffer -- radix_chunk_kernel turns the counts into prefixes in place -- so the buffer's owner must not read it afterwards)
+    u32* first = nullptr;
     u64 nblocks = 0, nchunks = 0;
     u32 chunk_blocks = 64;
     int init(u64 n, int nw, hipStream_t stream) {
@@ -392,13 +395,14 @@ static int radix_pass(const u64* kin, const u32* vin, u64 n, Digit dg, u64* kout
                       bool have_counts = false) {
     if (pb.nblocks > 0x7fffffffull) { set_error("radix pass: %llu keys exceed the grid limit", (unsigned long long)n); return KATOME_E_ARG; }
     dim3 block(BLOCK);
-    if (!have_counts) {          // (have_counts: whoever wrote the records counted this pass's digits per tile as it went -- pb.counts holds them)
+    u32* const counts = have_counts && pb.first ? pb.first : pb.counts.as<u32>();
+    if (!have_counts) {          // (have_counts: whoever wrote the records counted this pass's digits per tile as it went -- pb.first, or pb.counts, holds them)
         KernelScope ks(DigitTimers<Digit>::HIST, stream, n);
-        hipLaunchKernelGGL((radix_hist_kernel<NW, Digit>), dim3((unsigned)pb.nblocks), block, 0, stream, kin, n, dg, pb.counts.as<u32>());
+        hipLaunchKernelGGL((radix_hist_kernel<NW, Digit>), dim3((unsigned)pb.nblocks), block, 0, stream, kin, n, dg, counts);
     }
     {
         KernelScope ks(K_PASS_OFFSETS, stream, n);
-        hipLaunchKernelGGL(radix_chunk_kernel, dim3((unsigned)pb.nchunks), block, 0, stream, pb.counts.as<u32>(), pb.nblocks, pb.chunk.as<u64>(), pb.chunk_blocks);
+        hipLaunchKernelGGL(radix_chunk_kernel, dim3((unsigned)pb.nchunks), block, 0, stream, counts, pb.nblocks, pb.chunk.as<u64>(), pb.chunk_blocks);
         hipLaunchKernelGGL(radix_offsets_kernel, dim3(1), block, 0, stream, pb.chunk.as<u64>(), pb.nchunks, pb.totals.as<u64>());
     }
     const size_t lds = (size_t)SortTile<NW>::KEYS * NW * 8;
@@ -410,7 +414,7 @@ static int radix_pass(const u64* kin, const u32* vin, u64 n, Digit dg, u64* kout
         const u32 xcd_tiles = xcd_aware && pb.nblocks >= 64 ? (u32)((pb.nblocks + 7) / 8) : 0u;
         KernelScope ks((!HAS_VAL && DigitTimers<Digit>::SCATTER == K_SORT_SCATTER) ? (int)K_SORT_SCATTER_KEYS : (int)DigitTimers<Digit>::SCATTER, stream, n);
         hipLaunchKernelGGL((radix_scatter_kernel<NW, HAS_VAL, Digit, STABLE>), dim3(xcd_tiles ? xcd_tiles * 8u : (unsigned)pb.nblocks), block, lds, stream, kin, vin, n, dg,
-                           pb.counts.as<u32>(), pb.chunk.as<u64>(), kout, vout, pb.chunk_blocks, xcd_tiles);
+                           counts, pb.chunk.as<u64>(), kout, vout, pb.chunk_blocks, xcd_tiles);
     }
     KCHECK_HIP(hipGetLastError());
     return KATOME_OK;
@@ -827,11 +831,12 @@ int dev_partition_range(const uint64_t* d_vals, const uint32_t* idx_in, uint64_t
 // Result lands in `bufs[passes & 1]` where bufs = {scratch_a, scratch_b}; returns that pointer.
 template <int NW>
 static int region_order_t(const u64* d_in, const u32* w_in, u64 n, int passes, u64* ka, u64* kb, u32* wa, u32* wb,
-                          const u64** k_out, const u32** w_out, hipStream_t stream, const u32* first_counts = nullptr) {
+                          const u64** k_out, const u32** w_out, hipStream_t stream, u32* first_counts = nullptr) {
     PassBuffers pb;
     KCHECK(pb.init(n, NW, stream));
-    // (first_counts: the first pass's digit counts per tile, [ceil(n / dev_sort_tile_keys)][256], made while the records were written)
-    if (first_counts) KCHECK_HIP(hipMemcpyAsync(pb.counts.p, first_counts, pb.nblocks * RADIX * sizeof(u32), hipMemcpyDeviceToDevice, stream));
+    // (first_counts: the first pass's digit counts per tile, [ceil(n / dev_sort_tile_keys)][256], made while the records were written;
+    // the pass works in that buffer and leaves prefixes in it)
+    pb.first = first_counts;
     const u64* kin = d_in; const u32* win = w_in;
     u64* kdst[2] = {ka, kb}; u32* wdst[2] = {wa, wb};
     for (int p = 0; p < passes; ++p) {
@@ -851,7 +856,7 @@ static int region_order_t(const u64* d_in, const u32* w_in, u64 n, int passes, u
 // (k-mer, count) records of one to three words ordered by the top 16 bits of the k-mer's hash, for the counting in LDS (table.hip): two
 // stable 8-bit passes.  The result is where *k_out / *w_out point (one of the two buffer pairs); *group_bits = 16.
 int dev_hash_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t nw, uint64_t* ka, uint64_t* kb, uint32_t* wa, uint32_t* wb,
-                   const uint64_t** k_out, const uint32_t** w_out, uint32_t* group_bits, hipStream_t stream, const uint32_t* first_counts) {
+                   const uint64_t** k_out, const uint32_t** w_out, uint32_t* group_bits, hipStream_t stream, uint32_t* first_counts) {
     *group_bits = 16;
     if (nw == 1) return region_order_t<1>(d_in, w_in, n, 2, ka, kb, wa, wb, k_out, w_out, stream, first_counts);
     if (nw == 3) return region_order_t<3>(d_in, w_in, n, 2, ka, kb, wa, wb, k_out, w_out, stream, first_counts);      // (tiles of 64..95 bases)
@@ -860,11 +865,11 @@ int dev_hash_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint3
 // one-word (k-mer, count) records ordered by their leading 16 key bits (bits 2k - 16 .. 2k - 1): two stable 8-bit passes, the
 // result where *k_out / *w_out point (first_counts: the first pass's digit counts per tile, made while the records were written)
 int dev_key_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t k, uint64_t* ka, uint64_t* kb, uint32_t* wa, uint32_t* wb,
-                  const uint64_t** k_out, const uint32_t** w_out, hipStream_t stream, const uint32_t* first_counts) {
+                  const uint64_t** k_out, const uint32_t** w_out, hipStream_t stream, uint32_t* first_counts) {
     if (k < 8 || 2 * k > 64) { set_error("key order: k = %u", k); return KATOME_E_ARG; }
     PassBuffers pb;
     KCHECK(pb.init(n, 1, stream));
-    if (first_counts) KCHECK_HIP(hipMemcpyAsync(pb.counts.p, first_counts, pb.nblocks * RADIX * sizeof(u32), hipMemcpyDeviceToDevice, stream));
+    pb.first = first_counts;
     KCHECK((radix_pass<1, true>(d_in, w_in, n, LevelKeyDigit{2 * k - 16}, ka, wa, pb, stream, first_counts != nullptr)));
     KCHECK((radix_pass<1, true>(ka, wa, n, LevelKeyDigit{2 * k - 8}, kb, wb, pb, stream)));
     *k_out = kb; *w_out = wb;
@@ -965,20 +970,39 @@ int dev_half_merge(const uint64_t* a_key, const uint32_t* a_w, const uint64_t* a
 //           (or what is left), GM_MI to a thread after a merge-path search; they are final when the ring holds GM_STEP unconsumed
 //           entries or A's end, since B is all in LDS (as in half_merge_kernel).  A is read GM_STEP entries ahead into registers:
 //           a block goes into the ring once there is room, and the next block's loads are in flight during the step's merge.
-// LDS: 160 KiB -- B (the last 16 words hold the scan's wave totals and the step's A count, so GM_CAP is 16 short of 16 Ki) and the
-// ring, whose first 4 KiB hold the buckets while B is ordered.  One workgroup of 1024 per CU.
+// LDS: 160 KiB -- B (the last 16 words hold the scan's wave totals, the step's A count and HEADS' words, so GM_CAP is 16 short of
+// 16 Ki) and the ring, whose first 4 KiB hold the buckets while B is ordered.  One workgroup of 1024 per CU.
+// HEADS: the kernel also counts, per block of SRC_HEAD_BLOCK (source_ids_t's UNIQ_TILE) output edges, the source run heads among them (is_src_head: key >> 2 differs
+// from the edge before, or edge 0) into head_counts -- what src_count_kernel would read the whole list again for.  A step's
+// outputs [o, o + c), c <= GM_STEP = SRC_HEAD_BLOCK, lie in at most two such blocks; blocks straddle groups that other workgroups merge,
+// so head_counts starts at zero and is added to.  Output d is a head iff it is its group's first (the 16-bit prefix changed, and
+// 2k - 16 >= 2) or its entry differs from its predecessor's above the weight and the last base (e >> 18).  The predecessor of a
+// thread's first output is the larger of the two entries before its merge-path split; of the step's first output, the last output
+// of the step before, kept in one of two LDS words by step parity (never ring[ca - 1]: a full ring has overwritten it).
 constexpr u32 GM_THREADS = LDS_ORDER_THREADS, GM_PER = 16, GM_WORDS = GM_THREADS * GM_PER, GM_CAP = GM_WORDS - 16;
 constexpr u32 GM_STEP = 2048, GM_RING = 2 * GM_STEP, GM_MI = GM_STEP / GM_THREADS, GM_PF = GM_STEP / GM_THREADS;
 constexpr size_t GM_LDS = ((size_t)GM_WORDS + GM_RING) * 8;
-static_assert(LDS_ORDER_BUCKETS * 2 <= GM_RING * 8 && GM_THREADS / 64 + 1 <= 2 * 16, "aliases in the merge's LDS");
+constexpr u32 SRC_HEAD_BLOCK = 2048;          // edges to a count of source_ids_t (its UNIQ_TILE: asserted there)
+// the GM_WORDS - GM_CAP spare words behind B, as u32: the scan's wave totals, the step's A count, and (HEADS) the last entry of the
+// step before by step parity (two u64, so on an even u32) and the step's two head counts
+constexpr u32 GM_SP_WTOT = 0, GM_SP_USED_A = GM_SP_WTOT + GM_THREADS / 64, GM_SP_LAST_E = (GM_SP_USED_A + 1 + 1) / 2 * 2,
+              GM_SP_STEP_HEADS = GM_SP_LAST_E + 2 * 2, GM_SP_END = GM_SP_STEP_HEADS + 2;
+static_assert(LDS_ORDER_BUCKETS * 2 <= GM_RING * 8 && GM_SP_END <= 2 * (GM_WORDS - GM_CAP), "aliases in the merge's LDS");
+template <bool HEADS>
 __global__ __launch_bounds__(GM_THREADS) void group_merge_kernel(const u64* __restrict__ a_key, const u32* __restrict__ a_w, const u64* __restrict__ a_first,
                                                                    const u32* __restrict__ a_count, const u64* __restrict__ a_off, const u64* __restrict__ b_key,
                                                                    const u32* __restrict__ b_w, const u64* __restrict__ b_first, u32 k,
-                                                                   u64* __restrict__ out_key, u32* __restrict__ out_w, u64 out_cap) {
+                                                                   u64* __restrict__ out_key, u32* __restrict__ out_w, u64 out_cap,
+                                                                   u32* __restrict__ head_counts) {
     extern __shared__ unsigned long long gm_mem[];
     unsigned long long* bs = gm_mem;                                     // [GM_CAP]: the group's B in key order
-    u32* wtot = reinterpret_cast<u32*>(gm_mem + GM_CAP);                 // [GM_THREADS / 64]
-    u32* used_a = wtot + GM_THREADS / 64;
+    u32* spare = reinterpret_cast<u32*>(gm_mem + GM_CAP);                // (GM_SP_*)
+    u32* wtot = spare + GM_SP_WTOT;                                      // [GM_THREADS / 64]
+    u32* used_a = spare + GM_SP_USED_A;
+    unsigned long long* last_e = reinterpret_cast<unsigned long long*>(spare + GM_SP_LAST_E);      // [2] (HEADS): the last entry placed by the step before, by step parity
+    u32* step_heads = spare + GM_SP_STEP_HEADS;                          // [2] (HEADS): this step's heads in its first and its second block
+    static_assert(!HEADS || GM_STEP == SRC_HEAD_BLOCK, "a step's outputs lie in at most two blocks of head_counts");
+    if (HEADS && threadIdx.x < 2) step_heads[threadIdx.x] = 0u;          // (ordered before the first step by the barriers in between)
     unsigned long long* ring = gm_mem + GM_WORDS;                        // [GM_RING]: A
     u32* bucket = reinterpret_cast<u32*>(ring);                          // [LDS_ORDER_BUCKETS / 2], while B is ordered
     const u32 tid = threadIdx.x;
@@ -1002,6 +1026,7 @@ __global__ __launch_bounds__(GM_THREADS) void group_merge_kernel(const u64* __re
         // A's next block [la, la + pn) in registers
         u64 pk[GM_PF]; u32 pw[GM_PF];
         u32 ca = 0, cb = 0, la = 0, pn = na < GM_STEP ? na : GM_STEP;          // A consumed and in the ring, B consumed
+        u32 step = 0;                                     // (HEADS) steps of this group so far
 #pragma unroll
         for (u32 r = 0; r < GM_PF; ++r) { const u32 i = tid + r * GM_THREADS; if (i < pn) { pk[r] = ap[i]; pw[r] = awp[i]; } }
         while (ca < na || cb < nb) {
@@ -1019,6 +1044,7 @@ __global__ __launch_bounds__(GM_THREADS) void group_merge_kernel(const u64* __re
             __syncthreads();
             const u32 va = la - ca, vb = nb - cb, c = va + vb < GM_STEP ? va + vb : GM_STEP;
             const u32 d0 = tid * GM_MI;
+            u32 h_lo = 0, h_hi = 0;                           // (HEADS) bit r: this thread's output r is a head in the step's first / second block
             if (d0 < c) {
                 // merge path: the number of A entries among the first d0 outputs
                 u32 lo = d0 > vb ? d0 - vb : 0, hi = d0 < va ? d0 : va;
@@ -1028,30 +1054,60 @@ __global__ __launch_bounds__(GM_THREADS) void group_merge_kernel(const u64* __re
                 }
                 u32 i = lo, j = d0 - lo;
                 const u32 d1 = d0 + GM_MI < c ? d0 + GM_MI : c;
+                unsigned long long prev = 0;                  // (HEADS) the entry placed before this thread's next one
+                bool first = false;                           // ... or none: the group's first output
+                if (HEADS) {
+                    if (d0 == 0) { first = step == 0; if (!first) prev = last_e[(step - 1) & 1]; }
+                    else {
+                        const unsigned long long pa = i ? ring[(ca + i - 1) & (GM_RING - 1)] : 0ull, pb = j ? bs[cb + j - 1] : 0ull;
+                        prev = pa > pb ? pa : pb;             // (d0 > 0: one of the two exists, and entries are distinct above bit 16)
+                    }
+                }
                 for (u32 d = d0; d < d1; ++d) {
                     unsigned long long e;
                     if (i < va && (j >= vb || ring[(ca + i) & (GM_RING - 1)] < bs[cb + j])) e = ring[(ca + i++) & (GM_RING - 1)];
                     else e = bs[cb + j++];
-                    if (o + d < out_cap) { out_key[o + d] = ((u64)g << rem_bits) | (e >> 16); out_w[o + d] = (u32)e & 0xFFFFu; }
+                    if (o + d < out_cap) {
+                        out_key[o + d] = ((u64)g << rem_bits) | (e >> 16); out_w[o + d] = (u32)e & 0xFFFFu;
+                        if (HEADS && (first || (e >> 18) != (prev >> 18))) {
+                            if ((o + d) / SRC_HEAD_BLOCK != o / SRC_HEAD_BLOCK) h_hi |= 1u << (d - d0); else h_lo |= 1u << (d - d0);
+                        }
+                    }
+                    if (HEADS) { prev = e; first = false; }
                 }
-                if (d1 == c) *used_a = i;                     // (the thread that places the step's last output)
+                if (d1 == c) { *used_a = i; if (HEADS) last_e[step & 1] = prev; }      // (the thread that places the step's last output)
+            }
+            if (HEADS) {
+                u32 n_lo = 0, n_hi = 0;
+#pragma unroll
+                for (u32 r = 0; r < GM_MI; ++r) { n_lo += __popcll(__ballot((h_lo >> r) & 1u)); n_hi += __popcll(__ballot((h_hi >> r) & 1u)); }
+                if ((tid & 63) == 0) { if (n_lo) atomicAdd(&step_heads[0], n_lo); if (n_hi) atomicAdd(&step_heads[1], n_hi); }
             }
             __syncthreads();
             const u32 ua = *used_a;
-            ca += ua; cb += c - ua; o += c;
+            if (HEADS && tid == 0) {                          // (one thread: a global atomic per touched block and step)
+                const u64 blk = o / SRC_HEAD_BLOCK;
+                if (step_heads[0]) { atomicAdd(&head_counts[blk], step_heads[0]); step_heads[0] = 0u; }
+                if (step_heads[1]) { atomicAdd(&head_counts[blk + 1], step_heads[1]); step_heads[1] = 0u; }
+            }
+            ca += ua; cb += c - ua; o += c; ++step;
             __syncthreads();                                  // (used_a is read before the next step's last thread writes it)
         }
     }
 }
 uint32_t dev_group_merge_cap() { return GM_CAP; }
+uint64_t dev_source_head_blocks(uint64_t n_edges) { return (n_edges + SRC_HEAD_BLOCK - 1) / SRC_HEAD_BLOCK; }
 int dev_group_merge(const uint64_t* a_key, const uint32_t* a_w, const uint64_t* a_first, const uint32_t* a_count, const uint64_t* a_off,
                     const uint64_t* b_key, const uint32_t* b_w, const uint64_t* b_first, uint32_t k, uint64_t* out_key, uint32_t* out_w,
-                    uint64_t n_out, hipStream_t stream) {
+                    uint64_t n_out, hipStream_t stream, uint32_t* head_counts) {
     if (k < 9 || 2 * k > 62) { set_error("group merge: k = %u", k); return KATOME_E_ARG; }
-    KCHECK_HIP(hipFuncSetAttribute((const void*)group_merge_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GM_LDS));
+    // (head_counts: ceil(n_out / SRC_HEAD_BLOCK) counts, added to by every workgroup whose group reaches into the block)
+    if (head_counts) KCHECK_HIP(hipMemsetAsync(head_counts, 0, dev_source_head_blocks(n_out) * sizeof(u32), stream));
+    const auto kernel = head_counts ? group_merge_kernel<true> : group_merge_kernel<false>;
+    KCHECK_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GM_LDS));
     KernelScope ks(K_GROUP_MERGE, stream, n_out);
-    hipLaunchKernelGGL(group_merge_kernel, dim3(256u), dim3(GM_THREADS), GM_LDS, stream, a_key, a_w, a_first, a_count, a_off, b_key, b_w, b_first, k,
-                       out_key, out_w, n_out);
+    hipLaunchKernelGGL(kernel, dim3(256u), dim3(GM_THREADS), GM_LDS, stream, a_key, a_w, a_first, a_count, a_off, b_key, b_w, b_first, k, out_key, out_w, n_out,
+                       head_counts);
     KCHECK_HIP(hipGetLastError());
     return KATOME_OK;
 }
@@ -1077,10 +1133,10 @@ uint32_t dev_sort_tile_keys(uint32_t nw) { return nw == 1 ? SortTile<1>::KEYS : 
 // records of nwk + 1 words (k-mer, tag) with their counts, ordered by the top 16 bits of the K-MER's hash (two stable passes)
 template <int NW>
 static int tagged_order_t(const u64* d_in, const u32* w_in, u64 n, u64* ka, u64* kb, u32* wa, u32* wb, const u64** k_out, const u32** w_out, hipStream_t stream,
-                          const u32* first_counts = nullptr) {
+                          u32* first_counts = nullptr) {
     PassBuffers pb;
     KCHECK(pb.init(n, NW, stream));
-    if (first_counts) KCHECK_HIP(hipMemcpyAsync(pb.counts.p, first_counts, pb.nblocks * RADIX * sizeof(u32), hipMemcpyDeviceToDevice, stream));
+    pb.first = first_counts;
     const u64* kin = d_in; const u32* win = w_in;
     u64* kdst[2] = {ka, kb}; u32* wdst[2] = {wa, wb};
     for (int p = 0; p < 2; ++p) {
@@ -1114,7 +1170,7 @@ int dev_hash_order_core(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, 
     return KATOME_OK;
 }
 int dev_hash_order_tagged(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t nwk, uint64_t* ka, uint64_t* kb, uint32_t* wa, uint32_t* wb,
-                          const uint64_t** k_out, const uint32_t** w_out, uint32_t* group_bits, hipStream_t stream, const uint32_t* first_counts) {
+                          const uint64_t** k_out, const uint32_t** w_out, uint32_t* group_bits, hipStream_t stream, uint32_t* first_counts) {
     *group_bits = 16;
     if (nwk == 1) return tagged_order_t<2>(d_in, w_in, n, ka, kb, wa, wb, k_out, w_out, stream, first_counts);
     if (nwk == 2) return tagged_order_t<3>(d_in, w_in, n, ka, kb, wa, wb, k_out, w_out, stream, first_counts);
@@ -1332,6 +1388,7 @@ int dev_rank(const uint64_t* d_sorted, uint64_t n_sorted, uint32_t nw, uint32_t 
 template <int NW> __device__ __forceinline__ bool is_src_head(const u64* keys, u64 i) {
     return i == 0 || !key_eq(key_shr(load_key<NW>(keys, i), 2), key_shr(load_key<NW>(keys, i - 1), 2));
 }
+static_assert(SRC_HEAD_BLOCK == UNIQ_TILE, "group_merge_kernel counts the heads of exactly src_count_kernel's blocks");
 template <int NW>
 __global__ __launch_bounds__(BLOCK) void src_count_kernel(const u64* __restrict__ keys, u64 n, u32* __restrict__ block_counts) {
     __shared__ u32 wsum[BLOCK / 64];
@@ -1345,22 +1402,48 @@ __global__ __launch_bounds__(BLOCK) void src_count_kernel(const u64* __restrict_
 }
 // writes the distinct sources (= node keys) and every edge's source id.  Rows of BLOCK consecutive edges are
 // taken one after the other (coalesced loads and stores); a ballot scan per row keeps the running head count.
-template <int NW>
+// LABELS: the edges' labels too (labels_kernel's bytes exactly: [pad][ceil(k/4) bytes] per edge), from the keys the kernel holds
+// anyway -- built in LDS, UNIQ_TILE * stride bytes, and written out as whole dwords, so that no second pass reads the keys
+template <int NW, bool LABELS = false>
 __global__ __launch_bounds__(BLOCK) void src_write_kernel(const u64* __restrict__ keys, u64 n, const u64* __restrict__ block_offs,
-                                                           u64* __restrict__ nodes, u64* __restrict__ edge_src, u64* __restrict__ seg_edge, u32 seg_nodes) {
+                                                           u64* __restrict__ nodes, u64* __restrict__ edge_src, u64* __restrict__ seg_edge, u32 seg_nodes,
+                                                           u32 k, uint8_t* __restrict__ labels) {
     __shared__ u32 wtot[UNIQ_ITEMS][BLOCK / 64];
+    extern __shared__ u32 src_lbuf[];                      // LABELS: [UNIQ_TILE * stride / 4]
     const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const u64 base = (u64)blockIdx.x * UNIQ_TILE;
     bool head[UNIQ_ITEMS]; u32 before[UNIQ_ITEMS];
+    Key<NW> key[LABELS ? UNIQ_ITEMS : 1];                  // LABELS: the block's keys stay in registers
+    const u32 stride = LABELS ? label_stride_for_k(k) : 0u, pad = LABELS ? label_pad_for_k(k) : 0u;
+    if constexpr (LABELS) {
+#pragma unroll
+        for (int j = 0; j < UNIQ_ITEMS; ++j) { const u64 e = base + (u64)j * BLOCK + threadIdx.x; if (e < n) key[j] = load_key<NW>(keys, e); }
+    }
 #pragma unroll
     for (int j = 0; j < UNIQ_ITEMS; ++j) {
         const u64 e = base + (u64)j * BLOCK + threadIdx.x;
-        head[j] = e < n && is_src_head<NW>(keys, e);
+        if constexpr (LABELS) head[j] = e < n && (e == 0 || !key_eq(key_shr(key[j], 2), key_shr(load_key<NW>(keys, e - 1), 2)));
+        else head[j] = e < n && is_src_head<NW>(keys, e);
         const u64 m = __ballot(head[j]);
         before[j] = __popcll(m & (lane ? (~0ull >> (64 - lane)) : 0ull));
         if (lane == 0) wtot[j][wave] = __popcll(m);
+        if constexpr (LABELS) {
+            if (e < n) {
+                uint8_t* p = reinterpret_cast<uint8_t*>(src_lbuf) + (j * BLOCK + threadIdx.x) * stride;
+                p[0] = (uint8_t)pad;
+                for (u32 i = 0; i + 1 < stride; ++i) p[1 + i] = label_byte(key[j], k, i);
+            }
+        }
     }
     __syncthreads();
+    if constexpr (LABELS) {
+        // UNIQ_TILE * stride is a multiple of 4, so a block's labels start on a dword; the array's last bytes leave one by one
+        const u32 cnt = (u32)((n - base) < (u64)UNIQ_TILE ? (n - base) : (u64)UNIQ_TILE), nbytes = cnt * stride;
+        const u64 byte0 = base * stride;
+        u32* o32 = reinterpret_cast<u32*>(labels + byte0);
+        for (u32 i = threadIdx.x; i < nbytes / 4; i += BLOCK) o32[i] = src_lbuf[i];
+        for (u32 i = (nbytes / 4) * 4 + threadIdx.x; i < nbytes; i += BLOCK) labels[byte0 + i] = reinterpret_cast<uint8_t*>(src_lbuf)[i];
+    }
     u64 carry = block_offs[blockIdx.x];
 #pragma unroll
     for (int j = 0; j < UNIQ_ITEMS; ++j) {
@@ -1371,7 +1454,8 @@ __global__ __launch_bounds__(BLOCK) void src_write_kernel(const u64* __restrict_
         if (e < n) {
             const u64 pos = carry + woff + before[j];           // heads strictly before this edge
             if (head[j]) {
-                store_key<NW>(nodes, pos, key_shr(load_key<NW>(keys, e), 2));
+                if constexpr (LABELS) store_key<NW>(nodes, pos, key_shr(key[j], 2));
+                else store_key<NW>(nodes, pos, key_shr(load_key<NW>(keys, e), 2));
                 if (seg_edge && pos % seg_nodes == 0) seg_edge[pos / seg_nodes] = e;      // first out-edge of every seg_nodes-th source
             }
             edge_src[e] = head[j] ? pos : pos - 1;
@@ -1680,20 +1764,24 @@ __global__ __launch_bounds__(BLOCK) void missing_first_kernel(const u64* __restr
 
 // the distinct source (k-1)-mers of sorted edges (the run heads of key >> 2), ascending, and every edge's position among them
 // (`slack`: room kept behind them in node_key, in nodes, for the caller to append to)
+// (head_counts: the run heads of every block of UNIQ_TILE edges, counted already by whoever wrote the edges -- group_merge_kernel --
+// so that src_count_kernel need not read them; labels: the edges' labels (dev_labels' bytes) are written on the way, k their k)
 template <int NW>
 static int source_ids_t(const u64* d_edge_key, u64 E, DevBuf& node_key, u64* edge_src, u64* n_src_out, hipStream_t stream, bool with_slack = false,
-                        DevBuf* seg_edge = nullptr) {
+                        DevBuf* seg_edge = nullptr, const u32* head_counts = nullptr, u32 k = 0, uint8_t* labels = nullptr) {
     *n_src_out = 0;
     if (E == 0) { KCHECK(node_key.alloc(16, stream)); return KATOME_OK; }
     const u64 nblocks = (E + UNIQ_TILE - 1) / UNIQ_TILE;
     if (nblocks > 0x7fffffffull) { set_error("node numbering: too many edges"); return KATOME_E_ARG; }
+    if (labels && (uintptr_t)labels % 4) { set_error("label buffer must be 4-byte aligned"); return KATOME_E_ARG; }
     DevBuf counts(stream), offs(stream);
-    KCHECK(counts.alloc(nblocks * 4));
+    if (!head_counts) KCHECK(counts.alloc(nblocks * 4));
     KCHECK(offs.alloc((nblocks + 1) * 8));
     {
         KernelScope ks(K_SRC_IDS, stream, E);
-        hipLaunchKernelGGL(src_count_kernel<NW>, dim3((unsigned)nblocks), dim3(BLOCK), 0, stream, d_edge_key, E, counts.as<u32>());
-        KCHECK(dev_scan_counts(counts.as<u32>(), nblocks, offs.as<u64>(), stream));      // (C3: 8e5 counts -- one workgroup walking them alone took 1.2 ms)
+        if (!head_counts) hipLaunchKernelGGL(src_count_kernel<NW>, dim3((unsigned)nblocks), dim3(BLOCK), 0, stream, d_edge_key, E, counts.as<u32>());
+        else if (getenv("KATOME_LC_TRACE")) fprintf(stderr, "[node ids] heads from the merge\n");
+        KCHECK(dev_scan_counts(head_counts ? head_counts : counts.as<u32>(), nblocks, offs.as<u64>(), stream));      // (C3: 8e5 counts -- one workgroup walking them alone took 1.2 ms)
     }
     u64 n_src = 0;
     KCHECK_HIP(hipMemcpyAsync(&n_src, offs.as<u64>() + nblocks, 8, hipMemcpyDeviceToHost, stream));
@@ -1703,8 +1791,15 @@ static int source_ids_t(const u64* d_edge_key, u64 E, DevBuf& node_key, u64* edg
     if (seg_edge) KCHECK(seg_edge->alloc(((n_src + DST_SEG - 1) / DST_SEG + 1) * 8));        // first out-edge of every DST_SEG-th source
     {
         KernelScope ks(K_SRC_IDS, stream, E);
-        hipLaunchKernelGGL(src_write_kernel<NW>, dim3((unsigned)nblocks), dim3(BLOCK), 0, stream, d_edge_key, E, offs.as<u64>(), node_key.as<u64>(), edge_src,
-                           seg_edge ? seg_edge->as<u64>() : nullptr, DST_SEG);
+        if (labels) {
+            if (getenv("KATOME_LC_TRACE")) fprintf(stderr, "[node ids] labels written with the source ids\n");
+            const size_t lds = (size_t)UNIQ_TILE * label_stride_for_k(k);          // (18 KiB at k = 31, 34 KiB at k = 63)
+            hipLaunchKernelGGL((src_write_kernel<NW, true>), dim3((unsigned)nblocks), dim3(BLOCK), lds, stream, d_edge_key, E, offs.as<u64>(), node_key.as<u64>(),
+                               edge_src, seg_edge ? seg_edge->as<u64>() : nullptr, DST_SEG, k, labels);
+        } else {
+            hipLaunchKernelGGL((src_write_kernel<NW, false>), dim3((unsigned)nblocks), dim3(BLOCK), 0, stream, d_edge_key, E, offs.as<u64>(), node_key.as<u64>(), edge_src,
+                               seg_edge ? seg_edge->as<u64>() : nullptr, DST_SEG, 0u, (uint8_t*)nullptr);
+        }
     }
     KCHECK_HIP(hipGetLastError());
     *n_src_out = n_src;
@@ -1721,7 +1816,8 @@ int dev_source_ids(const uint64_t* d_edge_key, uint64_t n_edges, uint32_t k, Dev
 // as a target; left empty when the merging look-up is switched off (the caller then runs dev_node_first)
 template <int NW>
 static int node_ids_t(const u64* d_edge_key, u64 E, u32 k, DevBuf& node_key, u64* edge_src, u64* edge_dst, u64* n_nodes,
-                      hipStream_t stream, const u64* seq = nullptr, DevBuf* node_first = nullptr, u64* n_marked = nullptr) {
+                      hipStream_t stream, const u64* seq = nullptr, DevBuf* node_first = nullptr, u64* n_marked = nullptr,
+                      const u32* head_counts = nullptr, uint8_t* labels = nullptr) {
     *n_nodes = 0;
     if (n_marked) *n_marked = 0;
     if (node_first) node_first->release();
@@ -1734,7 +1830,7 @@ static int node_ids_t(const u64* d_edge_key, u64 E, u32 k, DevBuf& node_key, u64
     static const bool old_lookup = getenv("KATOME_DST_RANK") != nullptr;
     const bool first = seq && node_first && !old_lookup;
     DevBuf seg_edge(stream);
-    KCHECK((source_ids_t<NW>(d_edge_key, E, node_key, edge_src, &n_src, stream, true, first ? &seg_edge : nullptr)));
+    KCHECK((source_ids_t<NW>(d_edge_key, E, node_key, edge_src, &n_src, stream, true, first ? &seg_edge : nullptr, head_counts, k, labels)));
     u64* nodes = node_key.as<u64>();
     // targets -> positions among the sources
     if (first && n_marked) *n_marked = n_src;            // (edge_dst carries the merge's marks for the targets that are sources)
@@ -1833,9 +1929,11 @@ static int node_ids_t(const u64* d_edge_key, u64 E, u32 k, DevBuf& node_key, u64
 }
 
 int dev_node_ids(const uint64_t* d_edge_key, uint64_t n_edges, uint32_t k, DevBuf& node_key, uint64_t* d_edge_src,
-                 uint64_t* d_edge_dst, uint64_t* n_nodes, hipStream_t stream, const uint64_t* d_seq, DevBuf* node_first, uint64_t* n_marked) {
-    if (key_words_for_k(k) == 1) return node_ids_t<1>(d_edge_key, n_edges, k, node_key, d_edge_src, d_edge_dst, n_nodes, stream, d_seq, node_first, n_marked);
-    return node_ids_t<2>(d_edge_key, n_edges, k, node_key, d_edge_src, d_edge_dst, n_nodes, stream, d_seq, node_first, n_marked);
+                 uint64_t* d_edge_dst, uint64_t* n_nodes, hipStream_t stream, const uint64_t* d_seq, DevBuf* node_first, uint64_t* n_marked,
+                 const uint32_t* head_counts, uint8_t* d_label) {
+    if (key_words_for_k(k) == 1) return node_ids_t<1>(d_edge_key, n_edges, k, node_key, d_edge_src, d_edge_dst, n_nodes, stream, d_seq, node_first, n_marked,
+                                                      head_counts, d_label);
+    return node_ids_t<2>(d_edge_key, n_edges, k, node_key, d_edge_src, d_edge_dst, n_nodes, stream, d_seq, node_first, n_marked, head_counts, d_label);
 }
 
 // ---- first-seen order: small permutation helpers ---------------------------------------------------

@@ -2299,7 +2299,7 @@ int tiles_to_edges_sorted_seen(Table& tiles, uint32_t k, uint32_t span, bool rc,
 // {sequence number, weight}.  list == true (a tile level): the distinct keys with their tags, out_keys [d][nwk + 1], and their counts,
 // out_second [d] u32.  The records come back permuted.
 int tagged_records_sorted(DevBuf& recs, DevBuf& wts, uint64_t n, uint32_t k, bool rc, uint64_t seq_per_read, bool list, DevBuf& edge_key,
-                          DevBuf& seq_weight, uint64_t* n_edges, uint64_t* n_distinct, hipStream_t stream, const uint32_t* first_counts) {
+                          DevBuf& seq_weight, uint64_t* n_edges, uint64_t* n_distinct, hipStream_t stream, uint32_t* first_counts) {
     *n_edges = 0; *n_distinct = 0;
     const uint32_t nwk = (uint32_t)key_words_for_k(k), stride = nwk + 1;
     constexpr u32 FILL = (u32)(LC_THREADS * LCS_PER / 4096.0 * 2900);
@@ -2380,7 +2380,7 @@ int table_orient_records(uint64_t* d_keys, uint64_t n, uint32_t k, bool rep, hip
 // group of more distinct keys than the table holds (err 3: key ranges are far less even than hash ranges on skewed or low-complexity
 // input) or a count beyond 16 bits (err 5); the records are then still all there, ordered by key, in their representative orientation.
 static int ordered_count(DevBuf& keys, DevBuf& weights, uint64_t n, uint32_t k, bool rc, uint32_t min_weight, HalfSort& hs, uint64_t* n_edges,
-                         uint64_t* n_distinct, hipStream_t stream, const uint32_t* first_counts) {
+                         uint64_t* n_distinct, hipStream_t stream, uint32_t* first_counts) {
     // (one visit per record: a group must fit the 8-byte-slot table at lds_count_packed_kernel's planning load)
     const u64 avg = n >> 16;
     if (!n || !weights.p || k < 9 || 2 * k > 62 || (rc && !(k & 1)) || (double)avg * 0.56 > LP_SLOTS * 0.66) return KATOME_E_UNSUPPORTED;
@@ -2448,7 +2448,9 @@ static uint64_t s2_group_cap() {
 // S2 ordered per 16-bit group only, in LDS inside the merge (group_merge_kernel), when its largest group fits: two partition passes
 // instead of four and no run sort.  Otherwise, or with KATOME_S2_GROUP_SORT=0, S2 is sorted in full and half_merge_kernel merges it
 // (a full sort of the partitioned S2 leaves the same groups, so b_first stands).
-int half_sort_finish(HalfSort& hs, DevBuf& edge_key, DevBuf& edge_weight, hipStream_t stream) {
+// KATOME_MERGE_HEADS=0: the merge counts no source run heads for the node numbering (head_counts comes back empty)
+int half_sort_finish(HalfSort& hs, DevBuf& edge_key, DevBuf& edge_weight, hipStream_t stream, DevBuf* head_counts) {
+    if (head_counts) head_counts->release();
     if (!hs.taken) { set_error("half sort: no ordered count to finish"); return KATOME_E_ARG; }
     const uint32_t k = hs.k;
     DevBuf b_first(stream), a_off(stream);
@@ -2479,10 +2481,13 @@ int half_sort_finish(HalfSort& hs, DevBuf& edge_key, DevBuf& edge_weight, hipStr
     KCHECK(dev_scan_counts(hs.group_count.as<u32>(), 1ull << 16, a_off.as<u64>(), stream));
     const uint64_t n_out = hs.n_s1 + hs.n_s2;
     KCHECK(edge_key.alloc((n_out + 1) * 8, stream)); KCHECK(edge_weight.alloc((n_out + 1) * 4, stream));
-    if (grouped)
+    if (grouped) {
+        static const bool heads = !getenv("KATOME_MERGE_HEADS") || atoi(getenv("KATOME_MERGE_HEADS")) != 0;
+        if (head_counts && heads && n_out) KCHECK(head_counts->alloc(dev_source_head_blocks(n_out) * 4, stream));
         KCHECK(dev_group_merge(hs.s1_key.as<u64>(), hs.s1_w.as<u32>(), hs.group_first.as<u64>(), hs.group_count.as<u32>(), a_off.as<u64>(),
-                               hs.s2_key.as<u64>(), hs.s2_w.as<u32>(), b_first.as<u64>(), k, edge_key.as<u64>(), edge_weight.as<u32>(), n_out, stream));
-    else
+                               hs.s2_key.as<u64>(), hs.s2_w.as<u32>(), b_first.as<u64>(), k, edge_key.as<u64>(), edge_weight.as<u32>(), n_out, stream,
+                               head_counts ? head_counts->as<u32>() : nullptr));
+    } else
         KCHECK(dev_half_merge(hs.s1_key.as<u64>(), hs.s1_w.as<u32>(), hs.group_first.as<u64>(), hs.group_count.as<u32>(), a_off.as<u64>(),
                               hs.s2_key.as<u64>(), hs.s2_w.as<u32>(), b_first.as<u64>(), edge_key.as<u64>(), edge_weight.as<u32>(), n_out, stream));
     hs.release();
@@ -2491,7 +2496,7 @@ int half_sort_finish(HalfSort& hs, DevBuf& edge_key, DevBuf& edge_weight, hipStr
 
 int records_to_edges_sorted(DevBuf& keys, DevBuf& weights, uint64_t n, uint32_t k, bool rc, uint32_t min_weight, DevBuf& edge_key,
                             DevBuf& edge_weight, uint64_t* n_edges, uint64_t* n_distinct, hipStream_t stream, OwnerSplit* split,
-                            const uint32_t* first_counts, HalfSort* half) {
+                            uint32_t* first_counts, HalfSort* half) {
     *n_edges = 0; *n_distinct = 0;
     if (half) {
         half->taken = false;

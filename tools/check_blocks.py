@@ -10,6 +10,12 @@ for ln, line in enumerate(open(sys.argv[1])):
                 print("OVERLAP line", ln, hex(p), n, "with", hex(q), m2, "from line", l2); bad += 1
         live[p] = (n, ln)
         continue
+    m = re.match(r"\[katome block\] < (0x[0-9a-f]+) (\d+)", line)          # trimmed in place: what the block still holds
+    if m:
+        p = int(m.group(1), 16)
+        if p in live:
+            live[p] = (int(m.group(2)), live[p][1])
+        continue
     m = re.match(r"\[katome block\] - (0x[0-9a-f]+)", line)
     if m:
         p = int(m.group(1), 16)
