@@ -487,6 +487,7 @@ int tile_recs_valid(katome_builder* b, uint64_t* n, hipStream_t stream) {
 // no tile records are kept from here on (they were counted, or went into the tile table)
 static void close_tile_recs(katome_builder* b) {
     b->tile_recs.release(); b->tile_recs_count.release(); b->tile_recs_n = b->tile_recs_cap = 0;
+    b->tile_recs_hist.release(); b->tile_recs_hist_ok = false;
     b->tile_recs_exact = false; b->tile_recs_closed = true;
 }
 int flush_tile_recs(katome_builder* b, hipStream_t stream) {
@@ -555,6 +556,7 @@ static int reserve_tile_recs(katome_builder* b, uint64_t n, uint32_t nwt, bool* 
 // a batch's tiles kept aside as records; *kept = false: they go into the tile table
 int keep_tile_recs(katome_builder* b, const uint64_t* d_records, uint64_t n, uint32_t nwt, bool* kept, hipStream_t stream) {
     *kept = false;
+    b->tile_recs_hist_ok = false;          // (records that nobody counted as they were written)
     bool ok = false;
     // (first-seen order: a record is kept with its tag -- read << 32 | number of its first window << 16 | of its reverse complement's)
     const uint32_t words = nwt + (b->first_seen ? 1 : 0);
@@ -593,7 +595,10 @@ static uint64_t level_budget() {
 static bool level_fits(uint64_t n_records, uint32_t key_words, bool oriented, const char* what) {
     const char* sl = getenv("KATOME_LEVEL_SLACK");           // (room left for everything else: group index, cursors, the allocator's rounding)
     const uint64_t slack = sl ? strtoull(sl, nullptr, 10) : (256ull << 20);
-    const uint64_t pair = 8ull * key_words + 4, need = n_records * pair * (oriented ? 4 : 3) + slack, have = level_budget();
+    // (+ a byte per record where the partition passes keep a digit stream -- records of two or three words -- and a byte per oriented
+    // edge for S2's first digits)
+    const uint64_t digits = (dev_digit_stream_pays(key_words) ? 1 : 0) + (oriented ? 1 : 0);
+    const uint64_t pair = 8ull * key_words + 4, need = n_records * (pair * (oriented ? 4 : 3) + digits) + slack, have = level_budget();
     if (need <= have) return true;
     if (getenv("KATOME_LEVEL_TRACE"))
         fprintf(stderr, "[katome levels] %s: %llu records need %.1f GiB by sorting, %.1f GiB available -- this level and those below are counted in tables\n",
@@ -638,7 +643,8 @@ static int kmer_records_in_parts(katome_builder* b, const uint64_t* lk, const ui
     const uint64_t slack = sl ? strtoull(sl, nullptr, 10) : (256ull << 20);
     // a part's records, the passes' scratch and its list (three times the records) in half of what is there; the other half holds the lists
     uint32_t P = 2;
-    while (P <= 64 && (total / P + last_span) * pair * 3 + slack > have / 2) P *= 2;
+    const uint64_t digits = dev_digit_stream_pays(nw) ? 1 : 0;          // (the passes' digit stream, where records of this width keep one)
+    while (P <= 64 && (total / P + last_span) * (pair * 3 + digits) + slack > have / 2) P *= 2;
     if (P > 64 || n_last < P) return KATOME_E_UNSUPPORTED;
     if (getenv("KATOME_LEVEL_TRACE")) fprintf(stderr, "[katome levels] k-mers: counted in %u parts of %llu records\n", P, (unsigned long long)(total / P));
     PhaseScope ps(b->prof, PH_EXPAND_TILES, stream);
@@ -695,8 +701,11 @@ int tile_recs_to_kmer_records(katome_builder* b, DevBuf& keys, DevBuf& weights, 
         DevBuf ones(stream);          // (stays empty: records without weights count once each, and the passes move 16 bytes a record, not 20)
         uint64_t n = 0;
         KCHECK(tile_recs_valid(b, &n, stream));
-        rc = n ? records_to_edges_sorted(b->tile_recs, ones, n, tile_bases, false, 0, t1k, t1w, &n1, &d1, stream)
+        // (the whole array is ordered in this one call: the counts the extraction left, where they cover it, are its first pass's)
+        u32* const first = b->tile_recs_hist_ok && n == b->tile_recs_n && nwt == 2 ? b->tile_recs_hist.as<u32>() : nullptr;
+        rc = n ? records_to_edges_sorted(b->tile_recs, ones, n, tile_bases, false, 0, t1k, t1w, &n1, &d1, stream, nullptr, first)
                : KATOME_E_UNSUPPORTED;                          // (every read was skipped: nothing to count)
+        b->tile_recs_hist_ok = false;                           // (the pass worked in them: prefixes now)
         if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
     }
     if (rc == KATOME_E_UNSUPPORTED) {
@@ -886,6 +895,24 @@ static bool keeps_tile_recs(const katome_builder* b, uint32_t nwt) {
            sorted_tiles_mode() == 2;
 }
 
+// room in b->tile_recs_hist for the counts of n_total kept records (the record array's capacity; what is there is kept);
+// false: no room -- the first pass counts for itself
+static bool reserve_tile_hist(katome_builder* b, uint64_t n_total, uint32_t sort_tile, bool keep, hipStream_t stream) {
+    const uint64_t need = ((n_total + sort_tile - 1) / sort_tile) * 256 * 4 + 16;
+    if (need <= b->tile_recs_hist.bytes) return true;
+    DevBuf grown(stream);
+    if (grown.alloc(need) != KATOME_OK) return false;
+    if (keep && b->tile_recs_hist.p &&
+        hipMemcpyAsync(grown.p, b->tile_recs_hist.p, ((b->tile_recs_n + sort_tile - 1) / sort_tile) * 256 * 4, hipMemcpyDeviceToDevice, stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    const size_t grown_bytes = grown.bytes;
+    b->tile_recs_hist.adopt(grown.take(), grown_bytes);
+    b->tile_recs_hist.stream = stream;
+    return true;
+}
+
 int katome_dev_count_tiles(katome_builder* b, const uint8_t* d_packed, uint64_t n_reads, uint32_t read_len, uint32_t span,
                            const uint8_t* d_skip, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
@@ -906,7 +933,28 @@ int katome_dev_count_tiles(katome_builder* b, const uint8_t* d_packed, uint64_t 
             KCHECK(reserve_tile_recs(b, n, nwt, &ok, stream));
         }
         if (ok && b->tile_recs_exact) {
-            KCHECK(katome_dev_extract_tiles(b, d_packed, n_reads, read_len, span, nullptr, b->tile_recs.as<u64>() + b->tile_recs_n * nwt, stream));
+            // The extraction knows the index of every record it writes, so where this batch starts on a sort-tile boundary of the kept
+            // array -- and every batch before it did -- it also leaves the first partition pass's digit counts of the sort tiles it
+            // fills (KATOME_FUSED_HIST=0: never; the pass counts for itself, as it does in every other case)
+            static const bool fused_hist = !getenv("KATOME_FUSED_HIST") || atoi(getenv("KATOME_FUSED_HIST")) != 0;
+            const uint32_t sort_tile = dev_sort_tile_keys(nwt);
+            u64* const dst = b->tile_recs.as<u64>() + b->tile_recs_n * nwt;
+            const bool counted = fused_hist && (b->tile_recs_n == 0 || b->tile_recs_hist_ok) && b->tile_recs_n % sort_tile == 0 &&
+                                 extract_tile_counts_ok(b->s.k, read_len, span, sort_tile, d_packed, dst) &&
+                                 reserve_tile_hist(b, std::max<uint64_t>(b->tile_recs_n + n, b->tile_recs_cap), sort_tile, b->tile_recs_n != 0, stream);
+            if (getenv("KATOME_LC_TRACE"))
+                fprintf(stderr, "[tiles] batch of %llu records at %llu: %s\n", (unsigned long long)n, (unsigned long long)b->tile_recs_n,
+                        counted ? "first-pass counts from the extraction" : "no counts");
+            if (counted) {
+                KCHECK(check_seen_len(b, read_len));
+                PhaseScope ps(b->prof, PH_EXTRACT, stream);
+                b->seen_read_len = read_len;
+                KCHECK(launch_extract_tiles_counted(b->s.k, b->rc, d_packed, n_reads, read_len, span, dst, b->tile_recs_hist.as<u32>() + (b->tile_recs_n / sort_tile) * 256,
+                                                    sort_tile, stream));
+            } else {
+                KCHECK(katome_dev_extract_tiles(b, d_packed, n_reads, read_len, span, nullptr, dst, stream));
+            }
+            b->tile_recs_hist_ok = counted;
             b->span = span;
             b->tile_recs_n += n;
             return KATOME_OK;

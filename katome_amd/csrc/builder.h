@@ -49,6 +49,11 @@ struct katome_builder {
     DevBuf tile_recs, tile_recs_count;  // tile_recs_count: device cursor -- the valid ones among them (a skipped read's tiles are all-ones)
     uint64_t tile_recs_n = 0, tile_recs_cap = 0;      // tile_recs_n: records handed over (an upper bound of the cursor)
     bool tile_recs_closed = false;
+    // tile_recs_hist: counts[sort tile][256] of the first partition pass's digit over tile_recs, left by the extraction that wrote the
+    // records (katome_dev_count_tiles); tile_recs_hist_ok: they cover all of tile_recs -- every batch so far started on a sort-tile
+    // boundary and was written in place.  They grow and go with the records.
+    DevBuf tile_recs_hist;
+    bool tile_recs_hist_ok = false;
     bool tile_recs_exact = false;       // every record handed over so far was valid (tile_recs_n IS the count: katome_dev_count_tiles writes in place)
     DevBuf tile_scratch;                // katome_dev_count_tiles: a batch's records when they cannot be made where they are kept
     DevBuf rest_k, rest_count;          // rest_count: device cursor -- how many of them are valid records (reads with N leave invalid ones)

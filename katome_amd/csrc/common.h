@@ -185,6 +185,10 @@ inline unsigned grid_for(uint64_t work_items, unsigned per_block, unsigned cap =
 int launch_extract_fixed(uint32_t k, bool rc, const uint8_t* d_packed, uint64_t n_reads, uint32_t read_len,
                          const uint8_t* d_skip, uint64_t* d_records, hipStream_t stream, uint32_t span = 1, bool mark = false,
                          uint32_t first_window = 0, uint32_t records_per_read = 0);
+// (the tiles of a batch of clean reads written where they are kept, with the first partition pass's digit counts per sort tile: extract.hip)
+bool extract_tile_counts_ok(uint32_t k, uint32_t read_len, uint32_t span, uint32_t sort_tile, const uint8_t* d_packed, const uint64_t* d_records);
+int launch_extract_tiles_counted(uint32_t k, bool rc, const uint8_t* d_packed, uint64_t n_reads, uint32_t read_len, uint32_t span,
+                                 uint64_t* d_records, uint32_t* d_counts, uint32_t sort_tile, hipStream_t stream);
 int launch_extract_var(uint32_t k, bool rc, const uint8_t* d_packed, uint64_t packed_bytes, const uint64_t* d_byte_off,
                        const uint32_t* d_len, const uint64_t* d_win_prefix, uint64_t n_reads, uint64_t total_windows,
                        uint64_t* d_records, hipStream_t stream, bool mark = false, uint32_t span = 1, uint32_t mode = 0);
@@ -222,8 +226,13 @@ int dev_hash_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint3
                    const uint64_t** k_out, const uint32_t** w_out, uint32_t* group_bits, hipStream_t stream, uint32_t* first_counts = nullptr);
 uint32_t dev_sort_tile_keys(uint32_t nw);
 // one-word records by their leading 16 key bits (k = 8..32): two stable passes; the result where *k_out / *w_out point (kb / wb)
+// (first_digits: the first pass's digit of every record -- bits 2k - 16 .. 2k - 9 of its key --, one byte each at the record's index in
+// a buffer of dev_digit_stream_bytes(n, 1) bytes, left by whoever wrote the records; the pass then counts from them, not the keys)
 int dev_key_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t k, uint64_t* ka, uint64_t* kb, uint32_t* wa, uint32_t* wb,
-                  const uint64_t** k_out, const uint32_t** w_out, hipStream_t stream, uint32_t* first_counts = nullptr);
+                  const uint64_t** k_out, const uint32_t** w_out, hipStream_t stream, uint32_t* first_counts = nullptr,
+                  const uint8_t* first_digits = nullptr);
+size_t dev_digit_stream_bytes(uint64_t n, uint32_t nw);
+bool dev_digit_stream_pays(uint32_t nw);        // do records of nw words get a digit stream between their two partition passes?
 // index[g] (65537 of them) = first of n ascending one-word keys whose bits [shift, shift + 16) are >= g
 int dev_key_group_index(const uint64_t* d_keys, uint64_t n, uint32_t shift, uint64_t* d_index, hipStream_t stream);
 // merges, per 16-bit key prefix g, a_count[g] ascending keys at a_key + a_first[g] with the sorted b_key[b_first[g] .. b_first[g + 1])
@@ -413,11 +422,12 @@ struct OwnerSplit {
 // gives -- and releases them.
 struct HalfSort {
     DevBuf s1_key, s1_w, group_first, group_count, s2_key, s2_w;
+    DevBuf s2_digit;           // (beside s2_key: the first partition digit of every S2 key, one byte each -- dev_key_order's first_digits)
     uint64_t n_s1 = 0, n_s2 = 0;
     uint32_t k = 0;
     bool taken = false;
     void release() {
-        s1_key.release(); s1_w.release(); group_first.release(); group_count.release(); s2_key.release(); s2_w.release();
+        s1_key.release(); s1_w.release(); group_first.release(); group_count.release(); s2_key.release(); s2_w.release(); s2_digit.release();
         n_s1 = n_s2 = 0; taken = false;
     }
 };

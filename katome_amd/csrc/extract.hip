@@ -44,11 +44,19 @@ __device__ __forceinline__ Key<NW> record_from_lds(const u32* lds, const uint8_t
     return key;
 }
 
-template <int NW, bool RC, int TILE_READS>
+// HIST (two-word records, no read skipped, TILE_READS * W a multiple of sort_tile, `out` on a sort-tile boundary of the array the
+// records are kept in): the kernel also leaves counts[tile][256] of the first partition digit -- byte 6 of the record's hash,
+// radix.hip HashDigit<2>{48} -- for the sort tiles of sort_tile records it fills, as list_to_records_hist_kernel does for the
+// levels below.  A trip covers whole sort tiles, so the counts are stored, not added; the pass over these records then reads no key
+// to count (C3: 12.8 GB not read again, one hash less per record).
+template <int NW, bool RC, int TILE_READS, bool HIST = false>
 __global__ __launch_bounds__(BLOCK) void extract_fixed_kernel(const uint8_t* __restrict__ packed, u64 n_reads,
                                                                u32 stride_bytes, u32 k, u32 W, u32 magicW, u32 step, u32 win0,
-                                                               const uint8_t* __restrict__ skip, u64* __restrict__ out) {
+                                                               const uint8_t* __restrict__ skip, u64* __restrict__ out,
+                                                               u32* __restrict__ counts = nullptr, u32 sort_tile = 0) {
     extern __shared__ u32 lds[];
+    __shared__ u32 hist[HIST ? 256 : 1];
+    static_assert(!HIST || (NW == 2 && BLOCK == 256), "counts: two-word records, one thread per digit");
     const u32 tile_bytes_max = TILE_READS * stride_bytes;
     const u32 tile_dwords = ((tile_bytes_max + 15) / 16) * 4;
     uint8_t* lds_skip = (uint8_t*)(lds + tile_dwords + 8);
@@ -92,6 +100,19 @@ __global__ __launch_bounds__(BLOCK) void extract_fixed_kernel(const uint8_t* __r
                 } else {
                     out[out0 + i0] = a.w[0];
                 }
+            }
+        } else if (HIST) {
+            for (u32 s0 = 0; s0 < nrec; s0 += sort_tile) {          // (out0 is a multiple of sort_tile: s0 starts a sort tile)
+                hist[tid] = 0;
+                __syncthreads();
+                const u32 s1 = s0 + sort_tile < nrec ? s0 + sort_tile : nrec;
+                for (u32 i = s0 + tid; i < s1; i += BLOCK) {
+                    Key<NW> a = record_from_lds<NW, RC>(lds, lds_skip, i, W, magicW, stride_bytes, k, step, win0);
+                    *reinterpret_cast<ulonglong2*>(out + (out0 + i) * 2) = make_ulonglong2(a.w[0], a.w[NW - 1]);
+                    atomicAdd(&hist[(u32)(hash_key(a) >> 48) & 255u], 1u);
+                }
+                __syncthreads();
+                counts[((out0 + s0) / sort_tile) * 256 + tid] = hist[tid];
             }
         } else {
             for (u32 i = tid; i < nrec; i += BLOCK) {
@@ -176,6 +197,29 @@ __global__ __launch_bounds__(BLOCK) void extract_general_kernel(const uint8_t* _
     }
 }
 
+// reads a trip of the counting form of extract_fixed_kernel takes: twice the plain form's, so that 4 records a read fill a sort tile
+constexpr u32 HIST_TILE_READS = 512;
+static bool counts_shape(u32 read_len, u32 W, u32 sort_tile, const void* d_packed, const void* d_records) {
+    const u32 stride = (read_len + 3) / 4;
+    return sort_tile && sort_tile % BLOCK == 0 && (HIST_TILE_READS * W) % sort_tile == 0 && stride <= 64 && (u64)HIST_TILE_READS * W < 65536 &&
+           ((uintptr_t)d_packed % 16 == 0) && ((uintptr_t)d_records % 16 == 0);
+}
+template <bool RC>
+static int extract_fixed_counts_t(const uint8_t* d_packed, u64 n_reads, u32 read_len, u32 k, u32 step, u32 W, u64* d_records, u32* d_counts,
+                                  u32 sort_tile, hipStream_t stream) {
+    const u32 stride = (read_len + 3) / 4;
+    if (n_reads * (u64)W == 0) return KATOME_OK;
+    const u32 tile_dwords = ((HIST_TILE_READS * stride + 15) / 16) * 4;
+    const size_t lds_bytes = (tile_dwords + 8) * 4 + HIST_TILE_READS;
+    const u32 magicW = (u32)((1ull << 32) / W) + 1;
+    const u64 n_tiles = (n_reads + HIST_TILE_READS - 1) / HIST_TILE_READS;
+    const unsigned grid = (unsigned)(n_tiles < 256u * 8u ? n_tiles : 256u * 8u);
+    hipLaunchKernelGGL((extract_fixed_kernel<2, RC, (int)HIST_TILE_READS, true>), dim3(grid), dim3(BLOCK), lds_bytes, stream, d_packed, n_reads,
+                       stride, k, W, magicW, step, 0u, (const uint8_t*)nullptr, d_records, d_counts, sort_tile);
+    KCHECK_HIP(hipGetLastError());
+    return KATOME_OK;
+}
+
 // `k` is the length of the window that becomes a record; `step` the distance between consecutive window
 // starts and W the records per read (step 1, W = L-k+1: every k-mer; step = span, W = (L-k0+1)/span with
 // k = k0+span-1: the tiles of `span` consecutive k0-mers that the tiled counting path stores).
@@ -228,6 +272,22 @@ int launch_extract_fixed(uint32_t k, bool rc, const uint8_t* d_packed, uint64_t 
                            : extract_fixed_t<2, false>(d_packed, n_reads, read_len, kk, step, W, first_window, d_skip, d_records, stream);
     return rc ? extract_fixed_t<3, true>(d_packed, n_reads, read_len, kk, step, W, first_window, d_skip, d_records, stream)
               : extract_fixed_t<3, false>(d_packed, n_reads, read_len, kk, step, W, first_window, d_skip, d_records, stream);
+}
+
+// The tiles of `span` windows of fixed-length reads, none skipped, as two-word records at d_records, which is a sort-tile boundary
+// (a multiple of sort_tile records) of the array they are kept in -- and d_counts[tile][256], the first partition digit's counts of
+// the sort tiles they fill (extract_fixed_kernel, HIST).  extract_tile_counts_ok: whether this shape can be done so.
+bool extract_tile_counts_ok(uint32_t k, uint32_t read_len, uint32_t span, uint32_t sort_tile, const uint8_t* d_packed, const uint64_t* d_records) {
+    if (read_len < k || span == 0) return false;
+    const u32 W = (read_len - k + 1) / span;
+    return W && key_words_for_k(k + span - 1) == 2 && counts_shape(read_len, W, sort_tile, d_packed, d_records);
+}
+int launch_extract_tiles_counted(uint32_t k, bool rc, const uint8_t* d_packed, uint64_t n_reads, uint32_t read_len, uint32_t span,
+                                 uint64_t* d_records, uint32_t* d_counts, uint32_t sort_tile, hipStream_t stream) {
+    if (!extract_tile_counts_ok(k, read_len, span, sort_tile, d_packed, d_records)) { set_error("tile counts: not this shape"); return KATOME_E_ARG; }
+    const u32 W = (read_len - k + 1) / span;
+    return rc ? extract_fixed_counts_t<true>(d_packed, n_reads, read_len, k + span - 1, span, W, d_records, d_counts, sort_tile, stream)
+              : extract_fixed_counts_t<false>(d_packed, n_reads, read_len, k + span - 1, span, W, d_records, d_counts, sort_tile, stream);
 }
 
 // d_rec_prefix: records before each read ([n_reads + 1]); mode / span as in ArrayAddr (mode 1 records are (k+span-1)-mers)

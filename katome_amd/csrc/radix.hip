@@ -7,6 +7,7 @@
 // compress.rs:23-26) and the compress_edge labels (compress.rs:250-271; post-pass
 // pt_graph.rs:339-343).  All streaming, HBM-bound passes; no MFMA (integer keys).
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 #include "lds_order.h"
@@ -157,6 +158,58 @@ __global__ __launch_bounds__(BLOCK) void radix_hist_kernel(const u64* __restrict
     counts[(u64)blockIdx.x * RADIX + tid] = h[tid];
 }
 
+// ... the same counts from the pass's digits themselves, one byte per record at the record's index, left there by whoever placed the
+// records (radix_scatter_kernel with a next digit, lds_count_ordered_kernel): 1 byte read per record instead of the key's 8 * NW, and no hash.
+// A workgroup takes the bytes of one sort tile, VEC of them per load.  The stream is allocated in whole tiles (digit_stream_bytes),
+// so the last tile's loads stay inside it; bytes at n and beyond are not counted.
+typedef u32 u32x2_t __attribute__((ext_vector_type(2)));
+typedef u32 u32x4_t __attribute__((ext_vector_type(4)));
+template <int NW> struct DigitVec { typedef u32 T; };                   // 1280 bytes per tile: 320 words
+template <> struct DigitVec<1> { typedef u32x4_t T; };                  // 4096 bytes: one 16-byte load per thread
+template <> struct DigitVec<2> { typedef u32x2_t T; };                  // 2048 bytes: one 8-byte load per thread
+template <int NW>
+__global__ __launch_bounds__(BLOCK) void digit_hist_kernel(const uint8_t* __restrict__ digits, u64 n, u32* __restrict__ counts) {
+    typedef typename DigitVec<NW>::T V;
+    constexpr u32 SORT_TILE = SortTile<NW>::KEYS, VEC = sizeof(V), WORDS = VEC / 4, LOADS = SORT_TILE / VEC;
+    static_assert(SORT_TILE % VEC == 0, "whole loads per tile");
+    __shared__ u32 h[RADIX];
+    const u32 tid = threadIdx.x;
+    h[tid] = 0;
+    __syncthreads();
+    const u64 base = (u64)blockIdx.x * SORT_TILE;
+    const u32 cnt = (u32)((n - base) < (u64)SORT_TILE ? (n - base) : (u64)SORT_TILE);
+    const V* src = reinterpret_cast<const V*>(digits + base);
+    for (u32 l = tid; l < LOADS; l += BLOCK) {
+        const V v = __builtin_nontemporal_load(src + l);
+        u32 w[WORDS];
+        __builtin_memcpy(w, &v, VEC);
+        const u32 at = l * VEC;
+#pragma unroll
+        for (u32 q = 0; q < WORDS; ++q) {
+#pragma unroll
+            for (u32 b = 0; b < 4; ++b)
+                if (at + q * 4 + b < cnt) atomicAdd(&h[(w[q] >> (8 * b)) & 255u], 1u);
+        }
+    }
+    __syncthreads();
+    counts[(u64)blockIdx.x * RADIX + tid] = h[tid];
+}
+// Does a first pass that leaves the second one's digits pay for records of nw words?  The byte store costs the scatter about 1.2 ms
+// per 10^9 records whatever their width (as many write requests again as the keys'), the byte histogram 0.4; the key-reading
+// histogram it replaces costs 1.7 ms per 10^9 one-word records and 3 ms per 10^9 two-word ones, which are also hashed
+// (profiles/r11_histogram_reads.md: one-word records came out level, -0.2 ms per C3 build, so they stay on the keys)
+constexpr bool digit_stream_pays(int nw) { return nw >= 2; }
+bool dev_digit_stream_pays(uint32_t nw) { return digit_stream_pays((int)nw); }
+static bool order_trace() {          // KATOME_LC_TRACE: one line per ordered level (tests read them)
+    static const bool on = getenv("KATOME_LC_TRACE") != nullptr;
+    return on;
+}
+// bytes of a digit stream for n records of NW words: whole sort tiles (digit_hist_kernel loads whole vectors)
+static inline size_t digit_stream_bytes(u64 n, int nw) {
+    const u64 tile = nw == 1 ? SortTile<1>::KEYS : nw == 2 ? SortTile<2>::KEYS : SortTile<3>::KEYS;
+    return (size_t)((n + tile - 1) / tile * tile);
+}
+
 // ---- pass 2a: per chunk of workgroups, per digit: sum; counts become exclusive prefixes inside
 // the chunk (u32), chunk_sum[chunk][digit] holds the chunk totals ---------------------------------
 __global__ __launch_bounds__(BLOCK) void radix_chunk_kernel(u32* __restrict__ counts, u64 nblocks, u64* __restrict__ chunk_sum, u32 chunk_blocks) {
@@ -221,11 +274,22 @@ __global__ __launch_bounds__(BLOCK) void radix_offsets_kernel(u64* __restrict__ 
 // counter instead of the eight ballots of the match step.  Built to close the gap to the pass's memory-pattern ceiling
 // (profiles/r04_scatter_ceiling.txt: 0.80 of it) and measured at C3 on one box, A/B/A/B: 203.8 / 205.8 / 207.3 / 205.1 ms per build --
 // nothing: the LDS atomics cost what the ballots cost.  Kept behind KATOME_UNSTABLE_FIRST=1, off by default.
-template <int NW, bool HAS_VAL, class Digit, bool STABLE = true>
+// NEXT (round 11): the pass after this one partitions the same records by another digit, nx(key).  The output loop holds the key it
+// stores, so it leaves that digit, one byte, at the key's index of next_out, and the next pass counts its tiles from those bytes
+// (digit_hist_kernel) instead of reading the keys again.  NoNextDigit: a last pass -- nothing is computed or stored, the code is the
+// one the kernel had before.
+struct NoNextDigit {};
+template <class Next> struct NextDigitOut {
+    Next nx; uint8_t* out;
+    __device__ __forceinline__ void put(u64 at, u32 d) const { out[at] = (uint8_t)d; }
+};
+template <> struct NextDigitOut<NoNextDigit> {};
+template <int NW, bool HAS_VAL, class Digit, bool STABLE = true, class Next = NoNextDigit>
 __global__ __launch_bounds__(BLOCK, KATOME_SORT_WAVES) void radix_scatter_kernel(const u64* __restrict__ keys_in, const u32* __restrict__ vals_in,
                                                                u64 n, Digit dg, const u32* __restrict__ rel,
                                                                const u64* __restrict__ chunk_off, u64* __restrict__ keys_out,
-                                                               u32* __restrict__ vals_out, u32 chunk_blocks, u32 xcd_tiles) {
+                                                               u32* __restrict__ vals_out, u32 chunk_blocks, u32 xcd_tiles, NextDigitOut<Next> next) {
+    constexpr bool NEXT = !std::is_same<Next, NoNextDigit>::value;
     constexpr int SORT_ITEMS = SortTile<NW>::ITEMS, SORT_TILE = SortTile<NW>::KEYS;
     extern __shared__ u64 smem[];
     u64* skeys = smem;                                            // [SORT_TILE * NW]; reused for the values afterwards
@@ -337,6 +401,7 @@ __global__ __launch_bounds__(BLOCK, KATOME_SORT_WAVES) void radix_scatter_kernel
             const u32 d = dg(k);
             dout[j] = d;
             store_key<NW>(keys_out, gbase[d] + (i - dstart[d]), k);
+            if constexpr (NEXT) next.put(gbase[d] + (i - dstart[d]), next.nx(k));       // (a hash digit: another byte of the hash dg took)
         }
     }
     if (HAS_VAL) {
@@ -390,31 +455,39 @@ static bool unstable_first() {
     static const bool on = getenv("KATOME_UNSTABLE_FIRST") && atoi(getenv("KATOME_UNSTABLE_FIRST")) != 0;      // (off: measured, no gain -- see the kernel)
     return on;
 }
-template <int NW, bool HAS_VAL, class Digit, bool STABLE = true>
+// digits_in: this pass's digit of every record, one byte each at the record's index (see digit_hist_kernel) -- the per-tile counts are
+// then made from them and the keys are read by the scatter alone.  nx / digits_out: the scatter also leaves the NEXT pass's digits.
+template <int NW, bool HAS_VAL, class Digit, bool STABLE = true, class Next = NoNextDigit>
 static int radix_pass(const u64* kin, const u32* vin, u64 n, Digit dg, u64* kout, u32* vout, PassBuffers& pb, hipStream_t stream,
-                      bool have_counts = false) {
+                      bool have_counts = false, const uint8_t* digits_in = nullptr, Next nx = Next{}, uint8_t* digits_out = nullptr) {
     if (pb.nblocks > 0x7fffffffull) { set_error("radix pass: %llu keys exceed the grid limit", (unsigned long long)n); return KATOME_E_ARG; }
+    if (!std::is_same<Next, NoNextDigit>::value && !digits_out) { set_error("radix pass: a next digit and nowhere to write it"); return KATOME_E_ARG; }
     dim3 block(BLOCK);
     u32* const counts = have_counts && pb.first ? pb.first : pb.counts.as<u32>();
     if (!have_counts) {          // (have_counts: whoever wrote the records counted this pass's digits per tile as it went -- pb.first, or pb.counts, holds them)
         KernelScope ks(DigitTimers<Digit>::HIST, stream, n);
-        hipLaunchKernelGGL((radix_hist_kernel<NW, Digit>), dim3((unsigned)pb.nblocks), block, 0, stream, kin, n, dg, counts);
+        if (digits_in) hipLaunchKernelGGL((digit_hist_kernel<NW>), dim3((unsigned)pb.nblocks), block, 0, stream, digits_in, n, counts);
+        else hipLaunchKernelGGL((radix_hist_kernel<NW, Digit>), dim3((unsigned)pb.nblocks), block, 0, stream, kin, n, dg, counts);
     }
     {
         KernelScope ks(K_PASS_OFFSETS, stream, n);
         hipLaunchKernelGGL(radix_chunk_kernel, dim3((unsigned)pb.nchunks), block, 0, stream, counts, pb.nblocks, pb.chunk.as<u64>(), pb.chunk_blocks);
         hipLaunchKernelGGL(radix_offsets_kernel, dim3(1), block, 0, stream, pb.chunk.as<u64>(), pb.nchunks, pb.totals.as<u64>());
     }
+    constexpr bool NEXT = !std::is_same<Next, NoNextDigit>::value;
+    static_assert(!NEXT || STABLE, "the next digit is written by the stable scatter");
     const size_t lds = (size_t)SortTile<NW>::KEYS * NW * 8;
     if (lds > (64u << 10)) {          // three-word records: 96 KiB of the CU's 160 KiB
-        KCHECK_HIP(hipFuncSetAttribute((const void*)radix_scatter_kernel<NW, HAS_VAL, Digit, STABLE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        KCHECK_HIP(hipFuncSetAttribute((const void*)radix_scatter_kernel<NW, HAS_VAL, Digit, STABLE, Next>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
     {
         static const bool xcd_aware = !getenv("KATOME_XCD_TILES") || atoi(getenv("KATOME_XCD_TILES")) != 0;       // (0: workgroup i takes tile i)
         const u32 xcd_tiles = xcd_aware && pb.nblocks >= 64 ? (u32)((pb.nblocks + 7) / 8) : 0u;
         KernelScope ks((!HAS_VAL && DigitTimers<Digit>::SCATTER == K_SORT_SCATTER) ? (int)K_SORT_SCATTER_KEYS : (int)DigitTimers<Digit>::SCATTER, stream, n);
-        hipLaunchKernelGGL((radix_scatter_kernel<NW, HAS_VAL, Digit, STABLE>), dim3(xcd_tiles ? xcd_tiles * 8u : (unsigned)pb.nblocks), block, lds, stream, kin, vin, n, dg,
-                           counts, pb.chunk.as<u64>(), kout, vout, pb.chunk_blocks, xcd_tiles);
+        NextDigitOut<Next> next;
+        if constexpr (NEXT) { next.nx = nx; next.out = digits_out; }
+        hipLaunchKernelGGL((radix_scatter_kernel<NW, HAS_VAL, Digit, STABLE, Next>), dim3(xcd_tiles ? xcd_tiles * 8u : (unsigned)pb.nblocks), block, lds, stream, kin, vin, n, dg,
+                           counts, pb.chunk.as<u64>(), kout, vout, pb.chunk_blocks, xcd_tiles, next);
     }
     KCHECK_HIP(hipGetLastError());
     return KATOME_OK;
@@ -837,11 +910,28 @@ static int region_order_t(const u64* d_in, const u32* w_in, u64 n, int passes, u
     // (first_counts: the first pass's digit counts per tile, [ceil(n / dev_sort_tile_keys)][256], made while the records were written;
     // the pass works in that buffer and leaves prefixes in it)
     pb.first = first_counts;
+    DevBuf digits(stream);
     const u64* kin = d_in; const u32* win = w_in;
     u64* kdst[2] = {ka, kb}; u32* wdst[2] = {wa, wb};
     for (int p = 0; p < passes; ++p) {
         HashDigit<NW> dg{(u32)(64 - 8 * (passes - p))};     // least significant region byte first
         const bool have = p == 0 && first_counts != nullptr;
+        if (order_trace() && passes == 2 && p == 0)
+            fprintf(stderr, "[order] by hash: %llu records of %d words, first pass counted from %s, second from %s\n", (unsigned long long)n, NW,
+                    have ? "its writer's counts" : "the keys", digit_stream_pays(NW) && !unstable_first() ? "the digit stream" : "the keys");
+        if constexpr (digit_stream_pays(NW)) if (passes == 2 && !unstable_first()) {          // (the first pass leaves the second one's digits: no second read of the keys, no second hash)
+            if (p == 0) {
+                KCHECK(digits.alloc(digit_stream_bytes(n, NW)));
+                const HashDigit<NW> nx{56u};
+                if (w_in) KCHECK((radix_pass<NW, true, HashDigit<NW>, true, HashDigit<NW>>(kin, win, n, dg, kdst[0], wdst[0], pb, stream, have, nullptr, nx, digits.as<uint8_t>())));
+                else      KCHECK((radix_pass<NW, false, HashDigit<NW>, true, HashDigit<NW>>(kin, nullptr, n, dg, kdst[0], nullptr, pb, stream, have, nullptr, nx, digits.as<uint8_t>())));
+            } else {
+                if (w_in) KCHECK((radix_pass<NW, true>(kin, win, n, dg, kdst[1], wdst[1], pb, stream, false, digits.as<uint8_t>())));
+                else      KCHECK((radix_pass<NW, false>(kin, nullptr, n, dg, kdst[1], nullptr, pb, stream, false, digits.as<uint8_t>())));
+            }
+            kin = kdst[p & 1]; win = w_in ? wdst[p & 1] : nullptr;
+            continue;
+        }
         if (p == 0 && unstable_first()) {          // (nothing is ordered yet: the first pass need not be stable)
             if (w_in) KCHECK((radix_pass<NW, true, HashDigit<NW>, false>(kin, win, n, dg, kdst[p & 1], wdst[p & 1], pb, stream, have)));
             else      KCHECK((radix_pass<NW, false, HashDigit<NW>, false>(kin, nullptr, n, dg, kdst[p & 1], nullptr, pb, stream, have)));
@@ -865,12 +955,17 @@ int dev_hash_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint3
 // one-word (k-mer, count) records ordered by their leading 16 key bits (bits 2k - 16 .. 2k - 1): two stable 8-bit passes, the
 // result where *k_out / *w_out point (first_counts: the first pass's digit counts per tile, made while the records were written)
 int dev_key_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t k, uint64_t* ka, uint64_t* kb, uint32_t* wa, uint32_t* wb,
-                  const uint64_t** k_out, const uint32_t** w_out, hipStream_t stream, uint32_t* first_counts) {
+                  const uint64_t** k_out, const uint32_t** w_out, hipStream_t stream, uint32_t* first_counts, const uint8_t* first_digits) {
     if (k < 8 || 2 * k > 64) { set_error("key order: k = %u", k); return KATOME_E_ARG; }
     PassBuffers pb;
     KCHECK(pb.init(n, 1, stream));
     pb.first = first_counts;
-    KCHECK((radix_pass<1, true>(d_in, w_in, n, LevelKeyDigit{2 * k - 16}, ka, wa, pb, stream, first_counts != nullptr)));
+    // (one-word records: digit_stream_pays says no, so the second pass counts from the keys; the first from first_counts, else
+    // first_digits, else the keys)
+    if (order_trace())
+        fprintf(stderr, "[order] by key: %llu records of 1 words, first pass counted from %s, second from the keys\n", (unsigned long long)n,
+                first_counts ? "its writer's counts" : first_digits ? "its writer's digits" : "the keys");
+    KCHECK((radix_pass<1, true>(d_in, w_in, n, LevelKeyDigit{2 * k - 16}, ka, wa, pb, stream, first_counts != nullptr, first_digits)));
     KCHECK((radix_pass<1, true>(ka, wa, n, LevelKeyDigit{2 * k - 8}, kb, wb, pb, stream)));
     *k_out = kb; *w_out = wb;
     return KATOME_OK;
@@ -1129,6 +1224,7 @@ int dev_key_group_max(const uint64_t* d_index, uint64_t* d_out, hipStream_t stre
 
 // records per tile of a partition pass over records of nw words, and the digit of dev_hash_order's first pass (for a kernel that
 // writes such records and counts that pass's digits per tile as it goes: table.hip, list_to_records_kernel)
+size_t dev_digit_stream_bytes(uint64_t n, uint32_t nw) { return digit_stream_bytes(n, (int)nw); }
 uint32_t dev_sort_tile_keys(uint32_t nw) { return nw == 1 ? SortTile<1>::KEYS : nw == 2 ? SortTile<2>::KEYS : SortTile<3>::KEYS; }
 // records of nwk + 1 words (k-mer, tag) with their counts, ordered by the top 16 bits of the K-MER's hash (two stable passes)
 template <int NW>

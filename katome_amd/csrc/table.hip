@@ -1020,7 +1020,7 @@ static_assert(LC_THREADS == LDS_ORDER_THREADS, "the read-out orders with lds_ord
 template <bool RC>
 __global__ __launch_bounds__(LC_THREADS) void lds_count_ordered_kernel(const u64* keys, const u32* wts, const u64* __restrict__ index, u32 k,
                                                                         u32 min_weight, u64* s1_key, u32* s1_w, u32* group_count, u64* s2_key,
-                                                                        u32* s2_w, u64 s2_cap, unsigned long long* cursor,
+                                                                        u32* s2_w, uint8_t* s2_digit, u64 s2_cap, unsigned long long* cursor,
                                                                         unsigned long long* distinct, u32* err, u32 probe_limit) {
     extern __shared__ unsigned long long lc_mem[];
     unsigned long long* slot = lc_mem;                                   // [LP_SLOTS]: remainder << 16 | count; then the kept ones in key order
@@ -1097,7 +1097,11 @@ __global__ __launch_bounds__(LC_THREADS) void lds_count_ordered_kernel(const u64
             Key<1> x; x.w[0] = ((u64)g << rem_bits) | (e >> 16);
             const u32 c = (u32)e & 0xFFFFu;
             if (lo + i < hi) { s1_key[lo + i] = x.w[0]; s1_w[lo + i] = c; }
-            if (RC && base_sh + i < s2_cap) { s2_key[base_sh + i] = revcomp(x, k).w[0]; s2_w[base_sh + i] = c; }
+            if (RC && base_sh + i < s2_cap) {
+                // (beside the key, the digit of S2's first partition pass -- dev_key_order, bits 2k - 16 .. 2k - 9 --, which then reads no key to count)
+                const u64 r = revcomp(x, k).w[0];
+                s2_key[base_sh + i] = r; s2_w[base_sh + i] = c; s2_digit[base_sh + i] = (uint8_t)(r >> rem_bits);
+            }
         }
         __syncthreads();
         LC_PHASE(15);
@@ -2397,7 +2401,10 @@ static int ordered_count(DevBuf& keys, DevBuf& weights, uint64_t n, uint32_t k, 
     KCHECK_HIP(hipMemsetAsync(hs.group_count.p, 0, (1ull << 16) * 4, stream));
     KCHECK(hs.s1_key.alloc((n + 1) * 8, stream)); KCHECK(hs.s1_w.alloc((n + 1) * 4, stream));
     const u64 s2_cap = rc ? n + 1 : 0;          // (a reverse complement per distinct key: no more than the records)
-    if (rc) { KCHECK(hs.s2_key.alloc(s2_cap * 8, stream)); KCHECK(hs.s2_w.alloc(s2_cap * 4, stream)); }
+    if (rc) {
+        KCHECK(hs.s2_key.alloc(s2_cap * 8, stream)); KCHECK(hs.s2_w.alloc(s2_cap * 4, stream));
+        KCHECK(hs.s2_digit.alloc(dev_digit_stream_bytes(s2_cap, 1), stream));
+    }
     DevBuf aux(stream);
     KCHECK(aux.alloc(64));
     KCHECK_HIP(hipMemsetAsync(aux.p, 0, 64, stream));
@@ -2409,7 +2416,7 @@ static int ordered_count(DevBuf& keys, DevBuf& weights, uint64_t n, uint32_t k, 
             KCHECK_HIP(hipFuncSetAttribute((const void*)lds_count_ordered_kernel<RCV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
             KernelScope ks(K_LDS_COUNT, stream, n);                                                                                       \
             hipLaunchKernelGGL((lds_count_ordered_kernel<RCV>), dim3(256u), dim3(LC_THREADS), lds, stream, ko, wo, hs.group_first.as<u64>(), k, min_weight, \
-                               hs.s1_key.as<u64>(), hs.s1_w.as<u32>(), hs.group_count.as<u32>(), hs.s2_key.as<u64>(), hs.s2_w.as<u32>(), s2_cap,   \
+                               hs.s1_key.as<u64>(), hs.s1_w.as<u32>(), hs.group_count.as<u32>(), hs.s2_key.as<u64>(), hs.s2_w.as<u32>(), hs.s2_digit.as<uint8_t>(), s2_cap,   \
                                cursor, cursor + 1, reinterpret_cast<u32*>(cursor + 2), std::min<u32>(lc_probe_limit(), LP_SLOTS));              \
         } while (0)
         if (rc) KATOME_LO_LAUNCH(true); else KATOME_LO_LAUNCH(false);
@@ -2462,8 +2469,9 @@ int half_sort_finish(HalfSort& hs, DevBuf& edge_key, DevBuf& edge_weight, hipStr
             KCHECK(tk.alloc((hs.n_s2 + 1) * 8)); KCHECK(tw.alloc((hs.n_s2 + 1) * 4));
             const u64* ko = nullptr; const u32* wo = nullptr;
             KCHECK(dev_key_order(hs.s2_key.as<u64>(), hs.s2_w.as<u32>(), hs.n_s2, k, tk.as<u64>(), hs.s2_key.as<u64>(), tw.as<u32>(),
-                                 hs.s2_w.as<u32>(), &ko, &wo, stream));
+                                 hs.s2_w.as<u32>(), &ko, &wo, stream, nullptr, hs.s2_digit.as<uint8_t>()));
         }
+        hs.s2_digit.release();
         KCHECK(dev_key_group_index(hs.s2_key.as<u64>(), hs.n_s2, 2 * k - 16, b_first.as<u64>(), stream));
         KCHECK(dev_key_group_max(b_first.as<u64>(), a_off.as<u64>(), stream));      // (a_off: scratch until the scan below)
         uint64_t largest = 0;
