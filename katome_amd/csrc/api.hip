@@ -402,7 +402,7 @@ int bfc_set_edges(katome_builder* b, const uint64_t* d_fwd, const uint32_t* d_w,
 }
 
 int sorted_count_mode() {
-    static const int mode = getenv("KATOME_SORTED_COUNT") ? atoi(getenv("KATOME_SORTED_COUNT")) : 1;
+    static const int mode = env_int("KATOME_SORTED_COUNT", 1);
     return mode;
 }
 // is counting n records by sorting worth its extra launches?  (KATOME_SORTED_COUNT=2: however few -- tests)
@@ -460,7 +460,7 @@ bool sorted_fail(const char* level) {
 // (two-word tiles of one-word k-mers, either numbering; anything else takes the table) --, 1 the big tiles in their table and only
 // the mid tiles by sorting, out of that table; 0 both tile levels in tables.  C3 by packed key: 200 / 210 / 239 ms per build.
 int sorted_tiles_mode() {
-    static const int mode = getenv("KATOME_SORTED_TILES") ? atoi(getenv("KATOME_SORTED_TILES")) : 2;
+    static const int mode = env_int("KATOME_SORTED_TILES", 2);
     return mode;
 }
 
@@ -469,7 +469,7 @@ int sorted_tiles_mode() {
 // tiles of two-word k-mers); in the reference's numbering two-word tiles of one-word k-mers (the tagged kernels' shapes).
 // KATOME_SORTED_WIDE=0: the round-3 rule (A/B against the tables).
 bool tile_recs_shape(uint32_t nwt, uint32_t nw, bool first_seen) {
-    static const bool wide = !getenv("KATOME_SORTED_WIDE") || atoi(getenv("KATOME_SORTED_WIDE")) != 0;
+    static const bool wide = env_flag("KATOME_SORTED_WIDE", true);
     if (first_seen || !wide) return nwt == 2 && nw == 1;
     return (nwt == 2 || nwt == 3) && nw <= 2 && nw <= nwt;
 }
@@ -610,7 +610,7 @@ static bool level_fits(uint64_t n_records, uint32_t key_words, bool oriented, co
 // list moves into a buffer of its own size instead, as it did before the allocator could trim
 static int shrink_to_fit(DevBuf& buf, size_t used, hipStream_t stream) {
     if (!buf.p || buf.bytes < (1ull << 30) || used * 2 > buf.bytes) return KATOME_OK;
-    static const bool in_place = !getenv("KATOME_TRIM_IN_PLACE") || atoi(getenv("KATOME_TRIM_IN_PLACE")) != 0;
+    static const bool in_place = env_flag("KATOME_TRIM_IN_PLACE", true);
     if (in_place) {
         const size_t before = buf.bytes;
         if (buf.trim(used + 64) && getenv("KATOME_LC_TRACE"))
@@ -635,7 +635,7 @@ static int shrink_to_fit(DevBuf& buf, size_t used, hipStream_t stream) {
 // KATOME_LEVEL_PARTS=0: never
 static int kmer_records_in_parts(katome_builder* b, const uint64_t* lk, const uint32_t* lw, uint64_t n_last, uint32_t last_bases, uint32_t last_span,
                                  DevBuf& keys, DevBuf& weights, uint64_t* n_records, uint64_t extra_room, hipStream_t stream) {
-    static const bool on = !getenv("KATOME_LEVEL_PARTS") || atoi(getenv("KATOME_LEVEL_PARTS")) != 0;
+    static const bool on = env_flag("KATOME_LEVEL_PARTS", true);
     if (!on) return KATOME_E_UNSUPPORTED;
     const uint32_t nw = b->nw, k = b->s.k, nwl = (uint32_t)key_words_for_k(last_bases);
     const uint64_t pair = 8ull * nw + 4, total = n_last * last_span, have = level_budget();
@@ -770,11 +770,11 @@ int tile_recs_to_kmer_records(katome_builder* b, DevBuf& keys, DevBuf& weights, 
     return table_list_to_records(lk, lw, n_last, last_bases, k, last_span, 1, b->rc, keys, weights, n_records, stream, extra_room, first_counts, rep);
 }
 
-// The k-mer level counted in order (table.hip, lds_count_ordered_kernel): half of the edges leave the count sorted, the edge sort takes
+// The k-mer level counted in order (lds_count.hip, lds_count_ordered_kernel): half of the edges leave the count sorted, the edge sort takes
 // only the reverse complements and one merge (half_sort_finish).  Where lds_count_packed_kernel would run: one-word k-mers of odd k
 // (k >= 9: 16 key bits name the group) or one strand, default numbering, no owner split.  KATOME_EDGE_HALF_SORT=0: the full edge sort
 static bool half_sort_route(const katome_builder* b) {
-    static const bool on = !getenv("KATOME_EDGE_HALF_SORT") || atoi(getenv("KATOME_EDGE_HALF_SORT")) != 0;
+    static const bool on = env_flag("KATOME_EDGE_HALF_SORT", true);
     const uint32_t k = b->s.k;
     return on && b->nw == 1 && !b->first_seen && k >= 9 && ((k & 1) || !b->rc);
 }
@@ -824,7 +824,7 @@ int katome_dev_insert_weighted(katome_builder* b, const uint64_t* d_records, con
         KCHECK(keep_rest(b, d_records, n_records, &kept, stream));
         if (kept) return KATOME_OK;
     }
-    // first-seen order, reads of one length: the windows after the batch's tiles wait as tagged records (table.hip, seen_pack)
+    // first-seen order, reads of one length: the windows after the batch's tiles wait as tagged records (slot_bits.h, seen_pack)
     if (b->first_seen && b->rem_pending && !d_weights && !b->var_prefix && !b->var_seq_base && (b->tiles_ready || b->tile_recs_n) && !b->table_ready && !b->rest_closed &&
         b->nw <= 2 && sorted_count_mode() && b->seen_read_len >= b->s.k && 2ull * (b->seen_read_len - b->s.k + 1) <= 0xFFFFu &&
         b->last_batch_read0 + b->last_batch_reads < (1ull << 32) && n_records == b->last_batch_reads * b->rem_per_read) {
@@ -936,10 +936,9 @@ int katome_dev_count_tiles(katome_builder* b, const uint8_t* d_packed, uint64_t 
             // The extraction knows the index of every record it writes, so where this batch starts on a sort-tile boundary of the kept
             // array -- and every batch before it did -- it also leaves the first partition pass's digit counts of the sort tiles it
             // fills (KATOME_FUSED_HIST=0: never; the pass counts for itself, as it does in every other case)
-            static const bool fused_hist = !getenv("KATOME_FUSED_HIST") || atoi(getenv("KATOME_FUSED_HIST")) != 0;
             const uint32_t sort_tile = dev_sort_tile_keys(nwt);
             u64* const dst = b->tile_recs.as<u64>() + b->tile_recs_n * nwt;
-            const bool counted = fused_hist && (b->tile_recs_n == 0 || b->tile_recs_hist_ok) && b->tile_recs_n % sort_tile == 0 &&
+            const bool counted = fused_hist_on() && (b->tile_recs_n == 0 || b->tile_recs_hist_ok) && b->tile_recs_n % sort_tile == 0 &&
                                  extract_tile_counts_ok(b->s.k, read_len, span, sort_tile, d_packed, dst) &&
                                  reserve_tile_hist(b, std::max<uint64_t>(b->tile_recs_n + n, b->tile_recs_cap), sort_tile, b->tile_recs_n != 0, stream);
             if (getenv("KATOME_LC_TRACE"))
@@ -1079,7 +1078,7 @@ static int append_rest(katome_builder* b, DevBuf& keys, DevBuf& weights, uint64_
     return KATOME_OK;
 }
 
-// The last level counted by sorting instead of in a table (table.hip, lds_count_kernel / lds_count_wide_kernel): k <= 63, by packed
+// The last level counted by sorting instead of in a table (lds_count.hip, lds_count_kernel / lds_count_wide_kernel): k <= 63, by packed
 // key, nothing in the k-mer table yet (left-over windows were kept aside).  With the tiles kept as records (katome_dev_insert_tiles)
 // the tile levels above it are counted the same way: every level is "records -> two hash passes -> counted in LDS -> a compact list
 // of distinct keys with their counts", the next level's records are cut out of that list (table.hip, list_to_records_kernel).
@@ -1268,7 +1267,7 @@ static int seen_edges_from_tile_recs(katome_builder* b, DevBuf& raw_seq, bool* c
     return builder_insert(b, b->tiles, b->tiles_ready, nwt, b->s.table_slots_hint / 4, keys.as<u64>(), c1.as<u32>(), n1, &origin, PH_INSERT_TILES, stream);
 }
 
-// The k-mers of a first-seen-order build counted by sorting out of the tile table (table.hip, lds_count_seen_kernel): reads of one
+// The k-mers of a first-seen-order build counted by sorting out of the tile table (lds_count.hip, lds_count_seen_kernel): reads of one
 // length whose windows are whole tiles, so that a record's two sequence numbers pack into one word.
 // on fallback: the tiles are in their table (mid tiles in b->tiles2 if it made them); n_edges == 0
 static int seen_edges_from_tile_table(katome_builder* b, DevBuf& raw_seq, bool* counted, hipStream_t stream) {
@@ -1377,7 +1376,7 @@ int katome_dev_finalize(katome_builder* b, katome_dev_graph* out, void* stream_)
     // default numbering: the edges stay where they are, so the pass that writes their source ids writes their labels too (radix.hip
     // src_write_kernel) and no kernel reads the keys again for them.  KATOME_LABELS_IN_IDS=0: dev_labels afterwards, as in first-seen
     // order, whose edges are renumbered first
-    static const bool labels_in_ids = !getenv("KATOME_LABELS_IN_IDS") || atoi(getenv("KATOME_LABELS_IN_IDS")) != 0;
+    static const bool labels_in_ids = env_flag("KATOME_LABELS_IN_IDS", true);
     const bool labels_early = labels_in_ids && !b->first_seen && E;
     if (labels_early) KCHECK(b->edge_label.alloc((E + 1) * (size_t)stride + 16, stream));
     {

@@ -42,7 +42,7 @@ struct katome_builder {
     uint32_t var_mode = 0, var_span = 1;       // 0 every window, 1 whole tiles, 2 the windows after the last whole tile
     DevBuf edge_seq;                   // sequence number of each edge's first insertion, aligned with edge_key
     // by-packed-key builds: the windows left over after a batch's tiles wait here (records of weight 1), so that the last level can
-    // be counted by sorting (table.hip, records_to_edges_sorted) together with the tiles' k-mers; any other consumer of the k-mer
+    // be counted by sorting (lds_count.hip, records_to_edges_sorted) together with the tiles' k-mers; any other consumer of the k-mer
     // table flushes them into it first (flush_rest)
     // by-packed-key builds with two-word tiles and one-word k-mers: the tiles themselves are kept as records too and counted by
     // sorting when the edges are asked for (api.hip, count_tiles_sorted) -- no tile table, no device-scope atomics at any level

@@ -5,9 +5,11 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/katome_gpu.h"
+#include "env.h"
 #include "kmer_bits.h"
 
 namespace katome {
@@ -175,11 +177,23 @@ inline int check_k(uint32_t k) {
 }
 
 constexpr int BLOCK = 256;
+#ifdef __HIPCC__
+__device__ __forceinline__ u32 wave_sum(u32 v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+#endif
 inline unsigned grid_for(uint64_t work_items, unsigned per_block, unsigned cap = 256u * 16u) {
     uint64_t g = (work_items + per_block - 1) / per_block;
     if (g < 1) g = 1;
     return (unsigned)(g > cap ? cap : g);
 }
+
+// a run-time flag as a template argument: f gets it as a std::integral_constant (kernel<decltype(flag)::value>) and returns a status
+template <bool B> using BoolC = std::integral_constant<bool, B>;
+template <int I> using IntC = std::integral_constant<int, I>;
+template <class F> int with_bool(bool b, F f) { return b ? f(BoolC<true>{}) : f(BoolC<false>{}); }
 
 // ---- launchers implemented in the .hip files (all asynchronous on `stream`) -----------------
 int launch_extract_fixed(uint32_t k, bool rc, const uint8_t* d_packed, uint64_t n_reads, uint32_t read_len,
@@ -225,6 +239,8 @@ int dev_region_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uin
 int dev_hash_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t nw, uint64_t* ka, uint64_t* kb, uint32_t* wa, uint32_t* wb,
                    const uint64_t** k_out, const uint32_t** w_out, uint32_t* group_bits, hipStream_t stream, uint32_t* first_counts = nullptr);
 uint32_t dev_sort_tile_keys(uint32_t nw);
+// KATOME_FUSED_HIST=0: whoever writes a level's records does not count the first pass's digits per tile; the pass counts them itself
+inline bool fused_hist_on() { static const bool on = env_flag("KATOME_FUSED_HIST", true); return on; }
 // one-word records by their leading 16 key bits (k = 8..32): two stable passes; the result where *k_out / *w_out point (kb / wb)
 // (first_digits: the first pass's digit of every record -- bits 2k - 16 .. 2k - 9 of its key --, one byte each at the record's index in
 // a buffer of dev_digit_stream_bytes(n, 1) bytes, left by whoever wrote the records; the pass then counts from them, not the keys)
@@ -342,7 +358,7 @@ int dev_shrink_exact(const ShrinkInput& g, const uint32_t* edge_age, ShrinkOutpu
 
 constexpr int KATOME_MAX_RANKS = 16;      // ranks of a sharded build (an MI355X node has 8 GPUs)
 
-// table.hip
+// table.hip (the table in HBM) and lds_count.hip (a level counted by sorting)
 struct Table {
     DevBuf slots;          // NW=1: {u64 key|OCC, u32 count, u32 pad}; NW=2: {u64 hi|flags, u64 lo, u32 count, u32 pad[3]}
     DevBuf counter;        // u64 occupied
@@ -400,7 +416,7 @@ int table_tiles_to_records_fast(Table& tiles, uint32_t k, uint32_t span, bool rc
 // (d_extra / n_extra: tagged records to count with them -- the windows left over after the tiles, table_rest_to_tagged)
 int tiles_to_edges_sorted_seen(Table& tiles, uint32_t k, uint32_t span, bool rc, uint64_t seq_per_read, DevBuf& edge_key, DevBuf& seq_weight,
                                uint64_t* n_edges, uint64_t* n_distinct, hipStream_t stream, const uint64_t* d_extra = nullptr, uint64_t n_extra = 0);
-// appends the valid records of d_rec behind *d_cursor in d_out (tagged: as records of nw + 1 words, see seen_pack in table.hip)
+// appends the valid records of d_rec behind *d_cursor in d_out (tagged: as records of nw + 1 words, see seen_pack in slot_bits.h)
 int table_keep_rest(const uint64_t* d_rec, uint64_t n, uint32_t nw, bool tagged, uint64_t read0, uint32_t per_read, uint32_t win0, uint32_t seq_per_read,
                     uint64_t* d_out, uint64_t* d_cursor, hipStream_t stream, uint32_t win_stride = 1, uint32_t span = 1);
 int tagged_records_sorted(DevBuf& recs, DevBuf& wts, uint64_t n, uint32_t k, bool rc, uint64_t seq_per_read, bool list, DevBuf& out_keys,

@@ -313,7 +313,7 @@ int route_and_insert_var(katome_dist_builder* d, const u64* part, const u64* pai
 // operation of the communicator goes there for the duration), and added to the table on the build's stream again -- while
 // slice j + 1 is already on the links.  Two sets of buffers; events order the two streams (a buffer is written again only
 // behind the wait for the exchange or the insertion that read it, both of which the build's stream has passed by then).
-// what arrived, kept as records instead of being counted in a table (the last level counted by sorting, table.hip)
+// what arrived, kept as records instead of being counted in a table (the last level counted by sorting, lds_count.hip)
 struct Collected {
     DevBuf keys, weights;
     uint64_t n = 0, cap = 0;
@@ -1180,7 +1180,7 @@ int katome_dist_finalize(katome_dist_builder* d, katome_dist_graph* out, void* s
         bool split_used = false;
         // (owner split: grouped by the hash that names the owner, every group's keys written into its owner's stretch: no partition pass
         // before the exchange; KATOME_DIST_OWNER_SPLIT=0: by the whole k-mer's hash, then route_weighted's partition)
-        static const bool owner_split_on = !getenv("KATOME_DIST_OWNER_SPLIT") || atoi(getenv("KATOME_DIST_OWNER_SPLIT")) != 0;
+        static const bool owner_split_on = env_flag("KATOME_DIST_OWNER_SPLIT", true);
         if (b->tile_recs_n && (!may_collect(d) || !sorting_pays(b->tile_recs_n * b->span))) KCHECK(flush_tile_recs(b, stream));
         if (b->tile_recs_n) {
             // the tiles kept as records: every level by sorting, down to this rank's distinct k-mers

@@ -54,7 +54,7 @@ KD u64 mix64(u64 x) {
     return x;
 }
 // mix64 is a bijection of the 64-bit words (murmur3's finalizer): a xor-shift by 33 undoes itself, the multipliers have inverses mod 2^64.
-// table.hip's lds_count_packed_kernel stores a one-word k-mer as the low bits of its hash and gets it back with this
+// lds_count.hip's lds_count_packed_kernel stores a one-word k-mer as the low bits of its hash and gets it back with this
 // (tests/test_kmer_bits_host.py: unmix64(mix64(x)) == x)
 KD u64 unmix64(u64 x) {
     x ^= x >> 33; x *= 0x9cb4b2f8129337dbull;
@@ -198,7 +198,7 @@ template <int NW> KD Key<NW> canonical(const Key<NW>& a, u32 k) {
 // Odd k only: the orientation of a one-word k-mer whose middle base has a 0 in the high bit of its 2-bit code.  The middle base
 // is its own mirror under reverse complement and complement is bitwise NOT, so exactly one of x and rc(x) qualifies and
 // rep(rc x) = rep(x).  Unlike canonical(), which piles its leading bases at the low end, rep's leading bases are as uniform as the
-// input's: key ranges cut on them are as even as hash ranges (the k-mer level's ordered count, table.hip).
+// input's: key ranges cut on them are as even as hash ranges (the k-mer level's ordered count, lds_count.hip).
 KD Key<1> rep_orientation(const Key<1>& a, u32 k) { return ((a.w[0] >> k) & 1ull) ? revcomp(a, k) : a; }
 // same, telling whether the reverse complement was taken
 template <int NW> KD Key<NW> canonical_flip(const Key<NW>& a, u32 k, bool& flipped) {
@@ -220,7 +220,7 @@ template <int NW> KD Key<NW> canonical_flip(const Key<NW>& a, u32 k, bool& flipp
 template <int NW> KD u64 whole_key_owner(const Key<NW>& a, u64 n) { return hash_to_range(mix64(hash_key(a) ^ 0x5851F42D4C957F2Dull), n); }
 // hash of a record's core (the `core` bases `shift` bits above its low end, either strand); the record's owner is a function of
 // the top CORE_GROUP_BITS of it only, so that records ordered by those bits are ordered by owner as well (a rank's own distinct
-// k-mers leave its LDS count already grouped by owner: table.hip, records_to_edges_sorted with an OwnerSplit)
+// k-mers leave its LDS count already grouped by owner: lds_count.hip, records_to_edges_sorted with an OwnerSplit)
 constexpr u32 CORE_GROUP_BITS = 16;
 template <int NW> KD u64 core_hash(const Key<NW>& a, u32 shift, u32 core) {
     const Key<NW> m = key_low_bits(key_shr(a, shift), 2 * core);

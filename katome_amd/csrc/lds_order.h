@@ -1,5 +1,5 @@
 // lds_order.h -- one group of distinct one-word keys put in key order in LDS by a workgroup of 1024 threads (the k-mer level's
-// ordered count, table.hip lds_count_ordered_kernel, and the merge of the reverse-complement groups, radix.hip group_merge_kernel).
+// ordered count, lds_count.hip lds_count_ordered_kernel, and the merge of the reverse-complement groups, radix.hip group_merge_kernel).
 #pragma once
 
 #include "common.h"

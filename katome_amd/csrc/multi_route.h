@@ -12,10 +12,9 @@
 // gather as well.
 #pragma once
 #include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include "../../include/katome_gpu.h"
+#include "env.h"
 
 namespace katome {
 
@@ -41,11 +40,6 @@ struct MultiRoute {
     bool sharded_dead_paths() const { return first_seen && remove_dead_paths; }
     bool sharded_stage_letters() const { return first_seen && stages && !sharded_shrink; }
 };
-
-static inline bool env_is(const char* name, const char* value) {
-    const char* e = getenv(name);
-    return e && !strcmp(e, value);
-}
 
 static inline MultiRoute plan_multi_route(uint32_t flags, bool want_contigs, const char* stages) {
     MultiRoute p;

@@ -147,12 +147,6 @@ __device__ __forceinline__ void walk_mark(u32 v, u32 len, const u64* __restrict_
     }
 }
 
-__device__ __forceinline__ u32 wave_sum(u32 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 // Externals (pruner.rs:165-195): Input = no incoming edge.  (A vertex with no edge at all cannot exist here.)  The
 // Input vertices are gathered into a list first -- they are a few per cent of the vertices, and a walk is up to 2k
 // dependent look-ups long: walking from inside the scan leaves most lanes of a workgroup idle for that long.

@@ -103,7 +103,7 @@ template <int NW> struct CoreHashDigit {
     __device__ __forceinline__ u32 operator()(const Key<NW>& k) const { return (u32)(core_hash(k, core_shift, core_bases) >> shift) & (RADIX - 1); }
 };
 
-// ... and the k-mer level's KEY digit for the ordered count (table.hip, lds_count_ordered_kernel): the records are in their
+// ... and the k-mer level's KEY digit for the ordered count (lds_count.hip, lds_count_ordered_kernel): the records are in their
 // representative orientation and ordered by their leading 16 key bits, so that group g is a contiguous key range
 struct LevelKeyDigit {
     u32 shift;
@@ -452,7 +452,7 @@ template <> struct DigitTimers<SupermerOwnerDigit> { static constexpr int HIST =
 template <> struct DigitTimers<RangeDigit> { static constexpr int HIST = K_OWNER_HIST, SCATTER = K_OWNER_SCATTER; };
 
 static bool unstable_first() {
-    static const bool on = getenv("KATOME_UNSTABLE_FIRST") && atoi(getenv("KATOME_UNSTABLE_FIRST")) != 0;      // (off: measured, no gain -- see the kernel)
+    static const bool on = env_flag("KATOME_UNSTABLE_FIRST", false);      // (off: measured, no gain -- see the kernel)
     return on;
 }
 // digits_in: this pass's digit of every record, one byte each at the record's index (see digit_hist_kernel) -- the per-tile counts are
@@ -481,7 +481,7 @@ static int radix_pass(const u64* kin, const u32* vin, u64 n, Digit dg, u64* kout
         KCHECK_HIP(hipFuncSetAttribute((const void*)radix_scatter_kernel<NW, HAS_VAL, Digit, STABLE, Next>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
     {
-        static const bool xcd_aware = !getenv("KATOME_XCD_TILES") || atoi(getenv("KATOME_XCD_TILES")) != 0;       // (0: workgroup i takes tile i)
+        static const bool xcd_aware = env_flag("KATOME_XCD_TILES", true);       // (0: workgroup i takes tile i)
         const u32 xcd_tiles = xcd_aware && pb.nblocks >= 64 ? (u32)((pb.nblocks + 7) / 8) : 0u;
         KernelScope ks((!HAS_VAL && DigitTimers<Digit>::SCATTER == K_SORT_SCATTER) ? (int)K_SORT_SCATTER_KEYS : (int)DigitTimers<Digit>::SCATTER, stream, n);
         NextDigitOut<Next> next;
@@ -781,7 +781,7 @@ static int sort_t(u64* d_keys, u32* d_vals, u64 n, u32 key_bits, hipStream_t str
         const size_t lds = (size_t)(RUN_TILE + 2 * RUN_HALO) * NW * 8;
         if (lds > (64u << 10)) KCHECK_HIP(hipFuncSetAttribute((const void*)run_sort_kernel<NW, HAS_VAL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         {
-            static const int by_waves = getenv("KATOME_RUN_SORT") ? atoi(getenv("KATOME_RUN_SORT")) : 2;      // 1: the staged kernel (A/B)
+            static const int by_waves = env_int("KATOME_RUN_SORT", 2);      // 1: the staged kernel (A/B)
             KernelScope ks(HAS_VAL ? K_RUN_SORT : K_RUN_SORT_KEYS, stream, n);
             if (by_waves == 2)
                 hipLaunchKernelGGL((run_sort_wave_kernel<NW, HAS_VAL>), dim3((grid_for(n, (BLOCK / 64) * RW_OWN * 4, 256u * 32u) + 7u) & ~7u), dim3(BLOCK), 0, stream, kin, vin, n,
@@ -943,7 +943,7 @@ static int region_order_t(const u64* d_in, const u32* w_in, u64 n, int passes, u
     *k_out = kin; *w_out = win;
     return KATOME_OK;
 }
-// (k-mer, count) records of one to three words ordered by the top 16 bits of the k-mer's hash, for the counting in LDS (table.hip): two
+// (k-mer, count) records of one to three words ordered by the top 16 bits of the k-mer's hash, for the counting in LDS (lds_count.hip): two
 // stable 8-bit passes.  The result is where *k_out / *w_out point (one of the two buffer pairs); *group_bits = 16.
 int dev_hash_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t nw, uint64_t* ka, uint64_t* kb, uint32_t* wa, uint32_t* wb,
                    const uint64_t** k_out, const uint32_t** w_out, uint32_t* group_bits, hipStream_t stream, uint32_t* first_counts) {

@@ -6,7 +6,7 @@
 // MINIMIZER (kmer_bits.h): consecutive windows of a read mostly share it, so a read is cut into a dozen runs of windows with one
 // minimizer -- hence one owner -- and each run is shipped as ONE fixed-size record of nwin + k - 1 bases (16 bytes for k <= 31)
 // instead of nwin k-mer records: ~0.2 KB per 150-bp read against 0.96 KB, once, before anything is counted.  What arrives on a
-// rank is every occurrence of the k-mers it owns: it counts the distinct supermers by sorting (table.hip records_to_edges_sorted, as
+// rank is every occurrence of the k-mers it owns: it counts the distinct supermers by sorting (lds_count.hip records_to_edges_sorted, as
 // one GPU counts its tiles), cuts each distinct supermer into its k-mers with the supermer's count, counts those, and has its share
 // of the edges -- the one-GPU pipeline on what it received, no second exchange of records, no partition pass per level.
 //

@@ -840,7 +840,7 @@ def test_round_one_paths_give_the_same_arrays(tmp_path):
                   # the first partition pass of a level counts its digits itself instead of the records kernel on the way; the passes'
                   # tiles in plain order
                   {"KATOME_SORTED_COUNT": "2", "KATOME_FUSED_HIST": "0"}, {"KATOME_SORTED_COUNT": "2", "KATOME_XCD_TILES": "0"},
-                  # the k-mers counted in 8-byte LDS slots, one visit per record (table.hip lds_count_packed_kernel; by default only
+                  # the k-mers counted in 8-byte LDS slots, one visit per record (lds_count.hip lds_count_packed_kernel; by default only
                   # where a group would take two visits), and never
                   {"KATOME_SORTED_COUNT": "2", "KATOME_LC_PACKED": "2"}, {"KATOME_SORTED_COUNT": "2", "KATOME_LC_PACKED": "0"},
                   # the tile levels' two-word keys whole in the LDS slots (lds_count_full_kernel; by default a sample decides), and never
@@ -873,7 +873,7 @@ for k, rc, L, n, many in ((31, True, 150, 4000, 0), (31, False, 100, 3000, 0), (
 
 
 def test_kmers_counted_in_eight_byte_lds_slots(tmp_path):
-    """lds_count_packed_kernel (table.hip): the k-mer level's records counted in one visit -- a slot is the low 48 bits of the k-mer's
+    """lds_count_packed_kernel (lds_count.hip): the k-mer level's records counted in one visit -- a slot is the low 48 bits of the k-mer's
     (bijective) hash and a 16-bit count, the read-out inverts the hash.  Forced at small sizes (KATOME_LC_PACKED=2) against the
     oracle: both strand modes, k with one-word keys, a k-mer seen 70 001 times (the count does not fit: the library says so under
     KATOME_LC_TRACE and counts with the 12-byte slots), and even k with both strands, which stays with the 12-byte slots"""
@@ -917,7 +917,7 @@ for k, rc, L, n, salted in ((31, True, 150, 4000, 0), (31, False, 150, 3000, 1),
 
 
 def test_two_word_keys_counted_with_whole_keys_in_the_lds_slots(tmp_path):
-    """lds_count_full_kernel (table.hip): two-word keys -- the tiles of k <= 31, the k-mers of k = 32..63 -- counted in LDS slots that
+    """lds_count_full_kernel (lds_count.hip): two-word keys -- the tiles of k <= 31, the k-mers of k = 32..63 -- counted in LDS slots that
     hold the whole key, claimed word by word.  Forced at small sizes (KATOME_LC_FULL=1; by default a sample of 256 groups decides)
     against the oracle: both strand modes, even and odd k, tiles whose second word equals the salt that marks "not set" (the level
     falls back to the fingerprint slots: code 7 under KATOME_LC_TRACE)"""
@@ -1289,7 +1289,7 @@ print("OPT", dg.n_nodes, dg.n_edges, c["distinct_kmers"], int(c["kmer_slots"] ==
 
 @pytest.mark.parametrize("first_seen", [False, True])
 def test_optimistic_sub_rounds_fall_back_to_the_guaranteed_number(tmp_path, first_seen):
-    """the sorted last level first tries fewer sub-rounds than a group of distinct records needs (table.hip, lc_optimism); an
+    """the sorted last level first tries fewer sub-rounds than a group of distinct records needs (lds_count.hip, lc_optimism); an
     attempt that fills its LDS table gives up and the guaranteed number runs.  Half of C3 (groups of 11 k records): with
     KATOME_LC_OPTIMISM=0.05 and two probes of patience the first attempt is one round and must fail over (the library says so
     under KATOME_LC_TRACE); =1 never tries; the default tries and succeeds -- the same arrays all three times"""

@@ -1,5 +1,5 @@
 """The partition passes' histograms without a second read of the keys: the kernel that places a record for a pass also leaves that
-pass's digit, one byte, at the record's index (radix.hip radix_scatter_kernel with a next digit, table.hip lds_count_ordered_kernel
+pass's digit, one byte, at the record's index (radix.hip radix_scatter_kernel with a next digit, lds_count.hip lds_count_ordered_kernel
 for S2), and the pass counts its tiles from those bytes (digit_hist_kernel); the big tiles' first pass takes its counts from the
 extraction that wrote the records (extract.hip extract_fixed_kernel, HIST).  The counts are the same numbers from another source,
 so every array of every build must be byte for byte what the routes that use no partition pass at all give (both tile levels and

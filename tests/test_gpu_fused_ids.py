@@ -113,7 +113,7 @@ print("BIG", dg.n_nodes, dg.n_edges, int(dg.edge_weight.to(torch.int64).sum().it
 _HEADS = "[node ids] heads from the merge"
 _LABELS = "[node ids] labels written with the source ids"
 _TRIMMED = "[levels] list trimmed in place"
-_GROUPED = "ordered per group in the merge"          # (table.hip half_sort_finish: the edges leave group_merge_kernel)
+_GROUPED = "ordered per group in the merge"          # (lds_count.hip half_sort_finish: the edges leave group_merge_kernel)
 _ALL_OFF = dict(KATOME_TRIM_IN_PLACE="0", KATOME_MERGE_HEADS="0", KATOME_LABELS_IN_IDS="0")
 # the builds whose edges leave group_merge_kernel (one-word k-mers of odd k, both strands, default numbering) ...
 _MERGED = ["k11", "k13", "k17", "k21", "k25", "k31", "min_weight", "left_over_windows", "reads_with_n", "edges_before_finalize", "host_packed"]

@@ -1,4 +1,4 @@
-"""The k-mer level counted in key order (table.hip lds_count_ordered_kernel, KATOME_EDGE_HALF_SORT): the representatives leave the
+"""The k-mer level counted in key order (lds_count.hip lds_count_ordered_kernel, KATOME_EDGE_HALF_SORT): the representatives leave the
 count sorted, only their reverse complements are sorted, and one merge (radix.hip half_merge_kernel) makes the edge list.  The
 arrays must be byte for byte those of the usual route (KATOME_EDGE_HALF_SORT=0), which sorts every edge.  The switch is read once,
 so every route runs in a process of its own."""

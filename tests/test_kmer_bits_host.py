@@ -123,7 +123,7 @@ def test_owner_of_a_record_is_independent_of_its_table_slot():
 
 
 def test_the_group_hash_of_one_word_keys_is_a_bijection():
-    """lds_count_packed_kernel (table.hip) keeps a one-word k-mer as the low 48 bits of mix64(k-mer) inside the hash group the top 16
+    """lds_count_packed_kernel (lds_count.hip) keeps a one-word k-mer as the low 48 bits of mix64(k-mer) inside the hash group the top 16
     bits name, and reads it back with unmix64: the pair must be inverse to each other on all 64-bit words, and one-word keys of a
     group must differ in their low 48 bits"""
     L = hostshim()

@@ -1,5 +1,5 @@
 """kmer_bits.h rep_orientation, compiled for the host: the orientation the k-mer level's ordered count keys its groups on
-(table.hip, lds_count_ordered_kernel) -- runs without a GPU."""
+(lds_count.hip, lds_count_ordered_kernel) -- runs without a GPU."""
 import ctypes as C
 import os
 import random

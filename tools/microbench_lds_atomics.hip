@@ -1,5 +1,5 @@
 // What an LDS operation on random slots costs on gfx950, per wave64 instruction, when a workgroup of 1024 owns its CU (the shape of the
-// LDS counting kernels of table.hip): plain 8-byte reads, 64-bit compare-and-swap (returning), 32- and 64-bit adds (returning or not), on
+// LDS counting kernels of lds_count.hip): plain 8-byte reads, 64-bit compare-and-swap (returning), 32- and 64-bit adds (returning or not), on
 // 13312 / 19456 slots.  Prints cycles of CU time per wave instruction (= kernel time x clock / (wave instructions per CU)).
 //   hipcc -O3 --offload-arch=gfx950 tools/microbench_lds_atomics.hip -o tools/microbench_lds_atomics && tools/microbench_lds_atomics
 #include <hip/hip_runtime.h>
