@@ -523,8 +523,18 @@ int  katome_dist_remove_dead_paths(katome_dist_builder *d, katome_dist_graph *ou
  * edges) once a stage that may remove edges has run; edges stay on the rank that owns their source.  Collective.
  * KATOME_DIST_STAGES_FAIL=edges|nodes (tests): rank 0's index replay of that kind fails, and every rank returns the error.
  *   standardize_contigs (standardizer.rs:72-122): every contig gets the rounded mean of its weights, bit for bit as on one
- *     GPU.  Every rank holds a table of 12 bytes per node of the WHOLE graph while it runs: KATOME_E_OOM on every rank
- *     when a rank has no room for it (BASELINE config 5 in full on 8 ranks does not fit: DESIGN.md section 6).
+ *     GPU, by one of two routes with the same result.  "table": every rank holds a table of 12 bytes per node of the WHOLE
+ *     graph while it runs.  "ranked" (katome_amd/csrc/dist_contigs.hip): the contigs are ranked by pointer jumping with
+ *     sums, memory per rank O(share), the exchange rounds grow with log2 of the longest contig.  Without
+ *     KATOME_DIST_CONTIGS the table is taken when every rank has room for it and the ranked route otherwise (BASELINE
+ *     config 5 in full: DESIGN.md section 6); KATOME_DIST_CONTIGS=table gives KATOME_E_OOM on every rank when a rank has
+ *     no room, KATOME_DIST_CONTIGS=ranked takes the ranked route, any other value and ranks that disagree give
+ *     KATOME_E_ARG on every rank.  A contig of 2^32 edges or more: KATOME_E_UNSUPPORTED (ranked).
+ *     KATOME_DIST_CONTIGS_CHUNK=<n> (default 2^24): the most questions a rank sends in one exchange of the ranked route.
+ *     Tests: KATOME_DIST_CONTIGS_TABLE_LIMIT=<bytes> stands in for a rank's free memory; KATOME_DIST_CONTIGS_FAIL=<rank>:
+ *     that rank fails after the first ranking round and every rank returns KATOME_E_UNSUPPORTED naming it.
+ *     KATOME_DIST_CONTIGS_TRACE (set to anything): every rank prints one line per call on stderr, the stage's wall time,
+ *     its route and what katome_dist_standardize_stats_read would give.  All of these are read on every call.
  * A rank's share stays below 2^32 edges and 2^32 nodes (KATOME_E_UNSUPPORTED on every rank otherwise), and one retain may
  * remove fewer than 2^32 edges / nodes.
  *   prune_weak_edges: Clean::remove_weak_edges(threshold) (pruner.rs:84-93), at once: retain_edges, then retain_nodes,
@@ -537,6 +547,18 @@ int  katome_dist_standardize_contigs(katome_dist_builder *d, katome_dist_graph *
 int  katome_dist_prune_weak_edges(katome_dist_builder *d, uint32_t threshold, katome_dist_graph *out, void *stream);
 int  katome_dist_standardize_edges(katome_dist_builder *d, uint64_t original_genome_length, uint32_t threshold,
                                    katome_dist_graph *out, void *stream);
+/* what the last katome_dist_standardize_contigs that finished on this builder did (the host entries reach the stage
+ * through the same function); KATOME_E_ARG before any such call                                                     */
+typedef struct {
+    uint32_t route;          /* 0 table, 1 ranked: what the last katome_dist_standardize_contigs of this builder took */
+    uint32_t rank_rounds;    /* ranked: pointer-jumping rounds                                  */
+    uint64_t exchanges;      /* ranked: question/answer exchanges over all rounds (chunks)      */
+    uint64_t contigs;        /* ranked: contigs of the whole graph                              */
+    uint64_t longest_contig; /* ranked: edges of the longest one                                */
+    uint64_t cycle_edges;    /* ranked: edges of the whole graph left on cycles, untouched      */
+    uint64_t bytes_sent;     /* bytes this rank sent during the call, either route              */
+} katome_dist_standardize_stats;
+int  katome_dist_standardize_stats_read(katome_dist_builder *d, katome_dist_standardize_stats *out);
 /* this rank's merged edges after katome_dist_shrink, device arrays owned by the builder (valid until its next
  * katome_dist_shrink or destroy).  Node ids are the NEW ones: a surviving vertex's id is the number of surviving vertices
  * with a smaller global id, so they run over [0, total_nodes).                                                      */

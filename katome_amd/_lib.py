@@ -86,6 +86,11 @@ class DistShrinkStats(C.Structure):
                 ("bytes_sent", C.c_uint64)]
 
 
+class DistStandardizeStats(C.Structure):
+    _fields_ = [("route", C.c_uint32), ("rank_rounds", C.c_uint32), ("exchanges", C.c_uint64), ("contigs", C.c_uint64),
+                ("longest_contig", C.c_uint64), ("cycle_edges", C.c_uint64), ("bytes_sent", C.c_uint64)]
+
+
 # the caller's transport (katome_comm_callbacks)
 A2A_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, u64p, u64p, C.c_void_p, u64p, u64p, C.c_uint64, C.c_int)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, u64p, C.c_uint64, C.c_int)
@@ -187,6 +192,7 @@ SYMBOLS = {
     "katome_dist_remove_dead_paths": (_i, [_vp, C.POINTER(DistGraph), C.POINTER(PruneStats), _vp]),
     "katome_dist_current_graph": (_i, [_vp, C.POINTER(DistGraph)]),
     "katome_dist_standardize_contigs": (_i, [_vp, C.POINTER(DistGraph), _vp]),
+    "katome_dist_standardize_stats_read": (_i, [_vp, C.POINTER(DistStandardizeStats)]),
     "katome_dist_prune_weak_edges": (_i, [_vp, C.c_uint32, C.POINTER(DistGraph), _vp]),
     "katome_dist_standardize_edges": (_i, [_vp, C.c_uint64, C.c_uint32, C.POINTER(DistGraph), _vp]),
     "katome_dist_shrink": (_i, [_vp, C.POINTER(DistContigs), C.POINTER(DistShrinkStats), _vp]),

@@ -54,6 +54,9 @@ struct katome_dist_builder {
     // the last katome_dist_shrink's merged edges on this rank (dist_shrink.hip), kept until the next call or destroy
     DevBuf sh_src, sh_dst, sh_weight, sh_kmers, sh_label_off, sh_label, sh_head, sh_node_id, sh_node_key;
     uint64_t sh_edges = 0, sh_nodes = 0, sh_total_edges = 0, sh_total_nodes = 0, sh_label_bytes = 0;
+    // what the last katome_dist_standardize_contigs that finished on this builder did (katome_dist_standardize_stats_read)
+    katome_dist_standardize_stats contigs_stats = {};
+    bool contigs_stats_valid = false;
 
     int world() const { return comm->world(); }
     int rank() const { return comm->rank(); }
@@ -100,3 +103,5 @@ struct katome_dist_builder {
 
 // dist_stages.hip: edge_lsrc / edge_drank / edge_dlocal / n_src of the share as it stands (collective)
 int dist_rebuild_links(katome_dist_builder* d, hipStream_t stream);
+// dist_contigs.hip: standardize_contigs by list ranking, memory O(share) (collective; the caller has checked the builder and the sizes)
+int dist_contigs_ranked(katome_dist_builder* d, hipStream_t stream, katome_dist_standardize_stats* st);

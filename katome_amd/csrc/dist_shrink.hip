@@ -2,10 +2,11 @@
 // no gather, in either numbering:
 //   * a vertex is INNER when in-degree = out-degree = 1 and its edges are not one self-loop; an edge whose source is not inner
 //     is a HEAD and starts one merged edge; a cycle of inner vertices becomes a self-loop at its smallest global node id.
-//   * degrees and links: every edge sends one record to the owner of its target (first-seen order: edge_drank / edge_dlocal;
-//     by packed key: the allgathered node_base ranges).  The owner counts in-degrees, remembers the address (rank << 56 |
-//     local index) of the edge that comes in and answers whether the target is inner.  Every edge then knows its PREDECESSOR
-//     -- the in-edge of its source, if the source is inner -- from its own rank's tables.
+//   * degrees and links (dist_links.h, shared with dist_contigs.hip): every edge sends one record to the owner of its target
+//     (first-seen order: edge_drank / edge_dlocal; by packed key: the allgathered node_base ranges).  The owner counts
+//     in-degrees, remembers the address (rank << 56 | local index) of the edge that comes in and answers whether the target is
+//     inner.  Every edge then knows its PREDECESSOR -- the in-edge of its source, if the source is inner -- from its own
+//     rank's tables.
 //   * list ranking by pointer jumping (Wyllie): one state pair per edge, A = RESOLVED | head address or the address of the
 //     edge 2^round steps back, B = offset from the head or the smallest source id over the jumped span.  A round is one
 //     question (the pointer) and two answers (that edge's A and B) through the Router; every unresolved edge's span is 2^round
@@ -22,7 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "dist_route.h"
+#include "dist_links.h"
 
 namespace {
 
@@ -30,35 +31,6 @@ constexpr u64 RESOLVED = 1ull << 55;                  // state word A: the head'
 constexpr u64 ADDR = (0xFFull << 56) | 0xFFFFFFFFull;
 constexpr u64 ID_LIMIT = 1ull << 40;
 
-__device__ __forceinline__ u32 local_of(u64 a) { return (u32)a; }
-
-// every edge: its source's local index and its target's address (first-seen: the links; by packed key: the node_base ranges)
-__global__ __launch_bounds__(BLOCK) void target_kernel(const u64* __restrict__ src, const u64* __restrict__ dst, u64 E, const u64* __restrict__ lsrc_fs,
-                                                       const u64* __restrict__ drank, const u64* __restrict__ dlocal, const u64* __restrict__ bases,
-                                                       u32 world, u64 my_base, u32* __restrict__ lsrc, u64* __restrict__ tgt) {
-    WLOOP(e, E) if (e < E) {
-        if (lsrc_fs) { lsrc[e] = (u32)lsrc_fs[e]; tgt[e] = (drank[e] << 56) | dlocal[e]; continue; }
-        lsrc[e] = (u32)(src[e] - my_base);
-        const u64 v = dst[e];
-        u32 p = 0;
-        while (p + 1 < world && bases[p + 1] <= v) ++p;
-        tgt[e] = ((u64)p << 56) | (v - bases[p]);
-    }
-}
-__global__ __launch_bounds__(BLOCK) void own_addr_kernel(u64 E, u64 me, u64* __restrict__ out) { WLOOP(e, E) if (e < E) out[e] = (me << 56) | e; }
-__global__ __launch_bounds__(BLOCK) void out_deg_kernel(const u32* __restrict__ lsrc, u64 E, u32* __restrict__ outdeg, u32* __restrict__ out_edge) {
-    WLOOP(e, E) if (e < E) { atomicAdd(&outdeg[lsrc[e]], 1u); out_edge[lsrc[e]] = (u32)e; }
-}
-__global__ __launch_bounds__(BLOCK) void in_rec_kernel(const u64* __restrict__ A, const u64* __restrict__ B, u64 n, u64 N, u32* __restrict__ indeg, u64* __restrict__ in_edge) {
-    WLOOP(i, n) if (i < n && local_of(A[i]) < N) { atomicAdd(&indeg[local_of(A[i])], 1u); in_edge[local_of(A[i])] = B[i]; }
-}
-__global__ __launch_bounds__(BLOCK) void inner_kernel(u64 N, const u32* __restrict__ indeg, const u32* __restrict__ outdeg, const u64* __restrict__ in_edge,
-                                                      const u32* __restrict__ out_edge, u64 me, unsigned char* __restrict__ inner) {
-    WLOOP(j, N) if (j < N) inner[j] = indeg[j] == 1 && outdeg[j] == 1 && in_edge[j] != ((me << 56) | out_edge[j]);
-}
-__global__ __launch_bounds__(BLOCK) void answer_u8_kernel(const u64* __restrict__ A, u64 n, u64 N, const unsigned char* __restrict__ v, u64* __restrict__ out) {
-    WLOOP(i, n) if (i < n) out[i] = local_of(A[i]) < N ? v[local_of(A[i])] : 0;
-}
 // the ranking's start: heads are resolved at offset 0, every other edge points at its predecessor (span 1, its source id)
 __global__ __launch_bounds__(BLOCK) void init_kernel(u64 E, const u32* __restrict__ lsrc, const u64* __restrict__ src, const unsigned char* __restrict__ inner,
                                                      const u64* __restrict__ in_edge, const u64* __restrict__ dst_inner, u64 me, u64* __restrict__ pred,
@@ -322,47 +294,17 @@ int dist_shrink(katome_dist_builder* d, katome_dist_shrink_stats* stats, hipStre
         KCHECK(d->comm->allreduce(&bad, 1, OP_MAX));
         if (bad) { set_error("katome_dist_shrink: more than 2^32 edges or nodes on one rank, or more than 2^40 nodes"); return KATOME_E_UNSUPPORTED; }
     }
-    // ---- degrees and links --------------------------------------------------------------------------------------------
-    if (d->first_seen && !d->edge_lsrc.p) KCHECK(dist_rebuild_links(d, stream));
-    std::vector<uint64_t> n_of(world, 0), bases(world + 1, 0), e_of(world, 0);
-    KCHECK(d->comm->allgather(N, n_of.data()));
-    KCHECK(d->comm->allgather(E, e_of.data()));
-    uint64_t edge_base = 0;
-    for (int p = 0; p < world; ++p) { bases[p + 1] = bases[p] + n_of[p]; if (p < S.rank) edge_base += e_of[p]; }
-    DevBuf dbases(stream), lsrc(stream), tgt(stream), mine(stream);
-    KCHECK(dbases.alloc((world + 1) * 8)); KCHECK(lsrc.alloc((E + 1) * 4)); KCHECK(tgt.alloc((E + 1) * 8)); KCHECK(mine.alloc((E + 1) * 8));
-    KCHECK_HIP(hipMemcpyAsync(dbases.p, bases.data(), (world + 1) * 8, hipMemcpyHostToDevice, stream));
+    // ---- degrees and links (dist_links.h) --------------------------------------------------------------------------------
+    Links links(stream);
+    KCHECK(dist_links(d, S.router, stream, links));
+    const uint64_t edge_base = links.edge_base;
     const u64* src = d->edge_src.as<u64>(); const u64* dst = d->edge_dst.as<u64>();
-    if (E) {
-        KLAUNCH(target_kernel, E, stream, src, dst, E, d->first_seen ? d->edge_lsrc.as<u64>() : nullptr, d->edge_drank.as<u64>(), d->edge_dlocal.as<u64>(),
-                dbases.as<u64>(), (u32)world, d->node_base, lsrc.as<u32>(), tgt.as<u64>());
-        KLAUNCH(own_addr_kernel, E, stream, E, me, mine.as<u64>());
-    }
-    KCHECK_HIP(hipGetLastError());
-    DevBuf indeg(stream), outdeg(stream), in_edge(stream), out_edge(stream), inner(stream), dst_inner(stream);
-    KCHECK(indeg.alloc((N + 1) * 4)); KCHECK(outdeg.alloc((N + 1) * 4)); KCHECK(in_edge.alloc((N + 1) * 8)); KCHECK(out_edge.alloc((N + 1) * 4));
-    KCHECK(inner.alloc(N + 16)); KCHECK(dst_inner.alloc((E + 1) * 8));
-    KCHECK_HIP(hipMemsetAsync(indeg.p, 0, (N + 1) * 4, stream)); KCHECK_HIP(hipMemsetAsync(outdeg.p, 0, (N + 1) * 4, stream));
-    if (E) KLAUNCH(out_deg_kernel, E, stream, lsrc.as<u32>(), E, outdeg.as<u32>(), out_edge.as<u32>());
-    {
-        Routed r(stream);
-        KCHECK(S.router.send(tgt.as<u64>(), mine.as<u64>(), E, r));
-        if (r.n) KLAUNCH(in_rec_kernel, r.n, stream, r.a.as<u64>(), r.b.as<u64>(), r.n, N, indeg.as<u32>(), in_edge.as<u64>());
-        if (N) KLAUNCH(inner_kernel, N, stream, N, indeg.as<u32>(), outdeg.as<u32>(), in_edge.as<u64>(), out_edge.as<u32>(), me, inner.as<unsigned char>());
-        KCHECK_HIP(hipGetLastError());
-        DevBuf a(stream);
-        KCHECK(a.alloc((r.n + 1) * 8));
-        if (r.n) KLAUNCH(answer_u8_kernel, r.n, stream, r.a.as<u64>(), r.n, N, inner.as<unsigned char>(), a.as<u64>());
-        KCHECK_HIP(hipGetLastError());
-        KCHECK(S.router.reply(r, a.as<u64>(), dst_inner.as<u64>()));
-    }
-    tgt.release(); mine.release(); indeg.release(); outdeg.release(); out_edge.release();
     DevBuf pred(stream), st_a(stream), st_b(stream), last(stream);
     KCHECK(pred.alloc((E + 1) * 8)); KCHECK(st_a.alloc((E + 1) * 8)); KCHECK(st_b.alloc((E + 1) * 8)); KCHECK(last.alloc(E + 16));
-    if (E) KLAUNCH(init_kernel, E, stream, E, lsrc.as<u32>(), src, inner.as<unsigned char>(), in_edge.as<u64>(), dst_inner.as<u64>(), me, pred.as<u64>(),
-                   st_a.as<u64>(), st_b.as<u64>(), last.as<unsigned char>());
+    if (E) KLAUNCH(init_kernel, E, stream, E, links.lsrc.as<u32>(), src, links.inner.as<unsigned char>(), links.in_edge.as<u64>(), links.dst_inner.as<u64>(), me,
+                   pred.as<u64>(), st_a.as<u64>(), st_b.as<u64>(), last.as<unsigned char>());
     KCHECK_HIP(hipGetLastError());
-    lsrc.release(); inner.release(); in_edge.release(); dst_inner.release();
+    links.release();
     // ---- list ranking; then the cycles of inner vertices ------------------------------------------------------------------
     uint32_t rounds = 0, cycle_rounds = 0;
     uint64_t left = 0, n_cycles = 0;

@@ -1,10 +1,12 @@
 // dist_stages.hip -- the stages of assemble_with_graph between the two prunings (asm/basic_assembler.rs:63-72) on the
 // SHARDED graph of a first-seen-ordered build, in the reference's numbering and without a gather:
-//   * standardize_contigs (standardizer.rs:72-122): a REPLICATED table, one 8-byte word and one 4-byte weight per node of
-//     the whole graph (ambiguous / end / pass-through with (owner rank, target) of its single out-edge), is composed on
-//     the directory rank of each node id (in-degrees and out-records arrive there in one exchange each) and all-gathered.
-//     Every rank then walks the contigs that start at its own ambiguous nodes with the one-GPU loop, writes the first
-//     edge's mean itself and sends (node id, mean) to the owner of every other edge of the contig: one exchange.
+//   * standardize_contigs (standardizer.rs:72-122), the TABLE route (the other one, list ranking in O(share) memory, is
+//     dist_contigs.hip; contigs_route below chooses: KATOME_DIST_CONTIGS, or whether the table fits): a REPLICATED table,
+//     one 8-byte word and one 4-byte weight per node of the whole graph (ambiguous / end / pass-through with (owner rank,
+//     target) of its single out-edge), is composed on the directory rank of each node id (in-degrees and out-records
+//     arrive there in one exchange each) and all-gathered.  Every rank then walks the contigs that start at its own
+//     ambiguous nodes with the one-GPU loop, writes the first edge's mean itself and sends (node id, mean) to the owner
+//     of every other edge of the contig: one exchange.
 //   * prune_weak_edges (Clean::remove_weak_edges, pruner.rs:84-93): retain_edges and then retain_nodes, both "visit the
 //     indices in descending order, swap_remove the rejected ones".  The rejected positions go to rank 0, which replays
 //     the swap_removes on 64-bit positions (prune.hip's scan + pointer jumping, dev_replay_edges64, every position listed
@@ -15,6 +17,7 @@
 // Nothing narrower than 64 bits carries an index on the wire or in a replay; a rank's own share stays below 2^32 edges.
 // Node ids are below 2^40 (the table words carry them in 40 bits).  DESIGN.md section 6 has the bytes per stage.
 #include <math.h>
+#include <stdio.h>
 
 #include "dist_route.h"
 
@@ -573,6 +576,35 @@ int dist_rebuild_links(katome_dist_builder* d, hipStream_t stream) {
     return KATOME_OK;
 }
 
+namespace {
+
+// KATOME_DIST_CONTIGS=table|ranked names the route of katome_dist_standardize_contigs; unset: the table when it fits every
+// rank, the ranked route (dist_contigs.hip) otherwise.  One allreduce: the ranks' environments and whether the table fits;
+// ranks that disagree, or a value that names no route, are KATOME_E_ARG on every rank.
+// KATOME_DIST_CONTIGS_TABLE_LIMIT=<bytes> (tests) stands in for the free memory.
+enum ContigsRoute { CONTIGS_TABLE = 0, CONTIGS_RANKED = 1 };
+int contigs_route(katome_dist_builder* d, const Stage& S, uint32_t* route) {
+    const char* e = getenv("KATOME_DIST_CONTIGS");
+    const int said = !e || !*e ? 0 : !strcmp(e, "table") ? 1 : !strcmp(e, "ranked") ? 2 : 3;
+    // the replicated table: 12 bytes per node of the whole graph on every rank
+    size_t free_b = 0, total_b = 0;
+    KCHECK_HIP(hipMemGetInfo(&free_b, &total_b));
+    free_b += dev_cached_bytes();
+    const char* lim = getenv("KATOME_DIST_CONTIGS_TABLE_LIMIT");
+    if (lim && *lim) free_b = (size_t)strtoull(lim, nullptr, 10);
+    const uint64_t need = (S.TN + 1) * 12 + S.range * 28 + (S.E + 1) * 40 + (1ull << 30);
+    uint64_t v[5] = {said == 0, said == 1, said == 2, said == 3, need < free_b ? 0ull : 1ull};      // [4]: no room on some rank
+    KCHECK(d->comm->allreduce(v, 5, OP_MAX));
+    if (v[3]) { set_error("katome_dist_standardize_contigs: KATOME_DIST_CONTIGS must be table or ranked%s%s", said == 3 ? ", not " : " on every rank", said == 3 ? e : ""); return KATOME_E_ARG; }
+    if (v[0] + v[1] + v[2] != 1) { set_error("katome_dist_standardize_contigs: the ranks disagree on KATOME_DIST_CONTIGS"); return KATOME_E_ARG; }
+    if (v[1] && v[4]) { set_error("katome_dist_standardize_contigs: the replicated node table (%llu nodes, 12 B each) does not fit a rank's free HBM", (unsigned long long)S.TN); return KATOME_E_OOM; }
+    *route = v[2] || (v[0] && v[4]) ? CONTIGS_RANKED : CONTIGS_TABLE;
+    return KATOME_OK;
+}
+int contigs_table(katome_dist_builder* d, Stage& S, hipStream_t stream);
+
+}  // namespace
+
 extern "C" {
 
 int katome_dist_standardize_contigs(katome_dist_builder* d, katome_dist_graph* out, void* stream_) {
@@ -583,17 +615,31 @@ int katome_dist_standardize_contigs(katome_dist_builder* d, katome_dist_graph* o
     KCHECK(check_sizes(d));
     Stage S(d, stream);
     KCHECK(S.init());
+    const bool trace = getenv("KATOME_DIST_CONTIGS_TRACE") != nullptr;       // (asked for on every call, as the stage's other switches)
+    katome_dist_standardize_stats st = {};
+    const uint64_t bytes0 = d->comm->stats.bytes_out;
+    const double t0 = now_ms();
+    KCHECK(contigs_route(d, S, &st.route));
+    if (st.route == CONTIGS_RANKED) KCHECK(dist_contigs_ranked(d, stream, &st));
+    else KCHECK(contigs_table(d, S, stream));
+    st.bytes_sent = d->comm->stats.bytes_out - bytes0;
+    d->contigs_stats = st; d->contigs_stats_valid = true;
+    if (trace)
+        fprintf(stderr, "[katome_dist_standardize_contigs] rank %d/%d: %.2f ms, route %s, ranking rounds %u, exchanges %llu, contigs %llu, longest %llu, "
+                "cycle edges %llu, sent %llu bytes\n", d->rank(), d->world(), now_ms() - t0, st.route == CONTIGS_RANKED ? "ranked" : "table", st.rank_rounds,
+                (unsigned long long)st.exchanges, (unsigned long long)st.contigs, (unsigned long long)st.longest_contig, (unsigned long long)st.cycle_edges,
+                (unsigned long long)st.bytes_sent);
+    return katome_dist_current_graph(d, out);
+}
+
+}  // extern "C"
+
+namespace {
+
+// the table route
+int contigs_table(katome_dist_builder* d, Stage& S, hipStream_t stream) {
     katome_builder* b = d->b;
     const uint64_t E = S.E, TN = S.TN;
-    {   // the replicated table: 12 bytes per node of the whole graph on every rank; all ranks agree whether it fits
-        size_t free_b = 0, total_b = 0;
-        KCHECK_HIP(hipMemGetInfo(&free_b, &total_b));
-        free_b += dev_cached_bytes();
-        const uint64_t need = (TN + 1) * 12 + S.range * 28 + (E + 1) * 40 + (1ull << 30);
-        uint64_t ok = need < free_b ? 1 : 0;
-        KCHECK(d->comm->allreduce(&ok, 1, OP_MIN));
-        if (!ok) { set_error("katome_dist_standardize_contigs: the replicated node table (%llu nodes, 12 B each) does not fit a rank's free HBM", (unsigned long long)TN); return KATOME_E_OOM; }
-    }
     const u64* src = d->edge_src.as<u64>(); const u64* dst = d->edge_dst.as<u64>();
     // ---- in-degrees on the directory rank of each node id ---------------------------------------------------------------
     DevBuf indeg(stream), word(stream), wt(stream);
@@ -686,8 +732,12 @@ int katome_dist_standardize_contigs(katome_dist_builder* d, katome_dist_graph* o
     }
     A.release(); B.release();
     KCHECK(S.agree_clean("a contig's mean names a node that is not a single-out-edge node of its owner"));
-    return katome_dist_current_graph(d, out);
+    return KATOME_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int katome_dist_prune_weak_edges(katome_dist_builder* d, uint32_t threshold, katome_dist_graph* out, void* stream_) {
     KCHECK(check_builder(d, "katome_dist_prune_weak_edges"));

@@ -283,10 +283,18 @@ class ShardedBuilder(_ViewOwner):
 
     # ---- the stages after the first pruning on the sharded graph (katome_dist_*; first-seen order, shares not gathered) ----
     def standardize_contigs(self):
-        """Standardizable::standardize_contigs (standardizer.rs:72-122) -> this rank's share"""
+        """Standardizable::standardize_contigs (standardizer.rs:72-122) -> this rank's share.  KATOME_DIST_CONTIGS=table|ranked
+        names the route (unset: the replicated table when it fits every rank, list ranking in O(share) memory otherwise)"""
         g = _lib.DistGraph()
         _check(_lib.lib().katome_dist_standardize_contigs(self._h, C.byref(g), _stream()))
         return RankGraph(g, self, self.tdev)
+
+    def standardize_stats(self):
+        """what the last standardize_contigs() of this builder did (katome_dist_standardize_stats_read): route (0 table, 1
+        ranked), bytes_sent, and on the ranked route rank_rounds, exchanges, contigs, longest_contig, cycle_edges"""
+        st = _lib.DistStandardizeStats()
+        _check(_lib.lib().katome_dist_standardize_stats_read(self._h, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _lib.DistStandardizeStats._fields_}
 
     def prune_weak_edges(self, threshold):
         """Clean::remove_weak_edges(threshold) (pruner.rs:84-93) at once, in petgraph's numbering -> this rank's share
