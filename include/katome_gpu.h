@@ -145,6 +145,19 @@ int katome_build_packed(const katome_settings *s, const uint8_t *packed, uint64_
  * graph is read through katome_dist_* (katome_dist_graph.d_edge_age is 64-bit). */
 int katome_build_packed_staged(const katome_settings *s, const uint8_t *packed, uint64_t n_reads, uint32_t read_len,
                                const uint8_t *skip, const char *stages, uint64_t original_genome_length, katome_graph **out);
+/* The two staged entries that also describe the graph where assemble_with_graph logs it (graph.log_stats(),
+ * asm/basic_assembler.rs:58-75 -> stats/collections.rs:137-168), computed on the device before anything is copied out:
+ * stage_stats is the caller's array of strlen(stages) + 1 entries (NULL: KATOME_E_ARG); entry 0 is the graph as built, after
+ * the pruning KATOME_FLAG_REMOVE_DEAD_PATHS asks for, entry i the graph after the i-th letter of `stages`.  With "dcwced" and
+ * no flag, entries 0, 1, 3, 5 and 6 are the reference's five lines.  `stages` NULL or empty: entry 0 alone, and a packed-key
+ * build is taken as well (stats need no numbering).  With settings.n_devices > 1 the numbers come from whichever route the
+ * build takes: katome_dist_graph_stats on the shares (rank 0 writes the array) or katome_dev_graph_stats on the gathered
+ * graph.  Everything else as for the staged entries above. */
+int katome_build_files_staged_stats(const katome_settings *s, const char *const *paths, size_t n_paths, const char *stages,
+                                    uint64_t original_genome_length, katome_stats *stage_stats, katome_graph **out);
+int katome_build_packed_staged_stats(const katome_settings *s, const uint8_t *packed, uint64_t n_reads, uint32_t read_len,
+                                     const uint8_t *skip, const char *stages, uint64_t original_genome_length,
+                                     katome_stats *stage_stats, katome_graph **out);
 
 void katome_graph_free(katome_graph *g);
 
@@ -188,7 +201,7 @@ void katome_builder_destroy(katome_builder *b);
 /* optional per-phase timing with HIP events recorded on the caller's stream (bench.py's roofline
  * figures).  total_ms / launches have katome_phase_count() entries, named by katome_phase_name():
  * extract, region_order, insert, emit_edges, sort_edges, node_set, rank, labels, insert_tiles,
- * expand_tiles, expand_mid_tiles, first_seen_order.  Reading
+ * expand_tiles, expand_mid_tiles, first_seen_order ... (new names are appended: an index keeps its name).  Reading
  * synchronises the device and clears the record.                                            */
 int  katome_builder_profile(katome_builder *b, int enable);
 int  katome_builder_profile_read(katome_builder *b, double *total_ms, uint64_t *launches);
@@ -351,6 +364,13 @@ int katome_dev_remove_dead_paths(katome_builder *b, katome_dev_graph *graph, kat
 
 /* the finalized graph as it stands now (after katome_dev_remove_dead_paths / katome_dev_remove_weak_edges) */
 int katome_dev_current_graph(katome_builder *b, katome_dev_graph *out);
+/* Stats<CollectionStats>::stats for PtGraph (stats/collections.rs:137-168) and the weight spectrum (see
+ * katome_dev_weight_spectrum_arrays) of the finalized graph as it stands, in either numbering, after any of
+ * katome_dev_remove_dead_paths, katome_dev_remove_weak_edges and katome_dev_standardize_*: what graph.log_stats() prints
+ * at that point (asm/basic_assembler.rs:58-75), without copying the graph out.  Nothing in the builder changes.  Before
+ * katome_dev_finalize: KATOME_E_ARG.  Both synchronise.  Profile phases "graph_stats" and "weight_spectrum". */
+int katome_dev_graph_stats(katome_builder *b, katome_stats *out, void *stream);
+int katome_dev_weight_spectrum(katome_builder *b, uint64_t *bins /* host, [n_bins] */, uint32_t n_bins, void *stream);
 
 /* Standardizable for PtGraph (standardizer.rs:41-128), the two weight passes assemble_with_graph runs between its
  * prunings (asm/basic_assembler.rs:63-70), in place on the finalized graph as it stands:
@@ -599,6 +619,21 @@ typedef struct {
 int  katome_dist_shrink(katome_dist_builder *d, katome_dist_contigs *out, katome_dist_shrink_stats *stats, void *stream);
 /* this rank's share of the graph as it stands (after katome_dist_finalize / katome_dist_remove_dead_paths / the stages) */
 int  katome_dist_current_graph(katome_dist_builder *d, katome_dist_graph *out);
+/* katome_dev_graph_stats / katome_dev_weight_spectrum for the SHARDED graph, no gather (katome_amd/csrc/dist_stats.hip): the
+ * numbers of the WHOLE graph, the same on every rank, for a finalized build in either numbering, straight after
+ * katome_dist_finalize, after katome_dist_remove_dead_paths and after the katome_dist_standardize_* /
+ * katome_dist_prune_weak_edges stages.  Out-degrees and weights are local; for the in-degrees every edge sends its target's
+ * address to the target's owner, at most KATOME_DIST_STATS_CHUNK (default 2^24) records per rank and exchange; two allreduces
+ * (sums, maxima) combine the ranks.  All counts are u64: the graph may hold more than 2^32 edges, a rank's share may not
+ * (KATOME_E_UNSUPPORTED on every rank).  Memory per rank is O(share).  Not finalized, or gathered: KATOME_E_ARG.  A failure
+ * of a rank's own allocations, launches or checks comes back on every rank, with a message that names the rank (what the
+ * exchange layer allocates inside one exchange is not agreed, as in the other sharded stages); KATOME_DIST_STATS_FAIL=<rank>
+ * (tests): that rank fails after the first exchange.  The bytes sent are accounted to the "prune" exchange phase.  Where a stage has dropped
+ * the links of a FIRST_SEEN_ORDER build, katome_dist_graph_stats rebuilds them (as katome_dist_shrink and
+ * katome_dist_remove_dead_paths do), which re-orders the rank's node arrays: fetch them again with katome_dist_current_graph.
+ * Collective. */
+int  katome_dist_graph_stats(katome_dist_builder *d, katome_stats *out, void *stream);
+int  katome_dist_weight_spectrum(katome_dist_builder *d, uint64_t *bins /* host, [n_bins] */, uint32_t n_bins, void *stream);
 /* the rank's single-GPU builder underneath (per-phase kernel timing: katome_builder_profile*) */
 katome_builder *katome_dist_inner(katome_dist_builder *d);
 /* which records travel in this build: "local" (every rank counts its own reads, distinct k-mers routed: up to two ranks), "tiles"
@@ -669,6 +704,21 @@ int katome_dev_endpoints(int device, const uint64_t *d_edge_key, uint64_t n, uin
 /* compress_edge-format labels (compress.rs:250-271) of packed k-mers                       */
 int katome_dev_labels(int device, const uint64_t *d_edge_key, uint64_t n, uint32_t k,
                       uint8_t *d_label, void *stream);
+/* Stats<CollectionStats>::stats for PtGraph (stats/collections.rs:137-168) from device arrays, filled exactly as
+ * katome_graph_stats fills it from host arrays: u64 sums, the two averages one f64 division each on the host (no edges:
+ * avg_edge_weight is NaN, no nodes: avg_out_degree is NaN, as the reference's 0.0 / 0.0); externals(Incoming) and
+ * externals(Outgoing) (pt_graph.rs:64-77) both count isolated nodes; a self-loop counts once in and once out.  n_edges >=
+ * 2^32: KATOME_E_UNSUPPORTED.  Every id must be below n_nodes: the caller's contract, NOT checked.  Scratch: 8 bytes per
+ * node from the library's allocator (KATOME_E_OOM when there is no room).  Synchronises. */
+int katome_dev_stats_arrays(int device, const uint64_t *d_edge_src, const uint64_t *d_edge_dst,
+                            const uint32_t *d_edge_weight, uint64_t n_edges, uint64_t n_nodes,
+                            katome_stats *out, void *stream);
+/* the weight spectrum (the k-mer abundance histogram minimal_weight_threshold and standardize_edges' threshold,
+ * standardizer.rs:42-70, are chosen from): bins[w] = records of weight w for w < n_bins - 1, bins[n_bins - 1] = records of
+ * weight >= n_bins - 1; the bins add up to n.  2 <= n_bins <= 16384, anything else is KATOME_E_ARG before the device is
+ * touched.  Synchronises. */
+int katome_dev_weight_spectrum_arrays(int device, const uint32_t *d_weight, uint64_t n,
+                                      uint64_t *bins /* host, [n_bins] */, uint32_t n_bins, void *stream);
 
 /* ---- synthetic workload generator (bench/tests; DESIGN.md "Synthetic workload") ---------- */
 int katome_dev_synth_reads(int device, uint64_t first_read, uint64_t n_reads, uint32_t read_len,

@@ -108,6 +108,9 @@ SYMBOLS = {
     "katome_build_files_staged": (_i, [C.POINTER(Settings), _pp, _sz, C.c_char_p, _u64, C.POINTER(C.POINTER(Graph))]),
     "katome_build_packed": (_i, [C.POINTER(Settings), _vp, _u64, _u32, _vp, C.POINTER(C.POINTER(Graph))]),
     "katome_build_packed_staged": (_i, [C.POINTER(Settings), _vp, _u64, _u32, _vp, C.c_char_p, _u64, C.POINTER(C.POINTER(Graph))]),
+    "katome_build_files_staged_stats": (_i, [C.POINTER(Settings), _pp, _sz, C.c_char_p, _u64, C.POINTER(Stats), C.POINTER(C.POINTER(Graph))]),
+    "katome_build_packed_staged_stats": (_i, [C.POINTER(Settings), _vp, _u64, _u32, _vp, C.c_char_p, _u64, C.POINTER(Stats),
+                                         C.POINTER(C.POINTER(Graph))]),
     "katome_graph_free": (None, [C.POINTER(Graph)]),
     "katome_graph_stats": (_i, [C.POINTER(Graph), C.POINTER(Stats)]),
     "katome_last_error": (C.c_char_p, []),
@@ -153,6 +156,10 @@ SYMBOLS = {
     "katome_dev_shrink": (_i, [_vp, C.POINTER(DevContigs), _vp]),
     "katome_dev_shrink_mode": (_i, [_vp, C.c_uint32, C.POINTER(DevContigs), C.POINTER(C.c_double), _vp]),
     "katome_dev_current_graph": (_i, [_vp, C.POINTER(DevGraph)]),
+    "katome_dev_graph_stats": (_i, [_vp, C.POINTER(Stats), _vp]),
+    "katome_dev_weight_spectrum": (_i, [_vp, u64p, _u32, _vp]),
+    "katome_dev_stats_arrays": (_i, [_i, _vp, _vp, _vp, _u64, _u64, C.POINTER(Stats), _vp]),
+    "katome_dev_weight_spectrum_arrays": (_i, [_i, _vp, _u64, u64p, _u32, _vp]),
     "katome_dev_scan_counts": (_i, [_i, _vp, _u64, _vp, _vp]),
     "katome_dev_replay_node_removals": (_i, [_i, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
     "katome_dev_replay_edge_removals": (_i, [_i, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
@@ -196,6 +203,8 @@ SYMBOLS = {
     "katome_dist_prune_weak_edges": (_i, [_vp, C.c_uint32, C.POINTER(DistGraph), _vp]),
     "katome_dist_standardize_edges": (_i, [_vp, C.c_uint64, C.c_uint32, C.POINTER(DistGraph), _vp]),
     "katome_dist_shrink": (_i, [_vp, C.POINTER(DistContigs), C.POINTER(DistShrinkStats), _vp]),
+    "katome_dist_graph_stats": (_i, [_vp, C.POINTER(Stats), _vp]),
+    "katome_dist_weight_spectrum": (_i, [_vp, u64p, _u32, _vp]),
     "katome_dist_exchange_count": (_u32, []),
     "katome_dist_exchange_name": (C.c_char_p, [_u32]),
     "katome_dist_exchange_read": (_i, [_vp, u64p]),

@@ -109,6 +109,15 @@ class CollectionStats:
         return cls(node_count=node_count, edge_count=edge_count)
 
 
+def collection_stats(st, capacity=(0, None)) -> CollectionStats:
+    """a katome_stats (_lib.Stats) as the reference's CollectionStats"""
+    return CollectionStats(
+        node_count=st.node_count, edge_count=st.edge_count, max_edge_weight=st.max_edge_weight,
+        avg_edge_weight=st.avg_edge_weight, max_in_degree=st.max_in_degree, max_out_degree=st.max_out_degree,
+        avg_out_degree=st.avg_out_degree, incoming_vert_count=st.incoming_vert_count,
+        outgoing_vert_count=st.outgoing_vert_count, capacity=capacity)
+
+
 FLAG_FIRST_SEEN_ORDER = 1
 FLAG_REMOVE_DEAD_PATHS = 2
 FLAG_RANKS_SHARE_DEVICE = 4
@@ -185,8 +194,12 @@ class GpuGraph:
     # ---- Build::create (builder.rs:42-54) ----------------------------------------------------
     @classmethod
     def create(cls, input_files, ft, reverse_complement, minimal_weight_threshold=0, device=0, first_seen_order=False,
-               remove_dead_paths=False, stages=None, original_genome_length=0, n_devices=1, ranks_share_device=False):
+               remove_dead_paths=False, stages=None, original_genome_length=0, n_devices=1, ranks_share_device=False,
+               stage_stats=False):
         """-> (GpuGraph, number_of_read_bytes); uses the global k set by set_global_k_sizes.
+        stage_stats: also describe the graph on the device where assemble_with_graph logs it (graph.log_stats(),
+        asm/basic_assembler.rs:58-75): g.stage_stats is a list of CollectionStats, entry 0 the graph as built (after the
+        pruning remove_dead_paths asks for), entry i the graph after the i-th letter of `stages`.
         stages: stages of assemble_with_graph to run on the device after the build, e.g. "dcwced" = everything before
         collapse (d remove_dead_paths, c standardize_contigs, w remove_weak_edges(minimal_weight_threshold),
         e standardize_edges(original_genome_length, k, minimal_weight_threshold)); needs first_seen_order.
@@ -197,20 +210,28 @@ class GpuGraph:
                           first_seen_order=first_seen_order, remove_dead_paths=remove_dead_paths, n_devices=n_devices,
                           ranks_share_device=ranks_share_device)
         gp = C.POINTER(_lib.Graph)()
-        if stages:
+        described = None
+        if stage_stats:
+            described = (_lib.Stats * (len(stages or "") + 1))()
+            _check(_lib.lib().katome_build_files_staged_stats(C.byref(s), _paths(input_files), len(input_files), (stages or "").encode(),
+                                                              original_genome_length, described, C.byref(gp)))
+        elif stages:
             _check(_lib.lib().katome_build_files_staged(C.byref(s), _paths(input_files), len(input_files), stages.encode(),
                                                         original_genome_length, C.byref(gp)))
         else:
             _check(_lib.lib().katome_build_files(C.byref(s), _paths(input_files), len(input_files), C.byref(gp)))
         g = cls(gp)                                   # the arrays view the C result and free it with their last reference
+        if described is not None:
+            g.stage_stats = [collection_stats(st) for st in described]
         return g, g.read_bytes
 
     @classmethod
     def create_from_packed(cls, packed, n_reads, read_len, skip=None, reverse_complement=False, device=0, k=None,
                            first_seen_order=False, remove_dead_paths=False, n_devices=1, ranks_share_device=False,
-                           table_slots_hint=0, stages=None, original_genome_length=0, minimal_weight_threshold=0):
+                           table_slots_hint=0, stages=None, original_genome_length=0, minimal_weight_threshold=0,
+                           stage_stats=False):
         """Same build from 2-bit packed reads (numpy uint8), the synthetic-workload entry.  stages / original_genome_length /
-        minimal_weight_threshold: as for create(); with n_devices > 1 the stages run on the sharded graph when
+        minimal_weight_threshold / stage_stats: as for create(); with n_devices > 1 the stages run on the sharded graph when
         KATOME_DIST_STAGES=sharded is set or the graph is too big to gather, else on the gathered one."""
         s = make_settings(K_SIZE if k is None else k, InputFileType.Fastq, reverse_complement, minimal_weight_threshold, device,
                           table_slots_hint=table_slots_hint, first_seen_order=first_seen_order,
@@ -221,12 +242,19 @@ class GpuGraph:
             skip = np.ascontiguousarray(skip, dtype=np.uint8)
             skip_p = skip.ctypes.data
         gp = C.POINTER(_lib.Graph)()
-        if stages:
+        described = None
+        if stage_stats:
+            described = (_lib.Stats * (len(stages or "") + 1))()
+            _check(_lib.lib().katome_build_packed_staged_stats(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p,
+                                                               (stages or "").encode(), original_genome_length, described, C.byref(gp)))
+        elif stages:
             _check(_lib.lib().katome_build_packed_staged(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, stages.encode(),
                                                          original_genome_length, C.byref(gp)))
         else:
             _check(_lib.lib().katome_build_packed(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, C.byref(gp)))
         g = cls(gp)
+        if described is not None:
+            g.stage_stats = [collection_stats(st) for st in described]
         return g, g.read_bytes
 
     # ---- Stats<CollectionStats> (stats/collections.rs:137-168) ---------------------------------
@@ -235,11 +263,7 @@ class GpuGraph:
         if self._stats is None:
             st = _lib.Stats()
             _check(_lib.lib().katome_graph_stats(self._gptr, C.byref(st)))
-            self._stats = CollectionStats(
-                node_count=st.node_count, edge_count=st.edge_count, max_edge_weight=st.max_edge_weight,
-                avg_edge_weight=st.avg_edge_weight, max_in_degree=st.max_in_degree, max_out_degree=st.max_out_degree,
-                avg_out_degree=st.avg_out_degree, incoming_vert_count=st.incoming_vert_count,
-                outgoing_vert_count=st.outgoing_vert_count, capacity=(self.n_nodes, self.n_edges))
+            self._stats = collection_stats(st, capacity=(self.n_nodes, self.n_edges))
         return self._stats
 
     # ---- helpers for parity checks --------------------------------------------------------------

@@ -1627,6 +1627,26 @@ int katome_dev_current_graph(katome_builder* b, katome_dev_graph* out) {
     return KATOME_OK;
 }
 
+// Stats<CollectionStats>::stats (stats/collections.rs:137-168) and the weight spectrum of the finalized graph as it stands;
+// nothing in the builder changes
+int katome_dev_graph_stats(katome_builder* b, katome_stats* out, void* stream_) {
+    if (!b || !out) { set_error("null argument"); return KATOME_E_ARG; }
+    if (!b->finalized) { set_error("graph_stats: call katome_dev_finalize first"); return KATOME_E_ARG; }
+    hipStream_t stream = (hipStream_t)stream_;
+    KCHECK_HIP(hipSetDevice(b->s.device));
+    PhaseScope ps(b->prof, PH_GRAPH_STATS, stream);
+    return dev_graph_stats(b->edge_src.as<u64>(), b->edge_dst.as<u64>(), b->edge_weight.as<u32>(), b->n_edges, b->n_nodes, out, stream);
+}
+int katome_dev_weight_spectrum(katome_builder* b, uint64_t* bins, uint32_t n_bins, void* stream_) {
+    if (!b) { set_error("null argument"); return KATOME_E_ARG; }
+    KCHECK(check_spectrum_bins(bins, n_bins));
+    if (!b->finalized) { set_error("weight_spectrum: call katome_dev_finalize first"); return KATOME_E_ARG; }
+    hipStream_t stream = (hipStream_t)stream_;
+    KCHECK_HIP(hipSetDevice(b->s.device));
+    PhaseScope ps(b->prof, PH_WEIGHT_SPECTRUM, stream);
+    return dev_weight_spectrum(b->edge_weight.as<u32>(), b->n_edges, bins, n_bins, stream);
+}
+
 int katome_builder_counts(katome_builder* b, uint64_t* out8) {
     if (!b || !out8) { set_error("null argument"); return KATOME_E_ARG; }
     out8[0] = b->stat_tiles; out8[1] = b->stat_tile_slots; out8[2] = b->stat_kmers; out8[3] = b->stat_kmer_slots;

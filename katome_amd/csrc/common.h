@@ -98,6 +98,8 @@ enum Phase { PH_EXTRACT, PH_REGION_ORDER, PH_INSERT, PH_EMIT_EDGES, PH_SORT_EDGE
              K_SORT_SCATTER, K_SORT_HIST, K_RUN_SORT, K_HASH_SCATTER, K_HASH_HIST, K_OWNER_SCATTER, K_OWNER_HIST, K_PASS_OFFSETS,
              K_RECORDS, K_GROUP_INDEX, K_LDS_COUNT, K_SRC_IDS, K_DST_MERGE, K_EXPAND, K_SORT_SCATTER_KEYS, K_RUN_SORT_KEYS,
              K_TILE_HASH_SCATTER, K_TILE_HASH_HIST, K_TILE_RECORDS, K_TILE_GROUP_INDEX, K_TILE_LDS_COUNT, K_HALF_MERGE, K_GROUP_MERGE,
+             // (appended: the indices above are what callers of katome_phase_name have seen so far)
+             PH_GRAPH_STATS, PH_WEIGHT_SPECTRUM, K_STATS_DEGREES, K_STATS_WEIGHTS, K_STATS_NODES, K_SPECTRUM,
              PH_COUNT };
 static const char* const PHASE_NAMES[PH_COUNT] = {
     "extract", "region_order", "insert", "emit_edges", "sort_edges", "node_set", "rank", "labels", "insert_tiles", "expand_tiles",
@@ -111,7 +113,8 @@ static const char* const PHASE_NAMES[PH_COUNT] = {
     // (the same kernels counting a TILE level by sorting -- other record sizes, so timed apart: TileLevelScope)
     "k:radix_scatter_kernel<HashDigit> (tile records)", "k:radix_hist_kernel<HashDigit> (tile records)", "k:tiles_to_records_kernel (tile records)",
     "k:hash_group_index_kernel (tile records)", "k:lds_count_kernel (tile records)", "k:half_merge_kernel",
-    "k:group_merge_kernel"};
+    "k:group_merge_kernel",
+    "graph_stats", "weight_spectrum", "k:stats_degree_kernel", "k:stats_weight_kernel", "k:stats_node_kernel", "k:spectrum_kernel"};
 struct Profiler {
     bool on = false;
     struct Ev { int phase; hipEvent_t a, b; uint64_t work; };      // work: elements the launch processed (K_* entries)
@@ -342,6 +345,18 @@ int dev_standardize_scale(uint32_t* weight, uint64_t E, uint64_t original_genome
 int dev_weight_sums(const uint32_t* weight, uint64_t E, uint32_t threshold, uint64_t sums[2], hipStream_t stream);
 double standardization_ratio(uint64_t original_genome_length, uint32_t k, const uint64_t sums[2]);
 int dev_scale_weights(uint32_t* weight, uint64_t E, double p, uint32_t threshold, hipStream_t stream);
+
+// stats.hip: Stats<CollectionStats> for PtGraph (stats/collections.rs:137-168) and the weight spectrum
+int dev_graph_stats(const uint64_t* src, const uint64_t* dst, const uint32_t* weight, uint64_t E, uint64_t N, katome_stats* out, hipStream_t stream);
+int check_spectrum_bins(const uint64_t* bins, uint32_t n_bins);       // 2 <= n_bins <= 16384 and somewhere to put them, else KATOME_E_ARG
+int dev_weight_spectrum(const uint32_t* weight, uint64_t n, uint64_t* bins, uint32_t n_bins, hipStream_t stream);      // (bins: host)
+// their parts, for the sharded form (dist_stats.hip), which reduces over all ranks in between.  d_res: STATS_WORDS u64 on the
+// device, zeroed by the caller: {weight sum, max weight, max in-degree, max out-degree, nodes without in-edges, nodes without
+// out-edges, out-degree sum}; d_deg: one word per node, in-degree in the low half, out-degree in the high half
+constexpr int STATS_WORDS = 8;
+int dev_weight_max_sum(const uint32_t* weight, uint64_t n, uint64_t* d_res, hipStream_t stream);
+int dev_degree_reduce(const uint64_t* d_deg, uint64_t N, uint64_t* d_res, hipStream_t stream);
+void fill_stats(uint64_t n_nodes, uint64_t n_edges, const uint64_t res[STATS_WORDS], katome_stats* out);
 
 // shrink.hip: Shrinkable::shrink (shrinker.rs:165-209) on a finalized graph; the result lives in its own buffers
 struct ShrinkInput {

@@ -177,7 +177,12 @@ struct ShardedStages {
     int weak_edges() const { return katome_dist_prune_weak_edges(d, min_weight, g, stream); }
     int edges() const { return katome_dist_standardize_edges(d, genome_len, min_weight, g, stream); }
 };
-template <class Ops> static int run_stages(const char* stages, const Ops& ops) {
+// `at_stage` (optional) is called with 0 before the first stage and with i after the i-th: where assemble_with_graph logs the
+// graph (graph.log_stats(), asm/basic_assembler.rs:58-75)
+struct NoStageHook { int operator()(size_t) const { return KATOME_OK; } };
+template <class Ops, class Hook = NoStageHook> static int run_stages(const char* stages, const Ops& ops, const Hook& at_stage = Hook()) {
+    KCHECK(at_stage(0));
+    size_t done = 0;
     for (const char* st = stages ? stages : ""; *st; ++st) {
         switch (*st) {
             case 'd': KCHECK(ops.dead_paths()); break;
@@ -186,18 +191,22 @@ template <class Ops> static int run_stages(const char* stages, const Ops& ops) {
             case 'e': KCHECK(ops.edges()); break;
             default: set_error("unknown stage '%c' (d, c, w, e)", *st); return KATOME_E_ARG;      // (on the sharded graph: the same on every rank)
         }
+        KCHECK(at_stage(++done));
     }
     return KATOME_OK;
 }
 
-static int graph_to_host(katome_builder* b, uint64_t read_bytes, katome_graph** out, const char* stages = nullptr, uint64_t genome_len = 0) {
+// (stage_stats: the caller's strlen(stages) + 1 entries, filled on the device as the stages go by)
+static int graph_to_host(katome_builder* b, uint64_t read_bytes, katome_graph** out, const char* stages = nullptr, uint64_t genome_len = 0,
+                         katome_stats* stage_stats = nullptr) {
     katome_dev_graph dg;
     if (stages && *stages && !b->first_seen) { set_error("stages after the build need KATOME_FLAG_FIRST_SEEN_ORDER"); return KATOME_E_ARG; }
     build_lap("counting (H2D, kernels)");
     KCHECK(katome_dev_finalize(b, &dg, nullptr));
     build_lap("finalize");
     if (b->s.flags & KATOME_FLAG_REMOVE_DEAD_PATHS) KCHECK(katome_dev_remove_dead_paths(b, &dg, nullptr, nullptr));
-    KCHECK(run_stages(stages, BuilderStages{b, genome_len}));
+    KCHECK(run_stages(stages, BuilderStages{b, genome_len},
+                      [&](size_t i) { return stage_stats ? katome_dev_graph_stats(b, &stage_stats[i], nullptr) : KATOME_OK; }));
     KCHECK(katome_dev_current_graph(b, &dg));
     build_lap("stages after the build");
     GraphOwner* o = nullptr;
@@ -244,8 +253,9 @@ struct Finish {
     katome_graph** graph; katome_contigs** contigs;
     const char* stages = nullptr; uint64_t genome_len = 0;
     uint32_t shrink_mode = KATOME_SHRINK_AUTO;
+    katome_stats* stage_stats = nullptr;      // katome_build_*_staged_stats: the graph described before the first stage and after each
     int operator()(katome_builder* b, uint64_t read_bytes) const {
-        return contigs ? contigs_to_host(b, read_bytes, contigs, shrink_mode) : graph_to_host(b, read_bytes, graph, stages, genome_len);
+        return contigs ? contigs_to_host(b, read_bytes, contigs, shrink_mode) : graph_to_host(b, read_bytes, graph, stages, genome_len, stage_stats);
     }
 };
 
@@ -441,7 +451,16 @@ static int rank_build(MultiBuild& mb, int r, int n, katome_dist_builder* d, cons
     if (route.gathers(g.total_edges, g.total_nodes)) return gathered_finish(mb, r, d, stream);
     if (route.sharded_dead_paths()) KCHECK(katome_dist_remove_dead_paths(d, &g, nullptr, stream));
     if (route.sharded_shrink) return shrunk_to_host(d, mb.shrunk[r], stream);
-    if (route.sharded_stage_letters()) KCHECK(run_stages(mb.finish.stages, ShardedStages{d, &g, mb.s->min_weight, mb.finish.genome_len, stream}));
+    // (the whole graph's stats are the same on every rank: rank 0 writes the caller's array)
+    auto describe = [&](size_t i) -> int {
+        if (!mb.finish.stage_stats) return KATOME_OK;
+        katome_stats st;
+        KCHECK(katome_dist_graph_stats(d, &st, stream));
+        if (r == 0) mb.finish.stage_stats[i] = st;
+        return katome_dist_current_graph(d, &g);      // (the call may have rebuilt the links, which re-orders the rank's node arrays)
+    };
+    if (route.sharded_stage_letters()) KCHECK(run_stages(mb.finish.stages, ShardedStages{d, &g, mb.s->min_weight, mb.finish.genome_len, stream}, describe));
+    else KCHECK(describe(0));
     mb.n_edges[r] = g.n_edges;
     KCHECK(meet(mb));
     if (r == 0) alloc_shared_graph(mb, g);
@@ -643,6 +662,14 @@ int katome_build_packed_staged(const katome_settings* s, const uint8_t* packed, 
     f.stages = stages; f.genome_len = original_genome_length;
     return build_packed_impl(s, packed, n_reads, read_len, skip, f);
 }
+int katome_build_packed_staged_stats(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip,
+                                     const char* stages, uint64_t original_genome_length, katome_stats* stage_stats, katome_graph** out) {
+    if (!out || !stage_stats) { set_error("null argument"); return KATOME_E_ARG; }
+    *out = nullptr;
+    Finish f{out, nullptr};
+    f.stages = stages; f.genome_len = original_genome_length; f.stage_stats = stage_stats;
+    return build_packed_impl(s, packed, n_reads, read_len, skip, f);
+}
 int katome_shrink_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len,
                          const uint8_t* skip, katome_contigs** out) {
     if (!out) { set_error("null argument"); return KATOME_E_ARG; }
@@ -784,6 +811,14 @@ int katome_build_files_staged(const katome_settings* s, const char* const* paths
     *out = nullptr;
     Finish f{out, nullptr};
     f.stages = stages; f.genome_len = original_genome_length;
+    return build_files_impl(s, paths, n_paths, f);
+}
+int katome_build_files_staged_stats(const katome_settings* s, const char* const* paths, size_t n_paths, const char* stages,
+                                    uint64_t original_genome_length, katome_stats* stage_stats, katome_graph** out) {
+    if (!out || !stage_stats) { set_error("null argument"); return KATOME_E_ARG; }
+    *out = nullptr;
+    Finish f{out, nullptr};
+    f.stages = stages; f.genome_len = original_genome_length; f.stage_stats = stage_stats;
     return build_files_impl(s, paths, n_paths, f);
 }
 int katome_shrink_files(const katome_settings* s, const char* const* paths, size_t n_paths, katome_contigs** out) {

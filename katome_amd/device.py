@@ -7,10 +7,11 @@ pt_graph.rs:277-315,172-198,333-345): extract -> insert -> finalize.
 import ctypes as C
 import weakref
 
+import numpy as np
 import torch
 
 from . import _lib
-from .build import KatomePanic, make_settings
+from .build import KatomePanic, collection_stats, make_settings
 
 
 def _check(status):
@@ -310,6 +311,19 @@ class Builder(_ViewOwner):
         _check(_lib.lib().katome_dev_current_graph(self._h, C.byref(dg)))
         return DeviceGraph(dg, self, self.tdev)
 
+    def stats(self):
+        """Stats<CollectionStats>::stats (stats/collections.rs:137-168) of the finalized graph as it stands, computed on the
+        device (katome_dev_graph_stats) -> build.CollectionStats"""
+        st = _lib.Stats()
+        _check(_lib.lib().katome_dev_graph_stats(self._h, C.byref(st), _stream()))
+        return collection_stats(st, capacity=(st.node_count, st.edge_count))
+
+    def weight_spectrum(self, n_bins):
+        """np.uint64[n_bins]: edges of weight w at [w], those of weight >= n_bins - 1 in the last bin (katome_dev_weight_spectrum)"""
+        bins = np.zeros(max(int(n_bins), 0), np.uint64)
+        _check(_lib.lib().katome_dev_weight_spectrum(self._h, bins.ctypes.data_as(_lib.u64p), n_bins, _stream()))
+        return bins
+
     def table_count(self):
         out = C.c_uint64()
         _check(_lib.lib().katome_dev_table_count(self._h, C.byref(out), _stream()))
@@ -416,6 +430,24 @@ def rank_in_sorted(sorted_keys, queries, key_bits, key_words, device=0):
     _check(_lib.lib().katome_dev_rank(device, _ptr(sorted_keys), ns, key_words, key_bits, _ptr(queries), nq, _ptr(out),
                                       _stream()))
     return out[:nq]
+
+
+def stats_arrays(edge_src, edge_dst, edge_weight, n_nodes, device=0):
+    """CollectionStats of a graph given as device arrays (int64 endpoints below n_nodes -- not checked --, int32/uint32 weights):
+    katome_dev_stats_arrays"""
+    st = _lib.Stats()
+    _check(_lib.lib().katome_dev_stats_arrays(device, _ptr(edge_src), _ptr(edge_dst), _ptr(edge_weight), edge_src.numel(), n_nodes,
+                                              C.byref(st), _stream()))
+    return collection_stats(st, capacity=(st.node_count, st.edge_count))
+
+
+def weight_spectrum_arrays(weight, n_bins, device=0):
+    """np.uint64[n_bins] histogram of int32/uint32 weights on the device, weights >= n_bins - 1 in the last bin:
+    katome_dev_weight_spectrum_arrays"""
+    bins = np.zeros(max(int(n_bins), 0), np.uint64)
+    _check(_lib.lib().katome_dev_weight_spectrum_arrays(device, _ptr(weight), weight.numel(), bins.ctypes.data_as(_lib.u64p), n_bins,
+                                                        _stream()))
+    return bins
 
 
 def release_cache(device=0):

@@ -7,11 +7,12 @@ A single-process caller (the Rust shim of INTEGRATION.md) needs none of this: it
 """
 import ctypes as C
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
 from . import _lib
-from .build import KatomePanic, make_settings
+from .build import KatomePanic, collection_stats, make_settings
 from .device import Builder, DeviceContigs, _ViewOwner, _ptr, _stream, _view
 
 
@@ -315,6 +316,19 @@ class ShardedBuilder(_ViewOwner):
         c, st = _lib.DistContigs(), _lib.DistShrinkStats()
         _check(_lib.lib().katome_dist_shrink(self._h, C.byref(c), C.byref(st), _stream()))
         return RankContigs(c, st, self, self.tdev)
+
+    def stats(self):
+        """CollectionStats of the WHOLE graph as it stands, the same on every rank, no gather (katome_dist_graph_stats).
+        May re-order this rank's node arrays (the links are rebuilt where a stage dropped them): take graph() again afterwards"""
+        st = _lib.Stats()
+        _check(_lib.lib().katome_dist_graph_stats(self._h, C.byref(st), _stream()))
+        return collection_stats(st, capacity=(st.node_count, st.edge_count))
+
+    def weight_spectrum(self, n_bins):
+        """np.uint64[n_bins] weight spectrum of the WHOLE graph on every rank (katome_dist_weight_spectrum)"""
+        bins = np.zeros(max(int(n_bins), 0), np.uint64)
+        _check(_lib.lib().katome_dist_weight_spectrum(self._h, bins.ctypes.data_as(_lib.u64p), n_bins, _stream()))
+        return bins
 
     def graph(self):
         """this rank's share as it stands (katome_dist_current_graph)"""
