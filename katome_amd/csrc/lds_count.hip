@@ -24,9 +24,16 @@ namespace katome {
 __device__ unsigned long long lc_phase_cycles[16];
 #define LC_PHASE_BEGIN() unsigned long long lc_t0 = clock64()
 #define LC_PHASE(i) do { if (threadIdx.x == 0) { const unsigned long long lc_t = clock64(); atomicAdd(&lc_phase_cycles[i], lc_t - lc_t0); lc_t0 = lc_t; } } while (0)
+// (the ordered kernel's phase 14 once more, step by step: the kept count and lds_order.h's count, scan, place, rank and write --
+// katome_debug_lo_phases, tools/lds_order_phases.py)
+__device__ unsigned long long lo_phase_cycles[8];
+#define LO_PHASE_BEGIN() unsigned long long lo_t0 = clock64()
+#define LO_PHASE(i) do { if (threadIdx.x == 0) { const unsigned long long lo_t = clock64(); atomicAdd(&lo_phase_cycles[i], lo_t - lo_t0); lo_t0 = lo_t; } } while (0)
 #else
 #define LC_PHASE_BEGIN() do {} while (0)
 #define LC_PHASE(i) do {} while (0)
+#define LO_PHASE_BEGIN() do {} while (0)
+#define LO_PHASE(i) do {} while (0)
 #endif
 // LDS table: 8 B key + 4 B count per slot, LC_THREADS x PER slots (every thread reads PER slots out).  PER = 13: 13312 slots =
 // 156 KiB of the CU's 160 (one workgroup of 1024 per CU either way): groups of 22 k records (2^16 groups at C3) go through in 3
@@ -325,15 +332,24 @@ __global__ __launch_bounds__(LC_THREADS) void lds_count_packed_kernel(const u64*
 // one visit per record).  The records are in their representative orientation (kmer_bits.h rep_orientation; as they are with one
 // strand) and ordered by their leading 16 key bits (dev_key_order), so group g is the key range of prefix g.  The insert loop is
 // lds_count_packed_kernel's, with the key's low 2k - 16 bits in the slot instead of the hash's (the probe sequence still comes from the
-// hash).  At read-out the group's kept keys are put in key order in the table's own LDS -- a counting sort on the remainder's top 11
-// bits into 2048 buckets, then every key is placed by counting the keys of its bucket (about 6 at C3) below it -- and leave as two lists:
+// hash).  At read-out the group's kept keys are put in key order in the table's own LDS (lds_order.h: a counting sort on the
+// remainder's top bits, then every key is placed by counting the keys of its bucket below it) and leave as two lists:
 //   S1, the representatives, ascending, from the group's first record on (s1_key + index[g]: fixed before the count, so the groups
 //       stay in key order; a group has no more distinct keys than records), their number in group_count[g];
 //   S2 (both strands), their reverse complements, behind a cursor in no order.
 // group_merge_kernel (radix.hip) orders S2 group by group and merges it with S1 (half_merge_kernel when S2 is sorted in full).
+// The buckets: the table's entries are in registers while they are ordered, so its LDS is free but for the kept entries' places
+// [0, total).  Where total leaves the table's tail free (LO_FINE_MAX; always at C3, 12 300 of 19 456), 8192 buckets of 1.5 keys have
+// their counters there, in the slots from LO_FINE_SLOT on, which their owners clear as they read them out; a fuller table takes the 2048
+// buckets behind the table.  total is known before the ordering starts: the kept entries are added up across the barrier that the
+// tail's reuse needs anyway.
 // err 5 / err 3 as in lds_count_packed_kernel: the caller then counts the usual way.
-constexpr u32 LO_BUCKETS = LDS_ORDER_BUCKETS;
 static_assert(LC_THREADS == LDS_ORDER_THREADS, "the read-out orders with lds_order.h");
+constexpr u32 LO_COARSE_WORDS = (lds_order_words(LDS_ORDER_COARSE_BITS) + 1) / 2 * 2;                      // (u32 words behind the table)
+constexpr u32 LO_FINE_SLOT = (LP_SLOTS - (lds_order_words(LDS_ORDER_FINE_BITS) + 1) / 2) / 2 * 2;          // (an even slot: 16-byte aligned)
+constexpr u32 LO_FINE_MAX = LO_FINE_SLOT;
+constexpr size_t LO_LDS = (size_t)LP_SLOTS * 8 + LO_COARSE_WORDS * 4;
+static_assert((LP_SLOTS - LO_FINE_SLOT) * 2 >= lds_order_words(LDS_ORDER_FINE_BITS), "the fine buckets fit the table's tail");
 template <bool RC>
 __global__ __launch_bounds__(LC_THREADS) void lds_count_ordered_kernel(const u64* keys, const u32* wts, const u64* __restrict__ index, u32 k,
                                                                         u32 min_weight, u64* s1_key, u32* s1_w, u32* group_count, u64* s2_key,
@@ -341,11 +357,15 @@ __global__ __launch_bounds__(LC_THREADS) void lds_count_ordered_kernel(const u64
                                                                         unsigned long long* distinct, u32* err, u32 probe_limit) {
     extern __shared__ unsigned long long lc_mem[];
     unsigned long long* slot = lc_mem;                                   // [LP_SLOTS]: remainder << 16 | count; then the kept ones in key order
-    u32* bucket = reinterpret_cast<u32*>(lc_mem + LP_SLOTS);             // [LO_BUCKETS / 2]: counters of buckets 2i (low half), 2i + 1
+    u32* bucket = reinterpret_cast<u32*>(lc_mem + LP_SLOTS);             // [LO_COARSE_WORDS]: the 2048 buckets of a table too full for ...
+    u32* fine = reinterpret_cast<u32*>(lc_mem + LO_FINE_SLOT);           // ... the 8192 in the table's tail
     __shared__ u32 wtot[LC_THREADS / 64];
     __shared__ unsigned long long base_sh;
+    __shared__ u32 kept_sh;
     const u32 tid = threadIdx.x, lane = tid & 63;
-    const u32 rem_bits = 2 * k - 16, bshift = rem_bits > 11 ? rem_bits - 11 : 0;            // (bucket: the remainder's top 11 bits)
+    const u32 rem_bits = 2 * k - 16;
+    const u32 bshift_c = rem_bits > LDS_ORDER_COARSE_BITS ? rem_bits - LDS_ORDER_COARSE_BITS : 0;          // (bucket: the remainder's top bits)
+    const u32 bshift_f = rem_bits > LDS_ORDER_FINE_BITS ? rem_bits - LDS_ORDER_FINE_BITS : 0;
     const u64 REM = (1ull << rem_bits) - 1;
     u32 my_distinct = 0;
     LC_PHASE_BEGIN();
@@ -354,6 +374,7 @@ __global__ __launch_bounds__(LC_THREADS) void lds_count_ordered_kernel(const u64
         if (lo == hi) continue;
         for (u32 i = tid; i < LP_SLOTS; i += LC_THREADS) slot[i] = 0ull;
         bucket[tid] = 0u;
+        if (tid == 0) kept_sh = 0u;
         __syncthreads();
         LC_PHASE(12);
         constexpr u32 LU = KATOME_LC_LU;
@@ -398,18 +419,32 @@ __global__ __launch_bounds__(LC_THREADS) void lds_count_ordered_kernel(const u64
         __syncthreads();
         LC_PHASE(13);
         // read-out into registers; the table's LDS then takes the kept entries in bucket order
+        LO_PHASE_BEGIN();
+        u32 rt = tid;                                         // (through an empty asm: nothing of the read-out is hoisted out of the group loop, lds_order.h)
+        asm volatile("" : "+v"(rt));
         unsigned long long v[LP_PER]; u32 keep = 0;
 #pragma unroll
         for (u32 j = 0; j < LP_PER; ++j) {
-            v[j] = slot[tid * LP_PER + j];
+            v[j] = slot[rt * LP_PER + j];
             if (v[j]) { ++my_distinct; if (((u32)v[j] & 0xFFFFu) >= min_weight) keep |= 1u << j; }      // Clean::remove_weak_edges
         }
+        if ((rt + 1) * LP_PER > LO_FINE_SLOT) {               // (the fine buckets' counters: slots this thread has just read)
+#pragma unroll
+            for (u32 j = 0; j < LP_PER; ++j) if (rt * LP_PER + j >= LO_FINE_SLOT) slot[rt * LP_PER + j] = 0ull;
+        }
+        const u32 wave_kept = wave_sum((u32)__popc(keep));
+        if (lane == 0 && wave_kept) atomicAdd(&kept_sh, wave_kept);
+        __syncthreads();
+        LO_PHASE(0);
         // the kept ones into key order in the table's LDS (lds_order.h); the group's S2 room is reserved once their number is known
-        const u32 total = lds_order_entries<LP_PER>(v, keep, slot, bucket, wtot, bshift, [&](u32 t) {
+        const auto reserve = [&](u32 t) {
             if (tid == 0) { group_count[g] = t; base_sh = t ? atomicAdd(cursor, (unsigned long long)t) : 0ull; }
-        });
+        };
+        const auto stamp = [&](u32 i) { LO_PHASE(1 + i); (void)i; };
+        const u32 total = kept_sh <= LO_FINE_MAX ? lds_order_entries<LP_PER, LDS_ORDER_FINE_BITS>(v, keep, slot, fine, wtot, bshift_f, reserve, stamp)
+                                                 : lds_order_entries<LP_PER, LDS_ORDER_COARSE_BITS>(v, keep, slot, bucket, wtot, bshift_c, reserve, stamp);
         LC_PHASE(14);
-        for (u32 i = tid; i < total; i += LC_THREADS) {
+        for (u32 i = rt; i < total; i += LC_THREADS) {
             const unsigned long long e = slot[i];
             Key<1> x; x.w[0] = ((u64)g << rem_bits) | (e >> 16);
             const u32 c = (u32)e & 0xFFFFu;
@@ -1184,7 +1219,7 @@ static int ordered_count(DevBuf& keys, DevBuf& weights, uint64_t n, uint32_t k, 
     KCHECK(aux.buf.alloc(64));
     LcResult r;
     KCHECK(with_bool(rc, [&](auto rcv) {
-        return lc_launch(aux, lds_count_ordered_kernel<decltype(rcv)::value>, (size_t)LP_SLOTS * 8 + LO_BUCKETS * 2, n, r, ko, wo, hs.group_first.as<u64>(), k,
+        return lc_launch(aux, lds_count_ordered_kernel<decltype(rcv)::value>, LO_LDS, n, r, ko, wo, hs.group_first.as<u64>(), k,
                          min_weight, hs.s1_key.as<u64>(), hs.s1_w.as<u32>(), hs.group_count.as<u32>(), hs.s2_key.as<u64>(), hs.s2_w.as<u32>(),
                          hs.s2_digit.as<uint8_t>(), s2_cap, aux.cursor(), aux.distinct(), aux.err(), std::min<u32>(lc_probe_limit(), LP_SLOTS));
     }));
@@ -1456,5 +1491,14 @@ extern "C" int katome_debug_lc_phases(uint64_t* out16) {
     for (int i = 0; i < 16; ++i) out16[i] = h[i];
     memset(h, 0, sizeof h);
     return hipMemcpyToSymbol(HIP_SYMBOL(katome::lc_phase_cycles), h, sizeof h) == hipSuccess ? 0 : -1;
+}
+// (the ordered kernel's read-out step by step: 0 the table into registers and the kept count, 1-5 lds_order.h's count, scan, place, rank
+// and write; and back to zero)
+extern "C" int katome_debug_lo_phases(uint64_t* out8) {
+    unsigned long long h[8];
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(katome::lo_phase_cycles), sizeof h) != hipSuccess) return -1;
+    for (int i = 0; i < 8; ++i) out8[i] = h[i];
+    memset(h, 0, sizeof h);
+    return hipMemcpyToSymbol(HIP_SYMBOL(katome::lo_phase_cycles), h, sizeof h) == hipSuccess ? 0 : -1;
 }
 #endif

@@ -1060,13 +1060,15 @@ int dev_half_merge(const uint64_t* a_key, const uint32_t* a_w, const uint64_t* a
 // (dev_key_order), b_first[g] .. b_first[g + 1] of group g in no order.  A workgroup takes group g and
 //   loads   its B keys into registers, GM_PER to a thread, as remainder << 16 | weight: 2k - 16 <= 46 bits of remainder, and a B
 //           weight is its representative's count, below 2^16 in the ordered count.  At most GM_CAP of them (the caller checks);
-//   orders  them in LDS with the count's read-out (lds_order.h -- the remainders of a group are distinct);
+//   orders  them in LDS with the count's read-out (lds_order.h -- the remainders of a group are distinct), in 8192 buckets;
 //   merges  them with A[g], in the same form, through an LDS ring of GM_RING = 2 GM_STEP entries.  Every step places GM_STEP outputs
 //           (or what is left), GM_MI to a thread after a merge-path search; they are final when the ring holds GM_STEP unconsumed
 //           entries or A's end, since B is all in LDS (as in half_merge_kernel).  A is read GM_STEP entries ahead into registers:
 //           a block goes into the ring once there is room, and the next block's loads are in flight during the step's merge.
 // LDS: 160 KiB -- B (the last 16 words hold the scan's wave totals, the step's A count and HEADS' words, so GM_CAP is 16 short of
-// 16 Ki) and the ring, whose first 4 KiB hold the buckets while B is ordered.  One workgroup of 1024 per CU.
+// 16 Ki) and the ring, whose first half holds the buckets while B is ordered.  One workgroup of 1024 per CU.
+// (-DKATOME_LC_PHASES, experiment builds: the shader clocks of thread 0 per phase -- 0 B's load, 1-5 the ordering's count, scan, place,
+// rank and write, 6 the merge steps --, read through katome_debug_gm_phases)
 // HEADS: the kernel also counts, per block of SRC_HEAD_BLOCK (source_ids_t's UNIQ_TILE) output edges, the source run heads among them (is_src_head: key >> 2 differs
 // from the edge before, or edge 0) into head_counts -- what src_count_kernel would read the whole list again for.  A step's
 // outputs [o, o + c), c <= GM_STEP = SRC_HEAD_BLOCK, lie in at most two such blocks; blocks straddle groups that other workgroups merge,
@@ -1082,7 +1084,15 @@ constexpr u32 SRC_HEAD_BLOCK = 2048;          // edges to a count of source_ids_
 // step before by step parity (two u64, so on an even u32) and the step's two head counts
 constexpr u32 GM_SP_WTOT = 0, GM_SP_USED_A = GM_SP_WTOT + GM_THREADS / 64, GM_SP_LAST_E = (GM_SP_USED_A + 1 + 1) / 2 * 2,
               GM_SP_STEP_HEADS = GM_SP_LAST_E + 2 * 2, GM_SP_END = GM_SP_STEP_HEADS + 2;
-static_assert(LDS_ORDER_BUCKETS * 2 <= GM_RING * 8 && GM_SP_END <= 2 * (GM_WORDS - GM_CAP), "aliases in the merge's LDS");
+static_assert(lds_order_words(LDS_ORDER_FINE_BITS) * 4 <= GM_RING * 8 && GM_SP_END <= 2 * (GM_WORDS - GM_CAP), "aliases in the merge's LDS");
+#ifdef KATOME_LC_PHASES
+__device__ unsigned long long gm_phase_cycles[8];
+#define GM_PHASE_BEGIN() unsigned long long gm_t0 = clock64()
+#define GM_PHASE(i) do { if (threadIdx.x == 0) { const unsigned long long gm_t = clock64(); atomicAdd(&gm_phase_cycles[i], gm_t - gm_t0); gm_t0 = gm_t; } } while (0)
+#else
+#define GM_PHASE_BEGIN() do {} while (0)
+#define GM_PHASE(i) do {} while (0)
+#endif
 template <bool HEADS>
 __global__ __launch_bounds__(GM_THREADS) void group_merge_kernel(const u64* __restrict__ a_key, const u32* __restrict__ a_w, const u64* __restrict__ a_first,
                                                                    const u32* __restrict__ a_count, const u64* __restrict__ a_off, const u64* __restrict__ b_key,
@@ -1099,10 +1109,11 @@ __global__ __launch_bounds__(GM_THREADS) void group_merge_kernel(const u64* __re
     static_assert(!HEADS || GM_STEP == SRC_HEAD_BLOCK, "a step's outputs lie in at most two blocks of head_counts");
     if (HEADS && threadIdx.x < 2) step_heads[threadIdx.x] = 0u;          // (ordered before the first step by the barriers in between)
     unsigned long long* ring = gm_mem + GM_WORDS;                        // [GM_RING]: A
-    u32* bucket = reinterpret_cast<u32*>(ring);                          // [LDS_ORDER_BUCKETS / 2], while B is ordered
+    u32* bucket = reinterpret_cast<u32*>(ring);                          // [lds_order_words(LDS_ORDER_FINE_BITS)], while B is ordered
     const u32 tid = threadIdx.x;
-    const u32 rem_bits = 2 * k - 16, bshift = rem_bits > 11 ? rem_bits - 11 : 0;            // (bucket: the remainder's top 11 bits)
+    const u32 rem_bits = 2 * k - 16, bshift = rem_bits > LDS_ORDER_FINE_BITS ? rem_bits - LDS_ORDER_FINE_BITS : 0;      // (bucket: the remainder's top 13 bits)
     const u64 REM = (1ull << rem_bits) - 1;
+    GM_PHASE_BEGIN();
     for (u32 g = blockIdx.x; g < (1u << 16); g += gridDim.x) {
         const u64 b0 = b_first[g], a0 = a_first[g];
         const u32 na = a_count[g], nb = (u32)(b_first[g + 1] - b0);
@@ -1115,9 +1126,10 @@ __global__ __launch_bounds__(GM_THREADS) void group_merge_kernel(const u64* __re
             v[j] = 0;
             if (i < nb) { v[j] = ((b_key[b0 + i] & REM) << 16) | b_w[b0 + i]; keep |= 1u << j; }
         }
-        bucket[tid] = 0u;
+        reinterpret_cast<uint4*>(bucket)[tid] = make_uint4(0u, 0u, 0u, 0u);
         __syncthreads();                                  // (the last group's merge is done with the ring and bs)
-        lds_order_entries<GM_PER>(v, keep, bs, bucket, wtot, bshift, [](u32) {});
+        GM_PHASE(0);
+        lds_order_entries<GM_PER, LDS_ORDER_FINE_BITS>(v, keep, bs, bucket, wtot, bshift, [](u32) {}, [&](u32 i) { GM_PHASE(1 + i); (void)i; });
         // A's next block [la, la + pn) in registers
         u64 pk[GM_PF]; u32 pw[GM_PF];
         u32 ca = 0, cb = 0, la = 0, pn = na < GM_STEP ? na : GM_STEP;          // A consumed and in the ring, B consumed
@@ -1188,6 +1200,7 @@ __global__ __launch_bounds__(GM_THREADS) void group_merge_kernel(const u64* __re
             ca += ua; cb += c - ua; o += c; ++step;
             __syncthreads();                                  // (used_a is read before the next step's last thread writes it)
         }
+        GM_PHASE(6);
     }
 }
 uint32_t dev_group_merge_cap() { return GM_CAP; }
@@ -2396,3 +2409,14 @@ int dev_labels(const uint64_t* d_edge_key, uint64_t n, uint32_t k, uint8_t* d_la
 }
 
 }  // namespace katome
+
+#ifdef KATOME_LC_PHASES
+// (experiment builds only: group_merge_kernel's clocks per phase, and back to zero)
+extern "C" int katome_debug_gm_phases(uint64_t* out8) {
+    unsigned long long h[8];
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(katome::gm_phase_cycles), sizeof h) != hipSuccess) return -1;
+    for (int i = 0; i < 8; ++i) out8[i] = h[i];
+    memset(h, 0, sizeof h);
+    return hipMemcpyToSymbol(HIP_SYMBOL(katome::gm_phase_cycles), h, sizeof h) == hipSuccess ? 0 : -1;
+}
+#endif
