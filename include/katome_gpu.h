@@ -679,6 +679,13 @@ int katome_dev_replay_node_removals64(int device, const uint64_t *d_die, uint64_
                                       uint64_t *d_move_from, uint64_t *counts, void *stream);
 /* exclusive prefix sums of m u32 counts as u64: d_offs[i] = counts[0] + .. + counts[i-1], d_offs[m] = the total   */
 int katome_dev_scan_counts(int device, const uint32_t *d_counts, uint64_t m, uint64_t *d_offs, void *stream);
+/* test entry: the (sub-window, count) records of a list of n_tiles tiles of tile_bases bases -- record p is sub-window p % span (k
+ * bases, starts `stride` apart) of tile p / span, canonical (rc) or in the representative orientation (rep) -- after their first
+ * partition pass, in d_keys / d_weights, and that pass's digit counts per sort tile in d_digit_counts ([tiles][256]).  fused: the pass
+ * cuts its records out of the list; otherwise they are written first and the pass reads them (synchronises)                         */
+int katome_dev_list_first_pass(int device, const uint64_t *d_tiles, const uint32_t *d_counts, uint64_t n_tiles, uint32_t tile_bases,
+                               uint32_t k, uint32_t span, uint32_t stride, int rc, int rep, int fused, uint64_t *d_keys,
+                               uint32_t *d_weights, uint32_t *d_digit_counts, void *stream);
 /* in-place unique of sorted keys; returns the new count (synchronises)                     */
 int katome_dev_unique(int device, uint64_t *d_keys, uint64_t n, uint32_t key_words, uint64_t *n_out,
                       void *stream);

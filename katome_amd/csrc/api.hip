@@ -688,7 +688,7 @@ static int kmer_records_in_parts(katome_builder* b, const uint64_t* lk, const ui
 // the tile records are gone.  KATOME_E_UNSUPPORTED: a level could not be counted this way (or there is nothing to count) -- the
 // tile records, or the distinct big tiles with their counts, are in the tile table instead and the caller goes on in tables.
 int tile_recs_to_kmer_records(katome_builder* b, DevBuf& keys, DevBuf& weights, uint64_t* n_records, uint64_t extra_room, hipStream_t stream,
-                              DevBuf* first_counts, bool rep) {
+                              DevBuf* first_counts, bool rep, RecordSource* src) {
     *n_records = 0;
     const uint32_t k = b->s.k, span = b->span, tile_bases = k + span - 1, nwt = (uint32_t)key_words_for_k(tile_bases);
     b->span2 = mid_span(span);
@@ -725,12 +725,13 @@ int tile_recs_to_kmer_records(katome_builder* b, DevBuf& keys, DevBuf& weights, 
         DevBuf mk(stream), mw(stream);
         uint64_t n_mid = 0, n2 = 0, d2 = 0;
         DevBuf mid_counts(stream);        // (the first partition pass's digit counts per tile, made while the records are written)
+        RecordSource mid_src;             // (... or instead of them: that pass then cuts the records out of the list, which stays until the level is counted)
         // (input whose tiles hardly repeat -- thin coverage -- multiplies records level by level: a level that would not fit the card
         // by sorting is counted in a table, which takes its upserts in slot ranges of any size)
         if (sorted_fail("mid") || !level_fits(n1 * n_sub, (uint32_t)key_words_for_k(kk2), false, "mid tiles")) rc = KATOME_E_UNSUPPORTED;
         else {
-            KCHECK(table_list_to_records(lk, lw, n1, tile_bases, kk2, n_sub, b->span2, b->rc, mk, mw, &n_mid, stream, 0, &mid_counts));
-            rc = records_to_edges_sorted(mk, mw, n_mid, kk2, false, 0, t2k, t2w, &n2, &d2, stream, nullptr, mid_counts.as<u32>());
+            KCHECK(table_list_to_records(lk, lw, n1, tile_bases, kk2, n_sub, b->span2, b->rc, mk, mw, &n_mid, stream, 0, &mid_counts, false, &mid_src));
+            rc = records_to_edges_sorted(mk, mw, n_mid, kk2, false, 0, t2k, t2w, &n2, &d2, stream, nullptr, mid_counts.as<u32>(), nullptr, &mid_src);
         }
         if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
         if (rc == KATOME_E_UNSUPPORTED) {
@@ -767,7 +768,15 @@ int tile_recs_to_kmer_records(katome_builder* b, DevBuf& keys, DevBuf& weights, 
     }
     PhaseScope ps(b->prof, PH_EXPAND_TILES, stream);
     // (first_counts: for a caller that orders exactly these records by the whole k-mer's hash next -- table_list_to_records)
-    return table_list_to_records(lk, lw, n_last, last_bases, k, last_span, 1, b->rc, keys, weights, n_records, stream, extra_room, first_counts, rep);
+    KCHECK(table_list_to_records(lk, lw, n_last, last_bases, k, last_span, 1, b->rc, keys, weights, n_records, stream, extra_room, first_counts, rep, src));
+    if (src && src->pending) {
+        // the list has to outlive the first pass, which these locals do not: the source takes it and gives it up right after that pass
+        DevBuf& ok = b->span2 && t2k.p ? t2k : t1k; DevBuf& ow = b->span2 && t2w.p ? t2w : t1w;
+        src->own_tiles.stream = src->own_counts.stream = stream;
+        const size_t kbytes = ok.bytes, wbytes = ow.bytes;
+        src->own_tiles.adopt(ok.take(), kbytes); src->own_counts.adopt(ow.take(), wbytes);
+    }
+    return KATOME_OK;
 }
 
 // The k-mer level counted in order (lds_count.hip, lds_count_ordered_kernel): half of the edges leave the count sorted, the edge sort takes
@@ -1091,7 +1100,8 @@ static int edges_from_tile_recs(katome_builder* b, bool* counted, hipStream_t st
     DevBuf first_counts(stream);
     const bool half = half_sort_route(b);
     HalfSort hs;
-    int rc = tile_recs_to_kmer_records(b, rk, rw, &n_rec, n_rest, stream, &first_counts, half);
+    RecordSource src;          // (the k-mer records may be left to their first partition pass: see RecordSource)
+    int rc = tile_recs_to_kmer_records(b, rk, rw, &n_rec, n_rest, stream, &first_counts, half, &src);
     if (rc == KATOME_E_UNSUPPORTED) return KATOME_OK;          // (the tiles are in their table now, the table routes take it from there)
     if (rc != KATOME_OK) return rc;
     {
@@ -1099,10 +1109,11 @@ static int edges_from_tile_recs(katome_builder* b, bool* counted, hipStream_t st
         KCHECK(append_rest(b, rk, rw, &n_rec, n_rest, b->nw, half && b->rc, stream));
         rest_reset(b);
         const bool fail = sorted_fail("last");
+        if (fail) KCHECK(table_materialise_records(src));          // (the table wants the records)
         if (fail && half && b->rc) KCHECK(table_orient_records(rk.as<u64>(), n_rec, k, false, stream));     // (the table takes canonical k-mers)
         rc = fail ? KATOME_E_UNSUPPORTED
             : records_to_edges_sorted(rk, rw, n_rec, k, b->rc, b->prune_weight, b->edge_key, b->edge_weight, &b->n_edges, &distinct, stream, nullptr,
-                                      n_rest ? nullptr : first_counts.as<u32>(), half ? &hs : nullptr);
+                                      n_rest ? nullptr : first_counts.as<u32>(), half ? &hs : nullptr, &src);
         if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
     }
     if (rc != KATOME_OK) {
@@ -1774,6 +1785,13 @@ int katome_dev_scan_counts(int device, const uint32_t* d_counts, uint64_t m, uin
     KCHECK(use_device(device));
     if (!d_offs || (m && !d_counts)) { set_error("null argument"); return KATOME_E_ARG; }
     return dev_scan_counts(d_counts, m, d_offs, (hipStream_t)stream);
+}
+int katome_dev_list_first_pass(int device, const uint64_t* d_tiles, const uint32_t* d_counts, uint64_t n_tiles, uint32_t tile_bases, uint32_t k, uint32_t span,
+                               uint32_t stride, int rc, int rep, int fused, uint64_t* d_keys, uint32_t* d_weights, uint32_t* d_digit_counts, void* stream) {
+    KCHECK(use_device(device));
+    if (n_tiles && (!d_tiles || !d_counts || !d_keys || !d_weights || !d_digit_counts)) { set_error("null argument"); return KATOME_E_ARG; }
+    if (!span || tile_bases < k || (uint64_t)stride * (span - 1) + k > tile_bases || k < 9 || tile_bases > 64) { set_error("first pass off a list: the sub-windows do not lie in the tile"); return KATOME_E_ARG; }
+    return dev_list_first_pass(d_tiles, d_counts, n_tiles, tile_bases, k, span, stride, rc != 0, rep != 0, fused != 0, d_keys, d_weights, d_digit_counts, (hipStream_t)stream);
 }
 int katome_dev_unique(int device, uint64_t* d_keys, uint64_t n, uint32_t key_words, uint64_t* n_out, void* stream) {
     KCHECK(use_device(device));

@@ -98,7 +98,7 @@ int keep_tile_recs(katome_builder* b, const uint64_t* d_records, uint64_t n, uin
 int tile_recs_valid(katome_builder* b, uint64_t* n, hipStream_t stream);      // how many of them there are
 // ... counted level by level by sorting, down to the (k-mer, count) records of the last tile level (api.hip)
 int tile_recs_to_kmer_records(katome_builder* b, DevBuf& keys, DevBuf& weights, uint64_t* n_records, uint64_t extra_room, hipStream_t stream,
-                              DevBuf* first_counts = nullptr, bool rep = false);      // (rep: the k-mer records in their representative orientation)
+                              DevBuf* first_counts = nullptr, bool rep = false, RecordSource* src = nullptr);      // (rep: the k-mer records in their representative orientation)
 int sorted_count_mode();            // KATOME_SORTED_COUNT
 bool sorting_pays(uint64_t n);       // n records are worth counting by sorting
 bool lds_route_takes(uint64_t n);    // ... and not too many for the LDS counting route

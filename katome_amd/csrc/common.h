@@ -233,6 +233,37 @@ int dev_source_ids(const uint64_t* d_edge_key, uint64_t n_edges, uint32_t k, Dev
                    hipStream_t stream);
 int dev_hash_order_core(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t core_shift, uint32_t core_bases, uint64_t* ka, uint64_t* kb,
                         uint32_t* wa, uint32_t* wb, const uint64_t** k_out, const uint32_t** w_out, uint32_t* group_bits, hipStream_t stream);
+// KATOME_FUSED_RECORDS=0: a list-fed level's records are written out before their first partition pass, as they were before that pass
+// could cut them out of the list itself
+inline bool fused_records_on() { static const bool on = env_flag("KATOME_FUSED_RECORDS", true); return on; }
+// A level's records that are not written yet (table_list_to_records with a RecordSource): record p is sub-window p % span of list
+// entry p / span, in its level's orientation, with that entry's count.  While `pending`, *keys / *weights are not allocated; the first
+// partition pass (dev_key_order, dev_hash_order) makes its tiles from the list, gives the list up where the source owns it
+// (own_tiles / own_counts: a list that would otherwise be gone by then) and only then allocates *keys / *weights, the second pass's
+// destination -- after the two passes the records lie ordered there exactly as if they had been written first.  Whoever wants the
+// records BEFORE the first pass calls table_materialise_records, which writes them (list_to_records_kernel) and ends `pending`.
+struct RecordSource {
+    const uint64_t* tiles = nullptr; const uint32_t* counts = nullptr;
+    uint64_t n_tiles = 0;
+    uint32_t tile_bases = 0, k = 0, span = 0, stride = 0;
+    bool rc = false, rep = false, pending = false;
+    DevBuf* keys = nullptr; DevBuf* weights = nullptr;      // where the records go, and how large those buffers are to be
+    size_t key_bytes = 0, weight_bytes = 0;
+    hipStream_t stream = nullptr;
+    DevBuf own_tiles, own_counts;
+    uint64_t n_records() const { return n_tiles * span; }
+    // the first pass is launched: the list is not needed again, the records' buffers are
+    int first_pass_done() {
+        pending = false; tiles = nullptr; counts = nullptr;
+        own_tiles.release(); own_counts.release();
+        if (int rc = keys->alloc(key_bytes, stream)) return rc;
+        return weights->alloc(weight_bytes, stream);
+    }
+};
+// which lists the first pass can take its records from: two-word tiles into two-word sub-tiles ordered by hash, and one- or two-word
+// tiles into one-word k-mers in their representative orientation ordered by key (the two list-fed levels of a build with k <= 31)
+bool fused_records_takes(uint32_t nwt, uint32_t nwk, bool rep, uint32_t span);
+int table_materialise_records(RecordSource& src);
 // (first_counts of the three order calls below: the first pass's digit counts per tile, made by whoever wrote the records.  The pass
 // works IN that buffer and leaves prefixes there: its contents are gone after the call, and no caller reads them again)
 int dev_hash_order_tagged(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t nwk, uint64_t* ka, uint64_t* kb, uint32_t* wa, uint32_t* wb,
@@ -240,7 +271,10 @@ int dev_hash_order_tagged(const uint64_t* d_in, const uint32_t* w_in, uint64_t n
 int dev_region_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t nw, int passes, uint64_t* ka, uint64_t* kb,
                      uint32_t* wa, uint32_t* wb, const uint64_t** k_out, const uint32_t** w_out, hipStream_t stream);
 int dev_hash_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t nw, uint64_t* ka, uint64_t* kb, uint32_t* wa, uint32_t* wb,
-                   const uint64_t** k_out, const uint32_t** w_out, uint32_t* group_bits, hipStream_t stream, uint32_t* first_counts = nullptr);
+                   const uint64_t** k_out, const uint32_t** w_out, uint32_t* group_bits, hipStream_t stream, uint32_t* first_counts = nullptr,
+                   RecordSource* src = nullptr);
+// (src, here and in dev_key_order: records still to be made -- d_in / w_in and the second destination kb / wb are then taken from the
+// source once its first pass is launched, and first_counts are the counts table_list_to_records made for it)
 uint32_t dev_sort_tile_keys(uint32_t nw);
 // KATOME_FUSED_HIST=0: whoever writes a level's records does not count the first pass's digits per tile; the pass counts them itself
 inline bool fused_hist_on() { static const bool on = env_flag("KATOME_FUSED_HIST", true); return on; }
@@ -249,7 +283,12 @@ inline bool fused_hist_on() { static const bool on = env_flag("KATOME_FUSED_HIST
 // a buffer of dev_digit_stream_bytes(n, 1) bytes, left by whoever wrote the records; the pass then counts from them, not the keys)
 int dev_key_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t k, uint64_t* ka, uint64_t* kb, uint32_t* wa, uint32_t* wb,
                   const uint64_t** k_out, const uint32_t** w_out, hipStream_t stream, uint32_t* first_counts = nullptr,
-                  const uint8_t* first_digits = nullptr);
+                  const uint8_t* first_digits = nullptr, RecordSource* src = nullptr);
+// test entry (katome_dev_list_first_pass): the records of a list after their first partition pass, in d_keys / d_weights, and that
+// pass's digit counts per tile in d_counts -- fused: the count-only kernel and the pass that makes its tiles from the list; otherwise
+// list_to_records_hist_kernel and the pass over the written records
+int dev_list_first_pass(const uint64_t* d_tiles, const uint32_t* d_counts, uint64_t n_tiles, uint32_t tile_bases, uint32_t k, uint32_t span, uint32_t stride,
+                        bool rc, bool rep, bool fused, uint64_t* d_keys, uint32_t* d_weights, uint32_t* d_digit_counts, hipStream_t stream);
 size_t dev_digit_stream_bytes(uint64_t n, uint32_t nw);
 bool dev_digit_stream_pays(uint32_t nw);        // do records of nw words get a digit stream between their two partition passes?
 // index[g] (65537 of them) = first of n ascending one-word keys whose bits [shift, shift + 16) are >= g
@@ -415,7 +454,9 @@ int table_expand_tiles_to_records(Table& tiles, uint32_t k, uint32_t span, bool 
                                   uint64_t* n_records, hipStream_t stream, DevBuf* seen = nullptr);
 int table_list_to_records(const uint64_t* d_tiles, const uint32_t* d_counts, uint64_t n_tiles, uint32_t tile_bases, uint32_t k, uint32_t span, uint32_t stride, bool rc,
                           DevBuf& keys, DevBuf& weights, uint64_t* n_records, hipStream_t stream, uint64_t extra_room = 0, DevBuf* first_counts = nullptr,
-                          bool rep = false);
+                          bool rep = false, RecordSource* src = nullptr);
+// (src, with first_counts: where the first pass can make the records itself -- fused_records_takes, nothing to append -- no record is
+// written: first_counts are counted from the list alone, *src describes the records and keys / weights stay unallocated, see RecordSource)
 // (rep: the k-mers in their representative orientation -- kmer_bits.h rep_orientation -- for the ordered count, records_to_edges_sorted
 // with a HalfSort; first_counts are then that count's first key digit)
 // in place: n one-word k-mer records into their representative orientation (rep) or back into the canonical one
@@ -469,7 +510,9 @@ int half_sort_finish(HalfSort& hs, DevBuf& edge_key, DevBuf& edge_weight, hipStr
 // (first_counts, here and in tagged_records_sorted: handed to the order call, which overwrites them -- see dev_hash_order)
 int records_to_edges_sorted(DevBuf& keys, DevBuf& weights, uint64_t n, uint32_t k, bool rc, uint32_t min_weight, DevBuf& edge_key,
                             DevBuf& edge_weight, uint64_t* n_edges, uint64_t* n_distinct, hipStream_t stream, OwnerSplit* split = nullptr,
-                            uint32_t* first_counts = nullptr, HalfSort* half = nullptr);
+                            uint32_t* first_counts = nullptr, HalfSort* half = nullptr, RecordSource* src = nullptr);
+// (src: keys / weights may be records still to be made.  KATOME_E_UNSUPPORTED leaves them written all the same: before the passes
+// they are materialised, after the passes they lie ordered in keys / weights)
 int table_to_records(Table& t, DevBuf& keys, DevBuf& weights, uint64_t* n_records, hipStream_t stream, DevBuf* seen_pairs = nullptr);
 int table_expand_tiles_to_subtiles(Table& tiles, uint32_t k, uint32_t span, uint32_t stride, bool rc, DevBuf& keys, DevBuf& weights,
                                    uint64_t* n_records, hipStream_t stream, DevBuf* seen = nullptr);

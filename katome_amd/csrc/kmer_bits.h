@@ -282,6 +282,12 @@ KD Key<1> narrow_key(const Key<3>& a, Key<1>*) { Key<1> r; r.w[0] = a.w[2]; retu
 template <int NWT, int NWK> KD Key<NWK> sub_window(const Key<NWT>& tile, u32 sub_len, u32 n_sub, u32 stride, u32 o) {
     return narrow_key(key_low_bits(key_shr(tile, 2 * stride * (n_sub - 1 - o)), 2 * sub_len), (Key<NWK>*)nullptr);
 }
+// a level's record in the orientation its count takes: canonical, or (REP: one-word k-mers of the ordered count, lds_count.hip) the
+// representative one; as it is when one strand is counted
+template <int NWK, bool RC, bool REP> KD Key<NWK> level_orientation(const Key<NWK>& x, u32 k) {
+    if constexpr (REP) { static_assert(NWK == 1, "one-word k-mers"); return RC ? rep_orientation(x, k) : x; }
+    else return RC ? canonical(x, k) : x;
+}
 
 // ---- compress_edge label (compress.rs:250-271) ----------------------------------------------
 KD u32 label_stride_for_k(u32 k) { return 1 + (k + 3) / 4; }

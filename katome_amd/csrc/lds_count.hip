@@ -1196,14 +1196,19 @@ int table_orient_records(uint64_t* d_keys, uint64_t n, uint32_t k, bool rep, hip
 // group of more distinct keys than the table holds (err 3: key ranges are far less even than hash ranges on skewed or low-complexity
 // input) or a count beyond 16 bits (err 5); the records are then still all there, ordered by key, in their representative orientation.
 static int ordered_count(DevBuf& keys, DevBuf& weights, uint64_t n, uint32_t k, bool rc, uint32_t min_weight, HalfSort& hs, uint64_t* n_edges,
-                         uint64_t* n_distinct, hipStream_t stream, uint32_t* first_counts) {
+                         uint64_t* n_distinct, hipStream_t stream, uint32_t* first_counts, RecordSource* src) {
+    const bool pending = src && src->pending;          // (the records are still to be made: keys / weights come with the first pass)
     // (one visit per record: a group must fit the 8-byte-slot table at lds_count_packed_kernel's planning load)
-    if (!n || !weights.p || k < 9 || 2 * k > 62 || (rc && !(k & 1)) || !lp_group_fits(n >> 16)) return KATOME_E_UNSUPPORTED;
+    if (!n || (!weights.p && !pending) || k < 9 || 2 * k > 62 || (rc && !(k & 1)) || !lp_group_fits(n >> 16)) {
+        if (pending) KCHECK(table_materialise_records(*src));          // (a refusal leaves the records there)
+        return KATOME_E_UNSUPPORTED;
+    }
     const u64* ko = nullptr; const u32* wo = nullptr;
     {
         DevBuf kb(stream), wb(stream);
         KCHECK(kb.alloc((n + 1) * 8)); KCHECK(wb.alloc((n + 1) * 4));
-        KCHECK(dev_key_order(keys.as<u64>(), weights.as<u32>(), n, k, kb.as<u64>(), keys.as<u64>(), wb.as<u32>(), weights.as<u32>(), &ko, &wo, stream, first_counts));
+        KCHECK(dev_key_order(keys.as<u64>(), weights.as<u32>(), n, k, kb.as<u64>(), keys.as<u64>(), wb.as<u32>(), weights.as<u32>(), &ko, &wo, stream, first_counts,
+                             nullptr, src));
     }
     KCHECK(hs.group_first.alloc(((1ull << 16) + 1) * 8, stream));
     KCHECK(dev_key_group_index(ko, n, 2 * k - 16, hs.group_first.as<u64>(), stream));
@@ -1399,26 +1404,30 @@ static int count_packed(const LcLevel& c, u32 R_try, LcResult& r, bool* done) {
 // the input is out of the kernels' range (the caller counts in the table instead).
 int records_to_edges_sorted(DevBuf& keys, DevBuf& weights, uint64_t n, uint32_t k, bool rc, uint32_t min_weight, DevBuf& edge_key,
                             DevBuf& edge_weight, uint64_t* n_edges, uint64_t* n_distinct, hipStream_t stream, OwnerSplit* split,
-                            uint32_t* first_counts, HalfSort* half) {
+                            uint32_t* first_counts, HalfSort* half, RecordSource* src) {
     *n_edges = 0; *n_distinct = 0;
+    // (src: records still to be made.  Whatever wants them before the first partition pass has them written here first)
+    auto records = [&]() { return src && src->pending ? table_materialise_records(*src) : (int)KATOME_OK; };
     if (half) {
         half->taken = false;
-        const int orc = split ? KATOME_E_UNSUPPORTED : ordered_count(keys, weights, n, k, rc, min_weight, *half, n_edges, n_distinct, stream, first_counts);
+        if (split) KCHECK(records());
+        const int orc = split ? KATOME_E_UNSUPPORTED : ordered_count(keys, weights, n, k, rc, min_weight, *half, n_edges, n_distinct, stream, first_counts, src);
         if (orc != KATOME_E_UNSUPPORTED) return orc;
         if (rc) KCHECK(table_orient_records(keys.as<u64>(), n, k, false, stream));      // (the usual route and the table take canonical k-mers)
         first_counts = nullptr;
     }
     const uint32_t nw = (uint32_t)key_words_for_k(k);
-    if (nw > 3 || (nw == 3 && (rc || min_weight))) return KATOME_E_UNSUPPORTED;      // (three words: tiles of 64..95 bases -- never k-mers, so never oriented)
+    if (nw > 3 || (nw == 3 && (rc || min_weight))) { KCHECK(records()); return KATOME_E_UNSUPPORTED; }      // (three words: tiles of 64..95 bases -- never k-mers, so never oriented)
     if (split && (nw != 1 || rc || min_weight || split->n_parts == 0 || split->n_parts > (uint32_t)KATOME_MAX_RANKS)) {
         set_error("records by owner: one-word k-mers, one record per k-mer"); return KATOME_E_ARG;
     }
-    if (!lc_level_fits(n, LcTable<13>::FILL)) return KATOME_E_UNSUPPORTED;
+    if (!lc_level_fits(n, LcTable<13>::FILL)) { KCHECK(records()); return KATOME_E_UNSUPPORTED; }
+    if (split) KCHECK(records());          // (the core's hash: that order reads records)
     LcAux aux(stream);
     LcLevel c{aux};
     c.n = n; c.k = k; c.nw = nw; c.rc = rc; c.min_weight = min_weight; c.split = split;
     // (weights not allocated: every record counts once; the passes move keys only.  Two-word keys: lds_count_wide_kernel)
-    const bool unit = weights.p == nullptr;
+    const bool unit = weights.p == nullptr && !(src && src->pending);
     if (unit && (nw < 2 || split)) { set_error("records without weights: keys of two or three words"); return KATOME_E_ARG; }
     {
         DevBuf kb(stream), wb(stream);
@@ -1427,7 +1436,7 @@ int records_to_edges_sorted(DevBuf& keys, DevBuf& weights, uint64_t n, uint32_t 
         // two passes: the first one's output goes to the scratch, the second one's lands in keys / weights again
         if (split) KCHECK(dev_hash_order_core(keys.as<u64>(), weights.as<u32>(), n, split->core_shift, split->core_bases, kb.as<u64>(), keys.as<u64>(), wb.as<u32>(),
                                               weights.as<u32>(), &c.ko, &c.wo, &c.gbits, stream));
-        else KCHECK(dev_hash_order(keys.as<u64>(), weights.as<u32>(), n, nw, kb.as<u64>(), keys.as<u64>(), wb.as<u32>(), weights.as<u32>(), &c.ko, &c.wo, &c.gbits, stream, first_counts));
+        else KCHECK(dev_hash_order(keys.as<u64>(), weights.as<u32>(), n, nw, kb.as<u64>(), keys.as<u64>(), wb.as<u32>(), weights.as<u32>(), &c.ko, &c.wo, &c.gbits, stream, first_counts, src));
     }
     c.avg = n >> c.gbits;
     const u32 fill = c.avg <= LcTable<8>::FILL ? LcTable<8>::FILL : LcTable<13>::FILL;

@@ -278,18 +278,43 @@ __global__ __launch_bounds__(BLOCK) void radix_offsets_kernel(u64* __restrict__ 
 // stores, so it leaves that digit, one byte, at the key's index of next_out, and the next pass counts its tiles from those bytes
 // (digit_hist_kernel) instead of reading the keys again.  NoNextDigit: a last pass -- nothing is computed or stored, the code is the
 // one the kernel had before.
+// SRC (round 15): where the tile's records come from.  ArraySource: keys_in / vals_in at the record's index, the code the kernel had
+// before.  ListSource: the records do not exist yet -- record p is sub-window p % span of list entry p / span in its level's
+// orientation, with that entry's count (table.hip, list_to_records_kernel) --, and the pass that would read them first cuts them out
+// of the list, a fifth or a sixth of the bytes, so that they are neither written nor read back.  The workgroup divides its first
+// record's index by span once; a record q places behind that entry's first one lies in entry mulhi(q, inv), inv = 2^32 / span + 1
+// (q / span while q * span < 2^32).  Consecutive lanes read the same entry span times over: plain loads, the lines are shared.
 struct NoNextDigit {};
+struct ArraySource {
+    struct Origin {};
+    __device__ __forceinline__ Origin origin(u64) const { return Origin{}; }
+};
+template <int NWT, int NWK, bool RC, bool REP> struct ListSource {
+    const u64* tiles; const u32* counts; u32 k, span, stride, inv;
+    struct Origin { u64 t0; u32 o0; };
+    __device__ __forceinline__ Origin origin(u64 base) const { const u64 t0 = base / span; return Origin{t0, (u32)(base - t0 * span)}; }
+    __device__ __forceinline__ void load(const Origin& at, u32 idx, Key<NWK>& key, u32& val) const {
+        const u32 q = at.o0 + idx, tr = __umulhi(q, inv), o = q - tr * span;
+        const u64 t = at.t0 + tr;
+        Key<NWT> tile;
+#pragma unroll
+        for (int w = 0; w < NWT; ++w) tile.w[w] = tiles[t * NWT + w];
+        key = level_orientation<NWK, RC, REP>(sub_window<NWT, NWK>(tile, k, span, stride, o), k);
+        val = counts[t];
+    }
+};
 template <class Next> struct NextDigitOut {
     Next nx; uint8_t* out;
     __device__ __forceinline__ void put(u64 at, u32 d) const { out[at] = (uint8_t)d; }
 };
 template <> struct NextDigitOut<NoNextDigit> {};
-template <int NW, bool HAS_VAL, class Digit, bool STABLE = true, class Next = NoNextDigit>
+template <int NW, bool HAS_VAL, class Digit, bool STABLE = true, class Next = NoNextDigit, class Src = ArraySource>
 __global__ __launch_bounds__(BLOCK, KATOME_SORT_WAVES) void radix_scatter_kernel(const u64* __restrict__ keys_in, const u32* __restrict__ vals_in,
                                                                u64 n, Digit dg, const u32* __restrict__ rel,
                                                                const u64* __restrict__ chunk_off, u64* __restrict__ keys_out,
-                                                               u32* __restrict__ vals_out, u32 chunk_blocks, u32 xcd_tiles, NextDigitOut<Next> next) {
-    constexpr bool NEXT = !std::is_same<Next, NoNextDigit>::value;
+                                                               u32* __restrict__ vals_out, u32 chunk_blocks, u32 xcd_tiles, NextDigitOut<Next> next, Src src) {
+    constexpr bool NEXT = !std::is_same<Next, NoNextDigit>::value, LISTED = !std::is_same<Src, ArraySource>::value;
+    static_assert(!LISTED || HAS_VAL, "a list's records carry its counts");
     constexpr int SORT_ITEMS = SortTile<NW>::ITEMS, SORT_TILE = SortTile<NW>::KEYS;
     extern __shared__ u64 smem[];
     u64* skeys = smem;                                            // [SORT_TILE * NW]; reused for the values afterwards
@@ -312,12 +337,15 @@ __global__ __launch_bounds__(BLOCK, KATOME_SORT_WAVES) void radix_scatter_kernel
 
     Key<NW> key[SORT_ITEMS]; u32 val[SORT_ITEMS]; u32 dig[SORT_ITEMS]; u32 rnk[SORT_ITEMS];
     const u64 lt_mask = lane ? (~0ull >> (64 - lane)) : 0ull;
+    const typename Src::Origin from = src.origin(base);
 #pragma unroll
     for (int j = 0; j < SORT_ITEMS; ++j) {
         const u32 idx = wave * (64 * SORT_ITEMS) + j * 64 + lane;
         const bool valid = idx < cnt;
         u32 d = 0;
         if (valid) {
+            if constexpr (LISTED) src.load(from, idx, key[j], val[j]);
+            else {
 #if KATOME_STREAM_LOADS >= 1
             key[j] = load_key_stream<NW>(keys_in, base + idx);
             if (HAS_VAL) val[j] = __builtin_nontemporal_load(&vals_in[base + idx]);
@@ -325,6 +353,7 @@ __global__ __launch_bounds__(BLOCK, KATOME_SORT_WAVES) void radix_scatter_kernel
             key[j] = load_key<NW>(keys_in, base + idx);
             if (HAS_VAL) val[j] = vals_in[base + idx];
 #endif
+            }
             d = dg(key[j]);
         }
         if (!STABLE) {
@@ -457,9 +486,11 @@ static bool unstable_first() {
 }
 // digits_in: this pass's digit of every record, one byte each at the record's index (see digit_hist_kernel) -- the per-tile counts are
 // then made from them and the keys are read by the scatter alone.  nx / digits_out: the scatter also leaves the NEXT pass's digits.
-template <int NW, bool HAS_VAL, class Digit, bool STABLE = true, class Next = NoNextDigit>
+// src: the records are made from a list by the scatter itself (ListSource; kin / vin are not read, and the counts must be there)
+template <int NW, bool HAS_VAL, class Digit, bool STABLE = true, class Next = NoNextDigit, class Src = ArraySource>
 static int radix_pass(const u64* kin, const u32* vin, u64 n, Digit dg, u64* kout, u32* vout, PassBuffers& pb, hipStream_t stream,
-                      bool have_counts = false, const uint8_t* digits_in = nullptr, Next nx = Next{}, uint8_t* digits_out = nullptr) {
+                      bool have_counts = false, const uint8_t* digits_in = nullptr, Next nx = Next{}, uint8_t* digits_out = nullptr, Src src = Src{}) {
+    if (!std::is_same<Src, ArraySource>::value && !have_counts) { set_error("radix pass: records off a list and no counts of them"); return KATOME_E_ARG; }
     if (pb.nblocks > 0x7fffffffull) { set_error("radix pass: %llu keys exceed the grid limit", (unsigned long long)n); return KATOME_E_ARG; }
     if (!std::is_same<Next, NoNextDigit>::value && !digits_out) { set_error("radix pass: a next digit and nowhere to write it"); return KATOME_E_ARG; }
     dim3 block(BLOCK);
@@ -478,7 +509,7 @@ static int radix_pass(const u64* kin, const u32* vin, u64 n, Digit dg, u64* kout
     static_assert(!NEXT || STABLE, "the next digit is written by the stable scatter");
     const size_t lds = (size_t)SortTile<NW>::KEYS * NW * 8;
     if (lds > (64u << 10)) {          // three-word records: 96 KiB of the CU's 160 KiB
-        KCHECK_HIP(hipFuncSetAttribute((const void*)radix_scatter_kernel<NW, HAS_VAL, Digit, STABLE, Next>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        KCHECK_HIP(hipFuncSetAttribute((const void*)radix_scatter_kernel<NW, HAS_VAL, Digit, STABLE, Next, Src>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
     {
         static const bool xcd_aware = env_flag("KATOME_XCD_TILES", true);       // (0: workgroup i takes tile i)
@@ -486,8 +517,8 @@ static int radix_pass(const u64* kin, const u32* vin, u64 n, Digit dg, u64* kout
         KernelScope ks((!HAS_VAL && DigitTimers<Digit>::SCATTER == K_SORT_SCATTER) ? (int)K_SORT_SCATTER_KEYS : (int)DigitTimers<Digit>::SCATTER, stream, n);
         NextDigitOut<Next> next;
         if constexpr (NEXT) { next.nx = nx; next.out = digits_out; }
-        hipLaunchKernelGGL((radix_scatter_kernel<NW, HAS_VAL, Digit, STABLE, Next>), dim3(xcd_tiles ? xcd_tiles * 8u : (unsigned)pb.nblocks), block, lds, stream, kin, vin, n, dg,
-                           counts, pb.chunk.as<u64>(), kout, vout, pb.chunk_blocks, xcd_tiles, next);
+        hipLaunchKernelGGL((radix_scatter_kernel<NW, HAS_VAL, Digit, STABLE, Next, Src>), dim3(xcd_tiles ? xcd_tiles * 8u : (unsigned)pb.nblocks), block, lds, stream, kin, vin, n, dg,
+                           counts, pb.chunk.as<u64>(), kout, vout, pb.chunk_blocks, xcd_tiles, next, src);
     }
     KCHECK_HIP(hipGetLastError());
     return KATOME_OK;
@@ -899,20 +930,56 @@ int dev_partition_range(const uint64_t* d_vals, const uint32_t* idx_in, uint64_t
     return KATOME_OK;
 }
 
+// ---- a first pass that makes its records from a list (RecordSource, common.h) ------------------------------------------------------
+template <int NWT, int NWK, bool RC, bool REP> static ListSource<NWT, NWK, RC, REP> list_source(const RecordSource& s) {
+    return ListSource<NWT, NWK, RC, REP>{s.tiles, s.counts, s.k, s.span, s.stride, (u32)((1ull << 32) / s.span) + 1};
+}
+static bool source_by_key(const RecordSource& s) {          // dev_key_order's first pass can take it
+    return s.rep && key_words_for_k(s.k) == 1 && fused_records_takes((u32)key_words_for_k(s.tile_bases), 1, true, s.span);
+}
+static bool source_by_hash(const RecordSource& s, u32 nw) {          // dev_hash_order's
+    return !s.rep && nw == 2 && (u32)key_words_for_k(s.k) == 2 && fused_records_takes((u32)key_words_for_k(s.tile_bases), 2, false, s.span);
+}
+// the first pass of dev_key_order over the records of s, into ka / wa (pb.first: their counts per tile)
+static int list_pass_by_key(const RecordSource& s, u64 n, u32 k, u64* ka, u32* wa, PassBuffers& pb, hipStream_t stream) {
+    const LevelKeyDigit dg{2 * k - 16};
+    return with_bool(s.rc, [&](auto rcv) {
+        constexpr bool RC = decltype(rcv)::value;
+        if (key_words_for_k(s.tile_bases) == 2)
+            return radix_pass<1, true, LevelKeyDigit, true, NoNextDigit>(nullptr, nullptr, n, dg, ka, wa, pb, stream, true, nullptr, NoNextDigit{}, nullptr, list_source<2, 1, RC, true>(s));
+        return radix_pass<1, true, LevelKeyDigit, true, NoNextDigit>(nullptr, nullptr, n, dg, ka, wa, pb, stream, true, nullptr, NoNextDigit{}, nullptr, list_source<1, 1, RC, true>(s));
+    });
+}
+// the first pass of dev_hash_order over two-word records of s, leaving the second pass's digits
+static int list_pass_by_hash(const RecordSource& s, u64 n, u64* ka, u32* wa, PassBuffers& pb, uint8_t* digits, hipStream_t stream) {
+    const HashDigit<2> dg{48u}, nx{56u};
+    return with_bool(s.rc, [&](auto rcv) {
+        return radix_pass<2, true, HashDigit<2>, true, HashDigit<2>>(nullptr, nullptr, n, dg, ka, wa, pb, stream, true, nullptr, nx, digits, list_source<2, 2, decltype(rcv)::value, false>(s));
+    });
+}
+
 // order records by the table region they hash to (1 or 2 stable 8-bit passes over the top hash bits), so
 // that the insert kernel that follows works through the table one cache-sized region at a time.
 // Result lands in `bufs[passes & 1]` where bufs = {scratch_a, scratch_b}; returns that pointer.
 template <int NW>
 static int region_order_t(const u64* d_in, const u32* w_in, u64 n, int passes, u64* ka, u64* kb, u32* wa, u32* wb,
-                          const u64** k_out, const u32** w_out, hipStream_t stream, u32* first_counts = nullptr) {
+                          const u64** k_out, const u32** w_out, hipStream_t stream, u32* first_counts = nullptr, RecordSource* src = nullptr) {
     PassBuffers pb;
     KCHECK(pb.init(n, NW, stream));
+    // (src: records still to be made.  Where this order's first pass cannot make them, they are written now; either way the input
+    // and the second destination are the source's buffers)
+    const bool listed = src && src->pending && passes == 2 && first_counts && digit_stream_pays(NW) && !unstable_first() && source_by_hash(*src, NW);
+    if (src && src->pending && !listed) {
+        KCHECK(table_materialise_records(*src));
+        d_in = kb = src->keys->as<u64>(); w_in = wb = src->weights->as<u32>();
+    }
     // (first_counts: the first pass's digit counts per tile, [ceil(n / dev_sort_tile_keys)][256], made while the records were written;
     // the pass works in that buffer and leaves prefixes in it)
     pb.first = first_counts;
     DevBuf digits(stream);
     const u64* kin = d_in; const u32* win = w_in;
     u64* kdst[2] = {ka, kb}; u32* wdst[2] = {wa, wb};
+    const bool has_w = w_in || listed;          // (a list's records carry its counts)
     for (int p = 0; p < passes; ++p) {
         HashDigit<NW> dg{(u32)(64 - 8 * (passes - p))};     // least significant region byte first
         const bool have = p == 0 && first_counts != nullptr;
@@ -923,13 +990,20 @@ static int region_order_t(const u64* d_in, const u32* w_in, u64 n, int passes, u
             if (p == 0) {
                 KCHECK(digits.alloc(digit_stream_bytes(n, NW)));
                 const HashDigit<NW> nx{56u};
+                if (listed) {
+                    if constexpr (NW == 2) KCHECK(list_pass_by_hash(*src, n, kdst[0], wdst[0], pb, digits.as<uint8_t>(), stream));
+                    KCHECK(src->first_pass_done());          // (the list may go; the second pass's destination comes only now)
+                    kdst[1] = src->keys->as<u64>(); wdst[1] = src->weights->as<u32>();
+                    kin = kdst[0]; win = wdst[0];
+                    continue;
+                }
                 if (w_in) KCHECK((radix_pass<NW, true, HashDigit<NW>, true, HashDigit<NW>>(kin, win, n, dg, kdst[0], wdst[0], pb, stream, have, nullptr, nx, digits.as<uint8_t>())));
                 else      KCHECK((radix_pass<NW, false, HashDigit<NW>, true, HashDigit<NW>>(kin, nullptr, n, dg, kdst[0], nullptr, pb, stream, have, nullptr, nx, digits.as<uint8_t>())));
             } else {
-                if (w_in) KCHECK((radix_pass<NW, true>(kin, win, n, dg, kdst[1], wdst[1], pb, stream, false, digits.as<uint8_t>())));
+                if (has_w) KCHECK((radix_pass<NW, true>(kin, win, n, dg, kdst[1], wdst[1], pb, stream, false, digits.as<uint8_t>())));
                 else      KCHECK((radix_pass<NW, false>(kin, nullptr, n, dg, kdst[1], nullptr, pb, stream, false, digits.as<uint8_t>())));
             }
-            kin = kdst[p & 1]; win = w_in ? wdst[p & 1] : nullptr;
+            kin = kdst[p & 1]; win = has_w ? wdst[p & 1] : nullptr;
             continue;
         }
         if (p == 0 && unstable_first()) {          // (nothing is ordered yet: the first pass need not be stable)
@@ -946,28 +1020,67 @@ static int region_order_t(const u64* d_in, const u32* w_in, u64 n, int passes, u
 // (k-mer, count) records of one to three words ordered by the top 16 bits of the k-mer's hash, for the counting in LDS (lds_count.hip): two
 // stable 8-bit passes.  The result is where *k_out / *w_out point (one of the two buffer pairs); *group_bits = 16.
 int dev_hash_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t nw, uint64_t* ka, uint64_t* kb, uint32_t* wa, uint32_t* wb,
-                   const uint64_t** k_out, const uint32_t** w_out, uint32_t* group_bits, hipStream_t stream, uint32_t* first_counts) {
+                   const uint64_t** k_out, const uint32_t** w_out, uint32_t* group_bits, hipStream_t stream, uint32_t* first_counts, RecordSource* src) {
     *group_bits = 16;
-    if (nw == 1) return region_order_t<1>(d_in, w_in, n, 2, ka, kb, wa, wb, k_out, w_out, stream, first_counts);
-    if (nw == 3) return region_order_t<3>(d_in, w_in, n, 2, ka, kb, wa, wb, k_out, w_out, stream, first_counts);      // (tiles of 64..95 bases)
-    return region_order_t<2>(d_in, w_in, n, 2, ka, kb, wa, wb, k_out, w_out, stream, first_counts);
+    if (nw == 1) return region_order_t<1>(d_in, w_in, n, 2, ka, kb, wa, wb, k_out, w_out, stream, first_counts, src);
+    if (nw == 3) return region_order_t<3>(d_in, w_in, n, 2, ka, kb, wa, wb, k_out, w_out, stream, first_counts, src);      // (tiles of 64..95 bases)
+    return region_order_t<2>(d_in, w_in, n, 2, ka, kb, wa, wb, k_out, w_out, stream, first_counts, src);
 }
 // one-word (k-mer, count) records ordered by their leading 16 key bits (bits 2k - 16 .. 2k - 1): two stable 8-bit passes, the
 // result where *k_out / *w_out point (first_counts: the first pass's digit counts per tile, made while the records were written)
 int dev_key_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t k, uint64_t* ka, uint64_t* kb, uint32_t* wa, uint32_t* wb,
-                  const uint64_t** k_out, const uint32_t** w_out, hipStream_t stream, uint32_t* first_counts, const uint8_t* first_digits) {
+                  const uint64_t** k_out, const uint32_t** w_out, hipStream_t stream, uint32_t* first_counts, const uint8_t* first_digits, RecordSource* src) {
     if (k < 8 || 2 * k > 64) { set_error("key order: k = %u", k); return KATOME_E_ARG; }
     PassBuffers pb;
     KCHECK(pb.init(n, 1, stream));
     pb.first = first_counts;
+    // (src: records still to be made -- by the first pass where it can; the second pass's destination is then allocated after it)
+    const bool listed = src && src->pending && first_counts && source_by_key(*src);
+    if (src && src->pending && !listed) {
+        KCHECK(table_materialise_records(*src));
+        d_in = kb = src->keys->as<u64>(); w_in = wb = src->weights->as<u32>();
+    }
     // (one-word records: digit_stream_pays says no, so the second pass counts from the keys; the first from first_counts, else
     // first_digits, else the keys)
     if (order_trace())
         fprintf(stderr, "[order] by key: %llu records of 1 words, first pass counted from %s, second from the keys\n", (unsigned long long)n,
                 first_counts ? "its writer's counts" : first_digits ? "its writer's digits" : "the keys");
+    if (listed) {
+        KCHECK(list_pass_by_key(*src, n, k, ka, wa, pb, stream));
+        KCHECK(src->first_pass_done());
+        kb = src->keys->as<u64>(); wb = src->weights->as<u32>();
+    } else
     KCHECK((radix_pass<1, true>(d_in, w_in, n, LevelKeyDigit{2 * k - 16}, ka, wa, pb, stream, first_counts != nullptr, first_digits)));
     KCHECK((radix_pass<1, true>(ka, wa, n, LevelKeyDigit{2 * k - 8}, kb, wb, pb, stream)));
     *k_out = kb; *w_out = wb;
+    return KATOME_OK;
+}
+
+// the first partition pass over a list's records, both ways (test entry: see common.h)
+int dev_list_first_pass(const uint64_t* d_tiles, const uint32_t* d_counts, uint64_t n_tiles, uint32_t tile_bases, uint32_t k, uint32_t span, uint32_t stride,
+                        bool rc, bool rep, bool fused, uint64_t* d_keys, uint32_t* d_weights, uint32_t* d_digit_counts, hipStream_t stream) {
+    const u32 nwt = (u32)key_words_for_k(tile_bases), nwk = (u32)key_words_for_k(k);
+    if (!fused_records_takes(nwt, nwk, rep, span)) { set_error("first pass off a list: tiles of %u words into windows of %u, span %u", nwt, nwk, span); return KATOME_E_UNSUPPORTED; }
+    DevBuf rk(stream), rw(stream), counts(stream), digits(stream);
+    RecordSource src;
+    u64 n = 0;
+    KCHECK(table_list_to_records(d_tiles, d_counts, n_tiles, tile_bases, k, span, stride, rc, rk, rw, &n, stream, 0, &counts, rep, fused ? &src : nullptr));
+    if (!n) return KATOME_OK;
+    if (src.pending != fused || !counts.p) { set_error("first pass off a list: the records were written (KATOME_FUSED_RECORDS, KATOME_FUSED_HIST)"); return KATOME_E_UNSUPPORTED; }
+    PassBuffers pb;
+    KCHECK(pb.init(n, (int)nwk, stream));
+    pb.first = counts.as<u32>();
+    KCHECK_HIP(hipMemcpyAsync(d_digit_counts, counts.p, pb.nblocks * RADIX * sizeof(u32), hipMemcpyDeviceToDevice, stream));
+    if (rep) {
+        if (fused) KCHECK(list_pass_by_key(src, n, k, d_keys, d_weights, pb, stream));
+        else KCHECK((radix_pass<1, true>(rk.as<u64>(), rw.as<u32>(), n, LevelKeyDigit{2 * k - 16}, d_keys, d_weights, pb, stream, true)));
+    } else {
+        KCHECK(digits.alloc(digit_stream_bytes(n, 2)));
+        if (fused) KCHECK(list_pass_by_hash(src, n, d_keys, d_weights, pb, digits.as<uint8_t>(), stream));
+        else KCHECK((radix_pass<2, true, HashDigit<2>, true, HashDigit<2>>(rk.as<u64>(), rw.as<u32>(), n, HashDigit<2>{48u}, d_keys, d_weights, pb, stream, true, nullptr,
+                                                                             HashDigit<2>{56u}, digits.as<uint8_t>())));
+    }
+    KCHECK_HIP(hipStreamSynchronize(stream));
     return KATOME_OK;
 }
 

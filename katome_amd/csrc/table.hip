@@ -605,10 +605,6 @@ __global__ __launch_bounds__(BLOCK) void tiles_to_records_kernel(const typename 
 // a compact list of distinct tiles with their counts (what the sorted counting of a level leaves) -> the (sub-window, count) records
 // of the next level: record p is sub-window p % span of tile p / span; consecutive lanes write consecutive records
 // (REP: one-word k-mers of the ordered count, lds_count_ordered_kernel -- the representative orientation instead of the canonical one)
-template <int NWK, bool RC, bool REP> __device__ __forceinline__ Key<NWK> level_orientation(const Key<NWK>& x, u32 k) {
-    if constexpr (REP) { static_assert(NWK == 1, "one-word k-mers"); return RC ? rep_orientation(x, k) : x; }
-    else return RC ? canonical(x, k) : x;
-}
 template <int NWT, int NWK, bool RC, bool REP = false>
 __global__ __launch_bounds__(BLOCK) void list_to_records_kernel(const u64* __restrict__ tiles, const u32* __restrict__ counts, u64 n_tiles, u32 k, u32 span,
                                                                  u32 stride, u64* __restrict__ out_keys, u32* __restrict__ out_w) {
@@ -652,6 +648,45 @@ __global__ __launch_bounds__(BLOCK) void list_to_records_hist_kernel(const u64* 
             for (int q = 0; q < NWK; ++q) out_keys[p * NWK + q] = x.w[q];
             out_w[p] = counts[t];
             atomicAdd(&h[(REP ? (u32)(x.w[0] >> (2 * k - 16)) : (u32)(hash_key(x) >> 48)) & 255u], 1u);
+        }
+        __syncthreads();
+        digit_counts[ot * 256 + threadIdx.x] = h[threadIdx.x];
+        __syncthreads();
+    }
+}
+
+// The same counts and no records: the first partition pass makes its tiles from the list itself (radix.hip, ListSource), so all that
+// is needed beforehand is counts[tile][digit] of the tiles it will cut.  A workgroup divides its tile's first record index by span
+// once; inside the tile the entry of record q (counted from that entry's first record) is mulhi(q, inv), inv = 2^32 / span + 1, which
+// is q / span while q * span < 2^32.  REP: the digit is bits 2k - 16 .. 2k - 9 of the representative orientation -- the sub-window's own
+// when its middle base says so, else the complement of its bases 4..7 from the right, in reverse: no reverse complement is built.
+template <int NWT, int NWK, bool RC, bool REP = false>
+__global__ __launch_bounds__(BLOCK) void list_digit_counts_kernel(const u64* __restrict__ tiles, u64 n_tiles, u32 k, u32 span, u32 stride, u32 inv, u32 tile_keys,
+                                                                   u32* __restrict__ digit_counts) {
+    static_assert(BLOCK == 256, "one thread per digit");
+    __shared__ u32 h[256];
+    const u64 n = n_tiles * span, n_out_tiles = (n + tile_keys - 1) / tile_keys;
+    for (u64 ot = blockIdx.x; ot < n_out_tiles; ot += gridDim.x) {
+        h[threadIdx.x] = 0;
+        __syncthreads();
+        const u64 p0 = ot * tile_keys, t0 = p0 / span;
+        const u32 o0 = (u32)(p0 - t0 * span), cnt = (u32)(n - p0 < (u64)tile_keys ? n - p0 : (u64)tile_keys);
+        for (u32 i = threadIdx.x; i < cnt; i += BLOCK) {
+            const u32 q = o0 + i, tr = __umulhi(q, inv), o = q - tr * span;
+            const u64 t = t0 + tr;
+            Key<NWT> tile;
+#pragma unroll
+            for (int w = 0; w < NWT; ++w) tile.w[w] = tiles[t * NWT + w];
+            const Key<NWK> x = sub_window<NWT, NWK>(tile, k, span, stride, o);
+            u32 d;
+            if constexpr (REP) {
+                const u32 own = (u32)(x.w[0] >> (2 * k - 16)) & 255u;
+                u32 v = ~(u32)(x.w[0] >> 8) & 255u;                          // the reverse complement's: pairs of bits in reverse
+                v = ((v & 0x0Fu) << 4) | (v >> 4);
+                v = ((v & 0x33u) << 2) | ((v >> 2) & 0x33u);
+                d = RC && ((x.w[0] >> k) & 1ull) ? v : own;
+            } else d = (u32)(hash_key(level_orientation<NWK, RC, false>(x, k)) >> 48) & 255u;
+            atomicAdd(&h[d], 1u);
         }
         __syncthreads();
         digit_counts[ot * 256 + threadIdx.x] = h[threadIdx.x];
@@ -1041,22 +1076,83 @@ int table_to_records(Table& t, DevBuf& keys, DevBuf& weights, uint64_t* n_record
     return KATOME_OK;
 }
 
+// list_to_records_kernel over a whole list, into buffers that hold n_tiles * span records
+static int launch_list_to_records(const uint64_t* d_tiles, const uint32_t* d_counts, uint64_t n_tiles, uint32_t nwt, uint32_t nwk, uint32_t k, uint32_t span,
+                                  uint32_t stride, bool rc, bool rep, u64* d_keys, u32* d_weights, hipStream_t stream) {
+    const dim3 grid(grid_for(n_tiles * span, BLOCK, 256u * 32u)), block(BLOCK);
+    KernelScope ks(K_RECORDS, stream, n_tiles);
+#define KATOME_LR(NWT, NWK, REP) with_bool(rc, [&](auto rcv) { hipLaunchKernelGGL((list_to_records_kernel<NWT, NWK, decltype(rcv)::value, REP>), grid, block, 0, stream, d_tiles, d_counts, n_tiles, k, span, stride, d_keys, d_weights); return 0; })
+    if (rep) { if (nwt == 2) KATOME_LR(2, 1, true); else KATOME_LR(1, 1, true); }
+    else if (nwt == 3 && nwk == 3) KATOME_LR(3, 3, false);
+    else if (nwt == 3 && nwk == 2) KATOME_LR(3, 2, false);
+    else if (nwt == 2 && nwk == 2) KATOME_LR(2, 2, false);
+    else if (nwt == 2 && nwk == 1) KATOME_LR(2, 1, false);
+    else if (nwt == 1 && nwk == 1) KATOME_LR(1, 1, false);
+    else { set_error("records of a tile list: tiles of %u words into windows of %u", nwt, nwk); return KATOME_E_UNSUPPORTED; }
+#undef KATOME_LR
+    KCHECK_HIP(hipGetLastError());
+    return KATOME_OK;
+}
+
+bool fused_records_takes(uint32_t nwt, uint32_t nwk, bool rep, uint32_t span) {
+    if (span < 2 || span > 64) return false;          // (the kernels' reciprocal of span: 2^32 / span + 1 in 32 bits)
+    return rep ? (nwk == 1 && nwt <= 2) : (nwt == 2 && nwk == 2);
+}
+
+// the records of a source that somebody wants before its first pass: written out as they always were, in this one place
+int table_materialise_records(RecordSource& s) {
+    if (!s.pending) return KATOME_OK;
+    KCHECK(s.keys->alloc(s.key_bytes, s.stream));
+    KCHECK(s.weights->alloc(s.weight_bytes, s.stream));
+    if (getenv("KATOME_LC_TRACE")) fprintf(stderr, "[records] %llu records written after all: wanted before their first pass\n", (unsigned long long)s.n_records());
+    KCHECK(launch_list_to_records(s.tiles, s.counts, s.n_tiles, (uint32_t)key_words_for_k(s.tile_bases), (uint32_t)key_words_for_k(s.k), s.k, s.span, s.stride,
+                                  s.rc, s.rep, s.keys->as<u64>(), s.weights->as<u32>(), s.stream));
+    s.pending = false; s.tiles = nullptr; s.counts = nullptr;
+    s.own_tiles.release(); s.own_counts.release();
+    return KATOME_OK;
+}
+
 // the (sub-window, count) records of a compact list of distinct tiles (list_to_records_kernel); extra_room: see below
 int table_list_to_records(const uint64_t* d_tiles, const uint32_t* d_counts, uint64_t n_tiles, uint32_t tile_bases, uint32_t k, uint32_t span, uint32_t stride, bool rc,
-                          DevBuf& keys, DevBuf& weights, uint64_t* n_records, hipStream_t stream, uint64_t extra_room, DevBuf* first_counts, bool rep) {
+                          DevBuf& keys, DevBuf& weights, uint64_t* n_records, hipStream_t stream, uint64_t extra_room, DevBuf* first_counts, bool rep,
+                          RecordSource* src) {
     const uint32_t nwt = (uint32_t)key_words_for_k(tile_bases), nwk = (uint32_t)key_words_for_k(k);
     if (rep && (nwk != 1 || nwt > 2 || k < 9 || (rc && !(k & 1)))) { set_error("records in their representative orientation: one-word k-mers, k >= 9, odd k or one strand"); return KATOME_E_ARG; }
     *n_records = n_tiles * span;
+    // (first_counts: the caller sorts exactly these records next -- nothing appended -- and wants the first pass's digit counts per tile;
+    // KATOME_FUSED_HIST=0: the pass counts them itself)
+    const bool counted = first_counts && fused_hist_on() && !extra_room && ((nwt == 3 && nwk >= 2) || (nwt == 2 && nwk <= 2) || (nwt == 1 && nwk == 1));
+    // (src: ... and can do without the records until its first pass has made them -- KATOME_FUSED_RECORDS=0: never)
+    const bool fused = src && counted && *n_records && fused_records_on() && fused_records_takes(nwt, nwk, rep, span);
+    if (src && getenv("KATOME_LC_TRACE"))
+        fprintf(stderr, "[records] %llu records of %u words off a list of %llu: %s\n", (unsigned long long)*n_records, nwk, (unsigned long long)n_tiles,
+                fused ? "made by their first partition pass" : !fused_records_on() ? "written (KATOME_FUSED_RECORDS=0)"
+                : extra_room ? "written (left-over windows go behind them)" : !counted ? "written (no counts for the first pass)"
+                : !*n_records ? "written (none)" : "written (this shape's first pass reads records)");
+    const uint32_t tile_keys = dev_sort_tile_keys(nwk);
+    const uint64_t n_out_tiles = (*n_records + tile_keys - 1) / tile_keys;
+    const dim3 hgrid(grid_for(n_out_tiles, 1, 256u * 32u)), block(BLOCK);
+    if (fused) {
+        keys.release(); weights.release();
+        KCHECK(first_counts->alloc(n_out_tiles * 256 * 4 + 16, stream));
+        const uint32_t inv = (uint32_t)((1ull << 32) / span) + 1;
+        KernelScope ks(K_RECORDS, stream, n_tiles);
+#define KATOME_LDC(NWT, NWK, REP) with_bool(rc, [&](auto rcv) { hipLaunchKernelGGL((list_digit_counts_kernel<NWT, NWK, decltype(rcv)::value, REP>), hgrid, block, 0, stream, d_tiles, n_tiles, k, span, stride, inv, tile_keys, first_counts->as<u32>()); return 0; })
+        if (rep) { if (nwt == 2) KATOME_LDC(2, 1, true); else KATOME_LDC(1, 1, true); }
+        else KATOME_LDC(2, 2, false);
+#undef KATOME_LDC
+        KCHECK_HIP(hipGetLastError());
+        src->tiles = d_tiles; src->counts = d_counts; src->n_tiles = n_tiles;
+        src->tile_bases = tile_bases; src->k = k; src->span = span; src->stride = stride; src->rc = rc; src->rep = rep;
+        src->keys = &keys; src->weights = &weights; src->key_bytes = (*n_records + 1) * 8 * nwk; src->weight_bytes = (*n_records + 1) * 4;
+        src->stream = stream; src->pending = true;
+        return KATOME_OK;
+    }
     KCHECK(keys.alloc((*n_records + extra_room + 1) * 8 * nwk, stream));
     KCHECK(weights.alloc((*n_records + extra_room + 1) * 4, stream));
     if (*n_records == 0) return KATOME_OK;
-    // (first_counts: the caller sorts exactly these records next -- nothing appended -- and wants the first pass's digit counts per tile;
-    // KATOME_FUSED_HIST=0: the pass counts them itself)
-    if (first_counts && fused_hist_on() && !extra_room && ((nwt == 3 && nwk >= 2) || (nwt == 2 && nwk <= 2) || (nwt == 1 && nwk == 1))) {
-        const uint32_t tile_keys = dev_sort_tile_keys(nwk);
-        const uint64_t n_out_tiles = (*n_records + tile_keys - 1) / tile_keys;
+    if (counted) {
         KCHECK(first_counts->alloc(n_out_tiles * 256 * 4 + 16, stream));
-        const dim3 hgrid(grid_for(n_out_tiles, 1, 256u * 32u)), block(BLOCK);
         KernelScope ks(K_RECORDS, stream, n_tiles);
 #define KATOME_LRH(NWT, NWK, REP) with_bool(rc, [&](auto rcv) { hipLaunchKernelGGL((list_to_records_hist_kernel<NWT, NWK, decltype(rcv)::value, REP>), hgrid, block, 0, stream, d_tiles, d_counts, n_tiles, k, span, stride, keys.as<u64>(), weights.as<u32>(), tile_keys, first_counts->as<u32>()); return 0; })
         if (rep) { if (nwt == 2) KATOME_LRH(2, 1, true); else KATOME_LRH(1, 1, true); }      // (the ordered count's records: dev_key_order's first digit)
@@ -1070,19 +1166,7 @@ int table_list_to_records(const uint64_t* d_tiles, const uint32_t* d_counts, uin
         return KATOME_OK;
     }
     if (first_counts) first_counts->release();
-    const dim3 grid(grid_for(*n_records, BLOCK, 256u * 32u)), block(BLOCK);
-    KernelScope ks(K_RECORDS, stream, n_tiles);
-#define KATOME_LR(NWT, NWK, REP) with_bool(rc, [&](auto rcv) { hipLaunchKernelGGL((list_to_records_kernel<NWT, NWK, decltype(rcv)::value, REP>), grid, block, 0, stream, d_tiles, d_counts, n_tiles, k, span, stride, keys.as<u64>(), weights.as<u32>()); return 0; })
-    if (rep) { if (nwt == 2) KATOME_LR(2, 1, true); else KATOME_LR(1, 1, true); }
-    else if (nwt == 3 && nwk == 3) KATOME_LR(3, 3, false);
-    else if (nwt == 3 && nwk == 2) KATOME_LR(3, 2, false);
-    else if (nwt == 2 && nwk == 2) KATOME_LR(2, 2, false);
-    else if (nwt == 2 && nwk == 1) KATOME_LR(2, 1, false);
-    else if (nwt == 1 && nwk == 1) KATOME_LR(1, 1, false);
-    else { set_error("records of a tile list: tiles of %u words into windows of %u", nwt, nwk); return KATOME_E_UNSUPPORTED; }
-#undef KATOME_LR
-    KCHECK_HIP(hipGetLastError());
-    return KATOME_OK;
+    return launch_list_to_records(d_tiles, d_counts, n_tiles, nwt, nwk, k, span, stride, rc, rep, keys.as<u64>(), weights.as<u32>(), stream);
 }
 
 // the (k-mer, count) records of every distinct tile of the last level (no sequence numbers), written by the streaming kernel
