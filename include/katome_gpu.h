@@ -434,6 +434,89 @@ typedef struct {
 int katome_dev_shrink(katome_builder *b, katome_dev_contigs *out, void *stream);
 int katome_dev_shrink_mode(katome_builder *b, uint32_t mode, katome_dev_contigs *out, double *host_ms, void *stream);
 
+/* ---- collapse: the contigs, their text, FASTA and stats (collapser.rs:25-273, asm/mod.rs:57-72, stats/contigs.rs:31-89) --------
+ * Collapsable::collapse is `self.shrink()` followed by a walk that consumes edge weights one at a time and swap-removes edges
+ * and nodes as it goes: which contigs come out, and in which order, depends on petgraph's indices at every step.  As with the
+ * exact shrink that order is computed on one host core over petgraph's own layout (csrc/collapse_exact.h, after
+ * csrc/shrink_exact.h), which emits PIECES: piece p names the shrunk edge appended at step p (its index in the shrunk graph),
+ * with KATOME_PIECE_WHOLE set on a piece that begins a contig (EdgeSlice::name(), the whole label; every other piece is
+ * remainder(), the label from base k-1 on).  The number of pieces is the sum of the shrunk edges' weights.  The text is
+ * written on the device (csrc/collapse.hip), partitioned by output bytes, in one of two layouts:
+ *   KATOME_TEXT_PLAIN: the contigs back to back, ASCII ACGT;
+ *   KATOME_TEXT_FASTA: byte for byte what Contigs::save_to_file writes: record i = ">katome_<i>\n<contig>\n".
+ * d_contig_off[i] = offset of contig i's first base in d_text, d_contig_len[i] = its bases; d_text holds text_bytes bytes
+ * (the buffer is a multiple of 16 bytes; what lies past text_bytes is unspecified).                                    */
+#define KATOME_TEXT_PLAIN 0u
+#define KATOME_TEXT_FASTA 1u
+#define KATOME_PIECE_WHOLE 0x80000000u
+typedef struct {
+    uint64_t  n_contigs, text_bytes;
+    uint32_t  layout, _pad;
+    uint64_t *d_contig_off;
+    uint32_t *d_contig_len;
+    uint8_t  *d_text;
+} katome_dev_assembly;
+typedef struct {
+    uint64_t n_pieces, n_contigs;
+    uint64_t nodes_left, edges_left;     /* what the walk left of the graph: (0, 0)                                    */
+    uint64_t steps;                      /* iterations of contigs_from_vertex's loop that appended an edge              */
+    uint64_t ambiguity_cuts;             /* contigs ended at an ambiguous vertex                                        */
+    uint64_t self_loops, simple_loops;   /* taken                                                                       */
+    uint64_t scc_restarts;               /* starts from tarjan_scc(..).last()[0] (no vertex without incoming edges left) */
+    uint64_t nodes_removed;
+    uint64_t ambiguity_moves;            /* removals that copied a set ambiguity bit of the last node onto a lower index */
+    uint64_t shrunk_nodes, shrunk_edges; /* the graph after the shrink collapse starts with                             */
+    double   shrink_host_ms;             /* one host core: ShrinkExact                                                  */
+    double   host_ms;                    /* one host core: the walk                                                     */
+    double   text_ms;                    /* wall time of measuring, scanning and writing the text on the device         */
+} katome_collapse_stats;
+/* collapse() of the finalized graph as it stands (after finalize or any of the pruning / standardize stages), in either
+ * numbering: on a by-key builder it is the reference's collapse of THAT graph (no edge ages: index order).  The exact shrink
+ * inside is katome_dev_shrink_mode(KATOME_SHRINK_EXACT)'s.  The builder's graph is left untouched; the result arrays are owned
+ * by the builder until its next katome_dev_collapse or destroy.  An edge of weight 0 (the reference's decrement would wrap):
+ * KATOME_E_ARG.  2^31 pieces or more, or a contig of 2^32 bases or more: KATOME_E_UNSUPPORTED, with the number; pieces that do
+ * not fit host memory: KATOME_E_OOM.  No edges: zero contigs, KATOME_OK.  `stats` may be NULL.  Profile phase "collapse",
+ * kernel "k:text_write_kernel".  Synchronises.                                                                         */
+int katome_dev_collapse(katome_builder *b, uint32_t layout, katome_dev_assembly *out, katome_collapse_stats *stats, void *stream);
+/* the text of a shrink result (fast or exact), one contig per merged edge, each its whole label: no piece list.  `contigs` is
+ * what katome_dev_shrink / katome_dev_shrink_mode of this builder returned last.  Result owned by the builder until its next
+ * katome_dev_contigs_text or destroy.                                                                                  */
+int katome_dev_contigs_text(katome_builder *b, const katome_dev_contigs *contigs, uint32_t layout, katome_dev_assembly *out,
+                            void *stream);
+/* Contigs::stats (stats/contigs.rs:31-89) from the contigs' lengths: host, pure.  No contigs: all zeros.  A tipping point of 0
+ * with contigs present (sum / 2, (0.1 * sum) truncated, original_genome_length / 2), where the reference panics on
+ * `.last().unwrap()`: KATOME_E_ARG, with a message that names which one.                                               */
+typedef struct { uint64_t n50, l50, n90, ng50; } katome_contig_stats;
+int katome_contig_stats_of(const uint64_t *lengths, uint64_t n, uint64_t original_genome_length, katome_contig_stats *out);
+
+/* BasicAsm::assemble (asm/basic_assembler.rs:58-80) in host memory: the build, the stages "dcwced" with settings.min_weight and
+ * original_genome_length, collapse, Contigs::stats and -- with out_path -- Contigs::save_to_file.  Needs
+ * KATOME_FLAG_FIRST_SEEN_ORDER, like the staged entries.  The text is in KATOME_TEXT_FASTA layout: text[0, text_bytes) is the
+ * file, contig i its bytes [contig_off[i], contig_off[i] + contig_len[i]).  Owned by the library until katome_assembly_free.
+ * Errors, one status per panic site: the build's and the stages' as for katome_build_*_staged; a tipping point of 0 in the
+ * stats (see katome_contig_stats_of): KATOME_E_ARG; a path that cannot be created: KATOME_E_OPEN, "couldn't create <path>:
+ * <why>" (asm/mod.rs:62) -- the assembly is then still handed back when `out` is given.  With settings.n_devices > 1 the graph
+ * is built sharded, gathered to the first GPU in the reference's numbering, and the stages and collapse run there; a graph that
+ * cannot be gathered (2^32 edges or nodes) gives KATOME_E_UNSUPPORTED with a message that says so (collapse on the sharded
+ * graph is out of scope).                                                                                               */
+typedef struct {
+    uint64_t n_contigs, text_bytes, read_bytes;
+    uint32_t k, layout;
+    const uint64_t *contig_off;
+    const uint32_t *contig_len;
+    const uint8_t  *text;
+    katome_contig_stats   stats;
+    katome_collapse_stats collapse;
+} katome_assembly;
+int  katome_assemble_files(const katome_settings *s, const char *const *paths, size_t n_paths, uint64_t original_genome_length,
+                           const char *out_path /* nullable */, katome_assembly **out);
+int  katome_assemble_packed(const katome_settings *s, const uint8_t *packed, uint64_t n_reads, uint32_t read_len,
+                            const uint8_t *skip, uint64_t original_genome_length, const char *out_path /* nullable */,
+                            katome_assembly **out);
+/* Contigs::save_to_file (asm/mod.rs:57-72): KATOME_E_OPEN when the path cannot be created */
+int  katome_assembly_save(const katome_assembly *a, const char *path);
+void katome_assembly_free(katome_assembly *a);
+
 /* first half of finalize only: sorted distinct edges (key, weight); used by the multi-GPU
  * driver, which resolves node ids across ranks itself                                      */
 int katome_dev_edges(katome_builder *b, uint64_t **d_edge_key, uint32_t **d_edge_weight,
@@ -711,6 +794,19 @@ int katome_dev_endpoints(int device, const uint64_t *d_edge_key, uint64_t n, uin
 /* compress_edge-format labels (compress.rs:250-271) of packed k-mers                       */
 int katome_dev_labels(int device, const uint64_t *d_edge_key, uint64_t n, uint32_t k,
                       uint8_t *d_label, void *stream);
+/* the text kernel on the caller's arrays: n_labels labels in compress_edge format (compress.rs:250-271), label i at bytes
+ * [d_label_off[i], d_label_off[i + 1]) of d_label, and n_pieces pieces (see katome_dev_collapse; d_pieces NULL: piece p = label p,
+ * whole).  *n_contigs and *text_bytes are always set.  d_text NULL: nothing else is written (a size query).  Otherwise
+ * d_contig_off / d_contig_len need room for contig_cap >= *n_contigs entries and d_text, 16-byte aligned, for text_cap >=
+ * *text_bytes rounded up to 16 (KATOME_E_ARG when they are too small).  d_label must be 4-byte aligned and lie in an allocation
+ * whose size is a multiple of 4 (KATOME_E_ARG for a misaligned pointer): the kernel reads the aligned 32-bit words that hold the
+ * bytes it needs, so up to 3 bytes on either side of a label inside those words are read and ignored.  A piece that names no label, a label shorter than k bases
+ * or malformed offsets: KATOME_E_ARG, before anything is read through them.  n_pieces >= 2^31 or a contig of 2^32 bases or more:
+ * KATOME_E_UNSUPPORTED.  Synchronises. */
+int katome_dev_pieces_text(int device, uint32_t k, const uint8_t *d_label, const uint64_t *d_label_off, uint64_t n_labels,
+                           const uint32_t *d_pieces, uint64_t n_pieces, uint32_t layout, uint64_t *d_contig_off,
+                           uint32_t *d_contig_len, uint64_t contig_cap, uint8_t *d_text, uint64_t text_cap, uint64_t *n_contigs,
+                           uint64_t *text_bytes, void *stream);
 /* Stats<CollectionStats>::stats for PtGraph (stats/collections.rs:137-168) from device arrays, filled exactly as
  * katome_graph_stats fills it from host arrays: u64 sums, the two averages one f64 division each on the host (no edges:
  * avg_edge_weight is NaN, no nodes: avg_out_degree is NaN, as the reference's 0.0 / 0.0); externals(Incoming) and

@@ -58,6 +58,28 @@ class DevContigs(C.Structure):
                 ("d_node_key", C.c_void_p)]
 
 
+class DevAssembly(C.Structure):
+    _fields_ = [("n_contigs", C.c_uint64), ("text_bytes", C.c_uint64), ("layout", C.c_uint32), ("_pad", C.c_uint32),
+                ("d_contig_off", C.c_void_p), ("d_contig_len", C.c_void_p), ("d_text", C.c_void_p)]
+
+
+class CollapseStats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("n_pieces", "n_contigs", "nodes_left", "edges_left", "steps", "ambiguity_cuts", "self_loops",
+                                          "simple_loops", "scc_restarts", "nodes_removed", "ambiguity_moves", "shrunk_nodes",
+                                          "shrunk_edges")] + [("shrink_host_ms", C.c_double), ("host_ms", C.c_double),
+                                                              ("text_ms", C.c_double)]
+
+
+class ContigStats(C.Structure):
+    _fields_ = [("n50", C.c_uint64), ("l50", C.c_uint64), ("n90", C.c_uint64), ("ng50", C.c_uint64)]
+
+
+class Assembly(C.Structure):
+    _fields_ = [("n_contigs", C.c_uint64), ("text_bytes", C.c_uint64), ("read_bytes", C.c_uint64), ("k", C.c_uint32),
+                ("layout", C.c_uint32), ("contig_off", u64p), ("contig_len", u32p), ("text", u8p), ("stats", ContigStats),
+                ("collapse", CollapseStats)]
+
+
 class DevGraph(C.Structure):
     _fields_ = [("n_nodes", C.c_uint64), ("n_edges", C.c_uint64), ("key_words", C.c_uint32),
                 ("label_stride", C.c_uint32), ("d_edge_key", C.c_void_p), ("d_edge_weight", C.c_void_p),
@@ -155,6 +177,14 @@ SYMBOLS = {
     "katome_dev_standardize_edges": (_i, [_vp, _u64, _u32, _vp]),
     "katome_dev_shrink": (_i, [_vp, C.POINTER(DevContigs), _vp]),
     "katome_dev_shrink_mode": (_i, [_vp, C.c_uint32, C.POINTER(DevContigs), C.POINTER(C.c_double), _vp]),
+    "katome_dev_collapse": (_i, [_vp, _u32, C.POINTER(DevAssembly), C.POINTER(CollapseStats), _vp]),
+    "katome_dev_contigs_text": (_i, [_vp, C.POINTER(DevContigs), _u32, C.POINTER(DevAssembly), _vp]),
+    "katome_dev_pieces_text": (_i, [_i, _u32, _vp, _vp, _u64, _vp, _u64, _u32, _vp, _vp, _u64, _vp, _u64, u64p, u64p, _vp]),
+    "katome_contig_stats_of": (_i, [u64p, _u64, _u64, C.POINTER(ContigStats)]),
+    "katome_assemble_files": (_i, [C.POINTER(Settings), _pp, _sz, _u64, C.c_char_p, C.POINTER(C.POINTER(Assembly))]),
+    "katome_assemble_packed": (_i, [C.POINTER(Settings), _vp, _u64, _u32, _vp, _u64, C.c_char_p, C.POINTER(C.POINTER(Assembly))]),
+    "katome_assembly_save": (_i, [C.POINTER(Assembly), C.c_char_p]),
+    "katome_assembly_free": (None, [C.POINTER(Assembly)]),
     "katome_dev_current_graph": (_i, [_vp, C.POINTER(DevGraph)]),
     "katome_dev_graph_stats": (_i, [_vp, C.POINTER(Stats), _vp]),
     "katome_dev_weight_spectrum": (_i, [_vp, u64p, _u32, _vp]),

@@ -118,6 +118,58 @@ def collection_stats(st, capacity=(0, None)) -> CollectionStats:
         outgoing_vert_count=st.outgoing_vert_count, capacity=capacity)
 
 
+class ContigsStats:
+    """stats/contigs.rs:11-23"""
+
+    def __init__(self, n50=0, l50=0, n90=0, ng50=0):
+        self.n50, self.l50, self.n90, self.ng50 = n50, l50, n90, ng50
+
+    def astuple(self):
+        return (self.n50, self.l50, self.n90, self.ng50)
+
+    def __eq__(self, other):
+        return self.astuple() == (other.astuple() if isinstance(other, ContigsStats) else tuple(other))
+
+    def __repr__(self):
+        return "ContigsStats(n50=%d, l50=%d, n90=%d, ng50=%d)" % self.astuple()
+
+
+def contig_stats(lengths, genome_length) -> ContigsStats:
+    """Contigs::stats (stats/contigs.rs:31-89) from the contigs' lengths (katome_contig_stats_of: host, pure); a tipping point of
+    0 with contigs present, where the reference panics, raises KatomePanic(E_ARG)"""
+    a = np.ascontiguousarray(lengths, dtype=np.uint64)
+    st = _lib.ContigStats()
+    _check(_lib.lib().katome_contig_stats_of(a.ctypes.data_as(_lib.u64p), len(a), int(genome_length), C.byref(st)))
+    return ContigsStats(st.n50, st.l50, st.n90, st.ng50)
+
+
+class Assembly:
+    """result of GpuGraph.assemble: the contigs (list of str, in the reference's order), the FASTA text Contigs::save_to_file
+    writes, Contigs::stats, number_of_read_bytes and the collapse walk's counters.  Keeps the C result until it is collected."""
+
+    def __init__(self, ap):
+        self._ap = ap
+        a = ap.contents
+        nc, nb = a.n_contigs, a.text_bytes
+        self.k, self.read_bytes, self.n_contigs = a.k, a.read_bytes, nc
+        self.fasta = bytes(np.ctypeslib.as_array(a.text, (nb,))) if nb else b""
+        off = np.ctypeslib.as_array(a.contig_off, (nc,)).tolist() if nc else []
+        length = np.ctypeslib.as_array(a.contig_len, (nc,)).tolist() if nc else []
+        self.contigs = [self.fasta[o:o + n].decode() for o, n in zip(off, length)]
+        self.stats = ContigsStats(a.stats.n50, a.stats.l50, a.stats.n90, a.stats.ng50)
+        self.collapse_stats = {f: getattr(a.collapse, f) for f, _ in _lib.CollapseStats._fields_}
+
+    def save_to_file(self, path):
+        """Contigs::save_to_file (asm/mod.rs:57-72; katome_assembly_save): a path that cannot be created raises KatomePanic(E_OPEN)"""
+        _check(_lib.lib().katome_assembly_save(self._ap, os.fsencode(path)))
+
+    def __del__(self):
+        try:
+            _lib.lib().katome_assembly_free(self._ap)
+        except Exception:       # interpreter shutdown
+            pass
+
+
 FLAG_FIRST_SEEN_ORDER = 1
 FLAG_REMOVE_DEAD_PATHS = 2
 FLAG_RANKS_SHARE_DEVICE = 4
@@ -256,6 +308,43 @@ class GpuGraph:
         if described is not None:
             g.stage_stats = [collection_stats(st) for st in described]
         return g, g.read_bytes
+
+    # ---- BasicAsm::assemble (asm/basic_assembler.rs:17-27,58-80) ----------------------------------
+    @staticmethod
+    def assemble(input_files, ft, reverse_complement, minimal_weight_threshold, original_genome_length, output_file=None, device=0,
+                 n_devices=1, ranks_share_device=False):
+        """the build in the reference's numbering, the stages "dcwced", collapse, Contigs::stats and -- with output_file --
+        Contigs::save_to_file, all behind one call (katome_assemble_files) -> Assembly; uses the global k"""
+        s = make_settings(K_SIZE, ft, reverse_complement, minimal_weight_threshold, device, first_seen_order=True, n_devices=n_devices,
+                          ranks_share_device=ranks_share_device)
+        ap = C.POINTER(_lib.Assembly)()
+        rc = _lib.lib().katome_assemble_files(C.byref(s), _paths(input_files), len(input_files), original_genome_length,
+                                              os.fsencode(output_file) if output_file is not None else None, C.byref(ap))
+        if rc != 0:
+            if ap:                      # (a path that could not be created: the assembly was made all the same)
+                _lib.lib().katome_assembly_free(ap)
+            _check(rc)
+        return Assembly(ap)
+
+    @staticmethod
+    def assemble_from_packed(packed, n_reads, read_len, skip=None, reverse_complement=False, minimal_weight_threshold=0,
+                             original_genome_length=0, output_file=None, device=0, k=None, n_devices=1, ranks_share_device=False):
+        """the same from 2-bit packed reads (numpy uint8; katome_assemble_packed)"""
+        s = make_settings(K_SIZE if k is None else k, InputFileType.Fastq, reverse_complement, minimal_weight_threshold, device,
+                          first_seen_order=True, n_devices=n_devices, ranks_share_device=ranks_share_device)
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        skip_p = None
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.uint8)
+            skip_p = skip.ctypes.data
+        ap = C.POINTER(_lib.Assembly)()
+        rc = _lib.lib().katome_assemble_packed(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, original_genome_length,
+                                               os.fsencode(output_file) if output_file is not None else None, C.byref(ap))
+        if rc != 0:
+            if ap:                      # (a path that could not be created: the assembly was made all the same)
+                _lib.lib().katome_assembly_free(ap)
+            _check(rc)
+        return Assembly(ap)
 
     # ---- Stats<CollectionStats> (stats/collections.rs:137-168) ---------------------------------
     def stats(self) -> CollectionStats:

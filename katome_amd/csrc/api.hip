@@ -1626,6 +1626,73 @@ int katome_dev_shrink_mode(katome_builder* b, uint32_t mode, katome_dev_contigs*
     return KATOME_OK;
 }
 
+}  // extern "C"
+
+static void assembly_view(const TextOutput& t, katome_dev_assembly* out) {
+    memset(out, 0, sizeof *out);
+    out->n_contigs = t.n_contigs; out->text_bytes = t.text_bytes; out->layout = t.layout;
+    out->d_contig_off = t.contig_off.as<u64>(); out->d_contig_len = t.contig_len.as<u32>(); out->d_text = t.text.as<uint8_t>();
+}
+// (lengths: the contigs' bases as the walk knows them -- host_build.cpp's stats need no copy from the device)
+int builder_collapse(katome_builder* b, uint32_t layout, katome_dev_assembly* out, katome_collapse_stats* stats, std::vector<uint64_t>* lengths,
+                     hipStream_t stream) {
+    KCHECK_HIP(hipSetDevice(b->s.device));
+    if (!b->finalized) { set_error("collapse: call katome_dev_finalize first"); return KATOME_E_ARG; }
+    ShrinkInput in{b->edge_src.as<u64>(), b->edge_dst.as<u64>(), b->edge_weight.as<u32>(), b->edge_key.as<u64>(), b->node_key.as<u64>(),
+                   b->n_edges, b->n_nodes, b->nw, b->s.k};
+    {
+        PhaseScope ps(b->prof, PH_COLLAPSE, stream);
+        KCHECK(dev_collapse(in, b->edge_age.p ? b->edge_age.as<u32>() : nullptr, b->collapse_shrunk, layout, b->assembly, stats, lengths, stream));
+    }
+    if (out) assembly_view(b->assembly, out);
+    return KATOME_OK;
+}
+
+extern "C" {
+
+int katome_dev_collapse(katome_builder* b, uint32_t layout, katome_dev_assembly* out, katome_collapse_stats* stats, void* stream_) {
+    if (!b || !out) { set_error("null argument"); return KATOME_E_ARG; }
+    return builder_collapse(b, layout, out, stats, nullptr, (hipStream_t)stream_);
+}
+int katome_dev_contigs_text(katome_builder* b, const katome_dev_contigs* c, uint32_t layout, katome_dev_assembly* out, void* stream_) {
+    if (!b || !c || !out) { set_error("null argument"); return KATOME_E_ARG; }
+    hipStream_t stream = (hipStream_t)stream_;
+    KCHECK_HIP(hipSetDevice(b->s.device));
+    if (c->n_edges != b->shrunk.n_edges || c->d_edge_label != b->shrunk.edge_label.as<uint8_t>() || c->d_edge_label_off != b->shrunk.edge_label_off.as<u64>()) {
+        set_error("contigs_text: not the result of this builder's last katome_dev_shrink");
+        return KATOME_E_ARG;
+    }
+    {
+        PhaseScope ps(b->prof, PH_COLLAPSE, stream);
+        KCHECK(dev_pieces_text(b->s.k, c->d_edge_label, c->d_edge_label_off, c->n_edges, nullptr, c->n_edges, layout, b->unitig_text, stream));
+    }
+    assembly_view(b->unitig_text, out);
+    return KATOME_OK;
+}
+int katome_dev_pieces_text(int device, uint32_t k, const uint8_t* d_label, const uint64_t* d_label_off, uint64_t n_labels, const uint32_t* d_pieces,
+                           uint64_t n_pieces, uint32_t layout, uint64_t* d_contig_off, uint32_t* d_contig_len, uint64_t contig_cap, uint8_t* d_text,
+                           uint64_t text_cap, uint64_t* n_contigs, uint64_t* text_bytes, void* stream_) {
+    KCHECK(use_device(device));
+    KCHECK(check_k(k));
+    if (!n_contigs || !text_bytes) { set_error("null argument"); return KATOME_E_ARG; }
+    *n_contigs = *text_bytes = 0;
+    hipStream_t stream = (hipStream_t)stream_;
+    if ((uintptr_t)d_label & 3) { set_error("text: d_label must be 4-byte aligned (the kernel reads the aligned words around the bytes it needs)"); return KATOME_E_ARG; }
+    if (!d_pieces && n_pieces && n_pieces != n_labels) { set_error("text: without pieces there is one per label"); return KATOME_E_ARG; }
+    TextPlan plan;
+    KCHECK(dev_text_plan(k, d_label, d_label_off, n_labels, d_pieces, n_pieces, layout, plan, stream));
+    *n_contigs = plan.n_contigs; *text_bytes = plan.text_bytes;
+    if (!d_text || plan.text_bytes == 0) return KATOME_OK;
+    if (!d_contig_off || !d_contig_len || contig_cap < plan.n_contigs || text_cap < (plan.text_bytes + 15) / 16 * 16 || ((uintptr_t)d_text & 15)) {
+        set_error("text: %llu contigs and %llu bytes (rounded up to 16, 16-byte aligned) do not fit the caller's arrays", (unsigned long long)plan.n_contigs,
+                  (unsigned long long)plan.text_bytes);
+        return KATOME_E_ARG;
+    }
+    KCHECK(dev_text_write(k, d_label, d_label_off, d_pieces, n_pieces, layout, plan, d_contig_off, d_contig_len, d_text, stream));
+    KCHECK_HIP(hipStreamSynchronize(stream));
+    return KATOME_OK;
+}
+
 int katome_dev_current_graph(katome_builder* b, katome_dev_graph* out) {
     if (!b || !out) { set_error("null argument"); return KATOME_E_ARG; }
     if (!b->finalized) { set_error("katome_dev_current_graph: call katome_dev_finalize first"); return KATOME_E_ARG; }

@@ -78,6 +78,9 @@ struct katome_builder {
     // finalized graph
     DevBuf edge_src, edge_dst, edge_label, node_key;
     ShrinkOutput shrunk;               // result of katome_dev_shrink
+    ShrinkOutput collapse_shrunk;      // katome_dev_collapse: the shrunk graph its pieces name ...
+    TextOutput assembly;               // ... and its result
+    TextOutput unitig_text;            // result of katome_dev_contigs_text
     DevBuf edge_age;                   // first-seen-order graphs once remove_* has moved edges (PruneGraph::edge_age)
     uint64_t n_nodes = 0;
     bool finalized = false;
@@ -112,5 +115,8 @@ uint32_t mid_span(uint32_t span);      // span of the mid tiles a big tile is br
 #define KATOME_INTERNAL __attribute__((visibility("hidden")))
 // BFCounter input: one edge per kept line and strand; leaves the builder with its sorted edge list
 KATOME_INTERNAL int bfc_set_edges(katome_builder* b, const uint64_t* d_fwd, const uint32_t* d_w, uint64_t n_lines, hipStream_t stream);
+// katome_dev_collapse, also handing back every contig's length in bases (host: the walk knows them)
+KATOME_INTERNAL int builder_collapse(katome_builder* b, uint32_t layout, katome_dev_assembly* out, katome_collapse_stats* stats,
+                                     std::vector<uint64_t>* lengths, hipStream_t stream);
 // one tile span for reads of several lengths (none shorter than k), by katome_tile_plan's charges; 1: no tiles
 KATOME_INTERNAL uint32_t tile_span_for_lengths(uint32_t k, const uint32_t* len, uint64_t n_reads, uint64_t total_windows);

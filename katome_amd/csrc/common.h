@@ -100,6 +100,7 @@ enum Phase { PH_EXTRACT, PH_REGION_ORDER, PH_INSERT, PH_EMIT_EDGES, PH_SORT_EDGE
              K_TILE_HASH_SCATTER, K_TILE_HASH_HIST, K_TILE_RECORDS, K_TILE_GROUP_INDEX, K_TILE_LDS_COUNT, K_HALF_MERGE, K_GROUP_MERGE,
              // (appended: the indices above are what callers of katome_phase_name have seen so far)
              PH_GRAPH_STATS, PH_WEIGHT_SPECTRUM, K_STATS_DEGREES, K_STATS_WEIGHTS, K_STATS_NODES, K_SPECTRUM,
+             PH_COLLAPSE, K_TEXT_WRITE,
              PH_COUNT };
 static const char* const PHASE_NAMES[PH_COUNT] = {
     "extract", "region_order", "insert", "emit_edges", "sort_edges", "node_set", "rank", "labels", "insert_tiles", "expand_tiles",
@@ -114,7 +115,8 @@ static const char* const PHASE_NAMES[PH_COUNT] = {
     "k:radix_scatter_kernel<HashDigit> (tile records)", "k:radix_hist_kernel<HashDigit> (tile records)", "k:tiles_to_records_kernel (tile records)",
     "k:hash_group_index_kernel (tile records)", "k:lds_count_kernel (tile records)", "k:half_merge_kernel",
     "k:group_merge_kernel",
-    "graph_stats", "weight_spectrum", "k:stats_degree_kernel", "k:stats_weight_kernel", "k:stats_node_kernel", "k:spectrum_kernel"};
+    "graph_stats", "weight_spectrum", "k:stats_degree_kernel", "k:stats_weight_kernel", "k:stats_node_kernel", "k:spectrum_kernel",
+    "collapse", "k:text_write_kernel"};
 struct Profiler {
     bool on = false;
     struct Ev { int phase; hipEvent_t a, b; uint64_t work; };      // work: elements the launch processed (K_* entries)
@@ -408,7 +410,30 @@ struct ShrinkOutput {
 };
 int dev_shrink(const ShrinkInput& g, ShrinkOutput& out, hipStream_t stream);
 // the reference's own result: its cuts and petgraph's numbering (shrink_exact.h on the host for the order, the device for the bytes)
-int dev_shrink_exact(const ShrinkInput& g, const uint32_t* edge_age, ShrinkOutput& out, double* host_ms, hipStream_t stream);
+// (keep / kept: the caller's ShrinkExact is used and left as run() leaves it, with the nodes it kept -- where collapse starts)
+struct ShrinkExact;
+int dev_shrink_exact(const ShrinkInput& g, const uint32_t* edge_age, ShrinkOutput& out, double* host_ms, hipStream_t stream,
+                     ShrinkExact* keep = nullptr, std::vector<uint32_t>* kept = nullptr);
+
+// collapse.hip: Collapsable::collapse (collapser.rs:25-273): the walk on the host (collapse_exact.h), the text on the device
+struct TextOutput {
+    DevBuf contig_off, contig_len, text;
+    uint64_t n_contigs = 0, text_bytes = 0;
+    uint32_t layout = 0;
+};
+// sizes of the text of `n_pieces` pieces over `n_labels` labels (validated on the device first): every piece's contig (contig_idx) and output offset (piece_off), both scanned, one entry more than pieces
+struct TextPlan {
+    DevBuf contig_idx, piece_off;
+    uint64_t n_contigs = 0, text_bytes = 0;
+};
+int dev_text_plan(uint32_t k, const uint8_t* label, const uint64_t* label_off, uint64_t n_labels, const uint32_t* pieces, uint64_t n_pieces,
+                  uint32_t layout, TextPlan& plan, hipStream_t stream);
+int dev_text_write(uint32_t k, const uint8_t* label, const uint64_t* label_off, const uint32_t* pieces, uint64_t n_pieces, uint32_t layout,
+                   const TextPlan& plan, uint64_t* contig_off, uint32_t* contig_len, uint8_t* text, hipStream_t stream);
+int dev_pieces_text(uint32_t k, const uint8_t* label, const uint64_t* label_off, uint64_t n_labels, const uint32_t* pieces, uint64_t n_pieces,
+                    uint32_t layout, TextOutput& out, hipStream_t stream);
+int dev_collapse(const ShrinkInput& g, const uint32_t* edge_age, ShrinkOutput& shrunk, uint32_t layout, TextOutput& out,
+                 katome_collapse_stats* stats, std::vector<uint64_t>* lengths, hipStream_t stream);
 
 constexpr int KATOME_MAX_RANKS = 16;      // ranks of a sharded build (an MI355X node has 8 GPUs)
 

@@ -16,8 +16,11 @@
 
 #include <sys/mman.h>
 
+#include <errno.h>
+
 #include "builder.h"
 #include "comm.h"
+#include "contig_stats.h"
 #include "multi_route.h"
 
 extern "C" {
@@ -41,6 +44,17 @@ struct ContigsOwner {          // katome_contigs followed by what it owns
 void katome_contigs_free(katome_contigs* c) {
     if (!c) return;
     ContigsOwner* o = reinterpret_cast<ContigsOwner*>(c);
+    for (void* p : o->mem) free(p);
+    delete o;
+}
+
+struct AssemblyOwner {         // katome_assembly followed by what it owns
+    katome_assembly a;
+    std::vector<void*> mem;
+};
+void katome_assembly_free(katome_assembly* a) {
+    if (!a) return;
+    AssemblyOwner* o = reinterpret_cast<AssemblyOwner*>(a);
     for (void* p : o->mem) free(p);
     delete o;
 }
@@ -248,13 +262,74 @@ static int contigs_to_host(katome_builder* b, uint64_t read_bytes, katome_contig
     return KATOME_OK;
 }
 
-// what a host entry hands back: the graph, or the graph after shrink
+extern "C" int katome_contig_stats_of(const uint64_t* lengths, uint64_t n, uint64_t original_genome_length, katome_contig_stats* out) {
+    if (!out || (n && !lengths)) { set_error("null argument"); return KATOME_E_ARG; }
+    ContigStats st;
+    const int which = contig_stats(lengths, n, original_genome_length, &st);
+    out->n50 = st.n50; out->l50 = st.l50; out->n90 = st.n90; out->ng50 = st.ng50;
+    if (which) {
+        static const char* const names[] = {"", "n50 (sum of the lengths / 2)", "n90 (0.1 * sum of the lengths, truncated)", "ng50 (original_genome_length / 2)"};
+        set_error("called `Option::unwrap()` on a `None` value: the tipping point of %s is 0", names[which]);       // stats/contigs.rs:86-88
+        return KATOME_E_ARG;
+    }
+    return KATOME_OK;
+}
+
+// Contigs::save_to_file (asm/mod.rs:57-72): the text in FASTA layout is the file
+extern "C" int katome_assembly_save(const katome_assembly* a, const char* path) {
+    if (!a || !path) { set_error("null argument"); return KATOME_E_ARG; }
+    if (a->layout != KATOME_TEXT_FASTA) { set_error("assembly_save: the text is not in FASTA layout"); return KATOME_E_ARG; }
+    FILE* f = fopen(path, "wb");
+    if (!f) {
+        const int e = errno;                   // io::Error::description() of the kinds File::create meets
+        const char* why = e == ENOENT ? "entity not found" : (e == EACCES || e == EPERM) ? "permission denied" : e == EEXIST ? "entity already exists" : "other os error";
+        set_error("couldn't create %s: %s", path, why);      // asm/mod.rs:62
+        return KATOME_E_OPEN;
+    }
+    const size_t n = a->text_bytes ? fwrite(a->text, 1, a->text_bytes, f) : 0;
+    if (fclose(f) != 0 || n != a->text_bytes) { set_error("couldn't write %s", path); return KATOME_E_OPEN; }
+    return KATOME_OK;
+}
+
+// the stages "dcwced" (asm/basic_assembler.rs:58-75), collapse, Contigs::stats and, with a path, save_to_file: host arrays
+struct AssembleWant { katome_assembly** out; const char* path; };
+static int assembly_to_host(katome_builder* b, uint64_t read_bytes, const AssembleWant& want, uint64_t genome_len) {
+    katome_dev_graph dg;
+    if (!b->first_seen) { set_error("assemble needs KATOME_FLAG_FIRST_SEEN_ORDER"); return KATOME_E_ARG; }
+    KCHECK(katome_dev_finalize(b, &dg, nullptr));
+    if (b->s.flags & KATOME_FLAG_REMOVE_DEAD_PATHS) KCHECK(katome_dev_remove_dead_paths(b, &dg, nullptr, nullptr));
+    KCHECK(run_stages("dcwced", BuilderStages{b, genome_len}));
+    build_lap("build and stages");
+    AssemblyOwner* o = new (std::nothrow) AssemblyOwner();
+    if (!o) { set_error("out of host memory"); return KATOME_E_OOM; }
+    memset(&o->a, 0, sizeof o->a);
+    katome_assembly* a = &o->a;
+    katome_dev_assembly da;
+    memset(&da, 0, sizeof da);
+    std::vector<uint64_t> lengths;
+    int rc = builder_collapse(b, KATOME_TEXT_FASTA, &da, &a->collapse, &lengths, nullptr);
+    build_lap("collapse");
+    a->n_contigs = da.n_contigs; a->text_bytes = da.text_bytes; a->read_bytes = read_bytes; a->k = b->s.k; a->layout = KATOME_TEXT_FASTA;
+    if (!rc) rc = d2h(o, &a->contig_off, da.d_contig_off, da.n_contigs);
+    if (!rc) rc = d2h(o, &a->contig_len, da.d_contig_len, da.n_contigs);
+    if (!rc) rc = d2h(o, &a->text, da.d_text, da.text_bytes);
+    if (!rc) rc = katome_contig_stats_of(lengths.data(), lengths.size(), genome_len, &a->stats);      // contigs.log_stats()
+    if (rc) { katome_assembly_free(a); return rc; }
+    if (want.out) *want.out = a;
+    rc = want.path ? katome_assembly_save(a, want.path) : KATOME_OK;
+    if (!want.out) katome_assembly_free(a);
+    return rc;
+}
+
+// what a host entry hands back: the graph, the graph after shrink, or the assembly
 struct Finish {
     katome_graph** graph; katome_contigs** contigs;
+    AssembleWant assemble{nullptr, nullptr}; bool assembling = false;
     const char* stages = nullptr; uint64_t genome_len = 0;
     uint32_t shrink_mode = KATOME_SHRINK_AUTO;
     katome_stats* stage_stats = nullptr;      // katome_build_*_staged_stats: the graph described before the first stage and after each
     int operator()(katome_builder* b, uint64_t read_bytes) const {
+        if (assembling) return assembly_to_host(b, read_bytes, assemble, genome_len);
         return contigs ? contigs_to_host(b, read_bytes, contigs, shrink_mode) : graph_to_host(b, read_bytes, graph, stages, genome_len, stage_stats);
     }
 };
@@ -489,7 +564,7 @@ template <class AddReads>
 static int build_multi(const katome_settings* s, const Finish& finish, uint64_t read_bytes, const AddReads& add_reads) {
     const int n = s->n_devices;
     const bool share = (s->flags & KATOME_FLAG_RANKS_SHARE_DEVICE) != 0;
-    const MultiRoute route = plan_multi_route(s->flags, finish.contigs != nullptr, finish.stages);
+    const MultiRoute route = plan_multi_route(s->flags, finish.contigs != nullptr, finish.stages, finish.assembling);
     if (n > KATOME_MAX_RANKS) { set_error("n_devices = %d: at most %d", n, KATOME_MAX_RANKS); return KATOME_E_UNSUPPORTED; }
     KCHECK(use_device(s->device));
     int n_visible = 0;
@@ -670,6 +745,14 @@ int katome_build_packed_staged_stats(const katome_settings* s, const uint8_t* pa
     f.stages = stages; f.genome_len = original_genome_length; f.stage_stats = stage_stats;
     return build_packed_impl(s, packed, n_reads, read_len, skip, f);
 }
+int katome_assemble_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip,
+                           uint64_t original_genome_length, const char* out_path, katome_assembly** out) {
+    if (!out && !out_path) { set_error("null argument"); return KATOME_E_ARG; }
+    if (out) *out = nullptr;
+    Finish f{nullptr, nullptr};
+    f.assemble = AssembleWant{out, out_path}; f.assembling = true; f.genome_len = original_genome_length;
+    return build_packed_impl(s, packed, n_reads, read_len, skip, f);
+}
 int katome_shrink_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len,
                          const uint8_t* skip, katome_contigs** out) {
     if (!out) { set_error("null argument"); return KATOME_E_ARG; }
@@ -819,6 +902,14 @@ int katome_build_files_staged_stats(const katome_settings* s, const char* const*
     *out = nullptr;
     Finish f{out, nullptr};
     f.stages = stages; f.genome_len = original_genome_length; f.stage_stats = stage_stats;
+    return build_files_impl(s, paths, n_paths, f);
+}
+int katome_assemble_files(const katome_settings* s, const char* const* paths, size_t n_paths, uint64_t original_genome_length, const char* out_path,
+                          katome_assembly** out) {
+    if (!out && !out_path) { set_error("null argument"); return KATOME_E_ARG; }
+    if (out) *out = nullptr;
+    Finish f{nullptr, nullptr};
+    f.assemble = AssembleWant{out, out_path}; f.assembling = true; f.genome_len = original_genome_length;
     return build_files_impl(s, paths, n_paths, f);
 }
 int katome_shrink_files(const katome_settings* s, const char* const* paths, size_t n_paths, katome_contigs** out) {

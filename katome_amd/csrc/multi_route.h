@@ -41,8 +41,18 @@ struct MultiRoute {
     bool sharded_stage_letters() const { return first_seen && stages && !sharded_shrink; }
 };
 
-static inline MultiRoute plan_multi_route(uint32_t flags, bool want_contigs, const char* stages) {
+// assembling (katome_assemble_*): the stages "dcwced" and collapse run on the graph gathered to the first GPU, whatever the
+// environment says about shrink and the stages -- the exact shrink and the walk behind it are one GPU's
+static inline MultiRoute plan_multi_route(uint32_t flags, bool want_contigs, const char* stages, bool assembling = false) {
     MultiRoute p;
+    if (assembling) {
+        p.first_seen = (flags & KATOME_FLAG_FIRST_SEEN_ORDER) != 0;
+        p.remove_dead_paths = (flags & KATOME_FLAG_REMOVE_DEAD_PATHS) != 0;
+        p.contigs = true;                    // (as for a shrink: gathers() whatever the graph's size, and the gather refuses what does not fit)
+        p.bad_arg = !p.first_seen;      // (no stage letters on the shares: "dcwced" runs after the gather)
+        p.local_comm = (flags & KATOME_FLAG_RANKS_SHARE_DEVICE) != 0 || env_is("KATOME_COMM", "local");
+        return p;
+    }
     p.first_seen = (flags & KATOME_FLAG_FIRST_SEEN_ORDER) != 0;
     p.remove_dead_paths = (flags & KATOME_FLAG_REMOVE_DEAD_PATHS) != 0;
     p.contigs = want_contigs;

@@ -299,7 +299,8 @@ int dev_shrink(const ShrinkInput& g, ShrinkOutput& out, hipStream_t stream) {
 // graph its slot, its end points under the final numbering, and the chains of original edges behind the slots -- is turned into
 // weights, k-mer counts and compress_edge labels on the device again.  edge_age: the index every edge had when it was added (null:
 // the edges are still in that order).
-int dev_shrink_exact(const ShrinkInput& g, const uint32_t* edge_age, ShrinkOutput& out, double* host_ms, hipStream_t stream) {
+int dev_shrink_exact(const ShrinkInput& g, const uint32_t* edge_age, ShrinkOutput& out, double* host_ms, hipStream_t stream,
+                     ShrinkExact* keep, std::vector<uint32_t>* kept_out) {
     const u64 E = g.n_edges, N = g.n_nodes;
     const u32 nw = g.nw, k = g.k;
     out.n_edges = out.n_nodes = out.label_bytes = 0;
@@ -328,8 +329,10 @@ int dev_shrink_exact(const ShrinkInput& g, const uint32_t* edge_age, ShrinkOutpu
         }
         KCHECK_HIP(hipStreamSynchronize(stream));
     }
-    ShrinkExact sx;
-    std::vector<uint32_t> kept;
+    ShrinkExact own_sx;
+    std::vector<uint32_t> own_kept;
+    ShrinkExact& sx = keep ? *keep : own_sx;
+    std::vector<uint32_t>& kept = kept_out ? *kept_out : own_kept;
     const auto t0 = std::chrono::steady_clock::now();
     try {
         sx.init(h_src.data(), h_dst.data(), edge_age ? h_order.data() : nullptr, (uint32_t)E, (uint32_t)N);

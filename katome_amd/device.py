@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .build import KatomePanic, collection_stats, make_settings
+from .build import ContigsStats, KatomePanic, collection_stats, make_settings
 
 
 def _check(status):
@@ -110,6 +110,7 @@ class DeviceContigs:
         self.edge_label_off = _view(dc.d_edge_label_off, (ne + 1,), "<i8", builder, device)
         self.edge_label = _view(dc.d_edge_label, (dc.label_bytes,), "|u1", builder, device)
         self.node_key = _view(dc.d_node_key, (nn, nw), "<i8", builder, device)
+        self._dc, self._builder = dc, builder
 
     def sequences(self):
         """host: every merged edge decoded to its ACGT string (compress.rs:283-293 decompress_edge)"""
@@ -122,6 +123,48 @@ class DeviceContigs:
             bases = "".join("ACGT"[(int(x) >> s) & 3] for x in b[1:] for s in (6, 4, 2, 0))
             out.append(bases[:len(bases) - pad])
         return out
+
+
+    def text(self, layout="plain"):
+        """every merged edge's whole label as text, one contig per edge, written on the device (katome_dev_contigs_text) ->
+        DeviceAssembly; valid for the builder's last shrink() only"""
+        da = _lib.DevAssembly()
+        _check(_lib.lib().katome_dev_contigs_text(self._builder._h, C.byref(self._dc), LAYOUTS[layout], C.byref(da), _stream()))
+        return DeviceAssembly(da, self._builder, self._builder.tdev)
+
+
+LAYOUTS = {"plain": 0, "fasta": 1}
+
+
+class DeviceAssembly:
+    """contigs as text in HBM: contig i is text[contig_off[i]:contig_off[i] + contig_len[i]]; layout "plain": the contigs back
+    to back, "fasta": text[:text_bytes] is byte for byte what Contigs::save_to_file writes (asm/mod.rs:57-72)"""
+
+    def __init__(self, da, owner, device, stats=None):
+        self.n_contigs, self.text_bytes = da.n_contigs, da.text_bytes
+        self.layout = {v: k for k, v in LAYOUTS.items()}[da.layout]
+        self.contig_off = _view(da.d_contig_off, (da.n_contigs,), "<i8", owner, device)
+        self.contig_len = _view(da.d_contig_len, (da.n_contigs,), "<i4", owner, device)
+        self.text = _view(da.d_text, (da.text_bytes,), "|u1", owner, device)
+        self.collapse_stats = stats              # the walk's counters (Builder.collapse())
+        self.n_pieces = stats["n_pieces"] if stats else da.n_contigs
+
+    def lengths(self):
+        return [int(x) & 0xFFFFFFFF for x in self.contig_len.cpu().tolist()]
+
+    def contigs(self):
+        """host: the contigs as a list of str, in order"""
+        raw = bytes(self.text.cpu().numpy())
+        return [raw[o:o + n].decode() for o, n in zip(self.contig_off.cpu().tolist(), self.lengths())]
+
+    def contig_stats(self, original_genome_length):
+        """Contigs::stats (stats/contigs.rs:31-89) of these contigs"""
+        from .build import contig_stats
+        return contig_stats(self.lengths(), original_genome_length)
+
+    @property
+    def stats(self):
+        return self.collapse_stats
 
 
 class Builder(_ViewOwner):
@@ -304,6 +347,16 @@ class Builder(_ViewOwner):
                                                  _stream()))
         self.last_shrink_host_ms = host_ms.value
         return DeviceContigs(dc, self, self.tdev)
+
+    def collapse(self, layout="plain"):
+        """Collapsable::collapse (collapser.rs:25-273) of the finalized graph as it stands -> DeviceAssembly: the exact shrink, the
+        reference's walk on one host core (`self.last_collapse_host_ms`), the text written on the device.  The builder's graph
+        is left as it is; the result is valid until the next collapse() or close()"""
+        da, st = _lib.DevAssembly(), _lib.CollapseStats()
+        _check(_lib.lib().katome_dev_collapse(self._h, LAYOUTS[layout], C.byref(da), C.byref(st), _stream()))
+        stats = {f: getattr(st, f) for f, _ in _lib.CollapseStats._fields_}
+        self.last_collapse_host_ms = st.host_ms
+        return DeviceAssembly(da, self, self.tdev, stats)
 
     def graph(self):
         """the finalized graph as it stands (after remove_dead_paths / remove_weak_edges)"""
@@ -509,6 +562,27 @@ def labels(edge_keys, k, device=0):
     out = torch.empty((max(n, 1) * stride + 3) // 4 * 4, dtype=torch.uint8, device=edge_keys.device)
     _check(_lib.lib().katome_dev_labels(device, _ptr(edge_keys), n, k, _ptr(out), _stream()))
     return out[:n * stride].view(n, stride)
+
+
+def pieces_text(labels, label_off, pieces, k, layout="plain", device=0):
+    """the text kernel on the caller's arrays (katome_dev_pieces_text): labels uint8 (compress_edge format, label i at
+    labels[label_off[i]:label_off[i + 1]], label_off int64 with one more entry than labels), pieces int32/uint32 (label index,
+    bit 31 on a piece that begins a contig; None: one whole piece per label) -> (contig_off int64, contig_len int32, text uint8
+    of text_bytes rounded up to 16, text_bytes)"""
+    tdev = labels.device
+    n_labels = label_off.numel() - 1
+    n_pieces = pieces.numel() if pieces is not None else n_labels
+    nc, nb = C.c_uint64(), C.c_uint64()
+    L = _lib.lib()
+    _check(L.katome_dev_pieces_text(device, k, _ptr(labels), _ptr(label_off), n_labels, _ptr(pieces), n_pieces, LAYOUTS[layout], None, None, 0,
+                                    None, 0, C.byref(nc), C.byref(nb), _stream()))
+    cap = (nb.value + 15) // 16 * 16
+    off = torch.empty(max(nc.value, 1), dtype=torch.int64, device=tdev)
+    length = torch.empty(max(nc.value, 1), dtype=torch.int32, device=tdev)
+    text = torch.empty(max(cap, 16), dtype=torch.uint8, device=tdev)
+    _check(L.katome_dev_pieces_text(device, k, _ptr(labels), _ptr(label_off), n_labels, _ptr(pieces), n_pieces, LAYOUTS[layout], _ptr(off),
+                                    _ptr(length), nc.value, _ptr(text), cap, C.byref(nc), C.byref(nb), _stream()))
+    return off[:nc.value], length[:nc.value], text, nb.value
 
 
 def synth_reads(first_read, n_reads, read_len, genome_len, err_rate, n_inject_percent=0, device=0):
