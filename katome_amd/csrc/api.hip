@@ -1,8 +1,8 @@
 // api.hip -- the device half of the C ABI of include/katome_gpu.h (katome_dev_*, the counting levels, finalize): the
 // build driver behind `Build::create` (reference src/katome/algorithms/builder.rs:42-54) and the PtGraph::create
-// post-pass (collections/graphs/pt_graph.rs:333-345), composed from the kernels in extract.hip, table.hip and radix.hip.
-// The entries that take and return host memory are in host_build.cpp.  No CPU fallback: every entry that needs the
-// device fails with KATOME_E_DEVICE when there is none.
+// post-pass (collections/graphs/pt_graph.rs:333-345), composed from the kernels in extract.hip, table.hip, radix.hip,
+// node_ids.hip and first_seen.hip.  The entries that take and return host memory are in host_build.cpp.  No CPU
+// fallback: every entry that needs the device fails with KATOME_E_DEVICE when there is none.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -1371,25 +1371,35 @@ int katome_dev_edges(katome_builder* b, uint64_t** d_edge_key, uint32_t** d_edge
     return KATOME_OK;
 }
 
+// the finalized graph as the caller sees it: pointers into the builder's arrays as they stand
+static void graph_view(const katome_builder* b, katome_dev_graph* out) {
+    out->n_nodes = b->n_nodes; out->n_edges = b->n_edges;
+    out->key_words = b->nw; out->label_stride = label_stride_for_k(b->s.k);
+    out->d_edge_key = b->edge_key.as<u64>(); out->d_edge_weight = b->edge_weight.as<u32>();
+    out->d_edge_src = b->edge_src.as<u64>(); out->d_edge_dst = b->edge_dst.as<u64>();
+    out->d_edge_label = b->edge_label.as<uint8_t>(); out->d_node_key = b->node_key.as<u64>();
+    out->d_edge_age = b->edge_age.p ? b->edge_age.as<u32>() : nullptr;
+}
+
 int katome_dev_finalize(katome_builder* b, katome_dev_graph* out, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (b && b->finalized) return out ? katome_dev_current_graph(b, out) : KATOME_OK;      // (also: a graph installed by katome_dist_gather)
     KCHECK(katome_dev_edges(b, nullptr, nullptr, nullptr, stream_));
     const uint64_t E = b->n_edges;
-    const uint32_t nw = b->nw, k = b->s.k;
+    const uint32_t k = b->s.k;
     // node set = every source and target (k-1)-mer (add_fasta_node, pt_graph.rs:142-154): read off the
-    // sorted edge list (radix.hip, dev_node_ids)
+    // sorted edge list (node_ids.hip, dev_node_ids)
     KCHECK(b->edge_src.alloc((E + 1) * 8, stream));
     KCHECK(b->edge_dst.alloc((E + 1) * 8, stream));
     DevBuf node_first(stream);                 // first-seen order: the nodes' first touches come out of the same merge
     uint64_t n_marked = 0;                     // ... and, for targets below this index, "this edge touches it first" as a mark in edge_dst
-    const uint32_t stride = label_stride_for_k(k);
-    // default numbering: the edges stay where they are, so the pass that writes their source ids writes their labels too (radix.hip
+    const size_t label_bytes = (E + 1) * (size_t)label_stride_for_k(k) + 16;
+    // default numbering: the edges stay where they are, so the pass that writes their source ids writes their labels too (node_ids.hip
     // src_write_kernel) and no kernel reads the keys again for them.  KATOME_LABELS_IN_IDS=0: dev_labels afterwards, as in first-seen
     // order, whose edges are renumbered first
     static const bool labels_in_ids = env_flag("KATOME_LABELS_IN_IDS", true);
     const bool labels_early = labels_in_ids && !b->first_seen && E;
-    if (labels_early) KCHECK(b->edge_label.alloc((E + 1) * (size_t)stride + 16, stream));
+    if (labels_early) KCHECK(b->edge_label.alloc(label_bytes, stream));
     {
         PhaseScope ps(b->prof, PH_NODE_SET, stream);
         const bool fs = b->first_seen && E && b->edge_seq.p;
@@ -1401,146 +1411,28 @@ int katome_dev_finalize(katome_builder* b, katome_dev_graph* out, void* stream_)
         b->drop_edge_heads();
         if (rc != KATOME_OK) { b->edge_label.release(); return rc; }      // (a builder that is not finalized holds no labels)
     }
-    u64* cand = b->node_key.as<u64>();
     if (b->first_seen && E) {
         // Re-number everything the way the reference's loop would have: edges by the sequence number of their first
         // insertion, nodes by the first insertion that touches them (source of a strand's first window: 2*seq;
         // target: 2*seq + 1).  petgraph hands out indices in exactly that order (pt_graph.rs:149,194).
         PhaseScope ps(b->prof, PH_FIRST_SEEN, stream);
-        const bool trace = getenv("KATOME_TRACE_FINALIZE") != nullptr;
-        auto t_last = std::chrono::steady_clock::now();
-        auto lap = [&](const char* what) {
-            if (!trace) return;
-            (void)hipStreamSynchronize(stream);
-            const auto t = std::chrono::steady_clock::now();
-            fprintf(stderr, "[finalize] %-22s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(t - t_last).count());
-            t_last = t;
-        };
-        const uint64_t N = b->n_nodes;
-        if (N >= (1ull << 32)) { set_error("first-seen order: more than 2^32 nodes on one GPU"); return KATOME_E_UNSUPPORTED; }
         const uint64_t max_seq = b->direct_edges ? 2 * b->direct_edges + 2
                                  : b->var_seq_base ? 2 * b->var_seq_base + 2
                                                    : 2 * (b->reads_inserted + 1) * 2 * (uint64_t)(b->seen_read_len - k + 1) + 2;
         uint32_t bits = 1;
         while (bits < 64 && (max_seq >> bits)) ++bits;
-        // (buffers are taken and given back one at a time: at C3 every one of them is 6-13 GB)
-        DevBuf new_id(stream), eperm(stream), aos(stream);
-        if (!node_first.p) {
-            KCHECK(node_first.alloc((N + 1) * 8));
-            KCHECK_HIP(hipMemsetAsync(node_first.p, 0xFF, N * 8, stream));
-            KCHECK(dev_node_first(b->edge_src.as<u64>(), b->edge_dst.as<u64>(), b->edge_seq.as<u64>(), E, node_first.as<u64>(), stream));
-        }
-        lap("node_first");
-        KCHECK(eperm.alloc((E + 1) * 4));
-        if (!getenv("KATOME_SORT_NODES") && aos.alloc(E * 32 + 64) == KATOME_OK) {
-            // No sort of the nodes: every node is introduced by exactly one edge (the one whose first insertion is the node's
-            // first touch), so with the edges in sequence order the node indices are a running count (radix.hip).
-            KCHECK(dev_pack_edges_intro(b->edge_key.as<u64>(), b->edge_weight.as<u32>(), b->edge_src.as<u64>(), b->edge_dst.as<u64>(),
-                                        b->edge_seq.as<u64>(), node_first.as<u64>(), E, nw, aos.p, stream, n_marked));
-            node_first.release();
-            lap("pack + who introduces");
-            KCHECK(dev_iota(eperm.as<u32>(), E, stream));
-            KCHECK(dev_sort_bufs(b->edge_seq, &eperm, E, 1, bits, stream));       // eperm[new] = old; edge_seq now ascending
-            lap("sort edges by seq");
-            DevBuf cnt(stream), offs(stream), onode(stream);
-            KCHECK(cnt.alloc((E + 1) * 4));
-            KCHECK(dev_unpack_edges_intro(aos.p, eperm.as<u32>(), E, nw, b->edge_key.as<u64>(), b->edge_weight.as<u32>(), b->edge_src.as<u64>(),
-                                          b->edge_dst.as<u64>(), cnt.as<u32>(), stream));
-            aos.release(); eperm.release();
-            lap("edges to seq order");
-            KCHECK(offs.alloc((E + 2) * 8));
-            KCHECK(dev_scan_counts(cnt.as<u32>(), E, offs.as<u64>(), stream));
-            uint64_t introduced = 0;
-            KCHECK_HIP(hipMemcpyAsync(&introduced, offs.as<u64>() + E, 8, hipMemcpyDeviceToHost, stream));
-            KCHECK_HIP(hipStreamSynchronize(stream));
-            lap("scan");
-            if (introduced != N) { set_error("first-seen order: %llu nodes introduced, %llu nodes known", (unsigned long long)introduced, (unsigned long long)N); return KATOME_E_DEVICE; }
-            cnt.release();
-            DevBuf osrc(stream), odst(stream);
-            KCHECK(new_id.alloc((N + 1) * 8));
-            KCHECK(onode.alloc((N + 1) * 8 * nw));
-            KCHECK(osrc.alloc((E + 1) * 8));
-            KCHECK(odst.alloc((E + 1) * 8));
-            KCHECK(dev_assign_nodes(b->edge_key.as<u64>(), b->edge_src.as<u64>(), b->edge_dst.as<u64>(), offs.as<u64>(), E, nw, k,
-                                    new_id.as<u64>(), onode.as<u64>(), osrc.as<u64>(), odst.as<u64>(), stream));
-            { const size_t n = onode.bytes; b->node_key.adopt(onode.take(), n); }
-            { const size_t n = osrc.bytes; b->edge_src.adopt(osrc.take(), n); }
-            { const size_t n = odst.bytes; b->edge_dst.adopt(odst.take(), n); }
-            lap("node indices + end points");
-        } else {
-        aos.release();
-        KCHECK(dev_clear_dst_marks(b->edge_dst.as<u64>(), E, stream));      // (the merge's marks: only the other branch reads them)
-        KCHECK(new_id.alloc((N + 1) * 8));
-        {
-            DevBuf nperm(stream), onode(stream);
-            KCHECK(nperm.alloc((N + 1) * 4));
-            KCHECK(dev_iota(nperm.as<u32>(), N, stream));
-            KCHECK(dev_sort_bufs(node_first, &nperm, N, 1, bits, stream));        // nperm[new] = old
-            lap("sort nodes");
-            node_first.release();
-            KCHECK(dev_invert(nperm.as<u32>(), N, new_id.as<u64>(), stream));                   // new_id[old] = new
-            KCHECK(onode.alloc((N + 1) * 8 * nw));
-            KCHECK(dev_gather_keys(b->node_key.as<u64>(), nperm.as<u32>(), N, nw, onode.as<u64>(), stream));
-            const size_t n = onode.bytes; b->node_key.adopt(onode.take(), n);
-            lap("invert + node keys");
-        }
-        KCHECK(dev_iota(eperm.as<u32>(), E, stream));
-        KCHECK(dev_sort_bufs(b->edge_seq, &eperm, E, 1, bits, stream));           // eperm[new] = old; edge_seq now ascending
-        lap("sort edges by seq");
-        {
-            // one 32-byte record per edge, read once at random (radix.hip dev_permute_edges); if that much scratch is not
-            // to be had, the four separate gathers
-            DevBuf aos2(stream);
-            if (aos2.alloc(E * 32 + 64) == KATOME_OK) {
-                KCHECK(dev_permute_edges(b->edge_key.as<u64>(), b->edge_weight.as<u32>(), b->edge_src.as<u64>(), b->edge_dst.as<u64>(),
-                                         new_id.as<u64>(), eperm.as<u32>(), E, nw, aos2.p, stream));
-            } else {
-                {
-                    DevBuf o(stream);
-                    KCHECK(o.alloc((E + 1) * 8 * nw));
-                    KCHECK(dev_gather_keys(b->edge_key.as<u64>(), eperm.as<u32>(), E, nw, o.as<u64>(), stream));
-                    const size_t n = o.bytes; b->edge_key.adopt(o.take(), n);
-                }
-                {
-                    DevBuf o(stream);
-                    KCHECK(o.alloc((E + 1) * 4));
-                    KCHECK(dev_gather_u32(b->edge_weight.as<u32>(), eperm.as<u32>(), E, o.as<u32>(), stream));
-                    const size_t n = o.bytes; b->edge_weight.adopt(o.take(), n);
-                }
-                {
-                    DevBuf o(stream);
-                    KCHECK(o.alloc((E + 1) * 8));
-                    KCHECK(dev_gather_mapped(b->edge_src.as<u64>(), eperm.as<u32>(), new_id.as<u64>(), E, o.as<u64>(), stream));
-                    const size_t n = o.bytes; b->edge_src.adopt(o.take(), n);
-                }
-                {
-                    DevBuf o(stream);
-                    KCHECK(o.alloc((E + 1) * 8));
-                    KCHECK(dev_gather_mapped(b->edge_dst.as<u64>(), eperm.as<u32>(), new_id.as<u64>(), E, o.as<u64>(), stream));
-                    const size_t n = o.bytes; b->edge_dst.adopt(o.take(), n);
-                }
-            }
-        }
-        }
-        lap("edges to seq order");
+        FirstSeenGraph g{&b->edge_key, &b->edge_weight, &b->edge_src, &b->edge_dst, &b->edge_seq, &b->node_key, E, b->n_nodes, b->nw, k};
+        KCHECK(dev_first_seen_order(g, node_first, n_marked, bits, stream));
         if (b->prune_weight) KCHECK(weak_edges_ordered(b, b->prune_weight, stream));
-        cand = b->node_key.as<u64>();
     }
     if (!labels_early) {
-        KCHECK(b->edge_label.alloc((E + 1) * (size_t)stride + 16, stream));
+        KCHECK(b->edge_label.alloc(label_bytes, stream));
         PhaseScope ps(b->prof, PH_LABELS, stream);
         KCHECK(dev_labels(b->edge_key.as<u64>(), b->n_edges, k, b->edge_label.as<uint8_t>(), stream));
     }
     KCHECK_HIP(hipStreamSynchronize(stream));
     b->finalized = true;
-    if (out) {
-        out->n_nodes = b->n_nodes; out->n_edges = b->n_edges;
-        out->key_words = nw; out->label_stride = stride;
-        out->d_edge_key = b->edge_key.as<u64>(); out->d_edge_weight = b->edge_weight.as<u32>();
-        out->d_edge_src = b->edge_src.as<u64>(); out->d_edge_dst = b->edge_dst.as<u64>();
-        out->d_edge_label = b->edge_label.as<uint8_t>(); out->d_node_key = cand;
-        out->d_edge_age = b->edge_age.p ? b->edge_age.as<u32>() : nullptr;
-    }
+    if (out) graph_view(b, out);
     return KATOME_OK;
 }
 
@@ -1564,14 +1456,7 @@ int katome_dev_remove_dead_paths(katome_builder* b, katome_dev_graph* out, katom
     KCHECK_HIP(hipStreamSynchronize(stream));
     st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (stats) *stats = st;
-    if (out) {
-        out->n_nodes = b->n_nodes; out->n_edges = b->n_edges;
-        out->key_words = b->nw; out->label_stride = label_stride_for_k(b->s.k);
-        out->d_edge_key = b->edge_key.as<u64>(); out->d_edge_weight = b->edge_weight.as<u32>();
-        out->d_edge_src = b->edge_src.as<u64>(); out->d_edge_dst = b->edge_dst.as<u64>();
-        out->d_edge_label = b->edge_label.as<uint8_t>(); out->d_node_key = b->node_key.as<u64>();
-        out->d_edge_age = b->edge_age.p ? b->edge_age.as<u32>() : nullptr;
-    }
+    if (out) graph_view(b, out);
     return KATOME_OK;
 }
 
@@ -1696,12 +1581,7 @@ int katome_dev_pieces_text(int device, uint32_t k, const uint8_t* d_label, const
 int katome_dev_current_graph(katome_builder* b, katome_dev_graph* out) {
     if (!b || !out) { set_error("null argument"); return KATOME_E_ARG; }
     if (!b->finalized) { set_error("katome_dev_current_graph: call katome_dev_finalize first"); return KATOME_E_ARG; }
-    out->n_nodes = b->n_nodes; out->n_edges = b->n_edges;
-    out->key_words = b->nw; out->label_stride = label_stride_for_k(b->s.k);
-    out->d_edge_key = b->edge_key.as<u64>(); out->d_edge_weight = b->edge_weight.as<u32>();
-    out->d_edge_src = b->edge_src.as<u64>(); out->d_edge_dst = b->edge_dst.as<u64>();
-    out->d_edge_label = b->edge_label.as<uint8_t>(); out->d_node_key = b->node_key.as<u64>();
-        out->d_edge_age = b->edge_age.p ? b->edge_age.as<u32>() : nullptr;
+    graph_view(b, out);
     return KATOME_OK;
 }
 

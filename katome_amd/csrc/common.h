@@ -86,12 +86,13 @@ struct DevBuf {
     }
     void* take() { void* q = p; p = nullptr; bytes = 0; return q; }
     void adopt(void* q, size_t n) { release(); p = q; bytes = n; }
+    void adopt(DevBuf& from) { const size_t n = from.bytes; adopt(from.take(), n); }      // (neither stream changes)
     template <class T> T* as() const { return (T*)p; }
 };
 
 // Optional HIP-event timing on the stream the kernels are launched on (bench.py's roofline figures).  PHASES bracket a step of
 // the build (several launches); the K_* entries bracket ONE kernel launch each, so that a kernel's own average duration can be
-// priced against its algorithmic bytes -- the free-standing primitives (radix.hip, table.hip) find the builder's profiler
+// priced against its algorithmic bytes -- the free-standing primitives (radix.hip, node_ids.hip, table.hip) find the builder's profiler
 // through a thread-local pointer that the enclosing PhaseScope sets.
 enum Phase { PH_EXTRACT, PH_REGION_ORDER, PH_INSERT, PH_EMIT_EDGES, PH_SORT_EDGES, PH_NODE_SET, PH_RANK, PH_LABELS,
              PH_INSERT_TILES, PH_EXPAND_TILES, PH_EXPAND_MID, PH_FIRST_SEEN, PH_DEAD_PATHS, PH_SHRINK,
@@ -231,8 +232,6 @@ int dev_supermers_expand(const uint64_t* d_list, const uint32_t* d_counts, uint6
 int dev_partition_supermers(const uint64_t* d_in, uint64_t n, uint32_t n_parts, uint64_t* d_out, uint64_t* h_counts, hipStream_t stream);
 int dev_partition_range(const uint64_t* d_vals, const uint32_t* idx_in, uint64_t n, const uint64_t* d_bounds, uint32_t n_parts,
                         uint64_t* d_out, uint32_t* idx_out, uint64_t* h_counts, hipStream_t stream);
-int dev_source_ids(const uint64_t* d_edge_key, uint64_t n_edges, uint32_t k, DevBuf& node_key, uint64_t* d_edge_src, uint64_t* n_src,
-                   hipStream_t stream);
 int dev_hash_order_core(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t core_shift, uint32_t core_bases, uint64_t* ka, uint64_t* kb,
                         uint32_t* wa, uint32_t* wb, const uint64_t** k_out, const uint32_t** w_out, uint32_t* group_bits, hipStream_t stream);
 // KATOME_FUSED_RECORDS=0: a list-fed level's records are written out before their first partition pass, as they were before that pass
@@ -303,7 +302,7 @@ int dev_half_merge(const uint64_t* a_key, const uint32_t* a_w, const uint64_t* a
 // the same without a sort of B: b_key / b_w only partitioned by the 16-bit prefix (dev_key_order), at most dev_group_merge_cap() keys
 // to a prefix (dev_key_group_max), weights below 2^16; B's groups are put in key order in LDS (radix.hip group_merge_kernel)
 // (head_counts, dev_source_head_blocks(n_out) of them: also counts the source run heads of every block of output edges, which
-// dev_node_ids then need not count again)
+// dev_node_ids, node_ids.hip, then need not count again)
 uint32_t dev_group_merge_cap();
 uint64_t dev_source_head_blocks(uint64_t n_edges);
 int dev_group_merge(const uint64_t* a_key, const uint32_t* a_w, const uint64_t* a_first, const uint32_t* a_count, const uint64_t* a_off,
@@ -314,38 +313,38 @@ int dev_key_group_max(const uint64_t* d_index, uint64_t* d_out, hipStream_t stre
 int dev_unique(uint64_t* d_keys, uint64_t n, uint32_t nw, uint64_t* n_out, hipStream_t stream);
 int dev_rank(const uint64_t* d_sorted, uint64_t n_sorted, uint32_t nw, uint32_t key_bits, const uint64_t* d_q, uint64_t nq,
              uint64_t* d_out, hipStream_t stream);
-// d_seq + node_first (first-seen order): also the nodes' first touches (dev_node_first's result), filled on the way; node_first
-// comes back EMPTY when that was not done and dev_node_first has to run
-// head_counts: dev_group_merge's, made for exactly these edges (the heads are then not counted again); d_label: the edges' labels
-// (dev_labels' bytes) are written in the same pass as the source ids
-int dev_node_ids(const uint64_t* d_edge_key, uint64_t n_edges, uint32_t k, DevBuf& node_key, uint64_t* d_edge_src,
-                 uint64_t* d_edge_dst, uint64_t* n_nodes, hipStream_t stream, const uint64_t* d_seq = nullptr, DevBuf* node_first = nullptr,
-                 uint64_t* n_marked = nullptr, const uint32_t* head_counts = nullptr, uint8_t* d_label = nullptr);
+// dev_rank's index over the top B of key_bits bits of n ascending keys: d_index[b] ((1 << B) + 1 of them) = first key whose top bits are >= b
+int dev_bucket_index(const uint64_t* d_sorted, uint64_t n, uint32_t nw, uint32_t key_bits, uint32_t B, uint64_t* d_index, hipStream_t stream);
 int dev_iota(uint32_t* d, uint64_t n, hipStream_t stream);
 int dev_fill_u32(uint32_t* d, uint64_t n, uint32_t v, hipStream_t stream);
 int dev_gather_seq_weight(const uint64_t* pairs, const uint32_t* idx, uint64_t n, uint64_t* seq, uint32_t* weight, hipStream_t stream);
 int dev_gather_u32(const uint32_t* src, const uint32_t* idx, uint64_t n, uint32_t* dst, hipStream_t stream);
 int dev_gather_u64(const uint64_t* src, const uint32_t* idx, uint64_t n, uint64_t* dst, hipStream_t stream);
 int dev_gather_keys(const uint64_t* src, const uint32_t* idx, uint64_t n, uint32_t nw, uint64_t* dst, hipStream_t stream);
-int dev_gather_mapped(const uint64_t* src, const uint32_t* idx, const uint64_t* map, uint64_t n, uint64_t* dst, hipStream_t stream);
-int dev_invert(const uint32_t* perm, uint64_t n, uint64_t* inv, hipStream_t stream);
-int dev_permute_edges(uint64_t* key, uint32_t* weight, uint64_t* src, uint64_t* dst, const uint64_t* new_id, const uint32_t* idx,
-                      uint64_t n, uint32_t nw, void* scratch, hipStream_t stream);
-int dev_pack_edges_intro(const uint64_t* key, const uint32_t* weight, const uint64_t* src, const uint64_t* dst, const uint64_t* seq,
-                         const uint64_t* node_first, uint64_t n, uint32_t nw, void* aos, hipStream_t stream, uint64_t n_marked = 0);
-int dev_unpack_edges_intro(const void* aos, const uint32_t* idx, uint64_t n, uint32_t nw, uint64_t* key, uint32_t* weight, uint64_t* src,
-                           uint64_t* dst, uint32_t* cnt, hipStream_t stream);
-int dev_assign_nodes(const uint64_t* key, const uint64_t* src, const uint64_t* dst, const uint64_t* offs, uint64_t n, uint32_t nw, uint32_t k,
-                     uint64_t* new_id, uint64_t* node_key, uint64_t* out_src, uint64_t* out_dst, hipStream_t stream);
-int dev_clear_dst_marks(uint64_t* dst, uint64_t n, hipStream_t stream);
-int dev_node_first(const uint64_t* src, const uint64_t* dst, const uint64_t* seq, uint64_t n, uint64_t* node_first, hipStream_t stream);
+// exclusive scan of m u32 counts into u64 offsets (offs[m] = total), one workgroup
+int dev_scan_counts(const uint32_t* d_counts, uint64_t m, uint64_t* d_offs, hipStream_t stream);
+
+// node_ids.hip: the graph read off the sorted edge list
+int dev_source_ids(const uint64_t* d_edge_key, uint64_t n_edges, uint32_t k, DevBuf& node_key, uint64_t* d_edge_src, uint64_t* n_src,
+                   hipStream_t stream);
+// d_seq + node_first (first-seen order): also the nodes' first touches, filled on the way; node_first comes back EMPTY when that was
+// not done (dev_first_seen_order then fills it)
+// head_counts: dev_group_merge's, made for exactly these edges (the heads are then not counted again); d_label: the edges' labels
+// (dev_labels' bytes) are written in the same pass as the source ids
+int dev_node_ids(const uint64_t* d_edge_key, uint64_t n_edges, uint32_t k, DevBuf& node_key, uint64_t* d_edge_src,
+                 uint64_t* d_edge_dst, uint64_t* n_nodes, hipStream_t stream, const uint64_t* d_seq = nullptr, DevBuf* node_first = nullptr,
+                 uint64_t* n_marked = nullptr, const uint32_t* head_counts = nullptr, uint8_t* d_label = nullptr);
 int dev_endpoints(const uint64_t* d_edge_key, uint64_t n, uint32_t k, uint64_t* d_src, uint64_t* d_dst, hipStream_t stream);
 int dev_labels(const uint64_t* d_edge_key, uint64_t n, uint32_t k, uint8_t* d_label, hipStream_t stream);
 // BFCounter lines -> one edge per line (and per strand), unmerged (pt_graph.rs:201-213); seq (nullable) = petgraph index
 int dev_bfc_edges(const uint64_t* d_fwd, const uint32_t* d_w, uint64_t n, uint32_t k, bool rc, uint64_t* d_edge_key,
                   uint32_t* d_edge_weight, uint64_t* d_edge_seq, hipStream_t stream);
-// exclusive scan of m u32 counts into u64 offsets (offs[m] = total), one workgroup
-int dev_scan_counts(const uint32_t* d_counts, uint64_t m, uint64_t* d_offs, hipStream_t stream);
+
+// first_seen.hip: first-seen order (pt_graph.rs:149,194) -- edges to the order of their first insertion (edge_seq, below 2^seq_bits,
+// comes back ascending), nodes to the order of their first touch; counts stay, buffers are replaced.  node_first, n_marked: what
+// dev_node_ids left (node_first is given back on the way)
+struct FirstSeenGraph { DevBuf *edge_key, *edge_weight, *edge_src, *edge_dst, *edge_seq, *node_key; uint64_t n_edges, n_nodes; uint32_t nw, k; };
+int dev_first_seen_order(FirstSeenGraph& g, DevBuf& node_first, uint64_t n_marked, uint32_t seq_bits, hipStream_t stream);
 
 // prune.hip: Prunable::remove_dead_paths on a first-seen-ordered graph, in place (counts shrink, buffers stay)
 struct PruneGraph {

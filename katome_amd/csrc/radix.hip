@@ -1,15 +1,13 @@
 // radix.hip -- hand-written device primitives for gfx950 wave64: LSD radix sort (keys, optional
 // u32 values, 64- or 128-bit keys), partition-by-owner (the same pass with a different digit),
-// unique, rank-in-sorted-array, and the edge -> endpoints / label transforms.
-//
-// These build the graph out of the k-mer table: PtGraph node numbering (reference
-// collections/graphs/pt_graph.rs:142-154), the endpoints of each edge (compress_kmer halves,
-// compress.rs:23-26) and the compress_edge labels (compress.rs:250-271; post-pass
-// pt_graph.rs:339-343).  All streaming, HBM-bound passes; no MFMA (integer keys).
+// the group merges, unique, scan, rank-in-sorted-array, and the plain gathers.  The graph is read off the
+// sorted edges in node_ids.hip and brought into first-seen order in first_seen.hip; the key loads and
+// stores all three share are in edge_keys.h.  All streaming, HBM-bound passes; no MFMA (integer keys).
 #include <algorithm>
 #include <type_traits>
 
 #include "common.h"
+#include "edge_keys.h"
 #include "lds_order.h"
 
 namespace katome {
@@ -109,32 +107,6 @@ struct LevelKeyDigit {
     u32 shift;
     __device__ __forceinline__ u32 operator()(const Key<1>& k) const { return (u32)(k.w[0] >> shift) & (RADIX - 1); }
 };
-
-template <int NW> __device__ __forceinline__ Key<NW> load_key(const u64* p, u64 i) {
-    Key<NW> k;
-    if (NW == 1) { k.w[0] = p[i]; }
-    else if (NW == 2) { ulonglong2 v = *reinterpret_cast<const ulonglong2*>(p + 2 * i); k.w[0] = v.x; k.w[NW - 1] = v.y; }
-    else { k.w[0] = p[3 * i]; k.w[NW > 2 ? 1 : 0] = p[3 * i + 1]; k.w[NW - 1] = p[3 * i + 2]; }      // three-word tiles (64..95 bases)
-    return k;
-}
-// the same load for data that is read once and not again by this kernel (a pass's input): non-temporal, so that the L2 lines it
-// would take stay with the partial output lines that consecutive tiles complete (radix_scatter_kernel: 42.0 -> 40.5 ms per edge sort)
-typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
-#ifndef KATOME_STREAM_LOADS
-#define KATOME_STREAM_LOADS 1        // 0: plain loads; 1: the scatter pass; 2: + histogram; 3: + run sort
-#endif
-template <int NW> __device__ __forceinline__ Key<NW> load_key_stream(const u64* p, u64 i) {
-    Key<NW> k;
-    if (NW == 1) { k.w[0] = __builtin_nontemporal_load(p + i); }
-    else if (NW == 2) { u64x2_t v = __builtin_nontemporal_load(reinterpret_cast<const u64x2_t*>(p + 2 * i)); k.w[0] = v.x; k.w[NW - 1] = v.y; }
-    else { k.w[0] = __builtin_nontemporal_load(p + 3 * i); k.w[NW > 2 ? 1 : 0] = __builtin_nontemporal_load(p + 3 * i + 1); k.w[NW - 1] = __builtin_nontemporal_load(p + 3 * i + 2); }
-    return k;
-}
-template <int NW> __device__ __forceinline__ void store_key(u64* p, u64 i, const Key<NW>& k) {
-    if (NW == 1) p[i] = k.w[0];
-    else if (NW == 2) *reinterpret_cast<ulonglong2*>(p + 2 * i) = make_ulonglong2(k.w[0], k.w[NW - 1]);
-    else { p[3 * i] = k.w[0]; p[3 * i + 1] = k.w[NW > 2 ? 1 : 0]; p[3 * i + 2] = k.w[NW - 1]; }
-}
 
 // ---- pass 1: per-workgroup digit histogram -> counts[block][digit] ----------------------------
 template <int NW, class Digit>
@@ -1192,7 +1164,8 @@ int dev_half_merge(const uint64_t* a_key, const uint32_t* a_w, const uint64_t* a
 constexpr u32 GM_THREADS = LDS_ORDER_THREADS, GM_PER = 16, GM_WORDS = GM_THREADS * GM_PER, GM_CAP = GM_WORDS - 16;
 constexpr u32 GM_STEP = 2048, GM_RING = 2 * GM_STEP, GM_MI = GM_STEP / GM_THREADS, GM_PF = GM_STEP / GM_THREADS;
 constexpr size_t GM_LDS = ((size_t)GM_WORDS + GM_RING) * 8;
-constexpr u32 SRC_HEAD_BLOCK = 2048;          // edges to a count of source_ids_t (its UNIQ_TILE: asserted there)
+constexpr u32 SRC_HEAD_BLOCK = 2048;          // edges to a count of source_ids_t (node_ids.hip: its UNIQ_TILE)
+static_assert(SRC_HEAD_BLOCK == UNIQ_TILE, "group_merge_kernel counts the heads of exactly src_count_kernel's blocks");
 // the GM_WORDS - GM_CAP spare words behind B, as u32: the scan's wave totals, the step's A count, and (HEADS) the last entry of the
 // step before by step parity (two u64, so on an even u32) and the step's two head counts
 constexpr u32 GM_SP_WTOT = 0, GM_SP_USED_A = GM_SP_WTOT + GM_THREADS / 64, GM_SP_LAST_E = (GM_SP_USED_A + 1 + 1) / 2 * 2,
@@ -1406,25 +1379,9 @@ int dev_region_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uin
 }
 
 // ---- unique -------------------------------------------------------------------------------------
-constexpr int UNIQ_ITEMS = 8;
-constexpr int UNIQ_TILE = BLOCK * UNIQ_ITEMS;
 
 template <int NW> __device__ __forceinline__ bool is_head(const u64* keys, u64 i) {
     return i == 0 || !key_eq(load_key<NW>(keys, i), load_key<NW>(keys, i - 1));
-}
-
-__device__ __forceinline__ u32 block_excl_scan(u32 mine, u32* wsum /*[BLOCK/64]*/, u32& total) {
-    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u32 incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { u32 v = __shfl_up(incl, o, 64); if (lane >= (u32)o) incl += v; }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    u32 woff = 0; total = 0;
-#pragma unroll
-    for (int w = 0; w < BLOCK / 64; ++w) { if (w < (int)wave) woff += wsum[w]; total += wsum[w]; }
-    __syncthreads();
-    return woff + incl - mine;
 }
 
 template <int NW>
@@ -1553,7 +1510,6 @@ int dev_unique(uint64_t* d_keys, uint64_t n, uint32_t nw, uint64_t* n_out, hipSt
 // ---- rank of query keys in a sorted unique array ------------------------------------------------
 // A bucket index over the top B bits (index[b] = first position whose top bits are >= b) narrows
 // each lookup to a few consecutive keys; a binary search inside the bucket finishes it.
-template <int NW> __device__ __forceinline__ u32 top_bits(const Key<NW>& k, u32 key_bits, u32 B) { return key_digit(k, key_bits - B, B); }
 
 template <int NW>
 __global__ __launch_bounds__(BLOCK) void bucket_index_kernel(const u64* __restrict__ sorted, u64 n, u32 key_bits, u32 B, u64* __restrict__ index) {
@@ -1580,6 +1536,13 @@ __global__ __launch_bounds__(BLOCK) void rank_kernel(const u64* __restrict__ sor
     }
 }
 
+int dev_bucket_index(const uint64_t* d_sorted, uint64_t n, uint32_t nw, uint32_t key_bits, uint32_t B, uint64_t* d_index, hipStream_t stream) {
+    if (nw == 1) hipLaunchKernelGGL(bucket_index_kernel<1>, dim3(grid_for(n + 1, BLOCK)), dim3(BLOCK), 0, stream, d_sorted, n, key_bits, B, d_index);
+    else         hipLaunchKernelGGL(bucket_index_kernel<2>, dim3(grid_for(n + 1, BLOCK)), dim3(BLOCK), 0, stream, d_sorted, n, key_bits, B, d_index);
+    KCHECK_HIP(hipGetLastError());
+    return KATOME_OK;
+}
+
 int dev_rank(const uint64_t* d_sorted, uint64_t n_sorted, uint32_t nw, uint32_t key_bits, const uint64_t* d_q, uint64_t nq,
              uint64_t* d_out, hipStream_t stream) {
     if (nq == 0) return KATOME_OK;
@@ -1588,577 +1551,15 @@ int dev_rank(const uint64_t* d_sorted, uint64_t n_sorted, uint32_t nw, uint32_t 
     if (B > key_bits) B = key_bits;
     DevBuf index(stream);
     KCHECK(index.alloc(((1ull << B) + 2) * 8));
-    dim3 block(BLOCK);
-    if (nw == 1) {
-        hipLaunchKernelGGL(bucket_index_kernel<1>, dim3(grid_for(n_sorted + 1, BLOCK)), block, 0, stream, d_sorted, n_sorted, key_bits, B, index.as<u64>());
-        hipLaunchKernelGGL(rank_kernel<1>, dim3(grid_for(nq, BLOCK, 256u * 32u)), block, 0, stream, d_sorted, n_sorted, key_bits, B, index.as<u64>(), d_q, nq, d_out);
-    } else {
-        hipLaunchKernelGGL(bucket_index_kernel<2>, dim3(grid_for(n_sorted + 1, BLOCK)), block, 0, stream, d_sorted, n_sorted, key_bits, B, index.as<u64>());
-        hipLaunchKernelGGL(rank_kernel<2>, dim3(grid_for(nq, BLOCK, 256u * 32u)), block, 0, stream, d_sorted, n_sorted, key_bits, B, index.as<u64>(), d_q, nq, d_out);
-    }
+    KCHECK(dev_bucket_index(d_sorted, n_sorted, nw, key_bits, B, index.as<u64>(), stream));
+    const dim3 grid(grid_for(nq, BLOCK, 256u * 32u)), block(BLOCK);
+    if (nw == 1) hipLaunchKernelGGL(rank_kernel<1>, grid, block, 0, stream, d_sorted, n_sorted, key_bits, B, index.as<u64>(), d_q, nq, d_out);
+    else         hipLaunchKernelGGL(rank_kernel<2>, grid, block, 0, stream, d_sorted, n_sorted, key_bits, B, index.as<u64>(), d_q, nq, d_out);
     KCHECK_HIP(hipGetLastError());
     return KATOME_OK;
 }
 
-// ---- node numbering straight from the sorted edge list --------------------------------------------
-// Edges are sorted by packed k-mer, so their source (k-1)-mers (key >> 2) are sorted too: the nodes
-// that have out-edges are the run heads of that sequence -- no sort needed.  Targets are looked up in
-// that list; the few that are absent (nodes without out-edges: read ends nothing continues) are
-// collected, sorted and appended.  Node ids: sources in ascending key order, then the out-edge-less
-// nodes in ascending key order (add_fasta_node, pt_graph.rs:142-154, numbers in first-seen order; no
-// order is pinned by the reference -- DESIGN.md section 1).
-template <int NW> __device__ __forceinline__ bool is_src_head(const u64* keys, u64 i) {
-    return i == 0 || !key_eq(key_shr(load_key<NW>(keys, i), 2), key_shr(load_key<NW>(keys, i - 1), 2));
-}
-static_assert(SRC_HEAD_BLOCK == UNIQ_TILE, "group_merge_kernel counts the heads of exactly src_count_kernel's blocks");
-template <int NW>
-__global__ __launch_bounds__(BLOCK) void src_count_kernel(const u64* __restrict__ keys, u64 n, u32* __restrict__ block_counts) {
-    __shared__ u32 wsum[BLOCK / 64];
-    const u64 base = (u64)blockIdx.x * UNIQ_TILE + threadIdx.x;          // rows of BLOCK consecutive edges: coalesced loads
-    u32 mine = 0;
-#pragma unroll
-    for (int j = 0; j < UNIQ_ITEMS; ++j) if (base + (u64)j * BLOCK < n && is_src_head<NW>(keys, base + (u64)j * BLOCK)) ++mine;
-    u32 total;
-    (void)block_excl_scan(mine, wsum, total);
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = total;
-}
-// writes the distinct sources (= node keys) and every edge's source id.  Rows of BLOCK consecutive edges are
-// taken one after the other (coalesced loads and stores); a ballot scan per row keeps the running head count.
-// LABELS: the edges' labels too (labels_kernel's bytes exactly: [pad][ceil(k/4) bytes] per edge), from the keys the kernel holds
-// anyway -- built in LDS, UNIQ_TILE * stride bytes, and written out as whole dwords, so that no second pass reads the keys
-template <int NW, bool LABELS = false>
-__global__ __launch_bounds__(BLOCK) void src_write_kernel(const u64* __restrict__ keys, u64 n, const u64* __restrict__ block_offs,
-                                                           u64* __restrict__ nodes, u64* __restrict__ edge_src, u64* __restrict__ seg_edge, u32 seg_nodes,
-                                                           u32 k, uint8_t* __restrict__ labels) {
-    __shared__ u32 wtot[UNIQ_ITEMS][BLOCK / 64];
-    extern __shared__ u32 src_lbuf[];                      // LABELS: [UNIQ_TILE * stride / 4]
-    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u64 base = (u64)blockIdx.x * UNIQ_TILE;
-    bool head[UNIQ_ITEMS]; u32 before[UNIQ_ITEMS];
-    Key<NW> key[LABELS ? UNIQ_ITEMS : 1];                  // LABELS: the block's keys stay in registers
-    const u32 stride = LABELS ? label_stride_for_k(k) : 0u, pad = LABELS ? label_pad_for_k(k) : 0u;
-    if constexpr (LABELS) {
-#pragma unroll
-        for (int j = 0; j < UNIQ_ITEMS; ++j) { const u64 e = base + (u64)j * BLOCK + threadIdx.x; if (e < n) key[j] = load_key<NW>(keys, e); }
-    }
-#pragma unroll
-    for (int j = 0; j < UNIQ_ITEMS; ++j) {
-        const u64 e = base + (u64)j * BLOCK + threadIdx.x;
-        if constexpr (LABELS) head[j] = e < n && (e == 0 || !key_eq(key_shr(key[j], 2), key_shr(load_key<NW>(keys, e - 1), 2)));
-        else head[j] = e < n && is_src_head<NW>(keys, e);
-        const u64 m = __ballot(head[j]);
-        before[j] = __popcll(m & (lane ? (~0ull >> (64 - lane)) : 0ull));
-        if (lane == 0) wtot[j][wave] = __popcll(m);
-        if constexpr (LABELS) {
-            if (e < n) {
-                uint8_t* p = reinterpret_cast<uint8_t*>(src_lbuf) + (j * BLOCK + threadIdx.x) * stride;
-                p[0] = (uint8_t)pad;
-                for (u32 i = 0; i + 1 < stride; ++i) p[1 + i] = label_byte(key[j], k, i);
-            }
-        }
-    }
-    __syncthreads();
-    if constexpr (LABELS) {
-        // UNIQ_TILE * stride is a multiple of 4, so a block's labels start on a dword; the array's last bytes leave one by one
-        const u32 cnt = (u32)((n - base) < (u64)UNIQ_TILE ? (n - base) : (u64)UNIQ_TILE), nbytes = cnt * stride;
-        const u64 byte0 = base * stride;
-        u32* o32 = reinterpret_cast<u32*>(labels + byte0);
-        for (u32 i = threadIdx.x; i < nbytes / 4; i += BLOCK) o32[i] = src_lbuf[i];
-        for (u32 i = (nbytes / 4) * 4 + threadIdx.x; i < nbytes; i += BLOCK) labels[byte0 + i] = reinterpret_cast<uint8_t*>(src_lbuf)[i];
-    }
-    u64 carry = block_offs[blockIdx.x];
-#pragma unroll
-    for (int j = 0; j < UNIQ_ITEMS; ++j) {
-        u32 woff = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < BLOCK / 64; ++w) { if (w < (int)wave) woff += wtot[j][w]; total += wtot[j][w]; }
-        const u64 e = base + (u64)j * BLOCK + threadIdx.x;
-        if (e < n) {
-            const u64 pos = carry + woff + before[j];           // heads strictly before this edge
-            if (head[j]) {
-                if constexpr (LABELS) store_key<NW>(nodes, pos, key_shr(key[j], 2));
-                else store_key<NW>(nodes, pos, key_shr(load_key<NW>(keys, e), 2));
-                if (seg_edge && pos % seg_nodes == 0) seg_edge[pos / seg_nodes] = e;      // first out-edge of every seg_nodes-th source
-            }
-            edge_src[e] = head[j] ? pos : pos - 1;
-        }
-        carry += total;
-    }
-}
-// edge_dst[e] = position of the edge's target in `nodes`, or ~0 when it is not a source of any edge
-template <int NW>
-__global__ __launch_bounds__(BLOCK) void dst_rank_kernel(const u64* __restrict__ nodes, u64 n_nodes, u32 key_bits, u32 B,
-                                                          const u64* __restrict__ index, const u64* __restrict__ keys, u64 n,
-                                                          u32 k, u64* __restrict__ edge_dst, u64* __restrict__ n_missing) {
-    u32 miss = 0;
-    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
-        Key<NW> key = target_node(load_key<NW>(keys, i), k);
-        u32 b = top_bits(key, key_bits, B);
-        u64 lo = index[b], hi = index[b + 1];
-        while (lo < hi) {
-            u64 mid = (lo + hi) >> 1;
-            if (key_lt(load_key<NW>(nodes, mid), key)) lo = mid + 1; else hi = mid;
-        }
-        const bool found = lo < n_nodes && key_eq(load_key<NW>(nodes, lo), key);
-        edge_dst[i] = found ? lo : ~0ull;
-        miss += !found;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) miss += __shfl_down(miss, o, 64);
-    if ((threadIdx.x & 63) == 0 && miss) atomicAdd((unsigned long long*)n_missing, (unsigned long long)miss);
-}
-// gather the targets that were not found (unordered; they are sorted afterwards).  One cursor atomic per
-// workgroup tile: the misses are sparse, and one atomic per wave on a single address serialises.
-template <int NW>
-__global__ __launch_bounds__(BLOCK) void missing_gather_kernel(const u64* __restrict__ keys, u64 n, u32 k, const u64* __restrict__ edge_dst,
-                                                                u64* __restrict__ out, u64* __restrict__ out_edge, u64* cursor) {
-    __shared__ u32 wsum[BLOCK / 64];
-    __shared__ u64 block_base;
-    const u64 tile = (u64)BLOCK * UNIQ_ITEMS;
-    for (u64 t0 = (u64)blockIdx.x * tile; t0 < n; t0 += (u64)gridDim.x * tile) {
-        bool miss[UNIQ_ITEMS]; u32 mine = 0;
-#pragma unroll
-        for (int j = 0; j < UNIQ_ITEMS; ++j) {
-            const u64 i = t0 + (u64)j * BLOCK + threadIdx.x;
-            miss[j] = i < n && edge_dst[i] == ~0ull;
-            mine += miss[j];
-        }
-        u32 total;
-        const u32 excl = block_excl_scan(mine, wsum, total);
-        if (threadIdx.x == 0 && total) block_base = atomicAdd((unsigned long long*)cursor, (unsigned long long)total);
-        __syncthreads();
-        if (total) {
-            u64 pos = block_base + excl;
-#pragma unroll
-            for (int j = 0; j < UNIQ_ITEMS; ++j)
-                if (miss[j]) {
-                    const u64 e = t0 + (u64)j * BLOCK + threadIdx.x;
-                    store_key<NW>(out, pos, target_node(load_key<NW>(keys, e), k));
-                    out_edge[pos] = e;
-                    ++pos;
-                }
-        }
-        __syncthreads();
-    }
-}
-// second lookup, only for the edges whose target was not a source: id = n_sources + rank among the extra nodes
-template <int NW>
-__global__ __launch_bounds__(BLOCK) void missing_rank_kernel(const u64* __restrict__ miss_key, const u64* __restrict__ miss_edge, u64 n_miss,
-                                                              const u64* __restrict__ extra, u64 n_extra, u64 n_sources,
-                                                              u64* __restrict__ edge_dst) {
-    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n_miss; i += (u64)gridDim.x * BLOCK) {
-        Key<NW> key = load_key<NW>(miss_key, i);
-        u64 lo = 0, hi = n_extra;
-        while (lo < hi) {
-            u64 mid = (lo + hi) >> 1;
-            if (key_lt(load_key<NW>(extra, mid), key)) lo = mid + 1; else hi = mid;
-        }
-        edge_dst[miss_edge[i]] = n_sources + lo;
-    }
-}
-
-// ---- targets looked up by merging ----------------------------------------------------------------------------------
-// Sorted by packed k-mer, the edges fall into four quarters by their first base, and inside a quarter the TARGETS (the low
-// 2(k-1) bits) ascend too.  The sources (ascending) are cut into segments of DST_SEG nodes; a workgroup stages its segment
-// in LDS and walks, quarter by quarter, the one contiguous stretch of edges whose targets lie in the segment's key range:
-// sources and edges are each read once, coalesced, and a target costs a binary search in LDS -- instead of a bucket look-up
-// and a binary search in HBM per edge (dst_rank_kernel) and a second pass that collects the targets not found
-// (missing_gather_kernel): those are staged in LDS and leave with one cursor atomic per MISS_CAP of them.
-#ifndef KATOME_DST_SEG
-#define KATOME_DST_SEG 2048
-#endif
-constexpr u64 DST_IN1 = 1ull << 40;                      // first-seen order: mark in edge_dst, "the target has this in-edge only"
-constexpr u64 DST_FD = 1ull << 41;                       // ... and "this edge is the first to touch its target" (it introduces the node)
-constexpr u64 DST_MARKS = DST_IN1 | DST_FD;
-constexpr u32 DST_SEG = KATOME_DST_SEG;
-// edges per thread and trip (loads and searches in flight): 2 for one-word k-mers, 4 for two-word ones -- measured both ways at C3
-// (11.4 ms with 2, 15.4 with 4) and at k = 40 / 50 M reads (12.0 with 2, 9.2 with 4); -DKATOME_DST_ROWS=n sets both
-template <int NW> struct DstRows {
-#ifdef KATOME_DST_ROWS
-    static constexpr u32 value = KATOME_DST_ROWS;
-#else
-    static constexpr u32 value = NW == 1 ? 2 : 4;
-#endif
-};
-template <int NW> struct MissCap { static constexpr u32 value = (DstRows<NW>::value > 2 ? 2048 : 1024) / NW; };
-static_assert(MissCap<1>::value >= DstRows<1>::value * BLOCK && MissCap<2>::value >= DstRows<2>::value * BLOCK, "a whole trip of misses fits the staging buffer");
-
-template <int NW> __device__ __forceinline__ Key<NW> with_quarter(Key<NW> node, u32 q, u32 node_bits) {
-    if (NW == 1) node.w[0] |= (u64)q << node_bits;
-    else if (node_bits >= 64) node.w[0] |= (u64)q << (node_bits - 64);
-    else { node.w[NW - 1] |= (u64)q << node_bits; node.w[0] |= (u64)q >> (64 - node_bits); }      // (k = 32: node_bits = 62)
-    return node;
-}
-template <int NW> __device__ __forceinline__ u64 lower_bound_keys(const u64* __restrict__ keys, u64 n, const Key<NW>& x) {
-    u64 lo = 0, hi = n;
-    while (lo < hi) {
-        const u64 mid = (lo + hi) >> 1;
-        if (key_lt(load_key<NW>(keys, mid), x)) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-// seg[q][s] = first edge of quarter q whose target is not below the first source of segment s (s = 0: the quarter's start;
-// s = n_seg: its end)
-template <int NW>
-__global__ __launch_bounds__(BLOCK) void dst_seg_kernel(const u64* __restrict__ nodes, const u64* __restrict__ keys, u64 n, u32 node_bits,
-                                                         u64 n_seg, u64* __restrict__ seg) {
-    const u64 total = 4 * (n_seg + 1);
-    for (u64 t = (u64)blockIdx.x * BLOCK + threadIdx.x; t < total; t += (u64)gridDim.x * BLOCK) {
-        const u32 q = (u32)(t / (n_seg + 1));
-        const u64 s = t % (n_seg + 1);
-        Key<NW> v;
-#pragma unroll
-        for (int j = 0; j < NW; ++j) v.w[j] = 0;
-        u64 pos;
-        if (s == n_seg) pos = q == 3 ? n : lower_bound_keys<NW>(keys, n, with_quarter(v, q + 1, node_bits));
-        else {
-            if (s) v = load_key<NW>(nodes, s * DST_SEG);
-            pos = lower_bound_keys<NW>(keys, n, with_quarter(v, q, node_bits));
-        }
-        seg[t] = pos;
-    }
-}
-// edge_dst[e] = position of the edge's target among the sources, or ~0; the targets not found go to miss_key / miss_edge
-// (unordered, as many as fit miss_cap) and are counted in *cursor
-// FIRST (first-seen order): seq[e] = sequence number of the edge's first insertion; node_first[v] (holding the source-role
-// minimum, 2*seq, or all-ones) is lowered to the first touch as a target, 2*seq + 1, with atomics in LDS only
-template <int NW, bool FIRST>
-__global__ __launch_bounds__(BLOCK) void dst_merge_kernel(const u64* __restrict__ nodes, u64 n_src, const u64* __restrict__ keys, u32 k,
-                                                           u64 n_seg, const u64* __restrict__ seg, u64* __restrict__ edge_dst,
-                                                           u64* __restrict__ miss_key, u64* __restrict__ miss_edge, u64 miss_cap, u64* cursor,
-                                                           const u64* __restrict__ seq, u64* __restrict__ node_first,
-                                                           const u64* __restrict__ edge_src, const u64* __restrict__ seg_edge, u64 n_edges) {
-    constexpr u32 MISS_CAP = MissCap<NW>::value, DST_ROWS = DstRows<NW>::value;
-    extern __shared__ u64 lmem[];
-    u64* ls = lmem;                                     // [DST_SEG * NW] the segment's sources
-    u64* lmk = ls + DST_SEG * NW;                       // [MISS_CAP * NW] + [MISS_CAP]: targets not found, and their edges
-    u64* lme = lmk + MISS_CAP * NW;
-    u64* lfirst = lme + MISS_CAP;                       // FIRST: [DST_SEG] first touch as a target
-    u32* lonce = reinterpret_cast<u32*>(lfirst + DST_SEG);   // FIRST: two bitmaps [DST_SEG / 32]: has an in-edge, has several
-    u32* lmore = lonce + DST_SEG / 32;
-    __shared__ u32 lmiss;
-    __shared__ u64 lbase;
-    const u32 tid = threadIdx.x;
-    auto flush = [&]() {                                // (called by every thread, between barriers)
-        const u32 m = lmiss;
-        if (tid == 0 && m) lbase = atomicAdd((unsigned long long*)cursor, (unsigned long long)m);
-        __syncthreads();
-        if (m) {
-            const u64 base = lbase;
-            for (u32 j = tid; j < m; j += BLOCK)
-                if (base + j < miss_cap) {
-                    Key<NW> x;
-#pragma unroll
-                    for (int w = 0; w < NW; ++w) x.w[w] = lmk[j * NW + w];
-                    store_key<NW>(miss_key, base + j, x);
-                    miss_edge[base + j] = lme[j];
-                }
-        }
-        __syncthreads();
-        if (tid == 0) lmiss = 0;
-        __syncthreads();
-    };
-    for (u64 sg = blockIdx.x; sg < n_seg; sg += gridDim.x) {
-        const u64 a = sg * DST_SEG;
-        const u32 cnt = (u32)((n_src - a) < (u64)DST_SEG ? (n_src - a) : (u64)DST_SEG);
-        // the four stretches (one per quarter) are walked as one list of `total` edges, so that a trip is full whatever the
-        // quarters' sizes, and the loads of the next trip are issued before this one's searches (a segment was a chain of
-        // ~9 memory round trips: two per quarter, the second nearly empty)
-        const u64 lo0 = seg[sg], lo1 = seg[(n_seg + 1) + sg], lo2 = seg[2 * (n_seg + 1) + sg], lo3 = seg[3 * (n_seg + 1) + sg];
-        const u64 c1 = seg[sg + 1] - lo0, c2 = c1 + (seg[(n_seg + 1) + sg + 1] - lo1), c3 = c2 + (seg[2 * (n_seg + 1) + sg + 1] - lo2);
-        const u64 total = c3 + (seg[3 * (n_seg + 1) + sg + 1] - lo3);
-        auto edge_of = [&](u64 v) -> u64 { return v < c1 ? lo0 + v : v < c2 ? lo1 + (v - c1) : v < c3 ? lo2 + (v - c2) : lo3 + (v - c3); };
-        Key<NW> e[DST_ROWS], en[DST_ROWS]; u64 sq[DST_ROWS], sqn[DST_ROWS], ei[DST_ROWS], ein[DST_ROWS];
-        auto fetch = [&](u64 c, Key<NW>* ek, u64* es, u64* ex) {
-#pragma unroll
-            for (u32 r = 0; r < DST_ROWS; ++r) {
-                const u64 v = c + (u64)r * BLOCK + tid;
-#pragma unroll
-                for (int w = 0; w < NW; ++w) ek[r].w[w] = 0;
-                es[r] = 0; ex[r] = ~0ull;
-                if (v < total) { const u64 i = edge_of(v); ex[r] = i; ek[r] = load_key<NW>(keys, i); if (FIRST) es[r] = seq[i]; }
-            }
-        };
-        fetch(0, e, sq, ei);                            // (in flight together with the segment's sources below)
-        Key<NW> stage[DST_SEG / BLOCK];
-#pragma unroll
-        for (u32 r = 0; r < DST_SEG / BLOCK; ++r) { const u32 j = r * BLOCK + tid; if (j < cnt) stage[r] = load_key<NW>(nodes, a + j); }
-#pragma unroll
-        for (u32 r = 0; r < DST_SEG / BLOCK; ++r) {
-            const u32 j = r * BLOCK + tid;
-            if (j < cnt) {
-#pragma unroll
-                for (int w = 0; w < NW; ++w) ls[j * NW + w] = stage[r].w[w];
-                if (FIRST) lfirst[j] = ~0ull;
-            }
-        }
-        if (FIRST && tid < 2 * (DST_SEG / 32)) lonce[tid] = 0;          // (lmore follows lonce)
-        if (tid == 0) lmiss = 0;
-        __syncthreads();
-        if (FIRST) {    // source role: the segment's out-edges are one stretch of the edge list; first touch 2 * seq (pt_graph.rs:180-185)
-            const u64 e0 = seg_edge[sg], e1 = sg + 1 < n_seg ? seg_edge[sg + 1] : n_edges;
-            for (u64 e = e0 + tid; e < e1; e += BLOCK)
-                atomicMin((unsigned long long*)&lfirst[(u32)(edge_src[e] - a)], (unsigned long long)(2 * seq[e]));
-        }
-        for (u64 c = 0; c < total; c += (u64)DST_ROWS * BLOCK) {
-            fetch(c + (u64)DST_ROWS * BLOCK, en, sqn, ein);
-            // the searches of a thread's edges advance in lockstep, a fixed number of halving steps each (branch-free lower
-            // bound): DST_ROWS independent LDS reads are in flight per step
-            Key<NW> d[DST_ROWS]; u32 l[DST_ROWS];
-#pragma unroll
-            for (u32 r = 0; r < DST_ROWS; ++r) { d[r] = target_node(e[r], k); l[r] = 0; }
-#pragma unroll
-            for (u32 step = DST_SEG; step >= 1; step >>= 1) {
-#pragma unroll
-                for (u32 r = 0; r < DST_ROWS; ++r) {
-                    const u32 idx = l[r] + step;
-                    const bool in = idx <= cnt;
-                    Key<NW> x;
-#pragma unroll
-                    for (int w = 0; w < NW; ++w) x.w[w] = ls[(in ? idx - 1 : 0) * NW + w];
-                    if (in && key_lt(x, d[r])) l[r] = idx;
-                }
-            }
-#pragma unroll
-            for (u32 r = 0; r < DST_ROWS; ++r) {
-                const u64 i = ei[r];
-                if (i == ~0ull) continue;
-                bool found = false;
-                if (l[r] < cnt) {
-                    Key<NW> x;
-#pragma unroll
-                    for (int w = 0; w < NW; ++w) x.w[w] = ls[l[r] * NW + w];
-                    found = key_eq(x, d[r]);
-                }
-                if (found) {
-                    edge_dst[i] = a + l[r];
-                    if (FIRST) {
-                        atomicMin((unsigned long long*)&lfirst[l[r]], (unsigned long long)(2 * sq[r] + 1));
-                        const u32 bit = 1u << (l[r] & 31);
-                        if (atomicOr(&lonce[l[r] >> 5], bit) & bit) atomicOr(&lmore[l[r] >> 5], bit);
-                    }
-                } else {
-                    edge_dst[i] = ~0ull;
-                    const u32 p = atomicAdd(&lmiss, 1u);
-#pragma unroll
-                    for (int w = 0; w < NW; ++w) lmk[p * NW + w] = d[r].w[w];
-                    lme[p] = i;
-                }
-            }
-            // room for another trip's misses?  Every wave must decide the same, so the count is read between two barriers: a
-            // wave that ran ahead into the next trip could otherwise add to it before a slower one had looked (with the loads
-            // prefetched that did happen: waves parted ways at flush()'s barriers and the grid never finished)
-            __syncthreads();
-            const u32 staged = lmiss;
-            __syncthreads();
-            if (staged + DST_ROWS * BLOCK > MISS_CAP) flush();
-#pragma unroll
-            for (u32 r = 0; r < DST_ROWS; ++r) { e[r] = en[r]; sq[r] = sqn[r]; ei[r] = ein[r]; }
-        }
-        flush();
-        if (FIRST) {                                    // (flush ends with a barrier: the segment's minima are complete)
-            for (u32 j = tid; j < cnt; j += BLOCK) node_first[a + j] = lfirst[j];      // the node's first touch, either role
-            // (no barrier needed before the sweep below reads lfirst: flush ended with one, and nobody has written since)
-            // second sweep: the edge that is the first to touch its target is marked (DST_FD: what the renumbering asks of every
-            // edge, here without a look-up), and so is an edge whose target has no other in-edge (DST_IN1) -- with the matching
-            // mark on the source side (one out-edge) the renumbering can tell the nodes nobody will ever look up (dev_assign_nodes)
-            for (u64 v = tid; v < total; v += BLOCK) {              // (the thread that wrote edge_dst[i])
-                const u64 i = edge_of(v);
-                const u64 d = edge_dst[i];
-                if (d == ~0ull) continue;
-                const u32 l = (u32)(d - a), bit = 1u << (l & 31);
-                u64 marks = (lmore[l >> 5] & bit) ? 0 : DST_IN1;
-                if (lfirst[l] == 2 * seq[i] + 1) marks |= DST_FD;
-                if (marks) edge_dst[i] = d | marks;
-            }
-            __syncthreads();
-        }
-    }
-}
-// the targets that are no source (their ids were written by missing_rank_kernel): first touch of these nodes
-__global__ __launch_bounds__(BLOCK) void missing_first_kernel(const u64* __restrict__ miss_edge, u64 n_miss, const u64* __restrict__ edge_dst,
-                                                               const u64* __restrict__ seq, u64* node_first) {
-    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n_miss; i += (u64)gridDim.x * BLOCK) {
-        const u64 e = miss_edge[i];
-        atomicMin((unsigned long long*)&node_first[edge_dst[e]], (unsigned long long)(2 * seq[e] + 1));
-    }
-}
-
-// the distinct source (k-1)-mers of sorted edges (the run heads of key >> 2), ascending, and every edge's position among them
-// (`slack`: room kept behind them in node_key, in nodes, for the caller to append to)
-// (head_counts: the run heads of every block of UNIQ_TILE edges, counted already by whoever wrote the edges -- group_merge_kernel --
-// so that src_count_kernel need not read them; labels: the edges' labels (dev_labels' bytes) are written on the way, k their k)
-template <int NW>
-static int source_ids_t(const u64* d_edge_key, u64 E, DevBuf& node_key, u64* edge_src, u64* n_src_out, hipStream_t stream, bool with_slack = false,
-                        DevBuf* seg_edge = nullptr, const u32* head_counts = nullptr, u32 k = 0, uint8_t* labels = nullptr) {
-    *n_src_out = 0;
-    if (E == 0) { KCHECK(node_key.alloc(16, stream)); return KATOME_OK; }
-    const u64 nblocks = (E + UNIQ_TILE - 1) / UNIQ_TILE;
-    if (nblocks > 0x7fffffffull) { set_error("node numbering: too many edges"); return KATOME_E_ARG; }
-    if (labels && (uintptr_t)labels % 4) { set_error("label buffer must be 4-byte aligned"); return KATOME_E_ARG; }
-    DevBuf counts(stream), offs(stream);
-    if (!head_counts) KCHECK(counts.alloc(nblocks * 4));
-    KCHECK(offs.alloc((nblocks + 1) * 8));
-    {
-        KernelScope ks(K_SRC_IDS, stream, E);
-        if (!head_counts) hipLaunchKernelGGL(src_count_kernel<NW>, dim3((unsigned)nblocks), dim3(BLOCK), 0, stream, d_edge_key, E, counts.as<u32>());
-        else if (getenv("KATOME_LC_TRACE")) fprintf(stderr, "[node ids] heads from the merge\n");
-        KCHECK(dev_scan_counts(head_counts ? head_counts : counts.as<u32>(), nblocks, offs.as<u64>(), stream));      // (C3: 8e5 counts -- one workgroup walking them alone took 1.2 ms)
-    }
-    u64 n_src = 0;
-    KCHECK_HIP(hipMemcpyAsync(&n_src, offs.as<u64>() + nblocks, 8, hipMemcpyDeviceToHost, stream));
-    KCHECK_HIP(hipStreamSynchronize(stream));
-    // (with_slack: the caller appends the nodes without out-edges -- usually a few percent -- instead of copying the lot)
-    KCHECK(node_key.alloc((n_src + (with_slack ? n_src / 8 + (1u << 16) : 0) + 1) * 8 * NW, stream));
-    if (seg_edge) KCHECK(seg_edge->alloc(((n_src + DST_SEG - 1) / DST_SEG + 1) * 8));        // first out-edge of every DST_SEG-th source
-    {
-        KernelScope ks(K_SRC_IDS, stream, E);
-        if (labels) {
-            if (getenv("KATOME_LC_TRACE")) fprintf(stderr, "[node ids] labels written with the source ids\n");
-            const size_t lds = (size_t)UNIQ_TILE * label_stride_for_k(k);          // (18 KiB at k = 31, 34 KiB at k = 63)
-            hipLaunchKernelGGL((src_write_kernel<NW, true>), dim3((unsigned)nblocks), dim3(BLOCK), lds, stream, d_edge_key, E, offs.as<u64>(), node_key.as<u64>(),
-                               edge_src, seg_edge ? seg_edge->as<u64>() : nullptr, DST_SEG, k, labels);
-        } else {
-            hipLaunchKernelGGL((src_write_kernel<NW, false>), dim3((unsigned)nblocks), dim3(BLOCK), 0, stream, d_edge_key, E, offs.as<u64>(), node_key.as<u64>(), edge_src,
-                               seg_edge ? seg_edge->as<u64>() : nullptr, DST_SEG, 0u, (uint8_t*)nullptr);
-        }
-    }
-    KCHECK_HIP(hipGetLastError());
-    *n_src_out = n_src;
-    return KATOME_OK;
-}
-int dev_source_ids(const uint64_t* d_edge_key, uint64_t n_edges, uint32_t k, DevBuf& node_key, uint64_t* d_edge_src, uint64_t* n_src,
-                   hipStream_t stream) {
-    if (key_words_for_k(k) == 1) return source_ids_t<1>(d_edge_key, n_edges, node_key, d_edge_src, n_src, stream);
-    return source_ids_t<2>(d_edge_key, n_edges, node_key, d_edge_src, n_src, stream);
-}
-
-
-// seq + node_first (first-seen order, both or neither): node_first[v] = the first touch of node v, 2*seq as a source, 2*seq + 1
-// as a target; left empty when the merging look-up is switched off (the caller then runs dev_node_first)
-template <int NW>
-static int node_ids_t(const u64* d_edge_key, u64 E, u32 k, DevBuf& node_key, u64* edge_src, u64* edge_dst, u64* n_nodes,
-                      hipStream_t stream, const u64* seq = nullptr, DevBuf* node_first = nullptr, u64* n_marked = nullptr,
-                      const u32* head_counts = nullptr, uint8_t* labels = nullptr) {
-    *n_nodes = 0;
-    if (n_marked) *n_marked = 0;
-    if (node_first) node_first->release();
-    if (E == 0) { KCHECK(node_key.alloc(16, stream)); return KATOME_OK; }
-    const u32 node_bits = 2 * (k - 1);
-    DevBuf aux(stream);
-    KCHECK(aux.alloc(16));
-    KCHECK_HIP(hipMemsetAsync(aux.p, 0, 16, stream));
-    u64 n_src = 0;
-    static const bool old_lookup = getenv("KATOME_DST_RANK") != nullptr;
-    const bool first = seq && node_first && !old_lookup;
-    DevBuf seg_edge(stream);
-    KCHECK((source_ids_t<NW>(d_edge_key, E, node_key, edge_src, &n_src, stream, true, first ? &seg_edge : nullptr, head_counts, k, labels)));
-    u64* nodes = node_key.as<u64>();
-    // targets -> positions among the sources
-    if (first && n_marked) *n_marked = n_src;            // (edge_dst carries the merge's marks for the targets that are sources)
-    DevBuf miss_key(stream), miss_edge(stream);
-    u64 miss_cap = 0, n_missing = 0;
-    if (!old_lookup) {
-        // merged against the sources segment by segment; the targets that are no source are set aside on the way
-        const u64 n_seg = (n_src + DST_SEG - 1) / DST_SEG;
-        DevBuf seg(stream);
-        KCHECK(seg.alloc(4 * (n_seg + 1) * 8));
-        miss_cap = E / 8 + (1u << 16);
-        if (miss_key.alloc(miss_cap * 8 * NW + 16) != KATOME_OK || miss_edge.alloc(miss_cap * 8 + 16) != KATOME_OK) {
-            miss_key.release(); miss_edge.release();
-            miss_cap = 1u << 16;
-            KCHECK(miss_key.alloc(miss_cap * 8 * NW + 16));
-            KCHECK(miss_edge.alloc(miss_cap * 8 + 16));
-        }
-        hipLaunchKernelGGL(dst_seg_kernel<NW>, dim3(grid_for(4 * (n_seg + 1), BLOCK)), dim3(BLOCK), 0, stream, nodes, d_edge_key, E, node_bits, n_seg, seg.as<u64>());
-        const size_t lds = (size_t)(DST_SEG * NW + MissCap<NW>::value * (NW + 1) + (first ? DST_SEG : 0)) * 8 + (first ? 2 * (DST_SEG / 32) * 4 : 0);
-        const dim3 grid((unsigned)std::min<u64>(n_seg, 256u * 32u));
-        KernelScope ks(K_DST_MERGE, stream, E);
-        if (first) {
-            // (room for the nodes without out-edges, like node_key's)
-            // (the merge writes the first touch of every source; the room behind them, for the nodes without out-edges, starts at all-ones)
-            KCHECK(node_first->alloc(node_key.bytes / NW));
-            KCHECK_HIP(hipMemsetAsync(node_first->as<u64>() + n_src, 0xFF, node_first->bytes - n_src * 8, stream));
-            hipLaunchKernelGGL((dst_merge_kernel<NW, true>), grid, dim3(BLOCK), lds, stream, nodes, n_src, d_edge_key, k, n_seg, seg.as<u64>(), edge_dst,
-                               miss_key.as<u64>(), miss_edge.as<u64>(), miss_cap, aux.as<u64>(), seq, node_first->as<u64>(), edge_src, seg_edge.as<u64>(), E);
-        } else {
-            hipLaunchKernelGGL((dst_merge_kernel<NW, false>), grid, dim3(BLOCK), lds, stream, nodes, n_src, d_edge_key, k, n_seg, seg.as<u64>(), edge_dst,
-                               miss_key.as<u64>(), miss_edge.as<u64>(), miss_cap, aux.as<u64>(), nullptr, nullptr, nullptr, nullptr, E);
-        }
-        KCHECK_HIP(hipGetLastError());
-    } else {
-        u32 B = 1;
-        while ((2ull << B) <= n_src / 8 && B < 27) ++B;
-        if (B > node_bits) B = node_bits;
-        DevBuf index(stream);
-        KCHECK(index.alloc(((1ull << B) + 2) * 8));
-        hipLaunchKernelGGL(bucket_index_kernel<NW>, dim3(grid_for(n_src + 1, BLOCK)), dim3(BLOCK), 0, stream, nodes, n_src, node_bits, B, index.as<u64>());
-        hipLaunchKernelGGL(dst_rank_kernel<NW>, dim3(grid_for(E, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, nodes, n_src, node_bits, B,
-                           index.as<u64>(), d_edge_key, E, k, edge_dst, aux.as<u64>());
-        KCHECK_HIP(hipGetLastError());
-    }
-    KCHECK_HIP(hipMemcpyAsync(&n_missing, aux.p, 8, hipMemcpyDeviceToHost, stream));
-    KCHECK_HIP(hipStreamSynchronize(stream));
-    u64 n_extra = 0;
-    if (n_missing) {
-        DevBuf extra(stream);
-        KCHECK(extra.alloc(n_missing * 8 * NW + 16));
-        if (n_missing > miss_cap) {
-            // (the old look-up, or more targets without out-edges than were given room: a second pass over edge_dst collects
-            // them.  Setting them aside inside dst_rank_kernel was tried: 62 % of its waves hold one, and that many atomics
-            // on one cursor cost more than this pass)
-            miss_key.release(); miss_edge.release();
-            KCHECK(miss_key.alloc(n_missing * 8 * NW + 16));
-            KCHECK(miss_edge.alloc(n_missing * 8 + 16));
-            hipLaunchKernelGGL(missing_gather_kernel<NW>, dim3(grid_for(E, BLOCK * UNIQ_ITEMS, 256u * 16u)), dim3(BLOCK), 0, stream, d_edge_key, E, k,
-                               edge_dst, miss_key.as<u64>(), miss_edge.as<u64>(), aux.as<u64>() + 1);
-            KCHECK_HIP(hipGetLastError());
-        }
-        KCHECK_HIP(hipMemcpyAsync(extra.p, miss_key.p, n_missing * 8 * NW, hipMemcpyDeviceToDevice, stream));
-        KCHECK(dev_sort(extra.as<u64>(), nullptr, n_missing, NW, node_bits, stream));
-        n_extra = n_missing;
-        KCHECK(dev_unique(extra.as<u64>(), n_missing, NW, &n_extra, stream));
-        hipLaunchKernelGGL(missing_rank_kernel<NW>, dim3(grid_for(n_missing, BLOCK)), dim3(BLOCK), 0, stream, miss_key.as<u64>(),
-                           miss_edge.as<u64>(), n_missing, extra.as<u64>(), n_extra, n_src, edge_dst);
-        KCHECK_HIP(hipGetLastError());
-        if (first) {
-            if ((n_src + n_extra + 1) * 8 > node_first->bytes) {
-                DevBuf all(stream);
-                KCHECK(all.alloc((n_src + n_extra + 1) * 8));
-                KCHECK_HIP(hipMemcpyAsync(all.p, node_first->p, n_src * 8, hipMemcpyDeviceToDevice, stream));
-                KCHECK_HIP(hipMemsetAsync(all.as<u64>() + n_src, 0xFF, (n_extra + 1) * 8, stream));
-                const size_t bytes = all.bytes;
-                node_first->adopt(all.take(), bytes);
-            }
-            hipLaunchKernelGGL(missing_first_kernel, dim3(grid_for(n_missing, BLOCK)), dim3(BLOCK), 0, stream, miss_edge.as<u64>(), n_missing, edge_dst, seq,
-                               node_first->as<u64>());
-            KCHECK_HIP(hipGetLastError());
-        }
-        // node_key = sources ++ extra
-        if ((n_src + n_extra + 1) * 8 * NW <= node_key.bytes) {
-            KCHECK_HIP(hipMemcpyAsync(nodes + n_src * NW, extra.p, n_extra * 8 * NW, hipMemcpyDeviceToDevice, stream));
-        } else {
-            DevBuf all(stream);
-            KCHECK(all.alloc((n_src + n_extra + 1) * 8 * NW));
-            KCHECK_HIP(hipMemcpyAsync(all.p, nodes, n_src * 8 * NW, hipMemcpyDeviceToDevice, stream));
-            KCHECK_HIP(hipMemcpyAsync(all.as<u64>() + n_src * NW, extra.p, n_extra * 8 * NW, hipMemcpyDeviceToDevice, stream));
-            const size_t bytes = all.bytes;
-            node_key.adopt(all.take(), bytes);
-        }
-    }
-    *n_nodes = n_src + n_extra;
-    return KATOME_OK;
-}
-
-int dev_node_ids(const uint64_t* d_edge_key, uint64_t n_edges, uint32_t k, DevBuf& node_key, uint64_t* d_edge_src,
-                 uint64_t* d_edge_dst, uint64_t* n_nodes, hipStream_t stream, const uint64_t* d_seq, DevBuf* node_first, uint64_t* n_marked,
-                 const uint32_t* head_counts, uint8_t* d_label) {
-    if (key_words_for_k(k) == 1) return node_ids_t<1>(d_edge_key, n_edges, k, node_key, d_edge_src, d_edge_dst, n_nodes, stream, d_seq, node_first, n_marked,
-                                                      head_counts, d_label);
-    return node_ids_t<2>(d_edge_key, n_edges, k, node_key, d_edge_src, d_edge_dst, n_nodes, stream, d_seq, node_first, n_marked, head_counts, d_label);
-}
-
-// ---- first-seen order: small permutation helpers ---------------------------------------------------
+// ---- small permutation helpers ---------------------------------------------------------------------
 __global__ __launch_bounds__(BLOCK) void iota_kernel(u32* __restrict__ out, u64 n) {
     for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) out[i] = (u32)i;
 }
@@ -2170,196 +1571,6 @@ template <int NW>
 __global__ __launch_bounds__(BLOCK) void gather_keys_kernel(const u64* __restrict__ src, const u32* __restrict__ idx, u64 n, u64* __restrict__ dst) {
     for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) store_key<NW>(dst, i, load_key<NW>(src, idx[i]));
 }
-// dst[i] = map[src[idx[i]]]
-__global__ __launch_bounds__(BLOCK) void gather_mapped_kernel(const u64* __restrict__ src, const u32* __restrict__ idx, const u64* __restrict__ map,
-                                                               u64 n, u64* __restrict__ dst) {
-    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) dst[i] = map[src[idx[i]]];
-}
-// first-seen order: the edges leave key order for sequence order.  Four separate gathers cost six random reads per edge
-// (two of them through the node map); packing each edge into one 32-byte record first (its end points already mapped,
-// the source map read nearly in order because sources ascend with the keys) leaves two.
-struct PackedEdge { u64 k0, k1; u32 src, dst, weight, pad; };
-static_assert(sizeof(PackedEdge) == 32, "packed edge layout");
-template <int NW>
-__global__ __launch_bounds__(BLOCK) void pack_edges_kernel(const u64* __restrict__ key, const u32* __restrict__ weight, const u64* __restrict__ src,
-                                                            const u64* __restrict__ dst, const u64* __restrict__ new_id, u64 n,
-                                                            PackedEdge* __restrict__ out) {
-    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
-        PackedEdge e;
-        e.k0 = key[i * NW]; e.k1 = NW == 2 ? key[i * NW + 1] : 0;
-        e.src = (u32)new_id[src[i]]; e.dst = (u32)new_id[dst[i]]; e.weight = weight[i]; e.pad = 0;
-        out[i] = e;
-    }
-}
-template <int NW>
-__global__ __launch_bounds__(BLOCK) void unpack_edges_kernel(const PackedEdge* __restrict__ in, const u32* __restrict__ idx, u64 n,
-                                                              u64* __restrict__ key, u32* __restrict__ weight, u64* __restrict__ src,
-                                                              u64* __restrict__ dst) {
-    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
-        const PackedEdge e = in[idx[i]];
-        key[i * NW] = e.k0;
-        if (NW == 2) key[i * NW + 1] = e.k1;
-        weight[i] = e.weight; src[i] = e.src; dst[i] = e.dst;
-    }
-}
-// in place: edge arrays permuted by idx (new position i <- old position idx[i]) with end points mapped through new_id;
-// `scratch` needs n * 32 bytes
-int dev_permute_edges(uint64_t* key, uint32_t* weight, uint64_t* src, uint64_t* dst, const uint64_t* new_id, const uint32_t* idx,
-                      uint64_t n, uint32_t nw, void* scratch, hipStream_t stream) {
-    if (n == 0) return KATOME_OK;
-    PackedEdge* aos = (PackedEdge*)scratch;
-    const dim3 grid(grid_for(n, BLOCK, 256u * 32u)), blk(BLOCK);
-    if (nw == 1) {
-        hipLaunchKernelGGL(pack_edges_kernel<1>, grid, blk, 0, stream, key, weight, src, dst, new_id, n, aos);
-        hipLaunchKernelGGL(unpack_edges_kernel<1>, grid, blk, 0, stream, aos, idx, n, key, weight, src, dst);
-    } else {
-        hipLaunchKernelGGL(pack_edges_kernel<2>, grid, blk, 0, stream, key, weight, src, dst, new_id, n, aos);
-        hipLaunchKernelGGL(unpack_edges_kernel<2>, grid, blk, 0, stream, aos, idx, n, key, weight, src, dst);
-    }
-    KCHECK_HIP(hipGetLastError());
-    return KATOME_OK;
-}
-
-// ---- first-seen order without sorting the nodes -------------------------------------------------------------------------
-// A node's index is the rank of its first touch (2 * seq as the source of an edge's first insertion, 2 * seq + 1 as its
-// target), and every touch belongs to exactly one edge: once the edges are in sequence order, the node indices are a running
-// count of "this edge introduces its source / its target" -- a scan over the edges instead of a sort of the nodes.
-// pack: the 32-byte record of dev_permute_edges with the OLD end points and, in `pad`, bit 0 = introduces its source,
-// bit 1 = introduces its target (node_first from dev_node_first)
-template <int NW>
-__global__ __launch_bounds__(BLOCK) void pack_edges_intro_kernel(const u64* __restrict__ key, const u32* __restrict__ weight, const u64* __restrict__ src,
-                                                                  const u64* __restrict__ dst, const u64* __restrict__ seq,
-                                                                  const u64* __restrict__ node_first, u64 n, u64 n_marked, PackedEdge* __restrict__ out) {
-    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
-        PackedEdge e;
-        e.k0 = key[i * NW]; e.k1 = NW == 2 ? key[i * NW + 1] : 0;
-        const u64 s = src[i], dm = dst[i], d = dm & ~DST_MARKS, q = seq[i];
-        e.src = (u32)s; e.dst = (u32)d; e.weight = weight[i];
-        const bool out1 = (i == 0 || src[i - 1] != s) && (i + 1 >= n || src[i + 1] != s);     // the source has this out-edge only
-        // (targets below n_marked carry the answer as a mark from the merge; the others -- nodes without out-edges, or no merge --
-        // are looked up: node_first[s] is read in order, node_first[d] is not)
-        const bool fd = d < n_marked ? (dm & DST_FD) != 0 : node_first[d] == 2 * q + 1;
-        e.pad = (node_first[s] == 2 * q ? 1u : 0u) | (fd ? 2u : 0u) | ((dm & DST_IN1) ? 4u : 0u) | (out1 ? 8u : 0u);
-        out[i] = e;
-    }
-}
-// unpack in sequence order (new position i <- old position idx[i]); the flags ride in bit 32 of the (old) end points;
-// cnt[i] = nodes the edge introduces
-template <int NW>
-__global__ __launch_bounds__(BLOCK) void unpack_edges_intro_kernel(const PackedEdge* __restrict__ in, const u32* __restrict__ idx, u64 n,
-                                                                    u64* __restrict__ key, u32* __restrict__ weight, u64* __restrict__ src,
-                                                                    u64* __restrict__ dst, u32* __restrict__ cnt) {
-    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
-        const PackedEdge e = in[idx[i]];
-        key[i * NW] = e.k0;
-        if (NW == 2) key[i * NW + 1] = e.k1;
-        weight[i] = e.weight;
-        src[i] = (u64)e.src | ((u64)(e.pad & 1u) << 32) | ((u64)((e.pad >> 3) & 1u) << 33);
-        dst[i] = (u64)e.dst | ((u64)((e.pad >> 1) & 1u) << 32) | ((u64)((e.pad >> 2) & 1u) << 33);
-        cnt[i] = (e.pad & 1u) + ((e.pad >> 1) & 1u);
-    }
-}
-// offs = exclusive scan of cnt: the edge's nodes get indices offs[i] (source, if introduced) and the next one (target).
-// The indices reach the OTHER edges of a node through new_id[old index] -- a scattered write and a scattered read per node,
-// the two most expensive steps of the renumbering.  Most nodes never need either: in sequence order an edge is usually
-// followed by the next window of the same read, so a node is introduced as the target of edge i and used as the source of
-// edge i + 1 (remap_ends_kernel reads it off its neighbour); when it has no other in- or out-edge (bits 33: marks from the
-// merge and from the runs of sources) nobody else will ask for it and the write is left out as well.
-template <int NW>
-__global__ __launch_bounds__(BLOCK) void assign_nodes_kernel(const u64* __restrict__ key, const u64* __restrict__ src, const u64* __restrict__ dst,
-                                                              const u64* __restrict__ offs, u64 n, u32 k, u64* __restrict__ new_id,
-                                                              u64* __restrict__ node_key) {
-    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
-        const u64 s = src[i], d = dst[i];
-        const u32 fs = (u32)(s >> 32) & 1u, fd = (u32)(d >> 32) & 1u;
-        if (!(fs | fd)) continue;
-        const Key<NW> e = load_key<NW>(key, i);
-        const u64 base = offs[i];
-        if (fs) { new_id[(u32)s] = base; store_key<NW>(node_key, base, source_node(e)); }
-        if (fd) {
-            store_key<NW>(node_key, base + fs, target_node(e, k));
-            bool alone = false;                         // one in-edge (this one), one out-edge, and that one comes next
-            if (((d >> 33) & 1u) && i + 1 < n) { const u64 s1 = src[i + 1]; alone = ((s1 >> 33) & 1u) && (u32)s1 == (u32)d; }
-            if (!alone) new_id[(u32)d] = base + fs;
-        }
-    }
-}
-__global__ __launch_bounds__(BLOCK) void remap_ends_kernel(const u64* __restrict__ src, const u64* __restrict__ dst, const u64* __restrict__ offs,
-                                                            const u64* __restrict__ new_id, u64 n, u64* __restrict__ osrc, u64* __restrict__ odst) {
-    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
-        const u64 s = src[i], d = dst[i];
-        const u32 fs = (u32)(s >> 32) & 1u, fd = (u32)(d >> 32) & 1u;
-        const u64 base = (fs | fd) ? offs[i] : 0;
-        u64 so;
-        if (fs) so = base;
-        else {
-            const u64 dp = i ? dst[i - 1] : 0;
-            if (i && ((dp >> 32) & 1u) && (u32)dp == (u32)s) so = offs[i - 1] + ((src[i - 1] >> 32) & 1u);      // introduced by the edge before
-            else so = new_id[(u32)s];
-        }
-        osrc[i] = so;
-        odst[i] = fd ? base + fs : new_id[(u32)d];
-    }
-}
-__global__ __launch_bounds__(BLOCK) void clear_marks_kernel(u64* __restrict__ v, u64 n) {
-    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) v[i] &= ~DST_MARKS;
-}
-int dev_clear_dst_marks(uint64_t* dst, uint64_t n, hipStream_t stream) {
-    if (n) hipLaunchKernelGGL(clear_marks_kernel, dim3(grid_for(n, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, dst, n);
-    KCHECK_HIP(hipGetLastError());
-    return KATOME_OK;
-}
-int dev_pack_edges_intro(const uint64_t* key, const uint32_t* weight, const uint64_t* src, const uint64_t* dst, const uint64_t* seq,
-                         const uint64_t* node_first, uint64_t n, uint32_t nw, void* aos, hipStream_t stream, uint64_t n_marked) {
-    if (n == 0) return KATOME_OK;
-    const dim3 grid(grid_for(n, BLOCK, 256u * 32u)), blk(BLOCK);
-    if (nw == 1) hipLaunchKernelGGL(pack_edges_intro_kernel<1>, grid, blk, 0, stream, key, weight, src, dst, seq, node_first, n, n_marked, (PackedEdge*)aos);
-    else         hipLaunchKernelGGL(pack_edges_intro_kernel<2>, grid, blk, 0, stream, key, weight, src, dst, seq, node_first, n, n_marked, (PackedEdge*)aos);
-    KCHECK_HIP(hipGetLastError());
-    return KATOME_OK;
-}
-int dev_unpack_edges_intro(const void* aos, const uint32_t* idx, uint64_t n, uint32_t nw, uint64_t* key, uint32_t* weight, uint64_t* src,
-                           uint64_t* dst, uint32_t* cnt, hipStream_t stream) {
-    if (n == 0) return KATOME_OK;
-    const dim3 grid(grid_for(n, BLOCK, 256u * 32u)), blk(BLOCK);
-    if (nw == 1) hipLaunchKernelGGL(unpack_edges_intro_kernel<1>, grid, blk, 0, stream, (const PackedEdge*)aos, idx, n, key, weight, src, dst, cnt);
-    else         hipLaunchKernelGGL(unpack_edges_intro_kernel<2>, grid, blk, 0, stream, (const PackedEdge*)aos, idx, n, key, weight, src, dst, cnt);
-    KCHECK_HIP(hipGetLastError());
-    return KATOME_OK;
-}
-int dev_assign_nodes(const uint64_t* key, const uint64_t* src, const uint64_t* dst, const uint64_t* offs, uint64_t n, uint32_t nw, uint32_t k,
-                     uint64_t* new_id, uint64_t* node_key, uint64_t* out_src, uint64_t* out_dst, hipStream_t stream) {
-    if (n == 0) return KATOME_OK;
-    const dim3 grid(grid_for(n, BLOCK, 256u * 32u)), blk(BLOCK);
-    if (nw == 1) hipLaunchKernelGGL(assign_nodes_kernel<1>, grid, blk, 0, stream, key, src, dst, offs, n, k, new_id, node_key);
-    else         hipLaunchKernelGGL(assign_nodes_kernel<2>, grid, blk, 0, stream, key, src, dst, offs, n, k, new_id, node_key);
-    hipLaunchKernelGGL(remap_ends_kernel, grid, blk, 0, stream, src, dst, offs, new_id, n, out_src, out_dst);
-    KCHECK_HIP(hipGetLastError());
-    return KATOME_OK;
-}
-
-// inverse of a permutation: inv[perm[i]] = i
-__global__ __launch_bounds__(BLOCK) void invert_kernel(const u32* __restrict__ perm, u64 n, u64* __restrict__ inv) {
-    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) inv[perm[i]] = i;
-}
-// a node is created by the first edge insertion that touches it: as the source of the first window of a strand
-// (2*seq) or as a target (2*seq + 1) -- add_single_edge_fastaq, pt_graph.rs:180-185
-// Source role: the edges are in key order, so a node's out-edges are one run of equal src (and src ascending): the run's head
-// takes the minimum over its run and stores it plainly -- one writer per node, no atomic.  Target role: atomicMin, afterwards.
-__global__ __launch_bounds__(BLOCK) void node_first_src_kernel(const u64* __restrict__ src, const u64* __restrict__ seq, u64 n, u64* __restrict__ node_first) {
-    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
-        const u64 s = src[i];
-        if (i > 0 && src[i - 1] == s) continue;
-        u64 m = seq[i];
-        for (u64 j = i + 1; j < n && src[j] == s; ++j) m = seq[j] < m ? seq[j] : m;      // (<= 4 out-edges per node; BFCounter lists may repeat)
-        node_first[s] = 2 * m;
-    }
-}
-__global__ __launch_bounds__(BLOCK) void node_first_dst_kernel(const u64* __restrict__ dst, const u64* __restrict__ seq, u64 n, u64* node_first) {
-    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK)
-        atomicMin((unsigned long long*)&node_first[dst[i]], (unsigned long long)(2 * seq[i] + 1));
-}
-
 int dev_iota(uint32_t* d, uint64_t n, hipStream_t stream) {
     if (n) hipLaunchKernelGGL(iota_kernel, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, stream, d, n);
     KCHECK_HIP(hipGetLastError());
@@ -2402,121 +1613,6 @@ int dev_gather_keys(const uint64_t* src, const uint32_t* idx, uint64_t n, uint32
         if (nw == 1) hipLaunchKernelGGL(gather_keys_kernel<1>, dim3(grid_for(n, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, src, idx, n, dst);
         else         hipLaunchKernelGGL(gather_keys_kernel<2>, dim3(grid_for(n, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, src, idx, n, dst);
     }
-    KCHECK_HIP(hipGetLastError());
-    return KATOME_OK;
-}
-int dev_gather_mapped(const uint64_t* src, const uint32_t* idx, const uint64_t* map, uint64_t n, uint64_t* dst, hipStream_t stream) {
-    if (n) hipLaunchKernelGGL(gather_mapped_kernel, dim3(grid_for(n, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, src, idx, map, n, dst);
-    KCHECK_HIP(hipGetLastError());
-    return KATOME_OK;
-}
-int dev_invert(const uint32_t* perm, uint64_t n, uint64_t* inv, hipStream_t stream) {
-    if (n) hipLaunchKernelGGL(invert_kernel, dim3(grid_for(n, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, perm, n, inv);
-    KCHECK_HIP(hipGetLastError());
-    return KATOME_OK;
-}
-int dev_node_first(const uint64_t* src, const uint64_t* dst, const uint64_t* seq, uint64_t n, uint64_t* node_first, hipStream_t stream) {
-    // (edges in key order: src ascending in runs)
-    if (n) {
-        hipLaunchKernelGGL(node_first_src_kernel, dim3(grid_for(n, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, src, seq, n, node_first);
-        hipLaunchKernelGGL(node_first_dst_kernel, dim3(grid_for(n, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, dst, seq, n, node_first);
-    }
-    KCHECK_HIP(hipGetLastError());
-    return KATOME_OK;
-}
-
-// ---- edge -> endpoints, labels ----------------------------------------------------------------
-template <int NW>
-__global__ __launch_bounds__(BLOCK) void endpoints_kernel(const u64* __restrict__ ek, u64 n, u32 k, u64* __restrict__ src, u64* __restrict__ dst) {
-    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
-        Key<NW> key = load_key<NW>(ek, i);
-        if (src) store_key<NW>(src, i, source_node(key));
-        if (dst) store_key<NW>(dst, i, target_node(key, k));
-    }
-}
-int dev_endpoints(const uint64_t* d_edge_key, uint64_t n, uint32_t k, uint64_t* d_src, uint64_t* d_dst, hipStream_t stream) {
-    if (n == 0) return KATOME_OK;
-    dim3 grid(grid_for(n, BLOCK)), block(BLOCK);
-    if (key_words_for_k(k) == 1) hipLaunchKernelGGL(endpoints_kernel<1>, grid, block, 0, stream, d_edge_key, n, k, d_src, d_dst);
-    else                         hipLaunchKernelGGL(endpoints_kernel<2>, grid, block, 0, stream, d_edge_key, n, k, d_src, d_dst);
-    KCHECK_HIP(hipGetLastError());
-    return KATOME_OK;
-}
-
-// BFCounter input (create_bfc builder.rs:79-115 -> add_read_bfc pt_graph.rs:317-330 -> add_single_edge_bfc 201-213): every
-// kept line is ONE edge -- and with reverse_complement a second one for its reverse complement, right after it -- added
-// with `add_edge` unconditionally: a k-mer listed twice, or a k-mer that is its own reverse complement, stays as parallel
-// edges.  So there is no table here: line i becomes edge i (2i and 2i+1 with both strands), whose sequence number is its
-// petgraph index.
-template <int NW>
-__global__ __launch_bounds__(BLOCK) void bfc_edges_kernel(const u64* __restrict__ fwd, const u32* __restrict__ w, u64 n, u32 k, bool rc,
-                                                           u64* __restrict__ ek, u32* __restrict__ ew, u64* __restrict__ seq) {
-    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
-        Key<NW> key = load_key<NW>(fwd, i);
-        const u32 wi = w[i];
-        if (rc) {
-            store_key<NW>(ek, 2 * i, key); store_key<NW>(ek, 2 * i + 1, revcomp(key, k));
-            ew[2 * i] = wi; ew[2 * i + 1] = wi;
-            if (seq) { seq[2 * i] = 2 * i; seq[2 * i + 1] = 2 * i + 1; }
-        } else {
-            store_key<NW>(ek, i, key);
-            ew[i] = wi;
-            if (seq) seq[i] = i;
-        }
-    }
-}
-int dev_bfc_edges(const uint64_t* d_fwd, const uint32_t* d_w, uint64_t n, uint32_t k, bool rc, uint64_t* d_edge_key,
-                  uint32_t* d_edge_weight, uint64_t* d_edge_seq, hipStream_t stream) {
-    if (n == 0) return KATOME_OK;
-    dim3 grid(grid_for(n, BLOCK)), block(BLOCK);
-    if (key_words_for_k(k) == 1) hipLaunchKernelGGL(bfc_edges_kernel<1>, grid, block, 0, stream, d_fwd, d_w, n, k, rc, d_edge_key, d_edge_weight, d_edge_seq);
-    else                         hipLaunchKernelGGL(bfc_edges_kernel<2>, grid, block, 0, stream, d_fwd, d_w, n, k, rc, d_edge_key, d_edge_weight, d_edge_seq);
-    KCHECK_HIP(hipGetLastError());
-    return KATOME_OK;
-}
-
-// compress_edge format: [pad][ceil(k/4) bytes].  A workgroup builds the labels of LABEL_ITEMS * 256 edges in LDS and streams
-// them out as whole dwords (the byte stride is odd for most k); four keys per thread are loaded before the first is used (with
-// 256 edges per trip a workgroup moved 4 KB and a CU had too few bytes in flight: 8.1 ms for C3's 27.6 GB).
-constexpr u32 LABEL_ITEMS = 4;
-template <int NW>
-__global__ __launch_bounds__(BLOCK) void labels_kernel(const u64* __restrict__ ek, u64 n, u32 k, uint8_t* __restrict__ out) {
-    extern __shared__ u32 lbuf[];
-    uint8_t* lb = reinterpret_cast<uint8_t*>(lbuf);
-    const u32 stride = label_stride_for_k(k), nb = stride - 1, pad = label_pad_for_k(k);
-    constexpr u32 TILE = BLOCK * LABEL_ITEMS;
-    const u64 ntiles = (n + TILE - 1) / TILE;
-    for (u64 t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const u64 e0 = t * TILE;
-        const u32 cnt = (u32)((n - e0) < (u64)TILE ? (n - e0) : (u64)TILE);
-        Key<NW> key[LABEL_ITEMS];
-#pragma unroll
-        for (u32 r = 0; r < LABEL_ITEMS; ++r) { const u32 j = r * BLOCK + threadIdx.x; if (j < cnt) key[r] = load_key<NW>(ek, e0 + j); }
-#pragma unroll
-        for (u32 r = 0; r < LABEL_ITEMS; ++r) {
-            const u32 j = r * BLOCK + threadIdx.x;
-            if (j < cnt) {
-                uint8_t* p = lb + j * stride;
-                p[0] = (uint8_t)pad;
-                for (u32 i = 0; i < nb; ++i) p[1 + i] = label_byte(key[r], k, i);
-            }
-        }
-        __syncthreads();
-        const u64 byte0 = e0 * stride;                 // TILE*stride is a multiple of 4 -> dword aligned
-        const u32 nbytes = cnt * stride;
-        u32* o32 = reinterpret_cast<u32*>(out + byte0);
-        for (u32 i = threadIdx.x; i < nbytes / 4; i += BLOCK) o32[i] = lbuf[i];
-        for (u32 i = (nbytes / 4) * 4 + threadIdx.x; i < nbytes; i += BLOCK) out[byte0 + i] = lb[i];
-        __syncthreads();
-    }
-}
-int dev_labels(const uint64_t* d_edge_key, uint64_t n, uint32_t k, uint8_t* d_label, hipStream_t stream) {
-    if (n == 0) return KATOME_OK;
-    const size_t lds = (size_t)BLOCK * LABEL_ITEMS * label_stride_for_k(k) + 16;
-    dim3 grid(grid_for(n, BLOCK * LABEL_ITEMS, 256u * 16u)), block(BLOCK);
-    if ((uintptr_t)d_label % 4) { set_error("label buffer must be 4-byte aligned"); return KATOME_E_ARG; }
-    if (key_words_for_k(k) == 1) hipLaunchKernelGGL(labels_kernel<1>, grid, block, lds, stream, d_edge_key, n, k, d_label);
-    else                         hipLaunchKernelGGL(labels_kernel<2>, grid, block, lds, stream, d_edge_key, n, k, d_label);
     KCHECK_HIP(hipGetLastError());
     return KATOME_OK;
 }

@@ -242,7 +242,7 @@ def test_c2_in_full_equals_oracle(oracle):
     assert round(st.avg_out_degree, 2) == round(ref.stats["avg_out_degree"], 2)
     # the same input in the reference's own numbering (petgraph indices in first-seen order, pt_graph.rs:149,194): the four
     # arrays of the oracle's sequential build, index for index -- 1.1e7 edges, where the renumbering's neighbour shortcuts and
-    # left-out table writes (radix.hip) carry most nodes
+    # left-out table writes (first_seen.hip) carry most nodes
     del g, gl, gw, rl, rw
     clean = ascii_reads.copy()
     clean[clean == ord("N")] = ord("C")
@@ -523,7 +523,7 @@ def test_pruning_properties_at_scale():
         dg = b.finalize()
         E0, N0 = dg.n_edges, dg.n_nodes
         # petgraph's numbering: node indices are handed out in the order the edge list first mentions them (source before
-        # target) -- the renumbering's neighbour shortcuts and left-out table writes (radix.hip, assign_nodes_kernel) at a size
+        # target) -- the renumbering's neighbour shortcuts and left-out table writes (first_seen.hip, assign_nodes_kernel) at a size
         # where they carry nearly every node
         mention = torch.stack([dg.edge_src, dg.edge_dst], 1).reshape(-1)
         first = torch.full((N0,), 2 * E0, dtype=torch.int64, device=mention.device)
@@ -776,7 +776,7 @@ def test_first_seen_order_synthetic(oracle, k, rc, n, L, npct):
 def test_first_seen_order_when_most_nodes_have_no_out_edge(oracle, k, rc):
     """reads of exactly k bases: every read is one edge between two nodes nothing continues, so the nodes without out-edges
     outnumber the room the node numbering keeps behind the sources (node keys and first touches are re-housed) and the
-    targets set aside by the merge outnumber their buffer (the collecting pass runs instead) -- radix.hip node_ids_t"""
+    targets set aside by the merge outnumber their buffer (the collecting pass runs instead) -- node_ids.hip node_ids_t"""
     from katome_amd import device as kd
     n = 160_000
     rng = np.random.default_rng(k)

@@ -210,7 +210,7 @@ def test_source_ids(k):
 
 
 def _node_ids_reference(ints, k):
-    """sources ascending, then the targets that are no source, ascending (radix.hip node_ids_t)"""
+    """sources ascending, then the targets that are no source, ascending (node_ids.hip node_ids_t)"""
     mask = (1 << (2 * (k - 1))) - 1
     srcs = sorted({v >> 2 for v in ints})
     src_set = set(srcs)

@@ -24,6 +24,9 @@ def kernels(lib):
                 if cur and line.strip():
                     out[cur].append(re.sub(r"\s*//.*$", "", line).strip())
         at += len(MAGIC)
+    # (the filler behind the last kernel of a section is the file's, not the kernel's: it moves when another kernel comes last)
+    for body in out.values():
+        while body and body[-1] in ("s_nop 0", "s_code_end", "..."): body.pop()
     names = subprocess.run(["c++filt"], input="\n".join(out), capture_output=True, text=True).stdout.splitlines()
     res = {}
     for mangled, dem in zip(out, names):
