@@ -700,6 +700,65 @@ typedef struct {
  * O(share).  KATOME_DIST_SHRINK_FAIL=<rank> (tests): that rank fails after the first ranking round, and every rank returns
  * the error.  `out` and `stats` may be NULL.  Collective.                                                              */
 int  katome_dist_shrink(katome_dist_builder *d, katome_dist_contigs *out, katome_dist_shrink_stats *stats, void *stream);
+/* ---- the end of the sharded pipeline, no gather (katome_amd/csrc/dist_text.hip): text, Contigs::stats and the FASTA file of the
+ * merged edges (unitigs) of the builder's last katome_dist_shrink.  All three are collective; a builder without such a result, or
+ * whose shares were gathered, gets KATOME_E_ARG on every rank.  A failure of a rank's own allocations, launches or checks comes
+ * back on every rank with a message that names the rank (csrc/dist_agree.h).  Memory per rank is O(share).
+ *
+ * katome_dist_contigs_text: the text of this rank's merged edges, each its whole label, in KATOME_TEXT_PLAIN or KATOME_TEXT_FASTA
+ * layout (see katome_dev_collapse).  The order is RANK-MAJOR: contig first_contig + j is this rank's merged edge j, entry j
+ * of every array of katome_dist_contigs (by packed key that is d_edge_head_id order, and one rank's text is the one-GPU text byte
+ * for byte; in FIRST_SEEN_ORDER it is the order of the rank's own edges), and the ranks' texts one after the other, in rank
+ * order, are one valid text -- in FASTA layout a file with the headers >katome_0 ... >katome_<total_contigs - 1> in sequence.
+ * Sorting the records into the global head-id order of the one-GPU result would move the whole text between ranks and is
+ * deliberately not done: a reader that wants that order sorts by d_edge_head_id.  2^31 merged edges
+ * on a rank or a contig of 2^32 bases: KATOME_E_UNSUPPORTED.  KATOME_DIST_TEXT_FAIL=<rank> (tests): that rank fails after the
+ * sizes are known, and every rank returns KATOME_E_UNSUPPORTED naming it.  The arrays are owned by the builder until its next
+ * katome_dist_contigs_text or destroy; a katome_dist_shrink in between makes the result stale for katome_dist_contigs_save. */
+typedef struct {
+    uint64_t n_contigs, first_contig, total_contigs;    /* this rank's merged edges; contigs on lower ranks; all ranks */
+    uint64_t text_bytes, text_base, total_text_bytes;   /* this rank's bytes; bytes of lower ranks; the whole text     */
+    uint32_t layout, _pad;
+    uint64_t *d_contig_off;                             /* offsets relative to this rank's d_text                      */
+    uint32_t *d_contig_len;
+    uint8_t  *d_text;
+} katome_dist_assembly;
+int  katome_dist_contigs_text(katome_dist_builder *d, uint32_t layout, katome_dist_assembly *out, void *stream);
+/* Contigs::stats (see katome_contig_stats_of) of ALL ranks' contigs, the same on every rank and equal, field for field and status
+ * for status, to katome_contig_stats_of over the ranks' lengths put together -- without any rank holding another rank's lengths:
+ * the reference's scans are four radix selections over the k-mer counts (csrc/contig_select.h), four passes over the rank's
+ * d_edge_kmers with one allreduce of 2048 words each.  A contig's length is its k-mer count + k - 1.  The first form works on the
+ * caller's device array (n may be 0), the second on the builder's last katome_dist_shrink. */
+int  katome_dist_contig_stats_arrays(katome_comm *c, int device, const uint32_t *d_edge_kmers, uint64_t n, uint32_t k,
+                                     uint64_t original_genome_length, katome_contig_stats *out, void *stream);
+int  katome_dist_contig_stats(katome_dist_builder *d, uint64_t original_genome_length, katome_contig_stats *out, void *stream);
+/* the file of `a` (what this builder's last katome_dist_contigs_text returned), written by all ranks: rank 0 creates `path` and
+ * sets its length to total_text_bytes -- failure: KATOME_E_OPEN, "couldn't create <path>: <why>" (asm/mod.rs:62), on every rank --,
+ * then every rank copies its text down in chunks of KATOME_DIST_TEXT_CHUNK bytes (default 64 MiB: host memory is O(chunk)) and
+ * writes them at text_base.  Write errors are agreed at the end; when the call fails after the file was created, rank 0 removes
+ * it.  For ranks that are threads of one process, and for process ranks that see one filesystem. */
+int  katome_dist_contigs_save(katome_dist_builder *d, const katome_dist_assembly *a, const char *path);
+/* katome_unitigs_*, the host entry that ends in that file: the build, the flag's remove_dead_paths, the stage letters of `stages` (see
+ * katome_build_*_staged; NULL or "": none), the traversal-free shrink (KATOME_SHRINK_FAST), Contigs::stats of its merged edges
+ * and -- with out_path -- their FASTA file.  The result is a plain struct; the text goes to the file only.  With
+ * settings.n_devices > 1 everything runs on the ranks' shares, never a gather, whatever the environment says (so a graph of
+ * 2^32 edges and more gets its unitigs): katome_dist_remove_dead_paths, the katome_dist_* stages, katome_dist_shrink,
+ * katome_dist_contigs_text, katome_dist_contig_stats and katome_dist_contigs_save; the file's records are then in rank-major
+ * order.  On one GPU: katome_dev_shrink_mode(FAST), katome_dev_contigs_text, katome_contig_stats_of.  Stage letters or
+ * KATOME_FLAG_REMOVE_DEAD_PATHS without KATOME_FLAG_FIRST_SEEN_ORDER: KATOME_E_ARG; a packed-key build without them is fine.  A
+ * tipping point of 0 in the stats: KATOME_E_ARG, with `out` filled and the file written all the same; a path that cannot be
+ * created: KATOME_E_OPEN, "couldn't create <path>: <why>". */
+typedef struct {
+    uint64_t n_contigs, text_bytes, total_bases, longest, read_bytes;   /* text_bytes: of the FASTA text, written or not */
+    uint32_t k, n_devices;
+    katome_contig_stats stats;
+    katome_dist_shrink_stats shrink;       /* zeros on one GPU */
+} katome_unitigs;
+int  katome_unitigs_files(const katome_settings *s, const char *const *paths, size_t n_paths, const char *stages,
+                          uint64_t original_genome_length, const char *out_path /* nullable */, katome_unitigs *out);
+int  katome_unitigs_packed(const katome_settings *s, const uint8_t *packed, uint64_t n_reads, uint32_t read_len,
+                           const uint8_t *skip, const char *stages, uint64_t original_genome_length,
+                           const char *out_path /* nullable */, katome_unitigs *out);
 /* this rank's share of the graph as it stands (after katome_dist_finalize / katome_dist_remove_dead_paths / the stages) */
 int  katome_dist_current_graph(katome_dist_builder *d, katome_dist_graph *out);
 /* katome_dev_graph_stats / katome_dev_weight_spectrum for the SHARDED graph, no gather (katome_amd/csrc/dist_stats.hip): the
@@ -807,6 +866,13 @@ int katome_dev_pieces_text(int device, uint32_t k, const uint8_t *d_label, const
                            const uint32_t *d_pieces, uint64_t n_pieces, uint32_t layout, uint64_t *d_contig_off,
                            uint32_t *d_contig_len, uint64_t contig_cap, uint8_t *d_text, uint64_t text_cap, uint64_t *n_contigs,
                            uint64_t *text_bytes, void *stream);
+/* the same with a starting number: contig c's FASTA header reads ">katome_<first_contig + c>", up to 20 digits (a part of a text
+ * whose other parts are written elsewhere: katome_dist_contigs_text).  katome_dev_pieces_text is this with first_contig = 0.
+ * first_contig + *n_contigs past 2^64: KATOME_E_UNSUPPORTED. */
+int katome_dev_pieces_text_numbered(int device, uint32_t k, const uint8_t *d_label, const uint64_t *d_label_off, uint64_t n_labels,
+                                    const uint32_t *d_pieces, uint64_t n_pieces, uint32_t layout, uint64_t first_contig,
+                                    uint64_t *d_contig_off, uint32_t *d_contig_len, uint64_t contig_cap, uint8_t *d_text,
+                                    uint64_t text_cap, uint64_t *n_contigs, uint64_t *text_bytes, void *stream);
 /* Stats<CollectionStats>::stats for PtGraph (stats/collections.rs:137-168) from device arrays, filled exactly as
  * katome_graph_stats fills it from host arrays: u64 sums, the two averages one f64 division each on the host (no edges:
  * avg_edge_weight is NaN, no nodes: avg_out_degree is NaN, as the reference's 0.0 / 0.0); externals(Incoming) and

@@ -108,6 +108,18 @@ class DistShrinkStats(C.Structure):
                 ("bytes_sent", C.c_uint64)]
 
 
+class DistAssembly(C.Structure):
+    _fields_ = [("n_contigs", C.c_uint64), ("first_contig", C.c_uint64), ("total_contigs", C.c_uint64), ("text_bytes", C.c_uint64),
+                ("text_base", C.c_uint64), ("total_text_bytes", C.c_uint64), ("layout", C.c_uint32), ("_pad", C.c_uint32),
+                ("d_contig_off", C.c_void_p), ("d_contig_len", C.c_void_p), ("d_text", C.c_void_p)]
+
+
+class Unitigs(C.Structure):
+    _fields_ = [("n_contigs", C.c_uint64), ("text_bytes", C.c_uint64), ("total_bases", C.c_uint64), ("longest", C.c_uint64),
+                ("read_bytes", C.c_uint64), ("k", C.c_uint32), ("n_devices", C.c_uint32), ("stats", ContigStats),
+                ("shrink", DistShrinkStats)]
+
+
 class DistStandardizeStats(C.Structure):
     _fields_ = [("route", C.c_uint32), ("rank_rounds", C.c_uint32), ("exchanges", C.c_uint64), ("contigs", C.c_uint64),
                 ("longest_contig", C.c_uint64), ("cycle_edges", C.c_uint64), ("bytes_sent", C.c_uint64)]
@@ -180,6 +192,9 @@ SYMBOLS = {
     "katome_dev_collapse": (_i, [_vp, _u32, C.POINTER(DevAssembly), C.POINTER(CollapseStats), _vp]),
     "katome_dev_contigs_text": (_i, [_vp, C.POINTER(DevContigs), _u32, C.POINTER(DevAssembly), _vp]),
     "katome_dev_pieces_text": (_i, [_i, _u32, _vp, _vp, _u64, _vp, _u64, _u32, _vp, _vp, _u64, _vp, _u64, u64p, u64p, _vp]),
+    "katome_dev_pieces_text_numbered": (_i, [_i, _u32, _vp, _vp, _u64, _vp, _u64, _u32, _u64, _vp, _vp, _u64, _vp, _u64, u64p, u64p, _vp]),
+    "katome_unitigs_files": (_i, [C.POINTER(Settings), _pp, _sz, C.c_char_p, _u64, C.c_char_p, C.POINTER(Unitigs)]),
+    "katome_unitigs_packed": (_i, [C.POINTER(Settings), _vp, _u64, _u32, _vp, C.c_char_p, _u64, C.c_char_p, C.POINTER(Unitigs)]),
     "katome_contig_stats_of": (_i, [u64p, _u64, _u64, C.POINTER(ContigStats)]),
     "katome_assemble_files": (_i, [C.POINTER(Settings), _pp, _sz, _u64, C.c_char_p, C.POINTER(C.POINTER(Assembly))]),
     "katome_assemble_packed": (_i, [C.POINTER(Settings), _vp, _u64, _u32, _vp, _u64, C.c_char_p, C.POINTER(C.POINTER(Assembly))]),
@@ -234,6 +249,10 @@ SYMBOLS = {
     "katome_dist_prune_weak_edges": (_i, [_vp, C.c_uint32, C.POINTER(DistGraph), _vp]),
     "katome_dist_standardize_edges": (_i, [_vp, C.c_uint64, C.c_uint32, C.POINTER(DistGraph), _vp]),
     "katome_dist_shrink": (_i, [_vp, C.POINTER(DistContigs), C.POINTER(DistShrinkStats), _vp]),
+    "katome_dist_contigs_text": (_i, [_vp, _u32, C.POINTER(DistAssembly), _vp]),
+    "katome_dist_contig_stats_arrays": (_i, [_vp, _i, _vp, _u64, _u32, _u64, C.POINTER(ContigStats), _vp]),
+    "katome_dist_contig_stats": (_i, [_vp, _u64, C.POINTER(ContigStats), _vp]),
+    "katome_dist_contigs_save": (_i, [_vp, C.POINTER(DistAssembly), C.c_char_p]),
     "katome_dist_graph_stats": (_i, [_vp, C.POINTER(Stats), _vp]),
     "katome_dist_weight_spectrum": (_i, [_vp, u64p, _u32, _vp]),
     "katome_dist_exchange_count": (_u32, []),

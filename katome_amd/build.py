@@ -439,6 +439,51 @@ class GpuContigs:
         return sorted(zip(self.edge_seq, (int(w) for w in self.edge_weight)))
 
 
+class GpuUnitigs:
+    """The build, the stages asked for and the traversal-free shrink, ending in the unitigs' FASTA file and Contigs::stats
+    (katome_unitigs_*): n_contigs, text_bytes (of the FASTA text), total_bases, longest, read_bytes, k, n_devices, stats
+    (ContigsStats) and, over several GPUs, shrink (the sharded shrink's counters).  With n_devices > 1 everything runs on the
+    ranks' shares, never a gather; the file's records are then in rank-major order."""
+
+    def __init__(self, u):
+        for f in ("n_contigs", "text_bytes", "total_bases", "longest", "read_bytes", "k", "n_devices"):
+            setattr(self, f, getattr(u, f))
+        self.stats = ContigsStats(u.stats.n50, u.stats.l50, u.stats.n90, u.stats.ng50)
+        self.shrink = {f: getattr(u.shrink, f) for f, _ in _lib.DistShrinkStats._fields_}
+
+    @classmethod
+    def create(cls, input_files, ft, reverse_complement, minimal_weight_threshold=0, output_file=None, stages=None,
+               original_genome_length=0, device=0, first_seen_order=False, remove_dead_paths=False, n_devices=1,
+               ranks_share_device=False):
+        """-> (GpuUnitigs, number_of_read_bytes); uses the global k.  stages / remove_dead_paths need first_seen_order"""
+        s = make_settings(K_SIZE, ft, reverse_complement, minimal_weight_threshold, device, first_seen_order=first_seen_order,
+                          remove_dead_paths=remove_dead_paths, n_devices=n_devices, ranks_share_device=ranks_share_device)
+        u = _lib.Unitigs()
+        _check(_lib.lib().katome_unitigs_files(C.byref(s), _paths(input_files), len(input_files), (stages or "").encode(),
+                                               original_genome_length, os.fsencode(output_file) if output_file is not None else None,
+                                               C.byref(u)))
+        return cls(u), u.read_bytes
+
+    @classmethod
+    def create_from_packed(cls, packed, n_reads, read_len, skip=None, reverse_complement=False, minimal_weight_threshold=0,
+                           output_file=None, stages=None, original_genome_length=0, device=0, k=None, first_seen_order=False,
+                           remove_dead_paths=False, n_devices=1, ranks_share_device=False):
+        """the same from 2-bit packed reads (numpy uint8; katome_unitigs_packed)"""
+        s = make_settings(K_SIZE if k is None else k, InputFileType.Fastq, reverse_complement, minimal_weight_threshold, device,
+                          first_seen_order=first_seen_order, remove_dead_paths=remove_dead_paths, n_devices=n_devices,
+                          ranks_share_device=ranks_share_device)
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        skip_p = None
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.uint8)
+            skip_p = skip.ctypes.data
+        u = _lib.Unitigs()
+        _check(_lib.lib().katome_unitigs_packed(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, (stages or "").encode(),
+                                                original_genome_length, os.fsencode(output_file) if output_file is not None else None,
+                                                C.byref(u)))
+        return cls(u), u.read_bytes
+
+
 def _int_to_kmer(v, k):
     return "".join("ACGT"[(v >> (2 * (k - 1 - i))) & 3] for i in range(k))
 

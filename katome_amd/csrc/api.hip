@@ -1549,7 +1549,7 @@ int katome_dev_contigs_text(katome_builder* b, const katome_dev_contigs* c, uint
     }
     {
         PhaseScope ps(b->prof, PH_COLLAPSE, stream);
-        KCHECK(dev_pieces_text(b->s.k, c->d_edge_label, c->d_edge_label_off, c->n_edges, nullptr, c->n_edges, layout, b->unitig_text, stream));
+        KCHECK(dev_pieces_text(b->s.k, c->d_edge_label, c->d_edge_label_off, c->n_edges, nullptr, c->n_edges, layout, 0, b->unitig_text, stream));
     }
     assembly_view(b->unitig_text, out);
     return KATOME_OK;
@@ -1557,6 +1557,13 @@ int katome_dev_contigs_text(katome_builder* b, const katome_dev_contigs* c, uint
 int katome_dev_pieces_text(int device, uint32_t k, const uint8_t* d_label, const uint64_t* d_label_off, uint64_t n_labels, const uint32_t* d_pieces,
                            uint64_t n_pieces, uint32_t layout, uint64_t* d_contig_off, uint32_t* d_contig_len, uint64_t contig_cap, uint8_t* d_text,
                            uint64_t text_cap, uint64_t* n_contigs, uint64_t* text_bytes, void* stream_) {
+    return katome_dev_pieces_text_numbered(device, k, d_label, d_label_off, n_labels, d_pieces, n_pieces, layout, 0, d_contig_off, d_contig_len, contig_cap,
+                                           d_text, text_cap, n_contigs, text_bytes, stream_);
+}
+int katome_dev_pieces_text_numbered(int device, uint32_t k, const uint8_t* d_label, const uint64_t* d_label_off, uint64_t n_labels,
+                                    const uint32_t* d_pieces, uint64_t n_pieces, uint32_t layout, uint64_t first_contig, uint64_t* d_contig_off,
+                                    uint32_t* d_contig_len, uint64_t contig_cap, uint8_t* d_text, uint64_t text_cap, uint64_t* n_contigs,
+                                    uint64_t* text_bytes, void* stream_) {
     KCHECK(use_device(device));
     KCHECK(check_k(k));
     if (!n_contigs || !text_bytes) { set_error("null argument"); return KATOME_E_ARG; }
@@ -1565,7 +1572,7 @@ int katome_dev_pieces_text(int device, uint32_t k, const uint8_t* d_label, const
     if ((uintptr_t)d_label & 3) { set_error("text: d_label must be 4-byte aligned (the kernel reads the aligned words around the bytes it needs)"); return KATOME_E_ARG; }
     if (!d_pieces && n_pieces && n_pieces != n_labels) { set_error("text: without pieces there is one per label"); return KATOME_E_ARG; }
     TextPlan plan;
-    KCHECK(dev_text_plan(k, d_label, d_label_off, n_labels, d_pieces, n_pieces, layout, plan, stream));
+    KCHECK(dev_text_plan(k, d_label, d_label_off, n_labels, d_pieces, n_pieces, layout, first_contig, plan, stream));
     *n_contigs = plan.n_contigs; *text_bytes = plan.text_bytes;
     if (!d_text || plan.text_bytes == 0) return KATOME_OK;
     if (!d_contig_off || !d_contig_len || contig_cap < plan.n_contigs || text_cap < (plan.text_bytes + 15) / 16 * 16 || ((uintptr_t)d_text & 15)) {
@@ -1573,7 +1580,7 @@ int katome_dev_pieces_text(int device, uint32_t k, const uint8_t* d_label, const
                   (unsigned long long)plan.text_bytes);
         return KATOME_E_ARG;
     }
-    KCHECK(dev_text_write(k, d_label, d_label_off, d_pieces, n_pieces, layout, plan, d_contig_off, d_contig_len, d_text, stream));
+    KCHECK(dev_text_write(k, d_label, d_label_off, d_pieces, n_pieces, layout, first_contig, plan, d_contig_off, d_contig_len, d_text, stream));
     KCHECK_HIP(hipStreamSynchronize(stream));
     return KATOME_OK;
 }

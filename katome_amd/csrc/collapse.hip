@@ -10,6 +10,9 @@
 //   one 128-bit store: it finds its piece in LDS and, when its 16 bytes are 16 bases of that one piece, cuts 32 bits out of the 2-bit
 //   source at whatever base offset they start (k-1 is rarely a multiple of 4) and turns them into ASCII four at a time (v_perm_b32);
 //   lanes whose bytes straddle a piece boundary, a FASTA header or a newline go byte by byte, and still store once.
+// A FASTA header carries first_contig + the contig's index (u64, up to 20 digits): the text may be one rank's part of a larger one
+// (dist_text.hip).  Its digits are counted once, when the pieces are measured; the writing kernel takes a header's length from the
+// scanned sizes, so the 16-bases path does no digit arithmetic.
 #include <algorithm>
 #include <chrono>
 #include <new>
@@ -29,14 +32,14 @@ constexpr u32 ACGT = 0x54474341u;                      // 'A' 'C' 'G' 'T', code 
 constexpr u32 MAX_LABEL_BYTES = 1u << 29;              // a label of 2^31 bases: its sizes would not fit 32 bits
 enum { ERR_PIECE = 1, ERR_LABEL = 2, ERR_CONTIG_LEN = 4, ERR_LABEL_LEN = 8, ERR_FIRST = 16 };
 
-__device__ __forceinline__ u32 decimal_digits(u32 v) {
+__device__ __forceinline__ u32 decimal_digits(u64 v) {
     u32 d = 1;
-    for (u32 t = 10; d < 10 && v >= t; t *= 10) ++d;
+    for (u64 t = 10; v >= t; t *= 10) { ++d; if (d == 20) break; }      // (10^20 does not fit 64 bits)
     return d;
 }
 __device__ __forceinline__ u32 piece_word(const u32* pieces, u32 p) { return pieces ? pieces[p] : (p | WHOLE); }
-// bytes in front of a contig's bases (FASTA: ">katome_<i>\n")
-__device__ __forceinline__ u32 header_bytes(u32 fasta, u32 contig) { return fasta ? 9 + decimal_digits(contig) : 0; }
+// bytes in front of a contig's bases (FASTA: ">katome_<i>\n"; i = the caller's first_contig + the contig's index, up to 20 digits)
+__device__ __forceinline__ u32 header_bytes(u32 fasta, u64 contig) { return fasta ? 9 + decimal_digits(contig) : 0; }
 
 __global__ __launch_bounds__(BLOCK) void piece_flag_kernel(const u32* __restrict__ pieces, u64 P, u32* __restrict__ flag) {
     for (u64 p = (u64)blockIdx.x * BLOCK + threadIdx.x; p < P; p += (u64)gridDim.x * BLOCK) flag[p] = piece_word(pieces, (u32)p) >> 31;
@@ -46,8 +49,8 @@ __global__ __launch_bounds__(BLOCK) void piece_flag_kernel(const u32* __restrict
 // layout the header in front of a contig's first piece and the newline behind its last.  Checks everything the writing kernel will
 // read through: a piece names a label, the label's offsets lie inside the labels, its pad byte and length make sense.
 __global__ __launch_bounds__(BLOCK) void piece_measure_kernel(u32 k, const uint8_t* __restrict__ label, const u64* __restrict__ label_off, u64 n_labels,
-                                                              const u32* __restrict__ pieces, u64 P, u32 fasta, const u64* __restrict__ contig_idx,
-                                                              u32* __restrict__ size, u32* __restrict__ err) {
+                                                              const u32* __restrict__ pieces, u64 P, u32 fasta, u64 first_contig,
+                                                              const u64* __restrict__ contig_idx, u32* __restrict__ size, u32* __restrict__ err) {
     const u64 label_bytes = label_off[n_labels];
     for (u64 p = (u64)blockIdx.x * BLOCK + threadIdx.x; p < P; p += (u64)gridDim.x * BLOCK) {
         const u32 w = piece_word(pieces, (u32)p), id = w & ~WHOLE;
@@ -62,7 +65,7 @@ __global__ __launch_bounds__(BLOCK) void piece_measure_kernel(u32 k, const uint8
         if (pad > 3 || packed < pad + k) { atomicOr(err, (u32)ERR_LABEL); continue; }
         u32 n = packed - pad - (whole ? 0 : k - 1);
         if (fasta) {
-            if (whole) n += header_bytes(1, (u32)contig_idx[p]);
+            if (whole) n += header_bytes(1, first_contig + contig_idx[p]);
             if (p + 1 == P || piece_word(pieces, (u32)(p + 1)) >> 31) n += 1;
         }
         size[p] = n;
@@ -71,12 +74,12 @@ __global__ __launch_bounds__(BLOCK) void piece_measure_kernel(u32 k, const uint8
 
 // contig i's first base and its length in bases, from the pieces' offsets: the first piece of a contig writes the offset, the last
 // one (a launch later) the length
-__global__ __launch_bounds__(BLOCK) void contig_bounds_kernel(const u32* __restrict__ pieces, u64 P, u32 fasta, const u64* __restrict__ contig_idx,
-                                                              const u64* __restrict__ piece_off, int lengths, u64* __restrict__ contig_off,
-                                                              u32* __restrict__ contig_len, u32* __restrict__ err) {
+__global__ __launch_bounds__(BLOCK) void contig_bounds_kernel(const u32* __restrict__ pieces, u64 P, u32 fasta, u64 first_contig,
+                                                              const u64* __restrict__ contig_idx, const u64* __restrict__ piece_off, int lengths,
+                                                              u64* __restrict__ contig_off, u32* __restrict__ contig_len, u32* __restrict__ err) {
     for (u64 p = (u64)blockIdx.x * BLOCK + threadIdx.x; p < P; p += (u64)gridDim.x * BLOCK) {
         if (!lengths) {
-            if (piece_word(pieces, (u32)p) >> 31) { const u64 c = contig_idx[p]; contig_off[c] = piece_off[p] + header_bytes(fasta, (u32)c); }
+            if (piece_word(pieces, (u32)p) >> 31) { const u64 c = contig_idx[p]; contig_off[c] = piece_off[p] + header_bytes(fasta, first_contig + c); }
         } else if (p + 1 == P || piece_word(pieces, (u32)(p + 1)) >> 31) {
             const u64 c = contig_idx[p + 1] - 1, len = piece_off[p + 1] - (fasta ? 1 : 0) - contig_off[c];
             if (len > 0xFFFFFFFFull) atomicOr(err, (u32)ERR_CONTIG_LEN);
@@ -101,10 +104,12 @@ struct Piece {
     const uint8_t* src;       // the label's packed bases
     u32 first;                // the piece's first base in the label (0, or k - 1 for a remainder piece)
     u32 bases, head, total;   // bases it writes; bytes in front of them; all its bytes (a newline behind the bases when total > head + bases)
-    u32 contig;
+    u64 contig;               // the number in its header
 };
+// (the header's length is what the piece's scanned size leaves over: no digit is counted here, on the way to the 16-bases store)
 __device__ __forceinline__ Piece load_piece(u32 p, u32 P, u32 k, const uint8_t* __restrict__ label, const u64* __restrict__ label_off,
-                                            const u32* __restrict__ pieces, u32 fasta, const u64* __restrict__ contig_idx) {
+                                            const u32* __restrict__ pieces, u32 fasta, u64 first_contig, const u64* __restrict__ contig_idx,
+                                            const u64* __restrict__ piece_off) {
     const u32 w = piece_word(pieces, p), id = w & ~WHOLE;
     const bool whole = w >> 31;
     const u64 lo = label_off[id], hi = label_off[id + 1];
@@ -112,9 +117,10 @@ __device__ __forceinline__ Piece load_piece(u32 p, u32 P, u32 k, const uint8_t* 
     pc.src = label + lo + 1;
     pc.first = whole ? 0 : k - 1;
     pc.bases = 4 * (u32)(hi - lo - 1) - label[lo] - pc.first;
-    pc.contig = fasta && whole ? (u32)contig_idx[p] : 0;
-    pc.head = whole ? header_bytes(fasta, pc.contig) : 0;
-    pc.total = pc.head + pc.bases + (fasta && (p + 1 == P || piece_word(pieces, p + 1) >> 31) ? 1 : 0);
+    pc.contig = fasta && whole ? first_contig + contig_idx[p] : 0;
+    pc.total = (u32)(piece_off[p + 1] - piece_off[p]);
+    const u32 tail = fasta && (p + 1 == P || piece_word(pieces, p + 1) >> 31) ? 1 : 0;
+    pc.head = fasta && whole ? pc.total - pc.bases - tail : 0;
     return pc;
 }
 // byte r of a piece's output
@@ -123,7 +129,7 @@ __device__ __forceinline__ u32 piece_byte(const Piece& pc, u32 r) {
         if (r < 4) return (0x74616B3Eu >> (8 * r)) & 0xFF;               // ">kat"
         if (r < 8) return (0x5F656D6Fu >> (8 * (r - 4))) & 0xFF;         // "ome_"
         if (r == pc.head - 1) return '\n';
-        u32 v = pc.contig;
+        u64 v = pc.contig;
         for (u32 t = pc.head - 2 - r; t > 0; --t) v /= 10;               // digits behind this one
         return '0' + v % 10;
     }
@@ -152,8 +158,9 @@ __device__ __forceinline__ uint4 sixteen_bases(const uint8_t* src, u32 b) {
 }
 
 __global__ __launch_bounds__(BLOCK) void text_write_kernel(u32 k, const uint8_t* __restrict__ label, const u64* __restrict__ label_off,
-                                                           const u32* __restrict__ pieces, u32 P, u32 fasta, const u64* __restrict__ contig_idx,
-                                                           const u64* __restrict__ piece_off, u64 total, uint8_t* __restrict__ text) {
+                                                           const u32* __restrict__ pieces, u32 P, u32 fasta, u64 first_contig,
+                                                           const u64* __restrict__ contig_idx, const u64* __restrict__ piece_off, u64 total,
+                                                           uint8_t* __restrict__ text) {
     __shared__ uint16_t s_off[TILE];       // where the tile's pieces start, relative to the tile (every piece is at least one byte)
     const u32 tid = threadIdx.x;
     const u64 n_tiles = (total + TILE - 1) / TILE;
@@ -172,7 +179,7 @@ __global__ __launch_bounds__(BLOCK) void text_write_kernel(u32 k, const uint8_t*
             while (hi - lo > 1) { const u32 mid = (lo + hi) >> 1; if (s_off[mid] <= rel) lo = mid; else hi = mid; }
             u32 p = p_lo + lo;
             u32 r = (u32)(o - piece_off[p]);
-            Piece pc = load_piece(p, P, k, label, label_off, pieces, fasta, contig_idx);
+            Piece pc = load_piece(p, P, k, label, label_off, pieces, fasta, first_contig, contig_idx, piece_off);
             uint4 v;
             if (r >= pc.head && r - pc.head + 16 <= pc.bases) {
                 v = sixteen_bases(pc.src, pc.first + r - pc.head);
@@ -182,7 +189,7 @@ __global__ __launch_bounds__(BLOCK) void text_write_kernel(u32 k, const uint8_t*
                 for (int i = 0; i < 16; ++i) {
                     if (p < P && r >= pc.total) {
                         ++p; r = 0;
-                        if (p < P) pc = load_piece(p, P, k, label, label_off, pieces, fasta, contig_idx);
+                        if (p < P) pc = load_piece(p, P, k, label, label_off, pieces, fasta, first_contig, contig_idx, piece_off);
                     }
                     if (p < P) { w[i >> 2] |= piece_byte(pc, r) << (8 * (i & 3)); ++r; }
                 }
@@ -206,7 +213,7 @@ int check_plan_errors(u32 err) {
 }  // namespace
 
 int dev_text_plan(uint32_t k, const uint8_t* label, const uint64_t* label_off, uint64_t n_labels, const uint32_t* pieces, uint64_t n_pieces,
-                  uint32_t layout, TextPlan& plan, hipStream_t stream) {
+                  uint32_t layout, uint64_t first_contig, TextPlan& plan, hipStream_t stream) {
     plan.n_contigs = plan.text_bytes = 0;
     if (layout > KATOME_TEXT_FASTA) { set_error("text: unknown layout %u", layout); return KATOME_E_ARG; }
     if (n_pieces >= 0x80000000ull) { set_error("text: %llu pieces, at most 2^31 - 1", (unsigned long long)n_pieces); return KATOME_E_UNSUPPORTED; }
@@ -221,8 +228,8 @@ int dev_text_plan(uint32_t k, const uint8_t* label, const uint64_t* label_off, u
     hipLaunchKernelGGL(piece_flag_kernel, grid, blk, 0, stream, pieces, P, counts.as<u32>());
     KCHECK_HIP(hipGetLastError());
     KCHECK(dev_scan_counts(counts.as<u32>(), P, plan.contig_idx.as<u64>(), stream));
-    hipLaunchKernelGGL(piece_measure_kernel, grid, blk, 0, stream, k, label, label_off, n_labels, pieces, P, layout, plan.contig_idx.as<u64>(),
-                       counts.as<u32>(), tail.as<u32>());
+    hipLaunchKernelGGL(piece_measure_kernel, grid, blk, 0, stream, k, label, label_off, n_labels, pieces, P, layout, first_contig,
+                       plan.contig_idx.as<u64>(), counts.as<u32>(), tail.as<u32>());
     KCHECK_HIP(hipGetLastError());
     KCHECK(dev_scan_counts(counts.as<u32>(), P, plan.piece_off.as<u64>(), stream));
     u32 err = 0;
@@ -231,11 +238,17 @@ int dev_text_plan(uint32_t k, const uint8_t* label, const uint64_t* label_off, u
     KCHECK_HIP(hipMemcpyAsync(&err, tail.p, 4, hipMemcpyDeviceToHost, stream));
     KCHECK_HIP(hipStreamSynchronize(stream));
     if (err) { plan.n_contigs = plan.text_bytes = 0; }
-    return check_plan_errors(err);
+    KCHECK(check_plan_errors(err));
+    if (first_contig > ~0ull - plan.n_contigs) {
+        set_error("text: %llu contigs numbered from %llu on do not fit 64 bits", (unsigned long long)plan.n_contigs, (unsigned long long)first_contig);
+        plan.n_contigs = plan.text_bytes = 0;
+        return KATOME_E_UNSUPPORTED;
+    }
+    return KATOME_OK;
 }
 
 int dev_text_write(uint32_t k, const uint8_t* label, const uint64_t* label_off, const uint32_t* pieces, uint64_t n_pieces, uint32_t layout,
-                   const TextPlan& plan, uint64_t* contig_off, uint32_t* contig_len, uint8_t* text, hipStream_t stream) {
+                   uint64_t first_contig, const TextPlan& plan, uint64_t* contig_off, uint32_t* contig_len, uint8_t* text, hipStream_t stream) {
     if (n_pieces == 0 || plan.text_bytes == 0) return KATOME_OK;
     const u64 P = n_pieces;
     const dim3 grid(grid_for(P, BLOCK, 256u * 32u)), blk(BLOCK);
@@ -243,8 +256,8 @@ int dev_text_write(uint32_t k, const uint8_t* label, const uint64_t* label_off, 
     KCHECK(tail.alloc(16));
     KCHECK_HIP(hipMemsetAsync(tail.p, 0, 16, stream));
     for (int lengths = 0; lengths < 2; ++lengths)
-        hipLaunchKernelGGL(contig_bounds_kernel, grid, blk, 0, stream, pieces, P, layout, plan.contig_idx.as<u64>(), plan.piece_off.as<u64>(), lengths,
-                           contig_off, contig_len, tail.as<u32>());
+        hipLaunchKernelGGL(contig_bounds_kernel, grid, blk, 0, stream, pieces, P, layout, first_contig, plan.contig_idx.as<u64>(), plan.piece_off.as<u64>(),
+                           lengths, contig_off, contig_len, tail.as<u32>());
     KCHECK_HIP(hipGetLastError());
     u32 err = 0;
     KCHECK_HIP(hipMemcpyAsync(&err, tail.p, 4, hipMemcpyDeviceToHost, stream));
@@ -254,20 +267,20 @@ int dev_text_write(uint32_t k, const uint8_t* label, const uint64_t* label_off, 
         KernelScope ks(K_TEXT_WRITE, stream, plan.text_bytes);
         const u64 tiles = (plan.text_bytes + TILE - 1) / TILE;
         hipLaunchKernelGGL(text_write_kernel, dim3(grid_for(tiles, 1, 256u * 16u)), blk, 0, stream, k, label, label_off, pieces, (u32)P, layout,
-                           plan.contig_idx.as<u64>(), plan.piece_off.as<u64>(), plan.text_bytes, text);
+                           first_contig, plan.contig_idx.as<u64>(), plan.piece_off.as<u64>(), plan.text_bytes, text);
         KCHECK_HIP(hipGetLastError());
     }
     return KATOME_OK;
 }
 
 int dev_pieces_text(uint32_t k, const uint8_t* label, const uint64_t* label_off, uint64_t n_labels, const uint32_t* pieces, uint64_t n_pieces,
-                    uint32_t layout, TextOutput& out, hipStream_t stream) {
+                    uint32_t layout, uint64_t first_contig, TextOutput& out, hipStream_t stream) {
     out.n_contigs = out.text_bytes = 0; out.layout = layout;
     TextPlan plan;
-    KCHECK(dev_text_plan(k, label, label_off, n_labels, pieces, n_pieces, layout, plan, stream));
+    KCHECK(dev_text_plan(k, label, label_off, n_labels, pieces, n_pieces, layout, first_contig, plan, stream));
     KCHECK(out.contig_off.alloc((plan.n_contigs + 1) * 8, stream)); KCHECK(out.contig_len.alloc((plan.n_contigs + 1) * 4, stream));
     KCHECK(out.text.alloc((plan.text_bytes + 15) / 16 * 16 + 16, stream));
-    KCHECK(dev_text_write(k, label, label_off, pieces, n_pieces, layout, plan, out.contig_off.as<u64>(), out.contig_len.as<u32>(),
+    KCHECK(dev_text_write(k, label, label_off, pieces, n_pieces, layout, first_contig, plan, out.contig_off.as<u64>(), out.contig_len.as<u32>(),
                           out.text.as<uint8_t>(), stream));
     KCHECK_HIP(hipStreamSynchronize(stream));
     out.n_contigs = plan.n_contigs; out.text_bytes = plan.text_bytes;
@@ -333,7 +346,7 @@ int dev_collapse(const ShrinkInput& g, const uint32_t* edge_age, ShrinkOutput& s
     KCHECK(d_pieces.alloc(P * 4 + 16));
     const auto t1 = std::chrono::steady_clock::now();
     KCHECK_HIP(hipMemcpyAsync(d_pieces.p, pieces.data(), P * 4, hipMemcpyHostToDevice, stream));
-    KCHECK(dev_pieces_text(g.k, shrunk.edge_label.as<uint8_t>(), shrunk.edge_label_off.as<u64>(), H, d_pieces.as<u32>(), P, layout, out, stream));
+    KCHECK(dev_pieces_text(g.k, shrunk.edge_label.as<uint8_t>(), shrunk.edge_label_off.as<u64>(), H, d_pieces.as<u32>(), P, layout, 0, out, stream));
     st.text_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
     if (out.n_contigs != walk.n_contigs) { set_error("collapse: the device counted %llu contigs, the walk %llu", (unsigned long long)out.n_contigs, (unsigned long long)walk.n_contigs); return KATOME_E_DEVICE; }
     if (stats) *stats = st;

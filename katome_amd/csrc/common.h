@@ -1,6 +1,7 @@
 // common.h -- shared host-side plumbing of libkatome_gpu (error state, HIP checks, device buffers)
 #pragma once
 #include <hip/hip_runtime.h>
+#include <errno.h>
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -420,19 +421,31 @@ struct TextOutput {
     uint64_t n_contigs = 0, text_bytes = 0;
     uint32_t layout = 0;
 };
+// (first_contig: contig c's FASTA header reads ">katome_<first_contig + c>"; first_contig + the contigs past 2^64: KATOME_E_UNSUPPORTED)
 // sizes of the text of `n_pieces` pieces over `n_labels` labels (validated on the device first): every piece's contig (contig_idx) and output offset (piece_off), both scanned, one entry more than pieces
 struct TextPlan {
     DevBuf contig_idx, piece_off;
     uint64_t n_contigs = 0, text_bytes = 0;
 };
 int dev_text_plan(uint32_t k, const uint8_t* label, const uint64_t* label_off, uint64_t n_labels, const uint32_t* pieces, uint64_t n_pieces,
-                  uint32_t layout, TextPlan& plan, hipStream_t stream);
+                  uint32_t layout, uint64_t first_contig, TextPlan& plan, hipStream_t stream);
 int dev_text_write(uint32_t k, const uint8_t* label, const uint64_t* label_off, const uint32_t* pieces, uint64_t n_pieces, uint32_t layout,
-                   const TextPlan& plan, uint64_t* contig_off, uint32_t* contig_len, uint8_t* text, hipStream_t stream);
+                   uint64_t first_contig, const TextPlan& plan, uint64_t* contig_off, uint32_t* contig_len, uint8_t* text, hipStream_t stream);
 int dev_pieces_text(uint32_t k, const uint8_t* label, const uint64_t* label_off, uint64_t n_labels, const uint32_t* pieces, uint64_t n_pieces,
-                    uint32_t layout, TextOutput& out, hipStream_t stream);
+                    uint32_t layout, uint64_t first_contig, TextOutput& out, hipStream_t stream);
 int dev_collapse(const ShrinkInput& g, const uint32_t* edge_age, ShrinkOutput& shrunk, uint32_t layout, TextOutput& out,
                  katome_collapse_stats* stats, std::vector<uint64_t>* lengths, hipStream_t stream);
+
+// Contigs::stats' panic sites as a status (contig_stats.h's 1, 2, 3: which tipping point is 0), one message wherever the stats are made
+inline int contig_stats_status(int which) {
+    if (which <= 0) return KATOME_OK;
+    static const char* const names[] = {"", "n50 (sum of the lengths / 2)", "n90 (0.1 * sum of the lengths, truncated)", "ng50 (original_genome_length / 2)"};
+    set_error("called `Option::unwrap()` on a `None` value: the tipping point of %s is 0", names[which < 4 ? which : 0]);       // stats/contigs.rs:86-88
+    return KATOME_E_ARG;
+}
+// io::Error::description() of the kinds File::create meets (asm/mod.rs:62, "couldn't create <path>: <why>"), as an index that can travel
+static const char* const CREATE_ERROR_KINDS[5] = {"", "entity not found", "permission denied", "entity already exists", "other os error"};
+inline uint32_t create_error_kind(int e) { return e == ENOENT ? 1 : (e == EACCES || e == EPERM) ? 2 : e == EEXIST ? 3 : 4; }
 
 constexpr int KATOME_MAX_RANKS = 16;      // ranks of a sharded build (an MI355X node has 8 GPUs)
 

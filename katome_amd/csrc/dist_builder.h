@@ -54,6 +54,12 @@ struct katome_dist_builder {
     // the last katome_dist_shrink's merged edges on this rank (dist_shrink.hip), kept until the next call or destroy
     DevBuf sh_src, sh_dst, sh_weight, sh_kmers, sh_label_off, sh_label, sh_head, sh_node_id, sh_node_key;
     uint64_t sh_edges = 0, sh_nodes = 0, sh_total_edges = 0, sh_total_nodes = 0, sh_label_bytes = 0;
+    bool sh_valid = false;                   // a katome_dist_shrink has finished and none has started since
+    uint64_t sh_serial = 0;                  // katome_dist_shrink calls so far
+    // the text of that result on this rank (dist_text.hip, katome_dist_contigs_text), kept until the next call or destroy
+    katome::TextOutput sh_text;
+    uint64_t sh_text_serial = 0, sh_text_first = 0, sh_text_base = 0, sh_text_total = 0, sh_text_contigs = 0;
+    bool sh_text_valid = false;
     // what the last katome_dist_standardize_contigs that finished on this builder did (katome_dist_standardize_stats_read)
     katome_dist_standardize_stats contigs_stats = {};
     bool contigs_stats_valid = false;

@@ -489,7 +489,9 @@ int katome_dist_shrink(katome_dist_builder* d, katome_dist_contigs* out, katome_
     static const bool trace = getenv("KATOME_DIST_SHRINK_TRACE") != nullptr;
     katome_dist_shrink_stats st;
     const double t0 = now_ms();
+    d->sh_valid = false; ++d->sh_serial;      // (what katome_dist_contigs_text made of the last result is no longer this builder's text)
     KCHECK(dist_shrink(d, &st, stream));
+    d->sh_valid = true;
     if (trace)
         fprintf(stderr, "[katome_dist_shrink] rank %d/%d: %.2f ms, ranking rounds %u, cycle rounds %u, longest path %llu, sent %llu bytes\n", d->rank(),
                 d->world(), now_ms() - t0, st.rank_rounds, st.cycle_rounds, (unsigned long long)st.longest_path, (unsigned long long)st.bytes_sent);

@@ -17,6 +17,7 @@
 // exchange.
 #include <string>
 
+#include "dist_agree.h"
 #include "dist_links.h"
 
 namespace {
@@ -36,31 +37,6 @@ __global__ __launch_bounds__(BLOCK) void st_in_deg_kernel(const u64* __restrict_
     }
 }
 
-struct Collective {
-    katome_dist_builder* d; const char* name; int rank, world;
-    std::vector<uint64_t> all;
-    Collective(katome_dist_builder* d_, const char* name_) : d(d_), name(name_), rank(d_->rank()), world(d_->world()), all(d_->world(), 0) {}
-    // every rank's status since the last collective (0 or a KATOME_E_* code of its own, its message set) and a number below
-    // 2^48 of which all ranks get the largest.  One allgather; a failure anywhere comes back on every rank, naming the rank
-    int agree(int mine, uint64_t* largest = nullptr) {
-        const std::string why = mine ? get_error() : "";
-        const uint64_t word = ((uint64_t)(mine ? -mine : 0) << 48) | (largest ? *largest & ((1ull << 48) - 1) : 0);
-        KCHECK(d->comm->allgather(word, all.data()));
-        uint64_t mx = 0;
-        for (int p = 0; p < world; ++p) {
-            const int status = -(int)(all[p] >> 48);
-            if (status) {
-                if (p == rank) set_error("%s: rank %d of %d failed: %s", name, p, world, why.c_str());
-                else set_error("%s: rank %d of %d failed (status %d)", name, p, world, status);
-                return status;
-            }
-            mx = std::max<uint64_t>(mx, all[p] & ((1ull << 48) - 1));
-        }
-        if (largest) *largest = mx;
-        return KATOME_OK;
-    }
-};
-
 int check_stats_builder(katome_dist_builder* d, const char* name) {
     if (!d) { set_error("null argument"); return KATOME_E_ARG; }
     if (!d->finalized) { set_error("%s: call katome_dist_finalize first", name); return KATOME_E_ARG; }
@@ -74,7 +50,7 @@ int check_share(katome_dist_builder* d, const char* name) {
 
 int dist_graph_stats(katome_dist_builder* d, katome_stats* out, hipStream_t stream) {
     const char* name = "katome_dist_graph_stats";
-    Collective C(d, name);
+    Collective C(d->comm, name);
     const uint64_t E = d->n_edges, N = d->n_nodes, me = (uint64_t)C.rank;
     const int world = C.world;
     const long long fail_at = getenv("KATOME_DIST_STATS_FAIL") ? atoll(getenv("KATOME_DIST_STATS_FAIL")) : -1;
@@ -156,7 +132,7 @@ int dist_graph_stats(katome_dist_builder* d, katome_stats* out, hipStream_t stre
 
 int dist_weight_spectrum(katome_dist_builder* d, uint64_t* bins, uint32_t n_bins, hipStream_t stream) {
     const char* name = "katome_dist_weight_spectrum";
-    Collective C(d, name);
+    Collective C(d->comm, name);
     auto local = [&]() -> int {
         KCHECK(check_share(d, name));
         return dev_weight_spectrum(d->b->edge_weight.as<u32>(), d->n_edges, bins, n_bins, stream);

@@ -267,12 +267,7 @@ extern "C" int katome_contig_stats_of(const uint64_t* lengths, uint64_t n, uint6
     ContigStats st;
     const int which = contig_stats(lengths, n, original_genome_length, &st);
     out->n50 = st.n50; out->l50 = st.l50; out->n90 = st.n90; out->ng50 = st.ng50;
-    if (which) {
-        static const char* const names[] = {"", "n50 (sum of the lengths / 2)", "n90 (0.1 * sum of the lengths, truncated)", "ng50 (original_genome_length / 2)"};
-        set_error("called `Option::unwrap()` on a `None` value: the tipping point of %s is 0", names[which]);       // stats/contigs.rs:86-88
-        return KATOME_E_ARG;
-    }
-    return KATOME_OK;
+    return contig_stats_status(which);
 }
 
 // Contigs::save_to_file (asm/mod.rs:57-72): the text in FASTA layout is the file
@@ -281,9 +276,7 @@ extern "C" int katome_assembly_save(const katome_assembly* a, const char* path) 
     if (a->layout != KATOME_TEXT_FASTA) { set_error("assembly_save: the text is not in FASTA layout"); return KATOME_E_ARG; }
     FILE* f = fopen(path, "wb");
     if (!f) {
-        const int e = errno;                   // io::Error::description() of the kinds File::create meets
-        const char* why = e == ENOENT ? "entity not found" : (e == EACCES || e == EPERM) ? "permission denied" : e == EEXIST ? "entity already exists" : "other os error";
-        set_error("couldn't create %s: %s", path, why);      // asm/mod.rs:62
+        set_error("couldn't create %s: %s", path, CREATE_ERROR_KINDS[create_error_kind(errno)]);      // asm/mod.rs:62
         return KATOME_E_OPEN;
     }
     const size_t n = a->text_bytes ? fwrite(a->text, 1, a->text_bytes, f) : 0;
@@ -321,15 +314,64 @@ static int assembly_to_host(katome_builder* b, uint64_t read_bytes, const Assemb
     return rc;
 }
 
-// what a host entry hands back: the graph, the graph after shrink, or the assembly
+// katome_unitigs_* on one GPU: the flag's remove_dead_paths, the stage letters, the traversal-free shrink, its text in FASTA layout,
+// Contigs::stats of the merged edges and, with a path, the file -- copied down a chunk at a time, the text is never whole on the host
+struct UnitigsWant { katome_unitigs* out; const char* path; };
+static int save_device_text(const katome_dev_assembly& da, const char* path) {
+    FILE* f = fopen(path, "wb");
+    if (!f) { set_error("couldn't create %s: %s", path, CREATE_ERROR_KINDS[create_error_kind(errno)]); return KATOME_E_OPEN; }      // asm/mod.rs:62
+    const size_t chunk = std::min<uint64_t>(std::max<uint64_t>(da.text_bytes, 1), (uint64_t)64 << 20);
+    std::vector<uint8_t> buf;
+    int rc = KATOME_OK;
+    try { buf.resize(chunk); }
+    catch (const std::bad_alloc&) { set_error("out of host memory"); rc = KATOME_E_OOM; }
+    for (uint64_t at = 0; at < da.text_bytes && !rc; at += chunk) {
+        const size_t n = std::min<uint64_t>(chunk, da.text_bytes - at);
+        if (hipMemcpy(buf.data(), da.d_text + at, n, hipMemcpyDeviceToHost) != hipSuccess) { set_error("device -> host copy failed: %s", hipGetErrorString(hipGetLastError())); rc = KATOME_E_DEVICE; }
+        else if (fwrite(buf.data(), 1, n, f) != n) { set_error("couldn't write %s", path); rc = KATOME_E_OPEN; }
+    }
+    if (fclose(f) != 0 && !rc) { set_error("couldn't write %s", path); rc = KATOME_E_OPEN; }
+    if (rc) (void)remove(path);
+    return rc;
+}
+static int unitigs_to_host(katome_builder* b, uint64_t read_bytes, const UnitigsWant& want, const char* stages, uint64_t genome_len) {
+    katome_dev_graph dg;
+    KCHECK(katome_dev_finalize(b, &dg, nullptr));
+    if (b->s.flags & KATOME_FLAG_REMOVE_DEAD_PATHS) KCHECK(katome_dev_remove_dead_paths(b, &dg, nullptr, nullptr));
+    KCHECK(run_stages(stages, BuilderStages{b, genome_len}));
+    katome_dev_contigs dc;
+    KCHECK(katome_dev_shrink_mode(b, KATOME_SHRINK_FAST, &dc, nullptr, nullptr));
+    katome_dev_assembly da;
+    KCHECK(katome_dev_contigs_text(b, &dc, KATOME_TEXT_FASTA, &da, nullptr));
+    katome_unitigs* u = want.out;
+    u->n_contigs = da.n_contigs; u->text_bytes = da.text_bytes; u->read_bytes = read_bytes; u->k = b->s.k; u->n_devices = 1;
+    std::vector<uint32_t> kmers;
+    std::vector<uint64_t> lengths;
+    try { kmers.resize(dc.n_edges); lengths.resize(dc.n_edges); }
+    catch (const std::bad_alloc&) { set_error("out of host memory"); return KATOME_E_OOM; }
+    if (dc.n_edges) KCHECK_HIP(hipMemcpy(kmers.data(), dc.d_edge_kmers, dc.n_edges * 4, hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < dc.n_edges; ++i) {
+        lengths[i] = (uint64_t)kmers[i] + b->s.k - 1;
+        u->total_bases += lengths[i]; u->longest = std::max(u->longest, lengths[i]);
+    }
+    const int stats_rc = katome_contig_stats_of(lengths.data(), lengths.size(), genome_len, &u->stats);      // (a tipping point of 0: the file is written all the same)
+    const std::string stats_err = stats_rc ? get_error() : "";
+    if (want.path) KCHECK(save_device_text(da, want.path));
+    if (stats_rc) set_error("%s", stats_err.c_str());
+    return stats_rc;
+}
+
+// what a host entry hands back: the graph, the graph after shrink, the assembly, or the unitigs' numbers (and their file)
 struct Finish {
     katome_graph** graph; katome_contigs** contigs;
     AssembleWant assemble{nullptr, nullptr}; bool assembling = false;
+    UnitigsWant unitigs{nullptr, nullptr}; bool want_unitigs = false;
     const char* stages = nullptr; uint64_t genome_len = 0;
     uint32_t shrink_mode = KATOME_SHRINK_AUTO;
     katome_stats* stage_stats = nullptr;      // katome_build_*_staged_stats: the graph described before the first stage and after each
     int operator()(katome_builder* b, uint64_t read_bytes) const {
         if (assembling) return assembly_to_host(b, read_bytes, assemble, genome_len);
+        if (want_unitigs) return unitigs_to_host(b, read_bytes, unitigs, stages, genome_len);
         return contigs ? contigs_to_host(b, read_bytes, contigs, shrink_mode) : graph_to_host(b, read_bytes, graph, stages, genome_len, stage_stats);
     }
 };
@@ -513,6 +555,38 @@ static int copy_out_by_index(MultiBuild& mb, const katome_dist_graph& g, hipStre
     return KATOME_OK;
 }
 
+// FASTA headers ">katome_<i>\n" of contigs 0 .. n - 1 take this many bytes (9 + the digits of i)
+static uint64_t fasta_header_bytes(uint64_t n) {
+    uint64_t bytes = 0, lo = 0, digits = 1;
+    for (uint64_t hi = 10; lo < n; lo = hi, hi = hi > ~0ull / 10 ? ~0ull : hi * 10, ++digits) bytes += (std::min(hi, n) - lo) * (9 + digits);
+    return bytes;
+}
+
+// katome_unitigs_* on the shares, after the stages: the sharded shrink, its text, the stats of all ranks' contigs and the file, every
+// call collective; rank 0 fills the caller's struct.  Every rank takes the same way through it: the statuses are agreed inside the calls
+static int sharded_unitigs(MultiBuild& mb, int r, int n, katome_dist_builder* d, hipStream_t stream) {
+    const UnitigsWant& want = mb.finish.unitigs;
+    katome_dist_shrink_stats ss;
+    KCHECK(katome_dist_shrink(d, nullptr, &ss, stream));
+    katome_dist_assembly a;
+    KCHECK(katome_dist_contigs_text(d, KATOME_TEXT_FASTA, &a, stream));
+    katome_contig_stats cs;
+    const int stats_rc = katome_dist_contig_stats(d, mb.finish.genome_len, &cs, stream);
+    if (stats_rc && stats_rc != KATOME_E_ARG) return stats_rc;       // (KATOME_E_ARG: a tipping point of 0 -- the file is written all the same)
+    const std::string stats_err = stats_rc ? get_error() : "";
+    if (r == 0) {
+        katome_unitigs* u = want.out;
+        u->n_contigs = a.total_contigs; u->text_bytes = a.total_text_bytes; u->read_bytes = mb.read_bytes; u->k = mb.s->k; u->n_devices = (uint32_t)n;
+        // (the FASTA text is the headers, the bases and one newline per contig)
+        u->total_bases = a.total_text_bytes - a.total_contigs - fasta_header_bytes(a.total_contigs);
+        u->longest = a.total_contigs ? ss.longest_path + mb.s->k - 1 : 0;
+        u->stats = cs; u->shrink = ss;
+    }
+    if (want.path) KCHECK(katome_dist_contigs_save(d, &a, want.path));
+    if (stats_rc) set_error("%s", stats_err.c_str());
+    return stats_rc;
+}
+
 // one rank from its reads to its share of the result; the two meetings and the order of everything between them are what keeps
 // a failing rank from leaving the others waiting
 template <class AddReads>
@@ -526,6 +600,10 @@ static int rank_build(MultiBuild& mb, int r, int n, katome_dist_builder* d, cons
     if (route.gathers(g.total_edges, g.total_nodes)) return gathered_finish(mb, r, d, stream);
     if (route.sharded_dead_paths()) KCHECK(katome_dist_remove_dead_paths(d, &g, nullptr, stream));
     if (route.sharded_shrink) return shrunk_to_host(d, mb.shrunk[r], stream);
+    if (route.unitigs) {
+        if (route.sharded_stage_letters()) KCHECK(run_stages(mb.finish.stages, ShardedStages{d, &g, mb.s->min_weight, mb.finish.genome_len, stream}));
+        return sharded_unitigs(mb, r, n, d, stream);
+    }
     // (the whole graph's stats are the same on every rank: rank 0 writes the caller's array)
     auto describe = [&](size_t i) -> int {
         if (!mb.finish.stage_stats) return KATOME_OK;
@@ -564,12 +642,16 @@ template <class AddReads>
 static int build_multi(const katome_settings* s, const Finish& finish, uint64_t read_bytes, const AddReads& add_reads) {
     const int n = s->n_devices;
     const bool share = (s->flags & KATOME_FLAG_RANKS_SHARE_DEVICE) != 0;
-    const MultiRoute route = plan_multi_route(s->flags, finish.contigs != nullptr, finish.stages, finish.assembling);
+    const MultiRoute route = plan_multi_route(s->flags, finish.contigs != nullptr, finish.stages, finish.assembling, finish.want_unitigs);
     if (n > KATOME_MAX_RANKS) { set_error("n_devices = %d: at most %d", n, KATOME_MAX_RANKS); return KATOME_E_UNSUPPORTED; }
     KCHECK(use_device(s->device));
     int n_visible = 0;
     KCHECK_HIP(hipGetDeviceCount(&n_visible));
     if (!share && s->device + n > n_visible) { set_error("n_devices = %d from device %d, but %d GPU(s) are visible", n, s->device, n_visible); return KATOME_E_DEVICE; }
+    if (route.bad_arg && route.unitigs) {
+        set_error("unitigs: stage letters and KATOME_FLAG_REMOVE_DEAD_PATHS need KATOME_FLAG_FIRST_SEEN_ORDER");
+        return KATOME_E_ARG;
+    }
     if (route.bad_arg) {
         set_error("n_devices > 1: shrink and the stages after the build need KATOME_FLAG_FIRST_SEEN_ORDER (they run on the graph gathered in the reference's numbering; KATOME_DIST_SHRINK=sharded shrinks a packed-key build)");
         return KATOME_E_ARG;
@@ -753,6 +835,23 @@ int katome_assemble_packed(const katome_settings* s, const uint8_t* packed, uint
     f.assemble = AssembleWant{out, out_path}; f.assembling = true; f.genome_len = original_genome_length;
     return build_packed_impl(s, packed, n_reads, read_len, skip, f);
 }
+// (the same check on every route: the stages work on the links of a first-seen build)
+static int unitigs_finish(const katome_settings* s, const char* stages, uint64_t genome_len, const char* out_path, katome_unitigs* out, Finish& f) {
+    if (!out) { set_error("null argument"); return KATOME_E_ARG; }
+    memset(out, 0, sizeof *out);
+    if (s && !(s->flags & KATOME_FLAG_FIRST_SEEN_ORDER) && ((stages && *stages) || (s->flags & KATOME_FLAG_REMOVE_DEAD_PATHS))) {
+        set_error("unitigs: stage letters and KATOME_FLAG_REMOVE_DEAD_PATHS need KATOME_FLAG_FIRST_SEEN_ORDER");
+        return KATOME_E_ARG;
+    }
+    f.unitigs = UnitigsWant{out, out_path}; f.want_unitigs = true; f.stages = stages; f.genome_len = genome_len;
+    return KATOME_OK;
+}
+int katome_unitigs_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip,
+                          const char* stages, uint64_t original_genome_length, const char* out_path, katome_unitigs* out) {
+    Finish f{nullptr, nullptr};
+    KCHECK(unitigs_finish(s, stages, original_genome_length, out_path, out, f));
+    return build_packed_impl(s, packed, n_reads, read_len, skip, f);
+}
 int katome_shrink_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len,
                          const uint8_t* skip, katome_contigs** out) {
     if (!out) { set_error("null argument"); return KATOME_E_ARG; }
@@ -910,6 +1009,12 @@ int katome_assemble_files(const katome_settings* s, const char* const* paths, si
     if (out) *out = nullptr;
     Finish f{nullptr, nullptr};
     f.assemble = AssembleWant{out, out_path}; f.assembling = true; f.genome_len = original_genome_length;
+    return build_files_impl(s, paths, n_paths, f);
+}
+int katome_unitigs_files(const katome_settings* s, const char* const* paths, size_t n_paths, const char* stages, uint64_t original_genome_length,
+                         const char* out_path, katome_unitigs* out) {
+    Finish f{nullptr, nullptr};
+    KCHECK(unitigs_finish(s, stages, original_genome_length, out_path, out, f));
     return build_files_impl(s, paths, n_paths, f);
 }
 int katome_shrink_files(const katome_settings* s, const char* const* paths, size_t n_paths, katome_contigs** out) {

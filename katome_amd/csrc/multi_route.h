@@ -27,10 +27,11 @@ struct MultiRoute {
     bool direct = false;            // first-seen order and no gather, whatever the graph's size
     bool stages_sharded = false, stages_gathered = false;    // KATOME_DIST_STAGES = sharded / gather
     bool local_comm = false;        // the ranks exchange through host rendezvous and device copies, not RCCL
+    bool unitigs = false;           // katome_unitigs_*: everything on the shares, through the sharded shrink to its text; never a gather
 
     // after finalize, every rank with the same totals: gather the graph to the first GPU and finish it there?
     bool gathers(uint64_t total_edges, uint64_t total_nodes) const {
-        if (!first_seen || direct) return false;
+        if (unitigs || !first_seen || direct) return false;
         if (contigs || !stages) return true;
         const bool too_big = total_edges >= 0xFFFFFFFFull || total_nodes >= 0xFFFFFFFFull;
         return !(stages_sharded || (too_big && !stages_gathered));
@@ -43,8 +44,20 @@ struct MultiRoute {
 
 // assembling (katome_assemble_*): the stages "dcwced" and collapse run on the graph gathered to the first GPU, whatever the
 // environment says about shrink and the stages -- the exact shrink and the walk behind it are one GPU's
-static inline MultiRoute plan_multi_route(uint32_t flags, bool want_contigs, const char* stages, bool assembling = false) {
+// unitigs (katome_unitigs_*): remove_dead_paths, the stage letters, the traversal-free shrink, its text and its stats all run on the
+// shares, whatever the environment says; the sharded stages need the links of a first-seen build, a packed-key build without
+// stages does not
+static inline MultiRoute plan_multi_route(uint32_t flags, bool want_contigs, const char* stages, bool assembling = false, bool unitigs = false) {
     MultiRoute p;
+    if (unitigs) {
+        p.unitigs = true;
+        p.first_seen = (flags & KATOME_FLAG_FIRST_SEEN_ORDER) != 0;
+        p.remove_dead_paths = (flags & KATOME_FLAG_REMOVE_DEAD_PATHS) != 0;
+        p.stages = stages && *stages;
+        p.bad_arg = !p.first_seen && (p.stages || p.remove_dead_paths);
+        p.local_comm = (flags & KATOME_FLAG_RANKS_SHARE_DEVICE) != 0 || env_is("KATOME_COMM", "local");
+        return p;
+    }
     if (assembling) {
         p.first_seen = (flags & KATOME_FLAG_FIRST_SEEN_ORDER) != 0;
         p.remove_dead_paths = (flags & KATOME_FLAG_REMOVE_DEAD_PATHS) != 0;

@@ -564,8 +564,9 @@ def labels(edge_keys, k, device=0):
     return out[:n * stride].view(n, stride)
 
 
-def pieces_text(labels, label_off, pieces, k, layout="plain", device=0):
-    """the text kernel on the caller's arrays (katome_dev_pieces_text): labels uint8 (compress_edge format, label i at
+def pieces_text(labels, label_off, pieces, k, layout="plain", device=0, first_contig=0):
+    """the text kernel on the caller's arrays (katome_dev_pieces_text_numbered; first_contig: contig c's FASTA header reads
+    ">katome_<first_contig + c>"): labels uint8 (compress_edge format, label i at
     labels[label_off[i]:label_off[i + 1]], label_off int64 with one more entry than labels), pieces int32/uint32 (label index,
     bit 31 on a piece that begins a contig; None: one whole piece per label) -> (contig_off int64, contig_len int32, text uint8
     of text_bytes rounded up to 16, text_bytes)"""
@@ -574,14 +575,14 @@ def pieces_text(labels, label_off, pieces, k, layout="plain", device=0):
     n_pieces = pieces.numel() if pieces is not None else n_labels
     nc, nb = C.c_uint64(), C.c_uint64()
     L = _lib.lib()
-    _check(L.katome_dev_pieces_text(device, k, _ptr(labels), _ptr(label_off), n_labels, _ptr(pieces), n_pieces, LAYOUTS[layout], None, None, 0,
-                                    None, 0, C.byref(nc), C.byref(nb), _stream()))
+    _check(L.katome_dev_pieces_text_numbered(device, k, _ptr(labels), _ptr(label_off), n_labels, _ptr(pieces), n_pieces, LAYOUTS[layout],
+                                             first_contig, None, None, 0, None, 0, C.byref(nc), C.byref(nb), _stream()))
     cap = (nb.value + 15) // 16 * 16
     off = torch.empty(max(nc.value, 1), dtype=torch.int64, device=tdev)
     length = torch.empty(max(nc.value, 1), dtype=torch.int32, device=tdev)
     text = torch.empty(max(cap, 16), dtype=torch.uint8, device=tdev)
-    _check(L.katome_dev_pieces_text(device, k, _ptr(labels), _ptr(label_off), n_labels, _ptr(pieces), n_pieces, LAYOUTS[layout], _ptr(off),
-                                    _ptr(length), nc.value, _ptr(text), cap, C.byref(nc), C.byref(nb), _stream()))
+    _check(L.katome_dev_pieces_text_numbered(device, k, _ptr(labels), _ptr(label_off), n_labels, _ptr(pieces), n_pieces, LAYOUTS[layout],
+                                             first_contig, _ptr(off), _ptr(length), nc.value, _ptr(text), cap, C.byref(nc), C.byref(nb), _stream()))
     return off[:nc.value], length[:nc.value], text, nb.value
 
 

@@ -12,8 +12,8 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from .build import KatomePanic, collection_stats, make_settings
-from .device import Builder, DeviceContigs, _ViewOwner, _ptr, _stream, _view
+from .build import ContigsStats, KatomePanic, collection_stats, make_settings
+from .device import LAYOUTS, Builder, DeviceContigs, _ViewOwner, _ptr, _stream, _view
 
 
 def _check(status):
@@ -197,6 +197,32 @@ class RankContigs:
     sequences = DeviceContigs.sequences
 
 
+class RankAssembly:
+    """this rank's part of the text of the sharded shrink (ShardedBuilder.contigs_text; zero-copy views of the builder's device
+    arrays, valid until the next contigs_text or close).  The order is rank-major: contig first_contig + j is this rank's merged
+    edge j, text[contig_off[j]:contig_off[j] + contig_len[j]]; the ranks' text[:text_bytes] one after the other, in rank order, are
+    the whole text (this rank's part starts at byte text_base of total_text_bytes)."""
+
+    def __init__(self, a, owner, device):
+        self._a = a
+        self.n_contigs, self.first_contig, self.total_contigs = a.n_contigs, a.first_contig, a.total_contigs
+        self.text_bytes, self.text_base, self.total_text_bytes = a.text_bytes, a.text_base, a.total_text_bytes
+        self.layout = {v: k for k, v in LAYOUTS.items()}[a.layout]
+        self.contig_off = _view(a.d_contig_off, (a.n_contigs,), "<i8", owner, device)
+        self.contig_len = _view(a.d_contig_len, (a.n_contigs,), "<i4", owner, device)
+        self.text = _view(a.d_text, (a.text_bytes,), "|u1", owner, device)
+
+
+def contig_stats_arrays(comm, kmers, k, genome_len, device=0):
+    """Contigs::stats of ALL ranks' contigs from each rank's own k-mer counts (int32 / uint32 device tensor, may be empty; a
+    contig's length is its count + k - 1), no rank holding another's (katome_dist_contig_stats_arrays) -> ContigsStats, the same
+    on every rank; a tipping point of 0 raises KatomePanic(E_ARG) on every rank.  Collective."""
+    st = _lib.ContigStats()
+    n = int(kmers.numel())
+    _check(_lib.lib().katome_dist_contig_stats_arrays(comm._h, device, _ptr(kmers) if n else None, n, k, int(genome_len), C.byref(st), _stream()))
+    return ContigsStats(st.n50, st.l50, st.n90, st.ng50)
+
+
 class _InnerBuilder(Builder):
     """the single-GPU builder underneath a ShardedBuilder (owned by it): profile counters, and -- on the root after
     gather() -- the stages of device.Builder"""
@@ -316,6 +342,24 @@ class ShardedBuilder(_ViewOwner):
         c, st = _lib.DistContigs(), _lib.DistShrinkStats()
         _check(_lib.lib().katome_dist_shrink(self._h, C.byref(c), C.byref(st), _stream()))
         return RankContigs(c, st, self, self.tdev)
+
+    def contigs_text(self, layout="fasta"):
+        """the text of the last shrink()'s merged edges on this rank, numbered after the ranks before it
+        (katome_dist_contigs_text) -> RankAssembly"""
+        a = _lib.DistAssembly()
+        _check(_lib.lib().katome_dist_contigs_text(self._h, LAYOUTS[layout], C.byref(a), _stream()))
+        return RankAssembly(a, self, self.tdev)
+
+    def contig_stats(self, genome_len):
+        """Contigs::stats of all ranks' merged edges after the last shrink(), the same on every rank (katome_dist_contig_stats)"""
+        st = _lib.ContigStats()
+        _check(_lib.lib().katome_dist_contig_stats(self._h, int(genome_len), C.byref(st), _stream()))
+        return ContigsStats(st.n50, st.l50, st.n90, st.ng50)
+
+    def save_contigs(self, assembly, path):
+        """the file of the last contigs_text(), every rank writing its part at its offset (katome_dist_contigs_save)"""
+        import os
+        _check(_lib.lib().katome_dist_contigs_save(self._h, C.byref(assembly._a), os.fsencode(path)))
 
     def stats(self):
         """CollectionStats of the WHOLE graph as it stands, the same on every rank, no gather (katome_dist_graph_stats).
