@@ -300,6 +300,9 @@ uint32_t katome_tile_plan(uint32_t k, uint32_t read_len, uint32_t *span, uint32_
  * two-word records, asks for 2)                                                                          */
 uint32_t katome_tile_plan_limited(uint32_t k, uint32_t read_len, uint32_t max_tile_words, uint32_t *span,
                                   uint32_t *tiles, uint32_t *remainder);
+/* the same plan for reads of several lengths (host array `len`, none shorter than k): the one span katome_build_files uses
+ * for the whole input -- tiles from the front of every read + the windows left over; 1: tiling does not pay             */
+uint32_t katome_tile_span_for_lengths(uint32_t k, const uint32_t *len, uint64_t n_reads);
 int katome_dev_extract_remainder(katome_builder *b, const uint8_t *d_packed, uint64_t n_reads, uint32_t read_len,
                                  uint32_t span, const uint8_t *d_skip, uint64_t *d_records, void *stream);
 int katome_dev_extract_tiles(katome_builder *b, const uint8_t *d_packed, uint64_t n_reads, uint32_t read_len,

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "builder.h"
+#include "seen_tag.h"
 
 extern "C" {
 
@@ -131,6 +132,15 @@ uint32_t tile_span_for_lengths(uint32_t k, const uint32_t* len, uint64_t n_reads
 }
 
 extern "C" {
+
+uint32_t katome_tile_span_for_lengths(uint32_t k, const uint32_t* len, uint64_t n_reads) {
+    uint64_t total = 0;
+    for (uint64_t r = 0; r < n_reads; ++r) {
+        if (len[r] < k) return 1;                         // (a read with no window: the builds refuse it; no plan)
+        total += len[r] - k + 1;
+    }
+    return tile_span_for_lengths(k, len, n_reads, total);
+}
 
 int katome_dev_extract_tiles(katome_builder* b, const uint8_t* d_packed, uint64_t n_reads, uint32_t read_len, uint32_t span,
                              const uint8_t* d_skip, uint64_t* d_records, void* stream) {
@@ -423,6 +433,14 @@ static int insert_plain(katome_builder* b, const uint64_t* d_records, const uint
     return KATOME_OK;
 }
 
+// First-seen order, reads of varying length: the levels counted by sorting, the batches' records kept aside with delta tags
+// (seen_tag.h).  KATOME_SEEN_VAR_SORTED=1 switches it on; off, such a build counts every level in the tables
+static bool seen_var_sorted() { static const bool on = env_flag("KATOME_SEEN_VAR_SORTED", false); return on; }
+// how the builder's tagged records spell their two numbers
+static SeenTag builder_tag(const katome_builder* b) {
+    return b->seen_delta ? SeenTag::by_delta() : SeenTag::fixed(2ull * (b->seen_read_len - b->s.k + 1));
+}
+
 // how many valid records wait in b->rest_k (the device cursor; b->rest_n counts what was handed over, skipped reads included)
 static int rest_valid(katome_builder* b, uint64_t* n, hipStream_t stream) {
     *n = 0;
@@ -439,7 +457,7 @@ int flush_rest(katome_builder* b, hipStream_t stream) {
     if (n_valid && b->first_seen) {            // tagged records: back into keys + their two sequence numbers for the table
         DevBuf keys(stream), pairs(stream);
         KCHECK(keys.alloc(n_valid * 8 * b->nw + 16)); KCHECK(pairs.alloc(n_valid * 16 + 16));
-        KCHECK(table_tagged_to_pairs(b->rest_k.as<u64>(), n_valid, b->nw, 2ull * (b->seen_read_len - b->s.k + 1), keys.as<u64>(), pairs.as<u64>(), stream));
+        KCHECK(table_tagged_to_pairs(b->rest_k.as<u64>(), n_valid, b->nw, builder_tag(b), keys.as<u64>(), pairs.as<u64>(), stream));
         SeenOrigin origin;
         origin.pairs = pairs.as<u64>(); origin.rc = b->rc;
         KCHECK(builder_insert(b, b->table, b->table_ready, b->nw, b->s.table_slots_hint, keys.as<u64>(), nullptr, n_valid, &origin, PH_INSERT, stream));
@@ -499,7 +517,7 @@ int flush_tile_recs(katome_builder* b, hipStream_t stream) {
         if (b->first_seen && n) {            // tagged records: back into keys + their two sequence numbers for the table
             DevBuf keys(stream), pairs(stream);
             KCHECK(keys.alloc(n * 8 * nwt + 16)); KCHECK(pairs.alloc(n * 16 + 16));
-            KCHECK(table_tagged_to_pairs(b->tile_recs.as<u64>(), n, nwt, 2ull * (b->seen_read_len - b->s.k + 1), keys.as<u64>(), pairs.as<u64>(), stream));
+            KCHECK(table_tagged_to_pairs(b->tile_recs.as<u64>(), n, nwt, builder_tag(b), keys.as<u64>(), pairs.as<u64>(), stream));
             b->tile_recs.release();
             SeenOrigin origin;
             origin.pairs = pairs.as<u64>(); origin.rc = b->rc;
@@ -553,6 +571,19 @@ static int reserve_tile_recs(katome_builder* b, uint64_t n, uint32_t nwt, bool* 
     return KATOME_OK;
 }
 
+// the device cursor of the tile records, ready for a kernel that appends behind it
+static int tile_recs_cursor(katome_builder* b, hipStream_t stream) {
+    if (!b->tile_recs_count.p) KCHECK(b->tile_recs_count.alloc(8, stream));
+    if (b->tile_recs_exact) {
+        // from here on only the device knows how many of the records handed over were valid: its cursor starts at what the host knew
+        const uint64_t start = b->tile_recs_n;
+        KCHECK_HIP(hipMemcpyAsync(b->tile_recs_count.p, &start, 8, hipMemcpyHostToDevice, stream));
+        KCHECK_HIP(hipStreamSynchronize(stream));
+        b->tile_recs_exact = false;
+    }
+    return KATOME_OK;
+}
+
 // a batch's tiles kept aside as records; *kept = false: they go into the tile table
 int keep_tile_recs(katome_builder* b, const uint64_t* d_records, uint64_t n, uint32_t nwt, bool* kept, hipStream_t stream) {
     *kept = false;
@@ -562,14 +593,7 @@ int keep_tile_recs(katome_builder* b, const uint64_t* d_records, uint64_t n, uin
     const uint32_t words = nwt + (b->first_seen ? 1 : 0);
     KCHECK(reserve_tile_recs(b, n, words, &ok, stream));
     if (!ok) return KATOME_OK;
-    if (!b->tile_recs_count.p) KCHECK(b->tile_recs_count.alloc(8, stream));
-    if (b->tile_recs_exact) {
-        // from here on only the device knows how many of the records handed over were valid: its cursor starts at what the host knew
-        const uint64_t start = b->tile_recs_n;
-        KCHECK_HIP(hipMemcpyAsync(b->tile_recs_count.p, &start, 8, hipMemcpyHostToDevice, stream));
-        KCHECK_HIP(hipStreamSynchronize(stream));
-        b->tile_recs_exact = false;
-    }
+    KCHECK(tile_recs_cursor(b, stream));
     if (b->first_seen) {
         const uint32_t W = b->seen_read_len - b->s.k + 1;
         KCHECK(table_keep_rest(d_records, n, nwt, true, b->reads_inserted, W / b->span, 0, 2 * W, b->tile_recs.as<u64>(), b->tile_recs_count.as<u64>(), stream,
@@ -788,9 +812,10 @@ static bool half_sort_route(const katome_builder* b) {
     return on && b->nw == 1 && !b->first_seen && k >= 9 && ((k & 1) || !b->rc);
 }
 
-// keeps a batch's left-over windows aside (see builder.h); *kept = false: they have to go into the table
-static int keep_rest(katome_builder* b, const uint64_t* d_records, uint64_t n, bool* kept, hipStream_t stream) {
-    *kept = false;
+// room for n more left-over windows behind those kept aside, and their cursor; *ok = false: too many -- what was kept has gone into
+// the table and these follow it there
+static int reserve_rest(katome_builder* b, uint64_t n, bool* ok, hipStream_t stream) {
+    *ok = false;
     const uint32_t words = b->nw + (b->first_seen ? 1 : 0);          // (first-seen order: tagged records)
     if (b->rest_n + n > b->rest_cap) {
         size_t free_b = 0, total_b = 0;
@@ -807,9 +832,75 @@ static int keep_rest(katome_builder* b, const uint64_t* d_records, uint64_t n, b
         b->rest_cap = want;
     }
     if (!b->rest_count.p) { KCHECK(b->rest_count.alloc(8, stream)); KCHECK_HIP(hipMemsetAsync(b->rest_count.p, 0, 8, stream)); }
+    *ok = true;
+    return KATOME_OK;
+}
+
+// keeps a batch's left-over windows aside (see builder.h); *kept = false: they have to go into the table
+static int keep_rest(katome_builder* b, const uint64_t* d_records, uint64_t n, bool* kept, hipStream_t stream) {
+    *kept = false;
+    bool ok = false;
+    KCHECK(reserve_rest(b, n, &ok, stream));
+    if (!ok) return KATOME_OK;
     KCHECK(table_keep_rest(d_records, n, b->nw, b->first_seen, b->last_batch_read0, b->rem_per_read, b->rem_win0,
                            b->first_seen ? 2u * (b->seen_read_len - b->s.k + 1) : 0u, b->rest_k.as<u64>(), b->rest_count.as<u64>(), stream));
     b->rest_n += n;
+    *kept = true;
+    return KATOME_OK;
+}
+
+// ---- first-seen order, reads of varying length: a batch's records kept aside with delta tags (KATOME_SEEN_VAR_SORTED) ----------
+// Does every read of the batch just extracted pack (seen_tag.h)?  No read of more than DELTA_MAX_WINDOWS windows -- |Q - P| < 2 W for
+// every record cut from a read of W windows, and for the minima of a key --, and numbers below DELTA_P_LIMIT.
+// Asked once per batch, not per insert (a batch's tiles and its left-over windows share one prefix): the answer is kept under the
+// prefix's address AND the batch's sequence base.  The address alone would not do -- a caller may hand the next batch's prefix in at
+// the same address --, the base tells batches apart because every batch holds a read, a read a window, and the base moves on by twice
+// the batch's windows when the batch is closed.
+static int var_batch_packs(katome_builder* b, bool* ok, hipStream_t stream) {
+    if (b->var_checked != b->var_prefix || b->var_checked_base != b->var_seq_base) {
+        uint64_t max_w = 0;
+        KCHECK(table_max_windows(b->var_prefix, b->var_reads, &max_w, stream));
+        b->var_checked = b->var_prefix; b->var_checked_base = b->var_seq_base;
+        b->var_checked_ok = max_w <= DELTA_MAX_WINDOWS && b->var_seq_base + 2 * b->var_windows < DELTA_P_LIMIT;
+    }
+    *ok = b->var_checked_ok;
+    return KATOME_OK;
+}
+// a batch that does not pack closes the route: what was kept goes into the tables with its pairs, and the build goes on there
+static int close_seen_var(katome_builder* b, hipStream_t stream) {
+    if (!b->tile_recs_closed) KCHECK(flush_tile_recs(b, stream));
+    if (!b->rest_closed) KCHECK(flush_rest(b, stream));
+    return KATOME_OK;
+}
+// the tiles of the last katome_dev_extract_var_tiles call behind the tile records kept so far; *kept = false: into the tile table
+static int keep_var_tiles(katome_builder* b, const uint64_t* d_records, uint64_t n, uint32_t nwt, bool* kept, hipStream_t stream) {
+    *kept = false;
+    bool ok = false;
+    KCHECK(var_batch_packs(b, &ok, stream));
+    if (!ok) return close_seen_var(b, stream);
+    b->tile_recs_hist_ok = false;
+    KCHECK(reserve_tile_recs(b, n, nwt + 1, &ok, stream));
+    if (!ok) return KATOME_OK;
+    KCHECK(tile_recs_cursor(b, stream));
+    KCHECK(table_keep_var_tagged(d_records, n, nwt, b->rc, b->var_prefix, b->var_rec_prefix, b->var_reads, 1, b->var_span, b->var_seq_base,
+                                 b->tile_recs.as<u64>(), b->tile_recs_count.as<u64>(), stream));
+    b->tile_recs_n += n;
+    b->seen_delta = true;
+    *kept = true;
+    return KATOME_OK;
+}
+// ... and its windows (all of them, or those after the last whole tile) behind the left-over windows; *kept = false: into the k-mer table
+static int keep_var_rest(katome_builder* b, const uint64_t* d_records, uint64_t n, bool* kept, hipStream_t stream) {
+    *kept = false;
+    bool ok = false;
+    KCHECK(var_batch_packs(b, &ok, stream));
+    if (!ok) return close_seen_var(b, stream);
+    KCHECK(reserve_rest(b, n, &ok, stream));
+    if (!ok) return KATOME_OK;
+    KCHECK(table_keep_var_tagged(d_records, n, b->nw, b->rc, b->var_prefix, b->var_rec_prefix, b->var_reads, b->var_mode, b->var_span, b->var_seq_base,
+                                 b->rest_k.as<u64>(), b->rest_count.as<u64>(), stream));
+    b->rest_n += n;
+    b->seen_delta = true;
     *kept = true;
     return KATOME_OK;
 }
@@ -840,6 +931,18 @@ int katome_dev_insert_weighted(katome_builder* b, const uint64_t* d_records, con
         bool kept = false;
         KCHECK(keep_rest(b, d_records, n_records, &kept, stream));
         if (kept) { b->rem_pending = false; return KATOME_OK; }
+    }
+    // ... reads of varying length: the batch's windows -- all of them, or those after its tiles -- wait as delta-tagged records (seen_tag.h)
+    if (b->first_seen && b->var_prefix && seen_var_sorted() && !d_weights && b->var_mode != 1 && n_records == b->var_records && !b->table_ready &&
+        !b->rest_closed && !b->direct_edges && b->nw <= 2 && sorted_count_mode()) {
+        bool kept = false;
+        KCHECK(keep_var_rest(b, d_records, n_records, &kept, stream));
+        if (kept) {
+            b->var_seq_base += 2 * b->var_windows;          // the batch is complete, as below
+            b->var_prefix = b->var_rec_prefix = nullptr; b->var_reads = b->var_windows = 0;
+            b->rem_pending = false;
+            return KATOME_OK;
+        }
     }
     uint64_t room = 0;
     KCHECK(ensure_table(b, n_records, &room, stream));
@@ -897,8 +1000,13 @@ int katome_dev_insert(katome_builder* b, const uint64_t* d_records, uint64_t n_r
 
 // may this builder keep a batch's tile records aside and count them by sorting at the end?
 static bool keeps_tile_recs(const katome_builder* b, uint32_t nwt) {
+    // (the reference's numbering, reads of varying length: the tiles of the last katome_dev_extract_var_tiles call, tagged with their
+    // numbers themselves -- keep_var_tiles, which asks whether they pack.  One-word tiles too: short reads make short tiles)
+    if (b->first_seen && (b->var_prefix || b->var_seq_base))
+        return b->var_prefix && b->var_mode == 1 && seen_var_sorted() && !b->direct_edges && nwt <= 2 && b->nw == 1 && !b->tiles_ready && !b->table_ready &&
+               !b->tile_recs_closed && sorted_count_mode() && sorted_tiles_mode() == 2;
     // (the reference's numbering: reads of one length whose numbers pack into a record word -- lds_count_seen_kernel's rule)
-    const bool seen_ok = !b->first_seen || (!b->var_prefix && !b->var_seq_base && !b->direct_edges && b->seen_read_len >= b->s.k &&
+    const bool seen_ok = !b->first_seen || (!b->direct_edges && b->seen_read_len >= b->s.k &&
                                             2ull * (b->seen_read_len - b->s.k + 1) <= 0xFFFFull && (b->reads_inserted >> 31) == 0);
     return seen_ok && tile_recs_shape(nwt, b->nw, b->first_seen) && !b->tiles_ready && !b->table_ready && !b->tile_recs_closed && sorted_count_mode() &&
            sorted_tiles_mode() == 2;
@@ -982,7 +1090,13 @@ int katome_dev_insert_tiles(katome_builder* b, const uint64_t* d_records, uint64
     if (n_records == 0) return KATOME_OK;
     b->span = span;
     const uint32_t nwt = (uint32_t)key_words_for_k(b->s.k + span - 1);
-    if (keeps_tile_recs(b, nwt)) {
+    const bool var_tiles = b->first_seen && b->var_prefix != nullptr;
+    if (var_tiles && b->var_span == span && n_records == b->var_records && keeps_tile_recs(b, nwt)) {
+        bool kept = false;
+        PhaseScope ps(b->prof, PH_INSERT_TILES, stream);
+        KCHECK(keep_var_tiles(b, d_records, n_records, nwt, &kept, stream));
+        if (kept) return KATOME_OK;          // (the insert of the batch's left-over windows closes it, as on the table route)
+    } else if (!var_tiles && keeps_tile_recs(b, nwt)) {
         const uint32_t per_read = b->first_seen ? (b->seen_read_len - b->s.k + 1) / span : 1;
         if (b->first_seen && (per_read == 0 || n_records % per_read)) { set_error("first-seen order: a batch must hold whole reads"); return KATOME_E_ARG; }
         bool kept = false;
@@ -997,7 +1111,6 @@ int katome_dev_insert_tiles(katome_builder* b, const uint64_t* d_records, uint64
         }
     }
     SeenOrigin origin;
-    const bool var_tiles = b->first_seen && b->var_prefix != nullptr;
     if (var_tiles) {
         if (b->var_mode != 1 || b->var_span != span || n_records != b->var_records) { set_error("first-seen order: insert exactly the tiles katome_dev_extract_var_tiles produced"); return KATOME_E_ARG; }
         origin.win_prefix = b->var_prefix; origin.n_reads = b->var_reads; origin.seq_base = b->var_seq_base; origin.rc = b->rc;
@@ -1212,7 +1325,7 @@ static int edges_from_tile_table(katome_builder* b, bool* counted, hipStream_t s
 // on fallback: the tile records, or the distinct big tiles with their counts and numbers, are in the tile table; n_edges == 0
 static int seen_edges_from_tile_recs(katome_builder* b, DevBuf& raw_seq, bool* counted, hipStream_t stream) {
     const uint32_t k = b->s.k, span = b->span, tile_bases = k + span - 1;
-    const uint64_t spr = 2ull * (b->seen_read_len - k + 1);
+    const SeenTag tag = builder_tag(b);          // (reads of varying length: the delta tag)
     b->span2 = mid_span(span);
     uint64_t n = 0, n1 = 0, d1 = 0, distinct = 0;
     KCHECK(tile_recs_valid(b, &n, stream));
@@ -1222,7 +1335,7 @@ static int seen_edges_from_tile_recs(katome_builder* b, DevBuf& raw_seq, bool* c
         PhaseScope ps(b->prof, PH_INSERT_TILES, stream);
         TileLevelScope tl;
         DevBuf ones(stream);               // (stays empty: the records count once each)
-        rc = tagged_records_sorted(b->tile_recs, ones, n, tile_bases, b->rc, spr, true, l1, c1, &n1, &d1, stream);
+        rc = tagged_records_sorted(b->tile_recs, ones, n, tile_bases, b->rc, tag, true, l1, c1, &n1, &d1, stream);
         if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
     }
     if (rc == KATOME_E_UNSUPPORTED) return flush_tile_recs(b, stream);      // (the records are all still there, in another order: into the table with them)
@@ -1238,9 +1351,9 @@ static int seen_edges_from_tile_recs(katome_builder* b, DevBuf& raw_seq, bool* c
         DevBuf mk(stream), mw(stream);
         uint64_t n_mid = 0, n2 = 0, d2 = 0;
         DevBuf mid_counts(stream);         // (the first partition pass's digit counts per tile, made while the records are written)
-        KCHECK(table_list_to_tagged_records(lk, lw, n1, tile_bases, kk2, n_sub, b->span2, b->rc, mk, mw, &n_mid, stream, 0, &mid_counts));
+        KCHECK(table_list_to_tagged_records(lk, lw, n1, tile_bases, kk2, n_sub, b->span2, b->rc, mk, mw, &n_mid, stream, 0, &mid_counts, tag.delta));
         rc = sorted_fail("mid") ? KATOME_E_UNSUPPORTED
-            : tagged_records_sorted(mk, mw, n_mid, kk2, b->rc, spr, true, l2, c2, &n2, &d2, stream, mid_counts.as<u32>());
+            : tagged_records_sorted(mk, mw, n_mid, kk2, b->rc, tag, true, l2, c2, &n2, &d2, stream, mid_counts.as<u32>());
         if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
         if (rc == KATOME_OK) { b->stat_tiles2 = n2; lk = l2.as<u64>(); lw = c2.as<u32>(); n_last = n2; last_bases = kk2; last_span = b->span2; }
     }
@@ -1250,11 +1363,11 @@ static int seen_edges_from_tile_recs(katome_builder* b, DevBuf& raw_seq, bool* c
         uint64_t n_rec = 0, n_rest = 0;
         KCHECK(rest_valid(b, &n_rest, stream));
         DevBuf last_counts(stream);
-        KCHECK(table_list_to_tagged_records(lk, lw, n_last, last_bases, k, last_span, 1, b->rc, kr, kw, &n_rec, stream, n_rest, &last_counts));
+        KCHECK(table_list_to_tagged_records(lk, lw, n_last, last_bases, k, last_span, 1, b->rc, kr, kw, &n_rec, stream, n_rest, &last_counts, tag.delta));
         l2.release(); c2.release();
         KCHECK(append_rest(b, kr, kw, &n_rec, n_rest, b->nw + 1, false, stream));
         rc = sorted_fail("last") ? KATOME_E_UNSUPPORTED
-            : tagged_records_sorted(kr, kw, n_rec, k, b->rc, spr, false, b->edge_key, raw_seq, &b->n_edges, &distinct, stream, last_counts.as<u32>());
+            : tagged_records_sorted(kr, kw, n_rec, k, b->rc, tag, false, b->edge_key, raw_seq, &b->n_edges, &distinct, stream, last_counts.as<u32>());
         if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
     }
     if (rc == KATOME_OK) {
@@ -1271,7 +1384,7 @@ static int seen_edges_from_tile_recs(katome_builder* b, DevBuf& raw_seq, bool* c
     const uint32_t nwt = (uint32_t)key_words_for_k(tile_bases);
     DevBuf keys(stream), pairs(stream);
     KCHECK(keys.alloc(n1 * 8 * nwt + 16)); KCHECK(pairs.alloc(n1 * 16 + 16));
-    KCHECK(table_tagged_to_pairs(l1.as<u64>(), n1, nwt, spr, keys.as<u64>(), pairs.as<u64>(), stream));
+    KCHECK(table_tagged_to_pairs(l1.as<u64>(), n1, nwt, tag, keys.as<u64>(), pairs.as<u64>(), stream));
     l1.release();
     SeenOrigin origin;
     origin.pairs = pairs.as<u64>(); origin.rc = b->rc;
@@ -1279,12 +1392,14 @@ static int seen_edges_from_tile_recs(katome_builder* b, DevBuf& raw_seq, bool* c
 }
 
 // The k-mers of a first-seen-order build counted by sorting out of the tile table (lds_count.hip, lds_count_seen_kernel): reads of one
-// length whose windows are whole tiles, so that a record's two sequence numbers pack into one word.
+// length whose windows are whole tiles, so that a record's two sequence numbers pack into one word -- or, KATOME_SEEN_VAR_SORTED, reads
+// of varying length, whose tiles' pairs pack as they are (the delta tag); the left-over windows join as tagged records.
 // on fallback: the tiles are in their table (mid tiles in b->tiles2 if it made them); n_edges == 0
 static int seen_edges_from_tile_table(katome_builder* b, DevBuf& raw_seq, bool* counted, hipStream_t stream) {
-    if (!sorted_count_mode() || !b->tiles_ready || b->table_ready || b->nw > 2 || b->var_seq_base || b->var_prefix || b->direct_edges ||
-        b->seen_read_len < b->s.k)
+    const bool var = b->var_seq_base || b->var_prefix;
+    if (!sorted_count_mode() || !b->tiles_ready || b->table_ready || b->nw > 2 || b->direct_edges || (var ? !seen_var_sorted() : b->seen_read_len < b->s.k))
         return KATOME_OK;
+    const SeenTag tag = var ? SeenTag::by_delta() : builder_tag(b);
     uint64_t n_tiles = 0;
     KCHECK(table_occupied(b->tiles, &n_tiles, stream));
     if (!sorting_pays(n_tiles * b->span)) return KATOME_OK;     // (the last level's own size is checked where its records are made)
@@ -1296,13 +1411,34 @@ static int seen_edges_from_tile_table(katome_builder* b, DevBuf& raw_seq, bool* 
         PhaseScope ps(b->prof, PH_EXPAND_TILES, stream);
         uint64_t n_rest = 0;
         KCHECK(rest_valid(b, &n_rest, stream));
-        rc = tiles_to_edges_sorted_seen(*last, b->s.k, last_span, b->rc, 2ull * (b->seen_read_len - b->s.k + 1), b->edge_key, raw_seq, &b->n_edges,
-                                        &distinct, stream, n_rest ? b->rest_k.as<u64>() : nullptr, n_rest);
+        rc = sorted_fail("last") && var ? KATOME_E_UNSUPPORTED
+            : tiles_to_edges_sorted_seen(*last, b->s.k, last_span, b->rc, tag, b->edge_key, raw_seq, &b->n_edges,
+                                         &distinct, stream, n_rest ? b->rest_k.as<u64>() : nullptr, n_rest);
         if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
     }
     // (numbers that do not pack, or a group too large: the table counts, from the tiles that are still there)
     if (rc != KATOME_OK) { b->n_edges = 0; return KATOME_OK; }
     release_tile_tables(b);
+    rest_reset(b);
+    b->stat_kmers = distinct; b->stat_kmer_slots = 0;
+    *counted = true;
+    return KATOME_OK;
+}
+
+// ... and of one that kept windows only (KATOME_SEEN_VAR_SORTED: reads of varying length cut window by window, or none of them as long
+// as a tile): the tagged records kept aside are the level's records.
+// on fallback: they are still kept aside, in another order (the table route flushes them); n_edges == 0
+static int seen_edges_from_rest(katome_builder* b, DevBuf& raw_seq, bool* counted, hipStream_t stream) {
+    if (!b->seen_delta || !sorted_count_mode() || b->tiles_ready || b->table_ready || b->tile_recs_n || !b->rest_n || b->nw > 2) return KATOME_OK;
+    uint64_t n_rest = 0, distinct = 0;
+    KCHECK(rest_valid(b, &n_rest, stream));
+    if (!sorting_pays(n_rest)) return KATOME_OK;
+    PhaseScope ps(b->prof, PH_EXPAND_TILES, stream);
+    DevBuf ones(stream);               // (stays empty: the records count once each)
+    const int rc = sorted_fail("last") ? KATOME_E_UNSUPPORTED
+        : tagged_records_sorted(b->rest_k, ones, n_rest, b->s.k, b->rc, SeenTag::by_delta(), false, b->edge_key, raw_seq, &b->n_edges, &distinct, stream);
+    if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
+    if (rc != KATOME_OK) { b->n_edges = 0; return KATOME_OK; }
     rest_reset(b);
     b->stat_kmers = distinct; b->stat_kmer_slots = 0;
     *counted = true;
@@ -1359,8 +1495,13 @@ int katome_dev_edges(katome_builder* b, uint64_t** d_edge_key, uint32_t** d_edge
             if (!counted) KCHECK(edges_from_tile_table(b, &counted, stream));
             if (!counted) KCHECK(edges_from_table(b, false, raw_seq, stream));
         } else {
+            const char* route = "tile records";
             if (b->tile_recs_n) KCHECK(seen_edges_from_tile_recs(b, raw_seq, &counted, stream));
-            if (!counted) KCHECK(seen_edges_from_tile_table(b, raw_seq, &counted, stream));
+            if (!counted) { route = "tile table, k-mers by sorting"; KCHECK(seen_edges_from_tile_table(b, raw_seq, &counted, stream)); }
+            if (!counted) { route = "windows kept aside"; KCHECK(seen_edges_from_rest(b, raw_seq, &counted, stream)); }
+            if (b->var_seq_base && getenv("KATOME_LC_TRACE"))
+                fprintf(stderr, "[first-seen order, reads of varying length] levels counted %s%s (KATOME_SEEN_VAR_SORTED=%d)\n", counted ? "by sorting: " : "in the tables",
+                        counted ? route : "", (int)seen_var_sorted());
             KCHECK(edges_from_table(b, counted, raw_seq, stream));
         }
         b->edges_ready = true;

@@ -40,6 +40,11 @@ struct katome_builder {
     const uint64_t* var_rec_prefix = nullptr;  // records before each read for the records just extracted (tiles / left-over windows)
     uint64_t var_records = 0;                  // how many of them: the insert that follows must take exactly these
     uint32_t var_mode = 0, var_span = 1;       // 0 every window, 1 whole tiles, 2 the windows after the last whole tile
+    // first-seen order, reads of varying length, levels counted by sorting (KATOME_SEEN_VAR_SORTED): the tagged records kept aside
+    // (tile_recs, rest_k) carry the delta tag of seen_tag.h, not seen_pack's; set with the first batch kept so
+    bool seen_delta = false;
+    // ... which is kept only if every read of it packs: the last batch asked about (its prefix and sequence base) and the answer
+    const uint64_t* var_checked = nullptr; uint64_t var_checked_base = ~0ull; bool var_checked_ok = false;
     DevBuf edge_seq;                   // sequence number of each edge's first insertion, aligned with edge_key
     // by-packed-key builds: the windows left over after a batch's tiles wait here (records of weight 1), so that the last level can
     // be counted by sorting (lds_count.hip, records_to_edges_sorted) together with the tiles' k-mers; any other consumer of the k-mer

@@ -477,6 +477,15 @@ struct SeenOrigin {
     // out of another rank's tiles
     const uint64_t* pairs = nullptr;
 };
+// How a first-seen build's tagged records spell their two sequence numbers: reads of one length as read << 32 | offset << 16 | offset
+// (slot_bits.h, seen_pack; seq_per_read = 2 x windows turns the offsets back into numbers), reads of varying length as the numbers
+// themselves (seen_tag.h, the delta tag; seq_per_read means nothing)
+struct SeenTag {
+    bool delta = false; uint64_t seq_per_read = 0;
+    static SeenTag fixed(uint64_t seq_per_read) { SeenTag t; t.seq_per_read = seq_per_read; return t; }
+    static SeenTag by_delta() { SeenTag t; t.delta = true; return t; }
+    bool packs() const { return delta || (seq_per_read != 0 && seq_per_read <= 0xFFFFu); }
+};
 int table_alloc(Table& t, uint32_t nw, uint64_t cap, hipStream_t stream);
 int table_insert(Table& t, const uint64_t* d_records, const uint32_t* d_weights, uint64_t n, hipStream_t stream,
                  const SeenOrigin* origin = nullptr);
@@ -505,19 +514,25 @@ int table_tiles_to_records_fast(Table& tiles, uint32_t k, uint32_t span, bool rc
                                 uint64_t extra_room = 0);
 // first-seen builds, last level counted by sorting: the tiles' k-mers as (k-mer, packed sequence numbers) records, counted and
 // numbered in LDS; edge_key (unsorted) and seq_weight ([n][2]: {sequence number, weight}) come out as table_emit_edges leaves them.
-// seq_per_read: sequence numbers a read takes (2 x windows); E_UNSUPPORTED when the packing does not fit (the caller counts in the table)
+// tag: how the records spell their two numbers; E_UNSUPPORTED when the packing does not fit (the caller counts in the table)
 // (d_extra / n_extra: tagged records to count with them -- the windows left over after the tiles, table_rest_to_tagged)
-int tiles_to_edges_sorted_seen(Table& tiles, uint32_t k, uint32_t span, bool rc, uint64_t seq_per_read, DevBuf& edge_key, DevBuf& seq_weight,
+int tiles_to_edges_sorted_seen(Table& tiles, uint32_t k, uint32_t span, bool rc, SeenTag tag, DevBuf& edge_key, DevBuf& seq_weight,
                                uint64_t* n_edges, uint64_t* n_distinct, hipStream_t stream, const uint64_t* d_extra = nullptr, uint64_t n_extra = 0);
 // appends the valid records of d_rec behind *d_cursor in d_out (tagged: as records of nw + 1 words, see seen_pack in slot_bits.h)
 int table_keep_rest(const uint64_t* d_rec, uint64_t n, uint32_t nw, bool tagged, uint64_t read0, uint32_t per_read, uint32_t win0, uint32_t seq_per_read,
                     uint64_t* d_out, uint64_t* d_cursor, hipStream_t stream, uint32_t win_stride = 1, uint32_t span = 1);
-int tagged_records_sorted(DevBuf& recs, DevBuf& wts, uint64_t n, uint32_t k, bool rc, uint64_t seq_per_read, bool list, DevBuf& out_keys,
+int tagged_records_sorted(DevBuf& recs, DevBuf& wts, uint64_t n, uint32_t k, bool rc, SeenTag tag, bool list, DevBuf& out_keys,
                           DevBuf& out_second, uint64_t* n_out, uint64_t* n_distinct, hipStream_t stream, uint32_t* first_counts = nullptr);
 int table_list_to_tagged_records(const uint64_t* d_list, const uint32_t* d_counts, uint64_t n_tiles, uint32_t tile_bases, uint32_t sub_len, uint32_t n_sub,
                                  uint32_t stride, bool rc, DevBuf& recs, DevBuf& weights, uint64_t* n_records, hipStream_t stream, uint64_t extra_room = 0,
-                                 DevBuf* first_counts = nullptr);
-int table_tagged_to_pairs(const uint64_t* d_tagged, uint64_t n, uint32_t nw, uint64_t seq_per_read, uint64_t* d_keys, uint64_t* d_pairs, hipStream_t stream);
+                                 DevBuf* first_counts = nullptr, bool delta = false);
+int table_tagged_to_pairs(const uint64_t* d_tagged, uint64_t n, uint32_t nw, SeenTag tag, uint64_t* d_keys, uint64_t* d_pairs, hipStream_t stream);
+// The records of a batch of variable-length reads (mode / span / prefixes: seq_pair.h, var_seq_pair) as delta-tagged records of nw + 1
+// words: the valid ones are appended behind *d_cursor in d_out.  The caller has checked that every read of the batch packs
+// (table_max_windows: no read of more than DELTA_MAX_WINDOWS windows, numbers below DELTA_P_LIMIT)
+int table_keep_var_tagged(const uint64_t* d_rec, uint64_t n, uint32_t nw, bool rc, const uint64_t* d_win_prefix, const uint64_t* d_rec_prefix, uint64_t n_reads,
+                          uint32_t mode, uint32_t span, uint64_t seq_base, uint64_t* d_out, uint64_t* d_cursor, hipStream_t stream);
+int table_max_windows(const uint64_t* d_win_prefix, uint64_t n_reads, uint64_t* max_windows, hipStream_t stream);      // the longest read's windows (synchronises)
 // A rank's own distinct k-mers on their way to their owners (sharded build): with an OwnerSplit the records are grouped by the hash
 // of their CORE instead of the whole k-mer's, and every group's keys are written into its owner's stretch of the output -- base[p],
 // count[p] on return --, so that no partition pass is needed before the exchange.  One-word k-mers, one record per k-mer (rc = false).

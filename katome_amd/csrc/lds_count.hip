@@ -886,7 +886,9 @@ __global__ __launch_bounds__(LC_THREADS) void lds_count_full3_kernel(const u64* 
 // LIST: a TILE level of such a build -- every distinct key leaves once, as key + tag (the two lowered numbers
 // packed again: both come from the first read that holds the tile on either strand) in out_keys [n][NWK + 1] and its count in
 // out_pairs read as u32 [n]; RC then only says whether the second number is tracked.
-template <bool RC, int NWK, bool LIST = false>
+// DELTA: the records carry the delta tag (seen_tag.h: reads of varying length) -- lA / lB then hold the two numbers themselves, and
+// seq_per_read means nothing.
+template <bool RC, int NWK, bool LIST = false, bool DELTA = false>
 __global__ __launch_bounds__(LC_THREADS) void lds_count_seen_kernel(const u64* recs, const u32* wts, const u64* __restrict__ index, u32 gbits, u32 R, u32 k,
                                                                      u64 seq_per_read, u64* out_keys, u64* out_pairs, u64 out_cap,
                                                                      unsigned long long* cursor, unsigned long long* distinct, u32* err, u32 probe_limit) {
@@ -895,7 +897,7 @@ __global__ __launch_bounds__(LC_THREADS) void lds_count_seen_kernel(const u64* r
     constexpr unsigned long long REP_MASK = (1ull << 20) - 1;
     extern __shared__ unsigned long long lcs_mem[];
     unsigned long long* lkey = lcs_mem;                                  // [SLOTS]: OCC | key, or OCC | fingerprint << 20 | representative
-    unsigned long long* lA = lcs_mem + SLOTS;                            // [SLOTS]: read << 16 | offset, stored orientation
+    unsigned long long* lA = lcs_mem + SLOTS;                            // [SLOTS]: read << 16 | offset (DELTA: the number), stored orientation
     unsigned long long* lB = lcs_mem + 2 * SLOTS;                        // [SLOTS]: ... reverse complement
     u32* lcnt = reinterpret_cast<u32*>(lcs_mem + 3 * SLOTS);             // [SLOTS]
     __shared__ u32 wtot[LC_THREADS / 64];
@@ -949,8 +951,8 @@ __global__ __launch_bounds__(LC_THREADS) void lds_count_seen_kernel(const u64* r
                     }
                     if (mine) {
                         atomicAdd(&lcnt[s], w);
-                        atomicMin(&lA[s], (tag >> 32) << 16 | ((tag >> 16) & 0xFFFFull));
-                        if (RC) atomicMin(&lB[s], (tag >> 32) << 16 | (tag & 0xFFFFull));
+                        atomicMin(&lA[s], DELTA ? delta_p(tag) : (tag >> 32) << 16 | ((tag >> 16) & 0xFFFFull));
+                        if (RC) atomicMin(&lB[s], DELTA ? delta_q(tag) : (tag >> 32) << 16 | (tag & 0xFFFFull));
                         break;
                     }
                     s += step; if (s >= SLOTS) s -= SLOTS;
@@ -1007,14 +1009,19 @@ __global__ __launch_bounds__(LC_THREADS) void lds_count_seen_kernel(const u64* r
                     for (u32 j = 0; j < (u32)LCS_PER; ++j) {
                         if (!ne[j]) continue;
                         const unsigned long long a = sa[j], b = sb[j];
-                        const u64 seq_a = (a >> 16) * seq_per_read + (a & 0xFFFFull), seq_b = (b >> 16) * seq_per_read + (b & 0xFFFFull);
+                        const u64 seq_a = DELTA ? a : (a >> 16) * seq_per_read + (a & 0xFFFFull), seq_b = DELTA ? b : (b >> 16) * seq_per_read + (b & 0xFFFFull);
                         const u32 c = sc[j];
                         if (LIST) {
                             if (p < SC) {
 #pragma unroll
                                 for (int q = 0; q < NWK; ++q) skey[(size_t)p * KW + q] = kk[j].w[q];
+                                if (DELTA) {
+                                    if (!delta_packs(a, RC ? b : a)) *err = 6;          // (the two numbers of a tile too far apart: two reads -- cannot be -- or a read too long)
+                                    skey[(size_t)p * KW + NWK] = delta_pack(a, RC ? b : a);
+                                } else {
                                 if (RC && (a >> 16) != (b >> 16)) *err = 6;              // (the two numbers of a tile from two reads: cannot be)
                                 skey[(size_t)p * KW + NWK] = seen_pack(a >> 16, (u32)(a & 0xFFFFull), RC ? (u32)(b & 0xFFFFull) : 0u);
+                                }
                                 scount[p] = c;
                             }
                         } else if (ne[j] == 2) {
@@ -1129,15 +1136,16 @@ static int count_optimistic(const char* what, u32 R_try, u32 R, u32 guaranteed_l
     return count(R, guaranteed_limit);
 }
 
-// Tagged records [n][nwk + 1] (key, read << 32 | offset << 16 | offset) with their counts -> two hash passes on the key, counted in LDS
+// Tagged records [n][nwk + 1] (key, read << 32 | offset << 16 | offset -- or the delta tag, `tag`) with their counts -> two hash passes on the key, counted in LDS
 // with the two numbers lowered (lds_count_seen_kernel).  list == false: the oriented edges, out_keys [e][nwk] + out_second [e][2] =
 // {sequence number, weight}.  list == true (a tile level): the distinct keys with their tags, out_keys [d][nwk + 1], and their counts,
 // out_second [d] u32.  The records come back permuted.
-int tagged_records_sorted(DevBuf& recs, DevBuf& wts, uint64_t n, uint32_t k, bool rc, uint64_t seq_per_read, bool list, DevBuf& edge_key,
+int tagged_records_sorted(DevBuf& recs, DevBuf& wts, uint64_t n, uint32_t k, bool rc, SeenTag tag, bool list, DevBuf& edge_key,
                           DevBuf& seq_weight, uint64_t* n_edges, uint64_t* n_distinct, hipStream_t stream, uint32_t* first_counts) {
     *n_edges = 0; *n_distinct = 0;
     const uint32_t nwk = (uint32_t)key_words_for_k(k), stride = nwk + 1;
-    if (nwk > 2 || seq_per_read == 0 || seq_per_read > 0xFFFFu || !lcs_level_fits(n)) return KATOME_E_UNSUPPORTED;
+    if (nwk > 2 || !tag.packs() || !lcs_level_fits(n)) return KATOME_E_UNSUPPORTED;
+    const uint64_t seq_per_read = tag.seq_per_read;
     LcAux aux(stream);
     KCHECK(aux.buf.alloc(64));
     KCHECK(aux.reset());
@@ -1170,10 +1178,10 @@ int tagged_records_sorted(DevBuf& recs, DevBuf& wts, uint64_t n, uint32_t k, boo
             return lc_launch(aux, kernel, (size_t)LcsTable::SLOTS * 28, n, r, ko, wo, index.as<u64>(), gbits, rounds, k, seq_per_read, edge_key.as<u64>(),
                              seq_weight.as<u64>(), out_cap, aux.cursor(), aux.distinct(), aux.err(), probe_limit);
         };
-        return with_bool(rc, [&](auto rcv) { return with_bool(list, [&](auto lv) {
-            constexpr bool RC = decltype(rcv)::value, LIST = decltype(lv)::value;
-            return nwk == 1 ? launch(lds_count_seen_kernel<RC, 1, LIST>) : launch(lds_count_seen_kernel<RC, 2, LIST>);
-        }); });
+        return with_bool(rc, [&](auto rcv) { return with_bool(list, [&](auto lv) { return with_bool(tag.delta, [&](auto dv) {
+            constexpr bool RC = decltype(rcv)::value, LIST = decltype(lv)::value, DELTA = decltype(dv)::value;
+            return nwk == 1 ? launch(lds_count_seen_kernel<RC, 1, LIST, DELTA>) : launch(lds_count_seen_kernel<RC, 2, LIST, DELTA>);
+        }); }); });
     };
     KCHECK(count_optimistic("first-seen order", lc_rounds_try(avg, lc_optimism(), LcsTable::FILL), R, LcsTable::SLOTS, r, count));
     if (r.code == 4 || r.code == 6) return KATOME_E_UNSUPPORTED;

@@ -1,7 +1,9 @@
 // slot_bits.h -- what the table in HBM (table.hip) and the counting tables in LDS (lds_count.hip) both spell: a slot's flag bits and
-// the packed pair of sequence numbers in a first-seen build's tagged records.
+// the packed pair of sequence numbers in a first-seen build's tagged records -- seen_pack for reads of one length, the delta tag of
+// seen_tag.h for reads of varying length (the kernels that read a tag take the format as a template parameter, DELTA).
 #pragma once
 #include "common.h"
+#include "seen_tag.h"
 
 namespace katome {
 constexpr u64 OCC = 1ull << 63;    // slot holds a published key

@@ -762,22 +762,108 @@ __global__ __launch_bounds__(BLOCK) void keep_rest_kernel(const u64* __restrict_
         __syncthreads();
     }
 }
+// keep_rest_kernel<NW, true> for a batch of variable-length reads: record g's numbers are var_seq_pair's (seq_pair.h: the function the
+// table's insert uses) and leave as a delta tag (seen_tag.h).  One thread per record finds its read by the same binary search over
+// rec_prefix that extract_general_kernel ran to cut the record (a batch's prefix stays in L2), the KR_ITEMS searches of a thread in
+// step; the host has checked that every read of the batch packs (table_max_windows), so no record is refused here.
+template <int NW, bool RC>
+__global__ __launch_bounds__(BLOCK) void keep_var_kernel(const u64* __restrict__ rec, u64 n, const u64* __restrict__ win_prefix, const u64* __restrict__ rec_prefix,
+                                                          u64 n_reads, u32 mode, u32 span, u64 seq_base, u64* __restrict__ out, unsigned long long* cursor) {
+    constexpr int WORDS = NW + 1;
+    constexpr u32 TILE = BLOCK * KR_ITEMS;
+    __shared__ u32 wtot[KR_ITEMS][BLOCK / 64];       // as keep_rest_kernel's
+    __shared__ unsigned long long base_sh;
+    const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const u64 lt_mask = lane ? (~0ull >> (64 - lane)) : 0ull;
+    for (u64 t0 = (u64)blockIdx.x * TILE; t0 < n; t0 += (u64)gridDim.x * TILE) {
+        Key<NW> key[KR_ITEMS];
+        u32 before[KR_ITEMS];
+#pragma unroll
+        for (int j = 0; j < KR_ITEMS; ++j) {
+            const u64 i = t0 + (u64)j * BLOCK + tid;
+            key[j] = key_invalid<NW>();
+            if (i < n) {
+#pragma unroll
+                for (int q = 0; q < NW; ++q) key[j].w[q] = rec[i * NW + q];
+            }
+            const u64 m = __ballot(key_valid(key[j]));
+            before[j] = __popcll(m & lt_mask);
+            if (lane == 0) wtot[j][wave] = __popcll(m);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            u32 run = 0;
+#pragma unroll
+            for (int j = 0; j < KR_ITEMS; ++j)
+#pragma unroll
+                for (u32 w = 0; w < BLOCK / 64; ++w) { const u32 c = wtot[j][w]; wtot[j][w] = run; run += c; }
+            base_sh = run ? atomicAdd(cursor, (unsigned long long)run) : 0ull;
+        }
+        __syncthreads();
+        // var_seq_pair's search for the thread's KR_ITEMS records, step by step side by side: a step's loads are in flight together
+        // (one record after the other, the kernel waited for KR_ITEMS x log2(reads) dependent loads in a row)
+        u64 lo[KR_ITEMS], hi[KR_ITEMS];
+#pragma unroll
+        for (int j = 0; j < KR_ITEMS; ++j) { lo[j] = 0; hi[j] = key_valid(key[j]) ? n_reads : 1; }
+        for (bool more = true; more;) {
+            more = false;
+            u64 at_mid[KR_ITEMS];
+#pragma unroll
+            for (int j = 0; j < KR_ITEMS; ++j) at_mid[j] = rec_prefix[(lo[j] + hi[j]) >> 1];       // (a finished search reads [lo] once more: in bounds)
+#pragma unroll
+            for (int j = 0; j < KR_ITEMS; ++j) {
+                if (hi[j] - lo[j] <= 1) continue;
+                const u64 mid = (lo[j] + hi[j]) >> 1;
+                if (at_mid[j] <= t0 + (u64)j * BLOCK + tid) lo[j] = mid; else hi[j] = mid;
+                more = more || hi[j] - lo[j] > 1;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < KR_ITEMS; ++j) {
+            if (!key_valid(key[j])) continue;
+            const u64 i = t0 + (u64)j * BLOCK + tid;
+            const u64 at = (base_sh + wtot[j][wave] + before[j]) * WORDS;
+            const bool flipped = (key[j].w[0] & RC_MARK) != 0;
+            key[j].w[0] &= ~RC_MARK;
+#pragma unroll
+            for (int q = 0; q < NW; ++q) out[at + q] = key[j].w[q];
+            u64 P, Q;
+            var_pair_in_read(win_prefix, rec_prefix, lo[j], mode, span, seq_base, i, P, Q);
+            if (!RC) Q = P;                          // (one strand: one number)
+            out[at + NW] = flipped ? delta_pack(Q, P) : delta_pack(P, Q);
+        }
+        __syncthreads();
+    }
+}
+// the most windows any read of a batch has (prefix[r + 1] - prefix[r])
+__global__ __launch_bounds__(BLOCK) void max_windows_kernel(const u64* __restrict__ win_prefix, u64 n_reads, unsigned long long* out) {
+    u64 m = 0;
+    for (u64 r = (u64)blockIdx.x * BLOCK + threadIdx.x; r < n_reads; r += (u64)gridDim.x * BLOCK) {
+        const u64 w = win_prefix[r + 1] - win_prefix[r];
+        m = w > m ? w : m;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const u64 v = __shfl_xor(m, o, 64); m = v > m ? v : m; }
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(out, (unsigned long long)m);
+}
 // ... and back into (key, {first insertion of the stored orientation, of its reverse complement}) for the k-mer table
-template <int NW>
+// (DELTA: the delta tag of seen_tag.h -- the two numbers themselves)
+template <int NW, bool DELTA>
 __global__ __launch_bounds__(BLOCK) void tagged_to_pairs_kernel(const u64* __restrict__ tagged, u64 n, u64 seq_per_read, u64* __restrict__ keys,
                                                                  u64* __restrict__ pairs) {
     for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
 #pragma unroll
         for (int q = 0; q < NW; ++q) keys[i * NW + q] = tagged[i * (NW + 1) + q];
         const u64 tag = tagged[i * (NW + 1) + NW], base = (tag >> 32) * seq_per_read;
-        pairs[2 * i] = base + ((tag >> 16) & 0xFFFFull); pairs[2 * i + 1] = base + (tag & 0xFFFFull);
+        pairs[2 * i] = DELTA ? delta_p(tag) : base + ((tag >> 16) & 0xFFFFull); pairs[2 * i + 1] = DELTA ? delta_q(tag) : base + (tag & 0xFFFFull);
     }
 }
 
 // every distinct tile of the last level -> its `span` k-mers as records of NWK + 1 words + the tile's count (tiles_to_records_kernel's
 // shape: 2048 slots per trip).  read = fwd / seq_per_read as a multiplication by `magic` = floor(2^64 / seq_per_read) + 1: exact for
 // numbers below 2^64 / seq_per_read, which 2^32 reads of < 2^16 numbers each stay under.
-template <int NWT, int NWK, bool RC>
+// DELTA (reads of varying length): the tile's pair packs as it is (seen_tag.h) -- lread holds P, loff Q - P + DELTA_BIAS --, no division.
+template <int NWT, int NWK, bool RC, bool DELTA>
 __global__ __launch_bounds__(BLOCK) void seen_records_kernel(const typename SlotOf<NWT>::type* __restrict__ tiles, const u64* __restrict__ tile_seen, u64 tile_cap,
                                                               u32 k, u32 span, u64 seq_per_read, u64 magic, u64* __restrict__ out, u32* __restrict__ out_w,
                                                               u64* cursor, u32* err) {
@@ -819,10 +905,17 @@ __global__ __launch_bounds__(BLOCK) void seen_records_kernel(const typename Slot
 #pragma unroll
             for (int q = 0; q < NWT; ++q) lkey[at * NWT + q] = tk[j].w[q];
             lcnt[at] = tc[j];
+            if (DELTA) {
+                const u64 P = fwd[j], Q = RC ? rev[j] : fwd[j], gap = Q >= P ? Q - P : P - Q;
+                // (a sub-window's numbers are P + o and Q + span - 1 - o: the gap grows by less than span)
+                if (P + span >= DELTA_P_LIMIT || Q + span >= DELTA_P_LIMIT || gap + span >= DELTA_BIAS) *err = 5;      // (does not pack)
+                lread[at] = P; loff[2 * at] = (u32)(Q - P + DELTA_BIAS); loff[2 * at + 1] = 0u;
+            } else {
             const u64 read = __umul64hi(fwd[j], magic);
             const u64 a = fwd[j] - read * seq_per_read, b = RC ? rev[j] - read * seq_per_read : 0;        // (no reverse complements: one number)
             if (read >> 32 || a >= seq_per_read || a + span > 0xFFFFu || (RC && (rev[j] < read * seq_per_read || b > 0xFFFFu))) *err = 5;   // (does not pack)
             lread[at] = read; loff[2 * at] = (u32)a; loff[2 * at + 1] = (u32)b;
+            }
             ++at;
         }
         if (tid == 0 && total) bbase = atomicAdd((unsigned long long*)cursor, (unsigned long long)total * span);
@@ -842,6 +935,12 @@ __global__ __launch_bounds__(BLOCK) void seen_records_kernel(const typename Slot
             const u64 rec = (base + p) * (NWK + 1);
 #pragma unroll
             for (int q = 0; q < NWK; ++q) out[rec + q] = x.w[q];
+            if (DELTA) {
+                u64 Ps, Qs;
+                delta_sub(lread[t], lread[t] + loff[2 * t] - DELTA_BIAS, o, span, 1, Ps, Qs);
+                if (!RC) Qs = Ps;
+                out[rec + NWK] = flipped ? delta_pack(Qs, Ps) : delta_pack(Ps, Qs);
+            } else
             out[rec + NWK] = seen_pack(lread[t], flipped ? b : a, flipped ? a : b);
             out_w[base + p] = lcnt[t];
         }
@@ -853,7 +952,8 @@ __global__ __launch_bounds__(BLOCK) void seen_records_kernel(const typename Slot
 // sub-window p % n_sub of tile p / n_sub; its numbers are the tile's plus the sub-window's place in it (expand_tiles_kernel's rule)
 // (digit_counts: written tile by tile of the partition pass that follows -- tile_keys records per trip --, that pass's digit counted per
 // tile on the way, as list_to_records_hist_kernel does; without: a plain grid-stride walk)
-template <int NWT, int NWK, bool RC>
+// DELTA: list and records carry the delta tag (seen_tag.h)
+template <int NWT, int NWK, bool RC, bool DELTA>
 __global__ __launch_bounds__(BLOCK) void list_to_tagged_records_kernel(const u64* __restrict__ list, const u32* __restrict__ counts, u64 n_tiles, u32 sub_len,
                                                                         u32 n_sub, u32 stride, u64* __restrict__ out, u32* __restrict__ out_w,
                                                                         u32 tile_keys, u32* __restrict__ digit_counts) {
@@ -879,6 +979,12 @@ __global__ __launch_bounds__(BLOCK) void list_to_tagged_records_kernel(const u64
         const u32 a = (u32)((tag >> 16) & 0xFFFFull) + o * stride, b = RC ? (u32)(tag & 0xFFFFull) + (n_sub - 1 - o) * stride : 0u;
 #pragma unroll
         for (int q = 0; q < NWK; ++q) out[p * (NWK + 1) + q] = x.w[q];
+        if (DELTA) {
+            u64 Ps, Qs;
+            delta_sub(delta_p(tag), delta_q(tag), o, n_sub, stride, Ps, Qs);
+            if (!RC) Qs = Ps;
+            out[p * (NWK + 1) + NWK] = flipped ? delta_pack(Qs, Ps) : delta_pack(Ps, Qs);
+        } else
         out[p * (NWK + 1) + NWK] = seen_pack(tag >> 32, flipped ? b : a, flipped ? a : b);
         out_w[p] = counts[t];
         if (digit_counts) atomicAdd(&h[(u32)(hash_key(x) >> 48) & 255u], 1u);        // (HashTaggedDigit: the key's words only)
@@ -1212,19 +1318,51 @@ int table_keep_rest(const uint64_t* d_rec, uint64_t n, uint32_t nw, bool tagged,
     KCHECK_HIP(hipGetLastError());
     return KATOME_OK;
 }
-int table_tagged_to_pairs(const uint64_t* d_tagged, uint64_t n, uint32_t nw, uint64_t seq_per_read, uint64_t* d_keys, uint64_t* d_pairs, hipStream_t stream) {
+int table_tagged_to_pairs(const uint64_t* d_tagged, uint64_t n, uint32_t nw, SeenTag tag, uint64_t* d_keys, uint64_t* d_pairs, hipStream_t stream) {
     if (n == 0) return KATOME_OK;
     const dim3 grid(grid_for(n, BLOCK, 256u * 16u)), block(BLOCK);
-    if (nw == 1) hipLaunchKernelGGL(tagged_to_pairs_kernel<1>, grid, block, 0, stream, d_tagged, n, seq_per_read, d_keys, d_pairs);
-    else         hipLaunchKernelGGL(tagged_to_pairs_kernel<2>, grid, block, 0, stream, d_tagged, n, seq_per_read, d_keys, d_pairs);
+    with_bool(tag.delta, [&](auto dv) {
+        constexpr bool DELTA = decltype(dv)::value;
+        if (nw == 1) hipLaunchKernelGGL((tagged_to_pairs_kernel<1, DELTA>), grid, block, 0, stream, d_tagged, n, tag.seq_per_read, d_keys, d_pairs);
+        else         hipLaunchKernelGGL((tagged_to_pairs_kernel<2, DELTA>), grid, block, 0, stream, d_tagged, n, tag.seq_per_read, d_keys, d_pairs);
+        return 0;
+    });
     KCHECK_HIP(hipGetLastError());
+    return KATOME_OK;
+}
+
+int table_keep_var_tagged(const uint64_t* d_rec, uint64_t n, uint32_t nw, bool rc, const uint64_t* d_win_prefix, const uint64_t* d_rec_prefix, uint64_t n_reads,
+                          uint32_t mode, uint32_t span, uint64_t seq_base, uint64_t* d_out, uint64_t* d_cursor, hipStream_t stream) {
+    if (n == 0) return KATOME_OK;
+    if (nw > 2 || !n_reads || !d_win_prefix || !d_rec_prefix) { set_error("tagged records: keys of one or two words, cut from a batch of reads"); return KATOME_E_UNSUPPORTED; }
+    const dim3 grid(grid_for(n, BLOCK * KR_ITEMS, 256u * 8u)), block(BLOCK);
+    unsigned long long* cur = reinterpret_cast<unsigned long long*>(d_cursor);
+    with_bool(rc, [&](auto rcv) {
+        constexpr bool RC = decltype(rcv)::value;
+        if (nw == 1) hipLaunchKernelGGL((keep_var_kernel<1, RC>), grid, block, 0, stream, d_rec, n, d_win_prefix, d_rec_prefix, n_reads, mode, span, seq_base, d_out, cur);
+        else         hipLaunchKernelGGL((keep_var_kernel<2, RC>), grid, block, 0, stream, d_rec, n, d_win_prefix, d_rec_prefix, n_reads, mode, span, seq_base, d_out, cur);
+        return 0;
+    });
+    KCHECK_HIP(hipGetLastError());
+    return KATOME_OK;
+}
+int table_max_windows(const uint64_t* d_win_prefix, uint64_t n_reads, uint64_t* max_windows, hipStream_t stream) {
+    *max_windows = 0;
+    if (!n_reads) return KATOME_OK;
+    DevBuf out(stream);
+    KCHECK(out.alloc(8));
+    KCHECK_HIP(hipMemsetAsync(out.p, 0, 8, stream));
+    hipLaunchKernelGGL(max_windows_kernel, dim3(grid_for(n_reads, BLOCK, 256u * 8u)), dim3(BLOCK), 0, stream, d_win_prefix, n_reads, out.as<unsigned long long>());
+    KCHECK_HIP(hipGetLastError());
+    KCHECK_HIP(hipMemcpyAsync(max_windows, out.p, 8, hipMemcpyDeviceToHost, stream));
+    KCHECK_HIP(hipStreamSynchronize(stream));
     return KATOME_OK;
 }
 
 // the tagged records of the next level out of a list of distinct tiles with their tags and counts (list_to_tagged_records_kernel)
 int table_list_to_tagged_records(const uint64_t* d_list, const uint32_t* d_counts, uint64_t n_tiles, uint32_t tile_bases, uint32_t sub_len, uint32_t n_sub,
                                  uint32_t stride, bool rc, DevBuf& recs, DevBuf& weights, uint64_t* n_records, hipStream_t stream, uint64_t extra_room,
-                                 DevBuf* first_counts) {
+                                 DevBuf* first_counts, bool delta) {
     const uint32_t nwt = (uint32_t)key_words_for_k(tile_bases), nwk = (uint32_t)key_words_for_k(sub_len);
     *n_records = n_tiles * n_sub;
     KCHECK(recs.alloc((*n_records + extra_room + 1) * 8 * (nwk + 1), stream));
@@ -1238,7 +1376,7 @@ int table_list_to_tagged_records(const uint64_t* d_list, const uint32_t* d_count
     else if (first_counts) first_counts->release();
     const dim3 grid(with_counts ? grid_for(n_out_tiles, 1, 256u * 32u) : grid_for(*n_records, BLOCK, 256u * 32u)), block(BLOCK);
     KernelScope ks(K_RECORDS, stream, n_tiles);
-#define KATOME_LT(NWT, NWK) with_bool(rc, [&](auto rcv) { hipLaunchKernelGGL((list_to_tagged_records_kernel<NWT, NWK, decltype(rcv)::value>), grid, block, 0, stream, d_list, d_counts, n_tiles, sub_len, n_sub, stride, recs.as<u64>(), weights.as<u32>(), tile_keys, d_digit_counts); return 0; })
+#define KATOME_LT(NWT, NWK) with_bool(rc, [&](auto rcv) { return with_bool(delta, [&](auto dv) { hipLaunchKernelGGL((list_to_tagged_records_kernel<NWT, NWK, decltype(rcv)::value, decltype(dv)::value>), grid, block, 0, stream, d_list, d_counts, n_tiles, sub_len, n_sub, stride, recs.as<u64>(), weights.as<u32>(), tile_keys, d_digit_counts); return 0; }); })
     if (nwt == 2 && nwk == 2) KATOME_LT(2, 2);
     else if (nwt == 2 && nwk == 1) KATOME_LT(2, 1);
     else if (nwt == 1 && nwk == 1) KATOME_LT(1, 1);
@@ -1248,12 +1386,13 @@ int table_list_to_tagged_records(const uint64_t* d_list, const uint32_t* d_count
     return KATOME_OK;
 }
 
-int tiles_to_edges_sorted_seen(Table& tiles, uint32_t k, uint32_t span, bool rc, uint64_t seq_per_read, DevBuf& edge_key, DevBuf& seq_weight,
+int tiles_to_edges_sorted_seen(Table& tiles, uint32_t k, uint32_t span, bool rc, SeenTag tag, DevBuf& edge_key, DevBuf& seq_weight,
                                uint64_t* n_edges, uint64_t* n_distinct, hipStream_t stream, const uint64_t* d_extra, uint64_t n_extra) {
     *n_edges = 0; *n_distinct = 0;
     const uint32_t nwk = (uint32_t)key_words_for_k(k), stride = nwk + 1;
     const bool shapes = tiles.track_seen && ((nwk == 1 && tiles.nw <= 2) || (nwk == 2 && (tiles.nw == 2 || tiles.nw == 3)));
-    if (!shapes || seq_per_read == 0 || seq_per_read > 0xFFFFu) return KATOME_E_UNSUPPORTED;
+    if (!shapes || !tag.packs()) return KATOME_E_UNSUPPORTED;
+    const uint64_t seq_per_read = tag.seq_per_read;
     uint64_t occ = 0;
     KCHECK(table_occupied(tiles, &occ, stream));
     const u64 bound = occ * span + n_extra;
@@ -1268,13 +1407,13 @@ int tiles_to_edges_sorted_seen(Table& tiles, uint32_t k, uint32_t span, bool rc,
     {
         KernelScope ks(K_RECORDS, stream, tiles.cap);
         const dim3 grid(grid_for(tiles.cap, BLOCK * TR_ITEMS, 256u * 8u)), block(BLOCK);
-        const u64 magic = ~0ull / seq_per_read + 1;
-#define KATOME_SR(NWT, NWK) KCHECK(with_bool(rc, [&](auto rcv) -> int {                                                                 \
-            const auto kernel = seen_records_kernel<NWT, NWK, decltype(rcv)::value>;                                                     \
+        const u64 magic = tag.delta ? 0 : ~0ull / seq_per_read + 1;
+#define KATOME_SR(NWT, NWK) KCHECK(with_bool(rc, [&](auto rcv) -> int { return with_bool(tag.delta, [&](auto dv) -> int {              \
+            const auto kernel = seen_records_kernel<NWT, NWK, decltype(rcv)::value, decltype(dv)::value>;                                \
             const size_t lds = (size_t)BLOCK * TR_ITEMS * (8 * NWT + 8 + 8 + 4);                                                         \
             KCHECK_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                  \
             hipLaunchKernelGGL(kernel, grid, block, lds, stream, tiles.slots.as<SlotOf<NWT>::type>(), tiles.seen.as<u64>(), tiles.cap, k, span, seq_per_read, magic, recs.as<u64>(), wts.as<u32>(), rec_cursor, err); \
-            return KATOME_OK; }))
+            return KATOME_OK; }); }))
         if (nwk == 1) { if (tiles.nw == 1) KATOME_SR(1, 1); else KATOME_SR(2, 1); }
         else          { if (tiles.nw == 2) KATOME_SR(2, 2); else KATOME_SR(3, 2); }
 #undef KATOME_SR
@@ -1290,7 +1429,7 @@ int tiles_to_edges_sorted_seen(Table& tiles, uint32_t k, uint32_t span, bool rc,
         KCHECK(dev_fill_u32(wts.as<u32>() + n, n_extra, 1u, stream));
         n += n_extra;
     }
-    return tagged_records_sorted(recs, wts, n, k, rc, seq_per_read, false, edge_key, seq_weight, n_edges, n_distinct, stream);
+    return tagged_records_sorted(recs, wts, n, k, rc, tag, false, edge_key, seq_weight, n_edges, n_distinct, stream);
 }
 
 int table_emit_edges(Table& t, uint32_t k, bool rc, uint32_t min_weight, DevBuf& keys, DevBuf& weights, uint64_t* n_edges,

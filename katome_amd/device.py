@@ -296,6 +296,55 @@ class Builder(_ViewOwner):
                                                  _ptr(win_prefix), n_reads, total_windows, _ptr(out), _stream()))
         return out[:total_windows * self.nw]
 
+    def extract_var_tiles(self, packed, byte_off, lens, tile_prefix, win_prefix, total_tiles, total_windows, span, out=None):
+        """the whole tiles of `span` windows from the front of every read (tile_prefix: tiles before each read of the batch)"""
+        nwt = self.tile_words(span)
+        if out is None:
+            out = torch.empty(max(total_tiles, 1) * nwt, dtype=torch.int64, device=self.tdev)
+        assert out.numel() >= total_tiles * nwt
+        _check(_lib.lib().katome_dev_extract_var_tiles(self._h, _ptr(packed), packed.numel(), _ptr(byte_off), _ptr(lens), _ptr(tile_prefix),
+                                                       _ptr(win_prefix), lens.numel(), total_tiles, total_windows, span, _ptr(out), _stream()))
+        return out[:total_tiles * nwt]
+
+    def extract_var_remainder(self, packed, byte_off, lens, rest_prefix, win_prefix, total_rest, total_windows, span, out=None):
+        """the windows of every read after its last whole tile (rest_prefix: such windows before each read of the batch)"""
+        if out is None:
+            out = torch.empty(max(total_rest, 1) * self.nw, dtype=torch.int64, device=self.tdev)
+        assert out.numel() >= total_rest * self.nw
+        _check(_lib.lib().katome_dev_extract_var_remainder(self._h, _ptr(packed), packed.numel(), _ptr(byte_off), _ptr(lens), _ptr(rest_prefix),
+                                                           _ptr(win_prefix), lens.numel(), total_rest, total_windows, span, _ptr(out), _stream()))
+        return out[:total_rest * self.nw]
+
+    def count_var_reads(self, packed, byte_off, lens, span=None, batch_windows=None):
+        """Reads of varying length through the library's plan, as katome_build_files feeds them: batch by batch (of at most
+        `batch_windows` windows; None: one batch) the whole tiles of `span` windows, then the windows left over -- or every window on
+        its own (span 1).  packed: the reads' bases, 4 per byte, every read starting on a byte (byte_off [n + 1] int64, lens [n]
+        int32, both on the device); span None: tile_span_for_lengths' choice.  None of the reads may be shorter than k."""
+        k = self.k
+        h_len = lens.cpu().numpy().astype(np.int64)
+        assert h_len.size == 0 or h_len.min() >= k
+        if span is None:
+            span = tile_span_for_lengths(k, h_len)
+        W = h_len - k + 1
+        cum = np.cumsum(W)
+        r0, n = 0, int(h_len.size)
+        while r0 < n:
+            # (as many reads as stay within batch_windows, one at least)
+            r1 = n if batch_windows is None else max(r0 + 1, int(np.searchsorted(cum, (cum[r0 - 1] if r0 else 0) + batch_windows, "right")))
+            w = W[r0:r1]
+            dev = lambda a: torch.from_numpy(np.concatenate(([0], np.cumsum(a))).astype(np.int64)).to(self.tdev)
+            windows, boff, ln, pref = int(w.sum()), byte_off[r0:r1 + 1], lens[r0:r1], dev(w)
+            if span > 1:
+                tiles, rest = int((w // span).sum()), int((w % span).sum())
+                tpref, rpref = dev(w // span), dev(w % span)         # (the insert reads the prefixes its extraction was given)
+                if tiles:
+                    self.insert_tiles(self.extract_var_tiles(packed, boff, ln, tpref, pref, tiles, windows, span), span)
+                self.insert(self.extract_var_remainder(packed, boff, ln, rpref, pref, rest, windows, span))     # (also closes the batch)
+            else:
+                self.insert(self.extract_var(packed, boff, ln, pref, windows))
+            torch.cuda.synchronize(self.tdev)          # (the prefixes are read by the kernels: they stay until the batch is through)
+            r0 = r1
+
     # ---- routing for the multi-GPU exchange -----------------------------------------------------
     def partition(self, records, n_parts, key_words=None, values=None, core=None):
         """records grouped by owner rank (stable, invalid dropped); -> (records_out, counts[, values_out]).
@@ -401,6 +450,13 @@ class Builder(_ViewOwner):
         dg, st = _lib.DevGraph(), _lib.PruneStats()
         _check(_lib.lib().katome_dev_remove_dead_paths(self._h, C.byref(dg), C.byref(st), _stream()))
         return DeviceGraph(dg, self, self.tdev), {f: getattr(st, f) for f, _ in _lib.PruneStats._fields_}
+
+
+def tile_span_for_lengths(k, lens):
+    """one tile span for reads of several lengths (none shorter than k), the one katome_build_files picks
+    (katome_tile_span_for_lengths); 1: tiling does not pay, or KATOME_NO_TILES"""
+    h = np.ascontiguousarray(np.asarray(lens), np.uint32)
+    return int(_lib.lib().katome_tile_span_for_lengths(k, h.ctypes.data_as(C.POINTER(C.c_uint32)), h.size))
 
 
 # ---- primitives ------------------------------------------------------------------------------------
