@@ -1,18 +1,17 @@
-// api.hip -- the device half of the C ABI of include/katome_gpu.h (katome_dev_*, the counting levels, finalize): the
-// build driver behind `Build::create` (reference src/katome/algorithms/builder.rs:42-54) and the PtGraph::create
-// post-pass (collections/graphs/pt_graph.rs:333-345), composed from the kernels in extract.hip, table.hip, radix.hip,
-// node_ids.hip and first_seen.hip.  The entries that take and return host memory are in host_build.cpp.  No CPU
-// fallback: every entry that needs the device fails with KATOME_E_DEVICE when there is none.
+// api.hip -- the device half of the C ABI of include/katome_gpu.h (katome_dev_*: extraction, the table side, the insert entries,
+// finalize and the stages after it): the build driver behind `Build::create` (reference src/katome/algorithms/builder.rs:42-54) and
+// the PtGraph::create post-pass (collections/graphs/pt_graph.rs:333-345), composed from the kernels in extract.hip, table.hip,
+// radix.hip, node_ids.hip and first_seen.hip.  The records kept aside between batches are kept_records.hip's, katome_dev_edges and its
+// counting routes count_routes.hip's; the entries that take and return host memory are in host_build.cpp.  No CPU fallback: every
+// entry that needs the device fails with KATOME_E_DEVICE when there is none.
 #include <stdlib.h>
 
 #include <algorithm>
 #include <chrono>
-#include <memory>
 #include <new>
 #include <vector>
 
 #include "builder.h"
-#include "seen_tag.h"
 
 extern "C" {
 
@@ -348,8 +347,8 @@ void release_tile_tables(katome_builder* b) { b->tiles.release(); b->tiles2.rele
 
 // every distinct tile adds its count to its k-mers; afterwards the tile tables are released
 int expand_tiles(katome_builder* b, hipStream_t stream) {
-    if (b->tile_recs_n) KCHECK(flush_tile_recs(b, stream));
-    if (b->rest_n) KCHECK(flush_rest(b, stream));
+    if (b->tile_recs.n) KCHECK(flush_tile_recs(b, stream));
+    if (b->rest.n) KCHECK(flush_rest(b, stream));
     if (!b->tiles_ready) return KATOME_OK;
     Table* last = nullptr; uint32_t last_span = 1;
     KCHECK(expand_to_last_level(b, &last, &last_span, stream));
@@ -411,498 +410,52 @@ int bfc_set_edges(katome_builder* b, const uint64_t* d_fwd, const uint32_t* d_w,
     return KATOME_OK;
 }
 
-int sorted_count_mode() {
-    static const int mode = env_int("KATOME_SORTED_COUNT", 1);
-    return mode;
+// ---- first-seen order: where a batch's records sit in the read-ordered stream ---------------------------------------------------
+// the batch of variable-length reads last extracted is complete: its reads' windows, both strands, have their numbers
+static void close_var_batch(katome_builder* b) {
+    b->var_seq_base += 2 * b->var_windows;
+    b->var_prefix = b->var_rec_prefix = nullptr; b->var_reads = b->var_windows = 0;
 }
-// is counting n records by sorting worth its extra launches?  (KATOME_SORTED_COUNT=2: however few -- tests)
-bool sorting_pays(uint64_t n) { return n && (n >= (1ull << 22) || sorted_count_mode() == 2); }
-// the most records a caller hands to the LDS counting route (2^16 hash groups of 32 sub-rounds of 2900 records)
-bool lds_route_takes(uint64_t n) { return (n >> 21) <= 2900; }
-
-// plain (weight-1 or weighted) records into the k-mer table, by packed key (no origin)
-static int insert_plain(katome_builder* b, const uint64_t* d_records, const uint32_t* d_weights, uint64_t n_records, hipStream_t stream) {
-    for (uint64_t done = 0; done < n_records;) {
-        uint64_t room = 0;
-        KCHECK(ensure_table(b, n_records - done, &room, stream));
-        const uint64_t n = std::min(n_records - done, room);
-        PhaseScope ps(b->prof, PH_INSERT, stream);
-        KCHECK(table_insert(b->table, d_records + done * b->nw, d_weights ? d_weights + done : nullptr, n, stream, nullptr));
-        done += n;
+// n_records records of the last katome_dev_extract_var* call; mode 1: they are inserted as its tiles of `span` windows, else as windows
+static int var_origin(const katome_builder* b, uint64_t n_records, uint32_t mode, uint32_t span, SeenOrigin* origin) {
+    if (mode == 1) {
+        if (b->var_mode != 1 || b->var_span != span || n_records != b->var_records) { set_error("first-seen order: insert exactly the tiles katome_dev_extract_var_tiles produced"); return KATOME_E_ARG; }
+    } else if (b->var_mode == 1 || n_records != b->var_records) { set_error("first-seen order: insert exactly the records the last katome_dev_extract_var* call produced"); return KATOME_E_ARG; }
+    origin->win_prefix = b->var_prefix; origin->n_reads = b->var_reads; origin->seq_base = b->var_seq_base; origin->rc = b->rc;
+    origin->rec_prefix = b->var_rec_prefix; origin->mode = b->var_mode; origin->span = b->var_span;
+    return KATOME_OK;
+}
+// n_records records of reads of one length, cut in steps of `span` windows; remainder: they are the windows after the tiles of the
+// batch that was just inserted
+static int fixed_origin(const katome_builder* b, uint64_t n_records, uint32_t span, bool remainder, SeenOrigin* origin) {
+    if (b->var_seq_base) { set_error("first-seen order: fixed- and variable-length batches cannot be mixed in one build"); return KATOME_E_UNSUPPORTED; }
+    if (b->seen_read_len < b->s.k) { set_error("first-seen order: extract the records with this builder first"); return KATOME_E_ARG; }
+    origin->windows = b->seen_read_len - b->s.k + 1; origin->span = span; origin->rc = b->rc;
+    if (remainder) {
+        origin->per_read = b->rem_per_read; origin->win0 = b->rem_win0; origin->read0 = b->last_batch_read0;
+        if (n_records != b->last_batch_reads * origin->per_read) { set_error("first-seen order: insert the remainder of the batch whose tiles were inserted last"); return KATOME_E_ARG; }
+    } else {
+        origin->per_read = origin->windows / span; origin->read0 = b->reads_inserted;
+        if (origin->per_read == 0 || n_records % origin->per_read) { set_error("first-seen order: a batch must hold whole reads"); return KATOME_E_ARG; }
     }
     return KATOME_OK;
 }
 
-// First-seen order, reads of varying length: the levels counted by sorting, the batches' records kept aside with delta tags
-// (seen_tag.h).  KATOME_SEEN_VAR_SORTED=1 switches it on; off, such a build counts every level in the tables
-static bool seen_var_sorted() { static const bool on = env_flag("KATOME_SEEN_VAR_SORTED", false); return on; }
-// how the builder's tagged records spell their two numbers
-static SeenTag builder_tag(const katome_builder* b) {
-    return b->seen_delta ? SeenTag::by_delta() : SeenTag::fixed(2ull * (b->seen_read_len - b->s.k + 1));
+// ---- may a batch's windows wait aside (katome_builder::rest) instead of going into the k-mer table? -----------------------------
+// default numbering: the windows left over after a batch's tiles
+static bool keeps_rest_plain(const katome_builder* b, const uint32_t* d_weights) {
+    return !b->first_seen && !d_weights && (b->tiles_ready || b->tile_recs.n) && !b->table_ready && !b->rest.closed && b->nw <= 2 && sorted_count_mode();
 }
-
-// how many valid records wait in b->rest_k (the device cursor; b->rest_n counts what was handed over, skipped reads included)
-static int rest_valid(katome_builder* b, uint64_t* n, hipStream_t stream) {
-    *n = 0;
-    if (!b->rest_n || !b->rest_count.p) return KATOME_OK;
-    KCHECK_HIP(hipMemcpyAsync(n, b->rest_count.p, 8, hipMemcpyDeviceToHost, stream));
-    KCHECK_HIP(hipStreamSynchronize(stream));
-    return KATOME_OK;
+// first-seen order, reads of one length: the windows after the batch's tiles wait as tagged records (slot_bits.h, seen_pack)
+static bool keeps_rest_seen_fixed(const katome_builder* b, const uint32_t* d_weights, uint64_t n_records) {
+    return b->first_seen && b->rem_pending && !d_weights && !b->var_prefix && !b->var_seq_base && (b->tiles_ready || b->tile_recs.n) && !b->table_ready && !b->rest.closed &&
+           b->nw <= 2 && sorted_count_mode() && b->seen_read_len >= b->s.k && 2ull * (b->seen_read_len - b->s.k + 1) <= 0xFFFFu &&
+           b->last_batch_read0 + b->last_batch_reads < (1ull << 32) && n_records == b->last_batch_reads * b->rem_per_read;
 }
-static void rest_reset(katome_builder* b) { b->rest_k.release(); b->rest_count.release(); b->rest_n = b->rest_cap = 0; }
-
-int flush_rest(katome_builder* b, hipStream_t stream) {
-    uint64_t n_valid = 0;
-    KCHECK(rest_valid(b, &n_valid, stream));
-    if (n_valid && b->first_seen) {            // tagged records: back into keys + their two sequence numbers for the table
-        DevBuf keys(stream), pairs(stream);
-        KCHECK(keys.alloc(n_valid * 8 * b->nw + 16)); KCHECK(pairs.alloc(n_valid * 16 + 16));
-        KCHECK(table_tagged_to_pairs(b->rest_k.as<u64>(), n_valid, b->nw, builder_tag(b), keys.as<u64>(), pairs.as<u64>(), stream));
-        SeenOrigin origin;
-        origin.pairs = pairs.as<u64>(); origin.rc = b->rc;
-        KCHECK(builder_insert(b, b->table, b->table_ready, b->nw, b->s.table_slots_hint, keys.as<u64>(), nullptr, n_valid, &origin, PH_INSERT, stream));
-    } else if (n_valid) {
-        KCHECK(insert_plain(b, b->rest_k.as<u64>(), nullptr, n_valid, stream));
-    }
-    rest_reset(b);
-    b->rest_closed = true;
-    return KATOME_OK;
-}
-
-// KATOME_SORTED_FAIL=mid|last: that level's counting by sorting reports a group too large -- tests of the way back into the tables
-bool sorted_fail(const char* level) {
-    static const char* at = getenv("KATOME_SORTED_FAIL");
-    return at && !strcmp(at, level);
-}
-// KATOME_SORTED_TILES: 2 (default) both tile levels are counted by sorting -- the big tiles' records are kept aside batch by batch
-// (two-word tiles of one-word k-mers, either numbering; anything else takes the table) --, 1 the big tiles in their table and only
-// the mid tiles by sorting, out of that table; 0 both tile levels in tables.  C3 by packed key: 200 / 210 / 239 ms per build.
-int sorted_tiles_mode() {
-    static const int mode = env_int("KATOME_SORTED_TILES", 2);
-    return mode;
-}
-
-// Tile / k-mer shapes whose levels are all counted by sorting: tiles of two or three words (32..95 bases) over k-mers of one or two
-// (round 4: three-word tiles -- every k from 32 to 63 at 150 bp, the reference's example k = 40 and BASELINE's k = 63 -- and two-word
-// tiles of two-word k-mers); in the reference's numbering two-word tiles of one-word k-mers (the tagged kernels' shapes).
-// KATOME_SORTED_WIDE=0: the round-3 rule (A/B against the tables).
-bool tile_recs_shape(uint32_t nwt, uint32_t nw, bool first_seen) {
-    static const bool wide = env_flag("KATOME_SORTED_WIDE", true);
-    if (first_seen || !wide) return nwt == 2 && nw == 1;
-    return (nwt == 2 || nwt == 3) && nw <= 2 && nw <= nwt;
-}
-
-// the tile records kept aside (builder.h) go into the tile table after all: another consumer wants the table, or the sorted
-// counting of the tiles gave up
-int tile_recs_valid(katome_builder* b, uint64_t* n, hipStream_t stream) {
-    *n = 0;
-    if (b->tile_recs_exact) { *n = b->tile_recs_n; return KATOME_OK; }       // (every record kept so far was valid: nothing to ask the device)
-    if (!b->tile_recs_n || !b->tile_recs_count.p) return KATOME_OK;
-    KCHECK_HIP(hipMemcpyAsync(n, b->tile_recs_count.p, 8, hipMemcpyDeviceToHost, stream));
-    KCHECK_HIP(hipStreamSynchronize(stream));
-    return KATOME_OK;
-}
-// no tile records are kept from here on (they were counted, or went into the tile table)
-static void close_tile_recs(katome_builder* b) {
-    b->tile_recs.release(); b->tile_recs_count.release(); b->tile_recs_n = b->tile_recs_cap = 0;
-    b->tile_recs_hist.release(); b->tile_recs_hist_ok = false;
-    b->tile_recs_exact = false; b->tile_recs_closed = true;
-}
-int flush_tile_recs(katome_builder* b, hipStream_t stream) {
-    if (b->tile_recs_n) {
-        const uint32_t nwt = (uint32_t)key_words_for_k(b->s.k + b->span - 1);
-        uint64_t n = 0;
-        KCHECK(tile_recs_valid(b, &n, stream));
-        b->tile_recs_n = 0;
-        if (b->first_seen && n) {            // tagged records: back into keys + their two sequence numbers for the table
-            DevBuf keys(stream), pairs(stream);
-            KCHECK(keys.alloc(n * 8 * nwt + 16)); KCHECK(pairs.alloc(n * 16 + 16));
-            KCHECK(table_tagged_to_pairs(b->tile_recs.as<u64>(), n, nwt, builder_tag(b), keys.as<u64>(), pairs.as<u64>(), stream));
-            b->tile_recs.release();
-            SeenOrigin origin;
-            origin.pairs = pairs.as<u64>(); origin.rc = b->rc;
-            KCHECK(builder_insert(b, b->tiles, b->tiles_ready, nwt, b->s.table_slots_hint / 4, keys.as<u64>(), nullptr, n, &origin, PH_INSERT_TILES, stream));
-        } else
-        for (uint64_t done = 0; done < n;) {
-            uint64_t room = 0;
-            KCHECK(ensure_table(b, b->tiles, b->tiles_ready, nwt, b->s.table_slots_hint / 4, n - done, &room, stream));
-            const uint64_t m = std::min(n - done, room);
-            PhaseScope ps(b->prof, PH_INSERT_TILES, stream);
-            KCHECK(table_insert(b->tiles, b->tile_recs.as<u64>() + done * nwt, nullptr, m, stream, nullptr));
-            done += m;
-        }
-    }
-    close_tile_recs(b);
-    return KATOME_OK;
-}
-
-// room for n more tile records behind those kept aside; *ok = false: no room (or over the limit) -- what was kept has gone into the
-// tile table and later batches follow it there
-static int reserve_tile_recs(katome_builder* b, uint64_t n, uint32_t nwt, bool* ok, hipStream_t stream) {
-    *ok = false;
-    if (b->tile_recs_n + n > b->tile_recs_cap) {
-        size_t free_b = 0, total_b = 0;
-        KCHECK_HIP(hipMemGetInfo(&free_b, &total_b));
-        uint64_t pool[3] = {0, 0, 0};
-        dev_cache_stats(b->s.device, pool);
-        free_b += pool[1];                         // (what the caching allocator holds idle is as good as free)
-        // room for sixteen batches like this one to begin with (a build is a dozen batches), doubled when that was too little
-        const uint64_t want = std::max<uint64_t>(b->tile_recs_cap ? b->tile_recs_cap * 2 : n * 16, b->tile_recs_n + n);
-        // (the counting needs the records twice more -- the passes' scratch and the next level)
-        // (KATOME_TILE_RECS_LIMIT: no more records than this are kept aside -- tests; by default a sixth of the card's memory)
-        static const uint64_t limit = getenv("KATOME_TILE_RECS_LIMIT") ? strtoull(getenv("KATOME_TILE_RECS_LIMIT"), nullptr, 10) : ~0ull;
-        if (b->tile_recs_n + n > limit || want * 8 * nwt * 3 > free_b + b->tile_recs_cap * 8 * nwt || want * 8 * nwt > total_b / 6) {
-            KCHECK(flush_tile_recs(b, stream));
-            return KATOME_OK;
-        }
-        DevBuf grown(stream);
-        if (grown.alloc(want * 8 * nwt + 16) != KATOME_OK) {          // (no room after all: the table takes over)
-            KCHECK(flush_tile_recs(b, stream));
-            return KATOME_OK;
-        }
-        if (b->tile_recs_n) KCHECK_HIP(hipMemcpyAsync(grown.p, b->tile_recs.p, b->tile_recs_n * 8 * nwt, hipMemcpyDeviceToDevice, stream));
-        const size_t grown_bytes = grown.bytes;
-        b->tile_recs.adopt(grown.take(), grown_bytes);
-        b->tile_recs.stream = stream;
-        b->tile_recs_cap = want;
-    }
-    if (b->tile_recs_n == 0) b->tile_recs_exact = true;          // (nothing kept yet: the host knows the count until a batch with holes comes)
-    *ok = true;
-    return KATOME_OK;
-}
-
-// the device cursor of the tile records, ready for a kernel that appends behind it
-static int tile_recs_cursor(katome_builder* b, hipStream_t stream) {
-    if (!b->tile_recs_count.p) KCHECK(b->tile_recs_count.alloc(8, stream));
-    if (b->tile_recs_exact) {
-        // from here on only the device knows how many of the records handed over were valid: its cursor starts at what the host knew
-        const uint64_t start = b->tile_recs_n;
-        KCHECK_HIP(hipMemcpyAsync(b->tile_recs_count.p, &start, 8, hipMemcpyHostToDevice, stream));
-        KCHECK_HIP(hipStreamSynchronize(stream));
-        b->tile_recs_exact = false;
-    }
-    return KATOME_OK;
-}
-
-// a batch's tiles kept aside as records; *kept = false: they go into the tile table
-int keep_tile_recs(katome_builder* b, const uint64_t* d_records, uint64_t n, uint32_t nwt, bool* kept, hipStream_t stream) {
-    *kept = false;
-    b->tile_recs_hist_ok = false;          // (records that nobody counted as they were written)
-    bool ok = false;
-    // (first-seen order: a record is kept with its tag -- read << 32 | number of its first window << 16 | of its reverse complement's)
-    const uint32_t words = nwt + (b->first_seen ? 1 : 0);
-    KCHECK(reserve_tile_recs(b, n, words, &ok, stream));
-    if (!ok) return KATOME_OK;
-    KCHECK(tile_recs_cursor(b, stream));
-    if (b->first_seen) {
-        const uint32_t W = b->seen_read_len - b->s.k + 1;
-        KCHECK(table_keep_rest(d_records, n, nwt, true, b->reads_inserted, W / b->span, 0, 2 * W, b->tile_recs.as<u64>(), b->tile_recs_count.as<u64>(), stream,
-                               b->span, b->span));
-    } else
-    KCHECK(table_keep_rest(d_records, n, nwt, false, 0, 1, 0, 0, b->tile_recs.as<u64>(), b->tile_recs_count.as<u64>(), stream));      // (the valid ones, behind the cursor)
-    b->tile_recs_n += n;
-    *kept = true;
-    return KATOME_OK;
-}
-
-// Device memory a counting level may plan with: what the driver has free plus what the library's cache holds idle
-// (KATOME_LEVEL_BUDGET: no more than this many bytes -- tests of the ways back into the tables at sizes the oracle can check)
-static uint64_t level_budget() {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return ~0ull; }
-    const uint64_t avail = (uint64_t)free_b + dev_cached_bytes();
-    const char* e = getenv("KATOME_LEVEL_BUDGET");
-    return e ? std::min<uint64_t>(avail, strtoull(e, nullptr, 10)) : avail;
-}
-// a level counted by sorting holds its records, the partition passes' scratch of the same size and an output list sized for the case
-// that no record repeats: three times the records (oriented edges: the output twice over)
-static bool level_fits(uint64_t n_records, uint32_t key_words, bool oriented, const char* what) {
-    const char* sl = getenv("KATOME_LEVEL_SLACK");           // (room left for everything else: group index, cursors, the allocator's rounding)
-    const uint64_t slack = sl ? strtoull(sl, nullptr, 10) : (256ull << 20);
-    // (+ a byte per record where the partition passes keep a digit stream -- records of two or three words -- and a byte per oriented
-    // edge for S2's first digits)
-    const uint64_t digits = (dev_digit_stream_pays(key_words) ? 1 : 0) + (oriented ? 1 : 0);
-    const uint64_t pair = 8ull * key_words + 4, need = n_records * (pair * (oriented ? 4 : 3) + digits) + slack, have = level_budget();
-    if (need <= have) return true;
-    if (getenv("KATOME_LEVEL_TRACE"))
-        fprintf(stderr, "[katome levels] %s: %llu records need %.1f GiB by sorting, %.1f GiB available -- this level and those below are counted in tables\n",
-                what, (unsigned long long)n_records, need / 1073741824.0, have / 1073741824.0);
-    return false;
-}
-// a list that was sized for its records and holds far fewer keys gives the room behind them back (thin coverage: the room is needed).
-// The list already sits at the front of its block, so the block is trimmed where it lies (DevBuf::trim); KATOME_TRIM_IN_PLACE=0: the
-// list moves into a buffer of its own size instead, as it did before the allocator could trim
-static int shrink_to_fit(DevBuf& buf, size_t used, hipStream_t stream) {
-    if (!buf.p || buf.bytes < (1ull << 30) || used * 2 > buf.bytes) return KATOME_OK;
-    static const bool in_place = env_flag("KATOME_TRIM_IN_PLACE", true);
-    if (in_place) {
-        const size_t before = buf.bytes;
-        if (buf.trim(used + 64) && getenv("KATOME_LC_TRACE"))
-            fprintf(stderr, "[levels] list trimmed in place: %zu -> %zu bytes\n", before, buf.bytes);
-        return KATOME_OK;
-    }
-    DevBuf small(stream);
-    if (small.alloc(used + 64) != KATOME_OK) return KATOME_OK;          // (no room for the copy: the list stays where it is)
-    if (used) KCHECK_HIP(hipMemcpyAsync(small.p, buf.p, used, hipMemcpyDeviceToDevice, stream));
-    const size_t n = small.bytes;
-    buf.adopt(small.take(), n);
-    buf.stream = stream;
-    return KATOME_OK;
-}
-
-// The k-mer level of an input whose tiles hardly repeat, when its records do not fit the card at once (thin coverage at hundreds of
-// millions of reads): the last tile level's list is taken in P parts -- a part's tiles -> their k-mer records -> counted by sorting,
-// strands not yet told apart, into a list of (canonical k-mer, count) --, and the parts' lists, put behind one another, ARE weighted
-// k-mer records again: the caller counts them once more, as it would have counted the level's records, and has its edges.  A k-mer
-// that several parts hold is counted 1 + 1/P times over instead of once; the alternative is the k-mer table at a third of the speed
-// (profiles/r04_coverage_sweep.jsonl).  KATOME_E_UNSUPPORTED: not this way either (the caller goes on in tables; the list is untouched).
-// KATOME_LEVEL_PARTS=0: never
-static int kmer_records_in_parts(katome_builder* b, const uint64_t* lk, const uint32_t* lw, uint64_t n_last, uint32_t last_bases, uint32_t last_span,
-                                 DevBuf& keys, DevBuf& weights, uint64_t* n_records, uint64_t extra_room, hipStream_t stream) {
-    static const bool on = env_flag("KATOME_LEVEL_PARTS", true);
-    if (!on) return KATOME_E_UNSUPPORTED;
-    const uint32_t nw = b->nw, k = b->s.k, nwl = (uint32_t)key_words_for_k(last_bases);
-    const uint64_t pair = 8ull * nw + 4, total = n_last * last_span, have = level_budget();
-    const char* sl = getenv("KATOME_LEVEL_SLACK");
-    const uint64_t slack = sl ? strtoull(sl, nullptr, 10) : (256ull << 20);
-    // a part's records, the passes' scratch and its list (three times the records) in half of what is there; the other half holds the lists
-    uint32_t P = 2;
-    const uint64_t digits = dev_digit_stream_pays(nw) ? 1 : 0;          // (the passes' digit stream, where records of this width keep one)
-    while (P <= 64 && (total / P + last_span) * (pair * 3 + digits) + slack > have / 2) P *= 2;
-    if (P > 64 || n_last < P) return KATOME_E_UNSUPPORTED;
-    if (getenv("KATOME_LEVEL_TRACE")) fprintf(stderr, "[katome levels] k-mers: counted in %u parts of %llu records\n", P, (unsigned long long)(total / P));
-    PhaseScope ps(b->prof, PH_EXPAND_TILES, stream);
-    std::unique_ptr<DevBuf[]> pk(new DevBuf[P]), pw(new DevBuf[P]);
-    for (uint32_t p = 0; p < P; ++p) { pk[p].stream = stream; pw[p].stream = stream; }
-    std::vector<uint64_t> pn(P, 0);
-    uint64_t n_p = 0;
-    for (uint32_t p = 0; p < P; ++p) {
-        const uint64_t lo = n_last * p / P, hi = n_last * (p + 1) / P;
-        if (hi == lo) continue;
-        DevBuf rk(stream), rw(stream);
-        uint64_t n_rec = 0, ne = 0, nd = 0;
-        int rc = table_list_to_records(lk + lo * nwl, lw + lo, hi - lo, last_bases, k, last_span, 1, b->rc, rk, rw, &n_rec, stream, 0, nullptr);
-        if (rc == KATOME_OK) rc = records_to_edges_sorted(rk, rw, n_rec, k, false, 0, pk[p], pw[p], &ne, &nd, stream);
-        if (rc == KATOME_E_OOM || rc == KATOME_E_UNSUPPORTED) return KATOME_E_UNSUPPORTED;          // (less room than was planned with: the tables)
-        if (rc != KATOME_OK) return rc;
-        rk.release(); rw.release();
-        KCHECK(shrink_to_fit(pk[p], ne * 8 * nw, stream)); KCHECK(shrink_to_fit(pw[p], ne * 4, stream));
-        pn[p] = ne; n_p += ne;
-    }
-    if (!level_fits(n_p + extra_room, nw, b->rc, "k-mers (the parts' lists)")) return KATOME_E_UNSUPPORTED;
-    if (keys.alloc((n_p + extra_room + 1) * 8 * nw, stream) != KATOME_OK || weights.alloc((n_p + extra_room + 1) * 4, stream) != KATOME_OK) {
-        keys.release(); weights.release();
-        return KATOME_E_UNSUPPORTED;
-    }
-    uint64_t at = 0;
-    for (uint32_t p = 0; p < P; ++p) {
-        if (!pn[p]) continue;
-        KCHECK_HIP(hipMemcpyAsync(keys.as<u64>() + at * nw, pk[p].p, pn[p] * 8 * nw, hipMemcpyDeviceToDevice, stream));
-        KCHECK_HIP(hipMemcpyAsync(weights.as<u32>() + at, pw[p].p, pn[p] * 4, hipMemcpyDeviceToDevice, stream));
-        at += pn[p];
-        pk[p].release(); pw[p].release();
-    }
-    *n_records = n_p;
-    return KATOME_OK;
-}
-
-// The tile records kept aside -> the (k-mer, count) records of the last tile level, every level counted by sorting (DESIGN.md
-// section 4): records -> two hash passes -> counted in LDS -> a compact list of distinct tiles with their counts; the next level's
-// records are cut out of that list.  KATOME_OK: keys / weights hold *n_records records (room for extra_room more behind them) and
-// the tile records are gone.  KATOME_E_UNSUPPORTED: a level could not be counted this way (or there is nothing to count) -- the
-// tile records, or the distinct big tiles with their counts, are in the tile table instead and the caller goes on in tables.
-int tile_recs_to_kmer_records(katome_builder* b, DevBuf& keys, DevBuf& weights, uint64_t* n_records, uint64_t extra_room, hipStream_t stream,
-                              DevBuf* first_counts, bool rep, RecordSource* src) {
-    *n_records = 0;
-    const uint32_t k = b->s.k, span = b->span, tile_bases = k + span - 1, nwt = (uint32_t)key_words_for_k(tile_bases);
-    b->span2 = mid_span(span);
-    DevBuf t1k(stream), t1w(stream);
-    uint64_t n1 = 0, d1 = 0;
-    int rc;
-    {
-        PhaseScope ps(b->prof, PH_INSERT_TILES, stream);
-        TileLevelScope tl;
-        DevBuf ones(stream);          // (stays empty: records without weights count once each, and the passes move 16 bytes a record, not 20)
-        uint64_t n = 0;
-        KCHECK(tile_recs_valid(b, &n, stream));
-        // (the whole array is ordered in this one call: the counts the extraction left, where they cover it, are its first pass's)
-        u32* const first = b->tile_recs_hist_ok && n == b->tile_recs_n && nwt == 2 ? b->tile_recs_hist.as<u32>() : nullptr;
-        rc = n ? records_to_edges_sorted(b->tile_recs, ones, n, tile_bases, false, 0, t1k, t1w, &n1, &d1, stream, nullptr, first)
-               : KATOME_E_UNSUPPORTED;                          // (every read was skipped: nothing to count)
-        b->tile_recs_hist_ok = false;                           // (the pass worked in them: prefixes now)
-        if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
-    }
-    if (rc == KATOME_E_UNSUPPORTED) {
-        KCHECK(flush_tile_recs(b, stream));          // (the records are all still there, in another order: into the table with them)
-        return KATOME_E_UNSUPPORTED;
-    }
-    close_tile_recs(b);
-    b->stat_tiles = n1; b->stat_tile_slots = 0; b->stat_tiles2 = 0; b->stat_tile2_slots = 0;
-    KCHECK(shrink_to_fit(t1k, n1 * 8 * nwt, stream)); KCHECK(shrink_to_fit(t1w, n1 * 4, stream));
-    const uint64_t* lk = t1k.as<u64>(); const uint32_t* lw = t1w.as<u32>();
-    uint64_t n_last = n1; uint32_t last_bases = tile_bases, last_span = span;
-    DevBuf t2k(stream), t2w(stream);
-    if (b->span2 && n1) {
-        const uint32_t kk2 = k + b->span2 - 1, n_sub = span / b->span2;
-        PhaseScope ps(b->prof, PH_EXPAND_MID, stream);
-        TileLevelScope tl;
-        DevBuf mk(stream), mw(stream);
-        uint64_t n_mid = 0, n2 = 0, d2 = 0;
-        DevBuf mid_counts(stream);        // (the first partition pass's digit counts per tile, made while the records are written)
-        RecordSource mid_src;             // (... or instead of them: that pass then cuts the records out of the list, which stays until the level is counted)
-        // (input whose tiles hardly repeat -- thin coverage -- multiplies records level by level: a level that would not fit the card
-        // by sorting is counted in a table, which takes its upserts in slot ranges of any size)
-        if (sorted_fail("mid") || !level_fits(n1 * n_sub, (uint32_t)key_words_for_k(kk2), false, "mid tiles")) rc = KATOME_E_UNSUPPORTED;
-        else {
-            KCHECK(table_list_to_records(lk, lw, n1, tile_bases, kk2, n_sub, b->span2, b->rc, mk, mw, &n_mid, stream, 0, &mid_counts, false, &mid_src));
-            rc = records_to_edges_sorted(mk, mw, n_mid, kk2, false, 0, t2k, t2w, &n2, &d2, stream, nullptr, mid_counts.as<u32>(), nullptr, &mid_src);
-        }
-        if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
-        if (rc == KATOME_E_UNSUPPORTED) {
-            // the mid tiles cannot be counted this way: the distinct big tiles go into the tile table with their counts, and the build
-            // goes on from there as if they had been counted in it
-            mk.release(); mw.release(); t2k.release(); t2w.release();
-            KCHECK(builder_insert(b, b->tiles, b->tiles_ready, nwt, b->s.table_slots_hint / 4, t1k.as<u64>(), t1w.as<u32>(), n1, nullptr, PH_INSERT_TILES, stream));
-            return KATOME_E_UNSUPPORTED;
-        }
-        b->stat_tiles2 = n2;
-        t1k.release(); t1w.release();
-        mk.release(); mw.release();
-        KCHECK(shrink_to_fit(t2k, n2 * 8 * key_words_for_k(kk2), stream)); KCHECK(shrink_to_fit(t2w, n2 * 4, stream));
-        lk = t2k.as<u64>(); lw = t2w.as<u32>(); n_last = n2; last_bases = kk2; last_span = b->span2;
-    }
-    if (n_last && !level_fits(n_last * last_span + extra_room, b->nw, b->rc, "k-mers")) {
-        // in parts first (kmer_records_in_parts): their lists stand in for the level's records
-        if (first_counts) first_counts->release();
-        const int prc = kmer_records_in_parts(b, lk, lw, n_last, last_bases, last_span, keys, weights, n_records, extra_room, stream);
-        if (prc == KATOME_OK && rep && b->rc) return table_orient_records(keys.as<u64>(), *n_records, k, true, stream);
-        if (prc != KATOME_E_UNSUPPORTED) return prc;
-        keys.release(); weights.release(); *n_records = 0;
-        // the k-mer level would not fit by sorting: the distinct tiles of the last level go into their table with their counts (the mid
-        // tiles into `tiles2`, with nothing in `tiles`: expand_to_last_level's "done before" state) and the k-mers are counted in theirs
-        const uint32_t nwl = (uint32_t)key_words_for_k(last_bases);
-        if (b->span2) {
-            KCHECK(builder_insert(b, b->tiles2, b->tiles2_ready, nwl, std::max<uint64_t>(b->s.table_slots_hint / 4, n_last * 2), lk, lw, n_last, nullptr, PH_EXPAND_MID, stream));
-            b->tiles_ready = true;                   // (with b->tiles empty)
-            b->stat_tile2_slots = b->tiles2.cap;
-        } else {
-            KCHECK(builder_insert(b, b->tiles, b->tiles_ready, nwl, b->s.table_slots_hint / 4, lk, lw, n_last, nullptr, PH_INSERT_TILES, stream));
-        }
-        return KATOME_E_UNSUPPORTED;
-    }
-    PhaseScope ps(b->prof, PH_EXPAND_TILES, stream);
-    // (first_counts: for a caller that orders exactly these records by the whole k-mer's hash next -- table_list_to_records)
-    KCHECK(table_list_to_records(lk, lw, n_last, last_bases, k, last_span, 1, b->rc, keys, weights, n_records, stream, extra_room, first_counts, rep, src));
-    if (src && src->pending) {
-        // the list has to outlive the first pass, which these locals do not: the source takes it and gives it up right after that pass
-        DevBuf& ok = b->span2 && t2k.p ? t2k : t1k; DevBuf& ow = b->span2 && t2w.p ? t2w : t1w;
-        src->own_tiles.stream = src->own_counts.stream = stream;
-        const size_t kbytes = ok.bytes, wbytes = ow.bytes;
-        src->own_tiles.adopt(ok.take(), kbytes); src->own_counts.adopt(ow.take(), wbytes);
-    }
-    return KATOME_OK;
-}
-
-// The k-mer level counted in order (lds_count.hip, lds_count_ordered_kernel): half of the edges leave the count sorted, the edge sort takes
-// only the reverse complements and one merge (half_sort_finish).  Where lds_count_packed_kernel would run: one-word k-mers of odd k
-// (k >= 9: 16 key bits name the group) or one strand, default numbering, no owner split.  KATOME_EDGE_HALF_SORT=0: the full edge sort
-static bool half_sort_route(const katome_builder* b) {
-    static const bool on = env_flag("KATOME_EDGE_HALF_SORT", true);
-    const uint32_t k = b->s.k;
-    return on && b->nw == 1 && !b->first_seen && k >= 9 && ((k & 1) || !b->rc);
-}
-
-// room for n more left-over windows behind those kept aside, and their cursor; *ok = false: too many -- what was kept has gone into
-// the table and these follow it there
-static int reserve_rest(katome_builder* b, uint64_t n, bool* ok, hipStream_t stream) {
-    *ok = false;
-    const uint32_t words = b->nw + (b->first_seen ? 1 : 0);          // (first-seen order: tagged records)
-    if (b->rest_n + n > b->rest_cap) {
-        size_t free_b = 0, total_b = 0;
-        KCHECK_HIP(hipMemGetInfo(&free_b, &total_b));
-        const uint64_t want = std::max<uint64_t>(b->rest_n + n, b->rest_cap * 2);
-        // (they are sorted with the tiles' k-mers later: past an eighth of the card they stop being a side matter)
-        if ((want + b->rest_n) * 8 * words > free_b / 2 || want * 8 * words > total_b / 8) { KCHECK(flush_rest(b, stream)); return KATOME_OK; }
-        DevBuf grown(stream);
-        KCHECK(grown.alloc(want * 8 * words + 16));
-        if (b->rest_n) KCHECK_HIP(hipMemcpyAsync(grown.p, b->rest_k.p, b->rest_n * 8 * words, hipMemcpyDeviceToDevice, stream));
-        const size_t grown_bytes = grown.bytes;
-        b->rest_k.adopt(grown.take(), grown_bytes);
-        b->rest_k.stream = stream;
-        b->rest_cap = want;
-    }
-    if (!b->rest_count.p) { KCHECK(b->rest_count.alloc(8, stream)); KCHECK_HIP(hipMemsetAsync(b->rest_count.p, 0, 8, stream)); }
-    *ok = true;
-    return KATOME_OK;
-}
-
-// keeps a batch's left-over windows aside (see builder.h); *kept = false: they have to go into the table
-static int keep_rest(katome_builder* b, const uint64_t* d_records, uint64_t n, bool* kept, hipStream_t stream) {
-    *kept = false;
-    bool ok = false;
-    KCHECK(reserve_rest(b, n, &ok, stream));
-    if (!ok) return KATOME_OK;
-    KCHECK(table_keep_rest(d_records, n, b->nw, b->first_seen, b->last_batch_read0, b->rem_per_read, b->rem_win0,
-                           b->first_seen ? 2u * (b->seen_read_len - b->s.k + 1) : 0u, b->rest_k.as<u64>(), b->rest_count.as<u64>(), stream));
-    b->rest_n += n;
-    *kept = true;
-    return KATOME_OK;
-}
-
-// ---- first-seen order, reads of varying length: a batch's records kept aside with delta tags (KATOME_SEEN_VAR_SORTED) ----------
-// Does every read of the batch just extracted pack (seen_tag.h)?  No read of more than DELTA_MAX_WINDOWS windows -- |Q - P| < 2 W for
-// every record cut from a read of W windows, and for the minima of a key --, and numbers below DELTA_P_LIMIT.
-// Asked once per batch, not per insert (a batch's tiles and its left-over windows share one prefix): the answer is kept under the
-// prefix's address AND the batch's sequence base.  The address alone would not do -- a caller may hand the next batch's prefix in at
-// the same address --, the base tells batches apart because every batch holds a read, a read a window, and the base moves on by twice
-// the batch's windows when the batch is closed.
-static int var_batch_packs(katome_builder* b, bool* ok, hipStream_t stream) {
-    if (b->var_checked != b->var_prefix || b->var_checked_base != b->var_seq_base) {
-        uint64_t max_w = 0;
-        KCHECK(table_max_windows(b->var_prefix, b->var_reads, &max_w, stream));
-        b->var_checked = b->var_prefix; b->var_checked_base = b->var_seq_base;
-        b->var_checked_ok = max_w <= DELTA_MAX_WINDOWS && b->var_seq_base + 2 * b->var_windows < DELTA_P_LIMIT;
-    }
-    *ok = b->var_checked_ok;
-    return KATOME_OK;
-}
-// a batch that does not pack closes the route: what was kept goes into the tables with its pairs, and the build goes on there
-static int close_seen_var(katome_builder* b, hipStream_t stream) {
-    if (!b->tile_recs_closed) KCHECK(flush_tile_recs(b, stream));
-    if (!b->rest_closed) KCHECK(flush_rest(b, stream));
-    return KATOME_OK;
-}
-// the tiles of the last katome_dev_extract_var_tiles call behind the tile records kept so far; *kept = false: into the tile table
-static int keep_var_tiles(katome_builder* b, const uint64_t* d_records, uint64_t n, uint32_t nwt, bool* kept, hipStream_t stream) {
-    *kept = false;
-    bool ok = false;
-    KCHECK(var_batch_packs(b, &ok, stream));
-    if (!ok) return close_seen_var(b, stream);
-    b->tile_recs_hist_ok = false;
-    KCHECK(reserve_tile_recs(b, n, nwt + 1, &ok, stream));
-    if (!ok) return KATOME_OK;
-    KCHECK(tile_recs_cursor(b, stream));
-    KCHECK(table_keep_var_tagged(d_records, n, nwt, b->rc, b->var_prefix, b->var_rec_prefix, b->var_reads, 1, b->var_span, b->var_seq_base,
-                                 b->tile_recs.as<u64>(), b->tile_recs_count.as<u64>(), stream));
-    b->tile_recs_n += n;
-    b->seen_delta = true;
-    *kept = true;
-    return KATOME_OK;
-}
-// ... and its windows (all of them, or those after the last whole tile) behind the left-over windows; *kept = false: into the k-mer table
-static int keep_var_rest(katome_builder* b, const uint64_t* d_records, uint64_t n, bool* kept, hipStream_t stream) {
-    *kept = false;
-    bool ok = false;
-    KCHECK(var_batch_packs(b, &ok, stream));
-    if (!ok) return close_seen_var(b, stream);
-    KCHECK(reserve_rest(b, n, &ok, stream));
-    if (!ok) return KATOME_OK;
-    KCHECK(table_keep_var_tagged(d_records, n, b->nw, b->rc, b->var_prefix, b->var_rec_prefix, b->var_reads, b->var_mode, b->var_span, b->var_seq_base,
-                                 b->rest_k.as<u64>(), b->rest_count.as<u64>(), stream));
-    b->rest_n += n;
-    b->seen_delta = true;
-    *kept = true;
-    return KATOME_OK;
+// ... reads of varying length: the batch's windows -- all of them, or those after its tiles -- wait as delta-tagged records (seen_tag.h)
+static bool keeps_rest_seen_var(const katome_builder* b, const uint32_t* d_weights, uint64_t n_records) {
+    return b->first_seen && b->var_prefix && seen_var_sorted() && !d_weights && b->var_mode != 1 && n_records == b->var_records && !b->table_ready &&
+           !b->rest.closed && !b->direct_edges && b->nw <= 2 && sorted_count_mode();
 }
 
 extern "C" {
@@ -913,33 +466,24 @@ int katome_dev_insert_weighted(katome_builder* b, const uint64_t* d_records, con
     KCHECK_HIP(hipSetDevice(b->s.device));
     if (b->edges_ready) { set_error("builder already finalized"); return KATOME_E_ARG; }
     if (n_records == 0) {
-        if (b->first_seen && b->var_prefix && b->var_mode != 1 && b->var_records == 0) {   // a batch whose reads are all whole tiles
-            b->var_seq_base += 2 * b->var_windows;
-            b->var_prefix = b->var_rec_prefix = nullptr; b->var_reads = b->var_windows = 0;
-        }
+        if (b->first_seen && b->var_prefix && b->var_mode != 1 && b->var_records == 0) close_var_batch(b);   // a batch whose reads are all whole tiles
         return KATOME_OK;
     }
-    if (!b->first_seen && !d_weights && (b->tiles_ready || b->tile_recs_n) && !b->table_ready && !b->rest_closed && b->nw <= 2 && sorted_count_mode()) {
+    if (keeps_rest_plain(b, d_weights)) {
         bool kept = false;
         KCHECK(keep_rest(b, d_records, n_records, &kept, stream));
         if (kept) return KATOME_OK;
     }
-    // first-seen order, reads of one length: the windows after the batch's tiles wait as tagged records (slot_bits.h, seen_pack)
-    if (b->first_seen && b->rem_pending && !d_weights && !b->var_prefix && !b->var_seq_base && (b->tiles_ready || b->tile_recs_n) && !b->table_ready && !b->rest_closed &&
-        b->nw <= 2 && sorted_count_mode() && b->seen_read_len >= b->s.k && 2ull * (b->seen_read_len - b->s.k + 1) <= 0xFFFFu &&
-        b->last_batch_read0 + b->last_batch_reads < (1ull << 32) && n_records == b->last_batch_reads * b->rem_per_read) {
+    if (keeps_rest_seen_fixed(b, d_weights, n_records)) {
         bool kept = false;
         KCHECK(keep_rest(b, d_records, n_records, &kept, stream));
         if (kept) { b->rem_pending = false; return KATOME_OK; }
     }
-    // ... reads of varying length: the batch's windows -- all of them, or those after its tiles -- wait as delta-tagged records (seen_tag.h)
-    if (b->first_seen && b->var_prefix && seen_var_sorted() && !d_weights && b->var_mode != 1 && n_records == b->var_records && !b->table_ready &&
-        !b->rest_closed && !b->direct_edges && b->nw <= 2 && sorted_count_mode()) {
+    if (keeps_rest_seen_var(b, d_weights, n_records)) {
         bool kept = false;
         KCHECK(keep_var_rest(b, d_records, n_records, &kept, stream));
         if (kept) {
-            b->var_seq_base += 2 * b->var_windows;          // the batch is complete, as below
-            b->var_prefix = b->var_rec_prefix = nullptr; b->var_reads = b->var_windows = 0;
+            close_var_batch(b);
             b->rem_pending = false;
             return KATOME_OK;
         }
@@ -951,22 +495,8 @@ int katome_dev_insert_weighted(katome_builder* b, const uint64_t* d_records, con
     // measured on MI355X the insert kernel is bound by atomic throughput, not by where the slots live.
     const uint64_t* k_in = d_records; const uint32_t* w_in = d_weights;
     SeenOrigin origin;
-    if (b->first_seen && b->var_prefix) {
-        if (b->var_mode == 1 || n_records != b->var_records) { set_error("first-seen order: insert exactly the records the last katome_dev_extract_var* call produced"); return KATOME_E_ARG; }
-        origin.win_prefix = b->var_prefix; origin.n_reads = b->var_reads; origin.seq_base = b->var_seq_base; origin.rc = b->rc;
-        origin.rec_prefix = b->var_rec_prefix; origin.mode = b->var_mode; origin.span = b->var_span;
-    } else if (b->first_seen) {
-        if (b->var_seq_base) { set_error("first-seen order: fixed- and variable-length batches cannot be mixed in one build"); return KATOME_E_UNSUPPORTED; }
-        if (b->seen_read_len < b->s.k) { set_error("first-seen order: extract the records with this builder first"); return KATOME_E_ARG; }
-        origin.windows = b->seen_read_len - b->s.k + 1; origin.span = 1; origin.rc = b->rc;
-        if (b->rem_pending) {           // the windows after the tiles of the batch that was just inserted
-            origin.per_read = b->rem_per_read; origin.win0 = b->rem_win0; origin.read0 = b->last_batch_read0;
-            if (n_records != b->last_batch_reads * origin.per_read) { set_error("first-seen order: insert the remainder of the batch whose tiles were inserted last"); return KATOME_E_ARG; }
-        } else {
-            origin.per_read = origin.windows; origin.read0 = b->reads_inserted;
-            if (n_records % origin.per_read) { set_error("first-seen order: a batch must hold whole reads"); return KATOME_E_ARG; }
-        }
-    }
+    if (b->first_seen && b->var_prefix) KCHECK(var_origin(b, n_records, 0, 1, &origin));
+    else if (b->first_seen) KCHECK(fixed_origin(b, n_records, 1, b->rem_pending, &origin));
     const int passes = b->first_seen ? 0 : region_passes(b->table.cap * b->table.slot_bytes());
     if (passes > 0 && n_records >= (1u << 16)) {
         for (int i = 0; i < 2; ++i) {
@@ -986,8 +516,7 @@ int katome_dev_insert_weighted(katome_builder* b, const uint64_t* d_records, con
         done += n;
     }
     if (b->first_seen && origin.win_prefix) {
-        b->var_seq_base += 2 * b->var_windows;          // the batch is complete: its reads' windows, both strands
-        b->var_prefix = b->var_rec_prefix = nullptr; b->var_reads = b->var_windows = 0;
+        close_var_batch(b);
     } else if (b->first_seen && !b->rem_pending) {
         b->reads_inserted += n_records / origin.per_read;
     }
@@ -1004,30 +533,12 @@ static bool keeps_tile_recs(const katome_builder* b, uint32_t nwt) {
     // numbers themselves -- keep_var_tiles, which asks whether they pack.  One-word tiles too: short reads make short tiles)
     if (b->first_seen && (b->var_prefix || b->var_seq_base))
         return b->var_prefix && b->var_mode == 1 && seen_var_sorted() && !b->direct_edges && nwt <= 2 && b->nw == 1 && !b->tiles_ready && !b->table_ready &&
-               !b->tile_recs_closed && sorted_count_mode() && sorted_tiles_mode() == 2;
+               !b->tile_recs.closed && sorted_count_mode() && sorted_tiles_mode() == 2;
     // (the reference's numbering: reads of one length whose numbers pack into a record word -- lds_count_seen_kernel's rule)
     const bool seen_ok = !b->first_seen || (!b->direct_edges && b->seen_read_len >= b->s.k &&
                                             2ull * (b->seen_read_len - b->s.k + 1) <= 0xFFFFull && (b->reads_inserted >> 31) == 0);
-    return seen_ok && tile_recs_shape(nwt, b->nw, b->first_seen) && !b->tiles_ready && !b->table_ready && !b->tile_recs_closed && sorted_count_mode() &&
+    return seen_ok && tile_recs_shape(nwt, b->nw, b->first_seen) && !b->tiles_ready && !b->table_ready && !b->tile_recs.closed && sorted_count_mode() &&
            sorted_tiles_mode() == 2;
-}
-
-// room in b->tile_recs_hist for the counts of n_total kept records (the record array's capacity; what is there is kept);
-// false: no room -- the first pass counts for itself
-static bool reserve_tile_hist(katome_builder* b, uint64_t n_total, uint32_t sort_tile, bool keep, hipStream_t stream) {
-    const uint64_t need = ((n_total + sort_tile - 1) / sort_tile) * 256 * 4 + 16;
-    if (need <= b->tile_recs_hist.bytes) return true;
-    DevBuf grown(stream);
-    if (grown.alloc(need) != KATOME_OK) return false;
-    if (keep && b->tile_recs_hist.p &&
-        hipMemcpyAsync(grown.p, b->tile_recs_hist.p, ((b->tile_recs_n + sort_tile - 1) / sort_tile) * 256 * 4, hipMemcpyDeviceToDevice, stream) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    const size_t grown_bytes = grown.bytes;
-    b->tile_recs_hist.adopt(grown.take(), grown_bytes);
-    b->tile_recs_hist.stream = stream;
-    return true;
 }
 
 int katome_dev_count_tiles(katome_builder* b, const uint8_t* d_packed, uint64_t n_reads, uint32_t read_len, uint32_t span,
@@ -1043,36 +554,36 @@ int katome_dev_count_tiles(katome_builder* b, const uint8_t* d_packed, uint64_t 
     // No read skipped and every record kept so far valid: the records are made where they are kept -- no buffer in between, no copy
     // (C3: 12.8 GB not read and not written again per build).  Otherwise: into a scratch of the builder's, then as
     // katome_dev_insert_tiles does.
-    if (!d_skip && !b->first_seen && keeps_tile_recs(b, nwt) && (b->tile_recs_n == 0 || (b->tile_recs_exact && span == b->span))) {
+    if (!d_skip && !b->first_seen && keeps_tile_recs(b, nwt) && (b->tile_recs.n == 0 || (b->tile_recs.exact && span == b->span))) {
         bool ok = false;
         {
             PhaseScope ps(b->prof, PH_INSERT_TILES, stream);
-            KCHECK(reserve_tile_recs(b, n, nwt, &ok, stream));
+            KCHECK(b->tile_recs.reserve(b, n, nwt, &ok, stream));
         }
-        if (ok && b->tile_recs_exact) {
+        if (ok && b->tile_recs.exact) {
             // The extraction knows the index of every record it writes, so where this batch starts on a sort-tile boundary of the kept
             // array -- and every batch before it did -- it also leaves the first partition pass's digit counts of the sort tiles it
             // fills (KATOME_FUSED_HIST=0: never; the pass counts for itself, as it does in every other case)
             const uint32_t sort_tile = dev_sort_tile_keys(nwt);
-            u64* const dst = b->tile_recs.as<u64>() + b->tile_recs_n * nwt;
-            const bool counted = fused_hist_on() && (b->tile_recs_n == 0 || b->tile_recs_hist_ok) && b->tile_recs_n % sort_tile == 0 &&
+            u64* const dst = b->tile_recs.recs.as<u64>() + b->tile_recs.n * nwt;
+            const bool counted = fused_hist_on() && (b->tile_recs.n == 0 || b->tile_recs_hist_ok) && b->tile_recs.n % sort_tile == 0 &&
                                  extract_tile_counts_ok(b->s.k, read_len, span, sort_tile, d_packed, dst) &&
-                                 reserve_tile_hist(b, std::max<uint64_t>(b->tile_recs_n + n, b->tile_recs_cap), sort_tile, b->tile_recs_n != 0, stream);
+                                 reserve_tile_hist(b, std::max<uint64_t>(b->tile_recs.n + n, b->tile_recs.cap), sort_tile, b->tile_recs.n != 0, stream);
             if (getenv("KATOME_LC_TRACE"))
-                fprintf(stderr, "[tiles] batch of %llu records at %llu: %s\n", (unsigned long long)n, (unsigned long long)b->tile_recs_n,
+                fprintf(stderr, "[tiles] batch of %llu records at %llu: %s\n", (unsigned long long)n, (unsigned long long)b->tile_recs.n,
                         counted ? "first-pass counts from the extraction" : "no counts");
             if (counted) {
                 KCHECK(check_seen_len(b, read_len));
                 PhaseScope ps(b->prof, PH_EXTRACT, stream);
                 b->seen_read_len = read_len;
-                KCHECK(launch_extract_tiles_counted(b->s.k, b->rc, d_packed, n_reads, read_len, span, dst, b->tile_recs_hist.as<u32>() + (b->tile_recs_n / sort_tile) * 256,
+                KCHECK(launch_extract_tiles_counted(b->s.k, b->rc, d_packed, n_reads, read_len, span, dst, b->tile_recs_hist.as<u32>() + (b->tile_recs.n / sort_tile) * 256,
                                                     sort_tile, stream));
             } else {
                 KCHECK(katome_dev_extract_tiles(b, d_packed, n_reads, read_len, span, nullptr, dst, stream));
             }
             b->tile_recs_hist_ok = counted;
             b->span = span;
-            b->tile_recs_n += n;
+            b->tile_recs.n += n;
             return KATOME_OK;
         }
     }
@@ -1085,7 +596,7 @@ int katome_dev_insert_tiles(katome_builder* b, const uint64_t* d_records, uint64
     hipStream_t stream = (hipStream_t)stream_;
     KCHECK_HIP(hipSetDevice(b->s.device));
     if (b->edges_ready) { set_error("builder already finalized"); return KATOME_E_ARG; }
-    if (span < 2 || b->s.k + span - 1 > 95 || ((b->tiles_ready || b->tile_recs_n) && span != b->span)) { set_error("bad tile span %u", span); return KATOME_E_ARG; }
+    if (span < 2 || b->s.k + span - 1 > 95 || ((b->tiles_ready || b->tile_recs.n) && span != b->span)) { set_error("bad tile span %u", span); return KATOME_E_ARG; }
     if (b->first_seen && b->var_prefix && b->s.k + span - 1 > 95) { set_error("variable-length reads: tiles of at most 95 bases"); return KATOME_E_ARG; }
     if (n_records == 0) return KATOME_OK;
     b->span = span;
@@ -1111,17 +622,8 @@ int katome_dev_insert_tiles(katome_builder* b, const uint64_t* d_records, uint64
         }
     }
     SeenOrigin origin;
-    if (var_tiles) {
-        if (b->var_mode != 1 || b->var_span != span || n_records != b->var_records) { set_error("first-seen order: insert exactly the tiles katome_dev_extract_var_tiles produced"); return KATOME_E_ARG; }
-        origin.win_prefix = b->var_prefix; origin.n_reads = b->var_reads; origin.seq_base = b->var_seq_base; origin.rc = b->rc;
-        origin.rec_prefix = b->var_rec_prefix; origin.mode = 1; origin.span = span;
-    } else if (b->first_seen) {
-        if (b->var_seq_base) { set_error("first-seen order: fixed- and variable-length batches cannot be mixed in one build"); return KATOME_E_UNSUPPORTED; }
-        if (b->seen_read_len < b->s.k) { set_error("first-seen order: extract the records with this builder first"); return KATOME_E_ARG; }
-        origin.windows = b->seen_read_len - b->s.k + 1; origin.per_read = origin.windows / span; origin.span = span; origin.rc = b->rc;
-        origin.read0 = b->reads_inserted;
-        if (origin.per_read == 0 || n_records % origin.per_read) { set_error("first-seen order: a batch must hold whole reads"); return KATOME_E_ARG; }
-    }
+    if (var_tiles) KCHECK(var_origin(b, n_records, 1, span, &origin));
+    else if (b->first_seen) KCHECK(fixed_origin(b, n_records, span, false, &origin));
     for (uint64_t done = 0; done < n_records;) {
         uint64_t room = 0;
         KCHECK(ensure_table(b, b->tiles, b->tiles_ready, nwt, b->s.table_slots_hint / 4, n_records - done, &room, stream));
@@ -1144,8 +646,8 @@ int katome_dev_expand_tiles(katome_builder* b, uint64_t** d_keys, uint32_t** d_w
     KCHECK_HIP(hipSetDevice(b->s.device));
     *n_records = 0; *d_keys = nullptr; *d_weights = nullptr;
     if (b->first_seen) { set_error("first-seen order is not available on the multi-GPU route"); return KATOME_E_UNSUPPORTED; }
-    if (b->tile_recs_n) KCHECK(flush_tile_recs(b, stream));
-    if (b->rest_n) KCHECK(flush_rest(b, stream));
+    if (b->tile_recs.n) KCHECK(flush_tile_recs(b, stream));
+    if (b->rest.n) KCHECK(flush_rest(b, stream));
     if (!b->tiles_ready) return KATOME_OK;
     Table* last = nullptr; uint32_t last_span = 1;
     KCHECK(expand_to_last_level(b, &last, &last_span, stream));
@@ -1184,332 +686,9 @@ int katome_dev_remove_weak_edges(katome_builder* b, uint32_t threshold, void* st
 int katome_dev_table_count(katome_builder* b, uint64_t* out, void* stream) {
     KCHECK_HIP(hipSetDevice(b->s.device));
     *out = 0;
-    if (b->rest_n) KCHECK(flush_rest(b, (hipStream_t)stream));
+    if (b->rest.n) KCHECK(flush_rest(b, (hipStream_t)stream));
     if (!b->table_ready) return KATOME_OK;
     return table_occupied(b->table, out, (hipStream_t)stream);
-}
-
-// The left-over windows kept aside (b->rest_k, `words` words each: nw, or nw + 1 for tagged records) behind the n_rec records in
-// keys / weights, weight 1 each.  orient: the records are in their representative orientation (the half sort's k-mer records)
-static int append_rest(katome_builder* b, DevBuf& keys, DevBuf& weights, uint64_t* n_rec, uint64_t n_rest, uint32_t words, bool orient, hipStream_t stream) {
-    if (!n_rest) return KATOME_OK;
-    KCHECK_HIP(hipMemcpyAsync(keys.as<u64>() + *n_rec * words, b->rest_k.p, n_rest * 8 * words, hipMemcpyDeviceToDevice, stream));
-    KCHECK(dev_fill_u32(weights.as<u32>() + *n_rec, n_rest, 1u, stream));
-    if (orient) KCHECK(table_orient_records(keys.as<u64>() + *n_rec * words, n_rest, b->s.k, true, stream));
-    *n_rec += n_rest;
-    return KATOME_OK;
-}
-
-// The last level counted by sorting instead of in a table (lds_count.hip, lds_count_kernel / lds_count_wide_kernel): k <= 63, by packed
-// key, nothing in the k-mer table yet (left-over windows were kept aside).  With the tiles kept as records (katome_dev_insert_tiles)
-// the tile levels above it are counted the same way: every level is "records -> two hash passes -> counted in LDS -> a compact list
-// of distinct keys with their counts", the next level's records are cut out of that list (table.hip, list_to_records_kernel).
-// on fallback: the tiles are in their table, or the k-mer records with their counts in b->table; n_edges == 0
-static int edges_from_tile_recs(katome_builder* b, bool* counted, hipStream_t stream) {
-    const uint32_t k = b->s.k;
-    DevBuf rk(stream), rw(stream);
-    uint64_t n_rec = 0, n_rest = 0, distinct = 0;
-    KCHECK(rest_valid(b, &n_rest, stream));
-    DevBuf first_counts(stream);
-    const bool half = half_sort_route(b);
-    HalfSort hs;
-    RecordSource src;          // (the k-mer records may be left to their first partition pass: see RecordSource)
-    int rc = tile_recs_to_kmer_records(b, rk, rw, &n_rec, n_rest, stream, &first_counts, half, &src);
-    if (rc == KATOME_E_UNSUPPORTED) return KATOME_OK;          // (the tiles are in their table now, the table routes take it from there)
-    if (rc != KATOME_OK) return rc;
-    {
-        PhaseScope ps(b->prof, PH_EXPAND_TILES, stream);
-        KCHECK(append_rest(b, rk, rw, &n_rec, n_rest, b->nw, half && b->rc, stream));
-        rest_reset(b);
-        const bool fail = sorted_fail("last");
-        if (fail) KCHECK(table_materialise_records(src));          // (the table wants the records)
-        if (fail && half && b->rc) KCHECK(table_orient_records(rk.as<u64>(), n_rec, k, false, stream));     // (the table takes canonical k-mers)
-        rc = fail ? KATOME_E_UNSUPPORTED
-            : records_to_edges_sorted(rk, rw, n_rec, k, b->rc, b->prune_weight, b->edge_key, b->edge_weight, &b->n_edges, &distinct, stream, nullptr,
-                                      n_rest ? nullptr : first_counts.as<u32>(), half ? &hs : nullptr, &src);
-        if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
-    }
-    if (rc != KATOME_OK) {
-        // the k-mers cannot be counted this way (a hash group beyond the LDS route): their records, counts and all, go into the k-mer
-        // table and the edges are read out of it
-        b->n_edges = 0;
-        return builder_insert(b, b->table, b->table_ready, b->nw, b->s.table_slots_hint, rk.as<u64>(), rw.as<u32>(), n_rec, nullptr, PH_INSERT, stream);
-    }
-    b->stat_kmers = distinct; b->stat_kmer_slots = 0;
-    rk.release(); rw.release();
-    first_counts.release();                  // (the order call worked in them: prefixes now, of no use to anyone)
-    PhaseScope ps(b->prof, PH_SORT_EDGES, stream);
-    if (hs.taken) {
-        KCHECK(half_sort_finish(hs, b->edge_key, b->edge_weight, stream, &b->edge_heads));
-        if (b->edge_heads.p) { b->edge_heads_key = b->edge_key.p; b->edge_heads_n = b->n_edges; }
-    } else KCHECK(dev_sort_bufs(b->edge_key, &b->edge_weight, b->n_edges, b->nw, 2 * k, stream, true));
-    *counted = true;
-    return KATOME_OK;
-}
-
-// The k-mers counted by sorting when the big tiles are in their table (KATOME_SORTED_TILES=1, a build that could not keep them aside
-// as records, or one that had to give them up half-way), the mid tiles too where they can be.
-// on fallback: the tiles are in their table (the big ones still there if the mid tiles were counted by sorting), b->table is empty; n_edges == 0
-static int edges_from_tile_table(katome_builder* b, bool* counted, hipStream_t stream) {
-    if (!sorted_count_mode() || !b->tiles_ready || !b->tiles.cap || b->table_ready || b->nw > 2) return KATOME_OK;
-    uint64_t n_tiles = 0;
-    KCHECK(table_occupied(b->tiles, &n_tiles, stream));
-    const uint64_t bound = n_tiles * b->span + b->rest_n;        // the k-mer records can be no more than this
-    const uint32_t nwt = b->tiles.nw;
-    const bool shapes = (b->nw == 1 && nwt <= 2) || (b->nw == 2 && (nwt == 2 || nwt == 3));      // (what tiles_to_records streams)
-    if (!shapes || !sorting_pays(bound) || !lds_route_takes(bound)) return KATOME_OK;
-    Table* last = nullptr; uint32_t last_span = 1;
-    // The mid tiles are counted by sorting all the same: the big tiles' sub-tiles leave the tile table as records, two hash passes,
-    // counted in LDS into a compact list of (mid tile, count), and the k-mer records are cut out of that list -- no mid-tile table,
-    // no 7e8 128-bit upserts (C3: 45 -> 32 ms for the level).
-    DevBuf t2k(stream), t2w(stream);
-    uint64_t n_mid_list = 0;
-    bool mid_sorted = false;
-    const uint32_t sp2 = mid_span(b->span);
-    if (sorted_tiles_mode() && nwt == 2 && b->nw == 1 && sp2 && !b->tiles2_ready && b->tiles.cap && n_tiles &&
-        level_fits(n_tiles * (b->span / sp2), (uint32_t)key_words_for_k(b->s.k + sp2 - 1), false, "mid tiles (big tiles in their table)")) {
-        const uint32_t kk2 = b->s.k + sp2 - 1, n_sub = b->span / sp2;
-        PhaseScope ps(b->prof, PH_EXPAND_MID, stream);
-        TileLevelScope tl;
-        DevBuf mk(stream), mw(stream);
-        uint64_t n_mid = 0, d2 = 0;
-        KCHECK(table_expand_tiles_to_subtiles(b->tiles, kk2, n_sub, sp2, b->rc, mk, mw, &n_mid, stream, nullptr));
-        int rc2 = (n_mid && !sorted_fail("mid")) ? records_to_edges_sorted(mk, mw, n_mid, kk2, false, 0, t2k, t2w, &n_mid_list, &d2, stream) : KATOME_E_UNSUPPORTED;
-        if (rc2 != KATOME_OK && rc2 != KATOME_E_UNSUPPORTED) return rc2;
-        if (rc2 == KATOME_OK) {
-            mid_sorted = true;           // (the big-tile table stays until the k-mers are counted: the table route's way back)
-            b->stat_tiles = n_tiles; b->stat_tile_slots = b->tiles.cap;
-            b->span2 = sp2; b->stat_tiles2 = n_mid_list; b->stat_tile2_slots = 0;
-            last_span = sp2;
-        } else { t2k.release(); t2w.release(); }
-    }
-    if (!mid_sorted) KCHECK(expand_to_last_level(b, &last, &last_span, stream));
-    if (!mid_sorted && !((b->nw == 1 && last->nw <= 2) || (b->nw == 2 && (last->nw == 2 || last->nw == 3)))) return KATOME_OK;
-    uint64_t last_tiles = n_mid_list;          // (... and the records of the level fit the card with their scratch and their output)
-    if (!mid_sorted) KCHECK(table_occupied(*last, &last_tiles, stream));
-    if (!level_fits(last_tiles * last_span + b->rest_n, b->nw, b->rc, "k-mers (tiles in their table)")) return KATOME_OK;
-    DevBuf rk(stream), rw(stream);
-    uint64_t n_rec = 0, distinct = 0;
-    int rc = KATOME_OK;
-    {
-        PhaseScope ps(b->prof, PH_EXPAND_TILES, stream);
-        uint64_t n_rest = 0;
-        KCHECK(rest_valid(b, &n_rest, stream));
-        if (mid_sorted) {
-            KCHECK(table_list_to_records(t2k.as<u64>(), t2w.as<u32>(), n_mid_list, b->s.k + sp2 - 1, b->s.k, sp2, 1, b->rc, rk, rw, &n_rec, stream, n_rest));
-            t2k.release(); t2w.release();
-        } else
-        KCHECK(table_tiles_to_records_fast(*last, b->s.k, last_span, b->rc, rk, rw, &n_rec, stream, n_rest));
-        KCHECK(append_rest(b, rk, rw, &n_rec, n_rest, b->nw, false, stream));
-        rc = sorted_fail("last") ? KATOME_E_UNSUPPORTED
-            : records_to_edges_sorted(rk, rw, n_rec, b->s.k, b->rc, b->prune_weight, b->edge_key, b->edge_weight, &b->n_edges, &distinct, stream);
-        if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
-    }
-    // (a group too large for the LDS route: the table counts, from the tiles that are still there)
-    if (rc != KATOME_OK) { b->n_edges = 0; return KATOME_OK; }
-    release_tile_tables(b);
-    rest_reset(b);
-    b->stat_kmers = distinct; b->stat_kmer_slots = 0;
-    for (int i = 0; i < 2; ++i) { b->scratch_k[i].release(); b->scratch_w[i].release(); }
-    rk.release(); rw.release();
-    PhaseScope ps(b->prof, PH_SORT_EDGES, stream);
-    KCHECK(dev_sort_bufs(b->edge_key, &b->edge_weight, b->n_edges, b->nw, 2 * b->s.k, stream, true));
-    *counted = true;
-    return KATOME_OK;
-}
-
-// edges_from_tile_recs for a first-seen-order build, with the tiles kept as TAGGED records (keep_tile_recs in such a build): every level's
-// distinct keys leave with their counts and their two lowered numbers packed into a tag again (lds_count_seen_kernel, LIST), the
-// next level's tagged records are cut out of that list (list_to_tagged_records_kernel: a sub-window's numbers are its tile's plus its
-// place in it).
-// on fallback: the tile records, or the distinct big tiles with their counts and numbers, are in the tile table; n_edges == 0
-static int seen_edges_from_tile_recs(katome_builder* b, DevBuf& raw_seq, bool* counted, hipStream_t stream) {
-    const uint32_t k = b->s.k, span = b->span, tile_bases = k + span - 1;
-    const SeenTag tag = builder_tag(b);          // (reads of varying length: the delta tag)
-    b->span2 = mid_span(span);
-    uint64_t n = 0, n1 = 0, d1 = 0, distinct = 0;
-    KCHECK(tile_recs_valid(b, &n, stream));
-    DevBuf l1(stream), c1(stream);
-    int rc = KATOME_E_UNSUPPORTED;
-    if (n) {
-        PhaseScope ps(b->prof, PH_INSERT_TILES, stream);
-        TileLevelScope tl;
-        DevBuf ones(stream);               // (stays empty: the records count once each)
-        rc = tagged_records_sorted(b->tile_recs, ones, n, tile_bases, b->rc, tag, true, l1, c1, &n1, &d1, stream);
-        if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
-    }
-    if (rc == KATOME_E_UNSUPPORTED) return flush_tile_recs(b, stream);      // (the records are all still there, in another order: into the table with them)
-    close_tile_recs(b);
-    b->stat_tiles = n1; b->stat_tile_slots = 0; b->stat_tiles2 = 0; b->stat_tile2_slots = 0;
-    const uint64_t* lk = l1.as<u64>(); const uint32_t* lw = c1.as<u32>();
-    uint64_t n_last = n1; uint32_t last_bases = tile_bases, last_span = span;
-    DevBuf l2(stream), c2(stream);
-    if (b->span2 && n1) {
-        const uint32_t kk2 = k + b->span2 - 1, n_sub = span / b->span2;
-        PhaseScope ps(b->prof, PH_EXPAND_MID, stream);
-        TileLevelScope tl;
-        DevBuf mk(stream), mw(stream);
-        uint64_t n_mid = 0, n2 = 0, d2 = 0;
-        DevBuf mid_counts(stream);         // (the first partition pass's digit counts per tile, made while the records are written)
-        KCHECK(table_list_to_tagged_records(lk, lw, n1, tile_bases, kk2, n_sub, b->span2, b->rc, mk, mw, &n_mid, stream, 0, &mid_counts, tag.delta));
-        rc = sorted_fail("mid") ? KATOME_E_UNSUPPORTED
-            : tagged_records_sorted(mk, mw, n_mid, kk2, b->rc, tag, true, l2, c2, &n2, &d2, stream, mid_counts.as<u32>());
-        if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
-        if (rc == KATOME_OK) { b->stat_tiles2 = n2; lk = l2.as<u64>(); lw = c2.as<u32>(); n_last = n2; last_bases = kk2; last_span = b->span2; }
-    }
-    if (rc == KATOME_OK) {
-        PhaseScope ps(b->prof, PH_EXPAND_TILES, stream);
-        DevBuf kr(stream), kw(stream);
-        uint64_t n_rec = 0, n_rest = 0;
-        KCHECK(rest_valid(b, &n_rest, stream));
-        DevBuf last_counts(stream);
-        KCHECK(table_list_to_tagged_records(lk, lw, n_last, last_bases, k, last_span, 1, b->rc, kr, kw, &n_rec, stream, n_rest, &last_counts, tag.delta));
-        l2.release(); c2.release();
-        KCHECK(append_rest(b, kr, kw, &n_rec, n_rest, b->nw + 1, false, stream));
-        rc = sorted_fail("last") ? KATOME_E_UNSUPPORTED
-            : tagged_records_sorted(kr, kw, n_rec, k, b->rc, tag, false, b->edge_key, raw_seq, &b->n_edges, &distinct, stream, last_counts.as<u32>());
-        if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
-    }
-    if (rc == KATOME_OK) {
-        l1.release(); c1.release();
-        rest_reset(b);
-        b->stat_kmers = distinct; b->stat_kmer_slots = 0;
-        *counted = true;
-        return KATOME_OK;
-    }
-    // a level below gave up: the distinct big tiles go into the tile table with their counts and their numbers, and the build goes on
-    // from there as if they had been counted in it
-    b->n_edges = 0;
-    l2.release(); c2.release();
-    const uint32_t nwt = (uint32_t)key_words_for_k(tile_bases);
-    DevBuf keys(stream), pairs(stream);
-    KCHECK(keys.alloc(n1 * 8 * nwt + 16)); KCHECK(pairs.alloc(n1 * 16 + 16));
-    KCHECK(table_tagged_to_pairs(l1.as<u64>(), n1, nwt, tag, keys.as<u64>(), pairs.as<u64>(), stream));
-    l1.release();
-    SeenOrigin origin;
-    origin.pairs = pairs.as<u64>(); origin.rc = b->rc;
-    return builder_insert(b, b->tiles, b->tiles_ready, nwt, b->s.table_slots_hint / 4, keys.as<u64>(), c1.as<u32>(), n1, &origin, PH_INSERT_TILES, stream);
-}
-
-// The k-mers of a first-seen-order build counted by sorting out of the tile table (lds_count.hip, lds_count_seen_kernel): reads of one
-// length whose windows are whole tiles, so that a record's two sequence numbers pack into one word -- or, KATOME_SEEN_VAR_SORTED, reads
-// of varying length, whose tiles' pairs pack as they are (the delta tag); the left-over windows join as tagged records.
-// on fallback: the tiles are in their table (mid tiles in b->tiles2 if it made them); n_edges == 0
-static int seen_edges_from_tile_table(katome_builder* b, DevBuf& raw_seq, bool* counted, hipStream_t stream) {
-    const bool var = b->var_seq_base || b->var_prefix;
-    if (!sorted_count_mode() || !b->tiles_ready || b->table_ready || b->nw > 2 || b->direct_edges || (var ? !seen_var_sorted() : b->seen_read_len < b->s.k))
-        return KATOME_OK;
-    const SeenTag tag = var ? SeenTag::by_delta() : builder_tag(b);
-    uint64_t n_tiles = 0;
-    KCHECK(table_occupied(b->tiles, &n_tiles, stream));
-    if (!sorting_pays(n_tiles * b->span)) return KATOME_OK;     // (the last level's own size is checked where its records are made)
-    Table* last = nullptr; uint32_t last_span = 1;
-    KCHECK(expand_to_last_level(b, &last, &last_span, stream));
-    uint64_t distinct = 0;
-    int rc = KATOME_OK;
-    {
-        PhaseScope ps(b->prof, PH_EXPAND_TILES, stream);
-        uint64_t n_rest = 0;
-        KCHECK(rest_valid(b, &n_rest, stream));
-        rc = sorted_fail("last") && var ? KATOME_E_UNSUPPORTED
-            : tiles_to_edges_sorted_seen(*last, b->s.k, last_span, b->rc, tag, b->edge_key, raw_seq, &b->n_edges,
-                                         &distinct, stream, n_rest ? b->rest_k.as<u64>() : nullptr, n_rest);
-        if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
-    }
-    // (numbers that do not pack, or a group too large: the table counts, from the tiles that are still there)
-    if (rc != KATOME_OK) { b->n_edges = 0; return KATOME_OK; }
-    release_tile_tables(b);
-    rest_reset(b);
-    b->stat_kmers = distinct; b->stat_kmer_slots = 0;
-    *counted = true;
-    return KATOME_OK;
-}
-
-// ... and of one that kept windows only (KATOME_SEEN_VAR_SORTED: reads of varying length cut window by window, or none of them as long
-// as a tile): the tagged records kept aside are the level's records.
-// on fallback: they are still kept aside, in another order (the table route flushes them); n_edges == 0
-static int seen_edges_from_rest(katome_builder* b, DevBuf& raw_seq, bool* counted, hipStream_t stream) {
-    if (!b->seen_delta || !sorted_count_mode() || b->tiles_ready || b->table_ready || b->tile_recs_n || !b->rest_n || b->nw > 2) return KATOME_OK;
-    uint64_t n_rest = 0, distinct = 0;
-    KCHECK(rest_valid(b, &n_rest, stream));
-    if (!sorting_pays(n_rest)) return KATOME_OK;
-    PhaseScope ps(b->prof, PH_EXPAND_TILES, stream);
-    DevBuf ones(stream);               // (stays empty: the records count once each)
-    const int rc = sorted_fail("last") ? KATOME_E_UNSUPPORTED
-        : tagged_records_sorted(b->rest_k, ones, n_rest, b->s.k, b->rc, SeenTag::by_delta(), false, b->edge_key, raw_seq, &b->n_edges, &distinct, stream);
-    if (rc != KATOME_OK && rc != KATOME_E_UNSUPPORTED) return rc;
-    if (rc != KATOME_OK) { b->n_edges = 0; return KATOME_OK; }
-    rest_reset(b);
-    b->stat_kmers = distinct; b->stat_kmer_slots = 0;
-    *counted = true;
-    return KATOME_OK;
-}
-
-// The table route: what is left in the tile tables adds its counts to the k-mer table, whose edges are emitted and sorted.  It is
-// also the first-seen routes' sort tail: seen_counted -- their edges are in edge_key / raw_seq already, only the sort is left.
-static int edges_from_table(katome_builder* b, bool seen_counted, DevBuf& raw_seq, hipStream_t stream) {
-    DevBuf raw_w(stream);
-    if (!seen_counted) {
-        KCHECK(expand_tiles(b, stream));
-        if (!b->table_ready) {                    // (nothing was counted: an empty edge list)
-            KCHECK(b->edge_key.alloc(16, stream)); KCHECK(b->edge_weight.alloc(16, stream));
-            return KATOME_OK;
-        }
-        KCHECK(table_occupied(b->table, &b->stat_kmers, stream));
-        b->stat_kmer_slots = b->table.cap;
-        PhaseScope ps(b->prof, PH_EMIT_EDGES, stream);
-        // (first-seen order: the threshold is applied after the numbering, as the reference's retain passes do)
-        if (b->first_seen) KCHECK(table_emit_edges(b->table, b->s.k, b->rc, 0, b->edge_key, raw_w, &b->n_edges, stream, &raw_seq));
-        else KCHECK(table_emit_edges(b->table, b->s.k, b->rc, b->prune_weight, b->edge_key, b->edge_weight, &b->n_edges, stream));
-    }
-    for (int i = 0; i < 2; ++i) { b->scratch_k[i].release(); b->scratch_w[i].release(); }
-    b->table.release();                       // the table is spent; its memory serves the sort
-    b->table_ready = false;
-    PhaseScope ps(b->prof, PH_SORT_EDGES, stream);
-    if (!b->first_seen) return dev_sort_bufs(b->edge_key, &b->edge_weight, b->n_edges, b->nw, 2 * b->s.k, stream, true);
-    // sort (key, position) and bring weight and sequence number along through the positions
-    if (b->n_edges >= (1ull << 32)) { set_error("first-seen order: more than 2^32 edges on one GPU"); return KATOME_E_UNSUPPORTED; }
-    DevBuf idx(stream);
-    KCHECK(idx.alloc((b->n_edges + 1) * 4));
-    KCHECK(dev_iota(idx.as<u32>(), b->n_edges, stream));
-    KCHECK(dev_sort_bufs(b->edge_key, &idx, b->n_edges, b->nw, 2 * b->s.k, stream));
-    KCHECK(b->edge_weight.alloc((b->n_edges + 1) * 4, stream));
-    KCHECK(b->edge_seq.alloc((b->n_edges + 1) * 8, stream));
-    return dev_gather_seq_weight(raw_seq.as<u64>(), idx.as<u32>(), b->n_edges, b->edge_seq.as<u64>(), b->edge_weight.as<u32>(), stream);
-}
-
-// The builder's sorted distinct edges: the counting routes are tried in turn, each leaving to the next what it could not count
-int katome_dev_edges(katome_builder* b, uint64_t** d_edge_key, uint32_t** d_edge_weight, uint64_t* n_edges, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    KCHECK_HIP(hipSetDevice(b->s.device));
-    if (!b->edges_ready) {
-        b->n_edges = 0;
-        b->drop_edge_heads();
-        b->tile_scratch.release();
-        // (tile records with k-mers in the table already, or too few of them to be worth sorting: into the tile table)
-        if (b->tile_recs_n && (b->table_ready || !sorting_pays(b->tile_recs_n * b->span))) KCHECK(flush_tile_recs(b, stream));
-        bool counted = false;
-        DevBuf raw_seq(stream);                  // (first-seen order: the edges' sequence numbers and weights until the sort tail)
-        if (!b->first_seen) {
-            if (b->tile_recs_n) KCHECK(edges_from_tile_recs(b, &counted, stream));
-            if (!counted) KCHECK(edges_from_tile_table(b, &counted, stream));
-            if (!counted) KCHECK(edges_from_table(b, false, raw_seq, stream));
-        } else {
-            const char* route = "tile records";
-            if (b->tile_recs_n) KCHECK(seen_edges_from_tile_recs(b, raw_seq, &counted, stream));
-            if (!counted) { route = "tile table, k-mers by sorting"; KCHECK(seen_edges_from_tile_table(b, raw_seq, &counted, stream)); }
-            if (!counted) { route = "windows kept aside"; KCHECK(seen_edges_from_rest(b, raw_seq, &counted, stream)); }
-            if (b->var_seq_base && getenv("KATOME_LC_TRACE"))
-                fprintf(stderr, "[first-seen order, reads of varying length] levels counted %s%s (KATOME_SEEN_VAR_SORTED=%d)\n", counted ? "by sorting: " : "in the tables",
-                        counted ? route : "", (int)seen_var_sorted());
-            KCHECK(edges_from_table(b, counted, raw_seq, stream));
-        }
-        b->edges_ready = true;
-    }
-    if (d_edge_key) *d_edge_key = b->edge_key.as<u64>();
-    if (d_edge_weight) *d_edge_weight = b->edge_weight.as<u32>();
-    if (n_edges) *n_edges = b->n_edges;
-    return KATOME_OK;
 }
 
 // the finalized graph as the caller sees it: pointers into the builder's arrays as they stand

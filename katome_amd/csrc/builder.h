@@ -1,12 +1,43 @@
 // builder.h -- one GPU's share of a build: the state behind `katome_builder` and the internal steps that the C ABI
-// (api.hip, host_build.cpp) and the sharded driver (dist.hip) compose.  Reference path: Build::create (builder.rs:42-54) ->
+// (api.hip, kept_records.hip, count_routes.hip, host_build.cpp) and the sharded driver (dist.hip) compose.  Reference path: Build::create (builder.rs:42-54) ->
 // add_read_fastaq (pt_graph.rs:277-315) -> add_single_edge_fastaq (172-198) -> post-pass (333-345).
 #pragma once
 #include <vector>
 
 #include "common.h"
+#include "keep_plan.h"
 
 using namespace katome;
+
+// what crosses a file boundary inside the library, but not the library's: not among its dynamic symbols
+#define KATOME_INTERNAL __attribute__((visibility("hidden")))
+
+struct katome_builder;
+KATOME_INTERNAL int flush_tile_recs(katome_builder* b, hipStream_t stream);    // the tile records kept aside -> b->tiles
+KATOME_INTERNAL int flush_rest(katome_builder* b, hipStream_t stream);         // the left-over windows kept aside -> b->table
+
+// Records kept aside between batches, to be counted by sorting when the edges are asked for: a device array that kernels append to
+// behind a device cursor.  The builder has two, the big-tile records and the left-over windows; they differ in their KeepPolicy
+// (keep_plan.h) and in where `flush` puts them when keeping is given up.  Defined in kept_records.hip
+struct KATOME_INTERNAL KeptRecords {
+    const KeepPolicy policy;
+    int (*const flush)(katome_builder*, hipStream_t);      // what was kept goes into its table, and the set is closed
+    DevBuf recs, count;                 // count: the 8-byte device cursor -- how many of the records handed over were valid
+    uint64_t n = 0, cap = 0;            // n: records handed over so far (an upper bound of the cursor)
+    uint32_t words = 0;                 // u64 words per record the array was last grown for (first-seen order: key + tag)
+    bool closed = false;                // nothing is kept from here on (they were counted, or went into their table)
+    bool exact = false;                 // every record handed over so far was valid: n IS the count (katome_dev_count_tiles writes in place)
+    KeptRecords(const KeepPolicy& p, int (*f)(katome_builder*, hipStream_t)) : policy(p), flush(f) {}
+    // how many valid records wait
+    int valid(uint64_t* n_valid, hipStream_t stream);
+    // room for n_new more behind those kept; *ok = false: no room (or over the limit) -- what was kept has been flushed into its table
+    // and later batches follow it there
+    int reserve(katome_builder* b, uint64_t n_new, uint32_t words, bool* ok, hipStream_t stream);
+    // the device cursor, ready for a kernel that appends behind it
+    int cursor(hipStream_t stream);
+    void reset() { recs.release(); count.release(); n = cap = 0; exact = false; }
+    void close() { reset(); closed = true; }
+};
 
 struct katome_builder {
     katome_settings s;
@@ -41,7 +72,7 @@ struct katome_builder {
     uint64_t var_records = 0;                  // how many of them: the insert that follows must take exactly these
     uint32_t var_mode = 0, var_span = 1;       // 0 every window, 1 whole tiles, 2 the windows after the last whole tile
     // first-seen order, reads of varying length, levels counted by sorting (KATOME_SEEN_VAR_SORTED): the tagged records kept aside
-    // (tile_recs, rest_k) carry the delta tag of seen_tag.h, not seen_pack's; set with the first batch kept so
+    // (tile_recs, rest) carry the delta tag of seen_tag.h, not seen_pack's; set with the first batch kept so
     bool seen_delta = false;
     // ... which is kept only if every read of it packs: the last batch asked about (its prefix and sequence base) and the answer
     const uint64_t* var_checked = nullptr; uint64_t var_checked_base = ~0ull; bool var_checked_ok = false;
@@ -50,20 +81,16 @@ struct katome_builder {
     // be counted by sorting (lds_count.hip, records_to_edges_sorted) together with the tiles' k-mers; any other consumer of the k-mer
     // table flushes them into it first (flush_rest)
     // by-packed-key builds with two-word tiles and one-word k-mers: the tiles themselves are kept as records too and counted by
-    // sorting when the edges are asked for (api.hip, count_tiles_sorted) -- no tile table, no device-scope atomics at any level
-    DevBuf tile_recs, tile_recs_count;  // tile_recs_count: device cursor -- the valid ones among them (a skipped read's tiles are all-ones)
-    uint64_t tile_recs_n = 0, tile_recs_cap = 0;      // tile_recs_n: records handed over (an upper bound of the cursor)
-    bool tile_recs_closed = false;
+    // sorting when the edges are asked for (count_routes.hip, edges_from_tile_recs) -- no tile table, no device-scope atomics at any level
+    KeptRecords tile_recs{KEEP_TILES, flush_tile_recs};      // (a skipped read's tiles are all-ones: not valid, not kept)
     // tile_recs_hist: counts[sort tile][256] of the first partition pass's digit over tile_recs, left by the extraction that wrote the
     // records (katome_dev_count_tiles); tile_recs_hist_ok: they cover all of tile_recs -- every batch so far started on a sort-tile
-    // boundary and was written in place.  They grow and go with the records.
+    // boundary and was written in place.  They grow and go with the records (close_tile_recs).
     DevBuf tile_recs_hist;
     bool tile_recs_hist_ok = false;
-    bool tile_recs_exact = false;       // every record handed over so far was valid (tile_recs_n IS the count: katome_dev_count_tiles writes in place)
     DevBuf tile_scratch;                // katome_dev_count_tiles: a batch's records when they cannot be made where they are kept
-    DevBuf rest_k, rest_count;          // rest_count: device cursor -- how many of them are valid records (reads with N leave invalid ones)
-    uint64_t rest_n = 0, rest_cap = 0;  // rest_n: records handed over so far (an upper bound of the cursor)
-    bool rest_closed = false;           // too many to keep aside: from now on they go into the table directly
+    // (reads with N leave invalid left-over windows; rest.closed: too many to keep aside -- from now on they go into the table directly)
+    KeptRecords rest{KEEP_REST, flush_rest};
     uint64_t direct_edges = 0;         // BFCounter input: the edges were listed one per line and strand (no table); their count
     uint32_t prune_weight = 0;      // Clean::remove_weak_edges threshold applied when the edges are read out
     uint64_t stat_tiles = 0, stat_tile_slots = 0, stat_kmers = 0, stat_kmer_slots = 0;
@@ -92,32 +119,50 @@ struct katome_builder {
 };
 
 
-// ---- internal steps shared with dist.hip (defined in api.hip) --------------------------------------------------------
+// ---- internal steps, by the file that defines them; dist.hip and host_build.cpp compose them too ------------------------------
+
+// ---- api.hip: the table side ---------------------------------------------------------------------------------------------------
 // find-or-insert `n` records (weights: nullptr = 1 each) into `table`, growing it under the load policy; `origin` places
 // the records in the read-ordered stream when the builder tracks first-seen order (its rec0 is set per launch)
-int builder_insert(katome_builder* b, Table& table, bool& ready, uint32_t nw, uint64_t hint, const uint64_t* d_records,
-                   const uint32_t* d_weights, uint64_t n, SeenOrigin* origin, int phase, hipStream_t stream);
+KATOME_INTERNAL int builder_insert(katome_builder* b, Table& table, bool& ready, uint32_t nw, uint64_t hint, const uint64_t* d_records,
+                                   const uint32_t* d_weights, uint64_t n, SeenOrigin* origin, int phase, hipStream_t stream);
 // big tiles -> mid tiles (when the span is large); leaves the tiles that hold k-mers directly in `*last`
-int expand_to_last_level(katome_builder* b, Table** last, uint32_t* last_span, hipStream_t stream);
-void release_tile_tables(katome_builder* b);     // b->tiles and b->tiles2 are spent
-int expand_tiles(katome_builder* b, hipStream_t stream);       // every distinct tile adds its count to its k-mers (b->table); the tile tables go
-int flush_rest(katome_builder* b, hipStream_t stream);
-int keep_tile_recs(katome_builder* b, const uint64_t* d_records, uint64_t n, uint32_t nwt, bool* kept, hipStream_t stream);   // a batch's valid tile records behind those kept so far
-int tile_recs_valid(katome_builder* b, uint64_t* n, hipStream_t stream);      // how many of them there are
-// ... counted level by level by sorting, down to the (k-mer, count) records of the last tile level (api.hip)
-int tile_recs_to_kmer_records(katome_builder* b, DevBuf& keys, DevBuf& weights, uint64_t* n_records, uint64_t extra_room, hipStream_t stream,
-                              DevBuf* first_counts = nullptr, bool rep = false, RecordSource* src = nullptr);      // (rep: the k-mer records in their representative orientation)
-int sorted_count_mode();            // KATOME_SORTED_COUNT
-bool sorting_pays(uint64_t n);       // n records are worth counting by sorting
-bool lds_route_takes(uint64_t n);    // ... and not too many for the LDS counting route
-int sorted_tiles_mode();            // KATOME_SORTED_TILES
-bool tile_recs_shape(uint32_t nwt, uint32_t nw, bool first_seen);   // tile / k-mer word counts whose levels are all counted by sorting
-bool sorted_fail(const char* level);     // KATOME_SORTED_FAIL (tests)
-int flush_tile_recs(katome_builder* b, hipStream_t stream);    // the tile records kept aside -> b->tiles         // the left-over windows kept aside -> b->table
-uint32_t mid_span(uint32_t span);      // span of the mid tiles a big tile is broken into (0: expanded directly)
+KATOME_INTERNAL int expand_to_last_level(katome_builder* b, Table** last, uint32_t* last_span, hipStream_t stream);
+KATOME_INTERNAL void release_tile_tables(katome_builder* b);     // b->tiles and b->tiles2 are spent
+KATOME_INTERNAL int expand_tiles(katome_builder* b, hipStream_t stream);       // every distinct tile adds its count to its k-mers (b->table); the tile tables go
+KATOME_INTERNAL uint32_t mid_span(uint32_t span);      // span of the mid tiles a big tile is broken into (0: expanded directly)
 
-// ---- what the host entry points (host_build.cpp) take from api.hip; not part of the library's dynamic symbols ---------------
-#define KATOME_INTERNAL __attribute__((visibility("hidden")))
+// ---- kept_records.hip: KeptRecords, what keeps a batch aside and the ways back into the tables (flush_* are declared above) ----
+KATOME_INTERNAL SeenTag builder_tag(const katome_builder* b);      // how the builder's tagged records spell their two numbers
+KATOME_INTERNAL void close_tile_recs(katome_builder* b);           // no tile records are kept from here on; their digit counts go with them
+// a batch's valid tile records behind those kept so far; *kept = false: they go into the tile table
+KATOME_INTERNAL int keep_tile_recs(katome_builder* b, const uint64_t* d_records, uint64_t n, uint32_t nwt, bool* kept, hipStream_t stream);
+// ... its left-over windows (see katome_builder::rest); *kept = false: they have to go into the table
+KATOME_INTERNAL int keep_rest(katome_builder* b, const uint64_t* d_records, uint64_t n, bool* kept, hipStream_t stream);
+// first-seen order, reads of varying length: the records of the last katome_dev_extract_var* call with their delta tags
+KATOME_INTERNAL int keep_var_tiles(katome_builder* b, const uint64_t* d_records, uint64_t n, uint32_t nwt, bool* kept, hipStream_t stream);
+KATOME_INTERNAL int keep_var_rest(katome_builder* b, const uint64_t* d_records, uint64_t n, bool* kept, hipStream_t stream);
+// room in b->tile_recs_hist for the counts of n_total kept records; false: no room -- the first pass counts for itself
+KATOME_INTERNAL bool reserve_tile_hist(katome_builder* b, uint64_t n_total, uint32_t sort_tile, bool keep, hipStream_t stream);
+// n tagged records (key + tag; d_counts: their weights, nullptr = 1 each) back into keys and pairs of numbers, and into `table`.
+// spent: the buffer that holds d_tagged, given up between the two steps
+KATOME_INTERNAL int insert_tagged(katome_builder* b, Table& table, bool& ready, uint32_t nw, uint64_t hint, const uint64_t* d_tagged,
+                                  const uint32_t* d_counts, uint64_t n, int phase, hipStream_t stream, DevBuf* spent = nullptr);
+
+// ---- count_routes.hip: katome_dev_edges, its routes and their knobs --------------------------------------------------------------
+// the tile records kept aside counted level by level by sorting, down to the (k-mer, count) records of the last tile level
+KATOME_INTERNAL int tile_recs_to_kmer_records(katome_builder* b, DevBuf& keys, DevBuf& weights, uint64_t* n_records, uint64_t extra_room,
+                                              hipStream_t stream, DevBuf* first_counts = nullptr, bool rep = false,
+                                              RecordSource* src = nullptr);      // (rep: the k-mer records in their representative orientation)
+KATOME_INTERNAL int sorted_count_mode();            // KATOME_SORTED_COUNT
+KATOME_INTERNAL bool sorting_pays(uint64_t n);       // n records are worth counting by sorting
+KATOME_INTERNAL bool lds_route_takes(uint64_t n);    // ... and not too many for the LDS counting route
+KATOME_INTERNAL int sorted_tiles_mode();            // KATOME_SORTED_TILES
+KATOME_INTERNAL bool tile_recs_shape(uint32_t nwt, uint32_t nw, bool first_seen);   // tile / k-mer word counts whose levels are all counted by sorting
+KATOME_INTERNAL bool sorted_fail(const char* level);     // KATOME_SORTED_FAIL (tests)
+KATOME_INTERNAL bool seen_var_sorted();              // KATOME_SEEN_VAR_SORTED
+
+// ---- api.hip: what the host entry points (host_build.cpp) take from it ------------------------------------------------------------
 // BFCounter input: one edge per kept line and strand; leaves the builder with its sorted edge list
 KATOME_INTERNAL int bfc_set_edges(katome_builder* b, const uint64_t* d_fwd, const uint32_t* d_w, uint64_t n_lines, hipStream_t stream);
 // katome_dev_collapse, also handing back every contig's length in bases (host: the walk knows them)

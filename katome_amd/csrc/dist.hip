@@ -834,7 +834,7 @@ int katome_dist_add_reads(katome_dist_builder* d, const uint8_t* d_packed, uint6
                 b->span = d->span;
                 // (one GPU's rule: two-word tiles of one-word k-mers by packed key wait as records and are counted by sorting at the end)
                 bool kept = false;
-                if (!d->first_seen && tile_recs_shape(d->nwt, nw, false) && !b->tiles_ready && !b->tile_recs_closed && sorted_count_mode() && sorted_tiles_mode() == 2) {
+                if (!d->first_seen && tile_recs_shape(d->nwt, nw, false) && !b->tiles_ready && !b->tile_recs.closed && sorted_count_mode() && sorted_tiles_mode() == 2) {
                     PhaseScope ps(b->prof, PH_INSERT_TILES, stream);
                     KCHECK(keep_tile_recs(b, recbuf.as<u64>(), nr * per_read, d->nwt, &kept, stream));
                 }
@@ -941,7 +941,7 @@ int katome_dist_add_reads_var(katome_dist_builder* d, const uint8_t* d_packed, u
     else if (d->supermers) { set_error("the supermer route (planned by an earlier batch of one length) takes reads of one length only"); fail(KATOME_E_UNSUPPORTED); }
     // (by packed key after reads of one length on the local route: the tile records that batch kept aside go into the tile table,
     // where this call's tiles go -- finalize then expands one table)
-    if (!mine && d->local_first && b->tile_recs_n) { b->tile_recs_closed = true; fail(flush_tile_recs(b, stream)); }
+    if (!mine && d->local_first && b->tile_recs.n) { b->tile_recs.closed = true; fail(flush_tile_recs(b, stream)); }
     if (const char* f = getenv("KATOME_DIST_ADD_FAIL"))      // (tests: this rank's reads are refused, as a failed allocation would refuse them)
         if (!mine && atoi(f) == d->comm->rank()) { set_error("reads refused (KATOME_DIST_ADD_FAIL)"); fail(KATOME_E_OOM); }
     // every read's windows, and what each candidate span would cost on this rank's reads
@@ -1181,8 +1181,8 @@ int katome_dist_finalize(katome_dist_builder* d, katome_dist_graph* out, void* s
         // (owner split: grouped by the hash that names the owner, every group's keys written into its owner's stretch: no partition pass
         // before the exchange; KATOME_DIST_OWNER_SPLIT=0: by the whole k-mer's hash, then route_weighted's partition)
         static const bool owner_split_on = env_flag("KATOME_DIST_OWNER_SPLIT", true);
-        if (b->tile_recs_n && (!may_collect(d) || !sorting_pays(b->tile_recs_n * b->span))) KCHECK(flush_tile_recs(b, stream));
-        if (b->tile_recs_n) {
+        if (b->tile_recs.n && (!may_collect(d) || !sorting_pays(b->tile_recs.n * b->span))) KCHECK(flush_tile_recs(b, stream));
+        if (b->tile_recs.n) {
             // the tiles kept as records: every level by sorting, down to this rank's distinct k-mers
             DevBuf rk(stream), rw(stream);
             uint64_t n_win = 0, distinct = 0;

@@ -1099,7 +1099,7 @@ for k, L in ((31, 150), (40, 150)):
 
 def test_levels_that_do_not_fit_the_card_by_sorting_are_counted_in_tables(tmp_path):
     """input whose tiles hardly repeat (coverage of a few fold instead of C3's 300) multiplies records level by level; a level whose
-    records, scratch and output would not fit what the card has free goes the table way from there on (api.hip level_fits) instead of
+    records, scratch and output would not fit what the card has free goes the table way from there on (count_routes.hip level_fits) instead of
     dying in an allocation: forced at a small size with KATOME_LEVEL_BUDGET -- (a) nothing fits: the mid tiles and the k-mers in
     tables, (b) the mid level fits, the k-mer level does not: in parts by sorting when that is allowed, else the distinct mid tiles
     go into their table with their counts and the k-mers are counted in theirs, (c) everything fits: no table.  The oracle's graph
@@ -1135,7 +1135,7 @@ def test_levels_that_do_not_fit_the_card_by_sorting_are_counted_in_tables(tmp_pa
         mid = run((need_mid + need_last) // 2)[i]
         assert mid[2:6] == ["1", "0", "1", "1"], mid                                   # mid tiles and k-mers in tables, no big-tile table
         assert mid[8] == row[8]
-    # The k-mer level IN PARTS (the default; api.hip kmer_records_in_parts): when its records do not fit at once but repeat -- reads at
+    # The k-mer level IN PARTS (the default; count_routes.hip kmer_records_in_parts): when its records do not fit at once but repeat -- reads at
     # 22-fold coverage here --, the last tile level's list is cut, every part's k-mers are counted by sorting and the parts' lists are
     # counted once more: no table at all; with parts switched off the same budget sends the level to the tables
     deeper = run(None, genome=40000)
@@ -1153,7 +1153,7 @@ def test_levels_that_do_not_fit_the_card_by_sorting_are_counted_in_tables(tmp_pa
 
 
 def test_tile_records_kept_aside_grow_and_can_still_go_into_the_table(tmp_path):
-    """the big tiles of a build by packed key are kept aside as records and counted by sorting (api.hip keep_tile_recs): sixty
+    """the big tiles of a build by packed key are kept aside as records and counted by sorting (kept_records.hip keep_tile_recs): sixty
     batches (room for sixteen to begin with, doubled when that is too little), reads with N in them (their records are dropped),
     batches counted window by window in between -- and, in processes of their own, a limit on what may be kept that is reached
     half-way (the records kept so far go into the tile table, later batches too) and a level below that gives up (the distinct big

@@ -184,7 +184,7 @@ def test_c2_equals_all_switches_off():
 
 
 def test_lists_of_a_gibibyte_are_trimmed_in_place():
-    """a level's list is only worth trimming from 1 GiB (api.hip shrink_to_fit): C3's coverage on 24 M reads, whose tile levels' key
+    """a level's list is only worth trimming from 1 GiB (count_routes.hip shrink_to_fit): C3's coverage on 24 M reads, whose tile levels' key
     lists are 1.4-1.5 GiB for about a fifth of that used -- trimmed in place, the same checksums as copied"""
     new = _run(_BIG_SCRIPT, ["c3", "24000000"], 1200)
     old = _run(_BIG_SCRIPT, ["c3", "24000000"], 1200, **_ALL_OFF)

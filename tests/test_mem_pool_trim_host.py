@@ -1,5 +1,5 @@
 """SegmentPool::trim (katome_amd/csrc/mem_pool.h) over a fake backend on the host: a live block keeps its front and gives its
-tail back where it lies -- what shrink_to_fit (api.hip) does to a level's list instead of copying it."""
+tail back where it lies -- what shrink_to_fit (count_routes.hip) does to a level's list instead of copying it."""
 import ctypes as C
 import os
 import subprocess
