@@ -486,6 +486,36 @@ int katome_dev_collapse(katome_builder *b, uint32_t layout, katome_dev_assembly 
  * katome_dev_contigs_text or destroy.                                                                                  */
 int katome_dev_contigs_text(katome_builder *b, const katome_dev_contigs *contigs, uint32_t layout, katome_dev_assembly *out,
                             void *stream);
+/* ---- the unitig graph as GFA 1 (csrc/gfa.hip): segments, links and k-mer counts ------------------------------------------
+ * The text of a shrink result (n_edges merged edges over n_nodes vertices), byte for byte:
+ *   H\tVN:Z:1.0\n
+ *   S\t<i>\t<bases of edge i>\tLN:i:<bases>\tKC:i:<weight_i * kmers_i>\tew:i:<weight_i>\n    i = 0 .. n_edges - 1, in index order
+ *   L\t<a>\t+\t<b>\t+\t<k-1>M\n                                                              every (a, b) with edge_dst[a] == edge_src[b]
+ * Segment i is merged edge i, named by its decimal index: the record >katome_<i> of katome_dev_contigs_text on the same result;
+ * <bases> = edge_kmers[i] + k - 1.  KC is the 64-bit product (up to 20 digits) of what the shrunk edge carries: shrink keeps only
+ * the weight of a path's FIRST k-mer (shrinker.rs:181,200), so KC is that weight times the k-mers merged into the edge, not the
+ * sum of the path's k-mer counts; ew is that weight itself.  Links are ordered by a, then b; a self-loop links to itself, parallel
+ * merged edges are distinct segments, every orientation is + (the two strands of a reverse_complement build are separate edges
+ * and therefore separate segments; strand twins are not merged).  No edges: the header line alone.
+ * d_text holds text_bytes bytes in a buffer that is a multiple of 16 bytes (zeros behind the text up to the next multiple);
+ * d_segment_off[i] = offset of segment i's first base; the links of segment a are lines d_link_first[a] .. d_link_first[a + 1]
+ * of the L region (d_link_first[n_segments] = n_links).
+ * Everything the writer reads through is validated on the device first -- edge_src / edge_dst >= n_nodes, label offsets outside
+ * the labels, a pad byte > 3, a label shorter than k bases or whose bases are not edge_kmers + k - 1: KATOME_E_ARG, with a
+ * message.  2^32 segments or links or more (or 2^32 - 1 lines in all): KATOME_E_UNSUPPORTED, with the number.  Scratch and
+ * result beyond the text are a few words per segment, per vertex and per link (DESIGN.md section 11b has the bytes), never a
+ * second copy of the text.  Profile phase "gfa", kernel "k:gfa_write_kernel".  Synchronises.                              */
+typedef struct {
+    uint64_t  n_segments, n_links, text_bytes;
+    uint8_t  *d_text;
+    uint64_t *d_segment_off;             /* [n_segments]                                                               */
+    uint64_t *d_link_first;              /* [n_segments + 1]                                                           */
+} katome_dev_gfa;
+/* `contigs` is what katome_dev_shrink / katome_dev_shrink_mode of this builder returned last, in either numbering and either
+ * form.  The builder's graph and the shrink result are left untouched; the result is owned by the builder until its next
+ * katome_dev_contigs_gfa or destroy.                                                                                      */
+int katome_dev_contigs_gfa(katome_builder *b, const katome_dev_contigs *contigs, katome_dev_gfa *out, void *stream);
+
 /* Contigs::stats (stats/contigs.rs:31-89) from the contigs' lengths: host, pure.  No contigs: all zeros.  A tipping point of 0
  * with contigs present (sum / 2, (0.1 * sum) truncated, original_genome_length / 2), where the reference panics on
  * `.last().unwrap()`: KATOME_E_ARG, with a message that names which one.                                               */
@@ -519,6 +549,27 @@ int  katome_assemble_packed(const katome_settings *s, const uint8_t *packed, uin
 /* Contigs::save_to_file (asm/mod.rs:57-72): KATOME_E_OPEN when the path cannot be created */
 int  katome_assembly_save(const katome_assembly *a, const char *path);
 void katome_assembly_free(katome_assembly *a);
+
+/* The unitig graph of a read set as GFA 1 in host memory: the build, the stage letters as the staged entries take them (d, c, w,
+ * e; they need KATOME_FLAG_FIRST_SEEN_ORDER, an empty string works on a by-key build), katome_dev_shrink (AUTO) and
+ * katome_dev_contigs_gfa; text[0, text_bytes) is the file, written when out_path is given.  segment_off / link_first as in
+ * katome_dev_gfa.  Owned by the library until katome_gfa_free.  A path that cannot be created: KATOME_E_OPEN, "couldn't create
+ * <path>: <why>" -- the result is then still handed back when `out` is given (katome_assemble_*'s rule).  With
+ * settings.n_devices > 1 the graph is built sharded and gathered to the first GPU, as for katome_assemble_* (needs
+ * KATOME_FLAG_FIRST_SEEN_ORDER; a GFA of the sharded shrink without a gather is out of scope: links cross ranks).          */
+typedef struct {
+    uint64_t n_segments, n_links, text_bytes, read_bytes;
+    uint32_t k, _pad;
+    const uint8_t  *text;
+    const uint64_t *segment_off;         /* [n_segments]                                                               */
+    const uint64_t *link_first;          /* [n_segments + 1]                                                           */
+} katome_gfa;
+int  katome_gfa_files(const katome_settings *s, const char *const *paths, size_t n_paths, const char *stages,
+                      uint64_t original_genome_length, const char *out_path /* nullable */, katome_gfa **out);
+int  katome_gfa_packed(const katome_settings *s, const uint8_t *packed, uint64_t n_reads, uint32_t read_len, const uint8_t *skip,
+                       const char *stages, uint64_t original_genome_length, const char *out_path /* nullable */, katome_gfa **out);
+int  katome_gfa_save(const katome_gfa *g, const char *path);
+void katome_gfa_free(katome_gfa *g);
 
 /* first half of finalize only: sorted distinct edges (key, weight); used by the multi-GPU
  * driver, which resolves node ids across ranks itself                                      */
@@ -876,6 +927,17 @@ int katome_dev_pieces_text_numbered(int device, uint32_t k, const uint8_t *d_lab
                                     const uint32_t *d_pieces, uint64_t n_pieces, uint32_t layout, uint64_t first_contig,
                                     uint64_t *d_contig_off, uint32_t *d_contig_len, uint64_t contig_cap, uint8_t *d_text,
                                     uint64_t text_cap, uint64_t *n_contigs, uint64_t *text_bytes, void *stream);
+/* katome_dev_contigs_gfa on the caller's arrays (the layout of katome_dev_contigs; label_bytes: the size of d_edge_label, which
+ * every label offset is checked against).  *n_links and *text_bytes are always set.  d_text NULL: nothing else is written (a
+ * size query).  Otherwise d_segment_off needs room for n_edges entries, d_link_first for n_edges + 1, and d_text, 16-byte
+ * aligned, for text_cap >= *text_bytes rounded up to 16 (KATOME_E_ARG when it is too small).  d_edge_label as for
+ * katome_dev_pieces_text: 4-byte aligned, in an allocation whose size is a multiple of 4.  KATOME_GFA_TRACE=1 in the environment:
+ * the writing kernel's time on stderr (there is no builder whose profile could hold it).  Synchronises. */
+int katome_dev_gfa_arrays(int device, uint32_t k, uint64_t n_nodes, uint64_t n_edges, const uint64_t *d_edge_src,
+                          const uint64_t *d_edge_dst, const uint32_t *d_edge_weight, const uint32_t *d_edge_kmers,
+                          const uint64_t *d_edge_label_off, const uint8_t *d_edge_label, uint64_t label_bytes,
+                          uint64_t *d_segment_off, uint64_t *d_link_first, uint8_t *d_text, uint64_t text_cap,
+                          uint64_t *n_links, uint64_t *text_bytes, void *stream);
 /* Stats<CollectionStats>::stats for PtGraph (stats/collections.rs:137-168) from device arrays, filled exactly as
  * katome_graph_stats fills it from host arrays: u64 sums, the two averages one f64 division each on the host (no edges:
  * avg_edge_weight is NaN, no nodes: avg_out_degree is NaN, as the reference's 0.0 / 0.0); externals(Incoming) and

@@ -170,6 +170,40 @@ class Assembly:
             pass
 
 
+class Gfa:
+    """result of GpuGraph.gfa: the unitig graph as GFA 1 (include/katome_gpu.h has the format).  text: the file's bytes;
+    segment_off[i]: offset of segment i's first base; link_first[a] .. link_first[a + 1]: the L lines of segment a.  Keeps the C
+    result until it is collected."""
+
+    def __init__(self, gp):
+        self._gp = gp
+        g = gp.contents
+        ns, nb = g.n_segments, g.text_bytes
+        self.k, self.read_bytes, self.n_segments, self.n_links, self.text_bytes = g.k, g.read_bytes, ns, g.n_links, nb
+        self.text = bytes(np.ctypeslib.as_array(g.text, (nb,))) if nb else b""
+        self.segment_off = np.ctypeslib.as_array(g.segment_off, (ns,)).copy() if ns else np.zeros(0, np.uint64)
+        self.link_first = np.ctypeslib.as_array(g.link_first, (ns + 1,)).copy()
+
+    def save_to_file(self, path):
+        """the text as a file (katome_gfa_save): a path that cannot be created raises KatomePanic(E_OPEN)"""
+        _check(_lib.lib().katome_gfa_save(self._gp, os.fsencode(path)))
+
+    def __del__(self):
+        try:
+            _lib.lib().katome_gfa_free(self._gp)
+        except Exception:       # interpreter shutdown
+            pass
+
+
+def _gfa_result(rc, gp):
+    """a path that could not be created: the GFA was made all the same, and travels with the exception (`.result`)"""
+    if rc != 0:
+        err = KatomePanic(rc, _lib.last_error())
+        err.result = Gfa(gp) if gp else None
+        raise err
+    return Gfa(gp)
+
+
 FLAG_FIRST_SEEN_ORDER = 1
 FLAG_REMOVE_DEAD_PATHS = 2
 FLAG_RANKS_SHARE_DEVICE = 4
@@ -345,6 +379,41 @@ class GpuGraph:
                 _lib.lib().katome_assembly_free(ap)
             _check(rc)
         return Assembly(ap)
+
+    # ---- the unitig graph as GFA 1 ---------------------------------------------------------------
+    @staticmethod
+    def gfa(input_files, ft, reverse_complement, threshold, stages="", original_genome_length=0, output_file=None, device=0, n_devices=1,
+            first_seen_order=None, ranks_share_device=False):
+        """the build, the stage letters (as for create(); they need the reference's numbering), shrink and the GFA of the unitig
+        graph -- with output_file also the file --, all behind one call (katome_gfa_files) -> Gfa; uses the global k.
+        first_seen_order: None = whenever stage letters or several devices ask for it (an empty `stages` on one device builds by
+        packed key and shrinks in the fast form)"""
+        if first_seen_order is None:
+            first_seen_order = bool(stages) or n_devices > 1
+        s = make_settings(K_SIZE, ft, reverse_complement, threshold, device, first_seen_order=first_seen_order, n_devices=n_devices,
+                          ranks_share_device=ranks_share_device)
+        gp = C.POINTER(_lib.Gfa)()
+        rc = _lib.lib().katome_gfa_files(C.byref(s), _paths(input_files), len(input_files), (stages or "").encode(), original_genome_length,
+                                         os.fsencode(output_file) if output_file is not None else None, C.byref(gp))
+        return _gfa_result(rc, gp)
+
+    @staticmethod
+    def gfa_from_packed(packed, n_reads, read_len, skip=None, reverse_complement=False, threshold=0, stages="", original_genome_length=0,
+                        output_file=None, device=0, k=None, n_devices=1, first_seen_order=None, ranks_share_device=False):
+        """the same from 2-bit packed reads (numpy uint8; katome_gfa_packed)"""
+        if first_seen_order is None:
+            first_seen_order = bool(stages) or n_devices > 1
+        s = make_settings(K_SIZE if k is None else k, InputFileType.Fastq, reverse_complement, threshold, device,
+                          first_seen_order=first_seen_order, n_devices=n_devices, ranks_share_device=ranks_share_device)
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        skip_p = None
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.uint8)
+            skip_p = skip.ctypes.data
+        gp = C.POINTER(_lib.Gfa)()
+        rc = _lib.lib().katome_gfa_packed(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, (stages or "").encode(),
+                                          original_genome_length, os.fsencode(output_file) if output_file is not None else None, C.byref(gp))
+        return _gfa_result(rc, gp)
 
     # ---- Stats<CollectionStats> (stats/collections.rs:137-168) ---------------------------------
     def stats(self) -> CollectionStats:

@@ -1,5 +1,5 @@
 // builder.h -- one GPU's share of a build: the state behind `katome_builder` and the internal steps that the C ABI
-// (api.hip, kept_records.hip, count_routes.hip, host_build.cpp) and the sharded driver (dist.hip) compose.  Reference path: Build::create (builder.rs:42-54) ->
+// (api.hip, kept_records.hip, count_routes.hip, gfa.hip, host_build.cpp) and the sharded driver (dist.hip) compose.  Reference path: Build::create (builder.rs:42-54) ->
 // add_read_fastaq (pt_graph.rs:277-315) -> add_single_edge_fastaq (172-198) -> post-pass (333-345).
 #pragma once
 #include <vector>
@@ -113,6 +113,7 @@ struct katome_builder {
     ShrinkOutput collapse_shrunk;      // katome_dev_collapse: the shrunk graph its pieces name ...
     TextOutput assembly;               // ... and its result
     TextOutput unitig_text;            // result of katome_dev_contigs_text
+    GfaOutput gfa;                     // result of katome_dev_contigs_gfa
     DevBuf edge_age;                   // first-seen-order graphs once remove_* has moved edges (PruneGraph::edge_age)
     uint64_t n_nodes = 0;
     bool finalized = false;

@@ -19,6 +19,7 @@
 
 #include "collapse_exact.h"
 #include "common.h"
+#include "text_bases.h"
 
 namespace katome {
 namespace {
@@ -28,15 +29,9 @@ constexpr u32 WHOLE = KATOME_PIECE_WHOLE;
 constexpr int STORES = 2;                              // 16-byte stores per lane and tile
 constexpr u32 TILE = BLOCK * 16 * STORES;              // output bytes a workgroup owns at a time
 static_assert(TILE <= 65536, "offsets inside a tile are kept in 16 bits");
-constexpr u32 ACGT = 0x54474341u;                      // 'A' 'C' 'G' 'T', code 0 in the low byte
-constexpr u32 MAX_LABEL_BYTES = 1u << 29;              // a label of 2^31 bases: its sizes would not fit 32 bits
+constexpr u32 ACGT = TEXT_ACGT, MAX_LABEL_BYTES = TEXT_MAX_LABEL_BYTES;      // (text_bases.h: shared with gfa.hip)
 enum { ERR_PIECE = 1, ERR_LABEL = 2, ERR_CONTIG_LEN = 4, ERR_LABEL_LEN = 8, ERR_FIRST = 16 };
 
-__device__ __forceinline__ u32 decimal_digits(u64 v) {
-    u32 d = 1;
-    for (u64 t = 10; v >= t; t *= 10) { ++d; if (d == 20) break; }      // (10^20 does not fit 64 bits)
-    return d;
-}
 __device__ __forceinline__ u32 piece_word(const u32* pieces, u32 p) { return pieces ? pieces[p] : (p | WHOLE); }
 // bytes in front of a contig's bases (FASTA: ">katome_<i>\n"; i = the caller's first_contig + the contig's index, up to 20 digits)
 __device__ __forceinline__ u32 header_bytes(u32 fasta, u64 contig) { return fasta ? 9 + decimal_digits(contig) : 0; }
@@ -88,18 +83,6 @@ __global__ __launch_bounds__(BLOCK) void contig_bounds_kernel(const u32* __restr
     }
 }
 
-// the largest p < P with off[p] <= target (off ascending, off[0] = 0 <= target): every round the workgroup probes 256 places at once
-__device__ __forceinline__ u32 workgroup_search(const u64* __restrict__ off, u32 P, u64 target) {
-    u32 lo = 0, n = P;
-    while (n > 1) {
-        const u32 step = (n + BLOCK - 1) / BLOCK, at = threadIdx.x * step;
-        const int c = __syncthreads_count(at < n && off[lo + at] <= target);         // (a prefix of the threads: thread 0 always)
-        lo += (u32)(c - 1) * step;
-        n = min(step, n - (u32)(c - 1) * step);
-    }
-    return lo;
-}
-
 struct Piece {
     const uint8_t* src;       // the label's packed bases
     u32 first;                // the piece's first base in the label (0, or k - 1 for a remainder piece)
@@ -138,25 +121,6 @@ __device__ __forceinline__ u32 piece_byte(const Piece& pc, u32 r) {
     const u32 b = pc.first + r;
     return (ACGT >> (8 * ((pc.src[b >> 2] >> (6 - 2 * (b & 3))) & 3))) & 0xFF;
 }
-// 16 bases from base b on, as 16 ASCII bytes: the 32 bits are cut out of the two aligned words that hold them (the second one is
-// only read where the bits reach into it), first base in the top bits; four codes then select four bytes of "ACGT" at once
-__device__ __forceinline__ uint4 sixteen_bases(const uint8_t* src, u32 b) {
-    const uintptr_t a = (uintptr_t)(src + (b >> 2));
-    const u32 bit = 2 * (b & 3);
-    const uintptr_t a0 = a & ~(uintptr_t)3, a1 = (a + 3 + (bit ? 1 : 0)) & ~(uintptr_t)3;
-    const u32 hi = __builtin_bswap32(*(const u32*)a0), lo = __builtin_bswap32(*(const u32*)a1);
-    const u32 s = 8 * (u32)(a - a0) + bit;                              // 0 .. 30
-    const u32 v = s ? (hi << s) | (lo >> (32 - s)) : hi;                  // (s != 0 here means a1 == a0 + 4: the bits reach into it)
-    u32 out[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const u32 c = (v >> (24 - 8 * j)) & 0xFF;
-        const u32 sel = (c >> 6) | (((c >> 4) & 3) << 8) | (((c >> 2) & 3) << 16) | ((c & 3) << 24);
-        out[j] = __builtin_amdgcn_perm(0u, ACGT, sel);
-    }
-    return make_uint4(out[0], out[1], out[2], out[3]);
-}
-
 __global__ __launch_bounds__(BLOCK) void text_write_kernel(u32 k, const uint8_t* __restrict__ label, const u64* __restrict__ label_off,
                                                            const u32* __restrict__ pieces, u32 P, u32 fasta, u64 first_contig,
                                                            const u64* __restrict__ contig_idx, const u64* __restrict__ piece_off, u64 total,

@@ -103,6 +103,7 @@ enum Phase { PH_EXTRACT, PH_REGION_ORDER, PH_INSERT, PH_EMIT_EDGES, PH_SORT_EDGE
              // (appended: the indices above are what callers of katome_phase_name have seen so far)
              PH_GRAPH_STATS, PH_WEIGHT_SPECTRUM, K_STATS_DEGREES, K_STATS_WEIGHTS, K_STATS_NODES, K_SPECTRUM,
              PH_COLLAPSE, K_TEXT_WRITE,
+             PH_GFA, K_GFA_SORT, K_GFA_SIZES, K_GFA_WRITE,
              PH_COUNT };
 static const char* const PHASE_NAMES[PH_COUNT] = {
     "extract", "region_order", "insert", "emit_edges", "sort_edges", "node_set", "rank", "labels", "insert_tiles", "expand_tiles",
@@ -118,7 +119,8 @@ static const char* const PHASE_NAMES[PH_COUNT] = {
     "k:hash_group_index_kernel (tile records)", "k:lds_count_kernel (tile records)", "k:half_merge_kernel",
     "k:group_merge_kernel",
     "graph_stats", "weight_spectrum", "k:stats_degree_kernel", "k:stats_weight_kernel", "k:stats_node_kernel", "k:spectrum_kernel",
-    "collapse", "k:text_write_kernel"};
+    "collapse", "k:text_write_kernel",
+    "gfa", "k:gfa link sort", "k:gfa sizes", "k:gfa_write_kernel"};
 struct Profiler {
     bool on = false;
     struct Ev { int phase; hipEvent_t a, b; uint64_t work; };      // work: elements the launch processed (K_* entries)
@@ -435,6 +437,27 @@ int dev_pieces_text(uint32_t k, const uint8_t* label, const uint64_t* label_off,
                     uint32_t layout, uint64_t first_contig, TextOutput& out, hipStream_t stream);
 int dev_collapse(const ShrinkInput& g, const uint32_t* edge_age, ShrinkOutput& shrunk, uint32_t layout, TextOutput& out,
                  katome_collapse_stats* stats, std::vector<uint64_t>* lengths, hipStream_t stream);
+
+// gfa.hip: a shrink result as GFA 1 (include/katome_gpu.h has the format): the join of every edge into a vertex with every edge out
+// of it, the records' sizes and the text, partitioned by output bytes
+struct GfaGraph {
+    uint32_t k; uint64_t n_nodes, n_edges;
+    const uint64_t *edge_src, *edge_dst; const uint32_t *edge_weight, *edge_kmers;
+    const uint64_t* label_off; const uint8_t* label; uint64_t label_bytes;
+};
+// what dev_gfa_plan leaves for the writer: every line's offset (line 0 the header, 1 + i segment i, 1 + n_edges + l link l; one entry
+// more than lines), every segment's first base, every segment's first link (n_edges + 1), every link's two segments
+struct GfaPlan {
+    DevBuf line_off, segment_off, link_first, link_ab;
+    uint64_t n_links = 0, text_bytes = 0;
+};
+struct GfaOutput {
+    DevBuf text, segment_off, link_first;
+    uint64_t n_segments = 0, n_links = 0, text_bytes = 0;
+};
+int dev_gfa_plan(const GfaGraph& g, GfaPlan& plan, hipStream_t stream);                         // validates, joins, measures; synchronises
+int dev_gfa_write(const GfaGraph& g, const GfaPlan& plan, uint8_t* text, hipStream_t stream);  // text: plan.text_bytes rounded up to 16
+int dev_gfa(const GfaGraph& g, GfaOutput& out, hipStream_t stream);
 
 // Contigs::stats' panic sites as a status (contig_stats.h's 1, 2, 3: which tipping point is 0), one message wherever the stats are made
 inline int contig_stats_status(int which) {

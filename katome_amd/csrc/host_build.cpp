@@ -1,5 +1,5 @@
 // host_build.cpp -- the host-memory half of the C ABI of include/katome_gpu.h: katome_build_packed*, katome_build_files*,
-// katome_shrink_*, the host result arrays and the driver of a build over several GPUs.  No kernel is defined or launched here:
+// katome_shrink_*, katome_gfa_*, the host result arrays and the driver of a build over several GPUs.  No kernel is defined or launched here:
 // everything on the device goes through the device ABI (api.hip) and the sharded builder (dist*.hip).
 #include <stdlib.h>
 
@@ -55,6 +55,17 @@ struct AssemblyOwner {         // katome_assembly followed by what it owns
 void katome_assembly_free(katome_assembly* a) {
     if (!a) return;
     AssemblyOwner* o = reinterpret_cast<AssemblyOwner*>(a);
+    for (void* p : o->mem) free(p);
+    delete o;
+}
+
+struct GfaOwner {              // katome_gfa followed by what it owns
+    katome_gfa g;
+    std::vector<void*> mem;
+};
+void katome_gfa_free(katome_gfa* g) {
+    if (!g) return;
+    GfaOwner* o = reinterpret_cast<GfaOwner*>(g);
     for (void* p : o->mem) free(p);
     delete o;
 }
@@ -361,17 +372,60 @@ static int unitigs_to_host(katome_builder* b, uint64_t read_bytes, const Unitigs
     return stats_rc;
 }
 
-// what a host entry hands back: the graph, the graph after shrink, the assembly, or the unitigs' numbers (and their file)
+// the GFA's text is the file
+extern "C" int katome_gfa_save(const katome_gfa* g, const char* path) {
+    if (!g || !path) { set_error("null argument"); return KATOME_E_ARG; }
+    FILE* f = fopen(path, "wb");
+    if (!f) {
+        set_error("couldn't create %s: %s", path, CREATE_ERROR_KINDS[create_error_kind(errno)]);      // (katome_assembly_save's message)
+        return KATOME_E_OPEN;
+    }
+    const size_t n = g->text_bytes ? fwrite(g->text, 1, g->text_bytes, f) : 0;
+    if (fclose(f) != 0 || n != g->text_bytes) { set_error("couldn't write %s", path); return KATOME_E_OPEN; }
+    return KATOME_OK;
+}
+
+// katome_gfa_*: the flag's remove_dead_paths, the stage letters, shrink (AUTO: exact on a first-seen build, fast otherwise), the GFA of
+// the result copied to host arrays and, with a path, the file
+struct GfaWant { katome_gfa** out; const char* path; };
+static int gfa_to_host(katome_builder* b, uint64_t read_bytes, const GfaWant& want, const char* stages, uint64_t genome_len) {
+    katome_dev_graph dg;
+    if (stages && *stages && !b->first_seen) { set_error("stages after the build need KATOME_FLAG_FIRST_SEEN_ORDER"); return KATOME_E_ARG; }
+    KCHECK(katome_dev_finalize(b, &dg, nullptr));
+    if (b->s.flags & KATOME_FLAG_REMOVE_DEAD_PATHS) KCHECK(katome_dev_remove_dead_paths(b, &dg, nullptr, nullptr));
+    KCHECK(run_stages(stages, BuilderStages{b, genome_len}));
+    katome_dev_contigs dc;
+    KCHECK(katome_dev_shrink(b, &dc, nullptr));
+    katome_dev_gfa dgfa;
+    KCHECK(katome_dev_contigs_gfa(b, &dc, &dgfa, nullptr));
+    GfaOwner* o = new (std::nothrow) GfaOwner();
+    if (!o) { set_error("out of host memory"); return KATOME_E_OOM; }
+    memset(&o->g, 0, sizeof o->g);
+    katome_gfa* g = &o->g;
+    g->n_segments = dgfa.n_segments; g->n_links = dgfa.n_links; g->text_bytes = dgfa.text_bytes; g->read_bytes = read_bytes; g->k = b->s.k;
+    int rc = d2h(o, &g->text, dgfa.d_text, dgfa.text_bytes);
+    if (!rc) rc = d2h(o, &g->segment_off, dgfa.d_segment_off, dgfa.n_segments);
+    if (!rc) rc = d2h(o, &g->link_first, dgfa.d_link_first, dgfa.n_segments + 1);
+    if (rc) { katome_gfa_free(g); return rc; }
+    if (want.out) *want.out = g;
+    rc = want.path ? katome_gfa_save(g, want.path) : KATOME_OK;
+    if (!want.out) katome_gfa_free(g);
+    return rc;
+}
+
+// what a host entry hands back: the graph, the graph after shrink, the assembly, the unitigs' numbers (and their file), or the GFA
 struct Finish {
     katome_graph** graph; katome_contigs** contigs;
     AssembleWant assemble{nullptr, nullptr}; bool assembling = false;
     UnitigsWant unitigs{nullptr, nullptr}; bool want_unitigs = false;
+    GfaWant gfa{nullptr, nullptr}; bool want_gfa = false;
     const char* stages = nullptr; uint64_t genome_len = 0;
     uint32_t shrink_mode = KATOME_SHRINK_AUTO;
     katome_stats* stage_stats = nullptr;      // katome_build_*_staged_stats: the graph described before the first stage and after each
     int operator()(katome_builder* b, uint64_t read_bytes) const {
         if (assembling) return assembly_to_host(b, read_bytes, assemble, genome_len);
         if (want_unitigs) return unitigs_to_host(b, read_bytes, unitigs, stages, genome_len);
+        if (want_gfa) return gfa_to_host(b, read_bytes, gfa, stages, genome_len);
         return contigs ? contigs_to_host(b, read_bytes, contigs, shrink_mode) : graph_to_host(b, read_bytes, graph, stages, genome_len, stage_stats);
     }
 };
@@ -642,7 +696,8 @@ template <class AddReads>
 static int build_multi(const katome_settings* s, const Finish& finish, uint64_t read_bytes, const AddReads& add_reads) {
     const int n = s->n_devices;
     const bool share = (s->flags & KATOME_FLAG_RANKS_SHARE_DEVICE) != 0;
-    const MultiRoute route = plan_multi_route(s->flags, finish.contigs != nullptr, finish.stages, finish.assembling, finish.want_unitigs);
+    // (a GFA takes the assembly's route: gathered to the first GPU, where the stages, the shrink and the text run -- links cross ranks)
+    const MultiRoute route = plan_multi_route(s->flags, finish.contigs != nullptr, finish.stages, finish.assembling || finish.want_gfa, finish.want_unitigs);
     if (n > KATOME_MAX_RANKS) { set_error("n_devices = %d: at most %d", n, KATOME_MAX_RANKS); return KATOME_E_UNSUPPORTED; }
     KCHECK(use_device(s->device));
     int n_visible = 0;
@@ -852,6 +907,23 @@ int katome_unitigs_packed(const katome_settings* s, const uint8_t* packed, uint6
     KCHECK(unitigs_finish(s, stages, original_genome_length, out_path, out, f));
     return build_packed_impl(s, packed, n_reads, read_len, skip, f);
 }
+// (the same check on every route, before any GPU work)
+static int gfa_finish(const katome_settings* s, const char* stages, uint64_t genome_len, const char* out_path, katome_gfa** out, Finish& f) {
+    if (!out && !out_path) { set_error("null argument"); return KATOME_E_ARG; }
+    if (out) *out = nullptr;
+    if (s && !(s->flags & KATOME_FLAG_FIRST_SEEN_ORDER) && stages && *stages) {
+        set_error("stages after the build need KATOME_FLAG_FIRST_SEEN_ORDER");
+        return KATOME_E_ARG;
+    }
+    f.gfa = GfaWant{out, out_path}; f.want_gfa = true; f.stages = stages; f.genome_len = genome_len;
+    return KATOME_OK;
+}
+int katome_gfa_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip, const char* stages,
+                      uint64_t original_genome_length, const char* out_path, katome_gfa** out) {
+    Finish f{nullptr, nullptr};
+    KCHECK(gfa_finish(s, stages, original_genome_length, out_path, out, f));
+    return build_packed_impl(s, packed, n_reads, read_len, skip, f);
+}
 int katome_shrink_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len,
                          const uint8_t* skip, katome_contigs** out) {
     if (!out) { set_error("null argument"); return KATOME_E_ARG; }
@@ -1015,6 +1087,12 @@ int katome_unitigs_files(const katome_settings* s, const char* const* paths, siz
                          const char* out_path, katome_unitigs* out) {
     Finish f{nullptr, nullptr};
     KCHECK(unitigs_finish(s, stages, original_genome_length, out_path, out, f));
+    return build_files_impl(s, paths, n_paths, f);
+}
+int katome_gfa_files(const katome_settings* s, const char* const* paths, size_t n_paths, const char* stages, uint64_t original_genome_length,
+                     const char* out_path, katome_gfa** out) {
+    Finish f{nullptr, nullptr};
+    KCHECK(gfa_finish(s, stages, original_genome_length, out_path, out, f));
     return build_files_impl(s, paths, n_paths, f);
 }
 int katome_shrink_files(const katome_settings* s, const char* const* paths, size_t n_paths, katome_contigs** out) {

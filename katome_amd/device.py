@@ -132,6 +132,28 @@ class DeviceContigs:
         _check(_lib.lib().katome_dev_contigs_text(self._builder._h, C.byref(self._dc), LAYOUTS[layout], C.byref(da), _stream()))
         return DeviceAssembly(da, self._builder, self._builder.tdev)
 
+    def gfa(self):
+        """the shrunk graph as GFA 1, written on the device (katome_dev_contigs_gfa; include/katome_gpu.h has the format) ->
+        DeviceGfa; valid for the builder's last shrink() only, and until the next gfa()"""
+        dg = _lib.DevGfa()
+        _check(_lib.lib().katome_dev_contigs_gfa(self._builder._h, C.byref(self._dc), C.byref(dg), _stream()))
+        return DeviceGfa(dg.n_segments, dg.n_links, dg.text_bytes, _view(dg.d_text, (dg.text_bytes,), "|u1", self._builder, self._builder.tdev),
+                         _view(dg.d_segment_off, (dg.n_segments,), "<i8", self._builder, self._builder.tdev),
+                         _view(dg.d_link_first, (dg.n_segments + 1,), "<i8", self._builder, self._builder.tdev))
+
+
+class DeviceGfa:
+    """a GFA 1 text in HBM: text (uint8, text_bytes of them) is the file; segment_off[i] = offset of segment i's first base;
+    the L lines of segment a are lines link_first[a] .. link_first[a + 1] of the L region"""
+
+    def __init__(self, n_segments, n_links, text_bytes, text, segment_off, link_first):
+        self.n_segments, self.n_links, self.text_bytes = n_segments, n_links, text_bytes
+        self.text, self.segment_off, self.link_first = text, segment_off, link_first
+
+    def bytes(self):
+        """host: the file's bytes"""
+        return bytes(self.text.cpu().numpy())
+
 
 LAYOUTS = {"plain": 0, "fasta": 1}
 
@@ -640,6 +662,27 @@ def pieces_text(labels, label_off, pieces, k, layout="plain", device=0, first_co
     _check(L.katome_dev_pieces_text_numbered(device, k, _ptr(labels), _ptr(label_off), n_labels, _ptr(pieces), n_pieces, LAYOUTS[layout],
                                              first_contig, _ptr(off), _ptr(length), nc.value, _ptr(text), cap, C.byref(nc), C.byref(nb), _stream()))
     return off[:nc.value], length[:nc.value], text, nb.value
+
+
+def gfa_arrays(k, n_nodes, edge_src, edge_dst, edge_weight, edge_kmers, edge_label_off, edge_label, device=0, label_bytes=None):
+    """the GFA kernels on the caller's tensors (katome_dev_gfa_arrays): a graph in the layout of DeviceContigs -- edge_src /
+    edge_dst / edge_label_off int64, edge_weight / edge_kmers int32, edge_label uint8 in an allocation that is a multiple of 4
+    bytes (label_bytes: how many of them are labels, default all) -> DeviceGfa (text: text_bytes of a buffer rounded up to 16)"""
+    tdev = edge_label_off.device
+    n_edges = edge_label_off.numel() - 1
+    if label_bytes is None:
+        label_bytes = edge_label.numel()
+    nl, nb = C.c_uint64(), C.c_uint64()
+    L = _lib.lib()
+    args = (device, k, n_nodes, n_edges, _ptr(edge_src), _ptr(edge_dst), _ptr(edge_weight), _ptr(edge_kmers), _ptr(edge_label_off),
+            _ptr(edge_label), label_bytes)
+    _check(L.katome_dev_gfa_arrays(*args, None, None, None, 0, C.byref(nl), C.byref(nb), _stream()))
+    cap = (nb.value + 15) // 16 * 16
+    seg = torch.empty(max(n_edges, 1), dtype=torch.int64, device=tdev)
+    first = torch.empty(n_edges + 1, dtype=torch.int64, device=tdev)
+    text = torch.empty(max(cap, 16), dtype=torch.uint8, device=tdev)
+    _check(L.katome_dev_gfa_arrays(*args, _ptr(seg), _ptr(first), _ptr(text), cap, C.byref(nl), C.byref(nb), _stream()))
+    return DeviceGfa(n_edges, nl.value, nb.value, text[:nb.value], seg[:n_edges], first)
 
 
 def synth_reads(first_read, n_reads, read_len, genome_len, err_rate, n_inject_percent=0, device=0):
