@@ -882,6 +882,14 @@ int katome_dev_scan_counts(int device, const uint32_t *d_counts, uint64_t m, uin
 int katome_dev_list_first_pass(int device, const uint64_t *d_tiles, const uint32_t *d_counts, uint64_t n_tiles, uint32_t tile_bases,
                                uint32_t k, uint32_t span, uint32_t stride, int rc, int rep, int fused, uint64_t *d_keys,
                                uint32_t *d_weights, uint32_t *d_digit_counts, void *stream);
+/* test entry: the one partition pass that S2 of the ordered k-mer count takes when its writer placed it by its first digit.
+ * used[256] (host): the keys of every region; region d lies from start[d] on in d_keys / d_weights / d_digits, start[] (257 of them,
+ * the last one the arrays' length) being what katome_s2_region_starts gives for `used` -- every region a whole number of 4096-key
+ * tiles.  d_digits: bits 2k - 8 .. 2k - 1 of every key, one byte each at the key's index.  d_keys_out / d_weights_out: the sum of
+ * used[] records, the regions read in digit order and partitioned by those bits, stable (synchronises)                              */
+void katome_s2_region_starts(const uint64_t *used, uint64_t *start);
+int katome_dev_s2_region_pass(int device, uint32_t k, const uint64_t *used, const uint64_t *d_keys, const uint32_t *d_weights,
+                              const uint8_t *d_digits, uint64_t *d_keys_out, uint32_t *d_weights_out, void *stream);
 /* in-place unique of sorted keys; returns the new count (synchronises)                     */
 int katome_dev_unique(int device, uint64_t *d_keys, uint64_t n, uint32_t key_words, uint64_t *n_out,
                       void *stream);

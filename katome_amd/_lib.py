@@ -233,6 +233,8 @@ SYMBOLS = {
     "katome_dev_cache_stats": (_i, [_i, u64p]),
     "katome_dev_sort": (_i, [_i, _vp, _vp, _u64, _u32, _u32, _vp]),
     "katome_dev_list_first_pass": (_i, [_i, _vp, _vp, _u64, _u32, _u32, _u32, _u32, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "katome_s2_region_starts": (None, [u64p, u64p]),
+    "katome_dev_s2_region_pass": (_i, [_i, _u32, u64p, _vp, _vp, _vp, _vp, _vp, _vp]),
     "katome_dev_unique": (_i, [_i, _vp, _u64, _u32, u64p, _vp]),
     "katome_dev_rank": (_i, [_i, _vp, _u64, _u32, _u32, _vp, _u64, _vp, _vp]),
     "katome_dev_node_ids": (_i, [_i, _vp, _u64, _u32, _vp, _vp, _vp, u64p, _vp]),

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "builder.h"
+#include "s2_regions.h"
 
 extern "C" {
 
@@ -1066,6 +1067,22 @@ int katome_dev_list_first_pass(int device, const uint64_t* d_tiles, const uint32
     if (n_tiles && (!d_tiles || !d_counts || !d_keys || !d_weights || !d_digit_counts)) { set_error("null argument"); return KATOME_E_ARG; }
     if (!span || tile_bases < k || (uint64_t)stride * (span - 1) + k > tile_bases || k < 9 || tile_bases > 64) { set_error("first pass off a list: the sub-windows do not lie in the tile"); return KATOME_E_ARG; }
     return dev_list_first_pass(d_tiles, d_counts, n_tiles, tile_bases, k, span, stride, rc != 0, rep != 0, fused != 0, d_keys, d_weights, d_digit_counts, (hipStream_t)stream);
+}
+void katome_s2_region_starts(const uint64_t* used, uint64_t* start) {
+    uint64_t cap[S2_REGIONS];
+    for (uint32_t d = 0; d < S2_REGIONS; ++d) cap[d] = s2_tiles(used[d]) * S2_REGION_TILE;
+    s2_region_starts(cap, start);
+}
+int katome_dev_s2_region_pass(int device, uint32_t k, const uint64_t* used, const uint64_t* d_keys, const uint32_t* d_weights, const uint8_t* d_digits,
+                              uint64_t* d_keys_out, uint32_t* d_weights_out, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    KCHECK(use_device(device));
+    if (!used || !d_keys || !d_weights || !d_digits || !d_keys_out || !d_weights_out) { set_error("null argument"); return KATOME_E_ARG; }
+    uint64_t start[S2_REGIONS + 1];
+    katome_s2_region_starts(used, start);
+    KCHECK(dev_s2_region_pass(d_keys, d_weights, d_digits, k, start, used, d_keys_out, d_weights_out, nullptr, stream));
+    KCHECK_HIP(hipStreamSynchronize(stream));
+    return KATOME_OK;
 }
 int katome_dev_unique(int device, uint64_t* d_keys, uint64_t n, uint32_t key_words, uint64_t* n_out, void* stream) {
     KCHECK(use_device(device));

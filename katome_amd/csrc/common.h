@@ -293,6 +293,12 @@ int dev_key_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32
 // list_to_records_hist_kernel and the pass over the written records
 int dev_list_first_pass(const uint64_t* d_tiles, const uint32_t* d_counts, uint64_t n_tiles, uint32_t tile_bases, uint32_t k, uint32_t span, uint32_t stride,
                         bool rc, bool rep, bool fused, uint64_t* d_keys, uint32_t* d_weights, uint32_t* d_digit_counts, hipStream_t stream);
+// One-word (key, count) records lying in the 256 regions of s2_regions.h -- region d from start[d] on, used[d] of them, all of first
+// digit d; digits: bits 2k - 8 .. 2k - 1 of every key, one byte each at the key's index -- partitioned by those bits into k_out /
+// w_out, dense and stable: the regions in digit order, so that the 16-bit groups come out contiguous.  Counts its tiles from the
+// bytes.  *n_tiles: the tiles the pass walked.  (katome_dev_s2_region_pass is its test entry)
+int dev_s2_region_pass(const uint64_t* d_keys, const uint32_t* d_w, const uint8_t* d_digits, uint32_t k, const uint64_t* start, const uint64_t* used,
+                       uint64_t* k_out, uint32_t* w_out, uint64_t* n_tiles, hipStream_t stream);
 size_t dev_digit_stream_bytes(uint64_t n, uint32_t nw);
 bool dev_digit_stream_pays(uint32_t nw);        // do records of nw words get a digit stream between their two partition passes?
 // index[g] (65537 of them) = first of n ascending one-word keys whose bits [shift, shift + 16) are >= g
@@ -573,9 +579,13 @@ struct HalfSort {
     uint64_t n_s1 = 0, n_s2 = 0;
     uint32_t k = 0;
     bool taken = false;
+    // regions (s2_regions.h): S2 lies in 256 regions by its first partition digit -- region d from region_start[d] on, region_used[d]
+    // keys --, and s2_digit holds the SECOND digit of every key; half_sort_finish makes it dense with that one pass (dev_s2_region_pass)
+    bool regions = false;
+    uint64_t region_start[257] = {0}, region_used[256] = {0};
     void release() {
         s1_key.release(); s1_w.release(); group_first.release(); group_count.release(); s2_key.release(); s2_w.release(); s2_digit.release();
-        n_s1 = n_s2 = 0; taken = false;
+        n_s1 = n_s2 = 0; taken = false; regions = false;
     }
 };
 // (head_counts: filled with the merge's source run heads per block of edges -- dev_group_merge -- where the merge makes them, else released)

@@ -2,10 +2,12 @@
 // tables and leave as oriented edges or as the list of distinct keys.  The kernels, one per slot shape, and the host code that picks one
 // for a level (records_to_edges_sorted, tagged_records_sorted; sizes and planning arithmetic: lds_plan.h).  The table in HBM: table.hip.
 #include <algorithm>
+#include <vector>
 
 #include "common.h"
 #include "lds_order.h"
 #include "lds_plan.h"
+#include "s2_regions.h"
 #include "slot_bits.h"
 
 namespace katome {
@@ -19,7 +21,9 @@ namespace katome {
 // threshold), as one contiguous stretch behind a cursor.
 // ---------------------------------------------------------------------------------------------
 // (-DKATOME_LC_PHASES: an experiment build that adds up, per phase of the two counting kernels, the shader clocks thread 0 of every
-// workgroup sees go by -- tools/lc_phases.py reads them through katome_debug_lc_phases; never defined in the shipped library)
+// workgroup sees go by -- tools/lc_phases.py reads them through katome_debug_lc_phases; never defined in the shipped library.
+// 4 .. 7: the ordered kernel's REGIONS write phase -- S1 and the entries into registers, the digit count, scan and reservation, the
+// reorder; the stream-out is what is left of phase 15)
 #ifdef KATOME_LC_PHASES
 __device__ unsigned long long lc_phase_cycles[16];
 #define LC_PHASE_BEGIN() unsigned long long lc_t0 = clock64()
@@ -350,11 +354,27 @@ constexpr u32 LO_FINE_SLOT = (LP_SLOTS - (lds_order_words(LDS_ORDER_FINE_BITS) +
 constexpr u32 LO_FINE_MAX = LO_FINE_SLOT;
 constexpr size_t LO_LDS = (size_t)LP_SLOTS * 8 + LO_COARSE_WORDS * 4;
 static_assert((LP_SLOTS - LO_FINE_SLOT) * 2 >= lds_order_words(LDS_ORDER_FINE_BITS), "the fine buckets fit the table's tail");
-template <bool RC>
+// REGIONS (round 22): S2 leaves by the digit of its FIRST partition pass, bits 2k - 16 .. 2k - 9 of the reverse complement -- region d
+// of s2_key / s2_w / s2_digit starts at tile reg.start_tile[d], takes reg.cap[d] keys and has its append cursor at reg.cursor[d * S2_CURSOR_STEP]
+// (s2_regions.h; a 128-byte line to a cursor) -- with the SECOND pass's digit, bits 2k - 8 .. 2k - 1, in the byte stream: that
+// first pass then has nothing left to do (radix.hip, dev_s2_region_pass).  After S1 has left, every thread takes its entries of
+// slot[0, total) into registers as reverse complements and counts their digits into 256 LDS bins (the atomic's return value is the entry's arrival index);
+// the bins are scanned, threads 0 .. 255 reserve their digit's keys with one returning atomic on the region's cursor, every entry
+// goes back to slot[dstart[d] + arrival] (the scatter kernel's LDS reorder) and slot[] is streamed out, consecutive lanes to
+// consecutive addresses inside a digit's run.  The bins, their starts and the regions' offsets lie in the bucket words behind the
+// table, free by then.  No workgroup waits for another.  A region without room for the group's keys: err[1] = d + 1 and the group
+// writes no S2 (the host then rebuilds S2 from S1: s2_rebuild_kernel); the other groups go on.
+constexpr u32 S2_CURSOR_STEP = 16;          // u64 words between two regions' cursors
+// (32 bits each for a region's first tile and its keys: a level counted this way has fewer than 2^32 records, s2_regions_route)
+struct S2RegionsOut { const u32* start_tile; const u32* cap; unsigned long long* cursor; };
+// (Reg: one S2RegionsOut with REGIONS, nothing without -- the kernel's arguments are then the ones it had)
+template <bool RC, bool REGIONS = false, class... Reg>
 __global__ __launch_bounds__(LC_THREADS) void lds_count_ordered_kernel(const u64* keys, const u32* wts, const u64* __restrict__ index, u32 k,
                                                                         u32 min_weight, u64* s1_key, u32* s1_w, u32* group_count, u64* s2_key,
                                                                         u32* s2_w, uint8_t* s2_digit, u64 s2_cap, unsigned long long* cursor,
-                                                                        unsigned long long* distinct, u32* err, u32 probe_limit) {
+                                                                        unsigned long long* distinct, u32* err, u32 probe_limit, Reg... regions) {
+    static_assert(!REGIONS || RC, "one strand has no S2");
+    static_assert(sizeof...(Reg) == (REGIONS ? 1 : 0), "the regions come with REGIONS only");
     extern __shared__ unsigned long long lc_mem[];
     unsigned long long* slot = lc_mem;                                   // [LP_SLOTS]: remainder << 16 | count; then the kept ones in key order
     u32* bucket = reinterpret_cast<u32*>(lc_mem + LP_SLOTS);             // [LO_COARSE_WORDS]: the 2048 buckets of a table too full for ...
@@ -362,6 +382,8 @@ __global__ __launch_bounds__(LC_THREADS) void lds_count_ordered_kernel(const u64
     __shared__ u32 wtot[LC_THREADS / 64];
     __shared__ unsigned long long base_sh;
     __shared__ u32 kept_sh;
+    constexpr u32 RG_BINS = 256, RG_FULL = LO_COARSE_WORDS - 1;          // (REGIONS: bucket[RG_FULL] -- a region had no room for this group's keys)
+    static_assert(4 * RG_BINS < RG_FULL && lds_order_words(LDS_ORDER_COARSE_BITS) <= RG_FULL, "the bins, their starts, the regions' offsets and the flag fit the bucket words");
     const u32 tid = threadIdx.x, lane = tid & 63;
     const u32 rem_bits = 2 * k - 16;
     const u32 bshift_c = rem_bits > LDS_ORDER_COARSE_BITS ? rem_bits - LDS_ORDER_COARSE_BITS : 0;          // (bucket: the remainder's top bits)
@@ -444,6 +466,95 @@ __global__ __launch_bounds__(LC_THREADS) void lds_count_ordered_kernel(const u64
         const u32 total = kept_sh <= LO_FINE_MAX ? lds_order_entries<LP_PER, LDS_ORDER_FINE_BITS>(v, keep, slot, fine, wtot, bshift_f, reserve, stamp)
                                                  : lds_order_entries<LP_PER, LDS_ORDER_COARSE_BITS>(v, keep, slot, bucket, wtot, bshift_c, reserve, stamp);
         LC_PHASE(14);
+        if constexpr (REGIONS) {
+            const S2RegionsOut reg = [](const S2RegionsOut& r) { return r; }(regions...);
+            u32* hist = bucket;                                               // [256] keys per digit; then their starts in slot[]
+            u32* dstart = bucket + RG_BINS;                                   // [256]
+            u64* goff = reinterpret_cast<u64*>(bucket + 2 * RG_BINS);         // [256] where the digit's keys go in the region arrays
+            if (rt < RG_BINS) hist[rt] = 0u;
+            if (rt == 0) bucket[RG_FULL] = 0u;
+            unsigned long long e[LP_PER]; u32 arr[(LP_PER + 1) / 2];
+#pragma unroll
+            for (u32 t = 0; t < (LP_PER + 1) / 2; ++t) arr[t] = 0;
+            // (an entry turns into its reverse complement here, once: r's low 16 bits are the group's -- the reverse complement of the
+            // prefix g --, so r's other bits and the 16-bit count fit the entry's 64 bits, and r is one and-or away from then on)
+            Key<1> gx; gx.w[0] = (u64)g << rem_bits;
+            const u32 r_low = (u32)revcomp(gx, k).w[0] & 0xFFFFu;
+#pragma unroll
+            for (u32 t = 0; t < LP_PER; ++t) {
+                const u32 i = rt + t * LC_THREADS;
+                e[t] = 0;
+                if (i >= total) continue;
+                e[t] = slot[i];
+                Key<1> x; x.w[0] = gx.w[0] | (e[t] >> 16);
+                const u32 c = (u32)e[t] & 0xFFFFu;
+                if (lo + i < hi) { s1_key[lo + i] = x.w[0]; s1_w[lo + i] = c; }
+                e[t] = (revcomp(x, k).w[0] & ~0xFFFFull) | c;
+            }
+            const auto rc_of = [&](unsigned long long en) { return (en & ~0xFFFFull) | r_low; };
+            __syncthreads();
+            LC_PHASE(4);
+#pragma unroll
+            for (u32 t = 0; t < LP_PER; ++t) {
+                if (rt + t * LC_THREADS >= total) continue;
+                const u32 d = (u32)(rc_of(e[t]) >> rem_bits) & (RG_BINS - 1);
+                arr[t >> 1] |= atomicAdd(&hist[d], 1u) << ((t & 1u) * 16u);          // (a group holds fewer than 2^16 entries)
+            }
+            __syncthreads();
+            LC_PHASE(5);
+            // (the reservation's round trip and the loads of the region's room and start run under the scan and the reorder: thread d
+            // asks for digit d's place in its region, thread 256 + d for the region's keys, thread 512 + d for its first tile -- one
+            // register each --, and the three meet in LDS after the reorder)
+            static_assert(LC_THREADS >= 3 * RG_BINS, "three threads per digit");
+            u32 incl = 0, held = 0;
+            {
+                const u32 d = rt & (RG_BINS - 1), c = hist[d];
+                if (rt < RG_BINS) {
+                    if (c) held = (u32)atomicAdd(&reg.cursor[d * S2_CURSOR_STEP], (unsigned long long)c);
+                    incl = c;
+#pragma unroll
+                    for (int o = 1; o < 64; o <<= 1) { const u32 up = __shfl_up(incl, o, 64); if (lane >= (u32)o) incl += up; }
+                    if (lane == 63) wtot[rt >> 6] = incl;
+                } else if (rt < 2 * RG_BINS) held = reg.cap[d];
+                else if (rt < 3 * RG_BINS) held = reg.start_tile[d];
+            }
+            __syncthreads();
+            if (rt < RG_BINS) {
+                u32 woff = 0;
+#pragma unroll
+                for (u32 w = 0; w < RG_BINS / 64; ++w) if (w < (rt >> 6)) woff += wtot[w];
+                dstart[rt] = woff + incl - hist[rt];
+            }
+            __syncthreads();
+            LC_PHASE(6);
+#pragma unroll
+            for (u32 t = 0; t < LP_PER; ++t) {
+                if (rt + t * LC_THREADS >= total) continue;
+                const u32 d = (u32)(rc_of(e[t]) >> rem_bits) & (RG_BINS - 1);
+                slot[dstart[d] + ((arr[t >> 1] >> ((t & 1u) * 16u)) & 0xFFFFu)] = e[t];
+            }
+            if (rt >= RG_BINS && rt < 2 * RG_BINS) {          // hist[d]: the last place in the region that still takes the group's keys
+                const u32 d = rt - RG_BINS, c = hist[d];
+                if (c > held) { bucket[RG_FULL] = 1u; err[1] = d + 1; }
+                hist[d] = held - c;
+            } else if (rt >= 2 * RG_BINS && rt < 3 * RG_BINS) goff[rt - 2 * RG_BINS] = (u64)held * S2_REGION_TILE;
+            __syncthreads();
+            if (rt < RG_BINS) {          // (a digit without keys asked for no place: held = 0)
+                if (held > hist[rt]) { bucket[RG_FULL] = 1u; err[1] = rt + 1; }
+                goff[rt] += held;
+            }
+            __syncthreads();
+            LC_PHASE(7);
+            if (!bucket[RG_FULL]) {          // (the same for every thread)
+                for (u32 i = rt; i < total; i += LC_THREADS) {
+                    const unsigned long long en = slot[i];
+                    const u64 r = rc_of(en);
+                    const u32 d = (u32)(r >> rem_bits) & (RG_BINS - 1);
+                    const u64 to = goff[d] + (i - dstart[d]);
+                    s2_key[to] = r; s2_w[to] = (u32)en & 0xFFFFu; s2_digit[to] = (uint8_t)(r >> (rem_bits + 8));
+                }
+            }
+        } else
         for (u32 i = rt; i < total; i += LC_THREADS) {
             const unsigned long long e = slot[i];
             Key<1> x; x.w[0] = ((u64)g << rem_bits) | (e >> 16);
@@ -460,6 +571,40 @@ __global__ __launch_bounds__(LC_THREADS) void lds_count_ordered_kernel(const u64
     }
     my_distinct = wave_sum(my_distinct);
     if (lane == 0 && my_distinct) atomicAdd(distinct, (unsigned long long)my_distinct);
+}
+
+// How many of a level's ordered records have a reverse complement of first partition digit d (bits 2k - 16 .. 2k - 9), counted on
+// the sample of s2_regions.h: rows `stride` apart, 256 records each.  counts: 256 words, zero on entry.
+static_assert(S2_SAMPLE_ROW == BLOCK && S2_REGIONS == (u32)BLOCK, "a thread per record of a row and per bin");
+__global__ __launch_bounds__(BLOCK) void s2_region_sample_kernel(const u64* __restrict__ keys, u64 n, u32 k, u64 rows, u64 stride, u32* counts) {
+    __shared__ u32 h[S2_REGIONS];
+    h[threadIdx.x] = 0u;
+    __syncthreads();
+    for (u64 r = blockIdx.x; r < rows; r += gridDim.x) {
+        const u64 i = r * stride * S2_SAMPLE_ROW + threadIdx.x;
+        if (i >= n) continue;
+        Key<1> x; x.w[0] = keys[i];
+        atomicAdd(&h[(u32)(revcomp(x, k).w[0] >> (2 * k - 16)) & (S2_REGIONS - 1)], 1u);
+    }
+    __syncthreads();
+    if (h[threadIdx.x]) atomicAdd(&counts[threadIdx.x], h[threadIdx.x]);
+}
+
+// The way back of the REGIONS count: S2 made again from S1, which is complete in place -- group g's reverse complements at
+// off[g] .. off[g] + group_count[g] (off: the counts' prefix sums), with their first partition digits, as the count without regions
+// leaves them but for the order, which nobody depends on
+__global__ __launch_bounds__(BLOCK) void s2_rebuild_kernel(const u64* __restrict__ s1_key, const u32* __restrict__ s1_w, const u64* __restrict__ group_first,
+                                                           const u32* __restrict__ group_count, const u64* __restrict__ off, u32 k, u64* s2_key,
+                                                           u32* s2_w, uint8_t* s2_digit, u64 s2_cap) {
+    for (u32 g = blockIdx.x; g < (1u << 16); g += gridDim.x) {
+        const u64 from = group_first[g], to = off[g];
+        const u32 c = group_count[g];
+        for (u32 i = threadIdx.x; i < c; i += BLOCK) {
+            Key<1> x; x.w[0] = s1_key[from + i];
+            const u64 r = revcomp(x, k).w[0];
+            if (to + i < s2_cap) { s2_key[to + i] = r; s2_w[to + i] = s1_w[from + i]; s2_digit[to + i] = (uint8_t)(r >> (2 * k - 16)); }
+        }
+    }
 }
 
 // in place: the level's one-word k-mer records in their representative orientation (rep) or back in the canonical one
@@ -1086,6 +1231,8 @@ struct LcAux {
     DevBuf buf, owners;
     hipStream_t stream;
     const u64* index = nullptr; u32 gbits = 0, n_owners = 0;
+    // (more: device words a kernel leaves beside the 64 bytes -- the ordered count's region cursors --, read back with them)
+    const void* more = nullptr; void* more_host = nullptr; size_t more_bytes = 0;
     explicit LcAux(hipStream_t s) : buf(s), owners(s), stream(s) {}
     unsigned long long* cursor() const { return buf.as<unsigned long long>(); }
     unsigned long long* distinct() const { return cursor() + 1; }
@@ -1097,7 +1244,7 @@ struct LcAux {
         return KATOME_OK;
     }
 };
-struct LcResult { uint64_t n_out = 0, n_distinct = 0; uint32_t code = 0; };
+struct LcResult { uint64_t n_out = 0, n_distinct = 0; uint32_t code = 0, full = 0; };      // full: err[1] (the ordered count's regions)
 
 // One attempt of one counting kernel over the level's groups: counters cleared, the kernel on 256 workgroups, and what it left in
 // `aux` read back (n: the level's records, for the timer)
@@ -1112,8 +1259,9 @@ static int lc_launch(LcAux& aux, void (*kernel)(P...), size_t lds, uint64_t n, L
     KCHECK_HIP(hipGetLastError());
     uint64_t h[3] = {0, 0, 0};
     KCHECK_HIP(hipMemcpyAsync(h, aux.buf.p, 24, hipMemcpyDeviceToHost, aux.stream));
+    if (aux.more) KCHECK_HIP(hipMemcpyAsync(aux.more_host, aux.more, aux.more_bytes, hipMemcpyDeviceToHost, aux.stream));
     KCHECK_HIP(hipStreamSynchronize(aux.stream));
-    r.n_out = h[0]; r.n_distinct = h[1]; r.code = (uint32_t)h[2];
+    r.n_out = h[0]; r.n_distinct = h[1]; r.code = (uint32_t)h[2]; r.full = (uint32_t)(h[2] >> 32);
     return KATOME_OK;
 }
 
@@ -1200,6 +1348,69 @@ int table_orient_records(uint64_t* d_keys, uint64_t n, uint32_t k, bool rep, hip
     return KATOME_OK;
 }
 
+static bool s2_group_sort_on() { static const bool on = env_flag("KATOME_S2_GROUP_SORT", true); return on; }
+// KATOME_S2_REGIONS: S2 written by its first partition digit (lds_count_ordered_kernel with REGIONS; one partition pass instead of
+// two in half_sort_finish).  0: never; 1: for a level of S2_REGIONS_MIN_RECORDS (2^30) or more; 2: however small (tests).  Not with
+// KATOME_S2_GROUP_SORT=0, whose full sort takes S2 as it comes.  KATOME_S2_REGION_CAP=n: no region takes more than n keys (tests of
+// the way back)
+static bool s2_regions_route(uint64_t n) {
+    static const int mode = env_int("KATOME_S2_REGIONS", 1);
+    return mode && s2_group_sort_on() && (n >= S2_REGIONS_MIN_RECORDS || mode == 2) && n < (1ull << 32);
+}
+static uint64_t s2_region_cap_limit() {
+    static const uint64_t cap = [] { const char* e = getenv("KATOME_S2_REGION_CAP"); return e ? strtoull(e, nullptr, 10) : UINT64_MAX; }();
+    return cap;
+}
+// The regions of a level of n ordered records ko: their sizes from a sample of the records (s2_regions.h), S2's arrays that large,
+// {start, cap} and the cleared cursors on the device.  *on = false: no memory for them (they may exceed the n + 1 keys of the count
+// without regions by n / 16 + 512 tiles) -- the caller takes that route, nothing is allocated
+static int s2_regions_open(const u64* ko, uint64_t n, uint32_t k, HalfSort& hs, DevBuf& table, DevBuf& cursors, hipStream_t stream, bool* on) {
+    *on = false;
+    const S2Sample sp = s2_sample_plan(n);
+    DevBuf counts(stream);
+    KCHECK(counts.alloc(S2_REGIONS * 4));
+    KCHECK_HIP(hipMemsetAsync(counts.p, 0, S2_REGIONS * 4, stream));
+    hipLaunchKernelGGL(s2_region_sample_kernel, dim3(grid_for(sp.rows, 1)), dim3(BLOCK), 0, stream, ko, n, k, sp.rows, sp.stride, counts.as<u32>());
+    KCHECK_HIP(hipGetLastError());
+    uint32_t h[S2_REGIONS];
+    KCHECK_HIP(hipMemcpyAsync(h, counts.p, sizeof h, hipMemcpyDeviceToHost, stream));
+    KCHECK_HIP(hipStreamSynchronize(stream));
+    uint32_t cap[2 * S2_REGIONS];          // (the regions' first tiles, and behind them their keys, in one upload)
+    {
+        uint64_t c[S2_REGIONS];
+        s2_region_caps(h, s2_sample_records(n, sp), n, c);
+        s2_region_starts(c, hs.region_start);
+        for (uint32_t d = 0; d < S2_REGIONS; ++d) {
+            cap[d] = (uint32_t)(hs.region_start[d] / S2_REGION_TILE);
+            cap[S2_REGIONS + d] = (uint32_t)std::min<uint64_t>(std::min(c[d], s2_region_cap_limit()), UINT32_MAX);
+        }
+    }
+    const uint64_t total = hs.region_start[S2_REGIONS];
+    if (hs.s2_key.alloc(total * 8, stream) != KATOME_OK || hs.s2_w.alloc(total * 4, stream) != KATOME_OK || hs.s2_digit.alloc(total, stream) != KATOME_OK ||
+        table.alloc(sizeof cap) != KATOME_OK || cursors.alloc((size_t)S2_REGIONS * S2_CURSOR_STEP * 8) != KATOME_OK) {
+        hs.s2_key.release(); hs.s2_w.release(); hs.s2_digit.release(); table.release(); cursors.release();
+        lc_trace("[half sort] S2 regions: no memory for %llu keys; S2 behind one cursor\n", (unsigned long long)total);
+        return KATOME_OK;
+    }
+    KCHECK_HIP(hipMemcpyAsync(table.p, cap, sizeof cap, hipMemcpyHostToDevice, stream));
+    KCHECK_HIP(hipMemsetAsync(cursors.p, 0, cursors.bytes, stream));
+    *on = true;
+    return KATOME_OK;
+}
+// ... and the way back when a region filled: S2 again from S1, behind the groups' prefix sums, with its first-pass digits
+static int s2_rebuild(HalfSort& hs, uint64_t n_out, uint32_t k, hipStream_t stream) {
+    const u64 s2_cap = n_out + 1;
+    KCHECK(hs.s2_key.alloc(s2_cap * 8, stream)); KCHECK(hs.s2_w.alloc(s2_cap * 4, stream));
+    KCHECK(hs.s2_digit.alloc(dev_digit_stream_bytes(s2_cap, 1), stream));
+    DevBuf off(stream);
+    KCHECK(off.alloc(((1ull << 16) + 1) * 8));
+    KCHECK(dev_scan_counts(hs.group_count.as<u32>(), 1ull << 16, off.as<u64>(), stream));
+    hipLaunchKernelGGL(s2_rebuild_kernel, dim3(grid_for(1ull << 16, 1)), dim3(BLOCK), 0, stream, hs.s1_key.as<u64>(), hs.s1_w.as<u32>(), hs.group_first.as<u64>(),
+                       hs.group_count.as<u32>(), off.as<u64>(), k, hs.s2_key.as<u64>(), hs.s2_w.as<u32>(), hs.s2_digit.as<uint8_t>(), s2_cap);
+    KCHECK_HIP(hipGetLastError());
+    return KATOME_OK;
+}
+
 // The ordered count of records_to_edges_sorted (lds_count_ordered_kernel).  KATOME_E_UNSUPPORTED: not this way -- the level's shape, a
 // group of more distinct keys than the table holds (err 3: key ranges are far less even than hash ranges on skewed or low-complexity
 // input) or a count beyond 16 bits (err 5); the records are then still all there, ordered by key, in their representative orientation.
@@ -1224,23 +1435,45 @@ static int ordered_count(DevBuf& keys, DevBuf& weights, uint64_t n, uint32_t k, 
     KCHECK_HIP(hipMemsetAsync(hs.group_count.p, 0, (1ull << 16) * 4, stream));
     KCHECK(hs.s1_key.alloc((n + 1) * 8, stream)); KCHECK(hs.s1_w.alloc((n + 1) * 4, stream));
     const u64 s2_cap = rc ? n + 1 : 0;          // (a reverse complement per distinct key: no more than the records)
-    if (rc) {
+    bool regions = false;
+    DevBuf rg_table(stream), rg_cursors(stream);
+    if (rc && s2_regions_route(n)) KCHECK(s2_regions_open(ko, n, k, hs, rg_table, rg_cursors, stream, &regions));
+    if (rc && !regions) {
         KCHECK(hs.s2_key.alloc(s2_cap * 8, stream)); KCHECK(hs.s2_w.alloc(s2_cap * 4, stream));
         KCHECK(hs.s2_digit.alloc(dev_digit_stream_bytes(s2_cap, 1), stream));
     }
     LcAux aux(stream);
     KCHECK(aux.buf.alloc(64));
+    std::vector<unsigned long long> cursors(regions ? (size_t)S2_REGIONS * S2_CURSOR_STEP : 0);          // (read back with the counters: no sync of their own)
+    if (regions) { aux.more = rg_cursors.p; aux.more_host = cursors.data(); aux.more_bytes = cursors.size() * 8; }
+    const S2RegionsOut rg{rg_table.as<u32>(), rg_table.as<u32>() + S2_REGIONS, rg_cursors.as<unsigned long long>()};
     LcResult r;
-    KCHECK(with_bool(rc, [&](auto rcv) {
-        return lc_launch(aux, lds_count_ordered_kernel<decltype(rcv)::value>, LO_LDS, n, r, ko, wo, hs.group_first.as<u64>(), k,
+    auto launch = [&](auto kernel, auto... region_out) {
+        return lc_launch(aux, kernel, LO_LDS, n, r, ko, wo, hs.group_first.as<u64>(), k,
                          min_weight, hs.s1_key.as<u64>(), hs.s1_w.as<u32>(), hs.group_count.as<u32>(), hs.s2_key.as<u64>(), hs.s2_w.as<u32>(),
-                         hs.s2_digit.as<uint8_t>(), s2_cap, aux.cursor(), aux.distinct(), aux.err(), std::min<u32>(lc_probe_limit(), LP_SLOTS));
-    }));
+                         hs.s2_digit.as<uint8_t>(), s2_cap, aux.cursor(), aux.distinct(), aux.err(), std::min<u32>(lc_probe_limit(), LP_SLOTS), region_out...);
+    };
+    if (regions) KCHECK(launch(lds_count_ordered_kernel<true, true, S2RegionsOut>, rg));
+    else KCHECK(with_bool(rc, [&](auto rcv) { return launch(lds_count_ordered_kernel<decltype(rcv)::value>); }));
     lc_trace("[lds count] in key order, 8-byte slots, 1 visit(s) per record: code %u\n", (unsigned)r.code);
     if (r.code) {
         lc_trace("[lds count] in key order: %s; counting by hash groups\n", r.code == 5 ? "a count over 16 bits" : "a group filled its table");
         hs.release();
         return KATOME_E_UNSUPPORTED;
+    }
+    if (regions && r.full) {
+        lc_trace("[half sort] S2 regions: region %u full; rebuilt from S1\n", (unsigned)(r.full - 1));
+        KCHECK(s2_rebuild(hs, r.n_out, k, stream));
+    } else if (regions) {
+        uint64_t sum = 0;
+        for (uint32_t d = 0; d < S2_REGIONS; ++d) sum += hs.region_used[d] = cursors[(size_t)d * S2_CURSOR_STEP];
+        if (sum != r.n_out) { set_error("ordered count: the regions hold %llu keys of %llu", (unsigned long long)sum, (unsigned long long)r.n_out); return KATOME_E_DEVICE; }
+        uint32_t fullest = 0;          // (how tight the sampled sizes were: the region that used the largest share of its room)
+        const auto room = [&](uint32_t d) { return hs.region_start[d + 1] - hs.region_start[d]; };
+        for (uint32_t d = 1; d < S2_REGIONS; ++d) if (hs.region_used[d] * room(fullest) > hs.region_used[fullest] * room(d)) fullest = d;
+        lc_trace("[half sort] S2 regions: %llu keys of room in all, region %u the fullest with %llu of %llu\n", (unsigned long long)hs.region_start[S2_REGIONS],
+                 (unsigned)fullest, (unsigned long long)hs.region_used[fullest], (unsigned long long)room(fullest));
+        hs.regions = true;
     }
     hs.n_s1 = r.n_out; hs.n_s2 = rc ? r.n_out : 0; hs.k = k; hs.taken = true;
     *n_edges = hs.n_s1 + hs.n_s2; *n_distinct = r.n_distinct;
@@ -1249,7 +1482,6 @@ static int ordered_count(DevBuf& keys, DevBuf& weights, uint64_t n, uint32_t k, 
 
 // KATOME_S2_GROUP_SORT=0: S2 sorted in full and half_merge_kernel, as before group_merge_kernel.  KATOME_S2_GROUP_CAP=n: groups of more
 // than n keys (and always more than the kernel's LDS holds) take that route too -- tests of the way back
-static bool s2_group_sort_on() { static const bool on = env_flag("KATOME_S2_GROUP_SORT", true); return on; }
 static uint64_t s2_group_cap() {
     static const uint64_t cap = [] {
         const char* e = getenv("KATOME_S2_GROUP_CAP");
@@ -1271,7 +1503,16 @@ int half_sort_finish(HalfSort& hs, DevBuf& edge_key, DevBuf& edge_weight, hipStr
     KCHECK(b_first.alloc(((1ull << 16) + 1) * 8)); KCHECK(a_off.alloc(((1ull << 16) + 1) * 8));
     bool grouped = false;
     if (hs.n_s2 && s2_group_sort_on()) {
-        {
+        if (hs.regions) {          // (the count placed S2 by its first digit and left the second pass's digits: that pass alone, into dense arrays)
+            DevBuf tk(stream), tw(stream);
+            KCHECK(tk.alloc((hs.n_s2 + 1) * 8)); KCHECK(tw.alloc((hs.n_s2 + 1) * 4));
+            uint64_t tiles = 0;
+            KCHECK(dev_s2_region_pass(hs.s2_key.as<u64>(), hs.s2_w.as<u32>(), hs.s2_digit.as<uint8_t>(), k, hs.region_start, hs.region_used, tk.as<u64>(),
+                                      tw.as<u32>(), &tiles, stream));
+            lc_trace("[half sort] S2 regions: %llu keys in %llu tiles, one pass, counted from its writer's digits\n", (unsigned long long)hs.n_s2,
+                     (unsigned long long)tiles);
+            hs.s2_key.adopt(tk); hs.s2_w.adopt(tw);          // (the regions are released)
+        } else {
             DevBuf tk(stream), tw(stream);
             KCHECK(tk.alloc((hs.n_s2 + 1) * 8)); KCHECK(tw.alloc((hs.n_s2 + 1) * 4));
             const u64* ko = nullptr; const u32* wo = nullptr;

@@ -9,6 +9,7 @@
 #include "common.h"
 #include "edge_keys.h"
 #include "lds_order.h"
+#include "s2_regions.h"
 
 namespace katome {
 
@@ -139,8 +140,34 @@ typedef u32 u32x4_t __attribute__((ext_vector_type(4)));
 template <int NW> struct DigitVec { typedef u32 T; };                   // 1280 bytes per tile: 320 words
 template <> struct DigitVec<1> { typedef u32x4_t T; };                  // 4096 bytes: one 16-byte load per thread
 template <> struct DigitVec<2> { typedef u32x2_t T; };                  // 2048 bytes: one 8-byte load per thread
-template <int NW>
-__global__ __launch_bounds__(BLOCK) void digit_hist_kernel(const uint8_t* __restrict__ digits, u64 n, u32* __restrict__ counts) {
+// Where a pass's tiles lie (the SRC of radix_scatter_kernel below).  ArraySource: tile t at records t * SORT_TILE on.  RegionSource
+// (round 22): the one-word records lie in the 256 regions of s2_regions.h and the pass walks their used parts as one list of
+// LOGICAL tiles in digit order -- tile_first[d] .. tile_first[d + 1] are region d's, the last of them partial --, so that the counts,
+// the offsets and the tile order stay what they are for an array and only the tile's address and its records come from the source.
+// PLACED: origin(base) of the logical tile at base says where it lies and what it holds.
+struct ArraySource {
+    static constexpr bool PLACED = false;
+    struct Origin {};
+    __device__ __forceinline__ Origin origin(u64) const { return Origin{}; }
+};
+struct RegionSource {
+    static constexpr bool PLACED = true;
+    const u32* tile_first;          // [S2_REGIONS + 1]
+    const u64* start;               // [S2_REGIONS] ...
+    const u64* used;                // ... and [S2_REGIONS] behind it
+    struct Origin { u64 base; u32 cnt; };
+    __device__ __forceinline__ Origin origin(u64 base) const {          // (s2_regions.h, s2_region_tile)
+        const u32 t = (u32)(base / S2_REGION_TILE);
+        u32 lo = 0, hi = S2_REGIONS;
+        while (hi - lo > 1) { const u32 mid = (lo + hi) / 2; if (tile_first[mid] <= t) lo = mid; else hi = mid; }
+        const u64 at = (u64)(t - tile_first[lo]) * S2_REGION_TILE, left = used[lo] - at;
+        return Origin{start[lo] + at, (u32)(left < S2_REGION_TILE ? left : S2_REGION_TILE)};
+    }
+};
+static_assert(S2_REGION_TILE == (u64)SortTile<1>::KEYS && S2_REGIONS == (u32)RADIX, "a region is whole sort tiles, one region per digit");
+// (Src: where tile blockIdx.x lies -- at its own index, or where a RegionSource says)
+template <int NW, class Src = ArraySource>
+__global__ __launch_bounds__(BLOCK) void digit_hist_kernel(const uint8_t* __restrict__ digits, u64 n, u32* __restrict__ counts, Src from) {
     typedef typename DigitVec<NW>::T V;
     constexpr u32 SORT_TILE = SortTile<NW>::KEYS, VEC = sizeof(V), WORDS = VEC / 4, LOADS = SORT_TILE / VEC;
     static_assert(SORT_TILE % VEC == 0, "whole loads per tile");
@@ -148,8 +175,9 @@ __global__ __launch_bounds__(BLOCK) void digit_hist_kernel(const uint8_t* __rest
     const u32 tid = threadIdx.x;
     h[tid] = 0;
     __syncthreads();
-    const u64 base = (u64)blockIdx.x * SORT_TILE;
-    const u32 cnt = (u32)((n - base) < (u64)SORT_TILE ? (n - base) : (u64)SORT_TILE);
+    u64 base = (u64)blockIdx.x * SORT_TILE;
+    u32 cnt = (u32)((n - base) < (u64)SORT_TILE ? (n - base) : (u64)SORT_TILE);
+    if constexpr (Src::PLACED) { const typename Src::Origin at = from.origin(base); base = at.base; cnt = at.cnt; }
     const V* src = reinterpret_cast<const V*>(digits + base);
     for (u32 l = tid; l < LOADS; l += BLOCK) {
         const V v = __builtin_nontemporal_load(src + l);
@@ -257,11 +285,8 @@ __global__ __launch_bounds__(BLOCK) void radix_offsets_kernel(u64* __restrict__ 
 // record's index by span once; a record q places behind that entry's first one lies in entry mulhi(q, inv), inv = 2^32 / span + 1
 // (q / span while q * span < 2^32).  Consecutive lanes read the same entry span times over: plain loads, the lines are shared.
 struct NoNextDigit {};
-struct ArraySource {
-    struct Origin {};
-    __device__ __forceinline__ Origin origin(u64) const { return Origin{}; }
-};
 template <int NWT, int NWK, bool RC, bool REP> struct ListSource {
+    static constexpr bool PLACED = false;
     const u64* tiles; const u32* counts; u32 k, span, stride, inv;
     struct Origin { u64 t0; u32 o0; };
     __device__ __forceinline__ Origin origin(u64 base) const { const u64 t0 = base / span; return Origin{t0, (u32)(base - t0 * span)}; }
@@ -285,7 +310,7 @@ __global__ __launch_bounds__(BLOCK, KATOME_SORT_WAVES) void radix_scatter_kernel
                                                                u64 n, Digit dg, const u32* __restrict__ rel,
                                                                const u64* __restrict__ chunk_off, u64* __restrict__ keys_out,
                                                                u32* __restrict__ vals_out, u32 chunk_blocks, u32 xcd_tiles, NextDigitOut<Next> next, Src src) {
-    constexpr bool NEXT = !std::is_same<Next, NoNextDigit>::value, LISTED = !std::is_same<Src, ArraySource>::value;
+    constexpr bool NEXT = !std::is_same<Next, NoNextDigit>::value, PLACED = Src::PLACED, LISTED = !std::is_same<Src, ArraySource>::value && !PLACED;
     static_assert(!LISTED || HAS_VAL, "a list's records carry its counts");
     constexpr int SORT_ITEMS = SortTile<NW>::ITEMS, SORT_TILE = SortTile<NW>::KEYS;
     extern __shared__ u64 smem[];
@@ -303,13 +328,15 @@ __global__ __launch_bounds__(BLOCK, KATOME_SORT_WAVES) void radix_scatter_kernel
     const u64 bid = xcd_tiles ? (u64)(blockIdx.x & 7u) * xcd_tiles + (blockIdx.x >> 3) : (u64)blockIdx.x;
     const u64 base = bid * SORT_TILE;
     if (base >= n) return;                                  // (the grid is rounded up to 8 x xcd_tiles)
-    const u32 cnt = (u32)((n - base) < (u64)SORT_TILE ? (n - base) : (u64)SORT_TILE);
+    u32 cnt = (u32)((n - base) < (u64)SORT_TILE ? (n - base) : (u64)SORT_TILE);
     for (u32 i = tid; i < (BLOCK / 64) * RADIX; i += BLOCK) (&whist[0][0])[i] = 0;
     __syncthreads();
 
     Key<NW> key[SORT_ITEMS]; u32 val[SORT_ITEMS]; u32 dig[SORT_ITEMS]; u32 rnk[SORT_ITEMS];
     const u64 lt_mask = lane ? (~0ull >> (64 - lane)) : 0ull;
     const typename Src::Origin from = src.origin(base);
+    u64 in0 = base;                                         // (the tile's first record in keys_in / vals_in)
+    if constexpr (PLACED) { in0 = from.base; cnt = from.cnt; }
 #pragma unroll
     for (int j = 0; j < SORT_ITEMS; ++j) {
         const u32 idx = wave * (64 * SORT_ITEMS) + j * 64 + lane;
@@ -319,11 +346,11 @@ __global__ __launch_bounds__(BLOCK, KATOME_SORT_WAVES) void radix_scatter_kernel
             if constexpr (LISTED) src.load(from, idx, key[j], val[j]);
             else {
 #if KATOME_STREAM_LOADS >= 1
-            key[j] = load_key_stream<NW>(keys_in, base + idx);
-            if (HAS_VAL) val[j] = __builtin_nontemporal_load(&vals_in[base + idx]);
+            key[j] = load_key_stream<NW>(keys_in, in0 + idx);
+            if (HAS_VAL) val[j] = __builtin_nontemporal_load(&vals_in[in0 + idx]);
 #else
-            key[j] = load_key<NW>(keys_in, base + idx);
-            if (HAS_VAL) val[j] = vals_in[base + idx];
+            key[j] = load_key<NW>(keys_in, in0 + idx);
+            if (HAS_VAL) val[j] = vals_in[in0 + idx];
 #endif
             }
             d = dg(key[j]);
@@ -462,14 +489,18 @@ static bool unstable_first() {
 template <int NW, bool HAS_VAL, class Digit, bool STABLE = true, class Next = NoNextDigit, class Src = ArraySource>
 static int radix_pass(const u64* kin, const u32* vin, u64 n, Digit dg, u64* kout, u32* vout, PassBuffers& pb, hipStream_t stream,
                       bool have_counts = false, const uint8_t* digits_in = nullptr, Next nx = Next{}, uint8_t* digits_out = nullptr, Src src = Src{}) {
-    if (!std::is_same<Src, ArraySource>::value && !have_counts) { set_error("radix pass: records off a list and no counts of them"); return KATOME_E_ARG; }
+    if (!std::is_same<Src, ArraySource>::value && !Src::PLACED && !have_counts) { set_error("radix pass: records off a list and no counts of them"); return KATOME_E_ARG; }
     if (pb.nblocks > 0x7fffffffull) { set_error("radix pass: %llu keys exceed the grid limit", (unsigned long long)n); return KATOME_E_ARG; }
     if (!std::is_same<Next, NoNextDigit>::value && !digits_out) { set_error("radix pass: a next digit and nowhere to write it"); return KATOME_E_ARG; }
     dim3 block(BLOCK);
     u32* const counts = have_counts && pb.first ? pb.first : pb.counts.as<u32>();
     if (!have_counts) {          // (have_counts: whoever wrote the records counted this pass's digits per tile as it went -- pb.first, or pb.counts, holds them)
         KernelScope ks(DigitTimers<Digit>::HIST, stream, n);
-        if (digits_in) hipLaunchKernelGGL((digit_hist_kernel<NW>), dim3((unsigned)pb.nblocks), block, 0, stream, digits_in, n, counts);
+        if constexpr (Src::PLACED) {
+            if (!digits_in) { set_error("radix pass: records in regions and no digits of them"); return KATOME_E_ARG; }
+            hipLaunchKernelGGL((digit_hist_kernel<NW, Src>), dim3((unsigned)pb.nblocks), block, 0, stream, digits_in, n, counts, src);
+        } else
+        if (digits_in) hipLaunchKernelGGL((digit_hist_kernel<NW>), dim3((unsigned)pb.nblocks), block, 0, stream, digits_in, n, counts, ArraySource{});
         else hipLaunchKernelGGL((radix_hist_kernel<NW, Digit>), dim3((unsigned)pb.nblocks), block, 0, stream, kin, n, dg, counts);
     }
     {
@@ -1026,6 +1057,28 @@ int dev_key_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32
     KCHECK((radix_pass<1, true>(ka, wa, n, LevelKeyDigit{2 * k - 8}, kb, wb, pb, stream)));
     *k_out = kb; *w_out = wb;
     return KATOME_OK;
+}
+
+// S2 of the ordered count out of its regions (common.h): the second of dev_key_order's two passes, the first being done by whoever
+// placed the keys.  The tile table is made here from the used counts and uploaded with the regions' starts.
+int dev_s2_region_pass(const uint64_t* d_keys, const uint32_t* d_w, const uint8_t* d_digits, uint32_t k, const uint64_t* start, const uint64_t* used,
+                       uint64_t* k_out, uint32_t* w_out, uint64_t* n_tiles, hipStream_t stream) {
+    if (k < 8 || 2 * k > 64) { set_error("region pass: k = %u", k); return KATOME_E_ARG; }
+    struct { uint64_t start[S2_REGIONS], used[S2_REGIONS]; uint32_t tile_first[S2_REGIONS + 1]; } h;
+    for (u32 d = 0; d < S2_REGIONS; ++d) { h.start[d] = start[d]; h.used[d] = used[d]; }
+    s2_region_tiles(used, h.tile_first);
+    const u64 tiles = h.tile_first[S2_REGIONS];
+    if (n_tiles) *n_tiles = tiles;
+    if (!tiles) return KATOME_OK;
+    DevBuf table(stream);
+    KCHECK(table.alloc(sizeof h));
+    KCHECK_HIP(hipMemcpyAsync(table.p, &h, sizeof h, hipMemcpyHostToDevice, stream));
+    const RegionSource src{reinterpret_cast<const u32*>(table.as<u64>() + 2 * S2_REGIONS), table.as<u64>(), table.as<u64>() + S2_REGIONS};
+    PassBuffers pb;
+    const u64 n = tiles * S2_REGION_TILE;          // (the logical tiles' records, the partial tiles counted whole: the source knows what each holds)
+    KCHECK(pb.init(n, 1, stream));
+    return radix_pass<1, true, LevelKeyDigit, true, NoNextDigit, RegionSource>(d_keys, d_w, n, LevelKeyDigit{2 * k - 8}, k_out, w_out, pb, stream, false, d_digits,
+                                                                              NoNextDigit{}, nullptr, src);
 }
 
 // the first partition pass over a list's records, both ways (test entry: see common.h)

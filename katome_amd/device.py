@@ -488,6 +488,28 @@ def sort_keys(keys, key_bits, key_words, values=None, device=0):
     return keys, values
 
 
+def s2_region_starts(used):
+    """where the 256 regions of the ordered count's S2 begin for these used counts when every region is as many whole 4096-key
+    tiles as its keys need (257 numbers: the last one is the arrays' length)"""
+    u = np.ascontiguousarray(np.asarray(used), np.uint64)
+    assert u.size == 256
+    start = np.zeros(257, np.uint64)
+    _lib.lib().katome_s2_region_starts(u.ctypes.data_as(_lib.u64p), start.ctypes.data_as(_lib.u64p))
+    return start
+
+
+def s2_region_pass(k, used, keys, weights, digits, device=0):
+    """keys (int64), weights (int32) and the bytes of their bits 2k - 8 .. 2k - 1 (uint8) laid out in regions at
+    s2_region_starts(used) -> the dense (keys, weights) after the one partition pass by those bits (katome_dev_s2_region_pass)"""
+    u = np.ascontiguousarray(np.asarray(used), np.uint64)
+    n = int(u.sum())
+    out_k = torch.empty(max(n, 1), dtype=torch.int64, device=keys.device)
+    out_w = torch.empty(max(n, 1), dtype=torch.int32, device=keys.device)
+    _check(_lib.lib().katome_dev_s2_region_pass(device, k, u.ctypes.data_as(_lib.u64p), _ptr(keys), _ptr(weights), _ptr(digits), _ptr(out_k),
+                                                _ptr(out_w), _stream()))
+    return out_k[:n], out_w[:n]
+
+
 def unique_sorted(keys, key_words, device=0):
     n = keys.numel() // key_words
     out = C.c_uint64()

@@ -47,7 +47,9 @@ def main():
     lc, lo, gm = read("katome_debug_lc_phases", 16), read("katome_debug_lo_phases", 8), read("katome_debug_gm_phases", 8)
     print(json.dumps({"workload": wl.name, "builds": builds, "n_edges": n_edges,
                       "lds_count_ordered_kernel": {"clear": lc[12] // builds, "insert": lc[13] // builds, "read_out_and_order": lc[14] // builds,
-                                                   "write": lc[15] // builds, "order": {n: lo[i] // builds for i, n in enumerate(LO)}},
+                                                   "write": lc[15] // builds,
+                                                   "regions": {n: lc[4 + i] // builds for i, n in enumerate(("s1_and_registers", "digit_count", "scan_and_reserve", "reorder"))},
+                                                   "order": {n: lo[i] // builds for i, n in enumerate(LO)}},
                       "group_merge_kernel": {n: gm[i] // builds for i, n in enumerate(GM)}}))
 
 
