@@ -556,7 +556,7 @@ void katome_assembly_free(katome_assembly *a);
  * katome_dev_gfa.  Owned by the library until katome_gfa_free.  A path that cannot be created: KATOME_E_OPEN, "couldn't create
  * <path>: <why>" -- the result is then still handed back when `out` is given (katome_assemble_*'s rule).  With
  * settings.n_devices > 1 the graph is built sharded and gathered to the first GPU, as for katome_assemble_* (needs
- * KATOME_FLAG_FIRST_SEEN_ORDER; a GFA of the sharded shrink without a gather is out of scope: links cross ranks).          */
+ * KATOME_FLAG_FIRST_SEEN_ORDER; the GFA of the sharded shrink without a gather is katome_dist_contigs_gfa / katome_unitigs_gfa_*). */
 typedef struct {
     uint64_t n_segments, n_links, text_bytes, read_bytes;
     uint32_t k, _pad;
@@ -813,6 +813,60 @@ int  katome_unitigs_files(const katome_settings *s, const char *const *paths, si
 int  katome_unitigs_packed(const katome_settings *s, const uint8_t *packed, uint64_t n_reads, uint32_t read_len,
                            const uint8_t *skip, const char *stages, uint64_t original_genome_length,
                            const char *out_path /* nullable */, katome_unitigs *out);
+/* ---- the unitig graph of the sharded shrink as GFA 1, no gather (katome_amd/csrc/dist_gfa.hip) ---------------------------------
+ * Segments are numbered RANK-MAJOR, exactly like the records of katome_dist_contigs_text: segment first_segment + j is this
+ * rank's merged edge j (entry j of every array of katome_dist_contigs), first_segment the merged edges of the ranks before it, so
+ * segment <i> and the record >katome_<i> of the sharded FASTA of the same shrink result are the same unitig.  The whole text is
+ *   H\tVN:Z:1.0\n
+ *   the S lines of rank 0, of rank 1, ...       (each as for katome_dev_gfa, its name the global number)
+ *   the L lines of rank 0, of rank 1, ...       (a rank writes the links whose a is one of its segments, by a, then b)
+ * with links (a, b) where edge_dst[a] == edge_src[b] over the NEW global node ids, a and b global segment numbers, every
+ * orientation +, the overlap <k-1>M, KC and ew as for katome_dev_gfa: byte for byte what katome_dev_gfa_arrays gives for the
+ * ranks' arrays put together in rank order (on one rank: the one-GPU text of the same arrays).  Every rank therefore owns two byte
+ * ranges of the file: its S part at s_base (on rank 0 the header line comes first, s_base = 0) and its L part at l_base.  On the
+ * device they are one buffer: the S part at d_text, the L part at d_link_text = d_text + s_bytes rounded up to 16, zeros behind
+ * each up to its multiple of 16.  Segment names, link ends, offsets and totals are 64-bit (the whole graph may hold 2^32 segments
+ * and more); one rank's part has fewer than 2^32 - 2 lines, or every rank gets KATOME_E_UNSUPPORTED naming the rank and the number.
+ * The links cross ranks: every merged edge registers its number with the owner of its source vertex (vertex v lives on rank
+ * v / ceil(total_nodes / world)), every merged edge asks the owner of its target and gets the at most four out-segments back in
+ * ascending order, in chunks of KATOME_DIST_GFA_CHUNK records per rank and exchange (default 2^24).  A vertex with a fifth
+ * out-segment is a broken invariant: KATOME_E_DEVICE on every rank.  Memory per rank is O(share), never a second copy of the text
+ * (DESIGN.md section 11c has the bytes).  Preconditions as for katome_dist_contigs_text: no shrink result, or gathered shares:
+ * KATOME_E_ARG on every rank; the result is stale for katome_dist_gfa_save after the next katome_dist_shrink.  No edges anywhere:
+ * the header line alone, on rank 0.  KATOME_DIST_GFA_FAIL=<rank> (tests): that rank fails after the sizes are known, and every
+ * rank returns KATOME_E_UNSUPPORTED naming it.  KATOME_DIST_GFA_TRACE=1: every rank's wall time per call on stderr.  Profile
+ * phase "gfa"; the exchanges are accounted with the other sharded stages'.  Arrays owned by the builder until its next
+ * katome_dist_contigs_gfa or destroy.  Collective. */
+typedef struct {
+    uint64_t n_segments, first_segment, total_segments;
+    uint64_t n_links, total_links;
+    uint64_t s_bytes, s_base, l_bytes, l_base, total_text_bytes;   /* this rank's two parts and where they start in the whole text */
+    uint8_t  *d_text, *d_link_text;                               /* S part (rank 0: the header first); L part                     */
+    uint64_t *d_segment_off;                                       /* [n_segments], relative to d_text                              */
+    uint64_t *d_link_first;                                        /* [n_segments + 1]                                              */
+    uint64_t *d_link_b;                                            /* [n_links] global number of every link's second segment        */
+} katome_dist_gfa;
+int  katome_dist_contigs_gfa(katome_dist_builder *d, katome_dist_gfa *out, void *stream);
+/* the file of `g` (what this builder's last katome_dist_contigs_gfa returned), written by all ranks as katome_dist_contigs_save
+ * writes the FASTA file: rank 0 creates `path` at total_text_bytes -- failure: KATOME_E_OPEN, "couldn't create <path>: <why>", on
+ * every rank --, every rank writes its two parts at s_base and l_base in chunks of KATOME_DIST_TEXT_CHUNK bytes, write errors are
+ * agreed at the end and no partial file is left behind. */
+int  katome_dist_gfa_save(katome_dist_builder *d, const katome_dist_gfa *g, const char *path);
+/* katome_unitigs_gfa_*: katome_unitigs_* with the graph as its ending -- the same pipeline and the same refusals (stage letters or
+ * KATOME_FLAG_REMOVE_DEAD_PATHS without KATOME_FLAG_FIRST_SEEN_ORDER: KATOME_E_ARG; a packed-key build without them is fine; the
+ * create error as there).  With settings.n_devices > 1 everything runs on the shares and ends in katome_dist_contigs_gfa and
+ * katome_dist_gfa_save; on one GPU it is katome_dev_shrink_mode(FAST) and katome_dev_contigs_gfa, and the file is that entry's
+ * text.  The result is a plain struct; the text goes to the file only. */
+typedef struct {
+    uint64_t n_segments, n_links, text_bytes, total_bases, longest, read_bytes;
+    uint32_t k, n_devices;
+    katome_dist_shrink_stats shrink;     /* zeros on one GPU */
+} katome_unitigs_gfa;
+int  katome_unitigs_gfa_files (const katome_settings *s, const char *const *paths, size_t n_paths, const char *stages,
+                               uint64_t original_genome_length, const char *out_path /* nullable */, katome_unitigs_gfa *out);
+int  katome_unitigs_gfa_packed(const katome_settings *s, const uint8_t *packed, uint64_t n_reads, uint32_t read_len,
+                               const uint8_t *skip, const char *stages, uint64_t original_genome_length,
+                               const char *out_path /* nullable */, katome_unitigs_gfa *out);
 /* this rank's share of the graph as it stands (after katome_dist_finalize / katome_dist_remove_dead_paths / the stages) */
 int  katome_dist_current_graph(katome_dist_builder *d, katome_dist_graph *out);
 /* katome_dev_graph_stats / katome_dev_weight_spectrum for the SHARDED graph, no gather (katome_amd/csrc/dist_stats.hip): the
@@ -946,6 +1000,21 @@ int katome_dev_gfa_arrays(int device, uint32_t k, uint64_t n_nodes, uint64_t n_e
                           const uint64_t *d_edge_label_off, const uint8_t *d_edge_label, uint64_t label_bytes,
                           uint64_t *d_segment_off, uint64_t *d_link_first, uint8_t *d_text, uint64_t text_cap,
                           uint64_t *n_links, uint64_t *text_bytes, void *stream);
+/* the GFA writer on a numbered PART of a text whose other parts are written elsewhere (katome_dist_contigs_gfa): segment i is named
+ * first_segment + i (up to 20 digits), its links are d_link_b[d_link_first[i] .. d_link_first[i + 1]) -- global numbers, n_links =
+ * d_link_first[n_edges] --, the header line is written or not.  d_text holds the S part (the header first) at 0 and the L part
+ * at *l_offset = *s_bytes rounded up to 16, zeros behind each part up to its multiple of 16; it must be 16-byte aligned with
+ * text_cap >= *l_offset + *l_bytes rounded up to 16.  The three sizes are always set; d_text NULL: a size query.  Labels are
+ * validated on the device first and d_edge_label is aligned as for katome_dev_gfa_arrays; malformed labels or a d_link_first that
+ * does not ascend from 0: KATOME_E_ARG.  first_segment + n_edges past 2^64, or 2^32 - 2 lines or more: KATOME_E_UNSUPPORTED.
+ * With first_segment = 0, with_header = 1 and the links of katome_dev_gfa_arrays, the S part followed by the L part is that
+ * entry's text byte for byte.  Synchronises. */
+int katome_dev_gfa_part_arrays(int device, uint32_t k, uint64_t n_edges, const uint32_t *d_edge_weight, const uint32_t *d_edge_kmers,
+                               const uint64_t *d_edge_label_off, const uint8_t *d_edge_label, uint64_t label_bytes,
+                               uint64_t first_segment, int with_header,
+                               const uint64_t *d_link_first /* [n_edges + 1] */, const uint64_t *d_link_b /* [n_links] global numbers */,
+                               uint64_t *d_segment_off, uint8_t *d_text, uint64_t text_cap,
+                               uint64_t *s_bytes, uint64_t *l_offset, uint64_t *l_bytes, void *stream);
 /* Stats<CollectionStats>::stats for PtGraph (stats/collections.rs:137-168) from device arrays, filled exactly as
  * katome_graph_stats fills it from host arrays: u64 sums, the two averages one f64 division each on the host (no edges:
  * avg_edge_weight is NaN, no nodes: avg_out_degree is NaN, as the reference's 0.0 / 0.0); externals(Incoming) and

@@ -130,6 +130,19 @@ class Unitigs(C.Structure):
                 ("shrink", DistShrinkStats)]
 
 
+class DistGfa(C.Structure):
+    _fields_ = [("n_segments", C.c_uint64), ("first_segment", C.c_uint64), ("total_segments", C.c_uint64), ("n_links", C.c_uint64),
+                ("total_links", C.c_uint64), ("s_bytes", C.c_uint64), ("s_base", C.c_uint64), ("l_bytes", C.c_uint64),
+                ("l_base", C.c_uint64), ("total_text_bytes", C.c_uint64), ("d_text", C.c_void_p), ("d_link_text", C.c_void_p),
+                ("d_segment_off", C.c_void_p), ("d_link_first", C.c_void_p), ("d_link_b", C.c_void_p)]
+
+
+class UnitigsGfa(C.Structure):
+    _fields_ = [("n_segments", C.c_uint64), ("n_links", C.c_uint64), ("text_bytes", C.c_uint64), ("total_bases", C.c_uint64),
+                ("longest", C.c_uint64), ("read_bytes", C.c_uint64), ("k", C.c_uint32), ("n_devices", C.c_uint32),
+                ("shrink", DistShrinkStats)]
+
+
 class DistStandardizeStats(C.Structure):
     _fields_ = [("route", C.c_uint32), ("rank_rounds", C.c_uint32), ("exchanges", C.c_uint64), ("contigs", C.c_uint64),
                 ("longest_contig", C.c_uint64), ("cycle_edges", C.c_uint64), ("bytes_sent", C.c_uint64)]
@@ -206,12 +219,15 @@ SYMBOLS = {
     "katome_dev_pieces_text_numbered": (_i, [_i, _u32, _vp, _vp, _u64, _vp, _u64, _u32, _u64, _vp, _vp, _u64, _vp, _u64, u64p, u64p, _vp]),
     "katome_dev_contigs_gfa": (_i, [_vp, C.POINTER(DevContigs), C.POINTER(DevGfa), _vp]),
     "katome_dev_gfa_arrays": (_i, [_i, _u32, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, u64p, u64p, _vp]),
+    "katome_dev_gfa_part_arrays": (_i, [_i, _u32, _u64, _vp, _vp, _vp, _vp, _u64, _u64, _i, _vp, _vp, _vp, _vp, _u64, u64p, u64p, u64p, _vp]),
     "katome_gfa_files": (_i, [C.POINTER(Settings), _pp, _sz, C.c_char_p, _u64, C.c_char_p, C.POINTER(C.POINTER(Gfa))]),
     "katome_gfa_packed": (_i, [C.POINTER(Settings), _vp, _u64, _u32, _vp, C.c_char_p, _u64, C.c_char_p, C.POINTER(C.POINTER(Gfa))]),
     "katome_gfa_save": (_i, [C.POINTER(Gfa), C.c_char_p]),
     "katome_gfa_free": (None, [C.POINTER(Gfa)]),
     "katome_unitigs_files": (_i, [C.POINTER(Settings), _pp, _sz, C.c_char_p, _u64, C.c_char_p, C.POINTER(Unitigs)]),
     "katome_unitigs_packed": (_i, [C.POINTER(Settings), _vp, _u64, _u32, _vp, C.c_char_p, _u64, C.c_char_p, C.POINTER(Unitigs)]),
+    "katome_unitigs_gfa_files": (_i, [C.POINTER(Settings), _pp, _sz, C.c_char_p, _u64, C.c_char_p, C.POINTER(UnitigsGfa)]),
+    "katome_unitigs_gfa_packed": (_i, [C.POINTER(Settings), _vp, _u64, _u32, _vp, C.c_char_p, _u64, C.c_char_p, C.POINTER(UnitigsGfa)]),
     "katome_contig_stats_of": (_i, [u64p, _u64, _u64, C.POINTER(ContigStats)]),
     "katome_assemble_files": (_i, [C.POINTER(Settings), _pp, _sz, _u64, C.c_char_p, C.POINTER(C.POINTER(Assembly))]),
     "katome_assemble_packed": (_i, [C.POINTER(Settings), _vp, _u64, _u32, _vp, _u64, C.c_char_p, C.POINTER(C.POINTER(Assembly))]),
@@ -272,6 +288,8 @@ SYMBOLS = {
     "katome_dist_contig_stats_arrays": (_i, [_vp, _i, _vp, _u64, _u32, _u64, C.POINTER(ContigStats), _vp]),
     "katome_dist_contig_stats": (_i, [_vp, _u64, C.POINTER(ContigStats), _vp]),
     "katome_dist_contigs_save": (_i, [_vp, C.POINTER(DistAssembly), C.c_char_p]),
+    "katome_dist_contigs_gfa": (_i, [_vp, C.POINTER(DistGfa), _vp]),
+    "katome_dist_gfa_save": (_i, [_vp, C.POINTER(DistGfa), C.c_char_p]),
     "katome_dist_graph_stats": (_i, [_vp, C.POINTER(Stats), _vp]),
     "katome_dist_weight_spectrum": (_i, [_vp, u64p, _u32, _vp]),
     "katome_dist_exchange_count": (_u32, []),

@@ -508,6 +508,16 @@ class GpuContigs:
         return sorted(zip(self.edge_seq, (int(w) for w in self.edge_weight)))
 
 
+class UnitigsGfa:
+    """what GpuUnitigs.gfa / gfa_from_packed hand back (katome_unitigs_gfa): n_segments, n_links, text_bytes (of the GFA text),
+    total_bases, longest, read_bytes, k, n_devices and, over several GPUs, shrink (the sharded shrink's counters)"""
+
+    def __init__(self, u):
+        for f in ("n_segments", "n_links", "text_bytes", "total_bases", "longest", "read_bytes", "k", "n_devices"):
+            setattr(self, f, getattr(u, f))
+        self.shrink = {f: getattr(u.shrink, f) for f, _ in _lib.DistShrinkStats._fields_}
+
+
 class GpuUnitigs:
     """The build, the stages asked for and the traversal-free shrink, ending in the unitigs' FASTA file and Contigs::stats
     (katome_unitigs_*): n_contigs, text_bytes (of the FASTA text), total_bases, longest, read_bytes, k, n_devices, stats
@@ -519,6 +529,39 @@ class GpuUnitigs:
             setattr(self, f, getattr(u, f))
         self.stats = ContigsStats(u.stats.n50, u.stats.l50, u.stats.n90, u.stats.ng50)
         self.shrink = {f: getattr(u.shrink, f) for f, _ in _lib.DistShrinkStats._fields_}
+
+    @staticmethod
+    def gfa(input_files, ft, reverse_complement, minimal_weight_threshold=0, output_file=None, stages=None, original_genome_length=0,
+            device=0, first_seen_order=False, remove_dead_paths=False, n_devices=1, ranks_share_device=False):
+        """the same pipeline ending in the unitig GRAPH as a GFA 1 file (katome_unitigs_gfa_files): with n_devices > 1 the links are
+        joined across the ranks' shares, never a gather, and segment <i> is the record >katome_<i> of create()'s file ->
+        (UnitigsGfa, number_of_read_bytes); uses the global k"""
+        s = make_settings(K_SIZE, ft, reverse_complement, minimal_weight_threshold, device, first_seen_order=first_seen_order,
+                          remove_dead_paths=remove_dead_paths, n_devices=n_devices, ranks_share_device=ranks_share_device)
+        u = _lib.UnitigsGfa()
+        _check(_lib.lib().katome_unitigs_gfa_files(C.byref(s), _paths(input_files), len(input_files), (stages or "").encode(),
+                                                   original_genome_length, os.fsencode(output_file) if output_file is not None else None,
+                                                   C.byref(u)))
+        return UnitigsGfa(u), u.read_bytes
+
+    @staticmethod
+    def gfa_from_packed(packed, n_reads, read_len, skip=None, reverse_complement=False, minimal_weight_threshold=0, output_file=None,
+                        stages=None, original_genome_length=0, device=0, k=None, first_seen_order=False, remove_dead_paths=False,
+                        n_devices=1, ranks_share_device=False):
+        """the same from 2-bit packed reads (numpy uint8; katome_unitigs_gfa_packed)"""
+        s = make_settings(K_SIZE if k is None else k, InputFileType.Fastq, reverse_complement, minimal_weight_threshold, device,
+                          first_seen_order=first_seen_order, remove_dead_paths=remove_dead_paths, n_devices=n_devices,
+                          ranks_share_device=ranks_share_device)
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        skip_p = None
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.uint8)
+            skip_p = skip.ctypes.data
+        u = _lib.UnitigsGfa()
+        _check(_lib.lib().katome_unitigs_gfa_packed(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, (stages or "").encode(),
+                                                    original_genome_length, os.fsencode(output_file) if output_file is not None else None,
+                                                    C.byref(u)))
+        return UnitigsGfa(u), u.read_bytes
 
     @classmethod
     def create(cls, input_files, ft, reverse_complement, minimal_weight_threshold=0, output_file=None, stages=None,

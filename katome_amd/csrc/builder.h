@@ -163,6 +163,10 @@ KATOME_INTERNAL bool tile_recs_shape(uint32_t nwt, uint32_t nw, bool first_seen)
 KATOME_INTERNAL bool sorted_fail(const char* level);     // KATOME_SORTED_FAIL (tests)
 KATOME_INTERNAL bool seen_var_sorted();              // KATOME_SEEN_VAR_SORTED
 
+// ---- dist_gfa.hip: the k-mers on ALL ranks' merged edges of the last katome_dist_shrink (collective; katome_unitigs_gfa_*'s total_bases)
+struct katome_dist_builder;
+KATOME_INTERNAL int dist_gfa_total_kmers(katome_dist_builder* d, uint64_t* total, hipStream_t stream);
+
 // ---- api.hip: what the host entry points (host_build.cpp) take from it ------------------------------------------------------------
 // BFCounter input: one edge per kept line and strand; leaves the builder with its sorted edge list
 KATOME_INTERNAL int bfc_set_edges(katome_builder* b, const uint64_t* d_fwd, const uint32_t* d_w, uint64_t n_lines, hipStream_t stream);

@@ -464,6 +464,23 @@ struct GfaOutput {
 int dev_gfa_plan(const GfaGraph& g, GfaPlan& plan, hipStream_t stream);                         // validates, joins, measures; synchronises
 int dev_gfa_write(const GfaGraph& g, const GfaPlan& plan, uint8_t* text, hipStream_t stream);  // text: plan.text_bytes rounded up to 16
 int dev_gfa(const GfaGraph& g, GfaOutput& out, hipStream_t stream);
+// a numbered part of a GFA text whose other parts are written elsewhere (dist_gfa.hip): segment i is named first_segment + i, the
+// links of segment a are link_b[link_first[a] .. link_first[a + 1]) (global numbers); the header line is there or not.  The part's
+// text is one buffer: the S part (with the header) at 0, the L part at l_offset(), the next multiple of 16, zeros behind each
+struct GfaPart {
+    uint32_t k; uint64_t n_edges;
+    const uint32_t *edge_weight, *edge_kmers; const uint64_t* label_off; const uint8_t* label; uint64_t label_bytes;
+    uint64_t first_segment; bool with_header;
+    const uint64_t *link_first, *link_b;
+};
+struct GfaPartPlan {
+    DevBuf s_line_off, l_line_off, segment_off, link_a;      // line offsets of the two parts (one entry more than lines); every link's local a
+    uint64_t n_links = 0, s_bytes = 0, l_bytes = 0;
+    uint64_t l_offset() const { return (s_bytes + 15) / 16 * 16; }
+    uint64_t buffer_bytes() const { return l_offset() + (l_bytes + 15) / 16 * 16; }
+};
+int dev_gfa_part_plan(const GfaPart& g, GfaPartPlan& plan, hipStream_t stream);                        // validates, measures; synchronises
+int dev_gfa_part_write(const GfaPart& g, const GfaPartPlan& plan, uint8_t* text, hipStream_t stream);  // text: plan.buffer_bytes()
 
 // Contigs::stats' panic sites as a status (contig_stats.h's 1, 2, 3: which tipping point is 0), one message wherever the stats are made
 inline int contig_stats_status(int which) {

@@ -60,6 +60,12 @@ struct katome_dist_builder {
     katome::TextOutput sh_text;
     uint64_t sh_text_serial = 0, sh_text_first = 0, sh_text_base = 0, sh_text_total = 0, sh_text_contigs = 0;
     bool sh_text_valid = false;
+    // the GFA text of that result on this rank (dist_gfa.hip, katome_dist_contigs_gfa): one buffer, the S part at 0 and the L part at
+    // the next multiple of 16; kept until the next call or destroy
+    DevBuf sh_gfa_text, sh_gfa_segment_off, sh_gfa_link_first, sh_gfa_link_b;
+    katome_dist_gfa sh_gfa = {};             // what the call handed out (katome_dist_gfa_save checks against it)
+    uint64_t sh_gfa_serial = 0;
+    bool sh_gfa_valid = false;
     // what the last katome_dist_standardize_contigs that finished on this builder did (katome_dist_standardize_stats_read)
     katome_dist_standardize_stats contigs_stats = {};
     bool contigs_stats_valid = false;

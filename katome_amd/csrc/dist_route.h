@@ -72,6 +72,10 @@ __global__ __launch_bounds__(BLOCK) void alive_list_kernel(const unsigned char* 
 __global__ __launch_bounds__(BLOCK) void scatter_by_idx_kernel(const u64* __restrict__ vals, const u32* __restrict__ at, u64 n, u64* __restrict__ out) {
     WLOOP(i, n) if (i < n) out[at[i]] = vals[i];
 }
+// ... records of `words` u64 each (Router::reply with a width)
+__global__ __launch_bounds__(BLOCK) void scatter_wide_by_idx_kernel(const u64* __restrict__ vals, const u32* __restrict__ at, u64 n, u32 words, u64* __restrict__ out) {
+    WLOOP(i, n) if (i < n) for (u32 q = 0; q < words; ++q) out[(u64)at[i] * words + q] = vals[i * words + q];
+}
 template <class T>
 __global__ __launch_bounds__(BLOCK) void gather_by_kernel(const T* __restrict__ src, const u32* __restrict__ keep, u64 n, T* __restrict__ out) {
     WLOOP(i, n) if (i < n) out[i] = src[keep[i]];
@@ -172,14 +176,16 @@ struct Router {
         KCHECK_HIP(hipStreamSynchronize(stream));
         return KATOME_OK;
     }
-    // answers aligned with what `r` received travel back; out[i] = the answer to the i-th record of the sender's list
-    int reply(const Routed& r, const u64* ans, u64* out) {
+    // answers aligned with what `r` received travel back; out[i] = the answer to the i-th record of the sender's list (`words`
+    // u64 per answer: out[i * words ..])
+    int reply(const Routed& r, const u64* ans, u64* out, uint32_t words = 1) {
         ++n_reply;
         const double t0 = now_ms();
         DevBuf back(stream);
-        KCHECK(back.alloc((r.n_sent + 1) * 8));
-        KCHECK(d->xchg(X_PRUNE, ans, r.rcnt.data(), back.p, r.counts.data(), 8, stream, false, r.pair_max));
-        if (r.n_sent) KLAUNCH(scatter_by_idx_kernel, r.n_sent, stream, back.as<u64>(), r.pidx.as<u32>(), r.n_sent, out);
+        KCHECK(back.alloc((r.n_sent + 1) * 8 * words));
+        KCHECK(d->xchg(X_PRUNE, ans, r.rcnt.data(), back.p, r.counts.data(), 8 * (size_t)words, stream, false, r.pair_max));
+        if (r.n_sent && words == 1) KLAUNCH(scatter_by_idx_kernel, r.n_sent, stream, back.as<u64>(), r.pidx.as<u32>(), r.n_sent, out);
+        else if (r.n_sent) KLAUNCH(scatter_wide_by_idx_kernel, r.n_sent, stream, back.as<u64>(), r.pidx.as<u32>(), r.n_sent, words, out);
         KCHECK_HIP(hipGetLastError());
         KCHECK_HIP(hipStreamSynchronize(stream));
         t_xchg += now_ms() - t0;

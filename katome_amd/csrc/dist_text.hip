@@ -1,6 +1,6 @@
 // dist_text.hip -- what comes out at the end of the sharded pipeline, no gather: the text of the sharded shrink's merged edges
 // (unitigs), Contigs::stats of all ranks' contigs (reference src/katome/stats/contigs.rs:31-89) and the FASTA file
-// (Contigs::save_to_file, asm/mod.rs:57-72), written by every rank at its own offset.  Memory per rank is O(share) -- the text of
+// (Contigs::save_to_file, asm/mod.rs:57-72), written by every rank at its own offset (dist_save.h).  Memory per rank is O(share) -- the text of
 // its own merged edges -- plus one chunk of host memory while the file is written.
 //
 // The order is RANK-MAJOR: contig first_contig + j is this rank's merged edge j -- entry j of every array of katome_dist_contigs,
@@ -20,15 +20,12 @@
 // rank, a contig of 2^32 bases -- and write errors come back on every rank with a message that names the rank.
 // KATOME_DIST_TEXT_FAIL=<rank> (tests): that rank fails after the plan.  KATOME_DIST_TEXT_CHUNK=<bytes>: the host buffer of the
 // file writer (default 64 MiB).  KATOME_DIST_TEXT_TRACE=1: every rank's wall time per call on stderr (tools/bench_dist_text.py).
-#include <errno.h>
-#include <fcntl.h>
-#include <unistd.h>
-
 #include <chrono>
 
 #include "contig_select.h"
 #include "dist_agree.h"
 #include "dist_builder.h"
+#include "dist_save.h"
 
 namespace {
 
@@ -164,70 +161,10 @@ int dist_contigs_text(katome_dist_builder* d, uint32_t layout, hipStream_t strea
     return KATOME_OK;
 }
 
-// all of `buf` at `at`, whatever pwrite makes of it in one go
-int write_at(int fd, const uint8_t* buf, uint64_t n, uint64_t at, const char* path) {
-    while (n) {
-        const ssize_t w = pwrite(fd, buf, n, (off_t)at);
-        if (w < 0 && errno == EINTR) continue;
-        if (w <= 0) { set_error("couldn't write %s: %s", path, strerror(errno)); return KATOME_E_OPEN; }
-        buf += w; n -= (uint64_t)w; at += (uint64_t)w;
-    }
-    return KATOME_OK;
-}
-
+// the FASTA file: this rank's text is one part of it (dist_save.h)
 int dist_contigs_save(katome_dist_builder* d, const char* path, hipStream_t stream) {
-    const char* name = "katome_dist_contigs_save";
-    Collective C(d->comm, name);
-    const bool root = C.rank == 0;
-    int fd = -1;
-    bool created = false;
-    // rank 0 makes the file at its full length; why it could not travels as a number, so every rank reports the reference's message
-    uint64_t why = 0;
-    if (root) {
-        fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
-        if (fd < 0) why = create_error_kind(errno);
-        else {
-            created = true;
-            if (ftruncate(fd, (off_t)d->sh_text_total) != 0) why = create_error_kind(errno);
-        }
-    }
-    auto finish = [&](int rc) -> int {
-        if (fd >= 0 && close(fd) != 0 && !rc) { set_error("couldn't write %s: %s", path, strerror(errno)); rc = KATOME_E_OPEN; }
-        fd = -1;
-        return rc;
-    };
-    auto failed = [&](int rc) -> int {                       // (a caller never finds a partial file)
-        const std::string keep = get_error();
-        finish(rc);
-        if (created) (void)unlink(path);
-        set_error("%s", keep.c_str());
-        return rc;
-    };
-    { const int rc = C.agree(KATOME_OK, &why); if (rc) return failed(rc); }
-    if (why) { set_error("couldn't create %s: %s", path, CREATE_ERROR_KINDS[why < 5 ? why : 4]); return failed(KATOME_E_OPEN); }      // asm/mod.rs:62
-    auto copy_out = [&]() -> int {
-        const uint64_t n = d->sh_text.text_bytes;
-        if (n == 0) return KATOME_OK;
-        if (!root) {
-            fd = open(path, O_WRONLY);
-            if (fd < 0) { set_error("couldn't open %s to write this rank's part: %s", path, strerror(errno)); return KATOME_E_OPEN; }
-        }
-        uint64_t chunk = 64ull << 20;
-        if (const char* e = getenv("KATOME_DIST_TEXT_CHUNK")) chunk = std::max<long long>(1, atoll(e));
-        chunk = std::min(chunk, n);
-        std::vector<uint8_t> buf;
-        try { buf.resize(chunk); }
-        catch (const std::bad_alloc&) { set_error("out of host memory"); return KATOME_E_OOM; }
-        for (uint64_t at = 0; at < n; at += chunk) {
-            const uint64_t cnt = std::min(chunk, n - at);
-            KCHECK_HIP(hipMemcpyAsync(buf.data(), d->sh_text.text.as<uint8_t>() + at, cnt, hipMemcpyDeviceToHost, stream));
-            KCHECK_HIP(hipStreamSynchronize(stream));
-            KCHECK(write_at(fd, buf.data(), cnt, d->sh_text_base + at, path));
-        }
-        return KATOME_OK;
-    };
-    const int rc = C.agree(finish(copy_out()));              // (the closing agreement carries the write errors)
-    return rc ? failed(rc) : KATOME_OK;
+    const FilePart part{d->sh_text.text.as<uint8_t>(), d->sh_text.text_bytes, d->sh_text_base};
+    return save_parts(d->comm, "katome_dist_contigs_save", path, d->sh_text_total, &part, 1, stream);
 }
 
 }  // namespace

@@ -18,6 +18,10 @@
 //   left into an LDS image of the tile (a division by ten per digit, not per byte and lane).  Then every lane produces 16 consecutive
 //   bytes with one 128-bit store: 16 bases of one segment straight from the 2-bit label (sixteen_bases); in the L region the image's
 //   16 bytes as they are; anywhere else the image's bytes with the bases among them filled in one at a time.
+//   The numbered form (gfa_write_kernel<true>, dev_gfa_part_plan / dev_gfa_part_write, katome_dev_gfa_part_arrays) writes one PART of
+//   a text whose other parts are written elsewhere (dist_gfa.hip): names start at first_segment, links come as a table of 64-bit
+//   global numbers, the header is written or not, and the S part and the L part are two regions of one buffer, each a launch of its
+//   own.  It is a separate instantiation: gfa_write_kernel<false> is the one-GPU kernel as it was.
 #include "builder.h"
 #include "text_bases.h"
 
@@ -29,9 +33,14 @@ constexpr u32 TILE = BLOCK * 16 * STORES;              // output bytes a workgro
 constexpr u32 HEADER_BYTES = 11;                       // "H\tVN:Z:1.0\n": the shortest line (an L line has 13 bytes or more, an S line more still)
 constexpr u32 MAX_LINES = TILE / HEADER_BYTES + 2;     // lines that can overlap one tile
 constexpr int S_NAME_MAX = 2 + 10 + 1;                 // "S\t<i>\t", i < 2^32
+constexpr int S_NAME_MAX_NUMBERED = 2 + 20 + 1;        // ... of a numbered part: first_segment + i < 2^64
+constexpr u32 L_LINE_MAX_NUMBERED = 10 + 20 + 20 + 10; // "L\t<a>\t+\t<b>\t+\t<k-1>M\n" with two 64-bit numbers: far below a tile
 constexpr int S_TAGS_MAX = 3 * 6 + 10 + 20 + 10 + 1;   // "\tLN:i:<u32>\tKC:i:<u64>\tew:i:<u32>\n"
 static_assert(TILE <= 65536, "offsets inside a tile are kept in 16 bits");
-enum { ERR_NODE = 1, ERR_LABEL = 2, ERR_LABEL_LEN = 4, ERR_KMERS = 8 };
+// (no line of either form is shorter than the header's 11 bytes -- the shortest L line, "L\t0\t+\t0\t+\t0M\n", has 13 --, so MAX_LINES and
+// the 16-bit offsets hold for a numbered part too: longer numbers only make lines longer)
+static_assert(L_LINE_MAX_NUMBERED < TILE && HEADER_BYTES <= 13, "a tile holds at most MAX_LINES lines");
+enum { ERR_NODE = 1, ERR_LABEL = 2, ERR_LABEL_LEN = 4, ERR_KMERS = 8, ERR_LINKS = 16 };
 
 constexpr u64 tag(char a, char b, char c, char d, char e, char f) {      // six characters, the first in the low byte
     return (u64)(uint8_t)a | (u64)(uint8_t)b << 8 | (u64)(uint8_t)c << 16 | (u64)(uint8_t)d << 24 | (u64)(uint8_t)e << 32 | (u64)(uint8_t)f << 40;
@@ -108,25 +117,38 @@ struct Line {
     const uint8_t* src;       // a segment's packed bases
     u32 head, bases, total;   // bytes in front of the bases; the bases; all the line's bytes.  Not a segment: head = total, no bases
 };
-__device__ __forceinline__ Line load_line(u32 r, u32 E, const uint8_t* __restrict__ label, const u64* __restrict__ label_off,
+// (NUMBERED: a part of a sharded text, see PartNumbers below; its segments are lines hdr .. hdr + E - 1)
+template <bool NUMBERED>
+__device__ __forceinline__ Line load_line(u32 r, u32 E, u32 hdr, const uint8_t* __restrict__ label, const u64* __restrict__ label_off,
                                           const u64* __restrict__ segment_off, const u64* __restrict__ line_off) {
     Line ln;
     const u64 at = line_off[r];
     ln.total = (u32)(line_off[r + 1] - at);
     ln.head = ln.total; ln.bases = 0; ln.src = label;
-    if (r >= 1 && r <= E) {
-        const u64 lo = label_off[r - 1], hi = label_off[r];
+    if (NUMBERED ? (r >= hdr && r < hdr + E) : (r >= 1 && r <= E)) {
+        const u32 i = NUMBERED ? r - hdr : r - 1;
+        const u64 lo = label_off[i], hi = label_off[i + 1];
         ln.src = label + lo + 1;
         ln.bases = 4 * (u32)(hi - lo - 1) - label[lo];
-        ln.head = (u32)(segment_off[r - 1] - at);       // (the name's digits were counted when the line was measured: none is counted here)
+        ln.head = (u32)(segment_off[i] - at);       // (the name's digits were counted when the line was measured: none is counted here)
     }
     return ln;
 }
 
+// A numbered part of a text whose other parts are written elsewhere (dist_gfa.hip): segment i is named first + i, link l joins
+// first + link_a[l] to link_b[l] (a global number), and the header line is there or not (hdr = 1 or 0): the part's lines are hdr
+// header lines, E segments, then links.  The one-GPU text is the form without: NUMBERED = false is the kernel as it was, its
+// conditions and types untouched, and takes none of these.
+// (An S part is launched with hdr header lines and E segments, R = hdr + E; an L part with E = 0, hdr = 0 and R links.)
+struct PartNumbers { u64 first; u32 hdr; const u32* link_a; const u64* link_b; };
+
+template <bool NUMBERED>
 __global__ __launch_bounds__(BLOCK) void gfa_write_kernel(u32 k, u32 E, u32 R, const u32* __restrict__ weight, const u32* __restrict__ kmers,
                                                           const u64* __restrict__ label_off, const uint8_t* __restrict__ label,
                                                           const u64* __restrict__ line_off, const u64* __restrict__ segment_off,
-                                                          const u32* __restrict__ link_ab, u64 total, uint8_t* __restrict__ text) {
+                                                          const u32* __restrict__ link_ab, u64 total, uint8_t* __restrict__ text, const PartNumbers pn) {
+    const u32 hdr = NUMBERED ? pn.hdr : 1u;
+    constexpr int name_max = NUMBERED ? S_NAME_MAX_NUMBERED : S_NAME_MAX;
     __shared__ __align__(16) uint8_t s_img[TILE];      // the tile's bytes that are not bases
     __shared__ uint16_t s_off[MAX_LINES];              // where the tile's lines start, relative to the tile
     const u32 tid = threadIdx.x;
@@ -142,22 +164,28 @@ __global__ __launch_bounds__(BLOCK) void gfa_write_kernel(u32 k, u32 E, u32 R, c
             const u64 o = line_off[r];
             s_off[j] = o > base ? (uint16_t)(o - base) : 0;
             const int64_t rel = (int64_t)(o - base), end = (int64_t)(line_off[r + 1] - base);      // (end >= 1: the line overlaps the tile)
-            if (r == 0) {
+            if (NUMBERED ? r < hdr : r == 0) {
                 put_tag_back<3>(s_img, put_tag_back<6>(s_img, (int)end - 1, len, tag('Z', ':', '1', '.', '0', '\n')), len, tag('V', 'N', ':', 0, 0, 0));
                 put_tag_back<2>(s_img, (int)rel + 1, len, tag('H', '\t', 0, 0, 0, 0));
-            } else if (r > E) {
-                const u32 l = r - 1 - E;
+            } else if (NUMBERED ? r >= hdr + E : r > E) {
+                const u32 l = NUMBERED ? r - hdr - E : r - 1 - E;
                 int p = put_tag_back<2>(s_img, (int)end - 1, len, tag('M', '\n', 0, 0, 0, 0));
                 p = put_decimal_back(s_img, p, len, k - 1);
-                p = put_decimal_back(s_img, put_tag_back<3>(s_img, p, len, tag('\t', '+', '\t', 0, 0, 0)), len, link_ab[2 * l + 1]);
-                p = put_decimal_back(s_img, put_tag_back<3>(s_img, p, len, tag('\t', '+', '\t', 0, 0, 0)), len, link_ab[2 * l]);
+                if constexpr (NUMBERED) {
+                    p = put_decimal_back(s_img, put_tag_back<3>(s_img, p, len, tag('\t', '+', '\t', 0, 0, 0)), len, pn.link_b[l]);
+                    p = put_decimal_back(s_img, put_tag_back<3>(s_img, p, len, tag('\t', '+', '\t', 0, 0, 0)), len, pn.first + pn.link_a[l]);
+                } else {
+                    p = put_decimal_back(s_img, put_tag_back<3>(s_img, p, len, tag('\t', '+', '\t', 0, 0, 0)), len, link_ab[2 * l + 1]);
+                    p = put_decimal_back(s_img, put_tag_back<3>(s_img, p, len, tag('\t', '+', '\t', 0, 0, 0)), len, link_ab[2 * l]);
+                }
                 put_tag_back<2>(s_img, p, len, tag('L', '\t', 0, 0, 0, 0));
             } else {
-                const u32 i = r - 1;
-                if (rel > -S_NAME_MAX) {                                       // "S\t<i>\t" reaches into the tile
+                const u32 i = NUMBERED ? r - hdr : r - 1;
+                if (rel > -name_max) {                                         // "S\t<i>\t" reaches into the tile
                     int p = (int)rel + (int)(segment_off[i] - o) - 1;
                     put(s_img, p--, len, '\t');
-                    p = put_decimal_back(s_img, p, len, i);
+                    if constexpr (NUMBERED) p = put_decimal_back(s_img, p, len, pn.first + i);
+                    else p = put_decimal_back(s_img, p, len, i);
                     put_tag_back<2>(s_img, p, len, tag('S', '\t', 0, 0, 0, 0));
                 }
                 if (end - S_TAGS_MAX < len) {                                  // the tags behind the bases do
@@ -181,9 +209,9 @@ __global__ __launch_bounds__(BLOCK) void gfa_write_kernel(u32 k, u32 E, u32 R, c
             u32 r = r_lo + lo;
             const uint4 img = *(const uint4*)(s_img + rel);
             uint4 v = img;                                                   // (from the first link on there are no bases)
-            if (r <= E) {
+            if (NUMBERED ? r < hdr + E : r <= E) {
                 u32 at = (u32)(o - line_off[r]);
-                Line ln = load_line(r, E, label, label_off, segment_off, line_off);
+                Line ln = load_line<NUMBERED>(r, E, hdr, label, label_off, segment_off, line_off);
                 if (at >= ln.head && at - ln.head + 16 <= ln.bases) {
                     v = sixteen_bases(ln.src, at - ln.head);
                 } else {
@@ -193,7 +221,7 @@ __global__ __launch_bounds__(BLOCK) void gfa_write_kernel(u32 k, u32 E, u32 R, c
                     for (int i = 0; i < 16; ++i) {
                         if (r < R && at >= ln.total) {
                             ++r; at = 0;
-                            if (r < R) ln = load_line(r, E, label, label_off, segment_off, line_off);
+                            if (r < R) ln = load_line<NUMBERED>(r, E, hdr, label, label_off, segment_off, line_off);
                         }
                         const bool base_here = r < R && at >= ln.head && at - ln.head < ln.bases;
                         const u32 c = base_here ? one_base(ln.src, at - ln.head) : (in[i >> 2] >> (8 * (i & 3))) & 0xFF;
@@ -209,7 +237,42 @@ __global__ __launch_bounds__(BLOCK) void gfa_write_kernel(u32 k, u32 E, u32 R, c
     }
 }
 
+// ---- a numbered part: the same sizes, counted with the digits of the GLOBAL numbers --------------------------------------------
+// segment i of a part (named first + i): its label's checks, that its links' range ascends (link_first[0] = 0), its line's bytes
+__global__ __launch_bounds__(BLOCK) void gfa_part_measure_kernel(u32 k, u64 E, u64 first, u32 hdr, const u32* __restrict__ weight, const u32* __restrict__ kmers,
+                                                                 const u64* __restrict__ label_off, const uint8_t* __restrict__ label, u64 label_bytes,
+                                                                 const u64* __restrict__ link_first, u32* __restrict__ size, u32* __restrict__ err) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (hdr) size[0] = HEADER_BYTES;
+        if (link_first[0] != 0) atomicOr(err, (u32)ERR_LINKS);
+    }
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < E; i += (u64)gridDim.x * BLOCK) {
+        size[hdr + i] = 0;
+        if (link_first[i] > link_first[i + 1]) atomicOr(err, (u32)ERR_LINKS);
+        u32 bases = 0;
+        const int bad = label_check(label, label_off[i], label_off[i + 1], label_bytes, k, &bases);
+        if (bad) { atomicOr(err, (u32)(bad == 2 ? ERR_LABEL_LEN : ERR_LABEL)); continue; }
+        if ((u64)bases != (u64)kmers[i] + k - 1) { atomicOr(err, (u32)ERR_KMERS); continue; }
+        const u32 w = weight[i];
+        size[hdr + i] = 2 + decimal_digits(first + i) + 1 + bases + 6 + decimal_digits(bases) + 6 + decimal_digits((u64)w * kmers[i]) + 6 + decimal_digits(w) + 1;
+    }
+}
+// link l of a part: its segment is the last one whose first link is <= l (as gfa_link_fill_kernel finds it); its line's bytes
+__global__ __launch_bounds__(BLOCK) void gfa_part_link_kernel(u32 E, u64 L, u64 first, u32 k1_digits, const u64* __restrict__ link_first,
+                                                              const u64* __restrict__ link_b, u32* __restrict__ link_a, u32* __restrict__ size) {
+    for (u64 l = (u64)blockIdx.x * BLOCK + threadIdx.x; l < L; l += (u64)gridDim.x * BLOCK) {
+        u32 lo = 0, hi = E;
+        while (hi - lo > 1) { const u32 mid = lo + ((hi - lo) >> 1); if (link_first[mid] <= l) lo = mid; else hi = mid; }
+        link_a[l] = lo;
+        size[l] = 10 + decimal_digits(first + lo) + decimal_digits(link_b[l]) + k1_digits;
+    }
+}
+__global__ __launch_bounds__(BLOCK) void gfa_part_segment_off_kernel(u64 E, u64 first, u32 hdr, const u64* __restrict__ line_off, u64* __restrict__ segment_off) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < E; i += (u64)gridDim.x * BLOCK) segment_off[i] = line_off[hdr + i] + 3 + decimal_digits(first + i);
+}
+
 int check_gfa_errors(u32 err) {
+    if (err & ERR_LINKS) { set_error("gfa: d_link_first does not ascend from 0"); return KATOME_E_ARG; }
     if (err & ERR_NODE) { set_error("gfa: an edge's source or target is not below n_nodes"); return KATOME_E_ARG; }
     if (err & ERR_LABEL) { set_error("gfa: a label's offsets, pad byte or length (shorter than k bases) are malformed"); return KATOME_E_ARG; }
     if (err & ERR_LABEL_LEN) { set_error("gfa: a label of more than 2^31 bases"); return KATOME_E_UNSUPPORTED; }
@@ -290,8 +353,8 @@ int dev_gfa_plan(const GfaGraph& g, GfaPlan& plan, hipStream_t stream) {
 int dev_gfa_write(const GfaGraph& g, const GfaPlan& plan, uint8_t* text, hipStream_t stream) {
     const u64 R = 1 + g.n_edges + plan.n_links, tiles = (plan.text_bytes + TILE - 1) / TILE;
     KernelScope ks(K_GFA_WRITE, stream, plan.text_bytes);
-    hipLaunchKernelGGL(gfa_write_kernel, dim3(grid_for(tiles, 1, 256u * 16u)), dim3(BLOCK), 0, stream, g.k, (u32)g.n_edges, (u32)R, g.edge_weight, g.edge_kmers,
-                       g.label_off, g.label, plan.line_off.as<u64>(), plan.segment_off.as<u64>(), plan.link_ab.as<u32>(), plan.text_bytes, text);
+    hipLaunchKernelGGL(gfa_write_kernel<false>, dim3(grid_for(tiles, 1, 256u * 16u)), dim3(BLOCK), 0, stream, g.k, (u32)g.n_edges, (u32)R, g.edge_weight, g.edge_kmers,
+                       g.label_off, g.label, plan.line_off.as<u64>(), plan.segment_off.as<u64>(), plan.link_ab.as<u32>(), plan.text_bytes, text, PartNumbers{0, 1, nullptr, nullptr});
     KCHECK_HIP(hipGetLastError());
     return KATOME_OK;
 }
@@ -309,9 +372,105 @@ int dev_gfa(const GfaGraph& g, GfaOutput& out, hipStream_t stream) {
     return KATOME_OK;
 }
 
+int dev_gfa_part_plan(const GfaPart& g, GfaPartPlan& plan, hipStream_t stream) {
+    plan.n_links = plan.s_bytes = plan.l_bytes = 0;
+    const u64 E = g.n_edges, first = g.first_segment;
+    const u32 hdr = g.with_header ? 1u : 0u;
+    if (E >= (1ull << 32)) { set_error("gfa: %llu segments in one part, at most 2^32 - 1", (unsigned long long)E); return KATOME_E_UNSUPPORTED; }
+    if (first + E < first) { set_error("gfa: segment numbers from %llu on for %llu segments pass 2^64", (unsigned long long)first, (unsigned long long)E); return KATOME_E_UNSUPPORTED; }
+    if (!g.link_first || (E && (!g.edge_weight || !g.edge_kmers || !g.label_off || !g.label))) { set_error("null argument"); return KATOME_E_ARG; }
+    const dim3 blk(BLOCK), grid(grid_for(E, BLOCK, 256u * 32u));
+    plan.s_line_off.stream = plan.l_line_off.stream = plan.segment_off.stream = plan.link_a.stream = stream;
+    DevBuf size(stream), lsize(stream), tail(stream);
+    KCHECK(size.alloc((hdr + E + 1) * 4)); KCHECK(tail.alloc(16)); KCHECK(plan.s_line_off.alloc((hdr + E + 1) * 8)); KCHECK(plan.segment_off.alloc(E * 8 + 16));
+    KCHECK_HIP(hipMemsetAsync(tail.p, 0, 16, stream));
+    {
+        KernelScope ks(K_GFA_SIZES, stream, E);
+        hipLaunchKernelGGL(gfa_part_measure_kernel, grid, blk, 0, stream, g.k, E, first, hdr, g.edge_weight, g.edge_kmers, g.label_off, g.label, g.label_bytes,
+                           g.link_first, size.as<u32>(), tail.as<u32>());
+        KCHECK_HIP(hipGetLastError());
+    }
+    u32 err = 0;
+    u64 L = 0;
+    KCHECK_HIP(hipMemcpyAsync(&err, tail.p, 4, hipMemcpyDeviceToHost, stream));
+    KCHECK_HIP(hipMemcpyAsync(&L, g.link_first + E, 8, hipMemcpyDeviceToHost, stream));      // (the largest entry once the range is known to ascend)
+    KCHECK_HIP(hipStreamSynchronize(stream));
+    KCHECK(check_gfa_errors(err));
+    if (L && !g.link_b) { set_error("null argument"); return KATOME_E_ARG; }
+    const u64 R = hdr + E + L;
+    if (L >= (1ull << 32) || R >= 0xFFFFFFFEull) {
+        set_error("gfa: %llu lines in one part (%llu segments, %llu links), fewer than 2^32 - 2", (unsigned long long)R, (unsigned long long)E, (unsigned long long)L);
+        return KATOME_E_UNSUPPORTED;
+    }
+    KernelScope ks(K_GFA_SIZES, stream, R);
+    if (hdr + E) {
+        KCHECK(dev_scan_counts(size.as<u32>(), hdr + E, plan.s_line_off.as<u64>(), stream));
+        hipLaunchKernelGGL(gfa_part_segment_off_kernel, grid, blk, 0, stream, E, first, hdr, plan.s_line_off.as<u64>(), plan.segment_off.as<u64>());
+        KCHECK_HIP(hipGetLastError());
+        KCHECK_HIP(hipMemcpyAsync(&plan.s_bytes, plan.s_line_off.as<u64>() + hdr + E, 8, hipMemcpyDeviceToHost, stream));
+    }
+    if (L) {
+        KCHECK(lsize.alloc(L * 4)); KCHECK(plan.link_a.alloc(L * 4)); KCHECK(plan.l_line_off.alloc((L + 1) * 8));
+        hipLaunchKernelGGL(gfa_part_link_kernel, dim3(grid_for(L, BLOCK, 256u * 32u)), blk, 0, stream, (u32)E, L, first, host_digits(g.k - 1), g.link_first, g.link_b,
+                           plan.link_a.as<u32>(), lsize.as<u32>());
+        KCHECK_HIP(hipGetLastError());
+        KCHECK(dev_scan_counts(lsize.as<u32>(), L, plan.l_line_off.as<u64>(), stream));
+        KCHECK_HIP(hipMemcpyAsync(&plan.l_bytes, plan.l_line_off.as<u64>() + L, 8, hipMemcpyDeviceToHost, stream));
+    }
+    KCHECK_HIP(hipStreamSynchronize(stream));
+    plan.n_links = L;
+    return KATOME_OK;
+}
+
+// two launches of the numbered kernel: the S part's lines, then the L part's, each a text of its own that starts on a multiple of 16
+int dev_gfa_part_write(const GfaPart& g, const GfaPartPlan& plan, uint8_t* text, hipStream_t stream) {
+    const u32 hdr = g.with_header ? 1u : 0u, E = (u32)g.n_edges;
+    KernelScope ks(K_GFA_WRITE, stream, plan.s_bytes + plan.l_bytes);
+    if (plan.s_bytes) {
+        const PartNumbers pn{g.first_segment, hdr, nullptr, nullptr};
+        hipLaunchKernelGGL(gfa_write_kernel<true>, dim3(grid_for((plan.s_bytes + TILE - 1) / TILE, 1, 256u * 16u)), dim3(BLOCK), 0, stream, g.k, E, hdr + E, g.edge_weight,
+                           g.edge_kmers, g.label_off, g.label, plan.s_line_off.as<u64>(), plan.segment_off.as<u64>(), nullptr, plan.s_bytes, text, pn);
+    }
+    if (plan.l_bytes) {
+        const PartNumbers pn{g.first_segment, 0u, plan.link_a.as<u32>(), g.link_b};
+        hipLaunchKernelGGL(gfa_write_kernel<true>, dim3(grid_for((plan.l_bytes + TILE - 1) / TILE, 1, 256u * 16u)), dim3(BLOCK), 0, stream, g.k, 0u, (u32)plan.n_links,
+                           g.edge_weight, g.edge_kmers, g.label_off, g.label, plan.l_line_off.as<u64>(), plan.segment_off.as<u64>(), nullptr, plan.l_bytes,
+                           text + plan.l_offset(), pn);
+    }
+    KCHECK_HIP(hipGetLastError());
+    return KATOME_OK;
+}
+
 }  // namespace katome
 
 extern "C" {
+
+int katome_dev_gfa_part_arrays(int device, uint32_t k, uint64_t n_edges, const uint32_t* d_edge_weight, const uint32_t* d_edge_kmers,
+                               const uint64_t* d_edge_label_off, const uint8_t* d_edge_label, uint64_t label_bytes, uint64_t first_segment, int with_header,
+                               const uint64_t* d_link_first, const uint64_t* d_link_b, uint64_t* d_segment_off, uint8_t* d_text, uint64_t text_cap,
+                               uint64_t* s_bytes, uint64_t* l_offset, uint64_t* l_bytes, void* stream_) {
+    KCHECK(use_device(device));
+    KCHECK(check_k(k));
+    if (!s_bytes || !l_offset || !l_bytes) { set_error("null argument"); return KATOME_E_ARG; }
+    *s_bytes = *l_offset = *l_bytes = 0;
+    hipStream_t stream = (hipStream_t)stream_;
+    if ((uintptr_t)d_edge_label & 3) { set_error("gfa: d_edge_label must be 4-byte aligned (the kernel reads the aligned words around the bytes it needs)"); return KATOME_E_ARG; }
+    const GfaPart g{k, n_edges, d_edge_weight, d_edge_kmers, d_edge_label_off, d_edge_label, label_bytes, first_segment, with_header != 0, d_link_first, d_link_b};
+    GfaPartPlan plan;
+    KCHECK(dev_gfa_part_plan(g, plan, stream));
+    *s_bytes = plan.s_bytes; *l_offset = plan.l_offset(); *l_bytes = plan.l_bytes;
+    if (!d_text) return KATOME_OK;
+    if ((n_edges && !d_segment_off) || text_cap < plan.buffer_bytes() || ((uintptr_t)d_text & 15)) {
+        set_error("gfa: %llu + %llu bytes (each rounded up to 16, 16-byte aligned) do not fit the caller's arrays", (unsigned long long)plan.s_bytes,
+                  (unsigned long long)plan.l_bytes);
+        return KATOME_E_ARG;
+    }
+    KCHECK(dev_gfa_part_write(g, plan, d_text, stream));
+    if (n_edges) KCHECK_HIP(hipMemcpyAsync(d_segment_off, plan.segment_off.p, n_edges * 8, hipMemcpyDeviceToDevice, stream));
+    KCHECK_HIP(hipStreamSynchronize(stream));
+    return KATOME_OK;
+}
+
 
 int katome_dev_contigs_gfa(katome_builder* b, const katome_dev_contigs* c, katome_dev_gfa* out, void* stream_) {
     if (!b || !c || !out) { set_error("null argument"); return KATOME_E_ARG; }

@@ -327,24 +327,26 @@ static int assembly_to_host(katome_builder* b, uint64_t read_bytes, const Assemb
 
 // katome_unitigs_* on one GPU: the flag's remove_dead_paths, the stage letters, the traversal-free shrink, its text in FASTA layout,
 // Contigs::stats of the merged edges and, with a path, the file -- copied down a chunk at a time, the text is never whole on the host
-struct UnitigsWant { katome_unitigs* out; const char* path; };
-static int save_device_text(const katome_dev_assembly& da, const char* path) {
+// (katome_unitigs_gfa_*: the same pipeline with the graph as its ending -- `gfa` set, `out` not)
+struct UnitigsWant { katome_unitigs* out; const char* path; katome_unitigs_gfa* gfa = nullptr; };
+static int save_device_bytes(const uint8_t* d_text, uint64_t text_bytes, const char* path) {
     FILE* f = fopen(path, "wb");
     if (!f) { set_error("couldn't create %s: %s", path, CREATE_ERROR_KINDS[create_error_kind(errno)]); return KATOME_E_OPEN; }      // asm/mod.rs:62
-    const size_t chunk = std::min<uint64_t>(std::max<uint64_t>(da.text_bytes, 1), (uint64_t)64 << 20);
+    const size_t chunk = std::min<uint64_t>(std::max<uint64_t>(text_bytes, 1), (uint64_t)64 << 20);
     std::vector<uint8_t> buf;
     int rc = KATOME_OK;
     try { buf.resize(chunk); }
     catch (const std::bad_alloc&) { set_error("out of host memory"); rc = KATOME_E_OOM; }
-    for (uint64_t at = 0; at < da.text_bytes && !rc; at += chunk) {
-        const size_t n = std::min<uint64_t>(chunk, da.text_bytes - at);
-        if (hipMemcpy(buf.data(), da.d_text + at, n, hipMemcpyDeviceToHost) != hipSuccess) { set_error("device -> host copy failed: %s", hipGetErrorString(hipGetLastError())); rc = KATOME_E_DEVICE; }
+    for (uint64_t at = 0; at < text_bytes && !rc; at += chunk) {
+        const size_t n = std::min<uint64_t>(chunk, text_bytes - at);
+        if (hipMemcpy(buf.data(), d_text + at, n, hipMemcpyDeviceToHost) != hipSuccess) { set_error("device -> host copy failed: %s", hipGetErrorString(hipGetLastError())); rc = KATOME_E_DEVICE; }
         else if (fwrite(buf.data(), 1, n, f) != n) { set_error("couldn't write %s", path); rc = KATOME_E_OPEN; }
     }
     if (fclose(f) != 0 && !rc) { set_error("couldn't write %s", path); rc = KATOME_E_OPEN; }
     if (rc) (void)remove(path);
     return rc;
 }
+static int save_device_text(const katome_dev_assembly& da, const char* path) { return save_device_bytes(da.d_text, da.text_bytes, path); }
 static int unitigs_to_host(katome_builder* b, uint64_t read_bytes, const UnitigsWant& want, const char* stages, uint64_t genome_len) {
     katome_dev_graph dg;
     KCHECK(katome_dev_finalize(b, &dg, nullptr));
@@ -352,6 +354,21 @@ static int unitigs_to_host(katome_builder* b, uint64_t read_bytes, const Unitigs
     KCHECK(run_stages(stages, BuilderStages{b, genome_len}));
     katome_dev_contigs dc;
     KCHECK(katome_dev_shrink_mode(b, KATOME_SHRINK_FAST, &dc, nullptr, nullptr));
+    if (want.gfa) {                                                  // the graph: katome_dev_contigs_gfa's text is the file
+        katome_dev_gfa dgfa;
+        KCHECK(katome_dev_contigs_gfa(b, &dc, &dgfa, nullptr));
+        katome_unitigs_gfa* u = want.gfa;
+        u->n_segments = dgfa.n_segments; u->n_links = dgfa.n_links; u->text_bytes = dgfa.text_bytes; u->read_bytes = read_bytes; u->k = b->s.k; u->n_devices = 1;
+        std::vector<uint32_t> kmers;
+        try { kmers.resize(dc.n_edges); }
+        catch (const std::bad_alloc&) { set_error("out of host memory"); return KATOME_E_OOM; }
+        if (dc.n_edges) KCHECK_HIP(hipMemcpy(kmers.data(), dc.d_edge_kmers, dc.n_edges * 4, hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < dc.n_edges; ++i) {
+            const uint64_t len = (uint64_t)kmers[i] + b->s.k - 1;
+            u->total_bases += len; u->longest = std::max(u->longest, len);
+        }
+        return want.path ? save_device_bytes(dgfa.d_text, dgfa.text_bytes, want.path) : KATOME_OK;
+    }
     katome_dev_assembly da;
     KCHECK(katome_dev_contigs_text(b, &dc, KATOME_TEXT_FASTA, &da, nullptr));
     katome_unitigs* u = want.out;
@@ -622,6 +639,21 @@ static int sharded_unitigs(MultiBuild& mb, int r, int n, katome_dist_builder* d,
     const UnitigsWant& want = mb.finish.unitigs;
     katome_dist_shrink_stats ss;
     KCHECK(katome_dist_shrink(d, nullptr, &ss, stream));
+    if (want.gfa) {                                                  // the graph: the join across ranks, the numbered text, the file
+        katome_dist_gfa g;
+        KCHECK(katome_dist_contigs_gfa(d, &g, stream));
+        uint64_t bases[1] = {0};                                     // (the k-mers on all ranks' merged edges: their bases are k - 1 more each)
+        KCHECK(dist_gfa_total_kmers(d, bases, stream));
+        if (r == 0) {
+            katome_unitigs_gfa* u = want.gfa;
+            u->n_segments = g.total_segments; u->n_links = g.total_links; u->text_bytes = g.total_text_bytes; u->read_bytes = mb.read_bytes;
+            u->k = mb.s->k; u->n_devices = (uint32_t)n;
+            u->total_bases = bases[0] + g.total_segments * (uint64_t)(mb.s->k - 1);
+            u->longest = g.total_segments ? ss.longest_path + mb.s->k - 1 : 0;
+            u->shrink = ss;
+        }
+        return want.path ? katome_dist_gfa_save(d, &g, want.path) : KATOME_OK;
+    }
     katome_dist_assembly a;
     KCHECK(katome_dist_contigs_text(d, KATOME_TEXT_FASTA, &a, stream));
     katome_contig_stats cs;
@@ -891,13 +923,17 @@ int katome_assemble_packed(const katome_settings* s, const uint8_t* packed, uint
     return build_packed_impl(s, packed, n_reads, read_len, skip, f);
 }
 // (the same check on every route: the stages work on the links of a first-seen build)
-static int unitigs_finish(const katome_settings* s, const char* stages, uint64_t genome_len, const char* out_path, katome_unitigs* out, Finish& f) {
-    if (!out) { set_error("null argument"); return KATOME_E_ARG; }
-    memset(out, 0, sizeof *out);
+static int unitigs_refusal(const katome_settings* s, const char* stages) {
     if (s && !(s->flags & KATOME_FLAG_FIRST_SEEN_ORDER) && ((stages && *stages) || (s->flags & KATOME_FLAG_REMOVE_DEAD_PATHS))) {
         set_error("unitigs: stage letters and KATOME_FLAG_REMOVE_DEAD_PATHS need KATOME_FLAG_FIRST_SEEN_ORDER");
         return KATOME_E_ARG;
     }
+    return KATOME_OK;
+}
+static int unitigs_finish(const katome_settings* s, const char* stages, uint64_t genome_len, const char* out_path, katome_unitigs* out, Finish& f) {
+    if (!out) { set_error("null argument"); return KATOME_E_ARG; }
+    memset(out, 0, sizeof *out);
+    KCHECK(unitigs_refusal(s, stages));
     f.unitigs = UnitigsWant{out, out_path}; f.want_unitigs = true; f.stages = stages; f.genome_len = genome_len;
     return KATOME_OK;
 }
@@ -905,6 +941,20 @@ int katome_unitigs_packed(const katome_settings* s, const uint8_t* packed, uint6
                           const char* stages, uint64_t original_genome_length, const char* out_path, katome_unitigs* out) {
     Finish f{nullptr, nullptr};
     KCHECK(unitigs_finish(s, stages, original_genome_length, out_path, out, f));
+    return build_packed_impl(s, packed, n_reads, read_len, skip, f);
+}
+// katome_unitigs_gfa_*: the unitigs route with the graph as its ending
+static int unitigs_gfa_finish(const katome_settings* s, const char* stages, uint64_t genome_len, const char* out_path, katome_unitigs_gfa* out, Finish& f) {
+    if (!out) { set_error("null argument"); return KATOME_E_ARG; }
+    memset(out, 0, sizeof *out);
+    KCHECK(unitigs_refusal(s, stages));
+    f.unitigs = UnitigsWant{nullptr, out_path, out}; f.want_unitigs = true; f.stages = stages; f.genome_len = genome_len;
+    return KATOME_OK;
+}
+int katome_unitigs_gfa_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip,
+                              const char* stages, uint64_t original_genome_length, const char* out_path, katome_unitigs_gfa* out) {
+    Finish f{nullptr, nullptr};
+    KCHECK(unitigs_gfa_finish(s, stages, original_genome_length, out_path, out, f));
     return build_packed_impl(s, packed, n_reads, read_len, skip, f);
 }
 // (the same check on every route, before any GPU work)
@@ -1087,6 +1137,12 @@ int katome_unitigs_files(const katome_settings* s, const char* const* paths, siz
                          const char* out_path, katome_unitigs* out) {
     Finish f{nullptr, nullptr};
     KCHECK(unitigs_finish(s, stages, original_genome_length, out_path, out, f));
+    return build_files_impl(s, paths, n_paths, f);
+}
+int katome_unitigs_gfa_files(const katome_settings* s, const char* const* paths, size_t n_paths, const char* stages, uint64_t original_genome_length,
+                             const char* out_path, katome_unitigs_gfa* out) {
+    Finish f{nullptr, nullptr};
+    KCHECK(unitigs_gfa_finish(s, stages, original_genome_length, out_path, out, f));
     return build_files_impl(s, paths, n_paths, f);
 }
 int katome_gfa_files(const katome_settings* s, const char* const* paths, size_t n_paths, const char* stages, uint64_t original_genome_length,

@@ -707,6 +707,28 @@ def gfa_arrays(k, n_nodes, edge_src, edge_dst, edge_weight, edge_kmers, edge_lab
     return DeviceGfa(n_edges, nl.value, nb.value, text[:nb.value], seg[:n_edges], first)
 
 
+def gfa_part_arrays(k, edge_weight, edge_kmers, edge_label_off, edge_label, first_segment, with_header, link_first, link_b, device=0,
+                    label_bytes=None):
+    """the numbered GFA writer on the caller's tensors (katome_dev_gfa_part_arrays): one PART of a text whose other parts are
+    written elsewhere.  Segment i is named first_segment + i; its links are link_b[link_first[i]:link_first[i + 1]] (int64 tensors;
+    link_b holds global numbers as uint64 bit patterns); the header line is written or not -> (text uint8, s_bytes, l_offset,
+    l_bytes, segment_off int64): the S part is text[:s_bytes], the L part text[l_offset:l_offset + l_bytes]"""
+    tdev = edge_label_off.device
+    n_edges = edge_label_off.numel() - 1
+    if label_bytes is None:
+        label_bytes = edge_label.numel()
+    sb, lo, lb = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    L = _lib.lib()
+    args = (device, k, n_edges, _ptr(edge_weight), _ptr(edge_kmers), _ptr(edge_label_off), _ptr(edge_label), label_bytes, first_segment,
+            1 if with_header else 0, _ptr(link_first), _ptr(link_b))
+    _check(L.katome_dev_gfa_part_arrays(*args, None, None, 0, C.byref(sb), C.byref(lo), C.byref(lb), _stream()))
+    cap = lo.value + (lb.value + 15) // 16 * 16
+    seg = torch.empty(max(n_edges, 1), dtype=torch.int64, device=tdev)
+    text = torch.full((max(cap, 16),), 0xAA, dtype=torch.uint8, device=tdev)
+    _check(L.katome_dev_gfa_part_arrays(*args, _ptr(seg), _ptr(text), cap, C.byref(sb), C.byref(lo), C.byref(lb), _stream()))
+    return text[:cap], sb.value, lo.value, lb.value, seg[:n_edges]
+
+
 def synth_reads(first_read, n_reads, read_len, genome_len, err_rate, n_inject_percent=0, device=0):
     """deterministic synthetic workload, generated in HBM (DESIGN.md 'Synthetic workload')"""
     tdev = torch.device("cuda", device)

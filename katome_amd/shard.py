@@ -213,6 +213,26 @@ class RankAssembly:
         self.text = _view(a.d_text, (a.text_bytes,), "|u1", owner, device)
 
 
+class RankGfa:
+    """this rank's two parts of the GFA 1 text of the sharded shrink (ShardedBuilder.contigs_gfa; zero-copy views of the builder's
+    device arrays, valid until the next contigs_gfa or close).  Segments are numbered rank-major like the records of
+    contigs_text: segment first_segment + j is this rank's merged edge j.  The whole text is the header line, the ranks' S parts
+    in rank order, then their L parts: this rank's s_text (on rank 0 the header line first) starts at byte s_base, its l_text at
+    l_base of total_text_bytes.  segment_off[j]: segment j's first base in s_text; the links of segment j are lines
+    link_first[j] .. link_first[j + 1] of l_text and link_b holds their second segments' global numbers (uint64 bit patterns)."""
+
+    def __init__(self, g, owner, device):
+        self._g = g
+        for f in ("n_segments", "first_segment", "total_segments", "n_links", "total_links", "s_bytes", "s_base", "l_bytes", "l_base",
+                  "total_text_bytes"):
+            setattr(self, f, getattr(g, f))
+        self.s_text = _view(g.d_text, (g.s_bytes,), "|u1", owner, device)
+        self.l_text = _view(g.d_link_text, (g.l_bytes,), "|u1", owner, device)
+        self.segment_off = _view(g.d_segment_off, (g.n_segments,), "<i8", owner, device)
+        self.link_first = _view(g.d_link_first, (g.n_segments + 1,), "<i8", owner, device)
+        self.link_b = _view(g.d_link_b, (g.n_links,), "<i8", owner, device)
+
+
 def contig_stats_arrays(comm, kmers, k, genome_len, device=0):
     """Contigs::stats of ALL ranks' contigs from each rank's own k-mer counts (int32 / uint32 device tensor, may be empty; a
     contig's length is its count + k - 1), no rank holding another's (katome_dist_contig_stats_arrays) -> ContigsStats, the same
@@ -360,6 +380,18 @@ class ShardedBuilder(_ViewOwner):
         """the file of the last contigs_text(), every rank writing its part at its offset (katome_dist_contigs_save)"""
         import os
         _check(_lib.lib().katome_dist_contigs_save(self._h, C.byref(assembly._a), os.fsencode(path)))
+
+    def contigs_gfa(self):
+        """the unitig graph of the last shrink() as GFA 1, no gather: the links joined across ranks, this rank's S and L parts
+        written on the device (katome_dist_contigs_gfa) -> RankGfa.  Collective"""
+        g = _lib.DistGfa()
+        _check(_lib.lib().katome_dist_contigs_gfa(self._h, C.byref(g), _stream()))
+        return RankGfa(g, self, self.tdev)
+
+    def save_gfa(self, gfa, path):
+        """the file of the last contigs_gfa(), every rank writing its two parts at their offsets (katome_dist_gfa_save)"""
+        import os
+        _check(_lib.lib().katome_dist_gfa_save(self._h, C.byref(gfa._g), os.fsencode(path)))
 
     def stats(self):
         """CollectionStats of the WHOLE graph as it stands, the same on every rank, no gather (katome_dist_graph_stats).
