@@ -496,7 +496,7 @@ int katome_dev_contigs_text(katome_builder *b, const katome_dev_contigs *contigs
  * the weight of a path's FIRST k-mer (shrinker.rs:181,200), so KC is that weight times the k-mers merged into the edge, not the
  * sum of the path's k-mer counts; ew is that weight itself.  Links are ordered by a, then b; a self-loop links to itself, parallel
  * merged edges are distinct segments, every orientation is + (the two strands of a reverse_complement build are separate edges
- * and therefore separate segments; strand twins are not merged).  No edges: the header line alone.
+ * and therefore separate segments; katome_dev_contigs_gfa_strands below merges strand twins).  No edges: the header line alone.
  * d_text holds text_bytes bytes in a buffer that is a multiple of 16 bytes (zeros behind the text up to the next multiple);
  * d_segment_off[i] = offset of segment i's first base; the links of segment a are lines d_link_first[a] .. d_link_first[a + 1]
  * of the L region (d_link_first[n_segments] = n_links).
@@ -515,6 +515,42 @@ typedef struct {
  * form.  The builder's graph and the shrink result are left untouched; the result is owned by the builder until its next
  * katome_dev_contigs_gfa or destroy.                                                                                      */
 int katome_dev_contigs_gfa(katome_builder *b, const katome_dev_contigs *contigs, katome_dev_gfa *out, void *stream);
+
+/* ---- the unitig graph as BIDIRECTED GFA 1 (csrc/gfa_strands.hip): strand twins merged into one segment, +/- links ----------
+ * The same shrink result with a merged edge and its reverse complement written as ONE double-stranded segment, as GFA readers
+ * model it.  twin(i) = the j whose bases are the reverse complement of edge i's, or none: j is found through its first k-mer
+ * (revcomp of i's last k-mer; a k-mer lies on one merged edge, so a first k-mer names its segment) and counts only if the WHOLE
+ * text agrees, base for base (after remove_dead_paths a strand's middle can differ).  twin(i) == i: a self-twin.
+ * rep(i) = min(i, twin(i)), or i without a twin; o(i) = '-' where twin(i) < i, '+' otherwise (unpaired segments and self-twins too).
+ * The text, byte for byte:
+ *   H\tVN:Z:1.0\n
+ *   S\t<r>\t<bases of edge r>\tLN:i:<bases>\tKC:i:<w_r * kmers_r>\tew:i:<w_r>[\trc:i:<j>\trw:i:<w_j>]\n   one per representative r, ascending
+ *   L\t<x>\t<ox>\t<y>\t<oy>\t<k-1>M\n
+ * The bracketed tags are there exactly when r has a twin j (a self-twin: j = r).  The name stays the merged edge's own index, so
+ * S <r> is still the record >katome_<r> of the unitig FASTA and rc:i: names the record that was folded in; rw is the twin's weight
+ * (shrink keeps the weight of a path's FIRST k-mer, which for the twin is r's last: the two generally differ).
+ * Links: every (a, b) with edge_dst[a] == edge_src[b] spells (rep a, o a, rep b, o b); its conjugate spelling is
+ * (rep b, flip o b, rep a, flip o a), where flip exchanges + and - but leaves a self-twin at +.  The smaller of the two under the
+ * order (x, ox, y, oy) with + < - is kept, duplicates are dropped, and the lines ascend in that order: a link and its mirror are
+ * one line, a hairpin (x + x -) is written once, a link whose mirror is missing is still written.  No edges: the header alone.
+ * d_text as for katome_dev_gfa; d_segment_name[s] = the s-th S line's name r; d_segment_off[s] = offset of its first base; the
+ * links whose x is that segment are lines d_link_first[s] .. d_link_first[s + 1] of the L region; d_edge_twin[i] = twin(i), all
+ * ones for none.  n_unpaired: merged edges without a twin; n_self_twins: those that are their own.
+ * Validation and limits as for katome_dev_gfa; two segments with the same first k-mer (not a shrink result): KATOME_E_ARG, with a
+ * message that names one such pair.  Scratch: a few words per segment, per vertex and per link, never a
+ * second copy of the text or the labels.  Profile phase "gfa_strands".  Synchronises.  The merged form of the sharded shrink
+ * without a gather (katome_dist_contigs_gfa) is not offered.                                                                */
+typedef struct {
+    uint64_t  n_segments, n_links, text_bytes, n_unpaired, n_self_twins;
+    uint8_t  *d_text;
+    uint64_t *d_segment_name;            /* [n_segments]                                                               */
+    uint64_t *d_segment_off;             /* [n_segments]                                                               */
+    uint64_t *d_link_first;              /* [n_segments + 1]                                                           */
+    uint64_t *d_edge_twin;               /* [contigs->n_edges]                                                         */
+} katome_dev_gfa_strands;
+/* ownership as for katome_dev_contigs_gfa; the result has its own buffers: a later katome_dev_contigs_gfa leaves it valid, and
+ * this call leaves that one's.                                                                                            */
+int katome_dev_contigs_gfa_strands(katome_builder *b, const katome_dev_contigs *contigs, katome_dev_gfa_strands *out, void *stream);
 
 /* Contigs::stats (stats/contigs.rs:31-89) from the contigs' lengths: host, pure.  No contigs: all zeros.  A tipping point of 0
  * with contigs present (sum / 2, (0.1 * sum) truncated, original_genome_length / 2), where the reference panics on
@@ -570,6 +606,26 @@ int  katome_gfa_packed(const katome_settings *s, const uint8_t *packed, uint64_t
                        const char *stages, uint64_t original_genome_length, const char *out_path /* nullable */, katome_gfa **out);
 int  katome_gfa_save(const katome_gfa *g, const char *path);
 void katome_gfa_free(katome_gfa *g);
+/* the same with strand twins merged (katome_dev_contigs_gfa_strands has the format): stage letters, shrink (AUTO), out_path, the
+ * result handed back on KATOME_E_OPEN and n_devices > 1 (built sharded, gathered to the first GPU) exactly as katome_gfa_*.  The
+ * merged GFA of the sharded shrink WITHOUT a gather is not offered: katome_unitigs_gfa_* writes the two-strand form only.     */
+typedef struct {
+    uint64_t n_segments, n_links, text_bytes, read_bytes;
+    uint32_t k, _pad;
+    const uint8_t  *text;
+    const uint64_t *segment_off;         /* [n_segments]                                                               */
+    const uint64_t *link_first;          /* [n_segments + 1]                                                           */
+    uint64_t n_edges, n_unpaired, n_self_twins;
+    const uint64_t *segment_name;        /* [n_segments]                                                               */
+    const uint64_t *edge_twin;           /* [n_edges], all ones: none                                                  */
+} katome_gfa_strands;
+int  katome_gfa_strands_files(const katome_settings *s, const char *const *paths, size_t n_paths, const char *stages,
+                              uint64_t original_genome_length, const char *out_path /* nullable */, katome_gfa_strands **out);
+int  katome_gfa_strands_packed(const katome_settings *s, const uint8_t *packed, uint64_t n_reads, uint32_t read_len, const uint8_t *skip,
+                               const char *stages, uint64_t original_genome_length, const char *out_path /* nullable */,
+                               katome_gfa_strands **out);
+int  katome_gfa_strands_save(const katome_gfa_strands *g, const char *path);
+void katome_gfa_strands_free(katome_gfa_strands *g);
 
 /* first half of finalize only: sorted distinct edges (key, weight); used by the multi-GPU
  * driver, which resolves node ids across ranks itself                                      */
@@ -1000,6 +1056,15 @@ int katome_dev_gfa_arrays(int device, uint32_t k, uint64_t n_nodes, uint64_t n_e
                           const uint64_t *d_edge_label_off, const uint8_t *d_edge_label, uint64_t label_bytes,
                           uint64_t *d_segment_off, uint64_t *d_link_first, uint8_t *d_text, uint64_t text_cap,
                           uint64_t *n_links, uint64_t *text_bytes, void *stream);
+/* katome_dev_contigs_gfa_strands on the caller's arrays, in the form of katome_dev_gfa_arrays.  counts[5] = {n_segments, n_links,
+ * text_bytes, n_unpaired, n_self_twins} are always set.  d_text NULL: nothing else is written (a size query).  Otherwise
+ * d_segment_name and d_segment_off need room for n_segments entries, d_link_first for n_segments + 1, d_edge_twin for n_edges
+ * (n_segments <= n_edges), and d_text, 16-byte aligned, for text_cap >= text_bytes rounded up to 16.  Synchronises. */
+int katome_dev_gfa_strands_arrays(int device, uint32_t k, uint64_t n_nodes, uint64_t n_edges, const uint64_t *d_edge_src,
+                                  const uint64_t *d_edge_dst, const uint32_t *d_edge_weight, const uint32_t *d_edge_kmers,
+                                  const uint64_t *d_edge_label_off, const uint8_t *d_edge_label, uint64_t label_bytes,
+                                  uint64_t *d_segment_name, uint64_t *d_segment_off, uint64_t *d_link_first, uint64_t *d_edge_twin,
+                                  uint8_t *d_text, uint64_t text_cap, uint64_t *counts, void *stream);
 /* the GFA writer on a numbered PART of a text whose other parts are written elsewhere (katome_dist_contigs_gfa): segment i is named
  * first_segment + i (up to 20 digits), its links are d_link_b[d_link_first[i] .. d_link_first[i + 1]) -- global numbers, n_links =
  * d_link_first[n_edges] --, the header line is written or not.  d_text holds the S part (the header first) at 0 and the L part

@@ -90,6 +90,19 @@ class Gfa(C.Structure):
                 ("k", C.c_uint32), ("_pad", C.c_uint32), ("text", u8p), ("segment_off", u64p), ("link_first", u64p)]
 
 
+class DevGfaStrands(C.Structure):
+    _fields_ = [("n_segments", C.c_uint64), ("n_links", C.c_uint64), ("text_bytes", C.c_uint64), ("n_unpaired", C.c_uint64),
+                ("n_self_twins", C.c_uint64), ("d_text", C.c_void_p), ("d_segment_name", C.c_void_p), ("d_segment_off", C.c_void_p),
+                ("d_link_first", C.c_void_p), ("d_edge_twin", C.c_void_p)]
+
+
+class GfaStrands(C.Structure):
+    _fields_ = [("n_segments", C.c_uint64), ("n_links", C.c_uint64), ("text_bytes", C.c_uint64), ("read_bytes", C.c_uint64),
+                ("k", C.c_uint32), ("_pad", C.c_uint32), ("text", u8p), ("segment_off", u64p), ("link_first", u64p),
+                ("n_edges", C.c_uint64), ("n_unpaired", C.c_uint64), ("n_self_twins", C.c_uint64), ("segment_name", u64p),
+                ("edge_twin", u64p)]
+
+
 class DevGraph(C.Structure):
     _fields_ = [("n_nodes", C.c_uint64), ("n_edges", C.c_uint64), ("key_words", C.c_uint32),
                 ("label_stride", C.c_uint32), ("d_edge_key", C.c_void_p), ("d_edge_weight", C.c_void_p),
@@ -224,6 +237,12 @@ SYMBOLS = {
     "katome_gfa_packed": (_i, [C.POINTER(Settings), _vp, _u64, _u32, _vp, C.c_char_p, _u64, C.c_char_p, C.POINTER(C.POINTER(Gfa))]),
     "katome_gfa_save": (_i, [C.POINTER(Gfa), C.c_char_p]),
     "katome_gfa_free": (None, [C.POINTER(Gfa)]),
+    "katome_dev_contigs_gfa_strands": (_i, [_vp, C.POINTER(DevContigs), C.POINTER(DevGfaStrands), _vp]),
+    "katome_dev_gfa_strands_arrays": (_i, [_i, _u32, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, u64p, _vp]),
+    "katome_gfa_strands_files": (_i, [C.POINTER(Settings), _pp, _sz, C.c_char_p, _u64, C.c_char_p, C.POINTER(C.POINTER(GfaStrands))]),
+    "katome_gfa_strands_packed": (_i, [C.POINTER(Settings), _vp, _u64, _u32, _vp, C.c_char_p, _u64, C.c_char_p, C.POINTER(C.POINTER(GfaStrands))]),
+    "katome_gfa_strands_save": (_i, [C.POINTER(GfaStrands), C.c_char_p]),
+    "katome_gfa_strands_free": (None, [C.POINTER(GfaStrands)]),
     "katome_unitigs_files": (_i, [C.POINTER(Settings), _pp, _sz, C.c_char_p, _u64, C.c_char_p, C.POINTER(Unitigs)]),
     "katome_unitigs_packed": (_i, [C.POINTER(Settings), _vp, _u64, _u32, _vp, C.c_char_p, _u64, C.c_char_p, C.POINTER(Unitigs)]),
     "katome_unitigs_gfa_files": (_i, [C.POINTER(Settings), _pp, _sz, C.c_char_p, _u64, C.c_char_p, C.POINTER(UnitigsGfa)]),

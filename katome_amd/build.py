@@ -195,13 +195,35 @@ class Gfa:
             pass
 
 
-def _gfa_result(rc, gp):
+class GfaStrands(Gfa):
+    """result of GpuGraph.gfa(merge_strands=True): the same with strand twins merged into one segment and +/- links.  S line s is
+    merged edge segment_name[s]; edge_twin[i]: the merged edge that is edge i's reverse complement (2^64 - 1: none); n_edges merged
+    edges, n_unpaired of them without a twin, n_self_twins their own"""
+
+    def __init__(self, gp):
+        super().__init__(gp)
+        g = gp.contents
+        self.n_edges, self.n_unpaired, self.n_self_twins = g.n_edges, g.n_unpaired, g.n_self_twins
+        self.segment_name = np.ctypeslib.as_array(g.segment_name, (g.n_segments,)).copy() if g.n_segments else np.zeros(0, np.uint64)
+        self.edge_twin = np.ctypeslib.as_array(g.edge_twin, (g.n_edges,)).copy() if g.n_edges else np.zeros(0, np.uint64)
+
+    def save_to_file(self, path):
+        _check(_lib.lib().katome_gfa_strands_save(self._gp, os.fsencode(path)))
+
+    def __del__(self):
+        try:
+            _lib.lib().katome_gfa_strands_free(self._gp)
+        except Exception:       # interpreter shutdown
+            pass
+
+
+def _gfa_result(rc, gp, cls=Gfa):
     """a path that could not be created: the GFA was made all the same, and travels with the exception (`.result`)"""
     if rc != 0:
         err = KatomePanic(rc, _lib.last_error())
-        err.result = Gfa(gp) if gp else None
+        err.result = cls(gp) if gp else None
         raise err
-    return Gfa(gp)
+    return cls(gp)
 
 
 FLAG_FIRST_SEEN_ORDER = 1
@@ -383,24 +405,26 @@ class GpuGraph:
     # ---- the unitig graph as GFA 1 ---------------------------------------------------------------
     @staticmethod
     def gfa(input_files, ft, reverse_complement, threshold, stages="", original_genome_length=0, output_file=None, device=0, n_devices=1,
-            first_seen_order=None, ranks_share_device=False):
+            first_seen_order=None, ranks_share_device=False, merge_strands=False):
         """the build, the stage letters (as for create(); they need the reference's numbering), shrink and the GFA of the unitig
         graph -- with output_file also the file --, all behind one call (katome_gfa_files) -> Gfa; uses the global k.
         first_seen_order: None = whenever stage letters or several devices ask for it (an empty `stages` on one device builds by
-        packed key and shrinks in the fast form)"""
+        packed key and shrinks in the fast form).  merge_strands: strand twins as one segment with +/- links
+        (katome_gfa_strands_files) -> GfaStrands"""
         if first_seen_order is None:
             first_seen_order = bool(stages) or n_devices > 1
         s = make_settings(K_SIZE, ft, reverse_complement, threshold, device, first_seen_order=first_seen_order, n_devices=n_devices,
                           ranks_share_device=ranks_share_device)
-        gp = C.POINTER(_lib.Gfa)()
-        rc = _lib.lib().katome_gfa_files(C.byref(s), _paths(input_files), len(input_files), (stages or "").encode(), original_genome_length,
-                                         os.fsencode(output_file) if output_file is not None else None, C.byref(gp))
-        return _gfa_result(rc, gp)
+        gp = C.POINTER(_lib.GfaStrands if merge_strands else _lib.Gfa)()
+        entry = _lib.lib().katome_gfa_strands_files if merge_strands else _lib.lib().katome_gfa_files
+        rc = entry(C.byref(s), _paths(input_files), len(input_files), (stages or "").encode(), original_genome_length,
+                   os.fsencode(output_file) if output_file is not None else None, C.byref(gp))
+        return _gfa_result(rc, gp, GfaStrands if merge_strands else Gfa)
 
     @staticmethod
     def gfa_from_packed(packed, n_reads, read_len, skip=None, reverse_complement=False, threshold=0, stages="", original_genome_length=0,
-                        output_file=None, device=0, k=None, n_devices=1, first_seen_order=None, ranks_share_device=False):
-        """the same from 2-bit packed reads (numpy uint8; katome_gfa_packed)"""
+                        output_file=None, device=0, k=None, n_devices=1, first_seen_order=None, ranks_share_device=False, merge_strands=False):
+        """the same from 2-bit packed reads (numpy uint8; katome_gfa_packed, katome_gfa_strands_packed)"""
         if first_seen_order is None:
             first_seen_order = bool(stages) or n_devices > 1
         s = make_settings(K_SIZE if k is None else k, InputFileType.Fastq, reverse_complement, threshold, device,
@@ -410,10 +434,11 @@ class GpuGraph:
         if skip is not None:
             skip = np.ascontiguousarray(skip, dtype=np.uint8)
             skip_p = skip.ctypes.data
-        gp = C.POINTER(_lib.Gfa)()
-        rc = _lib.lib().katome_gfa_packed(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, (stages or "").encode(),
-                                          original_genome_length, os.fsencode(output_file) if output_file is not None else None, C.byref(gp))
-        return _gfa_result(rc, gp)
+        gp = C.POINTER(_lib.GfaStrands if merge_strands else _lib.Gfa)()
+        entry = _lib.lib().katome_gfa_strands_packed if merge_strands else _lib.lib().katome_gfa_packed
+        rc = entry(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, (stages or "").encode(),
+                   original_genome_length, os.fsencode(output_file) if output_file is not None else None, C.byref(gp))
+        return _gfa_result(rc, gp, GfaStrands if merge_strands else Gfa)
 
     # ---- Stats<CollectionStats> (stats/collections.rs:137-168) ---------------------------------
     def stats(self) -> CollectionStats:

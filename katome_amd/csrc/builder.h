@@ -114,6 +114,7 @@ struct katome_builder {
     TextOutput assembly;               // ... and its result
     TextOutput unitig_text;            // result of katome_dev_contigs_text
     GfaOutput gfa;                     // result of katome_dev_contigs_gfa
+    GfaStrandsOutput gfa_strands;      // result of katome_dev_contigs_gfa_strands (its own buffers: neither call touches the other's result)
     DevBuf edge_age;                   // first-seen-order graphs once remove_* has moved edges (PruneGraph::edge_age)
     uint64_t n_nodes = 0;
     bool finalized = false;

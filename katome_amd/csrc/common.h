@@ -104,6 +104,7 @@ enum Phase { PH_EXTRACT, PH_REGION_ORDER, PH_INSERT, PH_EMIT_EDGES, PH_SORT_EDGE
              PH_GRAPH_STATS, PH_WEIGHT_SPECTRUM, K_STATS_DEGREES, K_STATS_WEIGHTS, K_STATS_NODES, K_SPECTRUM,
              PH_COLLAPSE, K_TEXT_WRITE,
              PH_GFA, K_GFA_SORT, K_GFA_SIZES, K_GFA_WRITE,
+             PH_GFA_STRANDS, K_GFAS_KEYS, K_GFAS_SEARCH, K_GFAS_VERIFY, K_GFAS_LINKS, K_GFAS_SIZES, K_GFAS_WRITE,
              PH_COUNT };
 static const char* const PHASE_NAMES[PH_COUNT] = {
     "extract", "region_order", "insert", "emit_edges", "sort_edges", "node_set", "rank", "labels", "insert_tiles", "expand_tiles",
@@ -120,7 +121,8 @@ static const char* const PHASE_NAMES[PH_COUNT] = {
     "k:group_merge_kernel",
     "graph_stats", "weight_spectrum", "k:stats_degree_kernel", "k:stats_weight_kernel", "k:stats_node_kernel", "k:spectrum_kernel",
     "collapse", "k:text_write_kernel",
-    "gfa", "k:gfa link sort", "k:gfa sizes", "k:gfa_write_kernel"};
+    "gfa", "k:gfa link sort", "k:gfa sizes", "k:gfa_write_kernel",
+    "gfa_strands", "k:gfa_strands keys+sort", "k:strand_search_kernel", "k:strand_verify_kernel", "k:gfa_strands links", "k:gfa_strands sizes", "k:gfa_strands_write_kernel"};
 struct Profiler {
     bool on = false;
     struct Ev { int phase; hipEvent_t a, b; uint64_t work; };      // work: elements the launch processed (K_* entries)
@@ -481,6 +483,23 @@ struct GfaPartPlan {
 };
 int dev_gfa_part_plan(const GfaPart& g, GfaPartPlan& plan, hipStream_t stream);                        // validates, measures; synchronises
 int dev_gfa_part_write(const GfaPart& g, const GfaPartPlan& plan, uint8_t* text, hipStream_t stream);  // text: plan.buffer_bytes()
+// gfa_strands.hip: the same graph with strand twins folded into one segment and +/- links (include/katome_gpu.h has the format).
+// The plan: every line's offset (line 0 the header, 1 + s representative name[s], 1 + n_segments + l link l), every representative's
+// first base and first link, every edge's twin (all-ones: none) and the distinct links as keys of key_words words:
+// (2 * x + (ox == '-')) above (2 * y + (oy == '-')), field_bits each in one word, a word each in two
+struct GfaStrandsPlan {
+    DevBuf line_off, segment_off, link_first, name, twin, link_keys;
+    uint32_t key_words = 1, field_bits = 2;
+    uint64_t n_segments = 0, n_links = 0, text_bytes = 0, n_unpaired = 0, n_self_twins = 0;
+};
+struct GfaStrandsOutput {
+    DevBuf text, segment_name, segment_off, link_first, edge_twin;
+    uint64_t n_segments = 0, n_links = 0, text_bytes = 0, n_unpaired = 0, n_self_twins = 0;
+};
+int dev_gfa_strands_plan(const GfaGraph& g, GfaStrandsPlan& plan, hipStream_t stream);      // validates (dev_gfa_plan), pairs, verifies, measures; synchronises
+// text: plan.text_bytes rounded up to 16; segment_name: n_segments entries; edge_twin: n_edges entries
+int dev_gfa_strands_write(const GfaGraph& g, const GfaStrandsPlan& plan, uint8_t* text, uint64_t* segment_name, uint64_t* edge_twin, hipStream_t stream);
+int dev_gfa_strands(const GfaGraph& g, GfaStrandsOutput& out, hipStream_t stream);
 
 // Contigs::stats' panic sites as a status (contig_stats.h's 1, 2, 3: which tipping point is 0), one message wherever the stats are made
 inline int contig_stats_status(int which) {

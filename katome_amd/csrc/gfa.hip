@@ -22,29 +22,22 @@
 //   a text whose other parts are written elsewhere (dist_gfa.hip): names start at first_segment, links come as a table of 64-bit
 //   global numbers, the header is written or not, and the S part and the L part are two regions of one buffer, each a launch of its
 //   own.  It is a separate instantiation: gfa_write_kernel<false> is the one-GPU kernel as it was.
+//   Every segment is one strand here and every orientation +; gfa_strands.hip folds strand twins into one segment with +/- links, on
+//   top of this file's join (dev_gfa_plan) and the tile image both writers share (gfa_image.h).
 #include "builder.h"
+#include "gfa_image.h"
 #include "text_bases.h"
 
 namespace katome {
 namespace {
 
-constexpr int STORES = 2;                              // 16-byte stores per lane and tile
-constexpr u32 TILE = BLOCK * 16 * STORES;              // output bytes a workgroup owns at a time
-constexpr u32 HEADER_BYTES = 11;                       // "H\tVN:Z:1.0\n": the shortest line (an L line has 13 bytes or more, an S line more still)
-constexpr u32 MAX_LINES = TILE / HEADER_BYTES + 2;     // lines that can overlap one tile
-constexpr int S_NAME_MAX = 2 + 10 + 1;                 // "S\t<i>\t", i < 2^32
 constexpr int S_NAME_MAX_NUMBERED = 2 + 20 + 1;        // ... of a numbered part: first_segment + i < 2^64
 constexpr u32 L_LINE_MAX_NUMBERED = 10 + 20 + 20 + 10; // "L\t<a>\t+\t<b>\t+\t<k-1>M\n" with two 64-bit numbers: far below a tile
 constexpr int S_TAGS_MAX = 3 * 6 + 10 + 20 + 10 + 1;   // "\tLN:i:<u32>\tKC:i:<u64>\tew:i:<u32>\n"
-static_assert(TILE <= 65536, "offsets inside a tile are kept in 16 bits");
 // (no line of either form is shorter than the header's 11 bytes -- the shortest L line, "L\t0\t+\t0\t+\t0M\n", has 13 --, so MAX_LINES and
 // the 16-bit offsets hold for a numbered part too: longer numbers only make lines longer)
 static_assert(L_LINE_MAX_NUMBERED < TILE && HEADER_BYTES <= 13, "a tile holds at most MAX_LINES lines");
 enum { ERR_NODE = 1, ERR_LABEL = 2, ERR_LABEL_LEN = 4, ERR_KMERS = 8, ERR_LINKS = 16 };
-
-constexpr u64 tag(char a, char b, char c, char d, char e, char f) {      // six characters, the first in the low byte
-    return (u64)(uint8_t)a | (u64)(uint8_t)b << 8 | (u64)(uint8_t)c << 16 | (u64)(uint8_t)d << 24 | (u64)(uint8_t)e << 32 | (u64)(uint8_t)f << 40;
-}
 
 // Segment i's line: checks everything the later kernels read through (the two vertices, the label's offsets, pad byte and length, and
 // that the label spells edge_kmers + k - 1 bases), counts the line's bytes, and sets up the sort of the edge indices by source
@@ -99,24 +92,6 @@ __global__ __launch_bounds__(BLOCK) void gfa_segment_off_kernel(u64 E, const u64
     for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < E; i += (u64)gridDim.x * BLOCK) segment_off[i] = line_off[1 + i] + 3 + decimal_digits(i);
 }
 
-// ---- the LDS image of a tile: bytes at positions relative to the tile, those outside [0, len) dropped ------------------------------
-__device__ __forceinline__ void put(uint8_t* img, int pos, int len, u32 c) { if (pos >= 0 && pos < len) img[pos] = (uint8_t)c; }
-// v in decimal, its last digit at `pos`; returns the position in front of its first digit
-template <class T> __device__ __forceinline__ int put_decimal_back(uint8_t* img, int pos, int len, T v) {
-    do { put(img, pos--, len, '0' + (u32)(v % 10)); v /= 10; } while (v);
-    return pos;
-}
-// n characters of t (the first in the low byte), the last one at `pos`
-template <int n> __device__ __forceinline__ int put_tag_back(uint8_t* img, int pos, int len, u64 t) {
-#pragma unroll
-    for (int j = n - 1; j >= 0; --j) put(img, pos--, len, (u32)(t >> (8 * j)) & 0xFF);
-    return pos;
-}
-
-struct Line {
-    const uint8_t* src;       // a segment's packed bases
-    u32 head, bases, total;   // bytes in front of the bases; the bases; all the line's bytes.  Not a segment: head = total, no bases
-};
 // (NUMBERED: a part of a sharded text, see PartNumbers below; its segments are lines hdr .. hdr + E - 1)
 template <bool NUMBERED>
 __device__ __forceinline__ Line load_line(u32 r, u32 E, u32 hdr, const uint8_t* __restrict__ label, const u64* __restrict__ label_off,
@@ -279,8 +254,6 @@ int check_gfa_errors(u32 err) {
     if (err & ERR_KMERS) { set_error("gfa: a label's bases are not edge_kmers + k - 1"); return KATOME_E_ARG; }
     return KATOME_OK;
 }
-
-u32 host_digits(u64 v) { u32 d = 1; while (v >= 10) { v /= 10; ++d; } return d; }
 
 }  // namespace
 

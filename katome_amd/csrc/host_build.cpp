@@ -70,6 +70,17 @@ void katome_gfa_free(katome_gfa* g) {
     delete o;
 }
 
+struct GfaStrandsOwner {       // katome_gfa_strands followed by what it owns
+    katome_gfa_strands g;
+    std::vector<void*> mem;
+};
+void katome_gfa_strands_free(katome_gfa_strands* g) {
+    if (!g) return;
+    GfaStrandsOwner* o = reinterpret_cast<GfaStrandsOwner*>(g);
+    for (void* p : o->mem) free(p);
+    delete o;
+}
+
 }  // extern "C"
 
 // KATOME_TRACE_BUILD=1: wall time of the host entries' stages on stderr
@@ -390,21 +401,49 @@ static int unitigs_to_host(katome_builder* b, uint64_t read_bytes, const Unitigs
 }
 
 // the GFA's text is the file
-extern "C" int katome_gfa_save(const katome_gfa* g, const char* path) {
-    if (!g || !path) { set_error("null argument"); return KATOME_E_ARG; }
+static int save_gfa_text(const uint8_t* text, uint64_t text_bytes, const char* path) {
     FILE* f = fopen(path, "wb");
     if (!f) {
         set_error("couldn't create %s: %s", path, CREATE_ERROR_KINDS[create_error_kind(errno)]);      // (katome_assembly_save's message)
         return KATOME_E_OPEN;
     }
-    const size_t n = g->text_bytes ? fwrite(g->text, 1, g->text_bytes, f) : 0;
-    if (fclose(f) != 0 || n != g->text_bytes) { set_error("couldn't write %s", path); return KATOME_E_OPEN; }
+    const size_t n = text_bytes ? fwrite(text, 1, text_bytes, f) : 0;
+    if (fclose(f) != 0 || n != text_bytes) { set_error("couldn't write %s", path); return KATOME_E_OPEN; }
     return KATOME_OK;
+}
+extern "C" int katome_gfa_save(const katome_gfa* g, const char* path) {
+    if (!g || !path) { set_error("null argument"); return KATOME_E_ARG; }
+    return save_gfa_text(g->text, g->text_bytes, path);
+}
+extern "C" int katome_gfa_strands_save(const katome_gfa_strands* g, const char* path) {
+    if (!g || !path) { set_error("null argument"); return KATOME_E_ARG; }
+    return save_gfa_text(g->text, g->text_bytes, path);
 }
 
 // katome_gfa_*: the flag's remove_dead_paths, the stage letters, shrink (AUTO: exact on a first-seen build, fast otherwise), the GFA of
 // the result copied to host arrays and, with a path, the file
-struct GfaWant { katome_gfa** out; const char* path; };
+// (strands: the merged form, katome_gfa_strands_* -- the same pipeline up to the shrink)
+struct GfaWant { katome_gfa** out; const char* path; katome_gfa_strands** strands = nullptr; bool merge = false; };
+static int gfa_strands_to_host(katome_builder* b, const katome_dev_contigs& dc, uint64_t read_bytes, const GfaWant& want) {
+    katome_dev_gfa_strands d;
+    KCHECK(katome_dev_contigs_gfa_strands(b, &dc, &d, nullptr));
+    GfaStrandsOwner* o = new (std::nothrow) GfaStrandsOwner();
+    if (!o) { set_error("out of host memory"); return KATOME_E_OOM; }
+    memset(&o->g, 0, sizeof o->g);
+    katome_gfa_strands* g = &o->g;
+    g->n_segments = d.n_segments; g->n_links = d.n_links; g->text_bytes = d.text_bytes; g->read_bytes = read_bytes; g->k = b->s.k;
+    g->n_edges = dc.n_edges; g->n_unpaired = d.n_unpaired; g->n_self_twins = d.n_self_twins;
+    int rc = d2h(o, &g->text, d.d_text, d.text_bytes);
+    if (!rc) rc = d2h(o, &g->segment_off, d.d_segment_off, d.n_segments);
+    if (!rc) rc = d2h(o, &g->link_first, d.d_link_first, d.n_segments + 1);
+    if (!rc) rc = d2h(o, &g->segment_name, d.d_segment_name, d.n_segments);
+    if (!rc) rc = d2h(o, &g->edge_twin, d.d_edge_twin, dc.n_edges);
+    if (rc) { katome_gfa_strands_free(g); return rc; }
+    if (want.strands) *want.strands = g;
+    rc = want.path ? katome_gfa_strands_save(g, want.path) : KATOME_OK;
+    if (!want.strands) katome_gfa_strands_free(g);
+    return rc;
+}
 static int gfa_to_host(katome_builder* b, uint64_t read_bytes, const GfaWant& want, const char* stages, uint64_t genome_len) {
     katome_dev_graph dg;
     if (stages && *stages && !b->first_seen) { set_error("stages after the build need KATOME_FLAG_FIRST_SEEN_ORDER"); return KATOME_E_ARG; }
@@ -413,6 +452,7 @@ static int gfa_to_host(katome_builder* b, uint64_t read_bytes, const GfaWant& wa
     KCHECK(run_stages(stages, BuilderStages{b, genome_len}));
     katome_dev_contigs dc;
     KCHECK(katome_dev_shrink(b, &dc, nullptr));
+    if (want.merge) return gfa_strands_to_host(b, dc, read_bytes, want);
     katome_dev_gfa dgfa;
     KCHECK(katome_dev_contigs_gfa(b, &dc, &dgfa, nullptr));
     GfaOwner* o = new (std::nothrow) GfaOwner();
@@ -968,6 +1008,20 @@ static int gfa_finish(const katome_settings* s, const char* stages, uint64_t gen
     f.gfa = GfaWant{out, out_path}; f.want_gfa = true; f.stages = stages; f.genome_len = genome_len;
     return KATOME_OK;
 }
+static int gfa_strands_finish(const katome_settings* s, const char* stages, uint64_t genome_len, const char* out_path, katome_gfa_strands** out, Finish& f) {
+    if (!out && !out_path) { set_error("null argument"); return KATOME_E_ARG; }
+    if (out) *out = nullptr;
+    katome_gfa* none = nullptr;
+    KCHECK(gfa_finish(s, stages, genome_len, out_path, &none, f));      // (the same refusals, the same route)
+    f.gfa = GfaWant{nullptr, out_path, out, true};
+    return KATOME_OK;
+}
+int katome_gfa_strands_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip, const char* stages,
+                              uint64_t original_genome_length, const char* out_path, katome_gfa_strands** out) {
+    Finish f{nullptr, nullptr};
+    KCHECK(gfa_strands_finish(s, stages, original_genome_length, out_path, out, f));
+    return build_packed_impl(s, packed, n_reads, read_len, skip, f);
+}
 int katome_gfa_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip, const char* stages,
                       uint64_t original_genome_length, const char* out_path, katome_gfa** out) {
     Finish f{nullptr, nullptr};
@@ -1143,6 +1197,12 @@ int katome_unitigs_gfa_files(const katome_settings* s, const char* const* paths,
                              const char* out_path, katome_unitigs_gfa* out) {
     Finish f{nullptr, nullptr};
     KCHECK(unitigs_gfa_finish(s, stages, original_genome_length, out_path, out, f));
+    return build_files_impl(s, paths, n_paths, f);
+}
+int katome_gfa_strands_files(const katome_settings* s, const char* const* paths, size_t n_paths, const char* stages, uint64_t original_genome_length,
+                             const char* out_path, katome_gfa_strands** out) {
+    Finish f{nullptr, nullptr};
+    KCHECK(gfa_strands_finish(s, stages, original_genome_length, out_path, out, f));
     return build_files_impl(s, paths, n_paths, f);
 }
 int katome_gfa_files(const katome_settings* s, const char* const* paths, size_t n_paths, const char* stages, uint64_t original_genome_length,

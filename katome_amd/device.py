@@ -132,9 +132,17 @@ class DeviceContigs:
         _check(_lib.lib().katome_dev_contigs_text(self._builder._h, C.byref(self._dc), LAYOUTS[layout], C.byref(da), _stream()))
         return DeviceAssembly(da, self._builder, self._builder.tdev)
 
-    def gfa(self):
+    def gfa(self, merge_strands=False):
         """the shrunk graph as GFA 1, written on the device (katome_dev_contigs_gfa; include/katome_gpu.h has the format) ->
-        DeviceGfa; valid for the builder's last shrink() only, and until the next gfa()"""
+        DeviceGfa; valid for the builder's last shrink() only, and until the next gfa().  merge_strands: strand twins as one
+        segment with +/- links (katome_dev_contigs_gfa_strands) -> DeviceGfaStrands, valid until the next gfa(merge_strands=True)"""
+        if merge_strands:
+            d, b = _lib.DevGfaStrands(), self._builder
+            _check(_lib.lib().katome_dev_contigs_gfa_strands(b._h, C.byref(self._dc), C.byref(d), _stream()))
+            v = lambda p, n: _view(p, (n,), "<i8", b, b.tdev)
+            return DeviceGfaStrands(d.n_segments, d.n_links, d.text_bytes, _view(d.d_text, (d.text_bytes,), "|u1", b, b.tdev), v(d.d_segment_off, d.n_segments),
+                                    v(d.d_link_first, d.n_segments + 1), v(d.d_segment_name, d.n_segments), v(d.d_edge_twin, self.n_edges), d.n_unpaired,
+                                    d.n_self_twins)
         dg = _lib.DevGfa()
         _check(_lib.lib().katome_dev_contigs_gfa(self._builder._h, C.byref(self._dc), C.byref(dg), _stream()))
         return DeviceGfa(dg.n_segments, dg.n_links, dg.text_bytes, _view(dg.d_text, (dg.text_bytes,), "|u1", self._builder, self._builder.tdev),
@@ -153,6 +161,16 @@ class DeviceGfa:
     def bytes(self):
         """host: the file's bytes"""
         return bytes(self.text.cpu().numpy())
+
+
+class DeviceGfaStrands(DeviceGfa):
+    """a GFA 1 text with strand twins merged: S line s is merged edge segment_name[s] (segment_off[s]: its first base), the L lines
+    whose first segment it is are lines link_first[s] .. link_first[s + 1] of the L region; edge_twin[i] = the merged edge that is
+    edge i's reverse complement, -1 for none"""
+
+    def __init__(self, n_segments, n_links, text_bytes, text, segment_off, link_first, segment_name, edge_twin, n_unpaired, n_self_twins):
+        super().__init__(n_segments, n_links, text_bytes, text, segment_off, link_first)
+        self.segment_name, self.edge_twin, self.n_unpaired, self.n_self_twins = segment_name, edge_twin, n_unpaired, n_self_twins
 
 
 LAYOUTS = {"plain": 0, "fasta": 1}
@@ -705,6 +723,27 @@ def gfa_arrays(k, n_nodes, edge_src, edge_dst, edge_weight, edge_kmers, edge_lab
     text = torch.empty(max(cap, 16), dtype=torch.uint8, device=tdev)
     _check(L.katome_dev_gfa_arrays(*args, _ptr(seg), _ptr(first), _ptr(text), cap, C.byref(nl), C.byref(nb), _stream()))
     return DeviceGfa(n_edges, nl.value, nb.value, text[:nb.value], seg[:n_edges], first)
+
+
+def gfa_strands_arrays(k, n_nodes, edge_src, edge_dst, edge_weight, edge_kmers, edge_label_off, edge_label, device=0, label_bytes=None):
+    """gfa_arrays with strand twins merged (katome_dev_gfa_strands_arrays) -> DeviceGfaStrands"""
+    tdev = edge_label_off.device
+    n_edges = edge_label_off.numel() - 1
+    if label_bytes is None:
+        label_bytes = edge_label.numel()
+    counts = (C.c_uint64 * 5)()
+    L = _lib.lib()
+    args = (device, k, n_nodes, n_edges, _ptr(edge_src), _ptr(edge_dst), _ptr(edge_weight), _ptr(edge_kmers), _ptr(edge_label_off),
+            _ptr(edge_label), label_bytes)
+    _check(L.katome_dev_gfa_strands_arrays(*args, None, None, None, None, None, 0, counts, _stream()))
+    ns, cap = counts[0], (counts[2] + 15) // 16 * 16
+    name = torch.empty(max(ns, 1), dtype=torch.int64, device=tdev)
+    seg = torch.empty(max(ns, 1), dtype=torch.int64, device=tdev)
+    first = torch.empty(ns + 1, dtype=torch.int64, device=tdev)
+    twin = torch.empty(max(n_edges, 1), dtype=torch.int64, device=tdev)
+    text = torch.empty(max(cap, 16), dtype=torch.uint8, device=tdev)
+    _check(L.katome_dev_gfa_strands_arrays(*args, _ptr(name), _ptr(seg), _ptr(first), _ptr(twin), _ptr(text), cap, counts, _stream()))
+    return DeviceGfaStrands(counts[0], counts[1], counts[2], text[:counts[2]], seg[:ns], first, name[:ns], twin[:n_edges], counts[3], counts[4])
 
 
 def gfa_part_arrays(k, edge_weight, edge_kmers, edge_label_off, edge_label, first_segment, with_header, link_first, link_b, device=0,
