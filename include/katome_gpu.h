@@ -42,6 +42,11 @@ extern "C" {
  * ranks on one GPU).  Exercises the whole multi-GPU route -- sharding, routing, exchanges, global numbering -- on a
  * one-GPU box; no performance meaning.                                                                       */
 #define KATOME_FLAG_RANKS_SHARE_DEVICE 4u
+/* katome_unitigs_gfa_files / katome_unitigs_gfa_packed only (every other entry ignores it, as unknown flag bits are ignored): the
+ * shrink is katome_dev_shrink_coverage(FAST) and the text katome_dev_contigs_gfa_coverage's -- KC is the SUM of the unitig's
+ * k-mer counts and every S line ends in mn / mx.  With settings.n_devices > 1: katome_dist_shrink_coverage and
+ * katome_dist_contigs_gfa_coverage.                                                                              */
+#define KATOME_FLAG_PATH_COVERAGE 8u
 
 /* status codes: the reference's panics, one code each */
 enum {
@@ -436,6 +441,24 @@ typedef struct {
 } katome_dev_contigs;
 int katome_dev_shrink(katome_builder *b, katome_dev_contigs *out, void *stream);
 int katome_dev_shrink_mode(katome_builder *b, uint32_t mode, katome_dev_contigs *out, double *host_ms, void *stream);
+/* Unitig coverage.  The shrunk edge carries the weight of its path's FIRST k-mer only; katome_dev_shrink_coverage is
+ * katome_dev_shrink_mode(b, mode, out, host_ms, stream), array for array and in every mode, and ALSO leaves, per merged edge, what
+ * the k-mer counts (edge_weight) of the input edges on its path come to: their sum in 64 bits (the graph's u32 weights may have
+ * wrapped; the sum of what the graph holds does not), the smallest and the largest.  They are accumulated by the walk that
+ * writes the result anyway (fast form: the label writer; exact form: the chain measure), nothing is walked twice.  A cycle of
+ * inner vertices counts each of its edges once; the exact form counts the chain behind each slot, whatever the traversal's
+ * cuts made of it.  No edges: zero-length arrays, KATOME_OK.  Null out or cov: KATOME_E_ARG; before katome_dev_finalize: the
+ * refusal of katome_dev_shrink_mode.
+ * The arrays are owned by the builder until its next shrink OF ANY KIND or destroy: a later katome_dev_shrink or
+ * katome_dev_shrink_mode drops them, so a coverage can never outlive the shrink result it belongs to.  (A stage that changes
+ * the graph after a shrink leaves both the result and its coverage describing the graph as it was.)                          */
+typedef struct {
+    uint64_t  n_edges;                 /* = the shrink result's n_edges                                        */
+    uint64_t *d_kmer_sum;              /* [n_edges] sum of the input edges' weights on the path                */
+    uint32_t *d_kmer_min, *d_kmer_max; /* [n_edges] their smallest / largest                                   */
+} katome_dev_coverage;
+int katome_dev_shrink_coverage(katome_builder *b, uint32_t mode, katome_dev_contigs *out, katome_dev_coverage *cov,
+                               double *host_ms, void *stream);
 
 /* ---- collapse: the contigs, their text, FASTA and stats (collapser.rs:25-273, asm/mod.rs:57-72, stats/contigs.rs:31-89) --------
  * Collapsable::collapse is `self.shrink()` followed by a walk that consumes edge weights one at a time and swap-removes edges
@@ -494,7 +517,7 @@ int katome_dev_contigs_text(katome_builder *b, const katome_dev_contigs *contigs
  * Segment i is merged edge i, named by its decimal index: the record >katome_<i> of katome_dev_contigs_text on the same result;
  * <bases> = edge_kmers[i] + k - 1.  KC is the 64-bit product (up to 20 digits) of what the shrunk edge carries: shrink keeps only
  * the weight of a path's FIRST k-mer (shrinker.rs:181,200), so KC is that weight times the k-mers merged into the edge, not the
- * sum of the path's k-mer counts; ew is that weight itself.  Links are ordered by a, then b; a self-loop links to itself, parallel
+ * sum of the path's k-mer counts (katome_dev_contigs_gfa_coverage below writes that sum); ew is that weight itself.  Links are ordered by a, then b; a self-loop links to itself, parallel
  * merged edges are distinct segments, every orientation is + (the two strands of a reverse_complement build are separate edges
  * and therefore separate segments; katome_dev_contigs_gfa_strands below merges strand twins).  No edges: the header line alone.
  * d_text holds text_bytes bytes in a buffer that is a multiple of 16 bytes (zeros behind the text up to the next multiple);
@@ -515,6 +538,17 @@ typedef struct {
  * form.  The builder's graph and the shrink result are left untouched; the result is owned by the builder until its next
  * katome_dev_contigs_gfa or destroy.                                                                                      */
 int katome_dev_contigs_gfa(katome_builder *b, const katome_dev_contigs *contigs, katome_dev_gfa *out, void *stream);
+/* The same text with the unitig's coverage: only the S lines differ,
+ *   S\t<i>\t<bases>\tLN:i:<bases>\tKC:i:<kmer_sum_i>\tew:i:<weight_i>\tmn:i:<kmer_min_i>\tmx:i:<kmer_max_i>\n
+ * KC is the sum of the path's k-mer counts, so KC / kmers is the unitig's mean k-mer depth; ew stays the shrunk edge's weight
+ * (what collapse would consume); mn / mx are the smallest and largest count on the path (lower-case: user-space tags).  Header,
+ * names, L lines, ordering, d_segment_off, d_link_first, zero fill and limits are katome_dev_contigs_gfa's.
+ * `contigs` must be the builder's last shrink result AND that shrink a katome_dev_shrink_coverage: KATOME_E_ARG otherwise, the
+ * message says which.  The result shares katome_dev_contigs_gfa's buffers: each call invalidates the other's result
+ * (katome_dev_contigs_gfa_strands keeps its own).  The bidirected writer has no coverage form: a merged segment would need a
+ * rule for combining its two strands' counts, which is left open; katome_gfa_* and katome_gfa_strands_* (the gather routes)
+ * are unchanged too.  The sharded form is katome_dist_contigs_gfa_coverage.                                                */
+int katome_dev_contigs_gfa_coverage(katome_builder *b, const katome_dev_contigs *contigs, katome_dev_gfa *out, void *stream);
 
 /* ---- the unitig graph as BIDIRECTED GFA 1 (csrc/gfa_strands.hip): strand twins merged into one segment, +/- links ----------
  * The same shrink result with a merged edge and its reverse complement written as ONE double-stranded segment, as GFA readers
@@ -810,6 +844,15 @@ typedef struct {
  * O(share).  KATOME_DIST_SHRINK_FAIL=<rank> (tests): that rank fails after the first ranking round, and every rank returns
  * the error.  `out` and `stats` may be NULL.  Collective.                                                              */
 int  katome_dist_shrink(katome_dist_builder *d, katome_dist_contigs *out, katome_dist_shrink_stats *stats, void *stream);
+/* katome_dist_shrink plus this rank's coverage (katome_dev_coverage, as katome_dev_shrink_coverage leaves it): entry j belongs to
+ * this rank's merged edge j, like every array of katome_dist_contigs; matched by d_edge_head_id the ranks' values are the one-GPU
+ * FAST coverage of the same graph.  Every non-head edge sends its weight to the rank of its head next to its base (one more
+ * exchange over the same routing, counted in stats->bytes_sent); there the weights are staged where the bases are (4 bytes per
+ * non-head edge, transient) and reduced per merged edge together with the head's own weight.  Collective, with the
+ * preconditions, limits and KATOME_DIST_SHRINK_FAIL behaviour of katome_dist_shrink; cov NULL: KATOME_E_ARG.  A failing call
+ * leaves no coverage behind, and a later katome_dist_shrink drops it.                                                     */
+int  katome_dist_shrink_coverage(katome_dist_builder *d, katome_dist_contigs *out, katome_dev_coverage *cov,
+                                 katome_dist_shrink_stats *stats, void *stream);
 /* ---- the end of the sharded pipeline, no gather (katome_amd/csrc/dist_text.hip): text, Contigs::stats and the FASTA file of the
  * merged edges (unitigs) of the builder's last katome_dist_shrink.  All three are collective; a builder without such a result, or
  * whose shares were gathered, gets KATOME_E_ARG on every rank.  A failure of a rank's own allocations, launches or checks comes
@@ -903,6 +946,10 @@ typedef struct {
     uint64_t *d_link_b;                                            /* [n_links] global number of every link's second segment        */
 } katome_dist_gfa;
 int  katome_dist_contigs_gfa(katome_dist_builder *d, katome_dist_gfa *out, void *stream);
+/* katome_dist_contigs_gfa with the S lines of katome_dev_contigs_gfa_coverage (KC the sum, mn / mx behind ew).  The builder's last
+ * shrink must have been a katome_dist_shrink_coverage: KATOME_E_ARG otherwise, on every rank.  It shares katome_dist_contigs_gfa's
+ * buffers and staleness rule; katome_dist_gfa_save writes its result unchanged.  Collective. */
+int  katome_dist_contigs_gfa_coverage(katome_dist_builder *d, katome_dist_gfa *out, void *stream);
 /* the file of `g` (what this builder's last katome_dist_contigs_gfa returned), written by all ranks as katome_dist_contigs_save
  * writes the FASTA file: rank 0 creates `path` at total_text_bytes -- failure: KATOME_E_OPEN, "couldn't create <path>: <why>", on
  * every rank --, every rank writes its two parts at s_base and l_base in chunks of KATOME_DIST_TEXT_CHUNK bytes, write errors are
@@ -912,7 +959,8 @@ int  katome_dist_gfa_save(katome_dist_builder *d, const katome_dist_gfa *g, cons
  * KATOME_FLAG_REMOVE_DEAD_PATHS without KATOME_FLAG_FIRST_SEEN_ORDER: KATOME_E_ARG; a packed-key build without them is fine; the
  * create error as there).  With settings.n_devices > 1 everything runs on the shares and ends in katome_dist_contigs_gfa and
  * katome_dist_gfa_save; on one GPU it is katome_dev_shrink_mode(FAST) and katome_dev_contigs_gfa, and the file is that entry's
- * text.  The result is a plain struct; the text goes to the file only. */
+ * text.  The result is a plain struct; the text goes to the file only.  With KATOME_FLAG_PATH_COVERAGE in settings.flags the
+ * shrink is the _coverage one and the text the coverage form's (KC the sum, mn / mx), on one GPU and on the shares alike. */
 typedef struct {
     uint64_t n_segments, n_links, text_bytes, total_bases, longest, read_bytes;
     uint32_t k, n_devices;
@@ -1056,6 +1104,17 @@ int katome_dev_gfa_arrays(int device, uint32_t k, uint64_t n_nodes, uint64_t n_e
                           const uint64_t *d_edge_label_off, const uint8_t *d_edge_label, uint64_t label_bytes,
                           uint64_t *d_segment_off, uint64_t *d_link_first, uint8_t *d_text, uint64_t text_cap,
                           uint64_t *n_links, uint64_t *text_bytes, void *stream);
+/* katome_dev_contigs_gfa_coverage on the caller's arrays: katome_dev_gfa_arrays with the three coverage arrays (n_edges entries
+ * each) behind d_edge_kmers; the size query works the same.  On top of katome_dev_gfa_arrays' validation, per segment and on
+ * the device: min <= weight <= max and min * kmers <= sum <= max * kmers (64-bit) -- a violation: KATOME_E_ARG, "gfa: a segment's
+ * coverage does not fit its weight and k-mer count", and no line size is computed from the bad values.  A null coverage array
+ * with n_edges > 0: KATOME_E_ARG. */
+int katome_dev_gfa_coverage_arrays(int device, uint32_t k, uint64_t n_nodes, uint64_t n_edges, const uint64_t *d_edge_src,
+                                   const uint64_t *d_edge_dst, const uint32_t *d_edge_weight, const uint32_t *d_edge_kmers,
+                                   const uint64_t *d_kmer_sum, const uint32_t *d_kmer_min, const uint32_t *d_kmer_max,
+                                   const uint64_t *d_edge_label_off, const uint8_t *d_edge_label, uint64_t label_bytes,
+                                   uint64_t *d_segment_off, uint64_t *d_link_first, uint8_t *d_text, uint64_t text_cap,
+                                   uint64_t *n_links, uint64_t *text_bytes, void *stream);
 /* katome_dev_contigs_gfa_strands on the caller's arrays, in the form of katome_dev_gfa_arrays.  counts[5] = {n_segments, n_links,
  * text_bytes, n_unpaired, n_self_twins} are always set.  d_text NULL: nothing else is written (a size query).  Otherwise
  * d_segment_name and d_segment_off need room for n_segments entries, d_link_first for n_segments + 1, d_edge_twin for n_edges

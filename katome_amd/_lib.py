@@ -58,6 +58,10 @@ class DevContigs(C.Structure):
                 ("d_node_key", C.c_void_p)]
 
 
+class DevCoverage(C.Structure):
+    _fields_ = [("n_edges", C.c_uint64), ("d_kmer_sum", C.c_void_p), ("d_kmer_min", C.c_void_p), ("d_kmer_max", C.c_void_p)]
+
+
 class DevAssembly(C.Structure):
     _fields_ = [("n_contigs", C.c_uint64), ("text_bytes", C.c_uint64), ("layout", C.c_uint32), ("_pad", C.c_uint32),
                 ("d_contig_off", C.c_void_p), ("d_contig_len", C.c_void_p), ("d_text", C.c_void_p)]
@@ -226,12 +230,15 @@ SYMBOLS = {
     "katome_dev_standardize_edges": (_i, [_vp, _u64, _u32, _vp]),
     "katome_dev_shrink": (_i, [_vp, C.POINTER(DevContigs), _vp]),
     "katome_dev_shrink_mode": (_i, [_vp, C.c_uint32, C.POINTER(DevContigs), C.POINTER(C.c_double), _vp]),
+    "katome_dev_shrink_coverage": (_i, [_vp, C.c_uint32, C.POINTER(DevContigs), C.POINTER(DevCoverage), C.POINTER(C.c_double), _vp]),
     "katome_dev_collapse": (_i, [_vp, _u32, C.POINTER(DevAssembly), C.POINTER(CollapseStats), _vp]),
     "katome_dev_contigs_text": (_i, [_vp, C.POINTER(DevContigs), _u32, C.POINTER(DevAssembly), _vp]),
     "katome_dev_pieces_text": (_i, [_i, _u32, _vp, _vp, _u64, _vp, _u64, _u32, _vp, _vp, _u64, _vp, _u64, u64p, u64p, _vp]),
     "katome_dev_pieces_text_numbered": (_i, [_i, _u32, _vp, _vp, _u64, _vp, _u64, _u32, _u64, _vp, _vp, _u64, _vp, _u64, u64p, u64p, _vp]),
     "katome_dev_contigs_gfa": (_i, [_vp, C.POINTER(DevContigs), C.POINTER(DevGfa), _vp]),
     "katome_dev_gfa_arrays": (_i, [_i, _u32, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, u64p, u64p, _vp]),
+    "katome_dev_contigs_gfa_coverage": (_i, [_vp, C.POINTER(DevContigs), C.POINTER(DevGfa), _vp]),
+    "katome_dev_gfa_coverage_arrays": (_i, [_i, _u32, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, u64p, u64p, _vp]),
     "katome_dev_gfa_part_arrays": (_i, [_i, _u32, _u64, _vp, _vp, _vp, _vp, _u64, _u64, _i, _vp, _vp, _vp, _vp, _u64, u64p, u64p, u64p, _vp]),
     "katome_gfa_files": (_i, [C.POINTER(Settings), _pp, _sz, C.c_char_p, _u64, C.c_char_p, C.POINTER(C.POINTER(Gfa))]),
     "katome_gfa_packed": (_i, [C.POINTER(Settings), _vp, _u64, _u32, _vp, C.c_char_p, _u64, C.c_char_p, C.POINTER(C.POINTER(Gfa))]),
@@ -303,11 +310,13 @@ SYMBOLS = {
     "katome_dist_prune_weak_edges": (_i, [_vp, C.c_uint32, C.POINTER(DistGraph), _vp]),
     "katome_dist_standardize_edges": (_i, [_vp, C.c_uint64, C.c_uint32, C.POINTER(DistGraph), _vp]),
     "katome_dist_shrink": (_i, [_vp, C.POINTER(DistContigs), C.POINTER(DistShrinkStats), _vp]),
+    "katome_dist_shrink_coverage": (_i, [_vp, C.POINTER(DistContigs), C.POINTER(DevCoverage), C.POINTER(DistShrinkStats), _vp]),
     "katome_dist_contigs_text": (_i, [_vp, _u32, C.POINTER(DistAssembly), _vp]),
     "katome_dist_contig_stats_arrays": (_i, [_vp, _i, _vp, _u64, _u32, _u64, C.POINTER(ContigStats), _vp]),
     "katome_dist_contig_stats": (_i, [_vp, _u64, C.POINTER(ContigStats), _vp]),
     "katome_dist_contigs_save": (_i, [_vp, C.POINTER(DistAssembly), C.c_char_p]),
     "katome_dist_contigs_gfa": (_i, [_vp, C.POINTER(DistGfa), _vp]),
+    "katome_dist_contigs_gfa_coverage": (_i, [_vp, C.POINTER(DistGfa), _vp]),
     "katome_dist_gfa_save": (_i, [_vp, C.POINTER(DistGfa), C.c_char_p]),
     "katome_dist_graph_stats": (_i, [_vp, C.POINTER(Stats), _vp]),
     "katome_dist_weight_spectrum": (_i, [_vp, u64p, _u32, _vp]),

@@ -229,19 +229,21 @@ def _gfa_result(rc, gp, cls=Gfa):
 FLAG_FIRST_SEEN_ORDER = 1
 FLAG_REMOVE_DEAD_PATHS = 2
 FLAG_RANKS_SHARE_DEVICE = 4
+FLAG_PATH_COVERAGE = 8
 
 
 def make_settings(k, file_type=InputFileType.Fastq, reverse_complement=False, min_weight=0, device=0,
                   table_slots_hint=0, first_seen_order=False, remove_dead_paths=False, n_devices=1,
-                  ranks_share_device=False):
+                  ranks_share_device=False, path_coverage=False):
     """n_devices: GPUs of this node to build on (device .. device+n-1; one rank per GPU inside the call);
-    ranks_share_device: all those ranks on `device` -- the rehearsal of the sharded route on a one-GPU box"""
+    ranks_share_device: all those ranks on `device` -- the rehearsal of the sharded route on a one-GPU box;
+    path_coverage: GpuUnitigs.gfa*'s KC is the sum of the unitig's k-mer counts, with mn / mx tags (KATOME_FLAG_PATH_COVERAGE)"""
     s = _lib.Settings()
     s.k = k
     s.file_type = int(file_type)
     s.reverse_complement = 1 if reverse_complement else 0
     s.flags = ((FLAG_FIRST_SEEN_ORDER if first_seen_order else 0) | (FLAG_REMOVE_DEAD_PATHS if remove_dead_paths else 0) |
-               (FLAG_RANKS_SHARE_DEVICE if ranks_share_device else 0))
+               (FLAG_RANKS_SHARE_DEVICE if ranks_share_device else 0) | (FLAG_PATH_COVERAGE if path_coverage else 0))
     s.min_weight = min_weight
     s.device = device
     s.table_slots_hint = table_slots_hint
@@ -557,12 +559,14 @@ class GpuUnitigs:
 
     @staticmethod
     def gfa(input_files, ft, reverse_complement, minimal_weight_threshold=0, output_file=None, stages=None, original_genome_length=0,
-            device=0, first_seen_order=False, remove_dead_paths=False, n_devices=1, ranks_share_device=False):
+            device=0, first_seen_order=False, remove_dead_paths=False, n_devices=1, ranks_share_device=False, coverage=False):
         """the same pipeline ending in the unitig GRAPH as a GFA 1 file (katome_unitigs_gfa_files): with n_devices > 1 the links are
         joined across the ranks' shares, never a gather, and segment <i> is the record >katome_<i> of create()'s file ->
-        (UnitigsGfa, number_of_read_bytes); uses the global k"""
+        (UnitigsGfa, number_of_read_bytes); uses the global k.  coverage: KC is the sum of each unitig's k-mer counts and the S
+        lines end in mn / mx (KATOME_FLAG_PATH_COVERAGE)"""
         s = make_settings(K_SIZE, ft, reverse_complement, minimal_weight_threshold, device, first_seen_order=first_seen_order,
-                          remove_dead_paths=remove_dead_paths, n_devices=n_devices, ranks_share_device=ranks_share_device)
+                          remove_dead_paths=remove_dead_paths, n_devices=n_devices, ranks_share_device=ranks_share_device,
+                          path_coverage=coverage)
         u = _lib.UnitigsGfa()
         _check(_lib.lib().katome_unitigs_gfa_files(C.byref(s), _paths(input_files), len(input_files), (stages or "").encode(),
                                                    original_genome_length, os.fsencode(output_file) if output_file is not None else None,
@@ -572,11 +576,11 @@ class GpuUnitigs:
     @staticmethod
     def gfa_from_packed(packed, n_reads, read_len, skip=None, reverse_complement=False, minimal_weight_threshold=0, output_file=None,
                         stages=None, original_genome_length=0, device=0, k=None, first_seen_order=False, remove_dead_paths=False,
-                        n_devices=1, ranks_share_device=False):
+                        n_devices=1, ranks_share_device=False, coverage=False):
         """the same from 2-bit packed reads (numpy uint8; katome_unitigs_gfa_packed)"""
         s = make_settings(K_SIZE if k is None else k, InputFileType.Fastq, reverse_complement, minimal_weight_threshold, device,
                           first_seen_order=first_seen_order, remove_dead_paths=remove_dead_paths, n_devices=n_devices,
-                          ranks_share_device=ranks_share_device)
+                          ranks_share_device=ranks_share_device, path_coverage=coverage)
         packed = np.ascontiguousarray(packed, dtype=np.uint8)
         skip_p = None
         if skip is not None:

@@ -806,9 +806,10 @@ int katome_dev_standardize_edges(katome_builder* b, uint64_t original_genome_len
 int katome_dev_shrink(katome_builder* b, katome_dev_contigs* out, void* stream_) {
     return katome_dev_shrink_mode(b, KATOME_SHRINK_AUTO, out, nullptr, stream_);
 }
-int katome_dev_shrink_mode(katome_builder* b, uint32_t mode, katome_dev_contigs* out, double* host_ms, void* stream_) {
-    if (!b || !out) { set_error("null argument"); return KATOME_E_ARG; }
-    hipStream_t stream = (hipStream_t)stream_;
+// every shrink entry: `cov` null drops the builder's coverage (none can outlive the result it belongs to), non-null fills it
+static int builder_shrink(katome_builder* b, uint32_t mode, katome_dev_contigs* out, katome_dev_coverage* cov, bool want_cov, double* host_ms,
+                          hipStream_t stream) {
+    if (!b || !out || (want_cov && !cov)) { set_error("null argument"); return KATOME_E_ARG; }
     KCHECK_HIP(hipSetDevice(b->s.device));
     if (host_ms) *host_ms = 0;
     if (!b->finalized) { set_error("shrink: call katome_dev_finalize first"); return KATOME_E_ARG; }
@@ -817,10 +818,12 @@ int katome_dev_shrink_mode(katome_builder* b, uint32_t mode, katome_dev_contigs*
     const bool exact = mode == KATOME_SHRINK_EXACT || (mode == KATOME_SHRINK_AUTO && b->first_seen);
     ShrinkInput in{b->edge_src.as<u64>(), b->edge_dst.as<u64>(), b->edge_weight.as<u32>(), b->edge_key.as<u64>(), b->node_key.as<u64>(),
                    b->n_edges, b->n_nodes, b->nw, b->s.k};
+    b->shrunk_cov.drop();
+    ShrinkCoverage* sc = want_cov ? &b->shrunk_cov : nullptr;
     {
         PhaseScope ps(b->prof, PH_SHRINK, stream);
-        if (exact) KCHECK(dev_shrink_exact(in, b->edge_age.p ? b->edge_age.as<u32>() : nullptr, b->shrunk, host_ms, stream));
-        else KCHECK(dev_shrink(in, b->shrunk, stream));
+        if (exact) KCHECK(dev_shrink_exact(in, b->edge_age.p ? b->edge_age.as<u32>() : nullptr, b->shrunk, host_ms, stream, nullptr, nullptr, sc));
+        else KCHECK(dev_shrink(in, b->shrunk, stream, sc));
     }
     memset(out, 0, sizeof *out);
     out->n_nodes = b->shrunk.n_nodes; out->n_edges = b->shrunk.n_edges; out->label_bytes = b->shrunk.label_bytes;
@@ -829,7 +832,18 @@ int katome_dev_shrink_mode(katome_builder* b, uint32_t mode, katome_dev_contigs*
     out->d_edge_weight = b->shrunk.edge_weight.as<u32>(); out->d_edge_kmers = b->shrunk.edge_kmers.as<u32>();
     out->d_edge_label_off = b->shrunk.edge_label_off.as<u64>(); out->d_edge_label = b->shrunk.edge_label.as<uint8_t>();
     out->d_node_key = b->shrunk.node_key.as<u64>();
+    if (want_cov) {
+        memset(cov, 0, sizeof *cov);
+        cov->n_edges = b->shrunk_cov.n_edges;
+        cov->d_kmer_sum = b->shrunk_cov.kmer_sum.as<u64>(); cov->d_kmer_min = b->shrunk_cov.kmer_min.as<u32>(); cov->d_kmer_max = b->shrunk_cov.kmer_max.as<u32>();
+    }
     return KATOME_OK;
+}
+int katome_dev_shrink_mode(katome_builder* b, uint32_t mode, katome_dev_contigs* out, double* host_ms, void* stream_) {
+    return builder_shrink(b, mode, out, nullptr, false, host_ms, (hipStream_t)stream_);
+}
+int katome_dev_shrink_coverage(katome_builder* b, uint32_t mode, katome_dev_contigs* out, katome_dev_coverage* cov, double* host_ms, void* stream_) {
+    return builder_shrink(b, mode, out, cov, true, host_ms, (hipStream_t)stream_);
 }
 
 }  // extern "C"

@@ -110,6 +110,7 @@ struct katome_builder {
     // finalized graph
     DevBuf edge_src, edge_dst, edge_label, node_key;
     ShrinkOutput shrunk;               // result of katome_dev_shrink
+    ShrinkCoverage shrunk_cov;         // ... and, after katome_dev_shrink_coverage only, its k-mer count sum / min / max (any other shrink drops them)
     ShrinkOutput collapse_shrunk;      // katome_dev_collapse: the shrunk graph its pieces name ...
     TextOutput assembly;               // ... and its result
     TextOutput unitig_text;            // result of katome_dev_contigs_text

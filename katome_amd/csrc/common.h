@@ -418,12 +418,20 @@ struct ShrinkOutput {
     DevBuf edge_src, edge_dst, edge_weight, edge_kmers, edge_label_off, edge_label, node_key;
     uint64_t n_edges = 0, n_nodes = 0, label_bytes = 0;
 };
-int dev_shrink(const ShrinkInput& g, ShrinkOutput& out, hipStream_t stream);
+// what a shrink with coverage leaves beside its result: per merged edge the sum (64 bits: the graph's u32 weights add up without
+// wrapping), the smallest and the largest of the weights of the input edges on its path.  valid: they belong to the last shrink
+struct ShrinkCoverage {
+    DevBuf kmer_sum, kmer_min, kmer_max;
+    uint64_t n_edges = 0;
+    bool valid = false;
+    void drop() { kmer_sum.release(); kmer_min.release(); kmer_max.release(); n_edges = 0; valid = false; }
+};
+int dev_shrink(const ShrinkInput& g, ShrinkOutput& out, hipStream_t stream, ShrinkCoverage* cov = nullptr);
 // the reference's own result: its cuts and petgraph's numbering (shrink_exact.h on the host for the order, the device for the bytes)
 // (keep / kept: the caller's ShrinkExact is used and left as run() leaves it, with the nodes it kept -- where collapse starts)
 struct ShrinkExact;
 int dev_shrink_exact(const ShrinkInput& g, const uint32_t* edge_age, ShrinkOutput& out, double* host_ms, hipStream_t stream,
-                     ShrinkExact* keep = nullptr, std::vector<uint32_t>* kept = nullptr);
+                     ShrinkExact* keep = nullptr, std::vector<uint32_t>* kept = nullptr, ShrinkCoverage* cov = nullptr);
 
 // collapse.hip: Collapsable::collapse (collapser.rs:25-273): the walk on the host (collapse_exact.h), the text on the device
 struct TextOutput {
@@ -448,10 +456,18 @@ int dev_collapse(const ShrinkInput& g, const uint32_t* edge_age, ShrinkOutput& s
 
 // gfa.hip: a shrink result as GFA 1 (include/katome_gpu.h has the format): the join of every edge into a vertex with every edge out
 // of it, the records' sizes and the text, partitioned by output bytes
+// (optional: per segment the sum, smallest and largest of its path's k-mer counts -- all three or none; with them KC is the sum and
+// every S line ends in mn / mx)
+struct GfaCoverage {
+    const uint64_t* kmer_sum = nullptr; const uint32_t *kmer_min = nullptr, *kmer_max = nullptr;
+    bool any() const { return kmer_sum || kmer_min || kmer_max; }
+    bool all() const { return kmer_sum && kmer_min && kmer_max; }
+};
 struct GfaGraph {
     uint32_t k; uint64_t n_nodes, n_edges;
     const uint64_t *edge_src, *edge_dst; const uint32_t *edge_weight, *edge_kmers;
     const uint64_t* label_off; const uint8_t* label; uint64_t label_bytes;
+    GfaCoverage cov = {};
 };
 // what dev_gfa_plan leaves for the writer: every line's offset (line 0 the header, 1 + i segment i, 1 + n_edges + l link l; one entry
 // more than lines), every segment's first base, every segment's first link (n_edges + 1), every link's two segments
@@ -474,6 +490,7 @@ struct GfaPart {
     const uint32_t *edge_weight, *edge_kmers; const uint64_t* label_off; const uint8_t* label; uint64_t label_bytes;
     uint64_t first_segment; bool with_header;
     const uint64_t *link_first, *link_b;
+    GfaCoverage cov = {};
 };
 struct GfaPartPlan {
     DevBuf s_line_off, l_line_off, segment_off, link_a;      // line offsets of the two parts (one entry more than lines); every link's local a

@@ -56,6 +56,8 @@ struct katome_dist_builder {
     uint64_t sh_edges = 0, sh_nodes = 0, sh_total_edges = 0, sh_total_nodes = 0, sh_label_bytes = 0;
     bool sh_valid = false;                   // a katome_dist_shrink has finished and none has started since
     uint64_t sh_serial = 0;                  // katome_dist_shrink calls so far
+    katome::ShrinkCoverage sh_cov;           // katome_dist_shrink_coverage: the k-mer count sum / min / max of this rank's merged edges;
+                                             // dropped by the next shrink of either kind
     // the text of that result on this rank (dist_text.hip, katome_dist_contigs_text), kept until the next call or destroy
     katome::TextOutput sh_text;
     uint64_t sh_text_serial = 0, sh_text_first = 0, sh_text_base = 0, sh_text_total = 0, sh_text_contigs = 0;

@@ -201,8 +201,8 @@ int dist_gfa_join(katome_dist_builder* d, Collective& C, uint64_t first, DevBuf&
     return C.agree(compact());
 }
 
-int dist_contigs_gfa(katome_dist_builder* d, GfaTrace& trace, hipStream_t stream) {
-    const char* name = "katome_dist_contigs_gfa";
+// (coverage: the S lines of katome_dev_contigs_gfa_coverage, from d->sh_cov)
+int dist_contigs_gfa(katome_dist_builder* d, const char* name, bool coverage, GfaTrace& trace, hipStream_t stream) {
     Collective C(d->comm, name);
     const int world = C.world, me = C.rank;
     const uint64_t H = d->sh_edges;
@@ -216,8 +216,9 @@ int dist_contigs_gfa(katome_dist_builder* d, GfaTrace& trace, hipStream_t stream
     const uint64_t sent_before = d->xstats[X_PRUNE].bytes_out;
     KCHECK(dist_gfa_join(d, C, first, d->sh_gfa_link_first, d->sh_gfa_link_b, &L, stream));
     trace.join_ms = now_ms() - t_join; trace.join_bytes = d->xstats[X_PRUNE].bytes_out - sent_before;
-    const GfaPart part{d->s.k, H, d->sh_weight.as<u32>(), d->sh_kmers.as<u32>(), d->sh_label_off.as<u64>(), d->sh_label.as<uint8_t>(), d->sh_label_bytes,
-                       first, me == 0, d->sh_gfa_link_first.as<u64>(), d->sh_gfa_link_b.as<u64>()};
+    GfaPart part{d->s.k, H, d->sh_weight.as<u32>(), d->sh_kmers.as<u32>(), d->sh_label_off.as<u64>(), d->sh_label.as<uint8_t>(), d->sh_label_bytes,
+                 first, me == 0, d->sh_gfa_link_first.as<u64>(), d->sh_gfa_link_b.as<u64>()};
+    if (coverage) part.cov = GfaCoverage{d->sh_cov.kmer_sum.as<u64>(), d->sh_cov.kmer_min.as<u32>(), d->sh_cov.kmer_max.as<u32>()};
     GfaPartPlan plan;
     auto measure = [&]() -> int {
         KCHECK(dev_gfa_part_plan(part, plan, stream));
@@ -280,11 +281,14 @@ int dist_gfa_total_kmers(katome_dist_builder* d, uint64_t* total, hipStream_t st
 
 extern "C" {
 
-int katome_dist_contigs_gfa(katome_dist_builder* d, katome_dist_gfa* out, void* stream_) {
-    const char* name = "katome_dist_contigs_gfa";
+static int dist_contigs_gfa_entry(katome_dist_builder* d, const char* name, bool coverage, katome_dist_gfa* out, void* stream_) {
     if (out) memset(out, 0, sizeof *out);
     KCHECK(check_gfa_builder(d, name));
     if (!out) { set_error("null argument"); return KATOME_E_ARG; }
+    if (coverage && (!d->sh_cov.valid || d->sh_cov.n_edges != d->sh_edges)) {       // (every rank's last shrink was the same call: the same answer everywhere)
+        set_error("%s: this builder's last shrink was not a katome_dist_shrink_coverage", name);
+        return KATOME_E_ARG;
+    }
     hipStream_t stream = (hipStream_t)stream_;
     KCHECK_HIP(hipSetDevice(d->s.device));
     d->comm->use_stream(stream);
@@ -293,10 +297,16 @@ int katome_dist_contigs_gfa(katome_dist_builder* d, katome_dist_gfa* out, void* 
     GfaTrace trace{name, d->comm, &d->sh_gfa.total_text_bytes};
     {
         PhaseScope ps(d->b->prof, PH_GFA, stream);
-        KCHECK(dist_contigs_gfa(d, trace, stream));
+        KCHECK(dist_contigs_gfa(d, name, coverage, trace, stream));
     }
     *out = d->sh_gfa;
     return KATOME_OK;
+}
+int katome_dist_contigs_gfa(katome_dist_builder* d, katome_dist_gfa* out, void* stream_) {
+    return dist_contigs_gfa_entry(d, "katome_dist_contigs_gfa", false, out, stream_);
+}
+int katome_dist_contigs_gfa_coverage(katome_dist_builder* d, katome_dist_gfa* out, void* stream_) {
+    return dist_contigs_gfa_entry(d, "katome_dist_contigs_gfa_coverage", true, out, stream_);
 }
 
 int katome_dist_gfa_save(katome_dist_builder* d, const katome_dist_gfa* g, const char* path) {

@@ -16,6 +16,9 @@
 //   * merged edges live on the rank of their head: the last edge of each path sends its end node there, every other edge
 //     (offset, last base of its key); the bases land at fixed places of a one-byte-per-base staging array (offsets are dense
 //     per path: no sort, no atomics) that a pack kernel turns into compress_edge labels.
+//   * coverage (katome_dist_shrink_coverage only): every non-head edge also sends (head, offset << 32 | its weight) over the same
+//     routing; the weights land where the bases do, in a 4-byte staging array, and one wave per merged edge reduces them with the
+//     head's own weight to their sum, smallest and largest.  No atomics here either.
 //   * node numbering: a surviving vertex's new id is the number of surviving vertices with a smaller global id, counted per
 //     directory range (id / ceil(TN / world)), one question and answer per endpoint of a merged edge and per node of the share.
 // Memory per rank is O(share) (plus the staging of the paths whose heads it holds).  A rank's share stays below 2^32 edges
@@ -100,11 +103,12 @@ __global__ __launch_bounds__(BLOCK) void slot_kernel(const u32* __restrict__ hea
     WLOOP(i, H) if (i < H) { slot[heads[i]] = (u32)i; m[i] = 1; }
 }
 // last edges -> (head, end node); every other non-head edge -> (head, offset << 2 | the last base of its key)
-template <int NW>
+// COV (katome_dist_shrink_coverage): and, for the same head address, (offset << 32 | the edge's weight) -- offsets stay below 2^32
+template <int NW, bool COV>
 __global__ __launch_bounds__(BLOCK) void path_rec_kernel(const u64* __restrict__ st_a, const u64* __restrict__ st_b, const u64* __restrict__ dst,
                                                          const u64* __restrict__ key, const unsigned char* __restrict__ last, u64 E, u64 me,
                                                          u64* __restrict__ endA, u64* __restrict__ endB, u64* __restrict__ baseA, u64* __restrict__ baseB,
-                                                         unsigned long long* cursors) {
+                                                         unsigned long long* cursors, const u32* __restrict__ weight, u64* __restrict__ baseW) {
     WLOOP(e, E) {
         const bool ok = e < E;
         const u64 a = ok ? st_a[e] : 0;
@@ -112,7 +116,10 @@ __global__ __launch_bounds__(BLOCK) void path_rec_kernel(const u64* __restrict__
         const bool is_last = ok && last[e], is_base = ok && !head;
         const u64 at_end = wave_append(is_last, cursors), at_base = wave_append(is_base, cursors + 1);
         if (is_last) { endA[at_end] = a & ADDR; endB[at_end] = dst[e]; }
-        if (is_base) { baseA[at_base] = a & ADDR; baseB[at_base] = (st_b[e] << 2) | (key[e * NW + NW - 1] & 3); }
+        if (is_base) {
+            baseA[at_base] = a & ADDR; baseB[at_base] = (st_b[e] << 2) | (key[e * NW + NW - 1] & 3);
+            if constexpr (COV) baseW[at_base] = (st_b[e] << 32) | weight[e];
+        }
     }
 }
 // (records name head edges of this rank: slot < H; the checks only keep a broken invariant from writing out of bounds)
@@ -139,6 +146,35 @@ __global__ __launch_bounds__(BLOCK) void base_place_kernel(const u64* __restrict
         const u32 l = local_of(A[i]), s = l < E ? slot[l] : NONE32;
         const u64 off = B[i] >> 2;
         if (s < H && off >= 1 && off < m[s]) stage[stage_off[s] + off - 1] = (unsigned char)(B[i] & 3);
+    }
+}
+// coverage: every non-head edge's weight at the place its base has in the byte staging -- stage_off[s] + offset - 1, dense and
+// collision-free per path -- of a 4-byte staging array
+__global__ __launch_bounds__(BLOCK) void weight_place_kernel(const u64* __restrict__ A, const u64* __restrict__ W, u64 n, const u32* __restrict__ slot, u64 E,
+                                                             u64 H, const u32* __restrict__ m, const u64* __restrict__ stage_off, u32* __restrict__ wstage) {
+    WLOOP(i, n) if (i < n) {
+        const u32 l = local_of(A[i]), s = l < E ? slot[l] : NONE32;
+        const u64 off = W[i] >> 32;
+        if (s < H && off >= 1 && off < m[s]) wstage[stage_off[s] + off - 1] = (u32)W[i];
+    }
+}
+// one wave per merged edge (as pack_kernel): the head's own weight and the staged ones, reduced to their sum, smallest and largest
+__global__ __launch_bounds__(BLOCK) void weight_reduce_kernel(const u32* __restrict__ heads, u64 H, const u32* __restrict__ weight, const u32* __restrict__ m,
+                                                              const u64* __restrict__ stage_off, const u32* __restrict__ wstage, u64* __restrict__ o_sum,
+                                                              u32* __restrict__ o_min, u32* __restrict__ o_max) {
+    const u32 lane = threadIdx.x & 63;
+    for (u64 i = ((u64)blockIdx.x * BLOCK + threadIdx.x) >> 6; i < H; i += ((u64)gridDim.x * BLOCK) >> 6) {
+        const u32 hw = weight[heads[i]], staged = m[i] - 1;
+        const u32* st = wstage + stage_off[i];
+        u64 sum = lane == 0 ? hw : 0;
+        u32 mn = hw, mx = hw;
+        for (u32 j = lane; j < staged; j += 64) { const u32 w = st[j]; sum += w; mn = min(mn, w); mx = max(mx, w); }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            sum += __shfl_xor(sum, o, 64);
+            mn = min(mn, (u32)__shfl_xor(mn, o, 64)); mx = max(mx, (u32)__shfl_xor(mx, o, 64));
+        }
+        if (lane == 0) { o_sum[i] = sum; o_min[i] = mn; o_max[i] = mx; }
     }
 }
 // one wave per merged edge: compress_edge's padding byte, then 4 bases a byte (the head's k, then the staged ones), left-aligned
@@ -281,7 +317,8 @@ int check_shrink_builder(katome_dist_builder* d) {
     return KATOME_OK;
 }
 
-int dist_shrink(katome_dist_builder* d, katome_dist_shrink_stats* stats, hipStream_t stream) {
+// (want_cov: every rank's merged edges also get the sum, smallest and largest weight along their paths: d->sh_cov)
+int dist_shrink(katome_dist_builder* d, katome_dist_shrink_stats* stats, hipStream_t stream, bool want_cov) {
     Shrink S(d, stream);
     KCHECK(S.cursors.alloc(64)); KCHECK(S.router.init());
     katome_builder* b = d->b;
@@ -339,14 +376,16 @@ int dist_shrink(katome_dist_builder* d, katome_dist_shrink_stats* stats, hipStre
     KCHECK(slot.alloc((E + 1) * 4)); KCHECK(m.alloc((H + 1) * 4));
     KCHECK_HIP(hipMemsetAsync(slot.p, 0xFF, (E + 1) * 4, stream));
     if (H) KLAUNCH(slot_kernel, H, stream, heads.as<u32>(), H, slot.as<u32>(), m.as<u32>());
-    DevBuf endA(stream), endB(stream), baseA(stream), baseB(stream), end_node(stream);
+    DevBuf endA(stream), endB(stream), baseA(stream), baseB(stream), baseW(stream), end_node(stream);
     KCHECK(endA.alloc((E + 1) * 8)); KCHECK(endB.alloc((E + 1) * 8)); KCHECK(baseA.alloc((E + 1) * 8)); KCHECK(baseB.alloc((E + 1) * 8));
+    if (want_cov) KCHECK(baseW.alloc((E + 1) * 8));
     KCHECK(end_node.alloc((H + 1) * 8));
     KCHECK(S.reset());
-    if (E && nw == 1) KLAUNCH(path_rec_kernel<1>, E, stream, st_a.as<u64>(), st_b.as<u64>(), dst, b->edge_key.as<u64>(), last.as<unsigned char>(), E, me,
-                              endA.as<u64>(), endB.as<u64>(), baseA.as<u64>(), baseB.as<u64>(), S.cur());
-    if (E && nw == 2) KLAUNCH(path_rec_kernel<2>, E, stream, st_a.as<u64>(), st_b.as<u64>(), dst, b->edge_key.as<u64>(), last.as<unsigned char>(), E, me,
-                              endA.as<u64>(), endB.as<u64>(), baseA.as<u64>(), baseB.as<u64>(), S.cur());
+    if (E) {
+        auto rec_kernel = nw == 1 ? (want_cov ? path_rec_kernel<1, true> : path_rec_kernel<1, false>) : (want_cov ? path_rec_kernel<2, true> : path_rec_kernel<2, false>);
+        KLAUNCH(rec_kernel, E, stream, st_a.as<u64>(), st_b.as<u64>(), dst, b->edge_key.as<u64>(), last.as<unsigned char>(), E, me, endA.as<u64>(), endB.as<u64>(),
+                baseA.as<u64>(), baseB.as<u64>(), S.cur(), b->edge_weight.as<u32>(), baseW.as<u64>());
+    }
     KCHECK_HIP(hipGetLastError());
     uint64_t nrec[2] = {0, 0};
     KCHECK(S.read(nrec, 2));
@@ -354,11 +393,12 @@ int dist_shrink(katome_dist_builder* d, katome_dist_shrink_stats* stats, hipStre
     DevBuf label_off(stream), stage_off(stream), label(stream);
     uint64_t label_bytes = 0;
     {
-        Routed ends(stream), bases_r(stream);
+        Routed ends(stream), bases_r(stream), weights_r(stream);
         KCHECK(S.router.send(endA.as<u64>(), endB.as<u64>(), nrec[0], ends));
         endA.release(); endB.release();
         KCHECK(S.router.send(baseA.as<u64>(), baseB.as<u64>(), nrec[1], bases_r));
-        baseA.release(); baseB.release();
+        if (want_cov) KCHECK(S.router.send(baseA.as<u64>(), baseW.as<u64>(), nrec[1], weights_r));       // (the same routing: the same A array)
+        baseA.release(); baseB.release(); baseW.release();
         KCHECK(S.reset());
         if (ends.n) KLAUNCH(end_place_kernel, ends.n, stream, ends.a.as<u64>(), ends.b.as<u64>(), ends.n, slot.as<u32>(), E, H, end_node.as<u64>(), S.cur() + 7);
         if (bases_r.n) KLAUNCH(base_len_kernel, bases_r.n, stream, bases_r.a.as<u64>(), bases_r.b.as<u64>(), bases_r.n, slot.as<u32>(), E, H, m.as<u32>(), S.cur() + 7);
@@ -383,7 +423,7 @@ int dist_shrink(katome_dist_builder* d, katome_dist_shrink_stats* stats, hipStre
         } else {
             KCHECK_HIP(hipMemsetAsync(label_off.p, 0, 8, stream));
         }
-        bad = n_staged != bases_r.n ? 1 : 0;
+        bad = (n_staged != bases_r.n || (want_cov && weights_r.n != bases_r.n)) ? 1 : 0;       // (the weights' places are the bases': one check for both)
         KCHECK(d->comm->allreduce(&bad, 1, OP_MAX));
         if (bad) { set_error("katome_dist_shrink: the offsets of a path are not dense"); return KATOME_E_DEVICE; }
         KCHECK(stage.alloc(n_staged + 16)); KCHECK(label.alloc(label_bytes + 16));
@@ -395,6 +435,16 @@ int dist_shrink(katome_dist_builder* d, katome_dist_shrink_stats* stats, hipStre
         if (H && nw == 2) hipLaunchKernelGGL(pack_kernel<2>, pg, dim3(BLOCK), 0, stream, heads.as<u32>(), H, b->edge_key.as<u64>(), m.as<u32>(), label_off.as<u64>(),
                                              stage_off.as<u64>(), stage.as<unsigned char>(), k, label.as<unsigned char>());
         KCHECK_HIP(hipGetLastError());
+        DevBuf wstage(stream);                             // coverage: 4 bytes per non-head edge whose head this rank holds, transient
+        if (want_cov) {
+            KCHECK(wstage.alloc((n_staged + 4) * 4));
+            KCHECK(d->sh_cov.kmer_sum.alloc((H + 1) * 8, stream)); KCHECK(d->sh_cov.kmer_min.alloc((H + 1) * 4, stream)); KCHECK(d->sh_cov.kmer_max.alloc((H + 1) * 4, stream));
+            if (weights_r.n) KLAUNCH(weight_place_kernel, weights_r.n, stream, weights_r.a.as<u64>(), weights_r.b.as<u64>(), weights_r.n, slot.as<u32>(), E, H, m.as<u32>(),
+                                     stage_off.as<u64>(), wstage.as<u32>());
+            if (H) hipLaunchKernelGGL(weight_reduce_kernel, pg, dim3(BLOCK), 0, stream, heads.as<u32>(), H, b->edge_weight.as<u32>(), m.as<u32>(), stage_off.as<u64>(),
+                                      wstage.as<u32>(), d->sh_cov.kmer_sum.as<u64>(), d->sh_cov.kmer_min.as<u32>(), d->sh_cov.kmer_max.as<u32>());
+            KCHECK_HIP(hipGetLastError());
+        }
         KCHECK_HIP(hipStreamSynchronize(stream));
     }
     slot.release(); stage_off.release();
@@ -468,6 +518,7 @@ int dist_shrink(katome_dist_builder* d, katome_dist_shrink_stats* stats, hipStre
     install(d->sh_label_off, label_off); install(d->sh_label, label); install(d->sh_head, o_head); install(d->sh_node_id, o_nid);
     install(d->sh_node_key, o_nkey);
     d->sh_edges = H; d->sh_nodes = NK; d->sh_total_edges = TE_new; d->sh_total_nodes = TN_new; d->sh_label_bytes = label_bytes;
+    if (want_cov) { d->sh_cov.n_edges = H; d->sh_cov.valid = true; }
     if (stats) {
         stats->rank_rounds = rounds; stats->cycle_rounds = cycle_rounds; stats->cycles = n_cycles;
         stats->longest_path = longest; stats->bytes_sent = d->comm->stats.bytes_out - bytes0;
@@ -479,10 +530,13 @@ int dist_shrink(katome_dist_builder* d, katome_dist_shrink_stats* stats, hipStre
 
 extern "C" {
 
-int katome_dist_shrink(katome_dist_builder* d, katome_dist_contigs* out, katome_dist_shrink_stats* stats, void* stream_) {
+// katome_dist_shrink and katome_dist_shrink_coverage: the coverage of an earlier call never survives a later one of either kind
+static int dist_shrink_entry(katome_dist_builder* d, katome_dist_contigs* out, katome_dev_coverage* cov, bool want_cov, katome_dist_shrink_stats* stats, void* stream_) {
     if (out) memset(out, 0, sizeof *out);
+    if (cov) memset(cov, 0, sizeof *cov);
     if (stats) memset(stats, 0, sizeof *stats);
     KCHECK(check_shrink_builder(d));
+    if (want_cov && !cov) { set_error("null argument"); return KATOME_E_ARG; }
     hipStream_t stream = (hipStream_t)stream_;
     KCHECK_HIP(hipSetDevice(d->s.device));
     d->comm->use_stream(stream);
@@ -490,7 +544,9 @@ int katome_dist_shrink(katome_dist_builder* d, katome_dist_contigs* out, katome_
     katome_dist_shrink_stats st;
     const double t0 = now_ms();
     d->sh_valid = false; ++d->sh_serial;      // (what katome_dist_contigs_text made of the last result is no longer this builder's text)
-    KCHECK(dist_shrink(d, &st, stream));
+    d->sh_cov.drop();
+    const int rc = dist_shrink(d, &st, stream, want_cov);
+    if (rc != KATOME_OK) { d->sh_cov.drop(); return rc; }
     d->sh_valid = true;
     if (trace)
         fprintf(stderr, "[katome_dist_shrink] rank %d/%d: %.2f ms, ranking rounds %u, cycle rounds %u, longest path %llu, sent %llu bytes\n", d->rank(),
@@ -504,7 +560,18 @@ int katome_dist_shrink(katome_dist_builder* d, katome_dist_contigs* out, katome_
         out->d_edge_label_off = d->sh_label_off.as<uint64_t>(); out->d_edge_label = d->sh_label.as<uint8_t>();
         out->d_edge_head_id = d->sh_head.as<uint64_t>(); out->d_node_id = d->sh_node_id.as<uint64_t>(); out->d_node_key = d->sh_node_key.as<uint64_t>();
     }
+    if (want_cov) {
+        cov->n_edges = d->sh_cov.n_edges;
+        cov->d_kmer_sum = d->sh_cov.kmer_sum.as<uint64_t>(); cov->d_kmer_min = d->sh_cov.kmer_min.as<uint32_t>(); cov->d_kmer_max = d->sh_cov.kmer_max.as<uint32_t>();
+    }
     return KATOME_OK;
+}
+
+int katome_dist_shrink(katome_dist_builder* d, katome_dist_contigs* out, katome_dist_shrink_stats* stats, void* stream_) {
+    return dist_shrink_entry(d, out, nullptr, false, stats, stream_);
+}
+int katome_dist_shrink_coverage(katome_dist_builder* d, katome_dist_contigs* out, katome_dev_coverage* cov, katome_dist_shrink_stats* stats, void* stream_) {
+    return dist_shrink_entry(d, out, cov, true, stats, stream_);
 }
 
 }  // extern "C"

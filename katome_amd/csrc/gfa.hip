@@ -22,6 +22,9 @@
 //   a text whose other parts are written elsewhere (dist_gfa.hip): names start at first_segment, links come as a table of 64-bit
 //   global numbers, the header is written or not, and the S part and the L part are two regions of one buffer, each a launch of its
 //   own.  It is a separate instantiation: gfa_write_kernel<false> is the one-GPU kernel as it was.
+//   The coverage form (COV, a second template parameter of the two measure kernels and of the writer's S-tag branch): KC is the sum of
+//   the path's k-mer counts and "\tmn:i:<min>\tmx:i:<max>" follows ew (katome_dev_contigs_gfa_coverage, katome_dev_gfa_coverage_arrays,
+//   GfaGraph::cov / GfaPart::cov); the variants without it are the kernels as they were.  gfa_strands.hip has no coverage form.
 //   Every segment is one strand here and every orientation +; gfa_strands.hip folds strand twins into one segment with +/- links, on
 //   top of this file's join (dev_gfa_plan) and the tile image both writers share (gfa_image.h).
 #include "builder.h"
@@ -34,17 +37,34 @@ namespace {
 constexpr int S_NAME_MAX_NUMBERED = 2 + 20 + 1;        // ... of a numbered part: first_segment + i < 2^64
 constexpr u32 L_LINE_MAX_NUMBERED = 10 + 20 + 20 + 10; // "L\t<a>\t+\t<b>\t+\t<k-1>M\n" with two 64-bit numbers: far below a tile
 constexpr int S_TAGS_MAX = 3 * 6 + 10 + 20 + 10 + 1;   // "\tLN:i:<u32>\tKC:i:<u64>\tew:i:<u32>\n"
+constexpr int S_TAGS_MAX_COV = S_TAGS_MAX + 2 * (6 + 10);      // ... with coverage: "\tmn:i:<u32>\tmx:i:<u32>" in front of the line's end
+static_assert(S_TAGS_MAX_COV < (int)TILE, "a segment's tags fit a tile");
 // (no line of either form is shorter than the header's 11 bytes -- the shortest L line, "L\t0\t+\t0\t+\t0M\n", has 13 --, so MAX_LINES and
 // the 16-bit offsets hold for a numbered part too: longer numbers only make lines longer)
 static_assert(L_LINE_MAX_NUMBERED < TILE && HEADER_BYTES <= 13, "a tile holds at most MAX_LINES lines");
-enum { ERR_NODE = 1, ERR_LABEL = 2, ERR_LABEL_LEN = 4, ERR_KMERS = 8, ERR_LINKS = 16 };
+enum { ERR_NODE = 1, ERR_LABEL = 2, ERR_LABEL_LEN = 4, ERR_KMERS = 8, ERR_LINKS = 16, ERR_COVERAGE = 32 };
+
+// The coverage variant (COV, GfaCoverage of common.h): KC is the sum of the path's k-mer counts and the S line ends in mn / mx.  A
+// compile-time variant of the two measure kernels and of the writer's S-tag branch: without it they are the kernels they were.
+// a segment's coverage fits its weight and its k-mers: min <= weight <= max and min * kmers <= sum <= max * kmers (64-bit: u32 * u32)
+__device__ __forceinline__ bool coverage_fits(const GfaCoverage& c, u64 i, u32 w, u32 km) {
+    const u32 mn = c.kmer_min[i], mx = c.kmer_max[i];
+    const u64 sum = c.kmer_sum[i];
+    return mn <= w && w <= mx && (u64)mn * km <= sum && sum <= (u64)mx * km;
+}
+// the bytes of "\tKC:i:<sum>\tew:i:<w>\tmn:i:<min>\tmx:i:<max>\n"
+__device__ __forceinline__ u32 coverage_tag_bytes(const GfaCoverage& c, u64 i, u32 w) {
+    return 6 + decimal_digits(c.kmer_sum[i]) + 6 + decimal_digits(w) + 6 + decimal_digits(c.kmer_min[i]) + 6 + decimal_digits(c.kmer_max[i]) + 1;
+}
 
 // Segment i's line: checks everything the later kernels read through (the two vertices, the label's offsets, pad byte and length, and
 // that the label spells edge_kmers + k - 1 bases), counts the line's bytes, and sets up the sort of the edge indices by source
+template <bool COV>
 __global__ __launch_bounds__(BLOCK) void gfa_measure_kernel(u32 k, u64 N, u64 E, const u64* __restrict__ src, const u64* __restrict__ dst,
                                                             const u32* __restrict__ weight, const u32* __restrict__ kmers,
                                                             const u64* __restrict__ label_off, const uint8_t* __restrict__ label, u64 label_bytes,
-                                                            u32* __restrict__ size, u64* __restrict__ key, u32* __restrict__ order, u32* __restrict__ err) {
+                                                            u32* __restrict__ size, u64* __restrict__ key, u32* __restrict__ order, u32* __restrict__ err,
+                                                            const GfaCoverage cov) {
     if (blockIdx.x == 0 && threadIdx.x == 0) size[0] = HEADER_BYTES;
     for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < E; i += (u64)gridDim.x * BLOCK) {
         size[1 + i] = 0; key[i] = 0; order[i] = (u32)i;
@@ -55,6 +75,12 @@ __global__ __launch_bounds__(BLOCK) void gfa_measure_kernel(u32 k, u64 N, u64 E,
         if (bad) { atomicOr(err, (u32)(bad == 2 ? ERR_LABEL_LEN : ERR_LABEL)); continue; }
         if ((u64)bases != (u64)kmers[i] + k - 1) { atomicOr(err, (u32)ERR_KMERS); continue; }
         const u32 w = weight[i];
+        if constexpr (COV) {
+            if (!coverage_fits(cov, i, w, kmers[i])) { atomicOr(err, (u32)ERR_COVERAGE); continue; }      // (no size from the bad values)
+            key[i] = s;
+            size[1 + i] = 2 + decimal_digits(i) + 1 + bases + 6 + decimal_digits(bases) + coverage_tag_bytes(cov, i, w);
+            continue;
+        }
         key[i] = s;
         size[1 + i] = 2 + decimal_digits(i) + 1 + bases + 6 + decimal_digits(bases) + 6 + decimal_digits((u64)w * kmers[i]) + 6 + decimal_digits(w) + 1;
     }
@@ -117,12 +143,14 @@ __device__ __forceinline__ Line load_line(u32 r, u32 E, u32 hdr, const uint8_t* 
 // (An S part is launched with hdr header lines and E segments, R = hdr + E; an L part with E = 0, hdr = 0 and R links.)
 struct PartNumbers { u64 first; u32 hdr; const u32* link_a; const u64* link_b; };
 
-template <bool NUMBERED>
+template <bool NUMBERED, bool COV>
 __global__ __launch_bounds__(BLOCK) void gfa_write_kernel(u32 k, u32 E, u32 R, const u32* __restrict__ weight, const u32* __restrict__ kmers,
                                                           const u64* __restrict__ label_off, const uint8_t* __restrict__ label,
                                                           const u64* __restrict__ line_off, const u64* __restrict__ segment_off,
-                                                          const u32* __restrict__ link_ab, u64 total, uint8_t* __restrict__ text, const PartNumbers pn) {
+                                                          const u32* __restrict__ link_ab, u64 total, uint8_t* __restrict__ text, const PartNumbers pn,
+                                                          const GfaCoverage cov) {
     const u32 hdr = NUMBERED ? pn.hdr : 1u;
+    constexpr int tags_max = COV ? S_TAGS_MAX_COV : S_TAGS_MAX;
     constexpr int name_max = NUMBERED ? S_NAME_MAX_NUMBERED : S_NAME_MAX;
     __shared__ __align__(16) uint8_t s_img[TILE];      // the tile's bytes that are not bases
     __shared__ uint16_t s_off[MAX_LINES];              // where the tile's lines start, relative to the tile
@@ -163,12 +191,16 @@ __global__ __launch_bounds__(BLOCK) void gfa_write_kernel(u32 k, u32 E, u32 R, c
                     else p = put_decimal_back(s_img, p, len, i);
                     put_tag_back<2>(s_img, p, len, tag('S', '\t', 0, 0, 0, 0));
                 }
-                if (end - S_TAGS_MAX < len) {                                  // the tags behind the bases do
+                if (end - tags_max < len) {                                    // the tags behind the bases do
                     const u32 w = weight[i], km = kmers[i];
                     int p = (int)end - 1;
                     put(s_img, p--, len, '\n');
+                    if constexpr (COV) {
+                        p = put_tag_back<6>(s_img, put_decimal_back(s_img, p, len, cov.kmer_max[i]), len, tag('\t', 'm', 'x', ':', 'i', ':'));
+                        p = put_tag_back<6>(s_img, put_decimal_back(s_img, p, len, cov.kmer_min[i]), len, tag('\t', 'm', 'n', ':', 'i', ':'));
+                    }
                     p = put_tag_back<6>(s_img, put_decimal_back(s_img, p, len, w), len, tag('\t', 'e', 'w', ':', 'i', ':'));
-                    p = put_tag_back<6>(s_img, put_decimal_back(s_img, p, len, (u64)w * km), len, tag('\t', 'K', 'C', ':', 'i', ':'));
+                    p = put_tag_back<6>(s_img, put_decimal_back(s_img, p, len, COV ? cov.kmer_sum[i] : (u64)w * km), len, tag('\t', 'K', 'C', ':', 'i', ':'));
                     put_tag_back<6>(s_img, put_decimal_back(s_img, p, len, km + k - 1), len, tag('\t', 'L', 'N', ':', 'i', ':'));
                 }
             }
@@ -214,9 +246,11 @@ __global__ __launch_bounds__(BLOCK) void gfa_write_kernel(u32 k, u32 E, u32 R, c
 
 // ---- a numbered part: the same sizes, counted with the digits of the GLOBAL numbers --------------------------------------------
 // segment i of a part (named first + i): its label's checks, that its links' range ascends (link_first[0] = 0), its line's bytes
+template <bool COV>
 __global__ __launch_bounds__(BLOCK) void gfa_part_measure_kernel(u32 k, u64 E, u64 first, u32 hdr, const u32* __restrict__ weight, const u32* __restrict__ kmers,
                                                                  const u64* __restrict__ label_off, const uint8_t* __restrict__ label, u64 label_bytes,
-                                                                 const u64* __restrict__ link_first, u32* __restrict__ size, u32* __restrict__ err) {
+                                                                 const u64* __restrict__ link_first, u32* __restrict__ size, u32* __restrict__ err,
+                                                                 const GfaCoverage cov) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         if (hdr) size[0] = HEADER_BYTES;
         if (link_first[0] != 0) atomicOr(err, (u32)ERR_LINKS);
@@ -229,6 +263,11 @@ __global__ __launch_bounds__(BLOCK) void gfa_part_measure_kernel(u32 k, u64 E, u
         if (bad) { atomicOr(err, (u32)(bad == 2 ? ERR_LABEL_LEN : ERR_LABEL)); continue; }
         if ((u64)bases != (u64)kmers[i] + k - 1) { atomicOr(err, (u32)ERR_KMERS); continue; }
         const u32 w = weight[i];
+        if constexpr (COV) {
+            if (!coverage_fits(cov, i, w, kmers[i])) { atomicOr(err, (u32)ERR_COVERAGE); continue; }
+            size[hdr + i] = 2 + decimal_digits(first + i) + 1 + bases + 6 + decimal_digits(bases) + coverage_tag_bytes(cov, i, w);
+            continue;
+        }
         size[hdr + i] = 2 + decimal_digits(first + i) + 1 + bases + 6 + decimal_digits(bases) + 6 + decimal_digits((u64)w * kmers[i]) + 6 + decimal_digits(w) + 1;
     }
 }
@@ -252,6 +291,7 @@ int check_gfa_errors(u32 err) {
     if (err & ERR_LABEL) { set_error("gfa: a label's offsets, pad byte or length (shorter than k bases) are malformed"); return KATOME_E_ARG; }
     if (err & ERR_LABEL_LEN) { set_error("gfa: a label of more than 2^31 bases"); return KATOME_E_UNSUPPORTED; }
     if (err & ERR_KMERS) { set_error("gfa: a label's bases are not edge_kmers + k - 1"); return KATOME_E_ARG; }
+    if (err & ERR_COVERAGE) { set_error("gfa: a segment's coverage does not fit its weight and k-mer count"); return KATOME_E_ARG; }
     return KATOME_OK;
 }
 
@@ -262,6 +302,7 @@ int dev_gfa_plan(const GfaGraph& g, GfaPlan& plan, hipStream_t stream) {
     const u64 E = g.n_edges, N = g.n_nodes;
     if (E >= (1ull << 32)) { set_error("gfa: %llu segments, at most 2^32 - 1", (unsigned long long)E); return KATOME_E_UNSUPPORTED; }
     if (E && (!g.edge_src || !g.edge_dst || !g.edge_weight || !g.edge_kmers || !g.label_off || !g.label)) { set_error("null argument"); return KATOME_E_ARG; }
+    if (g.cov.any() && E && !g.cov.all()) { set_error("null argument"); return KATOME_E_ARG; }
     const dim3 blk(BLOCK), grid(grid_for(E, BLOCK, 256u * 32u));
     plan.line_off.stream = plan.segment_off.stream = plan.link_first.stream = plan.link_ab.stream = stream;
     DevBuf key(stream), order(stream), seg_size(stream), count(stream), range(stream), size(stream), tail(stream);
@@ -270,8 +311,8 @@ int dev_gfa_plan(const GfaGraph& g, GfaPlan& plan, hipStream_t stream) {
     KCHECK_HIP(hipMemsetAsync(tail.p, 0, 16, stream));
     {
         KernelScope ks(K_GFA_SIZES, stream, E);
-        hipLaunchKernelGGL(gfa_measure_kernel, grid, blk, 0, stream, g.k, N, E, g.edge_src, g.edge_dst, g.edge_weight, g.edge_kmers, g.label_off, g.label,
-                           g.label_bytes, seg_size.as<u32>(), key.as<u64>(), order.as<u32>(), tail.as<u32>());
+        hipLaunchKernelGGL(g.cov.any() ? gfa_measure_kernel<true> : gfa_measure_kernel<false>, grid, blk, 0, stream, g.k, N, E, g.edge_src, g.edge_dst, g.edge_weight,
+                           g.edge_kmers, g.label_off, g.label, g.label_bytes, seg_size.as<u32>(), key.as<u64>(), order.as<u32>(), tail.as<u32>(), g.cov);
         KCHECK_HIP(hipGetLastError());
     }
     u32 err = 0;
@@ -326,8 +367,9 @@ int dev_gfa_plan(const GfaGraph& g, GfaPlan& plan, hipStream_t stream) {
 int dev_gfa_write(const GfaGraph& g, const GfaPlan& plan, uint8_t* text, hipStream_t stream) {
     const u64 R = 1 + g.n_edges + plan.n_links, tiles = (plan.text_bytes + TILE - 1) / TILE;
     KernelScope ks(K_GFA_WRITE, stream, plan.text_bytes);
-    hipLaunchKernelGGL(gfa_write_kernel<false>, dim3(grid_for(tiles, 1, 256u * 16u)), dim3(BLOCK), 0, stream, g.k, (u32)g.n_edges, (u32)R, g.edge_weight, g.edge_kmers,
-                       g.label_off, g.label, plan.line_off.as<u64>(), plan.segment_off.as<u64>(), plan.link_ab.as<u32>(), plan.text_bytes, text, PartNumbers{0, 1, nullptr, nullptr});
+    hipLaunchKernelGGL((g.cov.any() ? gfa_write_kernel<false, true> : gfa_write_kernel<false, false>), dim3(grid_for(tiles, 1, 256u * 16u)), dim3(BLOCK), 0, stream, g.k,
+                       (u32)g.n_edges, (u32)R, g.edge_weight, g.edge_kmers, g.label_off, g.label, plan.line_off.as<u64>(), plan.segment_off.as<u64>(),
+                       plan.link_ab.as<u32>(), plan.text_bytes, text, PartNumbers{0, 1, nullptr, nullptr}, g.cov);
     KCHECK_HIP(hipGetLastError());
     return KATOME_OK;
 }
@@ -352,6 +394,7 @@ int dev_gfa_part_plan(const GfaPart& g, GfaPartPlan& plan, hipStream_t stream) {
     if (E >= (1ull << 32)) { set_error("gfa: %llu segments in one part, at most 2^32 - 1", (unsigned long long)E); return KATOME_E_UNSUPPORTED; }
     if (first + E < first) { set_error("gfa: segment numbers from %llu on for %llu segments pass 2^64", (unsigned long long)first, (unsigned long long)E); return KATOME_E_UNSUPPORTED; }
     if (!g.link_first || (E && (!g.edge_weight || !g.edge_kmers || !g.label_off || !g.label))) { set_error("null argument"); return KATOME_E_ARG; }
+    if (g.cov.any() && E && !g.cov.all()) { set_error("null argument"); return KATOME_E_ARG; }
     const dim3 blk(BLOCK), grid(grid_for(E, BLOCK, 256u * 32u));
     plan.s_line_off.stream = plan.l_line_off.stream = plan.segment_off.stream = plan.link_a.stream = stream;
     DevBuf size(stream), lsize(stream), tail(stream);
@@ -359,8 +402,8 @@ int dev_gfa_part_plan(const GfaPart& g, GfaPartPlan& plan, hipStream_t stream) {
     KCHECK_HIP(hipMemsetAsync(tail.p, 0, 16, stream));
     {
         KernelScope ks(K_GFA_SIZES, stream, E);
-        hipLaunchKernelGGL(gfa_part_measure_kernel, grid, blk, 0, stream, g.k, E, first, hdr, g.edge_weight, g.edge_kmers, g.label_off, g.label, g.label_bytes,
-                           g.link_first, size.as<u32>(), tail.as<u32>());
+        hipLaunchKernelGGL(g.cov.any() ? gfa_part_measure_kernel<true> : gfa_part_measure_kernel<false>, grid, blk, 0, stream, g.k, E, first, hdr, g.edge_weight,
+                           g.edge_kmers, g.label_off, g.label, g.label_bytes, g.link_first, size.as<u32>(), tail.as<u32>(), g.cov);
         KCHECK_HIP(hipGetLastError());
     }
     u32 err = 0;
@@ -401,14 +444,15 @@ int dev_gfa_part_write(const GfaPart& g, const GfaPartPlan& plan, uint8_t* text,
     KernelScope ks(K_GFA_WRITE, stream, plan.s_bytes + plan.l_bytes);
     if (plan.s_bytes) {
         const PartNumbers pn{g.first_segment, hdr, nullptr, nullptr};
-        hipLaunchKernelGGL(gfa_write_kernel<true>, dim3(grid_for((plan.s_bytes + TILE - 1) / TILE, 1, 256u * 16u)), dim3(BLOCK), 0, stream, g.k, E, hdr + E, g.edge_weight,
-                           g.edge_kmers, g.label_off, g.label, plan.s_line_off.as<u64>(), plan.segment_off.as<u64>(), nullptr, plan.s_bytes, text, pn);
+        hipLaunchKernelGGL((g.cov.any() ? gfa_write_kernel<true, true> : gfa_write_kernel<true, false>), dim3(grid_for((plan.s_bytes + TILE - 1) / TILE, 1, 256u * 16u)),
+                           dim3(BLOCK), 0, stream, g.k, E, hdr + E, g.edge_weight, g.edge_kmers, g.label_off, g.label, plan.s_line_off.as<u64>(),
+                           plan.segment_off.as<u64>(), nullptr, plan.s_bytes, text, pn, g.cov);
     }
     if (plan.l_bytes) {
         const PartNumbers pn{g.first_segment, 0u, plan.link_a.as<u32>(), g.link_b};
-        hipLaunchKernelGGL(gfa_write_kernel<true>, dim3(grid_for((plan.l_bytes + TILE - 1) / TILE, 1, 256u * 16u)), dim3(BLOCK), 0, stream, g.k, 0u, (u32)plan.n_links,
+        hipLaunchKernelGGL((gfa_write_kernel<true, false>), dim3(grid_for((plan.l_bytes + TILE - 1) / TILE, 1, 256u * 16u)), dim3(BLOCK), 0, stream, g.k, 0u, (u32)plan.n_links,
                            g.edge_weight, g.edge_kmers, g.label_off, g.label, plan.l_line_off.as<u64>(), plan.segment_off.as<u64>(), nullptr, plan.l_bytes,
-                           text + plan.l_offset(), pn);
+                           text + plan.l_offset(), pn, GfaCoverage{});      // (an L part has no segments)
     }
     KCHECK_HIP(hipGetLastError());
     return KATOME_OK;
@@ -445,7 +489,8 @@ int katome_dev_gfa_part_arrays(int device, uint32_t k, uint64_t n_edges, const u
 }
 
 
-int katome_dev_contigs_gfa(katome_builder* b, const katome_dev_contigs* c, katome_dev_gfa* out, void* stream_) {
+// katome_dev_contigs_gfa and its coverage form: one result, b->gfa, whichever wrote it last
+static int builder_contigs_gfa(katome_builder* b, const katome_dev_contigs* c, katome_dev_gfa* out, bool coverage, void* stream_) {
     if (!b || !c || !out) { set_error("null argument"); return KATOME_E_ARG; }
     hipStream_t stream = (hipStream_t)stream_;
     KCHECK_HIP(hipSetDevice(b->s.device));
@@ -455,9 +500,14 @@ int katome_dev_contigs_gfa(katome_builder* b, const katome_dev_contigs* c, katom
         set_error("contigs_gfa: not the result of this builder's last katome_dev_shrink");
         return KATOME_E_ARG;
     }
+    if (coverage && (!b->shrunk_cov.valid || b->shrunk_cov.n_edges != sh.n_edges)) {
+        set_error("contigs_gfa_coverage: this builder's last shrink was not a katome_dev_shrink_coverage");
+        return KATOME_E_ARG;
+    }
     memset(out, 0, sizeof *out);
-    const GfaGraph g{b->s.k, sh.n_nodes, sh.n_edges, sh.edge_src.as<u64>(), sh.edge_dst.as<u64>(), sh.edge_weight.as<u32>(), sh.edge_kmers.as<u32>(),
-                     sh.edge_label_off.as<u64>(), sh.edge_label.as<uint8_t>(), sh.label_bytes};
+    GfaGraph g{b->s.k, sh.n_nodes, sh.n_edges, sh.edge_src.as<u64>(), sh.edge_dst.as<u64>(), sh.edge_weight.as<u32>(), sh.edge_kmers.as<u32>(),
+               sh.edge_label_off.as<u64>(), sh.edge_label.as<uint8_t>(), sh.label_bytes};
+    if (coverage) g.cov = GfaCoverage{b->shrunk_cov.kmer_sum.as<u64>(), b->shrunk_cov.kmer_min.as<u32>(), b->shrunk_cov.kmer_max.as<u32>()};
     {
         PhaseScope ps(b->prof, PH_GFA, stream);
         KCHECK(dev_gfa(g, b->gfa, stream));
@@ -467,17 +517,25 @@ int katome_dev_contigs_gfa(katome_builder* b, const katome_dev_contigs* c, katom
     return KATOME_OK;
 }
 
-int katome_dev_gfa_arrays(int device, uint32_t k, uint64_t n_nodes, uint64_t n_edges, const uint64_t* d_edge_src, const uint64_t* d_edge_dst,
-                          const uint32_t* d_edge_weight, const uint32_t* d_edge_kmers, const uint64_t* d_edge_label_off, const uint8_t* d_edge_label,
-                          uint64_t label_bytes, uint64_t* d_segment_off, uint64_t* d_link_first, uint8_t* d_text, uint64_t text_cap, uint64_t* n_links,
-                          uint64_t* text_bytes, void* stream_) {
+int katome_dev_contigs_gfa(katome_builder* b, const katome_dev_contigs* c, katome_dev_gfa* out, void* stream_) {
+    return builder_contigs_gfa(b, c, out, false, stream_);
+}
+int katome_dev_contigs_gfa_coverage(katome_builder* b, const katome_dev_contigs* c, katome_dev_gfa* out, void* stream_) {
+    return builder_contigs_gfa(b, c, out, true, stream_);
+}
+
+// katome_dev_gfa_arrays and its coverage form (cov: all three arrays, or none)
+static int gfa_arrays(int device, uint32_t k, uint64_t n_nodes, uint64_t n_edges, const uint64_t* d_edge_src, const uint64_t* d_edge_dst,
+                      const uint32_t* d_edge_weight, const uint32_t* d_edge_kmers, const GfaCoverage& cov, const uint64_t* d_edge_label_off,
+                      const uint8_t* d_edge_label, uint64_t label_bytes, uint64_t* d_segment_off, uint64_t* d_link_first, uint8_t* d_text, uint64_t text_cap,
+                      uint64_t* n_links, uint64_t* text_bytes, void* stream_) {
     KCHECK(use_device(device));
     KCHECK(check_k(k));
     if (!n_links || !text_bytes) { set_error("null argument"); return KATOME_E_ARG; }
     *n_links = *text_bytes = 0;
     hipStream_t stream = (hipStream_t)stream_;
     if ((uintptr_t)d_edge_label & 3) { set_error("gfa: d_edge_label must be 4-byte aligned (the kernel reads the aligned words around the bytes it needs)"); return KATOME_E_ARG; }
-    const GfaGraph g{k, n_nodes, n_edges, d_edge_src, d_edge_dst, d_edge_weight, d_edge_kmers, d_edge_label_off, d_edge_label, label_bytes};
+    const GfaGraph g{k, n_nodes, n_edges, d_edge_src, d_edge_dst, d_edge_weight, d_edge_kmers, d_edge_label_off, d_edge_label, label_bytes, cov};
     GfaPlan plan;
     KCHECK(dev_gfa_plan(g, plan, stream));
     *n_links = plan.n_links; *text_bytes = plan.text_bytes;
@@ -504,6 +562,28 @@ int katome_dev_gfa_arrays(int device, uint32_t k, uint64_t n_nodes, uint64_t n_e
                     (unsigned long long)plan.text_bytes, (unsigned long long)n_edges, (unsigned long long)plan.n_links);
     }
     return KATOME_OK;
+}
+
+int katome_dev_gfa_arrays(int device, uint32_t k, uint64_t n_nodes, uint64_t n_edges, const uint64_t* d_edge_src, const uint64_t* d_edge_dst,
+                          const uint32_t* d_edge_weight, const uint32_t* d_edge_kmers, const uint64_t* d_edge_label_off, const uint8_t* d_edge_label,
+                          uint64_t label_bytes, uint64_t* d_segment_off, uint64_t* d_link_first, uint8_t* d_text, uint64_t text_cap, uint64_t* n_links,
+                          uint64_t* text_bytes, void* stream_) {
+    return gfa_arrays(device, k, n_nodes, n_edges, d_edge_src, d_edge_dst, d_edge_weight, d_edge_kmers, GfaCoverage{}, d_edge_label_off, d_edge_label, label_bytes,
+                      d_segment_off, d_link_first, d_text, text_cap, n_links, text_bytes, stream_);
+}
+int katome_dev_gfa_coverage_arrays(int device, uint32_t k, uint64_t n_nodes, uint64_t n_edges, const uint64_t* d_edge_src, const uint64_t* d_edge_dst,
+                                   const uint32_t* d_edge_weight, const uint32_t* d_edge_kmers, const uint64_t* d_kmer_sum, const uint32_t* d_kmer_min,
+                                   const uint32_t* d_kmer_max, const uint64_t* d_edge_label_off, const uint8_t* d_edge_label, uint64_t label_bytes,
+                                   uint64_t* d_segment_off, uint64_t* d_link_first, uint8_t* d_text, uint64_t text_cap, uint64_t* n_links, uint64_t* text_bytes,
+                                   void* stream_) {
+    if (n_edges && (!d_kmer_sum || !d_kmer_min || !d_kmer_max)) {
+        if (n_links) *n_links = 0;
+        if (text_bytes) *text_bytes = 0;
+        set_error("null argument");
+        return KATOME_E_ARG;
+    }
+    return gfa_arrays(device, k, n_nodes, n_edges, d_edge_src, d_edge_dst, d_edge_weight, d_edge_kmers, GfaCoverage{d_kmer_sum, d_kmer_min, d_kmer_max},
+                      d_edge_label_off, d_edge_label, label_bytes, d_segment_off, d_link_first, d_text, text_cap, n_links, text_bytes, stream_);
 }
 
 }  // extern "C"

@@ -364,10 +364,14 @@ static int unitigs_to_host(katome_builder* b, uint64_t read_bytes, const Unitigs
     if (b->s.flags & KATOME_FLAG_REMOVE_DEAD_PATHS) KCHECK(katome_dev_remove_dead_paths(b, &dg, nullptr, nullptr));
     KCHECK(run_stages(stages, BuilderStages{b, genome_len}));
     katome_dev_contigs dc;
-    KCHECK(katome_dev_shrink_mode(b, KATOME_SHRINK_FAST, &dc, nullptr, nullptr));
+    const bool coverage = want.gfa && (b->s.flags & KATOME_FLAG_PATH_COVERAGE);      // (the graph's ending only: every other entry ignores the flag)
+    katome_dev_coverage cov;
+    if (coverage) KCHECK(katome_dev_shrink_coverage(b, KATOME_SHRINK_FAST, &dc, &cov, nullptr, nullptr));
+    else KCHECK(katome_dev_shrink_mode(b, KATOME_SHRINK_FAST, &dc, nullptr, nullptr));
     if (want.gfa) {                                                  // the graph: katome_dev_contigs_gfa's text is the file
         katome_dev_gfa dgfa;
-        KCHECK(katome_dev_contigs_gfa(b, &dc, &dgfa, nullptr));
+        if (coverage) KCHECK(katome_dev_contigs_gfa_coverage(b, &dc, &dgfa, nullptr));
+        else KCHECK(katome_dev_contigs_gfa(b, &dc, &dgfa, nullptr));
         katome_unitigs_gfa* u = want.gfa;
         u->n_segments = dgfa.n_segments; u->n_links = dgfa.n_links; u->text_bytes = dgfa.text_bytes; u->read_bytes = read_bytes; u->k = b->s.k; u->n_devices = 1;
         std::vector<uint32_t> kmers;
@@ -678,10 +682,14 @@ static uint64_t fasta_header_bytes(uint64_t n) {
 static int sharded_unitigs(MultiBuild& mb, int r, int n, katome_dist_builder* d, hipStream_t stream) {
     const UnitigsWant& want = mb.finish.unitigs;
     katome_dist_shrink_stats ss;
-    KCHECK(katome_dist_shrink(d, nullptr, &ss, stream));
+    const bool coverage = want.gfa && (mb.s->flags & KATOME_FLAG_PATH_COVERAGE);      // (the same settings on every rank)
+    katome_dev_coverage cov;
+    if (coverage) KCHECK(katome_dist_shrink_coverage(d, nullptr, &cov, &ss, stream));
+    else KCHECK(katome_dist_shrink(d, nullptr, &ss, stream));
     if (want.gfa) {                                                  // the graph: the join across ranks, the numbered text, the file
         katome_dist_gfa g;
-        KCHECK(katome_dist_contigs_gfa(d, &g, stream));
+        if (coverage) KCHECK(katome_dist_contigs_gfa_coverage(d, &g, stream));
+        else KCHECK(katome_dist_contigs_gfa(d, &g, stream));
         uint64_t bases[1] = {0};                                     // (the k-mers on all ranks' merged edges: their bases are k - 1 more each)
         KCHECK(dist_gfa_total_kmers(d, bases, stream));
         if (r == 0) {

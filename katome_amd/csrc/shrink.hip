@@ -25,6 +25,13 @@ namespace {
 typedef uint32_t u32;
 constexpr u32 NO_EDGE = 0xFFFFFFFFu;
 constexpr int ITEMS = 8;
+// where a walk with coverage leaves its three values per merged edge (all null without)
+struct CoverageOut { u64* sum; u32 *mn, *mx; };
+// room for n merged edges' coverage
+int coverage_alloc(ShrinkCoverage& c, u64 n, hipStream_t stream) {
+    KCHECK(c.kmer_sum.alloc((n + 1) * 8, stream)); KCHECK(c.kmer_min.alloc((n + 1) * 4, stream)); KCHECK(c.kmer_max.alloc((n + 1) * 4, stream));
+    return KATOME_OK;
+}
 
 // degree words (in-degree low half, out-degree high half) and, per node, one incoming and one outgoing edge (the only
 // one where the degree is 1, which is all the walks ask for)
@@ -132,16 +139,21 @@ __global__ __launch_bounds__(BLOCK) void path_measure_kernel(const u32* __restri
     }
 }
 
-template <int NW>
+// COV: the walk also reads the weight of every edge it passes and leaves their sum, smallest and largest per merged edge (a cycle's
+// m edges once each); without it the kernel is the one it was
+template <int NW, bool COV>
 __global__ __launch_bounds__(BLOCK) void path_write_kernel(const u32* __restrict__ heads, u64 n_heads, const u64* __restrict__ src,
                                                            const u64* __restrict__ dst, const u32* __restrict__ weight, const u64* __restrict__ key,
                                                            const u64* __restrict__ word, const u32* __restrict__ path_len,
                                                            const u64* __restrict__ label_off, const u64* __restrict__ end_node,
                                                            const u32* __restrict__ new_id, u32 k, u64* __restrict__ o_src, u64* __restrict__ o_dst,
-                                                           u32* __restrict__ o_weight, uint8_t* __restrict__ o_label) {
+                                                           u32* __restrict__ o_weight, uint8_t* __restrict__ o_label, const CoverageOut cov) {
     for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n_heads; i += (u64)gridDim.x * BLOCK) {
         const u32 h = heads[i], m = path_len[i];
-        o_src[i] = new_id[src[h]]; o_dst[i] = new_id[end_node[i]]; o_weight[i] = weight[h];
+        o_src[i] = new_id[src[h]]; o_dst[i] = new_id[end_node[i]];
+        const u32 hw = weight[h];
+        o_weight[i] = hw;
+        u64 c_sum = hw; u32 c_min = hw, c_max = hw;      // (dead without COV)
         const u32 len = k + m - 1;
         uint8_t* out = o_label + label_off[i];
         *out++ = (uint8_t)((4 - len % 4) % 4);                   // compress_edge: padding byte first
@@ -158,9 +170,11 @@ __global__ __launch_bounds__(BLOCK) void path_write_kernel(const u32* __restrict
             const u64 w = word[cur];
             acc = (acc << 2) | (u32)(key[(u64)(u32)w * NW + NW - 1] & 3);
             if (++have == 4) { *out++ = (uint8_t)acc; acc = 0; have = 0; }
+            if constexpr (COV) { const u32 ew = weight[(u32)w]; c_sum += ew; c_min = min(c_min, ew); c_max = max(c_max, ew); }
             cur = w >> 32;
         }
         if (have) *out = (uint8_t)(acc << (2 * (4 - have)));     // left-aligned, zero padding in the low bits
+        if constexpr (COV) { cov.sum[i] = c_sum; cov.mn[i] = c_min; cov.mx[i] = c_max; }
     }
 }
 
@@ -181,16 +195,26 @@ __global__ __launch_bounds__(BLOCK) void age_keys_kernel(const u32* __restrict__
     for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) { keys[i] = age[i]; idx[i] = (u32)i; }
 }
 // per final edge: the original edges on its chain (= k-mers it spells), the bytes its label takes, its weight (its slot's: the first edge's)
+// (COV: and the sum, smallest and largest of the weights along the chain, whatever the traversal's cuts made of it)
+template <bool COV>
 __global__ __launch_bounds__(BLOCK) void chain_measure_kernel(const u32* __restrict__ slot, u64 n, const u32* __restrict__ chain_next,
                                                               const u32* __restrict__ weight, u32 k, u32* __restrict__ path_len,
-                                                              u32* __restrict__ label_bytes, u32* __restrict__ o_weight) {
+                                                              u32* __restrict__ label_bytes, u32* __restrict__ o_weight, const CoverageOut cov) {
     for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
         const u32 h = slot[i];
+        u32 hw = 0;
+        if constexpr (COV) hw = weight[h];                 // (without COV the weight is read where it always was: behind the walk)
+        u64 c_sum = hw; u32 c_min = hw, c_max = hw;
         u32 m = 1;
-        for (u32 c = chain_next[h]; c != NO_EDGE; c = chain_next[c]) ++m;
+        for (u32 c = chain_next[h]; c != NO_EDGE; c = chain_next[c]) {
+            ++m;
+            if constexpr (COV) { const u32 ew = weight[c]; c_sum += ew; c_min = min(c_min, ew); c_max = max(c_max, ew); }
+        }
         path_len[i] = m;
         label_bytes[i] = 1 + (k + m - 1 + 3) / 4;
-        o_weight[i] = weight[h];
+        if constexpr (!COV) hw = weight[h];
+        o_weight[i] = hw;
+        if constexpr (COV) { cov.sum[i] = c_sum; cov.mn[i] = c_min; cov.mx[i] = c_max; }
     }
 }
 template <int NW>
@@ -233,12 +257,13 @@ int compact(const u32* flag, u64 n, DevBuf& out_pos, u32* rank_of, u64* n_out, h
 
 }  // namespace
 
-int dev_shrink(const ShrinkInput& g, ShrinkOutput& out, hipStream_t stream) {
+int dev_shrink(const ShrinkInput& g, ShrinkOutput& out, hipStream_t stream, ShrinkCoverage* cov) {
     const u64 E = g.n_edges, N = g.n_nodes;
     const u32 nw = g.nw, k = g.k;
     out.n_edges = out.n_nodes = out.label_bytes = 0;
+    if (cov) cov->drop();
     if (E >= 0xFFFFFFFFull || N >= 0xFFFFFFFFull) { set_error("shrink: more than 2^32 edges or nodes on one GPU"); return KATOME_E_UNSUPPORTED; }
-    if (E == 0) return KATOME_OK;
+    if (E == 0) { if (cov) { KCHECK(coverage_alloc(*cov, 0, stream)); cov->valid = true; } return KATOME_OK; }
     DevBuf node_deg(stream), in_edge(stream), out_edge(stream), flag(stream), covered(stream), heads(stream);
     KCHECK(node_deg.alloc((N + 1) * 8)); KCHECK(in_edge.alloc((N + 1) * 4)); KCHECK(out_edge.alloc((N + 1) * 4));
     KCHECK(flag.alloc((std::max(E, N) + 1) * 4)); KCHECK(covered.alloc((E + 1) * 4));
@@ -274,14 +299,12 @@ int dev_shrink(const ShrinkInput& g, ShrinkOutput& out, hipStream_t stream) {
     KCHECK(out.edge_src.alloc((H + 1) * 8, stream)); KCHECK(out.edge_dst.alloc((H + 1) * 8, stream));
     KCHECK(out.edge_weight.alloc((H + 1) * 4, stream)); KCHECK(out.edge_label.alloc(total_bytes + 16, stream));
     KCHECK(out.node_key.alloc((NK + 1) * 8 * nw, stream));
-    if (nw == 1)
-        hipLaunchKernelGGL(path_write_kernel<1>, dim3(grid_for(H, BLOCK, 256u * 32u)), blk, 0, stream, heads.as<u32>(), H, g.edge_src, g.edge_dst,
-                           g.edge_weight, g.edge_key, word.as<u64>(), path_len.as<u32>(), label_off.as<u64>(), end_node.as<u64>(),
-                           new_id.as<u32>(), k, out.edge_src.as<u64>(), out.edge_dst.as<u64>(), out.edge_weight.as<u32>(), out.edge_label.as<uint8_t>());
-    else
-        hipLaunchKernelGGL(path_write_kernel<2>, dim3(grid_for(H, BLOCK, 256u * 32u)), blk, 0, stream, heads.as<u32>(), H, g.edge_src, g.edge_dst,
-                           g.edge_weight, g.edge_key, word.as<u64>(), path_len.as<u32>(), label_off.as<u64>(), end_node.as<u64>(),
-                           new_id.as<u32>(), k, out.edge_src.as<u64>(), out.edge_dst.as<u64>(), out.edge_weight.as<u32>(), out.edge_label.as<uint8_t>());
+    CoverageOut co{nullptr, nullptr, nullptr};
+    if (cov) { KCHECK(coverage_alloc(*cov, H, stream)); co = CoverageOut{cov->kmer_sum.as<u64>(), cov->kmer_min.as<u32>(), cov->kmer_max.as<u32>()}; }
+    auto write_kernel = nw == 1 ? (cov ? path_write_kernel<1, true> : path_write_kernel<1, false>) : (cov ? path_write_kernel<2, true> : path_write_kernel<2, false>);
+    hipLaunchKernelGGL(write_kernel, dim3(grid_for(H, BLOCK, 256u * 32u)), blk, 0, stream, heads.as<u32>(), H, g.edge_src, g.edge_dst,
+                       g.edge_weight, g.edge_key, word.as<u64>(), path_len.as<u32>(), label_off.as<u64>(), end_node.as<u64>(),
+                       new_id.as<u32>(), k, out.edge_src.as<u64>(), out.edge_dst.as<u64>(), out.edge_weight.as<u32>(), out.edge_label.as<uint8_t>(), co);
     if (NK) hipLaunchKernelGGL(gather_nodes_kernel, dim3(grid_for(NK, BLOCK, 256u * 32u)), blk, 0, stream, kept.as<u32>(), NK, g.node_key, nw,
                                out.node_key.as<u64>());
     KCHECK_HIP(hipGetLastError());
@@ -291,6 +314,7 @@ int dev_shrink(const ShrinkInput& g, ShrinkOutput& out, hipStream_t stream) {
     }
     KCHECK_HIP(hipStreamSynchronize(stream));
     out.n_edges = H; out.n_nodes = NK; out.label_bytes = total_bytes;
+    if (cov) { cov->n_edges = H; cov->valid = true; }
     return KATOME_OK;
 }
 
@@ -300,13 +324,14 @@ int dev_shrink(const ShrinkInput& g, ShrinkOutput& out, hipStream_t stream) {
 // weights, k-mer counts and compress_edge labels on the device again.  edge_age: the index every edge had when it was added (null:
 // the edges are still in that order).
 int dev_shrink_exact(const ShrinkInput& g, const uint32_t* edge_age, ShrinkOutput& out, double* host_ms, hipStream_t stream,
-                     ShrinkExact* keep, std::vector<uint32_t>* kept_out) {
+                     ShrinkExact* keep, std::vector<uint32_t>* kept_out, ShrinkCoverage* cov) {
     const u64 E = g.n_edges, N = g.n_nodes;
     const u32 nw = g.nw, k = g.k;
     out.n_edges = out.n_nodes = out.label_bytes = 0;
+    if (cov) cov->drop();
     if (host_ms) *host_ms = 0;
     if (E >= 0xFFFFFFFFull || N >= 0xFFFFFFFFull) { set_error("shrink: more than 2^32 edges or nodes on one GPU"); return KATOME_E_UNSUPPORTED; }
-    if (E == 0) return KATOME_OK;
+    if (E == 0) { if (cov) { KCHECK(coverage_alloc(*cov, 0, stream)); cov->valid = true; } return KATOME_OK; }
     const dim3 ge(grid_for(E, BLOCK, 256u * 32u)), blk(BLOCK);
     std::vector<uint32_t> h_src, h_dst, h_order;
     try { h_src.resize(E); h_dst.resize(E); if (edge_age) h_order.resize(E); }
@@ -355,11 +380,13 @@ int dev_shrink_exact(const ShrinkInput& g, const uint32_t* edge_age, ShrinkOutpu
     KCHECK(out.edge_weight.alloc((H + 1) * 4, stream)); KCHECK(out.node_key.alloc((NK + 1) * 8 * nw, stream));
     const dim3 gh(grid_for(std::max<u64>(H, 1), BLOCK, 256u * 32u));
     u64 total_bytes = 0;
+    CoverageOut co{nullptr, nullptr, nullptr};
+    if (cov) { KCHECK(coverage_alloc(*cov, H, stream)); co = CoverageOut{cov->kmer_sum.as<u64>(), cov->kmer_min.as<u32>(), cov->kmer_max.as<u32>()}; }
     if (H) {
         hipLaunchKernelGGL(widen_ids_kernel, gh, blk, 0, stream, s32.as<u32>(), H, out.edge_src.as<u64>());
         hipLaunchKernelGGL(widen_ids_kernel, gh, blk, 0, stream, d32.as<u32>(), H, out.edge_dst.as<u64>());
-        hipLaunchKernelGGL(chain_measure_kernel, gh, blk, 0, stream, slot.as<u32>(), H, chain.as<u32>(), g.edge_weight, k, path_len.as<u32>(),
-                           label_bytes.as<u32>(), out.edge_weight.as<u32>());
+        hipLaunchKernelGGL(cov ? chain_measure_kernel<true> : chain_measure_kernel<false>, gh, blk, 0, stream, slot.as<u32>(), H, chain.as<u32>(),
+                           g.edge_weight, k, path_len.as<u32>(), label_bytes.as<u32>(), out.edge_weight.as<u32>(), co);
         KCHECK_HIP(hipGetLastError());
         KCHECK(dev_scan_counts(label_bytes.as<u32>(), H, label_off.as<u64>(), stream));
         KCHECK_HIP(hipMemcpyAsync(&total_bytes, label_off.as<u64>() + H, 8, hipMemcpyDeviceToHost, stream));
@@ -383,6 +410,7 @@ int dev_shrink_exact(const ShrinkInput& g, const uint32_t* edge_age, ShrinkOutpu
     }
     KCHECK_HIP(hipStreamSynchronize(stream));
     out.n_edges = H; out.n_nodes = NK; out.label_bytes = total_bytes;
+    if (cov) { cov->n_edges = H; cov->valid = true; }
     return KATOME_OK;
 }
 

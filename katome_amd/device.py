@@ -98,9 +98,11 @@ class DeviceGraph:
 
 class DeviceContigs:
     """result of Builder.shrink(): merged edges with labels of any length (compress_edge format, edge i at
-    edge_label[edge_label_off[i]:edge_label_off[i+1]])"""
+    edge_label[edge_label_off[i]:edge_label_off[i+1]]).  After shrink(coverage=True) also kmer_sum (int64 view of u64), kmer_min and
+    kmer_max (int32 views of u32): per merged edge the sum, smallest and largest k-mer count of the input edges on its path.  The
+    library drops them at the builder's next shrink of any kind; from then on the attributes raise instead of handing out views"""
 
-    def __init__(self, dc, builder, device):
+    def __init__(self, dc, builder, device, cov=None):
         self.n_nodes, self.n_edges, self.label_bytes, self.key_words = dc.n_nodes, dc.n_edges, dc.label_bytes, dc.key_words
         ne, nn, nw = dc.n_edges, dc.n_nodes, dc.key_words
         self.edge_src = _view(dc.d_edge_src, (ne,), "<i8", builder, device)
@@ -111,6 +113,22 @@ class DeviceContigs:
         self.edge_label = _view(dc.d_edge_label, (dc.label_bytes,), "|u1", builder, device)
         self.node_key = _view(dc.d_node_key, (nn, nw), "<i8", builder, device)
         self._dc, self._builder = dc, builder
+        self.has_coverage = cov is not None
+        self._shrink_serial = getattr(builder, "_shrink_serial", 0)
+        if cov is not None:
+            self._cov = (_view(cov.d_kmer_sum, (ne,), "<i8", builder, device), _view(cov.d_kmer_min, (ne,), "<i4", builder, device),
+                         _view(cov.d_kmer_max, (ne,), "<i4", builder, device))
+
+    def _coverage(self, j):
+        if not self.has_coverage:
+            raise AttributeError("these contigs were shrunk without coverage: Builder.shrink(coverage=True)")
+        if self._shrink_serial != self._builder._shrink_serial:
+            raise ValueError("the builder has shrunk again since: this result's coverage was dropped")
+        return self._cov[j]
+
+    kmer_sum = property(lambda self: self._coverage(0))
+    kmer_min = property(lambda self: self._coverage(1))
+    kmer_max = property(lambda self: self._coverage(2))
 
     def sequences(self):
         """host: every merged edge decoded to its ACGT string (compress.rs:283-293 decompress_edge)"""
@@ -132,10 +150,22 @@ class DeviceContigs:
         _check(_lib.lib().katome_dev_contigs_text(self._builder._h, C.byref(self._dc), LAYOUTS[layout], C.byref(da), _stream()))
         return DeviceAssembly(da, self._builder, self._builder.tdev)
 
-    def gfa(self, merge_strands=False):
+    def gfa(self, merge_strands=False, coverage=False):
         """the shrunk graph as GFA 1, written on the device (katome_dev_contigs_gfa; include/katome_gpu.h has the format) ->
         DeviceGfa; valid for the builder's last shrink() only, and until the next gfa().  merge_strands: strand twins as one
-        segment with +/- links (katome_dev_contigs_gfa_strands) -> DeviceGfaStrands, valid until the next gfa(merge_strands=True)"""
+        segment with +/- links (katome_dev_contigs_gfa_strands) -> DeviceGfaStrands, valid until the next gfa(merge_strands=True).
+        coverage: KC is the sum of the path's k-mer counts and every S line ends in mn / mx (katome_dev_contigs_gfa_coverage);
+        needs contigs of shrink(coverage=True) and does not combine with merge_strands"""
+        if coverage:
+            if merge_strands:
+                raise ValueError("gfa: coverage=True does not combine with merge_strands=True (the bidirected writer has no coverage form)")
+            if not self.has_coverage:
+                raise ValueError("gfa: coverage=True needs the contigs of Builder.shrink(coverage=True)")
+            dg = _lib.DevGfa()
+            _check(_lib.lib().katome_dev_contigs_gfa_coverage(self._builder._h, C.byref(self._dc), C.byref(dg), _stream()))
+            return DeviceGfa(dg.n_segments, dg.n_links, dg.text_bytes, _view(dg.d_text, (dg.text_bytes,), "|u1", self._builder, self._builder.tdev),
+                             _view(dg.d_segment_off, (dg.n_segments,), "<i8", self._builder, self._builder.tdev),
+                             _view(dg.d_link_first, (dg.n_segments + 1,), "<i8", self._builder, self._builder.tdev))
         if merge_strands:
             d, b = _lib.DevGfaStrands(), self._builder
             _check(_lib.lib().katome_dev_contigs_gfa_strands(b._h, C.byref(self._dc), C.byref(d), _stream()))
@@ -425,13 +455,23 @@ class Builder(_ViewOwner):
         """Standardizable::standardize_edges (standardizer.rs:42-70): scale, round, remove_weak_edges(1)"""
         _check(_lib.lib().katome_dev_standardize_edges(self._h, original_genome_length, threshold, _stream()))
 
-    def shrink(self, mode=None):
+    _shrink_serial = 0
+
+    def shrink(self, mode=None, coverage=False):
         """Shrinkable::shrink (shrinker.rs:165-209) of the finalized graph as it stands -> DeviceContigs.  mode "exact": the
         reference's own cuts and numbering, index for index (its traversal order on one host core, the bytes on the device);
         "fast": traversal-free, all on the device, this library's numbering; None: exact on a first-seen-order builder.
-        `self.last_shrink_host_ms`: the sequential part of the last exact call"""
+        `self.last_shrink_host_ms`: the sequential part of the last exact call.  coverage: the result also has kmer_sum, kmer_min
+        and kmer_max per merged edge (katome_dev_shrink_coverage), accumulated by the same walk"""
         dc = _lib.DevContigs()
         host_ms = C.c_double(0)
+        self._shrink_serial += 1
+        if coverage:
+            cov = _lib.DevCoverage()
+            _check(_lib.lib().katome_dev_shrink_coverage(self._h, {None: 0, "auto": 0, "fast": 1, "exact": 2}[mode], C.byref(dc), C.byref(cov),
+                                                         C.byref(host_ms), _stream()))
+            self.last_shrink_host_ms = host_ms.value
+            return DeviceContigs(dc, self, self.tdev, cov)
         _check(_lib.lib().katome_dev_shrink_mode(self._h, {None: 0, "auto": 0, "fast": 1, "exact": 2}[mode], C.byref(dc), C.byref(host_ms),
                                                  _stream()))
         self.last_shrink_host_ms = host_ms.value
@@ -722,6 +762,27 @@ def gfa_arrays(k, n_nodes, edge_src, edge_dst, edge_weight, edge_kmers, edge_lab
     first = torch.empty(n_edges + 1, dtype=torch.int64, device=tdev)
     text = torch.empty(max(cap, 16), dtype=torch.uint8, device=tdev)
     _check(L.katome_dev_gfa_arrays(*args, _ptr(seg), _ptr(first), _ptr(text), cap, C.byref(nl), C.byref(nb), _stream()))
+    return DeviceGfa(n_edges, nl.value, nb.value, text[:nb.value], seg[:n_edges], first)
+
+
+def gfa_coverage_arrays(k, n_nodes, edge_src, edge_dst, edge_weight, edge_kmers, kmer_sum, kmer_min, kmer_max, edge_label_off, edge_label, device=0,
+                        label_bytes=None):
+    """gfa_arrays with the unitigs' coverage (katome_dev_gfa_coverage_arrays): kmer_sum int64, kmer_min / kmer_max int32 (the
+    u64 / u32 bits), one entry per edge -> DeviceGfa whose KC is kmer_sum and whose S lines end in mn / mx"""
+    tdev = edge_label_off.device
+    n_edges = edge_label_off.numel() - 1
+    if label_bytes is None:
+        label_bytes = edge_label.numel()
+    nl, nb = C.c_uint64(), C.c_uint64()
+    L = _lib.lib()
+    args = (device, k, n_nodes, n_edges, _ptr(edge_src), _ptr(edge_dst), _ptr(edge_weight), _ptr(edge_kmers), _ptr(kmer_sum), _ptr(kmer_min),
+            _ptr(kmer_max), _ptr(edge_label_off), _ptr(edge_label), label_bytes)
+    _check(L.katome_dev_gfa_coverage_arrays(*args, None, None, None, 0, C.byref(nl), C.byref(nb), _stream()))
+    cap = (nb.value + 15) // 16 * 16
+    seg = torch.empty(max(n_edges, 1), dtype=torch.int64, device=tdev)
+    first = torch.empty(n_edges + 1, dtype=torch.int64, device=tdev)
+    text = torch.empty(max(cap, 16), dtype=torch.uint8, device=tdev)
+    _check(L.katome_dev_gfa_coverage_arrays(*args, _ptr(seg), _ptr(first), _ptr(text), cap, C.byref(nl), C.byref(nb), _stream()))
     return DeviceGfa(n_edges, nl.value, nb.value, text[:nb.value], seg[:n_edges], first)
 
 

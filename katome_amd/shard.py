@@ -177,9 +177,11 @@ class RankContigs:
     """this rank's merged edges after ShardedBuilder.shrink() (zero-copy views of the builder's device arrays, valid until
     the next shrink or close): the paths whose head edge this rank holds, with NEW global node ids, and the surviving nodes
     it owns.  head_id: the head edge's global index in the input graph (petgraph index in the reference's numbering, the
-    rank's edge base + its local index by packed key).  stats: rank_rounds, cycle_rounds, cycles, longest_path, bytes_sent."""
+    rank's edge base + its local index by packed key).  stats: rank_rounds, cycle_rounds, cycles, longest_path, bytes_sent.
+    After shrink(coverage=True) also kmer_sum (int64 view of u64), kmer_min and kmer_max (int32 views of u32) per merged edge
+    (None otherwise); the next shrink of either kind drops them."""
 
-    def __init__(self, c, stats, owner, device):
+    def __init__(self, c, stats, owner, device, cov=None):
         ne, nn, nw = c.n_edges, c.n_nodes, c.key_words
         self.n_edges, self.n_nodes, self.total_edges, self.total_nodes = ne, nn, c.total_edges, c.total_nodes
         self.label_bytes, self.key_words = c.label_bytes, nw
@@ -193,6 +195,11 @@ class RankContigs:
         self.node_id = _view(c.d_node_id, (nn,), "<i8", owner, device)
         self.node_key = _view(c.d_node_key, (nn, nw), "<i8", owner, device)
         self.stats = {f: getattr(stats, f) for f, _ in _lib.DistShrinkStats._fields_}
+        self.kmer_sum = self.kmer_min = self.kmer_max = None
+        if cov is not None:
+            self.kmer_sum = _view(cov.d_kmer_sum, (ne,), "<i8", owner, device)
+            self.kmer_min = _view(cov.d_kmer_min, (ne,), "<i4", owner, device)
+            self.kmer_max = _view(cov.d_kmer_max, (ne,), "<i4", owner, device)
 
     sequences = DeviceContigs.sequences
 
@@ -356,10 +363,15 @@ class ShardedBuilder(_ViewOwner):
         _check(_lib.lib().katome_dist_standardize_edges(self._h, original_genome_length, threshold, C.byref(g), _stream()))
         return RankGraph(g, self, self.tdev)
 
-    def shrink(self):
+    def shrink(self, coverage=False):
         """Shrinkable::shrink in the traversal-free form (Builder.shrink(mode="fast")) on the sharded graph, no gather
-        (katome_dist_shrink) -> RankContigs; the rank's graph stays as it is"""
+        (katome_dist_shrink) -> RankContigs; the rank's graph stays as it is.  coverage: the result also has kmer_sum, kmer_min
+        and kmer_max per merged edge (katome_dist_shrink_coverage)"""
         c, st = _lib.DistContigs(), _lib.DistShrinkStats()
+        if coverage:
+            cov = _lib.DevCoverage()
+            _check(_lib.lib().katome_dist_shrink_coverage(self._h, C.byref(c), C.byref(cov), C.byref(st), _stream()))
+            return RankContigs(c, st, self, self.tdev, cov)
         _check(_lib.lib().katome_dist_shrink(self._h, C.byref(c), C.byref(st), _stream()))
         return RankContigs(c, st, self, self.tdev)
 
@@ -381,11 +393,13 @@ class ShardedBuilder(_ViewOwner):
         import os
         _check(_lib.lib().katome_dist_contigs_save(self._h, C.byref(assembly._a), os.fsencode(path)))
 
-    def contigs_gfa(self):
+    def contigs_gfa(self, coverage=False):
         """the unitig graph of the last shrink() as GFA 1, no gather: the links joined across ranks, this rank's S and L parts
-        written on the device (katome_dist_contigs_gfa) -> RankGfa.  Collective"""
+        written on the device (katome_dist_contigs_gfa) -> RankGfa.  coverage: KC is the sum of each unitig's k-mer counts and the
+        S lines end in mn / mx (katome_dist_contigs_gfa_coverage; needs shrink(coverage=True)).  Collective"""
         g = _lib.DistGfa()
-        _check(_lib.lib().katome_dist_contigs_gfa(self._h, C.byref(g), _stream()))
+        entry = _lib.lib().katome_dist_contigs_gfa_coverage if coverage else _lib.lib().katome_dist_contigs_gfa
+        _check(entry(self._h, C.byref(g), _stream()))
         return RankGfa(g, self, self.tdev)
 
     def save_gfa(self, gfa, path):
