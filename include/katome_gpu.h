@@ -502,7 +502,8 @@ typedef struct {
  * by the builder until its next katome_dev_collapse or destroy.  An edge of weight 0 (the reference's decrement would wrap):
  * KATOME_E_ARG.  2^31 pieces or more, or a contig of 2^32 bases or more: KATOME_E_UNSUPPORTED, with the number; pieces that do
  * not fit host memory: KATOME_E_OOM.  No edges: zero contigs, KATOME_OK.  `stats` may be NULL.  Profile phase "collapse",
- * kernel "k:text_write_kernel".  Synchronises.                                                                         */
+ * kernel "k:text_write_kernel".  Synchronises.  The device piece list (4 bytes per piece) and the shrunk graph it names stay
+ * in the builder until the next katome_dev_collapse or destroy: katome_dev_collapse_gfa below writes the contigs' paths from them. */
 int katome_dev_collapse(katome_builder *b, uint32_t layout, katome_dev_assembly *out, katome_collapse_stats *stats, void *stream);
 /* the text of a shrink result (fast or exact), one contig per merged edge, each its whole label: no piece list.  `contigs` is
  * what katome_dev_shrink / katome_dev_shrink_mode of this builder returned last.  Result owned by the builder until its next
@@ -586,6 +587,48 @@ typedef struct {
  * this call leaves that one's.                                                                                            */
 int katome_dev_contigs_gfa_strands(katome_builder *b, const katome_dev_contigs *contigs, katome_dev_gfa_strands *out, void *stream);
 
+/* ---- the GFA of the ASSEMBLY (csrc/gfa_paths.hip): collapse's contigs as P lines over the segments of its shrunk graph --------
+ * katome_dev_collapse's piece p names the shrunk edge appended at step p, and segment <i> of the GFA of that shrunk graph is that
+ * edge: a contig is a path over segments.  The text is, byte for byte, what katome_dev_contigs_gfa writes for the collapse's
+ * shrunk graph (H, the S lines in index order, the L lines), followed by the path region:
+ *   P\tkatome_<c>\t<s0>+,<s1>+,...,<sn>+\t*\n            run 0 of contig c
+ *   P\tkatome_<c>.<r>\t<s..>+,...\t*\n                    run r = 1, 2, ... of contig c
+ * <c> is the contig's number (katome_<c> is its FASTA header), <s> a piece's shrunk edge index in decimal; every orientation is +
+ * (the collapse runs on the two-strand graph) and the overlap column is * (the L lines carry <k-1>M).  Contigs in order, the runs
+ * of a contig in order.  A contig is not always one path: when contigs_from_vertex takes a simple loop (collapser.rs:181-193) it
+ * appends the entering edge b->c, the return edge c->b and continues from c, so the next piece does not start where the last one
+ * ended and the two have no L line.  Piece p therefore starts a run iff it has KATOME_PIECE_WHOLE or
+ * edge_dst[id(p - 1)] != edge_src[id(p)] (a jump), and n_paths = n_contigs + n_jumps.  Inside a P line every consecutive pair is
+ * an L line.  Concatenated in order (the first run's first piece whole, every other piece of every run from base k-1 on), the runs
+ * of contig c spell the text katome_dev_collapse writes for contig c.  No pieces: an empty region.
+ * On the device the path region starts at d_path_text = d_text + text_bytes rounded up to 16, with zeros behind each part up to
+ * its multiple of 16 (the two-part convention of katome_dist_gfa); in host memory and in the file the two parts are contiguous.
+ * d_path_line_off[j] = offset of path j's line in the path region ([n_paths] = path_bytes), d_path_contig[j] = its contig,
+ * d_path_first_piece[j] = its first piece ([n_paths] = n_pieces).
+ * Validated on the device before anything is read through the values, each KATOME_E_ARG with a message: a piece id >= n_edges, a
+ * first piece without KATOME_PIECE_WHOLE, n_pieces >= 2^31.  Scratch: at most 28 bytes per piece while the sizes are made, 16 of
+ * them while the text is written, 24 bytes per path and 8 per contig.  Profile phase "gfa_paths", kernel
+ * "k:gfa_paths_write_kernel".  Synchronises.
+ * Out of scope: the coverage form of the S lines, the bidirected form (katome_dev_contigs_gfa_strands) with paths, and anything
+ * on the sharded graph -- collapse needs the gathered graph.                                                               */
+typedef struct {
+    uint64_t  n_segments, n_links, text_bytes;
+    uint8_t  *d_text;
+    uint64_t *d_segment_off;             /* [n_segments]                                                               */
+    uint64_t *d_link_first;              /* [n_segments + 1]                                                           */
+    uint64_t  n_paths, n_jumps, path_bytes;
+    uint8_t  *d_path_text;               /* d_text + text_bytes rounded up to 16                                       */
+    uint64_t *d_path_line_off;           /* [n_paths + 1]                                                              */
+    uint64_t *d_path_contig;             /* [n_paths]                                                                  */
+    uint64_t *d_path_first_piece;        /* [n_paths + 1]                                                              */
+} katome_dev_gfa_paths;
+/* the whole text for the builder's LAST katome_dev_collapse (either layout), which keeps its device piece list in the builder
+ * until the next collapse or destroy for this call: 4 bytes per piece.  No collapse result (none yet, or the last one failed):
+ * KATOME_E_ARG, "collapse_gfa: no collapse result".  The result has its own buffers, owned by the builder until its next
+ * katome_dev_collapse_gfa or destroy: the results of katome_dev_contigs_gfa, katome_dev_contigs_gfa_strands and
+ * katome_dev_collapse stay valid, and the builder's graph is untouched.                                                   */
+int katome_dev_collapse_gfa(katome_builder *b, katome_dev_gfa_paths *out, void *stream);
+
 /* Contigs::stats (stats/contigs.rs:31-89) from the contigs' lengths: host, pure.  No contigs: all zeros.  A tipping point of 0
  * with contigs present (sum / 2, (0.1 * sum) truncated, original_genome_length / 2), where the reference panics on
  * `.last().unwrap()`: KATOME_E_ARG, with a message that names which one.                                               */
@@ -660,6 +703,36 @@ int  katome_gfa_strands_packed(const katome_settings *s, const uint8_t *packed, 
                                katome_gfa_strands **out);
 int  katome_gfa_strands_save(const katome_gfa_strands *g, const char *path);
 void katome_gfa_strands_free(katome_gfa_strands *g);
+
+/* katome_assemble_* followed by katome_dev_collapse_gfa: the assembly (FASTA) and the GFA of its shrunk graph with the contigs as
+ * P lines, from one build.  text[0, text_bytes) holds the H, S and L lines and text[text_bytes, text_bytes + path_bytes) the P
+ * lines, contiguous: text_bytes + path_bytes bytes are the file.  segment_off / link_first as in katome_dev_gfa; path_line_off
+ * (relative to the path region), path_contig and path_first_piece as in katome_dev_gfa_paths.  Owned by the library until
+ * katome_gfa_paths_free.  fasta_path, gfa_path, asm_out and gfa_out are each nullable (all four NULL: KATOME_E_ARG).
+ * Preconditions and statuses are katome_assemble_*'s: KATOME_FLAG_FIRST_SEEN_ORDER is required; a path that cannot be created
+ * gives KATOME_E_OPEN, "couldn't create <path>: <why>", with both results still handed back (the FASTA path is tried first; the
+ * first failure is the one reported, the other file is still written); with settings.n_devices > 1 the graph is built sharded
+ * and gathered to the first GPU.                                                                                          */
+typedef struct {
+    uint64_t n_segments, n_links, text_bytes, read_bytes;
+    uint32_t k, _pad;
+    const uint8_t  *text;                /* text_bytes + path_bytes                                                    */
+    const uint64_t *segment_off;         /* [n_segments]                                                               */
+    const uint64_t *link_first;          /* [n_segments + 1]                                                           */
+    uint64_t n_paths, n_jumps, path_bytes;
+    const uint64_t *path_line_off;       /* [n_paths + 1]                                                              */
+    const uint64_t *path_contig;         /* [n_paths]                                                                  */
+    const uint64_t *path_first_piece;    /* [n_paths + 1]                                                              */
+} katome_gfa_paths;
+int  katome_assemble_gfa_files(const katome_settings *s, const char *const *paths, size_t n_paths, uint64_t original_genome_length,
+                               const char *fasta_path /* nullable */, const char *gfa_path /* nullable */,
+                               katome_assembly **asm_out /* nullable */, katome_gfa_paths **gfa_out /* nullable */);
+int  katome_assemble_gfa_packed(const katome_settings *s, const uint8_t *packed, uint64_t n_reads, uint32_t read_len,
+                                const uint8_t *skip, uint64_t original_genome_length, const char *fasta_path /* nullable */,
+                                const char *gfa_path /* nullable */, katome_assembly **asm_out /* nullable */,
+                                katome_gfa_paths **gfa_out /* nullable */);
+int  katome_gfa_paths_save(const katome_gfa_paths *g, const char *path);
+void katome_gfa_paths_free(katome_gfa_paths *g);
 
 /* first half of finalize only: sorted distinct edges (key, weight); used by the multi-GPU
  * driver, which resolves node ids across ranks itself                                      */
@@ -1124,6 +1197,17 @@ int katome_dev_gfa_strands_arrays(int device, uint32_t k, uint64_t n_nodes, uint
                                   const uint64_t *d_edge_label_off, const uint8_t *d_edge_label, uint64_t label_bytes,
                                   uint64_t *d_segment_name, uint64_t *d_segment_off, uint64_t *d_link_first, uint64_t *d_edge_twin,
                                   uint8_t *d_text, uint64_t text_cap, uint64_t *counts, void *stream);
+/* the path region of katome_dev_collapse_gfa alone, on the caller's arrays: n_pieces pieces (see katome_dev_collapse) over a graph
+ * of n_edges edges, of which only d_edge_src and d_edge_dst are read.  counts[3] = {n_paths, n_jumps, text_bytes} are always set
+ * (zeros on an error).  d_text NULL: nothing else is written (a size query).  Otherwise d_path_line_off and d_path_first_piece
+ * need room for path_cap + 1 entries, d_path_contig for path_cap, with path_cap >= n_paths, and d_text, 16-byte aligned, for
+ * text_cap >= text_bytes rounded up to 16 (zeros behind the text up to that multiple): KATOME_E_ARG when either is too small.
+ * Validation as for katome_dev_collapse_gfa.  KATOME_GFA_PATHS_TRACE=1 in the environment: the writing kernel's time on stderr.
+ * Synchronises. */
+int katome_dev_gfa_paths_arrays(int device, uint64_t n_edges, const uint64_t *d_edge_src, const uint64_t *d_edge_dst,
+                                const uint32_t *d_pieces, uint64_t n_pieces, uint64_t *d_path_line_off /* [n_paths + 1] */,
+                                uint64_t *d_path_contig /* [n_paths] */, uint64_t *d_path_first_piece /* [n_paths + 1] */,
+                                uint64_t path_cap, uint8_t *d_text, uint64_t text_cap, uint64_t *counts /* [3] */, void *stream);
 /* the GFA writer on a numbered PART of a text whose other parts are written elsewhere (katome_dist_contigs_gfa): segment i is named
  * first_segment + i (up to 20 digits), its links are d_link_b[d_link_first[i] .. d_link_first[i + 1]) -- global numbers, n_links =
  * d_link_first[n_edges] --, the header line is written or not.  d_text holds the S part (the header first) at 0 and the L part

@@ -217,6 +217,46 @@ class GfaStrands(Gfa):
             pass
 
 
+class GfaPaths(Gfa):
+    """the GFA half of GpuGraph.assemble_gfa: the collapse's shrunk graph as H, S and L lines (text[:text_bytes], segment_off,
+    link_first as in Gfa) and its contigs as P lines (path_text = text[text_bytes:], path_bytes of them): path j is the line at
+    path_line_off[j] of path_text, a run of contig path_contig[j] whose first piece is piece path_first_piece[j]; n_jumps = n_paths
+    - n_contigs.  `text` is the whole file"""
+
+    def __init__(self, gp):
+        self._gp = gp
+        g = gp.contents
+        ns, nb, npaths = g.n_segments, g.text_bytes, g.n_paths
+        self.k, self.read_bytes, self.n_segments, self.n_links, self.text_bytes = g.k, g.read_bytes, ns, g.n_links, nb
+        self.n_paths, self.n_jumps, self.path_bytes = npaths, g.n_jumps, g.path_bytes
+        self.text = bytes(np.ctypeslib.as_array(g.text, (nb + g.path_bytes,))) if nb + g.path_bytes else b""
+        self.path_text = self.text[nb:]
+        self.segment_off = np.ctypeslib.as_array(g.segment_off, (ns,)).copy() if ns else np.zeros(0, np.uint64)
+        self.link_first = np.ctypeslib.as_array(g.link_first, (ns + 1,)).copy()
+        self.path_line_off = np.ctypeslib.as_array(g.path_line_off, (npaths + 1,)).copy()
+        self.path_contig = np.ctypeslib.as_array(g.path_contig, (npaths,)).copy() if npaths else np.zeros(0, np.uint64)
+        self.path_first_piece = np.ctypeslib.as_array(g.path_first_piece, (npaths + 1,)).copy()
+
+    def save_to_file(self, path):
+        _check(_lib.lib().katome_gfa_paths_save(self._gp, os.fsencode(path)))
+
+    def __del__(self):
+        try:
+            _lib.lib().katome_gfa_paths_free(self._gp)
+        except Exception:       # interpreter shutdown
+            pass
+
+
+def _assemble_gfa_result(rc, ap, gp):
+    """-> (Assembly, GfaPaths); a path that could not be created: both were made all the same, and travel with the exception (`.result`)"""
+    result = (Assembly(ap) if ap else None, GfaPaths(gp) if gp else None)
+    if rc != 0:
+        err = KatomePanic(rc, _lib.last_error())
+        err.result = result
+        raise err
+    return result
+
+
 def _gfa_result(rc, gp, cls=Gfa):
     """a path that could not be created: the GFA was made all the same, and travels with the exception (`.result`)"""
     if rc != 0:
@@ -403,6 +443,39 @@ class GpuGraph:
                 _lib.lib().katome_assembly_free(ap)
             _check(rc)
         return Assembly(ap)
+
+    # ---- the assembly and its GFA: the contigs as P lines over the unitigs -------------------------------
+    @staticmethod
+    def assemble_gfa(input_files, ft, reverse_complement, minimal_weight_threshold, original_genome_length, fasta_file=None, gfa_file=None,
+                     device=0, n_devices=1, ranks_share_device=False):
+        """assemble() and, from the same collapse, the GFA of its shrunk graph with every contig as P lines over the segments (one
+        line per run of properly linked pieces; katome_assemble_gfa_files) -> (Assembly, GfaPaths); fasta_file / gfa_file: the
+        two files; uses the global k"""
+        s = make_settings(K_SIZE, ft, reverse_complement, minimal_weight_threshold, device, first_seen_order=True, n_devices=n_devices,
+                          ranks_share_device=ranks_share_device)
+        ap, gp = C.POINTER(_lib.Assembly)(), C.POINTER(_lib.GfaPaths)()
+        enc = lambda f: os.fsencode(f) if f is not None else None
+        rc = _lib.lib().katome_assemble_gfa_files(C.byref(s), _paths(input_files), len(input_files), original_genome_length, enc(fasta_file),
+                                                  enc(gfa_file), C.byref(ap), C.byref(gp))
+        return _assemble_gfa_result(rc, ap, gp)
+
+    @staticmethod
+    def assemble_gfa_from_packed(packed, n_reads, read_len, skip=None, reverse_complement=False, minimal_weight_threshold=0,
+                                 original_genome_length=0, fasta_file=None, gfa_file=None, device=0, k=None, n_devices=1,
+                                 ranks_share_device=False):
+        """the same from 2-bit packed reads (numpy uint8; katome_assemble_gfa_packed)"""
+        s = make_settings(K_SIZE if k is None else k, InputFileType.Fastq, reverse_complement, minimal_weight_threshold, device,
+                          first_seen_order=True, n_devices=n_devices, ranks_share_device=ranks_share_device)
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        skip_p = None
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.uint8)
+            skip_p = skip.ctypes.data
+        ap, gp = C.POINTER(_lib.Assembly)(), C.POINTER(_lib.GfaPaths)()
+        enc = lambda f: os.fsencode(f) if f is not None else None
+        rc = _lib.lib().katome_assemble_gfa_packed(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, original_genome_length,
+                                                   enc(fasta_file), enc(gfa_file), C.byref(ap), C.byref(gp))
+        return _assemble_gfa_result(rc, ap, gp)
 
     # ---- the unitig graph as GFA 1 ---------------------------------------------------------------
     @staticmethod

@@ -860,10 +860,13 @@ int builder_collapse(katome_builder* b, uint32_t layout, katome_dev_assembly* ou
     if (!b->finalized) { set_error("collapse: call katome_dev_finalize first"); return KATOME_E_ARG; }
     ShrinkInput in{b->edge_src.as<u64>(), b->edge_dst.as<u64>(), b->edge_weight.as<u32>(), b->edge_key.as<u64>(), b->node_key.as<u64>(),
                    b->n_edges, b->n_nodes, b->nw, b->s.k};
+    b->collapse_valid = false; b->collapse_pieces.release(); b->collapse_n_pieces = 0;
     {
         PhaseScope ps(b->prof, PH_COLLAPSE, stream);
-        KCHECK(dev_collapse(in, b->edge_age.p ? b->edge_age.as<u32>() : nullptr, b->collapse_shrunk, layout, b->assembly, stats, lengths, stream));
+        KCHECK(dev_collapse(in, b->edge_age.p ? b->edge_age.as<u32>() : nullptr, b->collapse_shrunk, layout, b->assembly, stats, lengths, stream,
+                            &b->collapse_pieces, &b->collapse_n_pieces));
     }
+    b->collapse_valid = true;          // (no edges: no pieces, and a text of the header line alone)
     if (out) assembly_view(b->assembly, out);
     return KATOME_OK;
 }

@@ -113,6 +113,10 @@ struct katome_builder {
     ShrinkCoverage shrunk_cov;         // ... and, after katome_dev_shrink_coverage only, its k-mer count sum / min / max (any other shrink drops them)
     ShrinkOutput collapse_shrunk;      // katome_dev_collapse: the shrunk graph its pieces name ...
     TextOutput assembly;               // ... and its result
+    DevBuf collapse_pieces;            // ... and its piece list (4 bytes a piece), kept for katome_dev_collapse_gfa until the next collapse
+    uint64_t collapse_n_pieces = 0;
+    bool collapse_valid = false;       // the three above belong to one successful katome_dev_collapse
+    GfaPathsOutput gfa_paths;          // result of katome_dev_collapse_gfa (its own buffers)
     TextOutput unitig_text;            // result of katome_dev_contigs_text
     GfaOutput gfa;                     // result of katome_dev_contigs_gfa
     GfaStrandsOutput gfa_strands;      // result of katome_dev_contigs_gfa_strands (its own buffers: neither call touches the other's result)

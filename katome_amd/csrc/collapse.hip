@@ -254,7 +254,7 @@ int dev_pieces_text(uint32_t k, const uint8_t* label, const uint64_t* label_off,
 // collapse() of the graph `g`: the exact shrink (its result stays in `shrunk`: the pieces name its edges), the walk on the host, the
 // text on the device.  lengths (optional): every contig's bases, known on the host after the walk from the shrunk edges' k-mer counts
 int dev_collapse(const ShrinkInput& g, const uint32_t* edge_age, ShrinkOutput& shrunk, uint32_t layout, TextOutput& out,
-                 katome_collapse_stats* stats, std::vector<uint64_t>* lengths, hipStream_t stream) {
+                 katome_collapse_stats* stats, std::vector<uint64_t>* lengths, hipStream_t stream, DevBuf* keep_pieces, uint64_t* n_pieces) {
     katome_collapse_stats st;
     memset(&st, 0, sizeof st);
     out.n_contigs = out.text_bytes = 0; out.layout = layout;
@@ -313,6 +313,8 @@ int dev_collapse(const ShrinkInput& g, const uint32_t* edge_age, ShrinkOutput& s
     KCHECK(dev_pieces_text(g.k, shrunk.edge_label.as<uint8_t>(), shrunk.edge_label_off.as<u64>(), H, d_pieces.as<u32>(), P, layout, 0, out, stream));
     st.text_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
     if (out.n_contigs != walk.n_contigs) { set_error("collapse: the device counted %llu contigs, the walk %llu", (unsigned long long)out.n_contigs, (unsigned long long)walk.n_contigs); return KATOME_E_DEVICE; }
+    if (keep_pieces) { keep_pieces->stream = stream; keep_pieces->adopt(d_pieces); }
+    if (n_pieces) *n_pieces = P;
     if (stats) *stats = st;
     return KATOME_OK;
 }

@@ -105,6 +105,7 @@ enum Phase { PH_EXTRACT, PH_REGION_ORDER, PH_INSERT, PH_EMIT_EDGES, PH_SORT_EDGE
              PH_COLLAPSE, K_TEXT_WRITE,
              PH_GFA, K_GFA_SORT, K_GFA_SIZES, K_GFA_WRITE,
              PH_GFA_STRANDS, K_GFAS_KEYS, K_GFAS_SEARCH, K_GFAS_VERIFY, K_GFAS_LINKS, K_GFAS_SIZES, K_GFAS_WRITE,
+             PH_GFA_PATHS, K_GFA_PATHS_WRITE,
              PH_COUNT };
 static const char* const PHASE_NAMES[PH_COUNT] = {
     "extract", "region_order", "insert", "emit_edges", "sort_edges", "node_set", "rank", "labels", "insert_tiles", "expand_tiles",
@@ -122,7 +123,8 @@ static const char* const PHASE_NAMES[PH_COUNT] = {
     "graph_stats", "weight_spectrum", "k:stats_degree_kernel", "k:stats_weight_kernel", "k:stats_node_kernel", "k:spectrum_kernel",
     "collapse", "k:text_write_kernel",
     "gfa", "k:gfa link sort", "k:gfa sizes", "k:gfa_write_kernel",
-    "gfa_strands", "k:gfa_strands keys+sort", "k:strand_search_kernel", "k:strand_verify_kernel", "k:gfa_strands links", "k:gfa_strands sizes", "k:gfa_strands_write_kernel"};
+    "gfa_strands", "k:gfa_strands keys+sort", "k:strand_search_kernel", "k:strand_verify_kernel", "k:gfa_strands links", "k:gfa_strands sizes", "k:gfa_strands_write_kernel",
+    "gfa_paths", "k:gfa_paths_write_kernel"};
 struct Profiler {
     bool on = false;
     struct Ev { int phase; hipEvent_t a, b; uint64_t work; };      // work: elements the launch processed (K_* entries)
@@ -451,8 +453,10 @@ int dev_text_write(uint32_t k, const uint8_t* label, const uint64_t* label_off, 
                    uint64_t first_contig, const TextPlan& plan, uint64_t* contig_off, uint32_t* contig_len, uint8_t* text, hipStream_t stream);
 int dev_pieces_text(uint32_t k, const uint8_t* label, const uint64_t* label_off, uint64_t n_labels, const uint32_t* pieces, uint64_t n_pieces,
                     uint32_t layout, uint64_t first_contig, TextOutput& out, hipStream_t stream);
+// (keep_pieces, optional: the device piece list, n_pieces u32, is handed over instead of freed -- katome_dev_collapse_gfa reads it)
 int dev_collapse(const ShrinkInput& g, const uint32_t* edge_age, ShrinkOutput& shrunk, uint32_t layout, TextOutput& out,
-                 katome_collapse_stats* stats, std::vector<uint64_t>* lengths, hipStream_t stream);
+                 katome_collapse_stats* stats, std::vector<uint64_t>* lengths, hipStream_t stream, DevBuf* keep_pieces = nullptr,
+                 uint64_t* n_pieces = nullptr);
 
 // gfa.hip: a shrink result as GFA 1 (include/katome_gpu.h has the format): the join of every edge into a vertex with every edge out
 // of it, the records' sizes and the text, partitioned by output bytes
@@ -517,6 +521,23 @@ int dev_gfa_strands_plan(const GfaGraph& g, GfaStrandsPlan& plan, hipStream_t st
 // text: plan.text_bytes rounded up to 16; segment_name: n_segments entries; edge_twin: n_edges entries
 int dev_gfa_strands_write(const GfaGraph& g, const GfaStrandsPlan& plan, uint8_t* text, uint64_t* segment_name, uint64_t* edge_twin, hipStream_t stream);
 int dev_gfa_strands(const GfaGraph& g, GfaStrandsOutput& out, hipStream_t stream);
+// gfa_paths.hip: collapse's contigs as P lines over the segments of the shrunk graph's GFA (include/katome_gpu.h has the format): one
+// line per run of properly linked pieces.  The plan: every piece's path (path_idx, the exclusive scan of the run flags: a piece
+// starts a run where path_idx[p + 1] != path_idx[p]) and byte offset (piece_off), one entry more than pieces each; every contig's
+// first path; and what the caller gets: every path's line offset and first piece (one entry more than paths) and its contig
+struct GfaPathsPlan {
+    DevBuf path_idx, piece_off, contig_first_path, path_line_off, path_contig, path_first_piece;
+    uint64_t n_paths = 0, n_contigs = 0, text_bytes = 0;
+};
+// the whole text: H, S and L lines at 0 (text_bytes), the P lines at text_bytes rounded up to 16 (path_bytes), zeros behind each part
+struct GfaPathsOutput {
+    DevBuf text, segment_off, link_first, path_line_off, path_contig, path_first_piece;
+    uint64_t n_segments = 0, n_links = 0, text_bytes = 0, n_paths = 0, n_jumps = 0, path_bytes = 0;
+};
+// validates (an id below n_edges, a first piece that begins a contig, fewer than 2^31 pieces: KATOME_E_ARG), flags, scans; synchronises
+int dev_gfa_paths_plan(uint64_t n_edges, const uint64_t* edge_src, const uint64_t* edge_dst, const uint32_t* pieces, uint64_t n_pieces, GfaPathsPlan& plan,
+                       hipStream_t stream);
+int dev_gfa_paths_write(const uint32_t* pieces, uint64_t n_pieces, const GfaPathsPlan& plan, uint8_t* text, hipStream_t stream);   // text: plan.text_bytes rounded up to 16
 
 // Contigs::stats' panic sites as a status (contig_stats.h's 1, 2, 3: which tipping point is 0), one message wherever the stats are made
 inline int contig_stats_status(int which) {

@@ -203,6 +203,23 @@ class DeviceGfaStrands(DeviceGfa):
         self.segment_name, self.edge_twin, self.n_unpaired, self.n_self_twins = segment_name, edge_twin, n_unpaired, n_self_twins
 
 
+class DeviceGfaPaths(DeviceGfa):
+    """the GFA of an assembly in HBM (katome_dev_collapse_gfa): text / segment_off / link_first as in DeviceGfa for the collapse's
+    shrunk graph, then the contigs as P lines in path_text (uint8, path_bytes of them; on the device it starts at text_bytes
+    rounded up to 16).  Path j is the line at path_line_off[j] of path_text, a run of contig path_contig[j] whose first piece is
+    piece path_first_piece[j]; n_jumps = n_paths - n_contigs: the seams inside contigs that no L line covers"""
+
+    def __init__(self, n_segments, n_links, text_bytes, text, segment_off, link_first, n_paths, n_jumps, path_bytes, path_text, path_line_off,
+                 path_contig, path_first_piece):
+        super().__init__(n_segments, n_links, text_bytes, text, segment_off, link_first)
+        self.n_paths, self.n_jumps, self.path_bytes, self.path_text = n_paths, n_jumps, path_bytes, path_text
+        self.path_line_off, self.path_contig, self.path_first_piece = path_line_off, path_contig, path_first_piece
+
+    def bytes(self):
+        """host: the file's bytes, the two parts back to back"""
+        return bytes(self.text.cpu().numpy()) + bytes(self.path_text.cpu().numpy())
+
+
 LAYOUTS = {"plain": 0, "fasta": 1}
 
 
@@ -487,6 +504,17 @@ class Builder(_ViewOwner):
         self.last_collapse_host_ms = st.host_ms
         return DeviceAssembly(da, self, self.tdev, stats)
 
+    def collapse_gfa(self):
+        """the GFA of the last collapse(): its shrunk graph as H, S and L lines and its contigs as P lines over those segments, one
+        line per run of properly linked pieces (katome_dev_collapse_gfa; include/katome_gpu.h has the format) -> DeviceGfaPaths,
+        valid until the next collapse_gfa() or close().  The results of collapse() and of gfa() stay valid"""
+        d = _lib.DevGfaPaths()
+        _check(_lib.lib().katome_dev_collapse_gfa(self._h, C.byref(d), _stream()))
+        v = lambda p, n: _view(p, (n,), "<i8", self, self.tdev)
+        return DeviceGfaPaths(d.n_segments, d.n_links, d.text_bytes, _view(d.d_text, (d.text_bytes,), "|u1", self, self.tdev), v(d.d_segment_off, d.n_segments),
+                              v(d.d_link_first, d.n_segments + 1), d.n_paths, d.n_jumps, d.path_bytes, _view(d.d_path_text, (d.path_bytes,), "|u1", self, self.tdev),
+                              v(d.d_path_line_off, d.n_paths + 1), v(d.d_path_contig, d.n_paths), v(d.d_path_first_piece, d.n_paths + 1))
+
     def graph(self):
         """the finalized graph as it stands (after remove_dead_paths / remove_weak_edges)"""
         dg = _lib.DevGraph()
@@ -763,6 +791,24 @@ def gfa_arrays(k, n_nodes, edge_src, edge_dst, edge_weight, edge_kmers, edge_lab
     text = torch.empty(max(cap, 16), dtype=torch.uint8, device=tdev)
     _check(L.katome_dev_gfa_arrays(*args, _ptr(seg), _ptr(first), _ptr(text), cap, C.byref(nl), C.byref(nb), _stream()))
     return DeviceGfa(n_edges, nl.value, nb.value, text[:nb.value], seg[:n_edges], first)
+
+
+def gfa_paths_arrays(edge_src, edge_dst, pieces, device=0):
+    """the path kernels on the caller's tensors (katome_dev_gfa_paths_arrays): edge_src / edge_dst int64 (the shrunk graph the pieces
+    name), pieces int32/uint32 (edge index, bit 31 on a piece that begins a contig) -> (path_text uint8 of text_bytes rounded up to
+    16, {n_paths, n_jumps, text_bytes}, path_line_off, path_contig, path_first_piece)"""
+    tdev = pieces.device
+    counts = (C.c_uint64 * 3)()
+    L = _lib.lib()
+    args = (device, edge_src.numel(), _ptr(edge_src), _ptr(edge_dst), _ptr(pieces), pieces.numel())
+    _check(L.katome_dev_gfa_paths_arrays(*args, None, None, None, 0, None, 0, counts, _stream()))
+    n_paths, cap = counts[0], (counts[2] + 15) // 16 * 16
+    line_off = torch.empty(n_paths + 1, dtype=torch.int64, device=tdev)
+    contig = torch.empty(max(n_paths, 1), dtype=torch.int64, device=tdev)
+    first = torch.empty(n_paths + 1, dtype=torch.int64, device=tdev)
+    text = torch.empty(max(cap, 16), dtype=torch.uint8, device=tdev)
+    _check(L.katome_dev_gfa_paths_arrays(*args, _ptr(line_off), _ptr(contig), _ptr(first), n_paths, _ptr(text), cap, counts, _stream()))
+    return text, dict(n_paths=counts[0], n_jumps=counts[1], text_bytes=counts[2]), line_off, contig[:n_paths], first
 
 
 def gfa_coverage_arrays(k, n_nodes, edge_src, edge_dst, edge_weight, edge_kmers, kmer_sum, kmer_min, kmer_max, edge_label_off, edge_label, device=0,
