@@ -609,8 +609,8 @@ int katome_dev_contigs_gfa_strands(katome_builder *b, const katome_dev_contigs *
  * first piece without KATOME_PIECE_WHOLE, n_pieces >= 2^31.  Scratch: at most 28 bytes per piece while the sizes are made, 16 of
  * them while the text is written, 24 bytes per path and 8 per contig.  Profile phase "gfa_paths", kernel
  * "k:gfa_paths_write_kernel".  Synchronises.
- * Out of scope: the coverage form of the S lines, the bidirected form (katome_dev_contigs_gfa_strands) with paths, and anything
- * on the sharded graph -- collapse needs the gathered graph.                                                               */
+ * Out of scope: the coverage form of the S lines and anything on the sharded graph -- collapse needs the gathered graph.  The
+ * bidirected form with paths is katome_dev_collapse_gfa_strands below.                                                     */
 typedef struct {
     uint64_t  n_segments, n_links, text_bytes;
     uint8_t  *d_text;
@@ -628,6 +628,53 @@ typedef struct {
  * katome_dev_collapse_gfa or destroy: the results of katome_dev_contigs_gfa, katome_dev_contigs_gfa_strands and
  * katome_dev_collapse stay valid, and the builder's graph is untouched.                                                   */
 int katome_dev_collapse_gfa(katome_builder *b, katome_dev_gfa_paths *out, void *stream);
+
+/* ---- the BIDIRECTED GFA of the assembly (csrc/gfa_strand_paths.hip): the contigs as P lines over MERGED segments, and mirrors ----
+ * katome_dev_collapse_gfa writes its paths over the two-strand graph, so a reverse_complement assembly reaches a viewer as two
+ * disconnected mirror images.  Here the text is, byte for byte, what katome_dev_contigs_gfa_strands writes for the collapse's shrunk
+ * graph (H, one S line per representative, the canonical L lines), followed at text_bytes rounded up to 16 by the path region:
+ *   P\tkatome_<c>\t<r0><o0>,<r1><o1>,...,<rn><on>\t*\n   run 0 of contig c
+ *   P\tkatome_<c>.<r>\t...\t*\n                           run r = 1, 2, ... of contig c
+ * For a piece with shrunk edge i, <r> = rep(i) and <o> = o(i) exactly as katome_dev_contigs_gfa_strands defines them: rep =
+ * min(i, twin i), or i without a twin; '-' only where twin(i) < i; a self-twin and an unpaired edge are '+'.
+ * Runs: names, contig order and the run rule are katome_dev_collapse_gfa's, evaluated on the TWO-STRAND arrays (a piece starts a
+ * run iff it has KATOME_PIECE_WHOLE or edge_dst[id(p - 1)] != edge_src[id(p)]).  Merging cannot heal a seam: the conjugate of a
+ * pair (x, y) is (twin y, twin x), and that pair is adjacent only if x and y were.  So n_paths, n_jumps, d_path_contig and
+ * d_path_first_piece EQUAL katome_dev_collapse_gfa's for the same collapse; only the bytes and d_path_line_off differ.
+ * Inside a P line every consecutive pair (x ox),(y oy) is an L line of the merged text, either as written or in its conjugate
+ * spelling (y, flip oy, x, flip ox), where flip leaves a self-twin at +.
+ * Mirrors.  Collapse walks both strands, so most contigs come twice.  For path j with piece ids a_0 .. a_{n-1}, mirror(j) = the
+ * smallest q with n_q == n and id_q[t] == twin(a_{n-1-t}) for every t; an edge without a twin matches nothing; no such q: all ones.
+ * mirror(j) == j is a self-mirror (the path [a, twin a]).  d_path_mirror[j] = mirror(j); n_mirrored = the paths that have one,
+ * n_self_mirror = those that are their own.  The text does not change with it (optional fields on P lines are not something every
+ * reader accepts): the array lets a caller keep one path per molecule, those with no mirror or mirror(j) >= j.
+ * Validated on the device before anything is read through a value, each KATOME_E_ARG with a message: katome_dev_collapse_gfa's
+ * piece checks, and on the arrays entry, where the caller supplies the twin map, a twin entry that is neither all ones nor below
+ * n_edges and twin(twin(i)) != i.  Scratch beyond katome_dev_contigs_gfa_strands' and katome_dev_collapse_gfa's: 4 bytes per piece
+ * (the oriented names) and about 50 bytes per path while the mirrors are found.  Profile phase
+ * "gfa_strand_paths", kernel "k:gfa_strand_paths_write_kernel".  Synchronises.
+ * Out of scope: the coverage form of merged S lines, folding mirror paths out of the text, and anything on the sharded graph.   */
+typedef struct {
+    uint64_t  n_segments, n_links, text_bytes, n_unpaired, n_self_twins;
+    uint8_t  *d_text;
+    uint64_t *d_segment_name;            /* [n_segments]                                                               */
+    uint64_t *d_segment_off;             /* [n_segments]                                                               */
+    uint64_t *d_link_first;              /* [n_segments + 1]                                                           */
+    uint64_t *d_edge_twin;               /* [n_edges]                                                                  */
+    uint64_t  n_paths, n_jumps, path_bytes;
+    uint8_t  *d_path_text;               /* d_text + text_bytes rounded up to 16                                       */
+    uint64_t *d_path_line_off;           /* [n_paths + 1]                                                              */
+    uint64_t *d_path_contig;             /* [n_paths]                                                                  */
+    uint64_t *d_path_first_piece;        /* [n_paths + 1]                                                              */
+    uint64_t  n_mirrored, n_self_mirror;
+    uint64_t *d_path_mirror;             /* [n_paths], all ones: none                                                  */
+    uint64_t  n_edges;                   /* merged edges of the collapse's shrunk graph (both strands)                 */
+} katome_dev_gfa_strand_paths;
+/* the whole text for the builder's LAST katome_dev_collapse, as katome_dev_collapse_gfa.  No collapse result: KATOME_E_ARG,
+ * "collapse_gfa_strands: no collapse result".  The result has its own buffers, owned by the builder until its next
+ * katome_dev_collapse_gfa_strands or destroy: the results of katome_dev_collapse, katome_dev_collapse_gfa, katome_dev_contigs_gfa
+ * and katome_dev_contigs_gfa_strands stay valid, and the builder's graph is untouched.                                      */
+int katome_dev_collapse_gfa_strands(katome_builder *b, katome_dev_gfa_strand_paths *out, void *stream);
 
 /* Contigs::stats (stats/contigs.rs:31-89) from the contigs' lengths: host, pure.  No contigs: all zeros.  A tipping point of 0
  * with contigs present (sum / 2, (0.1 * sum) truncated, original_genome_length / 2), where the reference panics on
@@ -733,6 +780,36 @@ int  katome_assemble_gfa_packed(const katome_settings *s, const uint8_t *packed,
                                 katome_gfa_paths **gfa_out /* nullable */);
 int  katome_gfa_paths_save(const katome_gfa_paths *g, const char *path);
 void katome_gfa_paths_free(katome_gfa_paths *g);
+/* the same with strand twins merged: katome_assemble_* followed by katome_dev_collapse_gfa_strands (which has the format).  The
+ * fields of katome_gfa_strands, then those of katome_gfa_paths, then the mirrors; text[0, text_bytes) holds the H, S and L lines
+ * and text[text_bytes, text_bytes + path_bytes) the P lines.  Arguments, nullable files and results, KATOME_E_OPEN with the results
+ * still handed back and n_devices > 1 (built sharded, gathered to the first GPU) exactly as katome_assemble_gfa_*.  Owned by the
+ * library until katome_gfa_strand_paths_free.                                                                               */
+typedef struct {
+    uint64_t n_segments, n_links, text_bytes, read_bytes;
+    uint32_t k, _pad;
+    const uint8_t  *text;                /* text_bytes + path_bytes                                                    */
+    const uint64_t *segment_off;         /* [n_segments]                                                               */
+    const uint64_t *link_first;          /* [n_segments + 1]                                                           */
+    uint64_t n_edges, n_unpaired, n_self_twins;
+    const uint64_t *segment_name;        /* [n_segments]                                                               */
+    const uint64_t *edge_twin;           /* [n_edges], all ones: none                                                  */
+    uint64_t n_paths, n_jumps, path_bytes;
+    const uint64_t *path_line_off;       /* [n_paths + 1]                                                              */
+    const uint64_t *path_contig;         /* [n_paths]                                                                  */
+    const uint64_t *path_first_piece;    /* [n_paths + 1]                                                              */
+    uint64_t n_mirrored, n_self_mirror;
+    const uint64_t *path_mirror;         /* [n_paths], all ones: none                                                  */
+} katome_gfa_strand_paths;
+int  katome_assemble_gfa_strands_files(const katome_settings *s, const char *const *paths, size_t n_paths, uint64_t original_genome_length,
+                                       const char *fasta_path /* nullable */, const char *gfa_path /* nullable */,
+                                       katome_assembly **asm_out /* nullable */, katome_gfa_strand_paths **gfa_out /* nullable */);
+int  katome_assemble_gfa_strands_packed(const katome_settings *s, const uint8_t *packed, uint64_t n_reads, uint32_t read_len,
+                                        const uint8_t *skip, uint64_t original_genome_length, const char *fasta_path /* nullable */,
+                                        const char *gfa_path /* nullable */, katome_assembly **asm_out /* nullable */,
+                                        katome_gfa_strand_paths **gfa_out /* nullable */);
+int  katome_gfa_strand_paths_save(const katome_gfa_strand_paths *g, const char *path);
+void katome_gfa_strand_paths_free(katome_gfa_strand_paths *g);
 
 /* first half of finalize only: sorted distinct edges (key, weight); used by the multi-GPU
  * driver, which resolves node ids across ranks itself                                      */
@@ -1208,6 +1285,19 @@ int katome_dev_gfa_paths_arrays(int device, uint64_t n_edges, const uint64_t *d_
                                 const uint32_t *d_pieces, uint64_t n_pieces, uint64_t *d_path_line_off /* [n_paths + 1] */,
                                 uint64_t *d_path_contig /* [n_paths] */, uint64_t *d_path_first_piece /* [n_paths + 1] */,
                                 uint64_t path_cap, uint8_t *d_text, uint64_t text_cap, uint64_t *counts /* [3] */, void *stream);
+/* the path region of katome_dev_collapse_gfa_strands and d_path_mirror alone, on the caller's arrays: katome_dev_gfa_paths_arrays
+ * with the twin map d_edge_twin (n_edges entries as katome_dev_gfa_strands.d_edge_twin gives them: all ones for none) behind
+ * d_edge_dst and d_path_mirror (path_cap entries) behind d_path_first_piece.  counts[5] = {n_paths, n_jumps, text_bytes,
+ * n_mirrored, n_self_mirror} are always set (zeros on an error); d_text NULL: a size query.  The twin map is validated on the
+ * device first: an entry that is neither all ones nor below n_edges, or twin(twin(i)) != i: KATOME_E_ARG, each with its message;
+ * then the pieces as for katome_dev_gfa_paths_arrays.  2^32 - 1 edges or more: KATOME_E_UNSUPPORTED.
+ * KATOME_GFA_STRAND_PATHS_TRACE=1 in the environment: the times of the writer and of the mirror search's parts on stderr.
+ * Synchronises. */
+int katome_dev_gfa_strand_paths_arrays(int device, uint64_t n_edges, const uint64_t *d_edge_src, const uint64_t *d_edge_dst,
+                                       const uint64_t *d_edge_twin, const uint32_t *d_pieces, uint64_t n_pieces,
+                                       uint64_t *d_path_line_off /* [n_paths + 1] */, uint64_t *d_path_contig /* [n_paths] */,
+                                       uint64_t *d_path_first_piece /* [n_paths + 1] */, uint64_t *d_path_mirror /* [n_paths] */,
+                                       uint64_t path_cap, uint8_t *d_text, uint64_t text_cap, uint64_t *counts /* [5] */, void *stream);
 /* the GFA writer on a numbered PART of a text whose other parts are written elsewhere (katome_dist_contigs_gfa): segment i is named
  * first_segment + i (up to 20 digits), its links are d_link_b[d_link_first[i] .. d_link_first[i + 1]) -- global numbers, n_links =
  * d_link_first[n_edges] --, the header line is written or not.  d_text holds the S part (the header first) at 0 and the L part

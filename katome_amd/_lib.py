@@ -121,6 +121,24 @@ class GfaPaths(C.Structure):
                 ("path_contig", u64p), ("path_first_piece", u64p)]
 
 
+class DevGfaStrandPaths(C.Structure):
+    _fields_ = [("n_segments", C.c_uint64), ("n_links", C.c_uint64), ("text_bytes", C.c_uint64), ("n_unpaired", C.c_uint64),
+                ("n_self_twins", C.c_uint64), ("d_text", C.c_void_p), ("d_segment_name", C.c_void_p), ("d_segment_off", C.c_void_p),
+                ("d_link_first", C.c_void_p), ("d_edge_twin", C.c_void_p), ("n_paths", C.c_uint64), ("n_jumps", C.c_uint64),
+                ("path_bytes", C.c_uint64), ("d_path_text", C.c_void_p), ("d_path_line_off", C.c_void_p), ("d_path_contig", C.c_void_p),
+                ("d_path_first_piece", C.c_void_p), ("n_mirrored", C.c_uint64), ("n_self_mirror", C.c_uint64), ("d_path_mirror", C.c_void_p),
+                ("n_edges", C.c_uint64)]
+
+
+class GfaStrandPaths(C.Structure):
+    _fields_ = [("n_segments", C.c_uint64), ("n_links", C.c_uint64), ("text_bytes", C.c_uint64), ("read_bytes", C.c_uint64),
+                ("k", C.c_uint32), ("_pad", C.c_uint32), ("text", u8p), ("segment_off", u64p), ("link_first", u64p),
+                ("n_edges", C.c_uint64), ("n_unpaired", C.c_uint64), ("n_self_twins", C.c_uint64), ("segment_name", u64p),
+                ("edge_twin", u64p), ("n_paths", C.c_uint64), ("n_jumps", C.c_uint64), ("path_bytes", C.c_uint64), ("path_line_off", u64p),
+                ("path_contig", u64p), ("path_first_piece", u64p), ("n_mirrored", C.c_uint64), ("n_self_mirror", C.c_uint64),
+                ("path_mirror", u64p)]
+
+
 class DevGraph(C.Structure):
     _fields_ = [("n_nodes", C.c_uint64), ("n_edges", C.c_uint64), ("key_words", C.c_uint32),
                 ("label_stride", C.c_uint32), ("d_edge_key", C.c_void_p), ("d_edge_weight", C.c_void_p),
@@ -276,6 +294,14 @@ SYMBOLS = {
                                    C.POINTER(C.POINTER(GfaPaths))]),
     "katome_gfa_paths_save": (_i, [C.POINTER(GfaPaths), C.c_char_p]),
     "katome_gfa_paths_free": (None, [C.POINTER(GfaPaths)]),
+    "katome_dev_collapse_gfa_strands": (_i, [_vp, C.POINTER(DevGfaStrandPaths), _vp]),
+    "katome_dev_gfa_strand_paths_arrays": (_i, [_i, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _u64, u64p, _vp]),
+    "katome_assemble_gfa_strands_files": (_i, [C.POINTER(Settings), _pp, _sz, _u64, C.c_char_p, C.c_char_p, C.POINTER(C.POINTER(Assembly)),
+                                          C.POINTER(C.POINTER(GfaStrandPaths))]),
+    "katome_assemble_gfa_strands_packed": (_i, [C.POINTER(Settings), _vp, _u64, _u32, _vp, _u64, C.c_char_p, C.c_char_p,
+                                           C.POINTER(C.POINTER(Assembly)), C.POINTER(C.POINTER(GfaStrandPaths))]),
+    "katome_gfa_strand_paths_save": (_i, [C.POINTER(GfaStrandPaths), C.c_char_p]),
+    "katome_gfa_strand_paths_free": (None, [C.POINTER(GfaStrandPaths)]),
     "katome_contig_stats_of": (_i, [u64p, _u64, _u64, C.POINTER(ContigStats)]),
     "katome_assemble_files": (_i, [C.POINTER(Settings), _pp, _sz, _u64, C.c_char_p, C.POINTER(C.POINTER(Assembly))]),
     "katome_assemble_packed": (_i, [C.POINTER(Settings), _vp, _u64, _u32, _vp, _u64, C.c_char_p, C.POINTER(C.POINTER(Assembly))]),

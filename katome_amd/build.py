@@ -247,9 +247,38 @@ class GfaPaths(Gfa):
             pass
 
 
-def _assemble_gfa_result(rc, ap, gp):
+class GfaStrandPaths(GfaPaths):
+    """the GFA half of GpuGraph.assemble_gfa(merge_strands=True): the collapse's shrunk graph with strand twins merged (the fields
+    of GfaStrands) and its contigs as P lines over the merged segments (the fields of GfaPaths; a piece reads <rep><o>).
+    path_mirror[j]: the smallest path that spells the same molecule from its other end (2^64 - 1: none); n_mirrored paths have
+    one, n_self_mirror are their own"""
+
+    def __init__(self, gp):
+        super().__init__(gp)
+        g = gp.contents
+        self.n_edges, self.n_unpaired, self.n_self_twins = g.n_edges, g.n_unpaired, g.n_self_twins
+        self.segment_name = np.ctypeslib.as_array(g.segment_name, (g.n_segments,)).copy() if g.n_segments else np.zeros(0, np.uint64)
+        self.edge_twin = np.ctypeslib.as_array(g.edge_twin, (g.n_edges,)).copy() if g.n_edges else np.zeros(0, np.uint64)
+        self.n_mirrored, self.n_self_mirror = g.n_mirrored, g.n_self_mirror
+        self.path_mirror = np.ctypeslib.as_array(g.path_mirror, (g.n_paths,)).copy() if g.n_paths else np.zeros(0, np.uint64)
+
+    def unique_paths(self):
+        """the indices j with no mirror or mirror(j) >= j: one path per molecule"""
+        return [j for j, q in enumerate(self.path_mirror.tolist()) if q == 2 ** 64 - 1 or q >= j]
+
+    def save_to_file(self, path):
+        _check(_lib.lib().katome_gfa_strand_paths_save(self._gp, os.fsencode(path)))
+
+    def __del__(self):
+        try:
+            _lib.lib().katome_gfa_strand_paths_free(self._gp)
+        except Exception:       # interpreter shutdown
+            pass
+
+
+def _assemble_gfa_result(rc, ap, gp, cls=GfaPaths):
     """-> (Assembly, GfaPaths); a path that could not be created: both were made all the same, and travel with the exception (`.result`)"""
-    result = (Assembly(ap) if ap else None, GfaPaths(gp) if gp else None)
+    result = (Assembly(ap) if ap else None, cls(gp) if gp else None)
     if rc != 0:
         err = KatomePanic(rc, _lib.last_error())
         err.result = result
@@ -447,14 +476,20 @@ class GpuGraph:
     # ---- the assembly and its GFA: the contigs as P lines over the unitigs -------------------------------
     @staticmethod
     def assemble_gfa(input_files, ft, reverse_complement, minimal_weight_threshold, original_genome_length, fasta_file=None, gfa_file=None,
-                     device=0, n_devices=1, ranks_share_device=False):
+                     device=0, n_devices=1, ranks_share_device=False, merge_strands=False):
         """assemble() and, from the same collapse, the GFA of its shrunk graph with every contig as P lines over the segments (one
         line per run of properly linked pieces; katome_assemble_gfa_files) -> (Assembly, GfaPaths); fasta_file / gfa_file: the
-        two files; uses the global k"""
+        two files; uses the global k.  merge_strands: strand twins as one segment, +/- in links and paths, and every path's mirror
+        (katome_assemble_gfa_strands_files) -> (Assembly, GfaStrandPaths)"""
         s = make_settings(K_SIZE, ft, reverse_complement, minimal_weight_threshold, device, first_seen_order=True, n_devices=n_devices,
                           ranks_share_device=ranks_share_device)
-        ap, gp = C.POINTER(_lib.Assembly)(), C.POINTER(_lib.GfaPaths)()
         enc = lambda f: os.fsencode(f) if f is not None else None
+        if merge_strands:
+            ap, gp = C.POINTER(_lib.Assembly)(), C.POINTER(_lib.GfaStrandPaths)()
+            rc = _lib.lib().katome_assemble_gfa_strands_files(C.byref(s), _paths(input_files), len(input_files), original_genome_length,
+                                                              enc(fasta_file), enc(gfa_file), C.byref(ap), C.byref(gp))
+            return _assemble_gfa_result(rc, ap, gp, GfaStrandPaths)
+        ap, gp = C.POINTER(_lib.Assembly)(), C.POINTER(_lib.GfaPaths)()
         rc = _lib.lib().katome_assemble_gfa_files(C.byref(s), _paths(input_files), len(input_files), original_genome_length, enc(fasta_file),
                                                   enc(gfa_file), C.byref(ap), C.byref(gp))
         return _assemble_gfa_result(rc, ap, gp)
@@ -462,8 +497,8 @@ class GpuGraph:
     @staticmethod
     def assemble_gfa_from_packed(packed, n_reads, read_len, skip=None, reverse_complement=False, minimal_weight_threshold=0,
                                  original_genome_length=0, fasta_file=None, gfa_file=None, device=0, k=None, n_devices=1,
-                                 ranks_share_device=False):
-        """the same from 2-bit packed reads (numpy uint8; katome_assemble_gfa_packed)"""
+                                 ranks_share_device=False, merge_strands=False):
+        """the same from 2-bit packed reads (numpy uint8; katome_assemble_gfa_packed, katome_assemble_gfa_strands_packed)"""
         s = make_settings(K_SIZE if k is None else k, InputFileType.Fastq, reverse_complement, minimal_weight_threshold, device,
                           first_seen_order=True, n_devices=n_devices, ranks_share_device=ranks_share_device)
         packed = np.ascontiguousarray(packed, dtype=np.uint8)
@@ -471,8 +506,13 @@ class GpuGraph:
         if skip is not None:
             skip = np.ascontiguousarray(skip, dtype=np.uint8)
             skip_p = skip.ctypes.data
-        ap, gp = C.POINTER(_lib.Assembly)(), C.POINTER(_lib.GfaPaths)()
         enc = lambda f: os.fsencode(f) if f is not None else None
+        if merge_strands:
+            ap, gp = C.POINTER(_lib.Assembly)(), C.POINTER(_lib.GfaStrandPaths)()
+            rc = _lib.lib().katome_assemble_gfa_strands_packed(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, original_genome_length,
+                                                               enc(fasta_file), enc(gfa_file), C.byref(ap), C.byref(gp))
+            return _assemble_gfa_result(rc, ap, gp, GfaStrandPaths)
+        ap, gp = C.POINTER(_lib.Assembly)(), C.POINTER(_lib.GfaPaths)()
         rc = _lib.lib().katome_assemble_gfa_packed(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, original_genome_length,
                                                    enc(fasta_file), enc(gfa_file), C.byref(ap), C.byref(gp))
         return _assemble_gfa_result(rc, ap, gp)

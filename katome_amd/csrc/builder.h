@@ -117,6 +117,7 @@ struct katome_builder {
     uint64_t collapse_n_pieces = 0;
     bool collapse_valid = false;       // the three above belong to one successful katome_dev_collapse
     GfaPathsOutput gfa_paths;          // result of katome_dev_collapse_gfa (its own buffers)
+    GfaStrandPathsOutput gfa_strand_paths;      // result of katome_dev_collapse_gfa_strands (its own buffers)
     TextOutput unitig_text;            // result of katome_dev_contigs_text
     GfaOutput gfa;                     // result of katome_dev_contigs_gfa
     GfaStrandsOutput gfa_strands;      // result of katome_dev_contigs_gfa_strands (its own buffers: neither call touches the other's result)

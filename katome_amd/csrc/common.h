@@ -106,6 +106,7 @@ enum Phase { PH_EXTRACT, PH_REGION_ORDER, PH_INSERT, PH_EMIT_EDGES, PH_SORT_EDGE
              PH_GFA, K_GFA_SORT, K_GFA_SIZES, K_GFA_WRITE,
              PH_GFA_STRANDS, K_GFAS_KEYS, K_GFAS_SEARCH, K_GFAS_VERIFY, K_GFAS_LINKS, K_GFAS_SIZES, K_GFAS_WRITE,
              PH_GFA_PATHS, K_GFA_PATHS_WRITE,
+             PH_GFA_STRAND_PATHS, K_GFASP_WRITE, K_GFASP_SIGS, K_GFASP_SORT, K_GFASP_SEARCH, K_GFASP_VERIFY,
              PH_COUNT };
 static const char* const PHASE_NAMES[PH_COUNT] = {
     "extract", "region_order", "insert", "emit_edges", "sort_edges", "node_set", "rank", "labels", "insert_tiles", "expand_tiles",
@@ -124,7 +125,8 @@ static const char* const PHASE_NAMES[PH_COUNT] = {
     "collapse", "k:text_write_kernel",
     "gfa", "k:gfa link sort", "k:gfa sizes", "k:gfa_write_kernel",
     "gfa_strands", "k:gfa_strands keys+sort", "k:strand_search_kernel", "k:strand_verify_kernel", "k:gfa_strands links", "k:gfa_strands sizes", "k:gfa_strands_write_kernel",
-    "gfa_paths", "k:gfa_paths_write_kernel"};
+    "gfa_paths", "k:gfa_paths_write_kernel",
+    "gfa_strand_paths", "k:gfa_strand_paths_write_kernel", "k:mirror_sig_kernel", "k:mirror signature sort", "k:mirror_search_kernel", "k:mirror_verify_kernel"};
 struct Profiler {
     bool on = false;
     struct Ev { int phase; hipEvent_t a, b; uint64_t work; };      // work: elements the launch processed (K_* entries)
@@ -537,7 +539,29 @@ struct GfaPathsOutput {
 // validates (an id below n_edges, a first piece that begins a contig, fewer than 2^31 pieces: KATOME_E_ARG), flags, scans; synchronises
 int dev_gfa_paths_plan(uint64_t n_edges, const uint64_t* edge_src, const uint64_t* edge_dst, const uint32_t* pieces, uint64_t n_pieces, GfaPathsPlan& plan,
                        hipStream_t stream);
+// its two halves, for a writer with sizes of its own (gfa_strand_paths.hip): the checks and the run structure (everything of the plan
+// but piece_off, path_line_off and text_bytes; *size: room for a u32 per piece), then those three from every piece's bytes
+int dev_gfa_paths_runs(uint64_t n_edges, const uint64_t* edge_src, const uint64_t* edge_dst, const uint32_t* pieces, uint64_t n_pieces, GfaPathsPlan& plan,
+                       DevBuf& size, hipStream_t stream);
+int dev_gfa_paths_offsets(uint64_t n_pieces, const uint32_t* size, GfaPathsPlan& plan, hipStream_t stream);
 int dev_gfa_paths_write(const uint32_t* pieces, uint64_t n_pieces, const GfaPathsPlan& plan, uint8_t* text, hipStream_t stream);   // text: plan.text_bytes rounded up to 16
+// gfa_strand_paths.hip: the same paths over the MERGED segments of gfa_strands.hip (piece i reads <rep i><o i>), and every path's mirror:
+// the smallest path that spells the same double-stranded molecule from its other end (all-ones: none).  twin: n_edges u32, NO_TWIN = none
+struct GfaStrandPathsPlan {
+    GfaPathsPlan runs;                 // 11e's run structure with THIS text's piece_off / path_line_off / text_bytes
+    DevBuf oname;                      // every piece's oriented name: rep << 1 | (o == '-')
+    DevBuf mirror;                     // [n_paths] u64
+    uint64_t n_mirrored = 0, n_self_mirror = 0;
+};
+struct GfaStrandPathsOutput {
+    DevBuf text, segment_name, segment_off, link_first, edge_twin, path_line_off, path_contig, path_first_piece, path_mirror;
+    uint64_t n_segments = 0, n_links = 0, text_bytes = 0, n_unpaired = 0, n_self_twins = 0, n_paths = 0, n_jumps = 0, path_bytes = 0, n_mirrored = 0,
+             n_self_mirror = 0;
+};
+// validates the pieces (dev_gfa_paths_runs), names, measures, finds the mirrors; synchronises.  twin is trusted: an involution below n_edges
+int dev_gfa_strand_paths_plan(uint64_t n_edges, const uint64_t* edge_src, const uint64_t* edge_dst, const uint32_t* twin, const uint32_t* pieces,
+                              uint64_t n_pieces, GfaStrandPathsPlan& plan, hipStream_t stream);
+int dev_gfa_strand_paths_write(uint64_t n_pieces, const GfaStrandPathsPlan& plan, uint8_t* text, hipStream_t stream);   // text: runs.text_bytes rounded up to 16
 
 // Contigs::stats' panic sites as a status (contig_stats.h's 1, 2, 3: which tipping point is 0), one message wherever the stats are made
 inline int contig_stats_status(int which) {

@@ -18,17 +18,12 @@
 //   consecutive bytes of the image with one 128-bit store.  Neither a thread per piece nor one per path touches global memory: one
 //   path can be 10^6 pieces and the next 10^6 paths one piece each.
 #include "builder.h"
-#include "gfa_image.h"
-#include "text_bases.h"
+#include "gfa_path_lines.h"
 
 namespace katome {
 namespace {
 
 constexpr u32 WHOLE = KATOME_PIECE_WHOLE;
-constexpr u32 PIECE_MIN = 3;                               // "0+,": the shortest piece
-constexpr int PIECE_MAX = 9 + 10 + 1 + 10 + 1 + 10 + 4;    // "P\tkatome_<c>.<r>\t<id>+\t*\n" with c, r, id < 2^31: far below a tile
-constexpr u32 MAX_PIECES = TILE / PIECE_MIN + 2;           // pieces that can overlap one tile
-static_assert(PIECE_MAX < (int)TILE && MAX_PIECES < 65536, "a piece fits a tile; a tile's pieces are counted in 32 bits with room to spare");
 enum { ERR_PIECE = 1, ERR_FIRST = 2 };
 
 // piece p: checked, then run[p] = it starts a run, whole[p] = it starts a contig
@@ -62,9 +57,6 @@ __global__ __launch_bounds__(BLOCK) void path_fill_kernel(const u32* __restrict_
         if (pieces[p] >> 31) contig_first_path[c] = path;
     }
 }
-
-// the bytes of "P\tkatome_<c>[.<r>]\t"
-__device__ __forceinline__ u32 run_head_bytes(u64 c, u64 r) { return 9 + decimal_digits(c) + (r ? 1 + decimal_digits(r) : 0) + 1; }
 
 __global__ __launch_bounds__(BLOCK) void path_size_kernel(const u32* __restrict__ pieces, u64 P, const u64* __restrict__ path_idx, const u64* __restrict__ path_contig,
                                                           const u64* __restrict__ contig_first_path, u32* __restrict__ size) {
@@ -124,8 +116,8 @@ __global__ __launch_bounds__(BLOCK) void gfa_paths_write_kernel(const u32* __res
 
 }  // namespace
 
-int dev_gfa_paths_plan(uint64_t n_edges, const uint64_t* edge_src, const uint64_t* edge_dst, const uint32_t* pieces, uint64_t n_pieces, GfaPathsPlan& plan,
-                       hipStream_t stream) {
+int dev_gfa_paths_runs(uint64_t n_edges, const uint64_t* edge_src, const uint64_t* edge_dst, const uint32_t* pieces, uint64_t n_pieces, GfaPathsPlan& plan,
+                       DevBuf& run, hipStream_t stream) {
     plan.n_paths = plan.n_contigs = plan.text_bytes = 0;
     const u64 P = n_pieces, E = n_edges;
     if (P >= 0x80000000ull) { set_error("gfa_paths: %llu pieces, at most 2^31 - 1", (unsigned long long)P); return KATOME_E_ARG; }
@@ -138,7 +130,8 @@ int dev_gfa_paths_plan(uint64_t n_edges, const uint64_t* edge_src, const uint64_
     }
     if (!pieces || (E && (!edge_src || !edge_dst))) { set_error("null argument"); return KATOME_E_ARG; }
     const dim3 grid(grid_for(P, BLOCK, 256u * 32u)), blk(BLOCK);
-    DevBuf run(stream), whole(stream), contig_idx(stream), tail(stream);
+    DevBuf whole(stream), contig_idx(stream), tail(stream);
+    run.stream = stream;
     KCHECK(run.alloc(P * 4)); KCHECK(whole.alloc(P * 4)); KCHECK(tail.alloc(16));
     KCHECK(plan.path_idx.alloc((P + 1) * 8)); KCHECK(contig_idx.alloc((P + 1) * 8));
     KCHECK_HIP(hipMemsetAsync(tail.p, 0, 16, stream));
@@ -160,16 +153,34 @@ int dev_gfa_paths_plan(uint64_t n_edges, const uint64_t* edge_src, const uint64_
     KCHECK(plan.contig_first_path.alloc(n_contigs * 8)); KCHECK(plan.piece_off.alloc((P + 1) * 8));
     hipLaunchKernelGGL(path_fill_kernel, grid, blk, 0, stream, pieces, P, plan.path_idx.as<u64>(), contig_idx.as<u64>(), plan.path_contig.as<u64>(),
                        plan.path_first_piece.as<u64>(), plan.contig_first_path.as<u64>());
-    hipLaunchKernelGGL(path_size_kernel, grid, blk, 0, stream, pieces, P, plan.path_idx.as<u64>(), plan.path_contig.as<u64>(), plan.contig_first_path.as<u64>(),
-                       run.as<u32>());
     KCHECK_HIP(hipGetLastError());
-    KCHECK(dev_scan_counts(run.as<u32>(), P, plan.piece_off.as<u64>(), stream));
-    hipLaunchKernelGGL(path_line_off_kernel, grid, blk, 0, stream, P, plan.path_idx.as<u64>(), plan.piece_off.as<u64>(), plan.path_line_off.as<u64>());
+    KCHECK_HIP(hipStreamSynchronize(stream));                           // (contig_idx is freed on return)
+    plan.n_paths = n_paths; plan.n_contigs = n_contigs;
+    return KATOME_OK;
+}
+
+// size: every piece's bytes -> piece_off, path_line_off, text_bytes (no pieces: dev_gfa_paths_runs has left the empty region)
+int dev_gfa_paths_offsets(uint64_t n_pieces, const uint32_t* size, GfaPathsPlan& plan, hipStream_t stream) {
+    const u64 P = n_pieces;
+    if (P == 0) return KATOME_OK;
+    KCHECK(dev_scan_counts(size, P, plan.piece_off.as<u64>(), stream));
+    hipLaunchKernelGGL(path_line_off_kernel, dim3(grid_for(P, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, P, plan.path_idx.as<u64>(), plan.piece_off.as<u64>(),
+                       plan.path_line_off.as<u64>());
     KCHECK_HIP(hipGetLastError());
     KCHECK_HIP(hipMemcpyAsync(&plan.text_bytes, plan.piece_off.as<u64>() + P, 8, hipMemcpyDeviceToHost, stream));
     KCHECK_HIP(hipStreamSynchronize(stream));
-    plan.n_paths = n_paths; plan.n_contigs = n_contigs;
     return KATOME_OK;
+}
+
+int dev_gfa_paths_plan(uint64_t n_edges, const uint64_t* edge_src, const uint64_t* edge_dst, const uint32_t* pieces, uint64_t n_pieces, GfaPathsPlan& plan,
+                       hipStream_t stream) {
+    DevBuf size(stream);                                                // (the run flags first, then every piece's bytes)
+    KCHECK(dev_gfa_paths_runs(n_edges, edge_src, edge_dst, pieces, n_pieces, plan, size, stream));
+    if (n_pieces == 0) return KATOME_OK;
+    hipLaunchKernelGGL(path_size_kernel, dim3(grid_for(n_pieces, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, pieces, (u64)n_pieces, plan.path_idx.as<u64>(),
+                       plan.path_contig.as<u64>(), plan.contig_first_path.as<u64>(), size.as<u32>());
+    KCHECK_HIP(hipGetLastError());
+    return dev_gfa_paths_offsets(n_pieces, size.as<u32>(), plan, stream);
 }
 
 int dev_gfa_paths_write(const uint32_t* pieces, uint64_t n_pieces, const GfaPathsPlan& plan, uint8_t* text, hipStream_t stream) {

@@ -92,6 +92,17 @@ void katome_gfa_paths_free(katome_gfa_paths* g) {
     delete o;
 }
 
+struct GfaStrandPathsOwner {   // katome_gfa_strand_paths followed by what it owns
+    katome_gfa_strand_paths g;
+    std::vector<void*> mem;
+};
+void katome_gfa_strand_paths_free(katome_gfa_strand_paths* g) {
+    if (!g) return;
+    GfaStrandPathsOwner* o = reinterpret_cast<GfaStrandPathsOwner*>(g);
+    for (void* p : o->mem) free(p);
+    delete o;
+}
+
 }  // extern "C"
 
 // KATOME_TRACE_BUILD=1: wall time of the host entries' stages on stderr
@@ -350,9 +361,49 @@ static int gfa_paths_to_host(katome_builder* b, uint64_t read_bytes, katome_gfa_
     return KATOME_OK;
 }
 
+extern "C" int katome_gfa_strand_paths_save(const katome_gfa_strand_paths* g, const char* path) {
+    if (!g || !path) { set_error("null argument"); return KATOME_E_ARG; }
+    return save_gfa_text(g->text, g->text_bytes + g->path_bytes, path);      // (the two parts are contiguous on the host)
+}
+// katome_dev_collapse_gfa_strands of the builder's last collapse in host arrays: the two parts of the text back to back
+static int gfa_strand_paths_to_host(katome_builder* b, uint64_t read_bytes, katome_gfa_strand_paths** out) {
+    katome_dev_gfa_strand_paths d;
+    KCHECK(katome_dev_collapse_gfa_strands(b, &d, nullptr));
+    GfaStrandPathsOwner* o = new (std::nothrow) GfaStrandPathsOwner();
+    if (!o) { set_error("out of host memory"); return KATOME_E_OOM; }
+    memset(&o->g, 0, sizeof o->g);
+    katome_gfa_strand_paths* g = &o->g;
+    g->n_segments = d.n_segments; g->n_links = d.n_links; g->text_bytes = d.text_bytes; g->read_bytes = read_bytes; g->k = b->s.k;
+    g->n_edges = d.n_edges; g->n_unpaired = d.n_unpaired; g->n_self_twins = d.n_self_twins;
+    g->n_paths = d.n_paths; g->n_jumps = d.n_jumps; g->path_bytes = d.path_bytes; g->n_mirrored = d.n_mirrored; g->n_self_mirror = d.n_self_mirror;
+    bool oom = false;
+    uint8_t* text = (uint8_t*)take(o, std::max<uint64_t>(d.text_bytes + d.path_bytes, 1), &oom);
+    int rc = KATOME_OK;
+    if (oom) { set_error("out of host memory"); rc = KATOME_E_OOM; }
+    if (!rc && d.text_bytes && hipMemcpy(text, d.d_text, d.text_bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = KATOME_E_DEVICE;
+    if (!rc && d.path_bytes && hipMemcpy(text + d.text_bytes, d.d_path_text, d.path_bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = KATOME_E_DEVICE;
+    if (rc == KATOME_E_DEVICE) set_error("device -> host copy failed: %s", hipGetErrorString(hipGetLastError()));
+    g->text = text;
+    if (!rc) rc = d2h(o, &g->segment_off, d.d_segment_off, d.n_segments);
+    if (!rc) rc = d2h(o, &g->link_first, d.d_link_first, d.n_segments + 1);
+    if (!rc) rc = d2h(o, &g->segment_name, d.d_segment_name, d.n_segments);
+    if (!rc) rc = d2h(o, &g->edge_twin, d.d_edge_twin, d.n_edges);
+    if (!rc) rc = d2h(o, &g->path_line_off, d.d_path_line_off, d.n_paths + 1);
+    if (!rc) rc = d2h(o, &g->path_contig, d.d_path_contig, d.n_paths);
+    if (!rc) rc = d2h(o, &g->path_first_piece, d.d_path_first_piece, d.n_paths + 1);
+    if (!rc) rc = d2h(o, &g->path_mirror, d.d_path_mirror, d.n_paths);
+    if (rc) { katome_gfa_strand_paths_free(g); return rc; }
+    *out = g;
+    return KATOME_OK;
+}
+
 // the stages "dcwced" (asm/basic_assembler.rs:58-75), collapse, Contigs::stats and, with a path, save_to_file: host arrays
-// (with_gfa: katome_assemble_gfa_* -- the GFA of the collapse's shrunk graph with the contigs as P lines too)
-struct AssembleWant { katome_assembly** out; const char* path; bool with_gfa = false; katome_gfa_paths** gfa_out = nullptr; const char* gfa_path = nullptr; };
+// (with_gfa: katome_assemble_gfa_* -- the GFA of the collapse's shrunk graph with the contigs as P lines too; merge_strands:
+// katome_assemble_gfa_strands_* -- that GFA with strand twins merged, handed back through strands_out)
+struct AssembleWant {
+    katome_assembly** out; const char* path; bool with_gfa = false; katome_gfa_paths** gfa_out = nullptr; const char* gfa_path = nullptr;
+    bool merge_strands = false; katome_gfa_strand_paths** strands_out = nullptr;
+};
 static int assembly_to_host(katome_builder* b, uint64_t read_bytes, const AssembleWant& want, uint64_t genome_len) {
     katome_dev_graph dg;
     if (!b->first_seen) { set_error("assemble needs KATOME_FLAG_FIRST_SEEN_ORDER"); return KATOME_E_ARG; }
@@ -377,17 +428,20 @@ static int assembly_to_host(katome_builder* b, uint64_t read_bytes, const Assemb
     if (rc) { katome_assembly_free(a); return rc; }
     if (want.with_gfa) {
         katome_gfa_paths* g = nullptr;
-        rc = gfa_paths_to_host(b, read_bytes, &g);
-        build_lap("collapse_gfa");
+        katome_gfa_strand_paths* gs = nullptr;
+        rc = want.merge_strands ? gfa_strand_paths_to_host(b, read_bytes, &gs) : gfa_paths_to_host(b, read_bytes, &g);
+        build_lap(want.merge_strands ? "collapse_gfa_strands" : "collapse_gfa");
         if (rc) { katome_assembly_free(a); return rc; }
         if (want.out) *want.out = a;
         if (want.gfa_out) *want.gfa_out = g;
+        if (want.strands_out) *want.strands_out = gs;
         rc = want.path ? katome_assembly_save(a, want.path) : KATOME_OK;      // (both files are tried; the first failure is the one reported)
         const std::string first_err = rc ? get_error() : "";
-        const int rc_gfa = want.gfa_path ? katome_gfa_paths_save(g, want.gfa_path) : KATOME_OK;
+        const int rc_gfa = !want.gfa_path ? KATOME_OK : gs ? katome_gfa_strand_paths_save(gs, want.gfa_path) : katome_gfa_paths_save(g, want.gfa_path);
         if (rc) set_error("%s", first_err.c_str()); else rc = rc_gfa;
         if (!want.out) katome_assembly_free(a);
         if (!want.gfa_out) katome_gfa_paths_free(g);
+        if (!want.strands_out) katome_gfa_strand_paths_free(gs);
         return rc;
     }
     if (want.out) *want.out = a;
@@ -1045,6 +1099,22 @@ int katome_assemble_gfa_packed(const katome_settings* s, const uint8_t* packed, 
     KCHECK(assemble_gfa_finish(original_genome_length, fasta_path, gfa_path, asm_out, gfa_out, f));
     return build_packed_impl(s, packed, n_reads, read_len, skip, f);
 }
+// katome_assemble_gfa_strands_*: the same with strand twins merged
+static int assemble_gfa_strands_finish(uint64_t genome_len, const char* fasta_path, const char* gfa_path, katome_assembly** asm_out,
+                                       katome_gfa_strand_paths** gfa_out, Finish& f) {
+    if (asm_out) *asm_out = nullptr;
+    if (gfa_out) *gfa_out = nullptr;
+    if (!fasta_path && !gfa_path && !asm_out && !gfa_out) { set_error("null argument"); return KATOME_E_ARG; }
+    f.assemble = AssembleWant{asm_out, fasta_path, true, nullptr, gfa_path, true, gfa_out}; f.assembling = true; f.genome_len = genome_len;
+    return KATOME_OK;
+}
+int katome_assemble_gfa_strands_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip,
+                                       uint64_t original_genome_length, const char* fasta_path, const char* gfa_path, katome_assembly** asm_out,
+                                       katome_gfa_strand_paths** gfa_out) {
+    Finish f{nullptr, nullptr};
+    KCHECK(assemble_gfa_strands_finish(original_genome_length, fasta_path, gfa_path, asm_out, gfa_out, f));
+    return build_packed_impl(s, packed, n_reads, read_len, skip, f);
+}
 // (the same check on every route: the stages work on the links of a first-seen build)
 static int unitigs_refusal(const katome_settings* s, const char* stages) {
     if (s && !(s->flags & KATOME_FLAG_FIRST_SEEN_ORDER) && ((stages && *stages) || (s->flags & KATOME_FLAG_REMOVE_DEAD_PATHS))) {
@@ -1274,6 +1344,12 @@ int katome_assemble_gfa_files(const katome_settings* s, const char* const* paths
                               const char* gfa_path, katome_assembly** asm_out, katome_gfa_paths** gfa_out) {
     Finish f{nullptr, nullptr};
     KCHECK(assemble_gfa_finish(original_genome_length, fasta_path, gfa_path, asm_out, gfa_out, f));
+    return build_files_impl(s, paths, n_paths, f);
+}
+int katome_assemble_gfa_strands_files(const katome_settings* s, const char* const* paths, size_t n_paths, uint64_t original_genome_length,
+                                      const char* fasta_path, const char* gfa_path, katome_assembly** asm_out, katome_gfa_strand_paths** gfa_out) {
+    Finish f{nullptr, nullptr};
+    KCHECK(assemble_gfa_strands_finish(original_genome_length, fasta_path, gfa_path, asm_out, gfa_out, f));
     return build_files_impl(s, paths, n_paths, f);
 }
 int katome_unitigs_files(const katome_settings* s, const char* const* paths, size_t n_paths, const char* stages, uint64_t original_genome_length,

@@ -220,6 +220,34 @@ class DeviceGfaPaths(DeviceGfa):
         return bytes(self.text.cpu().numpy()) + bytes(self.path_text.cpu().numpy())
 
 
+def unique_paths(path_mirror):
+    """the paths that stay when every double-stranded molecule keeps one: those with no mirror (-1, or 2^64 - 1 as unsigned) or
+    with mirror(j) >= j -> list of path indices"""
+    return [j for j, q in enumerate(int(x) for x in path_mirror) if q < 0 or q >= j]
+
+
+class DeviceGfaStrandPaths(DeviceGfaStrands):
+    """the bidirected GFA of an assembly in HBM (katome_dev_collapse_gfa_strands): text and the segment / link / twin arrays as in
+    DeviceGfaStrands for the collapse's shrunk graph, then the contigs as P lines over the merged segments in path_text (the
+    fields of DeviceGfaPaths; a piece reads <rep><o>).  path_mirror[j]: the smallest path that spells the same molecule from its
+    other end, -1 for none; n_mirrored paths have one, n_self_mirror are their own"""
+
+    def __init__(self, strands, n_edges, n_paths, n_jumps, path_bytes, path_text, path_line_off, path_contig, path_first_piece, n_mirrored, n_self_mirror,
+                 path_mirror):
+        super().__init__(*strands)
+        self.n_edges, self.n_paths, self.n_jumps, self.path_bytes, self.path_text = n_edges, n_paths, n_jumps, path_bytes, path_text
+        self.path_line_off, self.path_contig, self.path_first_piece = path_line_off, path_contig, path_first_piece
+        self.n_mirrored, self.n_self_mirror, self.path_mirror = n_mirrored, n_self_mirror, path_mirror
+
+    def bytes(self):
+        """host: the file's bytes, the two parts back to back"""
+        return bytes(self.text.cpu().numpy()) + bytes(self.path_text.cpu().numpy())
+
+    def unique_paths(self):
+        """the indices j with no mirror or mirror(j) >= j: one path per molecule"""
+        return unique_paths(self.path_mirror.cpu().tolist())
+
+
 LAYOUTS = {"plain": 0, "fasta": 1}
 
 
@@ -504,10 +532,22 @@ class Builder(_ViewOwner):
         self.last_collapse_host_ms = st.host_ms
         return DeviceAssembly(da, self, self.tdev, stats)
 
-    def collapse_gfa(self):
+    def collapse_gfa(self, merge_strands=False):
         """the GFA of the last collapse(): its shrunk graph as H, S and L lines and its contigs as P lines over those segments, one
         line per run of properly linked pieces (katome_dev_collapse_gfa; include/katome_gpu.h has the format) -> DeviceGfaPaths,
-        valid until the next collapse_gfa() or close().  The results of collapse() and of gfa() stay valid"""
+        valid until the next collapse_gfa() or close().  The results of collapse() and of gfa() stay valid.  merge_strands: strand
+        twins as one segment, +/- in the links and in the paths, and every path's mirror (katome_dev_collapse_gfa_strands) ->
+        DeviceGfaStrandPaths, valid until the next collapse_gfa(merge_strands=True); neither call touches the other's result"""
+        if merge_strands:
+            d = _lib.DevGfaStrandPaths()
+            _check(_lib.lib().katome_dev_collapse_gfa_strands(self._h, C.byref(d), _stream()))
+            v = lambda p, n: _view(p, (n,), "<i8", self, self.tdev)
+            u = lambda p, n: _view(p, (n,), "|u1", self, self.tdev)
+            strands = (d.n_segments, d.n_links, d.text_bytes, u(d.d_text, d.text_bytes), v(d.d_segment_off, d.n_segments), v(d.d_link_first, d.n_segments + 1),
+                       v(d.d_segment_name, d.n_segments), v(d.d_edge_twin, d.n_edges), d.n_unpaired, d.n_self_twins)
+            return DeviceGfaStrandPaths(strands, d.n_edges, d.n_paths, d.n_jumps, d.path_bytes, u(d.d_path_text, d.path_bytes), v(d.d_path_line_off, d.n_paths + 1),
+                                        v(d.d_path_contig, d.n_paths), v(d.d_path_first_piece, d.n_paths + 1), d.n_mirrored, d.n_self_mirror,
+                                        v(d.d_path_mirror, d.n_paths))
         d = _lib.DevGfaPaths()
         _check(_lib.lib().katome_dev_collapse_gfa(self._h, C.byref(d), _stream()))
         v = lambda p, n: _view(p, (n,), "<i8", self, self.tdev)
@@ -809,6 +849,26 @@ def gfa_paths_arrays(edge_src, edge_dst, pieces, device=0):
     text = torch.empty(max(cap, 16), dtype=torch.uint8, device=tdev)
     _check(L.katome_dev_gfa_paths_arrays(*args, _ptr(line_off), _ptr(contig), _ptr(first), n_paths, _ptr(text), cap, counts, _stream()))
     return text, dict(n_paths=counts[0], n_jumps=counts[1], text_bytes=counts[2]), line_off, contig[:n_paths], first
+
+
+def gfa_strand_paths_arrays(edge_src, edge_dst, edge_twin, pieces, device=0):
+    """the path kernels over MERGED segments and the mirror search on the caller's tensors (katome_dev_gfa_strand_paths_arrays):
+    gfa_paths_arrays with edge_twin int64 (DeviceGfaStrands.edge_twin: -1 for none) -> (path_text uint8 of text_bytes rounded up to
+    16, {n_paths, n_jumps, text_bytes, n_mirrored, n_self_mirror}, path_line_off, path_contig, path_first_piece, path_mirror)"""
+    tdev = pieces.device
+    counts = (C.c_uint64 * 5)()
+    L = _lib.lib()
+    args = (device, edge_src.numel(), _ptr(edge_src), _ptr(edge_dst), _ptr(edge_twin), _ptr(pieces), pieces.numel())
+    _check(L.katome_dev_gfa_strand_paths_arrays(*args, None, None, None, None, 0, None, 0, counts, _stream()))
+    n_paths, cap = counts[0], (counts[2] + 15) // 16 * 16
+    line_off = torch.empty(n_paths + 1, dtype=torch.int64, device=tdev)
+    contig = torch.empty(max(n_paths, 1), dtype=torch.int64, device=tdev)
+    first = torch.empty(n_paths + 1, dtype=torch.int64, device=tdev)
+    mirror = torch.empty(max(n_paths, 1), dtype=torch.int64, device=tdev)
+    text = torch.empty(max(cap, 16), dtype=torch.uint8, device=tdev)
+    _check(L.katome_dev_gfa_strand_paths_arrays(*args, _ptr(line_off), _ptr(contig), _ptr(first), _ptr(mirror), n_paths, _ptr(text), cap, counts, _stream()))
+    names = ("n_paths", "n_jumps", "text_bytes", "n_mirrored", "n_self_mirror")
+    return text, dict(zip(names, counts)), line_off, contig[:n_paths], first, mirror[:n_paths]
 
 
 def gfa_coverage_arrays(k, n_nodes, edge_src, edge_dst, edge_weight, edge_kmers, kmer_sum, kmer_min, kmer_max, edge_label_off, edge_label, device=0,

@@ -32,6 +32,7 @@ def kernels(lib):
     for mangled, dem in zip(out, names):
         dem = dem.replace(" ", "").replace(",katome::ArraySource>", ">").replace("katome::ArraySource)", ")").replace(", katome::ArraySource)", ")")
         dem = re.sub(r"(lds_count_ordered_kernel<\w+),false>", r"\1>", dem)          # (REGIONS = false: the kernel as it was)
+        dem = dem.replace("(anonymousnamespace)::", "")                             # (or every such kernel would be cut down to "katome::" below)
         dem = re.sub(r"\(.*$", "", dem)
         res[dem] = (len(out[mangled]), hashlib.sha1("\n".join(out[mangled]).encode()).hexdigest())
     return res

@@ -32,6 +32,6 @@ while True:
             if pat not in d:
                 continue
             g = lambda k: (re.search(r"\.%s:\s+(\d+)" % k, b) or [None, "?"])[1]
-            print("%-90s vgpr %s sgpr %s scratch %s vgpr_spill %s sgpr_spill %s lds %s" % (d.split("(")[0][:90], g("vgpr_count"), g("sgpr_count"),
+            print("%-90s vgpr %s sgpr %s scratch %s vgpr_spill %s sgpr_spill %s lds %s" % (d.replace("(anonymous namespace)::", "").split("(")[0][:90], g("vgpr_count"), g("sgpr_count"),
                   g("private_segment_fixed_size"), g("vgpr_spill_count"), g("sgpr_spill_count"), g("group_segment_fixed_size")))
     at += len(MAGIC)
