@@ -170,6 +170,40 @@ KATOME_INTERNAL bool tile_recs_shape(uint32_t nwt, uint32_t nw, bool first_seen)
 KATOME_INTERNAL bool sorted_fail(const char* level);     // KATOME_SORTED_FAIL (tests)
 KATOME_INTERNAL bool seen_var_sorted();              // KATOME_SEEN_VAR_SORTED
 
+// ---- what the GFA entry points (gfa.hip, gfa_strands.hip, gfa_paths.hip, gfa_strand_paths.hip) share -----------------------------
+inline GfaGraph gfa_graph_of(uint32_t k, const ShrinkOutput& sh) {
+    return GfaGraph{k, sh.n_nodes, sh.n_edges, sh.edge_src.as<u64>(), sh.edge_dst.as<u64>(), sh.edge_weight.as<u32>(), sh.edge_kmers.as<u32>(),
+                    sh.edge_label_off.as<u64>(), sh.edge_label.as<uint8_t>(), sh.label_bytes};
+}
+// c is the result of b's last katome_dev_shrink
+inline bool is_last_shrink(const katome_builder* b, const katome_dev_contigs* c) {
+    const ShrinkOutput& sh = b->shrunk;
+    return c->n_edges == sh.n_edges && c->n_nodes == sh.n_nodes && c->d_edge_src == sh.edge_src.as<u64>() && c->d_edge_label == sh.edge_label.as<uint8_t>() &&
+           c->d_edge_label_off == sh.edge_label_off.as<u64>();
+}
+inline int check_label_alignment(const void* d_edge_label) {
+    if ((uintptr_t)d_edge_label & 3) { set_error("gfa: d_edge_label must be 4-byte aligned (the kernel reads the aligned words around the bytes it needs)"); return KATOME_E_ARG; }
+    return KATOME_OK;
+}
+// `bytes` of text, rounded up to 16, fit the caller's `cap` bytes at a 16-byte aligned d_text
+inline bool text_fits(uint64_t bytes, uint64_t cap, const void* d_text) { return cap >= (bytes + 15) / 16 * 16 && !((uintptr_t)d_text & 15); }
+// KATOME_*_TRACE of an *_arrays entry (there is no builder whose profile could hold its kernels' times): a profiler that is on where
+// `env` is set, to open a PhaseScope on round the launches, and the events of the phases first .. last on stderr afterwards, one line
+// each, in the form the tools/bench_gfa*.py parse
+struct ArraysTrace {
+    Profiler prof;
+    const char* entry;
+    ArraysTrace(const char* env, const char* entry_) : entry(entry_) { prof.on = getenv(env) != nullptr; }
+    void print(int first_phase, int last_phase, uint64_t bytes, uint64_t n1, const char* what1, uint64_t n2, const char* what2) const {
+        for (const Profiler::Ev& e : prof.evs) {
+            float ms = 0;
+            if (e.phase >= first_phase && e.phase <= last_phase && hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess)
+                fprintf(stderr, "[%s] %s %.4f ms, %llu bytes, %llu %s, %llu %s\n", entry, PHASE_NAMES[e.phase], ms, (unsigned long long)bytes, (unsigned long long)n1,
+                        what1, (unsigned long long)n2, what2);
+        }
+    }
+};
+
 // ---- dist_gfa.hip: the k-mers on ALL ranks' merged edges of the last katome_dist_shrink (collective; katome_unitigs_gfa_*'s total_bases)
 struct katome_dist_builder;
 KATOME_INTERNAL int dist_gfa_total_kmers(katome_dist_builder* d, uint64_t* total, hipStream_t stream);

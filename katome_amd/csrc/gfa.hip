@@ -9,56 +9,33 @@
 //   the sort is stable, so the indices ascend inside a vertex), the heads and tails of the sorted runs give every vertex its range,
 //   the link count of segment a is the out-degree of edge_dst[a], and a scan gives every segment its first link.  Links then come
 //   out ordered by a, then b.  The input's edge_src need not be ordered (the exact shrink's is not).
-//   The sizes: a line's bytes are counted once, here (an S line's bases from its label alone, as collapse.hip's piece_measure_kernel
-//   does, plus the digits of its five numbers; an L line's from the digits of a, b and k - 1), and scanned into 64-bit offsets: line 0
-//   is the header, line 1 + i segment i, line 1 + n_edges + l link l.
-//   gfa_write_kernel is partitioned by OUTPUT bytes like text_write_kernel: a workgroup owns TILE bytes, finds the lines that
-//   overlap them by the workgroup search and keeps their starts in LDS.  Everything that is not a base -- the header, an S line's
-//   name and tags, whole L lines: short records full of decimal numbers -- is formatted ONCE per line, one thread per line, right to
-//   left into an LDS image of the tile (a division by ten per digit, not per byte and lane).  Then every lane produces 16 consecutive
-//   bytes with one 128-bit store: 16 bases of one segment straight from the 2-bit label (sixteen_bases); in the L region the image's
-//   16 bytes as they are; anywhere else the image's bytes with the bases among them filled in one at a time.
-//   The numbered form (gfa_write_kernel<true>, dev_gfa_part_plan / dev_gfa_part_write, katome_dev_gfa_part_arrays) writes one PART of
-//   a text whose other parts are written elsewhere (dist_gfa.hip): names start at first_segment, links come as a table of 64-bit
-//   global numbers, the header is written or not, and the S part and the L part are two regions of one buffer, each a launch of its
-//   own.  It is a separate instantiation: gfa_write_kernel<false> is the one-GPU kernel as it was.
-//   The coverage form (COV, a second template parameter of the two measure kernels and of the writer's S-tag branch): KC is the sum of
-//   the path's k-mer counts and "\tmn:i:<min>\tmx:i:<max>" follows ew (katome_dev_contigs_gfa_coverage, katome_dev_gfa_coverage_arrays,
-//   GfaGraph::cov / GfaPart::cov); the variants without it are the kernels as they were.  gfa_strands.hip has no coverage form.
+//   The sizes: a line's bytes are counted once (an S line's bases from its label alone, as collapse.hip's piece_measure_kernel does,
+//   plus the digits of its numbers; an L line's from the digits of a, b and k - 1) and scanned into 64-bit offsets: line 0 is the
+//   header, line 1 + i segment i, line 1 + n_edges + l link l.
+//   What this file shares with gfa_strands.hip lies in two headers.  gfa_lines.h has the line rules: an S and an L line's bytes,
+//   check_segment, the search for a link's segment, and how a line's name, tags and numbers are formatted.  gfa_image.h has the tile
+//   scheme and write_line_tile, a whole tile, which takes a line description: which lines are segments, how line r's bytes
+//   that are not bases are formatted, and line r's bases.  gfa_write_kernel is the loop over the tiles round it, with one of two descriptions:
+//     TextLines (gfa_write_kernel<false, .>): the one-GPU text of dev_gfa_plan / dev_gfa_write;
+//     PartLines (gfa_write_kernel<true, .>, dev_gfa_part_plan / dev_gfa_part_write, katome_dev_gfa_part_arrays): one PART of a text
+//     whose other parts are written elsewhere (dist_gfa.hip): names start at first_segment, links come as a table of 64-bit global
+//     numbers, the header is written or not, and the S part and the L part are two regions of one buffer, each a launch of its own.
+//   The coverage form (COV, the second template parameter; katome_dev_contigs_gfa_coverage, katome_dev_gfa_coverage_arrays,
+//   GfaGraph::cov / GfaPart::cov): KC is the sum of the path's k-mer counts and "\tmn:i:<min>\tmx:i:<max>" follows ew.  Both
+//   parameters are compile-time: an instantiation carries no branch of another's.  gfa_strands.hip has no coverage form.
 //   Every segment is one strand here and every orientation +; gfa_strands.hip folds strand twins into one segment with +/- links, on
-//   top of this file's join (dev_gfa_plan) and the tile image both writers share (gfa_image.h).
+//   top of this file's join (dev_gfa_plan) and a line description of its own.
+//   The entry points' common checks (gfa_graph_of, is_last_shrink, check_label_alignment, text_fits, ArraysTrace) are builder.h's.
 #include "builder.h"
-#include "gfa_image.h"
-#include "text_bases.h"
+#include "gfa_lines.h"
 
 namespace katome {
 namespace {
 
-constexpr int S_NAME_MAX_NUMBERED = 2 + 20 + 1;        // ... of a numbered part: first_segment + i < 2^64
-constexpr u32 L_LINE_MAX_NUMBERED = 10 + 20 + 20 + 10; // "L\t<a>\t+\t<b>\t+\t<k-1>M\n" with two 64-bit numbers: far below a tile
-constexpr int S_TAGS_MAX = 3 * 6 + 10 + 20 + 10 + 1;   // "\tLN:i:<u32>\tKC:i:<u64>\tew:i:<u32>\n"
-constexpr int S_TAGS_MAX_COV = S_TAGS_MAX + 2 * (6 + 10);      // ... with coverage: "\tmn:i:<u32>\tmx:i:<u32>" in front of the line's end
-static_assert(S_TAGS_MAX_COV < (int)TILE, "a segment's tags fit a tile");
-// (no line of either form is shorter than the header's 11 bytes -- the shortest L line, "L\t0\t+\t0\t+\t0M\n", has 13 --, so MAX_LINES and
-// the 16-bit offsets hold for a numbered part too: longer numbers only make lines longer)
-static_assert(L_LINE_MAX_NUMBERED < TILE && HEADER_BYTES <= 13, "a tile holds at most MAX_LINES lines");
-enum { ERR_NODE = 1, ERR_LABEL = 2, ERR_LABEL_LEN = 4, ERR_KMERS = 8, ERR_LINKS = 16, ERR_COVERAGE = 32 };
+static_assert(S_TAGS_MAX + COV_TAGS_MAX < (int)TILE, "a segment's tags fit a tile");
 
-// The coverage variant (COV, GfaCoverage of common.h): KC is the sum of the path's k-mer counts and the S line ends in mn / mx.  A
-// compile-time variant of the two measure kernels and of the writer's S-tag branch: without it they are the kernels they were.
-// a segment's coverage fits its weight and its k-mers: min <= weight <= max and min * kmers <= sum <= max * kmers (64-bit: u32 * u32)
-__device__ __forceinline__ bool coverage_fits(const GfaCoverage& c, u64 i, u32 w, u32 km) {
-    const u32 mn = c.kmer_min[i], mx = c.kmer_max[i];
-    const u64 sum = c.kmer_sum[i];
-    return mn <= w && w <= mx && (u64)mn * km <= sum && sum <= (u64)mx * km;
-}
-// the bytes of "\tKC:i:<sum>\tew:i:<w>\tmn:i:<min>\tmx:i:<max>\n"
-__device__ __forceinline__ u32 coverage_tag_bytes(const GfaCoverage& c, u64 i, u32 w) {
-    return 6 + decimal_digits(c.kmer_sum[i]) + 6 + decimal_digits(w) + 6 + decimal_digits(c.kmer_min[i]) + 6 + decimal_digits(c.kmer_max[i]) + 1;
-}
-
-// Segment i's line: checks everything the later kernels read through (the two vertices, the label's offsets, pad byte and length, and
-// that the label spells edge_kmers + k - 1 bases), counts the line's bytes, and sets up the sort of the edge indices by source
+// Segment i's line: checks everything the later kernels read through (the two vertices and check_segment's), counts the line's bytes,
+// and sets up the sort of the edge indices by source
 template <bool COV>
 __global__ __launch_bounds__(BLOCK) void gfa_measure_kernel(u32 k, u64 N, u64 E, const u64* __restrict__ src, const u64* __restrict__ dst,
                                                             const u32* __restrict__ weight, const u32* __restrict__ kmers,
@@ -71,18 +48,10 @@ __global__ __launch_bounds__(BLOCK) void gfa_measure_kernel(u32 k, u64 N, u64 E,
         const u64 s = src[i];
         if (s >= N || dst[i] >= N) { atomicOr(err, (u32)ERR_NODE); continue; }
         u32 bases = 0;
-        const int bad = label_check(label, label_off[i], label_off[i + 1], label_bytes, k, &bases);
-        if (bad) { atomicOr(err, (u32)(bad == 2 ? ERR_LABEL_LEN : ERR_LABEL)); continue; }
-        if ((u64)bases != (u64)kmers[i] + k - 1) { atomicOr(err, (u32)ERR_KMERS); continue; }
-        const u32 w = weight[i];
-        if constexpr (COV) {
-            if (!coverage_fits(cov, i, w, kmers[i])) { atomicOr(err, (u32)ERR_COVERAGE); continue; }      // (no size from the bad values)
-            key[i] = s;
-            size[1 + i] = 2 + decimal_digits(i) + 1 + bases + 6 + decimal_digits(bases) + coverage_tag_bytes(cov, i, w);
-            continue;
-        }
+        const u32 bad = check_segment<COV>(k, i, weight, kmers, label_off, label, label_bytes, cov, &bases);
+        if (bad) { atomicOr(err, bad); continue; }
         key[i] = s;
-        size[1 + i] = 2 + decimal_digits(i) + 1 + bases + 6 + decimal_digits(bases) + 6 + decimal_digits((u64)w * kmers[i]) + 6 + decimal_digits(w) + 1;
+        size[1 + i] = checked_segment_bytes<COV>(i, i, bases, weight, kmers, cov);
     }
 }
 
@@ -100,152 +69,87 @@ __global__ __launch_bounds__(BLOCK) void gfa_link_count_kernel(const u64* __rest
                                                                u32* __restrict__ count) {
     for (u64 a = (u64)blockIdx.x * BLOCK + threadIdx.x; a < E; a += (u64)gridDim.x * BLOCK) { const u64 v = dst[a]; count[a] = last[v] - first[v]; }
 }
-// link l: its segment a is the last one whose first link is <= l (segments without links share their successor's first link and are
-// passed over), its b the (l - first link)-th edge out of a's target; its line's bytes go behind the header's and the segments'
+// link l: its b is the (l - first link)-th edge out of its segment a's target; its line's bytes go behind the header's and the segments'
 __global__ __launch_bounds__(BLOCK) void gfa_link_fill_kernel(u32 E, u64 L, u32 k1_digits, const u64* __restrict__ dst, const u32* __restrict__ first,
                                                               const u32* __restrict__ order, const u64* __restrict__ link_first, u32* __restrict__ link_ab,
                                                               u32* __restrict__ size) {
     for (u64 l = (u64)blockIdx.x * BLOCK + threadIdx.x; l < L; l += (u64)gridDim.x * BLOCK) {
-        u32 lo = 0, hi = E;
-        while (hi - lo > 1) { const u32 mid = lo + ((hi - lo) >> 1); if (link_first[mid] <= l) lo = mid; else hi = mid; }
-        const u32 a = lo, b = order[first[dst[a]] + (u32)(l - link_first[a])];
+        const u32 a = last_segment_with_first_link_le(link_first, E, l), b = order[first[dst[a]] + (u32)(l - link_first[a])];
         link_ab[2 * l] = a; link_ab[2 * l + 1] = b;
-        size[l] = 10 + decimal_digits(a) + decimal_digits(b) + k1_digits;
+        size[l] = link_line_bytes(a, b, k1_digits);
     }
 }
-// segment i's first base: behind "S\t<i>\t"
-__global__ __launch_bounds__(BLOCK) void gfa_segment_off_kernel(u64 E, const u64* __restrict__ line_off, u64* __restrict__ segment_off) {
-    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < E; i += (u64)gridDim.x * BLOCK) segment_off[i] = line_off[1 + i] + 3 + decimal_digits(i);
-}
-
-// (NUMBERED: a part of a sharded text, see PartNumbers below; its segments are lines hdr .. hdr + E - 1)
-template <bool NUMBERED>
-__device__ __forceinline__ Line load_line(u32 r, u32 E, u32 hdr, const uint8_t* __restrict__ label, const u64* __restrict__ label_off,
-                                          const u64* __restrict__ segment_off, const u64* __restrict__ line_off) {
-    Line ln;
-    const u64 at = line_off[r];
-    ln.total = (u32)(line_off[r + 1] - at);
-    ln.head = ln.total; ln.bases = 0; ln.src = label;
-    if (NUMBERED ? (r >= hdr && r < hdr + E) : (r >= 1 && r <= E)) {
-        const u32 i = NUMBERED ? r - hdr : r - 1;
-        const u64 lo = label_off[i], hi = label_off[i + 1];
-        ln.src = label + lo + 1;
-        ln.bases = 4 * (u32)(hi - lo - 1) - label[lo];
-        ln.head = (u32)(segment_off[i] - at);       // (the name's digits were counted when the line was measured: none is counted here)
-    }
-    return ln;
+// segment i's first base, its line being line hdr + i and its name first + i
+__global__ __launch_bounds__(BLOCK) void gfa_segment_off_kernel(u64 E, u64 first, u32 hdr, const u64* __restrict__ line_off, u64* __restrict__ segment_off) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < E; i += (u64)gridDim.x * BLOCK) segment_off[i] = segment_first_base(line_off[hdr + i], first + i);
 }
 
 // A numbered part of a text whose other parts are written elsewhere (dist_gfa.hip): segment i is named first + i, link l joins
 // first + link_a[l] to link_b[l] (a global number), and the header line is there or not (hdr = 1 or 0): the part's lines are hdr
-// header lines, E segments, then links.  The one-GPU text is the form without: NUMBERED = false is the kernel as it was, its
-// conditions and types untouched, and takes none of these.
+// header lines, E segments, then links.
 // (An S part is launched with hdr header lines and E segments, R = hdr + E; an L part with E = 0, hdr = 0 and R links.)
 struct PartNumbers { u64 first; u32 hdr; const u32* link_a; const u64* link_b; };
 
+// ---- the line descriptions (write_line_tile of gfa_image.h) ---------------------------------------------------------------------
+// what both have: the arrays behind an S line, and the S line of edge i under `name`
+struct SegmentArrays {
+    u32 k; const u32 *weight, *kmers; const u64 *label_off; const uint8_t* label; const u64* segment_off; GfaCoverage cov;
+    template <bool COV, int NAME_ROOM, class N>
+    __device__ __forceinline__ void format_segment(uint8_t* img, u32 i, N name, u64 o, int64_t rel, int64_t end, int len) const {
+        put_segment_name<NAME_ROOM>(img, rel, len, (int)(segment_off[i] - o), name);
+        if (end - (S_TAGS_MAX + (COV ? COV_TAGS_MAX : 0)) < len) {
+            const u32 w = weight[i], km = kmers[i];
+            put_segment_tags(img, end, len, km + k - 1, segment_kc<COV>(cov, i, w, km), w, [&](int p) { return put_coverage_tags<COV>(img, p, len, cov, i); });
+        }
+    }
+    // (line r; the segments are the E lines from line `first` on)
+    __device__ __forceinline__ Line line(u32 r, u32 first, u32 E, const u64* __restrict__ line_off) const {
+        Line ln = line_without_bases(line_off, r, label);
+        if (r >= first && r < first + E) { const u32 i = r - first; add_bases(ln, label, label_off, i, (u32)(segment_off[i] - line_off[r])); }
+        return ln;
+    }
+};
+// the one-GPU text: line 0 is the header, line 1 + i segment i, line 1 + E + l link l = (link_ab[2 l], link_ab[2 l + 1]), every orientation +
+template <bool COV> struct TextLines {
+    SegmentArrays s; u32 E; const u32* link_ab;
+    __device__ __forceinline__ bool before_links(u32 r) const { return r <= E; }
+    __device__ __forceinline__ void format(uint8_t* img, u32 r, u64 o, int64_t rel, int64_t end, int len) const {
+        if (r == 0) put_header_line(img, rel, end, len);
+        else if (r > E) put_link_line(img, end, len, link_ab[2 * (r - 1 - E)], '+', link_ab[2 * (r - 1 - E) + 1], '+', s.k - 1);
+        else s.format_segment<COV, S_NAME_MAX>(img, r - 1, r - 1, o, rel, end, len);
+    }
+    __device__ __forceinline__ Line line(u32 r, const u64* __restrict__ line_off) const { return s.line(r, 1, E, line_off); }
+};
+// the numbered part: pn.hdr header lines, then E segments named pn.first + i, then the links (pn.first + pn.link_a[l], pn.link_b[l])
+template <bool COV> struct PartLines {
+    SegmentArrays s; u32 E; PartNumbers pn;
+    __device__ __forceinline__ bool before_links(u32 r) const { return r < pn.hdr + E; }
+    __device__ __forceinline__ void format(uint8_t* img, u32 r, u64 o, int64_t rel, int64_t end, int len) const {
+        if (r < pn.hdr) put_header_line(img, rel, end, len);
+        else if (r >= pn.hdr + E) put_link_line(img, end, len, pn.first + pn.link_a[r - pn.hdr - E], '+', pn.link_b[r - pn.hdr - E], '+', s.k - 1);
+        else s.format_segment<COV, S_NAME_MAX_NUMBERED>(img, r - pn.hdr, pn.first + (r - pn.hdr), o, rel, end, len);
+    }
+    __device__ __forceinline__ Line line(u32 r, const u64* __restrict__ line_off) const { return s.line(r, pn.hdr, E, line_off); }
+};
+
+// NUMBERED and COV stay compile-time: an instantiation carries no branch and no argument's read that its text does not need
 template <bool NUMBERED, bool COV>
 __global__ __launch_bounds__(BLOCK) void gfa_write_kernel(u32 k, u32 E, u32 R, const u32* __restrict__ weight, const u32* __restrict__ kmers,
                                                           const u64* __restrict__ label_off, const uint8_t* __restrict__ label,
                                                           const u64* __restrict__ line_off, const u64* __restrict__ segment_off,
                                                           const u32* __restrict__ link_ab, u64 total, uint8_t* __restrict__ text, const PartNumbers pn,
                                                           const GfaCoverage cov) {
-    const u32 hdr = NUMBERED ? pn.hdr : 1u;
-    constexpr int tags_max = COV ? S_TAGS_MAX_COV : S_TAGS_MAX;
-    constexpr int name_max = NUMBERED ? S_NAME_MAX_NUMBERED : S_NAME_MAX;
-    __shared__ __align__(16) uint8_t s_img[TILE];      // the tile's bytes that are not bases
-    __shared__ uint16_t s_off[MAX_LINES];              // where the tile's lines start, relative to the tile
-    const u32 tid = threadIdx.x;
-    const u64 n_tiles = (total + TILE - 1) / TILE;
-    for (u64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const u64 base = tile * TILE;
-        const int len = (int)min((u64)TILE, total - base);
+    const SegmentArrays s{k, weight, kmers, label_off, label, segment_off, cov};
+    for (u64 base = (u64)blockIdx.x * TILE; base < total; base += (u64)gridDim.x * TILE) {
+        const int len = tile_len(base, total);
         const u32 r_lo = workgroup_search(line_off, R, base), r_hi = workgroup_search(line_off, R, base + len - 1);
-        const u32 n_in = min(r_hi - r_lo + 1, MAX_LINES);
-        if (tid < 16 && (u32)len + tid < TILE) s_img[(u32)len + tid] = 0;             // (behind the text, up to the next multiple of 16: zeros)
-        for (u32 j = tid; j < n_in; j += BLOCK) {
-            const u32 r = r_lo + j;
-            const u64 o = line_off[r];
-            s_off[j] = o > base ? (uint16_t)(o - base) : 0;
-            const int64_t rel = (int64_t)(o - base), end = (int64_t)(line_off[r + 1] - base);      // (end >= 1: the line overlaps the tile)
-            if (NUMBERED ? r < hdr : r == 0) {
-                put_tag_back<3>(s_img, put_tag_back<6>(s_img, (int)end - 1, len, tag('Z', ':', '1', '.', '0', '\n')), len, tag('V', 'N', ':', 0, 0, 0));
-                put_tag_back<2>(s_img, (int)rel + 1, len, tag('H', '\t', 0, 0, 0, 0));
-            } else if (NUMBERED ? r >= hdr + E : r > E) {
-                const u32 l = NUMBERED ? r - hdr - E : r - 1 - E;
-                int p = put_tag_back<2>(s_img, (int)end - 1, len, tag('M', '\n', 0, 0, 0, 0));
-                p = put_decimal_back(s_img, p, len, k - 1);
-                if constexpr (NUMBERED) {
-                    p = put_decimal_back(s_img, put_tag_back<3>(s_img, p, len, tag('\t', '+', '\t', 0, 0, 0)), len, pn.link_b[l]);
-                    p = put_decimal_back(s_img, put_tag_back<3>(s_img, p, len, tag('\t', '+', '\t', 0, 0, 0)), len, pn.first + pn.link_a[l]);
-                } else {
-                    p = put_decimal_back(s_img, put_tag_back<3>(s_img, p, len, tag('\t', '+', '\t', 0, 0, 0)), len, link_ab[2 * l + 1]);
-                    p = put_decimal_back(s_img, put_tag_back<3>(s_img, p, len, tag('\t', '+', '\t', 0, 0, 0)), len, link_ab[2 * l]);
-                }
-                put_tag_back<2>(s_img, p, len, tag('L', '\t', 0, 0, 0, 0));
-            } else {
-                const u32 i = NUMBERED ? r - hdr : r - 1;
-                if (rel > -name_max) {                                         // "S\t<i>\t" reaches into the tile
-                    int p = (int)rel + (int)(segment_off[i] - o) - 1;
-                    put(s_img, p--, len, '\t');
-                    if constexpr (NUMBERED) p = put_decimal_back(s_img, p, len, pn.first + i);
-                    else p = put_decimal_back(s_img, p, len, i);
-                    put_tag_back<2>(s_img, p, len, tag('S', '\t', 0, 0, 0, 0));
-                }
-                if (end - tags_max < len) {                                    // the tags behind the bases do
-                    const u32 w = weight[i], km = kmers[i];
-                    int p = (int)end - 1;
-                    put(s_img, p--, len, '\n');
-                    if constexpr (COV) {
-                        p = put_tag_back<6>(s_img, put_decimal_back(s_img, p, len, cov.kmer_max[i]), len, tag('\t', 'm', 'x', ':', 'i', ':'));
-                        p = put_tag_back<6>(s_img, put_decimal_back(s_img, p, len, cov.kmer_min[i]), len, tag('\t', 'm', 'n', ':', 'i', ':'));
-                    }
-                    p = put_tag_back<6>(s_img, put_decimal_back(s_img, p, len, w), len, tag('\t', 'e', 'w', ':', 'i', ':'));
-                    p = put_tag_back<6>(s_img, put_decimal_back(s_img, p, len, COV ? cov.kmer_sum[i] : (u64)w * km), len, tag('\t', 'K', 'C', ':', 'i', ':'));
-                    put_tag_back<6>(s_img, put_decimal_back(s_img, p, len, km + k - 1), len, tag('\t', 'L', 'N', ':', 'i', ':'));
-                }
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int it = 0; it < STORES; ++it) {
-            const u32 rel = (u32)it * BLOCK * 16 + tid * 16;
-            const u64 o = base + rel;
-            if (o >= total) continue;
-            u32 lo = 0, hi = n_in;                                           // the line that holds byte o
-            while (hi - lo > 1) { const u32 mid = (lo + hi) >> 1; if (s_off[mid] <= rel) lo = mid; else hi = mid; }
-            u32 r = r_lo + lo;
-            const uint4 img = *(const uint4*)(s_img + rel);
-            uint4 v = img;                                                   // (from the first link on there are no bases)
-            if (NUMBERED ? r < hdr + E : r <= E) {
-                u32 at = (u32)(o - line_off[r]);
-                Line ln = load_line<NUMBERED>(r, E, hdr, label, label_off, segment_off, line_off);
-                if (at >= ln.head && at - ln.head + 16 <= ln.bases) {
-                    v = sixteen_bases(ln.src, at - ln.head);
-                } else {
-                    const u32 in[4] = {img.x, img.y, img.z, img.w};
-                    u32 w[4] = {0, 0, 0, 0};
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        if (r < R && at >= ln.total) {
-                            ++r; at = 0;
-                            if (r < R) ln = load_line<NUMBERED>(r, E, hdr, label, label_off, segment_off, line_off);
-                        }
-                        const bool base_here = r < R && at >= ln.head && at - ln.head < ln.bases;
-                        const u32 c = base_here ? one_base(ln.src, at - ln.head) : (in[i >> 2] >> (8 * (i & 3))) & 0xFF;
-                        w[i >> 2] |= c << (8 * (i & 3));
-                        ++at;
-                    }
-                    v = make_uint4(w[0], w[1], w[2], w[3]);
-                }
-            }
-            *(uint4*)(text + o) = v;                                         // (the buffer is a multiple of 16 bytes)
-        }
-        __syncthreads();                                                     // (the image and s_off are rewritten by the next tile)
+        if constexpr (NUMBERED) write_line_tile(PartLines<COV>{s, E, pn}, R, r_lo, r_hi, base, len, line_off, total, text);
+        else write_line_tile(TextLines<COV>{s, E, link_ab}, R, r_lo, r_hi, base, len, line_off, total, text);
     }
 }
 
 // ---- a numbered part: the same sizes, counted with the digits of the GLOBAL numbers --------------------------------------------
-// segment i of a part (named first + i): its label's checks, that its links' range ascends (link_first[0] = 0), its line's bytes
+// segment i of a part (named first + i): check_segment's, that its links' range ascends (link_first[0] = 0), its line's bytes
 template <bool COV>
 __global__ __launch_bounds__(BLOCK) void gfa_part_measure_kernel(u32 k, u64 E, u64 first, u32 hdr, const u32* __restrict__ weight, const u32* __restrict__ kmers,
                                                                  const u64* __restrict__ label_off, const uint8_t* __restrict__ label, u64 label_bytes,
@@ -259,30 +163,19 @@ __global__ __launch_bounds__(BLOCK) void gfa_part_measure_kernel(u32 k, u64 E, u
         size[hdr + i] = 0;
         if (link_first[i] > link_first[i + 1]) atomicOr(err, (u32)ERR_LINKS);
         u32 bases = 0;
-        const int bad = label_check(label, label_off[i], label_off[i + 1], label_bytes, k, &bases);
-        if (bad) { atomicOr(err, (u32)(bad == 2 ? ERR_LABEL_LEN : ERR_LABEL)); continue; }
-        if ((u64)bases != (u64)kmers[i] + k - 1) { atomicOr(err, (u32)ERR_KMERS); continue; }
-        const u32 w = weight[i];
-        if constexpr (COV) {
-            if (!coverage_fits(cov, i, w, kmers[i])) { atomicOr(err, (u32)ERR_COVERAGE); continue; }
-            size[hdr + i] = 2 + decimal_digits(first + i) + 1 + bases + 6 + decimal_digits(bases) + coverage_tag_bytes(cov, i, w);
-            continue;
-        }
-        size[hdr + i] = 2 + decimal_digits(first + i) + 1 + bases + 6 + decimal_digits(bases) + 6 + decimal_digits((u64)w * kmers[i]) + 6 + decimal_digits(w) + 1;
+        const u32 bad = check_segment<COV>(k, i, weight, kmers, label_off, label, label_bytes, cov, &bases);
+        if (bad) { atomicOr(err, bad); continue; }
+        size[hdr + i] = checked_segment_bytes<COV>(first + i, i, bases, weight, kmers, cov);
     }
 }
-// link l of a part: its segment is the last one whose first link is <= l (as gfa_link_fill_kernel finds it); its line's bytes
+// link l of a part: its segment and its line's bytes
 __global__ __launch_bounds__(BLOCK) void gfa_part_link_kernel(u32 E, u64 L, u64 first, u32 k1_digits, const u64* __restrict__ link_first,
                                                               const u64* __restrict__ link_b, u32* __restrict__ link_a, u32* __restrict__ size) {
     for (u64 l = (u64)blockIdx.x * BLOCK + threadIdx.x; l < L; l += (u64)gridDim.x * BLOCK) {
-        u32 lo = 0, hi = E;
-        while (hi - lo > 1) { const u32 mid = lo + ((hi - lo) >> 1); if (link_first[mid] <= l) lo = mid; else hi = mid; }
-        link_a[l] = lo;
-        size[l] = 10 + decimal_digits(first + lo) + decimal_digits(link_b[l]) + k1_digits;
+        const u32 a = last_segment_with_first_link_le(link_first, E, l);
+        link_a[l] = a;
+        size[l] = link_line_bytes(first + a, link_b[l], k1_digits);
     }
-}
-__global__ __launch_bounds__(BLOCK) void gfa_part_segment_off_kernel(u64 E, u64 first, u32 hdr, const u64* __restrict__ line_off, u64* __restrict__ segment_off) {
-    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < E; i += (u64)gridDim.x * BLOCK) segment_off[i] = line_off[hdr + i] + 3 + decimal_digits(first + i);
 }
 
 int check_gfa_errors(u32 err) {
@@ -355,7 +248,7 @@ int dev_gfa_plan(const GfaGraph& g, GfaPlan& plan, hipStream_t stream) {
             KCHECK_HIP(hipGetLastError());
         }
         KCHECK(dev_scan_counts(size.as<u32>(), R, plan.line_off.as<u64>(), stream));
-        hipLaunchKernelGGL(gfa_segment_off_kernel, grid, blk, 0, stream, E, plan.line_off.as<u64>(), plan.segment_off.as<u64>());
+        hipLaunchKernelGGL(gfa_segment_off_kernel, grid, blk, 0, stream, E, (u64)0, 1u, plan.line_off.as<u64>(), plan.segment_off.as<u64>());
         KCHECK_HIP(hipGetLastError());
     }
     KCHECK_HIP(hipMemcpyAsync(&plan.text_bytes, plan.line_off.as<u64>() + R, 8, hipMemcpyDeviceToHost, stream));
@@ -421,7 +314,7 @@ int dev_gfa_part_plan(const GfaPart& g, GfaPartPlan& plan, hipStream_t stream) {
     KernelScope ks(K_GFA_SIZES, stream, R);
     if (hdr + E) {
         KCHECK(dev_scan_counts(size.as<u32>(), hdr + E, plan.s_line_off.as<u64>(), stream));
-        hipLaunchKernelGGL(gfa_part_segment_off_kernel, grid, blk, 0, stream, E, first, hdr, plan.s_line_off.as<u64>(), plan.segment_off.as<u64>());
+        hipLaunchKernelGGL(gfa_segment_off_kernel, grid, blk, 0, stream, E, first, hdr, plan.s_line_off.as<u64>(), plan.segment_off.as<u64>());
         KCHECK_HIP(hipGetLastError());
         KCHECK_HIP(hipMemcpyAsync(&plan.s_bytes, plan.s_line_off.as<u64>() + hdr + E, 8, hipMemcpyDeviceToHost, stream));
     }
@@ -471,13 +364,13 @@ int katome_dev_gfa_part_arrays(int device, uint32_t k, uint64_t n_edges, const u
     if (!s_bytes || !l_offset || !l_bytes) { set_error("null argument"); return KATOME_E_ARG; }
     *s_bytes = *l_offset = *l_bytes = 0;
     hipStream_t stream = (hipStream_t)stream_;
-    if ((uintptr_t)d_edge_label & 3) { set_error("gfa: d_edge_label must be 4-byte aligned (the kernel reads the aligned words around the bytes it needs)"); return KATOME_E_ARG; }
+    KCHECK(check_label_alignment(d_edge_label));
     const GfaPart g{k, n_edges, d_edge_weight, d_edge_kmers, d_edge_label_off, d_edge_label, label_bytes, first_segment, with_header != 0, d_link_first, d_link_b};
     GfaPartPlan plan;
     KCHECK(dev_gfa_part_plan(g, plan, stream));
     *s_bytes = plan.s_bytes; *l_offset = plan.l_offset(); *l_bytes = plan.l_bytes;
     if (!d_text) return KATOME_OK;
-    if ((n_edges && !d_segment_off) || text_cap < plan.buffer_bytes() || ((uintptr_t)d_text & 15)) {
+    if ((n_edges && !d_segment_off) || !text_fits(plan.buffer_bytes(), text_cap, d_text)) {
         set_error("gfa: %llu + %llu bytes (each rounded up to 16, 16-byte aligned) do not fit the caller's arrays", (unsigned long long)plan.s_bytes,
                   (unsigned long long)plan.l_bytes);
         return KATOME_E_ARG;
@@ -494,19 +387,13 @@ static int builder_contigs_gfa(katome_builder* b, const katome_dev_contigs* c, k
     if (!b || !c || !out) { set_error("null argument"); return KATOME_E_ARG; }
     hipStream_t stream = (hipStream_t)stream_;
     KCHECK_HIP(hipSetDevice(b->s.device));
-    const ShrinkOutput& sh = b->shrunk;
-    if (c->n_edges != sh.n_edges || c->n_nodes != sh.n_nodes || c->d_edge_src != sh.edge_src.as<u64>() || c->d_edge_label != sh.edge_label.as<uint8_t>() ||
-        c->d_edge_label_off != sh.edge_label_off.as<u64>()) {
-        set_error("contigs_gfa: not the result of this builder's last katome_dev_shrink");
-        return KATOME_E_ARG;
-    }
-    if (coverage && (!b->shrunk_cov.valid || b->shrunk_cov.n_edges != sh.n_edges)) {
+    if (!is_last_shrink(b, c)) { set_error("contigs_gfa: not the result of this builder's last katome_dev_shrink"); return KATOME_E_ARG; }
+    if (coverage && (!b->shrunk_cov.valid || b->shrunk_cov.n_edges != b->shrunk.n_edges)) {
         set_error("contigs_gfa_coverage: this builder's last shrink was not a katome_dev_shrink_coverage");
         return KATOME_E_ARG;
     }
     memset(out, 0, sizeof *out);
-    GfaGraph g{b->s.k, sh.n_nodes, sh.n_edges, sh.edge_src.as<u64>(), sh.edge_dst.as<u64>(), sh.edge_weight.as<u32>(), sh.edge_kmers.as<u32>(),
-               sh.edge_label_off.as<u64>(), sh.edge_label.as<uint8_t>(), sh.label_bytes};
+    GfaGraph g = gfa_graph_of(b->s.k, b->shrunk);
     if (coverage) g.cov = GfaCoverage{b->shrunk_cov.kmer_sum.as<u64>(), b->shrunk_cov.kmer_min.as<u32>(), b->shrunk_cov.kmer_max.as<u32>()};
     {
         PhaseScope ps(b->prof, PH_GFA, stream);
@@ -534,33 +421,27 @@ static int gfa_arrays(int device, uint32_t k, uint64_t n_nodes, uint64_t n_edges
     if (!n_links || !text_bytes) { set_error("null argument"); return KATOME_E_ARG; }
     *n_links = *text_bytes = 0;
     hipStream_t stream = (hipStream_t)stream_;
-    if ((uintptr_t)d_edge_label & 3) { set_error("gfa: d_edge_label must be 4-byte aligned (the kernel reads the aligned words around the bytes it needs)"); return KATOME_E_ARG; }
+    KCHECK(check_label_alignment(d_edge_label));
     const GfaGraph g{k, n_nodes, n_edges, d_edge_src, d_edge_dst, d_edge_weight, d_edge_kmers, d_edge_label_off, d_edge_label, label_bytes, cov};
     GfaPlan plan;
     KCHECK(dev_gfa_plan(g, plan, stream));
     *n_links = plan.n_links; *text_bytes = plan.text_bytes;
     if (!d_text) return KATOME_OK;
-    if (!d_segment_off || !d_link_first || text_cap < (plan.text_bytes + 15) / 16 * 16 || ((uintptr_t)d_text & 15)) {
+    if (!d_segment_off || !d_link_first || !text_fits(plan.text_bytes, text_cap, d_text)) {
         set_error("gfa: %llu bytes (rounded up to 16, 16-byte aligned) do not fit the caller's arrays", (unsigned long long)plan.text_bytes);
         return KATOME_E_ARG;
     }
     // KATOME_GFA_TRACE=1: the writer's own time on stderr (there is no builder whose profile could hold it; tools/bench_gfa.py times
     // the S region alone through this entry, on a graph without links)
-    Profiler prof;
-    prof.on = getenv("KATOME_GFA_TRACE") != nullptr;
+    ArraysTrace trace("KATOME_GFA_TRACE", "katome_dev_gfa_arrays");
     {
-        PhaseScope ps(prof, PH_GFA, stream);
+        PhaseScope ps(trace.prof, PH_GFA, stream);
         KCHECK(dev_gfa_write(g, plan, d_text, stream));
     }
     if (n_edges) KCHECK_HIP(hipMemcpyAsync(d_segment_off, plan.segment_off.p, n_edges * 8, hipMemcpyDeviceToDevice, stream));
     KCHECK_HIP(hipMemcpyAsync(d_link_first, plan.link_first.p, (n_edges + 1) * 8, hipMemcpyDeviceToDevice, stream));
     KCHECK_HIP(hipStreamSynchronize(stream));
-    for (const Profiler::Ev& e : prof.evs) {
-        float ms = 0;
-        if (e.phase == K_GFA_WRITE && hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess)
-            fprintf(stderr, "[katome_dev_gfa_arrays] k:gfa_write_kernel %.4f ms, %llu bytes, %llu segments, %llu links\n", ms,
-                    (unsigned long long)plan.text_bytes, (unsigned long long)n_edges, (unsigned long long)plan.n_links);
-    }
+    trace.print(K_GFA_WRITE, K_GFA_WRITE, plan.text_bytes, n_edges, "segments", plan.n_links, "links");
     return KATOME_OK;
 }
 

@@ -11,12 +11,10 @@
 //   contig, path_fill_kernel every path its contig and first piece and every contig its first path (the run index is the difference);
 //   path_size_kernel counts a piece's bytes -- "<id>+," or, on a run's last piece, "<id>+\t*\n", behind the line's head on its first
 //   -- and a third scan gives the 64-bit byte offsets (2^31 - 1 pieces can be tens of GB).
-//   gfa_paths_write_kernel is partitioned by OUTPUT bytes like text_write_kernel and gfa_write_kernel: a workgroup owns TILE bytes
-//   and finds the pieces that overlap them by the workgroup search in the scanned offsets.  A piece is a short record of decimal
-//   numbers, so the tile is written as gfa_write_kernel writes its L region: every piece is formatted ONCE, one thread per piece,
-//   right to left into the LDS image of the tile (gfa_image.h; what falls outside the tile is dropped), and then every lane stores 16
-//   consecutive bytes of the image with one 128-bit store.  Neither a thread per piece nor one per path touches global memory: one
-//   path can be 10^6 pieces and the next 10^6 paths one piece each.
+//   gfa_paths_write_kernel loops over the tile both path texts share (write_piece_tile of gfa_path_lines.h: partitioned by OUTPUT bytes,
+//   every piece formatted once into the LDS image of gfa_image.h, 128-bit stores) with this text's name of a piece: its id and '+'.
+//   Neither a thread per piece nor one per path touches global memory: one path can be 10^6 pieces and the next 10^6 paths one piece
+//   each.
 #include "builder.h"
 #include "gfa_path_lines.h"
 
@@ -78,39 +76,11 @@ __global__ __launch_bounds__(BLOCK) void path_line_off_kernel(u64 P, const u64* 
 __global__ __launch_bounds__(BLOCK) void gfa_paths_write_kernel(const u32* __restrict__ pieces, u32 P, const u64* __restrict__ path_idx, const u64* __restrict__ piece_off,
                                                                 const u64* __restrict__ path_contig, const u64* __restrict__ contig_first_path, u64 total,
                                                                 uint8_t* __restrict__ text) {
-    __shared__ __align__(16) uint8_t s_img[TILE];      // the tile's bytes
-    const u32 tid = threadIdx.x;
-    const u64 n_tiles = (total + TILE - 1) / TILE;
-    for (u64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const u64 base = tile * TILE;
-        const int len = (int)min((u64)TILE, total - base);
-        const u32 p_lo = workgroup_search(piece_off, P, base), p_hi = workgroup_search(piece_off, P, base + len - 1);
-        const u32 n_in = min(p_hi - p_lo + 1, MAX_PIECES);
-        if (tid < 16 && (u32)len + tid < TILE) s_img[(u32)len + tid] = 0;             // (behind the text, up to the next multiple of 16: zeros)
-        for (u32 j = tid; j < n_in; j += BLOCK) {
-            const u32 p = p_lo + j;
-            const u64 path = path_idx[p];
-            int pos = (int)(int64_t)(piece_off[p + 1] - base) - 1;                    // (>= 0: the piece overlaps the tile)
-            if (p + 1 == P || path_idx[p + 2] != path_idx[p + 1]) pos = put_tag_back<4>(s_img, pos, len, tag('+', '\t', '*', '\n', 0, 0));
-            else pos = put_tag_back<2>(s_img, pos, len, tag('+', ',', 0, 0, 0, 0));
-            pos = put_decimal_back(s_img, pos, len, pieces[p] & ~WHOLE);
-            if (path_idx[p + 1] != path && pos >= 0) {                                // the line's head, where it reaches into the tile
-                const u64 c = path_contig[path], r = path - contig_first_path[c];
-                put(s_img, pos--, len, '\t');
-                if (r) { pos = put_decimal_back(s_img, pos, len, r); put(s_img, pos--, len, '.'); }
-                pos = put_decimal_back(s_img, pos, len, c);
-                put_tag_back<3>(s_img, put_tag_back<6>(s_img, pos, len, tag('a', 't', 'o', 'm', 'e', '_')), len, tag('P', '\t', 'k', 0, 0, 0));
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int it = 0; it < STORES; ++it) {
-            const u32 rel = (u32)it * BLOCK * 16 + tid * 16;
-            const u64 o = base + rel;
-            if (o >= total) continue;
-            *(uint4*)(text + o) = *(const uint4*)(s_img + rel);                       // (the buffer is a multiple of 16 bytes)
-        }
-        __syncthreads();                                                              // (the image is rewritten by the next tile)
+    const auto name = [=](u32 p) { return PieceName{pieces[p] & ~WHOLE, '+'}; };
+    for (u64 base = (u64)blockIdx.x * TILE; base < total; base += (u64)gridDim.x * TILE) {
+        const int len = tile_len(base, total);
+        write_piece_tile(name, P, workgroup_search(piece_off, P, base), workgroup_search(piece_off, P, base + len - 1), base, len, path_idx, piece_off, path_contig,
+                         contig_first_path, total, text);
     }
 }
 
@@ -208,29 +178,23 @@ int katome_dev_gfa_paths_arrays(int device, uint64_t n_edges, const uint64_t* d_
     KCHECK(dev_gfa_paths_plan(n_edges, d_edge_src, d_edge_dst, d_pieces, n_pieces, plan, stream));
     counts[0] = plan.n_paths; counts[1] = plan.n_paths - plan.n_contigs; counts[2] = plan.text_bytes;
     if (!d_text) return KATOME_OK;
-    if (!d_path_line_off || !d_path_first_piece || (plan.n_paths && !d_path_contig) || path_cap < plan.n_paths || text_cap < (plan.text_bytes + 15) / 16 * 16 ||
-        ((uintptr_t)d_text & 15)) {
+    if (!d_path_line_off || !d_path_first_piece || (plan.n_paths && !d_path_contig) || path_cap < plan.n_paths ||
+        !text_fits(plan.text_bytes, text_cap, d_text)) {
         set_error("gfa_paths: %llu paths and %llu bytes (rounded up to 16, 16-byte aligned) do not fit the caller's arrays", (unsigned long long)plan.n_paths,
                   (unsigned long long)plan.text_bytes);
         return KATOME_E_ARG;
     }
     // KATOME_GFA_PATHS_TRACE=1: the writer's own time on stderr (there is no builder whose profile could hold it; tools/bench_gfa_paths.py)
-    Profiler prof;
-    prof.on = getenv("KATOME_GFA_PATHS_TRACE") != nullptr;
+    ArraysTrace trace("KATOME_GFA_PATHS_TRACE", "katome_dev_gfa_paths_arrays");
     {
-        PhaseScope ps(prof, PH_GFA_PATHS, stream);
+        PhaseScope ps(trace.prof, PH_GFA_PATHS, stream);
         KCHECK(dev_gfa_paths_write(d_pieces, n_pieces, plan, d_text, stream));
     }
     KCHECK_HIP(hipMemcpyAsync(d_path_line_off, plan.path_line_off.p, (plan.n_paths + 1) * 8, hipMemcpyDeviceToDevice, stream));
     KCHECK_HIP(hipMemcpyAsync(d_path_first_piece, plan.path_first_piece.p, (plan.n_paths + 1) * 8, hipMemcpyDeviceToDevice, stream));
     if (plan.n_paths) KCHECK_HIP(hipMemcpyAsync(d_path_contig, plan.path_contig.p, plan.n_paths * 8, hipMemcpyDeviceToDevice, stream));
     KCHECK_HIP(hipStreamSynchronize(stream));
-    for (const Profiler::Ev& e : prof.evs) {
-        float ms = 0;
-        if (e.phase == K_GFA_PATHS_WRITE && hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess)
-            fprintf(stderr, "[katome_dev_gfa_paths_arrays] k:gfa_paths_write_kernel %.4f ms, %llu bytes, %llu pieces, %llu paths\n", ms,
-                    (unsigned long long)plan.text_bytes, (unsigned long long)n_pieces, (unsigned long long)plan.n_paths);
-    }
+    trace.print(K_GFA_PATHS_WRITE, K_GFA_PATHS_WRITE, plan.text_bytes, n_pieces, "pieces", plan.n_paths, "paths");
     return KATOME_OK;
 }
 
@@ -242,8 +206,7 @@ int katome_dev_collapse_gfa(katome_builder* b, katome_dev_gfa_paths* out, void* 
     memset(out, 0, sizeof *out);
     if (!b->collapse_valid) { set_error("collapse_gfa: no collapse result"); return KATOME_E_ARG; }
     const ShrinkOutput& sh = b->collapse_shrunk;
-    const GfaGraph g{b->s.k, sh.n_nodes, sh.n_edges, sh.edge_src.as<u64>(), sh.edge_dst.as<u64>(), sh.edge_weight.as<u32>(), sh.edge_kmers.as<u32>(),
-                     sh.edge_label_off.as<u64>(), sh.edge_label.as<uint8_t>(), sh.label_bytes};
+    const GfaGraph g = gfa_graph_of(b->s.k, sh);
     GfaPathsOutput& o = b->gfa_paths;
     o.n_segments = o.n_links = o.text_bytes = o.n_paths = o.n_jumps = o.path_bytes = 0;
     {

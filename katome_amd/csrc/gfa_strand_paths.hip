@@ -9,9 +9,8 @@
 //   The plan: strand_piece_kernel maps every piece ONCE into its oriented name rep << 1 | (o == '-') -- the one random read of the
 //   twin map per piece: sizing needs the digits of rep anyway -- and counts its bytes, "<rep><o>," or, on a run's last piece,
 //   "<rep><o>\t*\n", behind the line's head on its first; dev_gfa_paths_offsets scans them into 64-bit byte offsets.
-//   gfa_strand_paths_write_kernel is gfa_paths_write_kernel's scheme on the names (gfa_path_lines.h, gfa_image.h): partitioned by OUTPUT
-//   bytes, every piece formatted once, right to left, into the LDS image of its tile, then one 128-bit store per 16 bytes.  It reads the
-//   names in order: no twin lookup, no 64-bit shift by a variable amount.
+//   gfa_strand_paths_write_kernel loops over the tile both path texts share (write_piece_tile of gfa_path_lines.h) with this text's name
+//   of a piece: the halves of its oriented name.  It reads the names in order: no twin lookup, no 64-bit shift by a variable amount.
 //   Mirrors.  mirror(j) = the smallest q with as many pieces as j and id_q[t] == twin(id_j[n - 1 - t]) for every t; a piece without a
 //   twin matches nothing.  Partitioned by PIECES throughout (one path can be 10^6 pieces and the next 10^6 paths one piece each):
 //   mirror_sig_kernel gives every path two 64-bit signatures, the sum over its pieces of hash(id, t) and of hash(twin id, n - 1 - t) --
@@ -64,37 +63,11 @@ __global__ __launch_bounds__(BLOCK) void strand_piece_kernel(const u32* __restri
 __global__ __launch_bounds__(BLOCK) void gfa_strand_paths_write_kernel(const u32* __restrict__ oname, u32 P, const u64* __restrict__ path_idx,
                                                                        const u64* __restrict__ piece_off, const u64* __restrict__ path_contig,
                                                                        const u64* __restrict__ contig_first_path, u64 total, uint8_t* __restrict__ text) {
-    __shared__ __align__(16) uint8_t s_img[TILE];      // the tile's bytes
-    const u32 tid = threadIdx.x;
-    const u64 n_tiles = (total + TILE - 1) / TILE;
-    for (u64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const u64 base = tile * TILE;
-        const int len = (int)min((u64)TILE, total - base);
-        const u32 p_lo = workgroup_search(piece_off, P, base), p_hi = workgroup_search(piece_off, P, base + len - 1);
-        const u32 n_in = min(p_hi - p_lo + 1, MAX_PIECES);
-        if (tid < 16 && (u32)len + tid < TILE) s_img[(u32)len + tid] = 0;             // (behind the text, up to the next multiple of 16: zeros)
-        for (u32 j = tid; j < n_in; j += BLOCK) {
-            const u32 p = p_lo + j, on = oname[p];
-            const char sign = (on & 1) ? '-' : '+';
-            const u64 path = path_idx[p];
-            int pos = (int)(int64_t)(piece_off[p + 1] - base) - 1;                    // (>= 0: the piece overlaps the tile)
-            if (p + 1 == P || path_idx[p + 2] != path_idx[p + 1]) pos = put_tag_back<4>(s_img, pos, len, tag(sign, '\t', '*', '\n', 0, 0));
-            else pos = put_tag_back<2>(s_img, pos, len, tag(sign, ',', 0, 0, 0, 0));
-            pos = put_decimal_back(s_img, pos, len, on >> 1);
-            if (path_idx[p + 1] != path && pos >= 0) {                                // the line's head, where it reaches into the tile
-                const u64 c = path_contig[path];
-                put_run_head(s_img, pos, len, c, path - contig_first_path[c]);
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int it = 0; it < STORES; ++it) {
-            const u32 rel = (u32)it * BLOCK * 16 + tid * 16;
-            const u64 o = base + rel;
-            if (o >= total) continue;
-            *(uint4*)(text + o) = *(const uint4*)(s_img + rel);                       // (the buffer is a multiple of 16 bytes)
-        }
-        __syncthreads();                                                              // (the image is rewritten by the next tile)
+    const auto name = [=](u32 p) { const u32 on = oname[p]; return PieceName{on >> 1, (on & 1) ? '-' : '+'}; };
+    for (u64 base = (u64)blockIdx.x * TILE; base < total; base += (u64)gridDim.x * TILE) {
+        const int len = tile_len(base, total);
+        write_piece_tile(name, P, workgroup_search(piece_off, P, base), workgroup_search(piece_off, P, base + len - 1), base, len, path_idx, piece_off, path_contig,
+                         contig_first_path, total, text);
     }
 }
 
@@ -292,11 +265,10 @@ int katome_dev_gfa_strand_paths_arrays(int device, uint64_t n_edges, const uint6
     if (E >= 0xFFFFFFFFull) { set_error("gfa_strand_paths: %llu edges, at most 2^32 - 2", (unsigned long long)E); return KATOME_E_UNSUPPORTED; }
     if (E && !d_edge_twin) { set_error("null argument"); return KATOME_E_ARG; }
     // KATOME_GFA_STRAND_PATHS_TRACE=1: the kernels' own times on stderr (there is no builder whose profile could hold them; tools/bench_gfa_strand_paths.py)
-    Profiler prof;
-    prof.on = getenv("KATOME_GFA_STRAND_PATHS_TRACE") != nullptr;
+    ArraysTrace trace("KATOME_GFA_STRAND_PATHS_TRACE", "katome_dev_gfa_strand_paths_arrays");
     GfaStrandPathsPlan plan;
     {
-        PhaseScope ps(prof, PH_GFA_STRAND_PATHS, stream);
+        PhaseScope ps(trace.prof, PH_GFA_STRAND_PATHS, stream);
         DevBuf twin(stream), tail(stream);
         KCHECK(twin.alloc(E * 4)); KCHECK(tail.alloc(16));
         KCHECK_HIP(hipMemsetAsync(tail.p, 0, 16, stream));
@@ -314,7 +286,7 @@ int katome_dev_gfa_strand_paths_arrays(int device, uint64_t n_edges, const uint6
         counts[0] = r.n_paths; counts[1] = r.n_paths - r.n_contigs; counts[2] = r.text_bytes; counts[3] = plan.n_mirrored; counts[4] = plan.n_self_mirror;
         if (!d_text) return KATOME_OK;
         if (!d_path_line_off || !d_path_first_piece || (r.n_paths && (!d_path_contig || !d_path_mirror)) || path_cap < r.n_paths ||
-            text_cap < (r.text_bytes + 15) / 16 * 16 || ((uintptr_t)d_text & 15)) {
+            !text_fits(r.text_bytes, text_cap, d_text)) {
             set_error("gfa_strand_paths: %llu paths and %llu bytes (rounded up to 16, 16-byte aligned) do not fit the caller's arrays", (unsigned long long)r.n_paths,
                       (unsigned long long)r.text_bytes);
             return KATOME_E_ARG;
@@ -328,12 +300,7 @@ int katome_dev_gfa_strand_paths_arrays(int device, uint64_t n_edges, const uint6
         }
     }
     KCHECK_HIP(hipStreamSynchronize(stream));
-    for (const Profiler::Ev& e : prof.evs) {
-        float ms = 0;
-        if (e.phase >= K_GFASP_WRITE && e.phase <= K_GFASP_VERIFY && hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess)
-            fprintf(stderr, "[katome_dev_gfa_strand_paths_arrays] %s %.4f ms, %llu bytes, %llu pieces, %llu paths\n", PHASE_NAMES[e.phase], ms,
-                    (unsigned long long)plan.runs.text_bytes, (unsigned long long)n_pieces, (unsigned long long)plan.runs.n_paths);
-    }
+    trace.print(K_GFASP_WRITE, K_GFASP_VERIFY, plan.runs.text_bytes, n_pieces, "pieces", plan.runs.n_paths, "paths");
     return KATOME_OK;
 }
 
@@ -346,8 +313,7 @@ int katome_dev_collapse_gfa_strands(katome_builder* b, katome_dev_gfa_strand_pat
     memset(out, 0, sizeof *out);
     if (!b->collapse_valid) { set_error("collapse_gfa_strands: no collapse result"); return KATOME_E_ARG; }
     const ShrinkOutput& sh = b->collapse_shrunk;
-    const GfaGraph g{b->s.k, sh.n_nodes, sh.n_edges, sh.edge_src.as<u64>(), sh.edge_dst.as<u64>(), sh.edge_weight.as<u32>(), sh.edge_kmers.as<u32>(),
-                     sh.edge_label_off.as<u64>(), sh.edge_label.as<uint8_t>(), sh.label_bytes};
+    const GfaGraph g = gfa_graph_of(b->s.k, sh);
     GfaStrandPathsOutput& o = b->gfa_strand_paths;
     o.n_segments = o.n_links = o.text_bytes = o.n_unpaired = o.n_self_twins = o.n_paths = o.n_jumps = o.path_bytes = o.n_mirrored = o.n_self_mirror = 0;
     {

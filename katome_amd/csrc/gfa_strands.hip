@@ -17,25 +17,22 @@
 //   Links: gfa.hip's join (dev_gfa_plan, unchanged) gives every (a, b); strand_link_kernel maps it to the smaller of its two spellings
 //   (rep a, o a, rep b, o b) and (rep b, flip o b, rep a, flip o a) -- flip leaves a self-twin at + -- as one key
 //   (x, ox, y, oy); dev_sort and dev_unique leave the distinct links in the order they are written in.
-//   The writer is gfa_write_kernel's scheme (gfa_image.h): partitioned by output bytes, every line formatted once into the LDS image,
-//   bases by 128-bit stores through sixteen_bases.  S lines exist for representatives only (a compacted list), carry two more tags
-//   where there is a twin, and a link's orientation bytes come from its key.
+//   The writer loops over the tile every H/S/L text shares (write_line_tile of gfa_image.h: partitioned by output bytes, every line
+//   formatted once into the LDS image, bases by 128-bit stores) with this text's line description, StrandLines: S lines exist for
+//   representatives only (a compacted list), carry two more tags where there is a twin, and a link's two names and orientation bytes
+//   come from its key.  A line's sizes and the formatting of its fields are gfa_lines.h's, as in gfa.hip.
 //   The merged GFA of the sharded shrink without a gather is not written here.
 #include "builder.h"
 #include "edge_keys.h"
-#include "gfa_image.h"
+#include "gfa_lines.h"
 #include "strand_bits.h"
-#include "text_bases.h"
 
 namespace katome {
 namespace {
 
 constexpr u32 NONE = NO_TWIN;
-// "\tLN:i:<u32>\tKC:i:<u64>\tew:i:<u32>\trc:i:<u32>\trw:i:<u32>\n": the longest tail of an S line
-constexpr int S_TAGS_MAX = 5 * 6 + 10 + 20 + 10 + 10 + 10 + 1;
-constexpr u32 L_LINE_MAX = 10 + 10 + 10 + 10;          // "L\t<x>\t<ox>\t<y>\t<oy>\t<k-1>M\n"
-// (the header's 11 bytes are still the shortest line: "L\t0\t+\t0\t+\t0M\n" has 13 and an S line more, so MAX_LINES holds)
-static_assert(L_LINE_MAX < TILE && HEADER_BYTES <= 13 && S_TAGS_MAX < (int)TILE, "a tile holds at most MAX_LINES lines");
+constexpr int TWIN_TAGS_MAX = 2 * (6 + 10);            // "\trc:i:<u32>\trw:i:<u32>": a twin's tags, between ew and the line's end
+static_assert(S_TAGS_MAX + TWIN_TAGS_MAX < (int)TILE, "a segment's tags fit a tile");
 constexpr u32 VERIFY_WORDS = 4;                        // 16-base words a thread compares per stretch
 constexpr u32 VERIFY_TILE = BLOCK * VERIFY_WORDS;
 
@@ -129,9 +126,7 @@ __global__ __launch_bounds__(BLOCK) void strand_segment_kernel(u32 k, u64 E, con
         if (t < (u32)i) continue;
         const u64 s = rep_off[i];
         const u32 w = weight[i], km = kmers[i], bases = km + k - 1;
-        u32 bytes = 2 + decimal_digits(i) + 1 + bases + 6 + decimal_digits(bases) + 6 + decimal_digits((u64)w * km) + 6 + decimal_digits(w) + 1;
-        if (t != NONE) bytes += 6 + decimal_digits(t) + 6 + decimal_digits(weight[t]);
-        name[s] = (u32)i; size[1 + s] = bytes;
+        name[s] = (u32)i; size[1 + s] = segment_line_bytes(i, bases, (u64)w * km, w, t != NONE ? 6 + decimal_digits(t) + 6 + decimal_digits(weight[t]) : 0);
     }
 }
 
@@ -155,7 +150,7 @@ __global__ __launch_bounds__(BLOCK) void strand_link_size_kernel(u64 L, u32 k1_d
     for (u64 l = (u64)blockIdx.x * BLOCK + threadIdx.x; l < L; l += (u64)gridDim.x * BLOCK) {
         u64 fx, fy;
         link_fields(lk, l, fx, fy);
-        size[l] = 10 + decimal_digits(fx >> 1) + decimal_digits(fy >> 1) + k1_digits;
+        size[l] = link_line_bytes(fx >> 1, fy >> 1, k1_digits);
     }
 }
 // segment s's first link: the first one whose x is not below its name (link_first[S] = L); its first base: behind "S\t<name>\t"
@@ -167,7 +162,7 @@ __global__ __launch_bounds__(BLOCK) void strand_segment_off_kernel(u64 S, u64 L,
         u64 lo = 0, hi = L;
         while (lo < hi) { const u64 mid = lo + ((hi - lo) >> 1); u64 fx, fy; link_fields(lk, mid, fx, fy); if (fx < want) lo = mid + 1; else hi = mid; }
         link_first[s] = lo;
-        segment_off[s] = line_off[1 + s] + 3 + decimal_digits(name[s]);
+        segment_off[s] = segment_first_base(line_off[1 + s], name[s]);
     }
 }
 // the 32-bit names and twins as the 64-bit arrays of the interface (all-ones: no twin)
@@ -175,111 +170,49 @@ __global__ __launch_bounds__(BLOCK) void strand_widen_kernel(u64 n, const u32* _
     for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) { const u32 v = in[i]; out[i] = v == NONE ? ~0ull : (u64)v; }
 }
 
-__device__ __forceinline__ Line load_strand_line(u32 r, u32 S, const uint8_t* __restrict__ label, const u64* __restrict__ label_off, const u32* __restrict__ name,
-                                                 const u64* __restrict__ segment_off, const u64* __restrict__ line_off) {
-    Line ln;
-    const u64 at = line_off[r];
-    ln.total = (u32)(line_off[r + 1] - at);
-    ln.head = ln.total; ln.bases = 0; ln.src = label;
-    if (r >= 1 && r <= S) {
-        const u32 i = name[r - 1];
-        const u64 lo = label_off[i], hi = label_off[i + 1];
-        ln.src = label + lo + 1;
-        ln.bases = 4 * (u32)(hi - lo - 1) - label[lo];
-        ln.head = (u32)(segment_off[r - 1] - at);
+// The line description of the merged text (write_line_tile of gfa_image.h): line 0 the header, line 1 + s representative name[s] --
+// S lines exist for representatives only, carry two more tags where there is a twin --, line 1 + S + l link l, its two names and
+// orientation bytes out of its key
+struct StrandLines {
+    u32 k, S; const u32 *weight, *kmers; const u64* label_off; const uint8_t* label; const u32 *name, *twin; const u64* segment_off; LinkKeys lk;
+    __device__ __forceinline__ bool before_links(u32 r) const { return r <= S; }
+    __device__ __forceinline__ void format(uint8_t* img, u32 r, u64 o, int64_t rel, int64_t end, int len) const {
+        if (r == 0) {
+            put_header_line(img, rel, end, len);
+        } else if (r > S) {
+            u64 fx, fy;
+            link_fields(lk, r - 1 - S, fx, fy);
+            put_link_line(img, end, len, (u32)(fx >> 1), (fx & 1) ? '-' : '+', (u32)(fy >> 1), (fy & 1) ? '-' : '+', k - 1);
+        } else {
+            const u32 i = name[r - 1];
+            put_segment_name<S_NAME_MAX>(img, rel, len, (int)(segment_off[r - 1] - o), i);
+            if (end - (S_TAGS_MAX + TWIN_TAGS_MAX) < len) {
+                const u32 w = weight[i], km = kmers[i], t = twin[i];
+                put_segment_tags(img, end, len, km + k - 1, (u64)w * km, w, [&](int p) {
+                    if (t != NONE) {
+                        p = put_tag_back<6>(img, put_decimal_back(img, p, len, weight[t]), len, tag('\t', 'r', 'w', ':', 'i', ':'));
+                        p = put_tag_back<6>(img, put_decimal_back(img, p, len, t), len, tag('\t', 'r', 'c', ':', 'i', ':'));
+                    }
+                    return p;
+                });
+            }
+        }
     }
-    return ln;
-}
+    __device__ __forceinline__ Line line(u32 r, const u64* __restrict__ line_off) const {
+        Line ln = line_without_bases(line_off, r, label);
+        if (r >= 1 && r <= S) add_bases(ln, label, label_off, name[r - 1], (u32)(segment_off[r - 1] - line_off[r]));
+        return ln;
+    }
+};
 
-// gfa_write_kernel's scheme on the merged text: line 0 the header, line 1 + s representative name[s], line 1 + S + l link l
 __global__ __launch_bounds__(BLOCK) void gfa_strands_write_kernel(u32 k, u32 S, u32 R, const u32* __restrict__ weight, const u32* __restrict__ kmers,
                                                                   const u64* __restrict__ label_off, const uint8_t* __restrict__ label, const u32* __restrict__ name,
                                                                   const u32* __restrict__ twin, const u64* __restrict__ line_off, const u64* __restrict__ segment_off,
                                                                   const LinkKeys lk, u64 total, uint8_t* __restrict__ text) {
-    __shared__ __align__(16) uint8_t s_img[TILE];      // the tile's bytes that are not bases
-    __shared__ uint16_t s_off[MAX_LINES];              // where the tile's lines start, relative to the tile
-    const u32 tid = threadIdx.x;
-    const u64 n_tiles = (total + TILE - 1) / TILE;
-    for (u64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const u64 base = tile * TILE;
-        const int len = (int)min((u64)TILE, total - base);
-        const u32 r_lo = workgroup_search(line_off, R, base), r_hi = workgroup_search(line_off, R, base + len - 1);
-        const u32 n_in = min(r_hi - r_lo + 1, MAX_LINES);
-        if (tid < 16 && (u32)len + tid < TILE) s_img[(u32)len + tid] = 0;             // (behind the text, up to the next multiple of 16: zeros)
-        for (u32 j = tid; j < n_in; j += BLOCK) {
-            const u32 r = r_lo + j;
-            const u64 o = line_off[r];
-            s_off[j] = o > base ? (uint16_t)(o - base) : 0;
-            const int64_t rel = (int64_t)(o - base), end = (int64_t)(line_off[r + 1] - base);      // (end >= 1: the line overlaps the tile)
-            if (r == 0) {
-                put_tag_back<3>(s_img, put_tag_back<6>(s_img, (int)end - 1, len, tag('Z', ':', '1', '.', '0', '\n')), len, tag('V', 'N', ':', 0, 0, 0));
-                put_tag_back<2>(s_img, (int)rel + 1, len, tag('H', '\t', 0, 0, 0, 0));
-            } else if (r > S) {
-                u64 fx, fy;
-                link_fields(lk, r - 1 - S, fx, fy);
-                int p = put_tag_back<2>(s_img, (int)end - 1, len, tag('M', '\n', 0, 0, 0, 0));
-                p = put_decimal_back(s_img, p, len, k - 1);
-                p = put_decimal_back(s_img, put_tag_back<3>(s_img, p, len, tag('\t', (fy & 1) ? '-' : '+', '\t', 0, 0, 0)), len, (u32)(fy >> 1));
-                p = put_decimal_back(s_img, put_tag_back<3>(s_img, p, len, tag('\t', (fx & 1) ? '-' : '+', '\t', 0, 0, 0)), len, (u32)(fx >> 1));
-                put_tag_back<2>(s_img, p, len, tag('L', '\t', 0, 0, 0, 0));
-            } else {
-                const u32 i = name[r - 1];
-                if (rel > -S_NAME_MAX) {                                       // "S\t<i>\t" reaches into the tile
-                    int p = (int)rel + (int)(segment_off[r - 1] - o) - 1;
-                    put(s_img, p--, len, '\t');
-                    p = put_decimal_back(s_img, p, len, i);
-                    put_tag_back<2>(s_img, p, len, tag('S', '\t', 0, 0, 0, 0));
-                }
-                if (end - S_TAGS_MAX < len) {                                  // the tags behind the bases do
-                    const u32 w = weight[i], km = kmers[i], t = twin[i];
-                    int p = (int)end - 1;
-                    put(s_img, p--, len, '\n');
-                    if (t != NONE) {
-                        p = put_tag_back<6>(s_img, put_decimal_back(s_img, p, len, weight[t]), len, tag('\t', 'r', 'w', ':', 'i', ':'));
-                        p = put_tag_back<6>(s_img, put_decimal_back(s_img, p, len, t), len, tag('\t', 'r', 'c', ':', 'i', ':'));
-                    }
-                    p = put_tag_back<6>(s_img, put_decimal_back(s_img, p, len, w), len, tag('\t', 'e', 'w', ':', 'i', ':'));
-                    p = put_tag_back<6>(s_img, put_decimal_back(s_img, p, len, (u64)w * km), len, tag('\t', 'K', 'C', ':', 'i', ':'));
-                    put_tag_back<6>(s_img, put_decimal_back(s_img, p, len, km + k - 1), len, tag('\t', 'L', 'N', ':', 'i', ':'));
-                }
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int it = 0; it < STORES; ++it) {
-            const u32 rel = (u32)it * BLOCK * 16 + tid * 16;
-            const u64 o = base + rel;
-            if (o >= total) continue;
-            u32 lo = 0, hi = n_in;                                           // the line that holds byte o
-            while (hi - lo > 1) { const u32 mid = (lo + hi) >> 1; if (s_off[mid] <= rel) lo = mid; else hi = mid; }
-            u32 r = r_lo + lo;
-            const uint4 img = *(const uint4*)(s_img + rel);
-            uint4 v = img;                                                   // (from the first link on there are no bases)
-            if (r <= S) {
-                u32 at = (u32)(o - line_off[r]);
-                Line ln = load_strand_line(r, S, label, label_off, name, segment_off, line_off);
-                if (at >= ln.head && at - ln.head + 16 <= ln.bases) {
-                    v = sixteen_bases(ln.src, at - ln.head);
-                } else {
-                    const u32 in[4] = {img.x, img.y, img.z, img.w};
-                    u32 w[4] = {0, 0, 0, 0};
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        if (r < R && at >= ln.total) {
-                            ++r; at = 0;
-                            if (r < R) ln = load_strand_line(r, S, label, label_off, name, segment_off, line_off);
-                        }
-                        const bool base_here = r < R && at >= ln.head && at - ln.head < ln.bases;
-                        const u32 c = base_here ? one_base(ln.src, at - ln.head) : (in[i >> 2] >> (8 * (i & 3))) & 0xFF;
-                        w[i >> 2] |= c << (8 * (i & 3));
-                        ++at;
-                    }
-                    v = make_uint4(w[0], w[1], w[2], w[3]);
-                }
-            }
-            *(uint4*)(text + o) = v;                                         // (the buffer is a multiple of 16 bytes)
-        }
-        __syncthreads();                                                     // (the image and s_off are rewritten by the next tile)
+    const StrandLines d{k, S, weight, kmers, label_off, label, name, twin, segment_off, lk};
+    for (u64 base = (u64)blockIdx.x * TILE; base < total; base += (u64)gridDim.x * TILE) {
+        const int len = tile_len(base, total);
+        write_line_tile(d, R, workgroup_search(line_off, R, base), workgroup_search(line_off, R, base + len - 1), base, len, line_off, total, text);
     }
 }
 
@@ -449,15 +382,9 @@ int katome_dev_contigs_gfa_strands(katome_builder* b, const katome_dev_contigs* 
     if (!b || !c || !out) { set_error("null argument"); return KATOME_E_ARG; }
     hipStream_t stream = (hipStream_t)stream_;
     KCHECK_HIP(hipSetDevice(b->s.device));
-    const ShrinkOutput& sh = b->shrunk;
-    if (c->n_edges != sh.n_edges || c->n_nodes != sh.n_nodes || c->d_edge_src != sh.edge_src.as<u64>() || c->d_edge_label != sh.edge_label.as<uint8_t>() ||
-        c->d_edge_label_off != sh.edge_label_off.as<u64>()) {
-        set_error("contigs_gfa_strands: not the result of this builder's last katome_dev_shrink");
-        return KATOME_E_ARG;
-    }
+    if (!is_last_shrink(b, c)) { set_error("contigs_gfa_strands: not the result of this builder's last katome_dev_shrink"); return KATOME_E_ARG; }
     memset(out, 0, sizeof *out);
-    const GfaGraph g{b->s.k, sh.n_nodes, sh.n_edges, sh.edge_src.as<u64>(), sh.edge_dst.as<u64>(), sh.edge_weight.as<u32>(), sh.edge_kmers.as<u32>(),
-                     sh.edge_label_off.as<u64>(), sh.edge_label.as<uint8_t>(), sh.label_bytes};
+    const GfaGraph g = gfa_graph_of(b->s.k, b->shrunk);
     GfaStrandsOutput& r = b->gfa_strands;
     {
         PhaseScope ps(b->prof, PH_GFA_STRANDS, stream);
@@ -478,13 +405,13 @@ int katome_dev_gfa_strands_arrays(int device, uint32_t k, uint64_t n_nodes, uint
     if (!counts) { set_error("null argument"); return KATOME_E_ARG; }
     for (int i = 0; i < 5; ++i) counts[i] = 0;
     hipStream_t stream = (hipStream_t)stream_;
-    if ((uintptr_t)d_edge_label & 3) { set_error("gfa: d_edge_label must be 4-byte aligned (the kernel reads the aligned words around the bytes it needs)"); return KATOME_E_ARG; }
+    KCHECK(check_label_alignment(d_edge_label));
     const GfaGraph g{k, n_nodes, n_edges, d_edge_src, d_edge_dst, d_edge_weight, d_edge_kmers, d_edge_label_off, d_edge_label, label_bytes};
     GfaStrandsPlan plan;
     KCHECK(dev_gfa_strands_plan(g, plan, stream));
     counts[0] = plan.n_segments; counts[1] = plan.n_links; counts[2] = plan.text_bytes; counts[3] = plan.n_unpaired; counts[4] = plan.n_self_twins;
     if (!d_text) return KATOME_OK;
-    if (!d_segment_name || !d_segment_off || !d_link_first || !d_edge_twin || text_cap < (plan.text_bytes + 15) / 16 * 16 || ((uintptr_t)d_text & 15)) {
+    if (!d_segment_name || !d_segment_off || !d_link_first || !d_edge_twin || !text_fits(plan.text_bytes, text_cap, d_text)) {
         set_error("gfa_strands: %llu bytes (rounded up to 16, 16-byte aligned) do not fit the caller's arrays", (unsigned long long)plan.text_bytes);
         return KATOME_E_ARG;
     }
