@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <chrono>
 #include <type_traits>
 #include <vector>
 
@@ -204,6 +205,10 @@ inline unsigned grid_for(uint64_t work_items, unsigned per_block, unsigned cap =
     if (g < 1) g = 1;
     return (unsigned)(g > cap ? cap : g);
 }
+// a grid-stride kernel over n items: workgroups of BLOCK, at most 32 per compute unit
+#define KLAUNCH(kernel, n, stream, ...) hipLaunchKernelGGL(kernel, dim3(grid_for((n), BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, __VA_ARGS__)
+// wall clock, for the stage traces and the host_ms / total_ms of the stats
+inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // a run-time flag as a template argument: f gets it as a std::integral_constant (kernel<decltype(flag)::value>) and returns a status
 template <bool B> using BoolC = std::integral_constant<bool, B>;

@@ -35,7 +35,6 @@ const char* const XPHASE_NAMES[X_COUNT] = {"exchange_records", "exchange_kmers",
 namespace {
 
 // ---- small kernels ---------------------------------------------------------------------------------------------------
-#define KLAUNCH(kernel, n, stream, ...) hipLaunchKernelGGL(kernel, dim3(grid_for((n), BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, __VA_ARGS__)
 #define KLOOP(i, n) for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < (n); i += (u64)gridDim.x * BLOCK)
 
 // every record whose key was not found among the sources (rank == UINT64_MAX): its key and where it stands.  One cursor

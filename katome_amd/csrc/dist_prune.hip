@@ -21,6 +21,21 @@
 //     touched a vertex last speaks for it" decides which removal takes an endpoint with it (prune.hip, death_emit_kernel).
 // No gather: the graph stays sharded, and no index is narrower than 64 bits on the wire or in the replays, so a graph of
 // more than 2^32 edges (BASELINE config 5 in full: 1.1e10) is in range; a rank's own share stays below 2^32 edges.
+//
+// The driver follows the kernels.  DistPrune holds one call's state (the persistent buffers, the Router, the running totals, the
+// stats, the trace), Pass what one pass allocates and more than one step needs.  katome_dist_remove_dead_paths: setup,
+// choose_walk_route [, setup_table], then per pass
+//     walks                    first out-edges; share_changed_words + walks_on_table, or walks_by_hopping
+//     collect_marks            allreduce: marks of all ranks (none: done); the marks -> rank 0
+//     agree_on_edge_replay     rank 0: root_edge_replay; allreduce: removed edges, duplicates, rank 0's status
+//     ask_edge_fates           candidates -> rank 0, two replies
+//     apply_edge_fates
+//     send_losses_and_dies     losses -> targets' owners; barrier allreduce; dies -> rank 0
+//     agree_on_node_replay     rank 0: root_node_replay; allreduce: removed nodes, rank 0's status
+//     ask_node_moves           candidates -> rank 0, one reply
+// and install_result (one question to the targets' owners) and the sum of the stats (allreduce).  Every rank passes through
+// exactly these collectives in this order.  Agreed between the ranks are the checks at the entry and a failure of rank 0's two
+// replays; any other failure of one rank alone (an allocation, say) still leaves the others waiting: ADVICE.md.
 #include <chrono>
 #include <cstring>
 
@@ -378,8 +393,540 @@ static int root_failed(int rank, int neg_status, const char* what) {
     return -neg_status;
 }
 
+// ---- the driver: one call's state, a pass as named steps ----------------------------------------------------------------
+// sections of the KATOME_DIST_PRUNE_TRACE line, in the order a pass goes through them
+enum Section {
+    S_BETWEEN,                                                                  // from one pass's last step to the next one's first (not printed)
+    S_FIRST_OUT,
+    S_WORDS_DELTA, S_ALLGATHER_APPLY, S_INPUT_LIST, S_WALK, S_SCAN_MARKS,       // the table route's walks
+    S_WALKS_MARKS,                // hopping: the walks and their marks, all of them; on the table: the marks routed to their edges' owners
+    S_MARKS_KERNEL, S_MARKS_SEND, S_SORT_REPLAY, S_EDGE_REPLAY,
+    S_EDGE_QUESTIONS, S_APPLY_LOSSES, S_DIES_NODE_REPLAY, S_NODE_QUESTIONS,
+    S_COUNT
+};
+
+// What a pass allocates and more than one step needs.  All of it goes at the end of the pass and nothing of it sooner, except
+// rank 0's seven edge tables: released as soon as the edge questions are answered.
+struct Pass {
+    Routed marks;                                                // at rank 0: every rank's marked (position, count) pairs
+    DevBuf victims, to_e, from_e, vict_sorted, vict_ord, from_sorted, from_idx;      // rank 0: the edge replay, as sorted tables to look up
+    ReplayScratch sc;
+    uint64_t m_removed = 0, E_new = 0, n_moves = 0, dups = 0;
+    DevBuf q, who, ans_ord, ans_pos;                             // this rank's candidate edges: position, local index, the two answers
+    uint64_t n_q = 0;
+    DevBuf dead_e, dead_t, msgA, msgB;                           // its edges that die, their removal numbers, the messages to their targets' owners
+    uint64_t n_dead = 0;
+    Routed losses;                                               // ... as they arrive here
+    DevBuf X, Y;
+    Routed dies;                                                 // at rank 0: (2 * removal + role, node position) of every endpoint that goes
+    DevBuf to_n, from_n, nfrom_sorted, nfrom_idx;                // rank 0: the node replay
+    uint64_t n_nmoves = 0, N_new = 0;
+    explicit Pass(hipStream_t s)
+        : marks(s), victims(s), to_e(s), from_e(s), vict_sorted(s), vict_ord(s), from_sorted(s), from_idx(s), sc(s), q(s), who(s), ans_ord(s), ans_pos(s),
+          dead_e(s), dead_t(s), msgA(s), msgB(s), losses(s), X(s), Y(s), dies(s), to_n(s), from_n(s), nfrom_sorted(s), nfrom_idx(s) {}
+};
+
+struct DistPrune {
+    katome_dist_builder* const d; katome_builder* const b; const hipStream_t stream;
+    Router router;
+    const int rank, world;
+    const uint32_t nw, k, two_k;
+    const uint64_t E, N, n_src;                       // this rank's share; its nodes [0, n_src) have out-edges
+    const u64 *lsrc, *drank, *dlocal;                 // every edge's source as a local node, its target as (owner rank, local node there)
+    const u64* edst;                                  // ... and as a first-seen node id (the call installs new arrays at the end)
+    const uint64_t TN0, per_rank;                     // the directory and the marks are sharded by first-seen node id, per_rank ids each
+    uint32_t pos_bits = 1;                            // positions (of edges and of nodes alike) fit this many bits: what rank 0's sorts and look-ups work on
+    bool use_table = true;
+    // ages: the first-seen index an edge was given never changes; `pos` / `npos` is where an edge / a node sits now
+    DevBuf age, pos, alive_e, mult, start, npos, indeg, outdeg, first_out, last_touch, alive_n, cursors;
+    DevBuf w_table, w_now, w_held, ngid0, dir;        // the table route: every rank's copy, this rank's words now / as the others hold them, ids, directory
+    uint64_t TE, TN;                                  // edges and nodes of the whole graph, as the passes shrink it
+    katome_prune_stats st;
+    const bool trace;
+    double t_sec[S_COUNT] = {0}, t_mark = 0;
+
+    DistPrune(katome_dist_builder* d_, hipStream_t s, bool trace_)
+        : d(d_), b(d_->b), stream(s), router(d_, s), rank(d_->rank()), world(d_->world()), nw(d_->nw), k(d_->s.k), two_k(2 * d_->s.k), E(d_->n_edges),
+          N(d_->n_nodes), n_src(d_->n_src), lsrc(d_->edge_lsrc.as<u64>()), drank(d_->edge_drank.as<u64>()), dlocal(d_->edge_dlocal.as<u64>()),
+          edst(d_->edge_dst.as<u64>()), TN0(d_->total_nodes), per_rank(std::max<uint64_t>(1, (TN0 + world - 1) / world)), age(s), pos(s), alive_e(s),
+          mult(s), start(s), npos(s), indeg(s), outdeg(s), first_out(s), last_touch(s), alive_n(s), cursors(s), w_table(s), w_now(s), w_held(s), ngid0(s),
+          dir(s), TE(d_->total_edges), TN(d_->total_nodes), trace(trace_) {
+        memset(&st, 0, sizeof st);
+        while (pos_bits < 64 && ((std::max(d->total_edges, d->total_nodes) + 1) >> pos_bits)) ++pos_bits;
+    }
+    // (synchronizes, so only under the trace)
+    void lap(Section s) { if (trace) { (void)hipStreamSynchronize(stream); const double t = now_ms(); t_sec[s] += t - t_mark; t_mark = t; } }
+
+    // ---- the three patterns --------------------------------------------------------------------------------------------
+    // a launch that appends through cursors: they are reset, `launch` gets them, and the one or two counts it declares are read back
+    template <class F> int counted(F launch, uint64_t* c0, uint64_t* c1 = nullptr) {
+        KCHECK_HIP(hipMemsetAsync(cursors.p, 0, 64, stream));
+        launch(cursors.as<unsigned long long>());
+        KCHECK_HIP(hipGetLastError());
+        uint64_t h[2] = {0, 0};
+        KCHECK_HIP(hipMemcpyAsync(h, cursors.p, c1 ? 16 : 8, hipMemcpyDeviceToHost, stream));
+        KCHECK_HIP(hipStreamSynchronize(stream));
+        *c0 = h[0];
+        if (c1) *c1 = h[1];
+        return KATOME_OK;
+    }
+    // a column of n positions in ascending order, with where each stood: sorted[i] = col[idx[i]]
+    int sorted_with_index(const DevBuf& col, uint64_t n, DevBuf& sorted, DevBuf& idx) {
+        KCHECK(sorted.alloc((n + 1) * 8)); KCHECK(idx.alloc((n + 1) * 4));
+        if (n) {
+            KCHECK_HIP(hipMemcpyAsync(sorted.p, col.p, n * 8, hipMemcpyDeviceToDevice, stream));
+            KLAUNCH(iota32_kernel, n, stream, idx.as<u32>(), n);
+            KCHECK(dev_sort(sorted.as<u64>(), idx.as<u32>(), n, 1, pos_bits, stream));
+        }
+        return KATOME_OK;
+    }
+    // found[i] = where the i-th question stands in sorted[n], NONE64 if it is not there
+    int rank_or_none(const DevBuf& sorted, uint64_t n, const Routed& asked, DevBuf& found) {
+        if (n) KCHECK(dev_rank(sorted.as<u64>(), n, 1, pos_bits, asked.a.as<u64>(), asked.n, found.as<u64>(), stream));
+        else KCHECK_HIP(hipMemsetAsync(found.p, 0xFF, asked.n * 8, stream));
+        return KATOME_OK;
+    }
+    // ... and for a table of moves: out[i] = where what sits at the asked position goes, NONE64 if it stays
+    int answer_moves(const DevBuf& from_sorted, const DevBuf& from_idx, const DevBuf& to, uint64_t n, const Routed& asked, DevBuf& found, DevBuf& out) {
+        KCHECK(rank_or_none(from_sorted, n, asked, found));
+        KLAUNCH(answer_to_kernel, asked.n, stream, found.as<u64>(), asked.n, from_idx.as<u32>(), to.as<u64>(), out.as<u64>());
+        return KATOME_OK;
+    }
+
+    // ---- once per call ---------------------------------------------------------------------------------------------------
+    // allocations, ages and positions, run starts, degrees (in-degrees: one message per edge to its target's owner; kept current afterwards)
+    int setup() {
+        KCHECK(router.init());
+        KCHECK(age.alloc((E + 1) * 8)); KCHECK(pos.alloc((E + 1) * 8)); KCHECK(alive_e.alloc(E + 16)); KCHECK(mult.alloc((E + 1) * 4));
+        KCHECK(start.alloc((n_src + 2) * 8));
+        KCHECK(npos.alloc((N + 1) * 8)); KCHECK(indeg.alloc((N + 1) * 4)); KCHECK(outdeg.alloc((N + 1) * 4)); KCHECK(first_out.alloc((n_src + 1) * 4));
+        KCHECK(last_touch.alloc((N + 1) * 4)); KCHECK(alive_n.alloc(N + 16)); KCHECK(cursors.alloc(64));
+        if (E) {
+            // (after a stage that removed edges the ages are kept in edge_age: a position is no age any more)
+            KCHECK_HIP(hipMemcpyAsync(age.p, d->edge_age.p ? d->edge_age.p : d->edge_gid.p, E * 8, hipMemcpyDeviceToDevice, stream));
+            KCHECK_HIP(hipMemcpyAsync(pos.p, d->edge_gid.p, E * 8, hipMemcpyDeviceToDevice, stream));
+            KCHECK_HIP(hipMemsetAsync(alive_e.p, 1, E, stream));
+            KCHECK_HIP(hipMemsetAsync(mult.p, 0, E * 4, stream));
+        }
+        KLAUNCH(run_start_kernel, E + 1, stream, lsrc, E, n_src, start.as<u64>());
+        if (N) {
+            KCHECK_HIP(hipMemcpyAsync(npos.p, d->node_gid.p, N * 8, hipMemcpyDeviceToDevice, stream));
+            KLAUNCH(node_init_kernel, N, stream, N, n_src, start.as<u64>(), outdeg.as<u32>(), indeg.as<u32>(), last_touch.as<u32>(), alive_n.as<unsigned char>());
+        }
+        KCHECK_HIP(hipGetLastError());
+        DevBuf msg(stream);
+        KCHECK(msg.alloc((E + 1) * 8));
+        if (E) KLAUNCH(target_msg_kernel, E, stream, drank, dlocal, E, msg.as<u64>());
+        Routed r(stream);
+        KCHECK(router.send(msg.as<u64>(), nullptr, E, r));
+        if (r.n) KLAUNCH(indeg_add_kernel, r.n, stream, r.a.as<u64>(), r.n, indeg.as<u32>());
+        KCHECK_HIP(hipGetLastError());
+        return KATOME_OK;
+    }
+    // The walks: on a replicated successor table when every rank has room for one word per node of the whole graph (the
+    // default), else walkers that hop from owner to owner (KATOME_DIST_PRUNE_WALKS=table|hop overrides; all ranks agree)
+    int choose_walk_route() {
+        size_t free_b = 0, total_b = 0;
+        KCHECK_HIP(hipMemGetInfo(&free_b, &total_b));
+        free_b += dev_cached_bytes();
+        uint64_t ok = (TN0 + 1) * 8 + (N + 1) * 24 + per_rank * 8 + (4ull << 30) < free_b ? 1 : 0;
+        if (const char* e = getenv("KATOME_DIST_PRUNE_WALKS")) ok = strcmp(e, "hop") == 0 ? 0 : strcmp(e, "table") == 0 ? 1 : ok;
+        KCHECK(d->comm->allreduce(&ok, 1, OP_MIN));
+        use_table = ok != 0;
+        return KATOME_OK;
+    }
+    // the table route's words (all 0: no live node's word is, so the first pass sends them all) and its directory, sharded by node
+    // id: where each node lives
+    int setup_table() {
+        KCHECK(w_table.alloc((TN0 + 1) * 8)); KCHECK(w_now.alloc((N + 1) * 8)); KCHECK(w_held.alloc((N + 1) * 8)); KCHECK(ngid0.alloc((N + 1) * 8));
+        KCHECK(dir.alloc((per_rank + 1) * 8));
+        KCHECK_HIP(hipMemsetAsync(w_table.p, 0, (TN0 + 1) * 8, stream));
+        KCHECK_HIP(hipMemsetAsync(w_held.p, 0, (N + 1) * 8, stream));
+        if (N) KCHECK_HIP(hipMemcpyAsync(ngid0.p, d->node_gid.p, N * 8, hipMemcpyDeviceToDevice, stream));
+        DevBuf da(stream), db(stream);
+        KCHECK(da.alloc((N + 1) * 8)); KCHECK(db.alloc((N + 1) * 8));
+        if (N) KLAUNCH(dir_msg_kernel, N, stream, N, (u64)rank, ngid0.as<u64>(), per_rank, da.as<u64>(), db.as<u64>());
+        Routed r(stream);
+        KCHECK(router.send(da.as<u64>(), db.as<u64>(), N, r));
+        if (r.n) KLAUNCH(dir_fill_kernel, r.n, stream, r.a.as<u64>(), r.b.as<u64>(), r.n, (u64)rank * per_rank, dir.as<u64>());
+        KCHECK_HIP(hipGetLastError());
+        KCHECK_HIP(hipStreamSynchronize(stream));
+        return KATOME_OK;
+    }
+
+    // ---- the walks of a pass: every dead walk's edges counted in mult ------------------------------------------------------
+    int walks() {
+        lap(S_BETWEEN);
+        if (n_src) KLAUNCH(first_out_kernel, n_src, stream, n_src, start.as<u64>(), age.as<u64>(), alive_e.as<unsigned char>(), first_out.as<u32>());
+        lap(S_FIRST_OUT);
+        if (use_table) {
+            KCHECK(share_changed_words());
+            KCHECK(walks_on_table());
+        } else {
+            KCHECK(walks_by_hopping());
+        }
+        lap(S_WALKS_MARKS);
+        return KATOME_OK;
+    }
+    // the words of this rank's nodes that changed -> every rank's copy of the table
+    int share_changed_words() {
+        if (N) KLAUNCH(own_words_kernel, N, stream, N, n_src, first_out.as<u32>(), edst, indeg.as<u32>(), alive_n.as<unsigned char>(), w_now.as<u64>());
+        DevBuf delta(stream), all_delta(stream);
+        KCHECK(delta.alloc((N + 1) * 16));
+        uint64_t n_mine = 0, n_delta = 0;
+        KCHECK(counted([&](auto* c) { if (N) KLAUNCH_T(delta_kernel, N, stream, N, w_now.as<u64>(), w_held.as<u64>(), ngid0.as<u64>(), delta.as<u64>(), c); }, &n_mine));
+        lap(S_WORDS_DELTA);
+        KCHECK(router.allgather(delta.p, n_mine, 16, all_delta, &n_delta));
+        if (n_delta) KLAUNCH(apply_words_kernel, n_delta, stream, all_delta.as<u64>(), n_delta, w_table.as<u64>());
+        delta.release(); all_delta.release();
+        lap(S_ALLGATHER_APPLY);
+        return KATOME_OK;
+    }
+    // walks from every vertex without incoming edges, local; the vertices the dead ones pass -> the directory rank of each -> its
+    // owner, where its first out-edge is counted
+    int walks_on_table() {
+        DevBuf inputs(stream), len(stream), offs(stream), marks(stream);
+        KCHECK(inputs.alloc((N + 1) * 4));
+        uint64_t n_in = 0, n_dead_walks = 0, n_marks = 0;
+        KCHECK(counted([&](auto* c) { if (N) KLAUNCH_T(input_list_kernel, N, stream, N, indeg.as<u32>(), outdeg.as<u32>(), alive_n.as<unsigned char>(), inputs.as<u32>(), c); }, &n_in));
+        st.walks += n_in;
+        lap(S_INPUT_LIST);
+        KCHECK(len.alloc((n_in + 1) * 4)); KCHECK(offs.alloc((n_in + 2) * 8));
+        KCHECK(counted([&](auto* c) { if (n_in) KLAUNCH(walk_table_kernel, n_in, stream, inputs.as<u32>(), n_in, ngid0.as<u64>(), w_table.as<u64>(), two_k, len.as<u32>(), c); }, &n_dead_walks));
+        st.dead_walks += n_dead_walks;
+        lap(S_WALK);
+        if (n_in) {
+            KCHECK(dev_scan_counts(len.as<u32>(), n_in, offs.as<u64>(), stream));
+            KCHECK_HIP(hipMemcpyAsync(&n_marks, offs.as<u64>() + n_in, 8, hipMemcpyDeviceToHost, stream));
+            KCHECK_HIP(hipStreamSynchronize(stream));
+        }
+        KCHECK(marks.alloc((n_marks + 1) * 8));
+        if (n_marks) KLAUNCH(walk_marks_kernel, n_in, stream, inputs.as<u32>(), n_in, ngid0.as<u64>(), w_table.as<u64>(), len.as<u32>(), offs.as<u64>(), per_rank, marks.as<u64>());
+        KCHECK_HIP(hipGetLastError());
+        lap(S_SCAN_MARKS);
+        Routed at_dir(stream), at_owner(stream);
+        KCHECK(router.send(marks.as<u64>(), nullptr, n_marks, at_dir));
+        DevBuf fwd(stream);
+        KCHECK(fwd.alloc((at_dir.n + 1) * 8));
+        if (at_dir.n) KLAUNCH(dir_forward_kernel, at_dir.n, stream, at_dir.a.as<u64>(), at_dir.n, (u64)rank * per_rank, dir.as<u64>(), fwd.as<u64>());
+        KCHECK_HIP(hipGetLastError());
+        KCHECK(router.send(fwd.as<u64>(), nullptr, at_dir.n, at_owner));
+        if (at_owner.n) KLAUNCH(mark_nodes_kernel, at_owner.n, stream, at_owner.a.as<u64>(), at_owner.n, first_out.as<u32>(), mult.as<u32>());
+        KCHECK_HIP(hipGetLastError());
+        return KATOME_OK;
+    }
+    // without room for the table: walkers hop from owner to owner, then the dead walks again from their start vertices to collect
+    // their edges.  One exchange per step; its count matrix tells every rank whether any walker moved anywhere (no agreement round
+    // of its own), so all ranks leave a loop after the same step
+    int walks_by_hopping() {
+        DevBuf A(stream), B(stream), deadv(stream);
+        uint64_t n_deadv = 0;
+        Routed arrivals(stream);
+        KCHECK(hop_walks(A, B, arrivals, deadv, &n_deadv));
+        st.dead_walks += n_deadv;
+        return hop_marks(deadv, n_deadv);
+    }
+    int hop_walks(DevBuf& A, DevBuf& B, Routed& arrivals, DevBuf& deadv, uint64_t* n_deadv_out) {
+        KCHECK(A.alloc((N + 1) * 8)); KCHECK(B.alloc((N + 1) * 8));
+        uint64_t n_walk = 0, n_deadv = 0, deadv_cap = 0;
+        KCHECK(counted([&](auto* c) { if (N) KLAUNCH(input_kernel, N, stream, N, (u64)rank, indeg.as<u32>(), outdeg.as<u32>(), alive_n.as<unsigned char>(), A.as<u64>(), B.as<u64>(), c); }, &n_walk));
+        st.walks += n_walk;
+        const u64 *wA = A.as<u64>(), *wB = B.as<u64>();
+        for (uint32_t step = 0;; ++step) {
+            if (step > two_k) { set_error("distributed pruning: a walk did not end within 2k steps"); return KATOME_E_DEVICE; }
+            DevBuf oA(stream), oB(stream);
+            KCHECK(oA.alloc((n_walk + 1) * 8)); KCHECK(oB.alloc((n_walk + 1) * 8));
+            if (n_deadv + n_walk > deadv_cap) {                              // the verdicts collected on this rank so far + this step's
+                DevBuf bigger(stream);
+                deadv_cap = (n_deadv + n_walk) * 2 + 1024;
+                KCHECK(bigger.alloc(deadv_cap * 8));
+                if (n_deadv) KCHECK_HIP(hipMemcpyAsync(bigger.p, deadv.p, n_deadv * 8, hipMemcpyDeviceToDevice, stream));
+                const size_t bytes = bigger.bytes;
+                deadv.adopt(bigger.take(), bytes);
+            }
+            uint64_t n_go = 0, n_die = 0;
+            if (n_walk) KCHECK(counted([&](auto* c) {
+                KLAUNCH(walk_step_kernel, n_walk, stream, wA, wB, n_walk, step ? 1u : 0u, two_k, indeg.as<u32>(), outdeg.as<u32>(), first_out.as<u32>(),
+                        drank, dlocal, oA.as<u64>(), oB.as<u64>(), c, deadv.as<u64>() + n_deadv, c + 1);
+            }, &n_go, &n_die));
+            n_deadv += n_die;
+            KCHECK(router.send(oA.as<u64>(), oB.as<u64>(), n_go, arrivals));
+            wA = arrivals.a.as<u64>(); wB = arrivals.b.as<u64>(); n_walk = arrivals.n;
+            if (arrivals.moved == 0) break;
+        }
+        *n_deadv_out = n_deadv;
+        return KATOME_OK;
+    }
+    int hop_marks(const DevBuf& deadv, uint64_t n_deadv) {
+        Routed m(stream);
+        KCHECK(router.send(deadv.as<u64>(), nullptr, n_deadv, m));
+        const u64* wM = m.a.as<u64>();
+        uint64_t n_m = m.n;
+        Routed arrived(stream);
+        for (uint32_t step = 0;; ++step) {
+            if (step > two_k) { set_error("distributed pruning: a marking walk did not end within 2k steps"); return KATOME_E_DEVICE; }
+            DevBuf oM(stream);
+            KCHECK(oM.alloc((n_m + 1) * 8));
+            uint64_t n_go = 0;
+            if (n_m) KCHECK(counted([&](auto* c) {       // (synchronises: the list just walked may be given up below)
+                KLAUNCH(mark_step_kernel, n_m, stream, wM, n_m, first_out.as<u32>(), drank, dlocal, mult.as<u32>(), oM.as<u64>(), c);
+            }, &n_go));
+            KCHECK(router.send(oM.as<u64>(), nullptr, n_go, arrived));
+            wM = arrived.a.as<u64>(); n_m = arrived.n;
+            if (arrived.moved == 0) break;
+        }
+        return KATOME_OK;
+    }
+
+    // ---- the edges of a pass ------------------------------------------------------------------------------------------------
+    // this rank's marked (position, count) pairs; all ranks agree on how many there are in all.  None: "if to_remove.is_empty() ...
+    // Graph is pruned" (pruner.rs:69-72), the caller leaves.  Else they go to rank 0 (top byte 0)
+    int collect_marks(Pass& p, uint64_t* u_local, uint64_t* u_total) {
+        DevBuf mp(stream), mm(stream);
+        KCHECK(mp.alloc((E + 1) * 8)); KCHECK(mm.alloc((E + 1) * 8));
+        uint64_t n_marked = 0;
+        KCHECK(counted([&](auto* c) { if (E) KLAUNCH_T(marks_kernel, E, stream, mult.as<u32>(), pos.as<u64>(), E, mp.as<u64>(), mm.as<u64>(), c, c + 1); }, u_local, &n_marked));
+        st.marked += n_marked;
+        *u_total = *u_local;
+        KCHECK(d->comm->allreduce(u_total, 1, OP_SUM));
+        if (*u_total == 0) return KATOME_OK;
+        lap(S_MARKS_KERNEL);
+        KCHECK(router.send(mp.as<u64>(), mm.as<u64>(), *u_local, p.marks));
+        lap(S_MARKS_SEND);
+        mp.release(); mm.release();
+        return KATOME_OK;
+    }
+    // rank 0 replays remove_paths' swap_removes: the victims by position with their removal numbers, the moves by where they come from
+    int root_edge_replay(Pass& p) {
+        const uint64_t u = p.marks.n;
+        DevBuf m32(stream);
+        KCHECK(m32.alloc((u + 1) * 4));
+        KLAUNCH(narrow_kernel, u, stream, p.marks.b.as<u64>(), u, m32.as<u32>());
+        KCHECK(dev_sort(p.marks.a.as<u64>(), m32.as<u32>(), u, 1, pos_bits, stream));
+        KCHECK(dev_replay_edges64(p.marks.a.as<u64>(), m32.as<u32>(), u, TE, p.sc, p.victims, p.to_e, p.from_e, &p.m_removed, &p.E_new, &p.n_moves, &p.dups, stream));
+        lap(S_SORT_REPLAY);
+        if (p.m_removed >= 0xFFFFFFFFull) { set_error("more than 2^32 edges removed in one pass"); return KATOME_E_UNSUPPORTED; }
+        KCHECK(sorted_with_index(p.victims, p.m_removed, p.vict_sorted, p.vict_ord));
+        KCHECK(sorted_with_index(p.from_e, p.n_moves, p.from_sorted, p.from_idx));
+        KCHECK_HIP(hipGetLastError());
+        return KATOME_OK;
+    }
+    // What fails on rank 0 alone must not leave the others waiting in the next collective: its status travels with the counts every
+    // rank agrees on, and all of them return it
+    int agree_on_edge_replay(Pass& p) {
+        p.E_new = TE;
+        int root_rc = rank == 0 ? root_edge_replay(p) : KATOME_OK;
+        if (rank == 0 && root_rc == KATOME_OK && fail_at("edges")) { set_error("distributed pruning: KATOME_DIST_PRUNE_FAIL=edges"); root_rc = KATOME_E_UNSUPPORTED; }
+        lap(S_EDGE_REPLAY);
+        uint64_t agreed[3] = {rank == 0 && root_rc == KATOME_OK ? TE - p.E_new : 0, rank == 0 ? p.dups : 0, (uint64_t)(-root_rc)};
+        KCHECK(d->comm->allreduce(agreed, 3, OP_MAX));
+        if (agreed[2]) return root_failed(rank, (int)agreed[2], "the replay of the removed edges");
+        p.m_removed = agreed[0]; p.E_new = TE - p.m_removed;
+        st.removed_edges += p.m_removed; st.removed_by_duplicates += agreed[1];
+        return KATOME_OK;
+    }
+    // every rank asks for the fate of its candidate edges: its removal number if it dies, its new position if it moves
+    int ask_edge_fates(Pass& p) {
+        KCHECK(p.q.alloc((E + 1) * 8)); KCHECK(p.who.alloc((E + 1) * 4));
+        KCHECK(counted([&](auto* c) {
+            if (E) KLAUNCH_T(edge_cand_kernel, E, stream, mult.as<u32>(), pos.as<u64>(), alive_e.as<unsigned char>(), E, p.E_new, p.q.as<u64>(), p.who.as<u32>(), c);
+        }, &p.n_q));
+        KCHECK(p.ans_ord.alloc((p.n_q + 1) * 8)); KCHECK(p.ans_pos.alloc((p.n_q + 1) * 8));
+        {
+            Routed asked(stream);
+            KCHECK(router.send(p.q.as<u64>(), nullptr, p.n_q, asked));
+            DevBuf found(stream), a1(stream), a2(stream);
+            KCHECK(found.alloc((asked.n + 1) * 8)); KCHECK(a1.alloc((asked.n + 1) * 8)); KCHECK(a2.alloc((asked.n + 1) * 8));
+            if (asked.n) {                                                   // (rank 0 only)
+                KCHECK(rank_or_none(p.vict_sorted, p.m_removed, asked, found));
+                KLAUNCH(answer_u32_kernel, asked.n, stream, found.as<u64>(), asked.n, p.vict_ord.as<u32>(), a1.as<u64>());
+                KCHECK(answer_moves(p.from_sorted, p.from_idx, p.to_e, p.n_moves, asked, found, a2));
+                KCHECK_HIP(hipGetLastError());
+            }
+            KCHECK(router.reply(asked, a1.as<u64>(), p.ans_ord.as<u64>()));
+            KCHECK(router.reply(asked, a2.as<u64>(), p.ans_pos.as<u64>()));
+        }
+        p.victims.release(); p.to_e.release(); p.from_e.release(); p.vict_sorted.release(); p.vict_ord.release(); p.from_sorted.release(); p.from_idx.release();
+        lap(S_EDGE_QUESTIONS);
+        return KATOME_OK;
+    }
+    // apply the answers: dead edges, their sources' degrees here, the messages for their targets' owners
+    int apply_edge_fates(Pass& p) {
+        const uint64_t n_q = p.n_q;
+        KCHECK(p.dead_e.alloc((n_q + 1) * 4)); KCHECK(p.dead_t.alloc((n_q + 1) * 4)); KCHECK(p.msgA.alloc((n_q + 1) * 8)); KCHECK(p.msgB.alloc((n_q + 1) * 8));
+        return counted([&](auto* c) {
+            if (!n_q) return;
+            KLAUNCH(edge_apply_kernel, n_q, stream, p.who.as<u32>(), p.ans_ord.as<u64>(), p.ans_pos.as<u64>(), n_q, (u64)rank, pos.as<u64>(), alive_e.as<unsigned char>(),
+                    lsrc, drank, dlocal, outdeg.as<u32>(), last_touch.as<u32>(), p.dead_e.as<u32>(), p.dead_t.as<u32>(), p.msgA.as<u64>(), p.msgB.as<u64>(), c);
+            KLAUNCH(clear_marks_kernel, n_q, stream, p.who.as<u32>(), n_q, mult.as<u32>());
+        }, &p.n_dead);
+    }
+
+    // ---- the nodes of a pass ------------------------------------------------------------------------------------------------
+    // the targets' owners learn of their losses; once every rank has applied every loss (the barrier), each removal's endpoints
+    // that go with it -> rank 0
+    int send_losses_and_dies(Pass& p) {
+        const uint64_t n_dead = p.n_dead;
+        Routed& losses = p.losses;
+        KCHECK(router.send(p.msgA.as<u64>(), p.msgB.as<u64>(), n_dead, losses));
+        if (losses.n) KLAUNCH(target_loss_kernel, losses.n, stream, losses.a.as<u64>(), losses.b.as<u64>(), losses.n, indeg.as<u32>(), last_touch.as<u32>());
+        KCHECK_HIP(hipGetLastError());
+        KCHECK_HIP(hipStreamSynchronize(stream));
+        { uint64_t bar = 0; KCHECK(d->comm->allreduce(&bar, 1, OP_MAX)); }   // every rank has applied every loss before anyone decides who dies
+        lap(S_APPLY_LOSSES);
+        KCHECK(p.X.alloc((n_dead + losses.n + 1) * 8)); KCHECK(p.Y.alloc((n_dead + losses.n + 1) * 8));
+        uint64_t n_dies = 0;
+        KCHECK(counted([&](auto* c) {
+            if (n_dead) KLAUNCH(die_src_kernel, n_dead, stream, p.dead_e.as<u32>(), p.dead_t.as<u32>(), n_dead, lsrc, indeg.as<u32>(), outdeg.as<u32>(), last_touch.as<u32>(),
+                                npos.as<u64>(), alive_n.as<unsigned char>(), p.X.as<u64>(), p.Y.as<u64>(), c);
+            if (losses.n) KLAUNCH(die_dst_kernel, losses.n, stream, losses.a.as<u64>(), losses.b.as<u64>(), losses.n, indeg.as<u32>(), outdeg.as<u32>(), last_touch.as<u32>(),
+                                  npos.as<u64>(), alive_n.as<unsigned char>(), p.X.as<u64>(), p.Y.as<u64>(), c);
+            if (n_dead) KLAUNCH(untouch_src_kernel, n_dead, stream, p.dead_e.as<u32>(), n_dead, lsrc, last_touch.as<u32>());
+            if (losses.n) KLAUNCH(untouch_dst_kernel, losses.n, stream, losses.a.as<u64>(), losses.n, last_touch.as<u32>());
+        }, &n_dies));
+        return router.send(p.X.as<u64>(), p.Y.as<u64>(), n_dies, p.dies);
+    }
+    // rank 0 replays remove_single_node: the moves of the tail nodes that stay, by where they come from
+    int root_node_replay(Pass& p) {
+        const uint64_t m = p.m_removed;
+        DevBuf die(stream);
+        NodeReplayScratch nsc(stream);
+        KCHECK(die.alloc((2 * m + 2) * 8));
+        KLAUNCH(fill64_kernel, 2 * m, stream, die.as<u64>(), 2 * m, NONE64);
+        if (p.dies.n) KLAUNCH(scatter64_kernel, p.dies.n, stream, p.dies.a.as<u64>(), p.dies.b.as<u64>(), p.dies.n, die.as<u64>());
+        KCHECK_HIP(hipGetLastError());
+        int fell_back = 0;      // (1: the pass's node moves chained further than the device form follows and were replayed on the host)
+        const double t_replay = now_ms();
+        KCHECK(dev_replay_nodes64(die.as<u64>(), m, TN, nsc, p.to_n, p.from_n, &p.n_nmoves, &p.N_new, &fell_back, stream));
+        if (fell_back) st.host_ms += now_ms() - t_replay;
+        KCHECK(sorted_with_index(p.from_n, p.n_nmoves, p.nfrom_sorted, p.nfrom_idx));
+        KCHECK_HIP(hipGetLastError());
+        return KATOME_OK;
+    }
+    // (rank 0's status travels as in agree_on_edge_replay)
+    int agree_on_node_replay(Pass& p) {
+        p.N_new = TN;
+        int root_rc = rank == 0 ? root_node_replay(p) : KATOME_OK;
+        if (rank == 0 && root_rc == KATOME_OK && fail_at("nodes")) { set_error("distributed pruning: KATOME_DIST_PRUNE_FAIL=nodes"); root_rc = KATOME_E_UNSUPPORTED; }
+        lap(S_DIES_NODE_REPLAY);
+        uint64_t removed_nodes[2] = {rank == 0 && root_rc == KATOME_OK ? TN - p.N_new : 0, (uint64_t)(-root_rc)};
+        KCHECK(d->comm->allreduce(removed_nodes, 2, OP_MAX));
+        if (removed_nodes[1]) return root_failed(rank, (int)removed_nodes[1], "the replay of the removed nodes");
+        p.N_new = TN - removed_nodes[0];
+        st.removed_nodes += removed_nodes[0];
+        return KATOME_OK;
+    }
+    // the nodes in the vacated tail that stay ask where they go
+    int ask_node_moves(Pass& p) {
+        DevBuf nq(stream), nwho(stream), nans(stream);
+        KCHECK(nq.alloc((N + 1) * 8)); KCHECK(nwho.alloc((N + 1) * 4));
+        uint64_t n_nq = 0;
+        KCHECK(counted([&](auto* c) { if (N) KLAUNCH_T(node_cand_kernel, N, stream, npos.as<u64>(), alive_n.as<unsigned char>(), N, p.N_new, nq.as<u64>(), nwho.as<u32>(), c); }, &n_nq));
+        KCHECK(nans.alloc((n_nq + 1) * 8));
+        Routed asked(stream);
+        KCHECK(router.send(nq.as<u64>(), nullptr, n_nq, asked));
+        DevBuf found(stream), a2(stream);
+        KCHECK(found.alloc((asked.n + 1) * 8)); KCHECK(a2.alloc((asked.n + 1) * 8));
+        if (asked.n) {
+            KCHECK(answer_moves(p.nfrom_sorted, p.nfrom_idx, p.to_n, p.n_nmoves, asked, found, a2));
+            KCHECK_HIP(hipGetLastError());
+        }
+        KCHECK(router.reply(asked, a2.as<u64>(), nans.as<u64>()));
+        if (n_nq) KLAUNCH(node_apply_kernel, n_nq, stream, nwho.as<u32>(), nans.as<u64>(), n_nq, npos.as<u64>());
+        KCHECK_HIP(hipGetLastError());
+        return KATOME_OK;
+    }
+    void end_pass(const Pass& p) { TE = p.E_new; TN = p.N_new; lap(S_NODE_QUESTIONS); }
+
+    void print_trace() const {
+        if (!trace) return;
+        fprintf(stderr, "[dist prune] rank %d router: %llu sends, %llu replies; host ms: partition %.1f, count rounds %.1f, exchanges %.1f\n", rank,
+                (unsigned long long)router.n_send, (unsigned long long)router.n_reply, router.t_part, router.t_counts, router.t_xchg);
+        // (S_WALKS_MARKS stands twice: as the walks' total where they hop, as the last part of the walks on the table)
+        fprintf(stderr, "[dist prune] rank %d: %llu passes; ms: walks+marks %.1f, marks->root+edge replay %.1f, edge questions %.1f, apply+losses %.1f, "
+                        "dies+node replay %.1f, node questions %.1f; of the second: marks kernel %.1f, send %.1f, sort+replay %.1f; walks: first_out %.1f, words+delta %.1f, allgather+apply %.1f, "
+                        "input list %.1f, walk %.1f, scan+marks %.1f, marks routed %.1f\n", rank, (unsigned long long)st.passes, t_sec[S_WALKS_MARKS], t_sec[S_EDGE_REPLAY],
+                t_sec[S_EDGE_QUESTIONS], t_sec[S_APPLY_LOSSES], t_sec[S_DIES_NODE_REPLAY], t_sec[S_NODE_QUESTIONS], t_sec[S_MARKS_KERNEL], t_sec[S_MARKS_SEND],
+                t_sec[S_SORT_REPLAY], t_sec[S_FIRST_OUT], t_sec[S_WORDS_DELTA], t_sec[S_ALLGATHER_APPLY], t_sec[S_INPUT_LIST], t_sec[S_WALK], t_sec[S_SCAN_MARKS],
+                t_sec[S_WALKS_MARKS]);
+    }
+
+    // ---- the pruned graph, still sharded: survivors compacted, positions as indices, ages kept -------------------------------
+    // (block_append hands out places in no particular order: back into local order, which is key order)
+    int in_local_order(DevBuf& keep, uint64_t n, DevBuf& k64) {
+        if (n < 2) return KATOME_OK;
+        KLAUNCH(widen_kernel, n, stream, keep.as<u32>(), n, k64.as<u64>());
+        KCHECK(dev_sort(k64.as<u64>(), nullptr, n, 1, 32, stream));
+        KLAUNCH(narrow_kernel, n, stream, k64.as<u64>(), n, keep.as<u32>());
+        KCHECK_HIP(hipGetLastError());
+        return KATOME_OK;
+    }
+    // the targets' indices, asked of their owners (all edges; the dead ones are dropped)
+    int target_positions(const DevBuf& keep_e, uint64_t E2, DevBuf& e_dst) {
+        DevBuf msg(stream), dst_all(stream), ans(stream);
+        KCHECK(msg.alloc((E + 1) * 8)); KCHECK(dst_all.alloc((E + 1) * 8));
+        if (E) KLAUNCH(target_msg_kernel, E, stream, drank, dlocal, E, msg.as<u64>());
+        Routed asked(stream);
+        KCHECK(router.send(msg.as<u64>(), nullptr, E, asked));
+        KCHECK(ans.alloc((asked.n + 1) * 8));
+        if (asked.n) KLAUNCH(npos_of_kernel, asked.n, stream, asked.a.as<u64>(), asked.n, npos.as<u64>(), ans.as<u64>());
+        KCHECK_HIP(hipGetLastError());
+        KCHECK(router.reply(asked, ans.as<u64>(), dst_all.as<u64>()));
+        if (E2) KLAUNCH(gather_by_kernel<u64>, E2, stream, dst_all.as<u64>(), keep_e.as<u32>(), E2, e_dst.as<u64>());
+        return KATOME_OK;
+    }
+    int install_result() {
+        DevBuf keep_e(stream), keep_n(stream);
+        KCHECK(keep_e.alloc((E + 1) * 4)); KCHECK(keep_n.alloc((N + 1) * 4));
+        uint64_t E2 = 0, N2 = 0;
+        KCHECK(counted([&](auto* c) {
+            if (E) KLAUNCH_T(alive_list_kernel, E, stream, alive_e.as<unsigned char>(), E, keep_e.as<u32>(), c);
+            if (N) KLAUNCH_T(alive_list_kernel, N, stream, alive_n.as<unsigned char>(), N, keep_n.as<u32>(), c + 1);
+        }, &E2, &N2));
+        {
+            DevBuf k64(stream);
+            KCHECK(k64.alloc((std::max(E2, N2) + 1) * 8));
+            KCHECK(in_local_order(keep_e, E2, k64)); KCHECK(in_local_order(keep_n, N2, k64));
+        }
+        DevBuf n_key(stream), n_gid(stream), e_key(stream), e_w(stream), e_gid(stream), e_age(stream), e_src(stream), e_dst(stream);
+        KCHECK(n_key.alloc((N2 + 1) * 8 * nw)); KCHECK(n_gid.alloc((N2 + 1) * 8));
+        KCHECK(e_key.alloc((E2 + 1) * 8 * nw)); KCHECK(e_w.alloc((E2 + 1) * 4)); KCHECK(e_gid.alloc((E2 + 1) * 8)); KCHECK(e_age.alloc((E2 + 1) * 8));
+        KCHECK(e_src.alloc((E2 + 1) * 8)); KCHECK(e_dst.alloc((E2 + 1) * 8));
+        KCHECK(target_positions(keep_e, E2, e_dst));
+        if (E2) {
+            KLAUNCH(gather_src_kernel, E2, stream, keep_e.as<u32>(), E2, lsrc, npos.as<u64>(), e_src.as<u64>());
+            KLAUNCH(gather_by_kernel<u64>, E2, stream, pos.as<u64>(), keep_e.as<u32>(), E2, e_gid.as<u64>());
+            KLAUNCH(gather_by_kernel<u64>, E2, stream, age.as<u64>(), keep_e.as<u32>(), E2, e_age.as<u64>());
+            KLAUNCH(gather_by_kernel<u32>, E2, stream, b->edge_weight.as<u32>(), keep_e.as<u32>(), E2, e_w.as<u32>());
+            if (nw == 1) KLAUNCH(gather_keys_by_kernel<1>, E2, stream, b->edge_key.as<u64>(), keep_e.as<u32>(), E2, e_key.as<u64>());
+            else         KLAUNCH(gather_keys_by_kernel<2>, E2, stream, b->edge_key.as<u64>(), keep_e.as<u32>(), E2, e_key.as<u64>());
+        }
+        if (N2) {
+            KLAUNCH(gather_by_kernel<u64>, N2, stream, npos.as<u64>(), keep_n.as<u32>(), N2, n_gid.as<u64>());
+            if (nw == 1) KLAUNCH(gather_keys_by_kernel<1>, N2, stream, d->node_key.as<u64>(), keep_n.as<u32>(), N2, n_key.as<u64>());
+            else         KLAUNCH(gather_keys_by_kernel<2>, N2, stream, d->node_key.as<u64>(), keep_n.as<u32>(), N2, n_key.as<u64>());
+        }
+        KCHECK_HIP(hipGetLastError());
+        KCHECK_HIP(hipStreamSynchronize(stream));
+        auto install = [&](DevBuf& dst, DevBuf& src) { const size_t bytes = src.bytes; dst.stream = stream; dst.adopt(src.take(), bytes); };
+        install(b->edge_key, e_key); install(b->edge_weight, e_w); install(d->edge_src, e_src); install(d->edge_dst, e_dst);
+        install(d->edge_gid, e_gid); install(d->edge_age, e_age); install(d->node_key, n_key); install(d->node_gid, n_gid);
+        b->edge_seq.release();
+        d->edge_lsrc.release(); d->edge_drank.release(); d->edge_dlocal.release();      // (local indices of the unpruned share: stale now)
+        KCHECK(d->edge_label.alloc((E2 + 1) * (size_t)label_stride_for_k(k) + 16, stream));
+        KCHECK(dev_labels(b->edge_key.as<u64>(), E2, k, d->edge_label.as<uint8_t>(), stream));
+        KCHECK_HIP(hipStreamSynchronize(stream));
+        b->n_edges = E2;
+        d->n_edges = E2; d->n_nodes = N2; d->total_edges = TE; d->total_nodes = TN; d->n_src = 0;
+        d->dead_paths_removed = true;
+        return KATOME_OK;
+    }
+};
+
 }  // namespace
 
+// The passes (the file's header has why they are cut this way).  Every rank goes through the same collectives in the same order:
+// a step that only rank 0 can fail in hands its status to all of them in the agreement that follows it.
 extern "C" int katome_dist_remove_dead_paths(katome_dist_builder* d, katome_dist_graph* out, katome_prune_stats* st_out, void* stream_) {
     if (!d) { set_error("null argument"); return KATOME_E_ARG; }
     if (!d->finalized || !d->first_seen) { set_error("katome_dist_remove_dead_paths: a finalized FIRST_SEEN_ORDER build only (petgraph's numbering decides what a repeated index removes)"); return KATOME_E_ARG; }
@@ -393,18 +940,12 @@ extern "C" int katome_dist_remove_dead_paths(katome_dist_builder* d, katome_dist
         return katome_dist_current_graph(d, out);
     }
     hipStream_t stream = (hipStream_t)stream_;
-    katome_builder* b = d->b;
     KCHECK_HIP(hipSetDevice(d->s.device));
     d->comm->use_stream(stream);
-    const int rank = d->rank(), world = d->world();
-    const uint32_t nw = d->nw, k = d->s.k, two_k = 2 * k;
-    const uint64_t E = d->n_edges, N = d->n_nodes;
     const double t_begin = now_ms();
-    katome_prune_stats st;
-    memset(&st, 0, sizeof st);
-    if (two_k > 255) { set_error("k too large for the walker's step counter"); return KATOME_E_UNSUPPORTED; }       // (the same on every rank)
+    if (2 * d->s.k > 255) { set_error("k too large for the walker's step counter"); return KATOME_E_UNSUPPORTED; }       // (the same on every rank)
     {   // a rank whose share cannot be pruned says so to all of them: nobody may leave alone before a collective the others wait in
-        uint64_t bad = (E >= 0xFFFFFFFFull || N >= 0xFFFFFFFFull) ? 1 : 0;
+        uint64_t bad = (d->n_edges >= 0xFFFFFFFFull || d->n_nodes >= 0xFFFFFFFFull) ? 1 : 0;
         KCHECK(d->comm->allreduce(&bad, 1, OP_MAX));
         if (bad) { set_error("more than 2^32 edges or nodes on one rank"); return KATOME_E_UNSUPPORTED; }
     }
@@ -413,453 +954,30 @@ extern "C" int katome_dist_remove_dead_paths(katome_dist_builder* d, katome_dist
         KCHECK(d->comm->allreduce(&stale, 1, OP_MAX));
         if (stale) KCHECK(dist_rebuild_links(d, stream));
     }
-    const uint64_t n_src = d->n_src;                  // (after the rebuild: the nodes [0, n_src) of this rank have out-edges)
-    Router router(d, stream);
-    KCHECK(router.init());
-    const u64* lsrc = d->edge_lsrc.as<u64>(); const u64* drank = d->edge_drank.as<u64>(); const u64* dlocal = d->edge_dlocal.as<u64>();
-    // ages: the first-seen index an edge was given never changes; `pos` is where it sits now
-    DevBuf age(stream), pos(stream), alive_e(stream), mult(stream), start(stream);
-    DevBuf npos(stream), indeg(stream), outdeg(stream), first_out(stream), last_touch(stream), alive_n(stream), cursors(stream);
-    KCHECK(age.alloc((E + 1) * 8)); KCHECK(pos.alloc((E + 1) * 8)); KCHECK(alive_e.alloc(E + 16)); KCHECK(mult.alloc((E + 1) * 4));
-    KCHECK(start.alloc((n_src + 2) * 8));
-    KCHECK(npos.alloc((N + 1) * 8)); KCHECK(indeg.alloc((N + 1) * 4)); KCHECK(outdeg.alloc((N + 1) * 4)); KCHECK(first_out.alloc((n_src + 1) * 4));
-    KCHECK(last_touch.alloc((N + 1) * 4)); KCHECK(alive_n.alloc(N + 16)); KCHECK(cursors.alloc(64));
-    unsigned long long* cur = cursors.as<unsigned long long>();
-    auto reset_cursors = [&]() -> int { KCHECK_HIP(hipMemsetAsync(cursors.p, 0, 64, stream)); return KATOME_OK; };
-    auto read_cursors = [&](uint64_t* h, int n) -> int {
-        KCHECK_HIP(hipMemcpyAsync(h, cursors.p, 8 * n, hipMemcpyDeviceToHost, stream));
-        KCHECK_HIP(hipStreamSynchronize(stream));
-        return KATOME_OK;
-    };
-    if (E) {
-        // (after a stage that removed edges the ages are kept in edge_age: a position is no age any more)
-        KCHECK_HIP(hipMemcpyAsync(age.p, d->edge_age.p ? d->edge_age.p : d->edge_gid.p, E * 8, hipMemcpyDeviceToDevice, stream));
-        KCHECK_HIP(hipMemcpyAsync(pos.p, d->edge_gid.p, E * 8, hipMemcpyDeviceToDevice, stream));
-        KCHECK_HIP(hipMemsetAsync(alive_e.p, 1, E, stream));
-        KCHECK_HIP(hipMemsetAsync(mult.p, 0, E * 4, stream));
-    }
-    KLAUNCH(run_start_kernel, E + 1, stream, lsrc, E, n_src, start.as<u64>());
-    if (N) {
-        KCHECK_HIP(hipMemcpyAsync(npos.p, d->node_gid.p, N * 8, hipMemcpyDeviceToDevice, stream));
-        KLAUNCH(node_init_kernel, N, stream, N, n_src, start.as<u64>(), outdeg.as<u32>(), indeg.as<u32>(), last_touch.as<u32>(), alive_n.as<unsigned char>());
-    }
-    KCHECK_HIP(hipGetLastError());
-    {   // in-degrees: one message per edge to its target's owner (once; kept current afterwards)
-        DevBuf msg(stream);
-        KCHECK(msg.alloc((E + 1) * 8));
-        if (E) KLAUNCH(target_msg_kernel, E, stream, drank, dlocal, E, msg.as<u64>());
-        Routed r(stream);
-        KCHECK(router.send(msg.as<u64>(), nullptr, E, r));
-        if (r.n) KLAUNCH(indeg_add_kernel, r.n, stream, r.a.as<u64>(), r.n, indeg.as<u32>());
-        KCHECK_HIP(hipGetLastError());
-    }
-    uint64_t TE = d->total_edges, TN = d->total_nodes;
-    // The walks: on a replicated successor table when every rank has room for one word per node of the whole graph (the
-    // default), else walkers that hop from owner to owner (KATOME_DIST_PRUNE_WALKS=table|hop overrides; all ranks agree)
-    const uint64_t TN0 = d->total_nodes, per_rank = std::max<uint64_t>(1, (TN0 + world - 1) / world);
-    const u64* edst = d->edge_dst.as<u64>();                      // every edge's target as a first-seen node id (the pass installs new arrays at the end)
-    bool use_table = true;
-    {
-        size_t free_b = 0, total_b = 0;
-        KCHECK_HIP(hipMemGetInfo(&free_b, &total_b));
-        free_b += dev_cached_bytes();
-        uint64_t ok = (TN0 + 1) * 8 + (N + 1) * 24 + per_rank * 8 + (4ull << 30) < free_b ? 1 : 0;
-        if (const char* e = getenv("KATOME_DIST_PRUNE_WALKS")) ok = strcmp(e, "hop") == 0 ? 0 : strcmp(e, "table") == 0 ? 1 : ok;
-        KCHECK(d->comm->allreduce(&ok, 1, OP_MIN));
-        use_table = ok != 0;
-    }
-    DevBuf w_table(stream), w_now(stream), w_held(stream), ngid0(stream), dir(stream);
-    if (use_table) {
-        KCHECK(w_table.alloc((TN0 + 1) * 8)); KCHECK(w_now.alloc((N + 1) * 8)); KCHECK(w_held.alloc((N + 1) * 8)); KCHECK(ngid0.alloc((N + 1) * 8));
-        KCHECK(dir.alloc((per_rank + 1) * 8));
-        KCHECK_HIP(hipMemsetAsync(w_table.p, 0, (TN0 + 1) * 8, stream));
-        KCHECK_HIP(hipMemsetAsync(w_held.p, 0, (N + 1) * 8, stream));             // (no live node's word is 0: the first pass sends them all)
-        if (N) KCHECK_HIP(hipMemcpyAsync(ngid0.p, d->node_gid.p, N * 8, hipMemcpyDeviceToDevice, stream));
-        // directory, sharded by node id: where each node lives
-        DevBuf da(stream), db(stream);
-        KCHECK(da.alloc((N + 1) * 8)); KCHECK(db.alloc((N + 1) * 8));
-        if (N) KLAUNCH(dir_msg_kernel, N, stream, N, (u64)rank, ngid0.as<u64>(), per_rank, da.as<u64>(), db.as<u64>());
-        Routed r(stream);
-        KCHECK(router.send(da.as<u64>(), db.as<u64>(), N, r));
-        if (r.n) KLAUNCH(dir_fill_kernel, r.n, stream, r.a.as<u64>(), r.b.as<u64>(), r.n, (u64)rank * per_rank, dir.as<u64>());
-        KCHECK_HIP(hipGetLastError());
-        KCHECK_HIP(hipStreamSynchronize(stream));
-    }
-    // positions (of edges and of nodes alike) fit this many bits: what the sorts and look-ups at rank 0 work on
-    uint32_t pos_bits = 1;
-    while (pos_bits < 64 && ((std::max(d->total_edges, d->total_nodes) + 1) >> pos_bits)) ++pos_bits;
     static const bool trace = getenv("KATOME_DIST_PRUNE_TRACE") != nullptr;
-    double t_sec[24] = {0}, t_mark = now_ms();
-    auto lap = [&](int i) { if (trace) { (void)hipStreamSynchronize(stream); const double t = now_ms(); t_sec[i] += t - t_mark; t_mark = t; } };
+    DistPrune S(d, stream, trace);                    // (after the rebuild: the links and n_src are current)
+    KCHECK(S.setup());
+    KCHECK(S.choose_walk_route());
+    if (S.use_table) KCHECK(S.setup_table());
+    S.t_mark = now_ms();
     for (;;) {
-        ++st.passes;
-        lap(7);
-        if (n_src) KLAUNCH(first_out_kernel, n_src, stream, n_src, start.as<u64>(), age.as<u64>(), alive_e.as<unsigned char>(), first_out.as<u32>());
-        uint64_t h[4] = {0, 0, 0, 0};
-        lap(11);
-        if (use_table) {
-            // ---- the words of this rank's nodes that changed -> every rank's copy of the table -------------------------------
-            if (N) KLAUNCH(own_words_kernel, N, stream, N, n_src, first_out.as<u32>(), edst, indeg.as<u32>(), alive_n.as<unsigned char>(), w_now.as<u64>());
-            DevBuf delta(stream), all_delta(stream);
-            KCHECK(delta.alloc((N + 1) * 16));
-            KCHECK(reset_cursors());
-            if (N) KLAUNCH_T(delta_kernel, N, stream, N, w_now.as<u64>(), w_held.as<u64>(), ngid0.as<u64>(), delta.as<u64>(), cur);
-            KCHECK_HIP(hipGetLastError());
-            KCHECK(read_cursors(h, 1));
-            lap(12);
-            uint64_t n_delta = 0;
-            KCHECK(router.allgather(delta.p, h[0], 16, all_delta, &n_delta));
-            if (n_delta) KLAUNCH(apply_words_kernel, n_delta, stream, all_delta.as<u64>(), n_delta, w_table.as<u64>());
-            delta.release(); all_delta.release();
-            lap(13);
-            // ---- walks from every vertex without incoming edges: local --------------------------------------------------------
-            DevBuf inputs(stream), len(stream), offs(stream), marks(stream);
-            KCHECK(inputs.alloc((N + 1) * 4));
-            KCHECK(reset_cursors());
-            if (N) KLAUNCH_T(input_list_kernel, N, stream, N, indeg.as<u32>(), outdeg.as<u32>(), alive_n.as<unsigned char>(), inputs.as<u32>(), cur);
-            KCHECK_HIP(hipGetLastError());
-            KCHECK(read_cursors(h, 1));
-            const uint64_t n_in = h[0];
-            st.walks += n_in;
-            lap(14);
-            KCHECK(len.alloc((n_in + 1) * 4)); KCHECK(offs.alloc((n_in + 2) * 8));
-            KCHECK(reset_cursors());
-            if (n_in) KLAUNCH(walk_table_kernel, n_in, stream, inputs.as<u32>(), n_in, ngid0.as<u64>(), w_table.as<u64>(), two_k, len.as<u32>(), cur);
-            KCHECK_HIP(hipGetLastError());
-            KCHECK(read_cursors(h, 1));
-            st.dead_walks += h[0];
-            lap(15);
-            uint64_t n_marks = 0;
-            if (n_in) {
-                KCHECK(dev_scan_counts(len.as<u32>(), n_in, offs.as<u64>(), stream));
-                KCHECK_HIP(hipMemcpyAsync(&n_marks, offs.as<u64>() + n_in, 8, hipMemcpyDeviceToHost, stream));
-                KCHECK_HIP(hipStreamSynchronize(stream));
-            }
-            KCHECK(marks.alloc((n_marks + 1) * 8));
-            if (n_marks) KLAUNCH(walk_marks_kernel, n_in, stream, inputs.as<u32>(), n_in, ngid0.as<u64>(), w_table.as<u64>(), len.as<u32>(), offs.as<u64>(), per_rank, marks.as<u64>());
-            KCHECK_HIP(hipGetLastError());
-            lap(16);
-            // the marks -> the directory rank of each vertex -> its owner, where its first out-edge is counted
-            Routed at_dir(stream), at_owner(stream);
-            KCHECK(router.send(marks.as<u64>(), nullptr, n_marks, at_dir));
-            DevBuf fwd(stream);
-            KCHECK(fwd.alloc((at_dir.n + 1) * 8));
-            if (at_dir.n) KLAUNCH(dir_forward_kernel, at_dir.n, stream, at_dir.a.as<u64>(), at_dir.n, (u64)rank * per_rank, dir.as<u64>(), fwd.as<u64>());
-            KCHECK_HIP(hipGetLastError());
-            KCHECK(router.send(fwd.as<u64>(), nullptr, at_dir.n, at_owner));
-            if (at_owner.n) KLAUNCH(mark_nodes_kernel, at_owner.n, stream, at_owner.a.as<u64>(), at_owner.n, first_out.as<u32>(), mult.as<u32>());
-            KCHECK_HIP(hipGetLastError());
-        } else {
-        // ---- walks from every vertex without incoming edges ------------------------------------------------------------
-        DevBuf A(stream), B(stream), deadv(stream);
-        KCHECK(A.alloc((N + 1) * 8)); KCHECK(B.alloc((N + 1) * 8));
-        KCHECK(reset_cursors());
-        if (N) KLAUNCH(input_kernel, N, stream, N, (u64)rank, indeg.as<u32>(), outdeg.as<u32>(), alive_n.as<unsigned char>(), A.as<u64>(), B.as<u64>(), cur);
-        KCHECK_HIP(hipGetLastError());
-        KCHECK(read_cursors(h, 1));
-        uint64_t n_walk = h[0], n_deadv = 0, deadv_cap = 0;
-        st.walks += n_walk;
-        const u64 *wA = A.as<u64>(), *wB = B.as<u64>();
-        Routed arrivals(stream);
-        for (uint32_t step = 0;; ++step) {
-            if (step > two_k) { set_error("distributed pruning: a walk did not end within 2k steps"); return KATOME_E_DEVICE; }
-            DevBuf oA(stream), oB(stream);
-            KCHECK(oA.alloc((n_walk + 1) * 8)); KCHECK(oB.alloc((n_walk + 1) * 8));
-            if (n_deadv + n_walk > deadv_cap) {                              // the verdicts collected on this rank so far + this step's
-                DevBuf bigger(stream);
-                deadv_cap = (n_deadv + n_walk) * 2 + 1024;
-                KCHECK(bigger.alloc(deadv_cap * 8));
-                if (n_deadv) KCHECK_HIP(hipMemcpyAsync(bigger.p, deadv.p, n_deadv * 8, hipMemcpyDeviceToDevice, stream));
-                const size_t bytes = bigger.bytes;
-                deadv.adopt(bigger.take(), bytes);
-            }
-            h[0] = h[1] = 0;
-            if (n_walk) {
-                KCHECK(reset_cursors());
-                KLAUNCH(walk_step_kernel, n_walk, stream, wA, wB, n_walk, step ? 1u : 0u, two_k, indeg.as<u32>(), outdeg.as<u32>(), first_out.as<u32>(),
-                        drank, dlocal, oA.as<u64>(), oB.as<u64>(), cur, deadv.as<u64>() + n_deadv, cur + 1);
-                KCHECK_HIP(hipGetLastError());
-                KCHECK(read_cursors(h, 2));
-            }
-            n_deadv += h[1];
-            // (the count matrix of the exchange tells every rank whether any walker moved anywhere: no agreement round of its own)
-            KCHECK(router.send(oA.as<u64>(), oB.as<u64>(), h[0], arrivals));
-            wA = arrivals.a.as<u64>(); wB = arrivals.b.as<u64>(); n_walk = arrivals.n;
-            if (arrivals.moved == 0) break;
-        }
-        st.dead_walks += n_deadv;
-        // ---- the dead walks again, from their start vertices, to collect their edges -----------------------------------
-        {
-            Routed m(stream);
-            KCHECK(router.send(deadv.as<u64>(), nullptr, n_deadv, m));
-            const u64* wM = m.a.as<u64>();
-            uint64_t n_m = m.n;
-            Routed arrived(stream);
-            for (uint32_t step = 0;; ++step) {
-                if (step > two_k) { set_error("distributed pruning: a marking walk did not end within 2k steps"); return KATOME_E_DEVICE; }
-                DevBuf oM(stream);
-                KCHECK(oM.alloc((n_m + 1) * 8));
-                h[0] = 0;
-                if (n_m) {
-                    KCHECK(reset_cursors());
-                    KLAUNCH(mark_step_kernel, n_m, stream, wM, n_m, first_out.as<u32>(), drank, dlocal, mult.as<u32>(), oM.as<u64>(), cur);
-                    KCHECK_HIP(hipGetLastError());
-                    KCHECK(read_cursors(h, 1));                   // (synchronises: the list just walked may be given up below)
-                }
-                KCHECK(router.send(oM.as<u64>(), nullptr, h[0], arrived));
-                wM = arrived.a.as<u64>(); n_m = arrived.n;
-                if (arrived.moved == 0) break;
-            }
-        }
-        }
-        lap(0);
-        // ---- marked (position, count) pairs -> rank 0, which replays remove_paths' swap_removes --------------------------
-        DevBuf mp(stream), mm(stream);
-        KCHECK(mp.alloc((E + 1) * 8)); KCHECK(mm.alloc((E + 1) * 8));
-        KCHECK(reset_cursors());
-        if (E) KLAUNCH_T(marks_kernel, E, stream, mult.as<u32>(), pos.as<u64>(), E, mp.as<u64>(), mm.as<u64>(), cur, cur + 1);
-        KCHECK_HIP(hipGetLastError());
-        KCHECK(read_cursors(h, 2));
-        const uint64_t u_local = h[0];
-        st.marked += h[1];
-        uint64_t u_total = u_local;
-        KCHECK(d->comm->allreduce(&u_total, 1, OP_SUM));
-        if (u_total == 0) break;                                            // "if to_remove.is_empty() ... Graph is pruned" (pruner.rs:69-72)
-        lap(8);
-        Routed marks(stream);
-        KCHECK(router.send(mp.as<u64>(), mm.as<u64>(), u_local, marks));   // (top byte 0: everything goes to rank 0)
-        lap(9);
-        mp.release(); mm.release();
-        // rank 0's tables for the questions that follow
-        DevBuf victims(stream), to_e(stream), from_e(stream), vict_sorted(stream), vict_ord(stream), from_sorted(stream), from_idx(stream);
-        ReplayScratch sc(stream);
-        uint64_t m_removed = 0, E_new = TE, n_moves = 0, dups = 0;
-        // (what fails on rank 0 alone must not leave the others waiting in the next collective: its status travels with the counts
-        // every rank agrees on below, and all of them return it)
-        auto root_edge_replay = [&]() -> int {
-            const uint64_t u = marks.n;
-            DevBuf m32(stream);
-            KCHECK(m32.alloc((u + 1) * 4));
-            KLAUNCH(narrow_kernel, u, stream, marks.b.as<u64>(), u, m32.as<u32>());
-            KCHECK(dev_sort(marks.a.as<u64>(), m32.as<u32>(), u, 1, pos_bits, stream));
-            KCHECK(dev_replay_edges64(marks.a.as<u64>(), m32.as<u32>(), u, TE, sc, victims, to_e, from_e, &m_removed, &E_new, &n_moves, &dups, stream));
-            lap(10);
-            if (m_removed >= 0xFFFFFFFFull) { set_error("more than 2^32 edges removed in one pass"); return KATOME_E_UNSUPPORTED; }
-            KCHECK(vict_sorted.alloc((m_removed + 1) * 8)); KCHECK(vict_ord.alloc((m_removed + 1) * 4));
-            if (m_removed) {
-                KCHECK_HIP(hipMemcpyAsync(vict_sorted.p, victims.p, m_removed * 8, hipMemcpyDeviceToDevice, stream));
-                KLAUNCH(iota32_kernel, m_removed, stream, vict_ord.as<u32>(), m_removed);
-                KCHECK(dev_sort(vict_sorted.as<u64>(), vict_ord.as<u32>(), m_removed, 1, pos_bits, stream));
-            }
-            KCHECK(from_sorted.alloc((n_moves + 1) * 8)); KCHECK(from_idx.alloc((n_moves + 1) * 4));
-            if (n_moves) {
-                KCHECK_HIP(hipMemcpyAsync(from_sorted.p, from_e.p, n_moves * 8, hipMemcpyDeviceToDevice, stream));
-                KLAUNCH(iota32_kernel, n_moves, stream, from_idx.as<u32>(), n_moves);
-                KCHECK(dev_sort(from_sorted.as<u64>(), from_idx.as<u32>(), n_moves, 1, pos_bits, stream));
-            }
-            KCHECK_HIP(hipGetLastError());
-            return KATOME_OK;
-        };
-        int root_rc = rank == 0 ? root_edge_replay() : KATOME_OK;
-        if (rank == 0 && root_rc == KATOME_OK && fail_at("edges")) { set_error("distributed pruning: KATOME_DIST_PRUNE_FAIL=edges"); root_rc = KATOME_E_UNSUPPORTED; }
-        lap(1);
-        uint64_t agreed[3] = {rank == 0 && root_rc == KATOME_OK ? TE - E_new : 0, rank == 0 ? dups : 0, (uint64_t)(-root_rc)};
-        KCHECK(d->comm->allreduce(agreed, 3, OP_MAX));
-        if (agreed[2]) return root_failed(rank, (int)agreed[2], "the replay of the removed edges");
-        m_removed = agreed[0]; E_new = TE - m_removed;
-        st.removed_edges += m_removed; st.removed_by_duplicates += agreed[1];
-        // ---- every rank asks for the fate of its candidate edges -----------------------------------------------------------
-        DevBuf q(stream), who(stream), ans_ord(stream), ans_pos(stream);
-        KCHECK(q.alloc((E + 1) * 8)); KCHECK(who.alloc((E + 1) * 4));
-        KCHECK(reset_cursors());
-        if (E) KLAUNCH_T(edge_cand_kernel, E, stream, mult.as<u32>(), pos.as<u64>(), alive_e.as<unsigned char>(), E, E_new, q.as<u64>(), who.as<u32>(), cur);
-        KCHECK_HIP(hipGetLastError());
-        KCHECK(read_cursors(h, 1));
-        const uint64_t n_q = h[0];
-        KCHECK(ans_ord.alloc((n_q + 1) * 8)); KCHECK(ans_pos.alloc((n_q + 1) * 8));
-        {
-            Routed asked(stream);
-            KCHECK(router.send(q.as<u64>(), nullptr, n_q, asked));
-            DevBuf found(stream), a1(stream), a2(stream);
-            KCHECK(found.alloc((asked.n + 1) * 8)); KCHECK(a1.alloc((asked.n + 1) * 8)); KCHECK(a2.alloc((asked.n + 1) * 8));
-            if (asked.n) {                                                   // (rank 0 only)
-                if (m_removed) KCHECK(dev_rank(vict_sorted.as<u64>(), m_removed, 1, pos_bits, asked.a.as<u64>(), asked.n, found.as<u64>(), stream));
-                else KCHECK_HIP(hipMemsetAsync(found.p, 0xFF, asked.n * 8, stream));
-                KLAUNCH(answer_u32_kernel, asked.n, stream, found.as<u64>(), asked.n, vict_ord.as<u32>(), a1.as<u64>());
-                if (n_moves) KCHECK(dev_rank(from_sorted.as<u64>(), n_moves, 1, pos_bits, asked.a.as<u64>(), asked.n, found.as<u64>(), stream));
-                else KCHECK_HIP(hipMemsetAsync(found.p, 0xFF, asked.n * 8, stream));
-                KLAUNCH(answer_to_kernel, asked.n, stream, found.as<u64>(), asked.n, from_idx.as<u32>(), to_e.as<u64>(), a2.as<u64>());
-                KCHECK_HIP(hipGetLastError());
-            }
-            KCHECK(router.reply(asked, a1.as<u64>(), ans_ord.as<u64>()));
-            KCHECK(router.reply(asked, a2.as<u64>(), ans_pos.as<u64>()));
-        }
-        victims.release(); to_e.release(); from_e.release(); vict_sorted.release(); vict_ord.release(); from_sorted.release(); from_idx.release();
-        lap(2);
-        // ---- apply: dead edges, their sources' degrees here, messages to their targets' owners ----------------------------
-        DevBuf dead_e(stream), dead_t(stream), msgA(stream), msgB(stream);
-        KCHECK(dead_e.alloc((n_q + 1) * 4)); KCHECK(dead_t.alloc((n_q + 1) * 4)); KCHECK(msgA.alloc((n_q + 1) * 8)); KCHECK(msgB.alloc((n_q + 1) * 8));
-        KCHECK(reset_cursors());
-        if (n_q) {
-            KLAUNCH(edge_apply_kernel, n_q, stream, who.as<u32>(), ans_ord.as<u64>(), ans_pos.as<u64>(), n_q, (u64)rank, pos.as<u64>(), alive_e.as<unsigned char>(),
-                    lsrc, drank, dlocal, outdeg.as<u32>(), last_touch.as<u32>(), dead_e.as<u32>(), dead_t.as<u32>(), msgA.as<u64>(), msgB.as<u64>(), cur);
-            KLAUNCH(clear_marks_kernel, n_q, stream, who.as<u32>(), n_q, mult.as<u32>());
-        }
-        KCHECK_HIP(hipGetLastError());
-        KCHECK(read_cursors(h, 1));
-        const uint64_t n_dead = h[0];
-        Routed losses(stream);
-        KCHECK(router.send(msgA.as<u64>(), msgB.as<u64>(), n_dead, losses));
-        if (losses.n) KLAUNCH(target_loss_kernel, losses.n, stream, losses.a.as<u64>(), losses.b.as<u64>(), losses.n, indeg.as<u32>(), last_touch.as<u32>());
-        KCHECK_HIP(hipGetLastError());
-        KCHECK_HIP(hipStreamSynchronize(stream));
-        { uint64_t bar = 0; KCHECK(d->comm->allreduce(&bar, 1, OP_MAX)); }   // every rank has applied every loss before anyone decides who dies
-        lap(3);
-        // ---- which endpoints go with which removal -> rank 0, which replays remove_single_node ------------------------------
-        DevBuf X(stream), Y(stream);
-        KCHECK(X.alloc((n_dead + losses.n + 1) * 8)); KCHECK(Y.alloc((n_dead + losses.n + 1) * 8));
-        KCHECK(reset_cursors());
-        if (n_dead) KLAUNCH(die_src_kernel, n_dead, stream, dead_e.as<u32>(), dead_t.as<u32>(), n_dead, lsrc, indeg.as<u32>(), outdeg.as<u32>(), last_touch.as<u32>(),
-                            npos.as<u64>(), alive_n.as<unsigned char>(), X.as<u64>(), Y.as<u64>(), cur);
-        if (losses.n) KLAUNCH(die_dst_kernel, losses.n, stream, losses.a.as<u64>(), losses.b.as<u64>(), losses.n, indeg.as<u32>(), outdeg.as<u32>(), last_touch.as<u32>(),
-                              npos.as<u64>(), alive_n.as<unsigned char>(), X.as<u64>(), Y.as<u64>(), cur);
-        if (n_dead) KLAUNCH(untouch_src_kernel, n_dead, stream, dead_e.as<u32>(), n_dead, lsrc, last_touch.as<u32>());
-        if (losses.n) KLAUNCH(untouch_dst_kernel, losses.n, stream, losses.a.as<u64>(), losses.n, last_touch.as<u32>());
-        KCHECK_HIP(hipGetLastError());
-        KCHECK(read_cursors(h, 1));
-        Routed dies(stream);
-        KCHECK(router.send(X.as<u64>(), Y.as<u64>(), h[0], dies));
-        DevBuf to_n(stream), from_n(stream), nfrom_sorted(stream), nfrom_idx(stream);
-        uint64_t n_nmoves = 0, N_new = TN;
-        auto root_node_replay = [&]() -> int {
-            DevBuf die(stream);
-            NodeReplayScratch nsc(stream);
-            KCHECK(die.alloc((2 * m_removed + 2) * 8));
-            KLAUNCH(fill64_kernel, 2 * m_removed, stream, die.as<u64>(), 2 * m_removed, NONE64);
-            if (dies.n) KLAUNCH(scatter64_kernel, dies.n, stream, dies.a.as<u64>(), dies.b.as<u64>(), dies.n, die.as<u64>());
-            KCHECK_HIP(hipGetLastError());
-            int fell_back = 0;      // (1: the pass's node moves chained further than the device form follows and were replayed on the host)
-            const double t_replay = now_ms();
-            KCHECK(dev_replay_nodes64(die.as<u64>(), m_removed, TN, nsc, to_n, from_n, &n_nmoves, &N_new, &fell_back, stream));
-            if (fell_back) st.host_ms += now_ms() - t_replay;
-            KCHECK(nfrom_sorted.alloc((n_nmoves + 1) * 8)); KCHECK(nfrom_idx.alloc((n_nmoves + 1) * 4));
-            if (n_nmoves) {
-                KCHECK_HIP(hipMemcpyAsync(nfrom_sorted.p, from_n.p, n_nmoves * 8, hipMemcpyDeviceToDevice, stream));
-                KLAUNCH(iota32_kernel, n_nmoves, stream, nfrom_idx.as<u32>(), n_nmoves);
-                KCHECK(dev_sort(nfrom_sorted.as<u64>(), nfrom_idx.as<u32>(), n_nmoves, 1, pos_bits, stream));
-            }
-            KCHECK_HIP(hipGetLastError());
-            return KATOME_OK;
-        };
-        root_rc = rank == 0 ? root_node_replay() : KATOME_OK;
-        if (rank == 0 && root_rc == KATOME_OK && fail_at("nodes")) { set_error("distributed pruning: KATOME_DIST_PRUNE_FAIL=nodes"); root_rc = KATOME_E_UNSUPPORTED; }
-        lap(4);
-        uint64_t removed_nodes[2] = {rank == 0 && root_rc == KATOME_OK ? TN - N_new : 0, (uint64_t)(-root_rc)};
-        KCHECK(d->comm->allreduce(removed_nodes, 2, OP_MAX));
-        if (removed_nodes[1]) return root_failed(rank, (int)removed_nodes[1], "the replay of the removed nodes");
-        N_new = TN - removed_nodes[0];
-        st.removed_nodes += removed_nodes[0];
-        {   // the nodes in the vacated tail that stay ask where they go
-            DevBuf nq(stream), nwho(stream), nans(stream);
-            KCHECK(nq.alloc((N + 1) * 8)); KCHECK(nwho.alloc((N + 1) * 4));
-            KCHECK(reset_cursors());
-            if (N) KLAUNCH_T(node_cand_kernel, N, stream, npos.as<u64>(), alive_n.as<unsigned char>(), N, N_new, nq.as<u64>(), nwho.as<u32>(), cur);
-            KCHECK_HIP(hipGetLastError());
-            KCHECK(read_cursors(h, 1));
-            const uint64_t n_nq = h[0];
-            KCHECK(nans.alloc((n_nq + 1) * 8));
-            Routed asked(stream);
-            KCHECK(router.send(nq.as<u64>(), nullptr, n_nq, asked));
-            DevBuf found(stream), a2(stream);
-            KCHECK(found.alloc((asked.n + 1) * 8)); KCHECK(a2.alloc((asked.n + 1) * 8));
-            if (asked.n) {
-                if (n_nmoves) KCHECK(dev_rank(nfrom_sorted.as<u64>(), n_nmoves, 1, pos_bits, asked.a.as<u64>(), asked.n, found.as<u64>(), stream));
-                else KCHECK_HIP(hipMemsetAsync(found.p, 0xFF, asked.n * 8, stream));
-                KLAUNCH(answer_to_kernel, asked.n, stream, found.as<u64>(), asked.n, nfrom_idx.as<u32>(), to_n.as<u64>(), a2.as<u64>());
-                KCHECK_HIP(hipGetLastError());
-            }
-            KCHECK(router.reply(asked, a2.as<u64>(), nans.as<u64>()));
-            if (n_nq) KLAUNCH(node_apply_kernel, n_nq, stream, nwho.as<u32>(), nans.as<u64>(), n_nq, npos.as<u64>());
-            KCHECK_HIP(hipGetLastError());
-        }
-        TE = E_new; TN = N_new;
-        lap(5);
+        ++S.st.passes;
+        Pass p(stream);
+        uint64_t u_local = 0, u_total = 0;
+        KCHECK(S.walks());                            // first out-edges; the walks, on the table or hopping; the dead walks' edges marked
+        KCHECK(S.collect_marks(p, &u_local, &u_total));       // the marked (position, count) pairs, to rank 0 ...
+        if (u_total == 0) break;                              // ... unless no rank has any: the graph is pruned
+        KCHECK(S.agree_on_edge_replay(p));            // rank 0 replays the edge removals; all ranks agree on their number
+        KCHECK(S.ask_edge_fates(p));                  // every rank's candidate edges: which die, which move where
+        KCHECK(S.apply_edge_fates(p));
+        KCHECK(S.send_losses_and_dies(p));            // losses to the targets' owners, the barrier, the endpoints that go to rank 0
+        KCHECK(S.agree_on_node_replay(p));            // rank 0 replays the node removals; all ranks agree on their number
+        KCHECK(S.ask_node_moves(p));                  // the tail nodes that stay: where they go
+        S.end_pass(p);
     }
-    if (trace)
-        fprintf(stderr, "[dist prune] rank %d router: %llu sends, %llu replies; host ms: partition %.1f, count rounds %.1f, exchanges %.1f\n", rank,
-                (unsigned long long)router.n_send, (unsigned long long)router.n_reply, router.t_part, router.t_counts, router.t_xchg);
-    if (trace)
-        fprintf(stderr, "[dist prune] rank %d: %llu passes; ms: walks+marks %.1f, marks->root+edge replay %.1f, edge questions %.1f, apply+losses %.1f, "
-                        "dies+node replay %.1f, node questions %.1f; of the second: marks kernel %.1f, send %.1f, sort+replay %.1f; walks: first_out %.1f, words+delta %.1f, allgather+apply %.1f, "
-                        "input list %.1f, walk %.1f, scan+marks %.1f, marks routed %.1f\n", rank, (unsigned long long)st.passes, t_sec[0], t_sec[1], t_sec[2], t_sec[3], t_sec[4], t_sec[5], t_sec[8], t_sec[9], t_sec[10],
-                t_sec[11], t_sec[12], t_sec[13], t_sec[14], t_sec[15], t_sec[16], t_sec[0]);
-    // ---- the pruned graph, still sharded: survivors compacted, positions as indices, ages kept ---------------------------------
-    DevBuf keep_e(stream), keep_n(stream);
-    KCHECK(keep_e.alloc((E + 1) * 4)); KCHECK(keep_n.alloc((N + 1) * 4));
-    KCHECK(reset_cursors());
-    if (E) KLAUNCH_T(alive_list_kernel, E, stream, alive_e.as<unsigned char>(), E, keep_e.as<u32>(), cur);
-    if (N) KLAUNCH_T(alive_list_kernel, N, stream, alive_n.as<unsigned char>(), N, keep_n.as<u32>(), cur + 1);
-    KCHECK_HIP(hipGetLastError());
-    uint64_t hc[2] = {0, 0};
-    KCHECK(read_cursors(hc, 2));
-    const uint64_t E2 = hc[0], N2 = hc[1];
-    // (wave_append hands out places in no particular order: back into local order, which is key order)
-    {
-        DevBuf k64(stream);
-        KCHECK(k64.alloc((std::max(E2, N2) + 1) * 8));
-        auto order = [&](DevBuf& keep, uint64_t n) -> int {
-            if (n < 2) return KATOME_OK;
-            KLAUNCH(widen_kernel, n, stream, keep.as<u32>(), n, k64.as<u64>());
-            KCHECK(dev_sort(k64.as<u64>(), nullptr, n, 1, 32, stream));
-            KLAUNCH(narrow_kernel, n, stream, k64.as<u64>(), n, keep.as<u32>());
-            KCHECK_HIP(hipGetLastError());
-            return KATOME_OK;
-        };
-        KCHECK(order(keep_e, E2)); KCHECK(order(keep_n, N2));
-    }
-    DevBuf n_key(stream), n_gid(stream), e_key(stream), e_w(stream), e_gid(stream), e_age(stream), e_src(stream), e_dst(stream);
-    KCHECK(n_key.alloc((N2 + 1) * 8 * nw)); KCHECK(n_gid.alloc((N2 + 1) * 8));
-    KCHECK(e_key.alloc((E2 + 1) * 8 * nw)); KCHECK(e_w.alloc((E2 + 1) * 4)); KCHECK(e_gid.alloc((E2 + 1) * 8)); KCHECK(e_age.alloc((E2 + 1) * 8));
-    KCHECK(e_src.alloc((E2 + 1) * 8)); KCHECK(e_dst.alloc((E2 + 1) * 8));
-    {   // targets' indices: asked of their owners (all edges; the dead ones are dropped below)
-        DevBuf msg(stream), dst_all(stream), ans(stream);
-        KCHECK(msg.alloc((E + 1) * 8)); KCHECK(dst_all.alloc((E + 1) * 8));
-        if (E) KLAUNCH(target_msg_kernel, E, stream, drank, dlocal, E, msg.as<u64>());
-        Routed asked(stream);
-        KCHECK(router.send(msg.as<u64>(), nullptr, E, asked));
-        KCHECK(ans.alloc((asked.n + 1) * 8));
-        if (asked.n) KLAUNCH(npos_of_kernel, asked.n, stream, asked.a.as<u64>(), asked.n, npos.as<u64>(), ans.as<u64>());
-        KCHECK_HIP(hipGetLastError());
-        KCHECK(router.reply(asked, ans.as<u64>(), dst_all.as<u64>()));
-        if (E2) KLAUNCH(gather_by_kernel<u64>, E2, stream, dst_all.as<u64>(), keep_e.as<u32>(), E2, e_dst.as<u64>());
-    }
-    if (E2) {
-        KLAUNCH(gather_src_kernel, E2, stream, keep_e.as<u32>(), E2, lsrc, npos.as<u64>(), e_src.as<u64>());
-        KLAUNCH(gather_by_kernel<u64>, E2, stream, pos.as<u64>(), keep_e.as<u32>(), E2, e_gid.as<u64>());
-        KLAUNCH(gather_by_kernel<u64>, E2, stream, age.as<u64>(), keep_e.as<u32>(), E2, e_age.as<u64>());
-        KLAUNCH(gather_by_kernel<u32>, E2, stream, b->edge_weight.as<u32>(), keep_e.as<u32>(), E2, e_w.as<u32>());
-        if (nw == 1) KLAUNCH(gather_keys_by_kernel<1>, E2, stream, b->edge_key.as<u64>(), keep_e.as<u32>(), E2, e_key.as<u64>());
-        else         KLAUNCH(gather_keys_by_kernel<2>, E2, stream, b->edge_key.as<u64>(), keep_e.as<u32>(), E2, e_key.as<u64>());
-    }
-    if (N2) {
-        KLAUNCH(gather_by_kernel<u64>, N2, stream, npos.as<u64>(), keep_n.as<u32>(), N2, n_gid.as<u64>());
-        if (nw == 1) KLAUNCH(gather_keys_by_kernel<1>, N2, stream, d->node_key.as<u64>(), keep_n.as<u32>(), N2, n_key.as<u64>());
-        else         KLAUNCH(gather_keys_by_kernel<2>, N2, stream, d->node_key.as<u64>(), keep_n.as<u32>(), N2, n_key.as<u64>());
-    }
-    KCHECK_HIP(hipGetLastError());
-    KCHECK_HIP(hipStreamSynchronize(stream));
-    auto install = [&](DevBuf& dst, DevBuf& src) { const size_t bytes = src.bytes; dst.stream = stream; dst.adopt(src.take(), bytes); };
-    install(b->edge_key, e_key); install(b->edge_weight, e_w); install(d->edge_src, e_src); install(d->edge_dst, e_dst);
-    install(d->edge_gid, e_gid); install(d->edge_age, e_age); install(d->node_key, n_key); install(d->node_gid, n_gid);
-    b->edge_seq.release();
-    d->edge_lsrc.release(); d->edge_drank.release(); d->edge_dlocal.release();      // (local indices of the unpruned share: stale now)
-    const uint32_t lstride = label_stride_for_k(k);
-    KCHECK(d->edge_label.alloc((E2 + 1) * (size_t)lstride + 16, stream));
-    KCHECK(dev_labels(b->edge_key.as<u64>(), E2, k, d->edge_label.as<uint8_t>(), stream));
-    KCHECK_HIP(hipStreamSynchronize(stream));
-    b->n_edges = E2;
-    d->n_edges = E2; d->n_nodes = N2; d->total_edges = TE; d->total_nodes = TN; d->n_src = 0;
-    d->dead_paths_removed = true;
+    S.print_trace();
+    KCHECK(S.install_result());
+    katome_prune_stats& st = S.st;
     {   // the walks and marks of all ranks
         uint64_t sums[3] = {st.walks, st.dead_walks, st.marked};
         KCHECK(d->comm->allreduce(sums, 3, OP_SUM));
@@ -869,3 +987,4 @@ extern "C" int katome_dist_remove_dead_paths(katome_dist_builder* d, katome_dist
     if (st_out) *st_out = st;
     return katome_dist_current_graph(d, out);
 }
+

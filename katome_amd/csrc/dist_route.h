@@ -9,7 +9,6 @@
 
 namespace {
 
-#define KLAUNCH(kernel, n, stream, ...) hipLaunchKernelGGL(kernel, dim3(grid_for((n), BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, __VA_ARGS__)
 // whole waves stay in the loop together (wave_append votes)
 #define WLOOP(i, n) for (u64 i##0 = (u64)blockIdx.x * BLOCK, i = i##0 + threadIdx.x; i##0 < (n); i##0 += (u64)gridDim.x * BLOCK, i = i##0 + threadIdx.x)
 
@@ -95,8 +94,6 @@ __global__ __launch_bounds__(BLOCK) void zip2_kernel(const u64* __restrict__ pa,
 __global__ __launch_bounds__(BLOCK) void unzip2_kernel(const u64* __restrict__ in, u64 n, u64* __restrict__ a, u64* __restrict__ b) {
     WLOOP(i, n) if (i < n) { a[i] = in[2 * i]; b[i] = in[2 * i + 1]; }
 }
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 // records with their destination rank in the top byte of column A [and a second column] -> their destinations
 struct Routed {
     DevBuf a, b, pidx;

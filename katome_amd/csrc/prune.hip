@@ -19,6 +19,13 @@
 //     which removal, and the resulting moves applied to the arrays;
 //   * prune_replay.h keeps the sequential statement of the two replays for a pass whose vertex moves chain further than
 //     the device form follows (and for A/B runs).
+//
+// The driver is at the end of the file.  PruneRun holds one call's state: the graph's arrays, the adjacency summary and the
+// slots, the scratch that lives across the passes, the environment switches (read once) and the KATOME_TRACE_PRUNE laps.
+// dev_remove_dead_paths builds the adjacency once (build_adjacency) and then repeats six steps until a pass's walks mark
+// nothing: (1) walk, (2) marked_indices, (3) replay_edges_step, (4) deaths, (5) replay_nodes_step, (6) apply -- with the slots
+// only what changed (apply_with_slots), without them a pass over all edges (apply_streaming).  What (3) and (5) find travels
+// to (6) as EdgeMoves / NodeMoves.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -783,9 +790,6 @@ __global__ __launch_bounds__(BLOCK) void node_moves_kernel(const unsigned char* 
     }
 }
 
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 // scratch that lives across the passes: re-allocated only when a pass needs more than any before it (the block sizes
 // differ from pass to pass, so handing them back each time defeats the caching allocator and hipMalloc/hipFree of
@@ -834,22 +838,19 @@ static int replay_edges_t(const I* d_pos, const uint32_t* d_mult, uint64_t u, ui
     KCHECK(ensure(to_e, u * W + 16, stream)); KCHECK(ensure(from_e, u * W + 16, stream));
     const u64 all = u;                                           // totals[4]: entries below the new count (default: all)
     KCHECK_HIP(hipMemcpyAsync(totals.as<u64>() + 4, &all, 8, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(iota_from_kernel<I>, dim3(grid_for(m, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, jump.as<I>(), m, (I)E_new);
-    hipLaunchKernelGGL(replay_links_kernel<I>, dim3(grid_for(u, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, d_pos, d_mult,
-                       size_before.as<I>(), u, E_new, jump.as<I>(), totals.as<u64>());
+    KLAUNCH(iota_from_kernel<I>, m, stream, jump.as<I>(), m, (I)E_new);
+    KLAUNCH(replay_links_kernel<I>, u, stream, d_pos, d_mult, size_before.as<I>(), u, E_new, jump.as<I>(), totals.as<u64>());
     for (int round = 0; round < 64; ++round) {
         KCHECK_HIP(hipMemsetAsync(totals.as<u64>() + 6, 0, 8, stream));
         for (int rep = 0; rep < 2; ++rep)
-            hipLaunchKernelGGL(retain_jump_kernel<I>, dim3(grid_for(m, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, jump.as<I>(), m, E_new,
-                               reinterpret_cast<u32*>(totals.as<u64>() + 6));
+            KLAUNCH(retain_jump_kernel<I>, m, stream, jump.as<I>(), m, E_new, reinterpret_cast<u32*>(totals.as<u64>() + 6));
         u64 changed = 0;
         KCHECK_HIP(hipMemcpyAsync(&changed, totals.as<u64>() + 6, 8, hipMemcpyDeviceToHost, stream));
         KCHECK_HIP(hipStreamSynchronize(stream));
         if (!changed) break;
     }
-    hipLaunchKernelGGL(replay_emit_kernel<I>, dim3(grid_for(u, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, d_pos, d_mult,
-                       size_before.as<I>(), u, E, E_new, jump.as<I>(), d_victims.as<I>(), to_e.as<I>(), from_e.as<I>(),
-                       totals.as<u64>());
+    KLAUNCH(replay_emit_kernel<I>, u, stream, d_pos, d_mult, size_before.as<I>(), u, E, E_new, jump.as<I>(), d_victims.as<I>(), to_e.as<I>(), from_e.as<I>(),
+            totals.as<u64>());
     KCHECK_HIP(hipGetLastError());
     u64 h2[2] = {0, 0};
     KCHECK_HIP(hipMemcpyAsync(h2, totals.as<u64>() + 4, 16, hipMemcpyDeviceToHost, stream));
@@ -895,16 +896,15 @@ static int replay_nodes_t(const I* d_die, uint64_t m, uint64_t N, NodeReplayScra
     u32 h_flags[2] = {1, 0};
     for (int round = 0; round < 256 && h_flags[0] && !h_flags[1]; ++round) {
         KCHECK_HIP(hipMemsetAsync(sc.flags.p, 0, 32, stream));
-        hipLaunchKernelGGL(node_holes_kernel<I>, dim3(grid_for(m, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, d_die, sc.first.as<I>(), m, N, base_pos,
-                           sc.hole.as<I>(), sc.flags.as<u32>());
+        KLAUNCH(node_holes_kernel<I>, m, stream, d_die, sc.first.as<I>(), m, N, base_pos, sc.hole.as<I>(), sc.flags.as<u32>());
         KCHECK_HIP(hipGetLastError());
         KCHECK_HIP(hipMemcpyAsync(h_flags, sc.flags.p, 8, hipMemcpyDeviceToHost, stream));
         KCHECK_HIP(hipStreamSynchronize(stream));
     }
     if (h_flags[0] || h_flags[1]) { *fell_back = 1; return KATOME_OK; }
     KCHECK_HIP(hipMemsetAsync(sc.flags.p, 0, 32, stream));
-    hipLaunchKernelGGL(node_moves_kernel<I>, dim3(grid_for(M, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, sc.dead.as<unsigned char>(), M, base_pos,
-                       sc.hole.as<I>(), to_n.as<I>(), from_n.as<I>(), reinterpret_cast<u64*>(sc.flags.as<u32>() + 4), sc.flags.as<u32>());
+    KLAUNCH(node_moves_kernel<I>, M, stream, sc.dead.as<unsigned char>(), M, base_pos, sc.hole.as<I>(), to_n.as<I>(), from_n.as<I>(),
+            reinterpret_cast<u64*>(sc.flags.as<u32>() + 4), sc.flags.as<u32>());
     KCHECK_HIP(hipGetLastError());
     u32 h_end[6] = {0, 0, 0, 0, 0, 0};
     KCHECK_HIP(hipMemcpyAsync(h_end, sc.flags.p, 24, hipMemcpyDeviceToHost, stream));
@@ -943,160 +943,190 @@ int dev_replay_nodes64(const uint64_t* d_die, uint64_t m, uint64_t N, NodeReplay
     return KATOME_OK;
 }
 
-int dev_remove_dead_paths(PruneGraph& g, uint32_t k, katome_prune_stats* st, hipStream_t stream) {
-    katome_prune_stats local;
-    memset(&local, 0, sizeof local);
-    if (g.n_edges >= 0xFFFFFFFFull || g.n_nodes >= 0xFFFFFFFFull) {
-        set_error("remove_dead_paths: more than 2^32 edges or nodes on one GPU");
-        return KATOME_E_UNSUPPORTED;
-    }
-    const u32 nw = g.nw, two_k = 2 * k;
-    u64 E = g.n_edges, N = g.n_nodes;
-    u64* src = g.edge_src->as<u64>(); u64* dst = g.edge_dst->as<u64>();
-    u32* weight = g.edge_weight->as<u32>(); u64* key = g.edge_key->as<u64>(); u64* node_key = g.node_key->as<u64>();
-    DevBuf node_deg(stream), first_out(stream), mult(stream), totals(stream), touched(stream);
-    DevBuf& orig = *g.edge_age;
-    if (orig.bytes < (E + 1) * 4) {
-        KCHECK(orig.alloc((E + 1) * 4, stream));
-        KCHECK(dev_iota(orig.as<u32>(), E, stream));
-    }
-    KCHECK(node_deg.alloc((N + 1) * 8)); KCHECK(first_out.alloc((N + 1) * 8)); KCHECK(mult.alloc((E + 1) * 4));
-    KCHECK(totals.alloc(64));
-    PinnedU32 h_pos, h_mult, h_die;
-    EdgeReplay er; NodeReplay nr;
-    DevBuf counts(stream), offs(stream), d_pos(stream), d_mult(stream), d_victims(stream), last_touch(stream), d_die(stream);
-    DevBuf to_e(stream), from_e(stream), to_n(stream), from_n(stream), tail_map(stream), inputs(stream);
-    ReplayScratch replay_scratch(stream);
-    NodeReplayScratch node_scratch(stream);
+// ---- the driver: one call's state, a pass as six steps ------------------------------------------------------------------
+namespace {
+
+// what stage (3) found: m victims in d_victims, n_moves moves in to_e / from_e; what stage (5) found: n_moves moves in to_n / from_n
+struct EdgeMoves { u64 m = 0, E_new = 0, n_moves = 0, dups = 0; double host_ms = 0; };
+struct NodeMoves { u64 n_moves = 0, N_new = 0; double host_ms = 0; };
+
+struct PruneRun {
+    const hipStream_t stream;
+    const u32 nw, k, two_k;
+    u64 E, N;
+    // the graph's arrays, changed in place
+    u64 *src, *dst; u32* weight; u64 *key, *node_key;
+    DevBuf& orig;                             // every edge's first-seen index
+    // the switches, read once
+    const bool parallel_edges;
     const bool host_nodes = getenv("KATOME_PRUNE_HOST_NODES") != nullptr;
     const bool host_edges = getenv("KATOME_PRUNE_HOST_EDGES") != nullptr;      // the sequential replay of prune_replay.h (A/B checks)
-    KCHECK(last_touch.alloc((N + 1) * 4));
-    // adjacency slots (32 B per vertex): without them -- not enough memory, or KATOME_PRUNE_NO_SLOTS -- every pass streams all edges
-    DevBuf out_slots(stream), in_slots(stream), redo_list(stream), stamp(stream);
-    Slots slots{nullptr, nullptr, nw, k};
-    if (!g.parallel_edges && !getenv("KATOME_PRUNE_NO_SLOTS") && out_slots.alloc((N + 1) * 16) == KATOME_OK && in_slots.alloc((N + 1) * 16) == KATOME_OK) {
-        slots.out = out_slots.as<u32>(); slots.in = in_slots.as<u32>();
-    } else {
-        out_slots.release(); in_slots.release();
-    }
+    const bool no_slots = getenv("KATOME_PRUNE_NO_SLOTS") != nullptr;
+    const bool check_walks = getenv("KATOME_PRUNE_CHECK_WALKS") != nullptr;    // walk everything and verify that the skipped walks are not dead
+    const u64 track_max = getenv("KATOME_PRUNE_WALK_ALL") ? 0 : (1ull << 20);  // passes that remove more edges than this re-walk everything
     const bool trace = getenv("KATOME_TRACE_PRUNE") != nullptr;
-    double lap_t = now_ms();
-    auto lap = [&](const char* what) {
+    double lap_t = 0;
+    // adjacency summary, built once and kept current
+    DevBuf node_deg, first_out, mult, totals, touched, last_touch, stamp;
+    // adjacency slots (32 B per vertex): without them -- not enough memory, or KATOME_PRUNE_NO_SLOTS -- every pass streams all edges
+    DevBuf out_slots, in_slots, redo_list;
+    Slots slots;
+    // scratch that lives across the passes and only grows (ensure)
+    DevBuf counts, offs, d_pos, d_mult, d_victims, d_die, to_e, from_e, to_n, from_n, tail_map;
+    DevBuf inputs, inputs_next, fresh_inputs, changed;
+    ReplayScratch replay_scratch;
+    NodeReplayScratch node_scratch;
+    PinnedU32 h_pos, h_mult, h_die;
+    EdgeReplay er; NodeReplay nr;
+    // carried from one pass to the next
+    bool nodes_moved = false;                 // tail_map holds the moves of the pass before
+    bool have_inputs = false;                 // `inputs` already holds this pass's Input vertices
+    u64 n_inputs = 0;
+    u32 walk_from = 0;                        // 0: walk every listed vertex; else only those stamped at or above this (affected_kernel)
+    katome_prune_stats st;
+
+    PruneRun(PruneGraph& g, u32 k_, hipStream_t s)
+        : stream(s), nw(g.nw), k(k_), two_k(2 * k_), E(g.n_edges), N(g.n_nodes), src(g.edge_src->as<u64>()), dst(g.edge_dst->as<u64>()),
+          weight(g.edge_weight->as<u32>()), key(g.edge_key->as<u64>()), node_key(g.node_key->as<u64>()), orig(*g.edge_age),
+          parallel_edges(g.parallel_edges), node_deg(s), first_out(s), mult(s), totals(s), touched(s), last_touch(s), stamp(s), out_slots(s),
+          in_slots(s), redo_list(s), slots{nullptr, nullptr, g.nw, k_}, counts(s), offs(s), d_pos(s), d_mult(s), d_victims(s), d_die(s), to_e(s),
+          from_e(s), to_n(s), from_n(s), tail_map(s), inputs(s), inputs_next(s), fresh_inputs(s), changed(s), replay_scratch(s), node_scratch(s) {
+        memset(&st, 0, sizeof st);
+    }
+    // (synchronizes, so only under the trace)
+    void lap(const char* what) {
         if (!trace) return;
         (void)hipStreamSynchronize(stream);
         const double t = now_ms();
         fprintf(stderr, "[prune]   %-18s %9.2f ms\n", what, t - lap_t);
         lap_t = t;
-    };
-    // adjacency summary, once
-    KCHECK_HIP(hipMemsetAsync(node_deg.p, 0, N * 8, stream));
-    KCHECK_HIP(hipMemsetAsync(first_out.p, 0, N * 8, stream));
-    KCHECK_HIP(hipMemsetAsync(mult.p, 0, E * 4, stream));
-    KCHECK(touched.alloc((E >> MARK_GROUP_SHIFT) + 16));
-    KCHECK_HIP(hipMemsetAsync(touched.p, 0, (E >> MARK_GROUP_SHIFT) + 16, stream));
-    if (E) hipLaunchKernelGGL(degree_kernel, dim3(grid_for(E, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, src, dst, orig.as<u32>(), E,
-                              node_deg.as<u64>(), first_out.as<u64>());
-    if (N) hipLaunchKernelGGL(successor_kernel, dim3(grid_for(N, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, N, first_out.as<u64>(), dst,
-                              node_deg.as<u64>());
-    KCHECK(stamp.alloc((slots.out ? N + 1 : 1) * 4));
-    if (slots.out) KCHECK_HIP(hipMemsetAsync(stamp.p, 0, (N + 1) * 4, stream));
-    if (slots.out && E) {
-        KCHECK_HIP(hipMemsetAsync(out_slots.p, 0xFF, N * 16, stream));
-        KCHECK_HIP(hipMemsetAsync(in_slots.p, 0xFF, N * 16, stream));
-        hipLaunchKernelGGL(slots_init_kernel, dim3(grid_for(E, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, src, dst, key, E, slots);
     }
-    KCHECK_HIP(hipGetLastError());
-    lap("adjacency");
-    bool nodes_moved = false;                 // tail_map holds the moves of the pass before
-    bool have_inputs = false;                 // `inputs` already holds this pass's Input vertices
-    u64 n_inputs = 0;
-    DevBuf inputs_next(stream), fresh_inputs(stream), changed(stream);
-    const bool check_walks = getenv("KATOME_PRUNE_CHECK_WALKS") != nullptr;   // walk everything and verify that the skipped walks are not dead
-    u32 walk_from = 0;                        // 0: walk every listed vertex; else only those stamped at or above this (affected_kernel)
-    const u64 track_max = getenv("KATOME_PRUNE_WALK_ALL") ? 0 : (1ull << 20);   // passes that remove more edges than this re-walk everything
-    while (E) {
-        const double pass_t0 = now_ms();
-        double pass_host = 0;
-        // (1) walks
+    u32 next_stamp() const { return (u32)(st.passes + 1) * STAMP_STEP; }
+
+    int build_adjacency() {
+        if (orig.bytes < (E + 1) * 4) {
+            KCHECK(orig.alloc((E + 1) * 4, stream));
+            KCHECK(dev_iota(orig.as<u32>(), E, stream));
+        }
+        KCHECK(node_deg.alloc((N + 1) * 8)); KCHECK(first_out.alloc((N + 1) * 8)); KCHECK(mult.alloc((E + 1) * 4));
+        KCHECK(totals.alloc(64));
+        KCHECK(last_touch.alloc((N + 1) * 4));
+        if (!parallel_edges && !no_slots && out_slots.alloc((N + 1) * 16) == KATOME_OK && in_slots.alloc((N + 1) * 16) == KATOME_OK) {
+            slots.out = out_slots.as<u32>(); slots.in = in_slots.as<u32>();
+        } else {
+            out_slots.release(); in_slots.release();
+        }
+        lap_t = now_ms();
+        KCHECK_HIP(hipMemsetAsync(node_deg.p, 0, N * 8, stream));
+        KCHECK_HIP(hipMemsetAsync(first_out.p, 0, N * 8, stream));
+        KCHECK_HIP(hipMemsetAsync(mult.p, 0, E * 4, stream));
+        KCHECK(touched.alloc((E >> MARK_GROUP_SHIFT) + 16));
+        KCHECK_HIP(hipMemsetAsync(touched.p, 0, (E >> MARK_GROUP_SHIFT) + 16, stream));
+        if (E) KLAUNCH(degree_kernel, E, stream, src, dst, orig.as<u32>(), E, node_deg.as<u64>(), first_out.as<u64>());
+        if (N) KLAUNCH(successor_kernel, N, stream, N, first_out.as<u64>(), dst, node_deg.as<u64>());
+        KCHECK(stamp.alloc((slots.out ? N + 1 : 1) * 4));
+        if (slots.out) KCHECK_HIP(hipMemsetAsync(stamp.p, 0, (N + 1) * 4, stream));
+        if (slots.out && E) {
+            KCHECK_HIP(hipMemsetAsync(out_slots.p, 0xFF, N * 16, stream));
+            KCHECK_HIP(hipMemsetAsync(in_slots.p, 0xFF, N * 16, stream));
+            KLAUNCH(slots_init_kernel, E, stream, src, dst, key, E, slots);
+        }
+        KCHECK_HIP(hipGetLastError());
+        lap("adjacency");
+        return KATOME_OK;
+    }
+
+    // (1) the walks from the Input vertices.  h_tot: {marks, dead walks, Input vertices, walks made, dead walks the tracking would have skipped}
+    int walk(u64 h_tot[5]) {
         KCHECK_HIP(hipMemsetAsync(totals.p, 0, 64, stream));
         if (have_inputs) {                                   // carried over from the pass before (inputs_update_kernel)
             KCHECK_HIP(hipMemcpyAsync(totals.as<u64>() + 2, &n_inputs, 8, hipMemcpyHostToDevice, stream));
         } else {
             KCHECK(ensure(inputs, N * 4 + 16, stream));
-            hipLaunchKernelGGL(input_list_kernel, dim3(grid_for(N, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, N, node_deg.as<u64>(),
-                               first_out.as<u64>(), dst, (nodes_moved && !slots.out) ? tail_map.as<u32>() : (const u32*)nullptr, inputs.as<u32>(), totals.as<u64>(), slots.out != nullptr);
+            KLAUNCH(input_list_kernel, N, stream, N, node_deg.as<u64>(), first_out.as<u64>(), dst,
+                    (nodes_moved && !slots.out) ? tail_map.as<u32>() : (const u32*)nullptr, inputs.as<u32>(), totals.as<u64>(), slots.out != nullptr);
         }
         hipLaunchKernelGGL(walk_kernel, dim3(256u * 16u), dim3(BLOCK), 0, stream, inputs.as<u32>(), two_k, first_out.as<u64>(), dst,
                            node_deg.as<u64>(), mult.as<u32>(), touched.as<unsigned char>(), stamp.as<u32>(), walk_from, check_walks, totals.as<u64>());
         KCHECK_HIP(hipGetLastError());
-        u64 h_tot[5] = {0, 0, 0, 0, 0};
+        memset(h_tot, 0, 40);
         KCHECK_HIP(hipMemcpyAsync(h_tot, totals.p, 40, hipMemcpyDeviceToHost, stream));
         KCHECK_HIP(hipStreamSynchronize(stream));
         lap("walks");
-        if (h_tot[4]) { set_error("remove_dead_paths: %llu dead walks started at vertices the change tracking would have skipped (pass %llu)", (unsigned long long)h_tot[4], (unsigned long long)local.passes + 1); return KATOME_E_DEVICE; }
-        local.passes += 1;
-        local.walks += h_tot[3];
-        if (h_tot[0] == 0) break;                         // to_remove.is_empty() (pruner.rs:76)
-        local.dead_walks += h_tot[1];
-        local.marked += h_tot[0];
-        // (2) the marked indices, ascending (the reference sorts them descending; they are consumed from the top)
+        if (h_tot[4]) { set_error("remove_dead_paths: %llu dead walks started at vertices the change tracking would have skipped (pass %llu)", (unsigned long long)h_tot[4], (unsigned long long)st.passes + 1); return KATOME_E_DEVICE; }
+        st.passes += 1;
+        st.walks += h_tot[3];
+        if (h_tot[0]) { st.dead_walks += h_tot[1]; st.marked += h_tot[0]; }
+        return KATOME_OK;
+    }
+
+    // (2) the marked indices, ascending (the reference sorts them descending; they are consumed from the top): d_pos / d_mult [*u]
+    int marked_indices(u64* u) {
         const u64 nblocks = (E + (u64)BLOCK * MARK_ITEMS - 1) / ((u64)BLOCK * MARK_ITEMS);
         KCHECK(ensure(counts, nblocks * 4 + 16, stream)); KCHECK(ensure(offs, (nblocks + 1) * 8 + 16, stream));
         hipLaunchKernelGGL(mark_count_kernel, dim3((unsigned)nblocks), dim3(BLOCK), 0, stream, mult.as<u32>(), E, counts.as<u32>(),
                            (const unsigned char*)touched.as<unsigned char>());
         KCHECK(dev_scan_counts(counts.as<u32>(), nblocks, offs.as<u64>(), stream));
-        u64 u = 0;
-        KCHECK_HIP(hipMemcpyAsync(&u, offs.as<u64>() + nblocks, 8, hipMemcpyDeviceToHost, stream));
+        *u = 0;
+        KCHECK_HIP(hipMemcpyAsync(u, offs.as<u64>() + nblocks, 8, hipMemcpyDeviceToHost, stream));
         KCHECK_HIP(hipStreamSynchronize(stream));
-        KCHECK(ensure(d_pos, u * 4 + 16, stream)); KCHECK(ensure(d_mult, u * 4 + 16, stream));
+        KCHECK(ensure(d_pos, *u * 4 + 16, stream)); KCHECK(ensure(d_mult, *u * 4 + 16, stream));
         hipLaunchKernelGGL(mark_write_kernel, dim3((unsigned)nblocks), dim3(BLOCK), 0, stream, mult.as<u32>(), E, offs.as<u64>(),
                            d_pos.as<u32>(), d_mult.as<u32>(), (const unsigned char*)touched.as<unsigned char>());
-        if (u) hipLaunchKernelGGL(mark_clear_kernel, dim3(grid_for(u, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, d_pos.as<u32>(), u, mult.as<u32>(),
-                                  touched.as<unsigned char>());
+        if (*u) KLAUNCH(mark_clear_kernel, *u, stream, d_pos.as<u32>(), *u, mult.as<u32>(), touched.as<unsigned char>());
         KCHECK_HIP(hipGetLastError());
-        u64 m = 0, E_new = E, n_edge_moves = 0, dups = 0;
-        double t_edges = 0;
+        return KATOME_OK;
+    }
+
+    // (3) replay of remove_edge: the sequential statement on the host, or the same as a scan + pointer jumping without leaving the device
+    int replay_edges_step(u64 u, u64 n_marks, EdgeMoves* em) {
+        em->E_new = E;
         if (host_edges) {
             KCHECK(h_pos.need(u)); KCHECK(h_mult.need(u));
             KCHECK_HIP(hipMemcpyAsync(h_pos.p, d_pos.p, u * 4, hipMemcpyDeviceToHost, stream));
             KCHECK_HIP(hipMemcpyAsync(h_mult.p, d_mult.p, u * 4, hipMemcpyDeviceToHost, stream));
             KCHECK_HIP(hipStreamSynchronize(stream));
             lap("marks to host");
-            // (3) replay of remove_edge
             const double t0 = now_ms();
-            replay_edges(h_pos.p, h_mult.p, u, E, h_tot[0], er);
-            t_edges = now_ms() - t0;
-            local.host_ms += t_edges; pass_host += t_edges;
-            m = er.victims.size(); E_new = er.n_new; dups = er.from_duplicates; n_edge_moves = er.move_to.size();
+            replay_edges(h_pos.p, h_mult.p, u, E, n_marks, er);
+            em->host_ms = now_ms() - t0;
+            st.host_ms += em->host_ms;
+            em->m = er.victims.size(); em->E_new = er.n_new; em->dups = er.from_duplicates; em->n_moves = er.move_to.size();
             KCHECK(upload(d_victims, er.victims, stream));
             KCHECK(upload(to_e, er.move_to, stream)); KCHECK(upload(from_e, er.move_from, stream));
         } else {
-            // (3) the same replay as a scan + pointer jumping, without leaving the device
-            KCHECK(dev_replay_edges(d_pos.as<u32>(), d_mult.as<u32>(), u, E, replay_scratch, d_victims, to_e, from_e, &m, &E_new, &n_edge_moves, &dups, stream));
+            KCHECK(dev_replay_edges(d_pos.as<u32>(), d_mult.as<u32>(), u, E, replay_scratch, d_victims, to_e, from_e, &em->m, &em->E_new, &em->n_moves,
+                                    &em->dups, stream));
         }
-        local.removed_edges += m;
-        local.removed_by_duplicates += dups;
+        st.removed_edges += em->m;
+        st.removed_by_duplicates += em->dups;
         lap("replay edges");
-        // (4) the nodes each removal isolates
+        return KATOME_OK;
+    }
+
+    // (4) the nodes each of the m removals isolates -> d_die.  *track: the pass is small enough to note what it changed (affected_kernel)
+    int deaths(u64 m, bool* track) {
         KCHECK(ensure(d_die, 2 * m * 4 + 16, stream));
         KCHECK_HIP(hipMemsetAsync(last_touch.p, 0, N * 4, stream));
         if (slots.out) {
             KCHECK(ensure(redo_list, m * 4 + 16, stream)); KCHECK(ensure(fresh_inputs, 2 * m * 4 + 16, stream));
             KCHECK_HIP(hipMemsetAsync(totals.as<u64>() + 4, 0, 24, stream));       // [4] changed vertices, [5] lost their first out-edge, [6] new Inputs
         }
-        const bool track = slots.out && m <= track_max;
-        if (track) KCHECK(ensure(changed, 2 * m * 4 + 16, stream));
-        hipLaunchKernelGGL(death_count_kernel, dim3(grid_for(m, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, d_victims.as<u32>(), m, src, dst,
-                           node_deg.as<u64>(), first_out.as<u64>(), last_touch.as<u32>(), slots, key, redo_list.as<u32>(), totals.as<u64>() + 5);
-        hipLaunchKernelGGL(death_emit_kernel, dim3(grid_for(m, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, d_victims.as<u32>(), m, src, dst,
-                           node_deg.as<u64>(), last_touch.as<u32>(), d_die.as<u32>(), slots.out ? fresh_inputs.as<u32>() : (u32*)nullptr,
-                           totals.as<u64>() + 6, track ? changed.as<u32>() : (u32*)nullptr, totals.as<u64>() + 4);
+        *track = slots.out && m <= track_max;
+        if (*track) KCHECK(ensure(changed, 2 * m * 4 + 16, stream));
+        KLAUNCH(death_count_kernel, m, stream, d_victims.as<u32>(), m, src, dst, node_deg.as<u64>(), first_out.as<u64>(), last_touch.as<u32>(), slots, key,
+                redo_list.as<u32>(), totals.as<u64>() + 5);
+        KLAUNCH(death_emit_kernel, m, stream, d_victims.as<u32>(), m, src, dst, node_deg.as<u64>(), last_touch.as<u32>(), d_die.as<u32>(),
+                slots.out ? fresh_inputs.as<u32>() : (u32*)nullptr, totals.as<u64>() + 6, *track ? changed.as<u32>() : (u32*)nullptr, totals.as<u64>() + 4);
         KCHECK_HIP(hipGetLastError());
-        // (5) replay of remove_node: on the device, or (chains too long for that form, or asked for) on the host
-        u64 n_node_moves = 0, N_new = N;
-        double t_nodes = 0;
+        return KATOME_OK;
+    }
+
+    // (5) replay of remove_node: on the device, or (chains too long for that form, or asked for) on the host
+    int replay_nodes_step(u64 m, NodeMoves* nm) {
+        nm->N_new = N;
         int on_host = host_nodes ? 1 : 0;
-        if (!on_host) KCHECK(dev_replay_nodes(d_die.as<u32>(), m, N, node_scratch, to_n, from_n, &n_node_moves, &N_new, &on_host, stream));
+        if (!on_host) KCHECK(dev_replay_nodes(d_die.as<u32>(), m, N, node_scratch, to_n, from_n, &nm->n_moves, &nm->N_new, &on_host, stream));
         if (on_host) {
             KCHECK(h_die.need(2 * m));
             KCHECK_HIP(hipMemcpyAsync(h_die.p, d_die.p, 2 * m * 4, hipMemcpyDeviceToHost, stream));
@@ -1104,77 +1134,106 @@ int dev_remove_dead_paths(PruneGraph& g, uint32_t k, katome_prune_stats* st, hip
             lap("deaths to host");
             const double t0 = now_ms();
             replay_nodes(h_die.p, m, N, nr);
-            t_nodes = now_ms() - t0;
-            local.host_ms += t_nodes; pass_host += t_nodes;
-            n_node_moves = nr.move_to.size(); N_new = nr.n_new;
+            nm->host_ms = now_ms() - t0;
+            st.host_ms += nm->host_ms;
+            nm->n_moves = nr.move_to.size(); nm->N_new = nr.n_new;
             KCHECK(upload(to_n, nr.move_to, stream)); KCHECK(upload(from_n, nr.move_from, stream));
         }
-        local.removed_nodes += N - N_new;
+        st.removed_nodes += N - nm->N_new;
         lap("replay nodes");
-        // (6) apply the moves, re-label the endpoints of the surviving edges
-        {
-            const u64 ne = n_edge_moves;
-            if (ne) hipLaunchKernelGGL(move_edges_kernel, dim3(grid_for(ne, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, to_e.as<u32>(),
-                                       from_e.as<u32>(), ne, nw, src, dst, weight, orig.as<u32>(), key, first_out.as<u64>(), slots);
-            E = E_new;
-            const u64 nn = n_node_moves;
-            nodes_moved = nn != 0;
-            KCHECK(ensure(tail_map, (N - N_new + 1) * 4, stream));
-            if (slots.out) {
-                // what changed, and nothing else: new first out-edges (edge positions are final, node ids still the old ones),
-                // then the vertices move, then the edges in a moved vertex's slots learn its new id
-                u64 h_cnt[3] = {0, 0, 0};
-                KCHECK_HIP(hipMemcpyAsync(h_cnt, totals.as<u64>() + 4, 24, hipMemcpyDeviceToHost, stream));
-                KCHECK_HIP(hipStreamSynchronize(stream));
-                const u64 n_changed = h_cnt[0], n_redo = h_cnt[1], n_fresh = h_cnt[2];
-                if (n_redo) hipLaunchKernelGGL(redo_slots_kernel, dim3(grid_for(n_redo, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, redo_list.as<u32>(),
-                                               n_redo, slots, orig.as<u32>(), dst, node_deg.as<u64>(), first_out.as<u64>());
-                if (nn) hipLaunchKernelGGL(move_nodes_kernel, dim3(grid_for(nn, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, to_n.as<u32>(),
-                                           from_n.as<u32>(), nn, nw, N_new, node_key, node_deg.as<u64>(), first_out.as<u64>(), tail_map.as<u32>(), slots);
-                if (nn) hipLaunchKernelGGL(remap_slots_kernel, dim3(grid_for(nn, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, to_n.as<u32>(), nn, N_new,
-                                           tail_map.as<u32>(), slots, src, dst, first_out.as<u64>(), node_deg.as<u64>());
-                // next pass's Input vertices from this pass's, without a look at every vertex
-                const u64 n_old = h_tot[2], cand = n_old + n_fresh;
-                KCHECK(ensure(inputs_next, cand * 4 + 16, stream));
-                KCHECK_HIP(hipMemsetAsync(totals.as<u64>() + 7, 0, 8, stream));
-                if (cand) hipLaunchKernelGGL(inputs_update_kernel, dim3(grid_for(cand, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, inputs.as<u32>(), n_old,
-                                             fresh_inputs.as<u32>(), n_fresh, last_touch.as<u32>(), N_new, tail_map.as<u32>(), node_deg.as<u64>(),
-                                             inputs_next.as<u32>(), totals.as<u64>() + 7, stamp.as<u32>(), (u32)(local.passes + 1) * STAMP_STEP + (STAMP_STEP - 1));
-                // which of them the next pass has to walk: everything, or what lies within reach of a change
-                walk_from = 0;
-                if (track) {
-                    if (n_changed) hipLaunchKernelGGL(affected_kernel, dim3(grid_for(n_changed, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, changed.as<u32>(),
-                                                      n_changed, N_new, tail_map.as<u32>(), slots, src, node_deg.as<u64>(), stamp.as<u32>(),
-                                                      (u32)(local.passes + 1) * STAMP_STEP + (STAMP_STEP - 1), two_k);
-                    walk_from = (u32)(local.passes + 1) * STAMP_STEP;
-                }
-                KCHECK_HIP(hipGetLastError());
-                KCHECK_HIP(hipMemcpyAsync(&n_inputs, totals.as<u64>() + 7, 8, hipMemcpyDeviceToHost, stream));
-                KCHECK_HIP(hipStreamSynchronize(stream));
-                std::swap(inputs.p, inputs_next.p); std::swap(inputs.bytes, inputs_next.bytes);
-                have_inputs = true;
-            } else {
-                if (nn) hipLaunchKernelGGL(move_nodes_kernel, dim3(grid_for(nn, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, to_n.as<u32>(),
-                                           from_n.as<u32>(), nn, nw, N_new, node_key, node_deg.as<u64>(), first_out.as<u64>(), tail_map.as<u32>(),
-                                           Slots{nullptr, nullptr, 0, 0});
-                if (E && nn) hipLaunchKernelGGL(first_out_redo_kernel<true>, dim3(grid_for(E, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, src, dst,
-                                                orig.as<u32>(), E, N_new, tail_map.as<u32>(), node_deg.as<u64>(), first_out.as<u64>());
-                else if (E) hipLaunchKernelGGL(first_out_redo_kernel<false>, dim3(grid_for(E, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, src, dst,
-                                               orig.as<u32>(), E, N_new, (const u32*)nullptr, node_deg.as<u64>(), first_out.as<u64>());
-            }
-            KCHECK_HIP(hipGetLastError());
-            N = N_new;
-            KCHECK_HIP(hipStreamSynchronize(stream));      // the host vectors are reused by the next pass
-        }
-        lap("apply");
-        if (trace)
-            fprintf(stderr, "[prune] pass %llu: E %llu N %llu walks %llu dead %llu marked %llu removed %llu (dup %llu) nodes %llu | %.2f ms, host %.2f (edges %.2f nodes %.2f)\n",
-                    (unsigned long long)local.passes, (unsigned long long)E, (unsigned long long)N, (unsigned long long)h_tot[2],
-                    (unsigned long long)h_tot[1], (unsigned long long)h_tot[0], (unsigned long long)m,
-                    (unsigned long long)dups, (unsigned long long)n_node_moves, now_ms() - pass_t0, pass_host, t_edges, t_nodes);
+        return KATOME_OK;
     }
-    g.n_edges = E; g.n_nodes = N;
-    if (st) *st = local;
+
+    // (6) apply the moves, re-label the endpoints of the surviving edges
+    int apply(const EdgeMoves& em, const NodeMoves& nm, u64 n_old_inputs, bool track) {
+        if (em.n_moves) KLAUNCH(move_edges_kernel, em.n_moves, stream, to_e.as<u32>(), from_e.as<u32>(), em.n_moves, nw, src, dst, weight, orig.as<u32>(), key,
+                                first_out.as<u64>(), slots);
+        E = em.E_new;
+        nodes_moved = nm.n_moves != 0;
+        KCHECK(ensure(tail_map, (N - nm.N_new + 1) * 4, stream));
+        if (slots.out) KCHECK(apply_with_slots(nm, n_old_inputs, track));
+        else apply_streaming(nm);
+        KCHECK_HIP(hipGetLastError());
+        N = nm.N_new;
+        KCHECK_HIP(hipStreamSynchronize(stream));      // the host vectors are reused by the next pass
+        lap("apply");
+        return KATOME_OK;
+    }
+    // what changed, and nothing else: new first out-edges (edge positions are final, node ids still the old ones), then the vertices
+    // move, then the edges in a moved vertex's slots learn its new id
+    int apply_with_slots(const NodeMoves& nm, u64 n_old, bool track) {
+        const u64 nn = nm.n_moves, N_new = nm.N_new;
+        u64 h_cnt[3] = {0, 0, 0};
+        KCHECK_HIP(hipMemcpyAsync(h_cnt, totals.as<u64>() + 4, 24, hipMemcpyDeviceToHost, stream));
+        KCHECK_HIP(hipStreamSynchronize(stream));
+        const u64 n_changed = h_cnt[0], n_redo = h_cnt[1], n_fresh = h_cnt[2];
+        if (n_redo) KLAUNCH(redo_slots_kernel, n_redo, stream, redo_list.as<u32>(), n_redo, slots, orig.as<u32>(), dst, node_deg.as<u64>(), first_out.as<u64>());
+        if (nn) KLAUNCH(move_nodes_kernel, nn, stream, to_n.as<u32>(), from_n.as<u32>(), nn, nw, N_new, node_key, node_deg.as<u64>(), first_out.as<u64>(),
+                        tail_map.as<u32>(), slots);
+        if (nn) KLAUNCH(remap_slots_kernel, nn, stream, to_n.as<u32>(), nn, N_new, tail_map.as<u32>(), slots, src, dst, first_out.as<u64>(), node_deg.as<u64>());
+        // next pass's Input vertices from this pass's, without a look at every vertex
+        const u64 cand = n_old + n_fresh;
+        KCHECK(ensure(inputs_next, cand * 4 + 16, stream));
+        KCHECK_HIP(hipMemsetAsync(totals.as<u64>() + 7, 0, 8, stream));
+        if (cand) KLAUNCH(inputs_update_kernel, cand, stream, inputs.as<u32>(), n_old, fresh_inputs.as<u32>(), n_fresh, last_touch.as<u32>(), N_new,
+                          tail_map.as<u32>(), node_deg.as<u64>(), inputs_next.as<u32>(), totals.as<u64>() + 7, stamp.as<u32>(), next_stamp() + (STAMP_STEP - 1));
+        // which of them the next pass has to walk: everything, or what lies within reach of a change
+        walk_from = 0;
+        if (track) {
+            if (n_changed) KLAUNCH(affected_kernel, n_changed, stream, changed.as<u32>(), n_changed, N_new, tail_map.as<u32>(), slots, src, node_deg.as<u64>(),
+                                   stamp.as<u32>(), next_stamp() + (STAMP_STEP - 1), two_k);
+            walk_from = next_stamp();
+        }
+        KCHECK_HIP(hipGetLastError());
+        KCHECK_HIP(hipMemcpyAsync(&n_inputs, totals.as<u64>() + 7, 8, hipMemcpyDeviceToHost, stream));
+        KCHECK_HIP(hipStreamSynchronize(stream));
+        std::swap(inputs.p, inputs_next.p); std::swap(inputs.bytes, inputs_next.bytes);
+        have_inputs = true;
+        return KATOME_OK;
+    }
+    // without slots: the vertices move, then a pass over all edges re-labels endpoints and finds every first out-edge again
+    void apply_streaming(const NodeMoves& nm) {
+        const u64 nn = nm.n_moves, N_new = nm.N_new;
+        if (nn) KLAUNCH(move_nodes_kernel, nn, stream, to_n.as<u32>(), from_n.as<u32>(), nn, nw, N_new, node_key, node_deg.as<u64>(), first_out.as<u64>(),
+                        tail_map.as<u32>(), Slots{nullptr, nullptr, 0, 0});
+        if (E && nn) KLAUNCH(first_out_redo_kernel<true>, E, stream, src, dst, orig.as<u32>(), E, N_new, tail_map.as<u32>(), node_deg.as<u64>(), first_out.as<u64>());
+        else if (E) KLAUNCH(first_out_redo_kernel<false>, E, stream, src, dst, orig.as<u32>(), E, N_new, (const u32*)nullptr, node_deg.as<u64>(), first_out.as<u64>());
+    }
+
+    void trace_pass(double pass_t0, const u64 h_tot[5], const EdgeMoves& em, const NodeMoves& nm) const {
+        if (!trace) return;
+        fprintf(stderr, "[prune] pass %llu: E %llu N %llu walks %llu dead %llu marked %llu removed %llu (dup %llu) nodes %llu | %.2f ms, host %.2f (edges %.2f nodes %.2f)\n",
+                (unsigned long long)st.passes, (unsigned long long)E, (unsigned long long)N, (unsigned long long)h_tot[2],
+                (unsigned long long)h_tot[1], (unsigned long long)h_tot[0], (unsigned long long)em.m,
+                (unsigned long long)em.dups, (unsigned long long)nm.n_moves, now_ms() - pass_t0, em.host_ms + nm.host_ms, em.host_ms, nm.host_ms);
+    }
+};
+
+}  // namespace
+
+int dev_remove_dead_paths(PruneGraph& g, uint32_t k, katome_prune_stats* st, hipStream_t stream) {
+    if (g.n_edges >= 0xFFFFFFFFull || g.n_nodes >= 0xFFFFFFFFull) {
+        set_error("remove_dead_paths: more than 2^32 edges or nodes on one GPU");
+        return KATOME_E_UNSUPPORTED;
+    }
+    PruneRun r(g, k, stream);
+    KCHECK(r.build_adjacency());
+    while (r.E) {
+        const double pass_t0 = now_ms();
+        u64 h_tot[5], u = 0;
+        EdgeMoves em; NodeMoves nm;
+        bool track = false;
+        KCHECK(r.walk(h_tot));                                      // (1) walks
+        if (h_tot[0] == 0) break;                                   //     to_remove.is_empty() (pruner.rs:76)
+        KCHECK(r.marked_indices(&u));                               // (2) the marked indices
+        KCHECK(r.replay_edges_step(u, h_tot[0], &em));              // (3) replay of remove_edge
+        KCHECK(r.deaths(em.m, &track));                             // (4) the nodes each removal isolates
+        KCHECK(r.replay_nodes_step(em.m, &nm));                     // (5) replay of remove_node
+        KCHECK(r.apply(em, nm, h_tot[2], track));                   // (6) apply the moves
+        r.trace_pass(pass_t0, h_tot, em, nm);
+    }
+    g.n_edges = r.E; g.n_nodes = r.N;
+    if (st) *st = r.st;
     return KATOME_OK;
 }
 
@@ -1270,13 +1329,13 @@ static int retain_on_device(const u32* d_flag, u64 n, DevBuf& to, DevBuf& from, 
     for (int round = 0; round < 64; ++round) {
         KCHECK_HIP(hipMemsetAsync(changed.p, 0, 4, stream));
         for (int rep = 0; rep < 2; ++rep)
-            hipLaunchKernelGGL(retain_jump_kernel, dim3(grid_for(u, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, jump.as<u32>(), u, M, changed.as<u32>());
+            KLAUNCH(retain_jump_kernel, u, stream, jump.as<u32>(), u, M, changed.as<u32>());
         u32 h = 0;
         KCHECK_HIP(hipMemcpyAsync(&h, changed.p, 4, hipMemcpyDeviceToHost, stream));
         KCHECK_HIP(hipStreamSynchronize(stream));
         if (!h) break;
     }
-    if (holes) hipLaunchKernelGGL(retain_resolve_kernel, dim3(grid_for(holes, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, jump.as<u32>(), M, holes, from.as<u32>());
+    if (holes) KLAUNCH(retain_resolve_kernel, holes, stream, jump.as<u32>(), M, holes, from.as<u32>());
     KCHECK_HIP(hipGetLastError());
     *n_moves = holes;
     return KATOME_OK;
@@ -1303,24 +1362,23 @@ int dev_remove_weak_edges_ordered(PruneGraph& g, uint32_t threshold, hipStream_t
         KCHECK(dev_iota(orig.as<u32>(), E, stream));
     }
     // retain_edges(|e| weight >= threshold)
-    hipLaunchKernelGGL(weak_flag_kernel, dim3(grid_for(E, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, weight, E, threshold, flag.as<u32>());
+    KLAUNCH(weak_flag_kernel, E, stream, weight, E, threshold, flag.as<u32>());
     u64 n_moves = 0, E_new = E;
     KCHECK(retain_on_device(flag.as<u32>(), E, to, from, &n_moves, &E_new, stream));
-    if (n_moves)
-        hipLaunchKernelGGL(move_edges_kernel, dim3(grid_for(n_moves, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, to.as<u32>(),
-                           from.as<u32>(), n_moves, nw, src, dst, weight, orig.as<u32>(), key, (u64*)nullptr, Slots{nullptr, nullptr, 0, 0});
+    if (n_moves) KLAUNCH(move_edges_kernel, n_moves, stream, to.as<u32>(), from.as<u32>(), n_moves, nw, src, dst, weight, orig.as<u32>(), key, (u64*)nullptr,
+                         Slots{nullptr, nullptr, 0, 0});
     E = E_new;
     // retain_nodes(|n| has a neighbour)
-    hipLaunchKernelGGL(fill_u32_kernel, dim3(grid_for(N, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, flag.as<u32>(), N, 1u);
-    if (E) hipLaunchKernelGGL(touch_nodes_kernel, dim3(grid_for(E, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, src, dst, E, flag.as<u32>());
+    KLAUNCH(fill_u32_kernel, N, stream, flag.as<u32>(), N, 1u);
+    if (E) KLAUNCH(touch_nodes_kernel, E, stream, src, dst, E, flag.as<u32>());
     KCHECK_HIP(hipGetLastError());
     u64 nn = 0, N_new = N;
     KCHECK(retain_on_device(flag.as<u32>(), N, to, from, &nn, &N_new, stream));
     DevBuf tail_map(stream);
     KCHECK(tail_map.alloc((N - N_new + 1) * 4));
-    if (nn) hipLaunchKernelGGL(move_nodes_kernel, dim3(grid_for(nn, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, to.as<u32>(), from.as<u32>(),
-                               nn, nw, N_new, node_key, (u64*)nullptr, (u64*)nullptr, tail_map.as<u32>(), Slots{nullptr, nullptr, 0, 0});
-    if (E && nn) hipLaunchKernelGGL(remap_kernel, dim3(grid_for(E, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, src, dst, E, N_new, tail_map.as<u32>());
+    if (nn) KLAUNCH(move_nodes_kernel, nn, stream, to.as<u32>(), from.as<u32>(), nn, nw, N_new, node_key, (u64*)nullptr, (u64*)nullptr, tail_map.as<u32>(),
+                    Slots{nullptr, nullptr, 0, 0});
+    if (E && nn) KLAUNCH(remap_kernel, E, stream, src, dst, E, N_new, tail_map.as<u32>());
     KCHECK_HIP(hipGetLastError());
     KCHECK_HIP(hipStreamSynchronize(stream));
     g.n_edges = E; g.n_nodes = N_new;

@@ -135,6 +135,56 @@ def test_quirks_are_exercised(oracle):
     assert dup > 0 and passes > 2
 
 
+def test_trace_lines_of_a_run(oracle, monkeypatch, capfd):
+    """KATOME_TRACE_PRUNE is read by tools/make_stage_profiles.py: one `[prune] pass N:` line per pass that removes something
+    (the closing pass leaves before it prints), N = 1, 2, ..., and in front of each the laps `[prune]   <name>` in the order
+    of the stages, `adjacency` once before the first"""
+    import re
+    from katome_amd import device as kd
+    seed, k = 7, 5
+    L = k + 3 + seed % 7
+    reads = _random_reads(seed, 30 + 40 * seed, L, 60 + 50 * seed, 0.04)
+    packed = torch.from_numpy(pack_reads_ascii(reads).reshape(-1).copy()).cuda()
+    b = kd.Builder(k, True, first_seen_order=True)
+    span = b.tile_span(L)
+    if span > 1:
+        b.insert_tiles(b.extract_tiles(packed, len(reads), L, span), span)
+    else:
+        b.insert(b.extract_fixed(packed, len(reads), L))
+    b.finalize()
+    monkeypatch.setenv("KATOME_TRACE_PRUNE", "1")
+    capfd.readouterr()
+    dg, st = b.remove_dead_paths()
+    torch.cuda.synchronize()
+    err = capfd.readouterr().err
+    assert st["passes"] > 1
+    passes, laps = [], [[]]                 # laps[i]: the lap names in front of the i-th pass line (the last: behind them all)
+    for line in err.splitlines():
+        m = re.match(r"\[prune\] pass (\d+): E \d+ N \d+ walks \d+ dead \d+ marked \d+ removed \d+ \(dup \d+\) nodes \d+ \| "
+                     r"[0-9.]+ ms, host [0-9.]+ \(edges [0-9.]+ nodes [0-9.]+\)$", line)
+        if m:
+            passes.append(int(m.group(1)))
+            laps.append([])
+            continue
+        m = re.match(r"\[prune\]   (.{18}) +[0-9.]+ ms$", line)
+        if m:
+            laps[-1].append(m.group(1).rstrip())
+        else:
+            assert not line.startswith("[prune]"), line
+    assert passes == list(range(1, st["passes"]))
+    stages = ["walks", "replay edges", "replay nodes", "apply"]
+    assert laps[0] == ["adjacency"] + stages
+    assert all(l == stages for l in laps[1:-1])
+    assert laps[-1] == ["walks"]            # the closing pass walks, finds nothing and leaves
+    ref = oracle.build_ascii(reads, k, True, remove_dead_paths=True)
+    assert (dg.n_nodes, dg.n_edges) == (ref.n_nodes, ref.n_edges)
+    assert np.array_equal(dg.edge_label.cpu().numpy(), ref.edge_label)
+    assert np.array_equal(dg.edge_weight.cpu().numpy().view(np.uint32), ref.edge_weight)
+    assert np.array_equal(dg.edge_src.cpu().numpy().view(np.uint64), ref.edge_src)
+    assert np.array_equal(dg.edge_dst.cpu().numpy().view(np.uint64), ref.edge_dst)
+    b.close()
+
+
 @pytest.mark.parametrize("k,rc,n,L,glen", [(31, True, 30000, 100, 100000), (21, False, 40000, 80, 100000),
                                            (40, True, 20000, 103, 50000)])
 def test_synthetic_workload_against_oracle(oracle, k, rc, n, L, glen):
