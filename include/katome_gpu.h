@@ -653,7 +653,8 @@ int katome_dev_collapse_gfa(katome_builder *b, katome_dev_gfa_paths *out, void *
  * n_edges and twin(twin(i)) != i.  Scratch beyond katome_dev_contigs_gfa_strands' and katome_dev_collapse_gfa's: 4 bytes per piece
  * (the oriented names) and about 50 bytes per path while the mirrors are found.  Profile phase
  * "gfa_strand_paths", kernel "k:gfa_strand_paths_write_kernel".  Synchronises.
- * Out of scope: the coverage form of merged S lines, folding mirror paths out of the text, and anything on the sharded graph.   */
+ * Out of scope: the coverage form of merged S lines, folding mirror paths out of the text (katome_dev_collapse_unique below
+ * selects one strand per molecule by CONTIG, and its kept names select their P lines), and anything on the sharded graph.   */
 typedef struct {
     uint64_t  n_segments, n_links, text_bytes, n_unpaired, n_self_twins;
     uint8_t  *d_text;
@@ -675,6 +676,56 @@ typedef struct {
  * katome_dev_collapse_gfa_strands or destroy: the results of katome_dev_collapse, katome_dev_collapse_gfa, katome_dev_contigs_gfa
  * and katome_dev_contigs_gfa_strands stay valid, and the builder's graph is untouched.                                      */
 int katome_dev_collapse_gfa_strands(katome_builder *b, katome_dev_gfa_strand_paths *out, void *stream);
+
+/* ---- the STRAND-UNIQUE assembly (csrc/unique_contigs.hip): one FASTA record per molecule, on the device ----------------------------
+ * A reverse_complement build keeps a k-mer and its reverse complement as two edges and collapse walks both strands, so the FASTA of
+ * katome_dev_collapse holds nearly every molecule twice, once per strand.  For the builder's last katome_dev_collapse this gives
+ * every contig's mirror, the kept set -- one strand per molecule, with all copies of that strand -- and the text of the kept contigs.
+ *   Contig.  Contig c is the pieces from the c-th piece that has KATOME_PIECE_WHOLE up to the next such piece.  Its ids are
+ *     a_0 .. a_{n-1}, each piece & ~KATOME_PIECE_WHOLE.  Runs and jumps (katome_dev_collapse_gfa) play no part: a contig with a seam
+ *     is still one sequence of ids.
+ *   Mirror.  mirror(c) is the smallest q with n_q == n and id_q[t] == twin(a_{n-1-t}) for every t.  twin is
+ *     katome_dev_contigs_gfa_strands', verified base for base.  A contig that has an edge without a twin has no mirror (all ones).
+ *     mirror(c) == c is a self-mirror.
+ *   First copy.  first(c) = mirror(mirror(c)) where a mirror exists.  Because twin is an involution, this is the smallest contig
+ *     with c's own piece sequence.  It costs two gathers and no second search.
+ *   Kept.  Contig c is kept iff mirror(c) is none or mirror(mirror(c)) <= mirror(c).  Of a molecule's two strands, the one whose
+ *     first copy comes first in the FASTA is kept, with all its copies.  Every copy of the other strand is dropped.  Contigs without
+ *     a mirror and self-mirrors are all kept.  n_kept >= 1 whenever there is a contig.
+ *   Text.  The kept contigs follow in ascending c.  KATOME_TEXT_PLAIN: their bases back to back.  KATOME_TEXT_FASTA:
+ *     ">katome_<c>\n<bases>\n" with the ORIGINAL number c.  The result is byte for byte the concatenation of the kept records of
+ *     katome_dev_collapse's FASTA.  Numbers have gaps.  A record is then the P lines katome_<c>, katome_<c>.1 ... of the assembly's
+ *     GFA files, and the same record in the full FASTA.
+ *   Sequence agreement.  Where c and mirror(c) are both single-run contigs, their texts are reverse complements of each other.
+ *     Lengths agree for every mirrored pair.  At a seam the texts need not agree, so the definition goes by pieces and not by bases.
+ * (The per-PATH rule of katome_dev_collapse_gfa_strands' d_path_mirror, mirror(j) >= j, keeps an irregular subset of a strand's
+ * copies; this is the rule that keeps them all.)
+ * d_contig_mirror[c] = mirror(c); n_mirrored = the contigs that have one, n_self_mirror = those that are their own.  d_kept_name
+ * ascends; d_kept_off[i] / d_kept_len[i] = the first base in d_text and the bases of kept contig i.  d_text holds text_bytes bytes;
+ * the buffer is a multiple of 16 bytes, with zeros behind the text up to it.
+ * Scratch: 20 bytes per piece for the plan of the checks, 12 per piece and 12 per contig for the selection,
+ * about 50 bytes per contig while the mirrors are found, then 4 + 16 bytes per kept piece for the compacted list and its text plan.
+ * Profile phase "unique_contigs", kernels "k:text_write_named_kernel" and "k:unique_contigs selection"; the mirror search reports
+ * to katome_dev_collapse_gfa_strands' "k:mirror_*" entries.
+ * Out of scope: a GFA with the dropped contigs' P lines folded out (the kept names already select them), coverage on merged S lines,
+ * anything on the sharded graph, and deduplicating by base sequence, such as contained or overlapping contigs.               */
+typedef struct {
+    uint64_t  n_contigs, n_mirrored, n_self_mirror;
+    uint64_t *d_contig_mirror;           /* [n_contigs], all ones: none                                                */
+    uint64_t  n_kept, text_bytes;
+    uint32_t  layout, _pad;
+    uint64_t *d_kept_name;               /* [n_kept], ascending: the contigs' numbers in katome_dev_collapse's result  */
+    uint64_t *d_kept_off;                /* [n_kept]                                                                   */
+    uint32_t *d_kept_len;                /* [n_kept]                                                                   */
+    uint8_t  *d_text;
+} katome_dev_unique_assembly;
+/* for the builder's LAST katome_dev_collapse, whatever layout that collapse used.  No collapse result: KATOME_E_ARG,
+ * "collapse_unique: no collapse result".  No contigs: all zero, KATOME_OK.  The twins are computed here (candidates, pairing,
+ * base-for-base verification, after the segments' validation), without katome_dev_contigs_gfa_strands' link join, link sort or
+ * line sizes.  The result has its own buffers, owned by the builder until its next katome_dev_collapse_unique or destroy: the
+ * results of katome_dev_collapse, katome_dev_collapse_gfa, katome_dev_collapse_gfa_strands, katome_dev_contigs_gfa and
+ * katome_dev_contigs_gfa_strands stay valid, and the builder's graph is untouched.  Synchronises.                           */
+int katome_dev_collapse_unique(katome_builder *b, uint32_t layout, katome_dev_unique_assembly *out, void *stream);
 
 /* Contigs::stats (stats/contigs.rs:31-89) from the contigs' lengths: host, pure.  No contigs: all zeros.  A tipping point of 0
  * with contigs present (sum / 2, (0.1 * sum) truncated, original_genome_length / 2), where the reference panics on
@@ -709,6 +760,36 @@ int  katome_assemble_packed(const katome_settings *s, const uint8_t *packed, uin
 /* Contigs::save_to_file (asm/mod.rs:57-72): KATOME_E_OPEN when the path cannot be created */
 int  katome_assembly_save(const katome_assembly *a, const char *path);
 void katome_assembly_free(katome_assembly *a);
+
+/* katome_assemble_* followed by katome_dev_collapse_unique(KATOME_TEXT_FASTA), which has the definitions: one build, the stages, one
+ * collapse, then the strand-unique form of its contigs in host memory.  text[0, text_bytes) is the file of the kept records, kept
+ * contig i (numbered kept_name[i] in the full FASTA) its bytes [kept_off[i], kept_off[i] + kept_len[i]); stats:
+ * katome_contig_stats_of over the kept lengths (a tipping point of 0: KATOME_E_ARG, as in katome_assemble_*).  fasta_path (all
+ * contigs) and unique_path (the kept ones) are written when given; asm_out and unique_out are filled when given; all four NULL:
+ * KATOME_E_ARG.  Statuses are katome_assemble_gfa_*'s: KATOME_FLAG_FIRST_SEEN_ORDER is needed; a file that cannot be created gives
+ * KATOME_E_OPEN, "couldn't create <path>: <why>", with both results still handed back -- the FASTA path is tried first, the first
+ * failure is the one reported, and the other file is still written; settings.n_devices > 1 is built sharded and gathered to the first
+ * GPU.  Owned by the library until katome_unique_assembly_free.                                                              */
+typedef struct {
+    uint64_t n_contigs, n_kept, text_bytes, read_bytes;
+    uint32_t k, _pad;
+    uint64_t n_mirrored, n_self_mirror;
+    const uint64_t *contig_mirror;       /* [n_contigs], all ones: none                                                */
+    const uint64_t *kept_name;           /* [n_kept], ascending                                                        */
+    const uint64_t *kept_off;            /* [n_kept]                                                                   */
+    const uint32_t *kept_len;            /* [n_kept]                                                                   */
+    const uint8_t  *text;
+    katome_contig_stats stats;
+} katome_unique_assembly;
+int  katome_assemble_unique_files(const katome_settings *s, const char *const *paths, size_t n_paths, uint64_t original_genome_length,
+                                  const char *fasta_path /* nullable */, const char *unique_path /* nullable */,
+                                  katome_assembly **asm_out /* nullable */, katome_unique_assembly **unique_out /* nullable */);
+int  katome_assemble_unique_packed(const katome_settings *s, const uint8_t *packed, uint64_t n_reads, uint32_t read_len,
+                                   const uint8_t *skip, uint64_t original_genome_length, const char *fasta_path /* nullable */,
+                                   const char *unique_path /* nullable */, katome_assembly **asm_out /* nullable */,
+                                   katome_unique_assembly **unique_out /* nullable */);
+int  katome_unique_assembly_save(const katome_unique_assembly *u, const char *path);
+void katome_unique_assembly_free(katome_unique_assembly *u);
 
 /* The unitig graph of a read set as GFA 1 in host memory: the build, the stage letters as the staged entries take them (d, c, w,
  * e; they need KATOME_FLAG_FIRST_SEEN_ORDER, an empty string works on a by-key build), katome_dev_shrink (AUTO) and
@@ -1231,7 +1312,7 @@ int katome_dev_labels(int device, const uint64_t *d_edge_key, uint64_t n, uint32
  * whose size is a multiple of 4 (KATOME_E_ARG for a misaligned pointer): the kernel reads the aligned 32-bit words that hold the
  * bytes it needs, so up to 3 bytes on either side of a label inside those words are read and ignored.  A piece that names no label, a label shorter than k bases
  * or malformed offsets: KATOME_E_ARG, before anything is read through them.  n_pieces >= 2^31 or a contig of 2^32 bases or more:
- * KATOME_E_UNSUPPORTED.  Synchronises. */
+ * KATOME_E_UNSUPPORTED.  KATOME_TEXT_TRACE=1 in the environment: the writing kernel's time on stderr.  Synchronises. */
 int katome_dev_pieces_text(int device, uint32_t k, const uint8_t *d_label, const uint64_t *d_label_off, uint64_t n_labels,
                            const uint32_t *d_pieces, uint64_t n_pieces, uint32_t layout, uint64_t *d_contig_off,
                            uint32_t *d_contig_len, uint64_t contig_cap, uint8_t *d_text, uint64_t text_cap, uint64_t *n_contigs,
@@ -1298,6 +1379,22 @@ int katome_dev_gfa_strand_paths_arrays(int device, uint64_t n_edges, const uint6
                                        uint64_t *d_path_line_off /* [n_paths + 1] */, uint64_t *d_path_contig /* [n_paths] */,
                                        uint64_t *d_path_first_piece /* [n_paths + 1] */, uint64_t *d_path_mirror /* [n_paths] */,
                                        uint64_t path_cap, uint8_t *d_text, uint64_t text_cap, uint64_t *counts /* [5] */, void *stream);
+/* katome_dev_collapse_unique on the caller's arrays: the labels and offsets of katome_dev_pieces_text (d_label aligned as there), a
+ * twin map of n_labels entries as katome_dev_gfa_strand_paths_arrays takes it (all ones: none) and checked by the same rules, the
+ * pieces (not NULL when n_pieces > 0) and the layout.  counts[5] = {n_contigs, n_kept, text_bytes, n_mirrored, n_self_mirror} are
+ * always set (zeros on an error); d_text NULL: nothing else is written (a size query).  Otherwise d_contig_mirror needs room for
+ * contig_cap >= n_contigs entries, d_kept_name / d_kept_off / d_kept_len for kept_cap >= n_kept, and d_text, 16-byte aligned, for
+ * text_cap >= text_bytes rounded up to 16 (zeros behind the text up to that multiple): KATOME_E_ARG when one is too small.
+ * Validated on the device before anything is read through a value, each KATOME_E_ARG with its message: the twin map (an entry that
+ * is neither all ones nor below n_labels, twin(twin(i)) != i), then the pieces and labels as for katome_dev_pieces_text.  2^31
+ * pieces or more, or 2^32 - 1 labels or more: KATOME_E_UNSUPPORTED.  KATOME_UNIQUE_TRACE=1 in the environment: the times of the
+ * named writer, the selection and the mirror search's parts on stderr.  Synchronises. */
+int katome_dev_unique_contigs_arrays(int device, uint32_t k, const uint8_t *d_label, const uint64_t *d_label_off, uint64_t n_labels,
+                                     const uint64_t *d_edge_twin, const uint32_t *d_pieces, uint64_t n_pieces, uint32_t layout,
+                                     uint64_t *d_contig_mirror /* [n_contigs] */, uint64_t contig_cap,
+                                     uint64_t *d_kept_name /* [n_kept] */, uint64_t *d_kept_off /* [n_kept] */,
+                                     uint32_t *d_kept_len /* [n_kept] */, uint64_t kept_cap, uint8_t *d_text, uint64_t text_cap,
+                                     uint64_t *counts /* [5] */, void *stream);
 /* the GFA writer on a numbered PART of a text whose other parts are written elsewhere (katome_dist_contigs_gfa): segment i is named
  * first_segment + i (up to 20 digits), its links are d_link_b[d_link_first[i] .. d_link_first[i + 1]) -- global numbers, n_links =
  * d_link_first[n_edges] --, the header line is written or not.  d_text holds the S part (the header first) at 0 and the L part

@@ -130,6 +130,19 @@ class DevGfaStrandPaths(C.Structure):
                 ("n_edges", C.c_uint64)]
 
 
+class DevUniqueAssembly(C.Structure):
+    _fields_ = [("n_contigs", C.c_uint64), ("n_mirrored", C.c_uint64), ("n_self_mirror", C.c_uint64), ("d_contig_mirror", C.c_void_p),
+                ("n_kept", C.c_uint64), ("text_bytes", C.c_uint64), ("layout", C.c_uint32), ("_pad", C.c_uint32),
+                ("d_kept_name", C.c_void_p), ("d_kept_off", C.c_void_p), ("d_kept_len", C.c_void_p), ("d_text", C.c_void_p)]
+
+
+class UniqueAssembly(C.Structure):
+    _fields_ = [("n_contigs", C.c_uint64), ("n_kept", C.c_uint64), ("text_bytes", C.c_uint64), ("read_bytes", C.c_uint64),
+                ("k", C.c_uint32), ("_pad", C.c_uint32), ("n_mirrored", C.c_uint64), ("n_self_mirror", C.c_uint64),
+                ("contig_mirror", u64p), ("kept_name", u64p), ("kept_off", u64p), ("kept_len", C.POINTER(C.c_uint32)), ("text", u8p),
+                ("stats", ContigStats)]
+
+
 class GfaStrandPaths(C.Structure):
     _fields_ = [("n_segments", C.c_uint64), ("n_links", C.c_uint64), ("text_bytes", C.c_uint64), ("read_bytes", C.c_uint64),
                 ("k", C.c_uint32), ("_pad", C.c_uint32), ("text", u8p), ("segment_off", u64p), ("link_first", u64p),
@@ -296,6 +309,14 @@ SYMBOLS = {
     "katome_gfa_paths_free": (None, [C.POINTER(GfaPaths)]),
     "katome_dev_collapse_gfa_strands": (_i, [_vp, C.POINTER(DevGfaStrandPaths), _vp]),
     "katome_dev_gfa_strand_paths_arrays": (_i, [_i, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _u64, u64p, _vp]),
+    "katome_dev_collapse_unique": (_i, [_vp, _u32, C.POINTER(DevUniqueAssembly), _vp]),
+    "katome_dev_unique_contigs_arrays": (_i, [_i, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64, u64p, _vp]),
+    "katome_assemble_unique_files": (_i, [C.POINTER(Settings), _pp, _sz, _u64, C.c_char_p, C.c_char_p, C.POINTER(C.POINTER(Assembly)),
+                                     C.POINTER(C.POINTER(UniqueAssembly))]),
+    "katome_assemble_unique_packed": (_i, [C.POINTER(Settings), _vp, _u64, _u32, _vp, _u64, C.c_char_p, C.c_char_p,
+                                      C.POINTER(C.POINTER(Assembly)), C.POINTER(C.POINTER(UniqueAssembly))]),
+    "katome_unique_assembly_save": (_i, [C.POINTER(UniqueAssembly), C.c_char_p]),
+    "katome_unique_assembly_free": (None, [C.POINTER(UniqueAssembly)]),
     "katome_assemble_gfa_strands_files": (_i, [C.POINTER(Settings), _pp, _sz, _u64, C.c_char_p, C.c_char_p, C.POINTER(C.POINTER(Assembly)),
                                           C.POINTER(C.POINTER(GfaStrandPaths))]),
     "katome_assemble_gfa_strands_packed": (_i, [C.POINTER(Settings), _vp, _u64, _u32, _vp, _u64, C.c_char_p, C.c_char_p,

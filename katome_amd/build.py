@@ -276,6 +276,38 @@ class GfaStrandPaths(GfaPaths):
             pass
 
 
+class UniqueAssembly:
+    """the strand-unique half of GpuGraph.assemble_unique (include/katome_gpu.h, katome_dev_collapse_unique, has the definitions):
+    contigs -- the kept ones, one strand per molecule with all its copies, as strings --, names -- their numbers in the full
+    assembly, ascending --, contig_mirror[c] -- the smallest contig that spells c's molecule from its other end by pieces (2^64 - 1:
+    none; n_mirrored have one, n_self_mirror are their own) --, stats -- Contigs::stats of the kept contigs -- and fasta, the kept
+    records of the full FASTA byte for byte.  Keeps the C result until it is collected."""
+
+    def __init__(self, up):
+        self._up = up
+        u = up.contents
+        nk, nb = u.n_kept, u.text_bytes
+        self.k, self.read_bytes, self.n_contigs, self.n_kept = u.k, u.read_bytes, u.n_contigs, nk
+        self.n_mirrored, self.n_self_mirror = u.n_mirrored, u.n_self_mirror
+        self.fasta = bytes(np.ctypeslib.as_array(u.text, (nb,))) if nb else b""
+        self.contig_mirror = np.ctypeslib.as_array(u.contig_mirror, (u.n_contigs,)).copy() if u.n_contigs else np.zeros(0, np.uint64)
+        self.names = np.ctypeslib.as_array(u.kept_name, (nk,)).tolist() if nk else []
+        off = np.ctypeslib.as_array(u.kept_off, (nk,)).tolist() if nk else []
+        length = np.ctypeslib.as_array(u.kept_len, (nk,)).tolist() if nk else []
+        self.contigs = [self.fasta[o:o + n].decode() for o, n in zip(off, length)]
+        self.stats = ContigsStats(u.stats.n50, u.stats.l50, u.stats.n90, u.stats.ng50)
+
+    def save_to_file(self, path):
+        """the kept records as a FASTA file (katome_unique_assembly_save): a path that cannot be created raises KatomePanic(E_OPEN)"""
+        _check(_lib.lib().katome_unique_assembly_save(self._up, os.fsencode(path)))
+
+    def __del__(self):
+        try:
+            _lib.lib().katome_unique_assembly_free(self._up)
+        except Exception:       # interpreter shutdown
+            pass
+
+
 def _assemble_gfa_result(rc, ap, gp, cls=GfaPaths):
     """-> (Assembly, GfaPaths); a path that could not be created: both were made all the same, and travel with the exception (`.result`)"""
     result = (Assembly(ap) if ap else None, cls(gp) if gp else None)
@@ -516,6 +548,39 @@ class GpuGraph:
         rc = _lib.lib().katome_assemble_gfa_packed(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, original_genome_length,
                                                    enc(fasta_file), enc(gfa_file), C.byref(ap), C.byref(gp))
         return _assemble_gfa_result(rc, ap, gp)
+
+    # ---- the assembly and its strand-unique form: one FASTA record per molecule --------------------------
+    @staticmethod
+    def assemble_unique(input_files, ft, reverse_complement, minimal_weight_threshold, original_genome_length, fasta_file=None, unique_file=None,
+                        device=0, n_devices=1, ranks_share_device=False):
+        """assemble() and, from the same collapse, its strand-unique form: of every molecule's two strands the one whose first copy
+        comes first, with all its copies, under the contigs' original numbers (katome_assemble_unique_files) -> (Assembly,
+        UniqueAssembly); fasta_file: all contigs, unique_file: the kept ones; uses the global k"""
+        s = make_settings(K_SIZE, ft, reverse_complement, minimal_weight_threshold, device, first_seen_order=True, n_devices=n_devices,
+                          ranks_share_device=ranks_share_device)
+        enc = lambda f: os.fsencode(f) if f is not None else None
+        ap, up = C.POINTER(_lib.Assembly)(), C.POINTER(_lib.UniqueAssembly)()
+        rc = _lib.lib().katome_assemble_unique_files(C.byref(s), _paths(input_files), len(input_files), original_genome_length, enc(fasta_file),
+                                                     enc(unique_file), C.byref(ap), C.byref(up))
+        return _assemble_gfa_result(rc, ap, up, UniqueAssembly)
+
+    @staticmethod
+    def assemble_unique_from_packed(packed, n_reads, read_len, skip=None, reverse_complement=False, minimal_weight_threshold=0,
+                                    original_genome_length=0, fasta_file=None, unique_file=None, device=0, k=None, n_devices=1,
+                                    ranks_share_device=False):
+        """the same from 2-bit packed reads (numpy uint8; katome_assemble_unique_packed)"""
+        s = make_settings(K_SIZE if k is None else k, InputFileType.Fastq, reverse_complement, minimal_weight_threshold, device,
+                          first_seen_order=True, n_devices=n_devices, ranks_share_device=ranks_share_device)
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        skip_p = None
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.uint8)
+            skip_p = skip.ctypes.data
+        enc = lambda f: os.fsencode(f) if f is not None else None
+        ap, up = C.POINTER(_lib.Assembly)(), C.POINTER(_lib.UniqueAssembly)()
+        rc = _lib.lib().katome_assemble_unique_packed(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, original_genome_length,
+                                                      enc(fasta_file), enc(unique_file), C.byref(ap), C.byref(up))
+        return _assemble_gfa_result(rc, ap, up, UniqueAssembly)
 
     # ---- the unitig graph as GFA 1 ---------------------------------------------------------------
     @staticmethod

@@ -909,17 +909,23 @@ int katome_dev_pieces_text_numbered(int device, uint32_t k, const uint8_t* d_lab
     hipStream_t stream = (hipStream_t)stream_;
     if ((uintptr_t)d_label & 3) { set_error("text: d_label must be 4-byte aligned (the kernel reads the aligned words around the bytes it needs)"); return KATOME_E_ARG; }
     if (!d_pieces && n_pieces && n_pieces != n_labels) { set_error("text: without pieces there is one per label"); return KATOME_E_ARG; }
+    // KATOME_TEXT_TRACE=1: the writing kernel's time on stderr (there is no builder whose profile could hold it; tools/bench_unique.py)
+    ArraysTrace trace("KATOME_TEXT_TRACE", "katome_dev_pieces_text");
     TextPlan plan;
-    KCHECK(dev_text_plan(k, d_label, d_label_off, n_labels, d_pieces, n_pieces, layout, first_contig, plan, stream));
-    *n_contigs = plan.n_contigs; *text_bytes = plan.text_bytes;
-    if (!d_text || plan.text_bytes == 0) return KATOME_OK;
-    if (!d_contig_off || !d_contig_len || contig_cap < plan.n_contigs || text_cap < (plan.text_bytes + 15) / 16 * 16 || ((uintptr_t)d_text & 15)) {
-        set_error("text: %llu contigs and %llu bytes (rounded up to 16, 16-byte aligned) do not fit the caller's arrays", (unsigned long long)plan.n_contigs,
-                  (unsigned long long)plan.text_bytes);
-        return KATOME_E_ARG;
+    {
+        PhaseScope ps(trace.prof, PH_COLLAPSE, stream);
+        KCHECK(dev_text_plan(k, d_label, d_label_off, n_labels, d_pieces, n_pieces, layout, first_contig, plan, stream));
+        *n_contigs = plan.n_contigs; *text_bytes = plan.text_bytes;
+        if (!d_text || plan.text_bytes == 0) return KATOME_OK;
+        if (!d_contig_off || !d_contig_len || contig_cap < plan.n_contigs || text_cap < (plan.text_bytes + 15) / 16 * 16 || ((uintptr_t)d_text & 15)) {
+            set_error("text: %llu contigs and %llu bytes (rounded up to 16, 16-byte aligned) do not fit the caller's arrays", (unsigned long long)plan.n_contigs,
+                      (unsigned long long)plan.text_bytes);
+            return KATOME_E_ARG;
+        }
+        KCHECK(dev_text_write(k, d_label, d_label_off, d_pieces, n_pieces, layout, first_contig, plan, d_contig_off, d_contig_len, d_text, stream));
     }
-    KCHECK(dev_text_write(k, d_label, d_label_off, d_pieces, n_pieces, layout, first_contig, plan, d_contig_off, d_contig_len, d_text, stream));
     KCHECK_HIP(hipStreamSynchronize(stream));
+    trace.print(K_TEXT_WRITE, K_TEXT_WRITE, plan.text_bytes, n_pieces, "pieces", plan.n_contigs, "contigs");
     return KATOME_OK;
 }
 

@@ -118,6 +118,7 @@ struct katome_builder {
     bool collapse_valid = false;       // the three above belong to one successful katome_dev_collapse
     GfaPathsOutput gfa_paths;          // result of katome_dev_collapse_gfa (its own buffers)
     GfaStrandPathsOutput gfa_strand_paths;      // result of katome_dev_collapse_gfa_strands (its own buffers)
+    UniqueOutput unique;               // result of katome_dev_collapse_unique (its own buffers)
     TextOutput unitig_text;            // result of katome_dev_contigs_text
     GfaOutput gfa;                     // result of katome_dev_contigs_gfa
     GfaStrandsOutput gfa_strands;      // result of katome_dev_contigs_gfa_strands (its own buffers: neither call touches the other's result)
@@ -170,7 +171,7 @@ KATOME_INTERNAL bool tile_recs_shape(uint32_t nwt, uint32_t nw, bool first_seen)
 KATOME_INTERNAL bool sorted_fail(const char* level);     // KATOME_SORTED_FAIL (tests)
 KATOME_INTERNAL bool seen_var_sorted();              // KATOME_SEEN_VAR_SORTED
 
-// ---- what the GFA entry points (gfa.hip, gfa_strands.hip, gfa_paths.hip, gfa_strand_paths.hip) share -----------------------------
+// ---- what the GFA entry points (gfa.hip, gfa_strands.hip, gfa_paths.hip, gfa_strand_paths.hip, unique_contigs.hip) share -----------------------------
 inline GfaGraph gfa_graph_of(uint32_t k, const ShrinkOutput& sh) {
     return GfaGraph{k, sh.n_nodes, sh.n_edges, sh.edge_src.as<u64>(), sh.edge_dst.as<u64>(), sh.edge_weight.as<u32>(), sh.edge_kmers.as<u32>(),
                     sh.edge_label_off.as<u64>(), sh.edge_label.as<uint8_t>(), sh.label_bytes};

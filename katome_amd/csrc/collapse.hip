@@ -13,6 +13,10 @@
 // A FASTA header carries first_contig + the contig's index (u64, up to 20 digits): the text may be one rank's part of a larger one
 // (dist_text.hip).  Its digits are counted once, when the pieces are measured; the writing kernel takes a header's length from the
 // scanned sizes, so the 16-bases path does no digit arithmetic.
+// The *_named kernels are the same three kernels for a text whose record i keeps the number it has in another text, name[i]
+// (unique_contigs.hip): one more indexed read where a header's number is needed, over the same device functions.  They are kernels
+// of their own, written out: with the number's source as a template argument of shared bodies the compiler did not leave the counted
+// kernels instruction for instruction what they were.
 #include <algorithm>
 #include <chrono>
 #include <new>
@@ -67,6 +71,32 @@ __global__ __launch_bounds__(BLOCK) void piece_measure_kernel(u32 k, const uint8
     }
 }
 
+// ... with contig c's header numbered name[c].  Pieces and labels have been checked by a piece_measure_kernel over the list these
+// pieces were taken from, and are checked again all the same
+__global__ __launch_bounds__(BLOCK) void piece_measure_named_kernel(u32 k, const uint8_t* __restrict__ label, const u64* __restrict__ label_off, u64 n_labels,
+                                                                    const u32* __restrict__ pieces, u64 P, u32 fasta, const u64* __restrict__ name,
+                                                                    const u64* __restrict__ contig_idx, u32* __restrict__ size, u32* __restrict__ err) {
+    const u64 label_bytes = label_off[n_labels];
+    for (u64 p = (u64)blockIdx.x * BLOCK + threadIdx.x; p < P; p += (u64)gridDim.x * BLOCK) {
+        const u32 w = piece_word(pieces, (u32)p), id = w & ~WHOLE;
+        const bool whole = w >> 31;
+        size[p] = 0;
+        if (p == 0 && !whole) { atomicOr(err, (u32)ERR_FIRST); continue; }
+        if (id >= n_labels) { atomicOr(err, (u32)ERR_PIECE); continue; }
+        const u64 lo = label_off[id], hi = label_off[id + 1];
+        if (lo >= hi || hi > label_bytes || hi - lo < 2) { atomicOr(err, (u32)ERR_LABEL); continue; }
+        if (hi - lo - 1 > MAX_LABEL_BYTES) { atomicOr(err, (u32)ERR_LABEL_LEN); continue; }
+        const u32 pad = label[lo], packed = 4 * (u32)(hi - lo - 1);
+        if (pad > 3 || packed < pad + k) { atomicOr(err, (u32)ERR_LABEL); continue; }
+        u32 n = packed - pad - (whole ? 0 : k - 1);
+        if (fasta) {
+            if (whole) n += header_bytes(1, name[contig_idx[p]]);
+            if (p + 1 == P || piece_word(pieces, (u32)(p + 1)) >> 31) n += 1;
+        }
+        size[p] = n;
+    }
+}
+
 // contig i's first base and its length in bases, from the pieces' offsets: the first piece of a contig writes the offset, the last
 // one (a launch later) the length
 __global__ __launch_bounds__(BLOCK) void contig_bounds_kernel(const u32* __restrict__ pieces, u64 P, u32 fasta, u64 first_contig,
@@ -75,6 +105,20 @@ __global__ __launch_bounds__(BLOCK) void contig_bounds_kernel(const u32* __restr
     for (u64 p = (u64)blockIdx.x * BLOCK + threadIdx.x; p < P; p += (u64)gridDim.x * BLOCK) {
         if (!lengths) {
             if (piece_word(pieces, (u32)p) >> 31) { const u64 c = contig_idx[p]; contig_off[c] = piece_off[p] + header_bytes(fasta, first_contig + c); }
+        } else if (p + 1 == P || piece_word(pieces, (u32)(p + 1)) >> 31) {
+            const u64 c = contig_idx[p + 1] - 1, len = piece_off[p + 1] - (fasta ? 1 : 0) - contig_off[c];
+            if (len > 0xFFFFFFFFull) atomicOr(err, (u32)ERR_CONTIG_LEN);
+            contig_len[c] = (u32)len;
+        }
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void contig_bounds_named_kernel(const u32* __restrict__ pieces, u64 P, u32 fasta, const u64* __restrict__ name,
+                                                                    const u64* __restrict__ contig_idx, const u64* __restrict__ piece_off, int lengths,
+                                                                    u64* __restrict__ contig_off, u32* __restrict__ contig_len, u32* __restrict__ err) {
+    for (u64 p = (u64)blockIdx.x * BLOCK + threadIdx.x; p < P; p += (u64)gridDim.x * BLOCK) {
+        if (!lengths) {
+            if (piece_word(pieces, (u32)p) >> 31) { const u64 c = contig_idx[p]; contig_off[c] = piece_off[p] + header_bytes(fasta, name[c]); }
         } else if (p + 1 == P || piece_word(pieces, (u32)(p + 1)) >> 31) {
             const u64 c = contig_idx[p + 1] - 1, len = piece_off[p + 1] - (fasta ? 1 : 0) - contig_off[c];
             if (len > 0xFFFFFFFFull) atomicOr(err, (u32)ERR_CONTIG_LEN);
@@ -165,6 +209,59 @@ __global__ __launch_bounds__(BLOCK) void text_write_kernel(u32 k, const uint8_t*
     }
 }
 
+// piece p of a text whose record i is numbered name[i]: load_piece numbering from 0 gives the record's index, which the name replaces
+__device__ __forceinline__ Piece load_named_piece(u32 p, u32 P, u32 k, const uint8_t* __restrict__ label, const u64* __restrict__ label_off,
+                                                  const u32* __restrict__ pieces, u32 fasta, const u64* __restrict__ name, const u64* __restrict__ contig_idx,
+                                                  const u64* __restrict__ piece_off) {
+    Piece pc = load_piece(p, P, k, label, label_off, pieces, fasta, 0, contig_idx, piece_off);
+    if (pc.head) pc.contig = name[pc.contig];
+    return pc;
+}
+// text_write_kernel with that one more indexed read on a record's first piece
+__global__ __launch_bounds__(BLOCK) void text_write_named_kernel(u32 k, const uint8_t* __restrict__ label, const u64* __restrict__ label_off,
+                                                                 const u32* __restrict__ pieces, u32 P, u32 fasta, const u64* __restrict__ name,
+                                                                 const u64* __restrict__ contig_idx, const u64* __restrict__ piece_off, u64 total,
+                                                                 uint8_t* __restrict__ text) {
+    __shared__ uint16_t s_off[TILE];
+    const u32 tid = threadIdx.x;
+    const u64 n_tiles = (total + TILE - 1) / TILE;
+    for (u64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const u64 base = tile * TILE, last = min(base + TILE, total) - 1;
+        const u32 p_lo = workgroup_search(piece_off, P, base), p_hi = workgroup_search(piece_off, P, last);
+        const u32 n_in = min(p_hi - p_lo + 1, TILE);
+        for (u32 j = tid; j < n_in; j += BLOCK) { const u64 o = piece_off[p_lo + j]; s_off[j] = o > base ? (uint16_t)(o - base) : 0; }
+        __syncthreads();
+#pragma unroll
+        for (int it = 0; it < STORES; ++it) {
+            const u32 rel = (u32)it * BLOCK * 16 + tid * 16;
+            const u64 o = base + rel;
+            if (o >= total) continue;
+            u32 lo = 0, hi = n_in;
+            while (hi - lo > 1) { const u32 mid = (lo + hi) >> 1; if (s_off[mid] <= rel) lo = mid; else hi = mid; }
+            u32 p = p_lo + lo;
+            u32 r = (u32)(o - piece_off[p]);
+            Piece pc = load_named_piece(p, P, k, label, label_off, pieces, fasta, name, contig_idx, piece_off);
+            uint4 v;
+            if (r >= pc.head && r - pc.head + 16 <= pc.bases) {
+                v = sixteen_bases(pc.src, pc.first + r - pc.head);
+            } else {
+                u32 w[4] = {0, 0, 0, 0};
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    if (p < P && r >= pc.total) {
+                        ++p; r = 0;
+                        if (p < P) pc = load_named_piece(p, P, k, label, label_off, pieces, fasta, name, contig_idx, piece_off);
+                    }
+                    if (p < P) { w[i >> 2] |= piece_byte(pc, r) << (8 * (i & 3)); ++r; }
+                }
+                v = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+            *(uint4*)(text + o) = v;
+        }
+        __syncthreads();
+    }
+}
+
 int check_plan_errors(u32 err) {
     if (err & ERR_FIRST) { set_error("text: the first piece does not begin a contig"); return KATOME_E_ARG; }
     if (err & ERR_PIECE) { set_error("text: a piece names a label that does not exist"); return KATOME_E_ARG; }
@@ -177,7 +274,7 @@ int check_plan_errors(u32 err) {
 }  // namespace
 
 int dev_text_plan(uint32_t k, const uint8_t* label, const uint64_t* label_off, uint64_t n_labels, const uint32_t* pieces, uint64_t n_pieces,
-                  uint32_t layout, uint64_t first_contig, TextPlan& plan, hipStream_t stream) {
+                  uint32_t layout, uint64_t first_contig, TextPlan& plan, hipStream_t stream, const uint64_t* names) {
     plan.n_contigs = plan.text_bytes = 0;
     if (layout > KATOME_TEXT_FASTA) { set_error("text: unknown layout %u", layout); return KATOME_E_ARG; }
     if (n_pieces >= 0x80000000ull) { set_error("text: %llu pieces, at most 2^31 - 1", (unsigned long long)n_pieces); return KATOME_E_UNSUPPORTED; }
@@ -192,8 +289,12 @@ int dev_text_plan(uint32_t k, const uint8_t* label, const uint64_t* label_off, u
     hipLaunchKernelGGL(piece_flag_kernel, grid, blk, 0, stream, pieces, P, counts.as<u32>());
     KCHECK_HIP(hipGetLastError());
     KCHECK(dev_scan_counts(counts.as<u32>(), P, plan.contig_idx.as<u64>(), stream));
-    hipLaunchKernelGGL(piece_measure_kernel, grid, blk, 0, stream, k, label, label_off, n_labels, pieces, P, layout, first_contig,
-                       plan.contig_idx.as<u64>(), counts.as<u32>(), tail.as<u32>());
+    if (names)
+        hipLaunchKernelGGL(piece_measure_named_kernel, grid, blk, 0, stream, k, label, label_off, n_labels, pieces, P, layout, names,
+                           plan.contig_idx.as<u64>(), counts.as<u32>(), tail.as<u32>());
+    else
+        hipLaunchKernelGGL(piece_measure_kernel, grid, blk, 0, stream, k, label, label_off, n_labels, pieces, P, layout, first_contig,
+                           plan.contig_idx.as<u64>(), counts.as<u32>(), tail.as<u32>());
     KCHECK_HIP(hipGetLastError());
     KCHECK(dev_scan_counts(counts.as<u32>(), P, plan.piece_off.as<u64>(), stream));
     u32 err = 0;
@@ -212,7 +313,8 @@ int dev_text_plan(uint32_t k, const uint8_t* label, const uint64_t* label_off, u
 }
 
 int dev_text_write(uint32_t k, const uint8_t* label, const uint64_t* label_off, const uint32_t* pieces, uint64_t n_pieces, uint32_t layout,
-                   uint64_t first_contig, const TextPlan& plan, uint64_t* contig_off, uint32_t* contig_len, uint8_t* text, hipStream_t stream) {
+                   uint64_t first_contig, const TextPlan& plan, uint64_t* contig_off, uint32_t* contig_len, uint8_t* text, hipStream_t stream,
+                   const uint64_t* names) {
     if (n_pieces == 0 || plan.text_bytes == 0) return KATOME_OK;
     const u64 P = n_pieces;
     const dim3 grid(grid_for(P, BLOCK, 256u * 32u)), blk(BLOCK);
@@ -220,16 +322,25 @@ int dev_text_write(uint32_t k, const uint8_t* label, const uint64_t* label_off, 
     KCHECK(tail.alloc(16));
     KCHECK_HIP(hipMemsetAsync(tail.p, 0, 16, stream));
     for (int lengths = 0; lengths < 2; ++lengths)
-        hipLaunchKernelGGL(contig_bounds_kernel, grid, blk, 0, stream, pieces, P, layout, first_contig, plan.contig_idx.as<u64>(), plan.piece_off.as<u64>(),
-                           lengths, contig_off, contig_len, tail.as<u32>());
+        if (names)
+            hipLaunchKernelGGL(contig_bounds_named_kernel, grid, blk, 0, stream, pieces, P, layout, names, plan.contig_idx.as<u64>(), plan.piece_off.as<u64>(),
+                               lengths, contig_off, contig_len, tail.as<u32>());
+        else
+            hipLaunchKernelGGL(contig_bounds_kernel, grid, blk, 0, stream, pieces, P, layout, first_contig, plan.contig_idx.as<u64>(), plan.piece_off.as<u64>(),
+                               lengths, contig_off, contig_len, tail.as<u32>());
     KCHECK_HIP(hipGetLastError());
     u32 err = 0;
     KCHECK_HIP(hipMemcpyAsync(&err, tail.p, 4, hipMemcpyDeviceToHost, stream));
     KCHECK_HIP(hipStreamSynchronize(stream));
     KCHECK(check_plan_errors(err));
-    {
+    const u64 tiles = (plan.text_bytes + TILE - 1) / TILE;
+    if (names) {
+        KernelScope ks(K_TEXT_WRITE_NAMED, stream, plan.text_bytes);
+        hipLaunchKernelGGL(text_write_named_kernel, dim3(grid_for(tiles, 1, 256u * 16u)), blk, 0, stream, k, label, label_off, pieces, (u32)P, layout,
+                           names, plan.contig_idx.as<u64>(), plan.piece_off.as<u64>(), plan.text_bytes, text);
+        KCHECK_HIP(hipGetLastError());
+    } else {
         KernelScope ks(K_TEXT_WRITE, stream, plan.text_bytes);
-        const u64 tiles = (plan.text_bytes + TILE - 1) / TILE;
         hipLaunchKernelGGL(text_write_kernel, dim3(grid_for(tiles, 1, 256u * 16u)), blk, 0, stream, k, label, label_off, pieces, (u32)P, layout,
                            first_contig, plan.contig_idx.as<u64>(), plan.piece_off.as<u64>(), plan.text_bytes, text);
         KCHECK_HIP(hipGetLastError());

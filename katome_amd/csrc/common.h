@@ -108,6 +108,7 @@ enum Phase { PH_EXTRACT, PH_REGION_ORDER, PH_INSERT, PH_EMIT_EDGES, PH_SORT_EDGE
              PH_GFA_STRANDS, K_GFAS_KEYS, K_GFAS_SEARCH, K_GFAS_VERIFY, K_GFAS_LINKS, K_GFAS_SIZES, K_GFAS_WRITE,
              PH_GFA_PATHS, K_GFA_PATHS_WRITE,
              PH_GFA_STRAND_PATHS, K_GFASP_WRITE, K_GFASP_SIGS, K_GFASP_SORT, K_GFASP_SEARCH, K_GFASP_VERIFY,
+             PH_UNIQUE_CONTIGS, K_TEXT_WRITE_NAMED, K_UNIQUE_SELECT,
              PH_COUNT };
 static const char* const PHASE_NAMES[PH_COUNT] = {
     "extract", "region_order", "insert", "emit_edges", "sort_edges", "node_set", "rank", "labels", "insert_tiles", "expand_tiles",
@@ -127,7 +128,8 @@ static const char* const PHASE_NAMES[PH_COUNT] = {
     "gfa", "k:gfa link sort", "k:gfa sizes", "k:gfa_write_kernel",
     "gfa_strands", "k:gfa_strands keys+sort", "k:strand_search_kernel", "k:strand_verify_kernel", "k:gfa_strands links", "k:gfa_strands sizes", "k:gfa_strands_write_kernel",
     "gfa_paths", "k:gfa_paths_write_kernel",
-    "gfa_strand_paths", "k:gfa_strand_paths_write_kernel", "k:mirror_sig_kernel", "k:mirror signature sort", "k:mirror_search_kernel", "k:mirror_verify_kernel"};
+    "gfa_strand_paths", "k:gfa_strand_paths_write_kernel", "k:mirror_sig_kernel", "k:mirror signature sort", "k:mirror_search_kernel", "k:mirror_verify_kernel",
+    "unique_contigs", "k:text_write_named_kernel", "k:unique_contigs selection"};
 struct Profiler {
     bool on = false;
     struct Ev { int phase; hipEvent_t a, b; uint64_t work; };      // work: elements the launch processed (K_* entries)
@@ -454,10 +456,13 @@ struct TextPlan {
     DevBuf contig_idx, piece_off;
     uint64_t n_contigs = 0, text_bytes = 0;
 };
+// (names, optional, device, one per contig: contig c's header reads ">katome_<names[c]>" instead -- first_contig is then not looked at;
+// the same list goes to both calls)
 int dev_text_plan(uint32_t k, const uint8_t* label, const uint64_t* label_off, uint64_t n_labels, const uint32_t* pieces, uint64_t n_pieces,
-                  uint32_t layout, uint64_t first_contig, TextPlan& plan, hipStream_t stream);
+                  uint32_t layout, uint64_t first_contig, TextPlan& plan, hipStream_t stream, const uint64_t* names = nullptr);
 int dev_text_write(uint32_t k, const uint8_t* label, const uint64_t* label_off, const uint32_t* pieces, uint64_t n_pieces, uint32_t layout,
-                   uint64_t first_contig, const TextPlan& plan, uint64_t* contig_off, uint32_t* contig_len, uint8_t* text, hipStream_t stream);
+                   uint64_t first_contig, const TextPlan& plan, uint64_t* contig_off, uint32_t* contig_len, uint8_t* text, hipStream_t stream,
+                   const uint64_t* names = nullptr);
 int dev_pieces_text(uint32_t k, const uint8_t* label, const uint64_t* label_off, uint64_t n_labels, const uint32_t* pieces, uint64_t n_pieces,
                     uint32_t layout, uint64_t first_contig, TextOutput& out, hipStream_t stream);
 // (keep_pieces, optional: the device piece list, n_pieces u32, is handed over instead of freed -- katome_dev_collapse_gfa reads it)
@@ -491,6 +496,7 @@ struct GfaOutput {
     uint64_t n_segments = 0, n_links = 0, text_bytes = 0;
 };
 int dev_gfa_plan(const GfaGraph& g, GfaPlan& plan, hipStream_t stream);                         // validates, joins, measures; synchronises
+int dev_gfa_validate(const GfaGraph& g, hipStream_t stream);                                    // dev_gfa_plan's checks alone; synchronises
 int dev_gfa_write(const GfaGraph& g, const GfaPlan& plan, uint8_t* text, hipStream_t stream);  // text: plan.text_bytes rounded up to 16
 int dev_gfa(const GfaGraph& g, GfaOutput& out, hipStream_t stream);
 // a numbered part of a GFA text whose other parts are written elsewhere (dist_gfa.hip): segment i is named first_segment + i, the
@@ -525,6 +531,10 @@ struct GfaStrandsOutput {
     uint64_t n_segments = 0, n_links = 0, text_bytes = 0, n_unpaired = 0, n_self_twins = 0;
 };
 int dev_gfa_strands_plan(const GfaGraph& g, GfaStrandsPlan& plan, hipStream_t stream);      // validates (dev_gfa_plan), pairs, verifies, measures; synchronises
+// the twins alone (what dev_gfa_strands_plan begins with): candidates by first k-mer, the pairs that name each other, verified base for
+// base.  twin: allocated here, n_edges u32, NO_TWIN = none.  validate: the segments are checked first (dev_gfa_validate) -- a caller that
+// has run dev_gfa_plan on g passes false.  No link is joined or sorted, no line is measured.  The verifying kernel is left running on `stream`
+int dev_strand_twins(const GfaGraph& g, DevBuf& twin, bool validate, hipStream_t stream);
 // text: plan.text_bytes rounded up to 16; segment_name: n_segments entries; edge_twin: n_edges entries
 int dev_gfa_strands_write(const GfaGraph& g, const GfaStrandsPlan& plan, uint8_t* text, uint64_t* segment_name, uint64_t* edge_twin, hipStream_t stream);
 int dev_gfa_strands(const GfaGraph& g, GfaStrandsOutput& out, hipStream_t stream);
@@ -567,6 +577,33 @@ struct GfaStrandPathsOutput {
 int dev_gfa_strand_paths_plan(uint64_t n_edges, const uint64_t* edge_src, const uint64_t* edge_dst, const uint32_t* twin, const uint32_t* pieces,
                               uint64_t n_pieces, GfaStrandPathsPlan& plan, hipStream_t stream);
 int dev_gfa_strand_paths_write(uint64_t n_pieces, const GfaStrandPathsPlan& plan, uint8_t* text, hipStream_t stream);   // text: runs.text_bytes rounded up to 16
+// the mirror search itself, over any grouping of consecutive pieces (the paths above; collapse's contigs in unique_contigs.hip): group_idx
+// is the EXCLUSIVE scan of the flags that begin a group (n_pieces + 1 entries), group_first every group's first piece (n_groups + 1).
+// mirror: allocated here, [n_groups] u64, all ones: none.  twin is trusted, every piece's id is below its length.  Synchronises
+int dev_find_mirrors(const uint32_t* pieces, uint64_t n_pieces, const uint32_t* twin, const uint64_t* group_idx, const uint64_t* group_first, uint64_t n_groups,
+                     DevBuf& mirror, uint64_t* n_mirrored, uint64_t* n_self_mirror, hipStream_t stream);
+// a caller's 64-bit twin map (all ones: none) checked on the device -- an entry is all ones or below n_edges, and names its edge back:
+// KATOME_E_ARG, the message begun with `who` -- and narrowed into twin (n_edges u32, NO_TWIN: none).  Synchronises
+int dev_strand_twin_check(const char* who, uint64_t n_edges, const uint64_t* twin64, uint32_t* twin, hipStream_t stream);
+
+// unique_contigs.hip: one strand per molecule (include/katome_gpu.h has the definitions).  Everything the result holds, in its own buffers
+struct UniqueOutput {
+    DevBuf contig_mirror, kept_name, kept_off, kept_len, text;
+    uint64_t n_contigs = 0, n_mirrored = 0, n_self_mirror = 0, n_kept = 0, text_bytes = 0;
+    uint32_t layout = 0;
+};
+// what the selection leaves for the writer: the mirrors, the kept contigs' names and their pieces, compacted, with the text's plan
+struct UniquePlan {
+    DevBuf mirror, name, pieces;
+    TextPlan text;
+    uint64_t n_contigs = 0, n_mirrored = 0, n_self_mirror = 0, n_kept = 0, n_kept_pieces = 0;
+};
+// validates the pieces (dev_text_plan), finds the contigs' mirrors, selects, compacts, measures; synchronises.  twin: n_labels u32, trusted
+int dev_unique_plan(uint32_t k, const uint8_t* label, const uint64_t* label_off, uint64_t n_labels, const uint32_t* twin, const uint32_t* pieces,
+                    uint64_t n_pieces, uint32_t layout, UniquePlan& plan, hipStream_t stream);
+// kept_off / kept_len: n_kept entries; text: plan.text.text_bytes rounded up to 16
+int dev_unique_write(uint32_t k, const uint8_t* label, const uint64_t* label_off, uint32_t layout, const UniquePlan& plan, uint64_t* kept_off, uint32_t* kept_len,
+                     uint8_t* text, hipStream_t stream);
 
 // Contigs::stats' panic sites as a status (contig_stats.h's 1, 2, 3: which tipping point is 0), one message wherever the stats are made
 inline int contig_stats_status(int which) {

@@ -190,6 +190,25 @@ int check_gfa_errors(u32 err) {
 
 }  // namespace
 
+// dev_gfa_plan's checks without its join: the measuring kernel into scratch of its own (16 bytes per segment), and its verdict
+int dev_gfa_validate(const GfaGraph& g, hipStream_t stream) {
+    const u64 E = g.n_edges;
+    if (E >= (1ull << 32)) { set_error("gfa: %llu segments, at most 2^32 - 1", (unsigned long long)E); return KATOME_E_UNSUPPORTED; }
+    if (E && (!g.edge_src || !g.edge_dst || !g.edge_weight || !g.edge_kmers || !g.label_off || !g.label)) { set_error("null argument"); return KATOME_E_ARG; }
+    if (g.cov.any() && E && !g.cov.all()) { set_error("null argument"); return KATOME_E_ARG; }
+    DevBuf key(stream), order(stream), seg_size(stream), tail(stream);
+    KCHECK(key.alloc(E * 8 + 16)); KCHECK(order.alloc(E * 4 + 16)); KCHECK(seg_size.alloc((E + 1) * 4)); KCHECK(tail.alloc(16));
+    KCHECK_HIP(hipMemsetAsync(tail.p, 0, 16, stream));
+    hipLaunchKernelGGL(g.cov.any() ? gfa_measure_kernel<true> : gfa_measure_kernel<false>, dim3(grid_for(E, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, g.k, g.n_nodes, E,
+                       g.edge_src, g.edge_dst, g.edge_weight, g.edge_kmers, g.label_off, g.label, g.label_bytes, seg_size.as<u32>(), key.as<u64>(), order.as<u32>(),
+                       tail.as<u32>(), g.cov);
+    KCHECK_HIP(hipGetLastError());
+    u32 err = 0;
+    KCHECK_HIP(hipMemcpyAsync(&err, tail.p, 4, hipMemcpyDeviceToHost, stream));
+    KCHECK_HIP(hipStreamSynchronize(stream));
+    return check_gfa_errors(err);
+}
+
 int dev_gfa_plan(const GfaGraph& g, GfaPlan& plan, hipStream_t stream) {
     plan.n_links = plan.text_bytes = 0;
     const u64 E = g.n_edges, N = g.n_nodes;

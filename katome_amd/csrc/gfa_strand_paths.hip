@@ -167,13 +167,17 @@ __global__ __launch_bounds__(BLOCK) void mirror_count_kernel(u64 n, const u64* _
     if ((threadIdx.x & 63) == 0) { if (mirrored) atomicAdd(&count[1], (unsigned long long)mirrored); if (self) atomicAdd(&count[2], (unsigned long long)self); }
 }
 
-int find_mirrors(const u32* pieces, u64 P, const u32* twin, GfaStrandPathsPlan& plan, hipStream_t stream) {
-    const u64 n = plan.runs.n_paths;
-    plan.n_mirrored = plan.n_self_mirror = 0;
-    KCHECK(plan.mirror.alloc(n * 8));
+}  // namespace
+
+// The mirrors of n groups of consecutive pieces -- the paths of this file, or collapse's contigs (unique_contigs.hip): group_idx is the
+// EXCLUSIVE scan of the flags that begin a group (piece p lies in group group_idx[p + 1] - 1; P + 1 entries), first every group's
+// first piece (n + 1 entries).  mirror: allocated here, [n] u64.  twin is trusted; synchronises
+int dev_find_mirrors(const uint32_t* pieces, uint64_t P, const uint32_t* twin, const uint64_t* path_idx, const uint64_t* first, uint64_t n, DevBuf& mirror,
+                     uint64_t* n_mirrored, uint64_t* n_self_mirror, hipStream_t stream) {
+    *n_mirrored = *n_self_mirror = 0;
+    mirror.stream = stream;
+    KCHECK(mirror.alloc(n * 8));
     if (n == 0) return KATOME_OK;
-    const u64* path_idx = plan.runs.path_idx.as<u64>();
-    const u64* first = plan.runs.path_first_piece.as<u64>();
     const dim3 blk(BLOCK), by_piece(grid_for(P, BLOCK, 256u * 32u)), by_path(grid_for(n, BLOCK, 256u * 32u));
     DevBuf fwd(stream), mir(stream), order(stream), cand(stream), fail(stream), count(stream);
     KCHECK(fwd.alloc(n * 8 + 16)); KCHECK(mir.alloc(n * 8)); KCHECK(order.alloc(n * 4 + 16)); KCHECK(cand.alloc(n * 4)); KCHECK(fail.alloc(n * 4)); KCHECK(count.alloc(24));
@@ -193,7 +197,7 @@ int find_mirrors(const u32* pieces, u64 P, const u32* twin, GfaStrandPathsPlan& 
     }
     {
         KernelScope ks(K_GFASP_SEARCH, stream, n);
-        hipLaunchKernelGGL(mirror_search_kernel, by_path, blk, 0, stream, n, fwd.as<u64>(), mir.as<u64>(), cand.as<u32>(), plan.mirror.as<u64>(),
+        hipLaunchKernelGGL(mirror_search_kernel, by_path, blk, 0, stream, n, fwd.as<u64>(), mir.as<u64>(), cand.as<u32>(), mirror.as<u64>(),
                            count.as<unsigned long long>());
         KCHECK_HIP(hipGetLastError());
     }
@@ -206,19 +210,33 @@ int find_mirrors(const u32* pieces, u64 P, const u32* twin, GfaStrandPathsPlan& 
         KernelScope ks(K_GFASP_VERIFY, stream, P);
         hipLaunchKernelGGL(mirror_verify_kernel, by_piece, blk, 0, stream, pieces, P, twin, path_idx, first, order.as<u32>(), cand.as<u32>(), fail.as<u32>());
         hipLaunchKernelGGL(mirror_settle_kernel, by_path, blk, 0, stream, n, fwd.as<u64>(), order.as<u32>(), mir.as<u64>(), cand.as<u32>(), fail.as<u32>(),
-                           plan.mirror.as<u64>(), count.as<unsigned long long>());
+                           mirror.as<u64>(), count.as<unsigned long long>());
         KCHECK_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(mirror_count_kernel, by_path, blk, 0, stream, n, plan.mirror.as<u64>(), count.as<unsigned long long>());
+    hipLaunchKernelGGL(mirror_count_kernel, by_path, blk, 0, stream, n, mirror.as<u64>(), count.as<unsigned long long>());
     KCHECK_HIP(hipGetLastError());
     u64 counted[3] = {0, 0, 0};
     KCHECK_HIP(hipMemcpyAsync(counted, count.p, 24, hipMemcpyDeviceToHost, stream));
     KCHECK_HIP(hipStreamSynchronize(stream));
-    plan.n_mirrored = counted[1]; plan.n_self_mirror = counted[2];
+    *n_mirrored = counted[1]; *n_self_mirror = counted[2];
     return KATOME_OK;
 }
 
-}  // namespace
+// a caller's twin map (64-bit, all ones: none) checked on the device and narrowed to the 32-bit one; `who` begins the messages; synchronises
+int dev_strand_twin_check(const char* who, uint64_t E, const uint64_t* twin64, uint32_t* twin, hipStream_t stream) {
+    if (E == 0) return KATOME_OK;
+    DevBuf tail(stream);
+    KCHECK(tail.alloc(16));
+    KCHECK_HIP(hipMemsetAsync(tail.p, 0, 16, stream));
+    u32 err = 0;
+    hipLaunchKernelGGL(strand_twin_check_kernel, dim3(grid_for(E, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, E, twin64, twin, tail.as<u32>());
+    KCHECK_HIP(hipGetLastError());
+    KCHECK_HIP(hipMemcpyAsync(&err, tail.p, 4, hipMemcpyDeviceToHost, stream));
+    KCHECK_HIP(hipStreamSynchronize(stream));
+    if (err & ERR_TWIN) { set_error("%s: a twin entry is neither all ones nor below n_edges", who); return KATOME_E_ARG; }
+    if (err & ERR_INVOLUTION) { set_error("%s: twin(twin(i)) != i for some edge i", who); return KATOME_E_ARG; }
+    return KATOME_OK;
+}
 
 int dev_gfa_strand_paths_plan(uint64_t n_edges, const uint64_t* edge_src, const uint64_t* edge_dst, const uint32_t* twin, const uint32_t* pieces,
                               uint64_t n_pieces, GfaStrandPathsPlan& plan, hipStream_t stream) {
@@ -235,7 +253,8 @@ int dev_gfa_strand_paths_plan(uint64_t n_edges, const uint64_t* edge_src, const 
         KCHECK(dev_gfa_paths_offsets(P, size.as<u32>(), plan.runs, stream));
     }
     size.release();
-    return find_mirrors(pieces, P, twin, plan, stream);
+    return dev_find_mirrors(pieces, P, twin, plan.runs.path_idx.as<u64>(), plan.runs.path_first_piece.as<u64>(), plan.runs.n_paths, plan.mirror, &plan.n_mirrored,
+                            &plan.n_self_mirror, stream);
 }
 
 int dev_gfa_strand_paths_write(uint64_t n_pieces, const GfaStrandPathsPlan& plan, uint8_t* text, hipStream_t stream) {
@@ -269,18 +288,9 @@ int katome_dev_gfa_strand_paths_arrays(int device, uint64_t n_edges, const uint6
     GfaStrandPathsPlan plan;
     {
         PhaseScope ps(trace.prof, PH_GFA_STRAND_PATHS, stream);
-        DevBuf twin(stream), tail(stream);
-        KCHECK(twin.alloc(E * 4)); KCHECK(tail.alloc(16));
-        KCHECK_HIP(hipMemsetAsync(tail.p, 0, 16, stream));
-        u32 err = 0;
-        if (E) {
-            hipLaunchKernelGGL(strand_twin_check_kernel, dim3(grid_for(E, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, E, d_edge_twin, twin.as<u32>(), tail.as<u32>());
-            KCHECK_HIP(hipGetLastError());
-            KCHECK_HIP(hipMemcpyAsync(&err, tail.p, 4, hipMemcpyDeviceToHost, stream));
-            KCHECK_HIP(hipStreamSynchronize(stream));
-        }
-        if (err & ERR_TWIN) { set_error("gfa_strand_paths: a twin entry is neither all ones nor below n_edges"); return KATOME_E_ARG; }
-        if (err & ERR_INVOLUTION) { set_error("gfa_strand_paths: twin(twin(i)) != i for some edge i"); return KATOME_E_ARG; }
+        DevBuf twin(stream);
+        KCHECK(twin.alloc(E * 4));
+        KCHECK(dev_strand_twin_check("gfa_strand_paths", E, d_edge_twin, twin.as<u32>(), stream));
         KCHECK(dev_gfa_strand_paths_plan(E, d_edge_src, d_edge_dst, twin.as<u32>(), d_pieces, n_pieces, plan, stream));
         const GfaPathsPlan& r = plan.runs;
         counts[0] = r.n_paths; counts[1] = r.n_paths - r.n_contigs; counts[2] = r.text_bytes; counts[3] = plan.n_mirrored; counts[4] = plan.n_self_mirror;

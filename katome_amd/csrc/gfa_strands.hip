@@ -257,6 +257,32 @@ int find_candidates(const GfaGraph& g, u32* cand, hipStream_t stream) {
 
 }  // namespace
 
+int dev_strand_twins(const GfaGraph& g, DevBuf& twin, bool validate, hipStream_t stream) {
+    const u64 E = g.n_edges;
+    if (validate) KCHECK(dev_gfa_validate(g, stream));
+    const dim3 blk(BLOCK), grid(grid_for(E, BLOCK, 256u * 32u));
+    twin.stream = stream;
+    DevBuf cand(stream), words(stream), word_off(stream);
+    KCHECK(twin.alloc(E * 4 + 16));
+    if (E == 0) return KATOME_OK;
+    KCHECK(cand.alloc(E * 4 + 16)); KCHECK(words.alloc(E * 4 + 16)); KCHECK(word_off.alloc((E + 1) * 8));
+    if (2 * g.k <= 64) KCHECK(find_candidates<1>(g, cand.as<u32>(), stream));
+    else KCHECK(find_candidates<2>(g, cand.as<u32>(), stream));
+    u64 W = 0;
+    KernelScope ks(K_GFAS_VERIFY, stream, E);
+    hipLaunchKernelGGL(strand_pair_kernel, grid, blk, 0, stream, g.k, E, cand.as<u32>(), g.edge_kmers, twin.as<u32>(), words.as<u32>());
+    KCHECK_HIP(hipGetLastError());
+    KCHECK(dev_scan_counts(words.as<u32>(), E, word_off.as<u64>(), stream));
+    KCHECK_HIP(hipMemcpyAsync(&W, word_off.as<u64>() + E, 8, hipMemcpyDeviceToHost, stream));
+    KCHECK_HIP(hipStreamSynchronize(stream));
+    if (W) {
+        hipLaunchKernelGGL(strand_verify_kernel, dim3(grid_for((W + VERIFY_TILE - 1) / VERIFY_TILE, 1, 256u * 32u)), blk, 0, stream, g.k, (u32)E, W, word_off.as<u64>(),
+                           cand.as<u32>(), g.edge_kmers, g.label_off, g.label, twin.as<u32>());
+        KCHECK_HIP(hipGetLastError());
+    }
+    return KATOME_OK;
+}
+
 int dev_gfa_strands_plan(const GfaGraph& g, GfaStrandsPlan& plan, hipStream_t stream) {
     plan.n_segments = plan.n_links = plan.text_bytes = plan.n_unpaired = plan.n_self_twins = 0;
     const u64 E = g.n_edges;
@@ -266,30 +292,14 @@ int dev_gfa_strands_plan(const GfaGraph& g, GfaStrandsPlan& plan, hipStream_t st
     const u64 L_in = join.n_links;
     const dim3 blk(BLOCK), grid(grid_for(E, BLOCK, 256u * 32u));
     plan.line_off.stream = plan.segment_off.stream = plan.link_first.stream = plan.name.stream = plan.twin.stream = plan.link_keys.stream = stream;
-    DevBuf cand(stream), words(stream), word_off(stream), count(stream), seg_size(stream), size(stream);
-    KCHECK(plan.twin.alloc(E * 4 + 16)); KCHECK(cand.alloc(E * 4 + 16)); KCHECK(words.alloc(E * 4 + 16)); KCHECK(word_off.alloc((E + 1) * 8)); KCHECK(count.alloc(16));
+    DevBuf words(stream), word_off(stream), count(stream), seg_size(stream), size(stream);
+    KCHECK(dev_strand_twins(g, plan.twin, false, stream));
+    KCHECK(words.alloc(E * 4 + 16)); KCHECK(word_off.alloc((E + 1) * 8)); KCHECK(count.alloc(16));
     KCHECK_HIP(hipMemsetAsync(count.p, 0, 16, stream));
     u64 S = 0;
     if (E) {
-        if (2 * g.k <= 64) KCHECK(find_candidates<1>(g, cand.as<u32>(), stream));
-        else KCHECK(find_candidates<2>(g, cand.as<u32>(), stream));
-        u64 W = 0;
-        {
-            KernelScope ks(K_GFAS_VERIFY, stream, E);
-            hipLaunchKernelGGL(strand_pair_kernel, grid, blk, 0, stream, g.k, E, cand.as<u32>(), g.edge_kmers, plan.twin.as<u32>(), words.as<u32>());
-            KCHECK_HIP(hipGetLastError());
-            KCHECK(dev_scan_counts(words.as<u32>(), E, word_off.as<u64>(), stream));
-            KCHECK_HIP(hipMemcpyAsync(&W, word_off.as<u64>() + E, 8, hipMemcpyDeviceToHost, stream));
-            KCHECK_HIP(hipStreamSynchronize(stream));
-            if (W) {
-                hipLaunchKernelGGL(strand_verify_kernel, dim3(grid_for((W + VERIFY_TILE - 1) / VERIFY_TILE, 1, 256u * 32u)), blk, 0, stream, g.k, (u32)E, W, word_off.as<u64>(),
-                                   cand.as<u32>(), g.edge_kmers, g.label_off, g.label, plan.twin.as<u32>());
-                KCHECK_HIP(hipGetLastError());
-            }
-        }
-        cand.release();
         KernelScope ks(K_GFAS_SIZES, stream, E);
-        // (words and word_off are spent: they hold the representatives' flags and their scan from here on)
+        // (words and word_off hold the representatives' flags and their scan)
         hipLaunchKernelGGL(strand_rep_kernel, grid, blk, 0, stream, E, plan.twin.as<u32>(), words.as<u32>(), count.as<unsigned long long>());
         KCHECK_HIP(hipGetLastError());
         KCHECK(dev_scan_counts(words.as<u32>(), E, word_off.as<u64>(), stream));

@@ -103,6 +103,17 @@ void katome_gfa_strand_paths_free(katome_gfa_strand_paths* g) {
     delete o;
 }
 
+struct UniqueAssemblyOwner {   // katome_unique_assembly followed by what it owns
+    katome_unique_assembly u;
+    std::vector<void*> mem;
+};
+void katome_unique_assembly_free(katome_unique_assembly* u) {
+    if (!u) return;
+    UniqueAssemblyOwner* o = reinterpret_cast<UniqueAssemblyOwner*>(u);
+    for (void* p : o->mem) free(p);
+    delete o;
+}
+
 }  // extern "C"
 
 // KATOME_TRACE_BUILD=1: wall time of the host entries' stages on stderr
@@ -397,12 +408,49 @@ static int gfa_strand_paths_to_host(katome_builder* b, uint64_t read_bytes, kato
     return KATOME_OK;
 }
 
+extern "C" int katome_unique_assembly_save(const katome_unique_assembly* u, const char* path) {
+    if (!u || !path) { set_error("null argument"); return KATOME_E_ARG; }
+    return save_gfa_text(u->text, u->text_bytes, path);      // (File::create's statuses and message, as for every text here)
+}
+// katome_dev_collapse_unique(FASTA) of the builder's last collapse in host arrays; lengths: every contig's bases, as the walk knows them
+static int unique_to_host(katome_builder* b, uint64_t read_bytes, const std::vector<uint64_t>& lengths, uint64_t genome_len, katome_unique_assembly** out) {
+    katome_dev_unique_assembly d;
+    KCHECK(katome_dev_collapse_unique(b, KATOME_TEXT_FASTA, &d, nullptr));
+    UniqueAssemblyOwner* o = new (std::nothrow) UniqueAssemblyOwner();
+    if (!o) { set_error("out of host memory"); return KATOME_E_OOM; }
+    memset(&o->u, 0, sizeof o->u);
+    katome_unique_assembly* u = &o->u;
+    u->n_contigs = d.n_contigs; u->n_kept = d.n_kept; u->text_bytes = d.text_bytes; u->read_bytes = read_bytes; u->k = b->s.k;
+    u->n_mirrored = d.n_mirrored; u->n_self_mirror = d.n_self_mirror;
+    int rc = d2h(o, &u->contig_mirror, d.d_contig_mirror, d.n_contigs);
+    if (!rc) rc = d2h(o, &u->kept_name, d.d_kept_name, d.n_kept);
+    if (!rc) rc = d2h(o, &u->kept_off, d.d_kept_off, d.n_kept);
+    if (!rc) rc = d2h(o, &u->kept_len, d.d_kept_len, d.n_kept);
+    if (!rc) rc = d2h(o, &u->text, d.d_text, d.text_bytes);
+    if (!rc) {
+        std::vector<uint64_t> kept;
+        try { kept.reserve(d.n_kept); }
+        catch (const std::bad_alloc&) { set_error("out of host memory"); rc = KATOME_E_OOM; }
+        for (uint64_t i = 0; i < d.n_kept && !rc; ++i) {
+            const uint64_t c = u->kept_name[i];
+            if (c >= lengths.size() || lengths[c] != u->kept_len[i]) { set_error("collapse_unique: kept contig %llu does not have the walk's length", (unsigned long long)c); rc = KATOME_E_DEVICE; }
+            else kept.push_back(lengths[c]);
+        }
+        if (!rc) rc = katome_contig_stats_of(kept.data(), kept.size(), genome_len, &u->stats);
+    }
+    if (rc) { katome_unique_assembly_free(u); return rc; }
+    *out = u;
+    return KATOME_OK;
+}
+
 // the stages "dcwced" (asm/basic_assembler.rs:58-75), collapse, Contigs::stats and, with a path, save_to_file: host arrays
 // (with_gfa: katome_assemble_gfa_* -- the GFA of the collapse's shrunk graph with the contigs as P lines too; merge_strands:
 // katome_assemble_gfa_strands_* -- that GFA with strand twins merged, handed back through strands_out)
 struct AssembleWant {
     katome_assembly** out; const char* path; bool with_gfa = false; katome_gfa_paths** gfa_out = nullptr; const char* gfa_path = nullptr;
     bool merge_strands = false; katome_gfa_strand_paths** strands_out = nullptr;
+    // (unique: katome_assemble_unique_* -- the strand-unique form of the contigs beside the assembly, no GFA)
+    bool unique = false; katome_unique_assembly** unique_out = nullptr; const char* unique_path = nullptr;
 };
 static int assembly_to_host(katome_builder* b, uint64_t read_bytes, const AssembleWant& want, uint64_t genome_len) {
     katome_dev_graph dg;
@@ -426,6 +474,21 @@ static int assembly_to_host(katome_builder* b, uint64_t read_bytes, const Assemb
     if (!rc) rc = d2h(o, &a->text, da.d_text, da.text_bytes);
     if (!rc) rc = katome_contig_stats_of(lengths.data(), lengths.size(), genome_len, &a->stats);      // contigs.log_stats()
     if (rc) { katome_assembly_free(a); return rc; }
+    if (want.unique) {
+        katome_unique_assembly* u = nullptr;
+        rc = unique_to_host(b, read_bytes, lengths, genome_len, &u);
+        build_lap("collapse_unique");
+        if (rc) { katome_assembly_free(a); return rc; }
+        if (want.out) *want.out = a;
+        if (want.unique_out) *want.unique_out = u;
+        rc = want.path ? katome_assembly_save(a, want.path) : KATOME_OK;      // (both files are tried; the first failure is the one reported)
+        const std::string first_err = rc ? get_error() : "";
+        const int rc_unique = want.unique_path ? katome_unique_assembly_save(u, want.unique_path) : KATOME_OK;
+        if (rc) set_error("%s", first_err.c_str()); else rc = rc_unique;
+        if (!want.out) katome_assembly_free(a);
+        if (!want.unique_out) katome_unique_assembly_free(u);
+        return rc;
+    }
     if (want.with_gfa) {
         katome_gfa_paths* g = nullptr;
         katome_gfa_strand_paths* gs = nullptr;
@@ -1115,6 +1178,24 @@ int katome_assemble_gfa_strands_packed(const katome_settings* s, const uint8_t* 
     KCHECK(assemble_gfa_strands_finish(original_genome_length, fasta_path, gfa_path, asm_out, gfa_out, f));
     return build_packed_impl(s, packed, n_reads, read_len, skip, f);
 }
+// katome_assemble_unique_*: the assembly and the strand-unique form of its contigs
+static int assemble_unique_finish(uint64_t genome_len, const char* fasta_path, const char* unique_path, katome_assembly** asm_out,
+                                  katome_unique_assembly** unique_out, Finish& f) {
+    if (asm_out) *asm_out = nullptr;
+    if (unique_out) *unique_out = nullptr;
+    if (!fasta_path && !unique_path && !asm_out && !unique_out) { set_error("null argument"); return KATOME_E_ARG; }
+    f.assemble = AssembleWant{asm_out, fasta_path};
+    f.assemble.unique = true; f.assemble.unique_out = unique_out; f.assemble.unique_path = unique_path;
+    f.assembling = true; f.genome_len = genome_len;
+    return KATOME_OK;
+}
+int katome_assemble_unique_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip,
+                                  uint64_t original_genome_length, const char* fasta_path, const char* unique_path, katome_assembly** asm_out,
+                                  katome_unique_assembly** unique_out) {
+    Finish f{nullptr, nullptr};
+    KCHECK(assemble_unique_finish(original_genome_length, fasta_path, unique_path, asm_out, unique_out, f));
+    return build_packed_impl(s, packed, n_reads, read_len, skip, f);
+}
 // (the same check on every route: the stages work on the links of a first-seen build)
 static int unitigs_refusal(const katome_settings* s, const char* stages) {
     if (s && !(s->flags & KATOME_FLAG_FIRST_SEEN_ORDER) && ((stages && *stages) || (s->flags & KATOME_FLAG_REMOVE_DEAD_PATHS))) {
@@ -1350,6 +1431,12 @@ int katome_assemble_gfa_strands_files(const katome_settings* s, const char* cons
                                       const char* fasta_path, const char* gfa_path, katome_assembly** asm_out, katome_gfa_strand_paths** gfa_out) {
     Finish f{nullptr, nullptr};
     KCHECK(assemble_gfa_strands_finish(original_genome_length, fasta_path, gfa_path, asm_out, gfa_out, f));
+    return build_files_impl(s, paths, n_paths, f);
+}
+int katome_assemble_unique_files(const katome_settings* s, const char* const* paths, size_t n_paths, uint64_t original_genome_length,
+                                 const char* fasta_path, const char* unique_path, katome_assembly** asm_out, katome_unique_assembly** unique_out) {
+    Finish f{nullptr, nullptr};
+    KCHECK(assemble_unique_finish(original_genome_length, fasta_path, unique_path, asm_out, unique_out, f));
     return build_files_impl(s, paths, n_paths, f);
 }
 int katome_unitigs_files(const katome_settings* s, const char* const* paths, size_t n_paths, const char* stages, uint64_t original_genome_length,

@@ -222,7 +222,9 @@ class DeviceGfaPaths(DeviceGfa):
 
 def unique_paths(path_mirror):
     """the paths that stay when every double-stranded molecule keeps one: those with no mirror (-1, or 2^64 - 1 as unsigned) or
-    with mirror(j) >= j -> list of path indices"""
+    with mirror(j) >= j -> list of path indices.  This is the per-PATH rule: where a sequence occurs more than once it keeps an
+    irregular subset of the copies.  The rule for CONTIGS, which keeps one strand with all its copies, is
+    Builder.collapse_unique()'s (include/katome_gpu.h, katome_dev_collapse_unique)"""
     return [j for j, q in enumerate(int(x) for x in path_mirror) if q < 0 or q >= j]
 
 
@@ -280,6 +282,31 @@ class DeviceAssembly:
     @property
     def stats(self):
         return self.collapse_stats
+
+
+class DeviceUniqueAssembly:
+    """the strand-unique assembly in HBM (katome_dev_collapse_unique, which has the definitions): contig_mirror[c] = the smallest
+    contig that spells c's molecule from its other end by pieces, -1 for none (n_mirrored have one, n_self_mirror are their own);
+    the kept contigs -- one strand per molecule with all its copies -- are kept_name (ascending, their numbers in collapse()'s
+    result), kept contig i is text[kept_off[i]:kept_off[i] + kept_len[i]]; layout "fasta": text is the kept records of
+    collapse("fasta")'s text, byte for byte"""
+
+    def __init__(self, n_contigs, n_mirrored, n_self_mirror, contig_mirror, n_kept, text_bytes, layout, kept_name, kept_off, kept_len, text):
+        self.n_contigs, self.n_mirrored, self.n_self_mirror, self.contig_mirror = n_contigs, n_mirrored, n_self_mirror, contig_mirror
+        self.n_kept, self.text_bytes, self.layout = n_kept, text_bytes, layout
+        self.kept_name, self.kept_off, self.kept_len, self.text = kept_name, kept_off, kept_len, text
+
+    def lengths(self):
+        return [int(x) & 0xFFFFFFFF for x in self.kept_len.cpu().tolist()]
+
+    def bytes(self):
+        """host: the text's bytes"""
+        return bytes(self.text.cpu().numpy()[:self.text_bytes])
+
+    def contigs(self):
+        """host: the kept contigs as a list of str, in order"""
+        raw = self.bytes()
+        return [raw[o:o + n].decode() for o, n in zip(self.kept_off.cpu().tolist(), self.lengths())]
 
 
 class Builder(_ViewOwner):
@@ -554,6 +581,17 @@ class Builder(_ViewOwner):
         return DeviceGfaPaths(d.n_segments, d.n_links, d.text_bytes, _view(d.d_text, (d.text_bytes,), "|u1", self, self.tdev), v(d.d_segment_off, d.n_segments),
                               v(d.d_link_first, d.n_segments + 1), d.n_paths, d.n_jumps, d.path_bytes, _view(d.d_path_text, (d.path_bytes,), "|u1", self, self.tdev),
                               v(d.d_path_line_off, d.n_paths + 1), v(d.d_path_contig, d.n_paths), v(d.d_path_first_piece, d.n_paths + 1))
+
+    def collapse_unique(self, layout="fasta"):
+        """the strand-unique form of the last collapse(), whatever layout that used: every contig's mirror by piece sequence, the
+        kept set and its text under the contigs' original numbers (katome_dev_collapse_unique; include/katome_gpu.h has the
+        definitions) -> DeviceUniqueAssembly, valid until the next collapse_unique() or close().  The results of collapse(),
+        collapse_gfa() and gfa() stay valid"""
+        d = _lib.DevUniqueAssembly()
+        _check(_lib.lib().katome_dev_collapse_unique(self._h, LAYOUTS[layout], C.byref(d), _stream()))
+        v = lambda p, n, t="<i8": _view(p, (n,), t, self, self.tdev)
+        return DeviceUniqueAssembly(d.n_contigs, d.n_mirrored, d.n_self_mirror, v(d.d_contig_mirror, d.n_contigs), d.n_kept, d.text_bytes, layout,
+                                    v(d.d_kept_name, d.n_kept), v(d.d_kept_off, d.n_kept), v(d.d_kept_len, d.n_kept, "<i4"), v(d.d_text, d.text_bytes, "|u1"))
 
     def graph(self):
         """the finalized graph as it stands (after remove_dead_paths / remove_weak_edges)"""
@@ -869,6 +907,26 @@ def gfa_strand_paths_arrays(edge_src, edge_dst, edge_twin, pieces, device=0):
     _check(L.katome_dev_gfa_strand_paths_arrays(*args, _ptr(line_off), _ptr(contig), _ptr(first), _ptr(mirror), n_paths, _ptr(text), cap, counts, _stream()))
     names = ("n_paths", "n_jumps", "text_bytes", "n_mirrored", "n_self_mirror")
     return text, dict(zip(names, counts)), line_off, contig[:n_paths], first, mirror[:n_paths]
+
+
+def unique_contigs_arrays(labels, label_off, edge_twin, pieces, k, layout="plain", device=0):
+    """katome_dev_collapse_unique on the caller's tensors (katome_dev_unique_contigs_arrays): labels / label_off as for pieces_text,
+    edge_twin int64 with an entry per label (-1 for none), pieces int32/uint32 -> DeviceUniqueAssembly (text: text_bytes of a
+    buffer rounded up to 16, zeros behind them)"""
+    tdev = label_off.device
+    n_labels = label_off.numel() - 1
+    counts = (C.c_uint64 * 5)()
+    L = _lib.lib()
+    args = (device, k, _ptr(labels), _ptr(label_off), n_labels, _ptr(edge_twin), _ptr(pieces), pieces.numel(), LAYOUTS[layout])
+    _check(L.katome_dev_unique_contigs_arrays(*args, None, 0, None, None, None, 0, None, 0, counts, _stream()))
+    n, n_kept, cap = counts[0], counts[1], (counts[2] + 15) // 16 * 16
+    mirror = torch.empty(max(n, 1), dtype=torch.int64, device=tdev)
+    name = torch.empty(max(n_kept, 1), dtype=torch.int64, device=tdev)
+    off = torch.empty(max(n_kept, 1), dtype=torch.int64, device=tdev)
+    length = torch.empty(max(n_kept, 1), dtype=torch.int32, device=tdev)
+    text = torch.empty(max(cap, 16), dtype=torch.uint8, device=tdev)
+    _check(L.katome_dev_unique_contigs_arrays(*args, _ptr(mirror), n, _ptr(name), _ptr(off), _ptr(length), n_kept, _ptr(text), cap, counts, _stream()))
+    return DeviceUniqueAssembly(counts[0], counts[3], counts[4], mirror[:n], counts[1], counts[2], layout, name[:n_kept], off[:n_kept], length[:n_kept], text)
 
 
 def gfa_coverage_arrays(k, n_nodes, edge_src, edge_dst, edge_weight, edge_kmers, kmer_sum, kmer_min, kmer_max, edge_label_off, edge_label, device=0,
