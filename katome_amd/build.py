@@ -143,78 +143,85 @@ def contig_stats(lengths, genome_length) -> ContigsStats:
     return ContigsStats(st.n50, st.l50, st.n90, st.ng50)
 
 
-class Assembly:
+class _COwned:
+    """a result the C library owns: its pointer and the names of the symbols that free it and write its text.  Keeps the C
+    result until it is collected."""
+    _free = None
+    _save = None
+
+    def __init__(self, ptr):
+        self._ptr = ptr
+
+    def save_to_file(self, path):
+        """the result's text as a file (katome_*_save; for an Assembly: Contigs::save_to_file, asm/mod.rs:57-72): a path that
+        cannot be created raises KatomePanic(E_OPEN)"""
+        _check(getattr(_lib.lib(), self._save)(self._ptr, os.fsencode(path)))
+
+    def __del__(self):
+        try:
+            getattr(_lib.lib(), self._free)(self._ptr)
+        except Exception:       # interpreter shutdown
+            pass
+
+
+def _array(ptr, n, dtype=np.uint64):
+    """a copy of the n elements at ptr (n = 0: the pointer is not read)"""
+    return np.ctypeslib.as_array(ptr, (n,)).copy() if n else np.zeros(0, dtype)
+
+
+def _text(ptr, n):
+    return bytes(np.ctypeslib.as_array(ptr, (n,))) if n else b""
+
+
+class Assembly(_COwned):
     """result of GpuGraph.assemble: the contigs (list of str, in the reference's order), the FASTA text Contigs::save_to_file
     writes, Contigs::stats, number_of_read_bytes and the collapse walk's counters.  Keeps the C result until it is collected."""
+    _free, _save = "katome_assembly_free", "katome_assembly_save"
 
     def __init__(self, ap):
-        self._ap = ap
+        super().__init__(ap)
         a = ap.contents
-        nc, nb = a.n_contigs, a.text_bytes
+        nc = a.n_contigs
         self.k, self.read_bytes, self.n_contigs = a.k, a.read_bytes, nc
-        self.fasta = bytes(np.ctypeslib.as_array(a.text, (nb,))) if nb else b""
-        off = np.ctypeslib.as_array(a.contig_off, (nc,)).tolist() if nc else []
-        length = np.ctypeslib.as_array(a.contig_len, (nc,)).tolist() if nc else []
+        self.fasta = _text(a.text, a.text_bytes)
+        off, length = _array(a.contig_off, nc).tolist(), _array(a.contig_len, nc).tolist()
         self.contigs = [self.fasta[o:o + n].decode() for o, n in zip(off, length)]
         self.stats = ContigsStats(a.stats.n50, a.stats.l50, a.stats.n90, a.stats.ng50)
         self.collapse_stats = {f: getattr(a.collapse, f) for f, _ in _lib.CollapseStats._fields_}
 
-    def save_to_file(self, path):
-        """Contigs::save_to_file (asm/mod.rs:57-72; katome_assembly_save): a path that cannot be created raises KatomePanic(E_OPEN)"""
-        _check(_lib.lib().katome_assembly_save(self._ap, os.fsencode(path)))
 
-    def __del__(self):
-        try:
-            _lib.lib().katome_assembly_free(self._ap)
-        except Exception:       # interpreter shutdown
-            pass
-
-
-class Gfa:
+class Gfa(_COwned):
     """result of GpuGraph.gfa: the unitig graph as GFA 1 (include/katome_gpu.h has the format).  text: the file's bytes;
     segment_off[i]: offset of segment i's first base; link_first[a] .. link_first[a + 1]: the L lines of segment a.  Keeps the C
     result until it is collected."""
+    _free, _save = "katome_gfa_free", "katome_gfa_save"
 
     def __init__(self, gp):
+        super().__init__(gp)
         self._gp = gp
         g = gp.contents
         ns, nb = g.n_segments, g.text_bytes
         self.k, self.read_bytes, self.n_segments, self.n_links, self.text_bytes = g.k, g.read_bytes, ns, g.n_links, nb
-        self.text = bytes(np.ctypeslib.as_array(g.text, (nb,))) if nb else b""
-        self.segment_off = np.ctypeslib.as_array(g.segment_off, (ns,)).copy() if ns else np.zeros(0, np.uint64)
-        self.link_first = np.ctypeslib.as_array(g.link_first, (ns + 1,)).copy()
+        self.text = _text(g.text, nb + getattr(g, "path_bytes", 0))      # (with paths: their lines follow, and `text` is the whole file)
+        self.segment_off = _array(g.segment_off, ns)
+        self.link_first = _array(g.link_first, ns + 1)
 
-    def save_to_file(self, path):
-        """the text as a file (katome_gfa_save): a path that cannot be created raises KatomePanic(E_OPEN)"""
-        _check(_lib.lib().katome_gfa_save(self._gp, os.fsencode(path)))
-
-    def __del__(self):
-        try:
-            _lib.lib().katome_gfa_free(self._gp)
-        except Exception:       # interpreter shutdown
-            pass
+    def _strands(self, g):
+        """the fields of the merged form"""
+        self.n_edges, self.n_unpaired, self.n_self_twins = g.n_edges, g.n_unpaired, g.n_self_twins
+        self.segment_name = _array(g.segment_name, g.n_segments)
+        self.edge_twin = _array(g.edge_twin, g.n_edges)
 
 
 class GfaStrands(Gfa):
     """result of GpuGraph.gfa(merge_strands=True): the same with strand twins merged into one segment and +/- links.  S line s is
     merged edge segment_name[s]; edge_twin[i]: the merged edge that is edge i's reverse complement (2^64 - 1: none); n_edges merged
     edges, n_unpaired of them without a twin, n_self_twins their own"""
+    _free, _save = "katome_gfa_strands_free", "katome_gfa_strands_save"
 
     def __init__(self, gp):
         super().__init__(gp)
-        g = gp.contents
-        self.n_edges, self.n_unpaired, self.n_self_twins = g.n_edges, g.n_unpaired, g.n_self_twins
-        self.segment_name = np.ctypeslib.as_array(g.segment_name, (g.n_segments,)).copy() if g.n_segments else np.zeros(0, np.uint64)
-        self.edge_twin = np.ctypeslib.as_array(g.edge_twin, (g.n_edges,)).copy() if g.n_edges else np.zeros(0, np.uint64)
-
-    def save_to_file(self, path):
-        _check(_lib.lib().katome_gfa_strands_save(self._gp, os.fsencode(path)))
-
-    def __del__(self):
-        try:
-            _lib.lib().katome_gfa_strands_free(self._gp)
-        except Exception:       # interpreter shutdown
-            pass
+        self._strands(gp.contents)
 
 
 class GfaPaths(Gfa):
@@ -222,29 +229,17 @@ class GfaPaths(Gfa):
     link_first as in Gfa) and its contigs as P lines (path_text = text[text_bytes:], path_bytes of them): path j is the line at
     path_line_off[j] of path_text, a run of contig path_contig[j] whose first piece is piece path_first_piece[j]; n_jumps = n_paths
     - n_contigs.  `text` is the whole file"""
+    _free, _save = "katome_gfa_paths_free", "katome_gfa_paths_save"
 
     def __init__(self, gp):
-        self._gp = gp
+        super().__init__(gp)
         g = gp.contents
-        ns, nb, npaths = g.n_segments, g.text_bytes, g.n_paths
-        self.k, self.read_bytes, self.n_segments, self.n_links, self.text_bytes = g.k, g.read_bytes, ns, g.n_links, nb
+        npaths = g.n_paths
         self.n_paths, self.n_jumps, self.path_bytes = npaths, g.n_jumps, g.path_bytes
-        self.text = bytes(np.ctypeslib.as_array(g.text, (nb + g.path_bytes,))) if nb + g.path_bytes else b""
-        self.path_text = self.text[nb:]
-        self.segment_off = np.ctypeslib.as_array(g.segment_off, (ns,)).copy() if ns else np.zeros(0, np.uint64)
-        self.link_first = np.ctypeslib.as_array(g.link_first, (ns + 1,)).copy()
-        self.path_line_off = np.ctypeslib.as_array(g.path_line_off, (npaths + 1,)).copy()
-        self.path_contig = np.ctypeslib.as_array(g.path_contig, (npaths,)).copy() if npaths else np.zeros(0, np.uint64)
-        self.path_first_piece = np.ctypeslib.as_array(g.path_first_piece, (npaths + 1,)).copy()
-
-    def save_to_file(self, path):
-        _check(_lib.lib().katome_gfa_paths_save(self._gp, os.fsencode(path)))
-
-    def __del__(self):
-        try:
-            _lib.lib().katome_gfa_paths_free(self._gp)
-        except Exception:       # interpreter shutdown
-            pass
+        self.path_text = self.text[g.text_bytes:]
+        self.path_line_off = _array(g.path_line_off, npaths + 1)
+        self.path_contig = _array(g.path_contig, npaths)
+        self.path_first_piece = _array(g.path_first_piece, npaths + 1)
 
 
 class GfaStrandPaths(GfaPaths):
@@ -252,60 +247,40 @@ class GfaStrandPaths(GfaPaths):
     of GfaStrands) and its contigs as P lines over the merged segments (the fields of GfaPaths; a piece reads <rep><o>).
     path_mirror[j]: the smallest path that spells the same molecule from its other end (2^64 - 1: none); n_mirrored paths have
     one, n_self_mirror are their own"""
+    _free, _save = "katome_gfa_strand_paths_free", "katome_gfa_strand_paths_save"
 
     def __init__(self, gp):
         super().__init__(gp)
         g = gp.contents
-        self.n_edges, self.n_unpaired, self.n_self_twins = g.n_edges, g.n_unpaired, g.n_self_twins
-        self.segment_name = np.ctypeslib.as_array(g.segment_name, (g.n_segments,)).copy() if g.n_segments else np.zeros(0, np.uint64)
-        self.edge_twin = np.ctypeslib.as_array(g.edge_twin, (g.n_edges,)).copy() if g.n_edges else np.zeros(0, np.uint64)
+        self._strands(g)
         self.n_mirrored, self.n_self_mirror = g.n_mirrored, g.n_self_mirror
-        self.path_mirror = np.ctypeslib.as_array(g.path_mirror, (g.n_paths,)).copy() if g.n_paths else np.zeros(0, np.uint64)
+        self.path_mirror = _array(g.path_mirror, g.n_paths)
 
     def unique_paths(self):
         """the indices j with no mirror or mirror(j) >= j: one path per molecule"""
         return [j for j, q in enumerate(self.path_mirror.tolist()) if q == 2 ** 64 - 1 or q >= j]
 
-    def save_to_file(self, path):
-        _check(_lib.lib().katome_gfa_strand_paths_save(self._gp, os.fsencode(path)))
 
-    def __del__(self):
-        try:
-            _lib.lib().katome_gfa_strand_paths_free(self._gp)
-        except Exception:       # interpreter shutdown
-            pass
-
-
-class UniqueAssembly:
+class UniqueAssembly(_COwned):
     """the strand-unique half of GpuGraph.assemble_unique (include/katome_gpu.h, katome_dev_collapse_unique, has the definitions):
     contigs -- the kept ones, one strand per molecule with all its copies, as strings --, names -- their numbers in the full
     assembly, ascending --, contig_mirror[c] -- the smallest contig that spells c's molecule from its other end by pieces (2^64 - 1:
     none; n_mirrored have one, n_self_mirror are their own) --, stats -- Contigs::stats of the kept contigs -- and fasta, the kept
     records of the full FASTA byte for byte.  Keeps the C result until it is collected."""
+    _free, _save = "katome_unique_assembly_free", "katome_unique_assembly_save"
 
     def __init__(self, up):
-        self._up = up
+        super().__init__(up)
         u = up.contents
-        nk, nb = u.n_kept, u.text_bytes
+        nk = u.n_kept
         self.k, self.read_bytes, self.n_contigs, self.n_kept = u.k, u.read_bytes, u.n_contigs, nk
         self.n_mirrored, self.n_self_mirror = u.n_mirrored, u.n_self_mirror
-        self.fasta = bytes(np.ctypeslib.as_array(u.text, (nb,))) if nb else b""
-        self.contig_mirror = np.ctypeslib.as_array(u.contig_mirror, (u.n_contigs,)).copy() if u.n_contigs else np.zeros(0, np.uint64)
-        self.names = np.ctypeslib.as_array(u.kept_name, (nk,)).tolist() if nk else []
-        off = np.ctypeslib.as_array(u.kept_off, (nk,)).tolist() if nk else []
-        length = np.ctypeslib.as_array(u.kept_len, (nk,)).tolist() if nk else []
+        self.fasta = _text(u.text, u.text_bytes)
+        self.contig_mirror = _array(u.contig_mirror, u.n_contigs)
+        self.names = _array(u.kept_name, nk).tolist()
+        off, length = _array(u.kept_off, nk).tolist(), _array(u.kept_len, nk).tolist()
         self.contigs = [self.fasta[o:o + n].decode() for o, n in zip(off, length)]
         self.stats = ContigsStats(u.stats.n50, u.stats.l50, u.stats.n90, u.stats.ng50)
-
-    def save_to_file(self, path):
-        """the kept records as a FASTA file (katome_unique_assembly_save): a path that cannot be created raises KatomePanic(E_OPEN)"""
-        _check(_lib.lib().katome_unique_assembly_save(self._up, os.fsencode(path)))
-
-    def __del__(self):
-        try:
-            _lib.lib().katome_unique_assembly_free(self._up)
-        except Exception:       # interpreter shutdown
-            pass
 
 
 def _assemble_gfa_result(rc, ap, gp, cls=GfaPaths):
@@ -356,6 +331,34 @@ def _paths(paths):
     return (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
 
 
+def _enc(path):
+    return os.fsencode(path) if path is not None else None
+
+
+class _Reads:
+    """where a host entry's reads come from: every entry of the C ABI exists as katome_<entry>_files and katome_<entry>_packed,
+    which differ in the arguments between the settings and the entry's own.  Holds the arrays those arguments point into."""
+
+    def __init__(self, twin, *args, keep=None):
+        self.twin, self.args, self._keep = twin, args, keep
+
+    @classmethod
+    def files(cls, input_files):
+        return cls("files", _paths(input_files), len(input_files))
+
+    @classmethod
+    def packed(cls, packed, n_reads, read_len, skip):
+        """2-bit packed reads (numpy uint8) and, optionally, one byte per read: not 0 = leave the read out"""
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.uint8)
+        return cls("packed", packed.ctypes.data, n_reads, read_len, None if skip is None else skip.ctypes.data, keep=(packed, skip))
+
+    def call(self, symbol, settings, *tail):
+        """katome_<symbol with this source's word in it>(settings, the reads, *tail) -> status"""
+        return getattr(_lib.lib(), symbol.format(self.twin))(C.byref(settings), *self.args, *tail)
+
+
 class GpuGraph:
     """The collection the GPU build produces: what `Convert<GpuGIR> for PtGraph` consumes.
 
@@ -364,17 +367,9 @@ class GpuGraph:
     (k-1)-mers, [n, key_words] u64, most significant word first).
     """
 
-    class _Owner:
+    class _Owner(_COwned):
         """frees the katome_graph when the last array that views it is gone"""
-
-        def __init__(self, gptr):
-            self.gptr = gptr
-
-        def __del__(self):
-            try:
-                _lib.lib().katome_graph_free(self.gptr)
-            except Exception:       # interpreter shutdown
-                pass
+        _free = "katome_graph_free"
 
     def __init__(self, gptr):
         g = gptr.contents
@@ -404,6 +399,22 @@ class GpuGraph:
 
     # ---- Build::create (builder.rs:42-54) ----------------------------------------------------
     @classmethod
+    def _create(cls, reads, s, stages, original_genome_length, stage_stats):
+        gp = C.POINTER(_lib.Graph)()
+        described = None
+        if stage_stats:
+            described = (_lib.Stats * (len(stages or "") + 1))()
+            _check(reads.call("katome_build_{}_staged_stats", s, (stages or "").encode(), original_genome_length, described, C.byref(gp)))
+        elif stages:
+            _check(reads.call("katome_build_{}_staged", s, stages.encode(), original_genome_length, C.byref(gp)))
+        else:
+            _check(reads.call("katome_build_{}", s, C.byref(gp)))
+        g = cls(gp)                                   # the arrays view the C result and free it with their last reference
+        if described is not None:
+            g.stage_stats = [collection_stats(st) for st in described]
+        return g, g.read_bytes
+
+    @classmethod
     def create(cls, input_files, ft, reverse_complement, minimal_weight_threshold=0, device=0, first_seen_order=False,
                remove_dead_paths=False, stages=None, original_genome_length=0, n_devices=1, ranks_share_device=False,
                stage_stats=False):
@@ -420,21 +431,7 @@ class GpuGraph:
         s = make_settings(K_SIZE, ft, reverse_complement, minimal_weight_threshold, device,
                           first_seen_order=first_seen_order, remove_dead_paths=remove_dead_paths, n_devices=n_devices,
                           ranks_share_device=ranks_share_device)
-        gp = C.POINTER(_lib.Graph)()
-        described = None
-        if stage_stats:
-            described = (_lib.Stats * (len(stages or "") + 1))()
-            _check(_lib.lib().katome_build_files_staged_stats(C.byref(s), _paths(input_files), len(input_files), (stages or "").encode(),
-                                                              original_genome_length, described, C.byref(gp)))
-        elif stages:
-            _check(_lib.lib().katome_build_files_staged(C.byref(s), _paths(input_files), len(input_files), stages.encode(),
-                                                        original_genome_length, C.byref(gp)))
-        else:
-            _check(_lib.lib().katome_build_files(C.byref(s), _paths(input_files), len(input_files), C.byref(gp)))
-        g = cls(gp)                                   # the arrays view the C result and free it with their last reference
-        if described is not None:
-            g.stage_stats = [collection_stats(st) for st in described]
-        return g, g.read_bytes
+        return cls._create(_Reads.files(input_files), s, stages, original_genome_length, stage_stats)
 
     @classmethod
     def create_from_packed(cls, packed, n_reads, read_len, skip=None, reverse_complement=False, device=0, k=None,
@@ -447,28 +444,19 @@ class GpuGraph:
         s = make_settings(K_SIZE if k is None else k, InputFileType.Fastq, reverse_complement, minimal_weight_threshold, device,
                           table_slots_hint=table_slots_hint, first_seen_order=first_seen_order,
                           remove_dead_paths=remove_dead_paths, n_devices=n_devices, ranks_share_device=ranks_share_device)
-        packed = np.ascontiguousarray(packed, dtype=np.uint8)
-        skip_p = None
-        if skip is not None:
-            skip = np.ascontiguousarray(skip, dtype=np.uint8)
-            skip_p = skip.ctypes.data
-        gp = C.POINTER(_lib.Graph)()
-        described = None
-        if stage_stats:
-            described = (_lib.Stats * (len(stages or "") + 1))()
-            _check(_lib.lib().katome_build_packed_staged_stats(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p,
-                                                               (stages or "").encode(), original_genome_length, described, C.byref(gp)))
-        elif stages:
-            _check(_lib.lib().katome_build_packed_staged(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, stages.encode(),
-                                                         original_genome_length, C.byref(gp)))
-        else:
-            _check(_lib.lib().katome_build_packed(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, C.byref(gp)))
-        g = cls(gp)
-        if described is not None:
-            g.stage_stats = [collection_stats(st) for st in described]
-        return g, g.read_bytes
+        return cls._create(_Reads.packed(packed, n_reads, read_len, skip), s, stages, original_genome_length, stage_stats)
 
     # ---- BasicAsm::assemble (asm/basic_assembler.rs:17-27,58-80) ----------------------------------
+    @staticmethod
+    def _assemble(reads, s, original_genome_length, output_file):
+        ap = C.POINTER(_lib.Assembly)()
+        rc = reads.call("katome_assemble_{}", s, original_genome_length, _enc(output_file), C.byref(ap))
+        if rc != 0:
+            if ap:                      # (a path that could not be created: the assembly was made all the same)
+                _lib.lib().katome_assembly_free(ap)
+            _check(rc)
+        return Assembly(ap)
+
     @staticmethod
     def assemble(input_files, ft, reverse_complement, minimal_weight_threshold, original_genome_length, output_file=None, device=0,
                  n_devices=1, ranks_share_device=False):
@@ -476,14 +464,7 @@ class GpuGraph:
         Contigs::save_to_file, all behind one call (katome_assemble_files) -> Assembly; uses the global k"""
         s = make_settings(K_SIZE, ft, reverse_complement, minimal_weight_threshold, device, first_seen_order=True, n_devices=n_devices,
                           ranks_share_device=ranks_share_device)
-        ap = C.POINTER(_lib.Assembly)()
-        rc = _lib.lib().katome_assemble_files(C.byref(s), _paths(input_files), len(input_files), original_genome_length,
-                                              os.fsencode(output_file) if output_file is not None else None, C.byref(ap))
-        if rc != 0:
-            if ap:                      # (a path that could not be created: the assembly was made all the same)
-                _lib.lib().katome_assembly_free(ap)
-            _check(rc)
-        return Assembly(ap)
+        return GpuGraph._assemble(_Reads.files(input_files), s, original_genome_length, output_file)
 
     @staticmethod
     def assemble_from_packed(packed, n_reads, read_len, skip=None, reverse_complement=False, minimal_weight_threshold=0,
@@ -491,21 +472,20 @@ class GpuGraph:
         """the same from 2-bit packed reads (numpy uint8; katome_assemble_packed)"""
         s = make_settings(K_SIZE if k is None else k, InputFileType.Fastq, reverse_complement, minimal_weight_threshold, device,
                           first_seen_order=True, n_devices=n_devices, ranks_share_device=ranks_share_device)
-        packed = np.ascontiguousarray(packed, dtype=np.uint8)
-        skip_p = None
-        if skip is not None:
-            skip = np.ascontiguousarray(skip, dtype=np.uint8)
-            skip_p = skip.ctypes.data
-        ap = C.POINTER(_lib.Assembly)()
-        rc = _lib.lib().katome_assemble_packed(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, original_genome_length,
-                                               os.fsencode(output_file) if output_file is not None else None, C.byref(ap))
-        if rc != 0:
-            if ap:                      # (a path that could not be created: the assembly was made all the same)
-                _lib.lib().katome_assembly_free(ap)
-            _check(rc)
-        return Assembly(ap)
+        return GpuGraph._assemble(_Reads.packed(packed, n_reads, read_len, skip), s, original_genome_length, output_file)
 
-    # ---- the assembly and its GFA: the contigs as P lines over the unitigs -------------------------------
+    # ---- the assembly and a second form of it from the same collapse, each with a file of its own ---------
+    @staticmethod
+    def _assemble_with(reads, s, entry, struct, cls, original_genome_length, fasta_file, second_file):
+        ap, gp = C.POINTER(_lib.Assembly)(), C.POINTER(struct)()
+        rc = reads.call(entry, s, original_genome_length, _enc(fasta_file), _enc(second_file), C.byref(ap), C.byref(gp))
+        return _assemble_gfa_result(rc, ap, gp, cls)
+
+    _WITH_GFA = {False: ("katome_assemble_gfa_{}", _lib.GfaPaths, GfaPaths),
+                 True: ("katome_assemble_gfa_strands_{}", _lib.GfaStrandPaths, GfaStrandPaths)}
+    _WITH_UNIQUE = ("katome_assemble_unique_{}", _lib.UniqueAssembly, UniqueAssembly)
+
+    # the contigs as P lines over the unitigs
     @staticmethod
     def assemble_gfa(input_files, ft, reverse_complement, minimal_weight_threshold, original_genome_length, fasta_file=None, gfa_file=None,
                      device=0, n_devices=1, ranks_share_device=False, merge_strands=False):
@@ -515,16 +495,8 @@ class GpuGraph:
         (katome_assemble_gfa_strands_files) -> (Assembly, GfaStrandPaths)"""
         s = make_settings(K_SIZE, ft, reverse_complement, minimal_weight_threshold, device, first_seen_order=True, n_devices=n_devices,
                           ranks_share_device=ranks_share_device)
-        enc = lambda f: os.fsencode(f) if f is not None else None
-        if merge_strands:
-            ap, gp = C.POINTER(_lib.Assembly)(), C.POINTER(_lib.GfaStrandPaths)()
-            rc = _lib.lib().katome_assemble_gfa_strands_files(C.byref(s), _paths(input_files), len(input_files), original_genome_length,
-                                                              enc(fasta_file), enc(gfa_file), C.byref(ap), C.byref(gp))
-            return _assemble_gfa_result(rc, ap, gp, GfaStrandPaths)
-        ap, gp = C.POINTER(_lib.Assembly)(), C.POINTER(_lib.GfaPaths)()
-        rc = _lib.lib().katome_assemble_gfa_files(C.byref(s), _paths(input_files), len(input_files), original_genome_length, enc(fasta_file),
-                                                  enc(gfa_file), C.byref(ap), C.byref(gp))
-        return _assemble_gfa_result(rc, ap, gp)
+        return GpuGraph._assemble_with(_Reads.files(input_files), s, *GpuGraph._WITH_GFA[bool(merge_strands)], original_genome_length,
+                                       fasta_file, gfa_file)
 
     @staticmethod
     def assemble_gfa_from_packed(packed, n_reads, read_len, skip=None, reverse_complement=False, minimal_weight_threshold=0,
@@ -533,23 +505,10 @@ class GpuGraph:
         """the same from 2-bit packed reads (numpy uint8; katome_assemble_gfa_packed, katome_assemble_gfa_strands_packed)"""
         s = make_settings(K_SIZE if k is None else k, InputFileType.Fastq, reverse_complement, minimal_weight_threshold, device,
                           first_seen_order=True, n_devices=n_devices, ranks_share_device=ranks_share_device)
-        packed = np.ascontiguousarray(packed, dtype=np.uint8)
-        skip_p = None
-        if skip is not None:
-            skip = np.ascontiguousarray(skip, dtype=np.uint8)
-            skip_p = skip.ctypes.data
-        enc = lambda f: os.fsencode(f) if f is not None else None
-        if merge_strands:
-            ap, gp = C.POINTER(_lib.Assembly)(), C.POINTER(_lib.GfaStrandPaths)()
-            rc = _lib.lib().katome_assemble_gfa_strands_packed(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, original_genome_length,
-                                                               enc(fasta_file), enc(gfa_file), C.byref(ap), C.byref(gp))
-            return _assemble_gfa_result(rc, ap, gp, GfaStrandPaths)
-        ap, gp = C.POINTER(_lib.Assembly)(), C.POINTER(_lib.GfaPaths)()
-        rc = _lib.lib().katome_assemble_gfa_packed(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, original_genome_length,
-                                                   enc(fasta_file), enc(gfa_file), C.byref(ap), C.byref(gp))
-        return _assemble_gfa_result(rc, ap, gp)
+        return GpuGraph._assemble_with(_Reads.packed(packed, n_reads, read_len, skip), s, *GpuGraph._WITH_GFA[bool(merge_strands)],
+                                       original_genome_length, fasta_file, gfa_file)
 
-    # ---- the assembly and its strand-unique form: one FASTA record per molecule --------------------------
+    # the strand-unique form: one FASTA record per molecule
     @staticmethod
     def assemble_unique(input_files, ft, reverse_complement, minimal_weight_threshold, original_genome_length, fasta_file=None, unique_file=None,
                         device=0, n_devices=1, ranks_share_device=False):
@@ -558,11 +517,7 @@ class GpuGraph:
         UniqueAssembly); fasta_file: all contigs, unique_file: the kept ones; uses the global k"""
         s = make_settings(K_SIZE, ft, reverse_complement, minimal_weight_threshold, device, first_seen_order=True, n_devices=n_devices,
                           ranks_share_device=ranks_share_device)
-        enc = lambda f: os.fsencode(f) if f is not None else None
-        ap, up = C.POINTER(_lib.Assembly)(), C.POINTER(_lib.UniqueAssembly)()
-        rc = _lib.lib().katome_assemble_unique_files(C.byref(s), _paths(input_files), len(input_files), original_genome_length, enc(fasta_file),
-                                                     enc(unique_file), C.byref(ap), C.byref(up))
-        return _assemble_gfa_result(rc, ap, up, UniqueAssembly)
+        return GpuGraph._assemble_with(_Reads.files(input_files), s, *GpuGraph._WITH_UNIQUE, original_genome_length, fasta_file, unique_file)
 
     @staticmethod
     def assemble_unique_from_packed(packed, n_reads, read_len, skip=None, reverse_complement=False, minimal_weight_threshold=0,
@@ -571,18 +526,18 @@ class GpuGraph:
         """the same from 2-bit packed reads (numpy uint8; katome_assemble_unique_packed)"""
         s = make_settings(K_SIZE if k is None else k, InputFileType.Fastq, reverse_complement, minimal_weight_threshold, device,
                           first_seen_order=True, n_devices=n_devices, ranks_share_device=ranks_share_device)
-        packed = np.ascontiguousarray(packed, dtype=np.uint8)
-        skip_p = None
-        if skip is not None:
-            skip = np.ascontiguousarray(skip, dtype=np.uint8)
-            skip_p = skip.ctypes.data
-        enc = lambda f: os.fsencode(f) if f is not None else None
-        ap, up = C.POINTER(_lib.Assembly)(), C.POINTER(_lib.UniqueAssembly)()
-        rc = _lib.lib().katome_assemble_unique_packed(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, original_genome_length,
-                                                      enc(fasta_file), enc(unique_file), C.byref(ap), C.byref(up))
-        return _assemble_gfa_result(rc, ap, up, UniqueAssembly)
+        return GpuGraph._assemble_with(_Reads.packed(packed, n_reads, read_len, skip), s, *GpuGraph._WITH_UNIQUE, original_genome_length,
+                                       fasta_file, unique_file)
 
     # ---- the unitig graph as GFA 1 ---------------------------------------------------------------
+    @staticmethod
+    def _gfa(reads, s, stages, original_genome_length, output_file, merge_strands):
+        entry, struct, cls = (("katome_gfa_strands_{}", _lib.GfaStrands, GfaStrands) if merge_strands else
+                              ("katome_gfa_{}", _lib.Gfa, Gfa))
+        gp = C.POINTER(struct)()
+        rc = reads.call(entry, s, (stages or "").encode(), original_genome_length, _enc(output_file), C.byref(gp))
+        return _gfa_result(rc, gp, cls)
+
     @staticmethod
     def gfa(input_files, ft, reverse_complement, threshold, stages="", original_genome_length=0, output_file=None, device=0, n_devices=1,
             first_seen_order=None, ranks_share_device=False, merge_strands=False):
@@ -595,11 +550,7 @@ class GpuGraph:
             first_seen_order = bool(stages) or n_devices > 1
         s = make_settings(K_SIZE, ft, reverse_complement, threshold, device, first_seen_order=first_seen_order, n_devices=n_devices,
                           ranks_share_device=ranks_share_device)
-        gp = C.POINTER(_lib.GfaStrands if merge_strands else _lib.Gfa)()
-        entry = _lib.lib().katome_gfa_strands_files if merge_strands else _lib.lib().katome_gfa_files
-        rc = entry(C.byref(s), _paths(input_files), len(input_files), (stages or "").encode(), original_genome_length,
-                   os.fsencode(output_file) if output_file is not None else None, C.byref(gp))
-        return _gfa_result(rc, gp, GfaStrands if merge_strands else Gfa)
+        return GpuGraph._gfa(_Reads.files(input_files), s, stages, original_genome_length, output_file, merge_strands)
 
     @staticmethod
     def gfa_from_packed(packed, n_reads, read_len, skip=None, reverse_complement=False, threshold=0, stages="", original_genome_length=0,
@@ -609,16 +560,7 @@ class GpuGraph:
             first_seen_order = bool(stages) or n_devices > 1
         s = make_settings(K_SIZE if k is None else k, InputFileType.Fastq, reverse_complement, threshold, device,
                           first_seen_order=first_seen_order, n_devices=n_devices, ranks_share_device=ranks_share_device)
-        packed = np.ascontiguousarray(packed, dtype=np.uint8)
-        skip_p = None
-        if skip is not None:
-            skip = np.ascontiguousarray(skip, dtype=np.uint8)
-            skip_p = skip.ctypes.data
-        gp = C.POINTER(_lib.GfaStrands if merge_strands else _lib.Gfa)()
-        entry = _lib.lib().katome_gfa_strands_packed if merge_strands else _lib.lib().katome_gfa_packed
-        rc = entry(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, (stages or "").encode(),
-                   original_genome_length, os.fsencode(output_file) if output_file is not None else None, C.byref(gp))
-        return _gfa_result(rc, gp, GfaStrands if merge_strands else Gfa)
+        return GpuGraph._gfa(_Reads.packed(packed, n_reads, read_len, skip), s, stages, original_genome_length, output_file, merge_strands)
 
     # ---- Stats<CollectionStats> (stats/collections.rs:137-168) ---------------------------------
     def stats(self) -> CollectionStats:
@@ -656,20 +598,26 @@ class GpuContigs:
         c = cptr.contents
         ne, nn, nw = c.n_edges, c.n_nodes, c.key_words
         self.k, self.n_nodes, self.n_edges, self.read_bytes, self.key_words = c.k, nn, ne, c.read_bytes, nw
-
-        def arr(ptr, n, dtype):
-            return np.ctypeslib.as_array(ptr, (n,)).copy() if n else np.zeros(0, dtype)
-
-        self.edge_src, self.edge_dst = arr(c.edge_src, ne, np.uint64), arr(c.edge_dst, ne, np.uint64)
-        self.edge_weight, self.edge_kmers = arr(c.edge_weight, ne, np.uint32), arr(c.edge_kmers, ne, np.uint32)
-        self.edge_label_off = np.ctypeslib.as_array(c.edge_label_off, (ne + 1,)).copy()
-        self.edge_label = arr(c.edge_label, c.label_bytes, np.uint8)
-        self.node_key = arr(c.node_key, nn * nw, np.uint64).reshape(nn, nw)
+        self.edge_src, self.edge_dst = _array(c.edge_src, ne), _array(c.edge_dst, ne)
+        self.edge_weight, self.edge_kmers = _array(c.edge_weight, ne, np.uint32), _array(c.edge_kmers, ne, np.uint32)
+        self.edge_label_off = _array(c.edge_label_off, ne + 1)
+        self.edge_label = _array(c.edge_label, c.label_bytes, np.uint8)
+        self.node_key = _array(c.node_key, nn * nw).reshape(nn, nw)
         self.edge_seq = []
         for i in range(ne):
             b = self.edge_label[int(self.edge_label_off[i]):int(self.edge_label_off[i + 1])]
             bases = "".join("ACGT"[(int(x) >> sh) & 3] for x in b[1:] for sh in (6, 4, 2, 0))
             self.edge_seq.append(bases[:len(bases) - int(b[0])])
+
+    @classmethod
+    def _create(cls, reads, s):
+        cp = C.POINTER(_lib.Contigs)()
+        _check(reads.call("katome_shrink_{}", s, C.byref(cp)))
+        try:
+            c = cls(cp)
+        finally:
+            _lib.lib().katome_contigs_free(cp)
+        return c, c.read_bytes
 
     @classmethod
     def create(cls, input_files, ft, reverse_complement, minimal_weight_threshold=0, device=0, first_seen_order=False,
@@ -679,13 +627,7 @@ class GpuContigs:
         s = make_settings(K_SIZE, ft, reverse_complement, minimal_weight_threshold, device,
                           first_seen_order=first_seen_order, remove_dead_paths=remove_dead_paths, n_devices=n_devices,
                           ranks_share_device=ranks_share_device)
-        cp = C.POINTER(_lib.Contigs)()
-        _check(_lib.lib().katome_shrink_files(C.byref(s), _paths(input_files), len(input_files), C.byref(cp)))
-        try:
-            c = cls(cp)
-        finally:
-            _lib.lib().katome_contigs_free(cp)
-        return c, c.read_bytes
+        return cls._create(_Reads.files(input_files), s)
 
     @classmethod
     def create_from_packed(cls, packed, n_reads, read_len, skip=None, reverse_complement=False, device=0, k=None,
@@ -695,18 +637,7 @@ class GpuContigs:
         s = make_settings(K_SIZE if k is None else k, InputFileType.Fastq, reverse_complement, 0, device,
                           first_seen_order=first_seen_order, remove_dead_paths=remove_dead_paths, n_devices=n_devices,
                           ranks_share_device=ranks_share_device)
-        packed = np.ascontiguousarray(packed, dtype=np.uint8)
-        skip_p = None
-        if skip is not None:
-            skip = np.ascontiguousarray(skip, dtype=np.uint8)
-            skip_p = skip.ctypes.data
-        cp = C.POINTER(_lib.Contigs)()
-        _check(_lib.lib().katome_shrink_packed(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, C.byref(cp)))
-        try:
-            c = cls(cp)
-        finally:
-            _lib.lib().katome_contigs_free(cp)
-        return c, c.read_bytes
+        return cls._create(_Reads.packed(packed, n_reads, read_len, skip), s)
 
     def contigs(self):
         """sorted (sequence, weight): the parity observable"""
@@ -736,6 +667,13 @@ class GpuUnitigs:
         self.shrink = {f: getattr(u.shrink, f) for f, _ in _lib.DistShrinkStats._fields_}
 
     @staticmethod
+    def _run(reads, s, entry, struct, cls, stages, original_genome_length, output_file):
+        """a katome_unitigs*_ entry: the caller's plain struct filled in -> (cls of it, number_of_read_bytes)"""
+        u = struct()
+        _check(reads.call(entry, s, (stages or "").encode(), original_genome_length, _enc(output_file), C.byref(u)))
+        return cls(u), u.read_bytes
+
+    @staticmethod
     def gfa(input_files, ft, reverse_complement, minimal_weight_threshold=0, output_file=None, stages=None, original_genome_length=0,
             device=0, first_seen_order=False, remove_dead_paths=False, n_devices=1, ranks_share_device=False, coverage=False):
         """the same pipeline ending in the unitig GRAPH as a GFA 1 file (katome_unitigs_gfa_files): with n_devices > 1 the links are
@@ -745,11 +683,8 @@ class GpuUnitigs:
         s = make_settings(K_SIZE, ft, reverse_complement, minimal_weight_threshold, device, first_seen_order=first_seen_order,
                           remove_dead_paths=remove_dead_paths, n_devices=n_devices, ranks_share_device=ranks_share_device,
                           path_coverage=coverage)
-        u = _lib.UnitigsGfa()
-        _check(_lib.lib().katome_unitigs_gfa_files(C.byref(s), _paths(input_files), len(input_files), (stages or "").encode(),
-                                                   original_genome_length, os.fsencode(output_file) if output_file is not None else None,
-                                                   C.byref(u)))
-        return UnitigsGfa(u), u.read_bytes
+        return GpuUnitigs._run(_Reads.files(input_files), s, "katome_unitigs_gfa_{}", _lib.UnitigsGfa, UnitigsGfa, stages,
+                               original_genome_length, output_file)
 
     @staticmethod
     def gfa_from_packed(packed, n_reads, read_len, skip=None, reverse_complement=False, minimal_weight_threshold=0, output_file=None,
@@ -759,16 +694,8 @@ class GpuUnitigs:
         s = make_settings(K_SIZE if k is None else k, InputFileType.Fastq, reverse_complement, minimal_weight_threshold, device,
                           first_seen_order=first_seen_order, remove_dead_paths=remove_dead_paths, n_devices=n_devices,
                           ranks_share_device=ranks_share_device, path_coverage=coverage)
-        packed = np.ascontiguousarray(packed, dtype=np.uint8)
-        skip_p = None
-        if skip is not None:
-            skip = np.ascontiguousarray(skip, dtype=np.uint8)
-            skip_p = skip.ctypes.data
-        u = _lib.UnitigsGfa()
-        _check(_lib.lib().katome_unitigs_gfa_packed(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, (stages or "").encode(),
-                                                    original_genome_length, os.fsencode(output_file) if output_file is not None else None,
-                                                    C.byref(u)))
-        return UnitigsGfa(u), u.read_bytes
+        return GpuUnitigs._run(_Reads.packed(packed, n_reads, read_len, skip), s, "katome_unitigs_gfa_{}", _lib.UnitigsGfa, UnitigsGfa,
+                               stages, original_genome_length, output_file)
 
     @classmethod
     def create(cls, input_files, ft, reverse_complement, minimal_weight_threshold=0, output_file=None, stages=None,
@@ -777,11 +704,7 @@ class GpuUnitigs:
         """-> (GpuUnitigs, number_of_read_bytes); uses the global k.  stages / remove_dead_paths need first_seen_order"""
         s = make_settings(K_SIZE, ft, reverse_complement, minimal_weight_threshold, device, first_seen_order=first_seen_order,
                           remove_dead_paths=remove_dead_paths, n_devices=n_devices, ranks_share_device=ranks_share_device)
-        u = _lib.Unitigs()
-        _check(_lib.lib().katome_unitigs_files(C.byref(s), _paths(input_files), len(input_files), (stages or "").encode(),
-                                               original_genome_length, os.fsencode(output_file) if output_file is not None else None,
-                                               C.byref(u)))
-        return cls(u), u.read_bytes
+        return cls._run(_Reads.files(input_files), s, "katome_unitigs_{}", _lib.Unitigs, cls, stages, original_genome_length, output_file)
 
     @classmethod
     def create_from_packed(cls, packed, n_reads, read_len, skip=None, reverse_complement=False, minimal_weight_threshold=0,
@@ -791,16 +714,8 @@ class GpuUnitigs:
         s = make_settings(K_SIZE if k is None else k, InputFileType.Fastq, reverse_complement, minimal_weight_threshold, device,
                           first_seen_order=first_seen_order, remove_dead_paths=remove_dead_paths, n_devices=n_devices,
                           ranks_share_device=ranks_share_device)
-        packed = np.ascontiguousarray(packed, dtype=np.uint8)
-        skip_p = None
-        if skip is not None:
-            skip = np.ascontiguousarray(skip, dtype=np.uint8)
-            skip_p = skip.ctypes.data
-        u = _lib.Unitigs()
-        _check(_lib.lib().katome_unitigs_packed(C.byref(s), packed.ctypes.data, n_reads, read_len, skip_p, (stages or "").encode(),
-                                                original_genome_length, os.fsencode(output_file) if output_file is not None else None,
-                                                C.byref(u)))
-        return cls(u), u.read_bytes
+        return cls._run(_Reads.packed(packed, n_reads, read_len, skip), s, "katome_unitigs_{}", _lib.Unitigs, cls, stages,
+                        original_genome_length, output_file)
 
 
 def _int_to_kmer(v, k):

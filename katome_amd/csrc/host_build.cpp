@@ -1,6 +1,9 @@
 // host_build.cpp -- the host-memory half of the C ABI of include/katome_gpu.h: katome_build_packed*, katome_build_files*,
-// katome_shrink_*, katome_gfa_*, the host result arrays and the driver of a build over several GPUs.  No kernel is defined or launched here:
-// everything on the device goes through the device ABI (api.hip) and the sharded builder (dist*.hip).
+// katome_shrink_*, katome_assemble_*, katome_unitigs_*, katome_gfa_*, the host results and the driver of a build over several GPUs.
+// No kernel is defined or launched here: everything on the device goes through the device ABI (api.hip) and the sharded builder
+// (dist*.hip).  In the order of the file: the host results (one owner type, one copier), the endings (what a build hands back:
+// `Finish`), the build over several GPUs, the two read sources (packed reads, files) and the entries, each ending written once.
+#include <stddef.h>
 #include <stdlib.h>
 
 #include <algorithm>
@@ -12,6 +15,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include <sys/mman.h>
@@ -23,107 +27,29 @@
 #include "contig_stats.h"
 #include "multi_route.h"
 
-extern "C" {
-
-struct GraphOwner {            // katome_graph followed by what it owns
-    katome_graph g;
-    std::vector<void*> mem;
-};
-
-void katome_graph_free(katome_graph* g) {
-    if (!g) return;
-    GraphOwner* o = reinterpret_cast<GraphOwner*>(g);
+// ---- host results ------------------------------------------------------------------------------------------------------------
+// A result as the caller sees it, followed by what it owns: the arrays its pointers name, each released with free().  The
+// public struct comes first, so that the pointer the caller holds is also the pointer to the whole.
+template <class T> struct Owned { T v; std::vector<void*> mem; };
+template <class T> static Owned<T>* owner_of(T* v) {
+    static_assert(std::is_standard_layout<Owned<T>>::value && offsetof(Owned<T>, v) == 0, "a result's public struct is the first thing in its owner");
+    return reinterpret_cast<Owned<T>*>(v);
+}
+template <class T> static void free_result(T* v) {
+    if (!v) return;
+    Owned<T>* o = owner_of(v);
     for (void* p : o->mem) free(p);
     delete o;
 }
-
-struct ContigsOwner {          // katome_contigs followed by what it owns
-    katome_contigs c;
-    std::vector<void*> mem;
-};
-void katome_contigs_free(katome_contigs* c) {
-    if (!c) return;
-    ContigsOwner* o = reinterpret_cast<ContigsOwner*>(c);
-    for (void* p : o->mem) free(p);
-    delete o;
-}
-
-struct AssemblyOwner {         // katome_assembly followed by what it owns
-    katome_assembly a;
-    std::vector<void*> mem;
-};
-void katome_assembly_free(katome_assembly* a) {
-    if (!a) return;
-    AssemblyOwner* o = reinterpret_cast<AssemblyOwner*>(a);
-    for (void* p : o->mem) free(p);
-    delete o;
-}
-
-struct GfaOwner {              // katome_gfa followed by what it owns
-    katome_gfa g;
-    std::vector<void*> mem;
-};
-void katome_gfa_free(katome_gfa* g) {
-    if (!g) return;
-    GfaOwner* o = reinterpret_cast<GfaOwner*>(g);
-    for (void* p : o->mem) free(p);
-    delete o;
-}
-
-struct GfaStrandsOwner {       // katome_gfa_strands followed by what it owns
-    katome_gfa_strands g;
-    std::vector<void*> mem;
-};
-void katome_gfa_strands_free(katome_gfa_strands* g) {
-    if (!g) return;
-    GfaStrandsOwner* o = reinterpret_cast<GfaStrandsOwner*>(g);
-    for (void* p : o->mem) free(p);
-    delete o;
-}
-
-struct GfaPathsOwner {         // katome_gfa_paths followed by what it owns
-    katome_gfa_paths g;
-    std::vector<void*> mem;
-};
-void katome_gfa_paths_free(katome_gfa_paths* g) {
-    if (!g) return;
-    GfaPathsOwner* o = reinterpret_cast<GfaPathsOwner*>(g);
-    for (void* p : o->mem) free(p);
-    delete o;
-}
-
-struct GfaStrandPathsOwner {   // katome_gfa_strand_paths followed by what it owns
-    katome_gfa_strand_paths g;
-    std::vector<void*> mem;
-};
-void katome_gfa_strand_paths_free(katome_gfa_strand_paths* g) {
-    if (!g) return;
-    GfaStrandPathsOwner* o = reinterpret_cast<GfaStrandPathsOwner*>(g);
-    for (void* p : o->mem) free(p);
-    delete o;
-}
-
-struct UniqueAssemblyOwner {   // katome_unique_assembly followed by what it owns
-    katome_unique_assembly u;
-    std::vector<void*> mem;
-};
-void katome_unique_assembly_free(katome_unique_assembly* u) {
-    if (!u) return;
-    UniqueAssemblyOwner* o = reinterpret_cast<UniqueAssemblyOwner*>(u);
-    for (void* p : o->mem) free(p);
-    delete o;
-}
-
-}  // extern "C"
-
-// KATOME_TRACE_BUILD=1: wall time of the host entries' stages on stderr
-static void build_lap(const char* what, bool reset = false) {
-    static const bool on = getenv("KATOME_TRACE_BUILD") != nullptr;
-    static std::chrono::steady_clock::time_point last;
-    if (!on) return;
-    const auto now = std::chrono::steady_clock::now();
-    if (!reset) fprintf(stderr, "[build] %-28s %9.2f ms\n", what, std::chrono::duration<double, std::milli>(now - last).count());
-    last = now;
+// a result under construction: freed with everything it has taken so far unless it is release()d to the caller
+template <class T> struct ResultFree { void operator()(T* v) const { free_result(v); } };
+template <class T> using Result = std::unique_ptr<T, ResultFree<T>>;
+// a zeroed T that owns nothing yet (nullptr and the error set: out of host memory)
+template <class T> static Result<T> make_result() {
+    Owned<T>* o = new (std::nothrow) Owned<T>();
+    if (!o) { set_error("out of host memory"); return nullptr; }
+    memset(&o->v, 0, sizeof o->v);
+    return Result<T>(&o->v);
 }
 
 // Host memory for a result array.  A device -> host copy into pages the process has never touched runs at the rate one
@@ -157,10 +83,11 @@ static void* host_result_alloc(size_t bytes) {
     return p;
 }
 
-// room for a result array of `bytes` bytes, recorded in the owner that will free it (nullptr and *oom set: out of host memory)
-template <class Owner> static void* take(Owner* o, size_t bytes, bool* oom, bool touch = true) {
+// room for an array of `bytes` bytes of the result `v`, recorded in its owner, which will free it (nullptr and *oom set: out of
+// host memory)
+template <class T> static void* take(T* v, size_t bytes, bool* oom, bool touch = true) {
     void* p = touch ? host_result_alloc(bytes) : host_result_reserve(bytes);
-    if (p) o->mem.push_back(p); else *oom = true;
+    if (p) owner_of(v)->mem.push_back(p); else *oom = true;
     return p;
 }
 
@@ -188,13 +115,119 @@ static int d2h_all(const std::vector<HostCopy>& jobs) {
     return rc;
 }
 
-template <class T, class Owner> static int d2h(Owner* o, const T** dst, const void* d_src, size_t count) {
+// `count` elements from the device into an array of the result `v`; a count of 0 still gets room for one element
+template <class E, class T> static int d2h(T* v, const E** dst, const void* d_src, size_t count) {
     bool oom = false;
-    T* h = (T*)take(o, std::max<size_t>(count, 1) * sizeof(T), &oom);
+    E* h = (E*)take(v, std::max<size_t>(count, 1) * sizeof(E), &oom);
     if (oom) { set_error("out of host memory"); return KATOME_E_OOM; }
-    if (count) KCHECK_HIP(hipMemcpy(h, d_src, count * sizeof(T), hipMemcpyDeviceToHost));
+    if (count) KCHECK_HIP(hipMemcpy(h, d_src, count * sizeof(E), hipMemcpyDeviceToHost));
     *dst = h;
     return KATOME_OK;
+}
+
+// The arrays of one result, copied down one after the other: the first failure is kept in `rc` and everything after it skipped.
+template <class T> struct Copier {
+    T* v; int rc = KATOME_OK;
+    template <class E> void operator()(const E** dst, const void* d_src, size_t count) { if (!rc) rc = d2h(v, dst, d_src, count); }
+    // two texts back to back in one array, `first` then `second` (a GFA's lines and its P lines: together they are the file)
+    void back_to_back(const uint8_t** dst, const void* d_first, uint64_t first, const void* d_second, uint64_t second) {
+        if (rc) return;
+        bool oom = false;
+        uint8_t* text = (uint8_t*)take(v, std::max<uint64_t>(first + second, 1), &oom);
+        if (oom) { set_error("out of host memory"); rc = KATOME_E_OOM; return; }
+        if ((first && hipMemcpy(text, d_first, first, hipMemcpyDeviceToHost) != hipSuccess) ||
+            (second && hipMemcpy(text + first, d_second, second, hipMemcpyDeviceToHost) != hipSuccess)) {
+            set_error("device -> host copy failed: %s", hipGetErrorString(hipGetLastError()));
+            rc = KATOME_E_DEVICE;
+        }
+        *dst = text;
+    }
+};
+
+extern "C" {      // (every katome_*_free of the header is the one free_result)
+void katome_graph_free(katome_graph* g) { free_result(g); }
+void katome_contigs_free(katome_contigs* c) { free_result(c); }
+void katome_assembly_free(katome_assembly* a) { free_result(a); }
+void katome_unique_assembly_free(katome_unique_assembly* u) { free_result(u); }
+void katome_gfa_free(katome_gfa* g) { free_result(g); }
+void katome_gfa_strands_free(katome_gfa_strands* g) { free_result(g); }
+void katome_gfa_paths_free(katome_gfa_paths* g) { free_result(g); }
+void katome_gfa_strand_paths_free(katome_gfa_strand_paths* g) { free_result(g); }
+}  // extern "C"
+
+#ifndef KATOME_HOST_RESULTS_ONLY      // (tests/hostshim/host_results_selftest.cpp builds the part above for the host alone)
+
+// One result of a build and its file: the result is handed out before the file is tried, so that a path that cannot be created
+// leaves the caller with the result all the same; a caller who did not ask for the result does not get one to free.
+template <class T> static int hand_out(Result<T> r, T** out, const char* path, int (*save)(const T*, const char*)) {
+    if (out) *out = r.get();
+    const int rc = path ? save(r.get(), path) : KATOME_OK;
+    if (out) (void)r.release();
+    return rc;
+}
+// Two results of one build and their two files, the assembly's FASTA first: both results are handed out before any file is
+// tried, both files are tried, and the first failure is the one reported.
+template <class T> static int hand_out_both(Result<katome_assembly> a, katome_assembly** a_out, const char* a_path, Result<T> r, T** out,
+                                            const char* path, int (*save)(const T*, const char*)) {
+    if (a_out) *a_out = a.get();
+    if (out) *out = r.get();
+    int rc = a_path ? katome_assembly_save(a.get(), a_path) : KATOME_OK;
+    const std::string first_err = rc ? get_error() : "";
+    const int rc_second = path ? save(r.get(), path) : KATOME_OK;
+    if (rc) set_error("%s", first_err.c_str()); else rc = rc_second;
+    if (a_out) (void)a.release();
+    if (out) (void)r.release();
+    return rc;
+}
+
+// these host bytes as a file, with File::create's statuses and message (asm/mod.rs:62); what a failed write leaves stays
+static int save_host_text(const uint8_t* text, uint64_t bytes, const char* path) {
+    FILE* f = fopen(path, "wb");
+    if (!f) {
+        set_error("couldn't create %s: %s", path, CREATE_ERROR_KINDS[create_error_kind(errno)]);
+        return KATOME_E_OPEN;
+    }
+    const size_t n = bytes ? fwrite(text, 1, bytes, f) : 0;
+    if (fclose(f) != 0 || n != bytes) { set_error("couldn't write %s", path); return KATOME_E_OPEN; }
+    return KATOME_OK;
+}
+// katome_*_save: the result's text is the file (the two parts of a GFA with paths are contiguous on the host)
+template <class T> static uint64_t file_bytes(const T& v) { return v.text_bytes; }
+static uint64_t file_bytes(const katome_gfa_paths& g) { return g.text_bytes + g.path_bytes; }
+static uint64_t file_bytes(const katome_gfa_strand_paths& g) { return g.text_bytes + g.path_bytes; }
+template <class T> static int save_result(const T* v, const char* path) {
+    if (!v || !path) { set_error("null argument"); return KATOME_E_ARG; }
+    return save_host_text(v->text, file_bytes(*v), path);
+}
+extern "C" {
+// Contigs::save_to_file (asm/mod.rs:57-72): the text in FASTA layout is the file
+int katome_assembly_save(const katome_assembly* a, const char* path) {
+    if (a && path && a->layout != KATOME_TEXT_FASTA) { set_error("assembly_save: the text is not in FASTA layout"); return KATOME_E_ARG; }
+    return save_result(a, path);
+}
+int katome_unique_assembly_save(const katome_unique_assembly* u, const char* path) { return save_result(u, path); }
+int katome_gfa_save(const katome_gfa* g, const char* path) { return save_result(g, path); }
+int katome_gfa_strands_save(const katome_gfa_strands* g, const char* path) { return save_result(g, path); }
+int katome_gfa_paths_save(const katome_gfa_paths* g, const char* path) { return save_result(g, path); }
+int katome_gfa_strand_paths_save(const katome_gfa_strand_paths* g, const char* path) { return save_result(g, path); }
+
+int katome_contig_stats_of(const uint64_t* lengths, uint64_t n, uint64_t original_genome_length, katome_contig_stats* out) {
+    if (!out || (n && !lengths)) { set_error("null argument"); return KATOME_E_ARG; }
+    ContigStats st;
+    const int which = contig_stats(lengths, n, original_genome_length, &st);
+    out->n50 = st.n50; out->l50 = st.l50; out->n90 = st.n90; out->ng50 = st.ng50;
+    return contig_stats_status(which);
+}
+}  // extern "C"
+
+// KATOME_TRACE_BUILD=1: wall time of the host entries' stages on stderr
+static void build_lap(const char* what, bool reset = false) {
+    static const bool on = getenv("KATOME_TRACE_BUILD") != nullptr;
+    static std::chrono::steady_clock::time_point last;
+    if (!on) return;
+    const auto now = std::chrono::steady_clock::now();
+    if (!reset) fprintf(stderr, "[build] %-28s %9.2f ms\n", what, std::chrono::duration<double, std::milli>(now - last).count());
+    last = now;
 }
 
 // these device -> host copies queued on `stream`, then the stream synchronised; the first failure is the one reported
@@ -211,21 +244,19 @@ static int copy_down(std::initializer_list<StreamCopy> jobs, hipStream_t stream)
 // A katome_graph of the given totals: its header filled in and its arrays reserved, their pages not touched yet.  `arrays`
 // lists them in the order edge_src, edge_dst, edge_weight, edge_label, edge_key, node_key and, with `ages`, edge_age.
 static int new_host_graph(uint64_t n_nodes, uint64_t n_edges, uint32_t k, uint32_t key_words, uint32_t label_stride, bool ages,
-                          uint64_t read_bytes, GraphOwner** out, std::vector<HostCopy>& arrays) {
-    GraphOwner* o = new (std::nothrow) GraphOwner();
-    if (!o) { set_error("out of host memory"); return KATOME_E_OOM; }
-    memset(&o->g, 0, sizeof o->g);
-    katome_graph* g = &o->g;
+                          uint64_t read_bytes, Result<katome_graph>& out, std::vector<HostCopy>& arrays) {
+    Result<katome_graph> g = make_result<katome_graph>();
+    if (!g) return KATOME_E_OOM;
     g->n_nodes = n_nodes; g->n_edges = n_edges; g->read_bytes = read_bytes;
     g->k = k; g->key_words = key_words; g->label_stride = label_stride;
     bool oom = false;
-    auto room = [&](size_t bytes) { arrays.push_back({take(o, bytes, &oom, false), bytes, nullptr}); return arrays.back().h; };
+    auto room = [&](size_t bytes) { arrays.push_back({take(g.get(), bytes, &oom, false), bytes, nullptr}); return arrays.back().h; };
     g->edge_src = (uint64_t*)room(n_edges * 8); g->edge_dst = (uint64_t*)room(n_edges * 8);
     g->edge_weight = (uint32_t*)room(n_edges * 4); g->edge_label = (uint8_t*)room(n_edges * (size_t)label_stride);
     g->edge_key = (uint64_t*)room(n_edges * 8 * (size_t)key_words); g->node_key = (uint64_t*)room(n_nodes * 8 * (size_t)key_words);
     if (ages) g->edge_age = (uint32_t*)room(n_edges * 4);
-    if (oom) { katome_graph_free(g); set_error("out of host memory"); return KATOME_E_OOM; }
-    *out = o;
+    if (oom) { set_error("out of host memory"); return KATOME_E_OOM; }
+    out = std::move(g);
     return KATOME_OK;
 }
 
@@ -265,252 +296,218 @@ template <class Ops, class Hook = NoStageHook> static int run_stages(const char*
     return KATOME_OK;
 }
 
-// (stage_stats: the caller's strlen(stages) + 1 entries, filled on the device as the stages go by)
-static int graph_to_host(katome_builder* b, uint64_t read_bytes, katome_graph** out, const char* stages = nullptr, uint64_t genome_len = 0,
-                         katome_stats* stage_stats = nullptr) {
+// ---- the endings on one GPU ----------------------------------------------------------------------------------------------------
+// What every ending starts with: finalize, the pruning the flag asks for, the stage letters
+template <class Hook = NoStageHook> static int prepare(katome_builder* b, const char* stages, uint64_t genome_len, const Hook& at_stage = Hook()) {
     katome_dev_graph dg;
-    if (stages && *stages && !b->first_seen) { set_error("stages after the build need KATOME_FLAG_FIRST_SEEN_ORDER"); return KATOME_E_ARG; }
     build_lap("counting (H2D, kernels)");
     KCHECK(katome_dev_finalize(b, &dg, nullptr));
     build_lap("finalize");
     if (b->s.flags & KATOME_FLAG_REMOVE_DEAD_PATHS) KCHECK(katome_dev_remove_dead_paths(b, &dg, nullptr, nullptr));
-    KCHECK(run_stages(stages, BuilderStages{b, genome_len},
-                      [&](size_t i) { return stage_stats ? katome_dev_graph_stats(b, &stage_stats[i], nullptr) : KATOME_OK; }));
-    KCHECK(katome_dev_current_graph(b, &dg));
+    KCHECK(run_stages(stages, BuilderStages{b, genome_len}, at_stage));
     build_lap("stages after the build");
-    GraphOwner* o = nullptr;
+    return KATOME_OK;
+}
+// (the stages work on the links of a first-seen build)
+static int stages_need_order(bool first_seen, const char* stages) {
+    if (first_seen || !stages || !*stages) return KATOME_OK;
+    set_error("stages after the build need KATOME_FLAG_FIRST_SEEN_ORDER");
+    return KATOME_E_ARG;
+}
+
+// (stage_stats: the caller's strlen(stages) + 1 entries, filled on the device as the stages go by)
+static int graph_to_host(katome_builder* b, uint64_t read_bytes, katome_graph** out, const char* stages, uint64_t genome_len, katome_stats* stage_stats) {
+    KCHECK(stages_need_order(b->first_seen, stages));
+    KCHECK(prepare(b, stages, genome_len, [&](size_t i) { return stage_stats ? katome_dev_graph_stats(b, &stage_stats[i], nullptr) : KATOME_OK; }));
+    katome_dev_graph dg;
+    KCHECK(katome_dev_current_graph(b, &dg));
+    Result<katome_graph> g;
     std::vector<HostCopy> jobs;
-    KCHECK(new_host_graph(dg.n_nodes, dg.n_edges, b->s.k, dg.key_words, dg.label_stride, dg.d_edge_age != nullptr, read_bytes, &o, jobs));
+    KCHECK(new_host_graph(dg.n_nodes, dg.n_edges, b->s.k, dg.key_words, dg.label_stride, dg.d_edge_age != nullptr, read_bytes, g, jobs));
     const void* from[] = {dg.d_edge_src, dg.d_edge_dst, dg.d_edge_weight, dg.d_edge_label, dg.d_edge_key, dg.d_node_key, dg.d_edge_age};
     for (size_t i = 0; i < jobs.size(); ++i) jobs[i].src = from[i];
-    const int rc = d2h_all(jobs);
-    if (rc) { katome_graph_free(&o->g); return rc; }
+    KCHECK(d2h_all(jobs));
     build_lap("graph to host arrays");
-    *out = &o->g;
+    *out = g.release();
     return KATOME_OK;
 }
 
 // finalize (+ the pruning the flags ask for) + shrink, copied to host arrays
-static int contigs_to_host(katome_builder* b, uint64_t read_bytes, katome_contigs** out, uint32_t shrink_mode = KATOME_SHRINK_AUTO) {
-    katome_dev_graph dg;
-    KCHECK(katome_dev_finalize(b, &dg, nullptr));
-    if (b->s.flags & KATOME_FLAG_REMOVE_DEAD_PATHS) KCHECK(katome_dev_remove_dead_paths(b, &dg, nullptr, nullptr));
+static int contigs_to_host(katome_builder* b, uint64_t read_bytes, katome_contigs** out, uint32_t shrink_mode) {
+    KCHECK(prepare(b, nullptr, 0));
     katome_dev_contigs dc;
     KCHECK(katome_dev_shrink_mode(b, shrink_mode, &dc, nullptr, nullptr));
-    ContigsOwner* o = new (std::nothrow) ContigsOwner();
-    if (!o) { set_error("out of host memory"); return KATOME_E_OOM; }
-    memset(&o->c, 0, sizeof o->c);
-    katome_contigs* c = &o->c;
+    Result<katome_contigs> c = make_result<katome_contigs>();
+    if (!c) return KATOME_E_OOM;
     c->n_nodes = dc.n_nodes; c->n_edges = dc.n_edges; c->label_bytes = dc.label_bytes; c->read_bytes = read_bytes;
     c->k = b->s.k; c->key_words = dc.key_words;
-    int rc = KATOME_OK;
-    if ((rc = d2h(o, &c->edge_src, dc.d_edge_src, dc.n_edges)) || (rc = d2h(o, &c->edge_dst, dc.d_edge_dst, dc.n_edges)) ||
-        (rc = d2h(o, &c->edge_weight, dc.d_edge_weight, dc.n_edges)) || (rc = d2h(o, &c->edge_kmers, dc.d_edge_kmers, dc.n_edges)) ||
-        (rc = d2h(o, &c->edge_label_off, dc.d_edge_label_off, dc.n_edges ? dc.n_edges + 1 : 0)) ||
-        (rc = d2h(o, &c->edge_label, dc.d_edge_label, dc.label_bytes)) ||
-        (rc = d2h(o, &c->node_key, dc.d_node_key, dc.n_nodes * dc.key_words))) {
-        katome_contigs_free(c);
-        return rc;
-    }
+    Copier<katome_contigs> down{c.get()};
+    down(&c->edge_src, dc.d_edge_src, dc.n_edges);
+    down(&c->edge_dst, dc.d_edge_dst, dc.n_edges);
+    down(&c->edge_weight, dc.d_edge_weight, dc.n_edges);
+    down(&c->edge_kmers, dc.d_edge_kmers, dc.n_edges);
+    down(&c->edge_label_off, dc.d_edge_label_off, dc.n_edges ? dc.n_edges + 1 : 0);
+    down(&c->edge_label, dc.d_edge_label, dc.label_bytes);
+    down(&c->node_key, dc.d_node_key, dc.n_nodes * dc.key_words);
+    KCHECK(down.rc);
     if (dc.n_edges == 0) const_cast<uint64_t*>(c->edge_label_off)[0] = 0;       // (d2h hands out room for one entry even when asked for none)
-    *out = c;
+    *out = c.release();
     return KATOME_OK;
 }
 
-extern "C" int katome_contig_stats_of(const uint64_t* lengths, uint64_t n, uint64_t original_genome_length, katome_contig_stats* out) {
-    if (!out || (n && !lengths)) { set_error("null argument"); return KATOME_E_ARG; }
-    ContigStats st;
-    const int which = contig_stats(lengths, n, original_genome_length, &st);
-    out->n50 = st.n50; out->l50 = st.l50; out->n90 = st.n90; out->ng50 = st.ng50;
-    return contig_stats_status(which);
+// The GFA family.  A host struct katome_gfa* and the device struct katome_dev_gfa* it is copied from name their fields alike, and
+// the four forms are made of three blocks: the segments (all four), the merged strands, the paths.
+template <class H, class D> static void segments_block(Copier<H>& down, const D& d, uint32_t k, uint64_t read_bytes) {
+    H* g = down.v;
+    g->n_segments = d.n_segments; g->n_links = d.n_links; g->text_bytes = d.text_bytes; g->read_bytes = read_bytes; g->k = k;
+    down(&g->segment_off, d.d_segment_off, d.n_segments);
+    down(&g->link_first, d.d_link_first, d.n_segments + 1);
+}
+// (n_edges: the merged edges the twins were sought among)
+template <class H, class D> static void strands_block(Copier<H>& down, const D& d, uint64_t n_edges) {
+    H* g = down.v;
+    g->n_edges = n_edges; g->n_unpaired = d.n_unpaired; g->n_self_twins = d.n_self_twins;
+    down(&g->segment_name, d.d_segment_name, d.n_segments);
+    down(&g->edge_twin, d.d_edge_twin, n_edges);
+}
+// (the text: the H, S and L lines and, straight after them, the P lines)
+template <class H, class D> static void paths_block(Copier<H>& down, const D& d) {
+    H* g = down.v;
+    g->n_paths = d.n_paths; g->n_jumps = d.n_jumps; g->path_bytes = d.path_bytes;
+    down.back_to_back(&g->text, d.d_text, d.text_bytes, d.d_path_text, d.path_bytes);
+    down(&g->path_line_off, d.d_path_line_off, d.n_paths + 1);
+    down(&g->path_contig, d.d_path_contig, d.n_paths);
+    down(&g->path_first_piece, d.d_path_first_piece, d.n_paths + 1);
 }
 
-// Contigs::save_to_file (asm/mod.rs:57-72): the text in FASTA layout is the file
-extern "C" int katome_assembly_save(const katome_assembly* a, const char* path) {
-    if (!a || !path) { set_error("null argument"); return KATOME_E_ARG; }
-    if (a->layout != KATOME_TEXT_FASTA) { set_error("assembly_save: the text is not in FASTA layout"); return KATOME_E_ARG; }
-    FILE* f = fopen(path, "wb");
-    if (!f) {
-        set_error("couldn't create %s: %s", path, CREATE_ERROR_KINDS[create_error_kind(errno)]);      // asm/mod.rs:62
-        return KATOME_E_OPEN;
-    }
-    const size_t n = a->text_bytes ? fwrite(a->text, 1, a->text_bytes, f) : 0;
-    if (fclose(f) != 0 || n != a->text_bytes) { set_error("couldn't write %s", path); return KATOME_E_OPEN; }
-    return KATOME_OK;
+// katome_dev_contigs_gfa of a shrunk graph in host arrays
+static int gfa_to_host(katome_builder* b, const katome_dev_contigs& dc, uint64_t read_bytes, Result<katome_gfa>& out) {
+    katome_dev_gfa d;
+    KCHECK(katome_dev_contigs_gfa(b, &dc, &d, nullptr));
+    if (!(out = make_result<katome_gfa>())) return KATOME_E_OOM;
+    Copier<katome_gfa> down{out.get()};
+    down(&out->text, d.d_text, d.text_bytes);
+    segments_block(down, d, b->s.k, read_bytes);
+    return down.rc;
 }
-
-static int save_gfa_text(const uint8_t* text, uint64_t text_bytes, const char* path);
-extern "C" int katome_gfa_paths_save(const katome_gfa_paths* g, const char* path) {
-    if (!g || !path) { set_error("null argument"); return KATOME_E_ARG; }
-    return save_gfa_text(g->text, g->text_bytes + g->path_bytes, path);      // (the two parts are contiguous on the host)
+// katome_dev_contigs_gfa_strands of a shrunk graph in host arrays
+static int gfa_strands_to_host(katome_builder* b, const katome_dev_contigs& dc, uint64_t read_bytes, Result<katome_gfa_strands>& out) {
+    katome_dev_gfa_strands d;
+    KCHECK(katome_dev_contigs_gfa_strands(b, &dc, &d, nullptr));
+    if (!(out = make_result<katome_gfa_strands>())) return KATOME_E_OOM;
+    Copier<katome_gfa_strands> down{out.get()};
+    down(&out->text, d.d_text, d.text_bytes);
+    segments_block(down, d, b->s.k, read_bytes);
+    strands_block(down, d, dc.n_edges);
+    return down.rc;
 }
-// katome_dev_collapse_gfa of the builder's last collapse in host arrays: the two parts of the text back to back
-static int gfa_paths_to_host(katome_builder* b, uint64_t read_bytes, katome_gfa_paths** out) {
+// katome_dev_collapse_gfa of the builder's last collapse in host arrays
+static int gfa_paths_to_host(katome_builder* b, uint64_t read_bytes, Result<katome_gfa_paths>& out) {
     katome_dev_gfa_paths d;
     KCHECK(katome_dev_collapse_gfa(b, &d, nullptr));
-    GfaPathsOwner* o = new (std::nothrow) GfaPathsOwner();
-    if (!o) { set_error("out of host memory"); return KATOME_E_OOM; }
-    memset(&o->g, 0, sizeof o->g);
-    katome_gfa_paths* g = &o->g;
-    g->n_segments = d.n_segments; g->n_links = d.n_links; g->text_bytes = d.text_bytes; g->read_bytes = read_bytes; g->k = b->s.k;
-    g->n_paths = d.n_paths; g->n_jumps = d.n_jumps; g->path_bytes = d.path_bytes;
-    bool oom = false;
-    uint8_t* text = (uint8_t*)take(o, std::max<uint64_t>(d.text_bytes + d.path_bytes, 1), &oom);
-    int rc = KATOME_OK;
-    if (oom) { set_error("out of host memory"); rc = KATOME_E_OOM; }
-    if (!rc && d.text_bytes && hipMemcpy(text, d.d_text, d.text_bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = KATOME_E_DEVICE;
-    if (!rc && d.path_bytes && hipMemcpy(text + d.text_bytes, d.d_path_text, d.path_bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = KATOME_E_DEVICE;
-    if (rc == KATOME_E_DEVICE) set_error("device -> host copy failed: %s", hipGetErrorString(hipGetLastError()));
-    g->text = text;
-    if (!rc) rc = d2h(o, &g->segment_off, d.d_segment_off, d.n_segments);
-    if (!rc) rc = d2h(o, &g->link_first, d.d_link_first, d.n_segments + 1);
-    if (!rc) rc = d2h(o, &g->path_line_off, d.d_path_line_off, d.n_paths + 1);
-    if (!rc) rc = d2h(o, &g->path_contig, d.d_path_contig, d.n_paths);
-    if (!rc) rc = d2h(o, &g->path_first_piece, d.d_path_first_piece, d.n_paths + 1);
-    if (rc) { katome_gfa_paths_free(g); return rc; }
-    *out = g;
-    return KATOME_OK;
+    if (!(out = make_result<katome_gfa_paths>())) return KATOME_E_OOM;
+    Copier<katome_gfa_paths> down{out.get()};
+    paths_block(down, d);
+    segments_block(down, d, b->s.k, read_bytes);
+    return down.rc;
 }
-
-extern "C" int katome_gfa_strand_paths_save(const katome_gfa_strand_paths* g, const char* path) {
-    if (!g || !path) { set_error("null argument"); return KATOME_E_ARG; }
-    return save_gfa_text(g->text, g->text_bytes + g->path_bytes, path);      // (the two parts are contiguous on the host)
-}
-// katome_dev_collapse_gfa_strands of the builder's last collapse in host arrays: the two parts of the text back to back
-static int gfa_strand_paths_to_host(katome_builder* b, uint64_t read_bytes, katome_gfa_strand_paths** out) {
+// katome_dev_collapse_gfa_strands of the builder's last collapse in host arrays
+static int gfa_strand_paths_to_host(katome_builder* b, uint64_t read_bytes, Result<katome_gfa_strand_paths>& out) {
     katome_dev_gfa_strand_paths d;
     KCHECK(katome_dev_collapse_gfa_strands(b, &d, nullptr));
-    GfaStrandPathsOwner* o = new (std::nothrow) GfaStrandPathsOwner();
-    if (!o) { set_error("out of host memory"); return KATOME_E_OOM; }
-    memset(&o->g, 0, sizeof o->g);
-    katome_gfa_strand_paths* g = &o->g;
-    g->n_segments = d.n_segments; g->n_links = d.n_links; g->text_bytes = d.text_bytes; g->read_bytes = read_bytes; g->k = b->s.k;
-    g->n_edges = d.n_edges; g->n_unpaired = d.n_unpaired; g->n_self_twins = d.n_self_twins;
-    g->n_paths = d.n_paths; g->n_jumps = d.n_jumps; g->path_bytes = d.path_bytes; g->n_mirrored = d.n_mirrored; g->n_self_mirror = d.n_self_mirror;
-    bool oom = false;
-    uint8_t* text = (uint8_t*)take(o, std::max<uint64_t>(d.text_bytes + d.path_bytes, 1), &oom);
-    int rc = KATOME_OK;
-    if (oom) { set_error("out of host memory"); rc = KATOME_E_OOM; }
-    if (!rc && d.text_bytes && hipMemcpy(text, d.d_text, d.text_bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = KATOME_E_DEVICE;
-    if (!rc && d.path_bytes && hipMemcpy(text + d.text_bytes, d.d_path_text, d.path_bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = KATOME_E_DEVICE;
-    if (rc == KATOME_E_DEVICE) set_error("device -> host copy failed: %s", hipGetErrorString(hipGetLastError()));
-    g->text = text;
-    if (!rc) rc = d2h(o, &g->segment_off, d.d_segment_off, d.n_segments);
-    if (!rc) rc = d2h(o, &g->link_first, d.d_link_first, d.n_segments + 1);
-    if (!rc) rc = d2h(o, &g->segment_name, d.d_segment_name, d.n_segments);
-    if (!rc) rc = d2h(o, &g->edge_twin, d.d_edge_twin, d.n_edges);
-    if (!rc) rc = d2h(o, &g->path_line_off, d.d_path_line_off, d.n_paths + 1);
-    if (!rc) rc = d2h(o, &g->path_contig, d.d_path_contig, d.n_paths);
-    if (!rc) rc = d2h(o, &g->path_first_piece, d.d_path_first_piece, d.n_paths + 1);
-    if (!rc) rc = d2h(o, &g->path_mirror, d.d_path_mirror, d.n_paths);
-    if (rc) { katome_gfa_strand_paths_free(g); return rc; }
-    *out = g;
-    return KATOME_OK;
+    if (!(out = make_result<katome_gfa_strand_paths>())) return KATOME_E_OOM;
+    Copier<katome_gfa_strand_paths> down{out.get()};
+    paths_block(down, d);
+    segments_block(down, d, b->s.k, read_bytes);
+    strands_block(down, d, d.n_edges);
+    out->n_mirrored = d.n_mirrored; out->n_self_mirror = d.n_self_mirror;
+    down(&out->path_mirror, d.d_path_mirror, d.n_paths);
+    return down.rc;
 }
 
-extern "C" int katome_unique_assembly_save(const katome_unique_assembly* u, const char* path) {
-    if (!u || !path) { set_error("null argument"); return KATOME_E_ARG; }
-    return save_gfa_text(u->text, u->text_bytes, path);      // (File::create's statuses and message, as for every text here)
-}
 // katome_dev_collapse_unique(FASTA) of the builder's last collapse in host arrays; lengths: every contig's bases, as the walk knows them
-static int unique_to_host(katome_builder* b, uint64_t read_bytes, const std::vector<uint64_t>& lengths, uint64_t genome_len, katome_unique_assembly** out) {
+static int unique_to_host(katome_builder* b, uint64_t read_bytes, const std::vector<uint64_t>& lengths, uint64_t genome_len,
+                          Result<katome_unique_assembly>& out) {
     katome_dev_unique_assembly d;
     KCHECK(katome_dev_collapse_unique(b, KATOME_TEXT_FASTA, &d, nullptr));
-    UniqueAssemblyOwner* o = new (std::nothrow) UniqueAssemblyOwner();
-    if (!o) { set_error("out of host memory"); return KATOME_E_OOM; }
-    memset(&o->u, 0, sizeof o->u);
-    katome_unique_assembly* u = &o->u;
+    if (!(out = make_result<katome_unique_assembly>())) return KATOME_E_OOM;
+    katome_unique_assembly* u = out.get();
     u->n_contigs = d.n_contigs; u->n_kept = d.n_kept; u->text_bytes = d.text_bytes; u->read_bytes = read_bytes; u->k = b->s.k;
     u->n_mirrored = d.n_mirrored; u->n_self_mirror = d.n_self_mirror;
-    int rc = d2h(o, &u->contig_mirror, d.d_contig_mirror, d.n_contigs);
-    if (!rc) rc = d2h(o, &u->kept_name, d.d_kept_name, d.n_kept);
-    if (!rc) rc = d2h(o, &u->kept_off, d.d_kept_off, d.n_kept);
-    if (!rc) rc = d2h(o, &u->kept_len, d.d_kept_len, d.n_kept);
-    if (!rc) rc = d2h(o, &u->text, d.d_text, d.text_bytes);
-    if (!rc) {
-        std::vector<uint64_t> kept;
-        try { kept.reserve(d.n_kept); }
-        catch (const std::bad_alloc&) { set_error("out of host memory"); rc = KATOME_E_OOM; }
-        for (uint64_t i = 0; i < d.n_kept && !rc; ++i) {
-            const uint64_t c = u->kept_name[i];
-            if (c >= lengths.size() || lengths[c] != u->kept_len[i]) { set_error("collapse_unique: kept contig %llu does not have the walk's length", (unsigned long long)c); rc = KATOME_E_DEVICE; }
-            else kept.push_back(lengths[c]);
+    Copier<katome_unique_assembly> down{u};
+    down(&u->contig_mirror, d.d_contig_mirror, d.n_contigs);
+    down(&u->kept_name, d.d_kept_name, d.n_kept);
+    down(&u->kept_off, d.d_kept_off, d.n_kept);
+    down(&u->kept_len, d.d_kept_len, d.n_kept);
+    down(&u->text, d.d_text, d.text_bytes);
+    KCHECK(down.rc);
+    std::vector<uint64_t> kept;
+    try { kept.reserve(d.n_kept); }
+    catch (const std::bad_alloc&) { set_error("out of host memory"); return KATOME_E_OOM; }
+    for (uint64_t i = 0; i < d.n_kept; ++i) {
+        const uint64_t c = u->kept_name[i];
+        if (c >= lengths.size() || lengths[c] != u->kept_len[i]) {
+            set_error("collapse_unique: kept contig %llu does not have the walk's length", (unsigned long long)c);
+            return KATOME_E_DEVICE;
         }
-        if (!rc) rc = katome_contig_stats_of(kept.data(), kept.size(), genome_len, &u->stats);
+        kept.push_back(lengths[c]);
     }
-    if (rc) { katome_unique_assembly_free(u); return rc; }
-    *out = u;
-    return KATOME_OK;
+    return katome_contig_stats_of(kept.data(), kept.size(), genome_len, &u->stats);
 }
 
-// the stages "dcwced" (asm/basic_assembler.rs:58-75), collapse, Contigs::stats and, with a path, save_to_file: host arrays
-// (with_gfa: katome_assemble_gfa_* -- the GFA of the collapse's shrunk graph with the contigs as P lines too; merge_strands:
-// katome_assemble_gfa_strands_* -- that GFA with strand twins merged, handed back through strands_out)
+// the stages "dcwced" (asm/basic_assembler.rs:58-75), collapse, Contigs::stats and, with a path, save_to_file: host arrays.
+// `with`: what else the same collapse hands back, with a file of its own (`with_path`) -- katome_assemble_gfa_*: the GFA of the
+// collapse's shrunk graph with the contigs as P lines; katome_assemble_gfa_strands_*: that GFA with strand twins merged;
+// katome_assemble_unique_*: the strand-unique form of the contigs
 struct AssembleWant {
-    katome_assembly** out; const char* path; bool with_gfa = false; katome_gfa_paths** gfa_out = nullptr; const char* gfa_path = nullptr;
-    bool merge_strands = false; katome_gfa_strand_paths** strands_out = nullptr;
-    // (unique: katome_assemble_unique_* -- the strand-unique form of the contigs beside the assembly, no GFA)
-    bool unique = false; katome_unique_assembly** unique_out = nullptr; const char* unique_path = nullptr;
+    katome_assembly** out; const char* path;
+    enum With { Alone, GfaPaths, GfaStrandPaths, Unique } with = Alone;
+    const char* with_path = nullptr;
+    katome_gfa_paths** gfa_out = nullptr; katome_gfa_strand_paths** strands_out = nullptr; katome_unique_assembly** unique_out = nullptr;
 };
 static int assembly_to_host(katome_builder* b, uint64_t read_bytes, const AssembleWant& want, uint64_t genome_len) {
-    katome_dev_graph dg;
     if (!b->first_seen) { set_error("assemble needs KATOME_FLAG_FIRST_SEEN_ORDER"); return KATOME_E_ARG; }
-    KCHECK(katome_dev_finalize(b, &dg, nullptr));
-    if (b->s.flags & KATOME_FLAG_REMOVE_DEAD_PATHS) KCHECK(katome_dev_remove_dead_paths(b, &dg, nullptr, nullptr));
-    KCHECK(run_stages("dcwced", BuilderStages{b, genome_len}));
-    build_lap("build and stages");
-    AssemblyOwner* o = new (std::nothrow) AssemblyOwner();
-    if (!o) { set_error("out of host memory"); return KATOME_E_OOM; }
-    memset(&o->a, 0, sizeof o->a);
-    katome_assembly* a = &o->a;
+    KCHECK(prepare(b, "dcwced", genome_len));
+    Result<katome_assembly> a = make_result<katome_assembly>();
+    if (!a) return KATOME_E_OOM;
     katome_dev_assembly da;
     memset(&da, 0, sizeof da);
     std::vector<uint64_t> lengths;
-    int rc = builder_collapse(b, KATOME_TEXT_FASTA, &da, &a->collapse, &lengths, nullptr);
+    const int collapse_rc = builder_collapse(b, KATOME_TEXT_FASTA, &da, &a->collapse, &lengths, nullptr);
     build_lap("collapse");
+    KCHECK(collapse_rc);
     a->n_contigs = da.n_contigs; a->text_bytes = da.text_bytes; a->read_bytes = read_bytes; a->k = b->s.k; a->layout = KATOME_TEXT_FASTA;
-    if (!rc) rc = d2h(o, &a->contig_off, da.d_contig_off, da.n_contigs);
-    if (!rc) rc = d2h(o, &a->contig_len, da.d_contig_len, da.n_contigs);
-    if (!rc) rc = d2h(o, &a->text, da.d_text, da.text_bytes);
-    if (!rc) rc = katome_contig_stats_of(lengths.data(), lengths.size(), genome_len, &a->stats);      // contigs.log_stats()
-    if (rc) { katome_assembly_free(a); return rc; }
-    if (want.unique) {
-        katome_unique_assembly* u = nullptr;
-        rc = unique_to_host(b, read_bytes, lengths, genome_len, &u);
-        build_lap("collapse_unique");
-        if (rc) { katome_assembly_free(a); return rc; }
-        if (want.out) *want.out = a;
-        if (want.unique_out) *want.unique_out = u;
-        rc = want.path ? katome_assembly_save(a, want.path) : KATOME_OK;      // (both files are tried; the first failure is the one reported)
-        const std::string first_err = rc ? get_error() : "";
-        const int rc_unique = want.unique_path ? katome_unique_assembly_save(u, want.unique_path) : KATOME_OK;
-        if (rc) set_error("%s", first_err.c_str()); else rc = rc_unique;
-        if (!want.out) katome_assembly_free(a);
-        if (!want.unique_out) katome_unique_assembly_free(u);
-        return rc;
+    Copier<katome_assembly> down{a.get()};
+    down(&a->contig_off, da.d_contig_off, da.n_contigs);
+    down(&a->contig_len, da.d_contig_len, da.n_contigs);
+    down(&a->text, da.d_text, da.text_bytes);
+    KCHECK(down.rc);
+    KCHECK(katome_contig_stats_of(lengths.data(), lengths.size(), genome_len, &a->stats));      // contigs.log_stats()
+    switch (want.with) {
+        case AssembleWant::GfaPaths: {
+            Result<katome_gfa_paths> g;
+            const int rc = gfa_paths_to_host(b, read_bytes, g);
+            build_lap("collapse_gfa");
+            KCHECK(rc);
+            return hand_out_both(std::move(a), want.out, want.path, std::move(g), want.gfa_out, want.with_path, katome_gfa_paths_save);
+        }
+        case AssembleWant::GfaStrandPaths: {
+            Result<katome_gfa_strand_paths> g;
+            const int rc = gfa_strand_paths_to_host(b, read_bytes, g);
+            build_lap("collapse_gfa_strands");
+            KCHECK(rc);
+            return hand_out_both(std::move(a), want.out, want.path, std::move(g), want.strands_out, want.with_path, katome_gfa_strand_paths_save);
+        }
+        case AssembleWant::Unique: {
+            Result<katome_unique_assembly> u;
+            const int rc = unique_to_host(b, read_bytes, lengths, genome_len, u);
+            build_lap("collapse_unique");
+            KCHECK(rc);
+            return hand_out_both(std::move(a), want.out, want.path, std::move(u), want.unique_out, want.with_path, katome_unique_assembly_save);
+        }
+        case AssembleWant::Alone: break;
     }
-    if (want.with_gfa) {
-        katome_gfa_paths* g = nullptr;
-        katome_gfa_strand_paths* gs = nullptr;
-        rc = want.merge_strands ? gfa_strand_paths_to_host(b, read_bytes, &gs) : gfa_paths_to_host(b, read_bytes, &g);
-        build_lap(want.merge_strands ? "collapse_gfa_strands" : "collapse_gfa");
-        if (rc) { katome_assembly_free(a); return rc; }
-        if (want.out) *want.out = a;
-        if (want.gfa_out) *want.gfa_out = g;
-        if (want.strands_out) *want.strands_out = gs;
-        rc = want.path ? katome_assembly_save(a, want.path) : KATOME_OK;      // (both files are tried; the first failure is the one reported)
-        const std::string first_err = rc ? get_error() : "";
-        const int rc_gfa = !want.gfa_path ? KATOME_OK : gs ? katome_gfa_strand_paths_save(gs, want.gfa_path) : katome_gfa_paths_save(g, want.gfa_path);
-        if (rc) set_error("%s", first_err.c_str()); else rc = rc_gfa;
-        if (!want.out) katome_assembly_free(a);
-        if (!want.gfa_out) katome_gfa_paths_free(g);
-        if (!want.strands_out) katome_gfa_strand_paths_free(gs);
-        return rc;
-    }
-    if (want.out) *want.out = a;
-    rc = want.path ? katome_assembly_save(a, want.path) : KATOME_OK;
-    if (!want.out) katome_assembly_free(a);
-    return rc;
+    return hand_out(std::move(a), want.out, want.path, katome_assembly_save);
 }
 
 // katome_unitigs_* on one GPU: the flag's remove_dead_paths, the stage letters, the traversal-free shrink, its text in FASTA layout,
@@ -534,12 +531,21 @@ static int save_device_bytes(const uint8_t* d_text, uint64_t text_bytes, const c
     if (rc) (void)remove(path);
     return rc;
 }
-static int save_device_text(const katome_dev_assembly& da, const char* path) { return save_device_bytes(da.d_text, da.text_bytes, path); }
+// every merged edge's bases (its k-mers and k - 1 more): their total, the longest and, where asked for, each of them
+static int unitig_bases(const katome_builder* b, const katome_dev_contigs& dc, uint64_t* total, uint64_t* longest, std::vector<uint64_t>* lengths) {
+    std::vector<uint32_t> kmers;
+    try { kmers.resize(dc.n_edges); if (lengths) lengths->resize(dc.n_edges); }
+    catch (const std::bad_alloc&) { set_error("out of host memory"); return KATOME_E_OOM; }
+    if (dc.n_edges) KCHECK_HIP(hipMemcpy(kmers.data(), dc.d_edge_kmers, dc.n_edges * 4, hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < dc.n_edges; ++i) {
+        const uint64_t len = (uint64_t)kmers[i] + b->s.k - 1;
+        if (lengths) (*lengths)[i] = len;
+        *total += len; *longest = std::max(*longest, len);
+    }
+    return KATOME_OK;
+}
 static int unitigs_to_host(katome_builder* b, uint64_t read_bytes, const UnitigsWant& want, const char* stages, uint64_t genome_len) {
-    katome_dev_graph dg;
-    KCHECK(katome_dev_finalize(b, &dg, nullptr));
-    if (b->s.flags & KATOME_FLAG_REMOVE_DEAD_PATHS) KCHECK(katome_dev_remove_dead_paths(b, &dg, nullptr, nullptr));
-    KCHECK(run_stages(stages, BuilderStages{b, genome_len}));
+    KCHECK(prepare(b, stages, genome_len));
     katome_dev_contigs dc;
     const bool coverage = want.gfa && (b->s.flags & KATOME_FLAG_PATH_COVERAGE);      // (the graph's ending only: every other entry ignores the flag)
     katome_dev_coverage cov;
@@ -551,122 +557,67 @@ static int unitigs_to_host(katome_builder* b, uint64_t read_bytes, const Unitigs
         else KCHECK(katome_dev_contigs_gfa(b, &dc, &dgfa, nullptr));
         katome_unitigs_gfa* u = want.gfa;
         u->n_segments = dgfa.n_segments; u->n_links = dgfa.n_links; u->text_bytes = dgfa.text_bytes; u->read_bytes = read_bytes; u->k = b->s.k; u->n_devices = 1;
-        std::vector<uint32_t> kmers;
-        try { kmers.resize(dc.n_edges); }
-        catch (const std::bad_alloc&) { set_error("out of host memory"); return KATOME_E_OOM; }
-        if (dc.n_edges) KCHECK_HIP(hipMemcpy(kmers.data(), dc.d_edge_kmers, dc.n_edges * 4, hipMemcpyDeviceToHost));
-        for (uint64_t i = 0; i < dc.n_edges; ++i) {
-            const uint64_t len = (uint64_t)kmers[i] + b->s.k - 1;
-            u->total_bases += len; u->longest = std::max(u->longest, len);
-        }
+        KCHECK(unitig_bases(b, dc, &u->total_bases, &u->longest, nullptr));
         return want.path ? save_device_bytes(dgfa.d_text, dgfa.text_bytes, want.path) : KATOME_OK;
     }
     katome_dev_assembly da;
     KCHECK(katome_dev_contigs_text(b, &dc, KATOME_TEXT_FASTA, &da, nullptr));
     katome_unitigs* u = want.out;
     u->n_contigs = da.n_contigs; u->text_bytes = da.text_bytes; u->read_bytes = read_bytes; u->k = b->s.k; u->n_devices = 1;
-    std::vector<uint32_t> kmers;
     std::vector<uint64_t> lengths;
-    try { kmers.resize(dc.n_edges); lengths.resize(dc.n_edges); }
-    catch (const std::bad_alloc&) { set_error("out of host memory"); return KATOME_E_OOM; }
-    if (dc.n_edges) KCHECK_HIP(hipMemcpy(kmers.data(), dc.d_edge_kmers, dc.n_edges * 4, hipMemcpyDeviceToHost));
-    for (uint64_t i = 0; i < dc.n_edges; ++i) {
-        lengths[i] = (uint64_t)kmers[i] + b->s.k - 1;
-        u->total_bases += lengths[i]; u->longest = std::max(u->longest, lengths[i]);
-    }
+    KCHECK(unitig_bases(b, dc, &u->total_bases, &u->longest, &lengths));
     const int stats_rc = katome_contig_stats_of(lengths.data(), lengths.size(), genome_len, &u->stats);      // (a tipping point of 0: the file is written all the same)
     const std::string stats_err = stats_rc ? get_error() : "";
-    if (want.path) KCHECK(save_device_text(da, want.path));
+    if (want.path) KCHECK(save_device_bytes(da.d_text, da.text_bytes, want.path));
     if (stats_rc) set_error("%s", stats_err.c_str());
     return stats_rc;
 }
 
-// the GFA's text is the file
-static int save_gfa_text(const uint8_t* text, uint64_t text_bytes, const char* path) {
-    FILE* f = fopen(path, "wb");
-    if (!f) {
-        set_error("couldn't create %s: %s", path, CREATE_ERROR_KINDS[create_error_kind(errno)]);      // (katome_assembly_save's message)
-        return KATOME_E_OPEN;
-    }
-    const size_t n = text_bytes ? fwrite(text, 1, text_bytes, f) : 0;
-    if (fclose(f) != 0 || n != text_bytes) { set_error("couldn't write %s", path); return KATOME_E_OPEN; }
-    return KATOME_OK;
-}
-extern "C" int katome_gfa_save(const katome_gfa* g, const char* path) {
-    if (!g || !path) { set_error("null argument"); return KATOME_E_ARG; }
-    return save_gfa_text(g->text, g->text_bytes, path);
-}
-extern "C" int katome_gfa_strands_save(const katome_gfa_strands* g, const char* path) {
-    if (!g || !path) { set_error("null argument"); return KATOME_E_ARG; }
-    return save_gfa_text(g->text, g->text_bytes, path);
-}
-
 // katome_gfa_*: the flag's remove_dead_paths, the stage letters, shrink (AUTO: exact on a first-seen build, fast otherwise), the GFA of
 // the result copied to host arrays and, with a path, the file
-// (strands: the merged form, katome_gfa_strands_* -- the same pipeline up to the shrink)
+// (merge: the merged form, katome_gfa_strands_*, handed back through `strands` -- the same pipeline up to the shrink)
 struct GfaWant { katome_gfa** out; const char* path; katome_gfa_strands** strands = nullptr; bool merge = false; };
-static int gfa_strands_to_host(katome_builder* b, const katome_dev_contigs& dc, uint64_t read_bytes, const GfaWant& want) {
-    katome_dev_gfa_strands d;
-    KCHECK(katome_dev_contigs_gfa_strands(b, &dc, &d, nullptr));
-    GfaStrandsOwner* o = new (std::nothrow) GfaStrandsOwner();
-    if (!o) { set_error("out of host memory"); return KATOME_E_OOM; }
-    memset(&o->g, 0, sizeof o->g);
-    katome_gfa_strands* g = &o->g;
-    g->n_segments = d.n_segments; g->n_links = d.n_links; g->text_bytes = d.text_bytes; g->read_bytes = read_bytes; g->k = b->s.k;
-    g->n_edges = dc.n_edges; g->n_unpaired = d.n_unpaired; g->n_self_twins = d.n_self_twins;
-    int rc = d2h(o, &g->text, d.d_text, d.text_bytes);
-    if (!rc) rc = d2h(o, &g->segment_off, d.d_segment_off, d.n_segments);
-    if (!rc) rc = d2h(o, &g->link_first, d.d_link_first, d.n_segments + 1);
-    if (!rc) rc = d2h(o, &g->segment_name, d.d_segment_name, d.n_segments);
-    if (!rc) rc = d2h(o, &g->edge_twin, d.d_edge_twin, dc.n_edges);
-    if (rc) { katome_gfa_strands_free(g); return rc; }
-    if (want.strands) *want.strands = g;
-    rc = want.path ? katome_gfa_strands_save(g, want.path) : KATOME_OK;
-    if (!want.strands) katome_gfa_strands_free(g);
-    return rc;
-}
-static int gfa_to_host(katome_builder* b, uint64_t read_bytes, const GfaWant& want, const char* stages, uint64_t genome_len) {
-    katome_dev_graph dg;
-    if (stages && *stages && !b->first_seen) { set_error("stages after the build need KATOME_FLAG_FIRST_SEEN_ORDER"); return KATOME_E_ARG; }
-    KCHECK(katome_dev_finalize(b, &dg, nullptr));
-    if (b->s.flags & KATOME_FLAG_REMOVE_DEAD_PATHS) KCHECK(katome_dev_remove_dead_paths(b, &dg, nullptr, nullptr));
-    KCHECK(run_stages(stages, BuilderStages{b, genome_len}));
+static int gfa_ending(katome_builder* b, uint64_t read_bytes, const GfaWant& want, const char* stages, uint64_t genome_len) {
+    KCHECK(stages_need_order(b->first_seen, stages));
+    KCHECK(prepare(b, stages, genome_len));
     katome_dev_contigs dc;
     KCHECK(katome_dev_shrink(b, &dc, nullptr));
-    if (want.merge) return gfa_strands_to_host(b, dc, read_bytes, want);
-    katome_dev_gfa dgfa;
-    KCHECK(katome_dev_contigs_gfa(b, &dc, &dgfa, nullptr));
-    GfaOwner* o = new (std::nothrow) GfaOwner();
-    if (!o) { set_error("out of host memory"); return KATOME_E_OOM; }
-    memset(&o->g, 0, sizeof o->g);
-    katome_gfa* g = &o->g;
-    g->n_segments = dgfa.n_segments; g->n_links = dgfa.n_links; g->text_bytes = dgfa.text_bytes; g->read_bytes = read_bytes; g->k = b->s.k;
-    int rc = d2h(o, &g->text, dgfa.d_text, dgfa.text_bytes);
-    if (!rc) rc = d2h(o, &g->segment_off, dgfa.d_segment_off, dgfa.n_segments);
-    if (!rc) rc = d2h(o, &g->link_first, dgfa.d_link_first, dgfa.n_segments + 1);
-    if (rc) { katome_gfa_free(g); return rc; }
-    if (want.out) *want.out = g;
-    rc = want.path ? katome_gfa_save(g, want.path) : KATOME_OK;
-    if (!want.out) katome_gfa_free(g);
-    return rc;
+    if (want.merge) {
+        Result<katome_gfa_strands> g;
+        KCHECK(gfa_strands_to_host(b, dc, read_bytes, g));
+        return hand_out(std::move(g), want.strands, want.path, katome_gfa_strands_save);
+    }
+    Result<katome_gfa> g;
+    KCHECK(gfa_to_host(b, dc, read_bytes, g));
+    return hand_out(std::move(g), want.out, want.path, katome_gfa_save);
 }
 
-// what a host entry hands back: the graph, the graph after shrink, the assembly, the unitigs' numbers (and their file), or the GFA
+// What a host entry hands back: the graph, the graph after shrink, the assembly, the unitigs' numbers (and their file), or the
+// GFA -- and what that ending needs.  The ending runs on the builder of a one-GPU build or of a graph gathered to one GPU.
+enum class Ending { Graph, Contigs, Assembly, Unitigs, Gfa };
 struct Finish {
-    katome_graph** graph; katome_contigs** contigs;
-    AssembleWant assemble{nullptr, nullptr}; bool assembling = false;
-    UnitigsWant unitigs{nullptr, nullptr}; bool want_unitigs = false;
-    GfaWant gfa{nullptr, nullptr}; bool want_gfa = false;
-    const char* stages = nullptr; uint64_t genome_len = 0;
+    Ending ending;
+    const char* stages = nullptr; uint64_t genome_len = 0;      // (Contigs takes no stages; Assembly runs its own)
+    katome_graph** graph = nullptr;                               // Graph
+    katome_stats* stage_stats = nullptr;                          // katome_build_*_staged_stats: the graph described before the first stage and after each
+    katome_contigs** contigs = nullptr;                           // Contigs
     uint32_t shrink_mode = KATOME_SHRINK_AUTO;
-    katome_stats* stage_stats = nullptr;      // katome_build_*_staged_stats: the graph described before the first stage and after each
+    AssembleWant assemble{nullptr, nullptr};                      // Assembly
+    UnitigsWant unitigs{nullptr, nullptr};                        // Unitigs
+    GfaWant gfa{nullptr, nullptr};                                // Gfa
     int operator()(katome_builder* b, uint64_t read_bytes) const {
-        if (assembling) return assembly_to_host(b, read_bytes, assemble, genome_len);
-        if (want_unitigs) return unitigs_to_host(b, read_bytes, unitigs, stages, genome_len);
-        if (want_gfa) return gfa_to_host(b, read_bytes, gfa, stages, genome_len);
-        return contigs ? contigs_to_host(b, read_bytes, contigs, shrink_mode) : graph_to_host(b, read_bytes, graph, stages, genome_len, stage_stats);
+        switch (ending) {
+            case Ending::Graph: return graph_to_host(b, read_bytes, graph, stages, genome_len, stage_stats);
+            case Ending::Contigs: return contigs_to_host(b, read_bytes, contigs, shrink_mode);
+            case Ending::Assembly: return assembly_to_host(b, read_bytes, assemble, genome_len);
+            case Ending::Unitigs: return unitigs_to_host(b, read_bytes, unitigs, stages, genome_len);
+            case Ending::Gfa: return gfa_ending(b, read_bytes, gfa, stages, genome_len);
+        }
+        set_error("unknown ending");
+        return KATOME_E_ARG;
     }
 };
+
 
 // records per extraction batch: bounded by a slice of free device memory
 static uint64_t batch_records(uint32_t nw) {
@@ -712,15 +663,14 @@ static int assemble_shrunk(std::vector<RankShrunk>& parts, uint32_t k, uint64_t 
     } catch (const std::bad_alloc&) { set_error("out of host memory"); return KATOME_E_OOM; }
     std::sort(order.begin(), order.end());
     for (auto& p : parts) lb += p.label.size();
-    ContigsOwner* o = new (std::nothrow) ContigsOwner();
-    if (!o) { set_error("out of host memory"); return KATOME_E_OOM; }
-    memset(&o->c, 0, sizeof o->c);
-    katome_contigs* c = &o->c;
+    Result<katome_contigs> owned = make_result<katome_contigs>();
+    if (!owned) return KATOME_E_OOM;
+    katome_contigs* c = owned.get();
     bool oom = false;
-    uint64_t* src = (uint64_t*)take(o, TE * 8, &oom); uint64_t* dst = (uint64_t*)take(o, TE * 8, &oom); uint32_t* w = (uint32_t*)take(o, TE * 4, &oom);
-    uint32_t* km = (uint32_t*)take(o, TE * 4, &oom); uint64_t* off = (uint64_t*)take(o, (TE + 1) * 8, &oom); uint8_t* lab = (uint8_t*)take(o, lb, &oom);
-    uint64_t* nkey = (uint64_t*)take(o, TN * 8 * nw, &oom); uint8_t* seen = (uint8_t*)take(o, TN, &oom);
-    if (oom) { katome_contigs_free(c); set_error("out of host memory"); return KATOME_E_OOM; }
+    uint64_t* src = (uint64_t*)take(c, TE * 8, &oom); uint64_t* dst = (uint64_t*)take(c, TE * 8, &oom); uint32_t* w = (uint32_t*)take(c, TE * 4, &oom);
+    uint32_t* km = (uint32_t*)take(c, TE * 4, &oom); uint64_t* off = (uint64_t*)take(c, (TE + 1) * 8, &oom); uint8_t* lab = (uint8_t*)take(c, lb, &oom);
+    uint64_t* nkey = (uint64_t*)take(c, TN * 8 * nw, &oom); uint8_t* seen = (uint8_t*)take(c, TN, &oom);
+    if (oom) { set_error("out of host memory"); return KATOME_E_OOM; }
     bool bad = order.size() != TE;
     uint64_t at = 0;
     off[0] = 0;
@@ -742,10 +692,10 @@ static int assemble_shrunk(std::vector<RankShrunk>& parts, uint32_t k, uint64_t 
             seen[id] = 1; ++placed;
             for (uint32_t q = 0; q < nw; ++q) nkey[id * nw + q] = P.nkey[j * nw + q];
         }
-    if (bad || placed != TN) { katome_contigs_free(c); set_error("sharded shrink: the ranks' merged edges or nodes do not fit together"); return KATOME_E_DEVICE; }
+    if (bad || placed != TN) { set_error("sharded shrink: the ranks' merged edges or nodes do not fit together"); return KATOME_E_DEVICE; }
     c->n_nodes = TN; c->n_edges = TE; c->label_bytes = lb; c->read_bytes = read_bytes; c->k = k; c->key_words = nw;
     c->edge_src = src; c->edge_dst = dst; c->edge_weight = w; c->edge_kmers = km; c->edge_label_off = off; c->edge_label = lab; c->node_key = nkey;
-    *out = c;
+    *out = owned.release();
     return KATOME_OK;
 }
 
@@ -758,7 +708,7 @@ struct MultiBuild {                      // what the rank threads of one call sh
     std::shared_ptr<LocalGroup> sync;    // host rendezvous of the rank threads, whatever moves the data
     std::vector<int> rc; std::vector<std::string> err;
     std::vector<uint64_t> n_edges;       // by packed key: the ranks' edge counts (the host arrays are their shares one after the other)
-    GraphOwner* owner = nullptr; int alloc_rc = KATOME_OK;      // the host graph every rank copies its share into (rank 0 makes it)
+    Result<katome_graph> graph; int alloc_rc = KATOME_OK;       // the host graph every rank copies its share into (rank 0 makes it)
     std::vector<RankShrunk> shrunk;
 };
 }  // namespace
@@ -787,18 +737,18 @@ static int gathered_finish(MultiBuild& mb, int r, katome_dist_builder* d, hipStr
     return rc;
 }
 
-// rank 0, between the two meetings: the host graph of the whole result (mb.owner; nullptr and mb.alloc_rc: no memory for it)
+// rank 0, between the two meetings: the host graph of the whole result (mb.graph; nullptr and mb.alloc_rc: no memory for it)
 static void alloc_shared_graph(MultiBuild& mb, const katome_dist_graph& g) {
     std::vector<HostCopy> arrays;
     mb.alloc_rc = new_host_graph(g.total_nodes, g.total_edges, mb.s->k, g.key_words, g.label_stride, g.d_edge_age != nullptr, mb.read_bytes,
-                                 &mb.owner, arrays);
+                                 mb.graph, arrays);
     if (mb.alloc_rc == KATOME_OK) for (const HostCopy& a : arrays) host_result_touch(a.h, a.bytes);
 }
 
 // by packed key the host arrays are the ranks' shares one after the other: rank r's edges start where those of the ranks
 // before it end, its nodes at node_base
 static int copy_out_by_key(MultiBuild& mb, int r, const katome_dist_graph& g, hipStream_t stream) {
-    const katome_graph* hg = &mb.owner->g;
+    const katome_graph* hg = mb.graph.get();
     uint64_t e0 = 0;
     for (int p = 0; p < r; ++p) e0 += mb.n_edges[p];
     const uint64_t E = g.n_edges, N = g.n_nodes;
@@ -814,7 +764,7 @@ static int copy_out_by_key(MultiBuild& mb, int r, const katome_dist_graph& g, hi
 // in the reference's numbering every edge and node goes to its petgraph index: the rank's share comes over in its own order
 // and is placed on the host
 static int copy_out_by_index(MultiBuild& mb, const katome_dist_graph& g, hipStream_t stream) {
-    const katome_graph* hg = &mb.owner->g;
+    const katome_graph* hg = mb.graph.get();
     const bool pruned = g.d_edge_age != nullptr;      // (the ages come along once a stage that may remove edges has run)
     const uint64_t E = g.n_edges, N = g.n_nodes;
     const uint32_t nwk = g.key_words, ls = g.label_stride;
@@ -929,7 +879,7 @@ static int rank_build(MultiBuild& mb, int r, int n, katome_dist_builder* d, cons
     KCHECK(meet(mb));
     if (r == 0) alloc_shared_graph(mb, g);
     KCHECK(meet(mb));
-    if (!mb.owner) return mb.alloc_rc ? mb.alloc_rc : KATOME_E_OOM;
+    if (!mb.graph) return mb.alloc_rc ? mb.alloc_rc : KATOME_E_OOM;
     return route.first_seen ? copy_out_by_index(mb, g, stream) : copy_out_by_key(mb, r, g, stream);
 }
 
@@ -954,7 +904,8 @@ static int build_multi(const katome_settings* s, const Finish& finish, uint64_t 
     const int n = s->n_devices;
     const bool share = (s->flags & KATOME_FLAG_RANKS_SHARE_DEVICE) != 0;
     // (a GFA takes the assembly's route: gathered to the first GPU, where the stages, the shrink and the text run -- links cross ranks)
-    const MultiRoute route = plan_multi_route(s->flags, finish.contigs != nullptr, finish.stages, finish.assembling || finish.want_gfa, finish.want_unitigs);
+    const MultiRoute route = plan_multi_route(s->flags, finish.ending == Ending::Contigs, finish.stages, finish.ending == Ending::Assembly || finish.ending == Ending::Gfa,
+                                               finish.ending == Ending::Unitigs);
     if (n > KATOME_MAX_RANKS) { set_error("n_devices = %d: at most %d", n, KATOME_MAX_RANKS); return KATOME_E_UNSUPPORTED; }
     KCHECK(use_device(s->device));
     int n_visible = 0;
@@ -995,10 +946,8 @@ static int build_multi(const katome_settings* s, const Finish& finish, uint64_t 
         for (int r = 0; r < n && !rc; ++r)
             if (mb.rc[r] && (gave_up || mb.err[r] != RANK_GAVE_UP)) { rc = mb.rc[r]; set_error("rank %d of %d: %s", r, n, mb.err[r].c_str()); }
     if (rc == KATOME_OK && route.sharded_shrink) rc = assemble_shrunk(mb.shrunk, s->k, read_bytes, finish.contigs);
-    if (mb.owner) {                                              // (the ranks' shares were copied out: no gathered route ran)
-        if (rc == KATOME_OK && finish.graph) *finish.graph = &mb.owner->g;
-        else katome_graph_free(&mb.owner->g);
-    }
+    // (mb.graph: the ranks' shares were copied out, no gathered route ran; a failed build frees it)
+    if (mb.graph && rc == KATOME_OK && finish.graph) *finish.graph = mb.graph.release();
     return rc;
 }
 
@@ -1116,158 +1065,6 @@ static int build_packed_impl(const katome_settings* s, const uint8_t* packed, ui
 }
 
 extern "C" {
-
-int katome_build_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len,
-                        const uint8_t* skip, katome_graph** out) {
-    if (!out) { set_error("null argument"); return KATOME_E_ARG; }
-    *out = nullptr;
-    return build_packed_impl(s, packed, n_reads, read_len, skip, Finish{out, nullptr});
-}
-int katome_build_packed_staged(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len,
-                               const uint8_t* skip, const char* stages, uint64_t original_genome_length, katome_graph** out) {
-    if (!out) { set_error("null argument"); return KATOME_E_ARG; }
-    *out = nullptr;
-    Finish f{out, nullptr};
-    f.stages = stages; f.genome_len = original_genome_length;
-    return build_packed_impl(s, packed, n_reads, read_len, skip, f);
-}
-int katome_build_packed_staged_stats(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip,
-                                     const char* stages, uint64_t original_genome_length, katome_stats* stage_stats, katome_graph** out) {
-    if (!out || !stage_stats) { set_error("null argument"); return KATOME_E_ARG; }
-    *out = nullptr;
-    Finish f{out, nullptr};
-    f.stages = stages; f.genome_len = original_genome_length; f.stage_stats = stage_stats;
-    return build_packed_impl(s, packed, n_reads, read_len, skip, f);
-}
-int katome_assemble_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip,
-                           uint64_t original_genome_length, const char* out_path, katome_assembly** out) {
-    if (!out && !out_path) { set_error("null argument"); return KATOME_E_ARG; }
-    if (out) *out = nullptr;
-    Finish f{nullptr, nullptr};
-    f.assemble = AssembleWant{out, out_path}; f.assembling = true; f.genome_len = original_genome_length;
-    return build_packed_impl(s, packed, n_reads, read_len, skip, f);
-}
-// katome_assemble_gfa_*: the assembly and the GFA of its shrunk graph with the contigs as P lines (the same check on both routes)
-static int assemble_gfa_finish(uint64_t genome_len, const char* fasta_path, const char* gfa_path, katome_assembly** asm_out, katome_gfa_paths** gfa_out, Finish& f) {
-    if (asm_out) *asm_out = nullptr;
-    if (gfa_out) *gfa_out = nullptr;
-    if (!fasta_path && !gfa_path && !asm_out && !gfa_out) { set_error("null argument"); return KATOME_E_ARG; }
-    f.assemble = AssembleWant{asm_out, fasta_path, true, gfa_out, gfa_path}; f.assembling = true; f.genome_len = genome_len;
-    return KATOME_OK;
-}
-int katome_assemble_gfa_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip,
-                               uint64_t original_genome_length, const char* fasta_path, const char* gfa_path, katome_assembly** asm_out,
-                               katome_gfa_paths** gfa_out) {
-    Finish f{nullptr, nullptr};
-    KCHECK(assemble_gfa_finish(original_genome_length, fasta_path, gfa_path, asm_out, gfa_out, f));
-    return build_packed_impl(s, packed, n_reads, read_len, skip, f);
-}
-// katome_assemble_gfa_strands_*: the same with strand twins merged
-static int assemble_gfa_strands_finish(uint64_t genome_len, const char* fasta_path, const char* gfa_path, katome_assembly** asm_out,
-                                       katome_gfa_strand_paths** gfa_out, Finish& f) {
-    if (asm_out) *asm_out = nullptr;
-    if (gfa_out) *gfa_out = nullptr;
-    if (!fasta_path && !gfa_path && !asm_out && !gfa_out) { set_error("null argument"); return KATOME_E_ARG; }
-    f.assemble = AssembleWant{asm_out, fasta_path, true, nullptr, gfa_path, true, gfa_out}; f.assembling = true; f.genome_len = genome_len;
-    return KATOME_OK;
-}
-int katome_assemble_gfa_strands_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip,
-                                       uint64_t original_genome_length, const char* fasta_path, const char* gfa_path, katome_assembly** asm_out,
-                                       katome_gfa_strand_paths** gfa_out) {
-    Finish f{nullptr, nullptr};
-    KCHECK(assemble_gfa_strands_finish(original_genome_length, fasta_path, gfa_path, asm_out, gfa_out, f));
-    return build_packed_impl(s, packed, n_reads, read_len, skip, f);
-}
-// katome_assemble_unique_*: the assembly and the strand-unique form of its contigs
-static int assemble_unique_finish(uint64_t genome_len, const char* fasta_path, const char* unique_path, katome_assembly** asm_out,
-                                  katome_unique_assembly** unique_out, Finish& f) {
-    if (asm_out) *asm_out = nullptr;
-    if (unique_out) *unique_out = nullptr;
-    if (!fasta_path && !unique_path && !asm_out && !unique_out) { set_error("null argument"); return KATOME_E_ARG; }
-    f.assemble = AssembleWant{asm_out, fasta_path};
-    f.assemble.unique = true; f.assemble.unique_out = unique_out; f.assemble.unique_path = unique_path;
-    f.assembling = true; f.genome_len = genome_len;
-    return KATOME_OK;
-}
-int katome_assemble_unique_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip,
-                                  uint64_t original_genome_length, const char* fasta_path, const char* unique_path, katome_assembly** asm_out,
-                                  katome_unique_assembly** unique_out) {
-    Finish f{nullptr, nullptr};
-    KCHECK(assemble_unique_finish(original_genome_length, fasta_path, unique_path, asm_out, unique_out, f));
-    return build_packed_impl(s, packed, n_reads, read_len, skip, f);
-}
-// (the same check on every route: the stages work on the links of a first-seen build)
-static int unitigs_refusal(const katome_settings* s, const char* stages) {
-    if (s && !(s->flags & KATOME_FLAG_FIRST_SEEN_ORDER) && ((stages && *stages) || (s->flags & KATOME_FLAG_REMOVE_DEAD_PATHS))) {
-        set_error("unitigs: stage letters and KATOME_FLAG_REMOVE_DEAD_PATHS need KATOME_FLAG_FIRST_SEEN_ORDER");
-        return KATOME_E_ARG;
-    }
-    return KATOME_OK;
-}
-static int unitigs_finish(const katome_settings* s, const char* stages, uint64_t genome_len, const char* out_path, katome_unitigs* out, Finish& f) {
-    if (!out) { set_error("null argument"); return KATOME_E_ARG; }
-    memset(out, 0, sizeof *out);
-    KCHECK(unitigs_refusal(s, stages));
-    f.unitigs = UnitigsWant{out, out_path}; f.want_unitigs = true; f.stages = stages; f.genome_len = genome_len;
-    return KATOME_OK;
-}
-int katome_unitigs_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip,
-                          const char* stages, uint64_t original_genome_length, const char* out_path, katome_unitigs* out) {
-    Finish f{nullptr, nullptr};
-    KCHECK(unitigs_finish(s, stages, original_genome_length, out_path, out, f));
-    return build_packed_impl(s, packed, n_reads, read_len, skip, f);
-}
-// katome_unitigs_gfa_*: the unitigs route with the graph as its ending
-static int unitigs_gfa_finish(const katome_settings* s, const char* stages, uint64_t genome_len, const char* out_path, katome_unitigs_gfa* out, Finish& f) {
-    if (!out) { set_error("null argument"); return KATOME_E_ARG; }
-    memset(out, 0, sizeof *out);
-    KCHECK(unitigs_refusal(s, stages));
-    f.unitigs = UnitigsWant{nullptr, out_path, out}; f.want_unitigs = true; f.stages = stages; f.genome_len = genome_len;
-    return KATOME_OK;
-}
-int katome_unitigs_gfa_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip,
-                              const char* stages, uint64_t original_genome_length, const char* out_path, katome_unitigs_gfa* out) {
-    Finish f{nullptr, nullptr};
-    KCHECK(unitigs_gfa_finish(s, stages, original_genome_length, out_path, out, f));
-    return build_packed_impl(s, packed, n_reads, read_len, skip, f);
-}
-// (the same check on every route, before any GPU work)
-static int gfa_finish(const katome_settings* s, const char* stages, uint64_t genome_len, const char* out_path, katome_gfa** out, Finish& f) {
-    if (!out && !out_path) { set_error("null argument"); return KATOME_E_ARG; }
-    if (out) *out = nullptr;
-    if (s && !(s->flags & KATOME_FLAG_FIRST_SEEN_ORDER) && stages && *stages) {
-        set_error("stages after the build need KATOME_FLAG_FIRST_SEEN_ORDER");
-        return KATOME_E_ARG;
-    }
-    f.gfa = GfaWant{out, out_path}; f.want_gfa = true; f.stages = stages; f.genome_len = genome_len;
-    return KATOME_OK;
-}
-static int gfa_strands_finish(const katome_settings* s, const char* stages, uint64_t genome_len, const char* out_path, katome_gfa_strands** out, Finish& f) {
-    if (!out && !out_path) { set_error("null argument"); return KATOME_E_ARG; }
-    if (out) *out = nullptr;
-    katome_gfa* none = nullptr;
-    KCHECK(gfa_finish(s, stages, genome_len, out_path, &none, f));      // (the same refusals, the same route)
-    f.gfa = GfaWant{nullptr, out_path, out, true};
-    return KATOME_OK;
-}
-int katome_gfa_strands_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip, const char* stages,
-                              uint64_t original_genome_length, const char* out_path, katome_gfa_strands** out) {
-    Finish f{nullptr, nullptr};
-    KCHECK(gfa_strands_finish(s, stages, original_genome_length, out_path, out, f));
-    return build_packed_impl(s, packed, n_reads, read_len, skip, f);
-}
-int katome_gfa_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip, const char* stages,
-                      uint64_t original_genome_length, const char* out_path, katome_gfa** out) {
-    Finish f{nullptr, nullptr};
-    KCHECK(gfa_finish(s, stages, original_genome_length, out_path, out, f));
-    return build_packed_impl(s, packed, n_reads, read_len, skip, f);
-}
-int katome_shrink_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len,
-                         const uint8_t* skip, katome_contigs** out) {
-    if (!out) { set_error("null argument"); return KATOME_E_ARG; }
-    *out = nullptr;
-    return build_packed_impl(s, packed, n_reads, read_len, skip, Finish{nullptr, out});
-}
 
 int katome_ingest_files(const katome_settings* s, const char* const* paths, size_t n_paths, katome_reads** out) {
     if (!s || !out || (!paths && n_paths)) { set_error("null argument"); return KATOME_E_ARG; }
@@ -1390,83 +1187,182 @@ static int build_files_impl(const katome_settings* s, const char* const* paths, 
     return rc;
 }
 
+// ---- the entries ---------------------------------------------------------------------------------------------------------------
+// Where the reads come from: 2-bit packed reads of one length in the caller's memory, or files.  Each builds with any ending.
+struct PackedReads {
+    const uint8_t* packed; uint64_t n_reads; uint32_t read_len; const uint8_t* skip;
+    int build(const katome_settings* s, const Finish& finish) const { return build_packed_impl(s, packed, n_reads, read_len, skip, finish); }
+};
+struct FileReads {
+    const char* const* paths; size_t n_paths;
+    int build(const katome_settings* s, const Finish& finish) const { return build_files_impl(s, paths, n_paths, finish); }
+};
+
+// Every ending's entry, once for both sources.  The order decides which error a caller sees: the caller's output pointers, then
+// the outputs cleared, then the ending's own refusals -- before any GPU work, the same on every route -- and only then the
+// source's checks (settings, reads or paths, k), the ingest and the device.
+static int null_argument() { set_error("null argument"); return KATOME_E_ARG; }
+
+// katome_build_*, katome_build_*_staged, katome_build_*_staged_stats (with_stats: the caller must bring stage_stats)
+template <class Reads> static int graph_entry(const Reads& reads, const katome_settings* s, const char* stages, uint64_t genome_len, bool with_stats,
+                                              katome_stats* stage_stats, katome_graph** out) {
+    if (!out || (with_stats && !stage_stats)) return null_argument();
+    *out = nullptr;
+    Finish f{Ending::Graph};
+    f.graph = out; f.stages = stages; f.genome_len = genome_len; f.stage_stats = stage_stats;
+    return reads.build(s, f);
+}
+// katome_shrink_*
+template <class Reads> static int contigs_entry(const Reads& reads, const katome_settings* s, katome_contigs** out) {
+    if (!out) return null_argument();
+    *out = nullptr;
+    Finish f{Ending::Contigs};
+    f.contigs = out;
+    return reads.build(s, f);
+}
+// katome_assemble_*, katome_assemble_gfa_*, katome_assemble_gfa_strands_*, katome_assemble_unique_*: a result or a file must be asked for
+template <class Reads> static int assemble_entry(const Reads& reads, const katome_settings* s, uint64_t genome_len, const AssembleWant& want) {
+    if (!want.out && !want.path && !want.with_path && !want.gfa_out && !want.strands_out && !want.unique_out) return null_argument();
+    if (want.out) *want.out = nullptr;
+    if (want.gfa_out) *want.gfa_out = nullptr;
+    if (want.strands_out) *want.strands_out = nullptr;
+    if (want.unique_out) *want.unique_out = nullptr;
+    Finish f{Ending::Assembly};
+    f.assemble = want; f.genome_len = genome_len;
+    return reads.build(s, f);
+}
+// katome_unitigs_* (out) and katome_unitigs_gfa_* (gfa): the caller's plain struct
+template <class Reads> static int unitigs_entry(const Reads& reads, const katome_settings* s, const char* stages, uint64_t genome_len, const char* out_path,
+                                                katome_unitigs* out, katome_unitigs_gfa* gfa) {
+    if (!out && !gfa) return null_argument();
+    if (out) memset(out, 0, sizeof *out);
+    if (gfa) memset(gfa, 0, sizeof *gfa);
+    // (the stages work on the links of a first-seen build, on every route)
+    if (s && !(s->flags & KATOME_FLAG_FIRST_SEEN_ORDER) && ((stages && *stages) || (s->flags & KATOME_FLAG_REMOVE_DEAD_PATHS))) {
+        set_error("unitigs: stage letters and KATOME_FLAG_REMOVE_DEAD_PATHS need KATOME_FLAG_FIRST_SEEN_ORDER");
+        return KATOME_E_ARG;
+    }
+    Finish f{Ending::Unitigs};
+    f.unitigs = UnitigsWant{out, out_path, gfa}; f.stages = stages; f.genome_len = genome_len;
+    return reads.build(s, f);
+}
+// katome_gfa_* (out) and katome_gfa_strands_* (strands): the result or the file must be asked for
+template <class Reads> static int gfa_entry(const Reads& reads, const katome_settings* s, const char* stages, uint64_t genome_len, const char* out_path,
+                                            katome_gfa** out, katome_gfa_strands** strands, bool merge) {
+    if (!out && !strands && !out_path) return null_argument();
+    if (out) *out = nullptr;
+    if (strands) *strands = nullptr;
+    if (s) KCHECK(stages_need_order((s->flags & KATOME_FLAG_FIRST_SEEN_ORDER) != 0, stages));
+    Finish f{Ending::Gfa};
+    f.gfa = GfaWant{out, out_path, strands, merge}; f.stages = stages; f.genome_len = genome_len;
+    return reads.build(s, f);
+}
+
 extern "C" {
 
+int katome_build_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip, katome_graph** out) {
+    return graph_entry(PackedReads{packed, n_reads, read_len, skip}, s, nullptr, 0, false, nullptr, out);
+}
 int katome_build_files(const katome_settings* s, const char* const* paths, size_t n_paths, katome_graph** out) {
-    if (!out) { set_error("null argument"); return KATOME_E_ARG; }
-    *out = nullptr;
-    return build_files_impl(s, paths, n_paths, Finish{out, nullptr});
+    return graph_entry(FileReads{paths, n_paths}, s, nullptr, 0, false, nullptr, out);
+}
+int katome_build_packed_staged(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip,
+                               const char* stages, uint64_t original_genome_length, katome_graph** out) {
+    return graph_entry(PackedReads{packed, n_reads, read_len, skip}, s, stages, original_genome_length, false, nullptr, out);
 }
 int katome_build_files_staged(const katome_settings* s, const char* const* paths, size_t n_paths, const char* stages,
                               uint64_t original_genome_length, katome_graph** out) {
-    if (!out) { set_error("null argument"); return KATOME_E_ARG; }
-    *out = nullptr;
-    Finish f{out, nullptr};
-    f.stages = stages; f.genome_len = original_genome_length;
-    return build_files_impl(s, paths, n_paths, f);
+    return graph_entry(FileReads{paths, n_paths}, s, stages, original_genome_length, false, nullptr, out);
+}
+int katome_build_packed_staged_stats(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip,
+                                     const char* stages, uint64_t original_genome_length, katome_stats* stage_stats, katome_graph** out) {
+    return graph_entry(PackedReads{packed, n_reads, read_len, skip}, s, stages, original_genome_length, true, stage_stats, out);
 }
 int katome_build_files_staged_stats(const katome_settings* s, const char* const* paths, size_t n_paths, const char* stages,
                                     uint64_t original_genome_length, katome_stats* stage_stats, katome_graph** out) {
-    if (!out || !stage_stats) { set_error("null argument"); return KATOME_E_ARG; }
-    *out = nullptr;
-    Finish f{out, nullptr};
-    f.stages = stages; f.genome_len = original_genome_length; f.stage_stats = stage_stats;
-    return build_files_impl(s, paths, n_paths, f);
+    return graph_entry(FileReads{paths, n_paths}, s, stages, original_genome_length, true, stage_stats, out);
+}
+
+int katome_shrink_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip, katome_contigs** out) {
+    return contigs_entry(PackedReads{packed, n_reads, read_len, skip}, s, out);
+}
+int katome_shrink_files(const katome_settings* s, const char* const* paths, size_t n_paths, katome_contigs** out) {
+    return contigs_entry(FileReads{paths, n_paths}, s, out);
+}
+
+int katome_assemble_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip,
+                           uint64_t original_genome_length, const char* out_path, katome_assembly** out) {
+    return assemble_entry(PackedReads{packed, n_reads, read_len, skip}, s, original_genome_length, AssembleWant{out, out_path});
 }
 int katome_assemble_files(const katome_settings* s, const char* const* paths, size_t n_paths, uint64_t original_genome_length, const char* out_path,
                           katome_assembly** out) {
-    if (!out && !out_path) { set_error("null argument"); return KATOME_E_ARG; }
-    if (out) *out = nullptr;
-    Finish f{nullptr, nullptr};
-    f.assemble = AssembleWant{out, out_path}; f.assembling = true; f.genome_len = original_genome_length;
-    return build_files_impl(s, paths, n_paths, f);
+    return assemble_entry(FileReads{paths, n_paths}, s, original_genome_length, AssembleWant{out, out_path});
+}
+int katome_assemble_gfa_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip,
+                               uint64_t original_genome_length, const char* fasta_path, const char* gfa_path, katome_assembly** asm_out,
+                               katome_gfa_paths** gfa_out) {
+    return assemble_entry(PackedReads{packed, n_reads, read_len, skip}, s, original_genome_length,
+                          AssembleWant{asm_out, fasta_path, AssembleWant::GfaPaths, gfa_path, gfa_out});
 }
 int katome_assemble_gfa_files(const katome_settings* s, const char* const* paths, size_t n_paths, uint64_t original_genome_length, const char* fasta_path,
                               const char* gfa_path, katome_assembly** asm_out, katome_gfa_paths** gfa_out) {
-    Finish f{nullptr, nullptr};
-    KCHECK(assemble_gfa_finish(original_genome_length, fasta_path, gfa_path, asm_out, gfa_out, f));
-    return build_files_impl(s, paths, n_paths, f);
+    return assemble_entry(FileReads{paths, n_paths}, s, original_genome_length, AssembleWant{asm_out, fasta_path, AssembleWant::GfaPaths, gfa_path, gfa_out});
+}
+int katome_assemble_gfa_strands_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip,
+                                       uint64_t original_genome_length, const char* fasta_path, const char* gfa_path, katome_assembly** asm_out,
+                                       katome_gfa_strand_paths** gfa_out) {
+    return assemble_entry(PackedReads{packed, n_reads, read_len, skip}, s, original_genome_length,
+                          AssembleWant{asm_out, fasta_path, AssembleWant::GfaStrandPaths, gfa_path, nullptr, gfa_out});
 }
 int katome_assemble_gfa_strands_files(const katome_settings* s, const char* const* paths, size_t n_paths, uint64_t original_genome_length,
                                       const char* fasta_path, const char* gfa_path, katome_assembly** asm_out, katome_gfa_strand_paths** gfa_out) {
-    Finish f{nullptr, nullptr};
-    KCHECK(assemble_gfa_strands_finish(original_genome_length, fasta_path, gfa_path, asm_out, gfa_out, f));
-    return build_files_impl(s, paths, n_paths, f);
+    return assemble_entry(FileReads{paths, n_paths}, s, original_genome_length,
+                          AssembleWant{asm_out, fasta_path, AssembleWant::GfaStrandPaths, gfa_path, nullptr, gfa_out});
+}
+int katome_assemble_unique_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip,
+                                  uint64_t original_genome_length, const char* fasta_path, const char* unique_path, katome_assembly** asm_out,
+                                  katome_unique_assembly** unique_out) {
+    return assemble_entry(PackedReads{packed, n_reads, read_len, skip}, s, original_genome_length,
+                          AssembleWant{asm_out, fasta_path, AssembleWant::Unique, unique_path, nullptr, nullptr, unique_out});
 }
 int katome_assemble_unique_files(const katome_settings* s, const char* const* paths, size_t n_paths, uint64_t original_genome_length,
                                  const char* fasta_path, const char* unique_path, katome_assembly** asm_out, katome_unique_assembly** unique_out) {
-    Finish f{nullptr, nullptr};
-    KCHECK(assemble_unique_finish(original_genome_length, fasta_path, unique_path, asm_out, unique_out, f));
-    return build_files_impl(s, paths, n_paths, f);
+    return assemble_entry(FileReads{paths, n_paths}, s, original_genome_length,
+                          AssembleWant{asm_out, fasta_path, AssembleWant::Unique, unique_path, nullptr, nullptr, unique_out});
+}
+
+int katome_unitigs_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip,
+                          const char* stages, uint64_t original_genome_length, const char* out_path, katome_unitigs* out) {
+    return unitigs_entry(PackedReads{packed, n_reads, read_len, skip}, s, stages, original_genome_length, out_path, out, nullptr);
 }
 int katome_unitigs_files(const katome_settings* s, const char* const* paths, size_t n_paths, const char* stages, uint64_t original_genome_length,
                          const char* out_path, katome_unitigs* out) {
-    Finish f{nullptr, nullptr};
-    KCHECK(unitigs_finish(s, stages, original_genome_length, out_path, out, f));
-    return build_files_impl(s, paths, n_paths, f);
+    return unitigs_entry(FileReads{paths, n_paths}, s, stages, original_genome_length, out_path, out, nullptr);
+}
+int katome_unitigs_gfa_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip,
+                              const char* stages, uint64_t original_genome_length, const char* out_path, katome_unitigs_gfa* out) {
+    return unitigs_entry(PackedReads{packed, n_reads, read_len, skip}, s, stages, original_genome_length, out_path, nullptr, out);
 }
 int katome_unitigs_gfa_files(const katome_settings* s, const char* const* paths, size_t n_paths, const char* stages, uint64_t original_genome_length,
                              const char* out_path, katome_unitigs_gfa* out) {
-    Finish f{nullptr, nullptr};
-    KCHECK(unitigs_gfa_finish(s, stages, original_genome_length, out_path, out, f));
-    return build_files_impl(s, paths, n_paths, f);
+    return unitigs_entry(FileReads{paths, n_paths}, s, stages, original_genome_length, out_path, nullptr, out);
 }
-int katome_gfa_strands_files(const katome_settings* s, const char* const* paths, size_t n_paths, const char* stages, uint64_t original_genome_length,
-                             const char* out_path, katome_gfa_strands** out) {
-    Finish f{nullptr, nullptr};
-    KCHECK(gfa_strands_finish(s, stages, original_genome_length, out_path, out, f));
-    return build_files_impl(s, paths, n_paths, f);
+
+int katome_gfa_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip, const char* stages,
+                      uint64_t original_genome_length, const char* out_path, katome_gfa** out) {
+    return gfa_entry(PackedReads{packed, n_reads, read_len, skip}, s, stages, original_genome_length, out_path, out, nullptr, false);
 }
 int katome_gfa_files(const katome_settings* s, const char* const* paths, size_t n_paths, const char* stages, uint64_t original_genome_length,
                      const char* out_path, katome_gfa** out) {
-    Finish f{nullptr, nullptr};
-    KCHECK(gfa_finish(s, stages, original_genome_length, out_path, out, f));
-    return build_files_impl(s, paths, n_paths, f);
+    return gfa_entry(FileReads{paths, n_paths}, s, stages, original_genome_length, out_path, out, nullptr, false);
 }
-int katome_shrink_files(const katome_settings* s, const char* const* paths, size_t n_paths, katome_contigs** out) {
-    if (!out) { set_error("null argument"); return KATOME_E_ARG; }
-    *out = nullptr;
-    return build_files_impl(s, paths, n_paths, Finish{nullptr, out});
+int katome_gfa_strands_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip, const char* stages,
+                              uint64_t original_genome_length, const char* out_path, katome_gfa_strands** out) {
+    return gfa_entry(PackedReads{packed, n_reads, read_len, skip}, s, stages, original_genome_length, out_path, nullptr, out, true);
+}
+int katome_gfa_strands_files(const katome_settings* s, const char* const* paths, size_t n_paths, const char* stages, uint64_t original_genome_length,
+                             const char* out_path, katome_gfa_strands** out) {
+    return gfa_entry(FileReads{paths, n_paths}, s, stages, original_genome_length, out_path, nullptr, out, true);
 }
 
 // Stats<CollectionStats> for PtGraph (stats/collections.rs:137-168), from the host arrays
@@ -1495,3 +1391,5 @@ int katome_graph_stats(const katome_graph* g, katome_stats* st) {
 }
 
 }  // extern "C"
+
+#endif  // KATOME_HOST_RESULTS_ONLY
