@@ -253,6 +253,9 @@ int dev_hash_order_core(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, 
 // KATOME_FUSED_RECORDS=0: a list-fed level's records are written out before their first partition pass, as they were before that pass
 // could cut them out of the list itself
 inline bool fused_records_on() { static const bool on = env_flag("KATOME_FUSED_RECORDS", true); return on; }
+// KATOME_ENTRY_CUT=0: the kernels that make such records off the list (radix.hip ListSource, table.hip list_digit_counts_kernel) cut
+// them once per record, as they did before entry_cut.h, instead of once per list entry
+inline bool entry_cut_on() { static const bool on = env_flag("KATOME_ENTRY_CUT", true); return on; }
 // A level's records that are not written yet (table_list_to_records with a RecordSource): record p is sub-window p % span of list
 // entry p / span, in its level's orientation, with that entry's count.  While `pending`, *keys / *weights are not allocated; the first
 // partition pass (dev_key_order, dev_hash_order) makes its tiles from the list, gives the list up where the source owns it

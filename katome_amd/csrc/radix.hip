@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "edge_keys.h"
+#include "entry_cut.h"
 #include "lds_order.h"
 #include "s2_regions.h"
 
@@ -285,8 +286,14 @@ __global__ __launch_bounds__(BLOCK) void radix_offsets_kernel(u64* __restrict__ 
 // record's index by span once; a record q places behind that entry's first one lies in entry mulhi(q, inv), inv = 2^32 / span + 1
 // (q / span while q * span < 2^32).  Consecutive lanes read the same entry span times over: plain loads, the lines are shared.
 struct NoNextDigit {};
-template <int NWT, int NWK, bool RC, bool REP> struct ListSource {
-    static constexpr bool PLACED = false;
+// ENTRY (entry_cut.h): the tile's records are cut once per list ENTRY instead of once per record.  Before the ranking loop a thread
+// takes whole entries -- one load of the entry, one reverse complement for its span records, shifts by amounts all lanes share -- and
+// leaves the records that lie in the tile at their index in the tile's LDS buffer, which is free until the reorder; the ranking loop
+// then reads record idx there, neighbouring lanes neighbouring words, and only the count is still fetched per record.  The first and
+// the last entry of a tile straddle its ends (neither 4096 nor 2048 is a multiple of 5 or 6): their records outside are dropped.
+// The tile, its record order and so the pass's output are what load() gives.
+template <int NWT, int NWK, bool RC, bool REP, bool ENTRY_CUT = true> struct ListSource {
+    static constexpr bool PLACED = false, ENTRY = ENTRY_CUT;
     const u64* tiles; const u32* counts; u32 k, span, stride, inv;
     struct Origin { u64 t0; u32 o0; };
     __device__ __forceinline__ Origin origin(u64 base) const { const u64 t0 = base / span; return Origin{t0, (u32)(base - t0 * span)}; }
@@ -299,6 +306,26 @@ template <int NWT, int NWK, bool RC, bool REP> struct ListSource {
         key = level_orientation<NWK, RC, REP>(sub_window<NWT, NWK>(tile, k, span, stride, o), k);
         val = counts[t];
     }
+    // records [0, cnt) of the tile at `at` into skeys[idx * NWK ..]; the caller's barrier ends it
+    __device__ __forceinline__ void stage(const Origin& at, u32 cnt, u64* skeys, u32 tid) const {
+        const u32 n_ent = (at.o0 + cnt + span - 1) / span;          // (entries that hold a record of the tile: the last is (o0 + cnt - 1) / span)
+        for (u32 e = tid; e < n_ent; e += BLOCK) {
+            Key<NWT> tile;
+#pragma unroll
+            for (int w = 0; w < NWT; ++w) tile.w[w] = tiles[(at.t0 + e) * NWT + w];
+            const EntryCut<NWT, NWK, RC, REP> cut(tile, k, span, stride);
+            const u32 first = e * span - at.o0;                     // (index of the entry's record 0; wraps for records before the tile)
+            for (u32 o = 0; o < span; ++o) {
+                const u32 idx = first + o;
+                if (idx < cnt) {
+                    const Key<NWK> x = cut.record(o);
+#pragma unroll
+                    for (int w = 0; w < NWK; ++w) skeys[idx * NWK + w] = x.w[w];
+                }
+            }
+        }
+    }
+    __device__ __forceinline__ u32 count_of(const Origin& at, u32 idx) const { return counts[at.t0 + __umulhi(at.o0 + idx, inv)]; }
 };
 template <class Next> struct NextDigitOut {
     Next nx; uint8_t* out;
@@ -330,6 +357,7 @@ __global__ __launch_bounds__(BLOCK, KATOME_SORT_WAVES) void radix_scatter_kernel
     if (base >= n) return;                                  // (the grid is rounded up to 8 x xcd_tiles)
     u32 cnt = (u32)((n - base) < (u64)SORT_TILE ? (n - base) : (u64)SORT_TILE);
     for (u32 i = tid; i < (BLOCK / 64) * RADIX; i += BLOCK) (&whist[0][0])[i] = 0;
+    if constexpr (LISTED) if constexpr (Src::ENTRY) src.stage(src.origin(base), cnt, skeys, tid);      // (the records, once per entry; read below)
     __syncthreads();
 
     Key<NW> key[SORT_ITEMS]; u32 val[SORT_ITEMS]; u32 dig[SORT_ITEMS]; u32 rnk[SORT_ITEMS];
@@ -343,8 +371,13 @@ __global__ __launch_bounds__(BLOCK, KATOME_SORT_WAVES) void radix_scatter_kernel
         const bool valid = idx < cnt;
         u32 d = 0;
         if (valid) {
-            if constexpr (LISTED) src.load(from, idx, key[j], val[j]);
-            else {
+            if constexpr (LISTED) {
+                if constexpr (Src::ENTRY) {
+#pragma unroll
+                    for (int q = 0; q < NW; ++q) key[j].w[q] = skeys[idx * NW + q];
+                    val[j] = src.count_of(from, idx);
+                } else src.load(from, idx, key[j], val[j]);
+            } else {
 #if KATOME_STREAM_LOADS >= 1
             key[j] = load_key_stream<NW>(keys_in, in0 + idx);
             if (HAS_VAL) val[j] = __builtin_nontemporal_load(&vals_in[in0 + idx]);
@@ -934,8 +967,8 @@ int dev_partition_range(const uint64_t* d_vals, const uint32_t* idx_in, uint64_t
 }
 
 // ---- a first pass that makes its records from a list (RecordSource, common.h) ------------------------------------------------------
-template <int NWT, int NWK, bool RC, bool REP> static ListSource<NWT, NWK, RC, REP> list_source(const RecordSource& s) {
-    return ListSource<NWT, NWK, RC, REP>{s.tiles, s.counts, s.k, s.span, s.stride, (u32)((1ull << 32) / s.span) + 1};
+template <int NWT, int NWK, bool RC, bool REP, bool ENTRY> static ListSource<NWT, NWK, RC, REP, ENTRY> list_source(const RecordSource& s) {
+    return ListSource<NWT, NWK, RC, REP, ENTRY>{s.tiles, s.counts, s.k, s.span, s.stride, (u32)((1ull << 32) / s.span) + 1};
 }
 static bool source_by_key(const RecordSource& s) {          // dev_key_order's first pass can take it
     return s.rep && key_words_for_k(s.k) == 1 && fused_records_takes((u32)key_words_for_k(s.tile_bases), 1, true, s.span);
@@ -946,19 +979,20 @@ static bool source_by_hash(const RecordSource& s, u32 nw) {          // dev_hash
 // the first pass of dev_key_order over the records of s, into ka / wa (pb.first: their counts per tile)
 static int list_pass_by_key(const RecordSource& s, u64 n, u32 k, u64* ka, u32* wa, PassBuffers& pb, hipStream_t stream) {
     const LevelKeyDigit dg{2 * k - 16};
-    return with_bool(s.rc, [&](auto rcv) {
-        constexpr bool RC = decltype(rcv)::value;
+    return with_bool(s.rc, [&](auto rcv) { return with_bool(entry_cut_on(), [&](auto cutv) {
+        constexpr bool RC = decltype(rcv)::value, CUT = decltype(cutv)::value;
         if (key_words_for_k(s.tile_bases) == 2)
-            return radix_pass<1, true, LevelKeyDigit, true, NoNextDigit>(nullptr, nullptr, n, dg, ka, wa, pb, stream, true, nullptr, NoNextDigit{}, nullptr, list_source<2, 1, RC, true>(s));
-        return radix_pass<1, true, LevelKeyDigit, true, NoNextDigit>(nullptr, nullptr, n, dg, ka, wa, pb, stream, true, nullptr, NoNextDigit{}, nullptr, list_source<1, 1, RC, true>(s));
-    });
+            return radix_pass<1, true, LevelKeyDigit, true, NoNextDigit>(nullptr, nullptr, n, dg, ka, wa, pb, stream, true, nullptr, NoNextDigit{}, nullptr, list_source<2, 1, RC, true, CUT>(s));
+        return radix_pass<1, true, LevelKeyDigit, true, NoNextDigit>(nullptr, nullptr, n, dg, ka, wa, pb, stream, true, nullptr, NoNextDigit{}, nullptr, list_source<1, 1, RC, true, CUT>(s));
+    }); });
 }
 // the first pass of dev_hash_order over two-word records of s, leaving the second pass's digits
 static int list_pass_by_hash(const RecordSource& s, u64 n, u64* ka, u32* wa, PassBuffers& pb, uint8_t* digits, hipStream_t stream) {
     const HashDigit<2> dg{48u}, nx{56u};
-    return with_bool(s.rc, [&](auto rcv) {
-        return radix_pass<2, true, HashDigit<2>, true, HashDigit<2>>(nullptr, nullptr, n, dg, ka, wa, pb, stream, true, nullptr, nx, digits, list_source<2, 2, decltype(rcv)::value, false>(s));
-    });
+    return with_bool(s.rc, [&](auto rcv) { return with_bool(entry_cut_on(), [&](auto cutv) {
+        return radix_pass<2, true, HashDigit<2>, true, HashDigit<2>>(nullptr, nullptr, n, dg, ka, wa, pb, stream, true, nullptr, nx, digits,
+                                                                      list_source<2, 2, decltype(rcv)::value, false, decltype(cutv)::value>(s));
+    }); });
 }
 
 // order records by the table region they hash to (1 or 2 stable 8-bit passes over the top hash bits), so

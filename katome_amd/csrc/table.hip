@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "common.h"
+#include "entry_cut.h"
 #include "lds_plan.h"
 #include "seq_pair.h"
 #include "slot_bits.h"
@@ -660,7 +661,11 @@ __global__ __launch_bounds__(BLOCK) void list_to_records_hist_kernel(const u64* 
 // once; inside the tile the entry of record q (counted from that entry's first record) is mulhi(q, inv), inv = 2^32 / span + 1, which
 // is q / span while q * span < 2^32.  REP: the digit is bits 2k - 16 .. 2k - 9 of the representative orientation -- the sub-window's own
 // when its middle base says so, else the complement of its bases 4..7 from the right, in reverse: no reverse complement is built.
-template <int NWT, int NWK, bool RC, bool REP = false>
+// ENTRY (entry_cut.h): a thread takes a list entry instead of a record -- one load of it, one reverse complement where the hash wants
+// the canonical record, and for REP no cut at all: with s = 2 * stride * (span - 1 - o), window o's own digit is the tile's bits
+// s + 2k - 16 .. s + 2k - 9, the other one comes from its bits s + 8 .. s + 15 and bit s + k chooses, all at offsets every lane shares.
+// Only the records inside the tile are counted: its first and last entry straddle its ends.
+template <int NWT, int NWK, bool RC, bool REP = false, bool ENTRY = true>
 __global__ __launch_bounds__(BLOCK) void list_digit_counts_kernel(const u64* __restrict__ tiles, u64 n_tiles, u32 k, u32 span, u32 stride, u32 inv, u32 tile_keys,
                                                                    u32* __restrict__ digit_counts) {
     static_assert(BLOCK == 256, "one thread per digit");
@@ -671,6 +676,30 @@ __global__ __launch_bounds__(BLOCK) void list_digit_counts_kernel(const u64* __r
         __syncthreads();
         const u64 p0 = ot * tile_keys, t0 = p0 / span;
         const u32 o0 = (u32)(p0 - t0 * span), cnt = (u32)(n - p0 < (u64)tile_keys ? n - p0 : (u64)tile_keys);
+        if constexpr (ENTRY) {
+            const u32 n_ent = (o0 + cnt + span - 1) / span;
+            for (u32 e = threadIdx.x; e < n_ent; e += BLOCK) {
+                Key<NWT> tile;
+#pragma unroll
+                for (int w = 0; w < NWT; ++w) tile.w[w] = tiles[(t0 + e) * NWT + w];
+                const u32 first = e * span - o0;          // (index of the entry's record 0 in the tile; wraps for records before it)
+                if constexpr (REP) {
+                    for (u32 o = 0; o < span; ++o) {
+                        const u32 s = 2 * stride * (span - 1 - o);
+                        const u32 own = key_digit(tile, s + 2 * k - 16, 8);
+                        u32 v = ~key_digit(tile, s + 8, 8) & 255u;
+                        v = ((v & 0x0Fu) << 4) | (v >> 4);
+                        v = ((v & 0x33u) << 2) | ((v >> 2) & 0x33u);
+                        const u32 d = RC && key_digit(tile, s + k, 1) ? v : own;
+                        if (first + o < cnt) atomicAdd(&h[d], 1u);
+                    }
+                } else {
+                    const EntryCut<NWT, NWK, RC, false> cut(tile, k, span, stride);
+                    for (u32 o = 0; o < span; ++o)
+                        if (first + o < cnt) atomicAdd(&h[(u32)(hash_key(cut.record(o)) >> 48) & 255u], 1u);
+                }
+            }
+        } else
         for (u32 i = threadIdx.x; i < cnt; i += BLOCK) {
             const u32 q = o0 + i, tr = __umulhi(q, inv), o = q - tr * span;
             const u64 t = t0 + tr;
@@ -1242,8 +1271,9 @@ int table_list_to_records(const uint64_t* d_tiles, const uint32_t* d_counts, uin
         keys.release(); weights.release();
         KCHECK(first_counts->alloc(n_out_tiles * 256 * 4 + 16, stream));
         const uint32_t inv = (uint32_t)((1ull << 32) / span) + 1;
+        if (getenv("KATOME_LC_TRACE")) fprintf(stderr, "[entry_cut] %s\n", entry_cut_on() ? "once per list entry" : "once per record (KATOME_ENTRY_CUT=0)");
         KernelScope ks(K_RECORDS, stream, n_tiles);
-#define KATOME_LDC(NWT, NWK, REP) with_bool(rc, [&](auto rcv) { hipLaunchKernelGGL((list_digit_counts_kernel<NWT, NWK, decltype(rcv)::value, REP>), hgrid, block, 0, stream, d_tiles, n_tiles, k, span, stride, inv, tile_keys, first_counts->as<u32>()); return 0; })
+#define KATOME_LDC(NWT, NWK, REP) with_bool(rc, [&](auto rcv) { return with_bool(entry_cut_on(), [&](auto cutv) { hipLaunchKernelGGL((list_digit_counts_kernel<NWT, NWK, decltype(rcv)::value, REP, decltype(cutv)::value>), hgrid, block, 0, stream, d_tiles, n_tiles, k, span, stride, inv, tile_keys, first_counts->as<u32>()); return 0; }); })
         if (rep) { if (nwt == 2) KATOME_LDC(2, 1, true); else KATOME_LDC(1, 1, true); }
         else KATOME_LDC(2, 2, false);
 #undef KATOME_LDC
