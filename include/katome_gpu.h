@@ -1271,6 +1271,16 @@ int katome_dev_scan_counts(int device, const uint32_t *d_counts, uint64_t m, uin
 int katome_dev_list_first_pass(int device, const uint64_t *d_tiles, const uint32_t *d_counts, uint64_t n_tiles, uint32_t tile_bases,
                                uint32_t k, uint32_t span, uint32_t stride, int rc, int rep, int fused, uint64_t *d_keys,
                                uint32_t *d_weights, uint32_t *d_digit_counts, void *stream);
+/* test entry: a list-fed level of two-word records on its own, from the list to the list of its distinct (key, count) -- the records
+ * of katome_dev_list_first_pass (rep = 0) through both partition passes and the count in LDS.  packed: 1 -- where the sub-windows have
+ * 33 .. 39 bases the records carry their count in the free bits of their first word and there is no
+ * weights array (csrc/counted_key.h); 0 -- plain keys and weights.  *took_packed says which it was.  d_pass1_* / d_pass2_* (null: not
+ * wanted): the n_tiles * span records after the first and the second pass as plain keys ([n][2]) and weights.  d_out_keys /
+ * d_out_weights: room for n_tiles * span entries; *n_out of them are written, in no particular order (synchronises)                     */
+int katome_dev_count_in_key(int device, const uint64_t *d_tiles, const uint32_t *d_counts, uint64_t n_tiles, uint32_t tile_bases, uint32_t k,
+                            uint32_t span, uint32_t stride, int rc, int packed, uint64_t *d_pass1_keys, uint32_t *d_pass1_weights,
+                            uint64_t *d_pass2_keys, uint32_t *d_pass2_weights, uint64_t *d_out_keys, uint32_t *d_out_weights,
+                            uint64_t *n_out, int *took_packed, void *stream);
 /* test entry: the one partition pass that S2 of the ordered k-mer count takes when its writer placed it by its first digit.
  * used[256] (host): the keys of every region; region d lies from start[d] on in d_keys / d_weights / d_digits, start[] (257 of them,
  * the last one the arrays' length) being what katome_s2_region_starts gives for `used` -- every region a whole number of 4096-key

@@ -1091,6 +1091,17 @@ int katome_dev_list_first_pass(int device, const uint64_t* d_tiles, const uint32
     if (!span || tile_bases < k || (uint64_t)stride * (span - 1) + k > tile_bases || k < 9 || tile_bases > 64) { set_error("first pass off a list: the sub-windows do not lie in the tile"); return KATOME_E_ARG; }
     return dev_list_first_pass(d_tiles, d_counts, n_tiles, tile_bases, k, span, stride, rc != 0, rep != 0, fused != 0, d_keys, d_weights, d_digit_counts, (hipStream_t)stream);
 }
+int katome_dev_count_in_key(int device, const uint64_t* d_tiles, const uint32_t* d_counts, uint64_t n_tiles, uint32_t tile_bases, uint32_t k, uint32_t span,
+                            uint32_t stride, int rc, int packed, uint64_t* d_pass1_keys, uint32_t* d_pass1_weights, uint64_t* d_pass2_keys,
+                            uint32_t* d_pass2_weights, uint64_t* d_out_keys, uint32_t* d_out_weights, uint64_t* n_out, int* took_packed, void* stream) {
+    KCHECK(use_device(device));
+    if (!n_out || !took_packed || (n_tiles && (!d_tiles || !d_counts || !d_out_keys || !d_out_weights))) { set_error("null argument"); return KATOME_E_ARG; }
+    if (!d_pass1_keys != !d_pass1_weights || !d_pass2_keys != !d_pass2_weights) { set_error("count in key: a pass's keys and weights go together"); return KATOME_E_ARG; }
+    if (!span || tile_bases < k || (uint64_t)stride * (span - 1) + k > tile_bases || k < 9 || tile_bases > 64) { set_error("count in key: the sub-windows do not lie in the tile"); return KATOME_E_ARG; }
+    uint64_t* const pk[2] = {d_pass1_keys, d_pass2_keys}; uint32_t* const pw[2] = {d_pass1_weights, d_pass2_weights};
+    return dev_count_in_key_level(d_tiles, d_counts, n_tiles, tile_bases, k, span, stride, rc != 0, packed != 0, pk, pw, d_out_keys, d_out_weights, n_out, took_packed,
+                                  (hipStream_t)stream);
+}
 void katome_s2_region_starts(const uint64_t* used, uint64_t* start) {
     uint64_t cap[S2_REGIONS];
     for (uint32_t d = 0; d < S2_REGIONS; ++d) cap[d] = s2_tiles(used[d]) * S2_REGION_TILE;

@@ -271,13 +271,16 @@ struct RecordSource {
     size_t key_bytes = 0, weight_bytes = 0;
     hipStream_t stream = nullptr;
     DevBuf own_tiles, own_counts;
+    // (test entry katome_dev_count_in_key: where dev_hash_order leaves copies of the records after its first and its second pass, as
+    // plain keys and weights whichever form they travel in)
+    uint64_t* tap_keys[2] = {nullptr, nullptr}; uint32_t* tap_weights[2] = {nullptr, nullptr};
     uint64_t n_records() const { return n_tiles * span; }
     // the first pass is launched: the list is not needed again, the records' buffers are
     int first_pass_done() {
         pending = false; tiles = nullptr; counts = nullptr;
         own_tiles.release(); own_counts.release();
         if (int rc = keys->alloc(key_bytes, stream)) return rc;
-        return weights->alloc(weight_bytes, stream);
+        return weight_bytes ? weights->alloc(weight_bytes, stream) : (int)KATOME_OK;      // (0: the counts ride in the keys, counted_key.h)
     }
 };
 // which lists the first pass can take its records from: two-word tiles into two-word sub-tiles ordered by hash, and one- or two-word
@@ -293,6 +296,18 @@ int dev_region_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uin
 int dev_hash_order(const uint64_t* d_in, const uint32_t* w_in, uint64_t n, uint32_t nw, uint64_t* ka, uint64_t* kb, uint32_t* wa, uint32_t* wb,
                    const uint64_t** k_out, const uint32_t** w_out, uint32_t* group_bits, hipStream_t stream, uint32_t* first_counts = nullptr,
                    RecordSource* src = nullptr);
+// (true: dev_hash_order makes the records of src with their count in the key word, counted_key.h -- *w_out comes back
+// null, no weights buffer is touched, and what *k_out points at is unpacked with dev_counted_unpack or counted as it is)
+bool dev_hash_order_counts_in_key(const RecordSource* src, uint32_t nw, const uint32_t* first_counts);
+void dev_count_in_key_force(int v);          // (test entry: 0 / 1 -- the route whatever KATOME_COUNT_IN_KEY says; -1 -- the switch again)
+// test entry (katome_dev_count_in_key): a list-fed two-word level from the list to the list of distinct (key, count), as
+// tile_recs_to_kmer_records runs its mid level.  packed: 1 the counted-key route where the level fits, 0 plain keys and weights.
+// d_pass_keys / d_pass_weights (two each, null: not wanted): the records after the first and the second partition pass, unpacked.
+// d_out_keys / d_out_weights: room for n_tiles * span entries; *n_out distinct keys.  *took_packed: which form the records took.
+int dev_count_in_key_level(const uint64_t* d_tiles, const uint32_t* d_counts, uint64_t n_tiles, uint32_t tile_bases, uint32_t k, uint32_t span, uint32_t stride,
+                           bool rc, bool packed, uint64_t* const d_pass_keys[2], uint32_t* const d_pass_weights[2], uint64_t* d_out_keys,
+                           uint32_t* d_out_weights, uint64_t* n_out, int* took_packed, hipStream_t stream);
+int dev_counted_unpack(const uint64_t* d_in, uint64_t n, uint64_t* d_keys, uint32_t* d_weights, hipStream_t stream);
 // (src, here and in dev_key_order: records still to be made -- d_in / w_in and the second destination kb / wb are then taken from the
 // source once its first pass is launched, and first_counts are the counts table_list_to_records made for it)
 uint32_t dev_sort_tile_keys(uint32_t nw);

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "common.h"
+#include "counted_key.h"
 #include "lds_order.h"
 #include "lds_plan.h"
 #include "s2_regions.h"
@@ -73,6 +74,33 @@ __global__ __launch_bounds__(BLOCK) void hash_group_index_kernel(const u64* __re
         }
         index[g] = lo;
     }
+}
+
+// ... the same boundaries of records that carry their count in the key word (counted_key.h): the hash is the plain key's
+__global__ __launch_bounds__(BLOCK) void counted_group_index_kernel(const u64* __restrict__ keys, u64 n, u64* __restrict__ index) {
+    for (u64 g = (u64)blockIdx.x * BLOCK + threadIdx.x; g <= (1ull << 16); g += (u64)gridDim.x * BLOCK) {
+        u64 lo = 0, hi = n;
+        while (lo < hi) {
+            const u64 mid = lo + ((hi - lo) >> 1);
+            Key<2> a; a.w[0] = counted_plain_word(keys[mid * 2]); a.w[1] = keys[mid * 2 + 1];
+            if ((hash_key(a) >> 48) < g) lo = mid + 1; else hi = mid;
+        }
+        index[g] = lo;
+    }
+}
+// the way back: packed records split in place into plain keys and a weights array, for the kernels that take those
+__global__ __launch_bounds__(BLOCK) void counted_unpack_kernel(const u64* keys_in, u64 n, u64* keys_out, u32* __restrict__ w_out) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
+        const u64 w0 = keys_in[2 * i], w1 = keys_in[2 * i + 1];          // (keys_out may be keys_in: a thread reads its record before it writes it)
+        keys_out[2 * i] = counted_plain_word(w0); keys_out[2 * i + 1] = w1;
+        w_out[i] = counted_count_word(w0);
+    }
+}
+int dev_counted_unpack(const uint64_t* d_in, uint64_t n, uint64_t* d_keys, uint32_t* d_weights, hipStream_t stream) {
+    if (!n) return KATOME_OK;
+    hipLaunchKernelGGL(counted_unpack_kernel, dim3(grid_for(n, BLOCK, 256u * 32u)), dim3(BLOCK), 0, stream, d_in, n, d_keys, d_weights);
+    KCHECK_HIP(hipGetLastError());
+    return KATOME_OK;
 }
 
 // (EVEN_K: only a k-mer of even length can be its own reverse complement; for odd k -- the headline's k = 31 -- the read-out's count step
@@ -816,10 +844,15 @@ __global__ __launch_bounds__(LC_THREADS) void lds_count_wide_kernel(const u64* k
 // (LF_PER slots per thread: 7 -> 7168 slots of 16 + 4 bytes = 140 KiB; 4 -> 4096 slots = 80 KiB for groups of few distinct keys:
 // less to clear and to read out per group)
 constexpr u64 LF_SALT = 0x9E3779B97F4A7C15ull;
-template <bool RC, bool EVEN_K, int LF_PER>
+// COUNTED (counted_key.h): the records carry their count in the key word and there is no weights array.  After
+// the load the count is taken out of the word and the word made plain; from there on the kernel is the same -- the hash for slot and
+// step, A, B, the salt test, the read-out -- and the list it writes holds plain keys and u32 counts.
+// (a tile level's records, the only ones that come packed, are never oriented and never thresholded: COUNTED with one strand only)
+template <bool RC, bool EVEN_K, int LF_PER, bool COUNTED = false>
 __global__ __launch_bounds__(LC_THREADS) void lds_count_full_kernel(const u64* keys, const u32* wts, const u64* __restrict__ index, u32 groups_run, u32 k,
                                                                      u32 min_weight, u64* out_keys, u32* out_w, u64 out_cap, unsigned long long* cursor,
                                                                      unsigned long long* distinct, u32* err, u32 probe_limit) {
+    static_assert(!COUNTED || (!RC && !EVEN_K), "packed records are a tile level's");
     constexpr u32 LF_SLOTS = LfTable<LF_PER>::SLOTS;
     extern __shared__ unsigned long long lc_mem[];
     ulonglong2* slot = reinterpret_cast<ulonglong2*>(lc_mem);            // [LF_SLOTS]: {first word | OCC, second word ^ salt}
@@ -840,6 +873,13 @@ __global__ __launch_bounds__(LC_THREADS) void lds_count_full_kernel(const u64* k
             for (u32 u = 0; u < LU; ++u) {
                 const u64 i = i0 + (u64)u * LC_THREADS;
                 a[u] = 0; b[u] = 0; w[u] = 0;
+                if constexpr (COUNTED) {
+                    // (no branch around the load: past the group's end a lane reads the group's last record, which nobody looks at.  Under
+                    // `if (i < hi)` hipcc 7.2 waited for each of these loads before it issued the next -- four memory latencies a turn instead
+                    // of one, 8.46 ms at C3 against the plain form's 8.22 with its weights array and all)
+                    const u64 ic = i < hi ? i : hi - 1;
+                    const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(keys + 2 * ic); a[u] = v.x; b[u] = v.y;
+                } else
                 if (i < hi) { const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(keys + 2 * i); a[u] = v.x; b[u] = v.y; w[u] = wts ? wts[i] : 1u; }
             }
         };
@@ -850,6 +890,7 @@ __global__ __launch_bounds__(LC_THREADS) void lds_count_full_kernel(const u64* k
 #pragma unroll
             for (u32 u = 0; u < LU; ++u) {
                 if (i0 + (u64)u * LC_THREADS >= hi) continue;
+                if constexpr (COUNTED) { wv[u] = counted_count_word(ka[u]); ka[u] = counted_plain_word(ka[u]); }
                 Key<2> key; key.w[0] = ka[u]; key.w[1] = kb[u];
                 const u64 h = hash_key(key);
                 const unsigned long long A = ka[u] | OCC, B = kb[u] ^ LF_SALT;
@@ -1553,6 +1594,7 @@ int half_sort_finish(HalfSort& hs, DevBuf& edge_key, DevBuf& edge_weight, hipStr
 struct LcLevel {
     LcAux& aux;
     const u64* ko = nullptr; const u32* wo = nullptr;      // the ordered records (wo null: every record counts once)
+    bool counted = false;                                  // ... which carry their counts in the key word (counted_key.h; wo null)
     const u64* index = nullptr; u32 gbits = 16;
     uint64_t n; uint32_t k, nw; bool rc; uint32_t min_weight;
     u64* out_keys = nullptr; u32* out_w = nullptr; uint64_t out_cap = 0;
@@ -1585,6 +1627,7 @@ struct WholeKeys2 {                     // lds_count_full_kernel
     static constexpr int SMALL = 4, LARGE = 7, SLOT_BYTES = 20;
     static constexpr const char* WHAT = "whole keys";
     template <int PER, class... A> static int launch(const LcLevel& c, size_t lds, LcResult& r, u32 groups, A... tail) {
+        if (c.counted) return lc_launch(c.aux, lds_count_full_kernel<false, false, PER, true>, lds, c.n, r, c.ko, c.wo, c.index, groups, c.k, c.min_weight, tail...);
         return with_strands(c.rc, c.k, [&](auto rcv, auto even) {
             return lc_launch(c.aux, lds_count_full_kernel<decltype(rcv)::value, decltype(even)::value, PER>, lds, c.n, r, c.ko, c.wo, c.index, groups, c.k, c.min_weight, tail...);
         });
@@ -1677,11 +1720,13 @@ int records_to_edges_sorted(DevBuf& keys, DevBuf& weights, uint64_t n, uint32_t 
     c.n = n; c.k = k; c.nw = nw; c.rc = rc; c.min_weight = min_weight; c.split = split;
     // (weights not allocated: every record counts once; the passes move keys only.  Two-word keys: lds_count_wide_kernel)
     const bool unit = weights.p == nullptr && !(src && src->pending);
+    // (a list-fed level whose records carry their counts in the key word, counted_key.h: no weights either, until somebody unpacks them)
+    c.counted = !split && dev_hash_order_counts_in_key(src, nw, first_counts);
     if (unit && (nw < 2 || split)) { set_error("records without weights: keys of two or three words"); return KATOME_E_ARG; }
     {
         DevBuf kb(stream), wb(stream);
         KCHECK(kb.alloc((n + 1) * 8 * nw));
-        if (!unit) KCHECK(wb.alloc((n + 1) * 4));
+        if (!unit && !c.counted) KCHECK(wb.alloc((n + 1) * 4));
         // two passes: the first one's output goes to the scratch, the second one's lands in keys / weights again
         if (split) KCHECK(dev_hash_order_core(keys.as<u64>(), weights.as<u32>(), n, split->core_shift, split->core_bases, kb.as<u64>(), keys.as<u64>(), wb.as<u32>(),
                                               weights.as<u32>(), &c.ko, &c.wo, &c.gbits, stream));
@@ -1701,6 +1746,7 @@ int records_to_edges_sorted(DevBuf& keys, DevBuf& weights, uint64_t n, uint32_t 
         if (split)   hipLaunchKernelGGL(core_group_index_kernel, igrid, dim3(BLOCK), 0, stream, c.ko, n, c.gbits, split->core_shift, split->core_bases, index.as<u64>());
         else if (nw == 1) hipLaunchKernelGGL(hash_group_index_kernel<1>, igrid, dim3(BLOCK), 0, stream, c.ko, n, c.gbits, index.as<u64>());
         else if (nw == 3) hipLaunchKernelGGL(hash_group_index_kernel<3>, igrid, dim3(BLOCK), 0, stream, c.ko, n, c.gbits, index.as<u64>());
+        else if (c.counted) hipLaunchKernelGGL(counted_group_index_kernel, igrid, dim3(BLOCK), 0, stream, c.ko, n, index.as<u64>());
         else         hipLaunchKernelGGL(hash_group_index_kernel<2>, igrid, dim3(BLOCK), 0, stream, c.ko, n, c.gbits, index.as<u64>());
     }
     c.out_cap = (rc ? 2 : 1) * n + 1;
@@ -1715,6 +1761,15 @@ int records_to_edges_sorted(DevBuf& keys, DevBuf& weights, uint64_t n, uint32_t 
     bool done = false;
     if (nw == 2) KCHECK(count_whole_keys<WholeKeys2>(c, r, &done));
     if (nw == 3) KCHECK(count_whole_keys<WholeKeys3>(c, r, &done));
+    if (!done && c.counted) {
+        // the way back (the sample said no, KATOME_LC_FULL=0, a table filled, the salt word): the records become plain keys and a weights
+        // array where they lie -- the group index holds, the order is the same -- and the kernels below count them as they always did
+        if (c.ko != keys.as<u64>()) { set_error("counting in LDS: packed records outside their buffer"); return KATOME_E_DEVICE; }
+        KCHECK(weights.alloc((n + 1) * 4, stream));
+        KCHECK(dev_counted_unpack(c.ko, n, keys.as<u64>(), weights.as<u32>(), stream));
+        lc_trace("[count_in_key] %llu records unpacked into plain keys and a weights array\n", (unsigned long long)n);
+        c.wo = weights.as<u32>(); c.counted = false;
+    }
     const u32 R_try = lc_rounds_try(c.avg, lc_optimism(), fill);
     if (!done) KCHECK(count_packed(c, R_try, r, &done));
     if (!done) {
@@ -1735,6 +1790,31 @@ int records_to_edges_sorted(DevBuf& keys, DevBuf& weights, uint64_t n, uint32_t 
         }
         *n_edges = total;             // (the records: scattered over the owners' stretches of edge_key / edge_weight)
     }
+    return KATOME_OK;
+}
+
+// a list-fed two-word level on its own (test entry: see common.h)
+int dev_count_in_key_level(const uint64_t* d_tiles, const uint32_t* d_counts, uint64_t n_tiles, uint32_t tile_bases, uint32_t k, uint32_t span, uint32_t stride,
+                           bool rc, bool packed, uint64_t* const d_pass_keys[2], uint32_t* const d_pass_weights[2], uint64_t* d_out_keys,
+                           uint32_t* d_out_weights, uint64_t* n_out, int* took_packed, hipStream_t stream) {
+    *n_out = 0; *took_packed = 0;
+    if (key_words_for_k(tile_bases) != 2 || key_words_for_k(k) != 2) { set_error("count in key: tiles and sub-windows of two words"); return KATOME_E_UNSUPPORTED; }
+    if (!n_tiles) return KATOME_OK;
+    struct Forced { Forced(int v) { dev_count_in_key_force(v); } ~Forced() { dev_count_in_key_force(-1); } } forced(packed ? 1 : 0);
+    DevBuf mk(stream), mw(stream), counts(stream), ok(stream), ow(stream);
+    RecordSource src;
+    u64 n = 0, n_list = 0, distinct = 0;
+    KCHECK(table_list_to_records(d_tiles, d_counts, n_tiles, tile_bases, k, span, stride, rc, mk, mw, &n, stream, 0, &counts, false, &src));
+    if (!src.pending) { set_error("count in key: the records were written (KATOME_FUSED_RECORDS, KATOME_FUSED_HIST)"); return KATOME_E_UNSUPPORTED; }
+    for (int p = 0; p < 2; ++p) { src.tap_keys[p] = d_pass_keys[p]; src.tap_weights[p] = d_pass_weights[p]; }
+    *took_packed = dev_hash_order_counts_in_key(&src, 2, counts.as<u32>()) ? 1 : 0;
+    TileLevelScope tl;
+    KCHECK(records_to_edges_sorted(mk, mw, n, k, false, 0, ok, ow, &n_list, &distinct, stream, nullptr, counts.as<u32>(), nullptr, &src));
+    if (n_list > n) { set_error("count in key: %llu distinct keys of %llu records", (unsigned long long)n_list, (unsigned long long)n); return KATOME_E_DEVICE; }
+    KCHECK_HIP(hipMemcpyAsync(d_out_keys, ok.p, n_list * 16, hipMemcpyDeviceToDevice, stream));
+    KCHECK_HIP(hipMemcpyAsync(d_out_weights, ow.p, n_list * 4, hipMemcpyDeviceToDevice, stream));
+    KCHECK_HIP(hipStreamSynchronize(stream));
+    *n_out = n_list;
     return KATOME_OK;
 }
 

@@ -7,9 +7,11 @@
 #include <type_traits>
 
 #include "common.h"
+#include "counted_key.h"
 #include "edge_keys.h"
 #include "entry_cut.h"
 #include "lds_order.h"
+#include "lds_plan.h"
 #include "s2_regions.h"
 
 namespace katome {
@@ -108,6 +110,12 @@ template <int NW> struct CoreHashDigit {
 struct LevelKeyDigit {
     u32 shift;
     __device__ __forceinline__ u32 operator()(const Key<1>& k) const { return (u32)(k.w[0] >> shift) & (RADIX - 1); }
+};
+
+// ... and HashDigit<2> for a record that carries its count in its first word (counted_key.h): the hash is the plain key's
+struct CountedDigit {
+    u32 shift;
+    __device__ __forceinline__ u32 operator()(const Key<2>& k) const { return (u32)(hash_key(counted_plain(k)) >> shift) & (RADIX - 1); }
 };
 
 // ---- pass 1: per-workgroup digit histogram -> counts[block][digit] ----------------------------
@@ -293,7 +301,7 @@ struct NoNextDigit {};
 // the last entry of a tile straddle its ends (neither 4096 nor 2048 is a multiple of 5 or 6): their records outside are dropped.
 // The tile, its record order and so the pass's output are what load() gives.
 template <int NWT, int NWK, bool RC, bool REP, bool ENTRY_CUT = true> struct ListSource {
-    static constexpr bool PLACED = false, ENTRY = ENTRY_CUT;
+    static constexpr bool PLACED = false, ENTRY = ENTRY_CUT, COUNTED = false;
     const u64* tiles; const u32* counts; u32 k, span, stride, inv;
     struct Origin { u64 t0; u32 o0; };
     __device__ __forceinline__ Origin origin(u64 base) const { const u64 t0 = base / span; return Origin{t0, (u32)(base - t0 * span)}; }
@@ -327,6 +335,33 @@ template <int NWT, int NWK, bool RC, bool REP, bool ENTRY_CUT = true> struct Lis
     }
     __device__ __forceinline__ u32 count_of(const Origin& at, u32 idx) const { return counts[at.t0 + __umulhi(at.o0 + idx, inv)]; }
 };
+// The keys-only form of ListSource<2, 2, RC, false, true> (counted_key.h): stage() takes the entry's count once, and what it leaves
+// in the tile's LDS buffer is counted_pack(record, count).  The pass then moves keys alone (HAS_VAL = false: one trip through the LDS
+// buffer, no count fetched per record) with CountedDigit for HashDigit<2>.
+template <bool RC> struct CountedListSource {
+    static constexpr bool PLACED = false, ENTRY = true, COUNTED = true;
+    const u64* tiles; const u32* counts; u32 k, span, stride;
+    struct Origin { u64 t0; u32 o0; };
+    __device__ __forceinline__ Origin origin(u64 base) const { const u64 t0 = base / span; return Origin{t0, (u32)(base - t0 * span)}; }
+    __device__ __forceinline__ void stage(const Origin& at, u32 cnt, u64* skeys, u32 tid) const {
+        const u32 n_ent = (at.o0 + cnt + span - 1) / span;
+        for (u32 e = tid; e < n_ent; e += BLOCK) {
+            Key<2> tile;
+            tile.w[0] = tiles[(at.t0 + e) * 2]; tile.w[1] = tiles[(at.t0 + e) * 2 + 1];
+            const u32 c = counts[at.t0 + e];
+            const EntryCut<2, 2, RC, false> cut(tile, k, span, stride);
+            const u32 first = e * span - at.o0;                     // (wraps for records before the tile, as in ListSource)
+            for (u32 o = 0; o < span; ++o) {
+                const u32 idx = first + o;
+                if (idx < cnt) {
+                    const Key<2> x = counted_pack(cut.record(o), c);
+                    skeys[idx * 2] = x.w[0]; skeys[idx * 2 + 1] = x.w[1];
+                }
+            }
+        }
+    }
+};
+template <class Src, bool LISTED> constexpr bool listed_keys_only() { if constexpr (LISTED) return Src::COUNTED; else return false; }
 template <class Next> struct NextDigitOut {
     Next nx; uint8_t* out;
     __device__ __forceinline__ void put(u64 at, u32 d) const { out[at] = (uint8_t)d; }
@@ -338,7 +373,7 @@ __global__ __launch_bounds__(BLOCK, KATOME_SORT_WAVES) void radix_scatter_kernel
                                                                const u64* __restrict__ chunk_off, u64* __restrict__ keys_out,
                                                                u32* __restrict__ vals_out, u32 chunk_blocks, u32 xcd_tiles, NextDigitOut<Next> next, Src src) {
     constexpr bool NEXT = !std::is_same<Next, NoNextDigit>::value, PLACED = Src::PLACED, LISTED = !std::is_same<Src, ArraySource>::value && !PLACED;
-    static_assert(!LISTED || HAS_VAL, "a list's records carry its counts");
+    static_assert(!LISTED || HAS_VAL != listed_keys_only<Src, LISTED>(), "a list's records carry its counts: beside the key, or in it");
     constexpr int SORT_ITEMS = SortTile<NW>::ITEMS, SORT_TILE = SortTile<NW>::KEYS;
     extern __shared__ u64 smem[];
     u64* skeys = smem;                                            // [SORT_TILE * NW]; reused for the values afterwards
@@ -375,7 +410,7 @@ __global__ __launch_bounds__(BLOCK, KATOME_SORT_WAVES) void radix_scatter_kernel
                 if constexpr (Src::ENTRY) {
 #pragma unroll
                     for (int q = 0; q < NW; ++q) key[j].w[q] = skeys[idx * NW + q];
-                    val[j] = src.count_of(from, idx);
+                    if constexpr (HAS_VAL) val[j] = src.count_of(from, idx);
                 } else src.load(from, idx, key[j], val[j]);
             } else {
 #if KATOME_STREAM_LOADS >= 1
@@ -507,6 +542,7 @@ template <class Digit> struct DigitTimers { static constexpr int HIST = K_SORT_H
 template <int NW> struct DigitTimers<HashDigit<NW>> { static constexpr int HIST = K_HASH_HIST, SCATTER = K_HASH_SCATTER; };
 template <int NW> struct DigitTimers<HashTaggedDigit<NW>> { static constexpr int HIST = K_HASH_HIST, SCATTER = K_HASH_SCATTER; };
 template <> struct DigitTimers<LevelKeyDigit> { static constexpr int HIST = K_HASH_HIST, SCATTER = K_HASH_SCATTER; };
+template <> struct DigitTimers<CountedDigit> { static constexpr int HIST = K_HASH_HIST, SCATTER = K_HASH_SCATTER; };
 template <int NW> struct DigitTimers<CoreHashDigit<NW>> { static constexpr int HIST = K_HASH_HIST, SCATTER = K_HASH_SCATTER; };
 template <int NW> struct DigitTimers<OwnerDigit<NW>> { static constexpr int HIST = K_OWNER_HIST, SCATTER = K_OWNER_SCATTER; };
 template <> struct DigitTimers<SupermerOwnerDigit> { static constexpr int HIST = K_OWNER_HIST, SCATTER = K_OWNER_SCATTER; };
@@ -995,6 +1031,53 @@ static int list_pass_by_hash(const RecordSource& s, u64 n, u64* ka, u32* wa, Pas
     }); });
 }
 
+// Does dev_hash_order carry the records of s with their count in the key word (counted_key.h)?  Where its first pass
+// makes them off the list, per entry, and their width leaves the room.  KATOME_COUNT_IN_KEY=0: never.  The caller then allocates no
+// weights for the level and gets none back; the records it gets are packed.
+static int count_in_key_forced = -1;          // (the test entry's flag: 0 / 1 instead of the switch, -1 the switch)
+void dev_count_in_key_force(int v) { count_in_key_forced = v; }
+static bool count_in_key_on() {
+    static const bool on = env_flag("KATOME_COUNT_IN_KEY", true);
+    return count_in_key_forced < 0 ? on : count_in_key_forced != 0;
+}
+static bool list_feeds_hash_order(const RecordSource* src, u32 nw, int passes, const u32* first_counts) {
+    return src && src->pending && passes == 2 && first_counts && digit_stream_pays((int)nw) && !unstable_first() && source_by_hash(*src, nw);
+}
+// Packed records pay where lds_count_full_kernel counts them as they are; where it refuses the level they are unpacked first, a pass
+// over all of them (30-fold coverage of 10^9 bases, 2.9 * 10^9 mid records: 722 / 725 -> 730 / 726 ms per build).  It refuses groups
+// of more distinct keys than LfTable<7>::FILL, and a level has about as many distinct records as the list it is cut from has
+// entries, or more (C3: 1.64 times as many): a list of more entries to a group than that keeps the plain form.  A guess about time
+// only -- either form counts any level.
+static bool counted_list_small_enough(const RecordSource& s) { return (s.n_tiles >> 16) <= (u64)LfTable<7>::FILL; }
+bool dev_hash_order_counts_in_key(const RecordSource* src, uint32_t nw, const uint32_t* first_counts) {
+    return list_feeds_hash_order(src, nw, 2, first_counts) && counted_fits(src->k) && entry_cut_on() && count_in_key_on() && counted_list_small_enough(*src);
+}
+static int tap_records(const RecordSource& s, int pass, const u64* k, const u32* w, u64 n, int nw, hipStream_t stream) {      // (RecordSource::tap_keys)
+    if (!s.tap_keys[pass]) return KATOME_OK;
+    KCHECK_HIP(hipMemcpyAsync(s.tap_keys[pass], k, n * 8 * nw, hipMemcpyDeviceToDevice, stream));
+    KCHECK_HIP(hipMemcpyAsync(s.tap_weights[pass], w, n * 4, hipMemcpyDeviceToDevice, stream));
+    return KATOME_OK;
+}
+// the two passes of that route: the first makes packed records off the list into ka, the second orders them into the source's keys
+static int counted_hash_order(RecordSource& s, u64 n, u64* ka, PassBuffers& pb, const u64** k_out, hipStream_t stream) {
+    DevBuf digits(stream);
+    KCHECK(digits.alloc(digit_stream_bytes(n, 2)));
+    const CountedDigit dg{48u}, nx{56u};
+    KCHECK(with_bool(s.rc, [&](auto rcv) {
+        constexpr bool RC = decltype(rcv)::value;
+        return radix_pass<2, false, CountedDigit, true, CountedDigit>(nullptr, nullptr, n, dg, ka, nullptr, pb, stream, true, nullptr, nx, digits.as<uint8_t>(),
+                                                                        CountedListSource<RC>{s.tiles, s.counts, s.k, s.span, s.stride});
+    }));
+    if (s.tap_keys[0]) KCHECK(dev_counted_unpack(ka, n, s.tap_keys[0], s.tap_weights[0], stream));
+    s.weight_bytes = 0;          // (no weights on this route; whoever unpacks the records allocates them)
+    KCHECK(s.first_pass_done());
+    u64* const kb = s.keys->as<u64>();
+    KCHECK((radix_pass<2, false, CountedDigit>(ka, nullptr, n, nx, kb, nullptr, pb, stream, false, digits.as<uint8_t>())));
+    if (s.tap_keys[1]) KCHECK(dev_counted_unpack(kb, n, s.tap_keys[1], s.tap_weights[1], stream));
+    *k_out = kb;
+    return KATOME_OK;
+}
+
 // order records by the table region they hash to (1 or 2 stable 8-bit passes over the top hash bits), so
 // that the insert kernel that follows works through the table one cache-sized region at a time.
 // Result lands in `bufs[passes & 1]` where bufs = {scratch_a, scratch_b}; returns that pointer.
@@ -1005,10 +1088,27 @@ static int region_order_t(const u64* d_in, const u32* w_in, u64 n, int passes, u
     KCHECK(pb.init(n, NW, stream));
     // (src: records still to be made.  Where this order's first pass cannot make them, they are written now; either way the input
     // and the second destination are the source's buffers)
-    const bool listed = src && src->pending && passes == 2 && first_counts && digit_stream_pays(NW) && !unstable_first() && source_by_hash(*src, NW);
+    const bool listed = list_feeds_hash_order(src, NW, passes, first_counts);
+    if (src && src->pending && order_trace()) {          // (one line per list-fed level: which form its records take)
+        const bool counted = passes == 2 && dev_hash_order_counts_in_key(src, NW, first_counts);
+        fprintf(stderr, "[count_in_key] %llu records of %u bases: %s\n", (unsigned long long)n, src->k,
+                counted ? "count in the key word, no weights array"
+                : !listed ? "plain keys and a weights array (records written before their first pass)"
+                : !counted_fits(src->k) ? "plain keys and a weights array (no room in the key word)"
+                : !entry_cut_on() ? "plain keys and a weights array (KATOME_ENTRY_CUT=0)"
+                : !counted_list_small_enough(*src) ? "plain keys and a weights array (more keys to a group than the whole-key table holds)"
+                : "plain keys and a weights array (KATOME_COUNT_IN_KEY=0)");
+    }
     if (src && src->pending && !listed) {
         KCHECK(table_materialise_records(*src));
         d_in = kb = src->keys->as<u64>(); w_in = wb = src->weights->as<u32>();
+    }
+    if constexpr (NW == 2) if (passes == 2 && dev_hash_order_counts_in_key(src, NW, first_counts)) {
+        pb.first = first_counts;
+        if (order_trace())
+            fprintf(stderr, "[order] by hash: %llu records of 2 words, first pass counted from its writer's counts, second from the digit stream\n", (unsigned long long)n);
+        *w_out = nullptr;
+        return counted_hash_order(*src, n, ka, pb, k_out, stream);
     }
     // (first_counts: the first pass's digit counts per tile, [ceil(n / dev_sort_tile_keys)][256], made while the records were written;
     // the pass works in that buffer and leaves prefixes in it)
@@ -1029,6 +1129,7 @@ static int region_order_t(const u64* d_in, const u32* w_in, u64 n, int passes, u
                 const HashDigit<NW> nx{56u};
                 if (listed) {
                     if constexpr (NW == 2) KCHECK(list_pass_by_hash(*src, n, kdst[0], wdst[0], pb, digits.as<uint8_t>(), stream));
+                    KCHECK(tap_records(*src, 0, kdst[0], wdst[0], n, NW, stream));
                     KCHECK(src->first_pass_done());          // (the list may go; the second pass's destination comes only now)
                     kdst[1] = src->keys->as<u64>(); wdst[1] = src->weights->as<u32>();
                     kin = kdst[0]; win = wdst[0];
@@ -1051,6 +1152,7 @@ static int region_order_t(const u64* d_in, const u32* w_in, u64 n, int passes, u
         else      KCHECK((radix_pass<NW, false>(kin, nullptr, n, dg, kdst[p & 1], nullptr, pb, stream, have)));
         kin = kdst[p & 1]; win = w_in ? wdst[p & 1] : nullptr;
     }
+    if (listed) KCHECK(tap_records(*src, 1, kin, win, n, NW, stream));
     *k_out = kin; *w_out = win;
     return KATOME_OK;
 }
