@@ -460,6 +460,97 @@ typedef struct {
 int katome_dev_shrink_coverage(katome_builder *b, uint32_t mode, katome_dev_contigs *out, katome_dev_coverage *cov,
                                double *host_ms, void *stream);
 
+/* ---- depth of any sequence against the graph (csrc/depth.hip) ---------------------------------------------------------------------
+ * Every window of every query sequence is looked up among the edges of the finalized graph AS IT STANDS NOW -- after whichever
+ * stages have run, in either numbering -- and reduced per sequence; no record array is made in between.
+ * Query: n_seqs sequences in d_seq (seq_bytes bytes); sequence s starts at byte d_byte_off[s] ([n_seqs]) and has d_len[s] bases.
+ *   KATOME_DEPTH_PACKED: 2-bit packed, 4 bases per byte, every sequence starting on a byte (katome_dev_extract_var's input);
+ *   KATOME_DEPTH_ASCII:  one byte per base; upper-case A, C, G, T are bases, EVERY other byte (N, lower case, a newline) is not.
+ * Windows: sequence s has max(0, len_s - k + 1) of them; one shorter than k has none and is not an error.  d_seq_window_off is the
+ *   exclusive prefix of those counts ([n_seqs + 1]); window w of the call belongs to the sequence whose range holds w.
+ * A window's k-mer is looked up as spelled.  (A reverse-complement build holds both strands as edges: the forward lookup is complete.)
+ *   present: the k-mer is edge e.  Value e -- the index in katome_dev_current_graph's arrays --, weight edge_weight[e] as it is now;
+ *            an edge of weight 0 is still present.
+ *   KATOME_DEPTH_EITHER_STRAND: a window whose k-mer is no edge but whose reverse complement is edge e is present too, with value
+ *            e | KATOME_DEPTH_REVERSE and weight edge_weight[e].  A palindrome is found forward.
+ *   invalid: under ASCII, a window that covers a byte other than A, C, G, T.  Counted in n_invalid / d_seq_invalid, not present,
+ *            value KATOME_DEPTH_INVALID.  PACKED has none.
+ *   absent:  every other window, value KATOME_DEPTH_ABSENT.
+ * Per sequence: d_seq_present / d_seq_invalid count its present / invalid windows, d_seq_sum is the 64-bit sum of the present
+ *   windows' weights, d_seq_min / d_seq_max the smallest / largest of them (nothing present: min = all ones, max = 0).
+ * Totals: n_present, n_invalid, weight_sum are the arrays' sums; n_edges is the graph's edge count.
+ * KATOME_DEPTH_WINDOWS: d_window_edge[w] is window w's value.  KATOME_DEPTH_EDGE_HITS: d_edge_hits[e] is the number of present
+ *   windows OF THIS CALL whose value names e on either strand (nothing accumulates across calls), n_edges_hit the edges with a
+ *   count above 0.  Without the flag the pointer is NULL (n_edges_hit 0) and the array is neither allocated nor written.
+ * A graph that holds one k-mer on several edges (BFCounter input lists it so) answers with one of them.
+ * Status: no sequences or no edges: well-formed zero results, KATOME_OK.  Before katome_dev_finalize, NULL out, an unknown encoding
+ *   or flag bit: KATOME_E_ARG.  Offsets that do not ascend, or a sequence that runs past seq_bytes (PACKED: d_byte_off[s] +
+ *   ceil(len / 4); ASCII: + len): KATOME_E_ARG naming the sequence, found on the device BEFORE anything is read through them.
+ *   2^32 windows or more in one call: KATOME_E_UNSUPPORTED with the number; the caller batches.
+ * Memory: the lookup keeps an index in the builder between calls -- a directory of at most n_edges / 8 eight-byte entries over the
+ *   top bits of the keys and, where d_edge_key does not ascend strictly (first-seen order, or after removals), a sorted copy of the
+ *   keys with the permutation back: 8 * key_words + 4 bytes per edge (katome_dev_depth_index_bytes: what it holds now).  Every call
+ *   that changes the set or the order of the edges drops it (finalize, remove_dead_paths, remove_weak_edges, standardize_edges);
+ *   weights are read from d_edge_weight, so standardize_contigs needs no rebuild.  A call takes 28 bytes per sequence and, when
+ *   asked, 8 per window and 4 per edge.
+ * The result has its own buffers, owned by the builder until its next katome_dev_depth or destroy; no other result and nothing in
+ * the graph is touched.  The call synchronises.  Profile phase "depth", kernels "k:depth_kernel" and "k:depth_index".
+ * Not offered: a sharded query without a gather (katome_depth_paths gathers), k outside 3..63, lower-case bases as bases.                         */
+#define KATOME_DEPTH_PACKED        0u
+#define KATOME_DEPTH_ASCII         1u
+#define KATOME_DEPTH_EITHER_STRAND 1u   /* flags */
+#define KATOME_DEPTH_WINDOWS       2u
+#define KATOME_DEPTH_EDGE_HITS     4u
+#define KATOME_DEPTH_ABSENT   0xFFFFFFFFFFFFFFFFull
+#define KATOME_DEPTH_INVALID  0xFFFFFFFFFFFFFFFEull
+#define KATOME_DEPTH_REVERSE  0x8000000000000000ull
+typedef struct {
+    uint64_t  n_seqs, n_windows, n_present, n_invalid, n_edges, n_edges_hit;
+    uint64_t  weight_sum;
+    uint64_t *d_seq_present, *d_seq_invalid, *d_seq_sum;   /* [n_seqs] */
+    uint32_t *d_seq_min, *d_seq_max;                       /* [n_seqs] */
+    uint64_t *d_seq_window_off;                            /* [n_seqs + 1] */
+    uint64_t *d_window_edge;                               /* [n_windows] or NULL */
+    uint32_t *d_edge_hits;                                 /* [n_edges]  or NULL */
+} katome_dev_depth_result;             /* (C has one name space for types and functions: the struct cannot share the entry's name) */
+int katome_dev_depth(katome_builder *b, uint32_t encoding, uint32_t flags, const uint8_t *d_seq, uint64_t seq_bytes,
+                     const uint64_t *d_byte_off, const uint32_t *d_len, uint64_t n_seqs, katome_dev_depth_result *out, void *stream);
+uint64_t katome_dev_depth_index_bytes(katome_builder *b);      /* device bytes the kept index holds now (0: none is kept) */
+/* The same kernels on the caller's arrays, like the other *_arrays entries: n_edges keys (katome_record_words(k) words each) in ANY
+ * order but distinct -- two equal keys are KATOME_E_ARG naming one such pair --, their weights, the query as above; the caller's
+ * per-sequence arrays ([n_seqs], d_seq_window_off [n_seqs + 1]), d_window_edge (room for window_cap values; needed with
+ * KATOME_DEPTH_WINDOWS, KATOME_E_ARG if the windows do not fit) and d_edge_hits ([n_edges]; needed with KATOME_DEPTH_EDGE_HITS).
+ * totals: {n_windows, n_present, n_invalid, weight_sum, n_edges_hit}.  The index is built and dropped inside the call.      */
+/* The same from files, with host arrays (csrc/host_build.cpp): the graph is built from the read files exactly as
+ * katome_build_files_staged builds it (an empty `stages` is allowed in either numbering; stage letters need
+ * KATOME_FLAG_FIRST_SEEN_ORDER), then EVERY record of the query files is queried, in file order, in ASCII, in batches under the
+ * window limit.  query_file_type: 0 FASTA (a record's lines are joined) or 1 FASTQ; BFCounter (2) is KATOME_E_ARG.  The query
+ * scanner drops nothing: a record with an N keeps its valid windows, one shorter than k (or empty) is a record without windows and
+ * no short-read error.  A query path that is missing, a directory or unreadable gives the ingest's own status (KATOME_E_PATH ...),
+ * a malformed record KATOME_E_PARSE.  flags: KATOME_DEPTH_EITHER_STRAND, KATOME_DEPTH_EDGE_HITS (edge_hits is NULL without it); the
+ * result has no per-window array, so KATOME_DEPTH_WINDOWS, like an unknown bit, is KATOME_E_ARG.  Names of query records are not kept.
+ * settings.n_devices > 1: the query runs on the graph gathered to the first GPU, which takes a first-seen build (the gather's own
+ * rule; a packed-key build on several GPUs is KATOME_E_ARG) and one that can be gathered (else the gather's KATOME_E_UNSUPPORTED).
+ * A sharded query without a gather is not offered.  Free with katome_depth_free.
+ * (The entry is katome_depth_PATHS: the *_files names are the halves of the files / packed pairs, every one of which has a twin that
+ * takes packed reads; a query has two sets of paths and no such twin.)                                                       */
+typedef struct {
+    uint64_t  read_bytes;                                  /* of the reads the graph was built from                */
+    uint64_t  n_records, n_windows, n_present, n_invalid, n_edges, n_edges_hit, weight_sum;
+    const uint64_t *seq_present, *seq_invalid, *seq_sum;   /* [n_records], in file order                            */
+    const uint32_t *seq_min, *seq_max;                     /* [n_records]                                           */
+    const uint32_t *edge_hits;                             /* [n_edges] or NULL                                     */
+} katome_depth;
+int  katome_depth_paths(const katome_settings *s, const char *const *read_paths, size_t n_read_paths, const char *stages,
+                        uint64_t original_genome_length, const char *const *query_paths, size_t n_query_paths,
+                        uint32_t query_file_type, uint32_t flags, katome_depth **out);
+void katome_depth_free(katome_depth *d);
+int katome_dev_depth_arrays(int device, uint32_t k, const uint64_t *d_edge_key, const uint32_t *d_edge_weight, uint64_t n_edges,
+                            uint32_t encoding, uint32_t flags, const uint8_t *d_seq, uint64_t seq_bytes, const uint64_t *d_byte_off,
+                            const uint32_t *d_len, uint64_t n_seqs, uint64_t *d_seq_present, uint64_t *d_seq_invalid,
+                            uint64_t *d_seq_sum, uint32_t *d_seq_min, uint32_t *d_seq_max, uint64_t *d_seq_window_off,
+                            uint64_t *d_window_edge, uint64_t window_cap, uint32_t *d_edge_hits, uint64_t totals[5], void *stream);
+
 /* ---- collapse: the contigs, their text, FASTA and stats (collapser.rs:25-273, asm/mod.rs:57-72, stats/contigs.rs:31-89) --------
  * Collapsable::collapse is `self.shrink()` followed by a walk that consumes edge weights one at a time and swap-removes edges
  * and nodes as it goes: which contigs come out, and in which order, depends on petgraph's indices at every step.  As with the

@@ -62,6 +62,21 @@ class DevCoverage(C.Structure):
     _fields_ = [("n_edges", C.c_uint64), ("d_kmer_sum", C.c_void_p), ("d_kmer_min", C.c_void_p), ("d_kmer_max", C.c_void_p)]
 
 
+class Depth(C.Structure):
+    """katome_depth"""
+    _fields_ = [("read_bytes", C.c_uint64), ("n_records", C.c_uint64), ("n_windows", C.c_uint64), ("n_present", C.c_uint64), ("n_invalid", C.c_uint64),
+                ("n_edges", C.c_uint64), ("n_edges_hit", C.c_uint64), ("weight_sum", C.c_uint64), ("seq_present", u64p), ("seq_invalid", u64p),
+                ("seq_sum", u64p), ("seq_min", C.POINTER(C.c_uint32)), ("seq_max", C.POINTER(C.c_uint32)), ("edge_hits", C.POINTER(C.c_uint32))]
+
+
+class DevDepth(C.Structure):
+    """katome_dev_depth_result"""
+    _fields_ = [("n_seqs", C.c_uint64), ("n_windows", C.c_uint64), ("n_present", C.c_uint64), ("n_invalid", C.c_uint64), ("n_edges", C.c_uint64),
+                ("n_edges_hit", C.c_uint64), ("weight_sum", C.c_uint64), ("d_seq_present", C.c_void_p), ("d_seq_invalid", C.c_void_p),
+                ("d_seq_sum", C.c_void_p), ("d_seq_min", C.c_void_p), ("d_seq_max", C.c_void_p), ("d_seq_window_off", C.c_void_p),
+                ("d_window_edge", C.c_void_p), ("d_edge_hits", C.c_void_p)]
+
+
 class DevAssembly(C.Structure):
     _fields_ = [("n_contigs", C.c_uint64), ("text_bytes", C.c_uint64), ("layout", C.c_uint32), ("_pad", C.c_uint32),
                 ("d_contig_off", C.c_void_p), ("d_contig_len", C.c_void_p), ("d_text", C.c_void_p)]
@@ -276,6 +291,11 @@ SYMBOLS = {
     "katome_dev_shrink": (_i, [_vp, C.POINTER(DevContigs), _vp]),
     "katome_dev_shrink_mode": (_i, [_vp, C.c_uint32, C.POINTER(DevContigs), C.POINTER(C.c_double), _vp]),
     "katome_dev_shrink_coverage": (_i, [_vp, C.c_uint32, C.POINTER(DevContigs), C.POINTER(DevCoverage), C.POINTER(C.c_double), _vp]),
+    "katome_dev_depth": (_i, [_vp, _u32, _u32, _vp, _u64, _vp, _vp, _u64, C.POINTER(DevDepth), _vp]),
+    "katome_dev_depth_index_bytes": (_u64, [_vp]),
+    "katome_depth_paths": (_i, [C.POINTER(Settings), _pp, _sz, C.c_char_p, _u64, _pp, _sz, _u32, _u32, C.POINTER(C.POINTER(Depth))]),
+    "katome_depth_free": (None, [C.POINTER(Depth)]),
+    "katome_dev_depth_arrays": (_i, [_i, _u32, _vp, _vp, _u64, _u32, _u32, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, u64p, _vp]),
     "katome_dev_collapse": (_i, [_vp, _u32, C.POINTER(DevAssembly), C.POINTER(CollapseStats), _vp]),
     "katome_dev_contigs_text": (_i, [_vp, C.POINTER(DevContigs), _u32, C.POINTER(DevAssembly), _vp]),
     "katome_dev_pieces_text": (_i, [_i, _u32, _vp, _vp, _u64, _vp, _u64, _u32, _vp, _vp, _u64, _vp, _u64, u64p, u64p, _vp]),
@@ -400,6 +420,9 @@ SYMBOLS = {
 # test entries that the library of an older commit, loaded with KATOME_LIB for an A/B of the benchmark, does not have: that library
 # loads without them (and a test that calls one fails on the missing attribute); every other symbol must be there
 _TEST_ENTRIES_AFTER_AB = {"katome_dev_count_in_key"}
+# public entries that the library of the commit before them lacks and the benchmark does not call: passed over ONLY in a library
+# named by KATOME_LIB -- the tree's own library must have every symbol
+_ENTRIES_AFTER_AB = {"katome_dev_depth", "katome_dev_depth_index_bytes", "katome_dev_depth_arrays", "katome_depth_paths", "katome_depth_free"}
 
 
 def lib_path():
@@ -417,6 +440,8 @@ def lib():
         L = C.CDLL(path)
         for name, (res, args) in SYMBOLS.items():
             if name in _TEST_ENTRIES_AFTER_AB and not hasattr(L, name):
+                continue
+            if name in _ENTRIES_AFTER_AB and os.environ.get("KATOME_LIB") and not hasattr(L, name):
                 continue
             fn = getattr(L, name)
             fn.restype = res

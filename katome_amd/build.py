@@ -293,6 +293,23 @@ def _assemble_gfa_result(rc, ap, gp, cls=GfaPaths):
     return result
 
 
+class Depth(_COwned):
+    """result of GpuGraph.depth (katome_depth_paths; include/katome_gpu.h has the definitions): per query record, in file order,
+    seq_present, seq_invalid, seq_sum (uint64) and seq_min, seq_max (uint32; nothing present: all ones and 0); the totals; edge_hits
+    (uint32 per edge of the graph) when asked for, else None.  Keeps the C result until it is collected."""
+    _free = "katome_depth_free"
+
+    def __init__(self, dp):
+        super().__init__(dp)
+        d = dp.contents
+        for f in ("read_bytes", "n_records", "n_windows", "n_present", "n_invalid", "n_edges", "n_edges_hit", "weight_sum"):
+            setattr(self, f, int(getattr(d, f)))
+        n = self.n_records
+        self.seq_present, self.seq_invalid, self.seq_sum = _array(d.seq_present, n), _array(d.seq_invalid, n), _array(d.seq_sum, n)
+        self.seq_min, self.seq_max = _array(d.seq_min, n, np.uint32), _array(d.seq_max, n, np.uint32)
+        self.edge_hits = (_array(d.edge_hits, self.n_edges, np.uint32) if d.edge_hits else None)
+
+
 def _gfa_result(rc, gp, cls=Gfa):
     """a path that could not be created: the GFA was made all the same, and travels with the exception (`.result`)"""
     if rc != 0:
@@ -528,6 +545,22 @@ class GpuGraph:
                           first_seen_order=True, n_devices=n_devices, ranks_share_device=ranks_share_device)
         return GpuGraph._assemble_with(_Reads.packed(packed, n_reads, read_len, skip), s, *GpuGraph._WITH_UNIQUE, original_genome_length,
                                        fasta_file, unique_file)
+
+    # ---- depth of query files against the graph ----------------------------------------------------
+    @staticmethod
+    def depth(input_files, ft, reverse_complement, query_files, query_ft, k=None, stages="", threshold=0, original_genome_length=0, device=0,
+              n_devices=1, first_seen_order=None, ranks_share_device=False, either_strand=False, edge_hits=False):
+        """the build from the read files as create() runs it (stage letters as there; they need the reference's numbering), then every
+        record of the query files (FASTA or FASTQ) looked up in the graph, in file order (katome_depth_paths) -> Depth.
+        first_seen_order: None = whenever stage letters or several devices ask for it.  k: None = the global k"""
+        fso = bool(stages) or n_devices > 1 if first_seen_order is None else first_seen_order
+        s = make_settings(K_SIZE if k is None else k, ft, reverse_complement, threshold, device, first_seen_order=fso, n_devices=n_devices,
+                          ranks_share_device=ranks_share_device)
+        dp = C.POINTER(_lib.Depth)()
+        _check(_lib.lib().katome_depth_paths(C.byref(s), _paths(input_files), len(input_files), (stages or "").encode(), original_genome_length,
+                                             _paths(query_files), len(query_files), int(query_ft), (1 if either_strand else 0) | (4 if edge_hits else 0),
+                                             C.byref(dp)))
+        return Depth(dp)
 
     # ---- the unitig graph as GFA 1 ---------------------------------------------------------------
     @staticmethod

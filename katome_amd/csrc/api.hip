@@ -674,6 +674,7 @@ int katome_dev_remove_weak_edges(katome_builder* b, uint32_t threshold, void* st
     if (b->finalized && b->first_seen) {
         // on the finished graph, with petgraph's numbering (retain_edges / retain_nodes: descending swap_removes)
         KCHECK_HIP(hipSetDevice(b->s.device));
+        b->depth_index.drop();
         KCHECK(weak_edges_ordered(b, threshold, stream));
         KCHECK(dev_labels(b->edge_key.as<u64>(), b->n_edges, b->s.k, b->edge_label.as<uint8_t>(), stream));
         KCHECK_HIP(hipStreamSynchronize(stream));
@@ -706,6 +707,7 @@ int katome_dev_finalize(katome_builder* b, katome_dev_graph* out, void* stream_)
     hipStream_t stream = (hipStream_t)stream_;
     if (b && b->finalized) return out ? katome_dev_current_graph(b, out) : KATOME_OK;      // (also: a graph installed by katome_dist_gather)
     KCHECK(katome_dev_edges(b, nullptr, nullptr, nullptr, stream_));
+    b->depth_index.drop();
     const uint64_t E = b->n_edges;
     const uint32_t k = b->s.k;
     // node set = every source and target (k-1)-mer (add_fasta_node, pt_graph.rs:142-154): read off the
@@ -767,6 +769,7 @@ int katome_dev_remove_dead_paths(katome_builder* b, katome_dev_graph* out, katom
     PruneGraph g{&b->edge_src, &b->edge_dst, &b->edge_weight, &b->edge_key, &b->node_key, &b->edge_age, b->n_edges, b->n_nodes, b->nw};
     g.parallel_edges = b->direct_edges != 0;
     katome_prune_stats st;
+    b->depth_index.drop();
     {
         PhaseScope ps(b->prof, PH_DEAD_PATHS, stream);
         KCHECK(dev_remove_dead_paths(g, b->s.k, &st, stream));
@@ -796,6 +799,7 @@ int katome_dev_standardize_edges(katome_builder* b, uint64_t original_genome_len
     hipStream_t stream = (hipStream_t)stream_;
     KCHECK_HIP(hipSetDevice(b->s.device));
     if (!b->finalized) { set_error("standardize_edges: call katome_dev_finalize first"); return KATOME_E_ARG; }
+    b->depth_index.drop();
     KCHECK(dev_standardize_scale(b->edge_weight.as<u32>(), b->n_edges, original_genome_length, b->s.k, threshold, stream));
     KCHECK(weak_edges_ordered(b, 1, stream));          // "remove edges with weight 0" (standardizer.rs:68-69)
     KCHECK(dev_labels(b->edge_key.as<u64>(), b->n_edges, b->s.k, b->edge_label.as<uint8_t>(), stream));

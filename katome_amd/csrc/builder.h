@@ -39,6 +39,23 @@ struct KATOME_INTERNAL KeptRecords {
     void close() { reset(); closed = true; }
 };
 
+// depth.hip: what katome_dev_depth searches -- the graph's edge keys in ascending order with a bucket directory over their top bits.
+// keys / perm are empty where the graph's own d_edge_key ascends strictly (a by-key build): it is then searched as it lies; otherwise
+// keys is a sorted copy and perm[i] the edge index of keys[i].  of_keys / n: the edge list the index was built for
+struct KATOME_INTERNAL DepthIndex {
+    DevBuf keys, perm, dir;
+    uint32_t B = 0;
+    bool valid = false;
+    const void* of_keys = nullptr;
+    uint64_t n = 0;
+    void drop() { keys.release(); perm.release(); dir.release(); B = 0; valid = false; of_keys = nullptr; n = 0; }
+    uint64_t bytes() const { return (keys.p ? keys.bytes : 0) + (perm.p ? perm.bytes : 0) + (dir.p ? dir.bytes : 0); }
+};
+// result of katome_dev_depth (its own buffers)
+struct KATOME_INTERNAL DepthOutput {
+    DevBuf present, invalid, sum, mn, mx, window_off, window_edge, edge_hits;
+};
+
 struct katome_builder {
     katome_settings s;
     Profiler prof;
@@ -123,6 +140,9 @@ struct katome_builder {
     GfaOutput gfa;                     // result of katome_dev_contigs_gfa
     GfaStrandsOutput gfa_strands;      // result of katome_dev_contigs_gfa_strands (its own buffers: neither call touches the other's result)
     DevBuf edge_age;                   // first-seen-order graphs once remove_* has moved edges (PruneGraph::edge_age)
+    DepthIndex depth_index;            // katome_dev_depth's index over edge_key, kept between calls; whoever changes the set or the order
+                                       // of the edges drops it (weights are read from edge_weight as it stands: they may change freely)
+    DepthOutput depth;                 // result of katome_dev_depth
     uint64_t n_nodes = 0;
     bool finalized = false;
 };

@@ -109,6 +109,7 @@ enum Phase { PH_EXTRACT, PH_REGION_ORDER, PH_INSERT, PH_EMIT_EDGES, PH_SORT_EDGE
              PH_GFA_PATHS, K_GFA_PATHS_WRITE,
              PH_GFA_STRAND_PATHS, K_GFASP_WRITE, K_GFASP_SIGS, K_GFASP_SORT, K_GFASP_SEARCH, K_GFASP_VERIFY,
              PH_UNIQUE_CONTIGS, K_TEXT_WRITE_NAMED, K_UNIQUE_SELECT,
+             PH_DEPTH, K_DEPTH_KERNEL, K_DEPTH_INDEX,
              PH_COUNT };
 static const char* const PHASE_NAMES[PH_COUNT] = {
     "extract", "region_order", "insert", "emit_edges", "sort_edges", "node_set", "rank", "labels", "insert_tiles", "expand_tiles",
@@ -129,7 +130,8 @@ static const char* const PHASE_NAMES[PH_COUNT] = {
     "gfa_strands", "k:gfa_strands keys+sort", "k:strand_search_kernel", "k:strand_verify_kernel", "k:gfa_strands links", "k:gfa_strands sizes", "k:gfa_strands_write_kernel",
     "gfa_paths", "k:gfa_paths_write_kernel",
     "gfa_strand_paths", "k:gfa_strand_paths_write_kernel", "k:mirror_sig_kernel", "k:mirror signature sort", "k:mirror_search_kernel", "k:mirror_verify_kernel",
-    "unique_contigs", "k:text_write_named_kernel", "k:unique_contigs selection"};
+    "unique_contigs", "k:text_write_named_kernel", "k:unique_contigs selection",
+    "depth", "k:depth_kernel", "k:depth_index"};
 struct Profiler {
     bool on = false;
     struct Ev { int phase; hipEvent_t a, b; uint64_t work; };      // work: elements the launch processed (K_* entries)
@@ -778,5 +780,15 @@ struct HostReads {
     ~HostReads();
 };
 int ingest_files(const katome_settings* s, const char* const* paths, size_t n_paths, HostReads& out);
+// the records of query files (katome_depth_paths) as they are spelled: EVERY record is kept -- one with an N, one shorter than k, an
+// empty one --, its bases as ASCII bytes back to back in `text`, record i at off[i], len[i] bytes
+struct HostQuery {
+    std::vector<uint8_t> text;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> len;
+};
+// file_type: 0 FASTA (a record's lines are joined), 1 FASTQ; anything else is KATOME_E_ARG
+int scan_query(uint32_t file_type, const uint8_t* p, size_t n, HostQuery& q);
+int ingest_query_files(uint32_t file_type, const char* const* paths, size_t n_paths, HostQuery& out);
 
 }  // namespace katome

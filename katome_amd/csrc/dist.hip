@@ -1455,6 +1455,7 @@ int katome_dist_gather(katome_dist_builder* d, int root, katome_builder** root_b
         KCHECK(dev_labels(b->edge_key.as<u64>(), TE, d->s.k, b->edge_label.as<uint8_t>(), stream));
         b->edge_age.release();
         b->drop_edge_heads();
+        b->depth_index.drop();
         b->edges_ready = true; b->finalized = true;
         if (root_builder) *root_builder = b;
     }

@@ -153,6 +153,7 @@ void katome_gfa_free(katome_gfa* g) { free_result(g); }
 void katome_gfa_strands_free(katome_gfa_strands* g) { free_result(g); }
 void katome_gfa_paths_free(katome_gfa_paths* g) { free_result(g); }
 void katome_gfa_strand_paths_free(katome_gfa_strand_paths* g) { free_result(g); }
+void katome_depth_free(katome_depth* d) { free_result(d); }
 }  // extern "C"
 
 #ifndef KATOME_HOST_RESULTS_ONLY      // (tests/hostshim/host_results_selftest.cpp builds the part above for the host alone)
@@ -592,9 +593,77 @@ static int gfa_ending(katome_builder* b, uint64_t read_bytes, const GfaWant& wan
     return hand_out(std::move(g), want.out, want.path, katome_gfa_save);
 }
 
+// katome_depth_paths: the flag's remove_dead_paths, the stage letters, then every record of the query files, in file order and in ASCII,
+// through katome_dev_depth in batches under its window limit (KATOME_DEPTH_BATCH_WINDOWS: a smaller one, for tests); the per-record
+// arrays land in the result batch by batch, the hits of the batches are added up on the host
+struct DepthWant { katome_depth** out; const char* const* paths; size_t n_paths; uint32_t file_type, flags; };
+static uint64_t depth_batch_windows() {
+    if (const char* e = getenv("KATOME_DEPTH_BATCH_WINDOWS")) { const long long v = atoll(e); if (v > 0) return std::min<uint64_t>((uint64_t)v, 0xFFFFFFFFull); }
+    return 1ull << 31;
+}
+static int depth_ending(katome_builder* b, uint64_t read_bytes, const DepthWant& want, const char* stages, uint64_t genome_len) {
+    KCHECK(stages_need_order(b->first_seen, stages));
+    HostQuery q;
+    KCHECK(ingest_query_files(want.file_type, want.paths, want.n_paths, q));
+    KCHECK(prepare(b, stages, genome_len));
+    const uint32_t k = b->s.k;
+    const uint64_t n = q.len.size(), E = b->n_edges;
+    Result<katome_depth> r = make_result<katome_depth>();
+    if (!r) return KATOME_E_OOM;
+    bool oom = false;
+    uint64_t* present = (uint64_t*)take(r.get(), std::max<uint64_t>(n, 1) * 8, &oom);
+    uint64_t* invalid = (uint64_t*)take(r.get(), std::max<uint64_t>(n, 1) * 8, &oom);
+    uint64_t* sum = (uint64_t*)take(r.get(), std::max<uint64_t>(n, 1) * 8, &oom);
+    uint32_t* mn = (uint32_t*)take(r.get(), std::max<uint64_t>(n, 1) * 4, &oom);
+    uint32_t* mx = (uint32_t*)take(r.get(), std::max<uint64_t>(n, 1) * 4, &oom);
+    const bool want_hits = (want.flags & KATOME_DEPTH_EDGE_HITS) != 0;
+    uint32_t* hits = want_hits ? (uint32_t*)take(r.get(), std::max<uint64_t>(E, 1) * 4, &oom) : nullptr;
+    if (oom) { set_error("out of host memory"); return KATOME_E_OOM; }
+    if (hits) memset(hits, 0, std::max<uint64_t>(E, 1) * 4);
+    r->read_bytes = read_bytes; r->n_records = n; r->n_edges = E;
+    r->seq_present = present; r->seq_invalid = invalid; r->seq_sum = sum; r->seq_min = mn; r->seq_max = mx; r->edge_hits = hits;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> batch_hits;
+    DevBuf d_text, d_off, d_len;
+    const uint64_t limit = depth_batch_windows();
+    for (uint64_t r0 = 0; r0 < n;) {
+        uint64_t r1 = r0, w = 0;
+        while (r1 < n) {      // (one record has fewer than 2^32 windows: a batch always takes one at least)
+            const uint64_t wn = q.len[r1] >= k ? (uint64_t)q.len[r1] - k + 1 : 0;
+            if (r1 > r0 && w + wn >= limit) break;
+            w += wn; ++r1;
+        }
+        const uint64_t m = r1 - r0, t0 = q.off[r0], t1 = r1 < n ? q.off[r1] : q.text.size();
+        off.resize(m);
+        for (uint64_t i = 0; i < m; ++i) off[i] = q.off[r0 + i] - t0;
+        KCHECK(d_text.alloc(t1 - t0)); KCHECK(d_off.alloc(m * 8)); KCHECK(d_len.alloc(m * 4));
+        if (t1 > t0) KCHECK_HIP(hipMemcpy(d_text.p, q.text.data() + t0, t1 - t0, hipMemcpyHostToDevice));
+        KCHECK_HIP(hipMemcpy(d_off.p, off.data(), m * 8, hipMemcpyHostToDevice));
+        KCHECK_HIP(hipMemcpy(d_len.p, q.len.data() + r0, m * 4, hipMemcpyHostToDevice));
+        katome_dev_depth_result d;
+        KCHECK(katome_dev_depth(b, KATOME_DEPTH_ASCII, want.flags, d_text.as<uint8_t>(), t1 - t0, d_off.as<uint64_t>(), d_len.as<uint32_t>(), m, &d, nullptr));
+        KCHECK_HIP(hipMemcpy(present + r0, d.d_seq_present, m * 8, hipMemcpyDeviceToHost));
+        KCHECK_HIP(hipMemcpy(invalid + r0, d.d_seq_invalid, m * 8, hipMemcpyDeviceToHost));
+        KCHECK_HIP(hipMemcpy(sum + r0, d.d_seq_sum, m * 8, hipMemcpyDeviceToHost));
+        KCHECK_HIP(hipMemcpy(mn + r0, d.d_seq_min, m * 4, hipMemcpyDeviceToHost));
+        KCHECK_HIP(hipMemcpy(mx + r0, d.d_seq_max, m * 4, hipMemcpyDeviceToHost));
+        r->n_windows += d.n_windows; r->n_present += d.n_present; r->n_invalid += d.n_invalid; r->weight_sum += d.weight_sum;
+        if (hits && E) {
+            batch_hits.resize(E);
+            KCHECK_HIP(hipMemcpy(batch_hits.data(), d.d_edge_hits, E * 4, hipMemcpyDeviceToHost));
+            for (uint64_t e = 0; e < E; ++e) hits[e] += batch_hits[e];
+        }
+        r0 = r1;
+    }
+    if (hits) for (uint64_t e = 0; e < E; ++e) r->n_edges_hit += hits[e] != 0;
+    build_lap("depth of the query files");
+    *want.out = r.release();
+    return KATOME_OK;
+}
+
 // What a host entry hands back: the graph, the graph after shrink, the assembly, the unitigs' numbers (and their file), or the
 // GFA -- and what that ending needs.  The ending runs on the builder of a one-GPU build or of a graph gathered to one GPU.
-enum class Ending { Graph, Contigs, Assembly, Unitigs, Gfa };
+enum class Ending { Graph, Contigs, Assembly, Unitigs, Gfa, Depth };
 struct Finish {
     Ending ending;
     const char* stages = nullptr; uint64_t genome_len = 0;      // (Contigs takes no stages; Assembly runs its own)
@@ -605,6 +674,7 @@ struct Finish {
     AssembleWant assemble{nullptr, nullptr};                      // Assembly
     UnitigsWant unitigs{nullptr, nullptr};                        // Unitigs
     GfaWant gfa{nullptr, nullptr};                                // Gfa
+    DepthWant depth{nullptr, nullptr, 0, 0, 0};                   // Depth
     int operator()(katome_builder* b, uint64_t read_bytes) const {
         switch (ending) {
             case Ending::Graph: return graph_to_host(b, read_bytes, graph, stages, genome_len, stage_stats);
@@ -612,6 +682,7 @@ struct Finish {
             case Ending::Assembly: return assembly_to_host(b, read_bytes, assemble, genome_len);
             case Ending::Unitigs: return unitigs_to_host(b, read_bytes, unitigs, stages, genome_len);
             case Ending::Gfa: return gfa_ending(b, read_bytes, gfa, stages, genome_len);
+            case Ending::Depth: return depth_ending(b, read_bytes, depth, stages, genome_len);
         }
         set_error("unknown ending");
         return KATOME_E_ARG;
@@ -903,8 +974,10 @@ template <class AddReads>
 static int build_multi(const katome_settings* s, const Finish& finish, uint64_t read_bytes, const AddReads& add_reads) {
     const int n = s->n_devices;
     const bool share = (s->flags & KATOME_FLAG_RANKS_SHARE_DEVICE) != 0;
-    // (a GFA takes the assembly's route: gathered to the first GPU, where the stages, the shrink and the text run -- links cross ranks)
-    const MultiRoute route = plan_multi_route(s->flags, finish.ending == Ending::Contigs, finish.stages, finish.ending == Ending::Assembly || finish.ending == Ending::Gfa,
+    // (a GFA takes the assembly's route: gathered to the first GPU, where the stages, the shrink and the text run -- links cross ranks;
+    // so does a depth query: the lookup needs all the edges in one index)
+    const MultiRoute route = plan_multi_route(s->flags, finish.ending == Ending::Contigs, finish.stages,
+                                               finish.ending == Ending::Assembly || finish.ending == Ending::Gfa || finish.ending == Ending::Depth,
                                                finish.ending == Ending::Unitigs);
     if (n > KATOME_MAX_RANKS) { set_error("n_devices = %d: at most %d", n, KATOME_MAX_RANKS); return KATOME_E_UNSUPPORTED; }
     KCHECK(use_device(s->device));
@@ -1258,7 +1331,28 @@ template <class Reads> static int gfa_entry(const Reads& reads, const katome_set
     return reads.build(s, f);
 }
 
+// katome_depth_paths
+template <class Reads> static int depth_entry(const Reads& reads, const katome_settings* s, const char* stages, uint64_t genome_len, const DepthWant& want) {
+    if (!want.out) return null_argument();
+    *want.out = nullptr;
+    if (want.file_type > 1) { set_error("depth: query files are FASTA (0) or FASTQ (1), not file type %u", want.file_type); return KATOME_E_ARG; }
+    if (want.flags & ~(uint32_t)(KATOME_DEPTH_EITHER_STRAND | KATOME_DEPTH_EDGE_HITS)) {
+        set_error("depth: flag bits 0x%x (the host result takes KATOME_DEPTH_EITHER_STRAND and KATOME_DEPTH_EDGE_HITS; it has no per-window array)", want.flags);
+        return KATOME_E_ARG;
+    }
+    if (want.n_paths && !want.paths) return null_argument();
+    if (s) KCHECK(stages_need_order((s->flags & KATOME_FLAG_FIRST_SEEN_ORDER) != 0, stages));
+    Finish f{Ending::Depth};
+    f.depth = want; f.stages = stages; f.genome_len = genome_len;
+    return reads.build(s, f);
+}
+
 extern "C" {
+
+int katome_depth_paths(const katome_settings* s, const char* const* read_paths, size_t n_read_paths, const char* stages, uint64_t original_genome_length,
+                       const char* const* query_paths, size_t n_query_paths, uint32_t query_file_type, uint32_t flags, katome_depth** out) {
+    return depth_entry(FileReads{read_paths, n_read_paths}, s, stages, original_genome_length, DepthWant{out, query_paths, n_query_paths, query_file_type, flags});
+}
 
 int katome_build_packed(const katome_settings* s, const uint8_t* packed, uint64_t n_reads, uint32_t read_len, const uint8_t* skip, katome_graph** out) {
     return graph_entry(PackedReads{packed, n_reads, read_len, skip}, s, nullptr, 0, false, nullptr, out);

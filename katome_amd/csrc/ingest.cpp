@@ -300,9 +300,8 @@ int scan_parallel(const katome_settings* s, const uint8_t* p, size_t n, HostRead
 
 }  // namespace
 
-int ingest_files(const katome_settings* s, const char* const* paths, size_t n_paths, HostReads& out) {
-    KCHECK(check_k(s->k));
-    if (s->file_type > 2) { set_error("unknown input file type %u", s->file_type); return KATOME_E_ARG; }
+// check_files and Reader::from_file for all inputs, before any of them is scanned
+static int map_files(const char* const* paths, size_t n_paths, std::vector<Mapped>& maps) {
     // check_files (builder.rs:57-77): every path is vetted before any file is opened
     std::vector<std::string> files;
     for (size_t i = 0; i < n_paths; ++i) {
@@ -313,9 +312,7 @@ int ingest_files(const katome_settings* s, const char* const* paths, size_t n_pa
         if (S_ISDIR(st.st_mode)) { set_error("%s is a directory", resolved); return KATOME_E_IS_DIR; }
         files.push_back(resolved);
     }
-    KCHECK(reserve_reads(out, 0));
-    out.byte_off[0] = 0;
-    std::vector<Mapped> maps(files.size());
+    maps = std::vector<Mapped>(files.size());
     for (size_t i = 0; i < files.size(); ++i) {            // Reader::from_file for all inputs first (builder.rs:146-149)
         Mapped& m = maps[i];
         m.fd = open(files[i].c_str(), O_RDONLY);
@@ -329,9 +326,60 @@ int ingest_files(const katome_settings* s, const char* const* paths, size_t n_pa
             madvise(p, m.n, MADV_SEQUENTIAL);
         }
     }
-    for (size_t i = 0; i < files.size(); ++i) KCHECK(scan_parallel(s, maps[i].p, maps[i].n, out));
+    return KATOME_OK;
+}
+
+int ingest_files(const katome_settings* s, const char* const* paths, size_t n_paths, HostReads& out) {
+    KCHECK(check_k(s->k));
+    if (s->file_type > 2) { set_error("unknown input file type %u", s->file_type); return KATOME_E_ARG; }
+    std::vector<Mapped> maps;
+    KCHECK(map_files(paths, n_paths, maps));
+    KCHECK(reserve_reads(out, 0));
+    out.byte_off[0] = 0;
+    for (size_t i = 0; i < maps.size(); ++i) KCHECK(scan_parallel(s, maps[i].p, maps[i].n, out));
     if (!out.all_fixed || out.n_reads == 0) out.fixed_len = 0;
     memset(out.packed + out.packed_bytes, 0, 32);          // slack for vector loads
+    return KATOME_OK;
+}
+
+// The query scanner of katome_depth_paths: bio 0.10.0's record framing as scan_fastq / scan_fasta have it, but nothing is filtered and
+// nothing is packed -- a record is its bases as spelled, so that one with an N keeps its valid windows and one shorter than k is a
+// record without windows, not an error
+static int keep_query_record(HostQuery& q, const uint8_t* seq, size_t n) {
+    if (n > 0xFFFFFFFFull) { set_error("query record longer than 2^32 bases"); return KATOME_E_UNSUPPORTED; }
+    q.off.push_back(q.text.size());
+    q.len.push_back((uint32_t)n);
+    q.text.insert(q.text.end(), seq, seq + n);
+    return KATOME_OK;
+}
+int scan_query(uint32_t file_type, const uint8_t* p, size_t n, HostQuery& q) {
+    if (file_type > 1) { set_error("query files are FASTA (0) or FASTQ (1), not file type %u", file_type); return KATOME_E_ARG; }
+    LineReader lr(p, n);
+    const uint8_t *h, *s, *sep, *ql; size_t hn, sn, sepn, qn;
+    if (file_type == 1) {
+        while (lr.next(h, hn)) {
+            if (h[0] != '@') { set_error("Expected @ at record start."); return KATOME_E_PARSE; }
+            lr.next(s, sn); lr.next(sep, sepn); lr.next(ql, qn);
+            if (qn == 0) { set_error("Incomplete record. Each FastQ record has to consist of 4 lines: header, sequence, separator and qualities."); return KATOME_E_PARSE; }
+            KCHECK(keep_query_record(q, s, rtrim(s, sn)));
+        }
+        return KATOME_OK;
+    }
+    std::vector<uint8_t> seq;
+    bool have = lr.next(h, hn);
+    while (have) {
+        if (h[0] != '>') { set_error("Expected > at record start."); return KATOME_E_PARSE; }
+        seq.clear();
+        while ((have = lr.next(h, hn)) && h[0] != '>') seq.insert(seq.end(), h, h + rtrim(h, hn));
+        KCHECK(keep_query_record(q, seq.data(), seq.size()));
+    }
+    return KATOME_OK;
+}
+int ingest_query_files(uint32_t file_type, const char* const* paths, size_t n_paths, HostQuery& out) {
+    if (file_type > 1) { set_error("query files are FASTA (0) or FASTQ (1), not file type %u", file_type); return KATOME_E_ARG; }
+    std::vector<Mapped> maps;
+    KCHECK(map_files(paths, n_paths, maps));
+    for (size_t i = 0; i < maps.size(); ++i) KCHECK(scan_query(file_type, maps[i].p, maps[i].n, out));
     return KATOME_OK;
 }
 

@@ -284,6 +284,37 @@ class DeviceAssembly:
         return self.collapse_stats
 
 
+DEPTH_ENCODINGS = {"packed": 0, "ascii": 1}
+DEPTH_ABSENT, DEPTH_INVALID, DEPTH_REVERSE = -1, -2, -(1 << 63)       # the per-window values as the int64 views show them
+
+
+def _depth_flags(either_strand, windows, edge_hits):
+    return (1 if either_strand else 0) | (2 if windows else 0) | (4 if edge_hits else 0)
+
+
+class DeviceDepth:
+    """result of Builder.depth() (katome_dev_depth, which has the definitions): per sequence seq_present, seq_invalid, seq_sum
+    (int64 views of u64), seq_min, seq_max (int32 views of u32: -1 is all ones) and seq_window_off [n_seqs + 1]; the totals; with
+    windows=True window_edge [n_windows] (int64 view: DEPTH_ABSENT, DEPTH_INVALID, or the edge's index, negative where
+    DEPTH_REVERSE is set), with edge_hits=True edge_hits [n_edges]; otherwise None.  Valid until the builder's next depth() or close()"""
+
+    def __init__(self, d, owner, device):
+        for f in ("n_seqs", "n_windows", "n_present", "n_invalid", "n_edges", "n_edges_hit", "weight_sum"):
+            setattr(self, f, int(getattr(d, f)))
+        v = lambda p, n, t="<i8": _view(p, (n,), t, owner, device)
+        self.seq_present, self.seq_invalid, self.seq_sum = v(d.d_seq_present, d.n_seqs), v(d.d_seq_invalid, d.n_seqs), v(d.d_seq_sum, d.n_seqs)
+        self.seq_min, self.seq_max = v(d.d_seq_min, d.n_seqs, "<i4"), v(d.d_seq_max, d.n_seqs, "<i4")
+        self.seq_window_off = v(d.d_seq_window_off, d.n_seqs + 1)
+        self.window_edge = v(d.d_window_edge, d.n_windows) if d.d_window_edge else None
+        self.edge_hits = v(d.d_edge_hits, d.n_edges, "<i4") if d.d_edge_hits else None
+
+    @staticmethod
+    def of_text(builder, assembly, either_strand=False, windows=False, edge_hits=False):
+        """the contigs of a DeviceAssembly (collapse() or contigs_text(), either layout, of any builder on this device) queried
+        against `builder`'s graph through contig_off / contig_len, in ASCII, without a copy of the text"""
+        return builder.depth(assembly.text, assembly.contig_off, assembly.contig_len, "ascii", either_strand, windows, edge_hits)
+
+
 class DeviceUniqueAssembly:
     """the strand-unique assembly in HBM (katome_dev_collapse_unique, which has the definitions): contig_mirror[c] = the smallest
     contig that spells c's molecule from its other end by pieces, -1 for none (n_mirrored have one, n_self_mirror are their own);
@@ -606,6 +637,21 @@ class Builder(_ViewOwner):
         _check(_lib.lib().katome_dev_graph_stats(self._h, C.byref(st), _stream()))
         return collection_stats(st, capacity=(st.node_count, st.edge_count))
 
+    def depth(self, seq, byte_off, lens, encoding="packed", either_strand=False, windows=False, edge_hits=False):
+        """every window of every sequence looked up among the edges of the finalized graph as it stands (katome_dev_depth) ->
+        DeviceDepth.  seq: uint8 on the device ("packed": 4 bases per byte, every sequence starting on a byte; "ascii": a byte per
+        base, only upper-case ACGT are bases); byte_off int64 [n] (more entries are ignored), lens int32 [n], both on the device"""
+        d = _lib.DevDepth()
+        n = lens.numel()
+        assert byte_off.numel() >= n and byte_off.dtype == torch.int64 and lens.dtype == torch.int32 and seq.dtype == torch.uint8
+        _check(_lib.lib().katome_dev_depth(self._h, DEPTH_ENCODINGS[encoding], _depth_flags(either_strand, windows, edge_hits), _ptr(seq), seq.numel(),
+                                           _ptr(byte_off), _ptr(lens), n, C.byref(d), _stream()))
+        return DeviceDepth(d, self, self.tdev)
+
+    def depth_index_bytes(self):
+        """device bytes of the lookup index depth() keeps between calls (0: none is kept)"""
+        return int(_lib.lib().katome_dev_depth_index_bytes(self._h))
+
     def weight_spectrum(self, n_bins):
         """np.uint64[n_bins]: edges of weight w at [w], those of weight >= n_bins - 1 in the last bin (katome_dev_weight_spectrum)"""
         bins = np.zeros(max(int(n_bins), 0), np.uint64)
@@ -747,6 +793,32 @@ def rank_in_sorted(sorted_keys, queries, key_bits, key_words, device=0):
     _check(_lib.lib().katome_dev_rank(device, _ptr(sorted_keys), ns, key_words, key_bits, _ptr(queries), nq, _ptr(out),
                                       _stream()))
     return out[:nq]
+
+
+def depth_arrays(k, edge_key, edge_weight, seq, byte_off, lens, encoding="packed", either_strand=False, windows=False, edge_hits=False, flags=None,
+                 device=0):
+    """katome_dev_depth on the caller's arrays (katome_dev_depth_arrays): edge_key int64 [n_edges * key_words] in any order but
+    distinct, edge_weight int32 [n_edges], the query as Builder.depth takes it -> dict of the per-sequence tensors, window_off,
+    window_edge / edge_hits (None unless asked for) and the totals.  flags: the raw flag word instead of the three switches"""
+    nw = record_words(k)
+    ne, n = edge_key.numel() // nw, lens.numel()
+    dev = seq.device
+    fl = _depth_flags(either_strand, windows, edge_hits) if flags is None else flags
+    i64 = lambda m: torch.empty(max(m, 1), dtype=torch.int64, device=dev)
+    i32 = lambda m: torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+    present, invalid, ssum, mn, mx, woff = i64(n), i64(n), i64(n), i32(n), i32(n), i64(n + 1)
+    # (the windows are known only to the call: room for every sequence's len - k + 1)
+    cap = int((lens.to(torch.int64) - k + 1).clamp(min=0).sum().item()) if n and (fl & 2) else 0
+    wedge = i64(cap) if fl & 2 else None
+    hits = i32(ne) if fl & 4 else None
+    totals = (C.c_uint64 * 5)()
+    _check(_lib.lib().katome_dev_depth_arrays(device, k, _ptr(edge_key), _ptr(edge_weight), ne, DEPTH_ENCODINGS.get(encoding, encoding), fl, _ptr(seq),
+                                              seq.numel(), _ptr(byte_off), _ptr(lens), n, _ptr(present), _ptr(invalid), _ptr(ssum), _ptr(mn), _ptr(mx),
+                                              _ptr(woff), _ptr(wedge), cap, _ptr(hits), totals, _stream()))
+    nwin = int(totals[0])
+    return dict(seq_present=present[:n], seq_invalid=invalid[:n], seq_sum=ssum[:n], seq_min=mn[:n], seq_max=mx[:n], seq_window_off=woff[:n + 1],
+                window_edge=wedge[:nwin] if wedge is not None else None, edge_hits=hits[:ne] if hits is not None else None, n_seqs=n,
+                n_windows=nwin, n_present=int(totals[1]), n_invalid=int(totals[2]), weight_sum=int(totals[3]), n_edges_hit=int(totals[4]), n_edges=ne)
 
 
 def stats_arrays(edge_src, edge_dst, edge_weight, n_nodes, device=0):

@@ -1,5 +1,6 @@
 // Random-access microbenchmarks on MI355X: what bounds the k-mer table's insert kernel?
 // build: hipcc -O3 --offload-arch=gfx950 tools/microbench_random.hip -o gpurun_out/microbench_random
+// usage: microbench_random [table MiB ...]   (default: 32 128 512 4096 32768)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -35,11 +36,14 @@ template <int MODE> float run(Slot* t, u64 cap, u64 n, u64 window, u64* sink) {
     CHECK(hipEventRecord(b)); CHECK(hipEventSynchronize(b));
     float ms; CHECK(hipEventElapsedTime(&ms, a, b)); return ms;
 }
-int main() {
+#include <vector>
+int main(int argc, char** argv) {
     const u64 n = 1ull << 29;   // 5.4e8 accesses
     u64* sink; CHECK(hipMalloc(&sink, 8));
     const char* names[5] = {"load8", "atomicAdd32", "load+atomicAdd32", "load+store (non-atomic)", "load+atomicAdd64"};
-    for (u64 mb : {32ull, 128ull, 512ull, 4096ull, 32768ull}) {
+    std::vector<u64> sizes = {32ull, 128ull, 512ull, 4096ull, 32768ull};
+    if (argc > 1) { sizes.clear(); for (int i = 1; i < argc; ++i) if (atoll(argv[i]) > 0) sizes.push_back((u64)atoll(argv[i])); }
+    for (u64 mb : sizes) {
         u64 cap = mb * 1024 * 1024 / sizeof(Slot);
         Slot* t; CHECK(hipMalloc(&t, cap * sizeof(Slot))); CHECK(hipMemset(t, 0, cap * sizeof(Slot)));
         for (u64 window : {cap, cap / 256 ? cap / 256 : 1, (u64)16384}) {
