@@ -873,12 +873,15 @@ __global__ __launch_bounds__(LC_THREADS) void lds_count_full_kernel(const u64* k
             for (u32 u = 0; u < LU; ++u) {
                 const u64 i = i0 + (u64)u * LC_THREADS;
                 a[u] = 0; b[u] = 0; w[u] = 0;
-                if constexpr (COUNTED) {
-                    // (no branch around the load: past the group's end a lane reads the group's last record, which nobody looks at.  Under
-                    // `if (i < hi)` hipcc 7.2 waited for each of these loads before it issued the next -- four memory latencies a turn instead
-                    // of one, 8.46 ms at C3 against the plain form's 8.22 with its weights array and all)
+                // (no branch around the load: past the group's end a lane reads the group's last record, which nobody looks at.  Under
+                // `if (i < hi)` hipcc 7.2 waited for each of these loads before it issued the next -- four memory latencies a turn instead
+                // of one, 8.46 ms at C3 for the counted form against the plain form's 8.22 with its weights array and all; the plain
+                // form waited the same way for the next turn's loads until it took the clamp too)
+                // (the both-strand forms keep the branch: at LF_PER = 7 they stand at 128 VGPRs and the clamped loads spilled)
+                if constexpr (COUNTED || !RC) {
                     const u64 ic = i < hi ? i : hi - 1;
                     const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(keys + 2 * ic); a[u] = v.x; b[u] = v.y;
+                    if constexpr (!COUNTED) w[u] = wts ? wts[ic] : 1u;
                 } else
                 if (i < hi) { const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(keys + 2 * i); a[u] = v.x; b[u] = v.y; w[u] = wts ? wts[i] : 1u; }
             }

@@ -40,17 +40,28 @@ __global__ __launch_bounds__(BLOCK) void src_write_kernel(const u64* __restrict_
     const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const u64 base = (u64)blockIdx.x * UNIQ_TILE;
     bool head[UNIQ_ITEMS]; u32 before[UNIQ_ITEMS];
-    Key<NW> key[LABELS ? UNIQ_ITEMS : 1];                  // LABELS: the block's keys stay in registers
+    Key<NW> key[UNIQ_ITEMS], prev[UNIQ_ITEMS];             // the block's keys, which stay in registers, and the keys of the edges before them
     const u32 stride = LABELS ? label_stride_for_k(k) : 0u, pad = LABELS ? label_pad_for_k(k) : 0u;
-    if constexpr (LABELS) {
+    // A whole block (every block but the list's last) loads its keys and their predecessors without a test, so that all of them go
+    // out together: behind `e < n && ...` in the loop below hipcc 7.2 waited for every row's predecessor before it loaded the next
+    // (9.8 -> 8.5 ms at C3, profiles/load_chains.md).  Edge 0 has no predecessor and reads itself: it is a head whatever it reads.
+    if (base + UNIQ_TILE <= n) {
 #pragma unroll
-        for (int j = 0; j < UNIQ_ITEMS; ++j) { const u64 e = base + (u64)j * BLOCK + threadIdx.x; if (e < n) key[j] = load_key<NW>(keys, e); }
+        for (int j = 0; j < UNIQ_ITEMS; ++j) {
+            const u64 e = base + (u64)j * BLOCK + threadIdx.x;
+            key[j] = load_key<NW>(keys, e); prev[j] = load_key<NW>(keys, e ? e - 1 : 0);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < UNIQ_ITEMS; ++j) {
+            const u64 e = base + (u64)j * BLOCK + threadIdx.x;
+            if (e < n) { key[j] = load_key<NW>(keys, e); prev[j] = load_key<NW>(keys, e ? e - 1 : 0); }
+        }
     }
 #pragma unroll
     for (int j = 0; j < UNIQ_ITEMS; ++j) {
         const u64 e = base + (u64)j * BLOCK + threadIdx.x;
-        if constexpr (LABELS) head[j] = e < n && (e == 0 || !key_eq(key_shr(key[j], 2), key_shr(load_key<NW>(keys, e - 1), 2)));
-        else head[j] = e < n && is_src_head<NW>(keys, e);
+        head[j] = e < n && (e == 0 || !key_eq(key_shr(key[j], 2), key_shr(prev[j], 2)));          // (is_src_head)
         const u64 m = __ballot(head[j]);
         before[j] = __popcll(m & (lane ? (~0ull >> (64 - lane)) : 0ull));
         if (lane == 0) wtot[j][wave] = __popcll(m);
@@ -81,8 +92,7 @@ __global__ __launch_bounds__(BLOCK) void src_write_kernel(const u64* __restrict_
         if (e < n) {
             const u64 pos = carry + woff + before[j];           // heads strictly before this edge
             if (head[j]) {
-                if constexpr (LABELS) store_key<NW>(nodes, pos, key_shr(key[j], 2));
-                else store_key<NW>(nodes, pos, key_shr(load_key<NW>(keys, e), 2));
+                store_key<NW>(nodes, pos, key_shr(key[j], 2));
                 if (seg_edge && pos % seg_nodes == 0) seg_edge[pos / seg_nodes] = e;      // first out-edge of every seg_nodes-th source
             }
             edge_src[e] = head[j] ? pos : pos - 1;

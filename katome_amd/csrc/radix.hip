@@ -127,14 +127,34 @@ __global__ __launch_bounds__(BLOCK) void radix_hist_kernel(const u64* __restrict
     __syncthreads();
     constexpr int SORT_ITEMS = SortTile<NW>::ITEMS, SORT_TILE = SortTile<NW>::KEYS;
     const u64 base = (u64)blockIdx.x * SORT_TILE;
+    // A whole tile (every tile of a pass but its last) loads its keys without a test, so that the loads go out together: behind
+    // `if (i < n)` hipcc 7.2 waited for each load before it issued the next, SORT_ITEMS memory latencies in a row instead of one
+    if (base + SORT_TILE <= n) {
+        Key<NW> key[SORT_ITEMS];
 #pragma unroll
-    for (int j = 0; j < SORT_ITEMS; ++j) {
-        u64 i = base + (u64)j * BLOCK + tid;
+        for (int j = 0; j < SORT_ITEMS; ++j) {
 #if KATOME_STREAM_LOADS >= 2
-        if (i < n) atomicAdd(&h[dg(load_key_stream<NW>(keys, i))], 1u);
+            key[j] = load_key_stream<NW>(keys, base + (u64)j * BLOCK + tid);
 #else
-        if (i < n) atomicAdd(&h[dg(load_key<NW>(keys, i))], 1u);
+            key[j] = load_key<NW>(keys, base + (u64)j * BLOCK + tid);
 #endif
+        }
+#pragma unroll
+        for (int j = 0; j < SORT_ITEMS; ++j) atomicAdd(&h[dg(key[j])], 1u);
+    } else {
+        // the pass's last tile (base < n): a thread past the end reads the last key and does not count it
+        Key<NW> key[SORT_ITEMS];
+#pragma unroll
+        for (int j = 0; j < SORT_ITEMS; ++j) {
+            const u64 i = base + (u64)j * BLOCK + tid, ic = i < n ? i : n - 1;
+#if KATOME_STREAM_LOADS >= 2
+            key[j] = load_key_stream<NW>(keys, ic);
+#else
+            key[j] = load_key<NW>(keys, ic);
+#endif
+        }
+#pragma unroll
+        for (int j = 0; j < SORT_ITEMS; ++j) if (base + (u64)j * BLOCK + tid < n) atomicAdd(&h[dg(key[j])], 1u);
     }
     __syncthreads();
     counts[(u64)blockIdx.x * RADIX + tid] = h[tid];
@@ -400,6 +420,37 @@ __global__ __launch_bounds__(BLOCK, KATOME_SORT_WAVES) void radix_scatter_kernel
     const typename Src::Origin from = src.origin(base);
     u64 in0 = base;                                         // (the tile's first record in keys_in / vals_in)
     if constexpr (PLACED) { in0 = from.base; cnt = from.cnt; }
+    // Keys alone, read from an array, by a pass that also leaves the next pass's digits: the tile's loads go out before the ranking
+    // loop, and a whole tile's (every tile of a pass but its last) without a test.  Inside the loop, behind `if (valid)`, hipcc 7.2
+    // waited for each load before it issued the next -- SORT_ITEMS memory latencies to a tile instead of one: 6.7 -> 5.9 ms for the
+    // big tiles' first pass at C3 (profiles/load_chains.md).  The same keys-only pass without a next digit waits the same way but
+    // already ran at 5.6 ms, and with its loads ahead it did not run faster (5.8), so it keeps the loop as it was; with values the
+    // loop's loads already go out in pairs behind partial waits.
+    constexpr bool LOAD_AHEAD = !LISTED && !HAS_VAL && !std::is_same<Next, NoNextDigit>::value;
+    if constexpr (LOAD_AHEAD) {
+        const u64 at = in0 + wave * (64 * SORT_ITEMS) + lane;
+        if (cnt == (u32)SORT_TILE) {
+#pragma unroll
+            for (int j = 0; j < SORT_ITEMS; ++j) {
+#if KATOME_STREAM_LOADS >= 1
+                key[j] = load_key_stream<NW>(keys_in, at + j * 64);
+#else
+                key[j] = load_key<NW>(keys_in, at + j * 64);
+#endif
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < SORT_ITEMS; ++j) {
+                if (wave * (64 * SORT_ITEMS) + j * 64 + lane < cnt) {
+#if KATOME_STREAM_LOADS >= 1
+                    key[j] = load_key_stream<NW>(keys_in, at + j * 64);
+#else
+                    key[j] = load_key<NW>(keys_in, at + j * 64);
+#endif
+                }
+            }
+        }
+    }
 #pragma unroll
     for (int j = 0; j < SORT_ITEMS; ++j) {
         const u32 idx = wave * (64 * SORT_ITEMS) + j * 64 + lane;
@@ -412,7 +463,7 @@ __global__ __launch_bounds__(BLOCK, KATOME_SORT_WAVES) void radix_scatter_kernel
                     for (int q = 0; q < NW; ++q) key[j].w[q] = skeys[idx * NW + q];
                     if constexpr (HAS_VAL) val[j] = src.count_of(from, idx);
                 } else src.load(from, idx, key[j], val[j]);
-            } else {
+            } else if constexpr (!LOAD_AHEAD) {
 #if KATOME_STREAM_LOADS >= 1
             key[j] = load_key_stream<NW>(keys_in, in0 + idx);
             if (HAS_VAL) val[j] = __builtin_nontemporal_load(&vals_in[in0 + idx]);
@@ -1353,6 +1404,8 @@ int dev_half_merge(const uint64_t* a_key, const uint32_t* a_w, const uint64_t* a
 constexpr u32 GM_THREADS = LDS_ORDER_THREADS, GM_PER = 16, GM_WORDS = GM_THREADS * GM_PER, GM_CAP = GM_WORDS - 16;
 constexpr u32 GM_STEP = 2048, GM_RING = 2 * GM_STEP, GM_MI = GM_STEP / GM_THREADS, GM_PF = GM_STEP / GM_THREADS;
 constexpr size_t GM_LDS = ((size_t)GM_WORDS + GM_RING) * 8;
+constexpr u32 GM_LOAD = 8;                    // B key + weight pairs a thread has in flight at once
+static_assert(GM_PER % GM_LOAD == 0, "the load of B goes in whole chunks");
 constexpr u32 SRC_HEAD_BLOCK = 2048;          // edges to a count of source_ids_t (node_ids.hip: its UNIQ_TILE)
 static_assert(SRC_HEAD_BLOCK == UNIQ_TILE, "group_merge_kernel counts the heads of exactly src_count_kernel's blocks");
 // the GM_WORDS - GM_CAP spare words behind B, as u32: the scan's wave totals, the step's A count, and (HEADS) the last entry of the
@@ -1396,10 +1449,28 @@ __global__ __launch_bounds__(GM_THREADS) void group_merge_kernel(const u64* __re
         u64 o = a_off[g] + b0;
         unsigned long long v[GM_PER]; u32 keep = 0;
 #pragma unroll
-        for (u32 j = 0; j < GM_PER; ++j) {
-            const u32 i = tid + j * GM_THREADS;
-            v[j] = 0;
-            if (i < nb) { v[j] = ((b_key[b0 + i] & REM) << 16) | b_w[b0 + i]; keep |= 1u << j; }
+        for (u32 j = 0; j < GM_PER; ++j) v[j] = 0;
+        // (no branch around a load: a lane past the group's end reads the group's last key, which it drops.  Behind `if (i < nb)`
+        // hipcc 7.2 waited for each key and weight before it issued the next pair -- up to GM_PER memory latencies a group, and one
+        // workgroup to a CU has nobody to hide them.  GM_LOAD pairs go out together, 14.3 -> 13.6 ms at C3 (profiles/load_chains.md);
+        // sixteen, 48 registers of loads beside v's 32 under a bound of 128, were not tried.)
+        if (nb) {
+            const u64 last = b0 + nb - 1;
+#pragma unroll
+            for (u32 j0 = 0; j0 < GM_PER; j0 += GM_LOAD) {
+                if (j0 * GM_THREADS >= nb) break;             // (the whole workgroup is past the end)
+                u64 bk[GM_LOAD]; u32 bw[GM_LOAD];
+#pragma unroll
+                for (u32 j = 0; j < GM_LOAD; ++j) {
+                    const u32 i = tid + (j0 + j) * GM_THREADS;
+                    const u64 ic = i < nb ? b0 + i : last;
+                    bk[j] = b_key[ic]; bw[j] = b_w[ic];
+                }
+#pragma unroll
+                for (u32 j = 0; j < GM_LOAD; ++j) {
+                    if (tid + (j0 + j) * GM_THREADS < nb) { v[j0 + j] = ((bk[j] & REM) << 16) | bw[j]; keep |= 1u << (j0 + j); }
+                }
+            }
         }
         reinterpret_cast<uint4*>(bucket)[tid] = make_uint4(0u, 0u, 0u, 0u);
         __syncthreads();                                  // (the last group's merge is done with the ring and bs)
