@@ -1372,6 +1372,21 @@ int katome_dev_count_in_key(int device, const uint64_t *d_tiles, const uint32_t 
                             uint32_t span, uint32_t stride, int rc, int packed, uint64_t *d_pass1_keys, uint32_t *d_pass1_weights,
                             uint64_t *d_pass2_keys, uint32_t *d_pass2_weights, uint64_t *d_out_keys, uint32_t *d_out_weights,
                             uint64_t *n_out, int *took_packed, void *stream);
+/* test entry: the count of a level by sorting on records of the caller's own -- n (key, count) records in any order, d_keys [n][nw]
+ * with nw the words of a key of k bases (k = 2 .. 95: one, two or three words), d_weights [n] or NULL (two and three words only:
+ * every record counts once) -- to the distinct keys with their counts summed in u32 (sums wrap).  rc: every key leaves with its
+ * reverse complement, both with the sum; a key that is its own reverse complement once with twice the sum; the records must hold
+ * one orientation of a k-mer only.  min_weight: an edge stays when its final weight is at least that.  Three words: rc = 0 and
+ * min_weight = 0 only.  n_parts > 0 (one word, rc = 0, min_weight = 0, at most 16): the keys leave grouped by the owner of their
+ * core, the middle k - 2 bases (katome_key_owner with core_shift 2, core_bases k - 2): owner p's in [owner_base[p], owner_base[p] +
+ * owner_count[p]) of the output; n_parts = 0: one stretch, owner_base / owner_count may be NULL.  The input is copied (the count
+ * permutes its records).  d_out_keys [out_capacity][nw] / d_out_weights [out_capacity], out_capacity >= (rc ? 2 : 1) * n + 1;
+ * *n_out entries in no particular order, *n_distinct distinct keys met.  The status is the count's own: KATOME_E_UNSUPPORTED where a
+ * build would count the level in the hash table instead (synchronises)                                                        */
+int katome_dev_count_records(int device, const uint64_t *d_keys, const uint32_t *d_weights, uint64_t n, uint32_t k, int rc,
+                             uint32_t min_weight, uint32_t n_parts, uint64_t *d_out_keys, uint32_t *d_out_weights,
+                             uint64_t out_capacity, uint64_t *n_out, uint64_t *n_distinct, uint64_t *owner_base,
+                             uint64_t *owner_count, void *stream);
 /* test entry: the one partition pass that S2 of the ordered k-mer count takes when its writer placed it by its first digit.
  * used[256] (host): the keys of every region; region d lies from start[d] on in d_keys / d_weights / d_digits, start[] (257 of them,
  * the last one the arrays' length) being what katome_s2_region_starts gives for `used` -- every region a whole number of 4096-key

@@ -365,6 +365,7 @@ SYMBOLS = {
     "katome_dev_sort": (_i, [_i, _vp, _vp, _u64, _u32, _u32, _vp]),
     "katome_dev_list_first_pass": (_i, [_i, _vp, _vp, _u64, _u32, _u32, _u32, _u32, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "katome_dev_count_in_key": (_i, [_i, _vp, _vp, _u64, _u32, _u32, _u32, _u32, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, u64p, C.POINTER(C.c_int), _vp]),
+    "katome_dev_count_records": (_i, [_i, _vp, _vp, _u64, _u32, _i, _u32, _u32, _vp, _vp, _u64, u64p, u64p, u64p, u64p, _vp]),
     "katome_s2_region_starts": (None, [u64p, u64p]),
     "katome_dev_s2_region_pass": (_i, [_i, _u32, u64p, _vp, _vp, _vp, _vp, _vp, _vp]),
     "katome_dev_unique": (_i, [_i, _vp, _u64, _u32, u64p, _vp]),
@@ -419,7 +420,7 @@ SYMBOLS = {
 
 # test entries that the library of an older commit, loaded with KATOME_LIB for an A/B of the benchmark, does not have: that library
 # loads without them (and a test that calls one fails on the missing attribute); every other symbol must be there
-_TEST_ENTRIES_AFTER_AB = {"katome_dev_count_in_key"}
+_TEST_ENTRIES_AFTER_AB = {"katome_dev_count_in_key", "katome_dev_count_records"}
 # public entries that the library of the commit before them lacks and the benchmark does not call: passed over ONLY in a library
 # named by KATOME_LIB -- the tree's own library must have every symbol
 _ENTRIES_AFTER_AB = {"katome_dev_depth", "katome_dev_depth_index_bytes", "katome_dev_depth_arrays", "katome_depth_paths", "katome_depth_free"}

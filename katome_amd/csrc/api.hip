@@ -1106,6 +1106,41 @@ int katome_dev_count_in_key(int device, const uint64_t* d_tiles, const uint32_t*
     return dev_count_in_key_level(d_tiles, d_counts, n_tiles, tile_bases, k, span, stride, rc != 0, packed != 0, pk, pw, d_out_keys, d_out_weights, n_out, took_packed,
                                   (hipStream_t)stream);
 }
+int katome_dev_count_records(int device, const uint64_t* d_keys, const uint32_t* d_weights, uint64_t n, uint32_t k, int rc, uint32_t min_weight, uint32_t n_parts,
+                             uint64_t* d_out_keys, uint32_t* d_out_weights, uint64_t out_capacity, uint64_t* n_out, uint64_t* n_distinct, uint64_t* owner_base,
+                             uint64_t* owner_count, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    KCHECK(use_device(device));
+    if (!n_out || !n_distinct || (n_parts && (!owner_base || !owner_count)) || (n && (!d_keys || !d_out_keys || !d_out_weights))) { set_error("null argument"); return KATOME_E_ARG; }
+    *n_out = 0; *n_distinct = 0;
+    if (k < 2 || k > 95) { set_error("count records: k = 2 .. 95"); return KATOME_E_ARG; }
+    if (n_parts > (uint32_t)KATOME_MAX_RANKS) { set_error("count records: at most %d owners", KATOME_MAX_RANKS); return KATOME_E_ARG; }
+    if (n >= (1ull << 40) || out_capacity < (rc ? 2 : 1) * n + 1) { set_error("count records: room for (rc ? 2 : 1) * n + 1 entries"); return KATOME_E_ARG; }
+    for (uint32_t p = 0; p < n_parts; ++p) owner_base[p] = owner_count[p] = 0;
+    if (!n) return KATOME_OK;
+    const size_t nw = (size_t)key_words_for_k(k);
+    DevBuf keys(stream), weights(stream), ok(stream), ow(stream);          // (copies: the count consumes and permutes its records)
+    KCHECK(keys.alloc((n + 1) * 8 * nw));
+    KCHECK_HIP(hipMemcpyAsync(keys.p, d_keys, n * 8 * nw, hipMemcpyDeviceToDevice, stream));
+    if (d_weights) {
+        KCHECK(weights.alloc((n + 1) * 4));
+        KCHECK_HIP(hipMemcpyAsync(weights.p, d_weights, n * 4, hipMemcpyDeviceToDevice, stream));
+    }
+    OwnerSplit split;
+    split.n_parts = n_parts; split.core_shift = 2; split.core_bases = k - 2;          // (as dist.hip sets them)
+    uint64_t n_list = 0, distinct = 0;
+    const int st = records_to_edges_sorted(keys, weights, n, k, rc != 0, min_weight, ok, ow, &n_list, &distinct, stream, n_parts ? &split : nullptr, nullptr, nullptr, nullptr);
+    if (st != KATOME_OK) { hipStreamSynchronize(stream); return st; }
+    // (with owners the stretches lie where the owners' first records lay: anywhere among the first n entries)
+    const uint64_t n_copy = n_parts ? n : n_list;
+    if (n_copy > out_capacity || n_list > out_capacity) { set_error("count records: %llu entries of %llu records", (unsigned long long)n_list, (unsigned long long)n); return KATOME_E_DEVICE; }
+    KCHECK_HIP(hipMemcpyAsync(d_out_keys, ok.p, n_copy * 8 * nw, hipMemcpyDeviceToDevice, stream));
+    KCHECK_HIP(hipMemcpyAsync(d_out_weights, ow.p, n_copy * 4, hipMemcpyDeviceToDevice, stream));
+    KCHECK_HIP(hipStreamSynchronize(stream));
+    for (uint32_t p = 0; p < n_parts; ++p) { owner_base[p] = split.base[p]; owner_count[p] = split.count[p]; }
+    *n_out = n_list; *n_distinct = distinct;
+    return KATOME_OK;
+}
 void katome_s2_region_starts(const uint64_t* used, uint64_t* start) {
     uint64_t cap[S2_REGIONS];
     for (uint32_t d = 0; d < S2_REGIONS; ++d) cap[d] = s2_tiles(used[d]) * S2_REGION_TILE;

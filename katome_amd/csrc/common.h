@@ -758,6 +758,8 @@ int records_to_edges_sorted(DevBuf& keys, DevBuf& weights, uint64_t n, uint32_t 
                             uint32_t* first_counts = nullptr, HalfSort* half = nullptr, RecordSource* src = nullptr);
 // (src: keys / weights may be records still to be made.  KATOME_E_UNSUPPORTED leaves them written all the same: before the passes
 // they are materialised, after the passes they lie ordered in keys / weights)
+// (test entry katome_dev_count_records, api.hip: this function on copies of the caller's records, without first_counts, half or src,
+// its status handed on as it is -- what tests/test_gpu_count_records.py compares with a dictionary, strategy by strategy)
 int table_to_records(Table& t, DevBuf& keys, DevBuf& weights, uint64_t* n_records, hipStream_t stream, DevBuf* seen_pairs = nullptr);
 int table_expand_tiles_to_subtiles(Table& tiles, uint32_t k, uint32_t span, uint32_t stride, bool rc, DevBuf& keys, DevBuf& weights,
                                    uint64_t* n_records, hipStream_t stream, DevBuf* seen = nullptr);

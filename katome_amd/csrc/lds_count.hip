@@ -1777,7 +1777,8 @@ int records_to_edges_sorted(DevBuf& keys, DevBuf& weights, uint64_t n, uint32_t 
     if (!done) KCHECK(count_packed(c, R_try, r, &done));
     if (!done) {
         KCHECK(count_optimistic("packed key", R_try, R, ~0u, r, [&](u32 rounds, u32 probe_limit) { return count_sub_rounds(c, rounds, probe_limit, r); }));
-        if (r.code == 4) return KATOME_E_UNSUPPORTED;          // (a group too large for the representative's 20 bits: the caller counts in the table)
+        lc_trace("[lds count] 12-byte slots, %u sub-round(s): code %u\n", R, (unsigned)r.code);
+        if (r.code == 4) { set_error("counting in LDS: a group of more than 2^20 records"); return KATOME_E_UNSUPPORTED; }          // (a group too large for the representative's 20 bits: the caller counts in the table)
         if (r.code) { set_error("counting in LDS: a sub-round did not fit its table (code %u)", (unsigned)r.code); return KATOME_E_DEVICE; }
     }
     *n_edges = r.n_out; *n_distinct = r.n_distinct;

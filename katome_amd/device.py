@@ -720,6 +720,24 @@ def s2_region_pass(k, used, keys, weights, digits, device=0):
     return out_k[:n], out_w[:n]
 
 
+def count_records(keys, weights, k, rc=False, min_weight=0, n_parts=0, device=0):
+    """(key, count) records in any order -- keys int64 [n * nw] on the device, weights int32 [n] or None: every record counts once
+    -- counted by sorting as a level of a build is (katome_dev_count_records) -> (keys [m * nw], weights [m], n_out, n_distinct,
+    base, count).  Without owners (n_parts = 0) m = n_out and base / count are empty; with them owner p's entries are
+    [base[p], base[p] + count[p]) of the m = n returned.  Raises KatomePanic with the count's own status."""
+    nw = record_words(k)
+    n = keys.numel() // nw
+    cap = (2 if rc else 1) * n + 1
+    out_k = torch.empty(cap * nw, dtype=torch.int64, device=keys.device)
+    out_w = torch.empty(cap, dtype=torch.int32, device=keys.device)
+    n_out, n_distinct = C.c_uint64(), C.c_uint64()
+    base, count = np.zeros(max(n_parts, 1), np.uint64), np.zeros(max(n_parts, 1), np.uint64)
+    _check(_lib.lib().katome_dev_count_records(device, _ptr(keys), _ptr(weights), n, k, int(bool(rc)), min_weight, n_parts, _ptr(out_k), _ptr(out_w), cap,
+                                               C.byref(n_out), C.byref(n_distinct), base.ctypes.data_as(_lib.u64p), count.ctypes.data_as(_lib.u64p), _stream()))
+    m = n if n_parts else n_out.value
+    return out_k[:m * nw], out_w[:m], n_out.value, n_distinct.value, [int(x) for x in base[:n_parts]], [int(x) for x in count[:n_parts]]
+
+
 def unique_sorted(keys, key_words, device=0):
     n = keys.numel() // key_words
     out = C.c_uint64()
